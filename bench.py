@@ -13,7 +13,11 @@ Workload: ml1m(s) graph of MovieLens-1M shape scaled by s (default 64: |U| = 386
 
 `python bench.py --gpus N` with no WORLD_SIZE in the environment starts its own N ranks
 (`python -m torch.distributed.run`, fresh child processes, before this process touches the GPU);
-under torchrun (WORLD_SIZE set) it is one rank.  Rank 0 prints ONE JSON line.  Extra objects:
+under torchrun (WORLD_SIZE set) it is one rank.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times
+--steps steps (`value`, `ms_per_step`) and prints the line.  --dump-outputs DIR writes the scores of the last timed step
+(the [P, 1] float32 array a caller of the step receives, all ranks' shards in pair-list order; a fixed seeded sample of
+DUMP_MAX_SCORES when larger) to DIR/scores.npy.  --full adds the objects below.
+Extra objects:
 `roofline` (dominant kernel = the fused GCN SpMM layer, algorithmic bytes nnz*8 + (N+1)*4 + 2*N*F*4
 per launch over its HIP-event time), `roofline_onchip` (the same launch against the DISPATCHED kernel's own on-chip
 floors: its L2 request count from this build's counters and its measured no-gather time), `s256` (the same step on ml1m(s=256):
@@ -53,6 +57,7 @@ HBM_PEAK_GBPS = 8000.0
 MFMA_BF16_PEAK_TFLOPS = 2500.0         # dense bf16 (MI355X_MICROARCH.md)
 MFMA_F32_PEAK_TFLOPS = 157.3
 L2_REQUESTS_PER_S = 270e9          # 256 CUs x 0.44 line requests per clock at 2.4 GHz (profiles/r1_exp_gather_frontend.txt)
+DUMP_MAX_SCORES = 15 << 20         # --dump-outputs stays under 64 MB: all 12 M scores of ml1m(s=64), a sample of larger runs
 
 
 def parse_args():
@@ -61,8 +66,13 @@ def parse_args():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--scale', type=int, default=64, help='ml1m(s) scale factor of the synthetic graph (64; 256 = the larger scaling workload)')
-    ap.add_argument('--no-cpu-baseline', action='store_true', help='skip the ml1m(s=1), hybrid-head and CPU legs')
-    ap.add_argument('--no-s256', action='store_true', help='skip the ml1m(s=256) leg (the larger scaling workload, run by default next to --scale 64)')
+    ap.add_argument('--full', action='store_true', help='also measure and check everything beyond the headline figure (kernel-level '
+                                                        'objects over instrumented eager steps, multi-rank self-check, the s256 leg, '
+                                                        'other models and sizes, CPU baselines)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the ml1m(s=1), hybrid-head and CPU legs')
+    ap.add_argument('--no-s256', action='store_true', help='with --full: skip the ml1m(s=256) leg (the larger scaling workload, run next to --scale 64)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the scores of the last timed step to DIR/scores.npy (float32, in the '
+                                                          'order of the pair list)')
     return ap.parse_args()
 
 
@@ -685,6 +695,25 @@ def larger_scale_leg(scale, steps, rank, world, local_rank, multi, rehearse):
     return out
 
 
+def dump_scores(out_dir, scores, n_pairs, runner, rank, multi, cdev):
+    """--dump-outputs: the scores of the last timed step in pair-list order.  With several ranks every rank calls it (a collective):
+    each scatters its shard into a zeroed [P] table and a sum brings the whole table to every rank, since each pair is scored on
+    exactly one.  Rank 0 writes DIR/scores.npy, [P, 1] float32, or the same seeded sample of DUMP_MAX_SCORES positions (sorted)."""
+    s = scores.detach().reshape(-1).to(torch.float32)
+    if multi:
+        whole = torch.zeros(n_pairs, dtype=torch.float32, device=cdev)
+        whole[runner.pair_index.to(cdev)] = s.to(cdev)
+        torch.distributed.all_reduce(whole)
+        s = whole
+    if rank != 0:
+        return
+    if s.numel() > DUMP_MAX_SCORES:
+        pick = np.sort(np.random.default_rng(0).choice(s.numel(), DUMP_MAX_SCORES, replace=False))
+        s = s[torch.from_numpy(pick).to(s.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'scores.npy'), s.cpu().numpy().reshape(-1, 1))
+
+
 def value_spread(scale):
     """min / max ms per step of the default run over the boxes of the build session (profiles/r<round>_bench_repeats.json, written by
     tools/collect_spread.py from the bench.py lines of different gpurun boxes), with the csrc/ hash it was measured at."""
@@ -815,33 +844,34 @@ def main():
     runner = parallel.make_runner(model, u_all, i_all, rank, world, dist=parallel.SharedDeviceCollectives(rank, world) if rehearse else None) \
         if not force_dist else parallel.PartitionedGCNRunner(model, u_all, i_all, rank, world)
 
-    spmm_events, kinds_seen = [], []
+    spmm_events, kinds_seen, pair_events, scatter_events = [], [], [], []
     # The timed steps replay the whole step — on several ranks its collectives too — from a hipGraph the runner captures itself
-    # (AMAR_STEP_GRAPH=0: the eager steps are the timed ones).  No per-launch event can be recorded inside a capture, so the
-    # kernel-level objects below (roofline, pair_stage) are timed over K EAGER steps run just before, whose own rate is reported
-    # as `eager`; the kernels and their durations are the same in both.
+    # (AMAR_STEP_GRAPH=0: eager steps are the timed ones).  No per-launch event can be recorded inside a capture, so with --full
+    # the kernel-level objects below (roofline, pair_stage) are timed over K EAGER steps run just before, whose own rate is
+    # reported as `eager`; the kernels and their durations are the same in both.
     graph_step = hasattr(runner, 'step_graphed') and os.environ.get('AMAR_STEP_GRAPH', '1') != '0' and not rehearse
-    restore_spmm = leaf_spmm_timers(capi, spmm_events, kinds_seen)       # whichever form the layer dispatches to, timed once
-    pair_events, raw_chain = [], capi.chain
+    if args.full:
+        restore_spmm = leaf_spmm_timers(capi, spmm_events, kinds_seen)       # whichever form the layer dispatches to, timed once
+        raw_chain = capi.chain
 
-    def timed_chain(*a, **k):                                  # the pair stage = the sum-input chain launch
-        if not k.get('sum_inputs'):
-            return raw_chain(*a, **k)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        raw_chain(*a, **k)
-        e1.record()
-        pair_events.append((e0, e1))
-    capi.chain = timed_chain
-    scatter_events, raw_scatter = [], capi.scatter
+        def timed_chain(*a, **k):                                  # the pair stage = the sum-input chain launch
+            if not k.get('sum_inputs'):
+                return raw_chain(*a, **k)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            raw_chain(*a, **k)
+            e1.record()
+            pair_events.append((e0, e1))
+        capi.chain = timed_chain
+        raw_scatter = capi.scatter
 
-    def timed_scatter(*a, **k):                                # the second launch of the pair stage: scores into the caller's order
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        raw_scatter(*a, **k)
-        e1.record()
-        scatter_events.append((e0, e1))
-    capi.scatter = timed_scatter
+        def timed_scatter(*a, **k):                                # the second launch of the pair stage: scores into the caller's order
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            raw_scatter(*a, **k)
+            e1.record()
+            scatter_events.append((e0, e1))
+        capi.scatter = timed_scatter
     multi = world > 1 or force_dist
     cdev = 'cpu' if rehearse else dev                          # gloo reduces host tensors
 
@@ -850,23 +880,25 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    for _ in range(max(args.warmup, 20)):                   # the kernel-level timings below want settled clocks too
+    for _ in range(max(args.warmup, 20)):                   # the kernel-level timings of --full want settled clocks too
         runner.step()
     barrier()
-    spmm_events.clear()
-    pair_events.clear()
-    scatter_events.clear()
-    del kinds_seen[:]
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        runner.step()
-    eager_host_dt = time.perf_counter() - t0
-    barrier()
-    eager_dt = time.perf_counter() - t0
-    restore_spmm()
-    capi.chain = raw_chain
-    capi.scatter = raw_scatter
-    phases = runner.phase_times() if hasattr(runner, 'phase_times') else None      # the last eager step, by phase (typed partition)
+    phases = None
+    if args.full:
+        spmm_events.clear()
+        pair_events.clear()
+        scatter_events.clear()
+        del kinds_seen[:]
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            scores = runner.step()
+        eager_host_dt = time.perf_counter() - t0
+        barrier()
+        eager_dt = time.perf_counter() - t0
+        restore_spmm()
+        capi.chain = raw_chain
+        capi.scatter = raw_scatter
+        phases = runner.phase_times() if hasattr(runner, 'phase_times') else None      # the last eager step, by phase (typed partition)
     step = runner.step
     if graph_step:
         # Capture first, replay only once EVERY rank has a graph: a replay enqueues the step's collectives, which a rank whose
@@ -892,19 +924,25 @@ def main():
             step = runner.step_graphed
         barrier()
     t0 = time.perf_counter()
-    if graph_step:
+    if graph_step or not args.full:
         for _ in range(args.steps):
-            step()
+            scores = step()
         host_dt = time.perf_counter() - t0                    # time to ENQUEUE the steps (host-side launch cost)
         barrier()
         dt = time.perf_counter() - t0
-    else:
+    else:                                                     # --full without a graph: the instrumented eager steps are the timed ones
         host_dt, dt = eager_host_dt, eager_dt
-    per_rank = None
     if multi:
-        t = torch.tensor([dt, eager_dt], device=cdev, dtype=torch.float64)
+        t = torch.tensor([dt], device=cdev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        dt, eager_dt = float(t[0].item()), float(t[1].item())
+        dt = float(t[0].item())
+    if args.dump_outputs:                                     # before anything else runs a step into the same buffers
+        dump_scores(args.dump_outputs, scores, n_pairs, runner, rank, multi, cdev)
+    per_rank = None
+    if multi and args.full:
+        t = torch.tensor([eager_dt], device=cdev, dtype=torch.float64)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        eager_dt = float(t[0].item())
         # Self-check of the partitioned step (after the timed region): every rank runs the SINGLE-GPU step on the same inputs once (it
         # holds the whole graph) and compares the scores of its own pair shard — the multi-rank exchange has nothing else to vouch
         # for it on a node the builder never had (the oracle-checked tests cover 2-3 ranks over gloo and rank threads on one GPU).
@@ -924,25 +962,24 @@ def main():
         per_rank = [None] * world
         torch.distributed.all_gather_object(per_rank, mine)
 
-    spmm_ms = [e0.elapsed_time(e1) for e0, e1 in spmm_events]
-    rows_local = runner.local_rows
-    nnz_local = runner.local_nnz
-    f = GRID1['n_hiddens'][0]
-    kind = {'gcn_layer': 'csr', 'spmm_sj': 'sj', 'spmm_xs': 'xs', 'spmm_lt': 'lt'}[kinds_seen[0]] if kinds_seen else 'none'
-    alg_bytes = nnz_local * 8 + (rows_local + 1) * 4 + (n_nodes + rows_local) * f * 4
-    avg_ms = float(np.mean(spmm_ms)) if spmm_ms else float('nan')
-    achieved = alg_bytes / (avg_ms * 1e-3) / 1e9
-    pmc, traffic_source = (pmc_profile(args.scale, kind) if not multi else (None, 'not profiled for multi-rank runs'))
-    kernel_names = {'sj': 'spmm_sj_kernel<8>', 'xs': 'spmm_xs_partial_kernel<8> + spmm_xs_combine_kernel<8>', 'csr': 'spmm_stream_kernel<8>',
-                    'lt': 'spmm_lt_kernel<8> (LDS-tiled, one launch)', 'none': 'none'}
+    if args.full:
+        spmm_ms = [e0.elapsed_time(e1) for e0, e1 in spmm_events]
+        rows_local = runner.local_rows
+        nnz_local = runner.local_nnz
+        f = GRID1['n_hiddens'][0]
+        kind = {'gcn_layer': 'csr', 'spmm_sj': 'sj', 'spmm_xs': 'xs', 'spmm_lt': 'lt'}[kinds_seen[0]] if kinds_seen else 'none'
+        alg_bytes = nnz_local * 8 + (rows_local + 1) * 4 + (n_nodes + rows_local) * f * 4
+        avg_ms = float(np.mean(spmm_ms)) if spmm_ms else float('nan')
+        achieved = alg_bytes / (avg_ms * 1e-3) / 1e9
+        pmc, traffic_source = (pmc_profile(args.scale, kind) if not multi else (None, 'not profiled for multi-rank runs'))
+        kernel_names = {'sj': 'spmm_sj_kernel<8>', 'xs': 'spmm_xs_partial_kernel<8> + spmm_xs_combine_kernel<8>', 'csr': 'spmm_stream_kernel<8>',
+                        'lt': 'spmm_lt_kernel<8> (LDS-tiled, one launch)', 'none': 'none'}
 
     s256 = None
-    if args.scale == 64 and not args.no_s256 and not rehearse:     # every rank takes part (its collectives); rank 0 reports
+    if args.full and args.scale == 64 and not args.no_s256 and not rehearse:     # every rank takes part (its collectives); rank 0 reports
         s256 = larger_scale_leg(256, args.steps, rank, world, local_rank, multi, rehearse)
 
     if rank == 0:
-        # what the dispatched image actually streams per launch (the 8(d) formula counts a canonical 8-byte CSR entry)
-        image_entry_bytes = {'csr': 8, 'sj': 8, 'xs': 4, 'lt': 4, 'none': 0}[kind]
         out = {
             'metric': '(user,item) pairs scored/sec, ML-1M basic-gnn 2-layer, 1/2/4/8 MI355X',
             'value': n_pairs * args.steps / dt, 'unit': 'pairs/s', 'csrc_sha': csrc_sha(),
@@ -959,19 +996,22 @@ def main():
                        'scale': args.scale, 'parallelism': runner.describe() + (' (step replayed from a hipGraph)' if graph_step else '') +
                        (' — one-GPU rehearsal over gloo: NOT a scaling measurement' if rehearse else ''),
                        **({'retry': retry + ': eager steps timed'} if retry else {})},
-            'roofline': {'bound': 'hbm', 'kernel': kernel_names[kind] + ' (fused GCN layer: SpMM + bias + ReLU + next X.W)', 'achieved': achieved,
-                         'peak': HBM_PEAK_GBPS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBPS,
-                         'traffic': pmc['traffic_bytes_per_launch'] if pmc else None, 'traffic_source': traffic_source,
-                         'algorithmic_bytes_per_launch': alg_bytes, 'avg_launch_ms': avg_ms,
-                         'launches_timed': len(spmm_ms), 'timed_in': 'the K eager steps just before the replayed ones' if graph_step else 'timed region',
-                         'note': 'achieved = SURVEY 8(d) bytes (canonical CSR: 8 B per non-zero) / time, i.e. a CSR-equivalent effective '
-                                 'bandwidth; the dispatched image streams {} B per non-zero'.format(image_entry_bytes)},
-            'propagation_ms': runner.last_propagation_ms(),
             'host_enqueue_ms_per_step': 1e3 * host_dt / args.steps,
-            'eager': {'ms_per_step': 1e3 * eager_dt / args.steps, 'value': n_pairs * args.steps / eager_dt, 'unit': 'pairs/s',
-                      'host_enqueue_ms_per_step': 1e3 * eager_host_dt / args.steps,
-                      'note': 'the same K steps launched one kernel at a time, each SpMM / pair-stage launch bracketed by HIP events'},
         }
+    if rank == 0 and args.full:
+        # what the dispatched image actually streams per launch (the 8(d) formula counts a canonical 8-byte CSR entry)
+        image_entry_bytes = {'csr': 8, 'sj': 8, 'xs': 4, 'lt': 4, 'none': 0}[kind]
+        out['roofline'] = {'bound': 'hbm', 'kernel': kernel_names[kind] + ' (fused GCN layer: SpMM + bias + ReLU + next X.W)', 'achieved': achieved,
+                           'peak': HBM_PEAK_GBPS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBPS,
+                           'traffic': pmc['traffic_bytes_per_launch'] if pmc else None, 'traffic_source': traffic_source,
+                           'algorithmic_bytes_per_launch': alg_bytes, 'avg_launch_ms': avg_ms,
+                           'launches_timed': len(spmm_ms), 'timed_in': 'the K eager steps just before the replayed ones' if graph_step else 'timed region',
+                           'note': 'achieved = SURVEY 8(d) bytes (canonical CSR: 8 B per non-zero) / time, i.e. a CSR-equivalent effective '
+                                   'bandwidth; the dispatched image streams {} B per non-zero'.format(image_entry_bytes)}
+        out['propagation_ms'] = runner.last_propagation_ms()
+        out['eager'] = {'ms_per_step': 1e3 * eager_dt / args.steps, 'value': n_pairs * args.steps / eager_dt, 'unit': 'pairs/s',
+                        'host_enqueue_ms_per_step': 1e3 * eager_host_dt / args.steps,
+                        'note': 'the same K steps launched one kernel at a time, each SpMM / pair-stage launch bracketed by HIP events'}
         if s256 is not None:
             out['s256'] = s256
         spread = value_spread(args.scale)
@@ -1053,6 +1093,7 @@ def main():
             out['ml1m_s1'], s1 = ml1m_true_size(dev)
             out['train_s1'] = train_true_size()
             out['cpu_baseline'] = cpu_baseline(s1, headline)
+    if rank == 0:
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
         print(json.dumps(out), flush=True)

@@ -1,30 +1,30 @@
 """CPU: the reference's own experiment files are consumed unmodified.
 
 Every `econfigs/*.yaml` of the reference tree is expanded with the product's grid logic on top of the reference's
-`config.yaml`, and every resulting model section is instantiated (weights built, no device work).  The reference tree only
-exists in the build container: elsewhere the test skips (nothing of it is copied into this repository)."""
-import glob
+`config.yaml`, and every resulting model section is instantiated (weights built, no device work).  The files' model sections and
+dataset load functions, as the product's YAML reader returns them, are stored in tests/golden/econfigs_reference.json
+(made by tests/golden/make_econfigs_golden.py)."""
+import json
 import os
 
 import numpy as np
 import pytest
 from scipy import sparse
 
-REFERENCE = '/root/reference'
-ECONFIGS = sorted(glob.glob(os.path.join(REFERENCE, 'econfigs', '*.yaml')))
+GOLDEN = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'econfigs_reference.json')))
+ECONFIGS = sorted(GOLDEN['econfigs'])
 
 
-@pytest.mark.skipif(not ECONFIGS, reason="reference tree not present")
-@pytest.mark.parametrize('path', ECONFIGS, ids=[os.path.basename(p) for p in ECONFIGS])
+@pytest.mark.parametrize('path', ECONFIGS)
 def test_every_reference_experiment_file_expands_and_builds(path):
     import copy
-    from deep_cbrs_amar_renaissance_amd import experiment, models as models_pkg
+    from deep_cbrs_amar_renaissance_amd import models as models_pkg
     from deep_cbrs_amar_renaissance_amd.data import loaders
     from deep_cbrs_amar_renaissance_amd.models.basic import BasicGNN
     from deep_cbrs_amar_renaissance_amd.models.hybrid import HybridBertGNN
     from deep_cbrs_amar_renaissance_amd.utilities.utils import make_grid, nested_dict_update
-    base = experiment.load_yaml(os.path.join(REFERENCE, 'config.yaml'))
-    cfg = experiment.load_yaml(path) or {}
+    base = GOLDEN['base']
+    cfg = GOLDEN['econfigs'][path]
     experiments = dict(cfg.get('linear') or {})
     for grid in (cfg.get('grid') or {}).values():
         experiments.update({str(e): e for e in make_grid(grid)})

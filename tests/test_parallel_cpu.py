@@ -69,6 +69,9 @@ class NumpyOps:
 def _typed_worker(rank, world, port, out_dir, phases):
     """The typed partition (GCN stack of a model that knows its user / item split): equal-height blocks per node type, per layer one
     all-gather of the next gathered table and one of the item rows."""
+    # the kernels are NumpyOps here, so the models' tensors must be host tensors on a machine with a GPU too (a spawned process:
+    # the test process itself is untouched)
+    torch.cuda.is_available = lambda: False
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), AMAR_PART_PHASES=phases)
     dist.init_process_group('gloo', rank=rank, world_size=world)
     try:

@@ -56,12 +56,41 @@ def test_bench_two_ranks_rehearsed_on_one_gpu():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                        '--scale', '4', '--no-cpu-baseline'], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        '--scale', '4', '--full', '--no-cpu-baseline'], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
     out = json.loads(lines[0])
     assert out['n_gpus'] == 2 and out['value'] > 0 and 'roofline' in out and 'rehearsal' in out['config']['parallelism']
+
+
+def test_bench_plain_run_dumps_the_scores_of_its_last_step(tmp_path):
+    """A plain `python bench.py` (no --full) prints the headline line only; --dump-outputs writes the [P, 1] float32 scores of the last
+    timed step.  Two runs with the same arguments get the same inputs, so their scores agree; a two-rank run (rehearsed on one GPU)
+    gathers its shards into the same pair order."""
+    import re
+    import numpy as np
+
+    def run(name, gpus, **extra_env):
+        env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', **extra_env)
+        for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
+            env.pop(k, None)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(gpus), '--steps', '3', '--warmup', '1',
+                            '--scale', '4', '--dump-outputs', str(tmp_path / name)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out['steps'] == 3 and out['value'] > 0 and out['ms_per_step'] > 0 and out['unit'] == 'pairs/s' and out['dtype'] == 'f32'
+        assert not {'roofline', 'eager', 's256', 'cpu_baseline', 'multi_rank_parity'} & set(out), sorted(out)
+        scores = np.load(str(tmp_path / name / 'scores.npy'))
+        n_pairs = int(re.search(r'(\d+) test pairs', out['config']['workload']).group(1))
+        assert scores.dtype == np.float32 and scores.shape == (n_pairs, 1) and np.isfinite(scores).all()
+        return scores
+    first, again = run('a', 1), run('b', 1)
+    assert np.abs(first - again).max() < 1e-5
+    two = run('two', 2, AMAR_REHEARSE_ONE_GPU='1')
+    assert np.abs(first - two).max() < 1e-5
 
 
 @pytest.mark.parametrize('gpus', [1, 2])
@@ -75,7 +104,7 @@ def test_bench_launches_its_own_ranks(gpus):
     if gpus == 1:
         env['AMAR_FORCE_DIST'] = '1'                                 # the partitioned runner + RCCL with a single rank
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(gpus), '--steps', '2', '--warmup', '1',
-                        '--scale', '4', '--no-cpu-baseline'], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        '--scale', '4', '--full', '--no-cpu-baseline'], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith('{')][-1]
     out = json.loads(line)
