@@ -93,6 +93,9 @@ SIGNATURES = {
     'amar_adam_multi_f32': (ctypes.c_int, [_P, _I32, _I64, _P, _F32, _F32, _F32, _F32, _P, _P]),
     'amar_sum_into_f32': (ctypes.c_int, [_P, _I64, _F32, _P, _P]),
     'amar_topk_segmented_f32': (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
+    'amar_recommend_slices': (ctypes.c_int32, [_I64, _I32, _P, _I32, _I32]),
+    'amar_recommend_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P,
+                                          _I32, _I32, _P, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -841,6 +844,45 @@ def topk_segmented(seg_ptr, item_ids, scores, k):
         _ptr(seg_ptr, torch.int32, 'seg_ptr'), _ptr(item_ids, torch.int32, 'item_ids'),
         _ptr(scores, torch.float32, 'scores'), n_users, k, _ptr(out_items), _ptr(out_scores), _stream())
     _check(code, 'amar_topk_segmented_f32')
+    return out_items, out_scores
+
+
+def recommend(Tu, Ti, wpack, dims, acts, in_act, k, users=None, excl_ptr=None, excl_items=None, n_slices=0):
+    """Fused full-catalogue top-k of the split head (amar_recommend_f32): for every user row of `users` (all rows of Tu when None)
+    the k best items of Ti that are not in its exclusion CSR.  Returns (items int32 [m, k] (-1 padded), scores float32 [m, k]).
+    n_slices <= 0: the library's automatic item slicing (AMAR_RECOMMEND_SLICES overrides it)."""
+    n_users, c1 = int(Tu.shape[0]), int(Tu.shape[1])
+    n_items = int(Ti.shape[0])
+    if int(Ti.shape[1]) != c1:
+        raise ValueError("recommend: Tu and Ti must have the same width")
+    m = int(users.numel()) if users is not None else n_users
+    if n_slices <= 0:
+        n_slices = int(os.environ.get('AMAR_RECOMMEND_SLICES', '0'))
+    lib = load()
+    dims_c = (ctypes.c_int32 * len(dims))(*dims)
+    acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
+    slices = lib.amar_recommend_slices(m, n_items, dims_c, len(acts), int(n_slices))
+    if slices < 0:
+        _check(int(slices), 'amar_recommend_slices')
+    dev = Tu.device
+    out_items = torch.empty((m, k), dtype=torch.int32, device=dev)
+    out_scores = torch.empty((m, k), dtype=torch.float32, device=dev)
+    ws_i = ws_s = None
+    if slices > 1:
+        ws_i = torch.empty((m * slices * k,), dtype=torch.int32, device=dev)
+        ws_s = torch.empty((m * slices * k,), dtype=torch.float32, device=dev)
+    if (excl_ptr is None) != (excl_items is None):
+        raise ValueError("recommend: excl_ptr and excl_items go together")
+    if excl_ptr is not None and excl_ptr.numel() != n_users + 1:
+        raise ValueError("recommend: excl_ptr must have n_users + 1 entries")
+    code = lib.amar_recommend_f32(
+        _ptr(Tu, torch.float32, 'Tu'), _ld(Tu, 'Tu'), n_users, _ptr(Ti, torch.float32, 'Ti'), _ld(Ti, 'Ti'), n_items, c1,
+        _ptr(wpack, torch.float32, 'wpack'), dims_c, acts_c, len(acts), ACT_CODES[in_act],
+        _ptr(users, torch.int32, 'users'), m, _ptr(excl_ptr, torch.int32, 'excl_ptr'),
+        _ptr_entries(excl_items, torch.int32, 'excl_items') if excl_items is not None else None,
+        int(k), int(slices) if slices > 1 else 1, _ptr(ws_i), _ptr(ws_s),
+        _ptr(out_items) if m else None, _ptr(out_scores) if m else None, _stream())
+    _check(code, 'amar_recommend_f32')
     return out_items, out_scores
 
 

@@ -36,7 +36,7 @@ from deep_cbrs_amar_renaissance_amd.data import loaders
 from deep_cbrs_amar_renaissance_amd.models.basic import BasicRS, BasicGNN, BasicKnowledgeGCN, BasicTSGNN, BasicTWGNN
 from deep_cbrs_amar_renaissance_amd.models.hybrid import HybridCBRS, HybridBertGNN
 from deep_cbrs_amar_renaissance_amd.utilities.keras import get_total_parameters
-from deep_cbrs_amar_renaissance_amd.utilities.metrics import top_k_predictions, top_k_metrics
+from deep_cbrs_amar_renaissance_amd.utilities.metrics import full_ranking_metrics, recommendations_frame, top_k_predictions, top_k_metrics
 from deep_cbrs_amar_renaissance_amd.utilities.utils import \
     get_experiment_logger, nested_dict_update, make_grid, mlflow_linearize, setup_mlflow
 
@@ -214,9 +214,28 @@ class Experimenter:
                                       "recall_at_{}".format(k): recall_at[k],
                                       "f1_at_{}".format(k): f1_at[k]})
         metrics = pd.DataFrame([precision_at, recall_at, f1_at], index=['precision_at', 'recall_at', 'f1_at'])
+        if self.config.parameters.get('full_ranking_ks'):
+            self.evaluate_full_ranking([int(k) for k in self.config.parameters.get('full_ranking_ks')])
         self.logger.info('\n' + str(metrics))
         print('\n' + str(metrics))
         return metrics
+
+    def evaluate_full_ranking(self, ks):
+        """Opt-in (parameters.full_ranking_ks): every user's top-max(ks) among ALL items it has not rated in training
+        (`recommend()`), written as <predictions_dest>/full_ranking/top_<k>.tsv (user, item, score; original ids) and scored
+        against the test ratings with Precision / Recall / NDCG / HitRate @k (utilities/metrics.py:full_ranking_metrics)."""
+        users, items, scores = self.model.recommend(self.trainset, k=max(ks))
+        dest = path_join(self.predictions_dest, "full_ranking")
+        os.makedirs(dest, exist_ok=True)
+        for k in ks:
+            recommendations_frame(users, items[:, :k], scores[:, :k], self.trainset.users, self.trainset.items).to_csv(
+                path_join(dest, "top_{}.tsv".format(k)), sep='\t', header=False, index=False)
+        full = full_ranking_metrics(users, items, self.testset.ratings, ks)
+        self.run_log.log_metrics({'full_' + name: value for name, value in full.items()
+                                  if name not in ('users_evaluated', 'users_skipped')})
+        self.run_log.log_metrics({'full_ranking_users_evaluated': full['users_evaluated'],
+                                  'full_ranking_users_skipped': full['users_skipped']})
+        return full
 
     def run(self):
         self.train()

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from deep_cbrs_amar_renaissance_amd import capi
+from deep_cbrs_amar_renaissance_amd import recommend as rec
 from deep_cbrs_amar_renaissance_amd.engine import Model, ids_to_device, to_device_tensor
 from deep_cbrs_amar_renaissance_amd.models.dense import build_dense_network, build_dense_classifier
 from deep_cbrs_amar_renaissance_amd.models.gnn import GCN, GAT, GraphSage, LightGCN, DGCF
@@ -168,6 +169,70 @@ class BasicRS(Model):
                    sum_inputs=True, in_act=plan['in_act'])
         return out
 
+    # -- full-catalogue top-k (recommend.py) ------------------------------------------------------------------------
+    def recommend(self, trainset, k=10, users=None, exclude_seen=True):
+        """The k best items of every user in `users` (all users by default) among all items of `trainset` — every training pair of
+        `trainset.ratings` excluded unless exclude_seen=False.  The towers read `trainset.embeddings` (node-indexed rows).
+        Returns (users int64 [m], items int64 [m, k] (node ids, -1 padded), scores float32 [m, k] (-inf padded)), see recommend.py."""
+        rec.check_k(k)
+        rec.check_users(users, len(trainset.users))
+        tables = self._recommend_tables(trainset)
+        split = self._recommend_split(*tables)
+        if split is not None:
+            return rec.fused(split, split[2], trainset, k, users, exclude_seen)
+        return self._recommend_pairs(trainset, k, users, exclude_seen, towers=self.towers(*tables))
+
+    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None):
+        rec.check_k(k)
+        rec.check_users(users, len(trainset.users))
+        towers = towers if towers is not None else self.towers(*self._recommend_tables(trainset))
+        return rec.pairs(lambda u, i: self.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
+
+    def _recommend_route(self, trainset):
+        d = np.asarray(trainset.embeddings).shape[1]
+        if not self.built:
+            self.build_head(d, d)
+        return 'fused' if self._split_plan(d, d) is not None or self._rank_plan() is not None else 'pairs'
+
+    def _recommend_tables(self, trainset):
+        n_users, n_items = len(trainset.users), len(trainset.items)
+        table = to_device_tensor(trainset.embeddings)
+        if not self.built:
+            self.build_head(table.shape[1], table.shape[1])
+        return table[:n_users], table[n_users:n_users + n_items]
+
+    def _rank_plan(self):
+        """The rest of the classifier packed for amar_recommend_f32 when the towers themselves are too wide for the split plan
+        (basic-kge: 512 -> 256 -> 128): classifier c1 -> ... -> 1 with c1 and every hidden width <= 128, c1 % 4 == 0; else None."""
+        clf = list(self.clf.layers)
+        if len(clf) < 3 or clf[-1].units != 1 or len(clf) - 1 > capi.CHAIN_MAX_LAYERS + 1:
+            return None
+        rdims = [clf[0].units] + [l.units for l in clf[1:]]
+        if max(rdims) > capi.CHAIN_MAX_WIDTH or rdims[0] % 4:
+            return None
+        np_ = lambda p: p.detach().cpu().numpy()
+        rb, _ = capi.chain_pack([np_(l.kernel) for l in clf[1:]], [np_(l.bias) for l in clf[1:]])
+        return {'rest': (torch.from_numpy(rb).to(clf[0].kernel.device), rdims, [l.activation for l in clf[1:]]), 'in_act': clf[0].activation}
+
+    def _recommend_split(self, u_table, i_table):
+        """(Tu, Ti, plan) for the fused ranking: the towers with the classifier's first layer folded in (b1 on the item side), per
+        entity — through the split plan's chains where it exists, else the towers' Dense stacks and one Dense launch per side.
+        None when the classifier's rest has no fused ranking kernel (the pair route then ranks)."""
+        plan = self._split_plan(u_table.shape[1], i_table.shape[1])
+        if plan is not None:
+            tu, ti, _ = self.towers(u_table, i_table)
+            return tu, ti, plan
+        plan = self._rank_plan()
+        if plan is None:
+            return None
+        tu_full, ti_full = self.unet.apply2(u_table), self.inet.apply2(i_table)
+        l0 = self.clf.layers[0]
+        w1, d, c1 = l0.kernel.detach(), tu_full.shape[1], l0.units
+        tu = torch.empty((tu_full.shape[0], c1), dtype=torch.float32, device=tu_full.device)
+        ti = torch.empty((ti_full.shape[0], c1), dtype=torch.float32, device=ti_full.device)
+        capi.dense(tu_full, w1[:d].contiguous(), None, tu, act=None)
+        capi.dense(ti_full, w1[d:].contiguous(), l0.bias.detach().contiguous(), ti, act=None)
+        return tu, ti, plan
 
 class PairPlan:
     """A pair list prepared ONCE per dataset for the pair stage (the test Sequence's pairs are constant across steps and
@@ -284,6 +349,41 @@ class BasicGNN(Model, abc.ABC):
         """Keras ``fit``: BCE + L2 + Adam over the batches of `sequence` (training.py)."""
         from deep_cbrs_amar_renaissance_amd import training
         return training.fit(self, sequence, epochs=epochs, **kwargs)
+
+    # -- full-catalogue top-k (recommend.py) ------------------------------------------------------------------------
+    def recommend(self, trainset, k=10, users=None, exclude_seen=True):
+        """The k best items of every user in `users` (all users by default) among all items of `trainset` — every training pair of
+        `trainset.ratings` excluded unless exclude_seen=False.  One propagation, the towers once per entity, then one fused
+        score-and-select launch (amar_recommend_f32).  Returns (users int64 [m], items int64 [m, k] (node ids, -1 padded),
+        scores float32 [m, k] (-inf padded)), see recommend.py."""
+        rec.check_k(k)
+        rec.check_users(users, len(trainset.users))
+        tables = self._recommend_tables(trainset)
+        split = self.rs._recommend_split(*tables)
+        if split is not None:
+            return rec.fused(split, split[2], trainset, k, users, exclude_seen)
+        return self._recommend_pairs(trainset, k, users, exclude_seen, towers=self.rs.towers(*tables))
+
+    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None):
+        rec.check_k(k)
+        rec.check_users(users, len(trainset.users))
+        towers = towers if towers is not None else self.rs.towers(*self._recommend_tables(trainset))
+        return rec.pairs(lambda u, i: self.rs.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
+
+    def _recommend_route(self, trainset):
+        d = self.gnn.output_dim()
+        return 'fused' if self.rs._split_plan(d, d) is not None or self.rs._rank_plan() is not None else 'pairs'
+
+    def _recommend_tables(self, trainset):
+        """User / item rows of one (hoisted) propagation; the model's hoist state is left as it was found."""
+        n_users, n_items = len(trainset.users), len(trainset.items)
+        saved = (self.gnn.hoist, getattr(self.gnn, '_hoisted', None), self._towers)
+        self.gnn.hoist = True
+        try:
+            emb = self.gnn(None)
+        finally:
+            self.gnn.hoist, self.gnn._hoisted, self._towers = saved
+        return emb[:n_users], emb[n_users:n_users + n_items]
 
     def _hoist_begin(self, hoist):
         self.gnn.hoist = bool(hoist)

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from deep_cbrs_amar_renaissance_amd import capi
+from deep_cbrs_amar_renaissance_amd import recommend as rec
 from deep_cbrs_amar_renaissance_amd.engine import Model, ids_to_device, to_device_tensor
 from deep_cbrs_amar_renaissance_amd.layers.fusion import FusionLayer
 from deep_cbrs_amar_renaissance_amd.models.dense import build_dense_classifier, build_dense_network, build_residual_dense_network
@@ -266,6 +267,29 @@ class HybridCBRS(Model):
             outs.append(x)
         return self.clf.apply2(outs[0], outs[1]) if plain else self._tail(outs[0], outs[1])
 
+    # -- full-catalogue top-k (recommend.py): the dual-branch head has no fused kernel, so the pair route ranks -----------------
+    def recommend(self, trainset, k=10, users=None, exclude_seen=True):
+        """The k best items of every user in `users` (all users by default) among all items of `trainset` (a HybridUserItemEmbeddings:
+        node-indexed graph and BERT tables) — every training pair excluded unless exclude_seen=False.  Returns (users int64 [m],
+        items int64 [m, k] (node ids, -1 padded), scores float32 [m, k] (-inf padded)), see recommend.py."""
+        return self._recommend_pairs(trainset, k, users, exclude_seen)
+
+    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None):
+        rec.check_k(k)
+        rec.check_users(users, len(trainset.users))
+        towers = towers if towers is not None else self._recommend_towers(trainset)
+        return rec.pairs(lambda u, i: self.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
+
+    def _recommend_route(self, trainset):
+        return 'pairs'
+
+    def _recommend_towers(self, trainset):
+        n_users, n_items = len(trainset.users), len(trainset.items)
+        g, b = to_device_tensor(trainset.graph_embeddings), to_device_tensor(trainset.bert_embeddings)
+        if not self.built:
+            self.build_head(g.shape[1], b.shape[1])
+        return self.towers(g[:n_users], g[n_users:n_users + n_items], b[:n_users], b[n_users:n_users + n_items])
+
     @staticmethod
     def _rows(table, ids, base):
         if ids is None:
@@ -371,6 +395,39 @@ class HybridBertGNN(Model, abc.ABC):
         if ids is not None:
             sequence = _IdsWithoutBlocks(ids)
         return super().predict(sequence, hoist=hoist, **kwargs)
+
+    # -- full-catalogue top-k (recommend.py): pair route (no fused kernel for the dual-branch trunk) -----------------------------
+    def recommend(self, trainset, k=10, users=None, exclude_seen=True):
+        """The k best items of every user in `users` (all users by default) among all items of `trainset` — every training pair
+        excluded unless exclude_seen=False.  The BERT rows come from the registered table (`set_bert_table`, or the reference's
+        hybrid Sequence, registered as predict() does).  Returns (users int64 [m], items int64 [m, k] (node ids, -1 padded),
+        scores float32 [m, k] (-inf padded)), see recommend.py."""
+        return self._recommend_pairs(trainset, k, users, exclude_seen)
+
+    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None):
+        rec.check_k(k)
+        rec.check_users(users, len(trainset.users))
+        towers = towers if towers is not None else self._recommend_towers(trainset)
+        return rec.pairs(lambda u, i: self.rs.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
+
+    def _recommend_route(self, trainset):
+        return 'pairs'
+
+    def _recommend_towers(self, trainset):
+        n_users, n_items = len(trainset.users), len(trainset.items)
+        self.resident_ids(trainset)                      # the reference's hybrid Sequence: its BERT table, registered as predict() does
+        if self.bert_table is None:
+            raise ValueError("recommend() needs the BERT table: register it with set_bert_table() or pass the hybrid training Sequence")
+        bert = self.bert_table
+        saved = (self.gnn.hoist, getattr(self.gnn, '_hoisted', None), self._towers)
+        self.gnn.hoist = True
+        try:
+            emb = self.gnn(None)
+            if not self.rs.built:
+                self.rs.build_head(emb.shape[1], bert.shape[1])
+            return self.rs.towers(emb[:n_users], emb[n_users:n_users + n_items], bert[:n_users], bert[n_users:n_users + n_items])
+        finally:
+            self.gnn.hoist, self.gnn._hoisted, self._towers = saved
 
     def _hoist_begin(self, hoist):
         self.gnn.hoist = bool(hoist)

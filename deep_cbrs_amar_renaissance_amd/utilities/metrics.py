@@ -63,6 +63,62 @@ def top_k_predictions(predictions, users, items, k=5):
     return df
 
 
+def recommendations_frame(users, items, scores, user_ids, item_ids):
+    """`recommend()`'s output (user indices [m], node ids [m, k] (-1 padded), scores [m, k]) as the (users, items, scores) DataFrame
+    of `top_k_predictions`: original identifiers, each user's rows best first, padding dropped."""
+    users = np.asarray(users, dtype=np.int64).reshape(-1)
+    items = np.asarray(items, dtype=np.int64).reshape(len(users), -1)
+    scores = np.asarray(scores, dtype=np.float32).reshape(items.shape)
+    valid = items >= 0
+    df = pd.DataFrame()
+    df['users'] = np.asarray(user_ids)[np.repeat(users, items.shape[1]).reshape(items.shape)[valid]]
+    df['items'] = np.asarray(item_ids)[items[valid] - len(user_ids)]
+    df['scores'] = scores[valid].astype(np.float64)
+    return df
+
+
+def full_ranking_metrics(users, items, test_ratings, ks):
+    """Full-ranking evaluation of `recommend()`'s lists (users [m], node ids [m, K] best first, -1 padded) against the test
+    ratings ([P, 3]: user index, item node id, label): for every k in `ks` (<= K) the means over the users of `users` that have at
+    least one relevant test item (label 1) of
+        Precision@k = hits / k,  Recall@k = hits / |relevant|,  HitRate@k = [hits > 0],
+        NDCG@k = sum_{hit at rank r <= k} 1 / log2(r + 1)  /  sum_{r <= min(|relevant|, k)} 1 / log2(r + 1)
+    A list shorter than k counts its missing ranks as misses.  Returns {'precision_at_<k>', 'recall_at_<k>', 'ndcg_at_<k>',
+    'hit_at_<k>' for each k, 'users_evaluated', 'users_skipped'} (users without a relevant test item are skipped and counted)."""
+    users = np.asarray(users, dtype=np.int64).reshape(-1)
+    items = np.asarray(items, dtype=np.int64).reshape(len(users), -1)
+    ks = [int(k) for k in ks]
+    if any(k < 1 or k > items.shape[1] for k in ks):
+        raise ValueError("every k must lie in [1, {}] (the length of the lists)".format(items.shape[1]))
+    t = np.asarray(test_ratings)
+    relevant = {}
+    if len(t):
+        liked = t[t[:, 2] == 1]
+        for u, i in zip(liked[:, 0].astype(np.int64).tolist(), liked[:, 1].astype(np.int64).tolist()):
+            relevant.setdefault(u, set()).add(i)
+    disc = 1.0 / np.log2(np.arange(items.shape[1]) + 2.0)
+    sums = {k: np.zeros(4) for k in ks}
+    evaluated = skipped = 0
+    for row, u in enumerate(users.tolist()):
+        rel = relevant.get(u)
+        if not rel:
+            skipped += 1
+            continue
+        evaluated += 1
+        hit = np.array([i in rel for i in items[row].tolist()], dtype=np.float64)
+        for k in ks:
+            h = hit[:k].sum()
+            idcg = disc[:min(len(rel), k)].sum()
+            sums[k] += (h / k, h / len(rel), float((hit[:k] * disc[:k]).sum() / idcg), float(h > 0))
+    out = {}
+    for k in ks:
+        mean = sums[k] / evaluated if evaluated else sums[k]
+        out.update({'precision_at_{}'.format(k): float(mean[0]), 'recall_at_{}'.format(k): float(mean[1]),
+                    'ndcg_at_{}'.format(k): float(mean[2]), 'hit_at_{}'.format(k): float(mean[3])})
+    out['users_evaluated'], out['users_skipped'] = evaluated, skipped
+    return out
+
+
 def precision_recall_f1_at_k(test_filepath, predictions_filepath, k, sep='\t', short_lists='skip', no_relevant='skip',
                              relevance_threshold=1.0, counts=None):
     """Precision / Recall / F1 @k of a top-k predictions file against the test ratings, as `mimir.jar -holdout -cutoff k`

@@ -554,6 +554,28 @@ int amar_topk_segmented_f32(const int32_t *seg_ptr, const int32_t *item_ids, con
                             int32_t n_users, int32_t k, int32_t *out_items, float *out_scores,
                             amar_stream_t stream);
 
+/* Full-catalogue top-k of the split scoring head (models/basic.py:_split_plan: the classifier's first Dense layer folded
+ * into the towers), fused: for every listed user j (users[j], or j itself when users == NULL, m == n_users) and EVERY item
+ * i in 0..n_items-1 that is not in the user's exclusion list,
+ *     score(u, i) = rest( in_act( Tu[u, 0:c1] + Ti[i, 0:c1] ) )
+ * rest = the Dense stack packed by amar_chain_pack_f32 (dims[0] = c1, dims[n_layers] = 1: at least one Dense layer, then the
+ * 1-unit scorer), and the k best (score descending, item ascending on ties) are written to out_items / out_scores [m, k],
+ * padded with -1 / -inf when fewer than k items remain.  Nothing of size m x n_items is written.  Item ids are Ti rows.
+ * Exclusion CSR (optional, both NULL = rank every item): excl_ptr[n_users+1], excl_items sorted and de-duplicated per user,
+ * values in 0..n_items-1.  PRECONDITION: every users[j] < n_users (not checked on the device).
+ * A score is bit-identical to amar_chain_f32's f32 generic kernel on the same pair (its loop order, fragments and dot stage).
+ * Limits: c1 and every width <= 128, c1 % 4 == 0, <= 8 Dense layers before the scorer, k <= 64; else AMAR_EUNSUPPORTED.
+ * Tu, Ti, wpack 16-byte aligned, ldu / ldi multiples of 4.
+ * n_slices: item slices per user block (<= 0: automatic).  amar_recommend_slices returns the count a call will launch; with
+ * more than one, workspace_items / workspace_scores hold m * slices * k entries each (any contents) and a second launch
+ * merges the slices.  The result does not depend on the slicing, the other users of the call or the grid. */
+int32_t amar_recommend_slices(int64_t m, int32_t n_items, const int32_t *dims, int32_t n_layers, int32_t n_slices);
+int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const float *Ti, int64_t ldi, int32_t n_items, int32_t c1,
+                       const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers, int32_t in_act,
+                       const int32_t *users, int64_t m, const int32_t *excl_ptr, const int32_t *excl_items,
+                       int32_t k, int32_t n_slices, int32_t *workspace_items, float *workspace_scores,
+                       int32_t *out_items, float *out_scores, amar_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
