@@ -877,7 +877,7 @@ __global__ __launch_bounds__(1024) void dual_chain_full_kernel(const DualArgs a)
 // stacks) is split by the workgroup into 126 KB of bf16 fragments at its start, straight from global memory — blob and fragments
 // would not fit the LDS together; biases and the 1-unit layer stay f32 in a small tail.  AMAR_PAIR_MFMA=f32 keeps the f32 kernel.
 // PT pair tiles of 16 per wave and iteration, THREADS per workgroup (the 126 KB of fragments allow one workgroup per CU, so THREADS sets
-// the waves per SIMD and the registers a lane may hold: 768 -> 3 waves, 168 registers, PT = 1 — the default, see the launcher).
+// the waves per SIMD and the registers a lane may hold: 768 -> 3 waves, 168 registers, PT = 1 — the one form launched, see the launcher).
 template <int PT, int THREADS>
 __global__ __launch_bounds__(THREADS) void dual_chain_split_kernel(const DualArgs a) {
     constexpr int T = 4, KS = 2;
@@ -1163,8 +1163,8 @@ static int chain_run(const float *A, int64_t lda, int32_t Da, const int32_t *ids
     if (P == 0) return AMAR_OK;
     const size_t lds_bytes = (size_t)off * sizeof(float);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // tile budget: MAXT = widest layer / 16 rounded up to {3, 4, 8}; PT pair tiles per wave (register budget ~ MAXT * PT)
-    static const int force_pt = getenv("AMAR_CHAIN_PT") ? atoi(getenv("AMAR_CHAIN_PT")) : 0;
+    // tile budget: MAXT = widest layer / 16 rounded up to {3, 4, 8}; two pair tiles per wave (register budget ~ MAXT * 2: measured
+    // best on grid1/grid2/grid6 shapes against one and four, tools/exp_chain.py)
     const int maxt = maxw <= 48 ? 3 : (maxw <= 64 ? 4 : 8);
     bool full = (dims[0] + 15) / 16 == maxt && (!a.has_dot || a.dot_kt == maxt);
     for (int l = 0; l < a.n_layers; ++l) full = full && a.kt[l] == maxt && a.nt[l] == maxt;
@@ -1173,45 +1173,37 @@ static int chain_run(const float *A, int64_t lda, int32_t Da, const int32_t *ids
         relu = relu && a.act[l] == AMAR_ACT_RELU;
         relu_but_last = relu_but_last && a.act[l] == (l == a.n_layers - 1 ? AMAR_ACT_NONE : AMAR_ACT_RELU);
     }
-    static const bool no_am2 = getenv("AMAR_CHAIN_AM2") && atoi(getenv("AMAR_CHAIN_AM2")) == 0;   // A/B: run-time activations for the towers
-    const int am = relu ? 1 : (relu_but_last && !no_am2 ? 2 : 0);
-    int pt = 2;                                                   // measured best on grid1/grid2/grid6 shapes (tools/exp_chain.py)
-    if (force_pt == 1 || force_pt == 2 || (force_pt == 4 && maxt != 8)) pt = force_pt;
-    static const int gen_cap = getenv("AMAR_CHAIN_GRID") ? atoi(getenv("AMAR_CHAIN_GRID")) : 4096;
-#define AMAR_CHAIN_LAUNCH(MT, PTT)                                                                                      \
+    const int am = relu ? 1 : (relu_but_last ? 2 : 0);
+#define AMAR_CHAIN_LAUNCH(MT)                                                                                           \
     do {                                                                                                                \
-        int64_t blocks = (P + 4 * 16 * PTT - 1) / (4 * 16 * PTT);                                                       \
-        if (blocks > gen_cap) blocks = gen_cap;                                                                         \
-        auto kern = full ? (am == 1 ? chain_kernel<MT, PTT, true, 1> : am == 2 ? chain_kernel<MT, PTT, true, 2>         \
-                                                                               : chain_kernel<MT, PTT, true, 0>)        \
-                         : (am == 1 ? chain_kernel<MT, PTT, false, 1> : am == 2 ? chain_kernel<MT, PTT, false, 2>       \
-                                                                                : chain_kernel<MT, PTT, false, 0>);     \
+        int64_t blocks = (P + 4 * 16 * 2 - 1) / (4 * 16 * 2);                                                           \
+        if (blocks > 4096) blocks = 4096;                                                                               \
+        auto kern = full ? (am == 1 ? chain_kernel<MT, 2, true, 1> : am == 2 ? chain_kernel<MT, 2, true, 2>             \
+                                                                             : chain_kernel<MT, 2, true, 0>)            \
+                         : (am == 1 ? chain_kernel<MT, 2, false, 1> : am == 2 ? chain_kernel<MT, 2, false, 2>           \
+                                                                              : chain_kernel<MT, 2, false, 0>);         \
         if (lds_bytes > 64 * 1024 &&                                                                                    \
             hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,       \
                                 (int)lds_bytes) != hipSuccess)                                                          \
             return AMAR_ELAUNCH;                                                                                        \
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds_bytes, st, a);                                  \
     } while (0)
-    // pair stage (ReLU of the sum of two gathered rows, square ReLU layers): the pipelined kernel; AMAR_CHAIN_PIPE=0 keeps the generic one
-    static const bool no_pipe = getenv("AMAR_CHAIN_PIPE") && atoi(getenv("AMAR_CHAIN_PIPE")) == 0;
+    // pair stage (ReLU of the sum of two gathered rows, square ReLU layers): the pipelined kernel
     const bool a_dot_ok = !a.has_dot || a.dot_kt == maxt;
     const bool small_tables = lda < (1ll << 30) && ldb < (1ll << 30) && P < (1ll << 30) - (4ll << 20);   // 32-bit row bytes and positions (+ 3 strides of <= 8 192 workgroups)
-    if (!no_pipe && relu && a.sum_inputs && a.in_act == AMAR_ACT_RELU && full && a_dot_ok && a.ids_a && a.ids_b && a.Da == 16 * maxt &&
-        a.Db == a.Da && maxt <= 4 && pt == 2 && lds_bytes <= 64 * 1024 && small_tables) {
+    if (relu && a.sum_inputs && a.in_act == AMAR_ACT_RELU && full && a_dot_ok && a.ids_a && a.ids_b && a.Da == 16 * maxt &&
+        a.Db == a.Da && maxt <= 4 && lds_bytes <= 64 * 1024 && small_tables) {
         int64_t blocks = (P + 4 * 16 * 2 - 1) / (4 * 16 * 2);
         // 1 536 = 256 CUs x 3 resident workgroups x 2: whole rounds of workgroups, no tail (ml1m(s=64): 0.639 ms against 0.647 at 4 096,
-        // 0.658 at 8 192; AMAR_CHAIN_BLOCKS overrides — keep it a multiple of 8: PairPlan's XCD affinity)
-        static const int cap = getenv("AMAR_CHAIN_BLOCKS") ? atoi(getenv("AMAR_CHAIN_BLOCKS")) : 1536;
-        if (blocks > cap) blocks = cap;
-        if (blocks > 8192) blocks = 8192;
+        // 0.658 at 8 192; a multiple of 8: PairPlan's XCD affinity)
+        if (blocks > 1536) blocks = 1536;
         const dim3 grid((unsigned)blocks), block(256);
         if (a.out_index && !a.has_dot) return AMAR_EUNSUPPORTED;
         // products on the bf16 matrix instruction with three-way split operands (see the kernel's header); AMAR_PAIR_MFMA=f32: the f32 one
         static const bool f32_only = getenv("AMAR_PAIR_MFMA") && !strcmp(getenv("AMAR_PAIR_MFMA"), "f32");
         const size_t split_bytes = (((size_t)off + 3) & ~(size_t)3) * sizeof(float) + (size_t)a.n_layers * maxt * ((maxt + 1) / 2) * 3 * 1024;
         const bool split = !f32_only && split_bytes <= 64 * 1024;
-        static const size_t lds_pad = getenv("AMAR_CHAIN_LDS_PAD") ? (size_t)atoi(getenv("AMAR_CHAIN_LDS_PAD")) : 0;   // dev: fewer resident workgroups
-        const size_t lds = (split ? split_bytes : lds_bytes) + ((split ? split_bytes : lds_bytes) + lds_pad <= 64 * 1024 ? lds_pad : 0);
+        const size_t lds = split ? split_bytes : lds_bytes;
 #define AMAR_PIPE_LAUNCH(MT, SC)                                                                                          \
         do {                                                                                                              \
             if (split) hipLaunchKernelGGL((chain_pipe_kernel<MT, 2, SC, true>), grid, block, lds, st, a);                 \
@@ -1225,18 +1217,14 @@ static int chain_run(const float *A, int64_t lda, int32_t Da, const int32_t *ids
 #undef AMAR_PIPE_LAUNCH
         return amar_check_launch();
     }
-    // entity towers (one table, no dot, ReLU with an optionally linear last layer) in a shape with a compile-time kernel; AMAR_CHAIN_ROWS=0
-    // keeps the generic one
-    static const bool no_rows = getenv("AMAR_CHAIN_ROWS") && atoi(getenv("AMAR_CHAIN_ROWS")) == 0;
-    if ((!no_rows || n_seg > 0) && (am == 1 || am == 2) && !a.sum_inputs && a.Db == 0 && !a.has_dot && !a.out_index && (pt == 2 || n_seg > 0) && a.n_layers <= 3 &&
+    // entity towers (one table, no dot, ReLU with an optionally linear last layer) in a shape with a compile-time kernel
+    if ((am == 1 || am == 2) && !a.sum_inputs && a.Db == 0 && !a.has_dot && !a.out_index && a.n_layers <= 3 &&
         maxt <= 4 && lds_bytes <= 64 * 1024 && lda < (1ll << 30) && P < (1ll << 30) - (4ll << 20)) {
         const int shape = chain_shape(a.n_layers, a.kt[0], a.nt[0], a.n_layers > 1 ? a.nt[1] : 0, a.n_layers > 2 ? a.nt[2] : 0);
         // 1 024 workgroups = 4 per CU, every wave a few iterations deep in its prefetch (ml1m(s=64) towers: 0.059 ms against 0.063 at
-        // 4 096 and 0.068 for the generic kernel; AMAR_CHAIN_GRID overrides)
+        // 4 096 and 0.068 for the generic kernel)
         int64_t blocks = (P + 4 * 16 * 2 - 1) / (4 * 16 * 2);
-        const int64_t rows_cap = getenv("AMAR_CHAIN_GRID") ? gen_cap : 1024;
-        if (blocks > rows_cap) blocks = rows_cap;
-        if (blocks > 8192) blocks = 8192;
+        if (blocks > 1024) blocks = 1024;
         const dim3 grid((unsigned)blocks), block(256);
         bool done = true;
 #define AMAR_ROWS_CASE(NLL, A0, A1, A2, A3)                                                                                      \
@@ -1260,9 +1248,7 @@ static int chain_run(const float *A, int64_t lda, int32_t Da, const int32_t *ids
         if (done) return amar_check_launch();
     }
     if (n_seg > 0) return AMAR_EUNSUPPORTED;       // segments are read by the compile-time tower shapes only: the caller concatenates for the others
-    if (maxt == 3) { if (pt == 1) AMAR_CHAIN_LAUNCH(3, 1); else if (pt == 2) AMAR_CHAIN_LAUNCH(3, 2); else AMAR_CHAIN_LAUNCH(3, 4); }
-    else if (maxt == 4) { if (pt == 1) AMAR_CHAIN_LAUNCH(4, 1); else if (pt == 2) AMAR_CHAIN_LAUNCH(4, 2); else AMAR_CHAIN_LAUNCH(4, 4); }
-    else { if (pt == 1) AMAR_CHAIN_LAUNCH(8, 1); else AMAR_CHAIN_LAUNCH(8, 2); }
+    if (maxt == 3) AMAR_CHAIN_LAUNCH(3); else if (maxt == 4) AMAR_CHAIN_LAUNCH(4); else AMAR_CHAIN_LAUNCH(8);
 #undef AMAR_CHAIN_LAUNCH
     return amar_check_launch();
 }
@@ -1330,8 +1316,7 @@ int amar_dual_chain_indexed_f32(const float *const *A, const int64_t *lda, const
     int64_t blocks = (P + (THREADS / 64) * 16 * PT - 1) / ((THREADS / 64) * 16 * PT);
     if (blocks > 1024) blocks = 1024;
     // the common shape of the hybrid head (64-wide everywhere, ids on every table, ReLU throughout): guard-free kernel
-    static const bool no_full = getenv("AMAR_DUAL_FULL") && atoi(getenv("AMAR_DUAL_FULL")) == 0;
-    bool full = !no_full && D == 64 && W == 64 && in_act == AMAR_ACT_RELU && n_branch >= 1 && ida[0] && ida[1] && idb[0] && idb[1];
+    bool full = D == 64 && W == 64 && in_act == AMAR_ACT_RELU && n_branch >= 1 && ida[0] && ida[1] && idb[0] && idb[1];
     for (int b = 0; b < 2; ++b) full = full && lda[b] < (1ll << 32) && ldb[b] < (1ll << 32);
     for (int l = 0; l < n_branch; ++l) full = full && branch_acts[l] == AMAR_ACT_RELU;
     for (int l = 0; l < n_trunk - 1; ++l) full = full && trunk_acts[l] == AMAR_ACT_RELU;
@@ -1346,31 +1331,16 @@ int amar_dual_chain_indexed_f32(const float *const *A, const int64_t *lda, const
         a.n_frag = nf; a.tail_floats = tl;
         const size_t bytes = (size_t)nf * 3 * 1024 + (size_t)tl * sizeof(float);
         if (bytes <= 160 * 1024) {
-            static bool lds_ok[AMAR_MAX_DEVICES];
             // one pair tile per wave in 768-thread workgroups: three waves per SIMD with up to 168 registers each (164 used, no spills) —
             // 1 024 threads leave a lane 128 registers (25 spilled), two tiles per wave in 512 threads need 256 (two waves per SIMD, which do
             // not cover the un-prefetched gathers at the top of an iteration: 35 % of a wave's time in s_waitcnt).  ml1m(s=64), prepared
-            // list: 2.70 ms against 2.82 (two tiles, 512 threads) and 2.93 (1 024 threads).  AMAR_DUAL_PT=1 / 2: those forms.
-            static const int dual_pt = getenv("AMAR_DUAL_PT") ? atoi(getenv("AMAR_DUAL_PT")) : 0;
-            static bool lds_ok2[AMAR_MAX_DEVICES], lds_ok3[AMAR_MAX_DEVICES];
-            hipStream_t st = static_cast<hipStream_t>(stream);
-            if (dual_pt == 1) {
-                if (bytes > 64 * 1024)                                // (allowed once per device, for the largest image)
-                    if (const int rc = amar_allow_lds(reinterpret_cast<const void *>(dual_chain_split_kernel<1, 1024>), 160 * 1024, lds_ok)) return rc;
-                hipLaunchKernelGGL((dual_chain_split_kernel<1, 1024>), dim3((unsigned)blocks), dim3(1024), bytes, st, a);
-            } else if (dual_pt == 2) {
-                if (bytes > 64 * 1024)
-                    if (const int rc = amar_allow_lds(reinterpret_cast<const void *>(dual_chain_split_kernel<2, 512>), 160 * 1024, lds_ok2)) return rc;
-                int64_t blocks2 = (P + 8 * 32 - 1) / (8 * 32);
-                if (blocks2 > 1024) blocks2 = 1024;
-                hipLaunchKernelGGL((dual_chain_split_kernel<2, 512>), dim3((unsigned)blocks2), dim3(512), bytes, st, a);
-            } else {
-                if (bytes > 64 * 1024)
-                    if (const int rc = amar_allow_lds(reinterpret_cast<const void *>(dual_chain_split_kernel<1, 768>), 160 * 1024, lds_ok3)) return rc;
-                int64_t blocks3 = (P + 12 * 16 - 1) / (12 * 16);
-                if (blocks3 > 1024) blocks3 = 1024;
-                hipLaunchKernelGGL((dual_chain_split_kernel<1, 768>), dim3((unsigned)blocks3), dim3(768), bytes, st, a);
-            }
+            // list: 2.70 ms against 2.82 (two tiles, 512 threads) and 2.93 (1 024 threads); those two forms were removed.
+            static bool lds_ok[AMAR_MAX_DEVICES];
+            if (bytes > 64 * 1024)                                    // (allowed once per device, for the largest image)
+                if (const int rc = amar_allow_lds(reinterpret_cast<const void *>(dual_chain_split_kernel<1, 768>), 160 * 1024, lds_ok)) return rc;
+            int64_t blocks3 = (P + 12 * 16 - 1) / (12 * 16);
+            if (blocks3 > 1024) blocks3 = 1024;
+            hipLaunchKernelGGL((dual_chain_split_kernel<1, 768>), dim3((unsigned)blocks3), dim3(768), bytes, static_cast<hipStream_t>(stream), a);
             return amar_check_launch();
         }
     }

@@ -10,7 +10,6 @@
 //   LDS images are k-major so that the MFMA operand fetch (lane l: row/col l&31, k = l>>5)
 //   is a conflict-free ds_read_b32 for A and B alike.
 #include "amar_common.h"
-#include <stdlib.h>
 #include <string.h>
 
 namespace {
@@ -224,7 +223,7 @@ __global__ __launch_bounds__(256) void dense_mfma_small_kernel(const DenseArgs a
 // 128 columns in FOUR accumulators, so one A fragment read feeds four MFMAs (three LDS reads per four MFMAs instead of three per two)
 // and a k-tile's two barriers are paid once per 32 MFMAs per wave instead of once per 16.  Same k order per output: bit-identical.
 constexpr int BN2 = 128, B2_LD = BN2;
-template <int BKT>                                                  // k-tile depth: 16 or 32
+template <int BKT>                                                  // k-tile depth: 16 (a 32-deep tile was slower, 112 TFLOP/s against 116, and was removed)
 __global__ __launch_bounds__(256) void dense_mfma128_kernel(const DenseArgs a) {
     __shared__ float As[BKT * A_LD];
     __shared__ float Bs[BKT * B2_LD];
@@ -511,25 +510,20 @@ int amar_dense_f32(const float *X, int64_t ldx, const int32_t *ids,
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool vx = (ldx & 3) == 0 && amar_aligned16(X);
     const bool vw = (N & 3) == 0 && amar_aligned16(W);
-    static const bool no_full = getenv("AMAR_DENSE_FULL") && atoi(getenv("AMAR_DENSE_FULL")) == 0;     // development switch (A/B timing)
-    static const bool no_small = getenv("AMAR_DENSE_SMALL") && atoi(getenv("AMAR_DENSE_SMALL")) == 0;  // ... the batch-sized form
-    if (vx && vw && !w_trans && K % SK == 0 && N % SB == 0 && M <= 4096 && !no_full && !no_small) {
+    if (vx && vw && !w_trans && K % SK == 0 && N % SB == 0 && M <= 4096) {
         hipLaunchKernelGGL(dense_mfma_small_kernel, dim3((unsigned)((M + SB - 1) / SB), (unsigned)(N / SB)), block, 0, st, a);
         return amar_check_launch();
     }
-    static const bool no_128 = getenv("AMAR_DENSE_128") && atoi(getenv("AMAR_DENSE_128")) == 0;        // ... the 128-column tile
     // the 128-column tile only where it still fills the chip: a batch-sized product (1 024 rows x 768 -> 256: the first layer of a content
     // tower inside model.fit) is 32 workgroups of it, each walking K alone on its CU — 64 us against 38 with the 64-column tile's 64 workgroups
-    if (vx && vw && !w_trans && K % BK == 0 && N % BN2 == 0 && !no_full && !no_128 && ((gx + 7) / 8) * 8 * (N / BN2) >= 256) {
+    if (vx && vw && !w_trans && K % BK == 0 && N % BN2 == 0 && ((gx + 7) / 8) * 8 * (N / BN2) >= 256) {
         DenseArgs a2 = a;
         a2.n_col_blocks = N / BN2;
         const int64_t total2 = ((gx + 7) / 8) * 8 * a2.n_col_blocks;
-        static const int bk2 = getenv("AMAR_DENSE_BK") ? atoi(getenv("AMAR_DENSE_BK")) : 16;            // development switch
-        if (bk2 == 32 && K % 32 == 0) hipLaunchKernelGGL(dense_mfma128_kernel<32>, dim3((unsigned)total2), block, 0, st, a2);
-        else hipLaunchKernelGGL(dense_mfma128_kernel<16>, dim3((unsigned)total2), block, 0, st, a2);
+        hipLaunchKernelGGL(dense_mfma128_kernel<16>, dim3((unsigned)total2), block, 0, st, a2);
         return amar_check_launch();
     }
-    if (vx && vw && !w_trans && K % BK == 0 && N % BN == 0 && !no_full) hipLaunchKernelGGL((dense_mfma_kernel<true, true, true>), grid, block, 0, st, a);
+    if (vx && vw && !w_trans && K % BK == 0 && N % BN == 0) hipLaunchKernelGGL((dense_mfma_kernel<true, true, true>), grid, block, 0, st, a);
     else if (vx && vw) hipLaunchKernelGGL((dense_mfma_kernel<true, true>), grid, block, 0, st, a);
     else if (vx) hipLaunchKernelGGL((dense_mfma_kernel<true, false>), grid, block, 0, st, a);
     else if (vw) hipLaunchKernelGGL((dense_mfma_kernel<false, true>), grid, block, 0, st, a);

@@ -2,7 +2,6 @@
 // sum / mean of ReductionLayer.  Reference semantics: src/layers/reduction.py:15-33,
 // src/layers/fusion.py:51-53.  Pure HBM-bound element work: one float per lane, rows contiguous.
 #include "amar_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -197,8 +196,7 @@ int amar_scatter_f32(const float *src, const int32_t *index, float *dst, int64_t
                      int32_t n_windows, amar_stream_t stream) {
     if (n < 0 || !src || !index || !dst || ldd < 1 || n_windows < 1 || n >= (1ll << 31)) return AMAR_EINVAL;
     if (n == 0) return AMAR_OK;
-    static const int per_xcd_env = getenv("AMAR_SCATTER_WG") ? atoi(getenv("AMAR_SCATTER_WG")) : 0;
-    const int per_xcd = per_xcd_env > 0 ? per_xcd_env : 32;   // 256 workgroups (ml1m(s=64): 0.060 ms against 0.064 at 512, 0.082 at 1 024)
+    constexpr int per_xcd = 32;                              // 256 workgroups (ml1m(s=64): 0.060 ms against 0.064 at 512, 0.082 at 1 024)
     hipLaunchKernelGGL(scatter_windows_kernel, dim3(8 * per_xcd), dim3(256), 0, static_cast<hipStream_t>(stream), src, index, dst, ldd, n,
                        window_off, n_windows, per_xcd);
     return amar_check_launch();

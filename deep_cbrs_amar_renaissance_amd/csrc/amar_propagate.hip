@@ -95,32 +95,14 @@ __device__ __forceinline__ void spmm_epilogue(const SpmmArgs &a, int row, float4
     }
 }
 
-// v1: one wavefront per row (kept for A/B timing: AMAR_SPMM_V1=1).
-template <int F, bool HAS_VALS, bool FUSE_NEXT>
-__global__ __launch_bounds__(WAVES_PER_BLOCK * AMAR_WAVE) void spmm_row_kernel(const SpmmArgs a) {
-    constexpr int LPN = F / 4;
-    const int lane = threadIdx.x & (AMAR_WAVE - 1);
-    const int row = blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
-    if (row >= a.n_rows) return;                       // wave-uniform
-    const int q = lane % LPN, slot = lane / LPN;
-    float wn[F];                                       // column `lane` of the next layer's kernel
-    if (FUSE_NEXT) {
-#pragma unroll
-        for (int k = 0; k < F; ++k) wn[k] = lane < a.Cn ? a.Wn[k * a.Cn + lane] : 0.f;
-    }
-    const int beg = a.rowptr[row], end = a.rowptr[row + 1];
-    const float4 y = row_gather_sum<LPN, HAS_VALS>(a.colidx, a.vals, a.X, a.ldx, beg, end, slot, q);
-    spmm_epilogue<F, FUSE_NEXT>(a, row, y, q, slot, lane, wn);
-}
-
-// v2: streaming form.  A wavefront owns `rpw` consecutive rows, i.e. ONE contiguous range of the
+// Streaming form.  A wavefront owns `rpw` consecutive rows, i.e. ONE contiguous range of the
 // colidx/vals arrays.  It streams that range in coalesced 64-entry register tiles (lane l holds
 // entry pt + l), always one tile ahead of use, so the HBM latency of the CSR stream is paid once
 // per wave instead of once per row; row boundaries come from one coalesced rowptr load kept in a
 // register and read with v_readlane.  Gather slots pick their (column, value) out of the tile
 // registers with a wavefront shuffle (ds_bpermute), gather the source row quad, and accumulate;
-// rows are finished in order with the same xor-butterfly and epilogue as v1, so v1 and v2 agree
-// bit for bit whenever a row's non-zeros fall in the same slot order (they do: slot = index mod NS).
+// rows are finished in order with row_gather_sum's xor-butterfly and spmm_epilogue, and slot s takes
+// the row's non-zeros s, s + NS, s + 2 NS, ... as it does there.
 template <int F, bool HAS_VALS, bool FUSE_NEXT>
 __global__ __launch_bounds__(WAVES_PER_BLOCK * AMAR_WAVE) void spmm_stream_kernel(const SpmmArgs a, const int rpw) {
     constexpr int LPN = F / 4, NS = AMAR_WAVE / LPN;
@@ -148,7 +130,7 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * AMAR_WAVE) void spmm_stream_kerne
         const int row_end = __builtin_amdgcn_readlane(rp, k + 1);
         float4 acc = f4_zero();
         int pos = row_beg;
-        // slot s of the row takes the row's non-zeros s, s+NS, s+2NS, ... exactly like v1
+        // slot s of the row takes the row's non-zeros s, s+NS, s+2NS, ...
         while (pos < row_end) {
             if (pos >= pt + 64) {                       // advance one tile, keep one tile in flight
                 ccur = cnxt; vcur = vnxt; pt += 64;
@@ -192,23 +174,9 @@ int spmm_rows_per_wave(int n_rows) {
 
 template <bool HAS_VALS, bool FUSE_NEXT>
 int launch_spmm(const SpmmArgs &a, int F, hipStream_t st) {
-    static const bool use_v1 = getenv("AMAR_SPMM_V1") != nullptr;
-    const dim3 block(WAVES_PER_BLOCK * AMAR_WAVE);
-    if (use_v1) {
-        const dim3 grid((a.n_rows + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-        switch (F) {
-        case 4:  hipLaunchKernelGGL((spmm_row_kernel<4, HAS_VALS, FUSE_NEXT>), grid, block, 0, st, a); break;
-        case 8:  hipLaunchKernelGGL((spmm_row_kernel<8, HAS_VALS, FUSE_NEXT>), grid, block, 0, st, a); break;
-        case 16: hipLaunchKernelGGL((spmm_row_kernel<16, HAS_VALS, FUSE_NEXT>), grid, block, 0, st, a); break;
-        case 32: hipLaunchKernelGGL((spmm_row_kernel<32, HAS_VALS, FUSE_NEXT>), grid, block, 0, st, a); break;
-        case 64: hipLaunchKernelGGL((spmm_row_kernel<64, HAS_VALS, FUSE_NEXT>), grid, block, 0, st, a); break;
-        default: return AMAR_EUNSUPPORTED;
-        }
-        return amar_check_launch();
-    }
     const int rpw = spmm_rows_per_wave(a.n_rows);
     const int waves = (a.n_rows + rpw - 1) / rpw;
-    const dim3 grid((waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
+    const dim3 grid((waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), block(WAVES_PER_BLOCK * AMAR_WAVE);
     switch (F) {
     case 4:  hipLaunchKernelGGL((spmm_stream_kernel<4, HAS_VALS, FUSE_NEXT>), grid, block, 0, st, a, rpw); break;
     case 8:  hipLaunchKernelGGL((spmm_stream_kernel<8, HAS_VALS, FUSE_NEXT>), grid, block, 0, st, a, rpw); break;
@@ -667,9 +635,9 @@ __device__ __forceinline__ int lt_lds_row(int v) {                    // virtual
     return AMAR_LT_WAVE_MAJOR ? w * RW + l : l * LT_WAVES + ((w + l) & (LT_WAVES - 1));
 }
 
-// ABL (development, tools/exp_lt.py): 1 = no atomic path, 2 = no LDS read-add-write, 4 = no gathers (timing only: wrong sums)
-// PACE: 0 = waves run free, 1 = one s_barrier per (pace_mask + 1) windows, 2 = arrival counters in LDS: a wave leaves window w
-// once every wave has left window w - 1 (one window of slack: measured slower than the barrier)
+// ABL (the on-chip floor of bench.py --full, AMAR_LT_VARIANT): 1 = no atomic path, 4 = no gathers (timing only: wrong sums)
+// PACE: 0 = waves run free, 1 = one s_barrier per (pace_mask + 1) windows (arrival counters in LDS with one window of slack
+// measured slower than the barrier; that form was removed)
 // OFF32: 0 = 64-bit gather addresses, 1 = 32-bit byte offsets, 2 = 32-bit offsets into a dense table (ldx == F: a shift, no multiply)
 // GAT: the attention layer on the same walk (amar_gat_lt_f32).  An entry (r, c) weighs w = exp(e_rc - M_r), e_rc =
 // LeakyReLU_0.2(s_self[r] + s_neigh[c]), against the row's fixed bound M_r = LeakyReLU(s_self[r] + max_j s_neigh[j]) >= max_c e_rc:
@@ -695,7 +663,8 @@ __global__ __launch_bounds__(LT_WAVES * AMAR_WAVE, AMAR_LT_MIN_WAVES) void spmm_
     float *ytile = lt_lds;                                            // [RW * LT_WAVES][F]
     float2 *side = reinterpret_cast<float2 *>(lt_lds + LT_WAVES * RW * F);          // GAT: [RW * LT_WAVES] (sum of weights, s_self)
     int32_t *ring_all = reinterpret_cast<int32_t *>(lt_lds + LT_WAVES * RW * (GAT ? F + 2 : F));   // [LT_WAVES][LT_CHUNK]
-    unsigned *arrived = reinterpret_cast<unsigned *>(ring_all + LT_WAVES * LT_CHUNK);   // [8] arrival counters (PACE 2)
+    // [8] arrival counters of the removed counter pacing: no longer read, still zeroed so that every kernel's code stays as measured
+    unsigned *arrived = reinterpret_cast<unsigned *>(ring_all + LT_WAVES * LT_CHUNK);
     const int t = blockIdx.x;
     const int lane = threadIdx.x & (AMAR_WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -749,7 +718,7 @@ __global__ __launch_bounds__(LT_WAVES * AMAR_WAVE, AMAR_LT_MIN_WAVES) void spmm_
         else if (OFF32 == 2) x[slot] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(a.X) + ((col * (unsigned)F + 4u * q) * 4u));
         else if (OFF32 == 1) x[slot] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(a.X) + (col * (unsigned)a.ldx + 4u * q) * 4u);
         else x[slot] = *reinterpret_cast<const float4 *>(a.X + (int64_t)col * a.ldx + 4 * q);
-        if (GAT) bs[slot] = (ABL & 8) ? 0.25f : *reinterpret_cast<const float *>(reinterpret_cast<const char *>(a.s_neigh) + (uint64_t)col * 4u);
+        if (GAT) bs[slot] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(a.s_neigh) + (uint64_t)col * 4u);
     };
     auto accumulate = [&](int slot) {
         const int w = wd[slot];
@@ -757,16 +726,12 @@ __global__ __launch_bounds__(LT_WAVES * AMAR_WAVE, AMAR_LT_MIN_WAVES) void spmm_
         const int lds_row = AMAR_LT_WAVE_MAJOR ? wave * RW + lrow : lrow * LT_WAVES + ((wave + lrow) & (LT_WAVES - 1));
         float *yp = ytile + lds_row * F + 4 * q;
         float4 xv = x[slot];
-        if (ABL & 2) {                                                // keep the gathers alive without LDS traffic
-            if (xv.x == 123.f && xv.y == 4.f) *reinterpret_cast<float4 *>(yp) = xv;
-            return;
-        }
         float wgt = 0.f, lsum = 0.f;
         if (GAT) {
-            const float2 sd = (ABL & 16) ? make_float2(0.f, 0.5f) : side[lds_row];   // (sum of weights so far, s_self of the row)
+            const float2 sd = side[lds_row];                         // (sum of weights so far, s_self of the row)
             lsum = sd.x;
             const float z = sd.y + bs[slot], zz = sd.y + bmax;
-            wgt = (ABL & 32) ? z * 0.01f : __expf(fmaxf(z, 0.2f * z) - fmaxf(zz, 0.2f * zz));
+            wgt = __expf(fmaxf(z, 0.2f * z) - fmaxf(zz, 0.2f * zz));
             xv.x *= wgt; xv.y *= wgt; xv.z *= wgt; xv.w *= wgt;
         }
         // implicit pair: same virtual row as the previous slot (row_shr: lane l reads l - LPN inside its 16-lane DPP row;
@@ -789,7 +754,7 @@ __global__ __launch_bounds__(LT_WAVES * AMAR_WAVE, AMAR_LT_MIN_WAVES) void spmm_
             float4 y = *reinterpret_cast<float4 *>(yp);
             y = f4_add(y, xv);
             *reinterpret_cast<float4 *>(yp) = y;
-            if (GAT && !(ABL & 16)) side[lds_row].x = lsum + wgt;     // the LPN lanes of the entry store the same value
+            if (GAT) side[lds_row].x = lsum + wgt;     // the LPN lanes of the entry store the same value
         }
         if (!(ABL & 1) && w < 0) {                                    // the row occurs earlier in this step: after its plain add
             atomicAdd(yp + 0, xv.x); atomicAdd(yp + 1, xv.y); atomicAdd(yp + 2, xv.z); atomicAdd(yp + 3, xv.w);
@@ -816,14 +781,6 @@ __global__ __launch_bounds__(LT_WAVES * AMAR_WAVE, AMAR_LT_MIN_WAVES) void spmm_
     auto pace = [&](int done) {                                       // `done` steps finished: leave every window that ends here
         while (wend <= done) {
             if (PACE == 1 && (win & a.pace_mask) == a.pace_mask) __builtin_amdgcn_s_barrier();
-            if (PACE == 2) {
-                if (lane == 0) atomicAdd(arrived + (win & 7), 1u);
-                if (win > 0) {
-                    const unsigned need = (unsigned)LT_WAVES * ((unsigned)(win - 1) / 8u + 1u);
-                    volatile unsigned *slot = arrived + ((win - 1) & 7);
-                    while (__builtin_amdgcn_readfirstlane((int)*slot) < (int)need) __builtin_amdgcn_s_sleep(1);
-                }
-            }
             ++win;
             wend = win < nwin ? window_end(win) : 0x7fffffff;
         }
@@ -1054,42 +1011,28 @@ int launch_spmm_lt(const LtArgs &a, int n_tiles, int off32, bool fuse, int varia
     constexpr int RW = LT_TILE_BYTES / (4 * F * LT_WAVES);
     const size_t lds = (size_t)LT_WAVES * RW * F * 4 + (size_t)LT_WAVES * LT_CHUNK * 4 + 32;
     const dim3 grid((unsigned)n_tiles), block(LT_WAVES * AMAR_WAVE);
-#define AMAR_LT_LAUNCH_S(OFF, FUSE, UU, PP, AA, SS) AMAR_LT_LAUNCH_P(OFF, FUSE, UU, PP, AA, SS, true)
-#define AMAR_LT_LAUNCH_P(OFF, FUSE, UU, PP, AA, SS, PR)                                                                 \
+#define AMAR_LT_LAUNCH_P(OFF, FUSE, PP, AA, SS, PR)                                                                     \
     do {                                                                                                                 \
-        auto kern = spmm_lt_kernel<F, OFF, FUSE, UU, PP, AA, false, SS, PR>;                                             \
+        auto kern = spmm_lt_kernel<F, OFF, FUSE, 4, PP, AA, false, SS, PR>;                                              \
         static bool allowed[AMAR_MAX_DEVICES] = {};                                                                      \
         if (const int rc = amar_allow_lds(reinterpret_cast<const void *>(kern), lds, allowed)) return rc;               \
         hipLaunchKernelGGL(kern, grid, block, lds, st, a);                                                               \
     } while (0)
-#define AMAR_LT_LAUNCH(OFF, FUSE, UU, PP, AA) AMAR_LT_LAUNCH_S(OFF, FUSE, UU, PP, AA, false)
+#define AMAR_LT_LAUNCH_S(OFF, FUSE, PP, AA, SS) AMAR_LT_LAUNCH_P(OFF, FUSE, PP, AA, SS, true)
+#define AMAR_LT_LAUNCH(OFF, FUSE, PP, AA) AMAR_LT_LAUNCH_S(OFF, FUSE, PP, AA, false)
     if constexpr (F >= 8) {
         if (sage) {                                                   // GraphSAGE tail fused (the layer's input is a dense table or a concat slice)
-            if (off32 == 2) AMAR_LT_LAUNCH_S(2, false, 4, 1, 0, true); else if (off32 == 1) AMAR_LT_LAUNCH_S(1, false, 4, 1, 0, true);
+            if (off32 == 2) AMAR_LT_LAUNCH_S(2, false, 1, 0, true); else if (off32 == 1) AMAR_LT_LAUNCH_S(1, false, 1, 0, true);
             else return AMAR_EUNSUPPORTED;
             return amar_check_launch();
         }
     } else if (sage) return AMAR_EUNSUPPORTED;
-    // variant (development, AMAR_LT_VARIANT; F = 8, dense table, no fused next layer only): see tools/exp_lt.py
+    // variant (AMAR_LT_VARIANT; F = 8, dense table, no fused next layer only): the on-chip floor of bench.py --full, wrong sums
     if constexpr (F == 8) {
         if (variant && off32 == 2 && !fuse) {
             switch (variant) {
-            case 1:  AMAR_LT_LAUNCH(2, false, 2, 1, 0); break;      // 1 step ahead
-            case 2:  AMAR_LT_LAUNCH(2, false, 4, 0, 0); break;      // unpaced
-            case 3:  AMAR_LT_LAUNCH(2, false, 8, 1, 0); break;      // 7 steps ahead
-            case 5:  AMAR_LT_LAUNCH(2, false, 4, 2, 0); break;      // counter pacing, one window of slack
-            case 8:  AMAR_LT_LAUNCH(1, false, 4, 1, 0); break;      // multiply-add addressing
-            // ablations (wrong sums; ABL bits: 1 no atomic path, 2 no LDS update, 4 no gathers): 20 + ABL paced, 30 + ABL unpaced
-            case 21: AMAR_LT_LAUNCH(2, false, 4, 1, 1); break;
-            case 22: AMAR_LT_LAUNCH(2, false, 4, 1, 2); break;
-            case 23: AMAR_LT_LAUNCH(2, false, 4, 1, 3); break;
-            case 24: AMAR_LT_LAUNCH(2, false, 4, 1, 4); break;
-            case 25: AMAR_LT_LAUNCH(2, false, 4, 1, 5); break;
-            case 27: AMAR_LT_LAUNCH(2, false, 4, 1, 7); break;
-            case 31: AMAR_LT_LAUNCH(2, false, 4, 0, 1); break;
-            case 33: AMAR_LT_LAUNCH(2, false, 4, 0, 3); break;
-            case 35: AMAR_LT_LAUNCH(2, false, 4, 0, 5); break;
-            case 37: AMAR_LT_LAUNCH(2, false, 4, 0, 7); break;
+            case 24: AMAR_LT_LAUNCH(2, false, 1, 4); break;         // no gathers, paced
+            case 35: AMAR_LT_LAUNCH(2, false, 0, 5); break;         // no gathers, no atomic path, unpaced
             default: return AMAR_EINVAL;
             }
             return amar_check_launch();
@@ -1097,32 +1040,14 @@ int launch_spmm_lt(const LtArgs &a, int n_tiles, int off32, bool fuse, int varia
     }
     if constexpr (F >= 8) {
         if (nopairs && off32 != 0) {                                  // an image without implicit pairs: the lean step (see PAIRS above)
-            if constexpr (F == 8) {                                   // development variants of the pair-free F = 8 kernel (tools/exp_lt8.py)
-                if (variant && off32 == 2 && !fuse) {
-                    switch (variant) {
-                    case 2:  AMAR_LT_LAUNCH_P(2, false, 4, 0, 0, false, false); break;      // unpaced
-                    case 3:  AMAR_LT_LAUNCH_P(2, false, 8, 1, 0, false, false); break;      // 7 steps ahead
-                    case 22: AMAR_LT_LAUNCH_P(2, false, 4, 1, 2, false, false); break;      // no LDS update (wrong sums)
-                    case 24: AMAR_LT_LAUNCH_P(2, false, 4, 1, 4, false, false); break;      // no gathers, paced (wrong sums)
-                    case 35: AMAR_LT_LAUNCH_P(2, false, 4, 0, 5, false, false); break;      // no gathers, no atomics, unpaced
-                    default: return AMAR_EINVAL;
-                    }
-                    return amar_check_launch();
-                }
-            }
-            static const int uenv = getenv("AMAR_LT_U") ? atoi(getenv("AMAR_LT_U")) : 0;      // development: steps of gathers in flight
-            if (uenv == 8 && off32 == 2) {
-                if (fuse) AMAR_LT_LAUNCH_P(2, true, 8, 1, 0, false, false); else AMAR_LT_LAUNCH_P(2, false, 8, 1, 0, false, false);
-                return amar_check_launch();
-            }
-            if (off32 == 2) { if (fuse) AMAR_LT_LAUNCH_P(2, true, 4, 1, 0, false, false); else AMAR_LT_LAUNCH_P(2, false, 4, 1, 0, false, false); }
-            else { if (fuse) AMAR_LT_LAUNCH_P(1, true, 4, 1, 0, false, false); else AMAR_LT_LAUNCH_P(1, false, 4, 1, 0, false, false); }
+            if (off32 == 2) { if (fuse) AMAR_LT_LAUNCH_P(2, true, 1, 0, false, false); else AMAR_LT_LAUNCH_P(2, false, 1, 0, false, false); }
+            else { if (fuse) AMAR_LT_LAUNCH_P(1, true, 1, 0, false, false); else AMAR_LT_LAUNCH_P(1, false, 1, 0, false, false); }
             return amar_check_launch();
         }
     }
-    if (off32 == 2) { if (fuse) AMAR_LT_LAUNCH(2, true, 4, 1, 0); else AMAR_LT_LAUNCH(2, false, 4, 1, 0); }
-    else if (off32 == 1) { if (fuse) AMAR_LT_LAUNCH(1, true, 4, 1, 0); else AMAR_LT_LAUNCH(1, false, 4, 1, 0); }
-    else { if (fuse) AMAR_LT_LAUNCH(0, true, 4, 1, 0); else AMAR_LT_LAUNCH(0, false, 4, 1, 0); }
+    if (off32 == 2) { if (fuse) AMAR_LT_LAUNCH(2, true, 1, 0); else AMAR_LT_LAUNCH(2, false, 1, 0); }
+    else if (off32 == 1) { if (fuse) AMAR_LT_LAUNCH(1, true, 1, 0); else AMAR_LT_LAUNCH(1, false, 1, 0); }
+    else { if (fuse) AMAR_LT_LAUNCH(0, true, 1, 0); else AMAR_LT_LAUNCH(0, false, 1, 0); }
 #undef AMAR_LT_LAUNCH
 #undef AMAR_LT_LAUNCH_S
 #undef AMAR_LT_LAUNCH_P
@@ -1135,31 +1060,15 @@ int launch_gat_lt(const LtArgs &a, int n_tiles, int off32, hipStream_t st) {
     const size_t lds = (size_t)LT_WAVES * RW * (F + 2) * 4 + (size_t)LT_WAVES * LT_CHUNK * 4 + 32;
     static_assert((size_t)LT_WAVES * RW * (F + 2) * 4 + (size_t)LT_WAVES * LT_CHUNK * 4 + 32 <= (160u << 10), "one workgroup's LDS");
     const dim3 grid((unsigned)n_tiles), block(LT_WAVES * AMAR_WAVE);
-#define AMAR_GAT_LT_LAUNCH_A(OFF, AA)                                                                                    \
+#define AMAR_GAT_LT_LAUNCH(OFF)                                                                                          \
     do {                                                                                                                 \
-        auto kern = spmm_lt_kernel<F, OFF, false, 4, 1, AA, true>;                                                       \
+        auto kern = spmm_lt_kernel<F, OFF, false, 4, 1, 0, true>;                                                        \
         static bool allowed[AMAR_MAX_DEVICES] = {};                                                                      \
         if (const int rc = amar_allow_lds(reinterpret_cast<const void *>(kern), lds, allowed)) return rc;               \
         hipLaunchKernelGGL(kern, grid, block, lds, st, a);                                                               \
     } while (0)
-#define AMAR_GAT_LT_LAUNCH(OFF) AMAR_GAT_LT_LAUNCH_A(OFF, 0)
-    if constexpr (F == 8) {                                           // development ablations (wrong results): tools/exp_gat_lt.py
-        static const int abl = getenv("AMAR_GAT_ABL") ? atoi(getenv("AMAR_GAT_ABL")) : 0;
-        if (abl && off32 == 2) {
-            switch (abl) {
-            case 8:  AMAR_GAT_LT_LAUNCH_A(2, 8); break;               // no s_neigh gather
-            case 16: AMAR_GAT_LT_LAUNCH_A(2, 16); break;              // no side-array traffic
-            case 24: AMAR_GAT_LT_LAUNCH_A(2, 24); break;
-            case 32: AMAR_GAT_LT_LAUNCH_A(2, 32); break;              // no exp
-            case 56: AMAR_GAT_LT_LAUNCH_A(2, 56); break;
-            default: return AMAR_EINVAL;
-            }
-            return amar_check_launch();
-        }
-    }
     if (off32 == 2) AMAR_GAT_LT_LAUNCH(2); else if (off32 == 1) AMAR_GAT_LT_LAUNCH(1); else AMAR_GAT_LT_LAUNCH(0);
 #undef AMAR_GAT_LT_LAUNCH
-#undef AMAR_GAT_LT_LAUNCH_A
     return amar_check_launch();
 }
 
@@ -1740,8 +1649,7 @@ static int rowwise_xw_run(const float *X, int64_t ldx, int32_t F, const float *W
     while (CP < C) CP <<= 1;
     if (attn && row_scale) return AMAR_EINVAL;                       // the attention scalars are defined on the un-scaled product
     XwArgs a{X, ldx, F, W, C, H, ldh, copy_to, ld_copy, a_self, a_neigh, attn ? s_self : nullptr, s_neigh, n_rows, row_scale, row_ids};
-    static const bool no_vec = getenv("AMAR_XW_VEC") && atoi(getenv("AMAR_XW_VEC")) == 0;            // development switch (A/B timing)
-    if (!no_vec && F == C && (F == 8 || F == 16) && (ldx & 3) == 0 && (ldh & 3) == 0 && amar_aligned16(X) && amar_aligned16(H) &&
+    if (F == C && (F == 8 || F == 16) && (ldx & 3) == 0 && (ldh & 3) == 0 && amar_aligned16(X) && amar_aligned16(H) &&
         (!copy_to || ((ld_copy & 3) == 0 && amar_aligned16(copy_to)))) {
         const int rows_per_block = F == 8 ? 512 : 256;              // (two rows per thread at F = 8)
         int64_t vblocks = ((int64_t)n_rows + rows_per_block - 1) / rows_per_block;
@@ -1988,7 +1896,7 @@ int amar_spmm_lt_f32(const int32_t *words, const int32_t *stream_start, const in
     a.e.Wn = Wnext; a.e.Cn = Cn; a.e.Hn = Hnext; a.e.ldhn = ldhn; a.e.n_rows = n_rows;
     const int off32 = (int64_t)n_cols * ldx * 4 < (int64_t(1) << 32) ? (ldx == F ? 2 : 1) : 0;
     const bool nopairs = (flags & AMAR_SPMM_LT_NOPAIRS) != 0;
-    const char *venv = getenv("AMAR_LT_VARIANT");               // development switch (tools/exp_lt.py)
+    const char *venv = getenv("AMAR_LT_VARIANT");               // on-chip floor of bench.py --full (24, 35)
     const int variant = venv ? atoi(venv) : 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (F) {

@@ -8,7 +8,6 @@
 // falls back to global float atomics (scatter_add_rows_kernel), whose last bits depend on the order of arrival; ids are range-checked
 // on the host (engine.ids_to_device).
 #include "amar_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -1349,11 +1348,8 @@ static int build_dense_stack(const float *X, int64_t ldx, const int32_t *ids, fl
     return AMAR_OK;
 }
 
-// batch-sized operands run in 16-row workgroups (see dense_stack_body); AMAR_DENSE_STACK_ROWS=64 keeps 64 (A/B timing)
-static bool dense_stack_small_rows(int64_t M) {
-    static const bool force64 = getenv("AMAR_DENSE_STACK_ROWS") && atoi(getenv("AMAR_DENSE_STACK_ROWS")) == 64;
-    return M <= 4096 && !force64;
-}
+// batch-sized operands run in 16-row workgroups (see dense_stack_body)
+static bool dense_stack_small_rows(int64_t M) { return M <= 4096; }
 
 int amar_dense_stack_f32(const float *X, int64_t ldx, const int32_t *ids, float *Xcopy, int64_t ldxc, int32_t n_layers,
                          const float *const *W, const float *const *bias, const int32_t *dims, const int32_t *acts,
@@ -1402,11 +1398,8 @@ int amar_dense_stack_pair_f32(const amar_dense_stack_desc *s0, const amar_dense_
 }
 
 // rows per workgroup (= per partial) of the stack's reverse pass: 16 up to 1 024 rows (64 workgroups of a batch instead of 16: the same
-// latency argument as the forward's), else 64; AMAR_DENSE_STACK_ROWS=64 keeps 64
-static int dense_stack_bwd_rows(int64_t M) {
-    static const bool force64 = getenv("AMAR_DENSE_STACK_ROWS") && atoi(getenv("AMAR_DENSE_STACK_ROWS")) == 64;
-    return (M <= 1024 && !force64) ? 16 : DB_ROWS;
-}
+// latency argument as the forward's), else 64
+static int dense_stack_bwd_rows(int64_t M) { return M <= 1024 ? 16 : DB_ROWS; }
 
 int64_t amar_dense_stack_bwd_groups(int64_t M) {
     if (M < 0) return AMAR_EINVAL;
@@ -1553,10 +1546,9 @@ int amar_dense_bwd_f32(const float *X, int64_t ldx, const float *Y, int64_t ldy,
     const bool vec_x = !use_x || ((K & 3) == 0 && (ldx & 3) == 0 && amar_aligned16(X));
     const bool vec = vec_rest && vec_x;
     // many rows of narrow operands (a convolution layer's reverse pass over every node): the row-walking kernel, `fold` of its workgroups
-    // per partial the caller sees (AMAR_DENSE_BWD_ROWS_OFF: the tile kernel, for A/B timing)
-    static const bool rows_off = getenv("AMAR_DENSE_BWD_ROWS_OFF") != nullptr;
+    // per partial the caller sees
     const bool rows_form = plan.fold > 1 && vec_rest && K <= 32 && N <= 32 && (!dX || ((lddx & 3) == 0 && amar_aligned16(dX))) &&
-                           (!dZ || ((lddz & 3) == 0 && amar_aligned16(dZ))) && !rows_off;      // (X may be read by single floats there)
+                           (!dZ || ((lddz & 3) == 0 && amar_aligned16(dZ)));      // (X may be read by single floats there)
     // the row-walking kernel up to 32 768 rows: one workgroup per partial the caller sees, no fold launch (9 228 rows at ml1m(s=1): 49
     // workgroups of three passes); beyond: up to 64 workgroups per partial
     const bool need_fold = plan.fold > 1 && !(rows_form && M <= 32768);
@@ -1632,8 +1624,7 @@ int amar_wgrad_f32(const float *X, int64_t ldx, const float *dZ, int64_t ldz, in
     if (dW && (!X || K < 1 || ldx < K)) return AMAR_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // wide layers over batch-sized operands: every 32 x 32 tile of dW by one workgroup on the matrix instruction, nothing to reduce
-    static const bool no_mfma = getenv("AMAR_WGRAD_MFMA") && atoi(getenv("AMAR_WGRAD_MFMA")) == 0;      // development switch (A/B timing)
-    if (dW && !no_mfma && M <= 16384 && (K & 3) == 0 && (N & 3) == 0 && (ldx & 3) == 0 && (ldz & 3) == 0 && amar_aligned16(X) && amar_aligned16(dZ) &&
+    if (dW && M <= 16384 && (K & 3) == 0 && (N & 3) == 0 && (ldx & 3) == 0 && (ldz & 3) == 0 && amar_aligned16(X) && amar_aligned16(dZ) &&
         (int64_t)((K + 31) / 32) * ((N + 31) / 32) >= 16) {
         const size_t lds = (size_t)2 * WM_ROWS * WM_STRIDE * sizeof(float);
         static bool allowed[AMAR_MAX_DEVICES] = {};
@@ -1666,8 +1657,7 @@ int amar_scatter_add_rows_f32(const float *src, int64_t lds, const int32_t *ids,
                               int64_t M, int32_t W, amar_stream_t stream) {
     if (M < 0 || W < 1 || !src || !ids || !dst || lds < W || ldd < W) return AMAR_EINVAL;
     if (M == 0) return AMAR_OK;
-    static const bool atomics = getenv("AMAR_SCATTER_ATOMIC") && atoi(getenv("AMAR_SCATTER_ATOMIC")) == 1;   // development switch (A/B)
-    if (M <= SCATTER_OWNER_MAX && !atomics) {
+    if (M <= SCATTER_OWNER_MAX) {
         int64_t blocks = (M + 3) / 4;                                 // one wavefront per position, every workgroup holds the id list
         if (blocks > 1024) blocks = 1024;
         hipLaunchKernelGGL(scatter_add_rows_owner_kernel, dim3((unsigned)blocks), dim3(256), (size_t)M * sizeof(int32_t), static_cast<hipStream_t>(stream),

@@ -244,11 +244,9 @@ class PairPlan:
 
     N_XCD, CHUNK = 8, 128
 
-    def __init__(self, u_ids, i_ids, phases=None):
+    def __init__(self, u_ids, i_ids, phases=1):
         p = int(u_ids.numel())
         dev = u_ids.device
-        if phases is None:
-            phases = int(os.environ.get('AMAR_PAIR_PHASES', '1'))
         pos = torch.arange(p, device=dev)
         # position -> class: (phase, XCD).  A workgroup walks its chunks in ascending position, so the first 1/phases of the
         # positions are visited first by every workgroup: with `phases` > 1 an XCD works through `phases` item ranges one after
@@ -263,12 +261,9 @@ class PairPlan:
         order_cls = torch.arange(n_cls, device=dev).view(phases, self.N_XCD).t().reshape(-1)     # (xcd, phase) -> class id
         bucket_sizes = slots[order_cls]
         bucket_of_rank = torch.repeat_interleave(order_cls, bucket_sizes)       # class of the k-th pair in item order
-        if os.environ.get('AMAR_PAIR_INNER', 'user') == 'user' and p:
-            # inside a range by user id, so that consecutive pairs also share user-tower rows (0.674 against 0.689 ms at
-            # ml1m(s=64) for the original order inside a range, AMAR_PAIR_INNER=pos; the scattered score writes cost nothing extra)
-            order = by_item[torch.argsort((bucket_of_rank * (int(u_ids.max()) + 1) + u_ids[by_item].to(torch.int64)) * p + by_item)]
-        else:
-            order = by_item[torch.argsort(bucket_of_rank * p + by_item)]        # (class, original position)
+        # inside a range by user id, so that consecutive pairs also share user-tower rows (0.674 against 0.689 ms at ml1m(s=64)
+        # for the original order inside a range, a form since removed; the scattered score writes cost nothing extra)
+        order = by_item[torch.argsort((bucket_of_rank * (int(u_ids.max()) + 1) + u_ids[by_item].to(torch.int64)) * p + by_item)] if p else by_item
         place = torch.argsort(cls * p + pos)                                    # positions grouped by class, ascending inside
         src = torch.empty(p, dtype=torch.int64, device=dev)
         src[place] = order                                                      # position -> original pair
@@ -282,15 +277,14 @@ class PairPlan:
         # list position) — each XCD appends to one open line per window, which its L2 completes —, and amar_scatter_f32 finishes inside
         # the windows, one window per XCD at a time (window_off).  Only for long lists: up to a few million scores the destination
         # mostly stays in the L2s and the direct store is the faster one (a rank of 4: 3.0 M pairs 0.115 against 0.125 ms; a rank of
-        # 2: 6.0 M pairs 0.289 against 0.242 ms) — AMAR_PAIR_WINDOW_MIN pairs (default 4 Mi); AMAR_PAIR_WINDOW=0: always direct.
+        # 2: 6.0 M pairs 0.289 against 0.242 ms) — AMAR_PAIR_WINDOW_MIN pairs (default 4 Mi).
         # window: about 185 of them (64 Ki scores at ml1m(s=64)'s 12 M pairs, 256 Ki at ml1m(s=256)'s 48 M: every XCD keeps one open line
         # per window, and the second launch's window stays a piece of the destination an L2 holds — ml1m(s=256): 5.05 ms per step
         # with 256 Ki against 5.14 with 64 Ki and 5.18 with the direct store)
-        auto = 1 << max(16, min(19, int(round(np.log2(max(p, 1) / 185.0)))))
-        self.window = int(os.environ.get('AMAR_PAIR_WINDOW', str(auto)))
+        self.window = 1 << max(16, min(19, int(round(np.log2(max(p, 1) / 185.0)))))
         self.mid_index = self.final_index = self.window_off = self.mid = None
         self.n_windows = 0
-        if self.window > 0 and p > 2 * self.window and p >= int(os.environ.get('AMAR_PAIR_WINDOW_MIN', str(1 << 22))):
+        if p > 2 * self.window and p >= int(os.environ.get('AMAR_PAIR_WINDOW_MIN', str(1 << 22))):
             n_win = -(-p // self.window)
             key = (src // self.window) * self.N_XCD + (pos // self.CHUNK) % self.N_XCD
             by_key = torch.argsort(key * p + pos)

@@ -229,7 +229,7 @@ class SingleRunner:
         self._prop_ms = None
         # the pair list does not change between steps: prepared once in XCD-affine item ranges (models/basic.py:PairPlan)
         self.pair_plan = None
-        if hasattr(model.rs, 'unet') and os.environ.get('AMAR_PAIR_PLAN', '1') != '0' and u_ids.numel() >= (1 << 16):
+        if hasattr(model.rs, 'unet') and u_ids.numel() >= (1 << 16):
             from deep_cbrs_amar_renaissance_amd.models.basic import PairPlan
             self.pair_plan = PairPlan(u_ids, i_ids)
 
@@ -365,7 +365,7 @@ class PartitionedGCNRunner:
         self.u_ids = u_ids[mine].to(torch.int32).contiguous()            # the reference's ids, unchanged
         self.i_ids = i_ids[mine].to(torch.int32).contiguous()
         self.pair_plan = None
-        if self.ops is capi and os.environ.get('AMAR_PAIR_PLAN', '1') != '0' and self.u_ids.numel() >= (1 << 16):
+        if self.ops is capi and self.u_ids.numel() >= (1 << 16):
             from deep_cbrs_amar_renaissance_amd.models.basic import PairPlan
             self.pair_plan = PairPlan(self.u_ids, self.i_ids)
         # item-row gathers behind the next kernels: only with a real process group (stand-ins copy synchronously)

@@ -89,9 +89,9 @@ class _DenseTape:
     @staticmethod
     def forward_pair(first, first_args, second, second_args):
         """Two independent stacks (the user and the item tower) in ONE launch where both take the one-launch forward
-        (capi.dense_stack_pair; AMAR_DENSE_PAIR=0: one launch each).  *_args = (x, ids, out_last)."""
+        (capi.dense_stack_pair).  *_args = (x, ids, out_last)."""
         s0, s1 = first._stack_spec(*first_args), second._stack_spec(*second_args)
-        if s0 is not None and s1 is not None and os.environ.get('AMAR_DENSE_PAIR', '1') != '0':
+        if s0 is not None and s1 is not None:
             capi.dense_stack_pair(s0, s1)
             return first._stack_done(s0), second._stack_done(s1)
         return first.forward(*first_args), second.forward(*second_args)
@@ -148,7 +148,7 @@ class _DenseTape:
         """The reverse passes of two independent stacks in ONE launch where both take the one-launch form (capi.dense_stack_bwd_pair)."""
         s0 = first._stack_bwd_spec(dy_first, False, need_input_grad, dx_out[0])
         s1 = second._stack_bwd_spec(dy_second, False, need_input_grad, dx_out[1])
-        if s0 is not None and s1 is not None and os.environ.get('AMAR_DENSE_PAIR', '1') != '0':
+        if s0 is not None and s1 is not None:
             lazy0, lazy1 = capi.dense_stack_bwd_pair(s0, s1)
             return first._stack_bwd_done(s0, lazy0, grads), second._stack_bwd_done(s1, lazy1, grads)
         return (first.backward(dy_first, grads, need_input_grad=need_input_grad, dx_out=dx_out[0]),
@@ -234,9 +234,8 @@ class _FusionTape:
 
     def plan_joined(self, rows, wa, wb, device):
         """For a concatenating fusion: (buffer, left half, right half) for the producers of its operands to store into, else
-        (None, None, None) — round 4: the two column copies of every `Concatenate` of a hybrid head were 6 of a batch's 54 launches
-        (AMAR_FUSION_INPLACE=0: copies)."""
-        if self.fuse.method != 'concatenate' or os.environ.get('AMAR_FUSION_INPLACE', '1') == '0':
+        (None, None, None) — round 4: the two column copies of every `Concatenate` of a hybrid head were 6 of a batch's 54 launches."""
+        if self.fuse.method != 'concatenate':
             return None, None, None
         buf = torch.empty((rows, wa + wb), dtype=torch.float32, device=device)
         return buf, buf[:, :wa], buf[:, wa:]

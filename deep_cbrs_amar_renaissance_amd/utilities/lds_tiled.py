@@ -40,7 +40,6 @@ Layout (all int32, device):
 Entries are value-free (weight 1; an entry of multiplicity c is stored c times): A = S C S exactly as the value-free
 XS image, with `diag`, `row_scale`, `col_scale`, `diag_offset` of the same meaning.
 """
-import os
 
 import numpy as np
 import torch
@@ -148,17 +147,17 @@ class LdsTiled:
         # each other in the L2s): one barrier per four 2 048-entry windows, 0.468 -> 0.430 ms per ml1m(s=64) product (every window 0.468,
         # every second 0.452, every eighth 0.456; F = 16 is flat: profiles/r3_exp_lt_pace_wide.txt)
         wide = F >= 32 and self.rw == geometry(F)[1]
-        self.pace_every = int(os.environ.get('AMAR_LT_PACE', 4 if steps == 1 or wide else (2 if steps == 2 else 1)))
+        self.pace_every = 4 if steps == 1 or wide else (2 if steps == 2 else 1)
 
     @classmethod
     def build(cls, rows, cols, n_rows, n_cols, F, diag, row_scale, col_scale, diag_offset=0, window_entries=None, n_cu=N_CU,
-              split=SPLIT, balance=True, row_breaks=(), rw=None, split_growth=2.0, pairs=None, layout=None, sub_window=None, spread=None, colsort=None):
+              split=SPLIT, balance=True, row_breaks=(), rw=None, split_growth=2.0, pairs=None, layout='deal', sub_window=None, spread=None):
         """`rows`/`cols`: int64 device tensors of the unit-weight off-diagonal entries (multiplicities expanded).
         `rw`: LDS rows per wave when the tile is smaller than the plain sum's (GAT mode); `split_growth`: factor by which the
         virtual-row length grows while the tiles do not fit the LDS (longer virtual rows repeat more often inside a step).
         `pairs`: whether the repeat in the slot right after a row's first entry of a step is left to the kernel's in-register
         pair (default: F < 16 — at 8 entries per step such repeats are 0.1 % of the entries and the pair logic a third of a step's
-        instructions; AMAR_LT_PAIRS=0|1 overrides).  An image without pairs runs with AMAR_SPMM_LT_NOPAIRS.
+        instructions).  An image without pairs runs with AMAR_SPMM_LT_NOPAIRS.
         `layout`: how a (wave, window) list is laid out over its steps.  'deal' (rounds 2-3): sorted by virtual row and dealt
         slot-major over the steps the list covers, so that a row's repeats land in different steps.  'defer' (round 4): the list
         keeps COLUMN order at the granularity of `sub_window` entries of the tile, and only the REPEATS of a virtual row inside
@@ -268,8 +267,6 @@ class LdsTiled:
         while True:
             tb, k_row_np, vcum, wanted, fill_in = make_tiles(cum, split)
             line_cost = 0.0 if big_table and not fill_in else COST_LINE
-            if os.environ.get('AMAR_LT_LINE_COST'):                   # development switch (A/B of the rule above)
-                line_cost = float(os.environ['AMAR_LT_LINE_COST'])
             for _ in range(BALANCE_PASSES if balance and m else 0):
                 tb0 = torch.tensor(tb, dtype=torch.int64, device=dev)
                 tile0 = torch.searchsorted(tb0, rows, right=True) - 1
@@ -327,8 +324,6 @@ class LdsTiled:
         # c. order inside a (tile, wave, window) list: by virtual row; then deal the list's entries to its stream positions
         #    slot-major over the steps the list covers, so that neighbours (same virtual row) land in different steps
         tw = tile * W + wave
-        if layout is None:
-            layout = os.environ.get('AMAR_LT_LAYOUT', 'deal')
         if layout == 'count':
             # windows by COUNT (round 4): window k of a wave = entries [k, k + 1) * S * EPS of the wave's OWN stream in column order,
             # S = window_entries / (W * EPS) steps — every wave runs exactly S steps between two barriers.  With windows cut by
@@ -351,7 +346,7 @@ class LdsTiled:
             raise ValueError("LT image: sort key overflow")
         defer = layout == 'defer'
         if defer:
-            sub_window = int(sub_window or os.environ.get('AMAR_LT_SUB_WINDOW', 0) or W * eps)
+            sub_window = int(sub_window or W * eps)
             n_sub = max(1, -(-window_entries // sub_window))
             o1 = torch.argsort(tile * n_cols + cols)                   # (column position inside the tile) // sub_window
             sw = torch.empty(m, dtype=torch.int64, device=dev)
@@ -387,23 +382,8 @@ class LdsTiled:
             del deal
         del rel
         lrow_s = lrow[order]
-        if spread is None:
-            spread = int(os.environ.get('AMAR_LT_SPREAD', 0))
         if spread:
             dest = _spread_repeats(dest, lrow_s, tw_s, stream_start, cnt_tw, eps, rw, total, int(spread))
-        if colsort is None:
-            colsort = os.environ.get('AMAR_LT_COLSORT') == '1'
-        if colsort and pairs is False and m:
-            # inside a step the slots are interchangeable once no pair logic reads them: order a step's entries by COLUMN, so that
-            # entries of one 128-byte line of X sit in neighbouring lanes of the gather (development: does the L1's tag path care?)
-            step_ = dest // eps
-            o5 = torch.argsort(step_ * n_cols + cols[order])
-            s5 = step_[o5]
-            first5 = torch.ones(m, dtype=torch.bool, device=dev)
-            first5[1:] = s5[1:] != s5[:-1]
-            dest = dest.clone()
-            dest[o5] = s5 * eps + (idx - _run_starts(first5, idx))
-            del o5, s5, first5, step_
         word = (lrow_s << cbits) | cols[order]
         # d. inside every step: the first entry of a virtual row is plain; the one in the next slot (same DPP row) is an implicit
         #    pair; every other repeat is flagged
@@ -419,8 +399,6 @@ class LdsTiled:
         rank = idx - run_start
         if pairs is None:
             pairs = F < 16 or rw_arg is not None                       # (the GAT geometry keeps them: its kernel form is not instantiated without)
-            if os.environ.get('AMAR_LT_PAIRS') in ('0', '1'):
-                pairs = os.environ['AMAR_LT_PAIRS'] == '1' or rw_arg is not None
         pair = (rank == 1) & (s4 == s4[run_start] + 1) & (s4 % spr != 0)
         if not pairs:
             pair = torch.zeros_like(pair)

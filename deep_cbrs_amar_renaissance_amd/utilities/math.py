@@ -426,8 +426,7 @@ def _csr_lds_tiled(self, F):
         # (a row block of a partition carries its type boundaries as LOCAL row numbers: parallel.TypedPartition.local_block)
         breaks = _row_breaks_of(self, rows, cols) if not hasattr(self, 'diag_offset') else tuple(getattr(self, 'row_breaks', None) or ())
         cache[F] = LdsTiled.build(rows, cols, n, self.shape[1], F, diag, col_scale[diag_offset:diag_offset + n].contiguous(),
-                                  col_scale, diag_offset, row_breaks=breaks,
-                                  window_entries=int(os.environ['AMAR_LT_WINDOW']) if os.environ.get('AMAR_LT_WINDOW') else None)
+                                  col_scale, diag_offset, row_breaks=breaks)
     return cache[F]
 
 
@@ -529,8 +528,7 @@ def _csr_tiled_gat_image(self, C):
         ones = torch.ones(self.shape[0], dtype=torch.float32, device=diag.device)
         breaks = _row_breaks_of(self, rows, cols) if not diag_offset else ()
         cache[C] = lds_tiled.LdsTiled.build(rows, cols, self.shape[0], self.shape[1], C, diag, ones, None, diag_offset,
-                                            row_breaks=breaks, rw=rw, split_growth=1.25,   # ml1m(s=64), C = 8: 0.364 ms (x2: 0.398)
-                                            window_entries=int(os.environ['AMAR_LT_WINDOW']) if os.environ.get('AMAR_LT_WINDOW') else None)
+                                            row_breaks=breaks, rw=rw, split_growth=1.25)   # ml1m(s=64), C = 8: 0.364 ms (x2: 0.398)
     return cache[C]
 
 

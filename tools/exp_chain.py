@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""A/B of the chain kernel's pair-tile count (AMAR_CHAIN_PT, read at first launch) on the bench's pair stage."""
+"""The chain kernels on the bench's pair stage: per-entity towers and pair classifier at three head shapes."""
 import os
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,8 +31,8 @@ def main():
         flops = P * (2 * d * clf[0] + clf[0] * clf[1]) * 2.0
         us = torch.sort(u).values
         med_s, _ = timeit(lambda: rs.score_towers(tw, us, i, 0, nu), reps=10)
-        print('{} PT={}: towers {:.3f} ms, pair clf {:.3f} ms ({:.2f} G pairs/s, {:.1f} TFLOP/s), user-sorted pairs {:.3f} ms'.format(
-            cfg_name, os.environ.get('AMAR_CHAIN_PT', 'default'), med_t, med_c, P / med_c / 1e6, flops / med_c / 1e9, med_s), flush=True)
+        print('{}: towers {:.3f} ms, pair clf {:.3f} ms ({:.2f} G pairs/s, {:.1f} TFLOP/s), user-sorted pairs {:.3f} ms'.format(
+            cfg_name, med_t, med_c, P / med_c / 1e6, flops / med_c / 1e9, med_s), flush=True)
 
 
 if __name__ == '__main__':

@@ -56,7 +56,7 @@ def main():
             times.append(e0.elapsed_time(e1) * 1e3)
             buf = (ctypes.c_ulonglong * (64 * 16))()
             assert lib.amar_ds_debug_copy(buf, 64 * 16) == 0
-            st = np.array(buf, dtype=np.int64).reshape(64, 16)[:min(64, (M + 15) // 16 if os.environ.get("AMAR_DENSE_STACK_ROWS") != "64" else M // 64)]
+            st = np.array(buf, dtype=np.int64).reshape(64, 16)[:min(64, (M + 15) // 16)]
             rows.append(st)
         st = np.stack(rows[2:])                                       # [rep, block, stamp]
         L = len(acts)

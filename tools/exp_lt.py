@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """LDS-tiled SpMM (amar_spmm_lt_f32) against the XCD-sliced form on ml1m(s): parity and time per launch, by window size
-and kernel variant (development aid).  Variants are selected per process (AMAR_LT_VARIANT is read once by the library):
-run as `python tools/exp_lt.py <scale> <F> <variant> [window ...]`."""
+and kernel variant (development aid).  Variants (AMAR_LT_VARIANT, F = 8 only): 0 the product, 24 / 35 the on-chip floors of
+bench.py --full (no gathers, paced / unpaced: wrong sums).  Run as `python tools/exp_lt.py <scale> <F> <variant,...> [window ...]`."""
 import os
 import sys
 import time

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Round 4: the F = 8 LT layer under image layouts / kernel forms (development aid).  One process = one build of the library
 (LT_LIB=tools/libamar_hip_old.so for the round-3 build).  `python tools/exp_lt8.py <scale> <F> <config> [<config> ...]` with
-config = layout:window:sub:pairs:pace:spread[:variant] (variant = AMAR_LT_VARIANT of the launch: development ablations), e.g. deal:0:0:1:0:0 (the round-3 image), deal:0:0:0:0:3 (no pairs, repeats spread), defer:2048:512:0:0:0.
+config = layout:window:sub:pairs:pace:spread[:variant] (variant = AMAR_LT_VARIANT of the launch: 24 / 35, the on-chip floors), e.g. deal:0:0:1:0:0 (the round-3 image), deal:0:0:0:0:3 (no pairs, repeats spread), defer:2048:512:0:0:0.
 Prints per config: build statistics, plain product and fused layer (bias + ReLU + concat slice + next X.W) ms per launch,
 max |diff| against the XCD-sliced form and bitwise reproducibility."""
 import os
@@ -58,8 +58,6 @@ def main():
         kw = {}
         if int(spread):
             kw['spread'] = int(spread)
-        if layout.endswith('+c'):
-            layout, kw['colsort'] = layout[:-2], True
         if layout != 'deal':
             kw.update(layout=layout, sub_window=int(sub) or None)
         t0 = time.perf_counter()

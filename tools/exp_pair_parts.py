@@ -50,20 +50,6 @@ def main():
                      ('(f) one row each, scattered store', run(zu, zi, po))):
         t, tmin = timeit(fn, reps=30)
         print('  %-44s %.4f ms (min %.4f)' % (name, t, tmin), flush=True)
-    # two-level way back: the kernel scatters into (window of the destination, XCD) streams, amar_scatter_f32 finishes inside windows
-    direct = rs.score_towers((tu, ti, True), u, i, 0, nu, pair_plan=plan).clone() if plan.mid_index is None else None
-    for win in (1 << 14, 1 << 15, 1 << 16, 1 << 17):
-        os.environ['AMAR_PAIR_WINDOW'] = str(win)
-        pl = basic.PairPlan(u, i)
-        t, tmin = timeit(lambda: rs.score_towers((tu, ti, True), u, i, 0, nu, pair_plan=pl), reps=30)
-        res2 = torch.empty((u.numel(), 1), dtype=torch.float32, device=dev)
-        t2, t2min = timeit(lambda: capi.scatter(pl.mid, pl.final_index, res2, pl.window_off, pl.n_windows), reps=30)
-        t3, t3min = timeit(lambda: capi.scatter(pl.mid, pl.final_index, res2, None, 1), reps=30)
-        got = rs.score_towers((tu, ti, True), u, i, 0, nu, pair_plan=pl)
-        os.environ['AMAR_PAIR_WINDOW'] = '0'
-        ref = rs.score_towers((tu, ti, True), u, i, 0, nu, pair_plan=basic.PairPlan(u, i))
-        print('  window %7d scores (%3d windows): both launches %.4f ms (min %.4f); the second alone %.4f ms (unwindowed walk %.4f); equal to the direct store: %s'
-              % (win, pl.n_windows, t, tmin, t2, t3, bool(torch.equal(got, ref))), flush=True)
     # the un-permute as its own pass (torch's indexing kernels as a first estimate)
     tmp = out.clone().view(-1)
     res = torch.empty_like(tmp)

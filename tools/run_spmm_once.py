@@ -27,7 +27,7 @@ def main():
         a.colidx.zero_()
     sj = a.sliced(F) if kind == 'sj' else None
     xs = a.xcd_sliced() if kind == 'xs' else None
-    lt = a.lds_tiled(F) if kind == 'lt' else None                    # AMAR_LT_WINDOW / AMAR_LT_VARIANT apply
+    lt = a.lds_tiled(F) if kind == 'lt' else None                    # AMAR_LT_VARIANT applies
     torch.cuda.synchronize()
     for _ in range(reps):
         if kind == 'sj':
