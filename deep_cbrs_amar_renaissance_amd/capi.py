@@ -90,6 +90,8 @@ SIGNATURES = {
     'amar_adam_f32': (ctypes.c_int, [_P, _P, _P, _P, _I64, _F32, _F32, _F32, _F32, _F32, _P]),
     'amar_adam_advance_f32': (ctypes.c_int, [_P, _F32, _F32, _F32, _P]),
     'amar_adam_dev_f32': (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _F32, _F32, _F32, _F32, _P]),
+    'amar_bpr_grad_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P]),
+    'amar_bpr_sample_i32': (ctypes.c_int, [_P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _I32, _I32, _P, _P, _P, _P]),
     'amar_adam_multi_f32': (ctypes.c_int, [_P, _I32, _I64, _P, _F32, _F32, _F32, _F32, _P, _P]),
     'amar_sum_into_f32': (ctypes.c_int, [_P, _I64, _F32, _P, _P]),
     'amar_topk_segmented_f32': (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
@@ -1119,6 +1121,31 @@ def bce_grad(p, y, dz, loss_terms):
     code = load().amar_bce_grad_f32(_ptr(p, torch.float32, 'p'), _ld(p, 'p') if p.dim() == 2 else 1, _ptr(y, torch.float32, 'y'),
                                     _ptr(dz, torch.float32, 'dz'), _ptr(loss_terms, torch.float32, 'loss_terms'), B, _stream())
     _check(code, 'amar_bce_grad_f32')
+
+
+def bpr_grad(p, dz, loss_terms):
+    """BPR loss terms and d(loss)/d(logit) for the probability column p ([B] or [B, 1]); dz [B, 1] / loss_terms [B] contiguous."""
+    B = p.shape[0]
+    if dz.numel() != B or loss_terms.numel() != B or not dz.is_contiguous() or not loss_terms.is_contiguous():
+        raise ValueError("bpr_grad: p [B] or [B, 1], dz and loss_terms of B contiguous floats expected")
+    code = load().amar_bpr_grad_f32(_ptr(p, torch.float32, 'p'), _ld(p, 'p') if p.dim() == 2 else 1, _ptr(dz, torch.float32, 'dz'),
+                                    _ptr(loss_terms, torch.float32, 'loss_terms'), B, _stream())
+    _check(code, 'amar_bpr_grad_f32')
+
+
+def bpr_sample(pos_ptr, pos_ids, neg_ptr, neg_ids, n_users, seed, step, u, items, y=None, advance=True):
+    """One BPR batch of h = items.numel() // 2 draws into u [2h], items [2h] (int32) and y [2h] (float32, optional); step: one
+    int64 on the device (the counter of the draws, advanced by one when `advance`).  The CSRs are int32 device tensors whose user
+    rows are all non-empty (checked by the caller where they are uploaded)."""
+    h = items.numel() // 2
+    if u.numel() != 2 * h or items.numel() != 2 * h or (y is not None and y.numel() != 2 * h) or step.numel() != 1 \
+            or step.dtype != torch.int64 or pos_ptr.numel() != n_users + 1 or neg_ptr.numel() != n_users + 1:
+        raise ValueError("bpr_sample: u, items (and y) of 2h elements, an int64 step and CSR row pointers [n_users + 1] expected")
+    code = load().amar_bpr_sample_i32(_ptr(pos_ptr, torch.int32, 'pos_ptr'), _ptr(pos_ids, torch.int32, 'pos_ids'),
+                                      _ptr(neg_ptr, torch.int32, 'neg_ptr'), _ptr(neg_ids, torch.int32, 'neg_ids'), int(n_users),
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, step.data_ptr() if step.is_cuda else _ptr(step), int(bool(advance)), h,
+                                      _ptr(u, torch.int32, 'u'), _ptr(items, torch.int32, 'items'), _ptr(y, torch.float32, 'y'), _stream())
+    _check(code, 'amar_bpr_sample_i32')
 
 
 def scatter_add_rows(src, ids, dst, base=0):

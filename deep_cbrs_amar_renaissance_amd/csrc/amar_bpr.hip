@@ -1,0 +1,93 @@
+// BPR training (gfx950): the pairwise loss's gradient and the on-device positive / negative sampler.
+//
+// amar_bpr_grad_f32 is the counterpart of amar_bce_grad_f32 (amar_train.hip) for utilities/losses.py:BPRLoss: one lane per pair
+// (j, h + j), no float atomics, so a training step stays reproducible bit for bit.
+// amar_bpr_sample_i32 draws one batch of data/datasets.py:UserItemGraphPosNegSample in the reference's layout from a counter-based
+// RNG (Philox4x32-10): the draws depend on (seed, step, j) only, so data/datasets.py:bpr_device_batch restates every id, and a step
+// index read from device memory lets a captured training graph draw new ids on every replay.
+#include "amar_common.h"
+
+namespace {
+
+// -log sigmoid(p[j] - p[h + j]) for j < h.  terms[j] = (B / h) * that, terms[h + j] = 0 (and the dropped trailing element of an odd
+// batch: 0), so that sum(terms) = B * loss like amar_bce_grad_f32's terms.  dz = d(loss)/d(logit) through the final sigmoid.
+__global__ __launch_bounds__(256) void bpr_grad_kernel(const float *__restrict__ p, int64_t ldp, float *__restrict__ dz,
+                                                       float *__restrict__ terms, int64_t B, int64_t h) {
+    const float scale = h ? (float)B / (float)h : 0.f, inv_h = h ? 1.f / (float)h : 0.f;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < h; j += (int64_t)gridDim.x * blockDim.x) {
+        const float a = p[j * ldp], b = p[(h + j) * ldp];
+        const float x = a - b;                                        // in (-1, 1): probabilities, so exp cannot overflow
+        const float e = expf(-x);
+        const float one_minus_s = e / (1.f + e);                      // 1 - sigmoid(x)
+        terms[j] = scale * log1pf(e);                                 // -log sigmoid(x)
+        terms[h + j] = 0.f;
+        const float g = one_minus_s * inv_h;
+        dz[j] = -g * (a * (1.f - a));
+        dz[h + j] = g * (b * (1.f - b));
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && 2 * h < B) {
+        dz[B - 1] = 0.f;
+        terms[B - 1] = 0.f;
+    }
+}
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
+        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+    }
+}
+
+__device__ __forceinline__ int32_t pick(uint32_t word, int32_t n) { return (int32_t)(((uint64_t)word * (uint32_t)n) >> 32); }
+
+// ONE workgroup: every lane reads *step before the barrier, one lane advances it after, so the batch sees one step value.
+__global__ __launch_bounds__(256) void bpr_sample_kernel(const int32_t *__restrict__ pos_ptr, const int32_t *__restrict__ pos_ids,
+                                                         const int32_t *__restrict__ neg_ptr, const int32_t *__restrict__ neg_ids,
+                                                         int32_t n_users, uint32_t key0, uint32_t key1, uint64_t *step, int32_t advance,
+                                                         int32_t h, int32_t *__restrict__ u, int32_t *__restrict__ items,
+                                                         float *__restrict__ y) {
+    const uint64_t s = *step;
+    for (int32_t j = threadIdx.x; j < h; j += blockDim.x) {
+        uint32_t c[4] = {(uint32_t)j, (uint32_t)s, (uint32_t)(s >> 32), 0u};
+        philox4x32_10(c, key0, key1);
+        const int32_t user = pick(c[0], n_users);
+        const int32_t p0 = pos_ptr[user], n_pos = pos_ptr[user + 1] - p0;
+        const int32_t q0 = neg_ptr[user], n_neg = neg_ptr[user + 1] - q0;
+        u[2 * j] = user;                                               // users = repeat(batch_users, 2)
+        u[2 * j + 1] = user;
+        items[j] = pos_ids[p0 + pick(c[1], n_pos)];                    // items = [pos ; neg]
+        items[h + j] = neg_ids[q0 + pick(c[2], n_neg)];
+        if (y) { y[j] = 1.f; y[h + j] = 0.f; }
+    }
+    __syncthreads();
+    if (advance && threadIdx.x == 0) *step = s + 1;
+}
+
+}  // namespace
+
+int amar_bpr_grad_f32(const float *p, int64_t ldp, float *dz, float *loss_terms, int64_t B, amar_stream_t stream) {
+    if (B < 1 || !p || !dz || !loss_terms || ldp < 1) return AMAR_EINVAL;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t h = B / 2;
+    if (h == 0) {                                                      // no pair: zero loss and gradient
+        hipLaunchKernelGGL(bpr_grad_kernel, dim3(1), dim3(64), 0, st, p, ldp, dz, loss_terms, B, (int64_t)0);
+        return amar_check_launch();
+    }
+    int64_t grid = (h + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(bpr_grad_kernel, dim3((unsigned)grid), dim3(256), 0, st, p, ldp, dz, loss_terms, B, h);
+    return amar_check_launch();
+}
+
+int amar_bpr_sample_i32(const int32_t *pos_ptr, const int32_t *pos_ids, const int32_t *neg_ptr, const int32_t *neg_ids,
+                        int32_t n_users, uint64_t seed, uint64_t *step, int32_t advance, int32_t h,
+                        int32_t *u, int32_t *items, float *y, amar_stream_t stream) {
+    if (n_users < 1 || h < 1 || !pos_ptr || !pos_ids || !neg_ptr || !neg_ids || !step || !u || !items) return AMAR_EINVAL;
+    hipLaunchKernelGGL(bpr_sample_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), pos_ptr, pos_ids, neg_ptr, neg_ids,
+                       n_users, (uint32_t)seed, (uint32_t)(seed >> 32), step, advance, h, u, items, y);
+    return amar_check_launch();
+}

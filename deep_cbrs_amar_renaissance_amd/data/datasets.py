@@ -10,9 +10,15 @@ Same constructor arguments, attributes (``ratings``, ``users``, ``items``, ``adj
 
 ids are int64 with item ids already offset by |U|; the last batch is short.  Shuffling uses
 ``np.random.RandomState(seed)`` re-drawn at every epoch end, like the reference.
-``UserItemGraphPosNegSample`` (BPR sampling) is out of scope.
+    UserItemGraphPosNegSample ((u_ids[2h], i_ids[2h]), y[2h]), h = batch_size // 2      datasets.py:216-306
+
+``UserItemGraphPosNegSample`` (BPR) draws its batches: on the host in ``__getitem__`` (the reference's stream) and, inside
+``fit()``, on the device (``bpr_device_batch`` states that kernel's draws).
 """
+import itertools as it
+
 import numpy as np
+from scipy import sparse
 
 
 class _RatingsSequence:
@@ -122,5 +128,129 @@ class UserItemGraphEmbeddings:
 
 
 class UserItemGraphPosNegSample:
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("BPR positive/negative sampling is out of scope (SURVEY.md §2 row 10)")
+    """Users with one positive and one negative candidate each, for the BPR loss (datasets.py:216-306 of the reference).
+
+    `adj_matrix` is the 'binary' adjacency (preprocess.build_adjacency_matrix): 1 for a liked pair, an explicit 0 for a disliked one.
+    As the reference does, the positives / negatives are the entries equal to 1 / 0 after ``todok()`` (which sums duplicates: a
+    positive rated twice becomes 2 and is in neither list), ``self.adj_matrix`` keeps the positives only (the graph the model
+    propagates over), and a user without an explicit negative gets `sample_size` candidates drawn once, with replacement, from the
+    items it has not liked.  All draws come from one ``np.random.RandomState(seed)`` in the reference's order.
+
+    ``__getitem__`` ignores `idx` and draws h = batch_size // 2 users, then one positive and one negative for each; it returns
+    ``users = repeat(batch_users, 2)``, ``items = [pos; neg]``, ``ratings = [1]*h + [0]*h``.  So pair j of the first half is
+    (batch_users[j // 2], pos_j), not (batch_users[j], pos_j): the reference's layout, kept as it is (DESIGN §7b).
+
+    ``pos_csr`` / ``neg_csr``: the per-user lists as CSR (int32 row pointers [|U|+1], int32 node ids), in the Sequence's own order —
+    what ``fit()`` uploads for the device sampler.
+    """
+
+    def __init__(self, ratings, users, items, adj_matrix, batch_size=512, seed=42, sample_size=10):
+        self.ratings = ratings
+        self.users = users
+        self.items = items
+        coo = adj_matrix if sparse.isspmatrix_coo(adj_matrix) else adj_matrix.tocoo()
+        coo.sum_duplicates()                              # what todok() does (in place): entries in (row, col) order = the dok's key order
+        row, col, val = coo.row, coo.col, coo.data
+        pos, neg = val == 1, val == 0
+        if not neg.any():
+            raise ValueError('Negative ratings are needed!!!')
+        self.adj_matrix = sparse.coo_matrix((val[pos], (row[pos], col[pos])), shape=adj_matrix.shape, dtype=adj_matrix.dtype)
+
+        self.contig_users = list(range(len(users)))
+        self.contig_items = set(range(len(users), len(users) + len(items)))
+        self.batch_size = batch_size
+        self.seed = seed
+        self.random_state = np.random.RandomState(seed)
+
+        # per user: its items in key order (a stable sort by user of row-major keys keeps the columns ascending)
+        n_users = len(users)
+
+        def lists(mask):
+            r, c = row[mask], col[mask]
+            keep = r < n_users
+            r, c = r[keep], c[keep]
+            ptr = np.zeros(n_users + 1, dtype=np.int64)
+            np.add.at(ptr, r + 1, 1)
+            ptr = np.cumsum(ptr)
+            return ptr, c.astype(np.int32)
+
+        pos_ptr, pos_ids = lists(pos)
+        neg_ptr, neg_ids = lists(neg)
+
+        def sample_negatives(user, positives):
+            if neg_ptr[user + 1] > neg_ptr[user]:
+                return neg_ids[neg_ptr[user]:neg_ptr[user + 1]]
+            return self.random_state.choice(list(set(self.contig_items) - set(positives)), size=sample_size)
+
+        self.user_item_dict = []
+        for user in self.contig_users:
+            if pos_ptr[user + 1] == pos_ptr[user]:
+                raise ValueError("user {} has no positive rating: every user needs one to be sampled".format(user))
+            positives = pos_ids[pos_ptr[user]:pos_ptr[user + 1]]
+            self.user_item_dict.append((positives, sample_negatives(user, positives)))
+        self.pos_csr = (pos_ptr.astype(np.int32), pos_ids)
+        neg_lists = [np.asarray(n, dtype=np.int32) for _, n in self.user_item_dict]
+        self.neg_csr = (np.concatenate([[0], np.cumsum([len(n) for n in neg_lists])]).astype(np.int32),
+                        np.concatenate(neg_lists).astype(np.int32) if neg_lists else np.zeros(0, np.int32))
+
+    def __len__(self):
+        return int(np.ceil(len(self.ratings) / self.batch_size))
+
+    def __iter__(self):
+        return (self[b] for b in range(len(self)))
+
+    def __getitem__(self, idx):
+        h = self.batch_size // 2
+        batch_users = self.random_state.choice(self.contig_users, size=h)
+        pos_items = np.fromiter((self.random_state.choice(self.user_item_dict[user][0]) for user in batch_users), dtype='int32')
+        neg_items = np.fromiter((self.random_state.choice(self.user_item_dict[user][1]) for user in batch_users), dtype='int32')
+        items = np.concatenate([pos_items, neg_items])
+        users = np.repeat(batch_users, 2)
+        ratings = np.concatenate([np.full(h, 1), np.full(h, 0)])
+        return (users, items), ratings
+
+    def device_batch(self, step):
+        """The batch the device sampler draws at `step` (the batches of fit()), in __getitem__'s layout."""
+        return bpr_device_batch(self.pos_csr, self.neg_csr, len(self.users), self.seed, step, self.batch_size // 2)
+
+
+# ---- the device sampler's draws, restated (csrc/amar_bpr.hip, include/amar_hip.h: amar_bpr_sample_i32) -----------------------
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = np.uint32(0x9E3779B9), np.uint32(0xBB67AE85)
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11) on arrays: counter [n, 4] uint32, key (k0, k1) -> [n, 4] uint32."""
+    c = np.array(counter, dtype=np.uint32).reshape(-1, 4).copy()
+    k0, k1 = np.uint32(key[0]), np.uint32(key[1])
+    mask = np.uint64(0xFFFFFFFF)
+    with np.errstate(over='ignore'):
+        for r in range(10):
+            if r:
+                k0, k1 = k0 + _PHILOX_W0, k1 + _PHILOX_W1
+            p0 = _PHILOX_M0 * c[:, 0].astype(np.uint64)
+            p1 = _PHILOX_M1 * c[:, 2].astype(np.uint64)
+            hi0, lo0 = (p0 >> np.uint64(32)).astype(np.uint32), (p0 & mask).astype(np.uint32)
+            hi1, lo1 = (p1 >> np.uint64(32)).astype(np.uint32), (p1 & mask).astype(np.uint32)
+            c = np.stack([hi1 ^ c[:, 1] ^ k0, lo1, hi0 ^ c[:, 3] ^ k1, lo0], axis=1)
+    return c
+
+
+def _pick(word, n):
+    return ((word.astype(np.uint64) * np.asarray(n, dtype=np.uint64)) >> np.uint64(32)).astype(np.int64)
+
+
+def bpr_device_batch(pos_csr, neg_csr, n_users, seed, step, h):
+    """What amar_bpr_sample_i32 writes for (seed, step): draw j uses Philox4x32-10 with key = (seed_lo, seed_hi) and counter =
+    (j, step_lo, step_hi, 0); word 0 picks the user among n_users, word 1 its positive, word 2 its negative candidate, each as
+    (uint64(word) * n) >> 32.  Returns ((users[2h], items[2h]), ratings[2h]) in the reference's layout (int64 ids, int64 labels)."""
+    seed, step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF
+    j = np.arange(h, dtype=np.uint64)
+    counter = np.stack([j, np.full(h, step & 0xFFFFFFFF, np.uint64), np.full(h, step >> 32, np.uint64), np.zeros(h, np.uint64)], axis=1)
+    w = philox4x32_10(counter.astype(np.uint32), (seed & 0xFFFFFFFF, seed >> 32))
+    users = _pick(w[:, 0], n_users)
+    (pp, pi), (npt, ni) = pos_csr, neg_csr
+    pp, npt = np.asarray(pp, np.int64), np.asarray(npt, np.int64)
+    pos = np.asarray(pi)[pp[users] + _pick(w[:, 1], pp[users + 1] - pp[users])].astype(np.int64)
+    neg = np.asarray(ni)[npt[users] + _pick(w[:, 2], npt[users + 1] - npt[users])].astype(np.int64)
+    return (np.repeat(users, 2), np.concatenate([pos, neg])), np.concatenate([np.ones(h, np.int64), np.zeros(h, np.int64)])

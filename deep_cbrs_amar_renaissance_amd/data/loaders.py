@@ -14,7 +14,7 @@ import pandas as pd
 
 from deep_cbrs_amar_renaissance_amd.data import jsonstream
 from deep_cbrs_amar_renaissance_amd.data.datasets import UserItemEmbeddings, HybridUserItemEmbeddings
-from deep_cbrs_amar_renaissance_amd.data.datasets import UserItemGraph, UserItemGraphEmbeddings
+from deep_cbrs_amar_renaissance_amd.data.datasets import UserItemGraph, UserItemGraphEmbeddings, UserItemGraphPosNegSample
 from deep_cbrs_amar_renaissance_amd.data.preprocess import build_adjacency_matrix, get_user_properties
 
 
@@ -170,6 +170,10 @@ def load_hybrid_embeddings(
 
 def _graph_ratings(train_ratings_filepath, test_ratings_filepath, props_triples_filepath, sep, type_adjacency,
                    sparse_adjacency, symmetric_adjacency, user_properties):
+    if type_adjacency == 'binary':
+        # stored zero-valued edges would change GAT / GraphSAGE neighbourhoods, and nothing pins how the reference's layers treat
+        # them: only the BPR sample loader takes this adjacency
+        raise NotImplementedError("type_adjacency 'binary' feeds the BPR sampler only (load_user_item_graph_sample)")
     ratings, (users, items), adj_matrix = load_train_test_ratings(
         train_ratings_filepath, test_ratings_filepath, props_triples_filepath,
         sep=sep, return_adjacency=True, type_adjacency=type_adjacency,
@@ -204,8 +208,26 @@ def load_user_item_graph(
     return data_train, data_test
 
 
-def load_user_item_graph_sample(*args, **kwargs):
-    raise NotImplementedError("BPR positive/negative sampling is out of scope (SURVEY.md §2 row 9)")
+def load_user_item_graph_sample(
+        train_ratings_filepath,
+        test_ratings_filepath,
+        props_triples_filepath=None,
+        sep='\t',
+        type_adjacency='binary',
+        sparse_adjacency=True,
+        symmetric_adjacency=True,
+        train_batch_size=1024,
+        test_batch_size=2048
+):
+    """BPR training (loaders.py:334-380): a sampling Sequence for training and an ordinary UserItemGraph for test, both built on
+    the same adjacency object (the sampler keeps its positives as the graph the model propagates over)."""
+    (train_ratings, test_ratings), (users, items), adj_matrix = load_train_test_ratings(
+        train_ratings_filepath, test_ratings_filepath, props_triples_filepath,
+        sep=sep, return_adjacency=True, type_adjacency=type_adjacency,
+        sparse_adjacency=sparse_adjacency, symmetric_adjacency=symmetric_adjacency)
+    data_train = UserItemGraphPosNegSample(train_ratings, users, items, adj_matrix, batch_size=train_batch_size)
+    data_test = UserItemGraph(test_ratings, users, items, adj_matrix, batch_size=test_batch_size, shuffle=False)
+    return data_train, data_test
 
 
 def load_user_item_graph_bert_embeddings(

@@ -5,7 +5,8 @@ Mirrors `/root/reference/src/data/preprocess.py:9-170`: ``'unary'`` (user-item g
 TwoStep / TwoWay stacks), ``get_user_properties`` (the two-hop user-property graph) and the offline
 ``process_item_properties_graph`` filter that produces the property files.  Output is a scipy COO with the
 same triplets, in the same order, as the reference builds — including duplicate (item, property) links and the
-un-deduplicated symmetric copy.  ``'binary'`` only feeds the BPR sampler, which is out of scope, and raises.
+un-deduplicated symmetric copy.  ``'binary'`` (every train rating with its 0/1 value, explicit zeros kept) feeds the BPR sampler
+(``datasets.UserItemGraphPosNegSample``); the other loaders refuse it.
 """
 import numpy as np
 from scipy import sparse
@@ -53,19 +54,21 @@ def build_adjacency_matrix(
     :param items: original item identifiers (only the count is used).
     :param props_triples: [L, 3] array (item index, property index + |I|, 1) or None.
     :param props: original property identifiers or None.
-    :param type_adjacency: 'unary', 'unary-uip' or 'unary-kg'.
+    :param type_adjacency: 'unary', 'unary-uip', 'unary-kg' or 'binary' (0/1 ratings, for the BPR sampler).
     :param sparse_adjacency: must be True (the HIP path consumes CSR).
     :param symmetric_adjacency: append the transposed triplets.
     :return: scipy COO float32 adjacency; for 'unary-kg' the pair (user-item [|U|+|I|]^2, item-property [|I|+|P|]^2).
     """
-    if type_adjacency == 'binary':
-        raise NotImplementedError("type_adjacency 'binary' only feeds the BPR sampler, which is out of scope")
-    if type_adjacency not in ('unary', 'unary-uip', 'unary-kg'):
+    if type_adjacency not in ('unary', 'unary-uip', 'unary-kg', 'binary'):
         raise ValueError("Unknown adjacency matrix type named {}".format(type_adjacency))
     if not sparse_adjacency:
         raise NotImplementedError("dense adjacency matrices are not supported by the HIP path")
 
     n_ui = len(users) + len(items)
+    if type_adjacency == 'binary':
+        # preprocess.py:88-110: every rating with its value, zeros stored explicitly
+        adj = sparse.coo_matrix((bi_ratings[:, 2], (bi_ratings[:, 0], bi_ratings[:, 1])), shape=[n_ui, n_ui], dtype=np.float32)
+        return symmetrize_matrix(adj) if symmetric_adjacency else adj
     liked = bi_ratings[:, 2] == 1
     rows, cols, data = bi_ratings[liked, 0], bi_ratings[liked, 1], bi_ratings[liked, 2]
     size = n_ui

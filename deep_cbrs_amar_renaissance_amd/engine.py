@@ -367,14 +367,26 @@ class Model(Layer):
                 prm.copy_(torch.from_numpy(np.ascontiguousarray(value, dtype=np.float32)).to(prm.device))
 
     def evaluate(self, sequence, **kwargs):
-        """Loss and accuracy on `sequence` (experiment.py:194).  As Keras' evaluate(), 'loss' is the binary cross-entropy plus
+        """Loss and accuracy on `sequence` (experiment.py:194).  As Keras' evaluate(), 'loss' is the compiled loss (binary cross-entropy,
+        or BPRLoss per batch) plus
         the regularisation losses of the model (l2 * sum(w^2) for every weight carrying a regulariser: gnn.py:45,293-294),
         the same sum fit() reports per epoch, so train and test losses of one run are comparable."""
         pred = self.predict(sequence).reshape(-1).astype(np.float64)
-        y = np.concatenate([np.asarray(sequence[b][1]).reshape(-1) for b in range(len(sequence))]).astype(np.float64)
-        eps = 1e-7                                                   # keras backend epsilon
-        p = np.clip(pred, eps, 1 - eps)
-        loss = float(-np.mean(y * np.log(p) + (1 - y) * np.log(1 - p))) if len(y) else 0.0
+        labels = [np.asarray(sequence[b][1]).reshape(-1) for b in range(len(sequence))]
+        y = np.concatenate(labels).astype(np.float64) if labels else np.zeros(0)
+        from deep_cbrs_amar_renaissance_amd.utilities.losses import BPRLoss, loss_kind
+        if loss_kind(getattr(self, 'loss', None)) == 'bpr':
+            # BPRLoss (utilities/losses.py) on each batch's own two halves, averaged over the batches weighted by their size (Keras'
+            # Mean loss tracker)
+            bpr, total, lo = BPRLoss(), 0.0, 0
+            for lab in labels:
+                total += bpr(None, pred[lo:lo + len(lab)]) * len(lab)
+                lo += len(lab)
+            loss = total / len(y) if len(y) else 0.0
+        else:
+            eps = 1e-7                                               # keras backend epsilon
+            p = np.clip(pred, eps, 1 - eps)
+            loss = float(-np.mean(y * np.log(p) + (1 - y) * np.log(1 - p))) if len(y) else 0.0
         for w in self.parameters():
             reg = getattr(w, 'regularizer', None)
             if reg is not None and getattr(reg, 'l2', 0.0):

@@ -35,6 +35,7 @@ from deep_cbrs_amar_renaissance_amd import engine, models as models_pkg
 from deep_cbrs_amar_renaissance_amd.data import loaders
 from deep_cbrs_amar_renaissance_amd.models.basic import BasicRS, BasicGNN, BasicKnowledgeGCN, BasicTSGNN, BasicTWGNN
 from deep_cbrs_amar_renaissance_amd.models.hybrid import HybridCBRS, HybridBertGNN
+from deep_cbrs_amar_renaissance_amd.utilities import losses
 from deep_cbrs_amar_renaissance_amd.utilities.keras import get_total_parameters
 from deep_cbrs_amar_renaissance_amd.utilities.metrics import full_ranking_metrics, recommendations_frame, top_k_predictions, top_k_metrics
 from deep_cbrs_amar_renaissance_amd.utilities.utils import \
@@ -167,6 +168,8 @@ class Experimenter:
             self.model = cls(**model_cfg)
         if hasattr(self.model, 'n_users'):                   # lets hoisted scoring run each tower on its own rows
             self.model.n_users, self.model.n_items = len(self.trainset.users), len(self.trainset.items)
+        if isinstance(self.parameters.loss, str) and hasattr(losses, self.parameters.loss):    # custom loss (experiment.py:155-157)
+            self.parameters['loss'] = getattr(losses, self.parameters.loss)()
         self.model.compile(loss=self.parameters.loss, optimizer=self.optimizer, metrics=self.parameters.metrics)
         self.model(self.trainset[0][0])                       # one prediction builds every weight
         self.model.summary(print_fn=self.logger.info, expand_nested=True)

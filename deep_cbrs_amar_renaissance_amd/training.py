@@ -22,6 +22,7 @@ Dense tapes; its BERT inputs are constants.  GAT (1 head) trains on the inferenc
 forms the softmax / attention-scalar gradients row-wise for both edge directions (symmetric edge multiset, no float
 atomics).
 """
+import itertools
 import os
 import types
 
@@ -35,6 +36,7 @@ from deep_cbrs_amar_renaissance_amd.layers.gat_conv import GATConv
 from deep_cbrs_amar_renaissance_amd.layers.gcn_conv import GCNConv
 from deep_cbrs_amar_renaissance_amd.layers.graphsage_conv import GraphSageConv
 from deep_cbrs_amar_renaissance_amd.layers.lightgcn_conv import LightGCNConv
+from deep_cbrs_amar_renaissance_amd.utilities.losses import loss_kind
 from deep_cbrs_amar_renaissance_amd.utilities.math import spmm_kind
 
 
@@ -594,6 +596,40 @@ def _require_symmetric(a):
                                   "pass multiplies by A where A^T is due")
 
 
+class DeviceSampler:
+    """The positive / negative lists of a UserItemGraphPosNegSample on the device, and the step counter of its draws
+    (amar_bpr_sample_i32).  Uploaded once per Sequence; a captured training graph keeps this object (and so its buffers) alive, and
+    `serial` (never reused) is part of the graph's key, so a graph never replays against another Sequence's lists."""
+
+    _serials = itertools.count()
+
+    def __init__(self, sequence, device):
+        (pp, pi), (npt, ni) = sequence.pos_csr, sequence.neg_csr
+        n_users, n_nodes = len(sequence.users), sequence.adj_matrix.shape[0]
+        for ptr, ids, what in ((pp, pi, 'positive'), (npt, ni, 'negative-candidate')):
+            ptr, ids = np.asarray(ptr), np.asarray(ids)
+            # the kernel reads without bounds checks: every user row non-empty, every id a node of the graph
+            if len(ptr) != n_users + 1 or ptr[0] != 0 or ptr[-1] != len(ids) or np.any(np.diff(ptr) < 1):
+                raise ValueError("every user needs a non-empty {} list".format(what))
+            if len(ids) and (ids.min() < 0 or ids.max() >= n_nodes):
+                raise ValueError("{} list holds ids outside the graph".format(what))
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)   # noqa: E731
+        self.pos_ptr, self.pos_ids, self.neg_ptr, self.neg_ids = up(pp), up(pi), up(npt), up(ni)
+        self.n_users, self.seed, self.h = n_users, int(sequence.seed), int(sequence.batch_size) // 2
+        if self.h < 1:
+            raise ValueError("a BPR batch needs batch_size >= 2")
+        self.step = torch.zeros(1, dtype=torch.int64, device=device)
+        self.serial = next(self._serials)
+        self.sequence, self.arrays = sequence, (pp, pi, npt, ni)
+
+    def matches(self, sequence):
+        return self.sequence is sequence and all(a is b for a, b in zip(self.arrays, (*sequence.pos_csr, *sequence.neg_csr)))
+
+    def sample(self, u, i, y):
+        """One batch into u [2h], i [2h], y [2h]; advances the step counter on the device."""
+        capi.bpr_sample(self.pos_ptr, self.pos_ids, self.neg_ptr, self.neg_ids, self.n_users, self.seed, self.step, u, i, y)
+
+
 class Trainer:
     """Holds the Adam state of a Basic* / HybridBert* model (single-graph, TwoStep or TwoWay stacks) and performs training batches."""
 
@@ -634,6 +670,17 @@ class Trainer:
         reg = getattr(param, 'regularizer', None)
         return float(reg.l2) if reg is not None else 0.0
 
+    def _loss_kind(self):
+        """The compiled loss (Model.compile): 'bce' (binary cross-entropy, the default) or 'bpr' (utilities/losses.py:BPRLoss)."""
+        return loss_kind(getattr(self.model, 'loss', None))
+
+    def _loss_grad(self, p, yv, dz, terms):
+        """Per-pair loss terms (their sum = B x the batch's loss) and d(loss)/d(logit) of the compiled loss."""
+        if self._loss_kind() == 'bpr':
+            capi.bpr_grad(p, dz, terms)
+        else:
+            capi.bce_grad(p, yv, dz, terms)
+
     # -- one batch ------------------------------------------------------------------------------------------------
     def _bert_rows(self, ids, block):
         if block is not None:
@@ -665,7 +712,7 @@ class Trainer:
         # ---- loss and its gradient through the final sigmoid
         dz = torch.empty((b, 1), dtype=torch.float32, device=dev)
         terms = torch.empty(b, dtype=torch.float32, device=dev)
-        capi.bce_grad(p, yv, dz, terms)
+        self._loss_grad(p, yv, dz, terms)
         grads = {}
         de = torch.zeros((e.shape[0], f), dtype=torch.float32, device=dev)
         both = None
@@ -698,7 +745,7 @@ class Trainer:
         return loss, grads
 
     # -- one batch as a hipGraph ------------------------------------------------------------------------------------
-    def _graph_body(self):
+    def _graph_body(self, upload_slots=False):
         g = self._g
         tapes = self._all_tapes()
         for t in tapes:                                              # weight-gradient partials stay partial: the Adam launch below adds them
@@ -719,6 +766,8 @@ class Trainer:
         g['keep'] = entries                                          # buffer allocated BEFORE it (memory of the capture's own pool is reused
         #                                                              by the graph's temporaries): the table never changes — the slots point
         #                                                              into tensors of the graph
+        if upload_slots:                                             # (the same body run eagerly: this step's own table, before its Adam launch)
+            g['slot_dev'][:g['slot_bytes']].copy_(g['slot_host'][:g['slot_bytes']])
         batch = float(g['u'].numel())
         capi.sum_into(terms, self._loss_sum)                         # sum of the per-pair terms = data loss x batch size
         capi.adam_multi(g['slot_dev'], len(entries), blocks, self._adam_state, self.b1, self.b2, self.eps,
@@ -732,11 +781,8 @@ class Trainer:
         b = len(y)
         dev = self.device
         with_blocks = bert is not None and bert[0] is not None
-        key = (b, with_blocks)
-        if not hasattr(self, '_graphs'):
-            self._graphs, self._seen, self._eager_loss, self._dev_t = {}, set(), 0.0, None
-            self._adam_state = torch.zeros(2, dtype=torch.float32, device=dev)
-            self._loss_sum = torch.zeros((), dtype=torch.float32, device=dev)
+        key = (b, with_blocks, self._loss_kind())                   # (a compile() with another loss captures anew)
+        self._init_graph_state()
         g = self._graphs.get(key)
         if g is None:
             if key not in self._seen:                               # first batch of this shape: eager (real) step
@@ -796,6 +842,84 @@ class Trainer:
         if self._dev_t != self.t:                                    # eager steps happened in between: resynchronise the counter
             self._adam_state[0] = float(self.t)
         g['graph'].replay()
+        self.t += 1
+        self._dev_t = self.t
+
+    def _init_graph_state(self):
+        if not hasattr(self, '_graphs'):
+            dev = self.device
+            self._graphs, self._seen, self._eager_loss, self._dev_t = {}, set(), 0.0, None
+            self._eager_sampled = {}
+            self._adam_state = torch.zeros(2, dtype=torch.float32, device=dev)
+            self._loss_sum = torch.zeros((), dtype=torch.float32, device=dev)
+
+    # -- batches drawn on the device (BPR: data/datasets.py:UserItemGraphPosNegSample) -------------------------------------------
+    def sampler_for(self, sequence):
+        """The DeviceSampler of `sequence`, uploaded once.  Another Sequence (or new lists) gets a new one, and the graphs captured
+        for the old one are dropped with it."""
+        sampler = getattr(self, '_sampler', None)
+        if sampler is None or not sampler.matches(sequence):
+            if hasattr(self, '_graphs'):
+                self._graphs = {k: v for k, v in self._graphs.items() if k[0] != 'sampled'}
+                self._seen = {k for k in self._seen if k[0] != 'sampled'}
+                self._eager_sampled = {}
+            sampler = self._sampler = DeviceSampler(sequence, self.device)
+        return sampler
+
+    def train_sampled(self, sampler, graph=True):
+        """One training batch whose ids the device sampler draws (nothing is uploaded per batch).  The step is the body of a
+        replayed batch — sample, forward, loss, reverse pass, one Adam launch, the loss kept on the device — either replayed from a
+        hipGraph (graph=True: captured at the second batch, the first runs the same body eagerly) or run eagerly every time; both give
+        the same weights and the same loss bit for bit.  The draws follow the sampler's device step counter."""
+        if self.hybrid:
+            raise NotImplementedError("the BPR sample Sequence carries no BERT rows: hybrid models do not train on it")
+        b = 2 * sampler.h
+        key = ('sampled', b, self._loss_kind(), sampler.serial)
+        self._init_graph_state()
+        g = self._graphs.get(key)
+        if g is None:
+            g = self._eager_sampled.get(key) if key in self._eager_sampled else self._sampled_buffers(sampler, b)
+            self._g = g
+            if graph and key in self._seen:
+                from deep_cbrs_amar_renaissance_amd.engine import capture_graph
+
+                def body():
+                    with torch.no_grad():
+                        sampler.sample(g['u'], g['i'], g['y'])
+                        self._graph_body()
+                self._sync_step()
+                g['graph'], _ = capture_graph(body)
+                g['slot_dev'][:g['slot_bytes']].copy_(g['slot_host'][:g['slot_bytes']])
+                self._graphs[key] = g
+            else:
+                self._seen.add(key)
+                self._eager_sampled = {key: g}                       # (buffers of the eager steps, kept for the next one)
+                self._sync_step()
+                with torch.no_grad():
+                    sampler.sample(g['u'], g['i'], g['y'])
+                    self._graph_body(upload_slots=True)
+                self._advanced()
+                return
+        self._g = g
+        self._sync_step()
+        g['graph'].replay()
+        self._advanced()
+
+    def _sampled_buffers(self, sampler, b):
+        dev = self.device
+        uiy = torch.zeros(3 * b, dtype=torch.int32, device=dev)
+        ui = uiy[:2 * b]
+        g = self._g = {'uiy': uiy, 'ui': ui, 'u': ui[:b], 'i': ui[b:], 'y': uiy[2 * b:].view(torch.float32), 'ub': None, 'ib': None,
+                       'sampler': sampler}
+        g['slot_host'] = torch.empty(64 * len(self.params) + 64, dtype=torch.uint8).pin_memory()
+        g['slot_dev'] = torch.empty(64 * len(self.params) + 64, dtype=torch.uint8, device=dev)
+        return g
+
+    def _sync_step(self):
+        if self._dev_t != self.t:                                    # host steps happened in between: resynchronise the counter
+            self._adam_state[0] = float(self.t)
+
+    def _advanced(self):
         self.t += 1
         self._dev_t = self.t
 
@@ -927,7 +1051,7 @@ class HeadTrainer(Trainer):
         p = self.head.forward(r[0], r[1], (r[2], r[3]) if self.hybrid else None)
         dz = torch.empty((b, 1), dtype=torch.float32, device=p.device)
         terms = torch.empty(b, dtype=torch.float32, device=p.device)
-        capi.bce_grad(p, yv, dz, terms)
+        self._loss_grad(p, yv, dz, terms)
         grads = {}
         self.head.backward(dz, grads, need_input_grad=False)
         return terms, grads
@@ -941,7 +1065,7 @@ class HeadTrainer(Trainer):
             p = self.head.forward(rows[0], rows[1], (rows[2], rows[3]) if self.hybrid else None)
             dz = torch.empty((b, 1), dtype=torch.float32, device=p.device)
             terms = torch.empty(b, dtype=torch.float32, device=p.device)
-            capi.bce_grad(p, yv, dz, terms)
+            self._loss_grad(p, yv, dz, terms)
             grads = {}
             self.head.backward(dz, grads, need_input_grad=False)
             loss = float(terms.sum().item()) / b
@@ -1024,6 +1148,9 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
     # batch's users and items — gathered on the host from ONE table indexed by node id and uploaded every batch (6 MB at batch 1 024).
     # That table is registered once on the device instead and the batches are read as ids only: the same rows, gathered there
     # (AMAR_RESIDENT_BERT=0: the batches as they come).  A replayed hybrid batch at ml1m(s=1): 0.41 against 0.71 ms.
+    from deep_cbrs_amar_renaissance_amd.data.datasets import UserItemGraphPosNegSample
+    if isinstance(sequence, UserItemGraphPosNegSample):
+        return _fit_sampled(model, sequence, epochs, verbose, hp)
     ids_only = model.resident_ids(sequence) if hasattr(model, 'resident_ids') else None
     trainer = getattr(model, '_trainer', None)
     if trainer is None:
@@ -1053,4 +1180,27 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
             print("Epoch {}/{} - loss: {:.4f}".format(epoch + 1, epochs, history[-1]))
         if hasattr(sequence, 'on_epoch_end'):
             sequence.on_epoch_end()
+    return {'loss': history}
+
+
+def _fit_sampled(model, sequence, epochs, verbose, hp):
+    """fit() on the BPR sample Sequence: its lists go to the device once and every batch is drawn there (amar_bpr_sample_i32), inside
+    the replayed training graph (AMAR_TRAIN_GRAPH=0: the same steps eagerly, the same ids).  len(sequence) steps per epoch; the host
+    stream of __getitem__ is not read."""
+    trainer = getattr(model, '_trainer', None)
+    if trainer is None:
+        trainer = model._trainer = Trainer(model, **hp)
+    sampler = trainer.sampler_for(sequence)
+    use_graph = os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
+    history = []
+    for epoch in range(int(epochs)):
+        count = 0
+        for _ in range(len(sequence)):
+            trainer.train_sampled(sampler, graph=use_graph)
+            count += 2 * sampler.h
+        total = trainer.pop_loss_sum()
+        trainer.touch_parameters()
+        history.append(total / max(count, 1))
+        if verbose:
+            print("Epoch {}/{} - loss: {:.4f}".format(epoch + 1, epochs, history[-1]))
     return {'loss': history}

@@ -544,6 +544,26 @@ int amar_sum_into_f32(const float *x, int64_t n, float scale, float *acc, amar_s
 int amar_adam_dev_f32(float *w, const float *g, float *m, float *v, int64_t n, const float *state, float beta_1, float beta_2,
                       float epsilon, float l2, amar_stream_t stream);
 
+/* ---- BPR training (utilities/losses.py:BPRLoss, data/datasets.py:UserItemGraphPosNegSample) ----------------------------------
+ * amar_bpr_grad_f32    the pairwise loss of src/utilities/losses.py:15-25 on the probability column p ([B], or a strided [B, 1] with
+ *                      leading dimension ldp): h = B / 2 (an odd B drops its last element), s_j = sigmoid(p[j] - p[h + j]),
+ *                      loss = -mean_{j<h} log s_j.  loss_terms[j] = (B / h) * (-log s_j), every other term 0 (so sum = B * loss, as
+ *                      amar_bce_grad_f32's terms); dz = d(loss)/d(logit) through the final sigmoid: dz[j] = -(1 - s_j) p_j (1 - p_j) / h,
+ *                      dz[h + j] = (1 - s_j) p_{h+j} (1 - p_{h+j}) / h, 0 for the dropped element.  B = 1: zero loss and gradient.
+ *                      One lane per pair, no atomics: reproducible bit for bit.  dz and loss_terms are contiguous [B].
+ * amar_bpr_sample_i32  one BPR batch of h draws into u[2h], items[2h] and (y != NULL) y[2h] = [1]*h + [0]*h, the layout of the
+ *                      reference's __getitem__ (datasets.py:286-306): u[2j] = u[2j+1] = user_j, items[j] = pos_j, items[h+j] = neg_j.
+ *                      Draw j: Philox4x32-10 with key = (seed & 0xffffffff, seed >> 32) and counter = (j, s & 0xffffffff, s >> 32, 0),
+ *                      s = *step read from DEVICE memory; word 0 -> user_j = (uint64(w0) * n_users) >> 32, word 1 -> pos_j =
+ *                      pos_ids[pos_ptr[user_j] + ((uint64(w1) * n_pos) >> 32)], word 2 -> neg_j likewise from the negative-candidate CSR.
+ *                      advance != 0: *step = s + 1 after the batch (a replayed graph draws new ids every step).  CSR row pointers
+ *                      [n_users + 1] and int32 node ids; every user row of both lists must be non-empty (the caller checks: the
+ *                      kernel reads without bounds checks).  One workgroup of 256 lanes. */
+int amar_bpr_grad_f32(const float *p, int64_t ldp, float *dz, float *loss_terms, int64_t B, amar_stream_t stream);
+int amar_bpr_sample_i32(const int32_t *pos_ptr, const int32_t *pos_ids, const int32_t *neg_ptr, const int32_t *neg_ids,
+                        int32_t n_users, uint64_t seed, uint64_t *step, int32_t advance, int32_t h,
+                        int32_t *u, int32_t *items, float *y, amar_stream_t stream);
+
 /* ---- ranking ------------------------------------------------------------------------------
  * Per-user top-k over that user's own test pairs (src/utilities/metrics.py:11-34):
  * pairs are grouped by user (seg_ptr[n_users+1] into item_ids/scores); for each user the k
