@@ -92,6 +92,12 @@ SIGNATURES = {
     'amar_adam_dev_f32': (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _F32, _F32, _F32, _F32, _P]),
     'amar_bpr_grad_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P]),
     'amar_bpr_sample_i32': (ctypes.c_int, [_P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _I32, _I32, _P, _P, _P, _P]),
+    'amar_dropout_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I32, ctypes.c_uint64, _P, _U32, _U32, _F32, _P]),
+    'amar_dropout_advance': (ctypes.c_int, [_P, _P]),
+    'amar_gat_layer_dropout_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32,
+                                                  ctypes.c_uint64, _P, _U32, _U32, _F32, _P]),
+    'amar_gat_bwd_dropout_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64,
+                                                _I32, _I32, ctypes.c_uint64, _P, _U32, _U32, _F32, _P]),
     'amar_adam_multi_f32': (ctypes.c_int, [_P, _I32, _I64, _P, _F32, _F32, _F32, _F32, _P, _P]),
     'amar_sum_into_f32': (ctypes.c_int, [_P, _I64, _F32, _P, _P]),
     'amar_topk_segmented_f32': (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
@@ -1146,6 +1152,102 @@ def bpr_sample(pos_ptr, pos_ids, neg_ptr, neg_ids, n_users, seed, step, u, items
                                       int(seed) & 0xFFFFFFFFFFFFFFFF, step.data_ptr() if step.is_cuda else _ptr(step), int(bool(advance)), h,
                                       _ptr(u, torch.int32, 'u'), _ptr(items, torch.int32, 'items'), _ptr(y, torch.float32, 'y'), _stream())
     _check(code, 'amar_bpr_sample_i32')
+
+
+class Dropout:
+    """The arguments of one dropout site as the library takes them: the 64-bit key, the step counter (one int64 on the device,
+    read by the kernels, advanced by `dropout_advance`), the site (1..255) and the rate as (threshold, scale): a 32-bit word
+    keeps its value iff word >= threshold = min(2^32 - 1, floor(rate * 2^32 + 0.5)), kept values are multiplied by
+    scale = float32(1 / (1 - rate)).  data/datasets.py:dropout_node_mask / dropout_edge_mask restate the bits."""
+
+    __slots__ = ('seed', 'step', 'site', 'rate', 'threshold', 'scale')
+
+    def __init__(self, seed, step, site, rate):
+        rate = check_dropout_rate(rate, 'rate')
+        if step.numel() != 1 or step.dtype != torch.int64:
+            raise ValueError("Dropout: step must be one int64 on the device")
+        if not 1 <= int(site) <= 255:
+            raise ValueError("Dropout: site must lie in 1..255")
+        self.seed, self.step, self.site, self.rate = int(seed) & 0xFFFFFFFFFFFFFFFF, step, int(site), rate
+        self.threshold, self.scale = dropout_threshold(rate), dropout_scale(rate)
+
+    def at(self, site):
+        return Dropout(self.seed, self.step, site, self.rate)
+
+    def _args(self):
+        return (self.seed, _ptr(self.step, torch.int64, 'step'), self.site, self.threshold, self.scale)
+
+
+def check_dropout_rate(rate, name='dropout'):
+    """None, 0 and 0.0 -> 0.0 (no dropout); a rate outside [0, 1) raises ValueError."""
+    if rate is None:
+        return 0.0
+    if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 <= float(rate) < 1.0:
+        raise ValueError("{} must be a number in [0, 1) or None (got {!r})".format(name, rate))
+    return float(rate)
+
+
+def dropout_threshold(rate):
+    return min(0xFFFFFFFF, int(float(rate) * 4294967296.0 + 0.5))
+
+
+def dropout_scale(rate):
+    return ctypes.c_float(1.0 / (1.0 - float(rate))).value         # the float32 nearest to 1 / (1 - rate)
+
+
+def dropout(X, drop, out=None):
+    """out = X * keep * scale on a 2-D slice (out None: in place); the same call on a gradient slice is the reverse pass."""
+    Y = X if out is None else out
+    if X.dim() != 2 or tuple(Y.shape) != tuple(X.shape):
+        raise ValueError("dropout: X and out [n, C] expected")
+    n, C = X.shape
+    code = load().amar_dropout_f32(_ptr(X, torch.float32, 'X'), _ld(X, 'X'), _ptr(Y, torch.float32, 'out'), _ld(Y, 'out'), n, C,
+                                   *drop._args(), _stream())
+    _check(code, 'amar_dropout_f32')
+    return Y
+
+
+def dropout_advance(step):
+    """step += 1 on the device: once per training step, after the last kernel that reads it."""
+    if step.numel() != 1 or step.dtype != torch.int64:
+        raise ValueError("dropout_advance: one int64 on the device expected")
+    _check(load().amar_dropout_advance(_ptr(step, torch.int64, 'step'), _stream()), 'amar_dropout_advance')
+
+
+def gat_layer_dropout(rowptr, colidx, H, s_self, s_neigh, bias, Y, drop, self_loop=True):
+    """gat_layer with the attention coefficients dropped after the softmax (training); symmetric edge multiset, sorted columns."""
+    n_rows = rowptr.numel() - 1
+    C = H.shape[1]
+    if tuple(Y.shape) != (n_rows, C) or bias.numel() != C or s_self.numel() < n_rows or s_neigh.numel() < H.shape[0]:
+        raise ValueError("gat_layer_dropout: bias [C], Y [n_rows, C], s_self/s_neigh [n] expected")
+    code = load().amar_gat_layer_dropout_f32(
+        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'),
+        _ptr(H, torch.float32, 'H'), _ld(H, 'H'), C, _ptr(s_self, torch.float32, 's_self'),
+        _ptr(s_neigh, torch.float32, 's_neigh'), _ptr(bias, torch.float32, 'bias'),
+        _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'), 1 if self_loop else 0, n_rows, *drop._args(), _stream())
+    _check(code, 'amar_gat_layer_dropout_f32')
+
+
+def gat_bwd_dropout(rowptr, colidx, H, s_self, s_neigh, Y, dY, bias, a_self, a_neigh, drop, self_loop=True):
+    """Reverse of gat_layer_dropout with the regenerated bits. Returns (dout [n, C], ds [n], dt [n], dH [n, C])."""
+    n = rowptr.numel() - 1
+    C = H.shape[1]
+    if tuple(Y.shape) != (n, C) or tuple(dY.shape) != (n, C) or H.shape[0] != n or bias.numel() != C or \
+            a_self.numel() != C or a_neigh.numel() != C:
+        raise ValueError("gat_bwd_dropout: H, Y, dY [n, C]; bias, a_self, a_neigh [C] expected")
+    dev = H.device
+    dout = torch.empty((n, C), dtype=torch.float32, device=dev)
+    scratch = torch.empty(3 * n, dtype=torch.float32, device=dev)
+    ds, dt = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+    dH = torch.empty((n, C), dtype=torch.float32, device=dev)
+    code = load().amar_gat_bwd_dropout_f32(
+        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), _ptr(H, torch.float32, 'H'), _ld(H, 'H'), C,
+        _ptr(s_self, torch.float32, 's_self'), _ptr(s_neigh, torch.float32, 's_neigh'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
+        _ptr(dY, torch.float32, 'dY'), _ld(dY, 'dY'), _ptr(bias, torch.float32, 'bias'), _ptr(a_self, torch.float32, 'a_self'),
+        _ptr(a_neigh, torch.float32, 'a_neigh'), _ptr(dout), _ptr(scratch), _ptr(ds), _ptr(dt), _ptr(dH), C,
+        1 if self_loop else 0, n, *drop._args(), _stream())
+    _check(code, 'amar_gat_bwd_dropout_f32')
+    return dout, ds, dt, dH
 
 
 def scatter_add_rows(src, ids, dst, base=0):

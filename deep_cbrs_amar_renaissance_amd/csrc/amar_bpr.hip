@@ -6,6 +6,7 @@
 // RNG (Philox4x32-10): the draws depend on (seed, step, j) only, so data/datasets.py:bpr_device_batch restates every id, and a step
 // index read from device memory lets a captured training graph draw new ids on every replay.
 #include "amar_common.h"
+#include "amar_philox.h"
 
 namespace {
 
@@ -28,17 +29,6 @@ __global__ __launch_bounds__(256) void bpr_grad_kernel(const float *__restrict__
     if (blockIdx.x == 0 && threadIdx.x == 0 && 2 * h < B) {
         dz[B - 1] = 0.f;
         terms[B - 1] = 0.f;
-    }
-}
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
     }
 }
 

@@ -12,6 +12,7 @@
 //
 // Reference semantics: see include/amar_hip.h (each entry point cites the reference file:line).
 #include "amar_common.h"
+#include "amar_philox.h"
 #include <stdlib.h>
 
 namespace {
@@ -1254,11 +1255,14 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * AMAR_WAVE) void sage_row_kernel(c
 struct GatArgs {
     const int32_t *rowptr; const int32_t *colidx; const float *H; int64_t ldh;
     const float *s_self; const float *s_neigh; const float *bias; float *Y; int64_t ldy; int self_loop; int n_rows;
+    AmarDropout drop;                            // read by the DROP instantiations only (amar_gat_layer_dropout_f32)
 };
 
 __device__ __forceinline__ float leaky02(float x) { return x > 0.f ? x : 0.2f * x; }
 
-template <int C>
+// DROP (training): every entry's softmax weight is multiplied by keep_ij * scale in the weighted sum; the maximum and the denominator
+// are those of the undropped logits (Spektral drops the coefficients AFTER the segment softmax).  One Philox call per entry.
+template <int C, bool DROP = false>
 __global__ __launch_bounds__(WAVES_PER_BLOCK * AMAR_WAVE) void gat_row_kernel(const GatArgs a) {
     constexpr int LPN = C / 4, NS = AMAR_WAVE / LPN;
     const int lane = threadIdx.x & (AMAR_WAVE - 1);
@@ -1277,17 +1281,19 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * AMAR_WAVE) void gat_row_kernel(co
     // pass 2: un-normalised softmax weights and the weighted sum of source rows
     float4 acc = f4_zero();
     float den = 0.f;
+    uint64_t step = 0;
+    if (DROP) step = *a.drop.step;
     for (int p = beg + slot; p < end; p += NS) {
         const int c = a.colidx[p];
         const float w = expf(leaky02(si + a.s_neigh[c]) - emax);
         const float4 h = *reinterpret_cast<const float4 *>(a.H + (int64_t)c * a.ldh + 4 * q);
-        acc = f4_fma(w, h, acc);
+        acc = f4_fma(DROP ? w * dropout_edge_factor(a.drop, step, row, c, edge_ordinal(a.colidx, beg, p, c)) : w, h, acc);
         if (q == 0) den += w;
     }
     if (a.self_loop && slot == 0) {
         const float w = expf(leaky02(si + a.s_neigh[row]) - emax);
         const float4 h = *reinterpret_cast<const float4 *>(a.H + (int64_t)row * a.ldh + 4 * q);
-        acc = f4_fma(w, h, acc);
+        acc = f4_fma(DROP ? w * dropout_edge_factor(a.drop, step, row, row, 255) : w, h, acc);
         if (q == 0) den += w;
     }
     acc = f4_wave_sum_stride<LPN>(acc);
@@ -1711,11 +1717,12 @@ int amar_sage_tail_f32(const float *X, int64_t ldx, const float *AGG, int64_t ld
     return amar_check_launch();
 }
 
-int amar_gat_layer_f32(const int32_t *rowptr, const int32_t *colidx,
-                       const float *H, int64_t ldh, int32_t C,
-                       const float *s_self, const float *s_neigh, const float *bias,
-                       float *Y, int64_t ldy, int32_t self_loop,
-                       int32_t n_rows, amar_stream_t stream) {
+// drop == nullptr: the inference kernels; else the DROP instantiations (training, attention dropout)
+static int gat_layer_launch(const int32_t *rowptr, const int32_t *colidx,
+                            const float *H, int64_t ldh, int32_t C,
+                            const float *s_self, const float *s_neigh, const float *bias,
+                            float *Y, int64_t ldy, int32_t self_loop,
+                            int32_t n_rows, const AmarDropout *drop, amar_stream_t stream) {
     if (n_rows < 0 || !rowptr || !H || !s_self || !s_neigh || !bias || !Y) return AMAR_EINVAL;
     if (!ld_ok(ldh, C) || !ld_ok(ldy, C) || !amar_aligned16(H) || !amar_aligned16(Y) || !amar_aligned16(bias))
         return AMAR_EINVAL;
@@ -1723,18 +1730,30 @@ int amar_gat_layer_f32(const int32_t *rowptr, const int32_t *colidx,
     if (!colidx) return AMAR_EINVAL;
     if (!native_width(C)) {
         // the attention coefficients only depend on the per-node scalars: each column chunk recomputes the same softmax
+        // (and, with dropout, regenerates the same keep bits: they depend on the entry, not on the column)
         if (C < 4 || (C & 3)) return AMAR_EUNSUPPORTED;
         for (int o = 0, w; o < C; o += w) {
             w = chunk_width(C - o);
-            const int rc = amar_gat_layer_f32(rowptr, colidx, H + o, ldh, w, s_self, s_neigh, bias + o, Y + o, ldy, self_loop,
-                                              n_rows, stream);
+            const int rc = gat_layer_launch(rowptr, colidx, H + o, ldh, w, s_self, s_neigh, bias + o, Y + o, ldy, self_loop,
+                                            n_rows, drop, stream);
             if (rc != AMAR_OK) return rc;
         }
         return AMAR_OK;
     }
-    GatArgs a{rowptr, colidx, H, ldh, s_self, s_neigh, bias, Y, ldy, self_loop ? 1 : 0, n_rows};
+    GatArgs a{rowptr, colidx, H, ldh, s_self, s_neigh, bias, Y, ldy, self_loop ? 1 : 0, n_rows, drop ? *drop : AmarDropout{}};
     const dim3 grid((n_rows + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), block(WAVES_PER_BLOCK * AMAR_WAVE);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (drop) {
+        switch (C) {
+        case 4:  hipLaunchKernelGGL((gat_row_kernel<4, true>), grid, block, 0, st, a); break;
+        case 8:  hipLaunchKernelGGL((gat_row_kernel<8, true>), grid, block, 0, st, a); break;
+        case 16: hipLaunchKernelGGL((gat_row_kernel<16, true>), grid, block, 0, st, a); break;
+        case 32: hipLaunchKernelGGL((gat_row_kernel<32, true>), grid, block, 0, st, a); break;
+        case 64: hipLaunchKernelGGL((gat_row_kernel<64, true>), grid, block, 0, st, a); break;
+        default: return AMAR_EUNSUPPORTED;
+        }
+        return amar_check_launch();
+    }
     switch (C) {
     case 4:  hipLaunchKernelGGL(gat_row_kernel<4>, grid, block, 0, st, a); break;
     case 8:  hipLaunchKernelGGL(gat_row_kernel<8>, grid, block, 0, st, a); break;
@@ -1744,6 +1763,26 @@ int amar_gat_layer_f32(const int32_t *rowptr, const int32_t *colidx,
     default: return AMAR_EUNSUPPORTED;
     }
     return amar_check_launch();
+}
+
+int amar_gat_layer_f32(const int32_t *rowptr, const int32_t *colidx,
+                       const float *H, int64_t ldh, int32_t C,
+                       const float *s_self, const float *s_neigh, const float *bias,
+                       float *Y, int64_t ldy, int32_t self_loop,
+                       int32_t n_rows, amar_stream_t stream) {
+    return gat_layer_launch(rowptr, colidx, H, ldh, C, s_self, s_neigh, bias, Y, ldy, self_loop, n_rows, nullptr, stream);
+}
+
+int amar_gat_layer_dropout_f32(const int32_t *rowptr, const int32_t *colidx,
+                               const float *H, int64_t ldh, int32_t C,
+                               const float *s_self, const float *s_neigh, const float *bias,
+                               float *Y, int64_t ldy, int32_t self_loop, int32_t n_rows,
+                               uint64_t seed, const uint64_t *step, uint32_t site, uint32_t threshold, float scale,
+                               amar_stream_t stream) {
+    if (!step || site < 1 || site > 255 || !(scale >= 1.f) || scale > 3.0e38f) return AMAR_EINVAL;
+    if (n_rows > AMAR_DROPOUT_MAX_NODES) return AMAR_EUNSUPPORTED;     // node ids share counter words with the ordinal and the site
+    const AmarDropout d{(uint32_t)seed, (uint32_t)(seed >> 32), step, site, threshold, scale};
+    return gat_layer_launch(rowptr, colidx, H, ldh, C, s_self, s_neigh, bias, Y, ldy, self_loop, n_rows, &d, stream);
 }
 
 int amar_gat_xs_f32(const int32_t *rowptr, const int32_t *colidx, int32_t n_slices,

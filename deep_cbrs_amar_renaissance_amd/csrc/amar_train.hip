@@ -8,6 +8,7 @@
 // falls back to global float atomics (scatter_add_rows_kernel), whose last bits depend on the order of arrival; ids are range-checked
 // on the host (engine.ids_to_device).
 #include "amar_common.h"
+#include "amar_philox.h"
 
 namespace {
 
@@ -249,6 +250,7 @@ struct GatBwdArgs {
     const float *Y; int64_t ldy; const float *dY; int64_t ldd; const float *bias; const float *a_self; const float *a_neigh;
     float *dout; float *row_max; float *row_inv; float *row_c; float *ds; float *dt; float *dH; int64_t lddh;
     int self_loop; int n_rows; int C;
+    AmarDropout drop;                            // read by the DROP instantiations only (amar_gat_bwd_dropout_f32)
 };
 
 __device__ __forceinline__ float leaky02(float x) { return x > 0.f ? x : 0.2f * x; }
@@ -262,7 +264,11 @@ __device__ __forceinline__ float group_sum(float v) {               // over the 
 
 // LPN = lanes per node = C / 4 rounded up to a power of two (the group sums are xor-shuffles); for widths in between
 // (C = 24: 6 of 8 lanes) the surplus lanes carry zeros and store nothing.
-template <int LPN>
+// DROP (attention dropout, forward out_i = sum_j alpha_ij m_ij h_j + b with m_ij = keep_ij * scale regenerated from the entry's
+// identity): d alpha_ij = m_ij (g_i . h_j) feeds the unchanged softmax reverse (c_i = g_i . (out_i - b) still is
+// sum_k alpha_ik d alpha_ik), and dh_j accumulates alpha_ij m_ij g_i.  The source walk sees entry (i, j, o) as entry (j, i, o) of
+// row j: same ordinal (the multiset is symmetric, columns sorted), so the same bit.
+template <int LPN, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_bwd_target_kernel(const GatBwdArgs a) {
     constexpr int NS = AMAR_WAVE / LPN;
     const int C = a.C;
@@ -290,22 +296,28 @@ __global__ __launch_bounds__(256) void gat_bwd_target_kernel(const GatBwdArgs a)
     den = wave_sum_stride<1>(den);
     const float inv = 1.f / (den + 1e-9f);
     float ds = 0.f;
-    auto edge = [&](int j) {
+    uint64_t step = 0;
+    if (DROP) step = *a.drop.step;
+    auto edge = [&](int j, int ordinal) {
         const float pre = si + a.s_neigh[j];
         const float alpha = expf(leaky02(pre) - emax) * inv;
         const float4 h = live ? *reinterpret_cast<const float4 *>(a.H + (int64_t)j * a.ldh + 4 * q) : f4_zero();
-        const float dalpha = group_sum<LPN>(dot4(g, h));
+        float dalpha = group_sum<LPN>(dot4(g, h));
+        if (DROP) dalpha *= dropout_edge_factor(a.drop, step, row, j, ordinal);
         const float dpre = alpha * (dalpha - ci) * (pre > 0.f ? 1.f : 0.2f);
         if (q == 0) ds += dpre;
     };
     // every lane of a slot group takes part in the shuffles: the loop bound is uniform per group
-    for (int p = beg + slot; p < end; p += NS) edge(a.colidx[p]);
-    if (a.self_loop && slot == 0) edge(row);
+    for (int p = beg + slot; p < end; p += NS) {
+        const int j = a.colidx[p];
+        edge(j, DROP ? edge_ordinal(a.colidx, beg, p, j) : 0);
+    }
+    if (a.self_loop && slot == 0) edge(row, 255);
     ds = wave_sum_stride<1>(ds);
     if (lane == 0) { a.ds[row] = ds; a.row_max[row] = emax; a.row_inv[row] = inv; a.row_c[row] = ci; }
 }
 
-template <int LPN>
+template <int LPN, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_bwd_source_kernel(const GatBwdArgs a) {
     constexpr int NS = AMAR_WAVE / LPN;
     const int C = a.C;
@@ -319,17 +331,24 @@ __global__ __launch_bounds__(256) void gat_bwd_source_kernel(const GatBwdArgs a)
     const float4 h = live ? *reinterpret_cast<const float4 *>(a.H + (int64_t)row * a.ldh + 4 * q) : f4_zero();
     float4 acc = f4_zero();
     float dt = 0.f;
-    auto edge = [&](int i) {
+    uint64_t step = 0;
+    if (DROP) step = *a.drop.step;
+    auto edge = [&](int i, int ordinal) {
         const float pre = a.s_self[i] + tj;
         const float alpha = expf(leaky02(pre) - a.row_max[i]) * a.row_inv[i];
         const float4 g = live ? *reinterpret_cast<const float4 *>(a.dout + (int64_t)i * C + 4 * q) : f4_zero();
-        acc = f4_fma(alpha, g, acc);
-        const float dalpha = group_sum<LPN>(dot4(g, h));
+        const float m = DROP ? dropout_edge_factor(a.drop, step, i, row, ordinal) : 1.f;
+        acc = f4_fma(DROP ? alpha * m : alpha, g, acc);
+        float dalpha = group_sum<LPN>(dot4(g, h));
+        if (DROP) dalpha *= m;
         const float dpre = alpha * (dalpha - a.row_c[i]) * (pre > 0.f ? 1.f : 0.2f);
         if (q == 0) dt += dpre;
     };
-    for (int p = beg + slot; p < end; p += NS) edge(a.colidx[p]);
-    if (a.self_loop && slot == 0) edge(row);
+    for (int p = beg + slot; p < end; p += NS) {
+        const int i = a.colidx[p];
+        edge(i, DROP ? edge_ordinal(a.colidx, beg, p, i) : 0);
+    }
+    if (a.self_loop && slot == 0) edge(row, 255);
     acc = f4_wave_sum_stride<LPN>(acc);
     dt = wave_sum_stride<1>(dt);
     if (slot == 0 && live) {
@@ -344,8 +363,13 @@ __global__ __launch_bounds__(256) void gat_bwd_source_kernel(const GatBwdArgs a)
 }
 
 template <int LPN>
-void launch_gat_bwd(const GatBwdArgs &a, hipStream_t st) {
+void launch_gat_bwd(const GatBwdArgs &a, bool drop, hipStream_t st) {
     const dim3 grid((a.n_rows + 3) / 4), block(256);
+    if (drop) {
+        hipLaunchKernelGGL((gat_bwd_target_kernel<LPN, true>), grid, block, 0, st, a);
+        hipLaunchKernelGGL((gat_bwd_source_kernel<LPN, true>), grid, block, 0, st, a);
+        return;
+    }
     hipLaunchKernelGGL(gat_bwd_target_kernel<LPN>, grid, block, 0, st, a);
     hipLaunchKernelGGL(gat_bwd_source_kernel<LPN>, grid, block, 0, st, a);
 }
@@ -1701,11 +1725,11 @@ int amar_l2norm_bwd_f32(const float *dY, int64_t ldd, const float *Nrm, int64_t 
     return amar_check_launch();
 }
 
-int amar_gat_bwd_f32(const int32_t *rowptr, const int32_t *colidx, const float *H, int64_t ldh, int32_t C,
-                     const float *s_self, const float *s_neigh, const float *Y, int64_t ldy, const float *dY, int64_t ldd,
-                     const float *bias, const float *a_self, const float *a_neigh,
-                     float *dout, float *row_scratch, float *ds, float *dt, float *dH, int64_t lddh,
-                     int32_t self_loop, int32_t n_rows, amar_stream_t stream) {
+static int gat_bwd_launch(const int32_t *rowptr, const int32_t *colidx, const float *H, int64_t ldh, int32_t C,
+                          const float *s_self, const float *s_neigh, const float *Y, int64_t ldy, const float *dY, int64_t ldd,
+                          const float *bias, const float *a_self, const float *a_neigh,
+                          float *dout, float *row_scratch, float *ds, float *dt, float *dH, int64_t lddh,
+                          int32_t self_loop, int32_t n_rows, const AmarDropout *drop, amar_stream_t stream) {
     if (n_rows < 0 || !rowptr || !H || !s_self || !s_neigh || !Y || !dY || !bias || !a_self || !a_neigh || !dout ||
         !row_scratch || !ds || !dt || !dH) return AMAR_EINVAL;
     if (ldh < C || ldy < C || ldd < C || lddh < C || (ldh & 3) || (ldy & 3) || (ldd & 3) || (lddh & 3)) return AMAR_EINVAL;
@@ -1714,15 +1738,38 @@ int amar_gat_bwd_f32(const int32_t *rowptr, const int32_t *colidx, const float *
     if (n_rows == 0) return AMAR_OK;
     if (!colidx) return AMAR_EINVAL;
     GatBwdArgs a{rowptr, colidx, H, ldh, s_self, s_neigh, Y, ldy, dY, ldd, bias, a_self, a_neigh, dout,
-                 row_scratch, row_scratch + n_rows, row_scratch + 2 * (int64_t)n_rows, ds, dt, dH, lddh, self_loop ? 1 : 0, n_rows, C};
+                 row_scratch, row_scratch + n_rows, row_scratch + 2 * (int64_t)n_rows, ds, dt, dH, lddh, self_loop ? 1 : 0, n_rows, C,
+                 drop ? *drop : AmarDropout{}};
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (C < 4 || C > 64 || (C & 3)) return AMAR_EUNSUPPORTED;
-    if (C <= 4) launch_gat_bwd<1>(a, st);
-    else if (C <= 8) launch_gat_bwd<2>(a, st);
-    else if (C <= 16) launch_gat_bwd<4>(a, st);
-    else if (C <= 32) launch_gat_bwd<8>(a, st);
-    else launch_gat_bwd<16>(a, st);
+    if (C <= 4) launch_gat_bwd<1>(a, drop != nullptr, st);
+    else if (C <= 8) launch_gat_bwd<2>(a, drop != nullptr, st);
+    else if (C <= 16) launch_gat_bwd<4>(a, drop != nullptr, st);
+    else if (C <= 32) launch_gat_bwd<8>(a, drop != nullptr, st);
+    else launch_gat_bwd<16>(a, drop != nullptr, st);
     return amar_check_launch();
+}
+
+int amar_gat_bwd_f32(const int32_t *rowptr, const int32_t *colidx, const float *H, int64_t ldh, int32_t C,
+                     const float *s_self, const float *s_neigh, const float *Y, int64_t ldy, const float *dY, int64_t ldd,
+                     const float *bias, const float *a_self, const float *a_neigh,
+                     float *dout, float *row_scratch, float *ds, float *dt, float *dH, int64_t lddh,
+                     int32_t self_loop, int32_t n_rows, amar_stream_t stream) {
+    return gat_bwd_launch(rowptr, colidx, H, ldh, C, s_self, s_neigh, Y, ldy, dY, ldd, bias, a_self, a_neigh, dout, row_scratch, ds, dt,
+                          dH, lddh, self_loop, n_rows, nullptr, stream);
+}
+
+int amar_gat_bwd_dropout_f32(const int32_t *rowptr, const int32_t *colidx, const float *H, int64_t ldh, int32_t C,
+                             const float *s_self, const float *s_neigh, const float *Y, int64_t ldy, const float *dY, int64_t ldd,
+                             const float *bias, const float *a_self, const float *a_neigh,
+                             float *dout, float *row_scratch, float *ds, float *dt, float *dH, int64_t lddh,
+                             int32_t self_loop, int32_t n_rows,
+                             uint64_t seed, const uint64_t *step, uint32_t site, uint32_t threshold, float scale, amar_stream_t stream) {
+    if (!step || site < 1 || site > 255 || !(scale >= 1.f) || scale > 3.0e38f) return AMAR_EINVAL;
+    if (n_rows > AMAR_DROPOUT_MAX_NODES) return AMAR_EUNSUPPORTED;
+    const AmarDropout d{(uint32_t)seed, (uint32_t)(seed >> 32), step, site, threshold, scale};
+    return gat_bwd_launch(rowptr, colidx, H, ldh, C, s_self, s_neigh, Y, ldy, dY, ldd, bias, a_self, a_neigh, dout, row_scratch, ds, dt,
+                          dH, lddh, self_loop, n_rows, &d, stream);
 }
 
 int amar_attention_mix_f32(const float *A, int64_t lda, const float *B, int64_t ldb, const float *TA, int64_t ldta,

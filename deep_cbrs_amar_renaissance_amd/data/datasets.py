@@ -254,3 +254,79 @@ def bpr_device_batch(pos_csr, neg_csr, n_users, seed, step, h):
     pos = np.asarray(pi)[pp[users] + _pick(w[:, 1], pp[users + 1] - pp[users])].astype(np.int64)
     neg = np.asarray(ni)[npt[users] + _pick(w[:, 2], npt[users + 1] - npt[users])].astype(np.int64)
     return (np.repeat(users, 2), np.concatenate([pos, neg])), np.concatenate([np.ones(h, np.int64), np.zeros(h, np.int64)])
+
+
+# ---- the dropout draws, restated (csrc/amar_philox.h; include/amar_hip.h: amar_dropout_f32, amar_gat_layer_dropout_f32) -------------
+def dropout_threshold(rate):
+    """A 32-bit word keeps its value iff word >= T = min(2^32 - 1, floor(rate * 2^32 + 0.5)): P(keep) = 1 - T / 2^32."""
+    return min(0xFFFFFFFF, int(float(rate) * 4294967296.0 + 0.5))
+
+
+def dropout_scale(rate):
+    """What kept values are multiplied by: the float32 nearest to 1 / (1 - rate)."""
+    return np.float32(1.0 / (1.0 - float(rate)))
+
+
+def dropout_stream_seed(seed, index):
+    """The 64-bit key of the index-th dropout stream under `seed` (engine.set_seed restarts the count; every Trainer that drops takes
+    the next one, so two models of one process do not share a stream and a re-run with the same seed repeats it): words 0 and 1 of
+    Philox4x32-10 with key = (seed_lo, seed_hi) and counter = (index, 0, 0, 0x44524F50), as word0 | word1 << 32."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w = philox4x32_10(np.array([[int(index) & 0xFFFFFFFF, 0, 0, 0x44524F50]], dtype=np.uint32), (seed & 0xFFFFFFFF, seed >> 32))[0]
+    return int(w[0]) | (int(w[1]) << 32)
+
+
+def _dropout_words(seed, step, site, c0, c3):
+    seed, step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF
+    if not 1 <= int(site) <= 255:
+        raise ValueError("site must lie in 1..255")
+    c0, c3 = np.asarray(c0, dtype=np.uint64), np.asarray(c3, dtype=np.uint64)
+    n = len(c0)
+    counter = np.stack([c0, np.full(n, step & 0xFFFFFFFF, np.uint64), np.full(n, step >> 32, np.uint64),
+                        (np.uint64(int(site)) << np.uint64(24)) | c3], axis=1)
+    return philox4x32_10(counter.astype(np.uint32), (seed & 0xFFFFFFFF, seed >> 32))
+
+
+def dropout_node_mask(seed, step, site, shape, rate):
+    """The keep mask (bool [n, C]) amar_dropout_f32 applies to an [n, C] slice: call e = r * ceil(C / 4) + c // 4 has counter
+    (e, step_lo, step_hi, site << 24) and its word c % 4 decides column c of row r (the surplus words of a row's last call are
+    unused when C is no multiple of 4)."""
+    n, c = int(shape[0]), int(shape[1])
+    qpr = (c + 3) // 4
+    if n * qpr >= 1 << 31:
+        raise ValueError("slice too large for one counter word")
+    w = _dropout_words(seed, step, site, np.arange(n * qpr, dtype=np.uint64), np.zeros(n * qpr, np.uint64))
+    return (w.reshape(n, 4 * qpr)[:, :c] >= np.uint32(dropout_threshold(rate)))
+
+
+def edge_ordinals(rowptr, colidx):
+    """Per stored entry: its position among the entries of its row with the same column (columns sorted per row), modulo 255."""
+    rowptr, colidx = np.asarray(rowptr, np.int64), np.asarray(colidx, np.int64)
+    nnz = len(colidx)
+    rows = np.repeat(np.arange(len(rowptr) - 1), np.diff(rowptr))
+    idx = np.arange(nnz)
+    first = np.ones(nnz, dtype=bool)
+    first[1:] = (rows[1:] != rows[:-1]) | (colidx[1:] != colidx[:-1])
+    start = np.maximum.accumulate(np.where(first, idx, 0))
+    return rows, (idx - start) % 255
+
+
+def dropout_edge_mask(seed, step, site, rowptr, colidx, self_loop, rate):
+    """The keep bits of amar_gat_layer_dropout_f32 / amar_gat_bwd_dropout_f32: (mask [nnz] per stored entry in CSR order, mask [n] of
+    the added self loops or None).  Entry (target i, source j, ordinal o): counter (min(i, j) | o << 24, step_lo, step_hi,
+    site << 24 | max(i, j)), word 0; the added self loop of node i is (i, i) with ordinal slot 255.  Entry (i, j, o) and its mirror
+    (j, i, o) of a symmetric multiset share the bit; parallel entries (different o) draw independently."""
+    rowptr = np.asarray(rowptr, np.int64)
+    n = len(rowptr) - 1
+    if n > 1 << 24:
+        raise ValueError("edge dropout numbers nodes in 24 bits")
+    t = np.uint32(dropout_threshold(rate))
+    rows, ordinal = edge_ordinals(rowptr, colidx)
+    cols = np.asarray(colidx, np.int64)
+    lo, hi = np.minimum(rows, cols).astype(np.uint64), np.maximum(rows, cols).astype(np.uint64)
+    w = _dropout_words(seed, step, site, lo | (ordinal.astype(np.uint64) << np.uint64(24)), hi)
+    loops = None
+    if self_loop:
+        i = np.arange(n, dtype=np.uint64)
+        loops = _dropout_words(seed, step, site, i | (np.uint64(255) << np.uint64(24)), i)[:, 0] >= t
+    return w[:, 0] >= t, loops

@@ -16,13 +16,25 @@ import torch
 
 _SEED = 42
 _RNG = np.random.default_rng(_SEED)
+_DROPOUT_STREAMS = 0
 
 
 def set_seed(seed):
     """Counterpart of ``tf.random.set_seed(config.seed)`` (experiment.py:56)."""
-    global _SEED, _RNG
+    global _SEED, _RNG, _DROPOUT_STREAMS
     _SEED = int(seed)
     _RNG = np.random.default_rng(_SEED)
+    _DROPOUT_STREAMS = 0
+
+
+def next_dropout_seed():
+    """The key of the next dropout stream under the current seed (data/datasets.py:dropout_stream_seed states the derivation): one
+    per Trainer that drops, counted from the last set_seed, so that two models of one process draw different masks and a re-run
+    with the same seed repeats them."""
+    global _DROPOUT_STREAMS
+    from deep_cbrs_amar_renaissance_amd.data.datasets import dropout_stream_seed
+    index, _DROPOUT_STREAMS = _DROPOUT_STREAMS, _DROPOUT_STREAMS + 1
+    return dropout_stream_seed(_SEED, index)
 
 
 def default_device():

@@ -1,12 +1,14 @@
 """GATConv: the Spektral layer the reference instantiates at `src/models/gnn.py:321-328`.
 
-Spektral 1.x single-mode sparse path (``_call_single``), attn_heads=1, concat_heads=True,
-dropout_rate=0.0, add_self_loops=True:
+Spektral 1.x single-mode sparse path (``_call_single``), attn_heads=1, concat_heads=True, add_self_loops=True:
 
     H = X . W                                   W  [F, 1, C]
     e_ij  = LeakyReLU_0.2( H_i . a_self + H_j . a_neigh )        over A's edges (duplicates kept) + (i, i)
     alpha = exp(e - max_i) / ( sum_i exp(e - max_i) + 1e-9 )      unsorted_segment_softmax over targets
     X'_i  = act( sum_j alpha_ij H_j + b )
+
+``dropout_rate`` drops the coefficients alpha after the softmax while training (training.py, `amar_gat_layer_dropout_f32` /
+`amar_gat_bwd_dropout_f32`); calling the layer, as every scoring path does, is inference and ignores it, as Keras does outside fit().
 
 On the device: `amar_rowwise_xw_f32` (H and the two attention scalars per node) followed by
 `amar_gat_layer_f32` (two passes over the row: max of the neighbour scalars, then the weighted sum); on graphs whose
@@ -29,8 +31,7 @@ class GATConv(Layer):
         super().__init__()
         if attn_heads != 1 or return_attn_coef:
             raise NotImplementedError("the HIP GAT layer implements attn_heads=1 without returned coefficients")
-        if dropout_rate:
-            raise NotImplementedError("attention dropout is a training-time feature; the reference uses 0.0 (config.yaml:20)")
+        self.dropout_rate = capi.check_dropout_rate(dropout_rate, 'dropout_rate')      # used by training.py only
         if activation != 'relu' or not use_bias:
             raise NotImplementedError("the HIP GAT layer is built for activation='relu', use_bias=True")
         self.channels, self.add_self_loops = channels, add_self_loops

@@ -46,7 +46,7 @@ class SequentialGNN(Model):
         :param seq_layers: list of GNN layers.
         :param embedding_dim: width of the trainable node table.
         :param final_node: 'concatenation', 'sum', 'mean', 'w-sum' or 'last'.
-        :param dropout: must be None (no `dropout` key exists in config.yaml; training-only anyway).
+        :param dropout: rate in [0, 1) applied to every layer's output while training (gnn.py:59, 76-81 of the reference); None / 0: none.
         :param regularizer: regulariser object carried by the node table.
         :param cache_neighbours: must be False (the reference raises NotImplementedError too, gnn.py:52-53).
         """
@@ -58,13 +58,12 @@ class SequentialGNN(Model):
     def _init_stack(self, adj_matrix, seq_layers, final_node, dropout, cache_neighbours):
         if cache_neighbours:
             raise NotImplementedError("Multi-hops neighbours caching is not yet completely supported!")
-        if dropout:
-            raise NotImplementedError("dropout is a training-time feature; inference treats it as identity")
         self.cache_neighbours = cache_neighbours
         # GraphSAGE / GAT ignore edge values and add their own self loop
         edge_list = any(isinstance(l, (GraphSageConv, GATConv)) for l in seq_layers)
         self.adj_matrix = convert_to_tensor(adj_matrix, with_values=not edge_list, drop_diagonal=edge_list)
-        self.dropout = None
+        rate = capi.check_dropout_rate(dropout, 'dropout')
+        self.dropout = rate if rate > 0.0 else None            # applied by training.py; calling the stack is inference (identity)
         self.final_node = final_node
         self.reduce = ReductionLayer(final_node)
         self.seq_layers = torch.nn.ModuleList(seq_layers)

@@ -382,12 +382,33 @@ class _StackTape:
         self.cat = self.tape = None
         self._workspaces = {}
         self.defer_reduce = False
+        self.node_drop = self.edge_drop = None                       # set by enable_dropout (Trainer): the stack trains without otherwise
 
     def _workspace(self, k, m, kk, n, device):
         key = (k, int(m), int(kk), int(n))
         if key not in self._workspaces:
             self._workspaces[key] = capi.dense_bwd_workspace(m, kk, n, device)
         return self._workspaces[key]
+
+    MAX_LAYERS = 32                                                  # sites of a stack: 2 * MAX_LAYERS, three stacks at most (< 256)
+
+    def dropout_rates(self):
+        """(stack rate, [GAT attention rate per layer]) with 0.0 for 'none'."""
+        gat = [float(getattr(l, 'dropout_rate', 0.0) or 0.0) for l in self.seq.seq_layers] if self.kind == 'gat' else []
+        return float(self.seq.dropout or 0.0), gat
+
+    def enable_dropout(self, seed, step, stack_index):
+        """The dropout sites of this stack: layer k's output has site 1 + 2 (32 stack_index + k), the attention
+        coefficients of GAT layer k site 2 + 2 (32 stack_index + k); all share the Trainer's key and step counter."""
+        rate, gat = self.dropout_rates()
+        n_layers = len(self.seq.seq_layers)
+        if n_layers > self.MAX_LAYERS or stack_index > 2:
+            raise NotImplementedError("dropout sites are numbered for at most {} layers in at most 3 stacks".format(self.MAX_LAYERS))
+        base = 2 * (self.MAX_LAYERS * stack_index)
+        if rate > 0.0:
+            self.node_drop = [capi.Dropout(seed, step, base + 2 * k + 1, rate) for k in range(n_layers)]
+        if any(r > 0.0 for r in gat):
+            self.edge_drop = [capi.Dropout(seed, step, base + 2 * k + 2, r) if r > 0.0 else None for k, r in enumerate(gat)]
 
     def _slices(self, t):
         offs = self.offs
@@ -401,7 +422,7 @@ class _StackTape:
         widths = self.widths = seq.layer_widths()
         seq._build_layers(widths)
         self.offs = [int(v) for v in np.cumsum([0] + widths)]
-        if self.kind in ('gcn', 'lightgcn'):
+        if self.kind in ('gcn', 'lightgcn') and self.node_drop is None:
             # the inference kernels: their outputs are all the reverse pass needs
             out, self.cat = seq._propagate(x0, with_layers=True)
             return out
@@ -413,7 +434,11 @@ class _StackTape:
         self.tape = []
         for k, layer in enumerate(seq.seq_layers):
             f, c = widths[k], widths[k + 1]
-            if self.kind == 'sage':
+            drop = self.node_drop[k] if self.node_drop is not None else None
+            if self.kind in ('gcn', 'lightgcn'):
+                # (a stack rate is set) layer by layer through the layers' own calls: the next layer must read the dropped slice
+                layer([sl(k), a], out=sl(k + 1))
+            elif self.kind == 'sage':
                 # layer by layer, keeping [x || mean(x)] and the l2-normalised pre-activation
                 xa = torch.empty((n, 2 * f), dtype=torch.float32, device=dev)
                 capi.copy_columns(sl(k), xa[:, :f])
@@ -433,10 +458,24 @@ class _StackTape:
                 s_neigh = torch.empty(n, dtype=torch.float32, device=dev)
                 capi.rowwise_xw(sl(k), layer.kernel.view(-1, c), h, a_self=layer.attn_kernel_self.view(c),
                                 a_neigh=layer.attn_kernel_neighs.view(c), s_self=s_self, s_neigh=s_neigh)
-                capi.gat_layer(a.rowptr, a.colidx, h, s_self, s_neigh, layer.bias, sl(k + 1), self_loop=layer.add_self_loops)
-                self.tape.append((h, s_self, s_neigh))
+                # with a stack rate the undropped output stays on the tape: the softmax reverse needs out_i itself (c_i = g_i . (out_i - b))
+                y = torch.empty((n, c), dtype=torch.float32, device=dev) if drop is not None else sl(k + 1)
+                edge = self.edge_drop[k] if self.edge_drop is not None else None
+                if edge is not None:
+                    capi.gat_layer_dropout(a.rowptr, a.colidx, h, s_self, s_neigh, layer.bias, y, edge, self_loop=layer.add_self_loops)
+                else:
+                    capi.gat_layer(a.rowptr, a.colidx, h, s_self, s_neigh, layer.bias, y, self_loop=layer.add_self_loops)
+                self.tape.append((h, s_self, s_neigh, y))
+                if drop is not None:
+                    capi.dropout(y, drop, out=sl(k + 1))
+                    continue
             else:                                                    # dgcf: every layer's input stays in `cat` (the gate's gradient needs it)
                 layer([sl(k), a], out=sl(k + 1))
+            if drop is not None:
+                # in place, before the reduction and the next layer read the slice (the reference's loop, gnn.py:76-81).  Sound for the
+                # reverse pass: it masks d(slice k + 1) first, so every `Y > 0` it then evaluates sees a kept element (same sign) or
+                # meets a gradient that already is zero
+                capi.dropout(sl(k + 1), drop)
         return seq._reduce(cat, [sl(k) for k in range(len(widths))], widths)
 
     # -- reverse ----------------------------------------------------------------------------------------------------
@@ -485,6 +524,8 @@ class _StackTape:
         for k in range(len(layers) - 1, -1, -1):
             layer = layers[k]
             f, c = widths[k], widths[k + 1]
+            if self.node_drop is not None:                           # the regenerated mask of layer k's output, on its gradient
+                capi.dropout(dsl(k + 1), self.node_drop[k])
             if self.kind == 'gcn':
                 dzk = torch.empty((n, c), dtype=torch.float32, device=dev)
                 dw, db = torch.empty_like(layer.kernel), torch.empty_like(layer.bias)
@@ -538,11 +579,15 @@ class _StackTape:
                 if self.self_loops:
                     capi.add_inplace(dsl(k), g)
             elif self.kind == 'gat':
-                h, s_self, s_neigh = self.tape[k]
+                h, s_self, s_neigh, y = self.tape[k]
                 w2d = layer.kernel.detach().view(f, c)
-                dout, ds, dt, dh = capi.gat_bwd(a.rowptr, a.colidx, h, s_self, s_neigh, sl(k + 1), dsl(k + 1), layer.bias,
-                                                layer.attn_kernel_self.detach().view(c), layer.attn_kernel_neighs.detach().view(c),
-                                                self_loop=layer.add_self_loops)
+                edge = self.edge_drop[k] if self.edge_drop is not None else None
+                gat_args = (a.rowptr, a.colidx, h, s_self, s_neigh, y, dsl(k + 1), layer.bias,
+                            layer.attn_kernel_self.detach().view(c), layer.attn_kernel_neighs.detach().view(c))
+                if edge is not None:
+                    dout, ds, dt, dh = capi.gat_bwd_dropout(*gat_args, edge, self_loop=layer.add_self_loops)
+                else:
+                    dout, ds, dt, dh = capi.gat_bwd(*gat_args, self_loop=layer.add_self_loops)
                 db = torch.empty_like(layer.bias)
                 das, dan = torch.empty((c, 1), dtype=torch.float32, device=dev), torch.empty((c, 1), dtype=torch.float32, device=dev)
                 fused = capi.dense_bwd_enabled() and capi.dense_bwd_supported(f, c) and n > 0
@@ -664,6 +709,25 @@ class Trainer:
         self.m = {p: torch.zeros_like(p) for p in self.params}
         self.v = {p: torch.zeros_like(p) for p in self.params}
         self.head = _HybridHead(model.rs) if self.hybrid else _BasicHead(model.rs)
+        self._init_dropout()
+
+    dropout_key, dropout_step = (), None                             # (HeadTrainer: the heads have no dropout, as in the reference)
+
+    def _init_dropout(self):
+        """Training-time dropout: where a stack rate or a GAT attention rate is set, one key (engine.next_dropout_seed:
+        derived from the seed, one stream per Trainer that drops) and one step counter in device memory that every mask kernel reads
+        and `_forward_backward` advances once per batch.  No rate set: nothing is allocated and every path is the one without dropout."""
+        rates = [t.dropout_rates() for t in self.tapes]
+        if not any(r > 0.0 or any(g > 0.0 for g in gat) for r, gat in rates):
+            return
+        from deep_cbrs_amar_renaissance_amd import engine
+        device = self.device
+        self.dropout_seed = engine.next_dropout_seed()
+        self.dropout_step = torch.zeros(1, dtype=torch.int64, device=device)
+        for index, tape in enumerate(self.tapes):
+            tape.enable_dropout(self.dropout_seed, self.dropout_step, index)
+        # part of a captured graph's key: the rates and the identity of the state its body reads
+        self.dropout_key = (self.dropout_seed, self.dropout_step.data_ptr(), tuple((r, tuple(gat)) for r, gat in rates))
 
     @staticmethod
     def _l2(param):
@@ -727,6 +791,8 @@ class Trainer:
             capi.scatter_add_rows(dgu, u, de)
             capi.scatter_add_rows(dgi, i, de)
         self._propagation_backward(e, de, grads)
+        if self.dropout_step is not None:                            # after the last reader of this batch's masks
+            capi.dropout_advance(self.dropout_step)
         return terms, grads
 
     def loss_and_grads(self, u_ids, i_ids, y, bert=None):
@@ -773,15 +839,17 @@ class Trainer:
         capi.adam_multi(g['slot_dev'], len(entries), blocks, self._adam_state, self.b1, self.b2, self.eps,
                         reg_scale=batch, loss_acc=self._loss_sum)
 
-    def train_batch_graphed(self, u_ids, i_ids, y, bert=None):
+    def train_batch_graphed(self, u_ids, i_ids, y, bert=None, graph=True):
         """One training batch replayed from a hipGraph: the forward, the reverse pass and the Adam update are ~100
         small launches that are otherwise bound by host launch time.  The graph is captured at the second batch of a
         given size (the first one runs eagerly and warms every lazily built buffer); the running loss stays on the
-        device (`pop_loss_sum`).  Batches of another size run eagerly."""
+        device (`pop_loss_sum`).  Batches of another size run eagerly.  graph=False: the same body, same buffers and uploads, run
+        eagerly at every batch instead of captured and replayed (what fit() does under AMAR_TRAIN_GRAPH=0 when the model drops: the
+        two then agree bit for bit, masks included)."""
         b = len(y)
         dev = self.device
         with_blocks = bert is not None and bert[0] is not None
-        key = (b, with_blocks, self._loss_kind())                   # (a compile() with another loss captures anew)
+        key = (b, with_blocks, self._loss_kind()) + self.dropout_key  # (a compile() with another loss captures anew; so would other dropout state)
         self._init_graph_state()
         g = self._graphs.get(key)
         if g is None:
@@ -789,6 +857,8 @@ class Trainer:
                 self._seen.add(key)
                 self._eager_loss += self.train_batch(u_ids, i_ids, y, bert=bert) * b
                 return
+            g = None if graph else self._eager_batches.get(key)
+        if g is None:
             d = int(np.asarray(bert[0]).shape[1]) if with_blocks else 0
             uiy = torch.zeros(3 * b, dtype=torch.int32, device=dev)  # u, i and the labels in ONE buffer: one upload per batch instead of three
             ui = uiy[:2 * b]                                          # (u and i side by side: one scatter of both towers' input gradients)
@@ -806,14 +876,17 @@ class Trainer:
                 host = torch.empty(3 * b, dtype=torch.int32).pin_memory()
                 g['stage'].append({'uiy': host, 'u': host[:b], 'i': host[b:2 * b], 'y': host[2 * b:].view(torch.float32), 'done': torch.cuda.Event()})
             g['turn'] = 0
-            from deep_cbrs_amar_renaissance_amd.engine import capture_graph
+            if graph:
+                from deep_cbrs_amar_renaissance_amd.engine import capture_graph
 
-            def body():
-                with torch.no_grad():
-                    self._graph_body()
-            g['graph'], _ = capture_graph(body)
-            g['slot_dev'][:g['slot_bytes']].copy_(g['slot_host'][:g['slot_bytes']])   # the Adam slot table of this graph (fixed addresses): once, not per replay
-            self._graphs[key] = g
+                def body():
+                    with torch.no_grad():
+                        self._graph_body()
+                g['graph'], _ = capture_graph(body)
+                g['slot_dev'][:g['slot_bytes']].copy_(g['slot_host'][:g['slot_bytes']])   # the Adam slot table of this graph (fixed addresses): once, not per replay
+                self._graphs[key] = g
+            else:
+                self._eager_batches = {key: g}
         self._g = g
         n_nodes = self.seq.adj_matrix.shape[0] if getattr(self, 'seq', None) is not None else None
         st = g['stage'][g['turn'] % len(g['stage'])]
@@ -841,7 +914,11 @@ class Trainer:
             g['ib'].copy_(to_device_tensor(bert[1]))
         if self._dev_t != self.t:                                    # eager steps happened in between: resynchronise the counter
             self._adam_state[0] = float(self.t)
-        g['graph'].replay()
+        if 'graph' in g:
+            g['graph'].replay()
+        else:
+            with torch.no_grad():
+                self._graph_body(upload_slots=True)
         self.t += 1
         self._dev_t = self.t
 
@@ -849,7 +926,7 @@ class Trainer:
         if not hasattr(self, '_graphs'):
             dev = self.device
             self._graphs, self._seen, self._eager_loss, self._dev_t = {}, set(), 0.0, None
-            self._eager_sampled = {}
+            self._eager_sampled, self._eager_batches = {}, {}
             self._adam_state = torch.zeros(2, dtype=torch.float32, device=dev)
             self._loss_sum = torch.zeros((), dtype=torch.float32, device=dev)
 
@@ -874,7 +951,7 @@ class Trainer:
         if self.hybrid:
             raise NotImplementedError("the BPR sample Sequence carries no BERT rows: hybrid models do not train on it")
         b = 2 * sampler.h
-        key = ('sampled', b, self._loss_kind(), sampler.serial)
+        key = ('sampled', b, self._loss_kind(), sampler.serial) + self.dropout_key
         self._init_graph_state()
         g = self._graphs.get(key)
         if g is None:
@@ -1160,6 +1237,7 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
                 hp['bert_dim'] = int(np.asarray(first[2]).shape[1])
         trainer = model._trainer = Trainer(model, **hp)
     use_graph = os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
+    same_body = not use_graph and trainer.dropout_step is not None      # a model that drops: the replayed body, run eagerly (same bits)
     history = []
     for epoch in range(int(epochs)):
         total, count = 0.0, 0
@@ -1167,12 +1245,12 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
             inputs, y = (ids_only if ids_only is not None else sequence)[b]
             u, i = inputs[0], inputs[1]
             bert = (inputs[2], inputs[3]) if len(inputs) >= 4 else None     # hybrid batches carry the BERT blocks (datasets.py:112-115)
-            if use_graph:
-                trainer.train_batch_graphed(u, i, y, bert=bert)
+            if use_graph or same_body:
+                trainer.train_batch_graphed(u, i, y, bert=bert, graph=use_graph)
             else:
                 total += trainer.train_batch(u, i, y, bert=bert) * len(y)
             count += len(y)
-        if use_graph:
+        if use_graph or same_body:
             total = trainer.pop_loss_sum()
             trainer.touch_parameters()
         history.append(total / max(count, 1))

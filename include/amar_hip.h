@@ -564,6 +564,42 @@ int amar_bpr_sample_i32(const int32_t *pos_ptr, const int32_t *pos_ids, const in
                         int32_t n_users, uint64_t seed, uint64_t *step, int32_t advance, int32_t h,
                         int32_t *u, int32_t *items, float *y, amar_stream_t stream);
 
+/* ---- training-time dropout (the `dropout` key of the GNN stacks, `dropout_rate` of GAT) ------------------------------------------
+ * No mask is stored: a keep bit is a function of (seed, step, site, element) through Philox4x32-10 and the reverse pass regenerates
+ * it.  key = (seed & 0xffffffff, seed >> 32); counter = (c0, s & 0xffffffff, s >> 32, (site << 24) | c3) with s = *step read from
+ * DEVICE memory (a replayed graph drops other elements every step) and site in 1..255 (which dropout of the model).  A value is
+ * kept iff its 32-bit word >= threshold (= min(2^32 - 1, round(rate * 2^32))) and then multiplied by scale (= float32(1 / (1 - rate)));
+ * a dropped value becomes +0.  None of these entries advances *step.
+ * amar_dropout_f32            Y[r, c] = X[r, c] * keep * scale on an [n_rows, C] slice (Y == X: in place); applied to a gradient slice
+ *                             it is its own reverse.  Element: c0 = r * ceil(C / 4) + c / 4, c3 = 0, word c % 4 of the call (one call
+ *                             per 16 bytes; a width that is no multiple of 4 leaves the surplus words of a row's last call unused and
+ *                             takes scalar accesses, as do slices that are not 16-byte aligned).  n_rows * ceil(C / 4) < 2^31.
+ * amar_dropout_advance        *step += 1, once per training step after the last reader.
+ * amar_gat_layer_dropout_f32  amar_gat_layer_f32 with the attention coefficients dropped AFTER the softmax (Spektral):
+ *                             Y_i = ReLU(sum_j alpha_ij keep_ij scale H_j + bias); maximum, denominator and the 1e-9 are those of the
+ *                             undropped logits.  Element of the stored entry (target i, source j) that is the o-th of its row's equal
+ *                             columns (colidx sorted per row): c0 = min(i, j) | ((o % 255) << 24), c3 = max(i, j), word 0; the added self
+ *                             loop is the entry (i, i) with ordinal slot 255.  The edge multiset must be symmetric: (i, j, o) and (j, i, o)
+ *                             then draw one bit, wherever the entry is visited.  n_rows <= 2^24.  threshold 0, scale 1: the bits of
+ *                             amar_gat_layer_f32.
+ * amar_gat_bwd_dropout_f32    amar_gat_bwd_f32 for that forward with the same bits: d alpha_ij = keep_ij scale (dout_i . H_j) into the
+ *                             unchanged softmax reverse, dH_j accumulates alpha_ij keep_ij scale dout_i; no float atomics. */
+int amar_dropout_f32(const float *X, int64_t ldx, float *Y, int64_t ldy, int64_t n_rows, int32_t C,
+                     uint64_t seed, const uint64_t *step, uint32_t site, uint32_t threshold, float scale, amar_stream_t stream);
+int amar_dropout_advance(uint64_t *step, amar_stream_t stream);
+int amar_gat_layer_dropout_f32(const int32_t *rowptr, const int32_t *colidx,
+                               const float *H, int64_t ldh, int32_t C,
+                               const float *s_self, const float *s_neigh, const float *bias,
+                               float *Y, int64_t ldy, int32_t self_loop, int32_t n_rows,
+                               uint64_t seed, const uint64_t *step, uint32_t site, uint32_t threshold, float scale,
+                               amar_stream_t stream);
+int amar_gat_bwd_dropout_f32(const int32_t *rowptr, const int32_t *colidx, const float *H, int64_t ldh, int32_t C,
+                             const float *s_self, const float *s_neigh, const float *Y, int64_t ldy, const float *dY, int64_t ldd,
+                             const float *bias, const float *a_self, const float *a_neigh,
+                             float *dout, float *row_scratch, float *ds, float *dt, float *dH, int64_t lddh,
+                             int32_t self_loop, int32_t n_rows,
+                             uint64_t seed, const uint64_t *step, uint32_t site, uint32_t threshold, float scale, amar_stream_t stream);
+
 /* ---- ranking ------------------------------------------------------------------------------
  * Per-user top-k over that user's own test pairs (src/utilities/metrics.py:11-34):
  * pairs are grouped by user (seg_ptr[n_users+1] into item_ids/scores); for each user the k
