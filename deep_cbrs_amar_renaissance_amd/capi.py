@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(_HERE, 'libamar_hip.so')
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 ACT_CODES = {None: ACT_NONE, 'linear': ACT_NONE, 'relu': ACT_RELU, 'sigmoid': ACT_SIGMOID}
+AGG_SUM, AGG_MAX, AGG_MIN = 0, 1, 2
+AGG_CODES = {'sum': AGG_SUM, 'max': AGG_MAX, 'min': AGG_MIN}
 SPMM_BIAS, SPMM_RELU, SPMM_ACCUM, SPMM_ACCUM_DIV, SPMM_SCALE_NEXT, SPMM_SAGE_TAIL, SPMM_LT_NOPAIRS = 1, 2, 4, 8, 16, 32, 64
 
 _P = ctypes.c_void_p
@@ -43,6 +45,9 @@ SIGNATURES = {
     'amar_rowwise_xw_gather_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _P, _I32, _P, _I64, _P, _I32, _P]),
     'amar_sage_layer_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _I32, _P, _I64, _I32, _I32, _P]),
     'amar_sage_tail_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I32, _P, _P, _I32, _P, _I64, _I64, _P]),
+    'amar_sage_layer_agg_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _I32, _P, _I64, _I32, _I32, _I32, _P]),
+    'amar_sage_aggregate_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _I64, _P, _I64, _I32, _I32, _I32, _P]),
+    'amar_sage_aggregate_bwd_f32': (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I32, _P, _P, _I64, _I32, _I32, _P]),
     'amar_gat_layer_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _P]),
     'amar_dense_f32': (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _P]),
     'amar_dense_split_bytes': (ctypes.c_int64, [_I32, _I32]),
@@ -454,6 +459,66 @@ def sage_tail(X, agg, W, bias, Y):
 
 def sage_tail_supported(F, C):
     return F % 4 == 0 and C % 4 == 0 and 4 <= F <= 64 and 4 <= C <= 64
+
+
+def _agg_code(op, what):
+    if op not in AGG_CODES:
+        raise ValueError("{}: op must be one of {} (got {!r})".format(what, sorted(AGG_CODES), op))
+    return AGG_CODES[op]
+
+
+def sage_layer_agg(rowptr, colidx, X, W, bias, Y, op, self_loop=True):
+    """Y = relu(l2_normalize([X || OP over the row's entries of X] . W + bias)), op in 'sum' | 'max' | 'min' (amar_sage_layer_agg_f32)."""
+    n_rows = rowptr.numel() - 1
+    F = X.shape[1]
+    if W.shape[0] != 2 * F or not W.is_contiguous() or bias.numel() != W.shape[1] or \
+            tuple(Y.shape) != (n_rows, W.shape[1]) or X.shape[0] < n_rows:
+        raise ValueError("sage_layer_agg: W [2F, C] contiguous, bias [C], Y [n_rows, C] expected")
+    code = load().amar_sage_layer_agg_f32(
+        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'),
+        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), F, _ptr(W, torch.float32, 'W'), _ptr(bias, torch.float32, 'bias'),
+        W.shape[1], _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'), 1 if self_loop else 0, _agg_code(op, 'sage_layer_agg'), n_rows, _stream())
+    _check(code, 'amar_sage_layer_agg_f32')
+
+
+def sage_agg_layer_supported(F, C):
+    return F in (4, 8, 16, 32) and 1 <= C <= 64
+
+
+def sage_aggregate(rowptr, colidx, X, agg, op, cnt=None, self_loop=True):
+    """agg = max | min over the row's entries (+ the row itself) of X; cnt (optional) = how many entries attain it (amar_sage_aggregate_f32)."""
+    n_rows = rowptr.numel() - 1
+    F = X.shape[1]
+    if tuple(agg.shape) != (n_rows, F) or X.shape[0] < n_rows or (cnt is not None and tuple(cnt.shape) != (n_rows, F)):
+        raise ValueError("sage_aggregate: X [>=n_rows, F], agg [n_rows, F], cnt [n_rows, F] or None expected")
+    code = load().amar_sage_aggregate_f32(
+        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'),
+        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), F, _ptr(agg, torch.float32, 'agg'), _ld(agg, 'agg'),
+        _ptr(cnt, torch.float32, 'cnt'), _ld(cnt, 'cnt') if cnt is not None else 0,
+        1 if self_loop else 0, _agg_code(op, 'sage_aggregate'), n_rows, _stream())
+    _check(code, 'amar_sage_aggregate_f32')
+
+
+def sage_aggregate_bwd(rowptr, colidx, X, agg, cnt, d_agg, dX, self_loop=True, pack=None):
+    """dX[j] += the shares of d_agg that X[j] attained (ties and duplicate edges share equally): the reverse pass of
+    sage_aggregate on a symmetric edge multiset (amar_sage_aggregate_bwd_f32).  pack: [n_rows, 2F] scratch (allocated if None)."""
+    n_rows = rowptr.numel() - 1
+    F = X.shape[1]
+    for t, name in ((agg, 'agg'), (cnt, 'cnt'), (d_agg, 'd_agg'), (dX, 'dX')):
+        if tuple(t.shape) != (n_rows, F):
+            raise ValueError("sage_aggregate_bwd: {} [n_rows, F] expected".format(name))
+    if X.shape[0] < n_rows:
+        raise ValueError("sage_aggregate_bwd: X [>=n_rows, F] expected")
+    if pack is None:
+        pack = torch.empty((n_rows, 2 * F), dtype=torch.float32, device=X.device)
+    if tuple(pack.shape) != (n_rows, 2 * F) or not pack.is_contiguous():
+        raise ValueError("sage_aggregate_bwd: pack [n_rows, 2F] contiguous expected")
+    code = load().amar_sage_aggregate_bwd_f32(
+        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'),
+        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), _ptr(agg, torch.float32, 'agg'), _ld(agg, 'agg'),
+        _ptr(cnt, torch.float32, 'cnt'), _ld(cnt, 'cnt'), _ptr(d_agg, torch.float32, 'd_agg'), _ld(d_agg, 'd_agg'), F,
+        _ptr(pack, torch.float32, 'pack'), _ptr(dX, torch.float32, 'dX'), _ld(dX, 'dX'), 1 if self_loop else 0, n_rows, _stream())
+    _check(code, 'amar_sage_aggregate_bwd_f32')
 
 
 def gat_layer(rowptr, colidx, H, s_self, s_neigh, bias, Y, self_loop=True):

@@ -45,18 +45,6 @@ __device__ __forceinline__ float4 row_gather_sum(const int32_t *__restrict__ col
     return f4_wave_sum_stride<LPN>(acc);
 }
 
-// All lanes receive the full reduced row y[0:F] (lane qq of slot 0 holds quad qq).
-template <int F>
-__device__ __forceinline__ void broadcast_row(const float4 yq, float (&full)[F]) {
-#pragma unroll
-    for (int qq = 0; qq < F / 4; ++qq) {                  // v_readlane: the value becomes a scalar operand
-        full[4 * qq + 0] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, yq.x), qq));
-        full[4 * qq + 1] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, yq.y), qq));
-        full[4 * qq + 2] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, yq.z), qq));
-        full[4 * qq + 3] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, yq.w), qq));
-    }
-}
-
 struct SpmmArgs {
     const int32_t *rowptr; const int32_t *colidx; const float *vals;
     const float *X; int64_t ldx;

@@ -322,6 +322,9 @@ class PartitionedGCNRunner:
         else:
             raise NotImplementedError("the partitioned runner covers GCN / GraphSAGE / GAT (8, 16 or 32 channels) stacks with "
                                       "'concatenation' and LightGCN / DGCF stacks ('mean')")
+        if self.kind == 'sage' and any(l.aggregate != 'mean' for l in layers):
+            raise NotImplementedError("the partitioned runner covers GraphSAGE with aggregate='mean' only; sum / max / min stacks "
+                                      "run on one GPU")
         if self.kind in ('sage', 'gat') and ops is not capi:
             raise NotImplementedError("partitioned GraphSAGE / GAT run on the XCD-sliced HIP kernels only")
         self.hybrid = hasattr(model.rs, 'dense1a')

@@ -371,14 +371,11 @@ class _StackTape:
         if seq.final_node not in ('concatenation', 'mean', 'sum', 'last', 'w-sum'):
             raise NotImplementedError("no reverse pass for the '{}' reduction".format(seq.final_node))
         if self.kind == 'sage':
-            a = seq.adj_matrix
-            deg = (a.rowptr[1:] - a.rowptr[:-1]).to(torch.float32)
-            if len({bool(l.self_loops) for l in layers}) != 1:
-                raise NotImplementedError("GraphSAGE layers with mixed self_loops settings")
-            self.self_loops = bool(layers[0].self_loops)
-            # unsorted_segment_mean: sum / count, 0 for an empty segment
-            self.inv_cnt = (1.0 / (deg + 1.0)) if self.self_loops else torch.where(deg > 0, 1.0 / deg.clamp(min=1.0), torch.zeros_like(deg))
-            self.inv_cnt = self.inv_cnt.contiguous()
+            if len({bool(l.self_loops) for l in layers}) != 1 or len({l.aggregate for l in layers}) != 1:
+                raise NotImplementedError("GraphSAGE layers with mixed self_loops / aggregate settings")
+            self.self_loops, self.aggregate = bool(layers[0].self_loops), layers[0].aggregate
+            # 'mean': sum / count (0 for an empty segment), 'sum': sum * 1 — the layer's cached vector; max / min keep a tie count instead
+            self.inv_cnt = layers[0].row_scale(seq.adj_matrix) if self.aggregate in ('mean', 'sum') else None
         self.cat = self.tape = None
         self._workspaces = {}
         self.defer_reduce = False
@@ -439,18 +436,23 @@ class _StackTape:
                 # (a stack rate is set) layer by layer through the layers' own calls: the next layer must read the dropped slice
                 layer([sl(k), a], out=sl(k + 1))
             elif self.kind == 'sage':
-                # layer by layer, keeping [x || mean(x)] and the l2-normalised pre-activation
+                # layer by layer, keeping [x || agg(x)] and the l2-normalised pre-activation
                 xa = torch.empty((n, 2 * f), dtype=torch.float32, device=dev)
                 capi.copy_columns(sl(k), xa[:, :f])
-                ssum = torch.empty((n, f), dtype=torch.float32, device=dev)
-                capi.spmm_csr(a.rowptr, a.colidx, None, sl(k), ssum)
-                capi.row_affine(ssum, self.inv_cnt, xa[:, f:], b=sl(k) if self.self_loops else None)
+                cnt = None
+                if self.inv_cnt is None:                             # max / min: the aggregate straight into xa, and how many entries attain it
+                    cnt = torch.empty((n, f), dtype=torch.float32, device=dev)
+                    capi.sage_aggregate(a.rowptr, a.colidx, sl(k), xa[:, f:], self.aggregate, cnt=cnt, self_loop=self.self_loops)
+                else:
+                    ssum = torch.empty((n, f), dtype=torch.float32, device=dev)
+                    capi.spmm_csr(a.rowptr, a.colidx, None, sl(k), ssum)
+                    capi.row_affine(ssum, self.inv_cnt, xa[:, f:], b=sl(k) if self.self_loops else None)
                 z = torch.empty((n, c), dtype=torch.float32, device=dev)
                 capi.dense(xa, layer.kernel, layer.bias, z, act=None)
                 nrm = torch.empty((n, c), dtype=torch.float32, device=dev)
                 inv = torch.empty(n, dtype=torch.float32, device=dev)
                 capi.l2norm_fwd(z, nrm, inv, sl(k + 1), act='relu')
-                self.tape.append((xa, nrm, inv))
+                self.tape.append((xa, nrm, inv, cnt))
             elif self.kind == 'gat':
                 # same kernels as inference, keeping H and the two attention scalars
                 h = torch.empty((n, c), dtype=torch.float32, device=dev)
@@ -556,7 +558,7 @@ class _StackTape:
                 _spmm(a, dsl(k + 1), back)
                 capi.add_inplace(dsl(k), back)
             elif self.kind == 'sage':
-                xa, nrm, inv = self.tape[k]
+                xa, nrm, inv, cnt = self.tape[k]
                 dz = torch.empty((n, c), dtype=torch.float32, device=dev)
                 capi.l2norm_bwd(dsl(k + 1), nrm, inv, dz, act='relu')
                 dw, db = torch.empty_like(layer.kernel), torch.empty_like(layer.bias)
@@ -571,13 +573,17 @@ class _StackTape:
                     capi.dense(dz, layer.kernel.detach(), None, dxa, act=None, w_transposed=True)
                 grads[layer.kernel], grads[layer.bias] = dw, db
                 capi.add_inplace(dsl(k), dxa[:, :f])
-                g = torch.empty((n, f), dtype=torch.float32, device=dev)
-                capi.row_affine(dxa[:, f:], self.inv_cnt, g)               # d(mean)/d(sum)
-                back = torch.empty((n, f), dtype=torch.float32, device=dev)
-                capi.spmm_csr(a.rowptr, a.colidx, None, g, back)           # the edge multiset is symmetric
-                capi.add_inplace(dsl(k), back)
-                if self.self_loops:
-                    capi.add_inplace(dsl(k), g)
+                if cnt is not None:
+                    # every entry that attains the extremum takes d_agg / cnt; row j finds its shares on its own CSR row (symmetric multiset)
+                    capi.sage_aggregate_bwd(a.rowptr, a.colidx, xa[:, :f], xa[:, f:], cnt, dxa[:, f:], dsl(k), self_loop=self.self_loops)
+                else:
+                    g = torch.empty((n, f), dtype=torch.float32, device=dev)
+                    capi.row_affine(dxa[:, f:], self.inv_cnt, g)           # d(mean)/d(sum); 'sum': a copy
+                    back = torch.empty((n, f), dtype=torch.float32, device=dev)
+                    capi.spmm_csr(a.rowptr, a.colidx, None, g, back)       # the edge multiset is symmetric
+                    capi.add_inplace(dsl(k), back)
+                    if self.self_loops:
+                        capi.add_inplace(dsl(k), g)
             elif self.kind == 'gat':
                 h, s_self, s_neigh, y = self.tape[k]
                 w2d = layer.kernel.detach().view(f, c)

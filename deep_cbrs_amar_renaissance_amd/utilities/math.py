@@ -369,11 +369,11 @@ def _csr_xcd_sliced(self):
     return self.__dict__['_xs_cache']
 
 
-def _csr_xcd_sliced_mean(self, self_loops=True):
+def _csr_xcd_sliced_mean(self, self_loops=True, aggregate='mean'):
     """XS image of an edge-list CSR (no values, duplicates kept, no diagonal) as GraphSAGE's mean aggregate:
     value-free entries, diag = 1 for the added self loop, row_scale = 1 / count (0 for an empty segment); the gathered
-    table is NOT pre-scaled (call capi.spmm_xs with prescaled=True)."""
-    key = '_xs_mean_cache_{}'.format(int(bool(self_loops)))
+    table is NOT pre-scaled (call capi.spmm_xs with prescaled=True).  aggregate='sum': the same image with row_scale = 1."""
+    key = '_xs_{}_cache_{}'.format(aggregate, int(bool(self_loops)))
     if key not in self.__dict__:
         if self.vals is not None:
             raise ValueError("the mean-aggregate image is built from an edge-list CSR (vals None)")
@@ -384,6 +384,8 @@ def _csr_xcd_sliced_mean(self, self_loops=True):
             inv = 1.0 / (deg + 1.0)
         else:
             inv = torch.where(deg > 0, 1.0 / deg.clamp(min=1.0), torch.zeros_like(deg))
+        if aggregate == 'sum':
+            inv = torch.ones_like(deg)
         xs.vals, xs.row_scale, xs.col_scale = None, inv.contiguous(), None
         self.__dict__[key] = xs
     return self.__dict__[key]
@@ -482,17 +484,18 @@ def _row_breaks_of(a, rows, cols):
     return tuple(a.row_breaks)
 
 
-def _csr_tiled_mean_image(self, F, self_loops=True):
+def _csr_tiled_mean_image(self, F, self_loops=True, aggregate='mean'):
     """GraphSAGE's mean aggregate of an edge-list CSR (vals None, duplicates kept) on whichever tiled image pays: the
     LDS-tiled one (value-free entries, diag = 1 for the added self loop, row_scale = 1 / count, X gathered as is: call
-    capi.spmm_xs with prescaled=True) under the same density rule as lt_eligible, else xcd_sliced_mean."""
+    capi.spmm_xs with prescaled=True) under the same density rule as lt_eligible, else xcd_sliced_mean.
+    aggregate='sum' (tiled_sum_image): the same images with row_scale = 1, cached beside the mean ones."""
     from deep_cbrs_amar_renaissance_amd.utilities import lds_tiled
     forced = os.environ.get('AMAR_SPMM_LT')
     ok = forced != '0' and self.vals is None and lds_tiled.supported(F, self.shape[1]) and \
         (forced == '1' or (F in (8, 16, 32) and self.nnz >= LT_MIN_DENSITY * lds_tiled.N_CU * getattr(self, 'active_cols', self.shape[1])))
     if not ok:
-        return self.xcd_sliced_mean(self_loops)
-    cache = self.__dict__.setdefault('_lt_mean_cache', {})
+        return self.xcd_sliced_mean(self_loops, aggregate)
+    cache = self.__dict__.setdefault('_lt_{}_cache'.format(aggregate), {})
     key = (F, bool(self_loops))
     if key not in cache:
         rows, cols, diag, diag_offset = _unit_entries(self, False)
@@ -502,6 +505,8 @@ def _csr_tiled_mean_image(self, F, self_loops=True):
             inv = 1.0 / (deg + 1.0)
         else:
             inv = torch.where(deg > 0, 1.0 / deg.clamp(min=1.0), torch.zeros_like(deg))
+        if aggregate == 'sum':
+            inv = torch.ones_like(deg)
         breaks = _row_breaks_of(self, rows, cols) if not diag_offset else ()
         cache[key] = lds_tiled.LdsTiled.build(rows, cols, self.shape[0], self.shape[1], F, diag, inv.contiguous(), None, diag_offset,
                                               row_breaks=breaks)
@@ -509,6 +514,7 @@ def _csr_tiled_mean_image(self, F, self_loops=True):
 
 
 DeviceCSR.tiled_mean_image = _csr_tiled_mean_image
+DeviceCSR.tiled_sum_image = lambda self, F, self_loops=True: _csr_tiled_mean_image(self, F, self_loops, 'sum')
 
 
 def _csr_tiled_gat_image(self, C):

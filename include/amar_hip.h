@@ -196,6 +196,47 @@ int amar_sage_tail_f32(const float *X, int64_t ldx, const float *AGG, int64_t ld
                        const float *W, const float *bias, int32_t C, float *Y, int64_t ldy,
                        int64_t n_rows, amar_stream_t stream);
 
+/* GraphSAGE's other aggregators (config.yaml:17-18 `model.aggregate`, handed to Spektral's GraphSageConv at
+ * src/models/gnn.py:331-361; Spektral 1.x resolves the name to a segment reduction).  The entries of row i are its CSR row
+ * (duplicates kept, values ignored) plus i itself when self_loop:
+ *     agg_i[f] = OP over entries j of X[j, f]          OP = sum | max | min;  a row without entries gives 0
+ * (a stated deviation from tf.math.unsorted_segment_max, which fills such a row with the lowest float).  Inputs are finite;
+ * max / min compare with IEEE ==, so +0 and -0 are one value. */
+#define AMAR_AGG_SUM 0
+#define AMAR_AGG_MAX 1
+#define AMAR_AGG_MIN 2
+
+/* One GraphSAGE layer with aggregator `op`, fused like amar_sage_layer_f32 (one wavefront per row):
+ *     Y_i = ReLU( l2_normalize( [X_i || agg_i] . W[2F, C] + bias ) )
+ * F in {4,8,16,32}; C <= 64; other shapes AMAR_EUNSUPPORTED (amar_sage_aggregate_f32 + amar_sage_tail_f32). */
+int amar_sage_layer_agg_f32(const int32_t *rowptr, const int32_t *colidx,
+                            const float *X, int64_t ldx, int32_t F,
+                            const float *W, const float *bias, int32_t C,
+                            float *Y, int64_t ldy, int32_t self_loop, int32_t op,
+                            int32_t n_rows, amar_stream_t stream);
+
+/* The max / min aggregate alone: AGG[n_rows, F] (leading dimension lda) and, when CNT is not NULL, the training tape's
+ *     CNT[i, f] = number of entries j of row i with X[j, f] == AGG[i, f]      (exact small integers stored as float; ldc)
+ * F % 4 == 0, F <= 64 (else AMAR_EUNSUPPORTED); op = AMAR_AGG_MAX | AMAR_AGG_MIN (AMAR_AGG_SUM: AMAR_EUNSUPPORTED — the sum is
+ * amar_spmm_csr_f32 without values, plus the own row).  Both results are exact, hence bitwise reproducible. */
+int amar_sage_aggregate_f32(const int32_t *rowptr, const int32_t *colidx,
+                            const float *X, int64_t ldx, int32_t F,
+                            float *AGG, int64_t lda, float *CNT, int64_t ldc,
+                            int32_t self_loop, int32_t op, int32_t n_rows, amar_stream_t stream);
+
+/* Reverse pass of the max / min aggregate (TensorFlow's _UnsortedSegmentMinOrMaxGrad: every entry that attains the
+ * extremum, duplicates included, takes an equal share):
+ *     DX[j, f] += sum over entries (i <- j) of  [X[j, f] == AGG[i, f]] * DAGG[i, f] / CNT[i, f]
+ * The adjacency must be symmetric as a multiset (training.py requires it), so the entries INTO j are the entries OF row j: row j
+ * walks its own CSR row (+ itself when self_loop) and adds in a fixed order — no atomics, bitwise reproducible.
+ * pack: scratch of n_rows * 2F floats; a first launch writes [AGG_i | DAGG_i / CNT_i] there (0 where CNT is 0) so that a
+ * neighbour is one contiguous read.  F % 4 == 0, F <= 64.  DX is accumulated into. */
+int amar_sage_aggregate_bwd_f32(const int32_t *rowptr, const int32_t *colidx,
+                                const float *X, int64_t ldx, const float *AGG, int64_t lda,
+                                const float *CNT, int64_t ldc, const float *DAGG, int64_t ldg, int32_t F,
+                                float *pack, float *DX, int64_t lddx,
+                                int32_t self_loop, int32_t n_rows, amar_stream_t stream);
+
 /* One GAT layer, 1 head (Spektral 1.x GATConv._call_single, built at src/models/gnn.py:321-328):
  *     e_ij  = LeakyReLU_0.2( s_self[i] + s_neigh[j] ),  j in N(i) (+ i itself if self_loop)
  *     alpha = exp(e_ij - max_j e_ij) / ( sum_j exp(e_ij - max_j e_ij) + 1e-9 )
