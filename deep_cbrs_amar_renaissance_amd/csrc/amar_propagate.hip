@@ -1071,8 +1071,9 @@ __global__ __launch_bounds__(256) void colmax_kernel(const float *__restrict__ x
     __syncthreads();
     if (threadIdx.x == 0) {
         m = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
-        if (m >= 0.f) atomicMax(reinterpret_cast<int *>(out), __builtin_bit_cast(int, m));      // non-negative floats order like ints,
-        else atomicMin(reinterpret_cast<unsigned *>(out), __builtin_bit_cast(unsigned, m));     // negative ones like reversed unsigneds
+        // by SIGN BIT, not by value: -0.0f compares >= 0 but its int image is INT_MIN, which atomicMax could never put in place of -inf
+        if (!(__builtin_bit_cast(unsigned, m) >> 31)) atomicMax(reinterpret_cast<int *>(out), __builtin_bit_cast(int, m));   // sign clear: floats order like ints,
+        else atomicMin(reinterpret_cast<unsigned *>(out), __builtin_bit_cast(unsigned, m));     // sign set (-0 included): like reversed unsigneds
     }
 }
 

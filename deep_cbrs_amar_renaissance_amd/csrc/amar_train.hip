@@ -170,17 +170,26 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float *__restrict_
     }
 }
 
+// One Adam update, shared by adam_kernel / adam_dev_kernel / adam_multi_kernel: the three give the same bits on the same element (the
+// header's promise).  The fused products are written out and nothing else may be fused, so the bits do not depend on the kernel around it.
+struct AdamStep { float w, m, v; };
+__device__ __forceinline__ AdamStep adam_step(float wi, float g, float mi, float vi, float lr_t, float b1, float b2, float eps, float l2x2) {
+#pragma clang fp contract(off)
+    const float gi = fmaf(l2x2, wi, g);
+    AdamStep o;
+    o.m = fmaf(b1, mi, (1.f - b1) * gi);
+    o.v = fmaf(b2, vi, ((1.f - b2) * gi) * gi);
+    o.w = wi - (lr_t * o.m) / (sqrtf(o.v) + eps);
+    return o;
+}
+
 // keras.optimizers.Adam: m, v moments; lr_t carries the bias correction; the L2 regulariser's gradient 2*l2*w is folded in
 __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m,
                                                    float *__restrict__ v, int64_t n, float lr_t, float b1, float b2, float eps,
                                                    float l2x2) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float wi = w[i];
-        const float gi = g[i] + l2x2 * wi;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        w[i] = wi - lr_t * mi / (sqrtf(vi) + eps);
+        const AdamStep o = adam_step(w[i], g[i], m[i], v[i], lr_t, b1, b2, eps, l2x2);
+        m[i] = o.m; v[i] = o.v; w[i] = o.w;
     }
 }
 
@@ -388,12 +397,8 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float *__restrict__ w, co
                                                        float b2, float eps, float l2x2) {
     const float lr_t = state[1];
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float wi = w[i];
-        const float gi = g[i] + l2x2 * wi;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        w[i] = wi - lr_t * mi / (sqrtf(vi) + eps);
+        const AdamStep o = adam_step(w[i], g[i], m[i], v[i], lr_t, b1, b2, eps, l2x2);
+        m[i] = o.m; v[i] = o.v; w[i] = o.w;
     }
 }
 
@@ -544,10 +549,8 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const amar_adam_slot *_
     float wo[4], mo[4], vo[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const float gi = gs[r] + l2x2 * wi[r];
-        mo[r] = b1 * mi[r] + (1.f - b1) * gi;
-        vo[r] = b2 * vi[r] + (1.f - b2) * gi * gi;
-        wo[r] = wi[r] - lr_t * mo[r] / (sqrtf(vo[r]) + eps);
+        const AdamStep o = adam_step(wi[r], gs[r], mi[r], vi[r], lr_t, b1, b2, eps, l2x2);
+        mo[r] = o.m; vo[r] = o.v; wo[r] = o.w;
         if (idx[r] < sl.n) sq = fmaf(wi[r], wi[r], sq);
     }
     if (vec) {
