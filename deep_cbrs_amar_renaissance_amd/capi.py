@@ -86,6 +86,8 @@ SIGNATURES = {
     'amar_l2norm_bwd_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _I64, _I64, _I32, _I32, _P]),
     'amar_gat_bwd_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64,
                                         _I32, _I32, _P]),
+    'amar_gat_bwd_directed_f32': (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64,
+                                                 _I32, _I32, _P]),
     'amar_attention_mix_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I32, _P]),
     'amar_attention_mix_bwd_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _I32, _P]),
     'amar_add3_act_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I32, _I32, _P]),
@@ -103,6 +105,9 @@ SIGNATURES = {
                                                   ctypes.c_uint64, _P, _U32, _U32, _F32, _P]),
     'amar_gat_bwd_dropout_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64,
                                                 _I32, _I32, ctypes.c_uint64, _P, _U32, _U32, _F32, _P]),
+    'amar_gat_bwd_directed_dropout_f32': (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                         _I64, _I32, _I32, ctypes.c_uint64, _P, _U32, _U32, _F32, _P]),
+    'amar_csr_transpose_i32': (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     'amar_adam_multi_f32': (ctypes.c_int, [_P, _I32, _I64, _P, _F32, _F32, _F32, _F32, _P, _P]),
     'amar_sum_into_f32': (ctypes.c_int, [_P, _I64, _F32, _P, _P]),
     'amar_topk_segmented_f32': (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
@@ -501,7 +506,9 @@ def sage_aggregate(rowptr, colidx, X, agg, op, cnt=None, self_loop=True):
 
 def sage_aggregate_bwd(rowptr, colidx, X, agg, cnt, d_agg, dX, self_loop=True, pack=None):
     """dX[j] += the shares of d_agg that X[j] attained (ties and duplicate edges share equally): the reverse pass of
-    sage_aggregate on a symmetric edge multiset (amar_sage_aggregate_bwd_f32).  pack: [n_rows, 2F] scratch (allocated if None)."""
+    sage_aggregate (amar_sage_aggregate_bwd_f32).  rowptr / colidx: the TRANSPOSE of the structure the forward pass walked (row j
+    lists the targets whose aggregate X[j] entered; DeviceCSR.transposed() — the same arrays for a symmetric edge multiset).
+    pack: [n_rows, 2F] scratch (allocated if None)."""
     n_rows = rowptr.numel() - 1
     F = X.shape[1]
     for t, name in ((agg, 'agg'), (cnt, 'cnt'), (d_agg, 'd_agg'), (dX, 'dX')):
@@ -1280,7 +1287,8 @@ def dropout_advance(step):
 
 
 def gat_layer_dropout(rowptr, colidx, H, s_self, s_neigh, bias, Y, drop, self_loop=True):
-    """gat_layer with the attention coefficients dropped after the softmax (training); symmetric edge multiset, sorted columns."""
+    """gat_layer with the attention coefficients dropped after the softmax (training); sorted columns.  Entries (i, j, o) and
+    (j, i, o) share one bit (a symmetric multiset's two images of an edge; on a directed graph, a reciprocal pair)."""
     n_rows = rowptr.numel() - 1
     C = H.shape[1]
     if tuple(Y.shape) != (n_rows, C) or bias.numel() != C or s_self.numel() < n_rows or s_neigh.numel() < H.shape[0]:
@@ -1293,8 +1301,10 @@ def gat_layer_dropout(rowptr, colidx, H, s_self, s_neigh, bias, Y, drop, self_lo
     _check(code, 'amar_gat_layer_dropout_f32')
 
 
-def gat_bwd_dropout(rowptr, colidx, H, s_self, s_neigh, Y, dY, bias, a_self, a_neigh, drop, self_loop=True):
-    """Reverse of gat_layer_dropout with the regenerated bits. Returns (dout [n, C], ds [n], dt [n], dH [n, C])."""
+def gat_bwd_dropout(rowptr, colidx, H, s_self, s_neigh, Y, dY, bias, a_self, a_neigh, drop, self_loop=True, transposed=None):
+    """Reverse of gat_layer_dropout with the regenerated bits. Returns (dout [n, C], ds [n], dt [n], dH [n, C]).
+    transposed = (t_rowptr, t_colidx), the stable transpose of the structure, for an edge multiset that is not symmetric
+    (amar_gat_bwd_directed_dropout_f32); None: the structure is its own transpose."""
     n = rowptr.numel() - 1
     C = H.shape[1]
     if tuple(Y.shape) != (n, C) or tuple(dY.shape) != (n, C) or H.shape[0] != n or bias.numel() != C or \
@@ -1305,13 +1315,15 @@ def gat_bwd_dropout(rowptr, colidx, H, s_self, s_neigh, Y, dY, bias, a_self, a_n
     scratch = torch.empty(3 * n, dtype=torch.float32, device=dev)
     ds, dt = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
     dH = torch.empty((n, C), dtype=torch.float32, device=dev)
-    code = load().amar_gat_bwd_dropout_f32(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), _ptr(H, torch.float32, 'H'), _ld(H, 'H'), C,
+    name = 'amar_gat_bwd_dropout_f32' if transposed is None else 'amar_gat_bwd_directed_dropout_f32'
+    code = getattr(load(), name)(
+        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), *_transposed_ptrs(transposed, n, colidx),
+        _ptr(H, torch.float32, 'H'), _ld(H, 'H'), C,
         _ptr(s_self, torch.float32, 's_self'), _ptr(s_neigh, torch.float32, 's_neigh'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
         _ptr(dY, torch.float32, 'dY'), _ld(dY, 'dY'), _ptr(bias, torch.float32, 'bias'), _ptr(a_self, torch.float32, 'a_self'),
         _ptr(a_neigh, torch.float32, 'a_neigh'), _ptr(dout), _ptr(scratch), _ptr(ds), _ptr(dt), _ptr(dH), C,
         1 if self_loop else 0, n, *drop._args(), _stream())
-    _check(code, 'amar_gat_bwd_dropout_f32')
+    _check(code, name)
     return dout, ds, dt, dH
 
 
@@ -1363,8 +1375,19 @@ def l2norm_bwd(dy, nrm, inv, dz, act='relu'):
     _check(code, 'amar_l2norm_bwd_f32')
 
 
-def gat_bwd(rowptr, colidx, H, s_self, s_neigh, Y, dY, bias, a_self, a_neigh, self_loop=True):
-    """Reverse of gat_layer. Returns (dout [n, C], ds [n], dt [n], dH [n, C])."""
+def _transposed_ptrs(transposed, n, colidx):
+    """The two extra pointers of the `directed` GAT reverse entry points (nothing for the symmetric ones)."""
+    if transposed is None:
+        return ()
+    t_rowptr, t_colidx = transposed
+    if t_rowptr.numel() != n + 1 or t_colidx.numel() != colidx.numel():
+        raise ValueError("gat_bwd: transposed = (t_rowptr [n + 1], t_colidx [nnz]) of the same square structure expected")
+    return _ptr(t_rowptr, torch.int32, 't_rowptr'), _ptr_entries(t_colidx, torch.int32, 't_colidx')
+
+
+def gat_bwd(rowptr, colidx, H, s_self, s_neigh, Y, dY, bias, a_self, a_neigh, self_loop=True, transposed=None):
+    """Reverse of gat_layer. Returns (dout [n, C], ds [n], dt [n], dH [n, C]).  transposed = (t_rowptr, t_colidx): as
+    gat_bwd_dropout (amar_gat_bwd_directed_f32)."""
     n = rowptr.numel() - 1
     C = H.shape[1]
     if tuple(Y.shape) != (n, C) or tuple(dY.shape) != (n, C) or H.shape[0] != n or bias.numel() != C or \
@@ -1375,14 +1398,42 @@ def gat_bwd(rowptr, colidx, H, s_self, s_neigh, Y, dY, bias, a_self, a_neigh, se
     scratch = torch.empty(3 * n, dtype=torch.float32, device=dev)
     ds, dt = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
     dH = torch.empty((n, C), dtype=torch.float32, device=dev)
-    code = load().amar_gat_bwd_f32(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), _ptr(H, torch.float32, 'H'), _ld(H, 'H'), C,
+    name = 'amar_gat_bwd_f32' if transposed is None else 'amar_gat_bwd_directed_f32'
+    code = getattr(load(), name)(
+        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), *_transposed_ptrs(transposed, n, colidx),
+        _ptr(H, torch.float32, 'H'), _ld(H, 'H'), C,
         _ptr(s_self, torch.float32, 's_self'), _ptr(s_neigh, torch.float32, 's_neigh'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
         _ptr(dY, torch.float32, 'dY'), _ld(dY, 'dY'), _ptr(bias, torch.float32, 'bias'), _ptr(a_self, torch.float32, 'a_self'),
         _ptr(a_neigh, torch.float32, 'a_neigh'), _ptr(dout), _ptr(scratch), _ptr(ds), _ptr(dt), _ptr(dH), C,
         1 if self_loop else 0, n, _stream())
-    _check(code, 'amar_gat_bwd_f32')
+    _check(code, name)
     return dout, ds, dt, dH
+
+
+def csr_transpose(rowptr, colidx, n_cols):
+    """The stable transpose of an int32 CSR structure [n_rows, n_cols] (amar_csr_transpose_i32): returns (t_rowptr [n_cols + 1],
+    t_colidx [nnz], perm [nnz]) with perm[q] = the input position of the entry at output position q — inside an output row the
+    entries keep the order of their input positions, so values and multiplicities follow as vals[perm].  Same bits on every run.
+    Checks the structure first (two host reads; this runs once per graph, never inside a captured graph)."""
+    n_rows, n_cols, nnz = int(rowptr.numel()) - 1, int(n_cols), int(colidx.numel())
+    if n_rows < 0 or n_cols < 0:
+        raise ValueError("csr_transpose: rowptr [n_rows + 1] and n_cols >= 0 expected")
+    dev = rowptr.device
+    _ptr(rowptr, torch.int32, 'rowptr'), _ptr(colidx, torch.int32, 'colidx')
+    if int(rowptr[0]) != 0 or int(rowptr[-1]) != nnz:
+        raise ValueError("csr_transpose: rowptr must run from 0 to nnz")
+    if nnz and (n_rows < 1 or bool((rowptr[1:] < rowptr[:-1]).any()) or int(colidx.min()) < 0 or int(colidx.max()) >= n_cols):
+        raise ValueError("csr_transpose: rowptr must not decrease and every column must lie in [0, n_cols)")
+    t_rowptr = torch.empty(n_cols + 1, dtype=torch.int32, device=dev)
+    t_colidx = torch.empty(nnz, dtype=torch.int32, device=dev)
+    perm = torch.empty(nnz, dtype=torch.int32, device=dev)
+    cursor = torch.empty(max(n_cols, 1), dtype=torch.int32, device=dev)
+    code = load().amar_csr_transpose_i32(
+        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), n_rows, n_cols, nnz,
+        _ptr(t_rowptr, torch.int32, 't_rowptr'), _ptr_entries(t_colidx, torch.int32, 't_colidx'), _ptr_entries(perm, torch.int32, 'perm'),
+        _ptr(cursor, torch.int32, 'cursor'), _stream())
+    _check(code, 'amar_csr_transpose_i32')
+    return t_rowptr, t_colidx, perm
 
 
 def attention_mix(a, b, ta, tb, out):

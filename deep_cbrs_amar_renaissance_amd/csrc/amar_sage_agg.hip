@@ -8,7 +8,8 @@
 //   sage_agg_row_kernel   the fused inference layer: gather-reduce, then [x || agg] . W + b, l2-normalise, ReLU in registers
 //   sage_agg_kernel       the aggregate alone for any F % 4 == 0, F <= 64, with the tie count the reverse pass divides by
 //   sage_agg_pack_kernel  [agg_i | d_agg_i / cnt_i] as one row of 2F floats
-//   sage_agg_bwd_kernel   row j walks its own CSR row (the edge multiset is symmetric) and adds the shares it attained
+//   sage_agg_bwd_kernel   row j walks the targets that list it — row j of the TRANSPOSED structure (its own row where the edge
+//                         multiset is symmetric) — and adds the shares it attained
 //
 // max / min / counts are exact and the reverse pass adds in a fixed order: every result is bitwise reproducible.  No atomics.
 // Reference semantics: see include/amar_hip.h.

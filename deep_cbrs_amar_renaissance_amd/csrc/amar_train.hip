@@ -252,10 +252,12 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float *__restrict
 // g_i = dL/dout_i (ReLU mask applied):   d alpha_ij = g_i . h_j,   sum_k alpha_ik d alpha_ik = g_i . (out_i - b) =: c_i,
 //   d e_ij = alpha_ij (d alpha_ij - c_i),  d pre_ij = d e_ij * LeakyReLU'(s_i + t_j),
 //   ds_i = sum_j d pre_ij,   dt_j = sum_i d pre_ij,   dh_j = sum_i alpha_ij g_i + ds_j a_self + dt_j a_neigh.
-// The edge multiset is symmetric, so "targets i that have j as a source" is CSR row j: both sums run row-wise, one
-// wavefront per node, without float atomics.  Kernel 1 (node as target) recomputes the softmax statistics.
+// Both sums run row-wise, one wavefront per node, without float atomics: kernel 1 (node as target) walks row i of A and recomputes
+// the softmax statistics; kernel 2 (node as source) needs "the targets i that have j as a source", which is row j of A^T
+// (t_rowptr / t_colidx: the stable transpose, amar_csr_transpose_i32).  For a symmetric edge multiset A^T = A and the entry
+// points without `directed` pass the one structure twice.
 struct GatBwdArgs {
-    const int32_t *rowptr; const int32_t *colidx; const float *H; int64_t ldh; const float *s_self; const float *s_neigh;
+    const int32_t *rowptr; const int32_t *colidx; const int32_t *t_rowptr; const int32_t *t_colidx; const float *H; int64_t ldh; const float *s_self; const float *s_neigh;
     const float *Y; int64_t ldy; const float *dY; int64_t ldd; const float *bias; const float *a_self; const float *a_neigh;
     float *dout; float *row_max; float *row_inv; float *row_c; float *ds; float *dt; float *dH; int64_t lddh;
     int self_loop; int n_rows; int C;
@@ -276,7 +278,7 @@ __device__ __forceinline__ float group_sum(float v) {               // over the 
 // DROP (attention dropout, forward out_i = sum_j alpha_ij m_ij h_j + b with m_ij = keep_ij * scale regenerated from the entry's
 // identity): d alpha_ij = m_ij (g_i . h_j) feeds the unchanged softmax reverse (c_i = g_i . (out_i - b) still is
 // sum_k alpha_ik d alpha_ik), and dh_j accumulates alpha_ij m_ij g_i.  The source walk sees entry (i, j, o) as entry (j, i, o) of
-// row j: same ordinal (the multiset is symmetric, columns sorted), so the same bit.
+// row j of A^T: same ordinal (the stable transpose keeps the order of parallel entries, columns sorted), so the same bit.
 template <int LPN, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_bwd_target_kernel(const GatBwdArgs a) {
     constexpr int NS = AMAR_WAVE / LPN;
@@ -335,7 +337,7 @@ __global__ __launch_bounds__(256) void gat_bwd_source_kernel(const GatBwdArgs a)
     if (row >= a.n_rows) return;
     const int q = lane % LPN, slot = lane / LPN;
     const bool live = 4 * q < C;
-    const int beg = a.rowptr[row], end = a.rowptr[row + 1];
+    const int beg = a.t_rowptr[row], end = a.t_rowptr[row + 1];
     const float tj = a.s_neigh[row];
     const float4 h = live ? *reinterpret_cast<const float4 *>(a.H + (int64_t)row * a.ldh + 4 * q) : f4_zero();
     float4 acc = f4_zero();
@@ -354,8 +356,8 @@ __global__ __launch_bounds__(256) void gat_bwd_source_kernel(const GatBwdArgs a)
         if (q == 0) dt += dpre;
     };
     for (int p = beg + slot; p < end; p += NS) {
-        const int i = a.colidx[p];
-        edge(i, DROP ? edge_ordinal(a.colidx, beg, p, i) : 0);
+        const int i = a.t_colidx[p];
+        edge(i, DROP ? edge_ordinal(a.t_colidx, beg, p, i) : 0);
     }
     if (a.self_loop && slot == 0) edge(row, 255);
     acc = f4_wave_sum_stride<LPN>(acc);
@@ -1728,19 +1730,20 @@ int amar_l2norm_bwd_f32(const float *dY, int64_t ldd, const float *Nrm, int64_t 
     return amar_check_launch();
 }
 
-static int gat_bwd_launch(const int32_t *rowptr, const int32_t *colidx, const float *H, int64_t ldh, int32_t C,
+static int gat_bwd_launch(const int32_t *rowptr, const int32_t *colidx, const int32_t *t_rowptr, const int32_t *t_colidx,
+                          const float *H, int64_t ldh, int32_t C,
                           const float *s_self, const float *s_neigh, const float *Y, int64_t ldy, const float *dY, int64_t ldd,
                           const float *bias, const float *a_self, const float *a_neigh,
                           float *dout, float *row_scratch, float *ds, float *dt, float *dH, int64_t lddh,
                           int32_t self_loop, int32_t n_rows, const AmarDropout *drop, amar_stream_t stream) {
-    if (n_rows < 0 || !rowptr || !H || !s_self || !s_neigh || !Y || !dY || !bias || !a_self || !a_neigh || !dout ||
+    if (n_rows < 0 || !rowptr || !t_rowptr || !H || !s_self || !s_neigh || !Y || !dY || !bias || !a_self || !a_neigh || !dout ||
         !row_scratch || !ds || !dt || !dH) return AMAR_EINVAL;
     if (ldh < C || ldy < C || ldd < C || lddh < C || (ldh & 3) || (ldy & 3) || (ldd & 3) || (lddh & 3)) return AMAR_EINVAL;
     if (!amar_aligned16(H) || !amar_aligned16(Y) || !amar_aligned16(dY) || !amar_aligned16(bias) || !amar_aligned16(a_self) ||
         !amar_aligned16(a_neigh) || !amar_aligned16(dout) || !amar_aligned16(dH)) return AMAR_EINVAL;
     if (n_rows == 0) return AMAR_OK;
-    if (!colidx) return AMAR_EINVAL;
-    GatBwdArgs a{rowptr, colidx, H, ldh, s_self, s_neigh, Y, ldy, dY, ldd, bias, a_self, a_neigh, dout,
+    if (!colidx || !t_colidx) return AMAR_EINVAL;
+    GatBwdArgs a{rowptr, colidx, t_rowptr, t_colidx, H, ldh, s_self, s_neigh, Y, ldy, dY, ldd, bias, a_self, a_neigh, dout,
                  row_scratch, row_scratch + n_rows, row_scratch + 2 * (int64_t)n_rows, ds, dt, dH, lddh, self_loop ? 1 : 0, n_rows, C,
                  drop ? *drop : AmarDropout{}};
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1758,7 +1761,7 @@ int amar_gat_bwd_f32(const int32_t *rowptr, const int32_t *colidx, const float *
                      const float *bias, const float *a_self, const float *a_neigh,
                      float *dout, float *row_scratch, float *ds, float *dt, float *dH, int64_t lddh,
                      int32_t self_loop, int32_t n_rows, amar_stream_t stream) {
-    return gat_bwd_launch(rowptr, colidx, H, ldh, C, s_self, s_neigh, Y, ldy, dY, ldd, bias, a_self, a_neigh, dout, row_scratch, ds, dt,
+    return gat_bwd_launch(rowptr, colidx, rowptr, colidx, H, ldh, C, s_self, s_neigh, Y, ldy, dY, ldd, bias, a_self, a_neigh, dout, row_scratch, ds, dt,
                           dH, lddh, self_loop, n_rows, nullptr, stream);
 }
 
@@ -1771,8 +1774,32 @@ int amar_gat_bwd_dropout_f32(const int32_t *rowptr, const int32_t *colidx, const
     if (!step || site < 1 || site > 255 || !(scale >= 1.f) || scale > 3.0e38f) return AMAR_EINVAL;
     if (n_rows > AMAR_DROPOUT_MAX_NODES) return AMAR_EUNSUPPORTED;
     const AmarDropout d{(uint32_t)seed, (uint32_t)(seed >> 32), step, site, threshold, scale};
-    return gat_bwd_launch(rowptr, colidx, H, ldh, C, s_self, s_neigh, Y, ldy, dY, ldd, bias, a_self, a_neigh, dout, row_scratch, ds, dt,
+    return gat_bwd_launch(rowptr, colidx, rowptr, colidx, H, ldh, C, s_self, s_neigh, Y, ldy, dY, ldd, bias, a_self, a_neigh, dout, row_scratch, ds, dt,
                           dH, lddh, self_loop, n_rows, &d, stream);
+}
+
+int amar_gat_bwd_directed_f32(const int32_t *rowptr, const int32_t *colidx, const int32_t *t_rowptr, const int32_t *t_colidx,
+                              const float *H, int64_t ldh, int32_t C,
+                              const float *s_self, const float *s_neigh, const float *Y, int64_t ldy, const float *dY, int64_t ldd,
+                              const float *bias, const float *a_self, const float *a_neigh,
+                              float *dout, float *row_scratch, float *ds, float *dt, float *dH, int64_t lddh,
+                              int32_t self_loop, int32_t n_rows, amar_stream_t stream) {
+    return gat_bwd_launch(rowptr, colidx, t_rowptr, t_colidx, H, ldh, C, s_self, s_neigh, Y, ldy, dY, ldd, bias, a_self, a_neigh, dout,
+                          row_scratch, ds, dt, dH, lddh, self_loop, n_rows, nullptr, stream);
+}
+
+int amar_gat_bwd_directed_dropout_f32(const int32_t *rowptr, const int32_t *colidx, const int32_t *t_rowptr, const int32_t *t_colidx,
+                                      const float *H, int64_t ldh, int32_t C,
+                                      const float *s_self, const float *s_neigh, const float *Y, int64_t ldy, const float *dY, int64_t ldd,
+                                      const float *bias, const float *a_self, const float *a_neigh,
+                                      float *dout, float *row_scratch, float *ds, float *dt, float *dH, int64_t lddh,
+                                      int32_t self_loop, int32_t n_rows,
+                                      uint64_t seed, const uint64_t *step, uint32_t site, uint32_t threshold, float scale, amar_stream_t stream) {
+    if (!step || site < 1 || site > 255 || !(scale >= 1.f) || scale > 3.0e38f) return AMAR_EINVAL;
+    if (n_rows > AMAR_DROPOUT_MAX_NODES) return AMAR_EUNSUPPORTED;
+    const AmarDropout d{(uint32_t)seed, (uint32_t)(seed >> 32), step, site, threshold, scale};
+    return gat_bwd_launch(rowptr, colidx, t_rowptr, t_colidx, H, ldh, C, s_self, s_neigh, Y, ldy, dY, ldd, bias, a_self, a_neigh, dout,
+                          row_scratch, ds, dt, dH, lddh, self_loop, n_rows, &d, stream);
 }
 
 int amar_attention_mix_f32(const float *A, int64_t lda, const float *B, int64_t ldb, const float *TA, int64_t ldta,

@@ -18,6 +18,7 @@ propagation on a node table that is (partly) handed in by the caller.
 import abc
 
 import torch
+from scipy import sparse
 
 from deep_cbrs_amar_renaissance_amd import capi
 from deep_cbrs_amar_renaissance_amd.engine import Model, L2
@@ -61,6 +62,12 @@ class SequentialGNN(Model):
         self.cache_neighbours = cache_neighbours
         # GraphSAGE / GAT ignore edge values and add their own self loop
         edge_list = any(isinstance(l, (GraphSageConv, GATConv)) for l in seq_layers)
+        if edge_list and sparse.issparse(adj_matrix) and adj_matrix.shape[0] == adj_matrix.shape[1] and (adj_matrix != adj_matrix.T).nnz:
+            # Spektral's message passing reads an entry (r, c) as "source r sends to target c" (targets = indices[:, 1]); the row
+            # kernels aggregate row i over its columns, so on a directed graph (dataset.symmetric_adjacency: False) they walk the
+            # transposed list.  A symmetric list is its own transpose and is taken as it comes.  (A DeviceCSR handed in is taken
+            # as the structure the kernels walk: row i lists the sources of target i.)
+            adj_matrix = adj_matrix.T
         self.adj_matrix = convert_to_tensor(adj_matrix, with_values=not edge_list, drop_diagonal=edge_list)
         rate = capi.check_dropout_rate(dropout, 'dropout')
         self.dropout = rate if rate > 0.0 else None            # applied by training.py; calling the stack is inference (identity)

@@ -8,19 +8,20 @@ Adam (`config.yaml:52-56`; Keras defaults beta_2 = 0.999, epsilon = 1e-7).
 
 Forward activations come from the same HIP kernels as inference; the reverse pass uses the
 training kernels of `csrc/amar_train.hip` (activation backward, two-stage deterministic weight
-gradients, row scatter-add for the embedding lookup, Adam) and reuses the forward SpMM for
-A_hat^T . dZ (A_hat is symmetric) and the forward GEMM for dX = dZ . W^T.
+gradients, row scatter-add for the embedding lookup, Adam) and reuses the forward SpMM, on the transposed image of the
+graph (`DeviceCSR.transposed()`: the matrix itself where it is symmetric, `dataset.symmetric_adjacency: True`; else the stable
+device transpose), for A_hat^T . dZ, and the forward GEMM for dX = dZ . W^T.
 
 Implemented for GCN, GraphSAGE, GAT, LightGCN and DGCF stacks under every reduction ('concatenation', 'mean', 'sum',
 'w-sum', 'last'), alone (models/gnn.py) or chained as TwoStep / TwoWay models (models/tsgnn.py, twgnn.py): `_StackTape` is the
 forward-with-kept-activations + reverse pass of ONE stack, and the Trainer chains the tapes the way the model chains the
 stacks (the gradient of a stack's leading rows is lifted back to its full node table).  GraphSAGE trains on an unfused
-forward that keeps what the reverse pass needs ([x || mean] and the normalised pre-activation); its aggregate
-(A + I) / count is symmetric up to the row scale, so the reverse aggregate is the same value-free SpMM.  The hybrid head
+forward that keeps what the reverse pass needs ([x || mean] and the normalised pre-activation); its aggregate is
+(A + I) / count, so the reverse aggregate is the row scale (A's counts) followed by the value-free SpMM on A^T.  The hybrid head
 (HybridCBRS: 'concatenate' / 'attention' fusion, residual classifier, both feature_based settings) trains on the same
 Dense tapes; its BERT inputs are constants.  GAT (1 head) trains on the inference kernels plus `amar_gat_bwd_f32`, which
-forms the softmax / attention-scalar gradients row-wise for both edge directions (symmetric edge multiset, no float
-atomics).
+forms the softmax / attention-scalar gradients row-wise for both edge directions (targets on A's rows, sources on A^T's rows:
+`amar_gat_bwd_directed_f32` where the two differ; no float atomics).
 """
 import itertools
 import os
@@ -357,8 +358,9 @@ class _StackTape:
 
     Every layer's output lives in a column slice of one [N, sum(widths)] buffer `cat`; the reduction (reduction.py:9-33)
     is undone first (d_cat = d_out for 'concatenation', d_out / (L+1) per slice for 'mean', ...), then the layers run
-    in reverse on the slices of (cat, d_cat).  All adjacency images are symmetric (config.yaml:36), so A^T . g reuses
-    the forward SpMM."""
+    in reverse on the slices of (cat, d_cat).  `at` = the transposed image of the stack's graph, taken once here (before any
+    capture; the tape keeps it and its images alive): every product or walk that needs A^T uses it.  For a symmetric graph
+    (config.yaml:36) `at is a` and the reverse pass reuses the forward structure."""
 
     KINDS = ((GCNConv, 'gcn'), (LightGCNConv, 'lightgcn'), (GraphSageConv, 'sage'), (GATConv, 'gat'), (DGCFConv, 'dgcf'))
 
@@ -376,6 +378,7 @@ class _StackTape:
             self.self_loops, self.aggregate = bool(layers[0].self_loops), layers[0].aggregate
             # 'mean': sum / count (0 for an empty segment), 'sum': sum * 1 — the layer's cached vector; max / min keep a tie count instead
             self.inv_cnt = layers[0].row_scale(seq.adj_matrix) if self.aggregate in ('mean', 'sum') else None
+        self.at = seq.adj_matrix.transposed()                        # A^T: the graph itself where it is symmetric
         self.cat = self.tape = None
         self._workspaces = {}
         self.defer_reduce = False
@@ -506,18 +509,18 @@ class _StackTape:
     def backward(self, d_out, grads):
         """Fills `grads` for the layers' weights; returns d(loss)/d(node table) [N, widths[0]] (a fresh buffer).
         `d_out` is consumed (it may be modified in place)."""
-        seq, a = self.seq, self.seq.adj_matrix
+        seq, a, at = self.seq, self.seq.adj_matrix, self.at
         layers, widths = list(seq.seq_layers), self.widths
         n, dev = d_out.shape[0], d_out.device
         if self.kind == 'lightgcn' and self.cat is None:
-            # running-sum route ('mean'): g0 = (I + A + A^2 + ...) d_out / (L + 1)
+            # running-sum route ('mean'): g0 = (I + A^T + (A^T)^2 + ...) d_out / (L + 1)
             n_terms = len(layers) + 1
             g0 = torch.zeros((n, widths[0]), dtype=torch.float32, device=dev)
             capi.add_inplace(g0, d_out, 1.0 / n_terms)
             acc = g0.clone()
             for _ in layers:
                 nxt = torch.empty_like(acc)
-                _spmm(a, acc, nxt)
+                _spmm(at, acc, nxt)
                 capi.add_inplace(g0, nxt)
                 acc = nxt
             return g0
@@ -540,7 +543,7 @@ class _StackTape:
                 else:
                     capi.act_bwd(dsl(k + 1), sl(k + 1), dzk, 'relu')
                 dh = torch.empty((n, c), dtype=torch.float32, device=dev)
-                _spmm(a, dzk, dh)                                     # A_hat^T = A_hat
+                _spmm(at, dzk, dh)                                    # A_hat^T . dZ
                 if fused:                                             # dW = X_k^T . dH, and dH . W^T added straight into the slice's gradient
                     lazy = capi.dense_bwd(sl(k), None, dh, layer.kernel.detach(), None, self._workspace(k, n, f, c, dev), dX=dsl(k), dW=dw,
                                           defer=self.defer_reduce, accumulate_dx=True)
@@ -555,7 +558,7 @@ class _StackTape:
                 grads[layer.kernel], grads[layer.bias] = dw, db
             elif self.kind == 'lightgcn':
                 back = torch.empty((n, f), dtype=torch.float32, device=dev)
-                _spmm(a, dsl(k + 1), back)
+                _spmm(at, dsl(k + 1), back)
                 capi.add_inplace(dsl(k), back)
             elif self.kind == 'sage':
                 xa, nrm, inv, cnt = self.tape[k]
@@ -574,13 +577,13 @@ class _StackTape:
                 grads[layer.kernel], grads[layer.bias] = dw, db
                 capi.add_inplace(dsl(k), dxa[:, :f])
                 if cnt is not None:
-                    # every entry that attains the extremum takes d_agg / cnt; row j finds its shares on its own CSR row (symmetric multiset)
-                    capi.sage_aggregate_bwd(a.rowptr, a.colidx, xa[:, :f], xa[:, f:], cnt, dxa[:, f:], dsl(k), self_loop=self.self_loops)
+                    # every entry that attains the extremum takes d_agg / cnt; row j finds its shares on the targets that list it: A^T's row j
+                    capi.sage_aggregate_bwd(at.rowptr, at.colidx, xa[:, :f], xa[:, f:], cnt, dxa[:, f:], dsl(k), self_loop=self.self_loops)
                 else:
                     g = torch.empty((n, f), dtype=torch.float32, device=dev)
-                    capi.row_affine(dxa[:, f:], self.inv_cnt, g)           # d(mean)/d(sum); 'sum': a copy
+                    capi.row_affine(dxa[:, f:], self.inv_cnt, g)           # d(mean)/d(sum) by A's row counts; 'sum': a copy
                     back = torch.empty((n, f), dtype=torch.float32, device=dev)
-                    capi.spmm_csr(a.rowptr, a.colidx, None, g, back)       # the edge multiset is symmetric
+                    capi.spmm_csr(at.rowptr, at.colidx, None, g, back)     # A^T . g
                     capi.add_inplace(dsl(k), back)
                     if self.self_loops:
                         capi.add_inplace(dsl(k), g)
@@ -590,10 +593,12 @@ class _StackTape:
                 edge = self.edge_drop[k] if self.edge_drop is not None else None
                 gat_args = (a.rowptr, a.colidx, h, s_self, s_neigh, y, dsl(k + 1), layer.bias,
                             layer.attn_kernel_self.detach().view(c), layer.attn_kernel_neighs.detach().view(c))
+                # targets walk A's rows, sources A^T's (one structure where the edge multiset is symmetric)
+                transposed = (at.rowptr, at.colidx) if at is not a else None
                 if edge is not None:
-                    dout, ds, dt, dh = capi.gat_bwd_dropout(*gat_args, edge, self_loop=layer.add_self_loops)
+                    dout, ds, dt, dh = capi.gat_bwd_dropout(*gat_args, edge, self_loop=layer.add_self_loops, transposed=transposed)
                 else:
-                    dout, ds, dt, dh = capi.gat_bwd(*gat_args, self_loop=layer.add_self_loops)
+                    dout, ds, dt, dh = capi.gat_bwd(*gat_args, self_loop=layer.add_self_loops, transposed=transposed)
                 db = torch.empty_like(layer.bias)
                 das, dan = torch.empty((c, 1), dtype=torch.float32, device=dev), torch.empty((c, 1), dtype=torch.float32, device=dev)
                 fused = capi.dense_bwd_enabled() and capi.dense_bwd_supported(f, c) and n > 0
@@ -625,7 +630,7 @@ class _StackTape:
                 grads[layer.attn_kernel_neighs] = dan if isinstance(dan, capi.DeferredGradient) else dan.view_as(layer.attn_kernel_neighs)
             else:                                                    # dgcf
                 back = torch.empty((n, f), dtype=torch.float32, device=dev)
-                _spmm(a, dsl(k + 1), back)                # A_dgcf is symmetric
+                _spmm(at, dsl(k + 1), back)               # A_dgcf^T . d(out)
                 dw = torch.empty(n, dtype=torch.float32, device=dev)
                 capi.locality_scale_bwd(back, sl(k), layer.w.detach().view(-1), dsl(k), dw, accumulate=True)
                 grads[layer.w] = dw.view_as(layer.w)
@@ -633,18 +638,6 @@ class _StackTape:
         capi.copy_columns(dsl(0), g0)
         self.tape = self.cat = None
         return g0
-
-
-def _require_symmetric(a):
-    """The reverse pass of every stack reuses the forward product (or edge list) as its transpose: A^T = A.  That holds for
-    `dataset.symmetric_adjacency: True` (config.yaml:36, every econfig); with False (preprocess.py:91 returns the
-    un-symmetrised matrix) the gradients would be silently wrong, so such a graph is refused.  One host check per graph."""
-    if getattr(a, '_symmetric_checked', None) is None:
-        m = a.to_scipy()
-        a._symmetric_checked = m.shape[0] == m.shape[1] and abs(m - m.T).max() <= 1e-6 * max(abs(m).max(), 1e-30)
-    if not a._symmetric_checked:
-        raise NotImplementedError("training needs a symmetric adjacency matrix (dataset.symmetric_adjacency: True): the reverse "
-                                  "pass multiplies by A where A^T is due")
 
 
 class DeviceSampler:
@@ -694,8 +687,6 @@ class Trainer:
             self.layout, stacks = 'two_way', [gnn.way_one_gnn_layers, gnn.way_two_gnn_layers, gnn.step_two_gnn_layers]
         else:
             raise NotImplementedError("no training recipe for {}".format(type(gnn).__name__))
-        for seq_ in stacks:
-            _require_symmetric(seq_.adj_matrix)
         self.tapes = [_StackTape(seq) for seq in stacks]
         self.kind = self.tapes[-1].kind
         seq = stacks[-1]

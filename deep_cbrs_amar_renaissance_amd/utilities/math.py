@@ -112,6 +112,37 @@ class DeviceCSR:
         return sparse.csr_matrix((vals, colidx, rowptr), shape=self.shape)
 
 
+    def is_symmetric(self):
+        """Whether A^T = A (square, and |A - A^T| <= 1e-6 max|A| with parallel entries summed) — what `dataset.symmetric_adjacency: True`
+        (config.yaml:36) produces.  One host check per graph, cached on the object."""
+        if '_symmetric' not in self.__dict__:
+            m = self.to_scipy()
+            self.__dict__['_symmetric'] = bool(m.shape[0] == m.shape[1] and abs(m - m.T).max() <= 1e-6 * max(abs(m).max(), 1e-30))
+        return self.__dict__['_symmetric']
+
+    def transposed(self):
+        """A^T as a DeviceCSR — what a reverse pass multiplies by (or walks) where the forward pass used A.  A symmetric matrix
+        is its own transpose: `self`, and no kernel runs.  Otherwise the stable transpose built on the device (capi.csr_transpose:
+        inside a row of A^T the entries keep their order in A, so sorted columns stay sorted and parallel entries keep their
+        ordinals), values and multiplicities gathered through its permutation (kept as `perm`), cached on the object.  A
+        gcn-filtered matrix hands its factors over unchanged: A_hat^T[j, i] = dinv[j] . mult . dinv[i] with the SAME vector — the
+        degrees are A's row sums on both sides (degrees recomputed from A^T would belong to another matrix).  The result is an
+        ordinary DeviceCSR: spmm_kind and the XS / SJ / LDS-tiled images apply to it by their own rules."""
+        if '_transposed' not in self.__dict__:
+            if self.is_symmetric():
+                self.__dict__['_transposed'] = self
+            else:
+                from deep_cbrs_amar_renaissance_amd import capi
+                t_rowptr, t_colidx, perm = capi.csr_transpose(self.rowptr, self.colidx, self.shape[1])
+                gather = perm.long()
+                t = DeviceCSR(t_rowptr, t_colidx, self.vals[gather] if self.vals is not None else None, (self.shape[1], self.shape[0]),
+                              gcn_filtered=self.gcn_filtered, dinv=self.dinv, mult=self.mult[gather] if self.mult is not None else None)
+                t.perm = perm
+                t.__dict__['_symmetric'], t.__dict__['_transposed'] = False, self
+                self.__dict__['_transposed'] = t
+        return self.__dict__['_transposed']
+
+
 def sparse_matrix_to_tensor(x, dtype=torch.float32, **kwargs):
     """scipy sparse -> :class:`DeviceCSR` (row-major order, duplicates kept)."""
     assert sparse.issparse(x), "The input matrix should be sparse"

@@ -227,8 +227,9 @@ int amar_sage_aggregate_f32(const int32_t *rowptr, const int32_t *colidx,
 /* Reverse pass of the max / min aggregate (TensorFlow's _UnsortedSegmentMinOrMaxGrad: every entry that attains the
  * extremum, duplicates included, takes an equal share):
  *     DX[j, f] += sum over entries (i <- j) of  [X[j, f] == AGG[i, f]] * DAGG[i, f] / CNT[i, f]
- * The adjacency must be symmetric as a multiset (training.py requires it), so the entries INTO j are the entries OF row j: row j
- * walks its own CSR row (+ itself when self_loop) and adds in a fixed order — no atomics, bitwise reproducible.
+ * rowptr / colidx here are the structure whose row j lists the entries INTO j — the TRANSPOSE of the one the forward pass walked
+ * (the stable transpose of the csr-transpose entry point; the same arrays where the edge multiset is symmetric): row j walks that row
+ * (+ itself when self_loop) and adds in a fixed order — no atomics, bitwise reproducible.
  * pack: scratch of n_rows * 2F floats; a first launch writes [AGG_i | DAGG_i / CNT_i] there (0 where CNT is 0) so that a
  * neighbour is one contiguous read.  F % 4 == 0, F <= 64.  DX is accumulated into. */
 int amar_sage_aggregate_bwd_f32(const int32_t *rowptr, const int32_t *colidx,
@@ -455,7 +456,8 @@ int amar_locality_scale_bwd_f32(const float *dOut, int64_t ldd, const float *X, 
  * What Keras' fit() adds around the forward path for one batch (src/experiment.py:155-188, config.yaml:50-58):
  * reverse-mode derivatives of Dense / GCNConv / LightGCNConv / embedding_lookup, binary cross-entropy,
  * L2 regularisers (src/models/gnn.py:45,293-294) and the Adam update.  The forward kernels above are reused
- * (A_hat is symmetric, so the SpMM is its own transpose; dX = dZ . W^T is amar_dense_f32 on the transposed kernel).
+ * (the SpMM on the transposed image of A_hat — A_hat itself where it is symmetric; dX = dZ . W^T is amar_dense_f32 on the
+ * transposed kernel).
  *
  * amar_act_bwd_f32          dZ = dY * act'(Y)        (Y = the layer's OUTPUT; relu / sigmoid / none)
  * amar_wgrad_f32            dW[K,N] = X^T . dZ and/or db[N] = column sums of dZ, reduced in two stages in a fixed
@@ -478,6 +480,9 @@ int amar_locality_scale_bwd_f32(const float *dOut, int64_t ldd, const float *X, 
  *                           dt (x) a_neigh terms.  row_scratch: 3 * n_rows floats.  Row-wise sums only (no float atomics):
  *                           relies on the edge multiset being symmetric, as build_adjacency_matrix + symmetrize_matrix
  *                           produce it (src/data/preprocess.py:44-170, src/utilities/math.py:6-21).  C in {4,8,16,32,64}.
+ * amar_gat_bwd_directed_f32 the same for ANY edge multiset (dataset.symmetric_adjacency: False): the target walk (softmax statistics,
+ *                           ds) reads rowptr / colidx, the source walk (dt, dH) reads t_rowptr / t_colidx = the stable transpose
+ *                           of that structure.  Passing one structure twice gives amar_gat_bwd_f32 bit for bit.
  * amar_transpose_f32        dst[N,K] = src[K,N]^T
  * amar_adam_f32             keras.optimizers.Adam on a flat parameter: g' = g + 2*l2*w; m, v moments; lr_t = the
  *                           bias-corrected step lr * sqrt(1 - b2^t) / (1 - b1^t);  w -= lr_t * m / (sqrt(v) + epsilon)
@@ -567,6 +572,12 @@ int amar_gat_bwd_f32(const int32_t *rowptr, const int32_t *colidx, const float *
                      const float *bias, const float *a_self, const float *a_neigh,
                      float *dout, float *row_scratch, float *ds, float *dt, float *dH, int64_t lddh,
                      int32_t self_loop, int32_t n_rows, amar_stream_t stream);
+int amar_gat_bwd_directed_f32(const int32_t *rowptr, const int32_t *colidx, const int32_t *t_rowptr, const int32_t *t_colidx,
+                              const float *H, int64_t ldh, int32_t C,
+                              const float *s_self, const float *s_neigh, const float *Y, int64_t ldy, const float *dY, int64_t ldd,
+                              const float *bias, const float *a_self, const float *a_neigh,
+                              float *dout, float *row_scratch, float *ds, float *dt, float *dH, int64_t lddh,
+                              int32_t self_loop, int32_t n_rows, amar_stream_t stream);
 int amar_transpose_f32(const float *src, int32_t K, int32_t N, float *dst, amar_stream_t stream);
 int amar_adam_f32(float *w, const float *g, float *m, float *v, int64_t n, float lr_t, float beta_1, float beta_2,
                   float epsilon, float l2, amar_stream_t stream);
@@ -620,11 +631,15 @@ int amar_bpr_sample_i32(const int32_t *pos_ptr, const int32_t *pos_ids, const in
  *                             Y_i = ReLU(sum_j alpha_ij keep_ij scale H_j + bias); maximum, denominator and the 1e-9 are those of the
  *                             undropped logits.  Element of the stored entry (target i, source j) that is the o-th of its row's equal
  *                             columns (colidx sorted per row): c0 = min(i, j) | ((o % 255) << 24), c3 = max(i, j), word 0; the added self
- *                             loop is the entry (i, i) with ordinal slot 255.  The edge multiset must be symmetric: (i, j, o) and (j, i, o)
- *                             then draw one bit, wherever the entry is visited.  n_rows <= 2^24.  threshold 0, scale 1: the bits of
- *                             amar_gat_layer_f32.
+ *                             loop is the entry (i, i) with ordinal slot 255.  (i, j, o) and (j, i, o) draw one bit: on a symmetric
+ *                             edge multiset the reverse pass may therefore visit an entry from either end; on a directed one a
+ *                             reciprocal pair shares its bit.  n_rows <= 2^24.  threshold 0, scale 1: the bits of amar_gat_layer_f32.
  * amar_gat_bwd_dropout_f32    amar_gat_bwd_f32 for that forward with the same bits: d alpha_ij = keep_ij scale (dout_i . H_j) into the
- *                             unchanged softmax reverse, dH_j accumulates alpha_ij keep_ij scale dout_i; no float atomics. */
+ *                             unchanged softmax reverse, dH_j accumulates alpha_ij keep_ij scale dout_i; no float atomics.
+ *                             Symmetric edge multiset, as amar_gat_bwd_f32.
+ * amar_gat_bwd_directed_dropout_f32   the same with the source walk on the stable transpose (t_rowptr / t_colidx), for any edge
+ *                             multiset: entry (i, j, o) of A is entry (j, i, o) of A^T — the stable transpose keeps the order of
+ *                             parallel entries — so both walks regenerate the same bit. */
 int amar_dropout_f32(const float *X, int64_t ldx, float *Y, int64_t ldy, int64_t n_rows, int32_t C,
                      uint64_t seed, const uint64_t *step, uint32_t site, uint32_t threshold, float scale, amar_stream_t stream);
 int amar_dropout_advance(uint64_t *step, amar_stream_t stream);
@@ -640,6 +655,30 @@ int amar_gat_bwd_dropout_f32(const int32_t *rowptr, const int32_t *colidx, const
                              float *dout, float *row_scratch, float *ds, float *dt, float *dH, int64_t lddh,
                              int32_t self_loop, int32_t n_rows,
                              uint64_t seed, const uint64_t *step, uint32_t site, uint32_t threshold, float scale, amar_stream_t stream);
+int amar_gat_bwd_directed_dropout_f32(const int32_t *rowptr, const int32_t *colidx, const int32_t *t_rowptr, const int32_t *t_colidx,
+                                      const float *H, int64_t ldh, int32_t C,
+                                      const float *s_self, const float *s_neigh, const float *Y, int64_t ldy, const float *dY, int64_t ldd,
+                                      const float *bias, const float *a_self, const float *a_neigh,
+                                      float *dout, float *row_scratch, float *ds, float *dt, float *dH, int64_t lddh,
+                                      int32_t self_loop, int32_t n_rows,
+                                      uint64_t seed, const uint64_t *step, uint32_t site, uint32_t threshold, float scale, amar_stream_t stream);
+
+/* ---- transposed image of a graph (training on directed graphs, dataset.symmetric_adjacency: False) --------------------------------
+ * The STABLE transpose of an int32 CSR structure [n_rows, n_cols] with nnz = rowptr[n_rows] entries:
+ *     t_rowptr[n_cols + 1], t_colidx[nnz]   the CSR structure of A^T
+ *     perm[nnz]                             perm[q] = the input position of the entry that stands at output position q
+ * Inside output row j the entries stand in the order of their input positions — by source row, parallel (duplicate) entries in
+ * their input order — which is scipy's csr -> csc conversion without summing duplicates; perm is strictly increasing inside every
+ * output row.  Hence: input rows with sorted columns give output rows with sorted columns, and an entry is the o-th of its equals
+ * in row i of A exactly when it is the o-th of its equals in row j of A^T.  Whatever else an entry carries (value, multiplicity)
+ * follows by a gather through perm.
+ * The result is the same bits on every run: integer counting (vector atomics on int32), a scan, a fill through atomic cursors and
+ * then a sort of every output row's positions, which removes the arrival order (long rows — hub columns — included).  No float or
+ * scalar atomics.  cursor: n_cols int32 of scratch.  Column indices must lie in [0, n_cols) (entries outside are skipped, never
+ * written out of bounds; the result is then unspecified).  nnz == 0: t_rowptr is zeroed, the other outputs may be NULL.
+ * Not meant for a captured graph's body: it runs once per graph. */
+int amar_csr_transpose_i32(const int32_t *rowptr, const int32_t *colidx, int32_t n_rows, int32_t n_cols, int32_t nnz,
+                           int32_t *t_rowptr, int32_t *t_colidx, int32_t *perm, int32_t *cursor, amar_stream_t stream);
 
 /* ---- ranking ------------------------------------------------------------------------------
  * Per-user top-k over that user's own test pairs (src/utilities/metrics.py:11-34):
