@@ -877,6 +877,11 @@ class DeferredGradient:
         return self.partials.view(self.groups, -1).sum(0).view(self.shape)
 
 
+def flat_gradient(g):
+    """A gradient as adam_slot_table takes it: a DeferredGradient as it is, a tensor flat and contiguous."""
+    return g if isinstance(g, DeferredGradient) else g.contiguous().view(-1)
+
+
 class AdamSlot(ctypes.Structure):
     """include/amar_hip.h: amar_adam_slot"""
     _fields_ = [('w', ctypes.c_void_p), ('g', ctypes.c_void_p), ('m', ctypes.c_void_p), ('v', ctypes.c_void_p),

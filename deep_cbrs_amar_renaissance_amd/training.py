@@ -15,7 +15,8 @@ device transpose), for A_hat^T . dZ, and the forward GEMM for dX = 
 Implemented for GCN, GraphSAGE, GAT, LightGCN and DGCF stacks under every reduction ('concatenation', 'mean', 'sum',
 'w-sum', 'last'), alone (models/gnn.py) or chained as TwoStep / TwoWay models (models/tsgnn.py, twgnn.py): `_StackTape` is the
 forward-with-kept-activations + reverse pass of ONE stack, and the Trainer chains the tapes the way the model chains the
-stacks (the gradient of a stack's leading rows is lifted back to its full node table).  GraphSAGE trains on an unfused
+stacks (the gradient of a stack's leading rows is lifted back to its full node table).  A layer type's forward and reverse sit side by side
+in its `_LayerKind`; every reverse of a linear map, the Dense tapes' included, is `_LinearReverse.linear_bwd`.  GraphSAGE trains on an unfused
 forward that keeps what the reverse pass needs ([x || mean] and the normalised pre-activation); its aggregate is
 (A + I) / count, so the reverse aggregate is the row scale (A's counts) followed by the value-free SpMM on A^T.  The hybrid head
 (HybridCBRS: 'concatenate' / 'attention' fusion, residual classifier, both feature_based settings) trains on the same
@@ -53,22 +54,72 @@ def _spmm(a, x, out):
     return out
 
 
-class _DenseTape:
-    """Forward of a Dense stack that keeps every layer's input and output, and its reverse pass."""
+def _buffer(like, rows, cols=None):
+    return torch.empty(rows if cols is None else (rows, cols), dtype=torch.float32, device=like.device)
 
-    def __init__(self, stack):
-        self.layers = list(stack.layers)
-        self.inputs, self.outputs = [], []
+
+class _LinearReverse:
+    """The reverse pass of a linear map Z = X . W (+ b) for the tapes: the workspaces of amar_dense_bwd_f32, the choice between that
+    kernel and the separate ones, and `defer_reduce` (set by Trainer._graph_body for a captured step: the partial sums of dW / db stay in
+    the workspace and the batch's ONE Adam launch adds them, see capi.DeferredGradient)."""
+
+    def __init__(self):
         self._workspaces = {}
-        self.defer_reduce = False                                    # set by Trainer._graph_body (see capi.DeferredGradient)
+        self.defer_reduce = False
 
-    def _workspace(self, k, m, kk, n, device):
-        """The workspace of layer k's fused reverse pass for batches of m rows (allocated at the first batch of that shape — an eager
-        one — and reused by every later batch, captured ones included)."""
-        key = (k, int(m), int(kk), int(n))
+    def _workspace(self, key, m, kk, n, device):
+        """Allocated at the first batch of a shape — an eager one — and reused by every later batch, captured ones included."""
+        key = (key, int(m), int(kk), int(n))
         if key not in self._workspaces:
             self._workspaces[key] = capi.dense_bwd_workspace(m, kk, n, device)
         return self._workspaces[key]
+
+    @staticmethod
+    def fused_route(K, N, rows):
+        """amar_dense_bwd_f32 (act', dX, dW, db in two launches) or the separate kernels.  A layer whose reverse is several linear_bwd calls asks
+        once with its own (f, c) and passes `fused=`: its K = 1 bias and attention-vector calls must go the layer's way, not that of (1, c)."""
+        return capi.dense_bwd_enabled() and capi.dense_bwd_supported(K, N) and rows > 0
+
+    def linear_bwd(self, key, dy, *, x=None, w=None, y=None, act=None, dX=None, dZ=None, dw_like=None, db_like=None,
+                   accumulate_dx=False, K=None, fused=None, column_x=False):
+        """Reverse of Z = x . w (+ b), Y = act(Z), given dy = d(loss)/dY [M, N] (y None: dy already is dZ).  Returns (dW, db, dX), each
+        ready for `grads` (a tensor shaped like dw_like / db_like, or what a captured step defers) or None where not asked for: dW takes
+        x and dw_like, db takes db_like, dX takes w (into dX where given, else a fresh buffer; accumulate_dx: added to dX).  dZ: where to
+        leave dZ itself.  key names the fused route's workspace, K its K where neither x nor w tells.  column_x: x is one column and
+        dw_like holds the N values of x^T . dy, which the separate kernels form as the [N, 1] product dy^T . x."""
+        m, n = dy.shape
+        kk = w.shape[0] if w is not None else (x.shape[1] if x is not None else int(K or 1))
+        dw, db = (torch.empty_like(p) if p is not None else None for p in (dw_like, db_like))
+        if w is not None and dX is None:
+            dX = _buffer(dy, m, kk)
+        if self.fused_route(kk, n, m) if fused is None else fused:
+            act = act if y is not None else None
+            lazy = capi.dense_bwd(x, y if act is not None else None, dy, w, act, self._workspace(key, m, kk, n, dy.device), dX=dX,
+                                  dW=dw.view(kk, n) if dw is not None else None, db=db, defer=self.defer_reduce, dZ=dZ, accumulate_dx=accumulate_dx, K=K)
+            return (dw, db, dX) if lazy is None else (*lazy, dX)
+        dz = dy
+        if y is not None:
+            dz = dZ if dZ is not None else torch.empty_like(y)
+            capi.act_bwd(dy, y, dz, act)
+        if column_x:
+            capi.wgrad(dz, x, dw.view(n, 1), None)
+        elif dw is not None or db is not None:
+            capi.wgrad(x if dw is not None else None, dz, dw.view(kk, n) if dw is not None else None, db)
+        if w is not None:
+            back = _buffer(dy, m, kk) if accumulate_dx else dX
+            capi.dense(dz, w, None, back, act=None, w_transposed=True)
+            if accumulate_dx:
+                capi.add_inplace(dX, back)
+        return dw, db, dX
+
+
+class _DenseTape(_LinearReverse):
+    """Forward of a Dense stack that keeps every layer's input and output, and its reverse pass."""
+
+    def __init__(self, stack):
+        super().__init__()
+        self.layers = list(stack.layers)
+        self.inputs, self.outputs = [], []
 
     def _stack_spec(self, x, ids, out_last):
         """The arguments of the one-launch forward (capi.dense_stack) for this call, or None where the stack runs layer by layer."""
@@ -161,41 +212,17 @@ class _DenseTape:
         """dy: gradient w.r.t. the stack's output (or, with last_is_dz, already w.r.t. the last pre-activation).
         Fills grads[param] for every kernel/bias; returns the gradient w.r.t. the stack's input (None when
         need_input_grad is False: constant inputs such as the BERT rows)."""
-        m = int(dy.shape[0])
         spec = self._stack_bwd_spec(dy, last_is_dz, need_input_grad, dx_out)
         if spec is not None:
             # the whole stack's reverse pass in ONE launch (amar_dense_stack_bwd_f32): dZ walks the layers in LDS
             return self._stack_bwd_done(spec, capi.dense_stack_bwd(**spec), grads)
-        for k in range(len(self.layers) - 1, -1, -1):
-            layer, x, y = self.layers[k], self.inputs[k], self.outputs[k]
-            kk, n = layer.kernel.shape
-            if capi.dense_bwd_enabled() and capi.dense_bwd_supported(kk, n) and x.shape[0] > 0:
-                # act', dX, dW, db in two launches (amar_dense_bwd_f32; round 4 — four launches of 5-10 us each before)
-                need_dx = not (k == 0 and not need_input_grad)
-                act = None if (last_is_dz and k == len(self.layers) - 1) else layer.activation
-                dw, db = torch.empty_like(layer.kernel), torch.empty_like(layer.bias)
-                dx = (dx_out if (k == 0 and dx_out is not None) else torch.empty((x.shape[0], kk), dtype=torch.float32, device=x.device)) if need_dx else None
-                lazy = capi.dense_bwd(x, y if act is not None else None, dy, layer.kernel.detach() if need_dx else None, act,
-                                      self._workspace(k, x.shape[0], kk, n, x.device), dX=dx, dW=dw, db=db, defer=self.defer_reduce)
-                # (defer_reduce: the partial sums stay in the workspace and the batch's ONE Adam launch adds them — no reduction launch)
-                grads[layer.kernel], grads[layer.bias] = lazy if lazy is not None else (dw, db)
-                if not need_dx:
-                    return None
-                dy = dx
-                continue
-            if last_is_dz and k == len(self.layers) - 1:
-                dz = dy
-            else:
-                dz = torch.empty_like(y)
-                capi.act_bwd(dy, y, dz, layer.activation)
-            dw, db = torch.empty_like(layer.kernel), torch.empty_like(layer.bias)
-            capi.wgrad(x, dz, dw, db)
-            grads[layer.kernel], grads[layer.bias] = dw, db
-            if k == 0 and not need_input_grad:
-                return None
-            dx = dx_out if (k == 0 and dx_out is not None) else torch.empty((x.shape[0], layer.kernel.shape[0]), dtype=torch.float32, device=x.device)
-            capi.dense(dz, layer.kernel.detach(), None, dx, act=None, w_transposed=True)
-            dy = dx
+        last = len(self.layers) - 1
+        for k in range(last, -1, -1):
+            layer = self.layers[k]
+            need_dx = k > 0 or need_input_grad
+            grads[layer.kernel], grads[layer.bias], dy = self.linear_bwd(
+                k, dy, x=self.inputs[k], w=layer.kernel.detach() if need_dx else None, y=None if (last_is_dz and k == last) else self.outputs[k],
+                act=layer.activation, dX=dx_out if (k == 0 and need_dx) else None, dw_like=layer.kernel, db_like=layer.bias)
         return dy
 
 
@@ -352,50 +379,184 @@ class _HybridHead:
         return _DenseTape.backward_pair(t['dense1a'], dg1, t['dense1b'], dg2, grads, need_input_grad=need_input_grad)
 
 
-class _StackTape:
+class _LayerKind:
+    """What `_StackTape` asks of one layer type, forward and reverse side by side.  `tape` is the owning _StackTape: its graph, its A^T,
+    its linear reverse pass.  forward_layer(k, layer, x, y) writes layer k's output into y and returns what the reverse needs (a named
+    record; the default suits layers that call themselves and keep nothing); backward_layer(k, layer, saved, x, y, dx, dy, grads) adds
+    d(loss)/dx into dx given dy and fills `grads` for the layer's weights.  forward_stack(x0): (output, cat) of the whole stack at once, taken
+    where no stack rate is set; backward_stack(d_out): d(loss)/d(node table) at once where that left no layers to walk.  None: layer by layer."""
+
+    saves_undropped_output = False                                   # see _StackTape.forward
+
+    def __init__(self, tape, layers):
+        self.tape, self.layers = tape, layers
+
+    def forward_stack(self, x0):
+        return None
+
+    def backward_stack(self, d_out):
+        return None
+
+    def forward_layer(self, k, layer, x, y):
+        layer([x, self.tape.seq.adj_matrix], out=y)
+
+
+class _GCNLayers(_LayerKind):
+    def forward_stack(self, x0):
+        return self.tape.seq._propagate(x0, with_layers=True)        # the inference kernels: their outputs are all the reverse pass needs
+
+    def backward_layer(self, k, layer, saved, x, y, dx, dy, grads):
+        tape, (n, c) = self.tape, y.shape
+        fused = tape.fused_route(x.shape[1], c, n)
+        dz = _buffer(y, n, c)
+        grads[layer.bias] = tape.linear_bwd(('b', k), dy, y=y, act='relu', dZ=dz, db_like=layer.bias, K=1, fused=fused)[1]
+        dh = _spmm(tape.at, dz, _buffer(y, n, c))                    # A_hat^T . dZ
+        # dW = X_k^T . dH, and dH . W^T added into the slice's gradient
+        grads[layer.kernel] = tape.linear_bwd(k, dh, x=x, w=layer.kernel.detach(), dX=dx, dw_like=layer.kernel, accumulate_dx=True, fused=fused)[0]
+
+
+class _LightGCNLayers(_LayerKind):
+    forward_stack = _GCNLayers.forward_stack                         # (under 'mean' the running-sum kernels: no `cat`, the layers never exist)
+
+    def backward_stack(self, d_out):
+        if self.tape.cat is not None:
+            return None
+        # g0 = (I + A^T + (A^T)^2 + ...) d_out / (L + 1)
+        g0 = torch.zeros((d_out.shape[0], self.tape.widths[0]), dtype=torch.float32, device=d_out.device)
+        capi.add_inplace(g0, d_out, 1.0 / (len(self.layers) + 1))
+        acc = g0.clone()
+        for _ in self.layers:
+            acc = _spmm(self.tape.at, acc, torch.empty_like(acc))
+            capi.add_inplace(g0, acc)
+        return g0
+
+    def backward_layer(self, k, layer, saved, x, y, dx, dy, grads):
+        capi.add_inplace(dx, _spmm(self.tape.at, dy, _buffer(x, *x.shape)))
+
+
+class _DGCFLayers(_LayerKind):
+    def backward_layer(self, k, layer, saved, x, y, dx, dy, grads):   # (every layer's input stays in `cat`: the gate's gradient needs it)
+        back, dw = _spmm(self.tape.at, dy, _buffer(x, *x.shape)), _buffer(x, x.shape[0])     # A_dgcf^T . d(out)
+        capi.locality_scale_bwd(back, x, layer.w.detach().view(-1), dx, dw, accumulate=True)
+        grads[layer.w] = dw.view_as(layer.w)
+
+
+class _SageLayers(_LayerKind):
+    """An unfused forward that keeps [x || agg(x)] and the l2-normalised pre-activation.  'mean' is (A + I) / count ('sum': scale 1), so
+    its reverse is the row scale, then the value-free SpMM on A^T; max / min keep how many entries attain the extremum and share among them."""
+
+    def __init__(self, tape, layers):
+        super().__init__(tape, layers)
+        if len({bool(l.self_loops) for l in layers}) != 1 or len({l.aggregate for l in layers}) != 1:
+            raise NotImplementedError("GraphSAGE layers with mixed self_loops / aggregate settings")
+        self.self_loops, self.aggregate = bool(layers[0].self_loops), layers[0].aggregate
+        # 'mean': sum / count (0 for an empty segment), 'sum': sum * 1 — the layer's cached vector; max / min keep a tie count instead
+        self.inv_cnt = layers[0].row_scale(tape.seq.adj_matrix) if self.aggregate in ('mean', 'sum') else None
+
+    def forward_layer(self, k, layer, x, y):
+        a, (n, f), c = self.tape.seq.adj_matrix, x.shape, y.shape[1]
+        xa, cnt = _buffer(x, n, 2 * f), None
+        capi.copy_columns(x, xa[:, :f])
+        if self.inv_cnt is None:                                     # max / min: the aggregate straight into xa, and how many entries attain it
+            cnt = _buffer(x, n, f)
+            capi.sage_aggregate(a.rowptr, a.colidx, x, xa[:, f:], self.aggregate, cnt=cnt, self_loop=self.self_loops)
+        else:
+            ssum = _buffer(x, n, f)
+            capi.spmm_csr(a.rowptr, a.colidx, None, x, ssum)
+            capi.row_affine(ssum, self.inv_cnt, xa[:, f:], b=x if self.self_loops else None)
+        z, nrm, inv = _buffer(x, n, c), _buffer(x, n, c), _buffer(x, n)
+        capi.dense(xa, layer.kernel, layer.bias, z, act=None)
+        capi.l2norm_fwd(z, nrm, inv, y, act='relu')
+        return types.SimpleNamespace(xa=xa, nrm=nrm, inv=inv, cnt=cnt)
+
+    def backward_layer(self, k, layer, saved, x, y, dx, dy, grads):
+        at, (n, f), xa = self.tape.at, x.shape, saved.xa
+        dz = _buffer(x, *y.shape)
+        capi.l2norm_bwd(dy, saved.nrm, saved.inv, dz, act='relu')
+        grads[layer.kernel], grads[layer.bias], dxa = self.tape.linear_bwd(k, dz, x=xa, w=layer.kernel.detach(), dw_like=layer.kernel, db_like=layer.bias)
+        capi.add_inplace(dx, dxa[:, :f])
+        if saved.cnt is not None:
+            # every entry that attains the extremum takes d_agg / cnt; row j finds its shares on the targets that list it: A^T's row j
+            capi.sage_aggregate_bwd(at.rowptr, at.colidx, xa[:, :f], xa[:, f:], saved.cnt, dxa[:, f:], dx, self_loop=self.self_loops)
+            return
+        g, back = _buffer(x, n, f), _buffer(x, n, f)
+        capi.row_affine(dxa[:, f:], self.inv_cnt, g)                 # d(mean)/d(sum) by A's row counts; 'sum': a copy
+        capi.spmm_csr(at.rowptr, at.colidx, None, g, back)           # A^T . g
+        capi.add_inplace(dx, back)
+        if self.self_loops:
+            capi.add_inplace(dx, g)
+
+
+class _GATLayers(_LayerKind):
+    """The inference kernels, keeping H = X . W and the two attention scalars, and amar_gat_bwd_f32 for the softmax reverse.  That reverse
+    needs out_i itself (c_i = g_i . (out_i - b)): under a stack rate the undropped output stays saved and the slice gets the dropped copy."""
+
+    saves_undropped_output = True
+    edge_drop = None                                                 # the attention masks, set by _StackTape.enable_dropout
+
+    def forward_layer(self, k, layer, x, y):
+        a, n, c = self.tape.seq.adj_matrix, x.shape[0], y.shape[1]
+        h, s_self, s_neigh = _buffer(x, n, c), _buffer(x, n), _buffer(x, n)
+        capi.rowwise_xw(x, layer.kernel.view(-1, c), h, a_self=layer.attn_kernel_self.view(c), a_neigh=layer.attn_kernel_neighs.view(c), s_self=s_self, s_neigh=s_neigh)
+        edge = self.edge_drop[k] if self.edge_drop is not None else None
+        if edge is not None:
+            capi.gat_layer_dropout(a.rowptr, a.colidx, h, s_self, s_neigh, layer.bias, y, edge, self_loop=layer.add_self_loops)
+        else:
+            capi.gat_layer(a.rowptr, a.colidx, h, s_self, s_neigh, layer.bias, y, self_loop=layer.add_self_loops)
+        return types.SimpleNamespace(h=h, s_self=s_self, s_neigh=s_neigh, y=y)
+
+    def backward_layer(self, k, layer, saved, x, y, dx, dy, grads):
+        tape, a, at, (n, f), c, h = self.tape, self.tape.seq.adj_matrix, self.tape.at, x.shape, y.shape[1], saved.h
+        edge = self.edge_drop[k] if self.edge_drop is not None else None
+        gat_args = (a.rowptr, a.colidx, h, saved.s_self, saved.s_neigh, saved.y, dy, layer.bias,
+                    layer.attn_kernel_self.detach().view(c), layer.attn_kernel_neighs.detach().view(c))
+        # targets walk A's rows, sources A^T's (one structure where the edge multiset is symmetric)
+        transposed = (at.rowptr, at.colidx) if at is not a else None
+        if edge is not None:
+            dout, ds, dt, dh = capi.gat_bwd_dropout(*gat_args, edge, self_loop=layer.add_self_loops, transposed=transposed)
+        else:
+            dout, ds, dt, dh = capi.gat_bwd(*gat_args, self_loop=layer.add_self_loops, transposed=transposed)
+        fused = tape.fused_route(f, c, n)
+        # H^T . ds as (ds^T . H)^T: a [1, c] weight gradient with X = ds, dZ = H
+        grads[layer.attn_kernel_self] = tape.linear_bwd(('s', k), h, x=ds.view(n, 1), dw_like=layer.attn_kernel_self, fused=fused, column_x=True)[0]
+        grads[layer.attn_kernel_neighs] = tape.linear_bwd(('t', k), h, x=dt.view(n, 1), dw_like=layer.attn_kernel_neighs, fused=fused, column_x=True)[0]
+        grads[layer.bias] = tape.linear_bwd(('b', k), dout, db_like=layer.bias, K=1, fused=fused)[1]
+        # dW = X_k^T . dH, and dH . W^T added into the slice's gradient
+        w = layer.kernel.detach().view(f, c).contiguous()
+        grads[layer.kernel] = tape.linear_bwd(k, dh, x=x, w=w, dX=dx, dw_like=layer.kernel, accumulate_dx=True, fused=fused)[0]
+
+
+class _StackTape(_LinearReverse):
     """Forward of ONE convolution stack (SequentialGNN / HalfInput / FullInputSequentialGNN) that keeps what its reverse
     pass needs, and that reverse pass: d(loss)/d(reduced output) -> weight gradients + d(loss)/d(node table).
 
     Every layer's output lives in a column slice of one [N, sum(widths)] buffer `cat`; the reduction (reduction.py:9-33)
     is undone first (d_cat = d_out for 'concatenation', d_out / (L+1) per slice for 'mean', ...), then the layers run
-    in reverse on the slices of (cat, d_cat).  `at` = the transposed image of the stack's graph, taken once here (before any
-    capture; the tape keeps it and its images alive): every product or walk that needs A^T uses it.  For a symmetric graph
-    (config.yaml:36) `at is a` and the reverse pass reuses the forward structure."""
+    in reverse on the slices of (cat, d_cat).  A layer's own forward and reverse are its `_LayerKind`'s, chosen once from KINDS.
+    `at` = the transposed image of the stack's graph, taken once here (before any capture; the tape keeps it and its images alive): every
+    product or walk that needs A^T uses it.  For a symmetric graph (config.yaml:36) `at is a` and the reverse pass reuses the forward structure."""
 
-    KINDS = ((GCNConv, 'gcn'), (LightGCNConv, 'lightgcn'), (GraphSageConv, 'sage'), (GATConv, 'gat'), (DGCFConv, 'dgcf'))
+    KINDS = ((GCNConv, 'gcn', _GCNLayers), (LightGCNConv, 'lightgcn', _LightGCNLayers), (GraphSageConv, 'sage', _SageLayers),
+             (GATConv, 'gat', _GATLayers), (DGCFConv, 'dgcf', _DGCFLayers))
+    MAX_LAYERS = 32                                                  # sites of a stack: 2 * MAX_LAYERS, three stacks at most (< 256)
+    edge_drop = property(lambda self: getattr(self.impl, 'edge_drop', None))     # (the GAT layers' own)
 
     def __init__(self, seq):
+        super().__init__()
         self.seq = seq
         layers = list(seq.seq_layers)
-        self.kind = next((name for cls, name in self.KINDS if layers and all(isinstance(l, cls) for l in layers)), None)
+        self.kind, kind_cls = next(((name, impl) for cls, name, impl in self.KINDS if layers and all(isinstance(l, cls) for l in layers)), (None, None))
         if self.kind is None:
             raise NotImplementedError("training needs a stack of one layer type (GCN, GraphSAGE, GAT, LightGCN or DGCF)")
         if seq.final_node not in ('concatenation', 'mean', 'sum', 'last', 'w-sum'):
             raise NotImplementedError("no reverse pass for the '{}' reduction".format(seq.final_node))
-        if self.kind == 'sage':
-            if len({bool(l.self_loops) for l in layers}) != 1 or len({l.aggregate for l in layers}) != 1:
-                raise NotImplementedError("GraphSAGE layers with mixed self_loops / aggregate settings")
-            self.self_loops, self.aggregate = bool(layers[0].self_loops), layers[0].aggregate
-            # 'mean': sum / count (0 for an empty segment), 'sum': sum * 1 — the layer's cached vector; max / min keep a tie count instead
-            self.inv_cnt = layers[0].row_scale(seq.adj_matrix) if self.aggregate in ('mean', 'sum') else None
+        self.impl = kind_cls(self, layers)
         self.at = seq.adj_matrix.transposed()                        # A^T: the graph itself where it is symmetric
-        self.cat = self.tape = None
-        self._workspaces = {}
-        self.defer_reduce = False
-        self.node_drop = self.edge_drop = None                       # set by enable_dropout (Trainer): the stack trains without otherwise
-
-    def _workspace(self, k, m, kk, n, device):
-        key = (k, int(m), int(kk), int(n))
-        if key not in self._workspaces:
-            self._workspaces[key] = capi.dense_bwd_workspace(m, kk, n, device)
-        return self._workspaces[key]
-
-    MAX_LAYERS = 32                                                  # sites of a stack: 2 * MAX_LAYERS, three stacks at most (< 256)
+        self.cat = self.saved = self.node_drop = None                # node_drop: set by enable_dropout (Trainer), the stack trains without otherwise
 
     def dropout_rates(self):
         """(stack rate, [GAT attention rate per layer]) with 0.0 for 'none'."""
-        gat = [float(getattr(l, 'dropout_rate', 0.0) or 0.0) for l in self.seq.seq_layers] if self.kind == 'gat' else []
-        return float(self.seq.dropout or 0.0), gat
+        return float(self.seq.dropout or 0.0), [float(getattr(l, 'dropout_rate', 0.0) or 0.0) for l in self.seq.seq_layers if isinstance(l, GATConv)]
 
     def enable_dropout(self, seed, step, stack_index):
         """The dropout sites of this stack: layer k's output has site 1 + 2 (32 stack_index + k), the attention
@@ -408,7 +569,7 @@ class _StackTape:
         if rate > 0.0:
             self.node_drop = [capi.Dropout(seed, step, base + 2 * k + 1, rate) for k in range(n_layers)]
         if any(r > 0.0 for r in gat):
-            self.edge_drop = [capi.Dropout(seed, step, base + 2 * k + 2, r) if r > 0.0 else None for k, r in enumerate(gat)]
+            self.impl.edge_drop = [capi.Dropout(seed, step, base + 2 * k + 2, r) if r > 0.0 else None for k, r in enumerate(gat)]
 
     def _slices(self, t):
         offs = self.offs
@@ -422,65 +583,25 @@ class _StackTape:
         widths = self.widths = seq.layer_widths()
         seq._build_layers(widths)
         self.offs = [int(v) for v in np.cumsum([0] + widths)]
-        if self.kind in ('gcn', 'lightgcn') and self.node_drop is None:
-            # the inference kernels: their outputs are all the reverse pass needs
-            out, self.cat = seq._propagate(x0, with_layers=True)
+        self.saved = [None] * len(seq.seq_layers)
+        whole = self.impl.forward_stack(x0) if self.node_drop is None else None
+        if whole is not None:
+            out, self.cat = whole
             return out
-        a = seq.adj_matrix
-        n, dev = a.shape[0], x0.device
-        cat = self.cat = torch.empty((n, self.offs[-1]), dtype=torch.float32, device=dev)
+        cat = self.cat = _buffer(x0, seq.adj_matrix.shape[0], self.offs[-1])
         sl = self._slices(cat)
         capi.copy_columns(x0, sl(0))
-        self.tape = []
         for k, layer in enumerate(seq.seq_layers):
-            f, c = widths[k], widths[k + 1]
             drop = self.node_drop[k] if self.node_drop is not None else None
-            if self.kind in ('gcn', 'lightgcn'):
-                # (a stack rate is set) layer by layer through the layers' own calls: the next layer must read the dropped slice
-                layer([sl(k), a], out=sl(k + 1))
-            elif self.kind == 'sage':
-                # layer by layer, keeping [x || agg(x)] and the l2-normalised pre-activation
-                xa = torch.empty((n, 2 * f), dtype=torch.float32, device=dev)
-                capi.copy_columns(sl(k), xa[:, :f])
-                cnt = None
-                if self.inv_cnt is None:                             # max / min: the aggregate straight into xa, and how many entries attain it
-                    cnt = torch.empty((n, f), dtype=torch.float32, device=dev)
-                    capi.sage_aggregate(a.rowptr, a.colidx, sl(k), xa[:, f:], self.aggregate, cnt=cnt, self_loop=self.self_loops)
-                else:
-                    ssum = torch.empty((n, f), dtype=torch.float32, device=dev)
-                    capi.spmm_csr(a.rowptr, a.colidx, None, sl(k), ssum)
-                    capi.row_affine(ssum, self.inv_cnt, xa[:, f:], b=sl(k) if self.self_loops else None)
-                z = torch.empty((n, c), dtype=torch.float32, device=dev)
-                capi.dense(xa, layer.kernel, layer.bias, z, act=None)
-                nrm = torch.empty((n, c), dtype=torch.float32, device=dev)
-                inv = torch.empty(n, dtype=torch.float32, device=dev)
-                capi.l2norm_fwd(z, nrm, inv, sl(k + 1), act='relu')
-                self.tape.append((xa, nrm, inv, cnt))
-            elif self.kind == 'gat':
-                # same kernels as inference, keeping H and the two attention scalars
-                h = torch.empty((n, c), dtype=torch.float32, device=dev)
-                s_self = torch.empty(n, dtype=torch.float32, device=dev)
-                s_neigh = torch.empty(n, dtype=torch.float32, device=dev)
-                capi.rowwise_xw(sl(k), layer.kernel.view(-1, c), h, a_self=layer.attn_kernel_self.view(c),
-                                a_neigh=layer.attn_kernel_neighs.view(c), s_self=s_self, s_neigh=s_neigh)
-                # with a stack rate the undropped output stays on the tape: the softmax reverse needs out_i itself (c_i = g_i . (out_i - b))
-                y = torch.empty((n, c), dtype=torch.float32, device=dev) if drop is not None else sl(k + 1)
-                edge = self.edge_drop[k] if self.edge_drop is not None else None
-                if edge is not None:
-                    capi.gat_layer_dropout(a.rowptr, a.colidx, h, s_self, s_neigh, layer.bias, y, edge, self_loop=layer.add_self_loops)
-                else:
-                    capi.gat_layer(a.rowptr, a.colidx, h, s_self, s_neigh, layer.bias, y, self_loop=layer.add_self_loops)
-                self.tape.append((h, s_self, s_neigh, y))
-                if drop is not None:
-                    capi.dropout(y, drop, out=sl(k + 1))
-                    continue
-            else:                                                    # dgcf: every layer's input stays in `cat` (the gate's gradient needs it)
-                layer([sl(k), a], out=sl(k + 1))
+            # a kind whose reverse pass needs the undropped output writes it to a buffer that stays saved; the slice takes the dropped copy
+            own = drop is not None and self.impl.saves_undropped_output
+            y = _buffer(x0, cat.shape[0], widths[k + 1]) if own else sl(k + 1)
+            self.saved[k] = self.impl.forward_layer(k, layer, sl(k), y)
             if drop is not None:
-                # in place, before the reduction and the next layer read the slice (the reference's loop, gnn.py:76-81).  Sound for the
-                # reverse pass: it masks d(slice k + 1) first, so every `Y > 0` it then evaluates sees a kept element (same sign) or
-                # meets a gradient that already is zero
-                capi.dropout(sl(k + 1), drop)
+                # before the reduction and the next layer read the slice (the reference's loop, gnn.py:76-81); in place where y is the
+                # slice.  Sound for the reverse pass: it masks d(slice k + 1) first, so every `Y > 0` it then evaluates sees a kept
+                # element (same sign) or meets a gradient that already is zero
+                capi.dropout(y, drop, out=sl(k + 1) if own else None)
         return seq._reduce(cat, [sl(k) for k in range(len(widths))], widths)
 
     # -- reverse ----------------------------------------------------------------------------------------------------
@@ -509,134 +630,17 @@ class _StackTape:
     def backward(self, d_out, grads):
         """Fills `grads` for the layers' weights; returns d(loss)/d(node table) [N, widths[0]] (a fresh buffer).
         `d_out` is consumed (it may be modified in place)."""
-        seq, a, at = self.seq, self.seq.adj_matrix, self.at
-        layers, widths = list(seq.seq_layers), self.widths
-        n, dev = d_out.shape[0], d_out.device
-        if self.kind == 'lightgcn' and self.cat is None:
-            # running-sum route ('mean'): g0 = (I + A^T + (A^T)^2 + ...) d_out / (L + 1)
-            n_terms = len(layers) + 1
-            g0 = torch.zeros((n, widths[0]), dtype=torch.float32, device=dev)
-            capi.add_inplace(g0, d_out, 1.0 / n_terms)
-            acc = g0.clone()
-            for _ in layers:
-                nxt = torch.empty_like(acc)
-                _spmm(at, acc, nxt)
-                capi.add_inplace(g0, nxt)
-                acc = nxt
+        g0 = self.impl.backward_stack(d_out)
+        if g0 is not None:
             return g0
-        e, de = self.cat, self._expand(d_out, grads)
-        sl, dsl = self._slices(e), self._slices(de)
-        for k in range(len(layers) - 1, -1, -1):
-            layer = layers[k]
-            f, c = widths[k], widths[k + 1]
+        sl, dsl = self._slices(self.cat), self._slices(self._expand(d_out, grads))
+        for k in reversed(range(len(self.saved))):
             if self.node_drop is not None:                           # the regenerated mask of layer k's output, on its gradient
                 capi.dropout(dsl(k + 1), self.node_drop[k])
-            if self.kind == 'gcn':
-                dzk = torch.empty((n, c), dtype=torch.float32, device=dev)
-                dw, db = torch.empty_like(layer.kernel), torch.empty_like(layer.bias)
-                fused = capi.dense_bwd_enabled() and capi.dense_bwd_supported(f, c) and n > 0
-                if fused:                                             # act', its bias gradient and dZ in one launch
-                    lazy = capi.dense_bwd(None, sl(k + 1), dsl(k + 1), None, 'relu', self._workspace(('b', k), n, 1, c, dev), db=db, dZ=dzk,
-                                          defer=self.defer_reduce, K=1)
-                    if lazy is not None:
-                        db = lazy[1]
-                else:
-                    capi.act_bwd(dsl(k + 1), sl(k + 1), dzk, 'relu')
-                dh = torch.empty((n, c), dtype=torch.float32, device=dev)
-                _spmm(at, dzk, dh)                                    # A_hat^T . dZ
-                if fused:                                             # dW = X_k^T . dH, and dH . W^T added straight into the slice's gradient
-                    lazy = capi.dense_bwd(sl(k), None, dh, layer.kernel.detach(), None, self._workspace(k, n, f, c, dev), dX=dsl(k), dW=dw,
-                                          defer=self.defer_reduce, accumulate_dx=True)
-                    if lazy is not None:
-                        dw = lazy[0]
-                else:
-                    back = torch.empty((n, f), dtype=torch.float32, device=dev)
-                    capi.wgrad(sl(k), dh, dw, None)
-                    capi.dense(dh, layer.kernel.detach(), None, back, act=None, w_transposed=True)
-                    capi.wgrad(None, dzk, None, db)
-                    capi.add_inplace(dsl(k), back)
-                grads[layer.kernel], grads[layer.bias] = dw, db
-            elif self.kind == 'lightgcn':
-                back = torch.empty((n, f), dtype=torch.float32, device=dev)
-                _spmm(at, dsl(k + 1), back)
-                capi.add_inplace(dsl(k), back)
-            elif self.kind == 'sage':
-                xa, nrm, inv, cnt = self.tape[k]
-                dz = torch.empty((n, c), dtype=torch.float32, device=dev)
-                capi.l2norm_bwd(dsl(k + 1), nrm, inv, dz, act='relu')
-                dw, db = torch.empty_like(layer.kernel), torch.empty_like(layer.bias)
-                dxa = torch.empty((n, 2 * f), dtype=torch.float32, device=dev)
-                if capi.dense_bwd_enabled() and capi.dense_bwd_supported(2 * f, c) and n > 0:     # dW, db and dZ . W^T in one launch (round 4)
-                    lazy = capi.dense_bwd(xa, None, dz, layer.kernel.detach(), None, self._workspace(k, n, 2 * f, c, dev), dX=dxa, dW=dw, db=db,
-                                          defer=self.defer_reduce)
-                    if lazy is not None:
-                        dw, db = lazy
-                else:
-                    capi.wgrad(xa, dz, dw, db)
-                    capi.dense(dz, layer.kernel.detach(), None, dxa, act=None, w_transposed=True)
-                grads[layer.kernel], grads[layer.bias] = dw, db
-                capi.add_inplace(dsl(k), dxa[:, :f])
-                if cnt is not None:
-                    # every entry that attains the extremum takes d_agg / cnt; row j finds its shares on the targets that list it: A^T's row j
-                    capi.sage_aggregate_bwd(at.rowptr, at.colidx, xa[:, :f], xa[:, f:], cnt, dxa[:, f:], dsl(k), self_loop=self.self_loops)
-                else:
-                    g = torch.empty((n, f), dtype=torch.float32, device=dev)
-                    capi.row_affine(dxa[:, f:], self.inv_cnt, g)           # d(mean)/d(sum) by A's row counts; 'sum': a copy
-                    back = torch.empty((n, f), dtype=torch.float32, device=dev)
-                    capi.spmm_csr(at.rowptr, at.colidx, None, g, back)     # A^T . g
-                    capi.add_inplace(dsl(k), back)
-                    if self.self_loops:
-                        capi.add_inplace(dsl(k), g)
-            elif self.kind == 'gat':
-                h, s_self, s_neigh, y = self.tape[k]
-                w2d = layer.kernel.detach().view(f, c)
-                edge = self.edge_drop[k] if self.edge_drop is not None else None
-                gat_args = (a.rowptr, a.colidx, h, s_self, s_neigh, y, dsl(k + 1), layer.bias,
-                            layer.attn_kernel_self.detach().view(c), layer.attn_kernel_neighs.detach().view(c))
-                # targets walk A's rows, sources A^T's (one structure where the edge multiset is symmetric)
-                transposed = (at.rowptr, at.colidx) if at is not a else None
-                if edge is not None:
-                    dout, ds, dt, dh = capi.gat_bwd_dropout(*gat_args, edge, self_loop=layer.add_self_loops, transposed=transposed)
-                else:
-                    dout, ds, dt, dh = capi.gat_bwd(*gat_args, self_loop=layer.add_self_loops, transposed=transposed)
-                db = torch.empty_like(layer.bias)
-                das, dan = torch.empty((c, 1), dtype=torch.float32, device=dev), torch.empty((c, 1), dtype=torch.float32, device=dev)
-                fused = capi.dense_bwd_enabled() and capi.dense_bwd_supported(f, c) and n > 0
-                if fused:                                             # H^T . ds as (ds^T . H)^T: a [1, c] weight gradient with X = ds, dZ = H — one launch each
-                    lazy_s = capi.dense_bwd(ds.view(n, 1), None, h, None, None, self._workspace(('s', k), n, 1, c, dev), dW=das.view(1, c), defer=self.defer_reduce)
-                    lazy_t = capi.dense_bwd(dt.view(n, 1), None, h, None, None, self._workspace(('t', k), n, 1, c, dev), dW=dan.view(1, c), defer=self.defer_reduce)
-                    if lazy_s is not None:
-                        das, dan = lazy_s[0], lazy_t[0]
-                else:
-                    capi.wgrad(h, ds.view(n, 1), das, None)
-                    capi.wgrad(h, dt.view(n, 1), dan, None)
-                dw = torch.empty((f, c), dtype=torch.float32, device=dev)
-                if fused:
-                    # round 4: the bias gradient in one launch, and dW = X_k^T . dH with dH . W^T added straight into the slice's gradient in
-                    # one more (ten launches of a layer's reverse pass were weight-gradient partials and their reductions)
-                    lazy_b = capi.dense_bwd(None, None, dout, None, None, self._workspace(('b', k), n, 1, c, dev), db=db, defer=self.defer_reduce, K=1)
-                    lazy_w = capi.dense_bwd(sl(k), None, dh, w2d.contiguous(), None, self._workspace(k, n, f, c, dev), dX=dsl(k), dW=dw,
-                                            defer=self.defer_reduce, accumulate_dx=True)
-                    grads[layer.kernel] = lazy_w[0] if lazy_w is not None else dw.view_as(layer.kernel)
-                    grads[layer.bias] = lazy_b[1] if lazy_b is not None else db
-                else:
-                    capi.wgrad(None, dout, None, db)
-                    capi.wgrad(sl(k), dh, dw, None)
-                    grads[layer.kernel], grads[layer.bias] = dw.view_as(layer.kernel), db
-                    back = torch.empty((n, f), dtype=torch.float32, device=dev)
-                    capi.dense(dh, w2d.contiguous(), None, back, act=None, w_transposed=True)
-                    capi.add_inplace(dsl(k), back)
-                grads[layer.attn_kernel_self] = das if isinstance(das, capi.DeferredGradient) else das.view_as(layer.attn_kernel_self)
-                grads[layer.attn_kernel_neighs] = dan if isinstance(dan, capi.DeferredGradient) else dan.view_as(layer.attn_kernel_neighs)
-            else:                                                    # dgcf
-                back = torch.empty((n, f), dtype=torch.float32, device=dev)
-                _spmm(at, dsl(k + 1), back)               # A_dgcf^T . d(out)
-                dw = torch.empty(n, dtype=torch.float32, device=dev)
-                capi.locality_scale_bwd(back, sl(k), layer.w.detach().view(-1), dsl(k), dw, accumulate=True)
-                grads[layer.w] = dw.view_as(layer.w)
-        g0 = torch.empty((n, widths[0]), dtype=torch.float32, device=dev)
+            self.impl.backward_layer(k, self.seq.seq_layers[k], self.saved[k], sl(k), sl(k + 1), dsl(k), dsl(k + 1), grads)
+        g0 = _buffer(d_out, d_out.shape[0], self.widths[0])
         capi.copy_columns(dsl(0), g0)
-        self.tape = self.cat = None
+        self.saved = self.cat = None
         return g0
 
 
@@ -821,7 +825,7 @@ class Trainer:
         capi.adam_advance(self._adam_state, self.lr, self.b1, self.b2)
         # one launch updates every parameter (a table of slots, uploaded by a captured copy from pinned memory: the
         # gradient buffers of this graph have fixed addresses) and adds the regularisation loss; one more adds the data loss
-        entries = [(prm.data.view(-1), grads[prm] if isinstance(grads[prm], capi.DeferredGradient) else grads[prm].contiguous().view(-1),
+        entries = [(prm.data.view(-1), capi.flat_gradient(grads[prm]),
                     self.m[prm].view(-1), self.v[prm].view(-1), self._l2(prm)) for prm in self.params]
         host, blocks = capi.adam_slot_table(entries)
         g['slot_host'][:host.numel()].copy_(host)                    # pinned buffer allocated before the capture began
@@ -999,13 +1003,9 @@ class Trainer:
 
     def _all_tapes(self):
         """Every tape of the trainer that owns a fused reverse pass (Dense stacks of the head, convolution stacks)."""
-        out = list(getattr(self, 'tapes', []) or [])
         head = getattr(self, 'head', None)
-        for name in ('unet', 'inet', 'clf'):
-            if hasattr(head, name):
-                out.append(getattr(head, name))
-        out.extend(getattr(head, 't', {}).values() if isinstance(getattr(head, 't', None), dict) else [])
-        return [t for t in out if hasattr(t, 'defer_reduce')]
+        dense = [getattr(head, name, None) for name in ('unet', 'inet', 'clf')] + list(getattr(head, 't', {}).values())
+        return [t for t in list(getattr(self, 'tapes', None) or []) + dense if isinstance(t, _LinearReverse)]
 
     def pop_loss_sum(self):
         """Sum over the batches since the last call of (batch loss x batch size); one host synchronisation."""
