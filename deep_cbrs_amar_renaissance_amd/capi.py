@@ -97,6 +97,10 @@ SIGNATURES = {
     'amar_adam_f32': (ctypes.c_int, [_P, _P, _P, _P, _I64, _F32, _F32, _F32, _F32, _F32, _P]),
     'amar_adam_advance_f32': (ctypes.c_int, [_P, _F32, _F32, _F32, _P]),
     'amar_adam_dev_f32': (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _F32, _F32, _F32, _F32, _P]),
+    'amar_optim_state_arrays': (ctypes.c_int, [_I32, _I32, _F32]),
+    'amar_optim_advance_f32': (ctypes.c_int, [_P, _I32, _I32, _P, _P]),
+    'amar_optim_f32': (ctypes.c_int, [_I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _F32, _P]),
+    'amar_optim_multi_f32': (ctypes.c_int, [_I32, _I32, _P, _P, _I32, _I64, _P, _F32, _P, _P]),
     'amar_bpr_grad_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P]),
     'amar_bpr_sample_i32': (ctypes.c_int, [_P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _I32, _I32, _P, _P, _P, _P]),
     'amar_dropout_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I32, ctypes.c_uint64, _P, _U32, _U32, _F32, _P]),
@@ -914,6 +918,90 @@ def adam_multi(table_dev, n_slots, total_blocks, state, beta_1, beta_2, epsilon,
                                       float(beta_1), float(beta_2), float(epsilon), float(reg_scale),
                                       _ptr(loss_acc, torch.float32, 'loss_acc'), _stream())
     _check(code, 'amar_adam_multi_f32')
+
+
+# ---- the other optimizers (include/amar_hip.h: AMAR_OPT_*) ----------------------------------------------------------------------------
+OPT_SGD, OPT_RMSPROP, OPT_ADAGRAD, OPT_ADAMAX, OPT_NADAM, OPT_AMSGRAD = 1, 2, 3, 4, 5, 6
+OPT_NESTEROV, OPT_CENTERED = 0x100, 0x200
+OPTIM_STATE_FLOATS = 8
+
+
+class OptimHyper(ctypes.Structure):
+    """include/amar_hip.h: amar_optim_hyper (a host struct; a rule ignores the members it does not use)"""
+    _fields_ = [(name, ctypes.c_float) for name in ('learning_rate', 'momentum', 'rho', 'beta_1', 'beta_2', 'epsilon')]
+
+
+def optim_hyper(learning_rate=0.001, momentum=0.0, rho=0.9, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
+    return OptimHyper(float(learning_rate), float(momentum), float(rho), float(beta_1), float(beta_2), float(epsilon))
+
+
+class OptimSlot(ctypes.Structure):
+    """include/amar_hip.h: amar_optim_slot"""
+    _fields_ = [('w', ctypes.c_void_p), ('g', ctypes.c_void_p), ('s0', ctypes.c_void_p), ('s1', ctypes.c_void_p), ('s2', ctypes.c_void_p),
+                ('n', ctypes.c_int64), ('first_block', ctypes.c_int64), ('l2', ctypes.c_float), ('g_groups', ctypes.c_int32)]
+
+
+def optim_state_arrays(rule, flags=0, momentum=0.0):
+    """How many state arrays (0 .. 3) a parameter needs under this rule."""
+    count = load().amar_optim_state_arrays(int(rule), int(flags), float(momentum))
+    _check(count if count < 0 else 0, 'amar_optim_state_arrays')
+    return count
+
+
+def optim_advance(state, rule, flags, hyper):
+    if state.numel() != OPTIM_STATE_FLOATS or not state.is_contiguous():
+        raise ValueError("optim_advance: state must be {} contiguous floats".format(OPTIM_STATE_FLOATS))
+    _check(load().amar_optim_advance_f32(_ptr(state, torch.float32, 'state'), int(rule), int(flags), ctypes.byref(hyper), _stream()),
+           'amar_optim_advance_f32')
+
+
+def optim(rule, flags, hyper, w, g, arrays, state, l2=0.0):
+    """One tensor under `rule`: arrays = its state arrays in the header's order (the first optim_state_arrays are used)."""
+    arrays = list(arrays) + [None] * (3 - len(arrays))
+    if not all(t.is_contiguous() and t.numel() == w.numel() for t in [w, g] + [a for a in arrays if a is not None]):
+        raise ValueError("optim: contiguous tensors of equal size expected")
+    if state.numel() != OPTIM_STATE_FLOATS:
+        raise ValueError("optim: state must be {} floats".format(OPTIM_STATE_FLOATS))
+    code = load().amar_optim_f32(int(rule), int(flags), ctypes.byref(hyper), _ptr(w, torch.float32, 'w'), _ptr(g, torch.float32, 'g'),
+                                 _ptr(arrays[0], torch.float32, 's0'), _ptr(arrays[1], torch.float32, 's1'),
+                                 _ptr(arrays[2], torch.float32, 's2'), w.numel(), _ptr(state, torch.float32, 'state'), float(l2), _stream())
+    _check(code, 'amar_optim_f32')
+
+
+def optim_slot_table(entries):
+    """entries: [(w, g, [state arrays], l2)] contiguous fp32 tensors (g: a tensor or a DeferredGradient) -> (host uint8 tensor holding the
+    slot table, total blocks): adam_slot_table for amar_optim_multi_f32."""
+    table = (OptimSlot * len(entries))()
+    block = 0
+    for k, (w, g, arrays, l2) in enumerate(entries):
+        groups = 0
+        if isinstance(g, DeferredGradient):                          # partial gradients [groups][n] left by dense_bwd(defer=True)
+            g, groups = g.partials, g.groups
+            if g.numel() != groups * w.numel():
+                raise ValueError("optim_slot_table: deferred gradient of the wrong size")
+        elif g.numel() != w.numel():
+            raise ValueError("optim_slot_table: gradient of the wrong size")
+        arrays = list(arrays)
+        if len(arrays) > 3 or not (w.is_contiguous() and g.is_contiguous()) or \
+                not all(a.is_contiguous() and a.numel() == w.numel() for a in arrays):
+            raise ValueError("optim_slot_table: at most three state arrays, contiguous tensors of equal size expected")
+        for a in arrays:
+            _ptr(a, torch.float32, 'state array')
+        ptrs = [a.data_ptr() for a in arrays] + [None] * (3 - len(arrays))
+        table[k] = OptimSlot(_ptr(w, torch.float32, 'w'), _ptr(g, torch.float32, 'g'), ptrs[0], ptrs[1], ptrs[2], w.numel(), block,
+                             float(l2), int(groups))
+        block += (w.numel() + 1023) // 1024
+    host = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).clone()
+    return host, block
+
+
+def optim_multi(rule, flags, hyper, table_dev, n_slots, total_blocks, state, reg_scale=0.0, loss_acc=None):
+    if state.numel() != OPTIM_STATE_FLOATS:
+        raise ValueError("optim_multi: state must be {} floats".format(OPTIM_STATE_FLOATS))
+    code = load().amar_optim_multi_f32(int(rule), int(flags), ctypes.byref(hyper), ctypes.c_void_p(table_dev.data_ptr()), n_slots,
+                                       total_blocks, _ptr(state, torch.float32, 'state'), float(reg_scale),
+                                       _ptr(loss_acc, torch.float32, 'loss_acc'), _stream())
+    _check(code, 'amar_optim_multi_f32')
 
 
 def sum_into(x, acc, scale=1.0):

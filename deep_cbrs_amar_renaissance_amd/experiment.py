@@ -95,13 +95,59 @@ class AttrDict(dict):
 
 
 class Adam:
-    """Optimizer placeholder with Keras' constructor (config.yaml:52-56); used once training lands."""
+    """keras.optimizers.Adam's constructor (config.yaml:52-56); amsgrad=True selects the AMSGrad rule.  The optimizer classes only carry
+    their rule and hyper-parameters: training.py keeps the state and runs the update on the device."""
+    rule = 'Adam'
+
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False, **kwargs):
+        self.learning_rate, self.beta_1, self.beta_2, self.epsilon, self.amsgrad = learning_rate, beta_1, beta_2, epsilon, bool(amsgrad)
+        if self.amsgrad:
+            self.rule = 'AMSGrad'
+
+
+class SGD:
+    rule = 'SGD'
+
+    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, **kwargs):
+        self.learning_rate, self.momentum, self.nesterov = learning_rate, momentum, bool(nesterov)
+
+
+class RMSprop:
+    rule = 'RMSprop'
+
+    def __init__(self, learning_rate=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False, **kwargs):
+        self.learning_rate, self.rho, self.momentum, self.epsilon, self.centered = learning_rate, rho, momentum, epsilon, bool(centered)
+
+
+class Adagrad:
+    rule = 'Adagrad'
+
+    def __init__(self, learning_rate=0.001, initial_accumulator_value=0.1, epsilon=1e-7, **kwargs):
+        self.learning_rate, self.initial_accumulator_value, self.epsilon = learning_rate, initial_accumulator_value, epsilon
+
+
+class Adamax:
+    rule = 'Adamax'
 
     def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, **kwargs):
         self.learning_rate, self.beta_1, self.beta_2, self.epsilon = learning_rate, beta_1, beta_2, epsilon
 
 
-OPTIMIZERS = {'Adam': Adam}
+class Nadam:
+    rule = 'Nadam'
+
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, **kwargs):
+        self.learning_rate, self.beta_1, self.beta_2, self.epsilon = learning_rate, beta_1, beta_2, epsilon
+
+
+OPTIMIZERS = {cls.__name__: cls for cls in (Adam, SGD, RMSprop, Adagrad, Adamax, Nadam)}
+
+
+def optimizer_class(name):
+    """`getattr(tf.keras.optimizers, name)` of the reference (src/experiment.py:111) for the rules that train on the device."""
+    if name not in OPTIMIZERS:
+        raise ValueError("optimizer '{}' is not supported: choose one of {} (Adam takes amsgrad: True)".format(name, ', '.join(sorted(OPTIMIZERS))))
+    return OPTIMIZERS[name]
 
 
 class Experimenter:
@@ -141,7 +187,7 @@ class Experimenter:
 
     def _retrieve_classes(self):
         """Object classes from name strings (experiment.py:107-118)."""
-        self.optimizer_class = OPTIMIZERS[self.config.parameters.optimizer.name]
+        self.optimizer_class = optimizer_class(self.config.parameters.optimizer.name)
         model_module, model_class = self.config.model.name.split('.')
         module = __import__(models_pkg.__name__ + '.' + model_module, fromlist=[model_class])
         self.model_class = getattr(module, model_class)

@@ -678,10 +678,53 @@ class DeviceSampler:
         capi.bpr_sample(self.pos_ptr, self.pos_ids, self.neg_ptr, self.neg_ids, self.n_users, self.seed, self.step, u, i, y)
 
 
-class Trainer:
-    """Holds the Adam state of a Basic* / HybridBert* model (single-graph, TwoStep or TwoWay stacks) and performs training batches."""
+_ADAM_HYPER = dict(learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7)
+# rule -> (AMAR_OPT_* name in capi, None = the amar_adam_* entry points; Keras' constructor defaults)
+OPTIMIZER_RULES = {
+    'Adam': (None, _ADAM_HYPER),
+    'AMSGrad': ('OPT_AMSGRAD', _ADAM_HYPER),
+    'SGD': ('OPT_SGD', dict(learning_rate=0.01, momentum=0.0, nesterov=False)),
+    'RMSprop': ('OPT_RMSPROP', dict(learning_rate=1e-3, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False)),
+    'Adagrad': ('OPT_ADAGRAD', dict(learning_rate=1e-3, initial_accumulator_value=0.1, epsilon=1e-7)),
+    'Adamax': ('OPT_ADAMAX', _ADAM_HYPER),
+    'Nadam': ('OPT_NADAM', _ADAM_HYPER),
+}
 
-    def __init__(self, model, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, bert_dim=None):
+
+class OptimizerSpec:
+    """The update rule and hyper-parameters a trainer runs: read from an optimizer object (experiment.py: `rule` + Keras' attribute
+    names; an object without a rule name means Adam) and / or keyword arguments, which win.  `key` identifies it: two optimizers with
+    equal keys train alike, so a cached trainer (and its state) is reused only for an equal key."""
+
+    def __init__(self, optimizer=None, rule=None, **hyper):
+        self.rule = rule or getattr(optimizer, 'rule', None) or 'Adam'
+        if self.rule not in OPTIMIZER_RULES:
+            raise ValueError("no update rule '{}': choose one of {}".format(self.rule, ', '.join(sorted(OPTIMIZER_RULES))))
+        code, defaults = OPTIMIZER_RULES[self.rule]
+        unknown = set(hyper) - set(defaults)
+        if unknown:
+            raise TypeError("{} has no hyper-parameter {}".format(self.rule, ', '.join(sorted(unknown))))
+        self.values = {k: type(d)(hyper[k] if k in hyper else getattr(optimizer, k, d)) for k, d in defaults.items()}
+        self.key = (self.rule, tuple(sorted(self.values.items())))
+        self.adam = code is None
+        if not self.adam:
+            self.code = getattr(capi, code)
+            self.flags = (capi.OPT_NESTEROV if self.values.get('nesterov') else 0) | (capi.OPT_CENTERED if self.values.get('centered') else 0)
+            self.hyper = capi.optim_hyper(**{k: v for k, v in self.values.items() if k in dict(capi.OptimHyper._fields_)})
+            self.n_arrays = capi.optim_state_arrays(self.code, self.flags, self.values.get('momentum', 0.0))
+        else:
+            self.n_arrays = 2
+
+    def new_arrays(self, param):
+        """The rule's state arrays for one parameter: zeros, Adagrad's accumulator at its initial value."""
+        fill = self.values.get('initial_accumulator_value', 0.0)
+        return [torch.full_like(param, fill) for _ in range(self.n_arrays)]
+
+
+class Trainer:
+    """Holds the optimizer state of a Basic* / HybridBert* model (single-graph, TwoStep or TwoWay stacks) and performs training batches."""
+
+    def __init__(self, model, optimizer=None, bert_dim=None, **hyper):
         gnn = model.gnn
         if hasattr(gnn, 'gnn_layers'):                               # one graph (gnn.py:210-264)
             self.layout, stacks = 'single', [gnn.gnn_layers]
@@ -703,14 +746,26 @@ class Trainer:
             else:
                 model.rs.build_head(model.gnn.output_dim(), model.gnn.output_dim())
         self.model, self.seq = model, seq
-        self.lr, self.b1, self.b2, self.eps = float(learning_rate), float(beta_1), float(beta_2), float(epsilon)
-        self.t = 0
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.device = self.params[0].device
-        self.m = {p: torch.zeros_like(p) for p in self.params}
-        self.v = {p: torch.zeros_like(p) for p in self.params}
+        self._init_optimizer(optimizer, hyper)
         self.head = _HybridHead(model.rs) if self.hybrid else _BasicHead(model.rs)
         self._init_dropout()
+
+    def _init_optimizer(self, optimizer, hyper):
+        """The rule (OptimizerSpec), the step count and every parameter's state arrays: Adam's m and v, or the 0 .. 3 arrays of another
+        rule together with its device state (step counter and step-dependent scalars: advanced by amar_optim_advance_f32 in the eager
+        and in the captured path alike, so the two are interchangeable step by step and Nadam's running product has one home)."""
+        self.spec = optimizer if isinstance(optimizer, OptimizerSpec) and not hyper else OptimizerSpec(optimizer, **hyper)
+        self.t = 0
+        self.opt_arrays = {p: self.spec.new_arrays(p) for p in self.params}
+        if self.spec.adam:
+            v = self.spec.values
+            self.lr, self.b1, self.b2, self.eps = v['learning_rate'], v['beta_1'], v['beta_2'], v['epsilon']
+            self.m = {p: a[0] for p, a in self.opt_arrays.items()}
+            self.v = {p: a[1] for p, a in self.opt_arrays.items()}
+        else:
+            self._opt_state = torch.zeros(capi.OPTIM_STATE_FLOATS, dtype=torch.float32, device=self.device)
 
     dropout_key, dropout_step = (), None                             # (HeadTrainer: the heads have no dropout, as in the reference)
 
@@ -822,12 +877,21 @@ class Trainer:
         finally:
             for t in tapes:
                 t.defer_reduce = False
-        capi.adam_advance(self._adam_state, self.lr, self.b1, self.b2)
+        spec = self.spec
+        if spec.adam:
+            capi.adam_advance(self._adam_state, self.lr, self.b1, self.b2)
+        else:
+            capi.optim_advance(self._opt_state, spec.code, spec.flags, spec.hyper)
         # one launch updates every parameter (a table of slots, uploaded by a captured copy from pinned memory: the
         # gradient buffers of this graph have fixed addresses) and adds the regularisation loss; one more adds the data loss
-        entries = [(prm.data.view(-1), capi.flat_gradient(grads[prm]),
-                    self.m[prm].view(-1), self.v[prm].view(-1), self._l2(prm)) for prm in self.params]
-        host, blocks = capi.adam_slot_table(entries)
+        if spec.adam:
+            entries = [(prm.data.view(-1), capi.flat_gradient(grads[prm]),
+                        self.m[prm].view(-1), self.v[prm].view(-1), self._l2(prm)) for prm in self.params]
+            host, blocks = capi.adam_slot_table(entries)
+        else:
+            entries = [(prm.data.view(-1), capi.flat_gradient(grads[prm]), [a.view(-1) for a in self.opt_arrays[prm]], self._l2(prm))
+                       for prm in self.params]
+            host, blocks = capi.optim_slot_table(entries)
         g['slot_host'][:host.numel()].copy_(host)                    # pinned buffer allocated before the capture began
         g['slot_bytes'] = int(host.numel())                          # uploaded ONCE, right after the capture (train_batch_graphed), into a
         g['keep'] = entries                                          # buffer allocated BEFORE it (memory of the capture's own pool is reused
@@ -837,8 +901,12 @@ class Trainer:
             g['slot_dev'][:g['slot_bytes']].copy_(g['slot_host'][:g['slot_bytes']])
         batch = float(g['u'].numel())
         capi.sum_into(terms, self._loss_sum)                         # sum of the per-pair terms = data loss x batch size
-        capi.adam_multi(g['slot_dev'], len(entries), blocks, self._adam_state, self.b1, self.b2, self.eps,
-                        reg_scale=batch, loss_acc=self._loss_sum)
+        if spec.adam:
+            capi.adam_multi(g['slot_dev'], len(entries), blocks, self._adam_state, self.b1, self.b2, self.eps,
+                            reg_scale=batch, loss_acc=self._loss_sum)
+        else:
+            capi.optim_multi(spec.code, spec.flags, spec.hyper, g['slot_dev'], len(entries), blocks, self._opt_state,
+                             reg_scale=batch, loss_acc=self._loss_sum)
 
     def train_batch_graphed(self, u_ids, i_ids, y, bert=None, graph=True):
         """One training batch replayed from a hipGraph: the forward, the reverse pass and the Adam update are ~100
@@ -913,8 +981,7 @@ class Trainer:
         if with_blocks:
             g['ub'].copy_(to_device_tensor(bert[0]))
             g['ib'].copy_(to_device_tensor(bert[1]))
-        if self._dev_t != self.t:                                    # eager steps happened in between: resynchronise the counter
-            self._adam_state[0] = float(self.t)
+        self._sync_step()                                            # eager steps happened in between: resynchronise the counter
         if 'graph' in g:
             g['graph'].replay()
         else:
@@ -994,8 +1061,8 @@ class Trainer:
         return g
 
     def _sync_step(self):
-        if self._dev_t != self.t:                                    # host steps happened in between: resynchronise the counter
-            self._adam_state[0] = float(self.t)
+        if self.spec.adam and self._dev_t != self.t:                 # host steps happened in between: resynchronise the counter
+            self._adam_state[0] = float(self.t)                      # (the other rules count on the device in both paths)
 
     def _advanced(self):
         self.t += 1
@@ -1067,6 +1134,15 @@ class Trainer:
 
     def apply_gradients(self, grads):
         self.t += 1
+        if not self.spec.adam:
+            spec = self.spec
+            with torch.no_grad():
+                capi.optim_advance(self._opt_state, spec.code, spec.flags, spec.hyper)
+                for prm in self.params:
+                    capi.optim(spec.code, spec.flags, spec.hyper, prm.data.view(-1), grads[prm].contiguous().view(-1),
+                               [a.view(-1) for a in self.opt_arrays[prm]], self._opt_state, l2=self._l2(prm))
+                    prm.add_(0)                                        # bumps the autograd version counter
+            return
         lr_t = self.lr * np.sqrt(1.0 - self.b2 ** self.t) / (1.0 - self.b1 ** self.t)
         with torch.no_grad():
             for prm in self.params:
@@ -1086,18 +1162,15 @@ class HeadTrainer(Trainer):
     """BasicRS / HybridCBRS on pre-computed embedding rows (econfigs/basic-kge.yaml, hybrid-kge.yaml): the batch Sequence
     delivers the rows themselves (datasets.py:43-77), so only the Dense stacks (and fusion weights) train."""
 
-    def __init__(self, model, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, **unused):
+    def __init__(self, model, optimizer=None, bert_dim=None, **hyper):
         if not model.built:
             raise ValueError("build the head first (one forward call, as Experimenter.build_model does)")
         self.model = model
         self.hybrid = hasattr(model, 'dense1a')
-        self.lr, self.b1, self.b2, self.eps = float(learning_rate), float(beta_1), float(beta_2), float(epsilon)
-        self.t = 0
         self.params = [p for p in model.parameters() if p.requires_grad]
-        self.m = {p: torch.zeros_like(p) for p in self.params}
-        self.v = {p: torch.zeros_like(p) for p in self.params}
-        self.head = _HybridHead(model) if self.hybrid else _BasicHead(model)
         self.device = self.params[0].device
+        self._init_optimizer(optimizer, hyper)
+        self.head = _HybridHead(model) if self.hybrid else _BasicHead(model)
         self.tables = None
 
     # -- batches as ids against tables kept on the device (round 4) ---------------------------------------------------------------
@@ -1166,12 +1239,21 @@ class HeadTrainer(Trainer):
         return loss
 
 
+def _cached_trainer(model, spec):
+    """model._trainer if it runs the currently compiled optimizer (rule and hyper-parameters equal), else None: a model compiled again
+    with another optimizer trains from fresh state (t = 0, new state arrays, new captured graphs), as Keras does."""
+    trainer = getattr(model, '_trainer', None)
+    if trainer is not None and trainer.spec.key != spec.key:
+        trainer = model._trainer = None
+    return trainer
+
+
 def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
     """Keras-style ``fit`` over a batch Sequence: ``epochs`` passes, ``on_epoch_end`` reshuffles (datasets.py:205-213)."""
-    opt = getattr(model, 'optimizer', None)
-    hp = {k: getattr(opt, k) for k in ('learning_rate', 'beta_1', 'beta_2', 'epsilon') if hasattr(opt, k)}
+    spec = OptimizerSpec(getattr(model, 'optimizer', None))
+    hp = {'optimizer': spec}
     if not hasattr(model, 'gnn'):                              # BasicRS / HybridCBRS on pre-computed rows: head-only training
-        trainer = getattr(model, '_trainer', None)
+        trainer = _cached_trainer(model, spec)
         if trainer is None:
             if not model.built and len(sequence):
                 model(sequence[0][0])                          # one forward call builds every weight (as Keras does)
@@ -1226,7 +1308,7 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
     if isinstance(sequence, UserItemGraphPosNegSample):
         return _fit_sampled(model, sequence, epochs, verbose, hp)
     ids_only = model.resident_ids(sequence) if hasattr(model, 'resident_ids') else None
-    trainer = getattr(model, '_trainer', None)
+    trainer = _cached_trainer(model, spec)
     if trainer is None:
         if hasattr(model.rs, 'dense1a') and not model.rs.built and len(sequence):
             first = sequence[0][0]
@@ -1262,7 +1344,7 @@ def _fit_sampled(model, sequence, epochs, verbose, hp):
     """fit() on the BPR sample Sequence: its lists go to the device once and every batch is drawn there (amar_bpr_sample_i32), inside
     the replayed training graph (AMAR_TRAIN_GRAPH=0: the same steps eagerly, the same ids).  len(sequence) steps per epoch; the host
     stream of __getitem__ is not read."""
-    trainer = getattr(model, '_trainer', None)
+    trainer = _cached_trainer(model, hp['optimizer'])
     if trainer is None:
         trainer = model._trainer = Trainer(model, **hp)
     sampler = trainer.sampler_for(sequence)

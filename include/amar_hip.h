@@ -596,6 +596,62 @@ int amar_sum_into_f32(const float *x, int64_t n, float scale, float *acc, amar_s
 int amar_adam_dev_f32(float *w, const float *g, float *m, float *v, int64_t n, const float *state, float beta_1, float beta_2,
                       float epsilon, float l2, amar_stream_t stream);
 
+/* ---- the other optimizers of tf.keras.optimizers (src/experiment.py:111,130-134: `parameters.optimizer.name` is a free choice) ----------
+ * SGD, RMSprop, Adagrad, Adamax, Nadam and Adam(amsgrad=True), built like the Adam entry points above (which keep their bits): a step
+ * counter and the step-dependent scalars in device memory, one launch for every parameter of a model, a single-tensor form reading the
+ * same state.  The formulas below are the contract; they restate Keras 2's optimizer_v2 classes.  Common to all rules: g' = g + 2 l2 w
+ * first (the L2 regulariser's gradient), t = 1 for the first step, `step` = state[1] of this step.  s0, s1, s2 are the rule's state arrays
+ * in the order given; a rule neither reads nor writes the arrays it does not have (their pointers may be NULL).
+ *
+ * AMAR_OPT_SGD      momentum == 0 (no array):       w -= lr g'
+ *                   momentum > 0 (s0 = a):          a = momentum a - lr g';  w += a
+ *                   ... with AMAR_OPT_NESTEROV:     a as above;  w += momentum a - lr g'  (the new a; without momentum the flag does nothing)
+ * AMAR_OPT_RMSPROP  s0 = rms:                       rms = rho rms + (1 - rho) g'^2;  d = rms
+ *                   AMAR_OPT_CENTERED (s1 = mg):    mg = rho mg + (1 - rho) g';  d = max(rms - mg^2, 0)  (the max is a stated deviation: it
+ *                                                   differs from TensorFlow only where TensorFlow returns NaN)
+ *                   momentum == 0:                  w -= lr g' / (sqrt(d) + epsilon)
+ *                   momentum > 0 (next array = mom): mom = momentum mom + lr g' / sqrt(d + epsilon);  w -= mom   (TensorFlow's fused op
+ *                                                   puts epsilon inside the root)
+ * AMAR_OPT_ADAGRAD  s0 = acc (the caller fills it with initial_accumulator_value):   acc += g'^2;  w -= lr g' / (sqrt(acc) + epsilon)
+ * AMAR_OPT_ADAMAX   s0 = m, s1 = u:                 m = b1 m + (1 - b1) g';  u = max(b2 u, |g'|);  w -= step m / (u + epsilon),
+ *                                                   step = lr / (1 - b1^t)
+ * AMAR_OPT_NADAM    s0 = m, s1 = v:                 mu_t = b1 (1 - 0.5 0.96^(0.004 t));  P_t = P_{t-1} mu_t, P_0 = 1;
+ *                                                   m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;
+ *                                                   w -= lr ((1 - mu_t) g' / (1 - P_t) + mu_{t+1} m / (1 - P_t mu_{t+1})) / (sqrt(v / (1 - b2^t)) + epsilon)
+ * AMAR_OPT_AMSGRAD  s0 = m, s1 = v, s2 = vhat:      Adam's m and v;  vhat = max(vhat, v);  w -= step m / (sqrt(vhat) + epsilon),
+ *                                                   step = Adam's lr_t = lr sqrt(1 - b2^t) / (1 - b1^t)
+ *
+ * The device state is AMAR_OPTIM_STATE_FLOATS floats, zero before the first step:
+ *   [0] t   [1] step (lr; Adamax, AMSGrad: as above)   and for Nadam   [2] mu_t   [3] mu_{t+1}   [4] P_t (the running product: read back
+ *   at the next step)   [5] 1 - b2^t   [6] lr (1 - mu_t) / (1 - P_t)   [7] lr mu_{t+1} / (1 - P_t mu_{t+1})   (0 for the other rules).
+ * amar_optim_advance_f32 (one thread, ordinary stores) sets [0] = t + 1 and the scalars of that step, computed in double from the float32
+ * hyper-parameters.  The update kernels read lr from [1], the two Nadam coefficients from [6] and [7]: nothing that changes from step to
+ * step is an argument, so a captured training batch replays as it is.
+ * The single-tensor and the multi-slot form share one element function per rule (fused products written out, nothing else fused): they
+ * give the same bits on the same element.  Unknown rule, flags the rule does not have, momentum < 0, null pointers (of arrays the rule
+ * has), negative sizes: AMAR_EINVAL. */
+#define AMAR_OPT_SGD      1
+#define AMAR_OPT_RMSPROP  2
+#define AMAR_OPT_ADAGRAD  3
+#define AMAR_OPT_ADAMAX   4
+#define AMAR_OPT_NADAM    5
+#define AMAR_OPT_AMSGRAD  6
+#define AMAR_OPT_NESTEROV 0x100   /* flag of AMAR_OPT_SGD     */
+#define AMAR_OPT_CENTERED 0x200   /* flag of AMAR_OPT_RMSPROP */
+#define AMAR_OPTIM_STATE_FLOATS 8
+/* HOST struct, read when the call is made; a rule ignores the members it does not use */
+typedef struct amar_optim_hyper { float learning_rate, momentum, rho, beta_1, beta_2, epsilon; } amar_optim_hyper;
+/* how many state arrays (0 .. 3) a slot of this rule needs */
+int amar_optim_state_arrays(int32_t rule, int32_t flags, float momentum);
+int amar_optim_advance_f32(float *state, int32_t rule, int32_t flags, const amar_optim_hyper *hyper, amar_stream_t stream);
+int amar_optim_f32(int32_t rule, int32_t flags, const amar_optim_hyper *hyper, float *w, const float *g, float *s0, float *s1, float *s2,
+                   int64_t n, const float *state, float l2, amar_stream_t stream);
+/* All parameters of a model in one launch: the slot table (device memory), blocks of 1024 elements, first_block, g_groups (partials [G][n]
+ * added in the order 0 .. G-1: the bits of an explicit reduction), reg_scale and loss_acc mean what they mean for amar_adam_multi_f32. */
+typedef struct amar_optim_slot { float *w; const float *g; float *s0; float *s1; float *s2; int64_t n; int64_t first_block; float l2; int32_t g_groups; } amar_optim_slot;
+int amar_optim_multi_f32(int32_t rule, int32_t flags, const amar_optim_hyper *hyper, const amar_optim_slot *slots, int32_t n_slots,
+                         int64_t total_blocks, const float *state, float reg_scale, float *loss_acc, amar_stream_t stream);
+
 /* ---- BPR training (utilities/losses.py:BPRLoss, data/datasets.py:UserItemGraphPosNegSample) ----------------------------------
  * amar_bpr_grad_f32    the pairwise loss of src/utilities/losses.py:15-25 on the probability column p ([B], or a strided [B, 1] with
  *                      leading dimension ldp): h = B / 2 (an odd B drops its last element), s_j = sigmoid(p[j] - p[h + j]),
