@@ -78,6 +78,7 @@ SIGNATURES = {
     'amar_dense_bwd_workspace_floats': (ctypes.c_int64, [_I64, _I32, _I32]),
     'amar_dense_bwd_groups': (ctypes.c_int64, [_I64]),
     'amar_dense_bwd_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I32, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I32, _I32, _P]),
+    'amar_dense_bwd_route': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I32, _P, _I64, _P, _P, _P, _I64, _I64, _I32, _I32, _P]),
     'amar_bce_grad_f32': (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P]),
     'amar_scatter_add_rows_f32': (ctypes.c_int, [_P, _I64, _P, _I32, _P, _I64, _I64, _I32, _P]),
     'amar_add_inplace_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I32, _F32, _P]),
@@ -878,7 +879,13 @@ class DeferredGradient:
         self.partials, self.groups, self.shape = partials, int(groups), tuple(shape)
 
     def materialize(self):
-        return self.partials.view(self.groups, -1).sum(0).view(self.shape)
+        """The sum in GROUP ORDER, starting from 0 — the order of the library's own reduction, so the bits are those of a call without
+        `defer` (a library-chosen order, as torch.sum's, need not be)."""
+        parts = self.partials.view(self.groups, -1)
+        total = torch.zeros_like(parts[0])
+        for g in range(self.groups):
+            total += parts[g]
+        return total.view(self.shape)
 
 
 def flat_gradient(g):
@@ -1285,6 +1292,35 @@ def dense_bwd(X, Y, dY, W, act, workspace, dX=None, dW=None, db=None, defer=Fals
         return (DeferredGradient(workspace[4:4 + nw], g, (K, N)) if dW is not None else None,
                 DeferredGradient(workspace[4 + nw:4 + nw + g * N], g, (N,)) if db is not None else None)
     return None
+
+
+class DenseBwdRouteInfo(ctypes.Structure):
+    """include/amar_hip.h: amar_dense_bwd_route_info"""
+    _fields_ = [(name, ctypes.c_int32) for name in ('kernel', 'mt', 'kp', 'np', 'vec', 'x_scalar', 'subtiles', 'fold', 'fold_launch')] + \
+               [('launched_groups', ctypes.c_int64), ('out_groups', ctypes.c_int64)]
+
+    def as_dict(self):
+        d = {name: int(getattr(self, name)) for name, _ in self._fields_}
+        d['kernel'] = 'rows' if d['kernel'] == 1 else 'tile'
+        d['vec'], d['x_scalar'], d['fold_launch'] = bool(d['vec']), bool(d['x_scalar']), bool(d['fold_launch'])
+        return d
+
+
+def dense_bwd_route(X, Y, dY, W, act, workspace=None, dX=None, dW=None, db=None, defer=False, dZ=None, accumulate_dx=False, K=None):
+    """Which kernel dense_bwd takes for these operands (amar_dense_bwd_route: host only, nothing is launched; the launcher asks the same
+    function).  A dict: kernel 'tile' | 'rows', mt (tile), kp / np (rows), vec, x_scalar, subtiles, launched_groups, fold, fold_launch,
+    out_groups."""
+    M, N = dY.shape
+    K = W.shape[0] if W is not None else (X.shape[1] if X is not None else int(K or 1))
+    info = DenseBwdRouteInfo()
+    code = load().amar_dense_bwd_route(
+        _ptr(X, torch.float32, 'X'), _ld(X, 'X') if X is not None else 0, _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y') if Y is not None else 0,
+        _ptr(dY, torch.float32, 'dY'), _ld(dY, 'dY'), _ptr(W, torch.float32, 'W'),
+        ACT_CODES[act] | (DENSE_BWD_DEFER if defer else 0) | (DENSE_BWD_ACCUM_DX if accumulate_dx else 0),
+        _ptr(dX, torch.float32, 'dX'), _ld(dX, 'dX') if dX is not None else 0, _ptr(dW, torch.float32, 'dW'), _ptr(db, torch.float32, 'db'),
+        _ptr(dZ, torch.float32, 'dZ'), _ld(dZ, 'dZ') if dZ is not None else 0, M, K, N, ctypes.byref(info))
+    _check(code, 'amar_dense_bwd_route')
+    return info.as_dict()
 
 
 def bce_grad(p, y, dz, loss_terms):

@@ -1547,11 +1547,14 @@ int64_t amar_dense_bwd_workspace_floats(int64_t M, int32_t K, int32_t N) {
     return 4 + (p.out_groups + (p.fold > 1 ? p.out_groups * p.fold : 0)) * ((int64_t)K * N + N);   // the partials a caller sees first, the raw ones behind them
 }
 
-int amar_dense_bwd_f32(const float *X, int64_t ldx, const float *Y, int64_t ldy, const float *dY, int64_t lddy, const float *W,
-                       int32_t act, float *dX, int64_t lddx, float *dW, float *db, float *dZ, int64_t lddz, float *workspace,
-                       int64_t M, int32_t K, int32_t N, amar_stream_t stream) {
-    const bool defer = (act & AMAR_DENSE_BWD_DEFER) != 0, accum = (act & AMAR_DENSE_BWD_ACCUM_DX) != 0;
-    act &= ~(AMAR_DENSE_BWD_DEFER | AMAR_DENSE_BWD_ACCUM_DX);
+// Which kernel a call takes, and how it is cut: decided HERE and nowhere else — amar_dense_bwd_f32 launches what this returns and
+// amar_dense_bwd_route reports it, so a test can assert the form it exercises.  Pointers are looked at for their alignment only.
+struct DenseBwdRoute {
+    DenseBwdPlan plan; bool use_x, use_w, use_y, vec_rest, vec_x, vec, rows_form, need_fold; int fold; int64_t n_raw; int mt, kp, np;
+};
+static int dense_bwd_route(const float *X, int64_t ldx, const float *Y, int64_t ldy, const float *dY, int64_t lddy, const float *W, int32_t act,
+                           const float *dX, int64_t lddx, const float *dW, const float *db, const float *dZ, int64_t lddz, bool have_workspace,
+                           int64_t M, int32_t K, int32_t N, DenseBwdRoute &r) {
     if (M < 0 || K < 1 || N < 1 || !dY || lddy < N || (!dX && !dW && !db && !dZ)) return AMAR_EINVAL;
     if (dZ && lddz < N) return AMAR_EINVAL;
     if (Y && ldy < N) return AMAR_EINVAL;
@@ -1559,30 +1562,71 @@ int amar_dense_bwd_f32(const float *X, int64_t ldx, const float *Y, int64_t ldy,
     if (act != AMAR_ACT_NONE && !Y) return AMAR_EINVAL;
     if (dX && (!W || lddx < K)) return AMAR_EINVAL;
     if (dW && (!X || ldx < K)) return AMAR_EINVAL;
-    if ((dW || db) && !workspace) return AMAR_EINVAL;
+    if ((dW || db) && !have_workspace) return AMAR_EINVAL;
     if (K > DB_MAXD || N > DB_MAXD) return AMAR_EUNSUPPORTED;
     if (M == 0) return AMAR_EUNSUPPORTED;                             // (an empty batch: the separate kernels define the zero gradients)
-    const DenseBwdPlan plan = dense_bwd_plan(M);
+    r.plan = dense_bwd_plan(M);
+    const DenseBwdPlan &plan = r.plan;
+    const int Kp = (K + 15) & ~15, Np = (N + 15) & ~15;
+    // 16-byte loads where every operand allows them (K, N and the leading dimensions multiples of 4 floats, 16-byte aligned bases)
+    r.use_x = dW != nullptr; r.use_w = dX != nullptr; r.use_y = act != AMAR_ACT_NONE;
+    r.vec_rest = (N & 3) == 0 && (lddy & 3) == 0 && amar_aligned16(dY) && (!r.use_y || ((ldy & 3) == 0 && amar_aligned16(Y))) &&
+                 (!r.use_w || ((K & 3) == 0 && amar_aligned16(W)));
+    r.vec_x = !r.use_x || ((K & 3) == 0 && (ldx & 3) == 0 && amar_aligned16(X));
+    r.vec = r.vec_rest && r.vec_x;
+    // many rows of narrow operands (a convolution layer's reverse pass over every node): the row-walking kernel, `fold` of its workgroups
+    // per partial the caller sees
+    r.rows_form = plan.fold > 1 && r.vec_rest && K <= 32 && N <= 32 && (!dX || ((lddx & 3) == 0 && amar_aligned16(dX))) &&
+                  (!dZ || ((lddz & 3) == 0 && amar_aligned16(dZ)));               // (X may be read by single floats there)
+    // the row-walking kernel up to 32 768 rows: one workgroup per partial the caller sees, no fold launch (9 228 rows at ml1m(s=1): 49
+    // workgroups of three passes); beyond: up to 64 workgroups per partial
+    r.need_fold = plan.fold > 1 && !(r.rows_form && M <= 32768);
+    r.fold = !r.need_fold ? 1 : r.rows_form ? (plan.fold < 64 ? plan.fold : 64) : plan.fold;
+    r.n_raw = r.rows_form ? plan.out_groups * r.fold : plan.launch_groups;     // workgroups of the main launch = raw partials
+    r.mt = (Kp >> 4) * (Np >> 4) <= 16 ? 4 : 16;                      // (tile kernel: 16 x 16 tiles of dW per wave)
+    r.kp = K <= 8 ? 8 : (K <= 16 ? 16 : 32);                          // (row-walking kernel: its compile-time widths)
+    r.np = N <= 8 ? 8 : (N <= 16 ? 16 : 32);
+    return AMAR_OK;
+}
+
+int amar_dense_bwd_route(const float *X, int64_t ldx, const float *Y, int64_t ldy, const float *dY, int64_t lddy, const float *W, int32_t act,
+                         float *dX, int64_t lddx, float *dW, float *db, float *dZ, int64_t lddz, int64_t M, int32_t K, int32_t N,
+                         amar_dense_bwd_route_info *out) {
+    if (!out) return AMAR_EINVAL;
+    act &= ~(AMAR_DENSE_BWD_DEFER | AMAR_DENSE_BWD_ACCUM_DX);
+    DenseBwdRoute r;
+    if (const int rc = dense_bwd_route(X, ldx, Y, ldy, dY, lddy, W, act, dX, lddx, dW, db, dZ, lddz, true, M, K, N, r)) return rc;
+    out->kernel = r.rows_form ? AMAR_DENSE_BWD_KERNEL_ROWS : AMAR_DENSE_BWD_KERNEL_TILE;
+    out->mt = r.rows_form ? 0 : r.mt;
+    out->kp = r.rows_form ? r.kp : 0;
+    out->np = r.rows_form ? r.np : 0;
+    out->vec = r.rows_form ? 1 : (r.vec ? 1 : 0);                     // (the row-walking kernel reads everything but X by 16 bytes)
+    out->x_scalar = r.rows_form && r.use_x && !r.vec_x ? 1 : 0;
+    out->subtiles = r.rows_form ? 0 : r.plan.sub;
+    out->fold = r.fold;
+    out->fold_launch = r.need_fold && (dW || db) ? 1 : 0;
+    out->launched_groups = r.n_raw;
+    out->out_groups = r.plan.out_groups;
+    return AMAR_OK;
+}
+
+int amar_dense_bwd_f32(const float *X, int64_t ldx, const float *Y, int64_t ldy, const float *dY, int64_t lddy, const float *W,
+                       int32_t act, float *dX, int64_t lddx, float *dW, float *db, float *dZ, int64_t lddz, float *workspace,
+                       int64_t M, int32_t K, int32_t N, amar_stream_t stream) {
+    const bool defer = (act & AMAR_DENSE_BWD_DEFER) != 0, accum = (act & AMAR_DENSE_BWD_ACCUM_DX) != 0;
+    act &= ~(AMAR_DENSE_BWD_DEFER | AMAR_DENSE_BWD_ACCUM_DX);
+    DenseBwdRoute route;
+    if (const int rc = dense_bwd_route(X, ldx, Y, ldy, dY, lddy, W, act, dX, lddx, dW, db, dZ, lddz, workspace != nullptr, M, K, N, route)) return rc;
+    const DenseBwdPlan &plan = route.plan;
     const int sub = plan.sub;
     const int64_t groups = plan.out_groups;
     const int64_t size_w = dW ? (int64_t)K * N : 0, size_b = db ? (int64_t)N : 0;
     const int Kp = (K + 15) & ~15, Np = (N + 15) & ~15;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // 16-byte loads where every operand allows them (K, N and the leading dimensions multiples of 4 floats, 16-byte aligned bases)
-    const bool use_x = dW != nullptr, use_w = dX != nullptr, use_y = act != AMAR_ACT_NONE;
-    const bool vec_rest = (N & 3) == 0 && (lddy & 3) == 0 && amar_aligned16(dY) && (!use_y || ((ldy & 3) == 0 && amar_aligned16(Y))) &&
-                          (!use_w || ((K & 3) == 0 && amar_aligned16(W)));
-    const bool vec_x = !use_x || ((K & 3) == 0 && (ldx & 3) == 0 && amar_aligned16(X));
-    const bool vec = vec_rest && vec_x;
-    // many rows of narrow operands (a convolution layer's reverse pass over every node): the row-walking kernel, `fold` of its workgroups
-    // per partial the caller sees
-    const bool rows_form = plan.fold > 1 && vec_rest && K <= 32 && N <= 32 && (!dX || ((lddx & 3) == 0 && amar_aligned16(dX))) &&
-                           (!dZ || ((lddz & 3) == 0 && amar_aligned16(dZ)));      // (X may be read by single floats there)
-    // the row-walking kernel up to 32 768 rows: one workgroup per partial the caller sees, no fold launch (9 228 rows at ml1m(s=1): 49
-    // workgroups of three passes); beyond: up to 64 workgroups per partial
-    const bool need_fold = plan.fold > 1 && !(rows_form && M <= 32768);
-    const int fold = !need_fold ? 1 : rows_form ? (plan.fold < 64 ? plan.fold : 64) : plan.fold;
-    const int64_t n_raw = rows_form ? groups * fold : plan.launch_groups;      // workgroups of the main launch = raw partials
+    const bool use_x = route.use_x, use_w = route.use_w, use_y = route.use_y, vec_x = route.vec_x, vec = route.vec;
+    const bool rows_form = route.rows_form, need_fold = route.need_fold;
+    const int fold = route.fold;
+    const int64_t n_raw = route.n_raw;
     float *part_w = dW ? workspace + 4 : nullptr;                    // [groups][K N], then [groups][N]: what the caller (or the Adam launch) adds
     float *part_b = db ? workspace + 4 + groups * size_w : nullptr;
     float *raw_w = part_w, *raw_b = part_b;                          // where the workgroups write: the same, unless a fold launch follows
@@ -1595,8 +1639,7 @@ int amar_dense_bwd_f32(const float *X, int64_t ldx, const float *Y, int64_t ldy,
                    dZ, lddz, accum ? 1 : 0, vec_x ? 0 : 1};
     if (rows_form) {
 #define AMAR_DBR_LAUNCH(KK, NN) hipLaunchKernelGGL((dense_bwd_rows_kernel<KK, NN>), dim3((unsigned)n_raw), dim3(256), 0, st, a)
-        const int kc = K <= 8 ? 0 : (K <= 16 ? 1 : 2), nc = N <= 8 ? 0 : (N <= 16 ? 1 : 2);
-        switch (3 * kc + nc) {
+        switch (3 * (route.kp >> 4) + (route.np >> 4)) {              // (8, 16, 32 -> 0, 1, 2)
         case 0: AMAR_DBR_LAUNCH(8, 8); break;
         case 1: AMAR_DBR_LAUNCH(8, 16); break;
         case 2: AMAR_DBR_LAUNCH(8, 32); break;
@@ -1610,7 +1653,7 @@ int amar_dense_bwd_f32(const float *X, int64_t ldx, const float *Y, int64_t ldy,
 #undef AMAR_DBR_LAUNCH
     } else {
         const size_t lds = ((size_t)DB_ROWS * (Kp + 2) + (size_t)DB_ROWS * (Np + 2) + (size_t)Kp * (Np + 2)) * sizeof(float);
-        const bool small = (Kp >> 4) * (Np >> 4) <= 16;
+        const bool small = route.mt == 4;
 #define AMAR_DB_LAUNCH(MT, VV)                                                                                           \
     do {                                                                                                                 \
         static bool allowed[AMAR_MAX_DEVICES] = {};                                                                      \

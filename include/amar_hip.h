@@ -552,6 +552,29 @@ int amar_dense_stack_bwd_pair_f32(const amar_dense_stack_bwd_desc *s0, const ama
 #define AMAR_DENSE_BWD_ACCUM_DX 0x200
 int64_t amar_dense_bwd_groups(int64_t M);
 int64_t amar_dense_bwd_workspace_floats(int64_t M, int32_t K, int32_t N);
+/* Which kernel an amar_dense_bwd_f32 call with these arguments takes (host only: nothing is launched, the pointers are looked at for
+ * their alignment and for NULL; `act` may carry the flags above).  The launcher asks the same function, so the two cannot disagree.
+ * Returns what the launcher's argument checks return (a workspace is taken as given).
+ *   kernel           AMAR_DENSE_BWD_KERNEL_TILE (64-row tiles, matrix instructions) or _ROWS (the row-walking kernel: M > 4 096, K, N <= 32,
+ *                    dY / Y / W / dX / dZ 16-byte aligned with leading dimensions that are multiples of 4 floats)
+ *   mt               tile kernel: 16 x 16 tiles of dW per wave, 4 or 16 (0 for the row-walking kernel)
+ *   kp, np           row-walking kernel: its compile-time widths, each 8, 16 or 32 (0 for the tile kernel)
+ *   vec              operands read by 16-byte loads (tile kernel: all of them or none; row-walking kernel: always 1)
+ *   x_scalar         row-walking kernel: X read by single floats (K not a multiple of 4, or X unaligned)
+ *   subtiles         tile kernel: 64-row tiles per workgroup (0 for the row-walking kernel)
+ *   launched_groups  workgroups of the main launch = raw partials
+ *   fold             raw partials added per partial the caller sees (1: the workgroups write the visible partials themselves)
+ *   fold_launch      1 if a launch that folds the raw partials follows (only where dW or db is asked for)
+ *   out_groups       amar_dense_bwd_groups(M) */
+#define AMAR_DENSE_BWD_KERNEL_TILE 0
+#define AMAR_DENSE_BWD_KERNEL_ROWS 1
+typedef struct amar_dense_bwd_route_info {
+    int32_t kernel, mt, kp, np, vec, x_scalar, subtiles, fold, fold_launch;
+    int64_t launched_groups, out_groups;
+} amar_dense_bwd_route_info;
+int amar_dense_bwd_route(const float *X, int64_t ldx, const float *Y, int64_t ldy, const float *dY, int64_t lddy, const float *W, int32_t act,
+                         float *dX, int64_t lddx, float *dW, float *db, float *dZ, int64_t lddz, int64_t M, int32_t K, int32_t N,
+                         amar_dense_bwd_route_info *out);
 int amar_dense_bwd_f32(const float *X, int64_t ldx, const float *Y, int64_t ldy, const float *dY, int64_t lddy, const float *W,
                        int32_t act, float *dX, int64_t lddx, float *dW, float *db, float *dZ, int64_t lddz, float *workspace,
                        int64_t M, int32_t K, int32_t N, amar_stream_t stream);

@@ -102,7 +102,10 @@ def test_training_kernels(hip):
 @pytest.mark.parametrize('M,K,N,act', [(1024, 48, 48, 'relu'), (85, 96, 64, 'relu'), (1024, 64, 1, 'sigmoid'), (1024, 64, 1, None),
                                          (9228, 16, 16, None), (1, 24, 24, 'relu'), (300, 128, 128, 'relu'), (64, 5, 3, 'sigmoid'), (40000, 32, 8, 'relu'),
                                          (600001, 8, 8, 'relu'), (40000, 8, 8, 'relu'), (40000, 16, 16, None), (70000, 32, 32, 'relu'), (40000, 16, 8, 'sigmoid'),
-                                         (40000, 8, 32, None), (40000, 24, 12, 'relu'), (40000, 6, 8, 'relu'), (9228, 1, 8, None), (40000, 2, 16, None)])     # (K = 1: a GAT attention vector's gradient, X read by single floats)                     # (a convolution layer's reverse pass over every node: folded partials, two tiles per workgroup)
+                                         (40000, 8, 32, None), (40000, 24, 12, 'relu'), (40000, 6, 8, 'relu'), (9228, 1, 8, None), (40000, 2, 16, None)])
+# (dY and dX below are 8 and 4 bytes off a 16-byte boundary, so ALL of these run the scalar tile kernel, dense_bwd_kernel<4 | 16, false> — the
+# M > 4 096 cases with folded partials, 600 001 with two tiles per workgroup.  The row-walking kernel a convolution layer's reverse pass
+# takes over every node, and the tile kernel's 16-byte loads, are tests/test_dense_bwd_routes_gpu.py's.)
 def test_dense_bwd_fused(hip, M, K, N, act):
     """amar_dense_bwd_f32 (round 4: the reverse pass of one Dense layer in two launches instead of four — act', dX = dZ . W^T, dW = X^T . dZ, db) against
     float64 arithmetic and against the separate kernels it replaces; strided operands (column slices of wider buffers, as the
@@ -122,6 +125,8 @@ def test_dense_bwd_fused(hip, M, K, N, act):
     ws = hip.dense_bwd_workspace(M, K, N, DEV)
     dxw = torch.zeros((M, K + 3), device=DEV)
     dx, dw, db = dxw[:, 1:1 + K], torch.empty((K, N), device=DEV), torch.empty(N, device=DEV)
+    route = hip.dense_bwd_route(x_d, y_d if act is not None else None, dy_d, w_d, act, ws, dX=dx, dW=dw, db=db)
+    assert route['kernel'] == 'tile' and not route['vec'] and route['mt'] == (4 if -(-K // 16) * -(-N // 16) <= 16 else 16), route    # the misaligned slices: the scalar route's test
     hip.dense_bwd(x_d, y_d if act is not None else None, dy_d, w_d, act, ws, dX=dx, dW=dw, db=db)
     tol = 3e-6
     assert helpers.rel_err(dx.cpu().numpy(), want_dx) < tol and helpers.rel_err(dw.cpu().numpy(), want_dw) < tol
@@ -146,7 +151,8 @@ def test_dense_bwd_fused(hip, M, K, N, act):
     hip.dense_bwd(x_d, y_d if act is not None else None, dy_d, w_d, act, ws, dX=dx7, accumulate_dx=True)
     assert helpers.rel_err(dx7.cpu().numpy() - 1.0, want_dx) < 1e-5
     lazy_w, lazy_b = hip.dense_bwd(x_d, y_d if act is not None else None, dy_d, w_d, act, ws, dX=dx2, dW=dw2, db=db2, defer=True)
-    assert torch.equal(lazy_w.materialize(), dw) is not None and helpers.rel_err(lazy_w.materialize().cpu().numpy(), want_dw) < tol
+    assert torch.equal(lazy_w.materialize(), dw) and torch.equal(lazy_b.materialize(), db)         # the partials, added in group order: the same bits
+    assert helpers.rel_err(lazy_w.materialize().cpu().numpy(), want_dw) < tol
     assert helpers.rel_err(lazy_b.materialize().cpu().numpy(), want_db) < tol and 1 <= lazy_w.groups == lazy_b.groups <= 64
     # against the kernels it replaces (other summation orders: tolerance, not bits)
     dz_d = torch.empty((M, N), device=DEV)
@@ -396,6 +402,51 @@ def test_gradients_match_autograd_oracle(hip, cls, graph):
         got = grads[prm].cpu().numpy().reshape(gw.shape).astype(np.float64)
         got += 2 * trainer._l2(prm) * prm.detach().cpu().numpy().reshape(gw.shape)
         # (absolute floor: d/d(attn_kernel_self) vanishes where a row's softmax is shift-invariant in s_i)
+        assert np.abs(got - gw).max() <= 2e-4 * np.abs(gw).max() + 1e-10, tuple(prm.shape)
+
+
+@pytest.mark.parametrize('cls', ['BasicGCN', 'BasicGAT'])
+def test_gradients_match_autograd_oracle_above_4096_nodes(hip, cls, monkeypatch):
+    """4 200 nodes: past 64 tiles of 64 rows the reverse pass of a convolution layer over every node takes the row-walking kernel
+    (dense_bwd_rows_kernel), which no graph of the other gradient tests reaches.  Every dense_bwd call of the step is asked for its
+    route on its real operands (capi.dense_bwd_route) before it runs; loss and gradients against torch autograd in float64."""
+    from deep_cbrs_amar_renaissance_amd import capi, engine, training
+    from deep_cbrs_amar_renaissance_amd.models import basic
+    engine.set_seed(5)
+    g = helpers.tiny_graph(n_users=2600, n_items=1600, n_ratings=20000, seed=9)
+    n_nodes = g['adj'].shape[0]
+    assert n_nodes == 4200
+    model = getattr(basic, cls)(g['adj'], **CFG)
+    helpers.randomize_biases(model, seed=6)
+    y = np.random.default_rng(2).integers(0, 2, len(g['u_ids']))
+    routes, launch = [], capi.dense_bwd
+
+    def recording(*args, **kwargs):
+        M, N = args[2].shape
+        K = args[3].shape[0] if args[3] is not None else (args[0].shape[1] if args[0] is not None else kwargs.get('K') or 1)
+        routes.append(dict(capi.dense_bwd_route(*args, **kwargs), M=M, K=K, N=N))
+        return launch(*args, **kwargs)
+
+    monkeypatch.setattr(capi, 'dense_bwd', recording)
+    trainer = training.Trainer(model)
+    loss, grads = trainer.loss_and_grads(g['u_ids'], g['i_ids'], y)
+    monkeypatch.setattr(capi, 'dense_bwd', launch)
+    node_calls = [r for r in routes if r['M'] == n_nodes]
+    print(node_calls)
+    # two layers: GCN (act' + db + dZ) and (dX += , dW); GAT two attention vectors (X one column), the bias, and (dX +=, dW)
+    assert len(node_calls) == (4 if cls == 'BasicGCN' else 8)
+    assert all(r['kernel'] == 'rows' and r['out_groups'] == 33 and r['launched_groups'] == 33 and not r['fold_launch'] for r in node_calls), node_calls
+    if cls == 'BasicGAT':
+        assert sum(r['x_scalar'] and r['K'] == 1 for r in node_calls) == 4, node_calls
+    want_loss, want, _ = otrain.torch_model_grads(g['adj'], helpers.gnn_to_oracle(model.gnn), helpers.basic_head_to_oracle(model.rs),
+                                                  g['u_ids'], g['i_ids'], y, l2=1e-4)
+    assert abs(loss - want_loss) < 1e-5
+    flat = _flatten_oracle_grads(model, want)
+    assert set(flat) == set(grads)
+    for prm, gw in flat.items():
+        got = grads[prm].cpu().numpy().reshape(gw.shape).astype(np.float64)
+        got += 2 * trainer._l2(prm) * prm.detach().cpu().numpy().reshape(gw.shape)
+        print(tuple(prm.shape), float(np.abs(got - gw).max()), float(np.abs(gw).max()))
         assert np.abs(got - gw).max() <= 2e-4 * np.abs(gw).max() + 1e-10, tuple(prm.shape)
 
 
