@@ -49,6 +49,8 @@ SIGNATURES = {
     'amar_sage_aggregate_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _I64, _P, _I64, _I32, _I32, _I32, _P]),
     'amar_sage_aggregate_bwd_f32': (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I32, _P, _P, _I64, _I32, _I32, _P]),
     'amar_gat_layer_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _P]),
+    'amar_rowwise_xw_heads_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I32, _I32, _P, _I64, _P, _P, _P, _I32, _P]),
+    'amar_gat_heads_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _P]),
     'amar_dense_f32': (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _P]),
     'amar_dense_split_bytes': (ctypes.c_int64, [_I32, _I32]),
     'amar_dense_split_pack_f32': (ctypes.c_int, [_P, _I32, _I32, _P]),
@@ -89,6 +91,8 @@ SIGNATURES = {
                                         _I32, _I32, _P]),
     'amar_gat_bwd_directed_f32': (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64,
                                                  _I32, _I32, _P]),
+    'amar_gat_heads_bwd_f32': (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64,
+                                              _I32, _I32, _I32, _P]),
     'amar_attention_mix_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I32, _P]),
     'amar_attention_mix_bwd_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _I32, _P]),
     'amar_add3_act_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I32, _I32, _P]),
@@ -544,6 +548,79 @@ def gat_layer(rowptr, colidx, H, s_self, s_neigh, bias, Y, self_loop=True):
         _ptr(s_neigh, torch.float32, 's_neigh'), _ptr(bias, torch.float32, 'bias'),
         _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'), 1 if self_loop else 0, n_rows, _stream())
     _check(code, 'amar_gat_layer_f32')
+
+
+GAT_HEADS_MAX_WIDTH = 64                                             # heads * channels the multi-head row kernels hold in one wavefront's lanes
+
+
+def gat_heads_supported(heads, C):
+    """The shapes amar_rowwise_xw_heads_f32 / amar_gat_heads_f32 / amar_gat_heads_bwd_f32 are built for."""
+    return heads >= 1 and C >= 4 and C % 4 == 0 and heads * C <= GAT_HEADS_MAX_WIDTH
+
+
+def rowwise_xw_heads(X, W, Hd, a_self, a_neigh, S):
+    """Hd [n, heads*C] = X . W with W [F, heads, C], and S [n, 2*heads]: per row the heads' self scalars, then their neighbour scalars
+    (a_self / a_neigh [C, heads, 1] in Keras's order)."""
+    n_rows, F = X.shape
+    if W.dim() != 3 or W.shape[0] != F or not W.is_contiguous():
+        raise ValueError("rowwise_xw_heads: W [F, heads, C] contiguous expected")
+    heads, C = int(W.shape[1]), int(W.shape[2])
+    if tuple(Hd.shape) != (n_rows, heads * C) or tuple(S.shape) != (n_rows, 2 * heads) or not S.is_contiguous() or \
+            any(v.numel() != C * heads or not v.is_contiguous() for v in (a_self, a_neigh)):
+        raise ValueError("rowwise_xw_heads: Hd [n, heads*C], S [n, 2*heads] contiguous, a_self / a_neigh [C, heads, 1] contiguous expected")
+    code = load().amar_rowwise_xw_heads_f32(
+        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), F, _ptr(W, torch.float32, 'W'), heads, C, _ptr(Hd, torch.float32, 'Hd'), _ld(Hd, 'Hd'),
+        _ptr(a_self, torch.float32, 'a_self'), _ptr(a_neigh, torch.float32, 'a_neigh'), _ptr(S, torch.float32, 'S'), n_rows, _stream())
+    _check(code, 'amar_rowwise_xw_heads_f32')
+
+
+def _gat_heads_shapes(what, rowptr, Hd, heads, S, bias, Y, concat):
+    n, HC = rowptr.numel() - 1, int(Hd.shape[1])
+    if heads < 1 or HC % heads:
+        raise ValueError("{}: Hd must be [n, heads*C]".format(what))
+    width = HC if concat else HC // heads
+    if Hd.shape[0] < n or tuple(S.shape) != (Hd.shape[0], 2 * heads) or not S.is_contiguous() or bias.numel() != width or tuple(Y.shape) != (n, width):
+        raise ValueError("{}: S [n, 2*heads] contiguous, bias and Y of width {} expected".format(what, width))
+    return n, HC // heads
+
+
+def gat_heads(rowptr, colidx, Hd, heads, S, bias, Y, concat=True, self_loop=True, out_tape=None):
+    """One multi-head GAT layer on rowwise_xw_heads' Hd / S (amar_gat_heads_f32).  concat: Y [n, heads*C], else the heads' mean,
+    Y [n, C].  out_tape [n, heads*C] contiguous: the heads' outputs before the bias, which gat_heads_bwd needs under concat=False."""
+    n, C = _gat_heads_shapes('gat_heads', rowptr, Hd, heads, S, bias, Y, concat)
+    if out_tape is not None and (tuple(out_tape.shape) != (n, heads * C) or not out_tape.is_contiguous()):
+        raise ValueError("gat_heads: out_tape must be a contiguous [n, heads*C] buffer")
+    code = load().amar_gat_heads_f32(
+        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), _ptr(Hd, torch.float32, 'Hd'), _ld(Hd, 'Hd'), heads, C,
+        _ptr(S, torch.float32, 'S'), _ptr(bias, torch.float32, 'bias'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
+        _ptr(out_tape, torch.float32, 'out_tape'), 1 if concat else 0, 1 if self_loop else 0, n, _stream())
+    _check(code, 'amar_gat_heads_f32')
+
+
+def gat_heads_bwd(rowptr, colidx, Hd, heads, S, Y, dY, bias, a_self, a_neigh, concat=True, self_loop=True, out_tape=None, transposed=None):
+    """Reverse of gat_heads (amar_gat_heads_bwd_f32).  Returns (dout [n, width of Y], dS [n, 2*heads], dHd [n, heads*C]); dS holds the
+    gradients of the self scalars, then of the neighbour scalars, as S does.  transposed = (t_rowptr, t_colidx) of a directed
+    structure (None: the edge multiset is symmetric and the one structure serves both walks)."""
+    n, C = _gat_heads_shapes('gat_heads_bwd', rowptr, Hd, heads, S, bias, Y, concat)
+    if Hd.shape[0] != n or tuple(dY.shape) != tuple(Y.shape) or a_self.numel() != C * heads or a_neigh.numel() != C * heads or \
+            not a_self.is_contiguous() or not a_neigh.is_contiguous():
+        raise ValueError("gat_heads_bwd: Hd [n, heads*C], dY like Y, a_self / a_neigh [C, heads, 1] contiguous expected")
+    if not concat and (out_tape is None or tuple(out_tape.shape) != (n, heads * C) or not out_tape.is_contiguous()):
+        raise ValueError("gat_heads_bwd: concat=False needs the forward's out_tape [n, heads*C]")
+    dev = Hd.device
+    dout = torch.empty(tuple(Y.shape), dtype=torch.float32, device=dev)
+    scratch = torch.empty(3 * heads * n, dtype=torch.float32, device=dev)
+    dS = torch.empty((n, 2 * heads), dtype=torch.float32, device=dev)
+    dHd = torch.empty((n, heads * C), dtype=torch.float32, device=dev)
+    t_ptrs = _transposed_ptrs(transposed, n, colidx) or (_ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'))
+    code = load().amar_gat_heads_bwd_f32(
+        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), *t_ptrs,
+        _ptr(Hd, torch.float32, 'Hd'), _ld(Hd, 'Hd'), heads, C, _ptr(S, torch.float32, 'S'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
+        _ptr(dY, torch.float32, 'dY'), _ld(dY, 'dY'), _ptr(bias, torch.float32, 'bias'), _ptr(a_self, torch.float32, 'a_self'),
+        _ptr(a_neigh, torch.float32, 'a_neigh'), _ptr(out_tape, torch.float32, 'out_tape'), _ptr(dout), _ptr(scratch), _ptr(dS), _ptr(dHd),
+        heads * C, 1 if concat else 0, 1 if self_loop else 0, n, _stream())
+    _check(code, 'amar_gat_heads_bwd_f32')
+    return dout, dS, dHd
 
 
 def gat_xs(xs, H, s_self, s_neigh, bias, Y, self_loop=True):

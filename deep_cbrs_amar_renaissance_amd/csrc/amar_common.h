@@ -95,6 +95,24 @@ __device__ __forceinline__ float wave_max_all(float v) {
     b = swap32_other(v, a); v = fmaxf(a, b);
     return v;
 }
+// Maximum over the lanes of equal index within their LPN-lane group (lane % LPN); every such lane receives it.
+template <int LPN>
+__device__ __forceinline__ float slot_max(float v) {
+#pragma unroll
+    for (int m = LPN; m < AMAR_WAVE; m <<= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+    return v;
+}
+// Maximum over CQ consecutive lanes starting at lane head0 (a group aligned to CQ where CQ is a power of two); every lane of the
+// group receives it.  The multi-head GAT kernels: the lanes of one head.
+__device__ __forceinline__ float head_max(float v, int CQ, int head0) {
+    if ((CQ & (CQ - 1)) == 0) {
+        for (int m = 1; m < CQ; m <<= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+        return v;
+    }
+    float s = -INFINITY;
+    for (int k = 0; k < CQ; ++k) s = fmaxf(s, __shfl(v, head0 + k, 64));
+    return s;
+}
 template <int STRIDE>
 __device__ __forceinline__ float4 f4_wave_sum_stride(float4 v) {
     return make_float4(wave_sum_stride<STRIDE>(v.x), wave_sum_stride<STRIDE>(v.y),

@@ -1296,6 +1296,107 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * AMAR_WAVE) void gat_row_kernel(co
     }
 }
 
+// ---- GAT (several heads) ---------------------------------------------------------------------
+// All heads of a layer walk the same CSR row, so one wavefront takes the row for every head: the row of Hd is heads*C floats =
+// heads*C/4 quads, LPN = that count rounded up to a power of two lanes per entry (gat_bwd_*_kernel's mapping; surplus lanes carry
+// zeros), NS = 64/LPN entries per step.  A lane's quad lies inside one head (C % 4 == 0): the lane keeps that head's maximum and
+// denominator, the lanes of one entry read its `heads` neighbour scalars from one contiguous stretch of S, and colidx[p] is read
+// once per entry for all heads.  Sums over the slots are the fixed butterflies of the single-head kernel: reproducible bits.
+struct GatHeadsArgs {
+    const int32_t *rowptr; const int32_t *colidx; const float *Hd; int64_t ldh; const float *S; const float *bias;
+    float *Y; int64_t ldy; float *tape; int heads; int C; int self_loop; int n_rows;
+};
+
+// One thread per (row, head): the two attention scalars of amar_rowwise_xw_heads_f32.
+__global__ __launch_bounds__(256) void gat_heads_scalars_kernel(const float *__restrict__ Hd, int64_t ldh, const float *__restrict__ a_self,
+                                                                const float *__restrict__ a_neigh, float *__restrict__ S, int heads, int C,
+                                                                int64_t n_rows) {
+    const int64_t total = n_rows * heads;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
+        const int64_t row = t / heads;
+        const int h = (int)(t - row * heads);
+        const float *hd = Hd + row * ldh + (int64_t)h * C;
+        float ps = 0.f, pn = 0.f;
+        for (int c = 0; c < C; c += 4) {
+            const float4 v = *reinterpret_cast<const float4 *>(hd + c);
+            ps = fmaf(v.x, a_self[c * heads + h], ps); pn = fmaf(v.x, a_neigh[c * heads + h], pn);
+            ps = fmaf(v.y, a_self[(c + 1) * heads + h], ps); pn = fmaf(v.y, a_neigh[(c + 1) * heads + h], pn);
+            ps = fmaf(v.z, a_self[(c + 2) * heads + h], ps); pn = fmaf(v.z, a_neigh[(c + 2) * heads + h], pn);
+            ps = fmaf(v.w, a_self[(c + 3) * heads + h], ps); pn = fmaf(v.w, a_neigh[(c + 3) * heads + h], pn);
+        }
+        S[row * 2 * heads + h] = ps;
+        S[row * 2 * heads + heads + h] = pn;
+    }
+}
+
+// MEAN: the averaging form (concat_heads False): the heads' results are added over the lanes of equal channel, h ascending, by
+// shuffles, and C columns are written.
+template <int LPN, bool MEAN>
+__global__ __launch_bounds__(WAVES_PER_BLOCK * AMAR_WAVE) void gat_heads_row_kernel(const GatHeadsArgs a) {
+    constexpr int NS = AMAR_WAVE / LPN;
+    const int lane = threadIdx.x & (AMAR_WAVE - 1);
+    const int row = blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    if (row >= a.n_rows) return;
+    const int q = lane % LPN, slot = lane / LPN;
+    const int HC = a.heads * a.C, S2 = 2 * a.heads, CQ = a.C / 4;     // CQ: quads (lanes) per head
+    const bool live = 4 * q < HC;
+    const int hq = live ? (4 * q) / a.C : 0;                          // the head of this lane's quad
+    const int beg = a.rowptr[row], end = a.rowptr[row + 1];
+    const float si = a.S[(int64_t)row * S2 + hq];
+    const float *tn = a.S + a.heads + hq;                             // tn[j * S2] = neighbour scalar of node j, this lane's head
+
+    // pass 1: LeakyReLU is monotone, so max_j e_ijh = LeakyReLU(s_ih + max_j t_jh).  The CQ lanes of a head share the entries of
+    // their slot's turn (lane r of the head takes entry slot * CQ + r of every NS * CQ), then the maximum goes over slots and head
+    float mn = a.self_loop ? tn[(int64_t)row * S2] : -INFINITY;
+    for (int p = beg + slot * CQ + (q - hq * CQ); p < end; p += NS * CQ) mn = fmaxf(mn, tn[(int64_t)a.colidx[p] * S2]);
+    mn = head_max(slot_max<LPN>(mn), CQ, slot * LPN + hq * CQ);
+    const float emax = leaky02(si + mn);
+
+    // pass 2: un-normalised softmax weights and the weighted sum of source rows, per head
+    float4 acc = f4_zero();
+    float den = 0.f;
+    for (int p = beg + slot; p < end; p += NS) {
+        const int c = a.colidx[p];
+        const float w = expf(leaky02(si + tn[(int64_t)c * S2]) - emax);
+        const float4 h = live ? *reinterpret_cast<const float4 *>(a.Hd + (int64_t)c * a.ldh + 4 * q) : f4_zero();
+        acc = f4_fma(w, h, acc);
+        den += w;
+    }
+    if (a.self_loop && slot == 0) {
+        const float w = expf(leaky02(si + tn[(int64_t)row * S2]) - emax);
+        const float4 h = live ? *reinterpret_cast<const float4 *>(a.Hd + (int64_t)row * a.ldh + 4 * q) : f4_zero();
+        acc = f4_fma(w, h, acc);
+        den += w;
+    }
+    acc = f4_wave_sum_stride<LPN>(acc);
+    den = wave_sum_stride<LPN>(den);                                  // every lane: the denominator of its own head
+    const float inv = 1.f / (den + 1e-9f);
+    float4 o = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
+    if (a.tape && slot == 0 && live) *reinterpret_cast<float4 *>(a.tape + (int64_t)row * HC + 4 * q) = o;
+    if (MEAN) {
+        const int src = slot * LPN + (q < CQ ? q : 0);
+        float4 s = f4_zero();
+        for (int h = 0; h < a.heads; ++h) s = f4_add(s, f4_shfl(o, src + h * CQ));
+        if (slot == 0 && q < CQ) {
+            const float r = 1.f / (float)a.heads;
+            const float4 b = *reinterpret_cast<const float4 *>(a.bias + 4 * q);
+            *reinterpret_cast<float4 *>(a.Y + (int64_t)row * a.ldy + 4 * q) =
+                make_float4(fmaxf(s.x * r + b.x, 0.f), fmaxf(s.y * r + b.y, 0.f), fmaxf(s.z * r + b.z, 0.f), fmaxf(s.w * r + b.w, 0.f));
+        }
+    } else if (slot == 0 && live) {
+        const float4 b = *reinterpret_cast<const float4 *>(a.bias + 4 * q);
+        *reinterpret_cast<float4 *>(a.Y + (int64_t)row * a.ldy + 4 * q) =
+            make_float4(fmaxf(o.x + b.x, 0.f), fmaxf(o.y + b.y, 0.f), fmaxf(o.z + b.z, 0.f), fmaxf(o.w + b.w, 0.f));
+    }
+}
+
+template <int LPN>
+void launch_gat_heads(const GatHeadsArgs &a, bool mean, hipStream_t st) {
+    const dim3 grid((a.n_rows + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), block(WAVES_PER_BLOCK * AMAR_WAVE);
+    if (mean) hipLaunchKernelGGL((gat_heads_row_kernel<LPN, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((gat_heads_row_kernel<LPN, false>), grid, block, 0, st, a);
+}
+
 
 // ---- GAT on the XCD-sliced image (large graphs) ----------------------------------------------------------------
 // Same tiling as spmm_xs_*: workgroup b works on column slice b % S, a wave on one (64-row block, slice) tile, a lane on
@@ -1772,6 +1873,45 @@ int amar_gat_layer_dropout_f32(const int32_t *rowptr, const int32_t *colidx,
     if (n_rows > AMAR_DROPOUT_MAX_NODES) return AMAR_EUNSUPPORTED;     // node ids share counter words with the ordinal and the site
     const AmarDropout d{(uint32_t)seed, (uint32_t)(seed >> 32), step, site, threshold, scale};
     return gat_layer_launch(rowptr, colidx, H, ldh, C, s_self, s_neigh, bias, Y, ldy, self_loop, n_rows, &d, stream);
+}
+
+// heads x C the multi-head entries are built for: a lane's quad inside one head, the row within one wavefront's 16 lanes per entry
+static bool gat_heads_shape_ok(int32_t heads, int32_t C) { return heads >= 1 && C >= 4 && (C & 3) == 0 && (int64_t)heads * C <= 64; }
+
+int amar_rowwise_xw_heads_f32(const float *X, int64_t ldx, int32_t F, const float *W, int32_t heads, int32_t C,
+                              float *Hd, int64_t ldh, const float *a_self, const float *a_neigh, float *S,
+                              int32_t n_rows, amar_stream_t stream) {
+    if (n_rows < 0 || !X || !W || !Hd || !a_self || !a_neigh || !S || F < 1 || heads < 1 || C < 1 || ldx < F) return AMAR_EINVAL;
+    if (!gat_heads_shape_ok(heads, C) || F > 64) return AMAR_EUNSUPPORTED;
+    if (!ld_ok(ldh, heads * C) || !amar_aligned16(Hd)) return AMAR_EINVAL;
+    const int rc = rowwise_xw_run(X, ldx, F, W, heads * C, Hd, ldh, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_rows, stream);
+    if (rc != AMAR_OK || n_rows == 0) return rc;
+    int64_t blocks = ((int64_t)n_rows * heads + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(gat_heads_scalars_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       Hd, ldh, a_self, a_neigh, S, heads, C, (int64_t)n_rows);
+    return amar_check_launch();
+}
+
+int amar_gat_heads_f32(const int32_t *rowptr, const int32_t *colidx,
+                       const float *Hd, int64_t ldh, int32_t heads, int32_t C,
+                       const float *S, const float *bias, float *Y, int64_t ldy, float *out_tape,
+                       int32_t concat, int32_t self_loop, int32_t n_rows, amar_stream_t stream) {
+    if (n_rows < 0 || !rowptr || !Hd || !S || !bias || !Y || heads < 1 || C < 1) return AMAR_EINVAL;
+    if (!gat_heads_shape_ok(heads, C)) return AMAR_EUNSUPPORTED;
+    const int HC = heads * C;
+    if (!ld_ok(ldh, HC) || !ld_ok(ldy, concat ? HC : C) || !amar_aligned16(Hd) || !amar_aligned16(Y) || !amar_aligned16(bias) ||
+        (out_tape && !amar_aligned16(out_tape))) return AMAR_EINVAL;
+    if (n_rows == 0) return AMAR_OK;
+    if (!colidx) return AMAR_EINVAL;
+    GatHeadsArgs a{rowptr, colidx, Hd, ldh, S, bias, Y, ldy, out_tape, heads, C, self_loop ? 1 : 0, n_rows};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (HC <= 4) launch_gat_heads<1>(a, !concat, st);
+    else if (HC <= 8) launch_gat_heads<2>(a, !concat, st);
+    else if (HC <= 16) launch_gat_heads<4>(a, !concat, st);
+    else if (HC <= 32) launch_gat_heads<8>(a, !concat, st);
+    else launch_gat_heads<16>(a, !concat, st);
+    return amar_check_launch();
 }
 
 int amar_gat_xs_f32(const int32_t *rowptr, const int32_t *colidx, int32_t n_slices,

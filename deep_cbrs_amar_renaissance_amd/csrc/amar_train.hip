@@ -385,6 +385,138 @@ void launch_gat_bwd(const GatBwdArgs &a, bool drop, hipStream_t st) {
     hipLaunchKernelGGL(gat_bwd_source_kernel<LPN>, grid, block, 0, st, a);
 }
 
+// ---- GAT reverse pass, several heads (forward: amar_gat_heads_f32) ----------------------------------------------------------------
+// The two walks above with the forward's lane mapping: LPN lanes per entry cover the heads*C floats of a row of Hd, a lane's quad lies
+// inside one head (C % 4 == 0) and the lane carries that head's statistics; the "group" sums of the single-head kernels become sums
+// over the C/4 lanes of one head.  S / dS are [n, 2*heads] (self scalars, then neighbour scalars); the per-(row, head) maximum,
+// inverse denominator and c_ih go through row_scratch as [n, 3*heads] so that the source walk reads one stretch per target.
+// concat == 0 (averaging form): g_ih = g_i / heads for every head, out[i,h,:] comes from the forward's tape, dout is C wide.
+struct GatHeadsBwdArgs {
+    const int32_t *rowptr; const int32_t *colidx; const int32_t *t_rowptr; const int32_t *t_colidx; const float *Hd; int64_t ldh; const float *S;
+    const float *Y; int64_t ldy; const float *dY; int64_t ldd; const float *bias; const float *a_self; const float *a_neigh; const float *tape;
+    float *dout; float *scratch; float *dS; float *dHd; int64_t lddh;
+    int heads; int C; int concat; int self_loop; int n_rows;
+};
+
+// Sum over the CQ = C/4 consecutive lanes of one head (first lane: head0); every lane of the head receives the same bits.
+__device__ __forceinline__ float head_sum(float v, int CQ, bool pow2, int head0) {
+    if (pow2) {
+        for (int m = 1; m < CQ; m <<= 1) v += __shfl_xor(v, m, 64);
+        return v;
+    }
+    float s = 0.f;
+    for (int k = 0; k < CQ; ++k) s += __shfl(v, head0 + k, 64);
+    return s;
+}
+
+template <int LPN>
+__global__ __launch_bounds__(256) void gat_heads_bwd_target_kernel(const GatHeadsBwdArgs a) {
+    constexpr int NS = AMAR_WAVE / LPN;
+    const int lane = threadIdx.x & (AMAR_WAVE - 1);
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= a.n_rows) return;
+    const int q = lane % LPN, slot = lane / LPN;
+    const int C = a.C, HC = a.heads * C, S2 = 2 * a.heads, CQ = C / 4;
+    const bool live = 4 * q < HC, pow2 = (CQ & (CQ - 1)) == 0;
+    const int hq = live ? (4 * q) / C : 0;
+    const int head0 = slot * LPN + hq * CQ;
+    const int yc = a.concat ? 4 * q : 4 * q - hq * C;               // this quad's column of Y / dY / dout
+    const int beg = a.rowptr[row], end = a.rowptr[row + 1];
+    const float si = a.S[(int64_t)row * S2 + hq];
+    const float *tn = a.S + a.heads + hq;
+    const float4 y = live ? *reinterpret_cast<const float4 *>(a.Y + (int64_t)row * a.ldy + yc) : f4_zero();
+    const float4 dy = live ? *reinterpret_cast<const float4 *>(a.dY + (int64_t)row * a.ldd + yc) : f4_zero();
+    float4 g = make_float4(y.x > 0.f ? dy.x : 0.f, y.y > 0.f ? dy.y : 0.f, y.z > 0.f ? dy.z : 0.f, y.w > 0.f ? dy.w : 0.f);
+    float4 out;
+    if (a.concat) {
+        const float4 b = live ? *reinterpret_cast<const float4 *>(a.bias + yc) : f4_zero();
+        out = make_float4(y.x - b.x, y.y - b.y, y.z - b.z, y.w - b.w);
+        if (slot == 0 && live) *reinterpret_cast<float4 *>(a.dout + (int64_t)row * HC + yc) = g;
+    } else {
+        out = live ? *reinterpret_cast<const float4 *>(a.tape + (int64_t)row * HC + 4 * q) : f4_zero();
+        if (slot == 0 && live && hq == 0) *reinterpret_cast<float4 *>(a.dout + (int64_t)row * C + yc) = g;
+        const float r = 1.f / (float)a.heads;
+        g = make_float4(g.x * r, g.y * r, g.z * r, g.w * r);
+    }
+    const float ci = head_sum(dot4(g, out), CQ, pow2, head0);
+    // softmax statistics as in the forward kernel
+    float mn = a.self_loop ? tn[(int64_t)row * S2] : -INFINITY;
+    for (int p = beg + slot * CQ + (q - hq * CQ); p < end; p += NS * CQ) mn = fmaxf(mn, tn[(int64_t)a.colidx[p] * S2]);
+    mn = head_max(slot_max<LPN>(mn), CQ, head0);
+    const float emax = leaky02(si + mn);
+    // one more walk for the denominator and the un-normalised ds (d pre_ijh is linear in 1 / denominator)
+    float den = 0.f, ds = 0.f;
+    auto edge = [&](int j) {
+        const float pre = si + tn[(int64_t)j * S2];
+        const float w = expf(leaky02(pre) - emax);
+        const float4 h = live ? *reinterpret_cast<const float4 *>(a.Hd + (int64_t)j * a.ldh + 4 * q) : f4_zero();
+        const float dalpha = head_sum(dot4(g, h), CQ, pow2, head0);
+        den += w;
+        ds += w * (dalpha - ci) * (pre > 0.f ? 1.f : 0.2f);
+    };
+    // every lane of a slot group takes part in the shuffles: the loop bound is uniform per group
+    for (int p = beg + slot; p < end; p += NS) edge(a.colidx[p]);
+    if (a.self_loop && slot == 0) edge(row);
+    den = wave_sum_stride<LPN>(den);
+    ds = wave_sum_stride<LPN>(ds);
+    const float inv = 1.f / (den + 1e-9f);
+    if (slot == 0 && live && 4 * q == hq * C) {
+        a.dS[(int64_t)row * S2 + hq] = ds * inv;
+        float *sc = a.scratch + (int64_t)row * 3 * a.heads;
+        sc[hq] = emax; sc[a.heads + hq] = inv; sc[2 * a.heads + hq] = ci;
+    }
+}
+
+template <int LPN>
+__global__ __launch_bounds__(256) void gat_heads_bwd_source_kernel(const GatHeadsBwdArgs a) {
+    constexpr int NS = AMAR_WAVE / LPN;
+    const int lane = threadIdx.x & (AMAR_WAVE - 1);
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= a.n_rows) return;
+    const int q = lane % LPN, slot = lane / LPN;
+    const int C = a.C, H = a.heads, HC = H * C, S2 = 2 * H, CQ = C / 4;
+    const bool live = 4 * q < HC, pow2 = (CQ & (CQ - 1)) == 0;
+    const int hq = live ? (4 * q) / C : 0;
+    const int head0 = slot * LPN + hq * CQ;
+    const int yc = a.concat ? 4 * q : 4 * q - hq * C, W = a.concat ? HC : C;
+    const float gs = a.concat ? 1.f : 1.f / (float)H;
+    const int beg = a.t_rowptr[row], end = a.t_rowptr[row + 1];
+    const float tj = a.S[(int64_t)row * S2 + H + hq];
+    const float4 h = live ? *reinterpret_cast<const float4 *>(a.Hd + (int64_t)row * a.ldh + 4 * q) : f4_zero();
+    float4 acc = f4_zero();
+    float dt = 0.f;
+    auto edge = [&](int i) {
+        const float *sc = a.scratch + (int64_t)i * 3 * H + hq;
+        const float pre = a.S[(int64_t)i * S2 + hq] + tj;
+        const float alpha = expf(leaky02(pre) - sc[0]) * sc[H];
+        float4 g = live ? *reinterpret_cast<const float4 *>(a.dout + (int64_t)i * W + yc) : f4_zero();
+        g = make_float4(g.x * gs, g.y * gs, g.z * gs, g.w * gs);
+        acc = f4_fma(alpha, g, acc);
+        const float dalpha = head_sum(dot4(g, h), CQ, pow2, head0);
+        dt += alpha * (dalpha - sc[2 * H]) * (pre > 0.f ? 1.f : 0.2f);
+    };
+    for (int p = beg + slot; p < end; p += NS) edge(a.t_colidx[p]);
+    if (a.self_loop && slot == 0) edge(row);
+    acc = f4_wave_sum_stride<LPN>(acc);
+    dt = wave_sum_stride<LPN>(dt);
+    if (slot == 0 && live) {
+        const float ds = a.dS[(int64_t)row * S2 + hq];
+        const int c0 = 4 * q - hq * C;                               // element (c, h) of the attention kernels: c * heads + h
+        const float *as = a.a_self + (int64_t)c0 * H + hq, *an = a.a_neigh + (int64_t)c0 * H + hq;
+        *reinterpret_cast<float4 *>(a.dHd + (int64_t)row * a.lddh + 4 * q) =
+            make_float4(acc.x + ds * as[0] + dt * an[0], acc.y + ds * as[H] + dt * an[H],
+                        acc.z + ds * as[2 * H] + dt * an[2 * H], acc.w + ds * as[3 * H] + dt * an[3 * H]);
+        if (4 * q == hq * C) a.dS[(int64_t)row * S2 + H + hq] = dt;
+    }
+}
+
+template <int LPN>
+void launch_gat_heads_bwd(const GatHeadsBwdArgs &a, hipStream_t st) {
+    const dim3 grid((a.n_rows + 3) / 4), block(256);
+    hipLaunchKernelGGL(gat_heads_bwd_target_kernel<LPN>, grid, block, 0, st, a);
+    hipLaunchKernelGGL(gat_heads_bwd_source_kernel<LPN>, grid, block, 0, st, a);
+}
+
 // The same update with the step size read from device memory, and the one-thread kernel that advances it:
 // state[0] = t (as float), state[1] = lr * sqrt(1 - b2^t) / (1 - b1^t).  Lets a whole training batch, optimizer
 // included, replay as one hipGraph with nothing baked in that changes from step to step.
@@ -1843,6 +1975,33 @@ int amar_gat_bwd_directed_dropout_f32(const int32_t *rowptr, const int32_t *coli
     const AmarDropout d{(uint32_t)seed, (uint32_t)(seed >> 32), step, site, threshold, scale};
     return gat_bwd_launch(rowptr, colidx, t_rowptr, t_colidx, H, ldh, C, s_self, s_neigh, Y, ldy, dY, ldd, bias, a_self, a_neigh, dout,
                           row_scratch, ds, dt, dH, lddh, self_loop, n_rows, &d, stream);
+}
+
+int amar_gat_heads_bwd_f32(const int32_t *rowptr, const int32_t *colidx, const int32_t *t_rowptr, const int32_t *t_colidx,
+                           const float *Hd, int64_t ldh, int32_t heads, int32_t C, const float *S,
+                           const float *Y, int64_t ldy, const float *dY, int64_t ldd, const float *bias,
+                           const float *a_self, const float *a_neigh, const float *out_tape,
+                           float *dout, float *row_scratch, float *dS, float *dHd, int64_t lddh,
+                           int32_t concat, int32_t self_loop, int32_t n_rows, amar_stream_t stream) {
+    if (n_rows < 0 || !rowptr || !t_rowptr || !Hd || !S || !Y || !dY || !bias || !a_self || !a_neigh || !dout || !row_scratch || !dS || !dHd ||
+        heads < 1 || C < 1) return AMAR_EINVAL;
+    if (!concat && !out_tape) return AMAR_EINVAL;                     // the averaging form cannot recover the heads' outputs from Y
+    if (C < 4 || (C & 3) || (int64_t)heads * C > 64) return AMAR_EUNSUPPORTED;
+    const int HC = heads * C, W = concat ? HC : C;
+    if (ldh < HC || lddh < HC || ldy < W || ldd < W || (ldh & 3) || (ldy & 3) || (ldd & 3) || (lddh & 3)) return AMAR_EINVAL;
+    if (!amar_aligned16(Hd) || !amar_aligned16(Y) || !amar_aligned16(dY) || !amar_aligned16(bias) || !amar_aligned16(dout) || !amar_aligned16(dHd) ||
+        (out_tape && !amar_aligned16(out_tape))) return AMAR_EINVAL;
+    if (n_rows == 0) return AMAR_OK;
+    if (!colidx || !t_colidx) return AMAR_EINVAL;
+    GatHeadsBwdArgs a{rowptr, colidx, t_rowptr, t_colidx, Hd, ldh, S, Y, ldy, dY, ldd, bias, a_self, a_neigh, out_tape, dout, row_scratch, dS, dHd, lddh,
+                      heads, C, concat ? 1 : 0, self_loop ? 1 : 0, n_rows};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (HC <= 4) launch_gat_heads_bwd<1>(a, st);
+    else if (HC <= 8) launch_gat_heads_bwd<2>(a, st);
+    else if (HC <= 16) launch_gat_heads_bwd<4>(a, st);
+    else if (HC <= 32) launch_gat_heads_bwd<8>(a, st);
+    else launch_gat_heads_bwd<16>(a, st);
+    return amar_check_launch();
 }
 
 int amar_attention_mix_f32(const float *A, int64_t lda, const float *B, int64_t ldb, const float *TA, int64_t ldta,

@@ -90,7 +90,9 @@ class SequentialGNN(Model):
     def layer_widths(self):
         widths = [self.input_width()]
         for layer in self.seq_layers:
-            widths.append(int(layer.channels) if layer.channels is not None else widths[-1])
+            # (GAT: the heads side by side or averaged, GATConv.output_width)
+            out = getattr(layer, 'output_width', layer.channels)
+            widths.append(int(out) if out is not None else widths[-1])
         return widths
 
     def output_dim(self):
@@ -319,14 +321,15 @@ class GCN(GNN):
 
 
 class GAT(GNN):
-    def __init__(self, adj_matrix, n_hiddens=(8, 8, 8), dropout_rate=0.0, **kwargs):
+    def __init__(self, adj_matrix, n_hiddens=(8, 8, 8), dropout_rate=0.0, attn_heads=1, concat_heads=True, **kwargs):
         self.n_hiddens = list(n_hiddens)
         self.dropout_rate = dropout_rate
+        self.attn_heads, self.concat_heads = int(attn_heads), bool(concat_heads)
         super().__init__(adj_matrix, len(self.n_hiddens), **kwargs)
 
     def build_gnn_layer(self, i, regularizer=None, **kwargs):
-        return GATConv(self.n_hiddens[i], dropout_rate=self.dropout_rate, activation='relu',
-                       kernel_regularizer=regularizer, bias_regularizer=regularizer)
+        return GATConv(self.n_hiddens[i], attn_heads=self.attn_heads, concat_heads=self.concat_heads, dropout_rate=self.dropout_rate,
+                       activation='relu', kernel_regularizer=regularizer, bias_regularizer=regularizer)
 
 
 class GraphSage(GNN):

@@ -72,15 +72,21 @@ class TwoStepGNN(Model, _Hoisted, abc.ABC):
                 else:
                     self.n_hiddens.extend([embedding_dim for _ in range(n_hops)])
         step_two = [self.build_gnn_layer(i + n_hops, regularizer=regularizer) for i in range(n_hops)]
+        table_dim = second_embedding_dim
+        if getattr(self, 'attn_heads', 1) > 1:
+            # several GAT heads side by side widen step one's slices beyond its channels: the user table takes the width step one
+            # really hands over (the channel counts of step two stay the ones above)
+            table_dim = self.step_one_gnn_layers.output_dim()
         # the user table carries no regulariser in the reference (tsgnn.py:77-81 does not pass one)
         self.step_two_gnn_layers = HalfInputSequentialGNN(
             adj_ui_matrix, step_two, n_users,
-            embedding_dim=second_embedding_dim, final_node=final_node,
+            embedding_dim=table_dim, final_node=final_node,
             dropout=dropout, cache_neighbours=cache_neighbours
         )
-        if self.step_one_gnn_layers.output_dim() != second_embedding_dim:
+        # (with one head table_dim is the reference's figure and this can fail; with several it holds by construction)
+        if self.step_one_gnn_layers.output_dim() != table_dim:
             raise ValueError("step one hands over {}-wide item rows, the user table is {} wide".format(
-                self.step_one_gnn_layers.output_dim(), second_embedding_dim))
+                self.step_one_gnn_layers.output_dim(), table_dim))
         self.built = True
         self._init_hoist()
 
@@ -126,14 +132,15 @@ class TwoStepGraphSage(TwoStepGNN):
 
 
 class TwoStepGAT(TwoStepGNN):
-    def __init__(self, n_users, n_items, adj_matrix, n_hiddens=(8, 8, 8), dropout_rate=0.0, **kwargs):
+    def __init__(self, n_users, n_items, adj_matrix, n_hiddens=(8, 8, 8), dropout_rate=0.0, attn_heads=1, concat_heads=True, **kwargs):
         self.n_hiddens = list(n_hiddens)
         self.dropout_rate = dropout_rate
+        self.attn_heads, self.concat_heads = int(attn_heads), bool(concat_heads)
         super().__init__(n_users, n_items, adj_matrix, len(self.n_hiddens), **kwargs)
 
     def build_gnn_layer(self, i, regularizer=None, **kwargs):
-        return GATConv(self.n_hiddens[i], dropout_rate=self.dropout_rate, activation='relu',
-                       kernel_regularizer=regularizer, bias_regularizer=regularizer)
+        return GATConv(self.n_hiddens[i], attn_heads=self.attn_heads, concat_heads=self.concat_heads, dropout_rate=self.dropout_rate,
+                       activation='relu', kernel_regularizer=regularizer, bias_regularizer=regularizer)
 
 
 class TwoStepLightGCN(TwoStepGNN):

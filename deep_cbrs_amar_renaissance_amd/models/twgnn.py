@@ -132,14 +132,15 @@ class TwoWayGraphSage(TwoWayGNN):
 
 
 class TwoWayGAT(TwoWayGNN):
-    def __init__(self, n_users, n_items, adj_matrix, n_hiddens=(8, 8, 8), dropout_rate=0.0, **kwargs):
+    def __init__(self, n_users, n_items, adj_matrix, n_hiddens=(8, 8, 8), dropout_rate=0.0, attn_heads=1, concat_heads=True, **kwargs):
         self.n_hiddens = list(n_hiddens)
         self.dropout_rate = dropout_rate
+        self.attn_heads, self.concat_heads = int(attn_heads), bool(concat_heads)
         super().__init__(n_users, n_items, adj_matrix, len(self.n_hiddens), **kwargs)
 
     def build_gnn_layer(self, i, regularizer=None, **kwargs):
-        return GATConv(self.n_hiddens[i], dropout_rate=self.dropout_rate, activation='relu',
-                       kernel_regularizer=regularizer, bias_regularizer=regularizer)
+        return GATConv(self.n_hiddens[i], attn_heads=self.attn_heads, concat_heads=self.concat_heads, dropout_rate=self.dropout_rate,
+                       activation='relu', kernel_regularizer=regularizer, bias_regularizer=regularizer)
 
 
 class TwoWayLightGCN(TwoWayGNN):

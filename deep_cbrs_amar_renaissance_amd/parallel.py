@@ -308,6 +308,9 @@ class PartitionedGCNRunner:
             raise NotImplementedError("the partitioned runner covers single-graph models; TwoStep / TwoWay stacks run on one GPU")
         seq = model.gnn.gnn_layers
         layers = list(seq.seq_layers)
+        if any(isinstance(l, GATConv) and l.attn_heads > 1 for l in layers):
+            raise NotImplementedError("the partitioned runner covers GAT with attn_heads=1 only; multi-head stacks (attn_heads > 1) "
+                                      "run on one GPU")
         if layers and all(isinstance(l, GCNConv) for l in layers) and seq.final_node == 'concatenation':
             self.kind = 'gcn'
         elif layers and all(isinstance(l, LightGCNConv) for l in layers) and seq.final_node == 'mean':

@@ -20,7 +20,7 @@ in its `_LayerKind`; every reverse of a linear map, the Dense tapes' included, i
 forward that keeps what the reverse pass needs ([x || mean] and the normalised pre-activation); its aggregate is
 (A + I) / count, so the reverse aggregate is the row scale (A's counts) followed by the value-free SpMM on A^T.  The hybrid head
 (HybridCBRS: 'concatenate' / 'attention' fusion, residual classifier, both feature_based settings) trains on the same
-Dense tapes; its BERT inputs are constants.  GAT (1 head) trains on the inference kernels plus `amar_gat_bwd_f32`, which
+Dense tapes; its BERT inputs are constants.  GAT (1 head; several heads: `amar_gat_heads_bwd_f32`) trains on the inference kernels plus `amar_gat_bwd_f32`, which
 forms the softmax / attention-scalar gradients row-wise for both edge directions (targets on A's rows, sources on A^T's rows:
 `amar_gat_bwd_directed_f32` where the two differ; no float atomics).
 """
@@ -489,13 +489,28 @@ class _SageLayers(_LayerKind):
 
 class _GATLayers(_LayerKind):
     """The inference kernels, keeping H = X . W and the two attention scalars, and amar_gat_bwd_f32 for the softmax reverse.  That reverse
-    needs out_i itself (c_i = g_i . (out_i - b)): under a stack rate the undropped output stays saved and the slice gets the dropped copy."""
+    needs out_i itself (c_i = g_i . (out_i - b)): under a stack rate the undropped output stays saved and the slice gets the dropped copy.
+    Layers with several heads take amar_gat_heads_f32 / amar_gat_heads_bwd_f32 (Hd [n, H*C], scalars S [n, 2H]); where the heads are
+    averaged the forward also leaves their outputs on the tape, which Y no longer holds apart."""
 
     saves_undropped_output = True
     edge_drop = None                                                 # the attention masks, set by _StackTape.enable_dropout
 
+    def __init__(self, tape, layers):
+        super().__init__(tape, layers)
+        if any(l.attn_heads > 1 and float(l.dropout_rate or 0.0) > 0.0 for l in layers):
+            # the Philox counter of an edge has no field for a head index (DESIGN §7g)
+            raise NotImplementedError("attention dropout (dropout_rate > 0) is not implemented for attn_heads > 1; train with dropout_rate=0 "
+                                      "(the stack's `dropout` works with any number of heads)")
+
     def forward_layer(self, k, layer, x, y):
         a, n, c = self.tape.seq.adj_matrix, x.shape[0], y.shape[1]
+        if layer.attn_heads > 1:
+            hd, s = layer.project_heads(x)
+            out = None if layer.concat_heads else _buffer(x, n, hd.shape[1])
+            capi.gat_heads(a.rowptr, a.colidx, hd, layer.attn_heads, s, layer.bias, y, concat=layer.concat_heads, self_loop=layer.add_self_loops,
+                           out_tape=out)
+            return types.SimpleNamespace(h=hd, s=s, y=y, out=out)
         h, s_self, s_neigh = _buffer(x, n, c), _buffer(x, n), _buffer(x, n)
         capi.rowwise_xw(x, layer.kernel.view(-1, c), h, a_self=layer.attn_kernel_self.view(c), a_neigh=layer.attn_kernel_neighs.view(c), s_self=s_self, s_neigh=s_neigh)
         edge = self.edge_drop[k] if self.edge_drop is not None else None
@@ -505,7 +520,25 @@ class _GATLayers(_LayerKind):
             capi.gat_layer(a.rowptr, a.colidx, h, s_self, s_neigh, layer.bias, y, self_loop=layer.add_self_loops)
         return types.SimpleNamespace(h=h, s_self=s_self, s_neigh=s_neigh, y=y)
 
+    def _backward_heads(self, k, layer, saved, x, dx, dy, grads):
+        tape, a, at, (n, f), hd = self.tape, self.tape.seq.adj_matrix, self.tape.at, x.shape, saved.h
+        heads, c = layer.attn_heads, layer.channels
+        dout, ds, dh = capi.gat_heads_bwd(a.rowptr, a.colidx, hd, heads, saved.s, saved.y, dy, layer.bias, layer.attn_kernel_self.detach(),
+                                          layer.attn_kernel_neighs.detach(), concat=layer.concat_heads, self_loop=layer.add_self_loops,
+                                          out_tape=saved.out, transposed=(at.rowptr, at.colidx) if at is not a else None)
+        # d a_self[:, h] = Hd[:, h, :]^T . ds[:, h]: the diagonal blocks of the [H, H*C] product ds^T . Hd, read as [C, H] by a view (the
+        # separate kernels: a captured step's deferred partial sums could not be viewed that way)
+        for key, param, cols in (('s', layer.attn_kernel_self, ds[:, :heads]), ('t', layer.attn_kernel_neighs, ds[:, heads:])):
+            full = tape.linear_bwd((key, k), hd, x=cols, dw_like=_buffer(x, heads, heads * c), fused=False)[0]
+            grads[param] = torch.diagonal(full.view(heads, heads, c), dim1=0, dim2=1).contiguous().view_as(param)
+        fused = tape.fused_route(f, heads * c, n)
+        grads[layer.bias] = tape.linear_bwd(('b', k), dout, db_like=layer.bias, K=1, fused=fused)[1]
+        w = layer.kernel.detach().view(f, heads * c)
+        grads[layer.kernel] = tape.linear_bwd(k, dh, x=x, w=w, dX=dx, dw_like=layer.kernel, accumulate_dx=True, fused=fused)[0]
+
     def backward_layer(self, k, layer, saved, x, y, dx, dy, grads):
+        if layer.attn_heads > 1:
+            return self._backward_heads(k, layer, saved, x, dx, dy, grads)
         tape, a, at, (n, f), c, h = self.tape, self.tape.seq.adj_matrix, self.tape.at, x.shape, y.shape[1], saved.h
         edge = self.edge_drop[k] if self.edge_drop is not None else None
         gat_args = (a.rowptr, a.colidx, h, saved.s_self, saved.s_neigh, saved.y, dy, layer.bias,

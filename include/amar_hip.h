@@ -251,6 +251,33 @@ int amar_gat_layer_f32(const int32_t *rowptr, const int32_t *colidx,
                        float *Y, int64_t ldy, int32_t self_loop,
                        int32_t n_rows, amar_stream_t stream);
 
+/* Multi-head GAT (Spektral 1.x GATConv._call_single + call with attn_heads = heads, heads x C output channels).  The prologue:
+ *     Hd[i, h*C + c] = X[i, 0:F] . W[0:F, h, c]            W [F, heads, C] in Keras's order = row-major [F, heads*C]
+ *     S[i, h]         = Hd[i, h, :] . a_self[:, h]          a_self, a_neigh [C, heads, 1]: element (c, h) at c*heads + h
+ *     S[i, heads + h] = Hd[i, h, :] . a_neigh[:, h]
+ * S is [n_rows, 2*heads] contiguous: one row holds the node's `heads` self scalars, then its `heads` neighbour scalars, so that a
+ * neighbour's scalars for every head are ONE contiguous read of heads floats.  The product is amar_rowwise_xw_f32's (same kernels,
+ * same bits for Hd); the scalars are one thread per (row, head), c ascending.  C % 4 == 0 and heads*C <= 64, F <= 64; other shapes
+ * AMAR_EUNSUPPORTED. */
+int amar_rowwise_xw_heads_f32(const float *X, int64_t ldx, int32_t F, const float *W, int32_t heads, int32_t C,
+                              float *Hd, int64_t ldh, const float *a_self, const float *a_neigh, float *S,
+                              int32_t n_rows, amar_stream_t stream);
+
+/* One multi-head GAT layer on Hd / S of amar_rowwise_xw_heads_f32, one wavefront per row, every head in the same walk:
+ *     e_ijh     = LeakyReLU_0.2( S[i, h] + S[j, heads + h] ),   j over the entries of row i (duplicates kept) (+ i itself if self_loop)
+ *     alpha_ijh = exp(e_ijh - max_j e_ijh) / ( sum_j exp(e_ijh - max_j e_ijh) + 1e-9 )         per target i AND head h
+ *     out[i, h, :] = sum_j alpha_ijh Hd[j, h, :]
+ *     concat != 0:  Y[i, 0:heads*C] = ReLU( out[i, :, :] flattened + bias[0:heads*C] )
+ *     concat == 0:  Y[i, 0:C]       = ReLU( (1/heads) sum_h out[i, h, :] + bias[0:C] )       (h ascending)
+ * A row without entries and without self loop gives ReLU(bias).  out_tape (may be NULL; [n_rows, heads*C] contiguous) receives
+ * out[i, :, :] before the bias: what amar_gat_heads_bwd_f32 needs under concat == 0, where Y no longer holds the heads apart.
+ * Y and Hd are strided (ldy, ldh; multiples of 4, 16-byte aligned bases).  C % 4 == 0 and heads*C <= 64; other shapes
+ * AMAR_EUNSUPPORTED. */
+int amar_gat_heads_f32(const int32_t *rowptr, const int32_t *colidx,
+                       const float *Hd, int64_t ldh, int32_t heads, int32_t C,
+                       const float *S, const float *bias, float *Y, int64_t ldy, float *out_tape,
+                       int32_t concat, int32_t self_loop, int32_t n_rows, amar_stream_t stream);
+
 /* ---- scoring head -------------------------------------------------------------------------
  * Y[M, N] = act( X[M, K] . W[K, N] + bias[N] )   fp32 MFMA GEMM (Keras Dense; src/models/dense.py:4-17)
  * ids != NULL gathers the input rows first: row m of the product reads X[ids[m], :]
@@ -601,6 +628,23 @@ int amar_gat_bwd_directed_f32(const int32_t *rowptr, const int32_t *colidx, cons
                               const float *bias, const float *a_self, const float *a_neigh,
                               float *dout, float *row_scratch, float *ds, float *dt, float *dH, int64_t lddh,
                               int32_t self_loop, int32_t n_rows, amar_stream_t stream);
+/* Reverse of amar_gat_heads_f32 given dY = dL/dY, with the structure of amar_gat_bwd_directed_f32: a target walk on rowptr / colidx
+ * (softmax statistics per (row, head), ds), then a source walk on t_rowptr / t_colidx = the stable transpose (dt, dHd); a symmetric
+ * edge multiset passes the one structure twice.  With g_i = dY_i * [Y_i > 0]:
+ *     concat != 0:  g_ih = g_i[h*C : (h+1)*C],  out[i,h,:] = Y[i, h*C : (h+1)*C] - bias   (only read where Y > 0)
+ *     concat == 0:  g_ih = g_i / heads,         out[i,h,:] = out_tape[i, h, :]            (the forward's tape; required)
+ *     c_ih = g_ih . out[i,h,:],   d e_ijh = alpha_ijh (g_ih . Hd[j,h,:] - c_ih),   d pre_ijh = d e_ijh * LeakyReLU'(S[i,h] + S[j,heads+h])
+ *     dS[i, h] = sum_j d pre_ijh,   dS[j, heads + h] = sum_i d pre_ijh                      ([n_rows, 2*heads], the layout of S)
+ *     dHd[j,h,:] = sum_i alpha_ijh g_ih + dS[j,h] a_self[:,h] + dS[j,heads+h] a_neigh[:,h]
+ * dout = g_i in Y's own width ([n_rows, heads*C] or [n_rows, C], contiguous): the source of the bias gradient.  row_scratch:
+ * 3 * heads * n_rows floats.  Row-wise sums in a fixed order, no float atomics: two runs give the same bits.  C % 4 == 0 and
+ * heads*C <= 64; other shapes AMAR_EUNSUPPORTED. */
+int amar_gat_heads_bwd_f32(const int32_t *rowptr, const int32_t *colidx, const int32_t *t_rowptr, const int32_t *t_colidx,
+                           const float *Hd, int64_t ldh, int32_t heads, int32_t C, const float *S,
+                           const float *Y, int64_t ldy, const float *dY, int64_t ldd, const float *bias,
+                           const float *a_self, const float *a_neigh, const float *out_tape,
+                           float *dout, float *row_scratch, float *dS, float *dHd, int64_t lddh,
+                           int32_t concat, int32_t self_loop, int32_t n_rows, amar_stream_t stream);
 int amar_transpose_f32(const float *src, int32_t K, int32_t N, float *dst, amar_stream_t stream);
 int amar_adam_f32(float *w, const float *g, float *m, float *v, int64_t n, float lr_t, float beta_1, float beta_2,
                   float epsilon, float l2, amar_stream_t stream);
