@@ -73,10 +73,12 @@ SIGNATURES = {
     'amar_wgrad_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I32, _I32, _P, _P, _P, _P]),
     'amar_dense_stack_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _I64, _P]),
     'amar_dense_stack_pair_f32': (ctypes.c_int, [_P, _P, _P]),
+    'amar_dense_stack_route': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _I64, _P]),
     'amar_dense_stack_bwd_groups': (ctypes.c_int64, [_I64]),
     'amar_dense_stack_bwd_workspace_floats': (ctypes.c_int64, [_I64, _I32, _P]),
     'amar_dense_stack_bwd_pair_f32': (ctypes.c_int, [_P, _P, _P]),
     'amar_dense_stack_bwd_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _I32, _I64, _P]),
+    'amar_dense_stack_bwd_route': (ctypes.c_int, [_P, _I64, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _I32, _I64, _P]),
     'amar_dense_bwd_workspace_floats': (ctypes.c_int64, [_I64, _I32, _I32]),
     'amar_dense_bwd_groups': (ctypes.c_int64, [_I64]),
     'amar_dense_bwd_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I32, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I32, _I32, _P]),
@@ -1306,6 +1308,44 @@ def dense_stack_bwd_pair(first, second):
     _check(load().amar_dense_stack_bwd_pair_f32(ctypes.byref(d0), ctypes.byref(d1), _stream()), 'amar_dense_stack_bwd_pair_f32')
     return (_deferred_stack_gradients(first['workspace'], *m0) if first.get('defer') else None,
             _deferred_stack_gradients(second['workspace'], *m1) if second.get('defer') else None)
+
+
+class DenseStackRouteInfo(ctypes.Structure):
+    """include/amar_hip.h: amar_dense_stack_route_info"""
+    _fields_ = [('rows', ctypes.c_int32), ('vec_x', ctypes.c_int32), ('vec_w', ctypes.c_int32 * 4), ('groups', ctypes.c_int64),
+                ('lds_bytes', ctypes.c_int64)]
+
+    def as_dict(self, n_layers=4):
+        return dict(rows=int(self.rows), groups=int(self.groups), lds_bytes=int(self.lds_bytes), vec_x=bool(self.vec_x),
+                    vec_w=[bool(v) for v in self.vec_w[:n_layers]])
+
+
+class DenseStackBwdRouteInfo(ctypes.Structure):
+    """include/amar_hip.h: amar_dense_stack_bwd_route_info"""
+    _fields_ = [('rows', ctypes.c_int32), ('vec_top', ctypes.c_int32), ('vec_x', ctypes.c_int32 * 4), ('vec_w', ctypes.c_int32 * 4),
+                ('groups', ctypes.c_int64), ('lds_bytes', ctypes.c_int64)]
+
+    def as_dict(self, n_layers=4):
+        return dict(rows=int(self.rows), groups=int(self.groups), lds_bytes=int(self.lds_bytes), vec_top=bool(self.vec_top),
+                    vec_x=[bool(v) for v in self.vec_x[:n_layers]], vec_w=[bool(v) for v in self.vec_w[:n_layers]])
+
+
+def dense_stack_route(X, weights, biases, acts, outs, ids=None, xcopy=None):
+    """What dense_stack does with these operands (amar_dense_stack_route: host only, nothing is launched; the launcher asks the same
+    functions).  A dict: rows (16 | 64), groups, lds_bytes, vec_x, vec_w (one per layer)."""
+    args = _dense_stack_args(X, weights, biases, acts, outs, ids=ids, xcopy=xcopy)
+    info = DenseStackRouteInfo()
+    _check(load().amar_dense_stack_route(*args, ctypes.byref(info)), 'amar_dense_stack_route')
+    return info.as_dict(len(weights))
+
+
+def dense_stack_bwd_route(dYtop, Ytop, inputs, weights, acts, workspace, dWs, dbs, dX0=None, defer=False):
+    """What dense_stack_bwd does with these operands (amar_dense_stack_bwd_route: host only).  A dict: rows (16 | 64), groups,
+    lds_bytes, vec_top, vec_x and vec_w (one per layer)."""
+    args, _ = _dense_stack_bwd_args(dYtop, Ytop, inputs, weights, acts, workspace, dWs, dbs, dX0=dX0, defer=defer)
+    info = DenseStackBwdRouteInfo()
+    _check(load().amar_dense_stack_bwd_route(*args, ctypes.byref(info)), 'amar_dense_stack_bwd_route')
+    return info.as_dict(len(weights))
 
 
 def dense_bwd_supported(K, N):

@@ -1511,6 +1511,26 @@ static int build_dense_stack(const float *X, int64_t ldx, const int32_t *ids, fl
 
 // batch-sized operands run in 16-row workgroups (see dense_stack_body)
 static bool dense_stack_small_rows(int64_t M) { return M <= 4096; }
+static int64_t dense_stack_groups(int64_t M, int rows) { return (M + rows - 1) / rows; }
+
+// What amar_dense_stack_f32 does with these arguments, from the functions it calls itself (build_dense_stack, dense_stack_small_rows,
+// dense_stack_groups): host only, nothing is launched, the device pointers are looked at for their alignment and for NULL.
+int amar_dense_stack_route(const float *X, int64_t ldx, const int32_t *ids, float *Xcopy, int64_t ldxc, int32_t n_layers,
+                           const float *const *W, const float *const *bias, const int32_t *dims, const int32_t *acts,
+                           float *const *Y, const int64_t *ldy, int64_t M, amar_dense_stack_route_info *out) {
+    if (!out) return AMAR_EINVAL;
+    DenseStackArgs a;
+    size_t lds = 0;
+    int64_t groups = 0;
+    if (const int rc = build_dense_stack(X, ldx, ids, Xcopy, ldxc, n_layers, W, bias, dims, acts, Y, ldy, M, a, lds, groups)) return rc;
+    *out = amar_dense_stack_route_info{};
+    out->rows = dense_stack_small_rows(M) ? 16 : DB_ROWS;
+    out->groups = dense_stack_groups(M, out->rows);                   // (0 for M = 0: no launch)
+    out->lds_bytes = (int64_t)lds;
+    out->vec_x = a.vec_x;
+    for (int l = 0; l < n_layers; ++l) out->vec_w[l] = a.vec_w[l];
+    return AMAR_OK;
+}
 
 int amar_dense_stack_f32(const float *X, int64_t ldx, const int32_t *ids, float *Xcopy, int64_t ldxc, int32_t n_layers,
                          const float *const *W, const float *const *bias, const int32_t *dims, const int32_t *acts,
@@ -1523,7 +1543,7 @@ int amar_dense_stack_f32(const float *X, int64_t ldx, const int32_t *ids, float 
     if (dense_stack_small_rows(M)) {
         static bool allowed16[AMAR_MAX_DEVICES] = {};
         if (const int rc = amar_allow_lds(reinterpret_cast<const void *>(dense_stack_kernel<16>), lds, allowed16)) return rc;
-        hipLaunchKernelGGL(dense_stack_kernel<16>, dim3((unsigned)((M + 15) / 16)), dim3(DB_THREADS), lds, static_cast<hipStream_t>(stream), a);
+        hipLaunchKernelGGL(dense_stack_kernel<16>, dim3((unsigned)dense_stack_groups(M, 16)), dim3(DB_THREADS), lds, static_cast<hipStream_t>(stream), a);
         return amar_check_launch();
     }
     static bool allowed[AMAR_MAX_DEVICES] = {};
@@ -1544,7 +1564,7 @@ int amar_dense_stack_pair_f32(const amar_dense_stack_desc *s0, const amar_dense_
     if (g0 + g1 == 0) return AMAR_OK;
     const size_t lds = lds0 > lds1 ? lds0 : lds1;
     if (dense_stack_small_rows(s0->M) && dense_stack_small_rows(s1->M)) {
-        g0 = (s0->M + 15) / 16; g1 = (s1->M + 15) / 16;
+        g0 = dense_stack_groups(s0->M, 16); g1 = dense_stack_groups(s1->M, 16);
         p.split = (int)g0;
         static bool allowed16[AMAR_MAX_DEVICES] = {};
         if (const int rc = amar_allow_lds(reinterpret_cast<const void *>(dense_stack_pair_kernel<16>), lds, allowed16)) return rc;
@@ -1639,6 +1659,26 @@ int amar_dense_stack_bwd_f32(const float *dYtop, int64_t lddy, const float *Ytop
     }
     if (!(flags & AMAR_DENSE_BWD_DEFER)) reduce_stack_partials(a, dims, dW, db, groups, st);
     return amar_check_launch();
+}
+
+// ... and what amar_dense_stack_bwd_f32 does with its arguments (build_dense_stack_bwd, dense_stack_bwd_rows): host only
+int amar_dense_stack_bwd_route(const float *dYtop, int64_t lddy, const float *Ytop, int64_t ldytop, int32_t n_layers,
+                               const float *const *X, const int64_t *ldx, const float *const *W, const int32_t *dims, const int32_t *acts,
+                               float *dX0, int64_t lddx0, float *const *dW, float *const *db, float *workspace, int32_t flags,
+                               int64_t M, amar_dense_stack_bwd_route_info *out) {
+    (void)flags;                                                     // (AMAR_DENSE_BWD_DEFER leaves the reduction launches out, not the route)
+    if (!out) return AMAR_EINVAL;
+    DenseStackBwdArgs a;
+    size_t lds = 0;
+    int64_t groups = 0;
+    if (const int rc = build_dense_stack_bwd(dYtop, lddy, Ytop, ldytop, n_layers, X, ldx, W, dims, acts, dX0, lddx0, dW, db, workspace, M, a, lds, groups)) return rc;
+    *out = amar_dense_stack_bwd_route_info{};
+    out->rows = dense_stack_bwd_rows(M);
+    out->groups = groups;
+    out->lds_bytes = (int64_t)lds;
+    out->vec_top = a.vec_top;
+    for (int l = 0; l < n_layers; ++l) { out->vec_x[l] = a.vec_x[l]; out->vec_w[l] = a.vec_w[l]; }
+    return AMAR_OK;
 }
 
 int amar_dense_stack_bwd_pair_f32(const amar_dense_stack_bwd_desc *s0, const amar_dense_stack_bwd_desc *s1, amar_stream_t stream) {

@@ -525,18 +525,39 @@ int64_t amar_wgrad_scratch_floats(int64_t M, int32_t K, int32_t N);
  * src/models/dense.py:4-17 called from src/models/basic.py:31-37): y_0 = X[ids] (ids == NULL: X), y_{l+1} = act_l(y_l . W_l + b_l) written to
  * Y[l] (leading dimension ldy[l]: a column slice of a wider buffer realises `Concatenate`), l < n_layers <= 4, every width <= 128
  * (else AMAR_EUNSUPPORTED: layer by layer with amar_dense_f32).  W, bias, Y, ldy, dims (n_layers + 1 widths), acts: HOST arrays of device
- * pointers / values.  Xcopy != NULL: the gathered input rows are also written there (the reverse pass multiplies by them). */
+ * pointers / values.  Xcopy != NULL: the gathered input rows are also written there (the reverse pass multiplies by them).
+ * bias[l] == NULL: layer l has no bias (a zero bias: the same bits as a bias vector of zeros); the `bias` array itself must be given.
+ * M = 0: AMAR_OK, nothing is launched.  Workgroups of 16 rows up to M = 4 096, of 64 rows above. */
 int amar_dense_stack_f32(const float *X, int64_t ldx, const int32_t *ids, float *Xcopy, int64_t ldxc, int32_t n_layers,
                          const float *const *W, const float *const *bias, const int32_t *dims, const int32_t *acts,
                          float *const *Y, const int64_t *ldy, int64_t M, amar_stream_t stream);
 /* Two INDEPENDENT stacks in one launch — the user and the item tower of src/models/basic.py:31-35 inside model.fit: each is 16 workgroups
  * of a 1 024-pair batch and ~18 us as a launch of its own, and a training batch at ML-1M size is a chain of such latencies.  A descriptor
- * holds the arguments of amar_dense_stack_f32 (same meaning, same limits, same error codes); the results are those of two separate calls. */
+ * holds the arguments of amar_dense_stack_f32 (same meaning, same limits, same error codes); the results are those of two separate calls,
+ * bit for bit.  Row form of the pair: 16-row workgroups if BOTH stacks have M <= 4 096, else 64-row workgroups for both (a stack's sums
+ * run in ascending k whatever the row form, so a stack that alone would run 16-row workgroups keeps its bits); the first stack's
+ * workgroups come first; a stack with M = 0 has none, and nothing is launched if both have none. */
 typedef struct amar_dense_stack_desc {
     const float *X; int64_t ldx; const int32_t *ids; float *Xcopy; int64_t ldxc; int32_t n_layers;
     const float *const *W; const float *const *bias; const int32_t *dims; const int32_t *acts; float *const *Y; const int64_t *ldy; int64_t M;
 } amar_dense_stack_desc;
 int amar_dense_stack_pair_f32(const amar_dense_stack_desc *s0, const amar_dense_stack_desc *s1, amar_stream_t stream);
+/* What an amar_dense_stack_f32 call with these arguments does (host only: nothing is launched, the device pointers are looked at for their
+ * alignment and for NULL; the host arrays are read).  The launcher calls the same functions, so the two cannot disagree.  Returns what the
+ * launcher's argument checks return.
+ *   rows       rows per workgroup: 16 (M <= 4 096) or 64
+ *   vec_x      X (and Xcopy, if given) moved by 16 bytes: dims[0] and ldx (and ldxc) multiples of 4 floats, 16-byte aligned bases
+ *   vec_w[l]   W[l] staged by 16-byte loads: dims[l + 1] a multiple of 4, a 16-byte aligned base (0 for l >= n_layers)
+ *   groups     workgroups launched = ceil(M / rows) (0: no launch)
+ *   lds_bytes  dynamic LDS asked for: (2 * 64 * (D + 2) + max_l Kp_l * (Np_l + 2)) floats, D = the widest width rounded up to 16,
+ *              Kp / Np = dims[l] / dims[l + 1] rounded up to 16 (the same for both row forms) */
+typedef struct amar_dense_stack_route_info {
+    int32_t rows, vec_x, vec_w[4];
+    int64_t groups, lds_bytes;
+} amar_dense_stack_route_info;
+int amar_dense_stack_route(const float *X, int64_t ldx, const int32_t *ids, float *Xcopy, int64_t ldxc, int32_t n_layers,
+                           const float *const *W, const float *const *bias, const int32_t *dims, const int32_t *acts,
+                           float *const *Y, const int64_t *ldy, int64_t M, amar_dense_stack_route_info *out);
 /* The reverse pass of a whole Dense stack (a tower / the classifier of src/models/basic.py:11-37 inside model.fit) in ONE launch: from
  * dYtop = d(loss)/d(last output) (Ytop = that output; Ytop == NULL: dYtop is already the last pre-activation's gradient) down to
  * dX0 = d(loss)/d(stack input) (or NULL), leaving every layer's dW[l] [K_l, N_l] and db[l] [N_l].  X[l] = layer l's input (X[l+1] is layer
@@ -551,13 +572,31 @@ int amar_dense_stack_bwd_f32(const float *dYtop, int64_t lddy, const float *Ytop
                              float *dX0, int64_t lddx0, float *const *dW, float *const *db, float *workspace, int32_t flags,
                              int64_t M, amar_stream_t stream);
 /* ... and the reverse passes of two independent stacks in one launch (descriptor = the arguments of amar_dense_stack_bwd_f32; each stack
- * with its own workspace; the partial sums of a stack without AMAR_DENSE_BWD_DEFER in `flags` are added by launches behind the shared one). */
+ * with its own workspace; the partial sums of a stack without AMAR_DENSE_BWD_DEFER in `flags` are added by launches behind the shared one).
+ * The results are those of two separate calls, bit for bit.  Row form of the pair: both stacks must select the same one (both M <= 1 024:
+ * 16-row workgroups; both 1 025 .. 4 096: 64-row workgroups), because a stack's partials are per workgroup; a pair that mixes the two
+ * returns AMAR_EUNSUPPORTED before anything is launched. */
 typedef struct amar_dense_stack_bwd_desc {
     const float *dYtop; int64_t lddy; const float *Ytop; int64_t ldytop; int32_t n_layers;
     const float *const *X; const int64_t *ldx; const float *const *W; const int32_t *dims; const int32_t *acts;
     float *dX0; int64_t lddx0; float *const *dW; float *const *db; float *workspace; int32_t flags; int64_t M;
 } amar_dense_stack_bwd_desc;
 int amar_dense_stack_bwd_pair_f32(const amar_dense_stack_bwd_desc *s0, const amar_dense_stack_bwd_desc *s1, amar_stream_t stream);
+/* What an amar_dense_stack_bwd_f32 call with these arguments does (host only, as amar_dense_stack_route; `flags` does not change it).
+ *   rows       rows per workgroup = rows per partial: 16 (M <= 1 024) or 64 (M <= 4 096; beyond: AMAR_EUNSUPPORTED)
+ *   vec_top    dYtop (and Ytop, if given) read by 16-byte loads: dims[n_layers], lddy (and ldytop) multiples of 4, aligned bases
+ *   vec_x[l]   X[l] read by 16-byte loads: dims[l] and ldx[l] multiples of 4, an aligned base
+ *   vec_w[l]   W[l] read by 16-byte loads: dims[l + 1] a multiple of 4, an aligned base
+ *   groups     workgroups launched = amar_dense_stack_bwd_groups(M)
+ *   lds_bytes  dynamic LDS asked for (the formula of amar_dense_stack_route_info) */
+typedef struct amar_dense_stack_bwd_route_info {
+    int32_t rows, vec_top, vec_x[4], vec_w[4];
+    int64_t groups, lds_bytes;
+} amar_dense_stack_bwd_route_info;
+int amar_dense_stack_bwd_route(const float *dYtop, int64_t lddy, const float *Ytop, int64_t ldytop, int32_t n_layers,
+                               const float *const *X, const int64_t *ldx, const float *const *W, const int32_t *dims, const int32_t *acts,
+                               float *dX0, int64_t lddx0, float *const *dW, float *const *db, float *workspace, int32_t flags,
+                               int64_t M, amar_dense_stack_bwd_route_info *out);
 /* The reverse pass of ONE Dense layer (Keras Dense inside model.fit: src/models/dense.py:4-17, src/experiment.py:183-188) in two launches
  * instead of four:
  *     dZ = dY * act'(Y)   (Y = the layer's OUTPUT; act == AMAR_ACT_NONE or Y == NULL: dY already is dZ)

@@ -173,7 +173,8 @@ def test_dense_bwd_fused(hip, M, K, N, act):
                                                (300, [128, 128, 16], ['relu', 'relu'], False)])
 def test_dense_stack_one_launch(hip, M, dims, acts, gather):
     """amar_dense_stack_f32 (round 4: a Dense stack's forward in one launch, every layer's output kept, optional row gather and a strided
-    last output) against float64 and against amar_dense_f32 layer by layer."""
+    last output) against float64 and against amar_dense_f32 layer by layer.
+    (The 64-row form, M > 4 096, and the edge forms: tests/test_dense_stack_forms_gpu.py.)"""
     rng = np.random.default_rng(M + sum(dims))
     n_src = 500
     x = rng.standard_normal((n_src if gather else M, dims[0])).astype(np.float32)
@@ -208,7 +209,8 @@ def test_dense_stack_one_launch(hip, M, dims, acts, gather):
 def test_dense_stack_bwd_one_launch(hip, M, dims, acts, top_is_dz):
     """amar_dense_stack_bwd_f32 (round 4: the reverse pass of a whole Dense stack in one launch) against float64: every layer's dW and
     db, the input gradient, with the top gradient given w.r.t. the last output or w.r.t. its pre-activation; strided top operands;
-    deferred partial sums equal the reduced gradients."""
+    deferred partial sums equal the reduced gradients.
+    (The 64-row form, 1 024 < M <= 4 096, and the edge forms: tests/test_dense_stack_forms_gpu.py.)"""
     rng = np.random.default_rng(M + sum(dims))
     L = len(acts)
     ws = [(rng.standard_normal((dims[l], dims[l + 1])) * 0.3).astype(np.float32) for l in range(L)]
@@ -731,10 +733,58 @@ def test_randomised_gradient_sweep(hip):
             assert np.abs(got - gw).max() <= 3e-4 * np.abs(gw).max() + 3e-7, (case, cls, tuple(prm.shape))
 
 
+def test_gradients_match_autograd_oracle_with_a_batch_above_1024(hip, monkeypatch):
+    """A batch of 1 100 pairs (train_batch_size above 1 024): the towers' reverse passes take the 64-row pair kernel and the
+    classifier's the 64-row single kernel, which no other gradient test reaches.  Every one-launch reverse call of the step is asked
+    for its route on its real operands (capi.dense_stack_bwd_route) before it runs; loss and gradients against torch autograd in float64,
+    with test_randomised_gradient_sweep's tolerance."""
+    from deep_cbrs_amar_renaissance_amd import capi, engine, training
+    from deep_cbrs_amar_renaissance_amd.models import basic
+    engine.set_seed(7)
+    g = helpers.tiny_graph(n_users=40, n_items=30, n_ratings=400, seed=4)
+    model = basic.BasicGCN(g['adj'], **CFG)
+    helpers.randomize_biases(model, seed=8)
+    rng = np.random.default_rng(3)
+    B = 1100
+    pick = rng.integers(0, len(g['u_ids']), B)                        # with repetitions
+    u, i, y = g['u_ids'][pick], g['i_ids'][pick], rng.integers(0, 2, B)
+    routes, single, pair = [], capi.dense_stack_bwd, capi.dense_stack_bwd_pair
+
+    def recording_single(**spec):
+        routes.append(('single', capi.dense_stack_bwd_route(**spec)))
+        return single(**spec)
+
+    def recording_pair(first, second):
+        routes.append(('pair', capi.dense_stack_bwd_route(**first), capi.dense_stack_bwd_route(**second)))
+        return pair(first, second)
+
+    monkeypatch.setattr(capi, 'dense_stack_bwd', recording_single)
+    monkeypatch.setattr(capi, 'dense_stack_bwd_pair', recording_pair)
+    trainer = training.Trainer(model)
+    loss, grads = trainer.loss_and_grads(u, i, y)
+    monkeypatch.setattr(capi, 'dense_stack_bwd', single)
+    monkeypatch.setattr(capi, 'dense_stack_bwd_pair', pair)
+    print(routes)
+    groups = -(-B // 64)
+    assert sorted(r[0] for r in routes) == ['pair', 'single']         # the classifier alone, both towers in one launch
+    assert all(r['rows'] == 64 and r['groups'] == groups for call in routes for r in call[1:]), routes
+    want_loss, want, _ = otrain.torch_model_grads(g['adj'], helpers.gnn_to_oracle(model.gnn), helpers.basic_head_to_oracle(model.rs),
+                                                  u, i, y, l2=1e-4)
+    assert abs(loss - want_loss) < 1e-5
+    flat = _flatten_oracle_grads(model, want)
+    assert set(flat) == set(grads)
+    for prm, gw in flat.items():
+        got = grads[prm].cpu().numpy().reshape(gw.shape).astype(np.float64)
+        got += 2 * trainer._l2(prm) * prm.detach().cpu().numpy().reshape(gw.shape)
+        print(tuple(prm.shape), float(np.abs(got - gw).max()), float(np.abs(gw).max()))
+        assert np.abs(got - gw).max() <= 3e-4 * np.abs(gw).max() + 3e-7, tuple(prm.shape)
+
+
 def test_dense_stack_pair_equals_two_launches(hip):
     """amar_dense_stack_pair_f32 / amar_dense_stack_bwd_pair_f32 (round 4: the user and the item tower of a training batch in ONE launch each way)
     against the two separate launches: every output, gradient and deferred partial sum bit for bit — stacks of different depth, width,
-    row count and input form (gathered rows / plain rows, a concat slice as the last output)."""
+    row count and input form (gathered rows / plain rows, a concat slice as the last output).
+    (Pairs on the 64-row forms and of mixed row forms: tests/test_dense_stack_forms_gpu.py.)"""
     rng = np.random.default_rng(11)
 
     def stack(dims, acts, M, gather):
