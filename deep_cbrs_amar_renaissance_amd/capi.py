@@ -108,6 +108,8 @@ SIGNATURES = {
     'amar_optim_advance_f32': (ctypes.c_int, [_P, _I32, _I32, _P, _P]),
     'amar_optim_f32': (ctypes.c_int, [_I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _F32, _P]),
     'amar_optim_multi_f32': (ctypes.c_int, [_I32, _I32, _P, _P, _I32, _I64, _P, _F32, _P, _P]),
+    'amar_grad_clip_workspace_floats': (ctypes.c_int64, [_I32, _I64]),
+    'amar_grad_clip_f32': (ctypes.c_int, [_I32, _F32, _P, _I32, _I64, _P, _P, _F32, _P, _P]),
     'amar_bpr_grad_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P]),
     'amar_bpr_sample_i32': (ctypes.c_int, [_P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _I32, _I32, _P, _P, _P, _P]),
     'amar_dropout_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I32, ctypes.c_uint64, _P, _U32, _U32, _F32, _P]),
@@ -1088,6 +1090,61 @@ def optim_multi(rule, flags, hyper, table_dev, n_slots, total_blocks, state, reg
                                        total_blocks, _ptr(state, torch.float32, 'state'), float(reg_scale),
                                        _ptr(loss_acc, torch.float32, 'loss_acc'), _stream())
     _check(code, 'amar_optim_multi_f32')
+
+
+# ---- gradient clipping (include/amar_hip.h: AMAR_CLIP_*) -------------------------------------------------------------------------------
+CLIP_VALUE, CLIP_NORM, CLIP_GLOBAL_NORM = 1, 2, 3
+
+
+class ClipSlot(ctypes.Structure):
+    """include/amar_hip.h: amar_clip_slot"""
+    _fields_ = [('w', ctypes.c_void_p), ('g', ctypes.c_void_p), ('n', ctypes.c_int64), ('first_block', ctypes.c_int64),
+                ('l2', ctypes.c_float), ('g_groups', ctypes.c_int32)]
+
+
+def clip_slot_table(entries):
+    """entries: [(w, g, l2)] contiguous fp32 tensors (g: a tensor or a DeferredGradient) -> (host uint8 tensor holding the slot table,
+    total blocks): the block partition of adam_slot_table / optim_slot_table over the same parameters."""
+    table = (ClipSlot * len(entries))()
+    block = 0
+    for k, (w, g, l2) in enumerate(entries):
+        groups = 0
+        if isinstance(g, DeferredGradient):
+            g, groups = g.partials, g.groups
+            if g.numel() != groups * w.numel():
+                raise ValueError("clip_slot_table: deferred gradient of the wrong size")
+        elif g.numel() != w.numel():
+            raise ValueError("clip_slot_table: gradient of the wrong size")
+        if not (w.is_contiguous() and g.is_contiguous()):
+            raise ValueError("clip_slot_table: contiguous tensors expected")
+        table[k] = ClipSlot(_ptr(w, torch.float32, 'w'), _ptr(g, torch.float32, 'g'), w.numel(), block, float(l2), int(groups))
+        block += (w.numel() + 1023) // 1024
+    host = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).clone()
+    return host, block
+
+
+def finished_gradient(g, n):
+    """Where amar_grad_clip_f32 leaves a slot's finished gradient: group 0 of a DeferredGradient's partials, else the tensor itself."""
+    return g.partials.view(-1)[:n] if isinstance(g, DeferredGradient) else g
+
+
+def grad_clip_workspace_floats(n_slots, total_blocks):
+    count = load().amar_grad_clip_workspace_floats(int(n_slots), int(total_blocks))
+    _check(count if count < 0 else 0, 'amar_grad_clip_workspace_floats')
+    return count
+
+
+def grad_clip(mode, clip, table_dev, n_slots, total_blocks, workspace=None, norms=None, reg_scale=0.0, loss_acc=None):
+    """Finish, measure and clip the gradients of a slot table in place (group 0 of every slot); see include/amar_hip.h."""
+    if workspace is not None and workspace.numel() < max(int(total_blocks), 0) + max(int(n_slots), 0):
+        raise ValueError("grad_clip: workspace of grad_clip_workspace_floats(n_slots, total_blocks) floats expected")
+    if norms is not None and mode in (CLIP_NORM, CLIP_GLOBAL_NORM) and norms.numel() < (n_slots if mode == CLIP_NORM else 1):
+        raise ValueError("grad_clip: norms must hold one float per slot (CLIP_NORM) or one float (CLIP_GLOBAL_NORM)")
+    code = load().amar_grad_clip_f32(int(mode), float(clip), None if table_dev is None else ctypes.c_void_p(table_dev.data_ptr()),
+                                     int(n_slots), int(total_blocks), _ptr(workspace, torch.float32, 'workspace'),
+                                     _ptr(norms, torch.float32, 'norms'), float(reg_scale), _ptr(loss_acc, torch.float32, 'loss_acc'),
+                                     _stream())
+    _check(code, 'amar_grad_clip_f32')
 
 
 def sum_into(x, acc, scale=1.0):

@@ -94,50 +94,75 @@ class AttrDict(dict):
     __setattr__ = __setitem__
 
 
+def _store_clip(optimizer, clipnorm, clipvalue, global_clipnorm):
+    """The gradient clip of every Keras 2 optimizer as attributes of `optimizer`: only what is set (None = off reads back as None through
+    the class attributes below), so an optimizer without a clip carries its hyper-parameters alone."""
+    for name, value in (('clipnorm', clipnorm), ('clipvalue', clipvalue), ('global_clipnorm', global_clipnorm)):
+        if value is not None:
+            setattr(optimizer, name, value)
+
+
 class Adam:
     """keras.optimizers.Adam's constructor (config.yaml:52-56); amsgrad=True selects the AMSGrad rule.  The optimizer classes only carry
-    their rule and hyper-parameters: training.py keeps the state and runs the update on the device."""
+    their rule, hyper-parameters and gradient clip (clipnorm / clipvalue / global_clipnorm, named in every signature so that
+    Experimenter.build_optimizer's filter lets them through; training.OptimizerSpec validates them): training.py keeps the state and runs
+    the clip and the update on the device."""
     rule = 'Adam'
+    clipnorm = clipvalue = global_clipnorm = None
 
-    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False, **kwargs):
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False,
+                 clipnorm=None, clipvalue=None, global_clipnorm=None, **kwargs):
         self.learning_rate, self.beta_1, self.beta_2, self.epsilon, self.amsgrad = learning_rate, beta_1, beta_2, epsilon, bool(amsgrad)
+        _store_clip(self, clipnorm, clipvalue, global_clipnorm)
         if self.amsgrad:
             self.rule = 'AMSGrad'
 
 
 class SGD:
     rule = 'SGD'
+    clipnorm = clipvalue = global_clipnorm = None
 
-    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, **kwargs):
+    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None, clipvalue=None, global_clipnorm=None, **kwargs):
         self.learning_rate, self.momentum, self.nesterov = learning_rate, momentum, bool(nesterov)
+        _store_clip(self, clipnorm, clipvalue, global_clipnorm)
 
 
 class RMSprop:
     rule = 'RMSprop'
+    clipnorm = clipvalue = global_clipnorm = None
 
-    def __init__(self, learning_rate=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False, **kwargs):
+    def __init__(self, learning_rate=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False,
+                 clipnorm=None, clipvalue=None, global_clipnorm=None, **kwargs):
         self.learning_rate, self.rho, self.momentum, self.epsilon, self.centered = learning_rate, rho, momentum, epsilon, bool(centered)
+        _store_clip(self, clipnorm, clipvalue, global_clipnorm)
 
 
 class Adagrad:
     rule = 'Adagrad'
+    clipnorm = clipvalue = global_clipnorm = None
 
-    def __init__(self, learning_rate=0.001, initial_accumulator_value=0.1, epsilon=1e-7, **kwargs):
+    def __init__(self, learning_rate=0.001, initial_accumulator_value=0.1, epsilon=1e-7,
+                 clipnorm=None, clipvalue=None, global_clipnorm=None, **kwargs):
         self.learning_rate, self.initial_accumulator_value, self.epsilon = learning_rate, initial_accumulator_value, epsilon
+        _store_clip(self, clipnorm, clipvalue, global_clipnorm)
 
 
 class Adamax:
     rule = 'Adamax'
+    clipnorm = clipvalue = global_clipnorm = None
 
-    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, **kwargs):
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, clipvalue=None, global_clipnorm=None, **kwargs):
         self.learning_rate, self.beta_1, self.beta_2, self.epsilon = learning_rate, beta_1, beta_2, epsilon
+        _store_clip(self, clipnorm, clipvalue, global_clipnorm)
 
 
 class Nadam:
     rule = 'Nadam'
+    clipnorm = clipvalue = global_clipnorm = None
 
-    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, **kwargs):
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, clipvalue=None, global_clipnorm=None, **kwargs):
         self.learning_rate, self.beta_1, self.beta_2, self.epsilon = learning_rate, beta_1, beta_2, epsilon
+        _store_clip(self, clipnorm, clipvalue, global_clipnorm)
 
 
 OPTIMIZERS = {cls.__name__: cls for cls in (Adam, SGD, RMSprop, Adagrad, Adamax, Nadam)}

@@ -723,22 +723,28 @@ OPTIMIZER_RULES = {
     'Nadam': ('OPT_NADAM', _ADAM_HYPER),
 }
 
+# gradient clip of every Keras 2 optimizer -> AMAR_CLIP_* name in capi
+CLIP_MODES = {'clipvalue': 'CLIP_VALUE', 'clipnorm': 'CLIP_NORM', 'global_clipnorm': 'CLIP_GLOBAL_NORM'}
+
 
 class OptimizerSpec:
     """The update rule and hyper-parameters a trainer runs: read from an optimizer object (experiment.py: `rule` + Keras' attribute
-    names; an object without a rule name means Adam) and / or keyword arguments, which win.  `key` identifies it: two optimizers with
-    equal keys train alike, so a cached trainer (and its state) is reused only for an equal key."""
+    names; an object without a rule name means Adam) and / or keyword arguments, which win — the gradient clip (clipvalue, clipnorm or
+    global_clipnorm: `clip` = (name, value) or None) in the same way.  `key` identifies it: two optimizers with equal keys train alike,
+    so a cached trainer (and its state) is reused only for an equal key."""
 
     def __init__(self, optimizer=None, rule=None, **hyper):
         self.rule = rule or getattr(optimizer, 'rule', None) or 'Adam'
         if self.rule not in OPTIMIZER_RULES:
             raise ValueError("no update rule '{}': choose one of {}".format(self.rule, ', '.join(sorted(OPTIMIZER_RULES))))
         code, defaults = OPTIMIZER_RULES[self.rule]
+        clips = {k: hyper.pop(k) if k in hyper else getattr(optimizer, k, None) for k in CLIP_MODES}
         unknown = set(hyper) - set(defaults)
         if unknown:
             raise TypeError("{} has no hyper-parameter {}".format(self.rule, ', '.join(sorted(unknown))))
         self.values = {k: type(d)(hyper[k] if k in hyper else getattr(optimizer, k, d)) for k, d in defaults.items()}
-        self.key = (self.rule, tuple(sorted(self.values.items())))
+        self.clip = self._checked_clip(clips)
+        self.key = (self.rule, tuple(sorted(self.values.items())), self.clip)
         self.adam = code is None
         if not self.adam:
             self.code = getattr(capi, code)
@@ -747,6 +753,28 @@ class OptimizerSpec:
             self.n_arrays = capi.optim_state_arrays(self.code, self.flags, self.values.get('momentum', 0.0))
         else:
             self.n_arrays = 2
+
+    @staticmethod
+    def _checked_clip(clips):
+        """None, or (name, value) of the one gradient clip that is set (Keras 2's OptimizerV2: None or absent means off)."""
+        given = {}
+        for name, value in clips.items():
+            if value is None:
+                continue
+            value = float(value)
+            if not value > 0.0:                                      # (NaN included)
+                raise ValueError("{} must be a positive number (got {})".format(name, value))
+            given[name] = value
+        if 'clipnorm' in given and 'global_clipnorm' in given:
+            raise ValueError("clipnorm and global_clipnorm cannot both be set (as in Keras)")
+        if 'clipvalue' in given and len(given) > 1:
+            raise ValueError("clipvalue together with clipnorm or global_clipnorm is refused: Keras allows the combination, but the order "
+                             "in which it applies the two could not be checked against it")
+        return next(iter(given.items()), None)
+
+    @property
+    def clip_mode(self):
+        return getattr(capi, CLIP_MODES[self.clip[0]])
 
     def new_arrays(self, param):
         """The rule's state arrays for one parameter: zeros, Adagrad's accumulator at its initial value."""
@@ -917,13 +945,19 @@ class Trainer:
             capi.optim_advance(self._opt_state, spec.code, spec.flags, spec.hyper)
         # one launch updates every parameter (a table of slots, uploaded by a captured copy from pinned memory: the
         # gradient buffers of this graph have fixed addresses) and adds the regularisation loss; one more adds the data loss
+        flat = [(prm.data.view(-1), capi.flat_gradient(grads[prm]), self._l2(prm)) for prm in self.params]
+        if spec.clip:
+            # the clip pass finishes every gradient into group 0 of its own buffer (partials added, L2 part included) and clips it
+            # there: its table is over the same flat buffers, and the optimizer's table below takes group 0 with g_groups = 0, l2 = 0
+            clip_host, _ = capi.clip_slot_table(flat)
+            g['clip_host'][:clip_host.numel()].copy_(clip_host)
+            g['clip_bytes'] = int(clip_host.numel())
+            flat = [(w, capi.finished_gradient(gr, w.numel()), 0.0) for w, gr, _ in flat]
         if spec.adam:
-            entries = [(prm.data.view(-1), capi.flat_gradient(grads[prm]),
-                        self.m[prm].view(-1), self.v[prm].view(-1), self._l2(prm)) for prm in self.params]
+            entries = [(w, gr, self.m[prm].view(-1), self.v[prm].view(-1), l2) for prm, (w, gr, l2) in zip(self.params, flat)]
             host, blocks = capi.adam_slot_table(entries)
         else:
-            entries = [(prm.data.view(-1), capi.flat_gradient(grads[prm]), [a.view(-1) for a in self.opt_arrays[prm]], self._l2(prm))
-                       for prm in self.params]
+            entries = [(w, gr, [a.view(-1) for a in self.opt_arrays[prm]], l2) for prm, (w, gr, l2) in zip(self.params, flat)]
             host, blocks = capi.optim_slot_table(entries)
         g['slot_host'][:host.numel()].copy_(host)                    # pinned buffer allocated before the capture began
         g['slot_bytes'] = int(host.numel())                          # uploaded ONCE, right after the capture (train_batch_graphed), into a
@@ -931,15 +965,38 @@ class Trainer:
         #                                                              by the graph's temporaries): the table never changes — the slots point
         #                                                              into tensors of the graph
         if upload_slots:                                             # (the same body run eagerly: this step's own table, before its Adam launch)
-            g['slot_dev'][:g['slot_bytes']].copy_(g['slot_host'][:g['slot_bytes']])
+            self._upload_slots(g)
         batch = float(g['u'].numel())
         capi.sum_into(terms, self._loss_sum)                         # sum of the per-pair terms = data loss x batch size
+        reg_acc = self._loss_sum
+        if spec.clip:                                                # (adds the regularisation loss itself: not a second time below)
+            capi.grad_clip(spec.clip_mode, spec.clip[1], g['clip_dev'], len(entries), blocks, g['clip_ws'],
+                           reg_scale=batch, loss_acc=reg_acc)
+            reg_acc = None
         if spec.adam:
             capi.adam_multi(g['slot_dev'], len(entries), blocks, self._adam_state, self.b1, self.b2, self.eps,
-                            reg_scale=batch, loss_acc=self._loss_sum)
+                            reg_scale=batch, loss_acc=reg_acc)
         else:
             capi.optim_multi(spec.code, spec.flags, spec.hyper, g['slot_dev'], len(entries), blocks, self._opt_state,
-                             reg_scale=batch, loss_acc=self._loss_sum)
+                             reg_scale=batch, loss_acc=reg_acc)
+
+    def _slot_buffers(self, g):
+        """The slot tables of a batch's buffers `g`: pinned host and device memory (and the clip pass's workspace), allocated before a
+        capture begins."""
+        n = len(self.params)
+        g['slot_host'] = torch.empty(64 * n + 64, dtype=torch.uint8).pin_memory()   # >= sizeof(amar_adam_slot) per parameter
+        g['slot_dev'] = torch.empty(64 * n + 64, dtype=torch.uint8, device=self.device)
+        if self.spec.clip:
+            blocks = sum((prm.numel() + 1023) // 1024 for prm in self.params)
+            g['clip_host'] = torch.empty(64 * n + 64, dtype=torch.uint8).pin_memory()
+            g['clip_dev'] = torch.empty(64 * n + 64, dtype=torch.uint8, device=self.device)
+            g['clip_ws'] = torch.zeros(capi.grad_clip_workspace_floats(n, blocks), dtype=torch.float32, device=self.device)
+
+    @staticmethod
+    def _upload_slots(g):
+        g['slot_dev'][:g['slot_bytes']].copy_(g['slot_host'][:g['slot_bytes']])
+        if 'clip_bytes' in g:
+            g['clip_dev'][:g['clip_bytes']].copy_(g['clip_host'][:g['clip_bytes']])
 
     def train_batch_graphed(self, u_ids, i_ids, y, bert=None, graph=True):
         """One training batch replayed from a hipGraph: the forward, the reverse pass and the Adam update are ~100
@@ -968,8 +1025,7 @@ class Trainer:
                            'y': uiy[2 * b:].view(torch.float32),
                            'ub': torch.zeros((b, d), dtype=torch.float32, device=dev) if with_blocks else None,
                            'ib': torch.zeros((b, d), dtype=torch.float32, device=dev) if with_blocks else None}
-            g['slot_host'] = torch.empty(64 * len(self.params) + 64, dtype=torch.uint8).pin_memory()   # >= sizeof(amar_adam_slot) per parameter
-            g['slot_dev'] = torch.empty(64 * len(self.params) + 64, dtype=torch.uint8, device=dev)
+            self._slot_buffers(g)
             # pinned staging for the batch's ids and labels, four sets in turn: the uploads are asynchronous, so the host prepares
             # batch k + 1 while the device still runs batch k (a pageable copy_ made the host wait for the stream every batch:
             # 0.13 ms of a 0.52 ms batch at ml1m(s=1))
@@ -985,7 +1041,7 @@ class Trainer:
                     with torch.no_grad():
                         self._graph_body()
                 g['graph'], _ = capture_graph(body)
-                g['slot_dev'][:g['slot_bytes']].copy_(g['slot_host'][:g['slot_bytes']])   # the Adam slot table of this graph (fixed addresses): once, not per replay
+                self._upload_slots(g)                                # the slot tables of this graph (fixed addresses): once, not per replay
                 self._graphs[key] = g
             else:
                 self._eager_batches = {key: g}
@@ -1067,7 +1123,7 @@ class Trainer:
                         self._graph_body()
                 self._sync_step()
                 g['graph'], _ = capture_graph(body)
-                g['slot_dev'][:g['slot_bytes']].copy_(g['slot_host'][:g['slot_bytes']])
+                self._upload_slots(g)
                 self._graphs[key] = g
             else:
                 self._seen.add(key)
@@ -1089,8 +1145,7 @@ class Trainer:
         ui = uiy[:2 * b]
         g = self._g = {'uiy': uiy, 'ui': ui, 'u': ui[:b], 'i': ui[b:], 'y': uiy[2 * b:].view(torch.float32), 'ub': None, 'ib': None,
                        'sampler': sampler}
-        g['slot_host'] = torch.empty(64 * len(self.params) + 64, dtype=torch.uint8).pin_memory()
-        g['slot_dev'] = torch.empty(64 * len(self.params) + 64, dtype=torch.uint8, device=dev)
+        self._slot_buffers(g)
         return g
 
     def _sync_step(self):
@@ -1165,15 +1220,34 @@ class Trainer:
         grads[one.embeddings] = tapes[0].backward(self._lift(dx0[:gnn.n_users], one.adj_matrix.shape[0]), grads)
         grads[two.embeddings] = tapes[1].backward(self._lift(dx0[gnn.n_users:], two.adj_matrix.shape[0]), grads)
 
+    def _clipped(self, grads):
+        """The eager form of the clip pass of `_graph_body`: {param: finished, clipped gradient} in buffers of the trainer's own (the
+        caller's gradients stay as they are); the L2 part is in them, so the update that follows runs with l2 = 0."""
+        spec = self.spec
+        c = getattr(self, '_eager_clip', None)
+        if c is None:
+            c = self._eager_clip = {'g': {prm: torch.empty(prm.numel(), dtype=torch.float32, device=self.device) for prm in self.params}}
+            host, c['blocks'] = capi.clip_slot_table([(prm.data.view(-1), c['g'][prm], self._l2(prm)) for prm in self.params])
+            c['table'] = host.to(self.device)
+            c['ws'] = torch.zeros(capi.grad_clip_workspace_floats(len(self.params), c['blocks']), dtype=torch.float32, device=self.device)
+        for prm in self.params:
+            c['g'][prm].copy_(grads[prm].reshape(-1))
+        capi.grad_clip(spec.clip_mode, spec.clip[1], c['table'], len(self.params), c['blocks'], c['ws'])
+        return c['g']
+
     def apply_gradients(self, grads):
         self.t += 1
+        l2_of = self._l2
+        if self.spec.clip:
+            with torch.no_grad():
+                grads, l2_of = self._clipped(grads), lambda prm: 0.0
         if not self.spec.adam:
             spec = self.spec
             with torch.no_grad():
                 capi.optim_advance(self._opt_state, spec.code, spec.flags, spec.hyper)
                 for prm in self.params:
                     capi.optim(spec.code, spec.flags, spec.hyper, prm.data.view(-1), grads[prm].contiguous().view(-1),
-                               [a.view(-1) for a in self.opt_arrays[prm]], self._opt_state, l2=self._l2(prm))
+                               [a.view(-1) for a in self.opt_arrays[prm]], self._opt_state, l2=l2_of(prm))
                     prm.add_(0)                                        # bumps the autograd version counter
             return
         lr_t = self.lr * np.sqrt(1.0 - self.b2 ** self.t) / (1.0 - self.b1 ** self.t)
@@ -1181,7 +1255,7 @@ class Trainer:
             for prm in self.params:
                 g = grads[prm]
                 capi.adam(prm.data.view(-1), g.contiguous().view(-1), self.m[prm].view(-1), self.v[prm].view(-1),
-                          lr_t, self.b1, self.b2, self.eps, l2=self._l2(prm))
+                          lr_t, self.b1, self.b2, self.eps, l2=l2_of(prm))
                 prm._version  # noqa: B018  (data-level update; bump below keeps hoisting caches honest)
                 prm.add_(0)                                            # bumps the autograd version counter
 

@@ -758,6 +758,37 @@ typedef struct amar_optim_slot { float *w; const float *g; float *s0; float *s1;
 int amar_optim_multi_f32(int32_t rule, int32_t flags, const amar_optim_hyper *hyper, const amar_optim_slot *slots, int32_t n_slots,
                          int64_t total_blocks, const float *state, float reg_scale, float *loss_acc, amar_stream_t stream);
 
+/* ---- gradient clipping: clipvalue, clipnorm, global_clipnorm of every tf.keras optimizer (Keras 2.7 / 2.8 OptimizerV2, restated) ---------
+ * The clipped quantity is the finished gradient of (data loss + regularisation losses), per parameter tensor (slot):
+ *   gi = fmaf(2 l2, w, g[0] + g[1] + ... + g[G-1])     the partials added in the order 0 .. G-1, as the optimizer launches add them
+ * AMAR_CLIP_VALUE        gi <- min(max(gi, -clip), clip)
+ * AMAR_CLIP_NORM         gi <- gi * s,  s = clip / max(||gi||_2, clip)                      one s per slot
+ * AMAR_CLIP_GLOBAL_NORM  gi <- gi * s,  s = clip / max(sqrt(sum over slots ||gi||_2^2), clip)   one s for all slots
+ * s is formed in float32 from a float32 sum of squares, as (norm > clip ? clip / norm : 1).  This differs from TensorFlow's
+ * (g * clip) / max(norm, clip) and clip * min(1 / norm, 1 / clip) by rounding only, and where the clip does not bind s == 1.0f exactly:
+ * no bit of a gradient changes.  A zero gradient has norm 0 and s = 1 (no NaN is made); non-finite gradients propagate, nothing special
+ * is done for them.
+ * The slot table (device memory) is partitioned as the optimizer slot tables are: slot k owns blocks [first_block_k, first_block_{k+1}) of
+ * 1024 elements, first_block_0 = 0, total_blocks = sum of ceil(n / 1024); g_groups == 0: g[n] is the gradient, g_groups = G > 0: g
+ * holds G partials [G][n].  After the call g[0 .. n) of every slot holds the clipped finished gradient and the groups 1 .. G-1 are as
+ * they were; if loss_acc != NULL, reg_scale * l2 * sum(w^2) has been added to *loss_acc (the expression of the optimizer launches).
+ * The optimizer launch that follows runs on a table whose slots have g_groups = 0 and l2 = 0: fmaf(0, w, g) == g, so it applies the
+ * clipped gradient as it is, and it is not given loss_acc a second time.
+ * Three launches: finish (gi into group 0; VALUE clamps and is done; per block the sum of squares into the workspace), scales (one
+ * workgroup per slot, or one in all, adds the block sums in ascending block order with a fixed tree and writes s), apply (g *= s).
+ * No float atomic takes part in a norm: the same inputs give the same bits on every run, eagerly or replayed from a captured graph,
+ * and every value that depends on the step lives in device memory (only mode and clip are arguments).
+ * workspace: the number of floats the _workspace_floats function returns (total_blocks + n_slots; VALUE does not use it, NULL allowed).
+ * norms: NULL, or [n_slots] (NORM) / [1] (GLOBAL_NORM) floats that receive the measured norms (before scaling); VALUE ignores it.
+ * Unknown mode, clip not > 0 (NaN included), NULL tables, n_slots < 1, total_blocks < 1 or > 2^31 - 1: AMAR_EINVAL. */
+#define AMAR_CLIP_VALUE       1
+#define AMAR_CLIP_NORM        2
+#define AMAR_CLIP_GLOBAL_NORM 3
+typedef struct amar_clip_slot { const float *w; float *g; int64_t n; int64_t first_block; float l2; int32_t g_groups; } amar_clip_slot;
+int64_t amar_grad_clip_workspace_floats(int32_t n_slots, int64_t total_blocks);
+int amar_grad_clip_f32(int32_t mode, float clip, const amar_clip_slot *slots, int32_t n_slots, int64_t total_blocks,
+                       float *workspace, float *norms, float reg_scale, float *loss_acc, amar_stream_t stream);
+
 /* ---- BPR training (utilities/losses.py:BPRLoss, data/datasets.py:UserItemGraphPosNegSample) ----------------------------------
  * amar_bpr_grad_f32    the pairwise loss of src/utilities/losses.py:15-25 on the probability column p ([B], or a strided [B, 1] with
  *                      leading dimension ldp): h = B / 2 (an odd B drops its last element), s_j = sigmoid(p[j] - p[h + j]),
