@@ -84,6 +84,8 @@ SIGNATURES = {
     'amar_dense_bwd_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I32, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I32, _I32, _P]),
     'amar_dense_bwd_route': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I32, _P, _I64, _P, _P, _P, _I64, _I64, _I32, _I32, _P]),
     'amar_bce_grad_f32': (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P]),
+    'amar_wgrad_route': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I32, _I32, _P, _P, _P]),
+    'amar_scatter_add_rows_route': (ctypes.c_int, [_I64, _I32, _P]),
     'amar_scatter_add_rows_f32': (ctypes.c_int, [_P, _I64, _P, _I32, _P, _I64, _I64, _I32, _P]),
     'amar_add_inplace_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I32, _F32, _P]),
     'amar_row_affine_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _I64, _I64, _I32, _P]),
@@ -1229,6 +1231,30 @@ def wgrad(X, dZ, dW=None, db=None):
     _check(code, 'amar_wgrad_f32')
 
 
+class WgradRouteInfo(ctypes.Structure):
+    """include/amar_hip.h: amar_wgrad_route_info"""
+    _fields_ = [(name, ctypes.c_int32) for name in ('kernel', 'wg_rows', 'grid_k', 'grid_n')] + \
+               [('chunks', ctypes.c_int64), ('scratch_floats', ctypes.c_int64)]
+
+    def as_dict(self):
+        d = {name: int(getattr(self, name)) for name, _ in self._fields_}
+        d['kernel'] = 'mfma' if d['kernel'] == 1 else 'partial'
+        return d
+
+
+def wgrad_route(X, dZ, dW=None, db=None):
+    """Which kernel wgrad takes for these operands (amar_wgrad_route: host only, nothing is launched; the launcher asks the same
+    function).  A dict: kernel 'mfma' | 'partial', wg_rows, chunks, grid_k, grid_n, scratch_floats."""
+    M, N = dZ.shape
+    K = X.shape[1] if X is not None else 0
+    info = WgradRouteInfo()
+    code = load().amar_wgrad_route(_ptr(X if dW is not None else None, torch.float32, 'X'), _ld(X, 'X') if dW is not None else 0,
+                                   _ptr(dZ, torch.float32, 'dZ'), _ld(dZ, 'dZ'), M, K, N,
+                                   _ptr(dW, torch.float32, 'dW'), _ptr(db, torch.float32, 'db'), ctypes.byref(info))
+    _check(code, 'amar_wgrad_route')
+    return info.as_dict()
+
+
 def dense_stack_supported(dims):
     """amar_dense_stack_f32 takes a stack of these widths (at most 4 layers, every width <= 128)."""
     return 2 <= len(dims) <= 5 and all(1 <= int(d) <= 128 for d in dims)
@@ -1628,6 +1654,24 @@ def gat_bwd_dropout(rowptr, colidx, H, s_self, s_neigh, Y, dY, bias, a_self, a_n
         1 if self_loop else 0, n, *drop._args(), _stream())
     _check(code, name)
     return dout, ds, dt, dH
+
+
+class ScatterAddRowsRouteInfo(ctypes.Structure):
+    """include/amar_hip.h: amar_scatter_add_rows_route_info"""
+    _fields_ = [(name, ctypes.c_int32) for name in ('kernel', 'blocks', 'lds_bytes', 'positions_per_wave')]
+
+    def as_dict(self):
+        d = {name: int(getattr(self, name)) for name, _ in self._fields_}
+        d['kernel'] = 'atomic' if d['kernel'] == 1 else 'owner'
+        return d
+
+
+def scatter_add_rows_route(M, W):
+    """Which kernel scatter_add_rows takes for M ids of W columns (amar_scatter_add_rows_route: host only).  A dict: kernel 'owner' |
+    'atomic', blocks, lds_bytes, positions_per_wave."""
+    info = ScatterAddRowsRouteInfo()
+    _check(load().amar_scatter_add_rows_route(int(M), int(W), ctypes.byref(info)), 'amar_scatter_add_rows_route')
+    return info.as_dict()
 
 
 def scatter_add_rows(src, ids, dst, base=0):

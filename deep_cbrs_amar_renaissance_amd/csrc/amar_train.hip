@@ -1862,28 +1862,62 @@ int64_t amar_wgrad_scratch_floats(int64_t M, int32_t K, int32_t N) {
     return chunks * ((int64_t)K * N + N);
 }
 
+// Which kernel a weight-gradient call takes, and how it is cut: decided HERE and nowhere else — amar_wgrad_f32 launches what this returns
+// and amar_wgrad_route reports it.  Pointers are looked at for NULL and for their alignment only.
+struct WgradRoute { bool mfma; int wg_rows; int64_t chunks; unsigned grid_k, grid_n; int64_t scratch_floats; };
+static int wgrad_route(const float *X, int64_t ldx, const float *dZ, int64_t ldz, int64_t M, int32_t K, int32_t N, const float *dW, const float *db,
+                       bool have_scratch, WgradRoute &r) {
+    if (M < 1 || N < 1 || !dZ || ldz < N || !have_scratch || (!dW && !db)) return AMAR_EINVAL;
+    if (dW && (!X || K < 1 || ldx < K)) return AMAR_EINVAL;
+    // wide layers over batch-sized operands: every 32 x 32 tile of dW by one workgroup on the matrix instruction, nothing to reduce
+    r.mfma = dW && M <= 16384 && (K & 3) == 0 && (N & 3) == 0 && (ldx & 3) == 0 && (ldz & 3) == 0 && amar_aligned16(X) && amar_aligned16(dZ) &&
+             (int64_t)((K + 31) / 32) * ((N + 31) / 32) >= 16;
+    if (r.mfma) {
+        r.wg_rows = 0; r.chunks = 1; r.scratch_floats = 0;
+        r.grid_k = (unsigned)((K + 31) / 32); r.grid_n = (unsigned)((N + 31) / 32);
+        return AMAR_OK;
+    }
+    r.wg_rows = wg_rows(M);
+    r.chunks = (M + r.wg_rows - 1) / r.wg_rows;
+    if (r.chunks > 0x7fffffff) return AMAR_EUNSUPPORTED;
+    r.grid_k = (unsigned)(dW ? (K + 15) / 16 : 1);
+    r.grid_n = (unsigned)((N + 15) / 16);
+    r.scratch_floats = r.chunks * ((int64_t)(dW ? K : 0) * N + N);
+    return AMAR_OK;
+}
+
+int amar_wgrad_route(const float *X, int64_t ldx, const float *dZ, int64_t ldz, int64_t M, int32_t K, int32_t N, float *dW, float *db,
+                     amar_wgrad_route_info *out) {
+    if (!out) return AMAR_EINVAL;
+    WgradRoute r;
+    if (const int rc = wgrad_route(X, ldx, dZ, ldz, M, K, N, dW, db, true, r)) return rc;
+    out->kernel = r.mfma ? AMAR_WGRAD_KERNEL_MFMA : AMAR_WGRAD_KERNEL_PARTIAL;
+    out->wg_rows = r.wg_rows;
+    out->grid_k = (int32_t)r.grid_k;
+    out->grid_n = (int32_t)r.grid_n;
+    out->chunks = r.chunks;
+    out->scratch_floats = r.scratch_floats;
+    return AMAR_OK;
+}
+
 int amar_wgrad_f32(const float *X, int64_t ldx, const float *dZ, int64_t ldz, int64_t M, int32_t K, int32_t N,
                    float *dW, float *db, float *scratch, amar_stream_t stream) {
-    if (M < 1 || N < 1 || !dZ || ldz < N || !scratch || (!dW && !db)) return AMAR_EINVAL;
-    if (dW && (!X || K < 1 || ldx < K)) return AMAR_EINVAL;
+    WgradRoute route;
+    if (const int rc = wgrad_route(X, ldx, dZ, ldz, M, K, N, dW, db, scratch != nullptr, route)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // wide layers over batch-sized operands: every 32 x 32 tile of dW by one workgroup on the matrix instruction, nothing to reduce
-    if (dW && M <= 16384 && (K & 3) == 0 && (N & 3) == 0 && (ldx & 3) == 0 && (ldz & 3) == 0 && amar_aligned16(X) && amar_aligned16(dZ) &&
-        (int64_t)((K + 31) / 32) * ((N + 31) / 32) >= 16) {
+    if (route.mfma) {
         const size_t lds = (size_t)2 * WM_ROWS * WM_STRIDE * sizeof(float);
         static bool allowed[AMAR_MAX_DEVICES] = {};
         if (const int rc = amar_allow_lds(reinterpret_cast<const void *>(wgrad_mfma_kernel), lds, allowed)) return rc;
-        hipLaunchKernelGGL(wgrad_mfma_kernel, dim3((unsigned)((K + 31) / 32), (unsigned)((N + 31) / 32)), dim3(256), lds, st, X, ldx, dZ, ldz, M, K, N, dW, db);
+        hipLaunchKernelGGL(wgrad_mfma_kernel, dim3(route.grid_k, route.grid_n), dim3(256), lds, st, X, ldx, dZ, ldz, M, K, N, dW, db);
         return amar_check_launch();
     }
     const int Kk = dW ? K : 0;
-    const int WG_ROWS = wg_rows(M);
-    const int64_t chunks = (M + WG_ROWS - 1) / WG_ROWS;
-    if (chunks > 0x7fffffff) return AMAR_EUNSUPPORTED;
+    const int64_t chunks = route.chunks;
     float *part_w = dW ? scratch : nullptr;
     float *part_b = db ? scratch + chunks * (int64_t)Kk * N : nullptr;
-    const dim3 grid((unsigned)chunks, (unsigned)(dW ? (K + 15) / 16 : 1), (unsigned)((N + 15) / 16));
-    hipLaunchKernelGGL(wgrad_partial_kernel, grid, dim3(256), 0, st, dW ? X : nullptr, ldx, dZ, ldz, M, Kk ? Kk : 1, N, part_w, part_b, WG_ROWS);
+    const dim3 grid((unsigned)chunks, route.grid_k, route.grid_n);
+    hipLaunchKernelGGL(wgrad_partial_kernel, grid, dim3(256), 0, st, dW ? X : nullptr, ldx, dZ, ldz, M, Kk ? Kk : 1, N, part_w, part_b, route.wg_rows);
     if (dW && db) hipLaunchKernelGGL(reduce_partials2_kernel, dim3(grid1d((int64_t)K * N + N)), dim3(256), 0, st, part_w, (int64_t)K * N, dW,
                                      part_b, (int64_t)N, db, (int)chunks);
     else if (dW) hipLaunchKernelGGL(reduce_partials_kernel, dim3(grid1d((int64_t)K * N)), dim3(256), 0, st, part_w, (int)chunks, (int64_t)K * N, dW);
@@ -1897,18 +1931,50 @@ int amar_bce_grad_f32(const float *p, int64_t ldp, const float *y, float *dz, fl
     return amar_check_launch();
 }
 
+// Owner kernel or atomics, and the launch of either: decided HERE and nowhere else — amar_scatter_add_rows_f32 launches what this returns
+// and amar_scatter_add_rows_route reports it.
+struct ScatterRoute { bool owner; unsigned blocks; size_t lds_bytes; int positions_per_wave; };
+static int scatter_route(int64_t M, int32_t W, ScatterRoute &r) {
+    if (M < 0 || W < 1) return AMAR_EINVAL;
+    r.owner = M <= SCATTER_OWNER_MAX;
+    if (M == 0) { r.blocks = 0; r.lds_bytes = 0; r.positions_per_wave = 0; return AMAR_OK; }       // nothing is launched
+    if (r.owner) {
+        int64_t blocks = (M + 3) / 4;                                 // one wavefront per position, every workgroup holds the id list
+        if (blocks > 1024) blocks = 1024;
+        r.blocks = (unsigned)blocks;
+        r.lds_bytes = (size_t)M * sizeof(int32_t);
+        r.positions_per_wave = (int)((M + blocks * 4 - 1) / (blocks * 4));     // trips of wave 0's position loop: p = 0, 4 blocks, ...
+    } else {
+        r.blocks = grid1d(M * W);
+        r.lds_bytes = 0;
+        r.positions_per_wave = 0;
+    }
+    return AMAR_OK;
+}
+
+int amar_scatter_add_rows_route(int64_t M, int32_t W, amar_scatter_add_rows_route_info *out) {
+    if (!out) return AMAR_EINVAL;
+    ScatterRoute r;
+    if (const int rc = scatter_route(M, W, r)) return rc;
+    out->kernel = r.owner ? AMAR_SCATTER_KERNEL_OWNER : AMAR_SCATTER_KERNEL_ATOMIC;
+    out->blocks = (int32_t)r.blocks;
+    out->lds_bytes = (int32_t)r.lds_bytes;
+    out->positions_per_wave = r.positions_per_wave;
+    return AMAR_OK;
+}
+
 int amar_scatter_add_rows_f32(const float *src, int64_t lds, const int32_t *ids, int32_t base, float *dst, int64_t ldd,
                               int64_t M, int32_t W, amar_stream_t stream) {
     if (M < 0 || W < 1 || !src || !ids || !dst || lds < W || ldd < W) return AMAR_EINVAL;
     if (M == 0) return AMAR_OK;
-    if (M <= SCATTER_OWNER_MAX) {
-        int64_t blocks = (M + 3) / 4;                                 // one wavefront per position, every workgroup holds the id list
-        if (blocks > 1024) blocks = 1024;
-        hipLaunchKernelGGL(scatter_add_rows_owner_kernel, dim3((unsigned)blocks), dim3(256), (size_t)M * sizeof(int32_t), static_cast<hipStream_t>(stream),
+    ScatterRoute route;
+    if (const int rc = scatter_route(M, W, route)) return rc;
+    if (route.owner) {
+        hipLaunchKernelGGL(scatter_add_rows_owner_kernel, dim3(route.blocks), dim3(256), route.lds_bytes, static_cast<hipStream_t>(stream),
                            src, lds, ids, base, dst, ldd, (int)M, W);
         return amar_check_launch();
     }
-    hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(grid1d(M * W)), dim3(256), 0, static_cast<hipStream_t>(stream), src, lds, ids, base, dst, ldd, M, W);
+    hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(route.blocks), dim3(256), 0, static_cast<hipStream_t>(stream), src, lds, ids, base, dst, ldd, M, W);
     return amar_check_launch();
 }
 

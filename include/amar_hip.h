@@ -644,9 +644,38 @@ int amar_dense_bwd_route(const float *X, int64_t ldx, const float *Y, int64_t ld
 int amar_dense_bwd_f32(const float *X, int64_t ldx, const float *Y, int64_t ldy, const float *dY, int64_t lddy, const float *W,
                        int32_t act, float *dX, int64_t lddx, float *dW, float *db, float *dZ, int64_t lddz, float *workspace,
                        int64_t M, int32_t K, int32_t N, amar_stream_t stream);
+/* Which kernel an amar_wgrad_f32 call with these arguments takes (host only: nothing is launched, the pointers are looked at for NULL
+ * and for their alignment).  The launcher asks the same function.  Returns what the launcher's argument checks return (a scratch
+ * buffer is taken as given).
+ *   kernel          AMAR_WGRAD_KERNEL_MFMA (one workgroup per 32 x 32 tile of dW walks all rows on the matrix instruction: dW asked for,
+ *                   M <= 16 384, K, N, ldx, ldz multiples of 4, X and dZ 16-byte aligned, at least 16 tiles) or _PARTIAL (16 x 16 tiles
+ *                   over row chunks, then a reduction launch in chunk order)
+ *   wg_rows         partial: rows per chunk, 128 ... 512 in steps of 64 (max(128, min(512, ceil(floor(M / 64) / 64) * 64))); mfma: 0
+ *   grid_k, grid_n  tiles of dW along K and N (partial: 16 wide, grid_k = 1 without dW; mfma: 32 wide)
+ *   chunks          partial: row chunks = partial sums per element; mfma: 1
+ *   scratch_floats  floats of `scratch` the call writes: chunks * (K N + N) with K taken as 0 without dW; mfma: 0 */
+#define AMAR_WGRAD_KERNEL_PARTIAL 0
+#define AMAR_WGRAD_KERNEL_MFMA 1
+typedef struct amar_wgrad_route_info {
+    int32_t kernel, wg_rows, grid_k, grid_n;
+    int64_t chunks, scratch_floats;
+} amar_wgrad_route_info;
+int amar_wgrad_route(const float *X, int64_t ldx, const float *dZ, int64_t ldz, int64_t M, int32_t K, int32_t N, float *dW, float *db,
+                     amar_wgrad_route_info *out);
 int amar_wgrad_f32(const float *X, int64_t ldx, const float *dZ, int64_t ldz, int64_t M, int32_t K, int32_t N,
                    float *dW, float *db, float *scratch, amar_stream_t stream);
 int amar_bce_grad_f32(const float *p, int64_t ldp, const float *y, float *dz, float *loss_terms, int64_t B, amar_stream_t stream);
+/* Which kernel an amar_scatter_add_rows_f32 call over M ids of W columns takes (host only; the launcher asks the same function).
+ *   kernel              AMAR_SCATTER_KERNEL_OWNER (M <= 8 192: no atomics, fixed order) or _ATOMIC
+ *   blocks              workgroups launched (owner: min(ceil(M / 4), 1 024) of four wavefronts; 0 for M = 0: nothing is launched)
+ *   lds_bytes           owner: the id list, 4 M bytes; atomic: 0
+ *   positions_per_wave  owner: positions the first wavefront walks (2 from M = 4 097 on); atomic: 0 */
+#define AMAR_SCATTER_KERNEL_OWNER 0
+#define AMAR_SCATTER_KERNEL_ATOMIC 1
+typedef struct amar_scatter_add_rows_route_info {
+    int32_t kernel, blocks, lds_bytes, positions_per_wave;
+} amar_scatter_add_rows_route_info;
+int amar_scatter_add_rows_route(int64_t M, int32_t W, amar_scatter_add_rows_route_info *out);
 int amar_scatter_add_rows_f32(const float *src, int64_t lds, const int32_t *ids, int32_t base, float *dst, int64_t ldd,
                               int64_t M, int32_t W, amar_stream_t stream);
 int amar_add_inplace_f32(float *dst, int64_t ldd, const float *src, int64_t lds, int64_t M, int32_t W, float scale, amar_stream_t stream);
