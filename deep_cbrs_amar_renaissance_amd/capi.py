@@ -60,6 +60,8 @@ SIGNATURES = {
     'amar_chain_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I32, _P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _I64, _I64, _P]),
     'amar_chain_indexed_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I32, _P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _I64, _P, _I64, _P]),
     'amar_chain_segments_f32': (ctypes.c_int, [_P, _P, _P, _I32, _P, _I32, _P, _P, _P, _I32, _P, _I64, _I64, _P]),
+    'amar_chain_route': (ctypes.c_int, [_P, _I64, _I32, _P, _I32, _P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _I64, _P, _I64, _P]),
+    'amar_chain_segments_route': (ctypes.c_int, [_P, _P, _P, _I32, _P, _I32, _P, _P, _P, _I32, _P, _I64, _I64, _P]),
     'amar_dual_chain_f32': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _I64, _I64, _P]),
     'amar_dual_chain_indexed_f32': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _I64, _P, _I64, _P]),
     'amar_copy_columns_f32': (ctypes.c_int, [_P, _I64, _P, _I32, _P, _I64, _I64, _I32, _P]),
@@ -731,15 +733,20 @@ def dense_split(X, Wq, K, N, bias, Y, act='relu', ids=None):
     _check(code, 'amar_dense_split_f32')
 
 
-CHAIN_MAX_WIDTH, CHAIN_MAX_LAYERS = 128, 8
+CHAIN_MAX_WIDTH, CHAIN_MAX_LAYERS, CHAIN_MAX_BLOB_BYTES = 128, 8, 150 * 1024
 
 
 def chain_supported(dims, in_a, in_b=0, sum_inputs=False):
-    """True when amar_chain_f32 can run a dense stack with these widths (else use dense() per layer)."""
+    """True when amar_chain_f32 can run a dense stack with these widths (else use dense() per layer): the width, layer-count and
+    alignment limits of include/amar_hip.h, and a packed blob (amar_chain_pack_floats) of at most 150 KB — three 128 x 128 layers
+    are too many."""
     width_in = in_a if sum_inputs else in_a + in_b
-    return (1 <= len(dims) - 1 <= CHAIN_MAX_LAYERS and max(dims) <= CHAIN_MAX_WIDTH and in_a % 4 == 0 and in_a >= 4
+    if not (1 <= len(dims) - 1 <= CHAIN_MAX_LAYERS and min(dims) >= 1 and max(dims) <= CHAIN_MAX_WIDTH and in_a % 4 == 0 and in_a >= 4
             and in_b % 4 == 0 and dims[0] == width_in and (not sum_inputs or in_a == in_b)
-            and (dims[-1] % 4 == 0 or (dims[-1] == 1 and len(dims) > 2)))
+            and (dims[-1] % 4 == 0 or (dims[-1] == 1 and len(dims) > 2))):
+        return False
+    floats = load().amar_chain_pack_floats((ctypes.c_int32 * len(dims))(*dims), len(dims) - 1)
+    return 0 < 4 * floats <= CHAIN_MAX_BLOB_BYTES
 
 
 def chain_pack(kernels, biases):
@@ -796,8 +803,7 @@ class ConcatTable:
         return out
 
 
-def chain_segments(table, wpack, dims, acts, out, ids=None, base=0):
-    """`chain` on a ConcatTable read in place; returns False when the stack's shape has no segment-reading kernel."""
+def _chain_segments_args(table, wpack, dims, acts, out, ids=None, base=0):
     P = out.shape[0]
     segs = table.segments
     if ids is not None and ids.numel() != P:
@@ -810,24 +816,20 @@ def chain_segments(table, wpack, dims, acts, out, ids=None, base=0):
     ws = (ctypes.c_int32 * n)(*[int(t.shape[1]) for t in segs])
     dims_c = (ctypes.c_int32 * len(dims))(*dims)
     acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
-    code = load().amar_chain_segments_f32(ptrs, lds, ws, n, _ptr(ids, torch.int32, 'ids'), int(base),
-                                          _ptr(wpack, torch.float32, 'wpack'), dims_c, acts_c, len(acts),
-                                          _ptr(out, torch.float32, 'out'), _ld(out, 'out'), P, _stream())
+    return [ptrs, lds, ws, n, _ptr(ids, torch.int32, 'ids'), int(base), _ptr(wpack, torch.float32, 'wpack'), dims_c, acts_c, len(acts),
+            _ptr(out, torch.float32, 'out'), _ld(out, 'out'), P]
+
+
+def chain_segments(table, wpack, dims, acts, out, ids=None, base=0):
+    """`chain` on a ConcatTable read in place; returns False when the stack's shape has no segment-reading kernel."""
+    code = load().amar_chain_segments_f32(*_chain_segments_args(table, wpack, dims, acts, out, ids=ids, base=base), _stream())
     if code == -2:                                                   # AMAR_EUNSUPPORTED: no compile-time tower shape for this stack
         return False
     _check(code, 'amar_chain_segments_f32')
     return True
 
 
-def chain(A, wpack, dims, acts, out, ids_a=None, base_a=0, B=None, ids_b=None, base_b=0, sum_inputs=False, in_act=None, out_index=None):
-    """out = DenseStack([A[ids_a - base_a] || B[ids_b - base_b]]), or DenseStack(in_act(A[..] + B[..])) with
-    sum_inputs; see amar_chain_f32 in include/amar_hip.h.  out_index (int32 [P]): row p goes to out[out_index[p]]
-    (amar_chain_indexed_f32: a pair list kept in XCD-affine order, scores back in the caller's order).
-    A may be a ConcatTable (per-layer tables read in place: amar_chain_segments_f32)."""
-    if isinstance(A, ConcatTable):
-        if A.in_place and B is None and not sum_inputs and out_index is None and chain_segments(A, wpack, dims, acts, out, ids=ids_a, base=base_a):
-            return
-        A = A.materialize()
+def _chain_args(A, wpack, dims, acts, out, ids_a=None, base_a=0, B=None, ids_b=None, base_b=0, sum_inputs=False, in_act=None, out_index=None):
     P = out.shape[0]
     Da, Db = A.shape[1], (B.shape[1] if B is not None else 0)
     for ids, nm in ((ids_a, 'ids_a'), (ids_b, 'ids_b')):
@@ -839,13 +841,65 @@ def chain(A, wpack, dims, acts, out, ids_a=None, base_a=0, B=None, ids_b=None, b
     acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
     if out_index is not None and out_index.numel() != P:
         raise ValueError("chain: out_index must have one entry per output row")
-    code = load().amar_chain_indexed_f32(
-        _ptr(A, torch.float32, 'A'), _ld(A, 'A'), Da, _ptr(ids_a, torch.int32, 'ids_a'), int(base_a),
-        _ptr(B, torch.float32, 'B'), _ld(B, 'B') if B is not None else 0, Db, _ptr(ids_b, torch.int32, 'ids_b'), int(base_b),
-        1 if sum_inputs else 0, ACT_CODES[in_act],
-        _ptr(wpack, torch.float32, 'wpack'), dims_c, acts_c, len(acts),
-        _ptr(out, torch.float32, 'out'), _ld(out, 'out'), _ptr(out_index, torch.int32, 'out_index'), P, _stream())
-    _check(code, 'amar_chain_indexed_f32' if out_index is not None else 'amar_chain_f32')
+    return [_ptr(A, torch.float32, 'A'), _ld(A, 'A'), Da, _ptr(ids_a, torch.int32, 'ids_a'), int(base_a),
+            _ptr(B, torch.float32, 'B'), _ld(B, 'B') if B is not None else 0, Db, _ptr(ids_b, torch.int32, 'ids_b'), int(base_b),
+            1 if sum_inputs else 0, ACT_CODES[in_act],
+            _ptr(wpack, torch.float32, 'wpack'), dims_c, acts_c, len(acts),
+            _ptr(out, torch.float32, 'out'), _ld(out, 'out'), _ptr(out_index, torch.int32, 'out_index'), P]
+
+
+def chain(A, wpack, dims, acts, out, ids_a=None, base_a=0, B=None, ids_b=None, base_b=0, sum_inputs=False, in_act=None, out_index=None):
+    """out = DenseStack([A[ids_a - base_a] || B[ids_b - base_b]]), or DenseStack(in_act(A[..] + B[..])) with
+    sum_inputs; see amar_chain_f32 in include/amar_hip.h.  out_index (int32 [P]): row p goes to out[out_index[p]]
+    (amar_chain_indexed_f32: a pair list kept in XCD-affine order, scores back in the caller's order).
+    A may be a ConcatTable (per-layer tables read in place: amar_chain_segments_f32)."""
+    if isinstance(A, ConcatTable):
+        if A.in_place and B is None and not sum_inputs and out_index is None and chain_segments(A, wpack, dims, acts, out, ids=ids_a, base=base_a):
+            return
+        A = A.materialize()
+    args = _chain_args(A, wpack, dims, acts, out, ids_a=ids_a, base_a=base_a, B=B, ids_b=ids_b, base_b=base_b, sum_inputs=sum_inputs,
+                       in_act=in_act, out_index=out_index)
+    _check(load().amar_chain_indexed_f32(*args, _stream()), 'amar_chain_indexed_f32' if out_index is not None else 'amar_chain_f32')
+
+
+CHAIN_KERNEL_GENERIC, CHAIN_KERNEL_PIPE, CHAIN_KERNEL_ROWS = 0, 1, 2
+
+
+class ChainRouteInfo(ctypes.Structure):
+    """include/amar_hip.h: amar_chain_route_info"""
+    _fields_ = [(name, ctypes.c_int32) for name in ('kernel', 'maxt', 'full', 'am', 'split', 'scatter', 'shape', 'lastlin', 'seg', 'has_dot',
+                                                    'layers', 'threads')] + [('blocks', ctypes.c_int64), ('lds_bytes', ctypes.c_int64)]
+
+    def as_dict(self):
+        d = {name: int(getattr(self, name)) for name, _ in self._fields_}
+        for name in ('full', 'split', 'scatter', 'lastlin', 'seg', 'has_dot'):
+            d[name] = bool(d[name])
+        return d
+
+
+def chain_shape(*tiles):
+    """The `shape` of ChainRouteInfo for a tower whose widths dims[0..n] have these tile counts (n = len(tiles) - 1 layers)."""
+    code = len(tiles) - 1
+    for j, t in enumerate(tiles):
+        code |= t << (3 * (j + 1))
+    return code
+
+
+def chain_route(A, wpack, dims, acts, out, ids_a=None, base_a=0, B=None, ids_b=None, base_b=0, sum_inputs=False, in_act=None, out_index=None):
+    """What `chain` does with these operands (amar_chain_route / amar_chain_segments_route: host only, nothing is launched; the
+    launchers start from the same function).  A dict of the fields of amar_chain_route_info.  A ConcatTable is asked about in
+    place: a shape without a segment-reading kernel raises AmarError (`chain` then assembles the table and runs that)."""
+    info = ChainRouteInfo()
+    if isinstance(A, ConcatTable):
+        if not (A.in_place and B is None and not sum_inputs and out_index is None):
+            raise ValueError("chain_route: this ConcatTable call is assembled first; ask about the assembled table")
+        args = _chain_segments_args(A, wpack, dims, acts, out, ids=ids_a, base=base_a)
+        _check(load().amar_chain_segments_route(*args, ctypes.byref(info)), 'amar_chain_segments_route')
+        return info.as_dict()
+    args = _chain_args(A, wpack, dims, acts, out, ids_a=ids_a, base_a=base_a, B=B, ids_b=ids_b, base_b=base_b, sum_inputs=sum_inputs,
+                       in_act=in_act, out_index=out_index)
+    _check(load().amar_chain_route(*args, ctypes.byref(info)), 'amar_chain_route')
+    return info.as_dict()
 
 
 def dual_chain_supported(D, n_branch_dims_equal, trunk_dims):

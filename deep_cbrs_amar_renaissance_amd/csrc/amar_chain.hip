@@ -1085,6 +1085,7 @@ static int chain_run(const float *A, int64_t lda, int32_t Da, const int32_t *ids
                      const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers,
                      float *out, int64_t ldo, const int32_t *out_index, int64_t P, amar_stream_t stream,
                      int32_t n_seg, const float *const *seg, const int64_t *seg_ld, const int32_t *seg_width);
+static int chain_segments_check(const float *const *seg, const int64_t *seg_ld, const int32_t *seg_width, int32_t n_seg, int64_t *da);
 
 int amar_chain_indexed_f32(const float *A, int64_t lda, int32_t Da, const int32_t *ids_a, int32_t base_a,
                            const float *B, int64_t ldb, int32_t Db, const int32_t *ids_b, int32_t base_b,
@@ -1099,32 +1100,61 @@ int amar_chain_segments_f32(const float *const *seg, const int64_t *seg_ld, cons
                             const int32_t *ids, int32_t base,
                             const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers,
                             float *out, int64_t ldo, int64_t P, amar_stream_t stream) {
-    if (!seg || !seg_ld || !seg_width || n_seg < 1 || n_seg > CHAIN_MAX_SEG) return AMAR_EINVAL;
     int64_t da = 0;
-    for (int j = 0; j < n_seg; ++j) {
-        if (!seg[j] || seg_width[j] < 4 || (seg_width[j] & 3) || seg_ld[j] < seg_width[j] || (seg_ld[j] & 3) || !amar_aligned16(seg[j]) ||
-            seg_ld[j] >= (1ll << 30))
-            return AMAR_EINVAL;
-        da += seg_width[j];
-    }
-    if (da > 128) return AMAR_EUNSUPPORTED;
+    if (const int rc = chain_segments_check(seg, seg_ld, seg_width, n_seg, &da)) return rc;
     return chain_run(seg[0], seg_ld[0], (int32_t)da, ids, base, nullptr, 0, 0, nullptr, 0, 0, AMAR_ACT_NONE, wpack, dims, acts, n_layers, out, ldo,
                      nullptr, P, stream, n_seg, seg, seg_ld, seg_width);
 }
 
-static int chain_run(const float *A, int64_t lda, int32_t Da, const int32_t *ids_a, int32_t base_a,
-                     const float *B, int64_t ldb, int32_t Db, const int32_t *ids_b, int32_t base_b,
-                     int32_t sum_inputs, int32_t in_act,
-                     const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers,
-                     float *out, int64_t ldo, const int32_t *out_index, int64_t P, amar_stream_t stream,
-                     int32_t n_seg, const float *const *seg, const int64_t *seg_ld, const int32_t *seg_width) {
+// The compile-time tower shapes of chain_rows_kernel: ONE list for the route query and for the launcher.
+#define AMAR_ROWS_SHAPES(X)                                                                                                          \
+    X(3, 2, 2, 2, 3)      /* 24 -> 24 -> 24 -> 48: basic-gnn grid1's towers with the classifier's first layer folded in */           \
+    X(3, 3, 3, 3, 4)      /* 48 -> 48 -> 48 -> 64: grid2 */                                                                          \
+    X(2, 2, 2, 2, 0)      /* 24 -> 24 -> 24: the graph towers of the hybrid head */                                                  \
+    X(3, 1, 2, 2, 3)      /*  8 -> 24 -> 24 -> 48: grid1's towers after a 'mean' / 'sum' / 'w-sum' reduction (LightGCN, DGCF) */     \
+    X(3, 1, 3, 3, 4)      /* 16 -> 48 -> 48 -> 64: grid2's */                                                                        \
+    X(2, 3, 3, 3, 0)      /* 48 -> 48 -> 48 */
+
+static bool chain_rows_shape_known(int shape) {
+    switch (shape) {
+#define AMAR_ROWS_KNOWN(NLL, A0, A1, A2, A3) case chain_shape(NLL, A0, A1, A2, A3):
+    AMAR_ROWS_SHAPES(AMAR_ROWS_KNOWN)
+#undef AMAR_ROWS_KNOWN
+        return true;
+    default: return false;
+    }
+}
+
+// The argument checks of amar_chain_segments_f32 / amar_chain_segments_route; *da = the summed width.
+static int chain_segments_check(const float *const *seg, const int64_t *seg_ld, const int32_t *seg_width, int32_t n_seg, int64_t *da) {
+    if (!seg || !seg_ld || !seg_width || n_seg < 1 || n_seg > CHAIN_MAX_SEG) return AMAR_EINVAL;
+    *da = 0;
+    for (int j = 0; j < n_seg; ++j) {
+        if (!seg[j] || seg_width[j] < 4 || (seg_width[j] & 3) || seg_ld[j] < seg_width[j] || (seg_ld[j] & 3) || !amar_aligned16(seg[j]) ||
+            seg_ld[j] >= (1ll << 30))
+            return AMAR_EINVAL;
+        *da += seg_width[j];
+    }
+    return *da > 128 ? AMAR_EUNSUPPORTED : AMAR_OK;
+}
+
+// Every decision of a chain call, on the host: the argument checks, the kernel's arguments (`a`) and which kernel runs how (`r`).
+// chain_run launches from `r`, amar_chain_route / amar_chain_segments_route return it: the two cannot disagree.  No HIP call.
+static int chain_route(const float *A, int64_t lda, int32_t Da, const int32_t *ids_a, int32_t base_a,
+                       const float *B, int64_t ldb, int32_t Db, const int32_t *ids_b, int32_t base_b,
+                       int32_t sum_inputs, int32_t in_act,
+                       const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers,
+                       float *out, int64_t ldo, const int32_t *out_index, int64_t P,
+                       int32_t n_seg, const float *const *seg, const int64_t *seg_ld, const int32_t *seg_width,
+                       ChainArgs &a, amar_chain_route_info &r) {
     if (P < 0 || !A || !wpack || !dims || !acts || !out || Da < 4 || Db < 0) return AMAR_EINVAL;
     if (sum_inputs && (Db != Da || !B)) return AMAR_EINVAL;
     if (in_act != AMAR_ACT_NONE && in_act != AMAR_ACT_RELU && in_act != AMAR_ACT_SIGMOID) return AMAR_EINVAL;
     if ((Da & 3) || (Db & 3) || (lda & 3) || (n_seg == 0 && lda < Da) || !amar_aligned16(A) || !amar_aligned16(wpack)) return AMAR_EINVAL;
     if (Db && (!B || (ldb & 3) || ldb < Db || !amar_aligned16(B))) return AMAR_EINVAL;
     if (n_layers < 1 || n_layers > CHAIN_MAX_LAYERS || dims[0] != (sum_inputs ? Da : Da + Db)) return AMAR_EINVAL;
-    ChainArgs a{};
+    a = ChainArgs{};
+    r = amar_chain_route_info{};
     a.A = A; a.lda = lda; a.Da = Da; a.ids_a = ids_a; a.base_a = base_a;
     a.B = B; a.ldb = ldb; a.Db = Db; a.ids_b = ids_b; a.base_b = base_b;
     a.wpack = wpack; a.out = out; a.ldo = ldo; a.P = P; a.sum_inputs = sum_inputs ? 1 : 0; a.in_act = in_act;
@@ -1160,9 +1190,7 @@ static int chain_run(const float *A, int64_t lda, int32_t Da, const int32_t *ids
     if (!a.has_dot && ((ldo & 3) || ldo < a.n_out || (a.n_out & 3) || !amar_aligned16(out))) return AMAR_EINVAL;
     if (a.has_dot && ldo < 1) return AMAR_EINVAL;
     if (maxw > 128 || (size_t)off * sizeof(float) > 150 * 1024) return AMAR_EUNSUPPORTED;
-    if (P == 0) return AMAR_OK;
     const size_t lds_bytes = (size_t)off * sizeof(float);
-    hipStream_t st = static_cast<hipStream_t>(stream);
     // tile budget: MAXT = widest layer / 16 rounded up to {3, 4, 8}; two pair tiles per wave (register budget ~ MAXT * 2: measured
     // best on grid1/grid2/grid6 shapes against one and four, tools/exp_chain.py)
     const int maxt = maxw <= 48 ? 3 : (maxw <= 64 ? 4 : 8);
@@ -1174,81 +1202,129 @@ static int chain_run(const float *A, int64_t lda, int32_t Da, const int32_t *ids
         relu_but_last = relu_but_last && a.act[l] == (l == a.n_layers - 1 ? AMAR_ACT_NONE : AMAR_ACT_RELU);
     }
     const int am = relu ? 1 : (relu_but_last ? 2 : 0);
-#define AMAR_CHAIN_LAUNCH(MT)                                                                                           \
-    do {                                                                                                                \
-        int64_t blocks = (P + 4 * 16 * 2 - 1) / (4 * 16 * 2);                                                           \
-        if (blocks > 4096) blocks = 4096;                                                                               \
-        auto kern = full ? (am == 1 ? chain_kernel<MT, 2, true, 1> : am == 2 ? chain_kernel<MT, 2, true, 2>             \
-                                                                             : chain_kernel<MT, 2, true, 0>)            \
-                         : (am == 1 ? chain_kernel<MT, 2, false, 1> : am == 2 ? chain_kernel<MT, 2, false, 2>           \
-                                                                              : chain_kernel<MT, 2, false, 0>);         \
-        if (lds_bytes > 64 * 1024 &&                                                                                    \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                (int)lds_bytes) != hipSuccess)                                                          \
-            return AMAR_ELAUNCH;                                                                                        \
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds_bytes, st, a);                                  \
-    } while (0)
-    // pair stage (ReLU of the sum of two gathered rows, square ReLU layers): the pipelined kernel
+    r.maxt = maxt; r.full = full; r.am = am; r.has_dot = a.has_dot; r.layers = a.n_layers; r.threads = 256;
+    r.lds_bytes = (int64_t)lds_bytes;
+    const int64_t tiles = (P + 4 * 16 * 2 - 1) / (4 * 16 * 2);       // 4 waves of two 16-row tiles per workgroup
+    // pair stage (ReLU of the sum of two gathered rows, square ReLU layers): the pipelined kernel.  Its vector-output form has no
+    // scattered store, so a call with out_index and no trailing 1-unit layer runs the generic kernel.
     const bool a_dot_ok = !a.has_dot || a.dot_kt == maxt;
     const bool small_tables = lda < (1ll << 30) && ldb < (1ll << 30) && P < (1ll << 30) - (4ll << 20);   // 32-bit row bytes and positions (+ 3 strides of <= 8 192 workgroups)
     if (relu && a.sum_inputs && a.in_act == AMAR_ACT_RELU && full && a_dot_ok && a.ids_a && a.ids_b && a.Da == 16 * maxt &&
-        a.Db == a.Da && maxt <= 4 && lds_bytes <= 64 * 1024 && small_tables) {
-        int64_t blocks = (P + 4 * 16 * 2 - 1) / (4 * 16 * 2);
-        // 1 536 = 256 CUs x 3 resident workgroups x 2: whole rounds of workgroups, no tail (ml1m(s=64): 0.639 ms against 0.647 at 4 096,
-        // 0.658 at 8 192; a multiple of 8: PairPlan's XCD affinity)
-        if (blocks > 1536) blocks = 1536;
-        const dim3 grid((unsigned)blocks), block(256);
-        if (a.out_index && !a.has_dot) return AMAR_EUNSUPPORTED;
+        a.Db == a.Da && maxt <= 4 && lds_bytes <= 64 * 1024 && small_tables && (a.has_dot || !a.out_index)) {
         // products on the bf16 matrix instruction with three-way split operands (see the kernel's header); AMAR_PAIR_MFMA=f32: the f32 one
         static const bool f32_only = getenv("AMAR_PAIR_MFMA") && !strcmp(getenv("AMAR_PAIR_MFMA"), "f32");
         const size_t split_bytes = (((size_t)off + 3) & ~(size_t)3) * sizeof(float) + (size_t)a.n_layers * maxt * ((maxt + 1) / 2) * 3 * 1024;
-        const bool split = !f32_only && split_bytes <= 64 * 1024;
-        const size_t lds = split ? split_bytes : lds_bytes;
-#define AMAR_PIPE_LAUNCH(MT, SC)                                                                                          \
-        do {                                                                                                              \
-            if (split) hipLaunchKernelGGL((chain_pipe_kernel<MT, 2, SC, true>), grid, block, lds, st, a);                 \
-            else hipLaunchKernelGGL((chain_pipe_kernel<MT, 2, SC, false>), grid, block, lds, st, a);                      \
-        } while (0)
-        if (a.out_index) {
-            if (maxt == 3) AMAR_PIPE_LAUNCH(3, true); else AMAR_PIPE_LAUNCH(4, true);
-        } else {
-            if (maxt == 3) AMAR_PIPE_LAUNCH(3, false); else AMAR_PIPE_LAUNCH(4, false);
-        }
-#undef AMAR_PIPE_LAUNCH
-        return amar_check_launch();
+        r.kernel = AMAR_CHAIN_KERNEL_PIPE;
+        r.split = !f32_only && split_bytes <= 64 * 1024;
+        r.scatter = a.out_index != nullptr;
+        // 1 536 = 256 CUs x 3 resident workgroups x 2: whole rounds of workgroups, no tail (ml1m(s=64): 0.639 ms against 0.647 at 4 096,
+        // 0.658 at 8 192; a multiple of 8: PairPlan's XCD affinity)
+        r.blocks = tiles > 1536 ? 1536 : tiles;
+        if (r.split) r.lds_bytes = (int64_t)split_bytes;
+        return AMAR_OK;
     }
     // entity towers (one table, no dot, ReLU with an optionally linear last layer) in a shape with a compile-time kernel
     if ((am == 1 || am == 2) && !a.sum_inputs && a.Db == 0 && !a.has_dot && !a.out_index && a.n_layers <= 3 &&
         maxt <= 4 && lds_bytes <= 64 * 1024 && lda < (1ll << 30) && P < (1ll << 30) - (4ll << 20)) {
         const int shape = chain_shape(a.n_layers, a.kt[0], a.nt[0], a.n_layers > 1 ? a.nt[1] : 0, a.n_layers > 2 ? a.nt[2] : 0);
-        // 1 024 workgroups = 4 per CU, every wave a few iterations deep in its prefetch (ml1m(s=64) towers: 0.059 ms against 0.063 at
-        // 4 096 and 0.068 for the generic kernel)
-        int64_t blocks = (P + 4 * 16 * 2 - 1) / (4 * 16 * 2);
-        if (blocks > 1024) blocks = 1024;
-        const dim3 grid((unsigned)blocks), block(256);
-        bool done = true;
+        if (chain_rows_shape_known(shape)) {
+            // 1 024 workgroups = 4 per CU, every wave a few iterations deep in its prefetch (ml1m(s=64) towers: 0.059 ms against 0.063 at
+            // 4 096 and 0.068 for the generic kernel)
+            r.kernel = AMAR_CHAIN_KERNEL_ROWS;
+            r.shape = shape; r.lastlin = am == 2; r.seg = n_seg > 0;
+            r.blocks = tiles > 1024 ? 1024 : tiles;
+            return AMAR_OK;
+        }
+    }
+    // segments are read by the compile-time tower shapes only: the caller concatenates for the others (an empty batch launches nothing
+    // and is not refused)
+    if (n_seg > 0 && P > 0) return AMAR_EUNSUPPORTED;
+    r.kernel = AMAR_CHAIN_KERNEL_GENERIC;
+    r.blocks = tiles > 4096 ? 4096 : tiles;
+    return AMAR_OK;
+}
+
+int amar_chain_route(const float *A, int64_t lda, int32_t Da, const int32_t *ids_a, int32_t base_a,
+                     const float *B, int64_t ldb, int32_t Db, const int32_t *ids_b, int32_t base_b,
+                     int32_t sum_inputs, int32_t in_act,
+                     const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers,
+                     float *out, int64_t ldo, const int32_t *out_index, int64_t P, amar_chain_route_info *info) {
+    if (!info) return AMAR_EINVAL;
+    ChainArgs a;
+    return chain_route(A, lda, Da, ids_a, base_a, B, ldb, Db, ids_b, base_b, sum_inputs, in_act, wpack, dims, acts, n_layers, out, ldo, out_index, P,
+                       0, nullptr, nullptr, nullptr, a, *info);
+}
+
+int amar_chain_segments_route(const float *const *seg, const int64_t *seg_ld, const int32_t *seg_width, int32_t n_seg,
+                              const int32_t *ids, int32_t base,
+                              const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers,
+                              float *out, int64_t ldo, int64_t P, amar_chain_route_info *info) {
+    if (!info) return AMAR_EINVAL;
+    int64_t da = 0;
+    if (const int rc = chain_segments_check(seg, seg_ld, seg_width, n_seg, &da)) return rc;
+    ChainArgs a;
+    return chain_route(seg[0], seg_ld[0], (int32_t)da, ids, base, nullptr, 0, 0, nullptr, 0, 0, AMAR_ACT_NONE, wpack, dims, acts, n_layers, out, ldo,
+                       nullptr, P, n_seg, seg, seg_ld, seg_width, a, *info);
+}
+
+static int chain_run(const float *A, int64_t lda, int32_t Da, const int32_t *ids_a, int32_t base_a,
+                     const float *B, int64_t ldb, int32_t Db, const int32_t *ids_b, int32_t base_b,
+                     int32_t sum_inputs, int32_t in_act,
+                     const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers,
+                     float *out, int64_t ldo, const int32_t *out_index, int64_t P, amar_stream_t stream,
+                     int32_t n_seg, const float *const *seg, const int64_t *seg_ld, const int32_t *seg_width) {
+    ChainArgs a;
+    amar_chain_route_info r;
+    if (const int rc = chain_route(A, lda, Da, ids_a, base_a, B, ldb, Db, ids_b, base_b, sum_inputs, in_act, wpack, dims, acts, n_layers, out, ldo,
+                                   out_index, P, n_seg, seg, seg_ld, seg_width, a, r))
+        return rc;
+    if (r.blocks == 0) return AMAR_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)r.blocks), block((unsigned)r.threads);
+    const size_t lds = (size_t)r.lds_bytes;
+    if (r.kernel == AMAR_CHAIN_KERNEL_PIPE) {
+#define AMAR_PIPE_LAUNCH(MT, SC)                                                                                          \
+        do {                                                                                                              \
+            if (r.split) hipLaunchKernelGGL((chain_pipe_kernel<MT, 2, SC, true>), grid, block, lds, st, a);               \
+            else hipLaunchKernelGGL((chain_pipe_kernel<MT, 2, SC, false>), grid, block, lds, st, a);                      \
+        } while (0)
+        if (r.scatter) {
+            if (r.maxt == 3) AMAR_PIPE_LAUNCH(3, true); else AMAR_PIPE_LAUNCH(4, true);
+        } else {
+            if (r.maxt == 3) AMAR_PIPE_LAUNCH(3, false); else AMAR_PIPE_LAUNCH(4, false);
+        }
+#undef AMAR_PIPE_LAUNCH
+        return amar_check_launch();
+    }
+    if (r.kernel == AMAR_CHAIN_KERNEL_ROWS) {
 #define AMAR_ROWS_CASE(NLL, A0, A1, A2, A3)                                                                                      \
         case chain_shape(NLL, A0, A1, A2, A3):                                                                                   \
-            if (n_seg > 0) {                                                                                                     \
-                if (am == 2) hipLaunchKernelGGL((chain_rows_kernel<chain_shape(NLL, A0, A1, A2, A3), 2, true, true>), grid, block, lds_bytes, st, a);   \
-                else hipLaunchKernelGGL((chain_rows_kernel<chain_shape(NLL, A0, A1, A2, A3), 2, false, true>), grid, block, lds_bytes, st, a);          \
-            } else if (am == 2) hipLaunchKernelGGL((chain_rows_kernel<chain_shape(NLL, A0, A1, A2, A3), 2, true, false>), grid, block, lds_bytes, st, a);   \
-            else hipLaunchKernelGGL((chain_rows_kernel<chain_shape(NLL, A0, A1, A2, A3), 2, false, false>), grid, block, lds_bytes, st, a);          \
-            break
-        switch (shape) {
-        AMAR_ROWS_CASE(3, 2, 2, 2, 3);      // 24 -> 24 -> 24 -> 48: basic-gnn grid1's towers with the classifier's first layer folded in
-        AMAR_ROWS_CASE(3, 3, 3, 3, 4);      // 48 -> 48 -> 48 -> 64: grid2
-        AMAR_ROWS_CASE(2, 2, 2, 2, 0);      // 24 -> 24 -> 24: the graph towers of the hybrid head
-        AMAR_ROWS_CASE(3, 1, 2, 2, 3);      //  8 -> 24 -> 24 -> 48: grid1's towers after a 'mean' / 'sum' / 'w-sum' reduction (LightGCN, DGCF)
-        AMAR_ROWS_CASE(3, 1, 3, 3, 4);      // 16 -> 48 -> 48 -> 64: grid2's
-        AMAR_ROWS_CASE(2, 3, 3, 3, 0);      // 48 -> 48 -> 48
-        default: done = false;
+            if (r.seg) {                                                                                                         \
+                if (r.lastlin) hipLaunchKernelGGL((chain_rows_kernel<chain_shape(NLL, A0, A1, A2, A3), 2, true, true>), grid, block, lds, st, a);   \
+                else hipLaunchKernelGGL((chain_rows_kernel<chain_shape(NLL, A0, A1, A2, A3), 2, false, true>), grid, block, lds, st, a);            \
+            } else if (r.lastlin) hipLaunchKernelGGL((chain_rows_kernel<chain_shape(NLL, A0, A1, A2, A3), 2, true, false>), grid, block, lds, st, a);   \
+            else hipLaunchKernelGGL((chain_rows_kernel<chain_shape(NLL, A0, A1, A2, A3), 2, false, false>), grid, block, lds, st, a);            \
+            break;
+        switch (r.shape) {
+        AMAR_ROWS_SHAPES(AMAR_ROWS_CASE)
+        default: return AMAR_EUNSUPPORTED;                          // (not reached: chain_route knows the same list)
         }
 #undef AMAR_ROWS_CASE
-        if (done) return amar_check_launch();
+        return amar_check_launch();
     }
-    if (n_seg > 0) return AMAR_EUNSUPPORTED;       // segments are read by the compile-time tower shapes only: the caller concatenates for the others
-    if (maxt == 3) AMAR_CHAIN_LAUNCH(3); else if (maxt == 4) AMAR_CHAIN_LAUNCH(4); else AMAR_CHAIN_LAUNCH(8);
+#define AMAR_CHAIN_LAUNCH(MT)                                                                                           \
+    do {                                                                                                                \
+        auto kern = r.full ? (r.am == 1 ? chain_kernel<MT, 2, true, 1> : r.am == 2 ? chain_kernel<MT, 2, true, 2>       \
+                                                                                 : chain_kernel<MT, 2, true, 0>)        \
+                           : (r.am == 1 ? chain_kernel<MT, 2, false, 1> : r.am == 2 ? chain_kernel<MT, 2, false, 2>     \
+                                                                                  : chain_kernel<MT, 2, false, 0>);     \
+        if (lds > 64 * 1024 &&                                                                                          \
+            hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,       \
+                                (int)lds) != hipSuccess)                                                                \
+            return AMAR_ELAUNCH;                                                                                        \
+        hipLaunchKernelGGL(kern, grid, block, lds, st, a);                                                              \
+    } while (0)
+    if (r.maxt == 3) AMAR_CHAIN_LAUNCH(3); else if (r.maxt == 4) AMAR_CHAIN_LAUNCH(4); else AMAR_CHAIN_LAUNCH(8);
 #undef AMAR_CHAIN_LAUNCH
     return amar_check_launch();
 }

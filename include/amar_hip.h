@@ -320,10 +320,13 @@ int amar_dense_split_f32(const float *X, int64_t ldx, const int32_t *ids, const 
  * row-major [dims[l], dims[l+1]] Keras kernel, biases[l] its bias; the blob is then copied to
  * the device by the caller.
  * Arithmetic: f32 values and f32 sums throughout.  The pair-stage form (sum_inputs with both id lists, ReLU, equal
- * layer widths of 48 or 64, a trailing 1-unit layer) and amar_dual_chain_f32's 64-wide form take their PRODUCTS on
+ * layer widths of 48 or 64, with or without a trailing 1-unit layer) and amar_dual_chain_f32's 64-wide form take their PRODUCTS on
  * the bf16 matrix instruction with both operands split into three bf16 parts (x = hi + mid + lo exactly; six part
  * products accumulated in f32): a term x.w is off by at most 3 * 2^-24 |x.w| — as close to a float64 evaluation as the
  * f32 instruction, not bit-identical to it.  Environment AMAR_PAIR_MFMA=f32 keeps v_mfma_f32_16x16x4_f32 everywhere.
+ * The pair-stage form does NOT need the trailing 1-unit layer: a [P, 48] or [P, 64] block out of square ReLU layers runs it too.
+ * It also keeps the f32 instruction, without being asked, when the packed weights plus their bf16 fragments (3 KB per pair of
+ * 16 x 16 tiles) exceed 64 KB of LDS: two or more square layers at 64, three or more at 48 (amar_chain_route reports `split`).
  */
 int64_t amar_chain_pack_floats(const int32_t *dims, int32_t n_layers);
 int amar_chain_pack_f32(const float *const *kernels, const float *const *biases, const int32_t *dims,
@@ -340,6 +343,9 @@ int amar_chain_f32(const float *A, int64_t lda, int32_t Da, const int32_t *ids_a
  * bucketed ONCE per dataset by item range so that the workgroups of one XCD (pairs p with (p >> 7) % 8 equal, under
  * round-robin dispatch) gather item-tower rows of one eighth of the items and find them in that XCD's L2: the list is
  * constant across steps and epochs, the scores still land in the Sequence's order.
+ * Every shape amar_chain_f32 takes is taken with an index too, except the segment form.  The pair-stage kernel scatters scores
+ * only: a pair-stage-shaped call with out_index and NO trailing 1-unit layer (a [P, N] block) runs the generic kernel, and its
+ * rows are, bit for bit, those of the same call without out_index, scattered.
  */
 int amar_chain_indexed_f32(const float *A, int64_t lda, int32_t Da, const int32_t *ids_a, int32_t base_a,
                            const float *B, int64_t ldb, int32_t Db, const int32_t *ids_b, int32_t base_b,
@@ -360,6 +366,47 @@ int amar_chain_segments_f32(const float *const *seg, const int64_t *seg_ld, cons
                             const int32_t *ids, int32_t base,
                             const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers,
                             float *out, int64_t ldo, int64_t P, amar_stream_t stream);
+
+/* What an amar_chain_indexed_f32 / amar_chain_segments_f32 call with these arguments does (host only: nothing is launched, the device
+ * pointers are looked at for NULL and alignment, dims and acts are read).  The launchers start from the same function, so the two
+ * cannot disagree.  Returns what the launcher's argument checks return (AMAR_OK, AMAR_EINVAL, AMAR_EUNSUPPORTED; info == NULL:
+ * AMAR_EINVAL); `info` is meaningful after AMAR_OK only.
+ *   kernel     AMAR_CHAIN_KERNEL_GENERIC  chain_kernel<maxt, 2, full, am>: any shape
+ *              AMAR_CHAIN_KERNEL_PIPE     chain_pipe_kernel<maxt, 2, scatter, split>: the pair stage — sum_inputs with in_act = relu, both
+ *                                         id lists, every width (Da, every layer) 16 maxt with maxt <= 4, ReLU layers, a trailing
+ *                                         1-unit layer or none (none: without out_index only), lda / ldb < 2^30, P < 2^30 - 2^22
+ *              AMAR_CHAIN_KERNEL_ROWS     chain_rows_kernel<shape, 2, lastlin, seg>: one table (Db = 0), no 1-unit layer, no
+ *                                         out_index, two or three ReLU layers with an optionally linear last one, in one of six shapes
+ *   maxt       tiles of 16 the widest width needs, rounded up to 3, 4 or 8 (widths <= 48, <= 64, <= 128)
+ *   full       every width (dims[0], every layer, the 1-unit layer's input) has exactly maxt tiles
+ *   am         1: ReLU on every layer (and on the summed input, with sum_inputs); 2: the same with a linear LAST layer and no 1-unit
+ *              layer; 0: anything else (activations are run-time values).  The 1-unit layer's activation never counts.
+ *   split      (pipe) products on the bf16 instruction with split operands: packed floats (rounded up to 4) * 4 +
+ *              layers * maxt * ceil(maxt / 2) * 3 072 bytes <= 65 536 and AMAR_PAIR_MFMA != f32 (read once per process)
+ *   scatter    (pipe) out_index given
+ *   shape      (rows) layers | tiles(dims[0]) << 3 | tiles(dims[1]) << 6 | tiles(dims[2]) << 9 | tiles(dims[3]) << 12; the six:
+ *              24-24-24-48, 48-48-48-64, 24-24-24, 8-24-24-48, 16-48-48-64, 48-48-48 (any widths with the same tile counts); else 0
+ *   lastlin    (rows) am == 2;  seg: (rows) called through amar_chain_segments_*
+ *   has_dot    the stack ends in a 1-unit layer evaluated as a dot product;  layers: the layers before it
+ *   blocks     workgroups launched: ceil(P / 128), at most 4 096 (generic), 1 536 (pipe), 1 024 (rows); 0: no launch
+ *   threads    256
+ *   lds_bytes  dynamic LDS asked for: amar_chain_pack_floats * 4, plus the fragments (see split) for the split pair stage */
+#define AMAR_CHAIN_KERNEL_GENERIC 0
+#define AMAR_CHAIN_KERNEL_PIPE 1
+#define AMAR_CHAIN_KERNEL_ROWS 2
+typedef struct amar_chain_route_info {
+    int32_t kernel, maxt, full, am, split, scatter, shape, lastlin, seg, has_dot, layers, threads;
+    int64_t blocks, lds_bytes;
+} amar_chain_route_info;
+int amar_chain_route(const float *A, int64_t lda, int32_t Da, const int32_t *ids_a, int32_t base_a,
+                     const float *B, int64_t ldb, int32_t Db, const int32_t *ids_b, int32_t base_b,
+                     int32_t sum_inputs, int32_t in_act,
+                     const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers,
+                     float *out, int64_t ldo, const int32_t *out_index, int64_t P, amar_chain_route_info *info);
+int amar_chain_segments_route(const float *const *seg, const int64_t *seg_ld, const int32_t *seg_width, int32_t n_seg,
+                              const int32_t *ids, int32_t base,
+                              const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers,
+                              float *out, int64_t ldo, int64_t P, amar_chain_route_info *info);
 
 /* Fused two-branch scorer for the hybrid head (src/models/hybrid.py:72-89) once the first Dense layers of
  * dense3a / dense3b have been folded into the per-entity tables:
