@@ -116,6 +116,8 @@ SIGNATURES = {
     'amar_grad_clip_f32': (ctypes.c_int, [_I32, _F32, _P, _I32, _I64, _P, _P, _F32, _P, _P]),
     'amar_bpr_grad_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P]),
     'amar_bpr_sample_i32': (ctypes.c_int, [_P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _I32, _I32, _P, _P, _P, _P]),
+    'amar_loss_counters': (ctypes.c_int32, []),
+    'amar_loss_grad_f32': (ctypes.c_int, [_I32, _P, _P, _I64, _P, _P, _P, _I64, _P, _P]),
     'amar_dropout_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I32, ctypes.c_uint64, _P, _U32, _U32, _F32, _P]),
     'amar_dropout_advance': (ctypes.c_int, [_P, _P]),
     'amar_gat_layer_dropout_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32,
@@ -1592,6 +1594,41 @@ def bpr_grad(p, dz, loss_terms):
     code = load().amar_bpr_grad_f32(_ptr(p, torch.float32, 'p'), _ld(p, 'p') if p.dim() == 2 else 1, _ptr(dz, torch.float32, 'dz'),
                                     _ptr(loss_terms, torch.float32, 'loss_terms'), B, _stream())
     _check(code, 'amar_bpr_grad_f32')
+
+
+# include/amar_hip.h: AMAR_LOSS_*
+LOSS_BCE, LOSS_MSE, LOSS_MAE, LOSS_HINGE, LOSS_SQUARED_HINGE, LOSS_HUBER, LOSS_LOG_COSH, LOSS_POISSON, LOSS_FOCAL = range(9)
+LOSS_HYPER_FLOATS = 4
+AUC_BUCKETS = 199
+LOSS_COUNTERS = 4 + 2 * AUC_BUCKETS
+
+
+def loss_counters():
+    """Size of the metric counter block of `loss_grad` (int64 cells), as the library states it."""
+    return int(load().amar_loss_counters())
+
+
+def loss_grad(loss, hyper, p, y, dz, loss_terms, counters=None):
+    """Per-pair terms and d(mean loss)/d(logit) of Keras loss `loss` (a LOSS_* code; hyper: LOSS_HYPER_FLOATS floats or None) for the
+    probability column p ([B] or [B, 1]) and labels y [B]; dz [B, 1] / loss_terms [B] contiguous.  counters: None, or the int64 block
+    of LOSS_COUNTERS cells on the device that this batch is added to (tp, fp, tn, fn, then the 2 x 199 AUC histogram)."""
+    B = p.shape[0]
+    if p.dim() not in (1, 2) or (p.dim() == 2 and p.shape[1] != 1) or (p.dim() == 1 and B > 1 and p.stride(0) != 1):
+        raise ValueError("loss_grad: p must be [B] contiguous or a [B, 1] column")
+    if y.numel() != B or dz.numel() != B or loss_terms.numel() != B or not y.is_contiguous() or not dz.is_contiguous() \
+            or not loss_terms.is_contiguous():
+        raise ValueError("loss_grad: y, dz and loss_terms of B contiguous floats expected")
+    if counters is not None and (counters.dtype != torch.int64 or counters.numel() != LOSS_COUNTERS or not counters.is_contiguous()):
+        raise ValueError("loss_grad: counters must be {} contiguous int64 cells".format(LOSS_COUNTERS))
+    hp = None
+    if hyper is not None:
+        if len(hyper) != LOSS_HYPER_FLOATS:
+            raise ValueError("loss_grad: hyper must hold {} floats".format(LOSS_HYPER_FLOATS))
+        hp = (ctypes.c_float * LOSS_HYPER_FLOATS)(*[float(v) for v in hyper])
+    code = load().amar_loss_grad_f32(int(loss), hp, _ptr(p, torch.float32, 'p'), _ld(p, 'p') if p.dim() == 2 else 1,
+                                     _ptr(y, torch.float32, 'y'), _ptr(dz, torch.float32, 'dz'),
+                                     _ptr(loss_terms, torch.float32, 'loss_terms'), B, _ptr(counters, torch.int64, 'counters'), _stream())
+    _check(code, 'amar_loss_grad_f32')
 
 
 def bpr_sample(pos_ptr, pos_ids, neg_ptr, neg_ids, n_users, seed, step, u, items, y=None, advance=True):

@@ -213,7 +213,14 @@ class Model(Layer):
     """Keras ``Model`` protocol used by the reference driver (experiment.py:155-198)."""
 
     def compile(self, loss=None, optimizer=None, metrics=None):
-        self.loss, self.optimizer, self.metrics = loss, optimizer, list(metrics or [])
+        """Keras' compile().  The loss (a name, a class name, a mapping {name: ..., <hyper-parameters>}, a BPRLoss, None = binary
+        cross-entropy) and the metrics (accuracy, Precision, Recall, AUC) are resolved here, so a name without a kernel raises now
+        (NotImplementedError where Keras knows it, ValueError otherwise) instead of training something else; fit() and evaluate()
+        resolve them again where they read them."""
+        from deep_cbrs_amar_renaissance_amd.utilities.metrics import resolve_compiled
+        metrics = list(metrics or [])
+        resolve_compiled(loss, metrics)
+        self.loss, self.optimizer, self.metrics = loss, optimizer, metrics
 
     def summary(self, print_fn=print, expand_nested=False):
         print_fn('Model: "{}"'.format(type(self).__name__))
@@ -379,15 +386,20 @@ class Model(Layer):
                 prm.copy_(torch.from_numpy(np.ascontiguousarray(value, dtype=np.float32)).to(prm.device))
 
     def evaluate(self, sequence, **kwargs):
-        """Loss and accuracy on `sequence` (experiment.py:194).  As Keras' evaluate(), 'loss' is the compiled loss (binary cross-entropy,
-        or BPRLoss per batch) plus
+        """Loss and metrics on `sequence` (experiment.py:194): [loss, accuracy] when no metric or only accuracy is compiled, else
+        [loss, m1, m2, ...] in compile order.  As Keras' evaluate(), 'loss' is the compiled loss (utilities/losses.py: a pointwise
+        loss over all pairs, or BPRLoss per batch) plus
         the regularisation losses of the model (l2 * sum(w^2) for every weight carrying a regulariser: gnn.py:45,293-294),
-        the same sum fit() reports per epoch, so train and test losses of one run are comparable."""
-        pred = self.predict(sequence).reshape(-1).astype(np.float64)
+        the same sum fit() reports per epoch, so train and test losses of one run are comparable.  The metrics are those of the
+        training counters, restated on the host (utilities/metrics.py: metric_counters, metric_values)."""
+        from deep_cbrs_amar_renaissance_amd.utilities.losses import BCE, BPR, BPRLoss, loss_terms
+        from deep_cbrs_amar_renaissance_amd.utilities.metrics import metric_counters, metric_values, resolve_compiled
+        code, hyper, names = resolve_compiled(getattr(self, 'loss', None), getattr(self, 'metrics', None))
+        pred32 = self.predict(sequence).reshape(-1)
+        pred = pred32.astype(np.float64)
         labels = [np.asarray(sequence[b][1]).reshape(-1) for b in range(len(sequence))]
         y = np.concatenate(labels).astype(np.float64) if labels else np.zeros(0)
-        from deep_cbrs_amar_renaissance_amd.utilities.losses import BPRLoss, loss_kind
-        if loss_kind(getattr(self, 'loss', None)) == 'bpr':
+        if code == BPR:
             # BPRLoss (utilities/losses.py) on each batch's own two halves, averaged over the batches weighted by their size (Keras'
             # Mean loss tracker)
             bpr, total, lo = BPRLoss(), 0.0, 0
@@ -395,13 +407,18 @@ class Model(Layer):
                 total += bpr(None, pred[lo:lo + len(lab)]) * len(lab)
                 lo += len(lab)
             loss = total / len(y) if len(y) else 0.0
-        else:
+        elif code == BCE and hyper[0] == 0.0:                        # (plain cross-entropy keeps the form this method always had)
             eps = 1e-7                                               # keras backend epsilon
             p = np.clip(pred, eps, 1 - eps)
             loss = float(-np.mean(y * np.log(p) + (1 - y) * np.log(1 - p))) if len(y) else 0.0
+        else:
+            loss = float(np.mean(loss_terms(code, hyper, y, pred))) if len(y) else 0.0
         for w in self.parameters():
             reg = getattr(w, 'regularizer', None)
             if reg is not None and getattr(reg, 'l2', 0.0):
                 loss += float(reg.l2) * float((w.detach().double() ** 2).sum())
-        acc = float(np.mean((pred > 0.5) == (y > 0.5))) if len(y) else 0.0
-        return [loss, acc]
+        if all(name == 'accuracy' for name in names):
+            acc = float(np.mean((pred > 0.5) == (y > 0.5))) if len(y) else 0.0
+            return [loss, acc]
+        values = metric_values(metric_counters(pred32, y), names)
+        return [loss] + [values[name] for name in names]

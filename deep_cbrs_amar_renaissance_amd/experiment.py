@@ -37,7 +37,8 @@ from deep_cbrs_amar_renaissance_amd.models.basic import BasicRS, BasicGNN, Basic
 from deep_cbrs_amar_renaissance_amd.models.hybrid import HybridCBRS, HybridBertGNN
 from deep_cbrs_amar_renaissance_amd.utilities import losses
 from deep_cbrs_amar_renaissance_amd.utilities.keras import get_total_parameters
-from deep_cbrs_amar_renaissance_amd.utilities.metrics import full_ranking_metrics, recommendations_frame, top_k_predictions, top_k_metrics
+from deep_cbrs_amar_renaissance_amd.utilities.metrics import full_ranking_metrics, recommendations_frame, resolve_compiled, top_k_predictions, \
+    top_k_metrics
 from deep_cbrs_amar_renaissance_amd.utilities.utils import \
     get_experiment_logger, nested_dict_update, make_grid, mlflow_linearize, setup_mlflow
 
@@ -239,8 +240,10 @@ class Experimenter:
             self.model = cls(**model_cfg)
         if hasattr(self.model, 'n_users'):                   # lets hoisted scoring run each tower on its own rows
             self.model.n_users, self.model.n_items = len(self.trainset.users), len(self.trainset.items)
-        if isinstance(self.parameters.loss, str) and hasattr(losses, self.parameters.loss):    # custom loss (experiment.py:155-157)
-            self.parameters['loss'] = getattr(losses, self.parameters.loss)()
+        # custom loss class (experiment.py:155-157); any other name, or a mapping {name: ..., <hyper-parameters>}, goes to compile()
+        custom = getattr(losses, self.parameters.loss, None) if isinstance(self.parameters.loss, str) else None
+        if isinstance(custom, type) and custom.__module__ == losses.__name__:
+            self.parameters['loss'] = custom()
         self.model.compile(loss=self.parameters.loss, optimizer=self.optimizer, metrics=self.parameters.metrics)
         self.model(self.trainset[0][0])                       # one prediction builds every weight
         self.model.summary(print_fn=self.logger.info, expand_nested=True)
@@ -262,7 +265,12 @@ class Experimenter:
 
     def evaluate(self):
         loss_acc = self.model.evaluate(self.testset)
-        self.run_log.log_metrics({'test_loss': loss_acc[0], 'test_accuracy': loss_acc[1]})
+        # evaluate(): [loss, accuracy] when no metric or only accuracy is compiled, else [loss, <metrics in compile order>]
+        names = resolve_compiled(self.model.loss, self.model.metrics)[2]
+        if all(name == 'accuracy' for name in names):
+            self.run_log.log_metrics({'test_loss': loss_acc[0], 'test_accuracy': loss_acc[1]})
+        else:
+            self.run_log.log_metrics(dict({'test_loss': loss_acc[0]}, **{'test_' + name: v for name, v in zip(names, loss_acc[1:])}))
         predictions = self.model.predict(self.testset)
         ratings_pred = np.concatenate([self.testset.ratings[:, [0, 1]], predictions], axis=1)
         precision_at, recall_at, f1_at = {}, {}, {}

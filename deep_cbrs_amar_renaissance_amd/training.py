@@ -38,8 +38,9 @@ from deep_cbrs_amar_renaissance_amd.layers.gat_conv import GATConv
 from deep_cbrs_amar_renaissance_amd.layers.gcn_conv import GCNConv
 from deep_cbrs_amar_renaissance_amd.layers.graphsage_conv import GraphSageConv
 from deep_cbrs_amar_renaissance_amd.layers.lightgcn_conv import LightGCNConv
-from deep_cbrs_amar_renaissance_amd.utilities.losses import loss_kind
+from deep_cbrs_amar_renaissance_amd.utilities.losses import BPR, loss_kind
 from deep_cbrs_amar_renaissance_amd.utilities.math import spmm_kind
+from deep_cbrs_amar_renaissance_amd.utilities.metrics import metric_values, resolve_compiled
 
 
 def _spmm(a, x, out):
@@ -855,12 +856,68 @@ class Trainer:
         """The compiled loss (Model.compile): 'bce' (binary cross-entropy, the default) or 'bpr' (utilities/losses.py:BPRLoss)."""
         return loss_kind(getattr(self.model, 'loss', None))
 
+    def _compiled(self):
+        """(loss code, its four hyper-parameters, history names of the metrics) of Model.compile, resolved where the loss is read
+        (utilities/metrics.py:resolve_compiled raises for what has no kernel) and kept until compile() hands over other objects."""
+        loss, metrics = getattr(self.model, 'loss', None), getattr(self.model, 'metrics', None)
+        held = getattr(self, '_compiled_held', None)
+        if held is None or held[0] is not loss or held[1] is not metrics:
+            held = self._compiled_held = (loss, metrics, resolve_compiled(loss, metrics))
+        return held[2]
+
+    def _loss_spec(self):
+        """What a captured batch has baked in of compile(): (loss code, hyper-parameters, whether the metric counters are on).  A
+        graph captured under another spec is dropped where it is looked up (`_captured`), so a second compile() captures anew."""
+        code, hyper, names = self._compiled()
+        return code, hyper, bool(names)
+
+    def _captured(self, key):
+        """The captured graph of `key`, or None — also when compile() has changed the loss, its hyper-parameters or the counters
+        since the capture: that graph is forgotten and the shape starts over with its eager batch."""
+        g = self._graphs.get(key)
+        if g is not None and g.get('compiled') != self._loss_spec():
+            del self._graphs[key]
+            self._seen.discard(key)
+            g = None
+        return g
+
+    def _metric_block(self):
+        """The int64 counter block the loss kernel adds every batch to (include/amar_hip.h: amar_loss_grad_f32), allocated at the
+        first counted batch — an eager one, so never inside a capture."""
+        if getattr(self, '_counters', None) is None:
+            self._counters = torch.zeros(capi.LOSS_COUNTERS, dtype=torch.int64, device=self.device)
+            self._counters_host = torch.zeros(capi.LOSS_COUNTERS, dtype=torch.int64).pin_memory()
+            self._counters_read = None
+        return self._counters
+
     def _loss_grad(self, p, yv, dz, terms):
-        """Per-pair loss terms (their sum = B x the batch's loss) and d(loss)/d(logit) of the compiled loss."""
-        if self._loss_kind() == 'bpr':
+        """Per-pair loss terms (their sum = B x the batch's loss) and d(loss)/d(logit) of the compiled loss; with metrics compiled
+        the same launch adds the batch to the counter block."""
+        code, hyper, names = self._compiled()
+        if code == BPR:
             capi.bpr_grad(p, dz, terms)
         else:
-            capi.bce_grad(p, yv, dz, terms)
+            capi.loss_grad(code, hyper, p, yv, dz, terms, counters=self._metric_block() if names else None)
+
+    def reset_metrics(self):
+        """Clear the counter block (the start of a fit(): batches counted outside an epoch do not belong to it)."""
+        if getattr(self, '_counters', None) is not None:
+            self._counters.zero_()
+            self._counters_read = None
+
+    def pop_metrics(self):
+        """{history name: value} of the compiled metrics over the batches since the last call, and the counters cleared.  After
+        `pop_loss_sum` the block has already come over in that call's synchronisation; otherwise (eager epochs) it is read here."""
+        names = self._compiled()[2]
+        if not names:
+            return {}
+        block = self._metric_block()
+        counts = self._counters_read
+        if counts is None:
+            counts = block.cpu().numpy()
+            block.zero_()
+        self._counters_read = None
+        return metric_values(counts, names)
 
     # -- one batch ------------------------------------------------------------------------------------------------
     def _bert_rows(self, ids, block):
@@ -1010,7 +1067,7 @@ class Trainer:
         with_blocks = bert is not None and bert[0] is not None
         key = (b, with_blocks, self._loss_kind()) + self.dropout_key  # (a compile() with another loss captures anew; so would other dropout state)
         self._init_graph_state()
-        g = self._graphs.get(key)
+        g = self._captured(key)
         if g is None:
             if key not in self._seen:                               # first batch of this shape: eager (real) step
                 self._seen.add(key)
@@ -1041,6 +1098,7 @@ class Trainer:
                     with torch.no_grad():
                         self._graph_body()
                 g['graph'], _ = capture_graph(body)
+                g['compiled'] = self._loss_spec()
                 self._upload_slots(g)                                # the slot tables of this graph (fixed addresses): once, not per replay
                 self._graphs[key] = g
             else:
@@ -1110,7 +1168,7 @@ class Trainer:
         b = 2 * sampler.h
         key = ('sampled', b, self._loss_kind(), sampler.serial) + self.dropout_key
         self._init_graph_state()
-        g = self._graphs.get(key)
+        g = self._captured(key)
         if g is None:
             g = self._eager_sampled.get(key) if key in self._eager_sampled else self._sampled_buffers(sampler, b)
             self._g = g
@@ -1123,6 +1181,7 @@ class Trainer:
                         self._graph_body()
                 self._sync_step()
                 g['graph'], _ = capture_graph(body)
+                g['compiled'] = self._loss_spec()
                 self._upload_slots(g)
                 self._graphs[key] = g
             else:
@@ -1166,9 +1225,15 @@ class Trainer:
         """Sum over the batches since the last call of (batch loss x batch size); one host synchronisation."""
         if not hasattr(self, '_graphs'):
             return 0.0
+        block = getattr(self, '_counters', None)
+        if block is not None:                                        # the metric counters come over under the same synchronisation
+            self._counters_host.copy_(block, non_blocking=True)
         total = self._eager_loss + float(self._loss_sum.item())
         self._eager_loss = 0.0
         self._loss_sum.zero_()
+        if block is not None:
+            self._counters_read = self._counters_host.numpy().copy()
+            block.zero_()
         return total
 
     def touch_parameters(self):
@@ -1355,6 +1420,25 @@ def _cached_trainer(model, spec):
     return trainer
 
 
+class _History:
+    """fit()'s return value in the making: {'loss': [...], '<metric>': [...]} with the compiled metrics in compile order under Keras'
+    history names.  Resolving them here is where fit() reads the compiled loss and metrics: what compile() refuses is refused again."""
+
+    def __init__(self, trainer):
+        self.trainer = trainer
+        self.values = {'loss': []}
+        self.values.update((name, []) for name in trainer._compiled()[2])
+        trainer.reset_metrics()
+
+    def epoch(self, loss, epoch, epochs, verbose):
+        """Close an epoch: its loss, and the metrics of its batches (read from the device counters, which start over)."""
+        self.values['loss'].append(loss)
+        for name, value in self.trainer.pop_metrics().items():
+            self.values[name].append(value)
+        if verbose:
+            print("Epoch {}/{} - ".format(epoch + 1, epochs) + " - ".join("{}: {:.4f}".format(k, v[-1]) for k, v in self.values.items()))
+
+
 def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
     """Keras-style ``fit`` over a batch Sequence: ``epochs`` passes, ``on_epoch_end`` reshuffles (datasets.py:205-213)."""
     spec = OptimizerSpec(getattr(model, 'optimizer', None))
@@ -1383,7 +1467,7 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
                 trainer.set_tables(tables)
                 trainer._table_sources = tables
         use_graph = tables is not None and os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
-        history = []
+        history = _History(trainer)
         for epoch in range(int(epochs)):
             total, count = 0.0, 0
             for b in range(len(sequence)):
@@ -1401,12 +1485,10 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
             if use_graph:
                 total = trainer.pop_loss_sum()
                 trainer.touch_parameters()
-            history.append(total / max(count, 1))
-            if verbose:
-                print("Epoch {}/{} - loss: {:.4f}".format(epoch + 1, epochs, history[-1]))
+            history.epoch(total / max(count, 1), epoch, epochs, verbose)
             if hasattr(sequence, 'on_epoch_end'):
                 sequence.on_epoch_end()
-        return {'loss': history}
+        return history.values
     # Hybrid batches of the reference's own Sequence (datasets.py:95-123 here, 112-115 there) carry, besides the ids, the BERT rows of the
     # batch's users and items — gathered on the host from ONE table indexed by node id and uploaded every batch (6 MB at batch 1 024).
     # That table is registered once on the device instead and the batches are read as ids only: the same rows, gathered there
@@ -1424,7 +1506,7 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
         trainer = model._trainer = Trainer(model, **hp)
     use_graph = os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
     same_body = not use_graph and trainer.dropout_step is not None      # a model that drops: the replayed body, run eagerly (same bits)
-    history = []
+    history = _History(trainer)
     for epoch in range(int(epochs)):
         total, count = 0.0, 0
         for b in range(len(sequence)):
@@ -1439,12 +1521,10 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
         if use_graph or same_body:
             total = trainer.pop_loss_sum()
             trainer.touch_parameters()
-        history.append(total / max(count, 1))
-        if verbose:
-            print("Epoch {}/{} - loss: {:.4f}".format(epoch + 1, epochs, history[-1]))
+        history.epoch(total / max(count, 1), epoch, epochs, verbose)
         if hasattr(sequence, 'on_epoch_end'):
             sequence.on_epoch_end()
-    return {'loss': history}
+    return history.values
 
 
 def _fit_sampled(model, sequence, epochs, verbose, hp):
@@ -1456,7 +1536,7 @@ def _fit_sampled(model, sequence, epochs, verbose, hp):
         trainer = model._trainer = Trainer(model, **hp)
     sampler = trainer.sampler_for(sequence)
     use_graph = os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
-    history = []
+    history = _History(trainer)
     for epoch in range(int(epochs)):
         count = 0
         for _ in range(len(sequence)):
@@ -1464,7 +1544,5 @@ def _fit_sampled(model, sequence, epochs, verbose, hp):
             count += 2 * sampler.h
         total = trainer.pop_loss_sum()
         trainer.touch_parameters()
-        history.append(total / max(count, 1))
-        if verbose:
-            print("Epoch {}/{} - loss: {:.4f}".format(epoch + 1, epochs, history[-1]))
-    return {'loss': history}
+        history.epoch(total / max(count, 1), epoch, epochs, verbose)
+    return history.values

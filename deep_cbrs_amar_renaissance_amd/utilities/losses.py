@@ -1,9 +1,14 @@
 """Losses named by `parameters.loss` in the configs (`/root/reference/src/utilities/losses.py:5-25`).
 
 The experiment looks a name up here first (``hasattr(losses, name)`` -> an instance, `experiment.py:155-157` of the reference);
-any other name, ``binary_crossentropy`` the default, stays a string and trains with binary cross-entropy.  ``fit()`` and
-``evaluate()`` read the compiled loss through `loss_kind`.
+any other value — a Keras loss name, a Keras class name, or a mapping ``{name: ..., <hyper-parameters>}`` — goes through
+`resolve_loss`, which names the pointwise losses the device computes (include/amar_hip.h: amar_loss_grad_f32) and refuses every other
+name: ``binary_crossentropy`` is the default.  ``fit()`` and ``evaluate()`` read the compiled loss through `resolve_loss`
+(`loss_kind` tells BPR from the pointwise losses).  `loss_terms` / `loss_dp` restate every pointwise loss in float64 numpy.
 """
+from collections.abc import Mapping
+
+
 import numpy as np
 
 
@@ -30,3 +35,144 @@ def loss_kind(loss):
     if isinstance(loss, BPRLoss) or loss == 'BPRLoss':
         return 'bpr'
     return 'bce'
+
+
+# ---- Keras 2's pointwise losses on one sigmoid output (include/amar_hip.h: AMAR_LOSS_*) ---------------------------------------------
+BCE, MSE, MAE, HINGE, SQUARED_HINGE, HUBER, LOG_COSH, POISSON, FOCAL = range(9)
+BPR = -1                                                              # (no code of amar_loss_grad_f32: amar_bpr_grad_f32's loss)
+
+LOSS_NAMES = {BCE: 'binary_crossentropy', MSE: 'mean_squared_error', MAE: 'mean_absolute_error', HINGE: 'hinge',
+              SQUARED_HINGE: 'squared_hinge', HUBER: 'huber', LOG_COSH: 'log_cosh', POISSON: 'poisson',
+              FOCAL: 'binary_focal_crossentropy', BPR: 'BPRLoss'}
+_ALIASES = {
+    'binary_crossentropy': BCE, 'BinaryCrossentropy': BCE,
+    'mean_squared_error': MSE, 'mse': MSE, 'MSE': MSE, 'MeanSquaredError': MSE,
+    'mean_absolute_error': MAE, 'mae': MAE, 'MAE': MAE, 'MeanAbsoluteError': MAE,
+    'hinge': HINGE, 'Hinge': HINGE,
+    'squared_hinge': SQUARED_HINGE, 'SquaredHinge': SQUARED_HINGE,
+    'huber': HUBER, 'huber_loss': HUBER, 'Huber': HUBER,
+    'log_cosh': LOG_COSH, 'logcosh': LOG_COSH, 'LogCosh': LOG_COSH,
+    'poisson': POISSON, 'Poisson': POISSON,
+    'binary_focal_crossentropy': FOCAL, 'BinaryFocalCrossentropy': FOCAL,
+    'BPRLoss': BPR,
+}
+# what tf.keras.losses.get resolves and no kernel here computes (multi-class, distribution and similarity losses)
+_KERAS_WITHOUT_KERNEL = {
+    'categorical_crossentropy', 'CategoricalCrossentropy', 'sparse_categorical_crossentropy', 'SparseCategoricalCrossentropy',
+    'categorical_hinge', 'CategoricalHinge', 'kl_divergence', 'kld', 'KLD', 'kullback_leibler_divergence', 'KLDivergence',
+    'cosine_similarity', 'CosineSimilarity', 'mean_absolute_percentage_error', 'mape', 'MAPE', 'MeanAbsolutePercentageError',
+    'mean_squared_logarithmic_error', 'msle', 'MSLE', 'MeanSquaredLogarithmicError',
+}
+# hyper-parameters a mapping may carry, with Keras' defaults; the kernel's array is (label_smoothing, delta | gamma, alpha, balancing)
+_HYPER_DEFAULTS = {BCE: {'label_smoothing': 0.0}, HUBER: {'delta': 1.0},
+                   FOCAL: {'gamma': 2.0, 'apply_class_balancing': False, 'alpha': 0.25, 'label_smoothing': 0.0}}
+
+
+def supported_losses():
+    """Every name `resolve_loss` accepts, sorted."""
+    return sorted(_ALIASES)
+
+
+def resolve_loss(loss):
+    """(code, hyper, name) of a compiled loss: `code` one of the AMAR_LOSS_* codes (or BPR), `hyper` the kernel's four floats
+    (label_smoothing, delta or gamma, alpha, apply_class_balancing as 0 / 1) as a tuple, `name` Keras' function name.
+    Accepts None (binary cross-entropy), a Keras loss or class name, a BPRLoss, or a mapping {name: ..., <hyper-parameters>}.
+    NotImplementedError: a loss Keras knows and no kernel here computes; ValueError: any other name or hyper-parameter."""
+    values = {}
+    if isinstance(loss, BPRLoss):
+        return BPR, (0.0, 0.0, 0.0, 0.0), LOSS_NAMES[BPR]
+    if isinstance(loss, Mapping):
+        values = {k: v for k, v in loss.items() if k not in ('name', 'class_name')}
+        loss = loss.get('name', loss.get('class_name'))
+    if loss is None:
+        loss = 'binary_crossentropy'
+    if not isinstance(loss, str):
+        raise ValueError("loss must be a name, a mapping with a name, a BPRLoss or None (got {!r})".format(loss))
+    if loss not in _ALIASES:
+        if loss in _KERAS_WITHOUT_KERNEL:
+            raise NotImplementedError("loss '{}' has no kernel here; supported: {}".format(loss, ', '.join(supported_losses())))
+        raise ValueError("unknown loss '{}'; supported: {}".format(loss, ', '.join(supported_losses())))
+    code = _ALIASES[loss]
+    known = dict(_HYPER_DEFAULTS.get(code, {}))
+    unknown = sorted(set(values) - set(known))
+    if unknown:
+        raise ValueError("loss '{}' takes no hyper-parameter {} (it takes: {})".format(loss, unknown, sorted(known) or 'none'))
+    known.update(values)
+    ls = float(known.get('label_smoothing', 0.0))
+    shape = float(known.get('delta', known.get('gamma', 0.0)))
+    if not 0.0 <= ls <= 1.0 or shape < 0.0:
+        raise ValueError("loss '{}': label_smoothing must lie in [0, 1], delta / gamma must not be negative".format(loss))
+    hyper = (ls, shape, float(known.get('alpha', 0.0)), 1.0 if known.get('apply_class_balancing', False) else 0.0)
+    return code, hyper, LOSS_NAMES[code]
+
+
+def _f32(x):
+    return float(np.float32(x))
+
+
+def _bce_parts(p, y, f32_constants):
+    """Keras' backend binary_crossentropy on probabilities: (term, d term / dp).  f32_constants: the clip points float32 arithmetic
+    produces (epsilon = float32(1e-7), upper clip 1 - epsilon rounded to float32), as the device and Keras itself compute them."""
+    eps = _f32(1e-7) if f32_constants else 1e-7
+    hi = _f32(np.float32(1) - np.float32(1e-7)) if f32_constants else 1.0 - eps
+    pc = np.clip(p, eps, hi)
+    term = -(y * np.log(pc + eps) + (1.0 - y) * np.log(1.0 - pc + eps))
+    inside = (p >= eps) & (p <= hi)
+    return term, np.where(inside, -(y / (pc + eps) - (1.0 - y) / (1.0 - pc + eps)), 0.0)
+
+
+def _pair_parts(code, hyper, y_true, y_pred, f32_constants=False):
+    y = np.asarray(y_true, dtype=np.float64).reshape(-1)
+    p = np.asarray(y_pred, dtype=np.float64).reshape(-1)
+    ls, shape, alpha, balance = (float(v) for v in hyper)
+    e, s = p - y, 2.0 * y - 1.0
+    if code == BCE:
+        return _bce_parts(p, y * (1.0 - ls) + 0.5 * ls, f32_constants)
+    if code == MSE:
+        return e * e, 2.0 * e
+    if code == MAE:
+        return np.abs(e), np.sign(e)
+    if code == HINGE:
+        m = np.maximum(1.0 - s * p, 0.0)
+        return m, np.where(m > 0.0, -s, 0.0)
+    if code == SQUARED_HINGE:
+        m = np.maximum(1.0 - s * p, 0.0)
+        return m * m, -2.0 * s * m
+    if code == HUBER:
+        quad = np.abs(e) <= shape
+        return np.where(quad, 0.5 * e * e, shape * np.abs(e) - 0.5 * shape * shape), np.where(quad, e, shape * np.sign(e))
+    if code == LOG_COSH:
+        return e + np.logaddexp(0.0, -2.0 * e) - np.log(2.0), np.tanh(e)
+    if code == POISSON:
+        q = p + (_f32(1e-7) if f32_constants else 1e-7)
+        return p - y * np.log(q), 1.0 - y / q
+    if code == FOCAL:
+        ys = y * (1.0 - ls) + 0.5 * ls
+        bce, dbce = _bce_parts(p, ys, f32_constants)
+        q = np.maximum(1.0 - (ys * p + (1.0 - ys) * (1.0 - p)), 0.0)
+        w = ys * alpha + (1.0 - ys) * (1.0 - alpha) if balance else 1.0
+        with np.errstate(divide='ignore', invalid='ignore'):
+            ff = np.power(q, shape)
+            dff = shape * np.power(q, shape - 1.0) * (1.0 - 2.0 * ys) if shape else np.zeros_like(q)
+        return w * ff * bce, w * (dff * bce + ff * dbce)
+    raise ValueError("no pointwise loss with code {}".format(code))
+
+
+def loss_terms(code, hyper, y_true, y_pred, f32_constants=False):
+    """float64 per-pair terms of pointwise loss `code` (their mean is the batch loss): what amar_loss_grad_f32 writes to loss_terms."""
+    return _pair_parts(code, hyper, y_true, y_pred, f32_constants)[0]
+
+
+def loss_dp(code, hyper, y_true, y_pred, f32_constants=False):
+    """float64 d(term_i)/d(p_i) of pointwise loss `code`: 0 where the loss is flat or clipped, TensorFlow's choice (0) at MAE's kink."""
+    return _pair_parts(code, hyper, y_true, y_pred, f32_constants)[1]
+
+
+def loss_value(loss, y_true, y_pred):
+    """float64 batch value of a compiled loss (anything `resolve_loss` accepts) on labels and probabilities: the mean of the
+    per-pair terms, BPRLoss's own value for BPR; an empty batch counts 0."""
+    code, hyper, _ = resolve_loss(loss)
+    if code == BPR:
+        return BPRLoss()(y_true, y_pred)
+    terms = loss_terms(code, hyper, y_true, y_pred)
+    return float(np.mean(terms)) if len(terms) else 0.0

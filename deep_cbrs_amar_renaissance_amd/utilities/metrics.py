@@ -12,6 +12,10 @@ Precision/Recall/F1@k is restated on the host from RiVal's ranking-metric semant
 (``precision_recall_f1_at_k``: hand-computed vectors in tests/test_metrics_cpu.py; the choices the
 jar's behaviour cannot settle here are explicit switches) and writes the same ``results.tsv``
 (label, P, R, F1 — `experiment.py:211-213` reads columns 1..3).
+
+The metrics of ``Model.compile(metrics=...)`` live here too: `resolve_metrics` names the ones the training kernel counts
+(include/amar_hip.h: amar_loss_grad_f32's counter block), `metric_counters` restates that block in numpy and `metric_values` turns
+either into Keras' accuracy / Precision / Recall / AUC.
 """
 import logging
 import os
@@ -202,3 +206,103 @@ def top_k_metrics(test_filepath, predictions_path, short_lists=None, no_relevant
                 'short_lists', 'no_relevant']
         pd.DataFrame([[f] + [info[key] for key in keys] for f, info in zip(found, infos)], columns=['file'] + keys).to_csv(
             os.path.join(root, "results_users.tsv"), sep='\t', index=False)
+
+
+# ---- compiled metrics (Model.compile(metrics=...)): binary accuracy, Precision, Recall, AUC from integer counters ----------------------
+AUC_BUCKETS = 199                                                      # include/amar_hip.h: AMAR_AUC_BUCKETS
+N_COUNTERS = 4 + 2 * AUC_BUCKETS                                       # tp, fp, tn, fn, then hist[label][bucket]
+_METRIC_ALIASES = {'accuracy': 'accuracy', 'acc': 'accuracy', 'binary_accuracy': 'accuracy', 'BinaryAccuracy': 'accuracy',
+                   'Precision': 'precision', 'precision': 'precision', 'Recall': 'recall', 'recall': 'recall',
+                   'AUC': 'auc', 'auc': 'auc'}
+_KERAS_METRICS_WITHOUT_KERNEL = {
+    'TopKCategoricalAccuracy', 'top_k_categorical_accuracy', 'SparseTopKCategoricalAccuracy', 'sparse_top_k_categorical_accuracy',
+    'CategoricalAccuracy', 'categorical_accuracy', 'SparseCategoricalAccuracy', 'sparse_categorical_accuracy',
+    'TruePositives', 'TrueNegatives', 'FalsePositives', 'FalseNegatives', 'PrecisionAtRecall', 'RecallAtPrecision',
+    'SensitivityAtSpecificity', 'SpecificityAtSensitivity', 'MeanSquaredError', 'mean_squared_error', 'mse', 'MSE',
+    'RootMeanSquaredError', 'MeanAbsoluteError', 'mean_absolute_error', 'mae', 'MAE', 'BinaryCrossentropy', 'binary_crossentropy',
+    'CategoricalCrossentropy', 'categorical_crossentropy', 'KLDivergence', 'kl_divergence', 'CosineSimilarity', 'cosine_similarity',
+    'Hinge', 'hinge', 'SquaredHinge', 'squared_hinge', 'LogCoshError', 'logcosh', 'Poisson', 'poisson', 'MeanIoU', 'BinaryIoU', 'F1Score',
+}
+
+
+def resolve_metrics(names):
+    """History names ('accuracy', 'precision', 'recall', 'auc') of the compiled metrics, in compile order, each once.
+    NotImplementedError: a metric Keras knows and the counters do not give; ValueError: any other name."""
+    out = []
+    for name in names or []:
+        if not isinstance(name, str) or name not in _METRIC_ALIASES:
+            supported = ', '.join(sorted(_METRIC_ALIASES))
+            if isinstance(name, str) and name in _KERAS_METRICS_WITHOUT_KERNEL:
+                raise NotImplementedError("metric '{}' is not computed here; supported: {}".format(name, supported))
+            raise ValueError("unknown metric {!r}; supported: {}".format(name, supported))
+        if _METRIC_ALIASES[name] not in out:
+            out.append(_METRIC_ALIASES[name])
+    return out
+
+
+def resolve_compiled(loss, metrics):
+    """(loss code, hyper, metric history names) of a Model.compile(loss=..., metrics=...), with the errors of `resolve_loss` and
+    `resolve_metrics`.  Under BPRLoss the labels carry no meaning: 'accuracy' is accepted and left out, any other metric raises
+    NotImplementedError."""
+    from deep_cbrs_amar_renaissance_amd.utilities.losses import BPR, resolve_loss
+    code, hyper, _ = resolve_loss(loss)
+    names = resolve_metrics(metrics)
+    if code == BPR:
+        if any(name != 'accuracy' for name in names):
+            raise NotImplementedError("BPRLoss trains on (positive, negative) pairs whose labels carry no meaning: metrics {} are not "
+                                      "defined under it".format([n for n in names if n != 'accuracy']))
+        names = []
+    return code, hyper, names
+
+
+def auc_thresholds():
+    """The 198 interior thresholds of Keras' AUC(num_thresholds=200): float32((i + 1) / 199) computed in double, as Keras does."""
+    return (np.arange(1, AUC_BUCKETS, dtype=np.float64) / float(AUC_BUCKETS)).astype(np.float32)
+
+
+def metric_counters(p, y):
+    """The counter block of amar_loss_grad_f32 for probabilities p (compared as float32) and labels y, as int64 [N_COUNTERS]:
+    tp, fp, tn, fn at threshold 0.5, then for each label the histogram of how many interior AUC thresholds p exceeds."""
+    p = np.asarray(p, dtype=np.float32).reshape(-1)
+    actual = np.asarray(y, dtype=np.float32).reshape(-1) > np.float32(0.5)
+    predicted = p > np.float32(0.5)
+    out = np.zeros(N_COUNTERS, dtype=np.int64)
+    out[0], out[1] = np.sum(actual & predicted), np.sum(~actual & predicted)
+    out[2], out[3] = np.sum(~actual & ~predicted), np.sum(actual & ~predicted)
+    bucket = (p[:, None] > auc_thresholds()[None, :]).sum(axis=1) if len(p) else np.zeros(0, dtype=np.int64)
+    for label in (0, 1):
+        out[4 + label * AUC_BUCKETS:4 + (label + 1) * AUC_BUCKETS] = np.bincount(bucket[actual == bool(label)], minlength=AUC_BUCKETS)
+    return out
+
+
+def _div_no_nan(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return np.divide(a, b, out=np.zeros(np.broadcast(a, b).shape), where=b != 0)
+
+
+def metric_values(counters, names):
+    """{history name: value} of the metrics `names` (as `resolve_metrics` returns them) from a counter block: accuracy = (tp + tn) / n,
+    precision = tp / (tp + fp) and recall = tp / (tp + fn) with Keras' div_no_nan (0 for an empty denominator), auc = Keras'
+    AUC(num_thresholds=200, curve='ROC', summation_method='interpolation'): cumulative counts above each of the 200 thresholds (every
+    p in [0, 1] exceeds the first, -1e-7, and none the last, 1 + 1e-7), then the trapezoid rule over (false-positive rate, recall)."""
+    c = np.asarray(counters, dtype=np.int64).reshape(-1)
+    if len(c) != N_COUNTERS:
+        raise ValueError("a counter block holds {} cells".format(N_COUNTERS))
+    tp, fp, tn, fn = (float(v) for v in c[:4])
+    out = {}
+    for name in names:
+        if name == 'accuracy':
+            out[name] = float(_div_no_nan(tp + tn, tp + fp + tn + fn))
+        elif name == 'precision':
+            out[name] = float(_div_no_nan(tp, tp + fp))
+        elif name == 'recall':
+            out[name] = float(_div_no_nan(tp, tp + fn))
+        elif name == 'auc':
+            hist = c[4:].reshape(2, AUC_BUCKETS).astype(np.float64)
+            above = np.concatenate([np.cumsum(hist[:, ::-1], axis=1)[:, ::-1], np.zeros((2, 1))], axis=1)   # [label, 200 thresholds]
+            total = hist.sum(axis=1, keepdims=True)
+            fpr, rec = _div_no_nan(above[0], total[0]), _div_no_nan(above[1], total[1])
+            out[name] = float(np.sum((fpr[:-1] - fpr[1:]) * (rec[:-1] + rec[1:]) / 2.0))
+        else:
+            raise ValueError("no metric named {!r}".format(name))
+    return out

@@ -885,6 +885,49 @@ int amar_bpr_sample_i32(const int32_t *pos_ptr, const int32_t *pos_ids, const in
                         int32_t n_users, uint64_t seed, uint64_t *step, int32_t advance, int32_t h,
                         int32_t *u, int32_t *items, float *y, amar_stream_t stream);
 
+/* ---- the compiled loss and the compiled metrics (Model.compile(loss=..., metrics=...)) -------------------------------------------
+ * amar_loss_grad_f32   Keras 2's pointwise losses on ONE sigmoid output, in amar_bce_grad_f32's place and conventions: p is [B] or a
+ *                      strided [B, 1] column (leading dimension ldp), y the 0/1 labels, loss_terms[i] the pair's term (their sum =
+ *                      B x batch loss), dz[i] = d(mean loss)/d(logit) = dL_i/dp . p (1 - p) / B; dz and loss_terms contiguous [B].
+ *                      With e = p - y and s = 2y - 1:
+ *                        AMAR_LOSS_BCE            amar_bce_grad_f32's term on y <- y (1 - ls) + ls / 2; ls = 0 gives its very bits
+ *                        AMAR_LOSS_MSE            e^2
+ *                        AMAR_LOSS_MAE            |e|, gradient 0 at e = 0
+ *                        AMAR_LOSS_HINGE          max(1 - s p, 0)
+ *                        AMAR_LOSS_SQUARED_HINGE  max(1 - s p, 0)^2
+ *                        AMAR_LOSS_HUBER          e^2 / 2 where |e| <= delta, else delta |e| - delta^2 / 2
+ *                        AMAR_LOSS_LOG_COSH       e + softplus(-2e) - log 2, evaluated as log1p(2 sinh^2(e / 2))
+ *                        AMAR_LOSS_POISSON        p - y log(p + 1e-7)
+ *                        AMAR_LOSS_FOCAL          [alpha y + (1 - alpha)(1 - y) if balance] (1 - p_t)^gamma bce(p, y), p_t = y p + (1 - y)(1 - p),
+ *                                                 y smoothed first as above, bce the clipped term of AMAR_LOSS_BCE
+ *                      hyper: AMAR_LOSS_HYPER_FLOATS host floats read at the call — [0] label_smoothing in [0, 1] (BCE, FOCAL),
+ *                      [1] delta (HUBER) or gamma (FOCAL), >= 0, [2] alpha, [3] apply_class_balancing as 0 / 1; NULL = Keras' defaults
+ *                      (0, 1 or 2, 0.25, 0).  Where a loss is flat or clipped (hinge beyond the margin, cross-entropy outside
+ *                      [1e-7, 1 - 1e-7]) and where p is exactly 0 or 1, dz is exactly 0.  float32, one lane per pair, no float atomics.
+ *                      counters (nullable): AMAR_LOSS_COUNTERS 64-bit integers in DEVICE memory that the launch ADDS this batch to
+ *                      (the host clears them): [0..3] = tp, fp, tn, fn with predicted positive <=> p > 0.5 and actual positive <=>
+ *                      y > 0.5 (binary accuracy, Precision, Recall at 0.5); [4 + label * AMAR_AUC_BUCKETS + b] = the pairs of that label
+ *                      whose p exceeds exactly b of the 198 interior thresholds float32(k / 199.0), k = 1..198, of Keras'
+ *                      AUC(num_thresholds=200) — b agrees with the float comparison p > threshold for every p.  Integer sums
+ *                      (per wavefront, LDS, one global atomic per non-zero cell and workgroup): the same bits on every run.
+ *                      NULL: nothing is counted and nothing is written.
+ * amar_loss_counters   AMAR_LOSS_COUNTERS, for a caller that sizes the block at run time. */
+#define AMAR_LOSS_BCE           0
+#define AMAR_LOSS_MSE           1
+#define AMAR_LOSS_MAE           2
+#define AMAR_LOSS_HINGE         3
+#define AMAR_LOSS_SQUARED_HINGE 4
+#define AMAR_LOSS_HUBER         5
+#define AMAR_LOSS_LOG_COSH      6
+#define AMAR_LOSS_POISSON       7
+#define AMAR_LOSS_FOCAL         8
+#define AMAR_LOSS_HYPER_FLOATS  4
+#define AMAR_AUC_BUCKETS        199
+#define AMAR_LOSS_COUNTERS      (4 + 2 * AMAR_AUC_BUCKETS)
+int32_t amar_loss_counters(void);
+int amar_loss_grad_f32(int32_t loss, const float *hyper, const float *p, int64_t ldp, const float *y, float *dz, float *loss_terms,
+                       int64_t B, int64_t *counters, amar_stream_t stream);
+
 /* ---- training-time dropout (the `dropout` key of the GNN stacks, `dropout_rate` of GAT) ------------------------------------------
  * No mask is stored: a keep bit is a function of (seed, step, site, element) through Philox4x32-10 and the reverse pass regenerates
  * it.  key = (seed & 0xffffffff, seed >> 32); counter = (c0, s & 0xffffffff, s >> 32, (site << 24) | c3) with s = *step read from
