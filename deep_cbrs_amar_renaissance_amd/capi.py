@@ -133,6 +133,7 @@ SIGNATURES = {
     'amar_recommend_slices': (ctypes.c_int32, [_I64, _I32, _P, _I32, _I32]),
     'amar_recommend_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P,
                                           _I32, _I32, _P, _P, _P, _P, _P]),
+    'amar_rank_metrics_f64': (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -1258,6 +1259,59 @@ def recommend(Tu, Ti, wpack, dims, acts, in_act, k, users=None, excl_ptr=None, e
         _ptr(out_items) if m else None, _ptr(out_scores) if m else None, _stream())
     _check(code, 'amar_recommend_f32')
     return out_items, out_scores
+
+
+RANK_METRICS_MAX_KS, RANK_METRICS_MAX_BLOCKS = 8, 1024                 # include/amar_hip.h: AMAR_RANK_METRICS_MAX_KS / _MAX_BLOCKS
+RANK_METRICS_CELLS = 4 * RANK_METRICS_MAX_KS + 2
+
+
+def rank_metrics_args(K, ks):
+    """The host arguments of amar_rank_metrics_f64, checked: (ks as a list of ints, cum_disc float64 [K + 1] with cum_disc[0] = 0 and
+    cum_disc[j] = sum_{r <= j} 1 / log2(r + 1)).  ValueError for K outside [1, 64], no or more than 8 cutoffs, a cutoff outside [1, K]."""
+    import numpy as np
+    K = int(K)
+    ks = [int(k) for k in ks]
+    if not 1 <= K <= 64:
+        raise ValueError("rank_metrics: the lists must hold between 1 and 64 ranks (got {})".format(K))
+    if not 1 <= len(ks) <= RANK_METRICS_MAX_KS:
+        raise ValueError("rank_metrics: between 1 and {} cutoffs (got {})".format(RANK_METRICS_MAX_KS, len(ks)))
+    if any(k < 1 or k > K for k in ks):
+        raise ValueError("every k must lie in [1, {}] (the length of the lists)".format(K))
+    cum = np.zeros(K + 1, dtype=np.float64)
+    np.cumsum(1.0 / np.log2(np.arange(K, dtype=np.float64) + 2.0), out=cum[1:])
+    return ks, cum
+
+
+def rank_metrics(lists, rel_ptr, rel_items, ks, users=None):
+    """Full-ranking metrics of device lists (amar_rank_metrics_f64): lists int32 [m, K] item rows best first (-1 padded), the relevant
+    items as a CSR over users (rel_ptr int32 [n_users + 1], rel_items int32 sorted and de-duplicated per user), row j belonging to
+    users[j] (int32 [m]; None: user j, m == n_users).  Returns (means float64 [nk, 4]: precision, recall, ndcg, hit per cutoff — the
+    sums over the evaluated users divided by their number, the sums themselves when nobody was evaluated —, evaluated, skipped)."""
+    import numpy as np
+    if lists.dim() != 2 or not lists.is_contiguous():
+        raise ValueError("rank_metrics: lists must be a contiguous [m, K] tensor")
+    m, K = int(lists.shape[0]), int(lists.shape[1])
+    ks, cum = rank_metrics_args(K, ks)
+    n_users = int(rel_ptr.numel()) - 1
+    if n_users < 0:
+        raise ValueError("rank_metrics: rel_ptr must have n_users + 1 entries")
+    if users is not None and int(users.numel()) != m:
+        raise ValueError("rank_metrics: users must name one user per list")
+    if users is None and m != n_users:
+        raise ValueError("rank_metrics: without users the lists must cover every user ({} lists, {} users)".format(m, n_users))
+    dev = rel_ptr.device
+    ws = torch.empty(RANK_METRICS_MAX_BLOCKS * RANK_METRICS_CELLS, dtype=torch.float64, device=dev)
+    sums = torch.empty((len(ks), 4), dtype=torch.float64, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    ks_c = (ctypes.c_int32 * len(ks))(*ks)
+    code = load().amar_rank_metrics_f64(
+        _ptr(lists, torch.int32, 'lists') if m else None, m, K, _ptr(users, torch.int32, 'users'), _ptr(rel_ptr, torch.int32, 'rel_ptr'),
+        _ptr_entries(rel_items, torch.int32, 'rel_items'), n_users, ks_c, len(ks), cum.ctypes.data_as(ctypes.c_void_p),
+        _ptr(ws), _ptr(sums), _ptr(counts), _stream())
+    _check(code, 'amar_rank_metrics_f64')
+    evaluated, skipped = (int(c) for c in counts.cpu().numpy())
+    sums = sums.cpu().numpy()
+    return (sums / evaluated if evaluated else sums), evaluated, skipped
 
 
 # ---- training step ----------------------------------------------------------------------------------------------

@@ -330,3 +330,33 @@ def dropout_edge_mask(seed, step, site, rowptr, colidx, self_loop, rate):
         i = np.arange(n, dtype=np.uint64)
         loops = _dropout_words(seed, step, site, i | (np.uint64(255) << np.uint64(24)), i)[:, 0] >= t
     return w[:, 0] >= t, loops
+
+
+def holdout_split(ratings, fraction, seed):
+    """Split rating rows into (kept, held out): about `fraction` of the rows, visited in the order of a generator seeded with `seed`,
+    move to the held-out part — a row only while its user AND its item each keep at least one other row in the kept part, so every
+    user and item of `ratings` still occurs in the kept part (the loaders refuse identifiers absent from training).  Both parts keep
+    the input's row order; the same seed gives the same split.  Fewer than round(fraction * n) rows move only when no further row may:
+    at least min(round(fraction * n), n - |users| - |items|) always do."""
+    r = np.asarray(ratings)
+    if not 0.0 <= float(fraction) < 1.0:
+        raise ValueError("fraction must lie in [0, 1) (got {!r})".format(fraction))
+    n = len(r)
+    target = int(round(float(fraction) * n))
+    moved = np.zeros(n, dtype=bool)
+    if n == 0 or target == 0:
+        return r[~moved], r[moved]
+    _, u_inv = np.unique(r[:, 0], return_inverse=True)
+    _, i_inv = np.unique(r[:, 1], return_inverse=True)
+    u_left, i_left = np.bincount(u_inv), np.bincount(i_inv)
+    done = 0
+    for row in np.random.RandomState(int(seed)).permutation(n).tolist():
+        u, i = u_inv[row], i_inv[row]
+        if u_left[u] > 1 and i_left[i] > 1:
+            moved[row] = True
+            u_left[u] -= 1
+            i_left[i] -= 1
+            done += 1
+            if done == target:
+                break
+    return r[~moved], r[moved]

@@ -33,10 +33,11 @@ import yaml
 
 from deep_cbrs_amar_renaissance_amd import engine, models as models_pkg
 from deep_cbrs_amar_renaissance_amd.data import loaders
+from deep_cbrs_amar_renaissance_amd.data.datasets import holdout_split
 from deep_cbrs_amar_renaissance_amd.models.basic import BasicRS, BasicGNN, BasicKnowledgeGCN, BasicTSGNN, BasicTWGNN
 from deep_cbrs_amar_renaissance_amd.models.hybrid import HybridCBRS, HybridBertGNN
 from deep_cbrs_amar_renaissance_amd.utilities import losses
-from deep_cbrs_amar_renaissance_amd.utilities.keras import get_total_parameters
+from deep_cbrs_amar_renaissance_amd.utilities.keras import Callback, EarlyStopping, get_total_parameters
 from deep_cbrs_amar_renaissance_amd.utilities.metrics import full_ranking_metrics, recommendations_frame, resolve_compiled, top_k_predictions, \
     top_k_metrics
 from deep_cbrs_amar_renaissance_amd.utilities.utils import \
@@ -176,6 +177,21 @@ def optimizer_class(name):
     return OPTIMIZERS[name]
 
 
+class RunLogCallback(Callback):
+    """The reference's LogCallback (utilities/keras.py there) for fit(): every epoch's logs go to the run log with step = epoch, and
+    the end of training logs where an EarlyStopping stopped and which epoch was best."""
+
+    def __init__(self, run_log, stopping=None):
+        self.run_log, self.stopping = run_log, stopping
+
+    def on_epoch_end(self, epoch, logs=None):
+        self.run_log.log_metrics({name: float(value) for name, value in (logs or {}).items()}, step=epoch)
+
+    def on_train_end(self, logs=None):
+        if self.stopping is not None:
+            self.run_log.log_metrics({'stopped_epoch': int(self.stopping.stopped_epoch), 'best_epoch': int(self.stopping.best_epoch)})
+
+
 class Experimenter:
     def __init__(self, config, run_log):
         """Holds every object of one experiment and performs its training and evaluation."""
@@ -222,7 +238,40 @@ class Experimenter:
     def build_dataset(self):
         accepted = inspect.signature(self.load_function).parameters
         kwargs = {k: self.config.dataset[k] for k in self.config.dataset.keys() & accepted.keys()}
+        self.valset = None
+        validation = self.config.parameters.get('validation')
+        if validation:
+            # parameters.validation: a share of the training rows is held out (datasets.holdout_split, seeded with config.seed) and both
+            # parts are written next to the run's other artifacts; the kept part is the training file of this run, so the graph holds
+            # no held-out edge, and the held-out part is read through the same load function as a test file
+            sep = kwargs.get('sep', '\t')
+            raw = pd.read_csv(kwargs['train_ratings_filepath'], sep=sep, header=None)
+            kept, held = holdout_split(raw.to_numpy(), float(validation.get('fraction', 0.1)), self.config.seed)
+            dest = path_join(self.config.dest, 'validation')
+            os.makedirs(dest, exist_ok=True)
+            kept_path, held_path = path_join(dest, 'train_kept.tsv'), path_join(dest, 'validation.tsv')
+            for part, path in ((kept, kept_path), (held, held_path)):
+                pd.DataFrame(part).astype(raw.dtypes.to_dict()).to_csv(path, sep=sep, header=False, index=False)
+            kwargs['train_ratings_filepath'] = kept_path
+            _, self.valset = self.load_function(**dict(kwargs, test_ratings_filepath=held_path))
         self.trainset, self.testset = self.load_function(**kwargs)
+
+    def validation_fit_args(self):
+        """fit()'s validation arguments from parameters.validation ({fraction, freq, ranking_ks, early_stopping}); {} without the key."""
+        validation = self.config.parameters.get('validation')
+        if not validation:
+            return {}
+        callbacks = []
+        stopping = None
+        if validation.get('early_stopping'):
+            stopping = EarlyStopping(**dict(validation.get('early_stopping')))
+            callbacks.append(stopping)
+        callbacks.append(RunLogCallback(self.run_log, stopping))
+        args = {'validation_data': self.valset, 'validation_freq': int(validation.get('freq', 1)), 'callbacks': callbacks}
+        if validation.get('ranking_ks'):
+            args['validation_ranking'] = {'trainset': self.trainset, 'ratings': self.valset.ratings,
+                                          'ks': [int(k) for k in validation.get('ranking_ks')], 'users': None}
+        return args
 
     def build_optimizer(self):
         accepted = inspect.signature(self.optimizer_class).parameters
@@ -259,7 +308,7 @@ class Experimenter:
         t0 = time.perf_counter()
         # a model or reduction without a training recipe raises here: the experiment fails (MultiExperimenter.run_experiment
         # logs the traceback, ends the run and goes on with the grid, experiment.py:295-302) instead of evaluating random weights
-        self.model.fit(self.trainset, epochs=self.parameters.epochs, workers=self.config.n_workers)
+        self.model.fit(self.trainset, epochs=self.parameters.epochs, workers=self.config.n_workers, **self.validation_fit_args())
         # the reference's LogCallback reports the fit wall time as 'training_time' (utilities/keras.py:43-51, 69-85)
         self.run_log.log_metrics({'training_time': time.perf_counter() - t0})
 

@@ -15,7 +15,12 @@ Two routes, chosen by the head alone (no user-facing switch):
 Both return ``(users int64 [m], items int64 [m, k], scores float32 [m, k])``: items are node ids (table row + |U|, the
 convention of ``predict()`` inputs and ``top_k_arrays``), rows ordered by score descending then item id ascending, users with
 fewer than k unexcluded items padded with -1 / -inf.
+
+Inside ``device_lists()`` both routes stop before that conversion and return ``(users int64 [m] on the host, items int32 [m, k] item
+ROWS on the device, scores float32 [m, k] on the device)``: ``evaluate_ranking`` scores the lists where they are
+(``amar_rank_metrics_f64``), which is what lets ``fit(validation_ranking=...)`` validate every epoch.
 """
+import contextlib
 import weakref
 
 import numpy as np
@@ -97,7 +102,38 @@ def _empty(k):
     return np.zeros(0, dtype=np.int64), np.zeros((0, k), dtype=np.int64), np.zeros((0, k), dtype=np.float32)
 
 
+_ON_DEVICE = False
+
+
+@contextlib.contextmanager
+def device_lists():
+    """Internal: while active, `fused` and `pairs` return their device tensors (item rows, scores) instead of host node ids."""
+    global _ON_DEVICE
+    saved, _ON_DEVICE = _ON_DEVICE, True
+    try:
+        yield
+    finally:
+        _ON_DEVICE = saved
+
+
+def evaluate_ranking(model, trainset, test_ratings, ks, users=None, exclude_seen=True):
+    """model.recommend at k = max(ks) with the lists kept on the device, then utilities.metrics.full_ranking_metrics_device: the
+    dict of `full_ranking_metrics(*model.recommend(...)[:2], test_ratings, ks)` without the lists (or a Python loop) on the host."""
+    from deep_cbrs_amar_renaissance_amd.utilities.metrics import full_ranking_metrics, full_ranking_metrics_device
+    ks = [int(k) for k in ks]
+    if not ks:
+        raise ValueError("evaluate_ranking needs at least one k")
+    n_users, n_items = _sizes(trainset)
+    with device_lists():
+        u, items, _ = model.recommend(trainset, k=check_k(max(ks)), users=users, exclude_seen=exclude_seen)
+    if len(u) == 0:
+        return full_ranking_metrics(u, items, test_ratings, ks)
+    return full_ranking_metrics_device(None if users is None else u, items.contiguous(), test_ratings, ks, n_users, n_items)
+
+
 def _finish(users, items, scores, n_users):
+    if _ON_DEVICE:
+        return users, items, scores
     items = items.cpu().numpy().astype(np.int64)
     items = np.where(items >= 0, items + n_users, -1)
     return users, items, scores.cpu().numpy().astype(np.float32)

@@ -1436,11 +1436,119 @@ class _History:
         for name, value in self.trainer.pop_metrics().items():
             self.values[name].append(value)
         if verbose:
-            print("Epoch {}/{} - ".format(epoch + 1, epochs) + " - ".join("{}: {:.4f}".format(k, v[-1]) for k, v in self.values.items()))
+            print("Epoch {}/{} - ".format(epoch + 1, epochs) + " - ".join("{}: {:.4f}".format(k, v[-1]) for k, v in self.values.items() if not k.startswith('val_')))
 
 
-def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
-    """Keras-style ``fit`` over a batch Sequence: ``epochs`` passes, ``on_epoch_end`` reshuffles (datasets.py:205-213)."""
+class _FitHooks:
+    """What fit() does around the step when it is asked to: Keras-style callbacks (duck-typed: on_train_begin / on_train_end(logs),
+    on_epoch_begin / on_epoch_end(epoch, logs), on_train_batch_begin / on_train_batch_end(batch, logs), set_model(model)), a validation
+    pass every `validation_freq`-th epoch (`validation_data`: anything evaluate() accepts -> val_loss, val_<metric>;
+    `validation_ranking`: {'trainset', 'ratings', 'ks', 'users'} -> val_precision_at_<k>, val_recall_at_<k>, val_ndcg_at_<k>,
+    val_hit_at_<k> through evaluate_ranking) and `model.stop_training`.
+
+    One `logs` dict per epoch goes to every callback in list order: the epoch's training entries, then its val_* entries; a callback
+    may add keys for the callbacks after it.  The batch hooks are called only on callbacks that define them (a method inherited from
+    utilities.keras.Callback does not count) and receive logs = {}: the batch loss stays on the device until the epoch ends, and
+    reading it would put a host synchronisation into every replayed batch.
+
+    Validation runs predict() / recommend() on the weights the epoch left: it reads neither the training Sequence nor the dropout /
+    BPR step counters, leaves the model's hoist state as it found it, and the next batch replays the captured training graph."""
+
+    _HOOKS = ('on_train_begin', 'on_train_end', 'on_epoch_begin', 'on_epoch_end', 'on_train_batch_begin', 'on_train_batch_end')
+
+    def __init__(self, model, history, callbacks, validation_data, validation_freq, validation_ranking):
+        from deep_cbrs_amar_renaissance_amd.utilities.keras import Callback
+        self.model, self.history = model, history
+        self.callbacks = list(callbacks or [])
+        self.validation_data = validation_data
+        self.freq = int(validation_freq)
+        if self.freq < 1:
+            raise ValueError("validation_freq must be a positive integer (got {!r})".format(validation_freq))
+        self.ranking = None
+        if validation_ranking is not None:
+            if not hasattr(model, 'recommend'):
+                raise NotImplementedError("{} has no recommend(): validation_ranking cannot rank with it".format(type(model).__name__))
+            missing = [key for key in ('trainset', 'ratings', 'ks') if key not in validation_ranking]
+            if missing:
+                raise ValueError("validation_ranking needs the keys 'trainset', 'ratings' and 'ks' (missing {})".format(missing))
+            self.ranking = dict(validation_ranking)
+        names = history.trainer._compiled()[2]
+        self.val_names = ['loss'] + (['accuracy'] if all(name == 'accuracy' for name in names) else list(names))   # what evaluate() returns
+        self.hooks = {}
+        for hook in self._HOOKS:
+            self.hooks[hook] = [getattr(cb, hook) for cb in self.callbacks
+                                if callable(getattr(cb, hook, None)) and getattr(type(cb), hook, None) is not getattr(Callback, hook)]
+        self.batch_begin, self.batch_end = self.hooks['on_train_batch_begin'], self.hooks['on_train_batch_end']
+        for cb in self.callbacks:
+            if callable(getattr(cb, 'set_model', None)):
+                cb.set_model(model)
+
+    def train_begin(self):
+        for hook in self.hooks['on_train_begin']:
+            hook({})
+
+    def train_end(self):
+        logs = {name: values[-1] for name, values in self.history.values.items() if values}
+        for hook in self.hooks['on_train_end']:
+            hook(logs)
+
+    def epoch_begin(self, epoch):
+        for hook in self.hooks['on_epoch_begin']:
+            hook(epoch, {})
+
+    def on_batch_begin(self, batch):
+        for hook in self.batch_begin:
+            hook(batch, {})
+
+    def on_batch_end(self, batch):
+        for hook in self.batch_end:
+            hook(batch, {})
+
+    def _validate(self):
+        out = {}
+        if self.validation_data is not None:
+            values = self.model.evaluate(self.validation_data)
+            out.update(('val_' + name, float(value)) for name, value in zip(self.val_names, values))
+        if self.ranking is not None:
+            r = self.ranking
+            found = self.model.evaluate_ranking(r['trainset'], r['ratings'], r['ks'], users=r.get('users'),
+                                                exclude_seen=r.get('exclude_seen', True))
+            out.update(('val_' + name, float(value)) for name, value in found.items() if not name.startswith('users_'))
+        return out
+
+    def epoch_end(self, epoch, verbose):
+        """After history.epoch(): validate when due, hand the epoch's logs to the callbacks; True when training is to stop."""
+        values = self.history.values
+        logs = {name: v[-1] for name, v in values.items() if v and not name.startswith('val_')}
+        if (self.validation_data is not None or self.ranking is not None) and (epoch + 1) % self.freq == 0:
+            found = self._validate()
+            for name, value in found.items():
+                values.setdefault(name, []).append(value)
+            logs.update(found)
+            if verbose:
+                print("    " + " - ".join("{}: {:.4f}".format(k, v) for k, v in found.items()))
+        for hook in self.hooks['on_epoch_end']:
+            hook(epoch, logs)
+        return bool(getattr(self.model, 'stop_training', False))
+
+
+def _fit_hooks(model, history, callbacks, validation_data, validation_freq, validation_ranking):
+    """The _FitHooks of a fit() call, or None when it has neither callbacks nor validation (the loop then runs as it always did)."""
+    if not callbacks and validation_data is None and validation_ranking is None:
+        return None
+    return _FitHooks(model, history, callbacks, validation_data, validation_freq, validation_ranking)
+
+
+def fit(model, sequence, epochs=1, callbacks=None, verbose=True, validation_data=None, validation_freq=1, validation_ranking=None,
+        initial_epoch=0, **kwargs):
+    """Keras-style ``fit`` over a batch Sequence: epochs ``initial_epoch`` .. ``epochs - 1``, ``on_epoch_end`` reshuffles
+    (datasets.py:205-213).  ``callbacks``, ``validation_data``, ``validation_freq``, ``validation_ranking``: _FitHooks; only validated
+    epochs add a val_* entry to the returned history, as in Keras.  ``model.stop_training = True`` set by a callback's on_epoch_end
+    ends training after that epoch."""
+    if validation_ranking is not None and not hasattr(model, 'recommend'):
+        raise NotImplementedError("{} has no recommend(): validation_ranking cannot rank with it".format(type(model).__name__))
+    model.stop_training = False
+    val = (callbacks, validation_data, validation_freq, validation_ranking)
     spec = OptimizerSpec(getattr(model, 'optimizer', None))
     hp = {'optimizer': spec}
     if not hasattr(model, 'gnn'):                              # BasicRS / HybridCBRS on pre-computed rows: head-only training
@@ -1468,9 +1576,16 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
                 trainer._table_sources = tables
         use_graph = tables is not None and os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
         history = _History(trainer)
-        for epoch in range(int(epochs)):
+        hooks = _fit_hooks(model, history, *val)
+        if hooks is not None:
+            hooks.train_begin()
+        for epoch in range(int(initial_epoch), int(epochs)):
             total, count = 0.0, 0
+            if hooks is not None:
+                hooks.epoch_begin(epoch)
             for b in range(len(sequence)):
+                if hooks is not None and hooks.batch_begin:
+                    hooks.on_batch_begin(b)
                 if tables is not None:
                     r = sequence._batch_ratings(b)
                     u, i, y = r[:, 0], r[:, 1], r[:, 2]
@@ -1482,12 +1597,19 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
                     blocks, y = sequence[b]
                     total += trainer.train_batch(blocks, y) * len(y)
                 count += len(y)
+                if hooks is not None and hooks.batch_end:
+                    hooks.on_batch_end(b)
             if use_graph:
                 total = trainer.pop_loss_sum()
                 trainer.touch_parameters()
             history.epoch(total / max(count, 1), epoch, epochs, verbose)
+            stop = hooks is not None and hooks.epoch_end(epoch, verbose)
             if hasattr(sequence, 'on_epoch_end'):
                 sequence.on_epoch_end()
+            if stop:
+                break
+        if hooks is not None:
+            hooks.train_end()
         return history.values
     # Hybrid batches of the reference's own Sequence (datasets.py:95-123 here, 112-115 there) carry, besides the ids, the BERT rows of the
     # batch's users and items — gathered on the host from ONE table indexed by node id and uploaded every batch (6 MB at batch 1 024).
@@ -1495,7 +1617,7 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
     # (AMAR_RESIDENT_BERT=0: the batches as they come).  A replayed hybrid batch at ml1m(s=1): 0.41 against 0.71 ms.
     from deep_cbrs_amar_renaissance_amd.data.datasets import UserItemGraphPosNegSample
     if isinstance(sequence, UserItemGraphPosNegSample):
-        return _fit_sampled(model, sequence, epochs, verbose, hp)
+        return _fit_sampled(model, sequence, epochs, verbose, hp, val, initial_epoch)
     ids_only = model.resident_ids(sequence) if hasattr(model, 'resident_ids') else None
     trainer = _cached_trainer(model, spec)
     if trainer is None:
@@ -1507,9 +1629,16 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
     use_graph = os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
     same_body = not use_graph and trainer.dropout_step is not None      # a model that drops: the replayed body, run eagerly (same bits)
     history = _History(trainer)
-    for epoch in range(int(epochs)):
+    hooks = _fit_hooks(model, history, *val)
+    if hooks is not None:
+        hooks.train_begin()
+    for epoch in range(int(initial_epoch), int(epochs)):
         total, count = 0.0, 0
+        if hooks is not None:
+            hooks.epoch_begin(epoch)
         for b in range(len(sequence)):
+            if hooks is not None and hooks.batch_begin:
+                hooks.on_batch_begin(b)
             inputs, y = (ids_only if ids_only is not None else sequence)[b]
             u, i = inputs[0], inputs[1]
             bert = (inputs[2], inputs[3]) if len(inputs) >= 4 else None     # hybrid batches carry the BERT blocks (datasets.py:112-115)
@@ -1518,16 +1647,23 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, **kwargs):
             else:
                 total += trainer.train_batch(u, i, y, bert=bert) * len(y)
             count += len(y)
+            if hooks is not None and hooks.batch_end:
+                hooks.on_batch_end(b)
         if use_graph or same_body:
             total = trainer.pop_loss_sum()
             trainer.touch_parameters()
         history.epoch(total / max(count, 1), epoch, epochs, verbose)
+        stop = hooks is not None and hooks.epoch_end(epoch, verbose)
         if hasattr(sequence, 'on_epoch_end'):
             sequence.on_epoch_end()
+        if stop:
+            break
+    if hooks is not None:
+        hooks.train_end()
     return history.values
 
 
-def _fit_sampled(model, sequence, epochs, verbose, hp):
+def _fit_sampled(model, sequence, epochs, verbose, hp, val=(None, None, 1, None), initial_epoch=0):
     """fit() on the BPR sample Sequence: its lists go to the device once and every batch is drawn there (amar_bpr_sample_i32), inside
     the replayed training graph (AMAR_TRAIN_GRAPH=0: the same steps eagerly, the same ids).  len(sequence) steps per epoch; the host
     stream of __getitem__ is not read."""
@@ -1537,12 +1673,25 @@ def _fit_sampled(model, sequence, epochs, verbose, hp):
     sampler = trainer.sampler_for(sequence)
     use_graph = os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
     history = _History(trainer)
-    for epoch in range(int(epochs)):
+    hooks = _fit_hooks(model, history, *val)
+    if hooks is not None:
+        hooks.train_begin()
+    for epoch in range(int(initial_epoch), int(epochs)):
         count = 0
-        for _ in range(len(sequence)):
+        if hooks is not None:
+            hooks.epoch_begin(epoch)
+        for b in range(len(sequence)):
+            if hooks is not None and hooks.batch_begin:
+                hooks.on_batch_begin(b)
             trainer.train_sampled(sampler, graph=use_graph)
             count += 2 * sampler.h
+            if hooks is not None and hooks.batch_end:
+                hooks.on_batch_end(b)
         total = trainer.pop_loss_sum()
         trainer.touch_parameters()
         history.epoch(total / max(count, 1), epoch, epochs, verbose)
+        if hooks is not None and hooks.epoch_end(epoch, verbose):
+            break
+    if hooks is not None:
+        hooks.train_end()
     return history.values

@@ -89,8 +89,11 @@ class RunLog:
     def log_params(self, params):
         self._write({'event': 'params', 'params': params})
 
-    def log_metrics(self, metrics):
-        self._write({'event': 'metrics', 'metrics': metrics})
+    def log_metrics(self, metrics, step=None):
+        record = {'event': 'metrics', 'metrics': metrics}
+        if step is not None:                                 # (mlflow.log_metrics(metrics, step=epoch): the per-epoch entries of fit())
+            record['step'] = int(step)
+        self._write(record)
 
     def end_run(self):
         if self.run_dir is not None:

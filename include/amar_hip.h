@@ -1024,6 +1024,28 @@ int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const floa
                        int32_t k, int32_t n_slices, int32_t *workspace_items, float *workspace_scores,
                        int32_t *out_items, float *out_scores, amar_stream_t stream);
 
+/* Full-ranking metrics of top-K lists that are already on the device (utilities/metrics.py:full_ranking_metrics, restated):
+ * lists [m, K] holds item ROWS best first, padded with -1 (what amar_recommend_f32 / amar_topk_segmented_f32 write); row j
+ * belongs to user users[j] (j itself when users == NULL, m == n_users).  The relevant items are a CSR over users:
+ * rel_ptr[n_users+1], rel_items sorted ascending and de-duplicated per user.  A user with an empty relevant segment (or an id
+ * outside 0..n_users-1) is skipped and counted; a padded rank is a miss.  For every other user and every cutoff k = ks[q], with
+ * hits = relevant items among the first k ranks:
+ *     precision = hits / k,  recall = hits / |rel|,  hit = [hits > 0],
+ *     ndcg = sum_{hit at rank r <= k} 1 / log2(r + 1)  /  cum_disc[min(|rel|, k)]
+ * in float64.  out_sums [nk, 4] (device) receives the SUMS over the evaluated users in the order precision, recall, ndcg, hit;
+ * out_counts [2] (device, int64) receives (evaluated, skipped): the caller divides.
+ * ks (nk cutoffs) and cum_disc (K + 1 entries: cum_disc[0] = 0, cum_disc[j] = sum_{r <= j} 1 / log2(r + 1)) are HOST arrays.
+ * workspace: AMAR_RANK_METRICS_MAX_BLOCKS * AMAR_RANK_METRICS_CELLS doubles of device scratch (any contents).
+ * Two launches, no atomics: users are summed in an order fixed by m alone, so a call returns the same bits on every run.
+ * K > 64 or nk > AMAR_RANK_METRICS_MAX_KS: AMAR_EUNSUPPORTED; K < 1, nk < 1, a k outside [1, K], a NULL pointer (lists may be
+ * NULL when m == 0), users == NULL with m != n_users, negative sizes: AMAR_EINVAL. */
+#define AMAR_RANK_METRICS_MAX_KS     8
+#define AMAR_RANK_METRICS_MAX_BLOCKS 1024
+#define AMAR_RANK_METRICS_CELLS      (4 * AMAR_RANK_METRICS_MAX_KS + 2)
+int amar_rank_metrics_f64(const int32_t *lists, int64_t m, int32_t K, const int32_t *users, const int32_t *rel_ptr,
+                          const int32_t *rel_items, int32_t n_users, const int32_t *ks, int32_t nk, const double *cum_disc,
+                          double *workspace, double *out_sums, int64_t *out_counts, amar_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
