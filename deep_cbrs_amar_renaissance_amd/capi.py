@@ -112,6 +112,9 @@ SIGNATURES = {
     'amar_optim_advance_f32': (ctypes.c_int, [_P, _I32, _I32, _P, _P]),
     'amar_optim_f32': (ctypes.c_int, [_I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _F32, _P]),
     'amar_optim_multi_f32': (ctypes.c_int, [_I32, _I32, _P, _P, _I32, _I64, _P, _F32, _P, _P]),
+    'amar_lr_rates_f32': (ctypes.c_int, [_P, _P, _I64, _I64, _P, _P]),
+    'amar_adam_advance_lr_f32': (ctypes.c_int, [_P, _P, _P, _F32, _F32, _P]),
+    'amar_optim_advance_lr_f32': (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P]),
     'amar_grad_clip_workspace_floats': (ctypes.c_int64, [_I32, _I64]),
     'amar_grad_clip_f32': (ctypes.c_int, [_I32, _F32, _P, _I32, _I64, _P, _P, _F32, _P, _P]),
     'amar_bpr_grad_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P]),
@@ -1149,6 +1152,87 @@ def optim_multi(rule, flags, hyper, table_dev, n_slots, total_blocks, state, reg
                                        total_blocks, _ptr(state, torch.float32, 'state'), float(reg_scale),
                                        _ptr(loss_acc, torch.float32, 'loss_acc'), _stream())
     _check(code, 'amar_optim_multi_f32')
+
+
+# ---- learning-rate schedules (include/amar_hip.h: AMAR_LR_*) ---------------------------------------------------------------------------
+LR_CONSTANT, LR_EXPONENTIAL, LR_INVERSE_TIME, LR_POLYNOMIAL, LR_COSINE, LR_PIECEWISE = 0, 1, 2, 3, 4, 5
+LR_STAIRCASE, LR_CYCLE = 0x1, 0x2
+LR_MAX_BOUNDARIES, LR_STATE_FLOATS, LR_MAX_STEP = 16, 2, 1 << 24
+LR_KINDS = {'constant': LR_CONSTANT, 'exponential': LR_EXPONENTIAL, 'inverse_time': LR_INVERSE_TIME, 'polynomial': LR_POLYNOMIAL,
+            'cosine': LR_COSINE, 'piecewise': LR_PIECEWISE}
+
+
+class LrSchedule(ctypes.Structure):
+    """include/amar_hip.h: amar_lr_schedule (a host struct; a kind ignores the members it does not use)"""
+    _fields_ = [('kind', ctypes.c_int32), ('flags', ctypes.c_int32)] + \
+               [(name, ctypes.c_float) for name in ('initial_learning_rate', 'decay_steps', 'decay_rate', 'end_learning_rate', 'power', 'alpha')] + \
+               [('n_boundaries', ctypes.c_int32), ('boundaries', ctypes.c_float * LR_MAX_BOUNDARIES),
+                ('values', ctypes.c_float * (LR_MAX_BOUNDARIES + 1))]
+
+
+def lr_schedule(schedule=None):
+    """The amar_lr_schedule of a host schedule: None -> AMAR_LR_CONSTANT (the rate is lr_state[0]); else an object of
+    utilities/schedules.py, or anything whose `device_args()` returns {'kind': a name of LR_KINDS, 'staircase' / 'cycle': bool, the
+    struct's float members by name, 'boundaries', 'values'} — what is left out stays zero."""
+    if schedule is None:
+        return LrSchedule(LR_CONSTANT, 0)
+    args = dict(schedule.device_args())
+    kind = args.pop('kind')
+    if kind not in LR_KINDS:
+        raise ValueError("lr_schedule: no schedule kind '{}': one of {}".format(kind, ', '.join(sorted(LR_KINDS))))
+    flags = (LR_STAIRCASE if args.pop('staircase', False) else 0) | (LR_CYCLE if args.pop('cycle', False) else 0)
+    boundaries, values = list(args.pop('boundaries', ())), list(args.pop('values', ()))
+    if len(boundaries) > LR_MAX_BOUNDARIES:
+        raise ValueError("lr_schedule: at most {} boundaries (got {})".format(LR_MAX_BOUNDARIES, len(boundaries)))
+    if LR_KINDS[kind] == LR_PIECEWISE and len(values) != len(boundaries) + 1:
+        raise ValueError("lr_schedule: a piecewise schedule needs one value more than boundaries")
+    out = LrSchedule(LR_KINDS[kind], flags)
+    for name, value in args.items():
+        if name not in ('initial_learning_rate', 'decay_steps', 'decay_rate', 'end_learning_rate', 'power', 'alpha'):
+            raise ValueError("lr_schedule: amar_lr_schedule has no member '{}'".format(name))
+        setattr(out, name, float(value))
+    out.n_boundaries = len(boundaries)
+    for k, b in enumerate(boundaries):
+        out.boundaries[k] = float(b)
+    for k, v in enumerate(values):
+        out.values[k] = float(v)
+    return out
+
+
+def _lr_state(lr_state, what):
+    if lr_state.numel() != LR_STATE_FLOATS or not lr_state.is_contiguous():
+        raise ValueError("{}: lr_state must be {} contiguous floats (base rate, rate of the last step)".format(what, LR_STATE_FLOATS))
+    return _ptr(lr_state, torch.float32, 'lr_state')
+
+
+def lr_rates(sched, lr_state, first_step, n, out=None):
+    """The rates of the steps first_step .. first_step + n - 1 (zero-based) under `sched` (an LrSchedule), into out[:n] (float32, on the
+    device; allocated when not given).  Returns out."""
+    first_step, n = int(first_step), int(n)
+    if first_step < 0 or n < 0 or first_step + n > LR_MAX_STEP:
+        raise ValueError("lr_rates: steps {} .. {} are outside 0 .. 2^24".format(first_step, first_step + n))
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=lr_state.device)
+    if out.numel() < n or not out.is_contiguous():
+        raise ValueError("lr_rates: out must hold {} contiguous floats".format(n))
+    _check(load().amar_lr_rates_f32(ctypes.byref(sched), _lr_state(lr_state, 'lr_rates'), first_step, n, _ptr(out, torch.float32, 'out'),
+                                    _stream()), 'amar_lr_rates_f32')
+    return out
+
+
+def adam_advance_lr(state, sched, lr_state, beta_1, beta_2):
+    if state.numel() != 2 or not state.is_contiguous():
+        raise ValueError("adam_advance_lr: state must be 2 contiguous floats (t, lr_t)")
+    _check(load().amar_adam_advance_lr_f32(_ptr(state, torch.float32, 'state'), ctypes.byref(sched), _lr_state(lr_state, 'adam_advance_lr'),
+                                           float(beta_1), float(beta_2), _stream()), 'amar_adam_advance_lr_f32')
+
+
+def optim_advance_lr(state, rule, flags, hyper, sched, lr_state):
+    if state.numel() != OPTIM_STATE_FLOATS or not state.is_contiguous():
+        raise ValueError("optim_advance_lr: state must be {} contiguous floats".format(OPTIM_STATE_FLOATS))
+    _check(load().amar_optim_advance_lr_f32(_ptr(state, torch.float32, 'state'), int(rule), int(flags), ctypes.byref(hyper),
+                                            ctypes.byref(sched), _lr_state(lr_state, 'optim_advance_lr'), _stream()),
+           'amar_optim_advance_lr_f32')
 
 
 # ---- gradient clipping (include/amar_hip.h: AMAR_CLIP_*) -------------------------------------------------------------------------------

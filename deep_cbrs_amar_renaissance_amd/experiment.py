@@ -37,9 +37,10 @@ from deep_cbrs_amar_renaissance_amd.data.datasets import holdout_split
 from deep_cbrs_amar_renaissance_amd.models.basic import BasicRS, BasicGNN, BasicKnowledgeGCN, BasicTSGNN, BasicTWGNN
 from deep_cbrs_amar_renaissance_amd.models.hybrid import HybridCBRS, HybridBertGNN
 from deep_cbrs_amar_renaissance_amd.utilities import losses
-from deep_cbrs_amar_renaissance_amd.utilities.keras import Callback, EarlyStopping, get_total_parameters
+from deep_cbrs_amar_renaissance_amd.utilities.keras import Callback, EarlyStopping, ReduceLROnPlateau, get_total_parameters
 from deep_cbrs_amar_renaissance_amd.utilities.metrics import full_ranking_metrics, recommendations_frame, resolve_compiled, top_k_predictions, \
     top_k_metrics
+from deep_cbrs_amar_renaissance_amd.utilities.schedules import resolve as resolve_learning_rate
 from deep_cbrs_amar_renaissance_amd.utilities.utils import \
     get_experiment_logger, nested_dict_update, make_grid, mlflow_linearize, setup_mlflow
 
@@ -104,67 +105,85 @@ def _store_clip(optimizer, clipnorm, clipvalue, global_clipnorm):
             setattr(optimizer, name, value)
 
 
+def _store_rate(optimizer, learning_rate, decay):
+    """`learning_rate` as a number or a schedule (utilities/schedules.py:resolve — an object, an experiment file's mapping {name: ...} or
+    Keras' {class_name, config}) and Keras 2's `decay`, the rate lr / (1 + decay * step), kept as an attribute only where it is set.
+    Refused here, where the optimizer is built, by training.OptimizerSpec's rule: what is no rate, a negative decay, a decay together
+    with a schedule.  OptimizerSpec turns the two into the schedule the device follows."""
+    from deep_cbrs_amar_renaissance_amd.training import OptimizerSpec
+    optimizer.learning_rate = resolve_learning_rate(learning_rate)
+    if decay is not None:
+        optimizer.decay = decay
+    OptimizerSpec._checked_schedule(optimizer.learning_rate, decay)
+
+
 class Adam:
     """keras.optimizers.Adam's constructor (config.yaml:52-56); amsgrad=True selects the AMSGrad rule.  The optimizer classes only carry
     their rule, hyper-parameters and gradient clip (clipnorm / clipvalue / global_clipnorm, named in every signature so that
     Experimenter.build_optimizer's filter lets them through; training.OptimizerSpec validates them): training.py keeps the state and runs
     the clip and the update on the device."""
     rule = 'Adam'
-    clipnorm = clipvalue = global_clipnorm = None
+    clipnorm = clipvalue = global_clipnorm = decay = None
 
     def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False,
-                 clipnorm=None, clipvalue=None, global_clipnorm=None, **kwargs):
+                 clipnorm=None, clipvalue=None, global_clipnorm=None, decay=None, **kwargs):
         self.learning_rate, self.beta_1, self.beta_2, self.epsilon, self.amsgrad = learning_rate, beta_1, beta_2, epsilon, bool(amsgrad)
         _store_clip(self, clipnorm, clipvalue, global_clipnorm)
+        _store_rate(self, learning_rate, decay)
         if self.amsgrad:
             self.rule = 'AMSGrad'
 
 
 class SGD:
     rule = 'SGD'
-    clipnorm = clipvalue = global_clipnorm = None
+    clipnorm = clipvalue = global_clipnorm = decay = None
 
-    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None, clipvalue=None, global_clipnorm=None, **kwargs):
+    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None, clipvalue=None, global_clipnorm=None, decay=None, **kwargs):
         self.learning_rate, self.momentum, self.nesterov = learning_rate, momentum, bool(nesterov)
         _store_clip(self, clipnorm, clipvalue, global_clipnorm)
+        _store_rate(self, learning_rate, decay)
 
 
 class RMSprop:
     rule = 'RMSprop'
-    clipnorm = clipvalue = global_clipnorm = None
+    clipnorm = clipvalue = global_clipnorm = decay = None
 
     def __init__(self, learning_rate=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False,
-                 clipnorm=None, clipvalue=None, global_clipnorm=None, **kwargs):
+                 clipnorm=None, clipvalue=None, global_clipnorm=None, decay=None, **kwargs):
         self.learning_rate, self.rho, self.momentum, self.epsilon, self.centered = learning_rate, rho, momentum, epsilon, bool(centered)
         _store_clip(self, clipnorm, clipvalue, global_clipnorm)
+        _store_rate(self, learning_rate, decay)
 
 
 class Adagrad:
     rule = 'Adagrad'
-    clipnorm = clipvalue = global_clipnorm = None
+    clipnorm = clipvalue = global_clipnorm = decay = None
 
     def __init__(self, learning_rate=0.001, initial_accumulator_value=0.1, epsilon=1e-7,
-                 clipnorm=None, clipvalue=None, global_clipnorm=None, **kwargs):
+                 clipnorm=None, clipvalue=None, global_clipnorm=None, decay=None, **kwargs):
         self.learning_rate, self.initial_accumulator_value, self.epsilon = learning_rate, initial_accumulator_value, epsilon
         _store_clip(self, clipnorm, clipvalue, global_clipnorm)
+        _store_rate(self, learning_rate, decay)
 
 
 class Adamax:
     rule = 'Adamax'
-    clipnorm = clipvalue = global_clipnorm = None
+    clipnorm = clipvalue = global_clipnorm = decay = None
 
-    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, clipvalue=None, global_clipnorm=None, **kwargs):
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, clipvalue=None, global_clipnorm=None, decay=None, **kwargs):
         self.learning_rate, self.beta_1, self.beta_2, self.epsilon = learning_rate, beta_1, beta_2, epsilon
         _store_clip(self, clipnorm, clipvalue, global_clipnorm)
+        _store_rate(self, learning_rate, decay)
 
 
 class Nadam:
     rule = 'Nadam'
-    clipnorm = clipvalue = global_clipnorm = None
+    clipnorm = clipvalue = global_clipnorm = decay = None
 
-    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, clipvalue=None, global_clipnorm=None, **kwargs):
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, clipvalue=None, global_clipnorm=None, decay=None, **kwargs):
         self.learning_rate, self.beta_1, self.beta_2, self.epsilon = learning_rate, beta_1, beta_2, epsilon
         _store_clip(self, clipnorm, clipvalue, global_clipnorm)
+        _store_rate(self, learning_rate, decay)
 
 
 OPTIMIZERS = {cls.__name__: cls for cls in (Adam, SGD, RMSprop, Adagrad, Adamax, Nadam)}
@@ -257,7 +276,8 @@ class Experimenter:
         self.trainset, self.testset = self.load_function(**kwargs)
 
     def validation_fit_args(self):
-        """fit()'s validation arguments from parameters.validation ({fraction, freq, ranking_ks, early_stopping}); {} without the key."""
+        """fit()'s validation arguments from parameters.validation ({fraction, freq, ranking_ks, early_stopping, reduce_lr}); {} without
+        the key."""
         validation = self.config.parameters.get('validation')
         if not validation:
             return {}
@@ -266,7 +286,9 @@ class Experimenter:
         if validation.get('early_stopping'):
             stopping = EarlyStopping(**dict(validation.get('early_stopping')))
             callbacks.append(stopping)
-        callbacks.append(RunLogCallback(self.run_log, stopping))
+        if validation.get('reduce_lr'):                              # {monitor, factor, patience, cooldown, min_lr, min_delta}
+            callbacks.append(ReduceLROnPlateau(**dict(validation.get('reduce_lr'))))
+        callbacks.append(RunLogCallback(self.run_log, stopping))     # (last: it logs what the others added, `lr` among it)
         args = {'validation_data': self.valset, 'validation_freq': int(validation.get('freq', 1)), 'callbacks': callbacks}
         if validation.get('ranking_ks'):
             args['validation_ranking'] = {'trainset': self.trainset, 'ratings': self.valset.ratings,

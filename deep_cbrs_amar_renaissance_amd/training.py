@@ -41,6 +41,7 @@ from deep_cbrs_amar_renaissance_amd.layers.lightgcn_conv import LightGCNConv
 from deep_cbrs_amar_renaissance_amd.utilities.losses import BPR, loss_kind
 from deep_cbrs_amar_renaissance_amd.utilities.math import spmm_kind
 from deep_cbrs_amar_renaissance_amd.utilities.metrics import metric_values, resolve_compiled
+from deep_cbrs_amar_renaissance_amd.utilities.schedules import InverseTimeDecay, LearningRateSchedule, resolve as resolve_learning_rate
 
 
 def _spmm(a, x, out):
@@ -732,7 +733,12 @@ class OptimizerSpec:
     """The update rule and hyper-parameters a trainer runs: read from an optimizer object (experiment.py: `rule` + Keras' attribute
     names; an object without a rule name means Adam) and / or keyword arguments, which win — the gradient clip (clipvalue, clipnorm or
     global_clipnorm: `clip` = (name, value) or None) in the same way.  `key` identifies it: two optimizers with equal keys train alike,
-    so a cached trainer (and its state) is reused only for an equal key."""
+    so a cached trainer (and its state) is reused only for an equal key.
+
+    `learning_rate` is whatever utilities/schedules.py:resolve takes: a number, or a schedule (object or mapping) that the device
+    evaluates at the step counter — `schedule` then holds it, its key is part of `key` and values['learning_rate'] is its rate at
+    step 0.  `decay` (Keras 2's optimizer argument) is InverseTimeDecay(learning_rate, 1, decay).  A plain number without decay:
+    `schedule` is None and the key is what it was before schedules existed."""
 
     def __init__(self, optimizer=None, rule=None, **hyper):
         self.rule = rule or getattr(optimizer, 'rule', None) or 'Adam'
@@ -740,12 +746,17 @@ class OptimizerSpec:
             raise ValueError("no update rule '{}': choose one of {}".format(self.rule, ', '.join(sorted(OPTIMIZER_RULES))))
         code, defaults = OPTIMIZER_RULES[self.rule]
         clips = {k: hyper.pop(k) if k in hyper else getattr(optimizer, k, None) for k in CLIP_MODES}
+        decay = hyper.pop('decay') if 'decay' in hyper else getattr(optimizer, 'decay', None)
         unknown = set(hyper) - set(defaults)
         if unknown:
             raise TypeError("{} has no hyper-parameter {}".format(self.rule, ', '.join(sorted(unknown))))
-        self.values = {k: type(d)(hyper[k] if k in hyper else getattr(optimizer, k, d)) for k, d in defaults.items()}
+        given = {k: hyper[k] if k in hyper else getattr(optimizer, k, d) for k, d in defaults.items()}
+        self.schedule = self._checked_schedule(resolve_learning_rate(given['learning_rate']), decay)
+        if self.schedule is not None:
+            given['learning_rate'] = float(self.schedule(0))
+        self.values = {k: type(d)(given[k]) for k, d in defaults.items()}
         self.clip = self._checked_clip(clips)
-        self.key = (self.rule, tuple(sorted(self.values.items())), self.clip)
+        self.key = (self.rule, tuple(sorted(self.values.items())), self.clip) + ((self.schedule.key,) if self.schedule is not None else ())
         self.adam = code is None
         if not self.adam:
             self.code = getattr(capi, code)
@@ -754,6 +765,18 @@ class OptimizerSpec:
             self.n_arrays = capi.optim_state_arrays(self.code, self.flags, self.values.get('momentum', 0.0))
         else:
             self.n_arrays = 2
+
+    @staticmethod
+    def _checked_schedule(rate, decay):
+        """The schedule the device follows, or None for a fixed rate.  decay: None or 0 means off (Keras 2's default)."""
+        decay = 0.0 if decay is None else float(decay)
+        if not decay >= 0.0:                                         # (NaN included)
+            raise ValueError("decay must not be negative (got {})".format(decay))
+        if isinstance(rate, LearningRateSchedule):
+            if decay:
+                raise ValueError("decay together with a learning-rate schedule is refused: the schedule already says how the rate decays")
+            return rate
+        return InverseTimeDecay(rate, 1, decay) if decay else None
 
     @staticmethod
     def _checked_clip(clips):
@@ -828,8 +851,70 @@ class Trainer:
             self.v = {p: a[1] for p, a in self.opt_arrays.items()}
         else:
             self._opt_state = torch.zeros(capi.OPTIM_STATE_FLOATS, dtype=torch.float32, device=self.device)
+        self.capture_count = 0                                       # hipGraph captures so far (a set learning rate must not add one)
+        self._lr_state = None                                        # static rate: the launches are those of a trainer without schedules
+        if self.spec.schedule is not None:
+            self._make_rate_dynamic()
 
-    dropout_key, dropout_step = (), None                             # (HeadTrainer: the heads have no dropout, as in the reference)
+    # -- the learning rate -----------------------------------------------------------------------------------------
+    @property
+    def dynamic_rate(self):
+        """False: the rate is an argument of the advance launch, baked into the captured graphs.  True (a schedule, a decay, or a rate
+        that was set): it lives in `_lr_state` on the device and the advance launch evaluates it there."""
+        return self._lr_state is not None
+
+    def _make_rate_dynamic(self):
+        """Static -> dynamic, once: the device rate state (base rate, rate of the last step) starts at the compiled rate, and whatever
+        was captured with the rate baked in is dropped (every shape starts over with its eager batch).  Optimizer state and t stay."""
+        if self._lr_state is not None:
+            return
+        base = self.spec.values['learning_rate']
+        self._lr_sched = capi.lr_schedule(self.spec.schedule)
+        self._lr_base = float(np.float32(base))
+        self._lr_state = torch.full((capi.LR_STATE_FLOATS,), base, dtype=torch.float32, device=self.device)
+        self._lr_host = torch.zeros(capi.LR_STATE_FLOATS, dtype=torch.float32).pin_memory()
+        self._lr_read = None
+        self._init_graph_state()
+        self._graphs.clear()
+        self._seen.clear()
+        self._eager_sampled, self._eager_batches = {}, {}
+
+    def set_learning_rate(self, value):
+        """A new base rate from the next batch on: after the first call (which makes the rate dynamic) one write of _lr_state[0]."""
+        if self.spec.schedule is not None:
+            raise ValueError("the optimizer follows a learning-rate schedule ({!r}): its rate cannot be set (as in Keras)".format(self.spec.schedule))
+        value = float(value)
+        if not (value >= 0.0 and np.isfinite(np.float32(value))):
+            raise ValueError("the learning rate must be a finite, non-negative number (got {})".format(value))
+        self._make_rate_dynamic()
+        self._lr_base = float(np.float32(value))
+        self._lr_state[:1].fill_(value)
+
+    def get_learning_rate(self):
+        """The rate the next batch trains with, as the float32 the device holds: the base rate, or the schedule at the step count."""
+        if self.spec.schedule is not None:
+            return float(self.spec.schedule(self.t))
+        return self._lr_base if self._lr_state is not None else float(np.float32(self.spec.values['learning_rate']))
+
+    def pop_learning_rate(self):
+        """The rate the last batch trained with (_lr_state[1]); after `pop_loss_sum` it has come over in that call's synchronisation."""
+        value, self._lr_read = self._lr_read, None
+        return float(self._lr_state[1].item()) if value is None else value
+
+    def _advance_state(self):
+        """The one-thread launch that opens an optimizer step: t + 1 and the step's scalars, under a dynamic rate also the rate."""
+        spec = self.spec
+        if self._lr_state is None:
+            if spec.adam:
+                capi.adam_advance(self._adam_state, self.lr, self.b1, self.b2)
+            else:
+                capi.optim_advance(self._opt_state, spec.code, spec.flags, spec.hyper)
+        elif spec.adam:
+            capi.adam_advance_lr(self._adam_state, self._lr_sched, self._lr_state, self.b1, self.b2)
+        else:
+            capi.optim_advance_lr(self._opt_state, spec.code, spec.flags, spec.hyper, self._lr_sched, self._lr_state)
+
+    dropout_key, dropout_step = (), None                            # (HeadTrainer: the heads have no dropout, as in the reference)
 
     def _init_dropout(self):
         """Training-time dropout: where a stack rate or a GAT attention rate is set, one key (engine.next_dropout_seed:
@@ -996,10 +1081,7 @@ class Trainer:
             for t in tapes:
                 t.defer_reduce = False
         spec = self.spec
-        if spec.adam:
-            capi.adam_advance(self._adam_state, self.lr, self.b1, self.b2)
-        else:
-            capi.optim_advance(self._opt_state, spec.code, spec.flags, spec.hyper)
+        self._advance_state()
         # one launch updates every parameter (a table of slots, uploaded by a captured copy from pinned memory: the
         # gradient buffers of this graph have fixed addresses) and adds the regularisation loss; one more adds the data loss
         flat = [(prm.data.view(-1), capi.flat_gradient(grads[prm]), self._l2(prm)) for prm in self.params]
@@ -1098,6 +1180,7 @@ class Trainer:
                     with torch.no_grad():
                         self._graph_body()
                 g['graph'], _ = capture_graph(body)
+                self.capture_count += 1
                 g['compiled'] = self._loss_spec()
                 self._upload_slots(g)                                # the slot tables of this graph (fixed addresses): once, not per replay
                 self._graphs[key] = g
@@ -1181,6 +1264,7 @@ class Trainer:
                         self._graph_body()
                 self._sync_step()
                 g['graph'], _ = capture_graph(body)
+                self.capture_count += 1
                 g['compiled'] = self._loss_spec()
                 self._upload_slots(g)
                 self._graphs[key] = g
@@ -1228,7 +1312,11 @@ class Trainer:
         block = getattr(self, '_counters', None)
         if block is not None:                                        # the metric counters come over under the same synchronisation
             self._counters_host.copy_(block, non_blocking=True)
+        if self._lr_state is not None:                               # ... and so does the rate of the last step
+            self._lr_host.copy_(self._lr_state, non_blocking=True)
         total = self._eager_loss + float(self._loss_sum.item())
+        if self._lr_state is not None:
+            self._lr_read = float(self._lr_host[1])
         self._eager_loss = 0.0
         self._loss_sum.zero_()
         if block is not None:
@@ -1301,15 +1389,29 @@ class Trainer:
         return c['g']
 
     def apply_gradients(self, grads):
+        dynamic_adam = self.spec.adam and self._lr_state is not None
+        if dynamic_adam:
+            self._sync_step()                                        # (steps counted on the host before the rate became dynamic)
         self.t += 1
         l2_of = self._l2
         if self.spec.clip:
             with torch.no_grad():
                 grads, l2_of = self._clipped(grads), lambda prm: 0.0
+        if dynamic_adam:
+            # the step size comes from the device state the replayed batches advance (amar_adam_dev_f32 reads it): a rate that a
+            # schedule or a callback moves is one state for both paths
+            with torch.no_grad():
+                self._advance_state()
+                for prm in self.params:
+                    capi.adam_dev(prm.data.view(-1), grads[prm].contiguous().view(-1), self.m[prm].view(-1), self.v[prm].view(-1),
+                                  self._adam_state, self.b1, self.b2, self.eps, l2=l2_of(prm))
+                    prm.add_(0)                                        # bumps the autograd version counter
+            self._dev_t = self.t
+            return
         if not self.spec.adam:
             spec = self.spec
             with torch.no_grad():
-                capi.optim_advance(self._opt_state, spec.code, spec.flags, spec.hyper)
+                self._advance_state()
                 for prm in self.params:
                     capi.optim(spec.code, spec.flags, spec.hyper, prm.data.view(-1), grads[prm].contiguous().view(-1),
                                [a.view(-1) for a in self.opt_arrays[prm]], self._opt_state, l2=l2_of(prm))
@@ -1420,9 +1522,54 @@ def _cached_trainer(model, spec):
     return trainer
 
 
+def _trainer_for(model):
+    """The trainer of the compiled optimizer: the cached one, or a new one where the model can have one already (fit() creates it
+    otherwise, from its first batch)."""
+    spec = OptimizerSpec(getattr(model, 'optimizer', None))
+    trainer = _cached_trainer(model, spec)
+    if trainer is None:
+        if hasattr(model, 'gnn'):
+            trainer = Trainer(model, optimizer=spec)                 # (ValueError for a hybrid head that is not built yet)
+        elif getattr(model, 'built', False):
+            trainer = HeadTrainer(model, optimizer=spec)
+        else:
+            raise ValueError("the model has no trainer yet and cannot have one before its weights are built: call it once, or fit() first")
+        model._trainer = trainer
+    return trainer
+
+
+def get_learning_rate(model):
+    """The learning rate the next batch trains with (float32 as the device holds it): the compiled rate, the rate last set, or the
+    schedule at the trainer's step count."""
+    trainer = _cached_trainer(model, OptimizerSpec(getattr(model, 'optimizer', None)))
+    if trainer is not None:
+        return trainer.get_learning_rate()
+    spec = OptimizerSpec(getattr(model, 'optimizer', None))
+    return float(spec.schedule(0)) if spec.schedule is not None else float(np.float32(spec.values['learning_rate']))
+
+
+def set_learning_rate(model, value):
+    """Train with another rate from the next batch on (`backend.set_value(model.optimizer.lr, value)` of Keras 2's callbacks).  The rate
+    in force is trainer state, like the moments: it holds across fit() calls until the model is compiled with another optimizer.  The
+    first call drops the captured training graphs once; every later one is a write of one float on the device.  ValueError: the
+    optimizer follows a schedule, or the model cannot have a trainer yet."""
+    spec = OptimizerSpec(getattr(model, 'optimizer', None))
+    if spec.schedule is not None:
+        raise ValueError("the optimizer follows a learning-rate schedule ({!r}): its rate cannot be set (as in Keras)".format(spec.schedule))
+    _trainer_for(model).set_learning_rate(value)
+
+
+def make_learning_rate_dynamic(model):
+    """Move the rate into device memory now, at its current value, where it would otherwise move at the first set_learning_rate: a
+    callback that is going to set the rate calls this when training begins, so that the whole fit() reports `lr` and no graph is
+    captured only to be dropped.  Nothing to do under a schedule: the rate is on the device already."""
+    if OptimizerSpec(getattr(model, 'optimizer', None)).schedule is None:
+        _trainer_for(model)._make_rate_dynamic()
+
+
 class _History:
     """fit()'s return value in the making: {'loss': [...], '<metric>': [...]} with the compiled metrics in compile order under Keras'
-    history names.  Resolving them here is where fit() reads the compiled loss and metrics: what compile() refuses is refused again."""
+    history names (and 'lr', the rate of the epoch's last batch, once the rate is dynamic).  Resolving them here is where fit() reads the compiled loss and metrics: what compile() refuses is refused again."""
 
     def __init__(self, trainer):
         self.trainer = trainer
@@ -1435,6 +1582,10 @@ class _History:
         self.values['loss'].append(loss)
         for name, value in self.trainer.pop_metrics().items():
             self.values[name].append(value)
+        if self.trainer.dynamic_rate:                                # the rate of the epoch's last step; a static rate adds no key
+            if 'lr' not in self.values:                              # (set for the first time in mid-fit: the epochs before ran at the compiled rate)
+                self.values['lr'] = [float(np.float32(self.trainer.spec.values['learning_rate']))] * (len(self.values['loss']) - 1)
+            self.values['lr'].append(self.trainer.pop_learning_rate())
         if verbose:
             print("Epoch {}/{} - ".format(epoch + 1, epochs) + " - ".join("{}: {:.4f}".format(k, v[-1]) for k, v in self.values.items() if not k.startswith('val_')))
 

@@ -1,6 +1,7 @@
 """Parameter counting used by the driver — mirrors `/root/reference/src/utilities/keras.py:10-22` — and the callbacks of
-``fit(callbacks=[...])``: `Callback` (no-op hooks), `EarlyStopping` and `ModelCheckpoint` after Keras 2's classes of the same names.
-ReduceLROnPlateau and the like are not offered: the learning rate is baked into the captured training graph."""
+``fit(callbacks=[...])``: `Callback` (no-op hooks), `EarlyStopping`, `ModelCheckpoint`, `LearningRateScheduler` and `ReduceLROnPlateau`
+after Keras 2's classes of the same names.  The two that move the learning rate go through training.set_learning_rate: the rate lives
+in device memory, so the captured training graph replays under the new rate as it is."""
 import logging
 import re
 
@@ -164,3 +165,101 @@ class ModelCheckpoint(Callback):
         path = self.filepath.format(epoch=epoch + 1, **logs)
         self.model.save_weights(path)
         self.saved.append(path)
+
+
+def _get_lr(model):
+    fn = getattr(model, 'get_learning_rate', None)
+    if callable(fn):
+        return float(fn())
+    from deep_cbrs_amar_renaissance_amd import training
+    return training.get_learning_rate(model)
+
+
+def _set_lr(model, value):
+    fn = getattr(model, 'set_learning_rate', None)
+    if callable(fn):
+        return fn(value)
+    from deep_cbrs_amar_renaissance_amd import training
+    return training.set_learning_rate(model, value)
+
+
+class LearningRateScheduler(Callback):
+    """Keras 2's LearningRateScheduler: at every on_epoch_begin the rate becomes schedule(epoch, current rate) — schedule(epoch) for a
+    function of one argument (a TypeError of the first call) — which must be a float; on_epoch_end puts the rate in force into
+    logs['lr'].  A model may bring its own get_learning_rate() / set_learning_rate(value) (the tests do); otherwise the rate is the
+    trainer's (training.get_learning_rate / set_learning_rate)."""
+
+    def __init__(self, schedule, verbose=0):
+        self.schedule, self.verbose = schedule, int(verbose)
+
+    def on_epoch_begin(self, epoch, logs=None):
+        try:
+            value = self.schedule(epoch, _get_lr(self.model))
+        except TypeError:                                            # the older form: a function of the epoch alone
+            value = self.schedule(epoch)
+        if not isinstance(value, (float, np.float32, np.float64)):
+            raise ValueError('The output of the "schedule" function should be float (got {!r})'.format(value))
+        _set_lr(self.model, float(value))
+        if self.verbose:
+            print("Epoch {}: LearningRateScheduler setting learning rate to {}.".format(epoch + 1, float(value)))
+
+    def on_epoch_end(self, epoch, logs=None):
+        if logs is not None:
+            logs['lr'] = _get_lr(self.model)
+
+
+class ReduceLROnPlateau(Callback):
+    """Keras 2's ReduceLROnPlateau.  on_train_begin resets best (+-inf), wait and cooldown_counter.  On every on_epoch_end: logs['lr'] =
+    the rate in force; a missing monitor key warns once and ends the call; in cooldown the counter goes down and wait = 0; a value
+    better than best by more than min_delta (value < best - min_delta for 'min', value > best + min_delta for 'max') becomes best and
+    sets wait = 0; otherwise, outside cooldown, wait += 1, and with wait >= patience and rate > min_lr the rate becomes
+    max(rate * factor, min_lr), the cooldown starts and wait = 0."""
+
+    def __init__(self, monitor='val_loss', factor=0.1, patience=10, verbose=0, mode='auto', min_delta=1e-4, cooldown=0, min_lr=0):
+        if float(factor) >= 1.0:
+            raise ValueError("ReduceLROnPlateau does not support a factor >= 1.0 (got {})".format(factor))
+        self.monitor, self.factor, self.patience, self.verbose = monitor, float(factor), int(patience), int(verbose)
+        self.min_delta, self.cooldown, self.min_lr = float(min_delta), int(cooldown), float(min_lr)
+        self.mode = monitor_mode(monitor, mode)
+        self._warned = False
+        self.on_train_begin()
+
+    def _better(self, value, reference):
+        return value < reference - self.min_delta if self.mode == 'min' else value > reference + self.min_delta
+
+    def in_cooldown(self):
+        return self.cooldown_counter > 0
+
+    def on_train_begin(self, logs=None):
+        self.best = np.inf if self.mode == 'min' else -np.inf
+        self.wait, self.cooldown_counter = 0, 0
+        if self.model is not None and not callable(getattr(self.model, 'set_learning_rate', None)):
+            from deep_cbrs_amar_renaissance_amd import training
+            training.make_learning_rate_dynamic(self.model)          # the rate on the device from the first epoch on: one capture, `lr` in every epoch
+
+    def on_epoch_end(self, epoch, logs=None):
+        logs = logs if logs is not None else {}
+        logs['lr'] = _get_lr(self.model)
+        value = logs.get(self.monitor)
+        if value is None:
+            if not self._warned:
+                logger.warning("ReduceLROnPlateau: the monitored value '%s' is not in the epoch's logs (%s)", self.monitor,
+                               ', '.join(sorted(logs)))
+                self._warned = True
+            return
+        value = float(value)
+        if self.in_cooldown():
+            self.cooldown_counter -= 1
+            self.wait = 0
+        if self._better(value, self.best):
+            self.best, self.wait = value, 0
+        elif not self.in_cooldown():
+            self.wait += 1
+            if self.wait >= self.patience:
+                old = _get_lr(self.model)
+                if old > np.float32(self.min_lr):
+                    new = max(old * self.factor, self.min_lr)
+                    _set_lr(self.model, new)
+                    if self.verbose:
+                        print("Epoch {}: ReduceLROnPlateau reducing learning rate to {}.".format(epoch + 1, new))
+                    self.cooldown_counter, self.wait = self.cooldown, 0

@@ -834,6 +834,58 @@ typedef struct amar_optim_slot { float *w; const float *g; float *s0; float *s1;
 int amar_optim_multi_f32(int32_t rule, int32_t flags, const amar_optim_hyper *hyper, const amar_optim_slot *slots, int32_t n_slots,
                          int64_t total_blocks, const float *state, float reg_scale, float *loss_acc, amar_stream_t stream);
 
+/* ---- learning-rate schedules: tf.keras.optimizers.schedules, Keras 2's optimizer argument `decay`, and a rate the host sets --------------
+ * The learning rate of the two advance entry points above is an argument, so a captured training batch has it baked in.  Their siblings
+ * below take it from device memory instead and evaluate a schedule inside the same one-thread launch: a captured batch then replays
+ * under a rate that follows the step counter, or that the host rewrites between replays, without being captured again.
+ *
+ * lr_state: AMAR_LR_STATE_FLOATS floats in device memory.
+ *   [0] the base rate: what AMAR_LR_CONSTANT returns.  The host writes it; no kernel does.
+ *   [1] the rate the last step used: written by the advance kernels, for the host to read.
+ * The rate of the ZERO-BASED step s (the first step has s = 0, as Keras' `iterations`), computed in double from the float32 members
+ * and rounded once to float32 (Keras holds the rate as float32), without fused products.  lr0 = initial_learning_rate, d = decay_steps:
+ *   AMAR_LR_CONSTANT      lr_state[0]
+ *   AMAR_LR_EXPONENTIAL   lr0 * decay_rate^p,  p = s / d;  AMAR_LR_STAIRCASE: p = floor(s / d)                  (ExponentialDecay)
+ *   AMAR_LR_INVERSE_TIME  lr0 / (1 + decay_rate * p),  p as above                                                (InverseTimeDecay;
+ *                         Keras 2's optimizer argument `decay` is this with d = 1 and decay_rate = decay)
+ *   AMAR_LR_POLYNOMIAL    (lr0 - end_learning_rate) * (1 - p)^power + end_learning_rate,  p = min(s, d) / d;     (PolynomialDecay)
+ *                         AMAR_LR_CYCLE: p = s / (d * (s == 0 ? 1 : ceil(s / d))), without the min
+ *   AMAR_LR_COSINE        lr0 * ((1 - alpha) * 0.5 * (1 + cos(pi * (min(s, d) / d))) + alpha)                    (CosineDecay)
+ *   AMAR_LR_PIECEWISE     values[i] for the first i < n_boundaries with s <= boundaries[i], values[n_boundaries] if there is none
+ *                         (PiecewiseConstantDecay): 1 <= n_boundaries <= AMAR_LR_MAX_BOUNDARIES, one value more than boundaries
+ * A kind ignores the members it does not use.  The step counter is state[0] of the optimizer state, a float: it counts exactly up to
+ * 2^24 = AMAR_LR_MAX_STEP steps, and so do the boundaries; a run longer than that is outside this contract.
+ * Unknown kind, a flag the kind does not have, decay_steps <= 0 (or NaN) where the kind divides by it, n_boundaries outside
+ * 1 .. 16, null pointers: AMAR_EINVAL. */
+#define AMAR_LR_CONSTANT     0
+#define AMAR_LR_EXPONENTIAL  1
+#define AMAR_LR_INVERSE_TIME 2
+#define AMAR_LR_POLYNOMIAL   3
+#define AMAR_LR_COSINE       4
+#define AMAR_LR_PIECEWISE    5
+#define AMAR_LR_STAIRCASE 0x1     /* flag of AMAR_LR_EXPONENTIAL and AMAR_LR_INVERSE_TIME */
+#define AMAR_LR_CYCLE     0x2     /* flag of AMAR_LR_POLYNOMIAL */
+#define AMAR_LR_MAX_BOUNDARIES 16
+#define AMAR_LR_STATE_FLOATS 2
+#define AMAR_LR_MAX_STEP 16777216
+/* HOST struct, read when the call is made (the kernels receive it by value) */
+typedef struct amar_lr_schedule {
+    int32_t kind, flags;
+    float initial_learning_rate, decay_steps, decay_rate, end_learning_rate, power, alpha;
+    int32_t n_boundaries;
+    float boundaries[AMAR_LR_MAX_BOUNDARIES], values[AMAR_LR_MAX_BOUNDARIES + 1];
+} amar_lr_schedule;
+/* out[i] = the rate of step first_step + i, i < n (one thread each; first_step >= 0, first_step + n <= AMAR_LR_MAX_STEP; n = 0: AMAR_OK,
+ * nothing is launched).  The advance entry points below call the same device function: the same bits. */
+int amar_lr_rates_f32(const amar_lr_schedule *sched, const float *lr_state, int64_t first_step, int64_t n, float *out, amar_stream_t stream);
+/* amar_adam_advance_f32 / amar_optim_advance_f32 with the rate of step s = state[0] in place of the learning-rate argument (one thread,
+ * one launch, ordinary stores): lr_state[1] = that rate, then state[0] = s + 1 and the step-dependent scalars exactly as those entry
+ * points form them from a float32 rate.  hyper->learning_rate is not read.  Under AMAR_LR_CONSTANT with lr_state[0] = lr every float of
+ * `state` equals, bit for bit, what the entry point with the argument lr writes. */
+int amar_adam_advance_lr_f32(float *state, const amar_lr_schedule *sched, float *lr_state, float beta_1, float beta_2, amar_stream_t stream);
+int amar_optim_advance_lr_f32(float *state, int32_t rule, int32_t flags, const amar_optim_hyper *hyper, const amar_lr_schedule *sched,
+                              float *lr_state, amar_stream_t stream);
+
 /* ---- gradient clipping: clipvalue, clipnorm, global_clipnorm of every tf.keras optimizer (Keras 2.7 / 2.8 OptimizerV2, restated) ---------
  * The clipped quantity is the finished gradient of (data loss + regularisation losses), per parameter tensor (slot):
  *   gi = fmaf(2 l2, w, g[0] + g[1] + ... + g[G-1])     the partials added in the order 0 .. G-1, as the optimizer launches add them
