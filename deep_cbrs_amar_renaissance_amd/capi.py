@@ -1070,8 +1070,8 @@ def adam_multi(table_dev, n_slots, total_blocks, state, beta_1, beta_2, epsilon,
     _check(code, 'amar_adam_multi_f32')
 
 
-# ---- the other optimizers (include/amar_hip.h: AMAR_OPT_*) ----------------------------------------------------------------------------
-OPT_SGD, OPT_RMSPROP, OPT_ADAGRAD, OPT_ADAMAX, OPT_NADAM, OPT_AMSGRAD = 1, 2, 3, 4, 5, 6
+# ---- the optimizers as rules (include/amar_hip.h: AMAR_OPT_*) --------------------------------------------------------------------------
+OPT_SGD, OPT_RMSPROP, OPT_ADAGRAD, OPT_ADAMAX, OPT_NADAM, OPT_AMSGRAD, OPT_ADAM = 1, 2, 3, 4, 5, 6, 7
 OPT_NESTEROV, OPT_CENTERED = 0x100, 0x200
 OPTIM_STATE_FLOATS = 8
 

@@ -1,6 +1,6 @@
 // Gradient clipping of tf.keras optimizers (gfx950): clipvalue, clipnorm and global_clipnorm, as include/amar_hip.h states them.  The
-// clipped quantity is the FINISHED gradient gi = fmaf(2 l2, w, sum of the deferred partials in group order) — what optim_multi_kernel /
-// adam_multi_kernel form in registers and never store — so the pass finishes the gradients itself, into group 0 of every slot, and the
+// clipped quantity is the FINISHED gradient gi = fmaf(2 l2, w, sum of the deferred partials in group order) — what optim_multi_kernel
+// forms in registers and never stores — so the pass finishes the gradients itself, into group 0 of every slot, and the
 // optimizer launch that follows runs on a table with g_groups = 0 and l2 = 0 (fmaf(0, w, g) == g: the update kernels stay as they are).
 // Three small launches over the block partition of the optimizer slot tables (1024 elements per block):
 //   finish   gi into group 0 (clipvalue: clamped, and done); per block the sum of gi^2 into workspace[block]; the L2 part of the loss

@@ -1,56 +1,33 @@
-// The optimizers of tf.keras.optimizers besides Adam (gfx950): SGD (momentum, Nesterov), RMSprop (momentum, centered), Adagrad, Adamax,
-// Nadam and Adam(amsgrad=True), as include/amar_hip.h states them.  Same build as the Adam kernels of amar_train.hip, which stay as they
-// are: a one-thread kernel advances the step counter and the step-dependent scalars in device memory (nothing that changes from step to
-// step is baked into a captured training graph), ONE launch updates every parameter of a model from a slot table (adding the deferred
-// weight-gradient partials in group order and the L2 part of the reported loss), and a single-tensor form reads the same device state.
-// The rule is a template parameter: a rule loads and stores only the arrays it uses and nothing inside the element loop branches on it.
-#include "amar_common.h"
+// The optimizers of tf.keras.optimizers (gfx950): Adam, SGD (momentum, Nesterov), RMSprop (momentum, centered), Adagrad, Adamax, Nadam and
+// Adam(amsgrad=True), as include/amar_hip.h states them.  A one-thread kernel advances the step counter and the step-dependent scalars in
+// device memory (nothing that changes from step to step is baked into a captured training graph), ONE launch updates every parameter of
+// a model from a slot table (adding the deferred weight-gradient partials in group order and the L2 part of the reported loss), and a
+// single-tensor form reads the same device state.  The rule is a template parameter: a rule loads and stores only the arrays it uses and
+// nothing inside the element loop branches on it.  The amar_adam_* entry points are Adam's instantiations of the same kernels.
+#include "amar_optim.h"
 
 namespace {
-
-// A rule with its flags resolved: what the kernels are instantiated for.
-enum Variant {
-    V_SGD, V_SGD_MOM, V_SGD_NESTEROV, V_RMS, V_RMS_MOM, V_RMS_CENTERED, V_RMS_CENTERED_MOM, V_ADAGRAD, V_ADAMAX, V_NADAM, V_AMSGRAD, V_COUNT
-};
-
-__host__ __device__ constexpr int state_arrays_of(int v) {
-    return v == V_SGD ? 0
-         : (v == V_SGD_MOM || v == V_SGD_NESTEROV || v == V_RMS || v == V_ADAGRAD) ? 1
-         : (v == V_RMS_MOM || v == V_RMS_CENTERED || v == V_ADAMAX || v == V_NADAM) ? 2 : 3;
-}
-
-// -1: not a rule, flags the rule does not have, or a momentum that is negative or NaN
-int resolve_variant(int32_t rule, int32_t flags, float momentum) {
-    if (!(momentum >= 0.f)) return -1;
-    const bool mom = momentum > 0.f;
-    switch (rule) {
-    case AMAR_OPT_SGD:
-        if (flags & ~AMAR_OPT_NESTEROV) return -1;
-        return !mom ? V_SGD : ((flags & AMAR_OPT_NESTEROV) ? V_SGD_NESTEROV : V_SGD_MOM);     // (Keras: nesterov without momentum is plain SGD)
-    case AMAR_OPT_RMSPROP:
-        if (flags & ~AMAR_OPT_CENTERED) return -1;
-        return (flags & AMAR_OPT_CENTERED) ? (mom ? V_RMS_CENTERED_MOM : V_RMS_CENTERED) : (mom ? V_RMS_MOM : V_RMS);
-    case AMAR_OPT_ADAGRAD: return flags ? -1 : V_ADAGRAD;
-    case AMAR_OPT_ADAMAX:  return flags ? -1 : V_ADAMAX;
-    case AMAR_OPT_NADAM:   return flags ? -1 : V_NADAM;
-    case AMAR_OPT_AMSGRAD: return flags ? -1 : V_AMSGRAD;
-    default: return -1;
-    }
-}
 
 // What an element update reads besides its own element: the hyper-parameters and the device state of this step (wave-uniform).
 struct OptK { float step, momentum, rho, b1, b2, eps, mu_next, omb2, cg, cm; };
 
-__device__ __forceinline__ OptK load_k(const float *__restrict__ state, const amar_optim_hyper h) {
-    OptK k;
-    k.step = state[1]; k.momentum = h.momentum; k.rho = h.rho; k.b1 = h.beta_1; k.b2 = h.beta_2; k.eps = h.epsilon;
-    k.mu_next = state[3]; k.omb2 = state[5]; k.cg = state[6]; k.cm = state[7];
+__device__ __forceinline__ OptK hyper_k(const amar_optim_hyper h, float step) {
+    OptK k = {};
+    k.step = step; k.momentum = h.momentum; k.rho = h.rho; k.b1 = h.beta_1; k.b2 = h.beta_2; k.eps = h.epsilon;
     return k;
 }
 
-// One update of one element, shared by optim_kernel and optim_multi_kernel: the two give the same bits on the same element (the header's
-// promise).  As adam_step: the fused products are written out and nothing else may be fused, so the bits do not depend on the kernel
-// around it.  s0..s2 are the rule's state arrays in the header's order; the ones a rule does not have are neither read nor written.
+// Every rule reads state[1]; Nadam alone reads above it (Adam's state ends there).
+template <int V>
+__device__ __forceinline__ OptK load_k(const float *__restrict__ state, const amar_optim_hyper h) {
+    OptK k = hyper_k(h, state[1]);
+    if constexpr (V == V_NADAM) { k.mu_next = state[3]; k.omb2 = state[5]; k.cg = state[6]; k.cm = state[7]; }
+    return k;
+}
+
+// One update of one element, shared by every update kernel: they give the same bits on the same element (the header's promise).  The
+// fused products are written out and nothing else may be fused, so the bits do not depend on the kernel around it.  s0..s2 are the
+// rule's state arrays in the header's order; the ones a rule does not have are neither read nor written.
 template <int V>
 __device__ __forceinline__ void optim_step(float &w, float g, float &s0, float &s1, float &s2, const OptK &k, float l2x2) {
 #pragma clang fp contract(off)
@@ -91,41 +68,25 @@ __device__ __forceinline__ void optim_step(float &w, float g, float &s0, float &
         s0 = fmaf(k.b1, s0, (1.f - k.b1) * gi);
         s1 = fmaf(k.b2, s1, ((1.f - k.b2) * gi) * gi);
         w = w - fmaf(k.cg, gi, k.cm * s0) / (sqrtf(s1 / k.omb2) + k.eps);
-    } else {                                                          // V_AMSGRAD
+    } else {                                                          // V_ADAM, V_AMSGRAD: step carries the bias correction
         s0 = fmaf(k.b1, s0, (1.f - k.b1) * gi);
         s1 = fmaf(k.b2, s1, ((1.f - k.b2) * gi) * gi);
-        s2 = fmaxf(s2, s1);
-        w = w - (k.step * s0) / (sqrtf(s2) + k.eps);
+        float d = s1;
+        if constexpr (V == V_AMSGRAD) d = s2 = fmaxf(s2, s1);
+        w = w - (k.step * s0) / (sqrtf(d) + k.eps);
     }
 }
 
-// state[0] = t + 1 and the scalars of that step, computed in double from the float32 hyper-parameters (as adam_advance_kernel); plain
-// vector stores from the one thread.  Nadam's running product P_t lives in state[4]: P_t = P_{t-1} * mu_t with P_0 = 1 (t == 1 starts it).
 __global__ void optim_advance_kernel(float *__restrict__ state, int rule, const amar_optim_hyper h) {
-    const double t = (double)state[0] + 1.0;
-    const double lr = (double)h.learning_rate, b1 = (double)h.beta_1, b2 = (double)h.beta_2;
-    const double p_prev = t == 1.0 ? 1.0 : (double)state[4];
-    double out[AMAR_OPTIM_STATE_FLOATS] = {t, lr, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (rule == AMAR_OPT_ADAMAX) {
-        out[1] = lr / (1.0 - pow(b1, t));
-    } else if (rule == AMAR_OPT_AMSGRAD) {
-        out[1] = lr * sqrt(1.0 - pow(b2, t)) / (1.0 - pow(b1, t));
-    } else if (rule == AMAR_OPT_NADAM) {
-        const double mu = b1 * (1.0 - 0.5 * pow(0.96, 0.004 * t)), mu_next = b1 * (1.0 - 0.5 * pow(0.96, 0.004 * (t + 1.0)));
-        const double p = p_prev * mu;
-        out[2] = mu; out[3] = mu_next; out[4] = p; out[5] = 1.0 - pow(b2, t);
-        out[6] = lr * (1.0 - mu) / (1.0 - p);
-        out[7] = lr * mu_next / (1.0 - p * mu_next);
-    }
-    for (int k = 0; k < AMAR_OPTIM_STATE_FLOATS; ++k) state[k] = (float)out[k];
+    optim_advance_state(state, rule, h.learning_rate, h);
 }
 
+// The single-tensor form.  The step scalars come from the device state, or (amar_adam_f32 alone: a step size formed on the host) from
+// the argument.
 template <int V>
-__global__ __launch_bounds__(256) void optim_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ s0,
-                                                    float *__restrict__ s1, float *__restrict__ s2, int64_t n,
-                                                    const float *__restrict__ state, const amar_optim_hyper h, float l2x2) {
+__device__ __forceinline__ void optim_elements(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ s0,
+                                               float *__restrict__ s1, float *__restrict__ s2, int64_t n, const OptK k, float l2x2) {
     constexpr int NS = state_arrays_of(V);
-    const OptK k = load_k(state, h);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         float wi = w[i], a = 0.f, b = 0.f, c = 0.f;
         if constexpr (NS > 0) a = s0[i];
@@ -139,24 +100,48 @@ __global__ __launch_bounds__(256) void optim_kernel(float *__restrict__ w, const
     }
 }
 
+template <int V>
+__global__ __launch_bounds__(256) void optim_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ s0,
+                                                    float *__restrict__ s1, float *__restrict__ s2, int64_t n,
+                                                    const float *__restrict__ state, const amar_optim_hyper h, float l2x2) {
+    optim_elements<V>(w, g, s0, s1, s2, n, load_k<V>(state, h), l2x2);
+}
+
+__global__ __launch_bounds__(256) void adam_host_step_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m,
+                                                             float *__restrict__ v, int64_t n, float lr_t, const amar_optim_hyper h,
+                                                             float l2x2) {
+    optim_elements<V_ADAM>(w, g, m, v, nullptr, n, hyper_k(h, lr_t), l2x2);
+}
+
+// State array a of a slot, for both slot layouts of the header.
+__device__ __forceinline__ float *slot_array(const amar_optim_slot &sl, int a) { return a == 0 ? sl.s0 : (a == 1 ? sl.s1 : sl.s2); }
+__device__ __forceinline__ float *slot_array(const amar_adam_slot &sl, int a) { return a == 0 ? sl.m : sl.v; }
+
 __device__ __forceinline__ void f4_to(float (&dst)[4], const float4 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w; }
 __device__ __forceinline__ float4 f4_from(const float (&src)[4]) { return make_float4(src[0], src[1], src[2], src[3]); }
 
-// Every parameter of a model in ONE launch — adam_multi_kernel's build for the other rules: block b works on 1024 elements of the slot
-// that owns it, all loads of a thread's four elements first, then the deferred partial gradients (loads before adds, the adds in group
-// order), 16 bytes per lane where the slot's arrays allow it, one atomic per block into *loss_acc for the L2 part of the loss.
-template <int V>
-__global__ __launch_bounds__(256) void optim_multi_kernel(const amar_optim_slot *__restrict__ slots, int n_slots,
+// Every parameter of a model in ONE launch: block b works on 1024 elements of the slot that owns it (slots carry their first block).
+// All loads of a thread's four elements first, then the deferred partial gradients sixteen (scalar path: four) groups at a time, loads
+// before adds, the adds in group order: written as one load -> add chain per element, the 16 partials of a Dense kernel's gradient were
+// 16 dependent memory round trips — 30 us of every training batch, whatever the model's size.  Slots whose arrays allow it (16-byte
+// aligned, n a multiple of 4: every table and kernel of the models here) move 16 bytes per lane — a thread then owns four NEIGHBOURING
+// elements instead of four 256 apart; each element's arithmetic is the same either way.  Also adds reg_scale * l2 * sum(w^2) of the
+// PRE-update weights to *loss_acc (the regularisation part of the batch loss Keras reports), one atomic per block, so no separate
+// reduction launches are needed.  Slot: amar_optim_slot, or amar_adam_slot (V_ADAM) read where it lies.
+template <int V, typename Slot>
+__global__ __launch_bounds__(256) void optim_multi_kernel(const Slot *__restrict__ slots, int n_slots,
                                                           const float *__restrict__ state, const amar_optim_hyper h,
                                                           float reg_scale, float *__restrict__ loss_acc) {
     constexpr int NS = state_arrays_of(V);
     int sidx = 0;
     while (sidx + 1 < n_slots && (int64_t)blockIdx.x >= slots[sidx + 1].first_block) ++sidx;
-    const amar_optim_slot sl = slots[sidx];
-    const OptK k = load_k(state, h);
+    const Slot sl = slots[sidx];
+    const OptK k = load_k<V>(state, h);
     const float l2x2 = 2.f * sl.l2;
     const int64_t base = ((int64_t)blockIdx.x - sl.first_block) * 1024;
-    float *const sp[3] = {sl.s0, sl.s1, sl.s2};
+    float *sp[3] = {nullptr, nullptr, nullptr};                      // (the arrays the rule has: the others are never looked at)
+#pragma unroll
+    for (int a = 0; a < NS; ++a) sp[a] = slot_array(sl, a);
     uintptr_t bits = reinterpret_cast<uintptr_t>(sl.w) | reinterpret_cast<uintptr_t>(sl.g);
 #pragma unroll
     for (int a = 0; a < NS; ++a) bits |= reinterpret_cast<uintptr_t>(sp[a]);
@@ -253,10 +238,10 @@ void launch_single(float *w, const float *g, float *s0, float *s1, float *s2, in
     hipLaunchKernelGGL(optim_kernel<V>, dim3(grid_of(n)), dim3(256), 0, st, w, g, s0, s1, s2, n, state, h, 2.f * l2);
 }
 
-template <int V>
-void launch_multi(const amar_optim_slot *slots, int32_t n_slots, int64_t total_blocks, const float *state, const amar_optim_hyper &h,
+template <int V, typename Slot>
+void launch_multi(const Slot *slots, int32_t n_slots, int64_t total_blocks, const float *state, const amar_optim_hyper &h,
                   float reg_scale, float *loss_acc, hipStream_t st) {
-    hipLaunchKernelGGL(optim_multi_kernel<V>, dim3((unsigned)total_blocks), dim3(256), 0, st, slots, n_slots, state, h, reg_scale, loss_acc);
+    hipLaunchKernelGGL((optim_multi_kernel<V, Slot>), dim3((unsigned)total_blocks), dim3(256), 0, st, slots, n_slots, state, h, reg_scale, loss_acc);
 }
 
 #define AMAR_FOR_EACH_VARIANT(CALL)                                                                                                      \
@@ -266,7 +251,8 @@ void launch_multi(const amar_optim_slot *slots, int32_t n_slots, int64_t total_b
     case V_RMS_MOM: CALL(V_RMS_MOM); break;             case V_RMS_CENTERED: CALL(V_RMS_CENTERED); break;                                \
     case V_RMS_CENTERED_MOM: CALL(V_RMS_CENTERED_MOM); break;                                                                            \
     case V_ADAGRAD: CALL(V_ADAGRAD); break;             case V_ADAMAX: CALL(V_ADAMAX); break;                                            \
-    case V_NADAM: CALL(V_NADAM); break;                 default: CALL(V_AMSGRAD); break;                                                 \
+    case V_NADAM: CALL(V_NADAM); break;                 case V_AMSGRAD: CALL(V_AMSGRAD); break;                                          \
+    default: CALL(V_ADAM); break;                                                                                                        \
     }
 
 }  // namespace
@@ -308,6 +294,39 @@ int amar_optim_multi_f32(int32_t rule, int32_t flags, const amar_optim_hyper *hy
 #define AMAR_CALL(V) launch_multi<V>(slots, n_slots, total_blocks, state, *hyper, reg_scale, loss_acc, st)
     AMAR_FOR_EACH_VARIANT(AMAR_CALL)
 #undef AMAR_CALL
+    return amar_check_launch();
+}
+
+// ---- Adam by its own entry points: the V_ADAM instantiations over two floats of state and amar_adam_slot ------------------------------
+int amar_adam_f32(float *w, const float *g, float *m, float *v, int64_t n, float lr_t, float beta_1, float beta_2,
+                  float epsilon, float l2, amar_stream_t stream) {
+    if (n < 0 || !w || !g || !m || !v) return AMAR_EINVAL;
+    if (n == 0) return AMAR_OK;
+    hipLaunchKernelGGL(adam_host_step_kernel, dim3(grid_of(n)), dim3(256), 0, static_cast<hipStream_t>(stream), w, g, m, v, n, lr_t,
+                       adam_hyper(0.f, beta_1, beta_2, epsilon), 2.f * l2);
+    return amar_check_launch();
+}
+
+int amar_adam_advance_f32(float *state, float learning_rate, float beta_1, float beta_2, amar_stream_t stream) {
+    if (!state) return AMAR_EINVAL;
+    hipLaunchKernelGGL(optim_advance_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), state, AMAR_OPT_ADAM,
+                       adam_hyper(learning_rate, beta_1, beta_2, 0.f));
+    return amar_check_launch();
+}
+
+int amar_adam_dev_f32(float *w, const float *g, float *m, float *v, int64_t n, const float *state, float beta_1, float beta_2,
+                      float epsilon, float l2, amar_stream_t stream) {
+    if (n < 0 || !w || !g || !m || !v || !state) return AMAR_EINVAL;
+    if (n == 0) return AMAR_OK;
+    launch_single<V_ADAM>(w, g, m, v, nullptr, n, state, adam_hyper(0.f, beta_1, beta_2, epsilon), l2, static_cast<hipStream_t>(stream));
+    return amar_check_launch();
+}
+
+int amar_adam_multi_f32(const amar_adam_slot *slots, int32_t n_slots, int64_t total_blocks, const float *state, float beta_1,
+                        float beta_2, float epsilon, float reg_scale, float *loss_acc, amar_stream_t stream) {
+    if (!slots || n_slots < 1 || total_blocks < 1 || total_blocks > 0x7fffffff || !state) return AMAR_EINVAL;
+    launch_multi<V_ADAM>(slots, n_slots, total_blocks, state, adam_hyper(0.f, beta_1, beta_2, epsilon), reg_scale, loss_acc,
+                         static_cast<hipStream_t>(stream));
     return amar_check_launch();
 }
 

@@ -170,29 +170,6 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float *__restrict_
     }
 }
 
-// One Adam update, shared by adam_kernel / adam_dev_kernel / adam_multi_kernel: the three give the same bits on the same element (the
-// header's promise).  The fused products are written out and nothing else may be fused, so the bits do not depend on the kernel around it.
-struct AdamStep { float w, m, v; };
-__device__ __forceinline__ AdamStep adam_step(float wi, float g, float mi, float vi, float lr_t, float b1, float b2, float eps, float l2x2) {
-#pragma clang fp contract(off)
-    const float gi = fmaf(l2x2, wi, g);
-    AdamStep o;
-    o.m = fmaf(b1, mi, (1.f - b1) * gi);
-    o.v = fmaf(b2, vi, ((1.f - b2) * gi) * gi);
-    o.w = wi - (lr_t * o.m) / (sqrtf(o.v) + eps);
-    return o;
-}
-
-// keras.optimizers.Adam: m, v moments; lr_t carries the bias correction; the L2 regulariser's gradient 2*l2*w is folded in
-__global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m,
-                                                   float *__restrict__ v, int64_t n, float lr_t, float b1, float b2, float eps,
-                                                   float l2x2) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const AdamStep o = adam_step(w[i], g[i], m[i], v[i], lr_t, b1, b2, eps, l2x2);
-        m[i] = o.m; v[i] = o.v; w[i] = o.w;
-    }
-}
-
 // out = (A + B) * scale[row]   (B optional): GraphSAGE's mean aggregate (s + x) / count and its reverse
 __global__ __launch_bounds__(256) void row_affine_kernel(const float *__restrict__ A, int64_t lda, const float *__restrict__ B,
                                                          int64_t ldb, const float *__restrict__ scale, float *__restrict__ out,
@@ -517,25 +494,6 @@ void launch_gat_heads_bwd(const GatHeadsBwdArgs &a, hipStream_t st) {
     hipLaunchKernelGGL(gat_heads_bwd_source_kernel<LPN>, grid, block, 0, st, a);
 }
 
-// The same update with the step size read from device memory, and the one-thread kernel that advances it:
-// state[0] = t (as float), state[1] = lr * sqrt(1 - b2^t) / (1 - b1^t).  Lets a whole training batch, optimizer
-// included, replay as one hipGraph with nothing baked in that changes from step to step.
-__global__ void adam_advance_kernel(float *__restrict__ state, float lr, float b1, float b2) {
-    const double t = (double)state[0] + 1.0;
-    state[0] = (float)t;
-    state[1] = (float)((double)lr * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t)));
-}
-
-__global__ __launch_bounds__(256) void adam_dev_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m,
-                                                       float *__restrict__ v, int64_t n, const float *__restrict__ state, float b1,
-                                                       float b2, float eps, float l2x2) {
-    const float lr_t = state[1];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const AdamStep o = adam_step(w[i], g[i], m[i], v[i], lr_t, b1, b2, eps, l2x2);
-        m[i] = o.m; v[i] = o.v; w[i] = o.w;
-    }
-}
-
 // ---- FusionLayer('attention') (src/layers/fusion.py:54-68) and the residual head's sum (src/models/hybrid.py:89) ----
 // With ta = a . W_att, tb = b . W_att (two Dense products done by the caller):  the softmax over the two stacked
 // sources is, per feature, wa = sigmoid(tanh(ta) - tanh(tb)), wb = 1 - wa, and out = wa * a + wb * b.
@@ -613,97 +571,6 @@ __global__ __launch_bounds__(256) void add3_act_kernel(const float *__restrict__
         if (act == AMAR_ACT_RELU) v = fmaxf(v, 0.f);
         else if (act == AMAR_ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
         out[r * ldo + c] = v;
-    }
-}
-
-// Every parameter of a model in ONE launch: block b works on 1024 elements of the slot that owns it (slots carry their
-// first block).  Also adds reg_scale * l2 * sum(w^2) of the PRE-update weights to *loss_acc (the regularisation part of the
-// batch loss Keras reports), so no separate reduction launches are needed.
-__global__ __launch_bounds__(256) void adam_multi_kernel(const amar_adam_slot *__restrict__ slots, int n_slots,
-                                                         const float *__restrict__ state, float b1, float b2, float eps,
-                                                         float reg_scale, float *__restrict__ loss_acc) {
-    int sidx = 0;
-    while (sidx + 1 < n_slots && (int64_t)blockIdx.x >= slots[sidx + 1].first_block) ++sidx;
-    const amar_adam_slot sl = slots[sidx];
-    const float lr_t = state[1], l2x2 = 2.f * sl.l2;
-    const int64_t base = ((int64_t)blockIdx.x - sl.first_block) * 1024;
-    // all loads of the block's four elements per thread first, then the deferred partial gradients four groups at a time (loads before
-    // adds, the adds in group order): written as one load -> add chain per element, the 16 partials of a Dense kernel's gradient were 16
-    // dependent memory round trips — 30 us of every training batch, whatever the model's size.  Slots whose arrays allow it (16-byte
-    // aligned, n a multiple of 4: every table and kernel of the models here) move 16 bytes per lane — a thread then owns four NEIGHBOURING
-    // elements instead of four 256 apart; each element's arithmetic is the same either way.
-    const bool vec = (sl.n & 3) == 0 && ((reinterpret_cast<uintptr_t>(sl.w) | reinterpret_cast<uintptr_t>(sl.g) | reinterpret_cast<uintptr_t>(sl.m) |
-                                          reinterpret_cast<uintptr_t>(sl.v)) & 15u) == 0;
-    float wi[4], gs[4], mi[4], vi[4];
-    int64_t idx[4];
-    if (vec) {
-        const int64_t i0 = base + 4 * threadIdx.x;
-        const bool ok = i0 < sl.n;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) idx[r] = ok ? i0 + r : sl.n;
-        const float4 w4 = ok ? *reinterpret_cast<const float4 *>(sl.w + i0) : f4_zero(), g4 = ok ? *reinterpret_cast<const float4 *>(sl.g + i0) : f4_zero();
-        const float4 m4 = ok ? *reinterpret_cast<const float4 *>(sl.m + i0) : f4_zero(), v4 = ok ? *reinterpret_cast<const float4 *>(sl.v + i0) : f4_zero();
-        wi[0] = w4.x; wi[1] = w4.y; wi[2] = w4.z; wi[3] = w4.w;  gs[0] = g4.x; gs[1] = g4.y; gs[2] = g4.z; gs[3] = g4.w;
-        mi[0] = m4.x; mi[1] = m4.y; mi[2] = m4.z; mi[3] = m4.w;  vi[0] = v4.x; vi[1] = v4.y; vi[2] = v4.z; vi[3] = v4.w;
-        for (int c = 1; c < sl.g_groups; c += 16) {                  // sixteen groups in flight
-            float4 part[16];
-#pragma unroll
-            for (int cc = 0; cc < 16; ++cc)
-                part[cc] = (c + cc < sl.g_groups && ok) ? *reinterpret_cast<const float4 *>(sl.g + (int64_t)(c + cc) * sl.n + i0) : f4_zero();
-#pragma unroll
-            for (int cc = 0; cc < 16; ++cc)
-                if (c + cc < sl.g_groups) { gs[0] += part[cc].x; gs[1] += part[cc].y; gs[2] += part[cc].z; gs[3] += part[cc].w; }
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            idx[r] = base + r * 256 + threadIdx.x;
-            const bool ok = idx[r] < sl.n;
-            wi[r] = ok ? sl.w[idx[r]] : 0.f;
-            gs[r] = ok ? sl.g[idx[r]] : 0.f;
-            mi[r] = ok ? sl.m[idx[r]] : 0.f;
-            vi[r] = ok ? sl.v[idx[r]] : 0.f;
-        }
-        for (int c = 1; c < sl.g_groups; c += 4) {
-            float part[4][4];
-#pragma unroll
-            for (int cc = 0; cc < 4; ++cc)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    part[cc][r] = (c + cc < sl.g_groups && idx[r] < sl.n) ? sl.g[(int64_t)(c + cc) * sl.n + idx[r]] : 0.f;
-#pragma unroll
-            for (int cc = 0; cc < 4; ++cc)
-                if (c + cc < sl.g_groups) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) gs[r] += part[cc][r];
-                }
-        }
-    }
-    float sq = 0.f;
-    float wo[4], mo[4], vo[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const AdamStep o = adam_step(wi[r], gs[r], mi[r], vi[r], lr_t, b1, b2, eps, l2x2);
-        mo[r] = o.m; vo[r] = o.v; wo[r] = o.w;
-        if (idx[r] < sl.n) sq = fmaf(wi[r], wi[r], sq);
-    }
-    if (vec) {
-        if (idx[0] < sl.n) {
-            *reinterpret_cast<float4 *>(sl.m + idx[0]) = make_float4(mo[0], mo[1], mo[2], mo[3]);
-            *reinterpret_cast<float4 *>(sl.v + idx[0]) = make_float4(vo[0], vo[1], vo[2], vo[3]);
-            *reinterpret_cast<float4 *>(sl.w + idx[0]) = make_float4(wo[0], wo[1], wo[2], wo[3]);
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (idx[r] < sl.n) { sl.m[idx[r]] = mo[r]; sl.v[idx[r]] = vo[r]; sl.w[idx[r]] = wo[r]; }
-    }
-    if (loss_acc && sl.l2 != 0.f) {                                  // block sum, one atomic per block
-        __shared__ float red[4];
-        sq = wave_sum_stride<1>(sq);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
-        __syncthreads();
-        if (threadIdx.x == 0) atomicAdd(loss_acc, reg_scale * sl.l2 * (red[0] + red[1] + red[2] + red[3]));
     }
 }
 
@@ -2156,36 +2023,6 @@ int amar_add3_act_f32(const float *A, int64_t lda, const float *B, int64_t ldb, 
 int amar_transpose_f32(const float *src, int32_t K, int32_t N, float *dst, amar_stream_t stream) {
     if (K < 1 || N < 1 || !src || !dst) return AMAR_EINVAL;
     hipLaunchKernelGGL(transpose_kernel, dim3(grid1d((int64_t)K * N)), dim3(256), 0, static_cast<hipStream_t>(stream), src, K, N, dst);
-    return amar_check_launch();
-}
-
-int amar_adam_f32(float *w, const float *g, float *m, float *v, int64_t n, float lr_t, float beta_1, float beta_2,
-                  float epsilon, float l2, amar_stream_t stream) {
-    if (n < 0 || !w || !g || !m || !v) return AMAR_EINVAL;
-    if (n == 0) return AMAR_OK;
-    hipLaunchKernelGGL(adam_kernel, dim3(grid1d(n)), dim3(256), 0, static_cast<hipStream_t>(stream), w, g, m, v, n, lr_t, beta_1, beta_2, epsilon, 2.f * l2);
-    return amar_check_launch();
-}
-
-int amar_adam_advance_f32(float *state, float learning_rate, float beta_1, float beta_2, amar_stream_t stream) {
-    if (!state) return AMAR_EINVAL;
-    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), state, learning_rate, beta_1, beta_2);
-    return amar_check_launch();
-}
-
-int amar_adam_dev_f32(float *w, const float *g, float *m, float *v, int64_t n, const float *state, float beta_1, float beta_2,
-                      float epsilon, float l2, amar_stream_t stream) {
-    if (n < 0 || !w || !g || !m || !v || !state) return AMAR_EINVAL;
-    if (n == 0) return AMAR_OK;
-    hipLaunchKernelGGL(adam_dev_kernel, dim3(grid1d(n)), dim3(256), 0, static_cast<hipStream_t>(stream), w, g, m, v, n, state, beta_1, beta_2, epsilon, 2.f * l2);
-    return amar_check_launch();
-}
-
-int amar_adam_multi_f32(const amar_adam_slot *slots, int32_t n_slots, int64_t total_blocks, const float *state, float beta_1,
-                        float beta_2, float epsilon, float reg_scale, float *loss_acc, amar_stream_t stream) {
-    if (!slots || n_slots < 1 || total_blocks < 1 || total_blocks > 0x7fffffff || !state) return AMAR_EINVAL;
-    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), slots, n_slots, state,
-                       beta_1, beta_2, epsilon, reg_scale, loss_acc);
     return amar_check_launch();
 }
 

@@ -714,9 +714,9 @@ class DeviceSampler:
 
 
 _ADAM_HYPER = dict(learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7)
-# rule -> (AMAR_OPT_* name in capi, None = the amar_adam_* entry points; Keras' constructor defaults)
+# rule -> (AMAR_OPT_* name in capi, Keras' constructor defaults)
 OPTIMIZER_RULES = {
-    'Adam': (None, _ADAM_HYPER),
+    'Adam': ('OPT_ADAM', _ADAM_HYPER),
     'AMSGrad': ('OPT_AMSGRAD', _ADAM_HYPER),
     'SGD': ('OPT_SGD', dict(learning_rate=0.01, momentum=0.0, nesterov=False)),
     'RMSprop': ('OPT_RMSPROP', dict(learning_rate=1e-3, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False)),
@@ -757,14 +757,14 @@ class OptimizerSpec:
         self.values = {k: type(d)(given[k]) for k, d in defaults.items()}
         self.clip = self._checked_clip(clips)
         self.key = (self.rule, tuple(sorted(self.values.items())), self.clip) + ((self.schedule.key,) if self.schedule is not None else ())
-        self.adam = code is None
-        if not self.adam:
-            self.code = getattr(capi, code)
-            self.flags = (capi.OPT_NESTEROV if self.values.get('nesterov') else 0) | (capi.OPT_CENTERED if self.values.get('centered') else 0)
-            self.hyper = capi.optim_hyper(**{k: v for k, v in self.values.items() if k in dict(capi.OptimHyper._fields_)})
-            self.n_arrays = capi.optim_state_arrays(self.code, self.flags, self.values.get('momentum', 0.0))
-        else:
-            self.n_arrays = 2
+        self.code = getattr(capi, code)
+        self.flags = (capi.OPT_NESTEROV if self.values.get('nesterov') else 0) | (capi.OPT_CENTERED if self.values.get('centered') else 0)
+        self.hyper = capi.optim_hyper(**{k: v for k, v in self.values.items() if k in dict(capi.OptimHyper._fields_)})
+        self.n_arrays = capi.optim_state_arrays(self.code, self.flags, self.values.get('momentum', 0.0))
+
+    @property
+    def adam(self):
+        return self.rule == 'Adam'
 
     @staticmethod
     def _checked_schedule(rate, decay):
@@ -838,19 +838,14 @@ class Trainer:
         self._init_dropout()
 
     def _init_optimizer(self, optimizer, hyper):
-        """The rule (OptimizerSpec), the step count and every parameter's state arrays: Adam's m and v, or the 0 .. 3 arrays of another
-        rule together with its device state (step counter and step-dependent scalars: advanced by amar_optim_advance_f32 in the eager
-        and in the captured path alike, so the two are interchangeable step by step and Nadam's running product has one home)."""
+        """The rule (OptimizerSpec), the step count, every parameter's 0 .. 3 state arrays and the rule's device state (step counter and
+        step-dependent scalars: advanced by amar_optim_advance_f32 in the eager and in the captured path alike, so the two are
+        interchangeable step by step and Nadam's running product has one home; Adam uses its first two floats)."""
         self.spec = optimizer if isinstance(optimizer, OptimizerSpec) and not hyper else OptimizerSpec(optimizer, **hyper)
         self.t = 0
+        self._dev_t = 0                                              # the step count the device state holds (see _sync_step)
         self.opt_arrays = {p: self.spec.new_arrays(p) for p in self.params}
-        if self.spec.adam:
-            v = self.spec.values
-            self.lr, self.b1, self.b2, self.eps = v['learning_rate'], v['beta_1'], v['beta_2'], v['epsilon']
-            self.m = {p: a[0] for p, a in self.opt_arrays.items()}
-            self.v = {p: a[1] for p, a in self.opt_arrays.items()}
-        else:
-            self._opt_state = torch.zeros(capi.OPTIM_STATE_FLOATS, dtype=torch.float32, device=self.device)
+        self._opt_state = torch.zeros(capi.OPTIM_STATE_FLOATS, dtype=torch.float32, device=self.device)
         self.capture_count = 0                                       # hipGraph captures so far (a set learning rate must not add one)
         self._lr_state = None                                        # static rate: the launches are those of a trainer without schedules
         if self.spec.schedule is not None:
@@ -905,12 +900,7 @@ class Trainer:
         """The one-thread launch that opens an optimizer step: t + 1 and the step's scalars, under a dynamic rate also the rate."""
         spec = self.spec
         if self._lr_state is None:
-            if spec.adam:
-                capi.adam_advance(self._adam_state, self.lr, self.b1, self.b2)
-            else:
-                capi.optim_advance(self._opt_state, spec.code, spec.flags, spec.hyper)
-        elif spec.adam:
-            capi.adam_advance_lr(self._adam_state, self._lr_sched, self._lr_state, self.b1, self.b2)
+            capi.optim_advance(self._opt_state, spec.code, spec.flags, spec.hyper)
         else:
             capi.optim_advance_lr(self._opt_state, spec.code, spec.flags, spec.hyper, self._lr_sched, self._lr_state)
 
@@ -1073,7 +1063,7 @@ class Trainer:
     def _graph_body(self, upload_slots=False):
         g = self._g
         tapes = self._all_tapes()
-        for t in tapes:                                              # weight-gradient partials stay partial: the Adam launch below adds them
+        for t in tapes:                                              # weight-gradient partials stay partial: the update launch below adds them
             t.defer_reduce = True
         try:
             terms, grads = self._forward_backward(g['u'], g['i'], g['y'], (g['ub'], g['ib']) if g['ub'] is not None else None, ui=g['ui'])
@@ -1092,18 +1082,14 @@ class Trainer:
             g['clip_host'][:clip_host.numel()].copy_(clip_host)
             g['clip_bytes'] = int(clip_host.numel())
             flat = [(w, capi.finished_gradient(gr, w.numel()), 0.0) for w, gr, _ in flat]
-        if spec.adam:
-            entries = [(w, gr, self.m[prm].view(-1), self.v[prm].view(-1), l2) for prm, (w, gr, l2) in zip(self.params, flat)]
-            host, blocks = capi.adam_slot_table(entries)
-        else:
-            entries = [(w, gr, [a.view(-1) for a in self.opt_arrays[prm]], l2) for prm, (w, gr, l2) in zip(self.params, flat)]
-            host, blocks = capi.optim_slot_table(entries)
+        entries = [(w, gr, [a.view(-1) for a in self.opt_arrays[prm]], l2) for prm, (w, gr, l2) in zip(self.params, flat)]
+        host, blocks = capi.optim_slot_table(entries)
         g['slot_host'][:host.numel()].copy_(host)                    # pinned buffer allocated before the capture began
         g['slot_bytes'] = int(host.numel())                          # uploaded ONCE, right after the capture (train_batch_graphed), into a
         g['keep'] = entries                                          # buffer allocated BEFORE it (memory of the capture's own pool is reused
         #                                                              by the graph's temporaries): the table never changes — the slots point
         #                                                              into tensors of the graph
-        if upload_slots:                                             # (the same body run eagerly: this step's own table, before its Adam launch)
+        if upload_slots:                                             # (the same body run eagerly: this step's own table, before its update launch)
             self._upload_slots(g)
         batch = float(g['u'].numel())
         capi.sum_into(terms, self._loss_sum)                         # sum of the per-pair terms = data loss x batch size
@@ -1112,18 +1098,14 @@ class Trainer:
             capi.grad_clip(spec.clip_mode, spec.clip[1], g['clip_dev'], len(entries), blocks, g['clip_ws'],
                            reg_scale=batch, loss_acc=reg_acc)
             reg_acc = None
-        if spec.adam:
-            capi.adam_multi(g['slot_dev'], len(entries), blocks, self._adam_state, self.b1, self.b2, self.eps,
-                            reg_scale=batch, loss_acc=reg_acc)
-        else:
-            capi.optim_multi(spec.code, spec.flags, spec.hyper, g['slot_dev'], len(entries), blocks, self._opt_state,
-                             reg_scale=batch, loss_acc=reg_acc)
+        capi.optim_multi(spec.code, spec.flags, spec.hyper, g['slot_dev'], len(entries), blocks, self._opt_state,
+                         reg_scale=batch, loss_acc=reg_acc)
 
     def _slot_buffers(self, g):
         """The slot tables of a batch's buffers `g`: pinned host and device memory (and the clip pass's workspace), allocated before a
         capture begins."""
         n = len(self.params)
-        g['slot_host'] = torch.empty(64 * n + 64, dtype=torch.uint8).pin_memory()   # >= sizeof(amar_adam_slot) per parameter
+        g['slot_host'] = torch.empty(64 * n + 64, dtype=torch.uint8).pin_memory()   # >= sizeof(amar_optim_slot) per parameter
         g['slot_dev'] = torch.empty(64 * n + 64, dtype=torch.uint8, device=self.device)
         if self.spec.clip:
             blocks = sum((prm.numel() + 1023) // 1024 for prm in self.params)
@@ -1223,9 +1205,8 @@ class Trainer:
     def _init_graph_state(self):
         if not hasattr(self, '_graphs'):
             dev = self.device
-            self._graphs, self._seen, self._eager_loss, self._dev_t = {}, set(), 0.0, None
+            self._graphs, self._seen, self._eager_loss = {}, set(), 0.0
             self._eager_sampled, self._eager_batches = {}, {}
-            self._adam_state = torch.zeros(2, dtype=torch.float32, device=dev)
             self._loss_sum = torch.zeros((), dtype=torch.float32, device=dev)
 
     # -- batches drawn on the device (BPR: data/datasets.py:UserItemGraphPosNegSample) -------------------------------------------
@@ -1292,8 +1273,9 @@ class Trainer:
         return g
 
     def _sync_step(self):
-        if self.spec.adam and self._dev_t != self.t:                 # host steps happened in between: resynchronise the counter
-            self._adam_state[0] = float(self.t)                      # (the other rules count on the device in both paths)
+        if self.spec.adam and self._dev_t != self.t:                 # host steps happened in between (apply_gradients under a static
+            self._opt_state[0] = float(self.t)                       # rate): resynchronise the counter; the other rules count on the
+            #                                                          device in both paths
 
     def _advanced(self):
         self.t += 1
@@ -1389,42 +1371,34 @@ class Trainer:
         return c['g']
 
     def apply_gradients(self, grads):
-        dynamic_adam = self.spec.adam and self._lr_state is not None
-        if dynamic_adam:
+        spec = self.spec
+        host_step = spec.adam and self._lr_state is None
+        if not host_step:
             self._sync_step()                                        # (steps counted on the host before the rate became dynamic)
         self.t += 1
         l2_of = self._l2
-        if self.spec.clip:
+        if spec.clip:
             with torch.no_grad():
                 grads, l2_of = self._clipped(grads), lambda prm: 0.0
-        if dynamic_adam:
-            # the step size comes from the device state the replayed batches advance (amar_adam_dev_f32 reads it): a rate that a
-            # schedule or a callback moves is one state for both paths
-            with torch.no_grad():
-                self._advance_state()
-                for prm in self.params:
-                    capi.adam_dev(prm.data.view(-1), grads[prm].contiguous().view(-1), self.m[prm].view(-1), self.v[prm].view(-1),
-                                  self._adam_state, self.b1, self.b2, self.eps, l2=l2_of(prm))
-                    prm.add_(0)                                        # bumps the autograd version counter
-            self._dev_t = self.t
-            return
-        if not self.spec.adam:
-            spec = self.spec
-            with torch.no_grad():
-                self._advance_state()
-                for prm in self.params:
-                    capi.optim(spec.code, spec.flags, spec.hyper, prm.data.view(-1), grads[prm].contiguous().view(-1),
-                               [a.view(-1) for a in self.opt_arrays[prm]], self._opt_state, l2=l2_of(prm))
-                    prm.add_(0)                                        # bumps the autograd version counter
-            return
-        lr_t = self.lr * np.sqrt(1.0 - self.b2 ** self.t) / (1.0 - self.b1 ** self.t)
+        if host_step:
+            # The one place where Adam is not a rule like the others: under a static rate the eager step forms its step size here, from
+            # Python doubles (the rate not rounded to float32), and counts t on the host; _sync_step hands t to the device state before
+            # the next step that reads it.  The device scalars start from the float32 rate and can differ in the last bit, so moving
+            # this step onto them changes trained weights.
+            v = spec.values
+            lr_t = v['learning_rate'] * np.sqrt(1.0 - v['beta_2'] ** self.t) / (1.0 - v['beta_1'] ** self.t)
         with torch.no_grad():
+            if not host_step:
+                self._advance_state()                                # the device state the replayed batches advance: one state for both
             for prm in self.params:
-                g = grads[prm]
-                capi.adam(prm.data.view(-1), g.contiguous().view(-1), self.m[prm].view(-1), self.v[prm].view(-1),
-                          lr_t, self.b1, self.b2, self.eps, l2=l2_of(prm))
-                prm._version  # noqa: B018  (data-level update; bump below keeps hoisting caches honest)
-                prm.add_(0)                                            # bumps the autograd version counter
+                w, g, arrays = prm.data.view(-1), grads[prm].contiguous().view(-1), [a.view(-1) for a in self.opt_arrays[prm]]
+                if host_step:
+                    capi.adam(w, g, arrays[0], arrays[1], lr_t, v['beta_1'], v['beta_2'], v['epsilon'], l2=l2_of(prm))
+                else:
+                    capi.optim(spec.code, spec.flags, spec.hyper, w, g, arrays, self._opt_state, l2=l2_of(prm))
+                prm.add_(0)                                          # bumps the autograd version counter (hoisting caches key on it)
+        if not host_step:
+            self._dev_t = self.t
 
     def train_batch(self, u_ids, i_ids, y, bert=None):
         loss, grads = self.loss_and_grads(u_ids, i_ids, y, bert=bert)

@@ -778,10 +778,10 @@ int amar_sum_into_f32(const float *x, int64_t n, float scale, float *acc, amar_s
 int amar_adam_dev_f32(float *w, const float *g, float *m, float *v, int64_t n, const float *state, float beta_1, float beta_2,
                       float epsilon, float l2, amar_stream_t stream);
 
-/* ---- the other optimizers of tf.keras.optimizers (src/experiment.py:111,130-134: `parameters.optimizer.name` is a free choice) ----------
- * SGD, RMSprop, Adagrad, Adamax, Nadam and Adam(amsgrad=True), built like the Adam entry points above (which keep their bits): a step
- * counter and the step-dependent scalars in device memory, one launch for every parameter of a model, a single-tensor form reading the
- * same state.  The formulas below are the contract; they restate Keras 2's optimizer_v2 classes.  Common to all rules: g' = g + 2 l2 w
+/* ---- the optimizers of tf.keras.optimizers as rules (src/experiment.py:111,130-134: `parameters.optimizer.name` is a free choice) -------
+ * Adam, SGD, RMSprop, Adagrad, Adamax, Nadam and Adam(amsgrad=True): a step counter and the step-dependent scalars in device memory, one
+ * launch for every parameter of a model, a single-tensor form reading the same state.  The Adam entry points above are the AMAR_OPT_ADAM
+ * instantiations of the same kernels, over their own slot struct and two floats of state: the same bits either way.  The formulas below are the contract; they restate Keras 2's optimizer_v2 classes.  Common to all rules: g' = g + 2 l2 w
  * first (the L2 regulariser's gradient), t = 1 for the first step, `step` = state[1] of this step.  s0, s1, s2 are the rule's state arrays
  * in the order given; a rule neither reads nor writes the arrays it does not have (their pointers may be NULL).
  *
@@ -802,13 +802,16 @@ int amar_adam_dev_f32(float *w, const float *g, float *m, float *v, int64_t n, c
  *                                                   w -= lr ((1 - mu_t) g' / (1 - P_t) + mu_{t+1} m / (1 - P_t mu_{t+1})) / (sqrt(v / (1 - b2^t)) + epsilon)
  * AMAR_OPT_AMSGRAD  s0 = m, s1 = v, s2 = vhat:      Adam's m and v;  vhat = max(vhat, v);  w -= step m / (sqrt(vhat) + epsilon),
  *                                                   step = Adam's lr_t = lr sqrt(1 - b2^t) / (1 - b1^t)
+ * AMAR_OPT_ADAM     s0 = m, s1 = v:                 m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;  w -= step m / (sqrt(v) + epsilon),
+ *                                                   step = lr_t as above (amar_adam_dev_f32 / amar_adam_multi_f32)
  *
  * The device state is AMAR_OPTIM_STATE_FLOATS floats, zero before the first step:
- *   [0] t   [1] step (lr; Adamax, AMSGrad: as above)   and for Nadam   [2] mu_t   [3] mu_{t+1}   [4] P_t (the running product: read back
+ *   [0] t   [1] step (lr; Adamax, AMSGrad, Adam: as above)   and for Nadam   [2] mu_t   [3] mu_{t+1}   [4] P_t (the running product: read back
  *   at the next step)   [5] 1 - b2^t   [6] lr (1 - mu_t) / (1 - P_t)   [7] lr mu_{t+1} / (1 - P_t mu_{t+1})   (0 for the other rules).
  * amar_optim_advance_f32 (one thread, ordinary stores) sets [0] = t + 1 and the scalars of that step, computed in double from the float32
- * hyper-parameters.  The update kernels read lr from [1], the two Nadam coefficients from [6] and [7]: nothing that changes from step to
- * step is an argument, so a captured training batch replays as it is.
+ * hyper-parameters.  The update kernels read lr from [1], Nadam's also [3], [5], [6] and [7]: nothing that changes from step to
+ * step is an argument, so a captured training batch replays as it is.  AMAR_OPT_ADAM reads and writes [0] and [1] alone (the state of
+ * the amar_adam_* entry points, which is those two floats) and leaves [2] .. [7] as they are.
  * The single-tensor and the multi-slot form share one element function per rule (fused products written out, nothing else fused): they
  * give the same bits on the same element.  Unknown rule, flags the rule does not have, momentum < 0, null pointers (of arrays the rule
  * has), negative sizes: AMAR_EINVAL. */
@@ -818,6 +821,7 @@ int amar_adam_dev_f32(float *w, const float *g, float *m, float *v, int64_t n, c
 #define AMAR_OPT_ADAMAX   4
 #define AMAR_OPT_NADAM    5
 #define AMAR_OPT_AMSGRAD  6
+#define AMAR_OPT_ADAM     7
 #define AMAR_OPT_NESTEROV 0x100   /* flag of AMAR_OPT_SGD     */
 #define AMAR_OPT_CENTERED 0x200   /* flag of AMAR_OPT_RMSPROP */
 #define AMAR_OPTIM_STATE_FLOATS 8

@@ -429,7 +429,7 @@ def _multi_layout():
 
 
 def test_adam_multi_every_path(hip):
-    """adam_multi_kernel: vector and scalar path (by n % 4 and by alignment), block boundaries, deferred partial gradients in groups of 16
+    """optim_multi_kernel<V_ADAM> over amar_adam_slot: vector and scalar path (by n % 4 and by alignment), block boundaries, deferred partial gradients in groups of 16
     (vector) and 4 (scalar) with their tails, slot lookup by block number, the per-block atomic into loss_acc.  Every slot equals adam_dev on
     the partial gradients summed in order 0 .. G-1 in float32 bit for bit, and float64 within 1e-6; the memory between slots is untouched."""
     rng = np.random.default_rng(11)
@@ -522,8 +522,8 @@ def _run_golden_adam_case(hip):
 
 
 def test_adam_multi_keeps_the_recorded_bits(hip):
-    """The Adam kernels share one update (adam_step, csrc/amar_train.hip) whose fused products are those adam_multi_kernel — the kernel
-    every fit() runs — had before the three were unified: its results equal, bit for bit, the ones recorded from the library before that
+    """The Adam kernels share one update (optim_step, csrc/amar_optim.hip) whose fused products are those adam_multi_kernel — the kernel
+    every fit() ran — had before the three were unified: its results equal, bit for bit, the ones recorded from the library before that
     change (tests/golden/adam_multi_bits.npz), so trained weights did not move."""
     got, want = _run_golden_adam_case(hip), np.load(GOLDEN_ADAM)
     for key in 'wmv':

@@ -263,8 +263,7 @@ def test_replayed_batches_equal_eager_batches_under_a_schedule(hip, rule):
         assert torch.equal(eager._lr_state, graphed._lr_state)
         assert lref.ulps32(graphed._lr_state[1:].cpu().numpy(), [schedule(k)]).max() <= 1
     assert graphed._graphs and not eager._graphs and graphed.t == eager.t == 12
-    state = '_adam_state' if rule == 'Adam' else '_opt_state'
-    assert torch.equal(getattr(eager, state), getattr(graphed, state)) and float(getattr(eager, state)[0]) == 12
+    assert torch.equal(eager._opt_state, graphed._opt_state) and float(eager._opt_state[0]) == 12
 
 
 def test_replayed_head_and_bpr_loops_follow_a_schedule(hip):
@@ -309,7 +308,7 @@ def test_replayed_head_and_bpr_loops_follow_a_schedule(hip):
         eager.train_sampled(samplers[0], graph=False)
         graphed.train_sampled(samplers[1], graph=True)
     assert graphed._graphs and not eager._graphs and graphed.capture_count == 1
-    assert torch.equal(graphed._adam_state, eager._adam_state) and torch.equal(graphed._lr_state, eager._lr_state)
+    assert torch.equal(graphed._opt_state, eager._opt_state) and torch.equal(graphed._lr_state, eager._lr_state)
     assert lref.ulps32(graphed._lr_state[1:].cpu().numpy(), [schedule(7)]).max() <= 1 and _equal_models(eager.model, graphed.model)
 
 
@@ -359,11 +358,11 @@ def test_learning_rate_scheduler_equals_the_piecewise_schedule(hip):
     # one shape, one capture — made under the first set rate; the sets of epochs 1 and 2 add none
     assert spy.counts == [1, 1, 1] and trainer.capture_count == 1 and trainer.t == 9
     # a set is one float on the device: moments, step count and captured graphs stay, and the rate holds across fit() calls
-    moments = [m.clone() for m in trainer.m.values()]
+    moments = [a[0].clone() for a in trainer.opt_arrays.values()]
     training.set_learning_rate(by_callback, 0.003)
     assert training.get_learning_rate(by_callback) == float(np.float32(0.003))
-    assert trainer.t == 9 and trainer.capture_count == 1 and all(torch.equal(a, b) for a, b in zip(moments, trainer.m.values()))
-    assert float(trainer._adam_state[0]) == 9
+    assert trainer.t == 9 and trainer.capture_count == 1 and all(torch.equal(a, b) for a, b in zip(moments, (a[0] for a in trainer.opt_arrays.values())))
+    assert float(trainer._opt_state[0]) == 9
     again = by_callback.fit(seq_a, epochs=1, verbose=False)
     assert by_callback._trainer is trainer and again['lr'] == [float(np.float32(0.003))] and trainer.capture_count == 1 and trainer.t == 12
     # under a schedule the rate cannot be set (as in Keras), and is read off the schedule

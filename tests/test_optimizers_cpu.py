@@ -246,6 +246,40 @@ def test_argument_checks_need_no_device():
     assert lib.amar_optim_f32(capi.OPT_SGD, 0, ctypes.byref(hyper), None, None, None, None, None, -1, None, 0.0, None) == -1
     assert lib.amar_optim_multi_f32(77, 0, ctypes.byref(hyper), None, 1, 1, None, 0.0, None, None) == -1
     assert ctypes.sizeof(capi.OptimSlot) == 64 and ctypes.sizeof(capi.OptimHyper) == 24
+    # Adam as a rule: no flags, two arrays, refused like the others by every entry point that takes a rule
+    assert capi.optim_state_arrays(capi.OPT_ADAM) == 2 and lib.amar_optim_state_arrays(capi.OPT_ADAM, 0, 0.9) == 2
+    sched, dummy = capi.lr_schedule(None), ctypes.c_void_p(64)       # (a non-null address: the checks return before anything reads it)
+    for flag in (capi.OPT_NESTEROV, capi.OPT_CENTERED, 1):
+        assert lib.amar_optim_state_arrays(capi.OPT_ADAM, flag, 0.0) == -1
+        assert lib.amar_optim_advance_f32(dummy, capi.OPT_ADAM, flag, ctypes.byref(hyper), None) == -1
+        assert lib.amar_optim_f32(capi.OPT_ADAM, flag, ctypes.byref(hyper), dummy, dummy, dummy, dummy, None, 4, dummy, 0.0, None) == -1
+        assert lib.amar_optim_multi_f32(capi.OPT_ADAM, flag, ctypes.byref(hyper), dummy, 1, 1, dummy, 0.0, None, None) == -1
+        assert lib.amar_optim_advance_lr_f32(dummy, capi.OPT_ADAM, flag, ctypes.byref(hyper), ctypes.byref(sched), dummy, None) == -1
+    assert lib.amar_optim_f32(capi.OPT_ADAM, 0, ctypes.byref(hyper), dummy, dummy, dummy, None, None, 4, dummy, 0.0, None) == -1   # needs s1
+    assert lib.amar_optim_f32(capi.OPT_ADAM, 0, ctypes.byref(hyper), dummy, dummy, dummy, dummy, None, 0, dummy, 0.0, None) == 0   # n = 0
+
+
+def test_spec_keys_are_what_cached_trainers_were_stored_under():
+    """OptimizerSpec.key of eight representative specs, as literals taken from the commit before Adam became a rule of the shared
+    kernels: a cached trainer is reused by this key."""
+    from deep_cbrs_amar_renaissance_amd import training
+    from deep_cbrs_amar_renaissance_amd.utilities import schedules as S
+    adam = (('beta_1', 0.9), ('beta_2', 0.999), ('epsilon', 1e-07), ('learning_rate', 0.001))
+    adam32 = (('beta_1', 0.9), ('beta_2', 0.999), ('epsilon', 1e-07), ('learning_rate', 0.0010000000474974513))
+    S_ = training.OptimizerSpec
+    assert S_().key == ('Adam', adam, None)
+    assert S_(learning_rate=S.ExponentialDecay(1e-3, 100, 0.9)).key == ('Adam', adam32, None, ('ExponentialDecay', 0.001, 100, 0.9, False))
+    assert S_(decay=1e-4).key == ('Adam', adam32, None, ('InverseTimeDecay', 0.001, 1, 0.0001, False))
+    assert S_(clipnorm=1.0).key == ('Adam', adam, ('clipnorm', 1.0))
+    assert S_(rule='AMSGrad').key == ('AMSGrad', adam, None)
+    assert S_(rule='SGD', momentum=0.9, nesterov=True).key == ('SGD', (('learning_rate', 0.01), ('momentum', 0.9), ('nesterov', True)), None)
+    assert S_(rule='RMSprop', centered=True, momentum=0.5).key == \
+        ('RMSprop', (('centered', True), ('epsilon', 1e-07), ('learning_rate', 0.001), ('momentum', 0.5), ('rho', 0.9)), None)
+    assert S_(rule='Nadam').key == ('Nadam', adam, None)
+    spec = S_()
+    assert spec.adam and (spec.code, spec.flags, spec.n_arrays) == (7, 0, 2)
+    with pytest.raises(AttributeError):
+        spec.adam = False                                            # read-only
 
 
 def test_new_entry_points_are_declared_and_bound():
@@ -256,7 +290,7 @@ def test_new_entry_points_are_declared_and_bound():
         assert name in capi.SIGNATURES, name
         assert name in declared, name
     for define, value in (('AMAR_OPT_SGD', capi.OPT_SGD), ('AMAR_OPT_RMSPROP', capi.OPT_RMSPROP), ('AMAR_OPT_ADAGRAD', capi.OPT_ADAGRAD),
-                          ('AMAR_OPT_ADAMAX', capi.OPT_ADAMAX), ('AMAR_OPT_NADAM', capi.OPT_NADAM), ('AMAR_OPT_AMSGRAD', capi.OPT_AMSGRAD),
+                          ('AMAR_OPT_ADAMAX', capi.OPT_ADAMAX), ('AMAR_OPT_NADAM', capi.OPT_NADAM), ('AMAR_OPT_AMSGRAD', capi.OPT_AMSGRAD), ('AMAR_OPT_ADAM', capi.OPT_ADAM),
                           ('AMAR_OPT_NESTEROV', capi.OPT_NESTEROV), ('AMAR_OPT_CENTERED', capi.OPT_CENTERED),
                           ('AMAR_OPTIM_STATE_FLOATS', capi.OPTIM_STATE_FLOATS)):
         found = re.search(r'#define\s+' + define + r'\s+(\w+)', header)

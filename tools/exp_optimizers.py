@@ -50,13 +50,10 @@ def main():
         for e in g['keep']:
             grad = e[1]
             floats += e[0].numel() * (2 + 2 * tr.spec.n_arrays) + (grad.partials.numel() if isinstance(grad, capi.DeferredGradient) else grad.numel())
-        if tr.spec.adam:
-            def launch(tr=tr, g=g, n_slots=n_slots, blocks=blocks):
-                capi.adam_multi(g['slot_dev'], n_slots, blocks, tr._adam_state, tr.b1, tr.b2, tr.eps, reg_scale=float(bs), loss_acc=tr._loss_sum)
-        else:
-            def launch(tr=tr, g=g, n_slots=n_slots, blocks=blocks):
-                s = tr.spec
-                capi.optim_multi(s.code, s.flags, s.hyper, g['slot_dev'], n_slots, blocks, tr._opt_state, reg_scale=float(bs), loss_acc=tr._loss_sum)
+
+        def launch(tr=tr, g=g, n_slots=n_slots, blocks=blocks):
+            s = tr.spec
+            capi.optim_multi(s.code, s.flags, s.hyper, g['slot_dev'], n_slots, blocks, tr._opt_state, reg_scale=float(bs), loss_acc=tr._loss_sum)
         name = rule + ''.join('+' + k for k, v in hyper.items() if v)
         launches.append({'rule': name, 'launch': launch, 'bytes': 4 * floats, 'keep': (tr, model), 'events': [],
                          'state_arrays': tr.spec.n_arrays, 'parameters': sum(e[0].numel() for e in g['keep']), 'slots': n_slots})
