@@ -39,6 +39,7 @@ SIGNATURES = {
     'amar_colmax_f32': (ctypes.c_int, [_P, _I64, _P, _P]),
     'amar_spmm_lt_f32': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _I32, _P, _P, _I64, _I32, _I32, _U32, _P,
                                         _P, _I64, _P, _I64, _F32, _P, _I32, _P, _I64, _P]),
+    'amar_propagate_route': (ctypes.c_int, [_I32, _I64, _I64, _I32, _U32, _P]),
     'amar_gat_xs_f32': (ctypes.c_int, [_P, _P, _I32, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P]),
     'amar_gcn_layer_f32': (ctypes.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _I64, _P, _I32, _P, _I64, _I32, _P]),
     'amar_rowwise_xw_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I32, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I32, _P]),
@@ -403,6 +404,44 @@ def spmm_lt(lt, X, Y=None, bias=None, relu=False, acc_in=None, acc_out=None, acc
         _ptr(Wnext, torch.float32, 'Wnext'), Cn, _ptr(Hnext, torch.float32, 'Hnext'),
         _ld(Hnext, 'Hnext') if Hnext is not None else 0, _stream())
     _check(code, 'amar_spmm_lt_f32')
+
+
+PROPAGATE_KINDS = {'lt': 0, 'gat_lt': 1, 'xs': 2, 'gat_xs': 3}
+ADDR_64, ADDR_32, ADDR_32_DENSE = 0, 1, 2
+LT_KERNELS = ('pairs', 'nopairs', 'sage_tail', 'unsupported')
+
+
+class PropagateRouteInfo(ctypes.Structure):
+    """include/amar_hip.h: amar_propagate_route_info"""
+    _fields_ = [(name, ctypes.c_int32) for name in ('form', 'kernel', 'col_bits', 'reserved')] + \
+               [(name, ctypes.c_int64) for name in ('max_cols', 'span_bytes')]
+
+    def as_dict(self):
+        return {'form': int(self.form), 'kernel': LT_KERNELS[self.kernel], 'col_bits': int(self.col_bits),
+                'max_cols': int(self.max_cols), 'span_bytes': int(self.span_bytes)}
+
+
+def propagate_route(kind, n_cols, ld, width, flags=0, code=False):
+    """Which gather-address form (0: 64-bit, 1: 32-bit byte offsets, 2: 32-bit offsets into a dense table) and, for 'lt', which kernel
+    ('pairs' | 'nopairs' | 'sage_tail' | 'unsupported') a spmm_lt / gat_lt / spmm_xs / gat_xs call over a table of `n_cols` rows with
+    leading dimension `ld` takes (amar_propagate_route: host only, the launchers ask the same function).  kind: 'lt' | 'gat_lt' | 'xs' |
+    'gat_xs'; flags: SPMM_SAGE_TAIL / SPMM_LT_NOPAIRS.  A dict with `code` = the launcher's return code for these arguments added when
+    code=True (nothing raised), else raises as the launcher's wrapper would."""
+    info = PropagateRouteInfo()
+    rc = load().amar_propagate_route(PROPAGATE_KINDS[kind], int(n_cols), int(ld), int(width), int(flags), ctypes.byref(info))
+    if not code:
+        _check(rc, 'amar_propagate_route')
+    d = info.as_dict()
+    if code:
+        d['code'] = int(rc)
+    return d
+
+
+def sage_tail_on_lt_supported(x, f):
+    """Whether spmm_lt's fused GraphSAGE tail (sage_tail=...) has a kernel for the table `x` [n_cols, f] as it lies in memory:
+    amar_spmm_lt_f32's own decision (widths 8 / 16 / 32 and a table whose span stays below 2^32 bytes), from shapes and strides alone."""
+    r = propagate_route('lt', x.shape[0], _ld(x, 'x'), f, SPMM_SAGE_TAIL, code=True)
+    return r['code'] == 0 and r['kernel'] == 'sage_tail'
 
 
 def gcn_layer(rowptr, colidx, vals, H, bias, Y, Wnext=None, Hnext=None):

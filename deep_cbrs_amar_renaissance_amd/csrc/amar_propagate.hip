@@ -996,7 +996,11 @@ __global__ __launch_bounds__(LT_WAVES * AMAR_WAVE, AMAR_LT_MIN_WAVES) void spmm_
 }
 
 template <int F>
-int launch_spmm_lt(const LtArgs &a, int n_tiles, int off32, bool fuse, int variant, bool sage, bool nopairs, hipStream_t st) {
+int launch_spmm_lt(const LtArgs &a, int n_tiles, const amar_propagate_route_info &route, bool fuse, int variant, hipStream_t st) {
+    // the address form and the kernel variant are propagate_route's decision (amar_propagate_route reports the same)
+    const int off32 = route.form;
+    const bool sage = route.kernel == AMAR_LT_KERNEL_SAGE_TAIL, nopairs = route.kernel == AMAR_LT_KERNEL_NOPAIRS;
+    if (route.kernel == AMAR_LT_KERNEL_UNSUPPORTED || off32 < 0) return AMAR_EUNSUPPORTED;
     constexpr int RW = LT_TILE_BYTES / (4 * F * LT_WAVES);
     const size_t lds = (size_t)LT_WAVES * RW * F * 4 + (size_t)LT_WAVES * LT_CHUNK * 4 + 32;
     const dim3 grid((unsigned)n_tiles), block(LT_WAVES * AMAR_WAVE);
@@ -1011,11 +1015,10 @@ int launch_spmm_lt(const LtArgs &a, int n_tiles, int off32, bool fuse, int varia
 #define AMAR_LT_LAUNCH(OFF, FUSE, PP, AA) AMAR_LT_LAUNCH_S(OFF, FUSE, PP, AA, false)
     if constexpr (F >= 8) {
         if (sage) {                                                   // GraphSAGE tail fused (the layer's input is a dense table or a concat slice)
-            if (off32 == 2) AMAR_LT_LAUNCH_S(2, false, 1, 0, true); else if (off32 == 1) AMAR_LT_LAUNCH_S(1, false, 1, 0, true);
-            else return AMAR_EUNSUPPORTED;
+            if (off32 == 2) AMAR_LT_LAUNCH_S(2, false, 1, 0, true); else AMAR_LT_LAUNCH_S(1, false, 1, 0, true);
             return amar_check_launch();
         }
-    } else if (sage) return AMAR_EUNSUPPORTED;
+    }
     // variant (AMAR_LT_VARIANT; F = 8, dense table, no fused next layer only): the on-chip floor of bench.py --full, wrong sums
     if constexpr (F == 8) {
         if (variant && off32 == 2 && !fuse) {
@@ -1028,7 +1031,7 @@ int launch_spmm_lt(const LtArgs &a, int n_tiles, int off32, bool fuse, int varia
         }
     }
     if constexpr (F >= 8) {
-        if (nopairs && off32 != 0) {                                  // an image without implicit pairs: the lean step (see PAIRS above)
+        if (nopairs) {                                                // an image without implicit pairs: the lean step (see PAIRS above)
             if (off32 == 2) { if (fuse) AMAR_LT_LAUNCH_P(2, true, 1, 0, false, false); else AMAR_LT_LAUNCH_P(2, false, 1, 0, false, false); }
             else { if (fuse) AMAR_LT_LAUNCH_P(1, true, 1, 0, false, false); else AMAR_LT_LAUNCH_P(1, false, 1, 0, false, false); }
             return amar_check_launch();
@@ -1078,6 +1081,52 @@ __global__ __launch_bounds__(256) void colmax_kernel(const float *__restrict__ x
 }
 
 bool ld_ok(int64_t ld, int F) { return ld >= F && (ld & 3) == 0; }
+
+// ---- the gather-address form of the tiled propagation kernels ------------------------------------------------------------
+// ONE decision for the four families that pick their address arithmetic from the size of the table they gather from
+// (spmm_lt_kernel, its GAT mode, spmm_xs_partial_kernel, gat_xs_partial_kernel): the launchers below and the host-only query
+// amar_propagate_route both call it, so what the query reports is what a launch with those arguments runs.
+//   form  AMAR_ADDR_64 (0): X + (int64)col * ld;  AMAR_ADDR_32 (1): byte offset (col * (unsigned)ld + 4 q) * 4 < 2^32;
+//         AMAR_ADDR_32_DENSE (2): the same with a compile-time row width (LT: ld == F; GAT_XS: the packed table, 2C wide).
+//   The span that must stay below 2^32 bytes is n_cols * ld * 4 (GAT_XS: n_cols * 2C * 4, whatever ld): the largest offset
+//   a gather forms is ((n_cols - 1) * ld + F - 4) * 4 + 12 < span.
+// Refusals come in the launchers' own order; `form` stays -1 when an argument is refused before the form is decided.
+int propagate_route(int kind, int64_t n_cols, int64_t ld, int width, uint32_t flags, amar_propagate_route_info *r) {
+    r->form = -1; r->kernel = AMAR_LT_KERNEL_PAIRS; r->col_bits = 0; r->reserved = 0; r->max_cols = 0; r->span_bytes = 0;
+    if (n_cols < 0) return AMAR_EINVAL;
+    const bool lt = kind == AMAR_PROPAGATE_LT, gat_lt = kind == AMAR_PROPAGATE_GAT_LT;
+    const bool xs = kind == AMAR_PROPAGATE_XS, gat_xs = kind == AMAR_PROPAGATE_GAT_XS;
+    if (!lt && !gat_lt && !xs && !gat_xs) return AMAR_EINVAL;
+    const bool width_ok = lt ? (width == 4 || width == 8 || width == 16 || width == 32)
+                        : xs ? (width == 4 || width == 8 || width == 16 || width == 32 || width == 64)
+                             : (width == 8 || width == 16 || width == 32);
+    // the XS kinds check the leading dimension first (their width switch comes last), the LT kinds the width and the columns
+    const bool ld_bad = gat_xs ? ld < width : !ld_ok(ld, width);
+    if ((xs || gat_xs) && ld_bad) return AMAR_EINVAL;
+    if (!width_ok) return AMAR_EUNSUPPORTED;
+    // the packed entry word: LT keeps the LDS row above the column (RW rows per wave), XS the row inside its 64-row block
+    r->col_bits = lt ? 31 - lt_bits(LT_TILE_BYTES / (4 * width * LT_WAVES)) : gat_lt ? 31 - lt_bits(lt_gat_rw(width)) : 26;
+    r->max_cols = int64_t(1) << r->col_bits;
+    if (n_cols > r->max_cols) return AMAR_EUNSUPPORTED;
+    if ((lt || gat_lt) && ld_bad) return AMAR_EINVAL;
+    const int64_t row_floats = gat_xs ? 2 * (int64_t)width : ld;
+    if (row_floats > (int64_t(1) << 34)) return AMAR_EINVAL;             // (the span below must not wrap)
+    r->span_bytes = n_cols * row_floats * 4;
+    const bool fits32 = r->span_bytes < (int64_t(1) << 32);
+    r->form = !fits32 ? AMAR_ADDR_64 : (gat_xs || ((lt || gat_lt) && ld == width)) ? AMAR_ADDR_32_DENSE : AMAR_ADDR_32;
+    if (lt) {
+        if (flags & AMAR_SPMM_SAGE_TAIL) {
+            // the fused GraphSAGE tail is instantiated for the 32-bit forms of F >= 8 only
+            r->kernel = (width >= 8 && r->form != AMAR_ADDR_64) ? AMAR_LT_KERNEL_SAGE_TAIL : AMAR_LT_KERNEL_UNSUPPORTED;
+            if (r->kernel == AMAR_LT_KERNEL_UNSUPPORTED) return AMAR_EUNSUPPORTED;
+        } else if ((flags & AMAR_SPMM_LT_NOPAIRS) && width >= 8 && r->form != AMAR_ADDR_64) {
+            r->kernel = AMAR_LT_KERNEL_NOPAIRS;
+        }
+        // else the kernel with the pair logic: right on an image without pairs too (every repeat there is flagged, so the
+        // pair test never fires), which is what the 64-bit form and F = 4 run under AMAR_SPMM_LT_NOPAIRS
+    }
+    return AMAR_OK;
+}
 
 // The row kernels are instantiated for widths 4, 8, 16, 32, 64.  Every operation below that is separable by feature
 // column (SpMM and its bias / ReLU / running-sum epilogue, the GAT aggregation once the per-node attention scalars
@@ -1921,14 +1970,15 @@ int amar_gat_xs_f32(const int32_t *rowptr, const int32_t *colidx, int32_t n_slic
     if (n_rows < 0 || n_slices < 1 || !rowptr || !H || !s_self || !s_neigh || !bias || !packed || !partials || !Y) return AMAR_EINVAL;
     if (n_cols < n_rows || row_offset < 0 || row_offset + n_rows > n_cols) return AMAR_EINVAL;
     if (ldh < C || ldy < C || !amar_aligned16(packed) || !amar_aligned16(partials)) return AMAR_EINVAL;
-    if (C != 8 && C != 16 && C != 32) return AMAR_EUNSUPPORTED;
+    amar_propagate_route_info route;
+    if (const int rc = propagate_route(AMAR_PROPAGATE_GAT_XS, n_cols, ldh, C, 0u, &route)) return rc;
     if (n_rows == 0) return AMAR_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t total = (int64_t)n_cols * (2 * C);
     hipLaunchKernelGGL(gat_pack_kernel, dim3((unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256)), dim3(256), 0, st,
                        H, ldh, s_neigh, packed, n_cols, C);
     GatXsArgs pa{rowptr, colidx, packed, s_self, partials, n_rows, n_slices,
-                 (n_rows + XS_WAVES * AMAR_WAVE - 1) / (XS_WAVES * AMAR_WAVE), (int64_t)n_cols * (2 * C) * 4 < (int64_t(1) << 32), row_offset};
+                 (n_rows + XS_WAVES * AMAR_WAVE - 1) / (XS_WAVES * AMAR_WAVE), route.form != AMAR_ADDR_64, row_offset};
     const dim3 pgrid((unsigned)(pa.blocks_per_slice * pa.n_slices)), block(XS_WAVES * AMAR_WAVE);
     GatXsCombineArgs ca{partials, rowptr, packed, s_self, bias, Y, ldy, n_rows, n_slices, self_loop ? 1 : 0, row_offset};
     const dim3 cgrid((n_rows + 255) / 256);
@@ -1985,7 +2035,9 @@ int amar_spmm_xs_f32(const float *diag, const int32_t *rowptr, const int32_t *co
     // colidx / vals may be NULL when the matrix has no off-diagonal entry (every segment is then empty)
     const bool accum = flags & AMAR_SPMM_ACCUM;
     if (!Y && !accum) return AMAR_EINVAL;
-    if (!ld_ok(ldx, F) || !amar_aligned16(X) || !amar_aligned16(partials)) return AMAR_EINVAL;
+    amar_propagate_route_info route;
+    const int route_rc = propagate_route(AMAR_PROPAGATE_XS, n_cols, ldx, F, flags, &route);
+    if (route_rc == AMAR_EINVAL || !amar_aligned16(X) || !amar_aligned16(partials)) return AMAR_EINVAL;   // (the leading dimension)
     if (Y && (!ld_ok(ldy, F) || !amar_aligned16(Y))) return AMAR_EINVAL;
     if ((flags & AMAR_SPMM_BIAS) && (!bias || !amar_aligned16(bias))) return AMAR_EINVAL;
     if (accum && (!acc_in || !acc_out || !ld_ok(ld_acc_in, F) || !ld_ok(ld_acc_out, F) ||
@@ -1995,9 +2047,10 @@ int amar_spmm_xs_f32(const float *diag, const int32_t *rowptr, const int32_t *co
     if (Wnext && Cn > 64) return AMAR_EUNSUPPORTED;
     if ((flags & AMAR_SPMM_SCALE_NEXT) && (!row_scale || !Wnext)) return AMAR_EINVAL;
     if ((vals != nullptr) == (row_scale != nullptr) && colidx) return AMAR_EINVAL;   // exactly one of them (unless there are no entries)
+    if (route_rc != AMAR_OK) return route_rc;                         // a width without a kernel, more columns than the entry word holds
     XsArgs pa{rowptr, colidx, vals, X, ldx, partials, n_rows, n_slices,
               (n_rows + XS_WAVES * AMAR_WAVE - 1) / (XS_WAVES * AMAR_WAVE),
-              (int64_t)n_cols * ldx * 4 < (int64_t(1) << 32)};
+              route.form != AMAR_ADDR_64};
     XsCombineArgs ca{};
     ca.diag = diag; ca.P = partials; ca.rowptr = rowptr; ca.n_slices = n_slices; ca.row_scale = row_scale; ca.Xself = Xself;
     ca.e.next_scale = (flags & AMAR_SPMM_SCALE_NEXT) ? row_scale : nullptr;
@@ -2027,17 +2080,15 @@ int amar_spmm_lt_f32(const int32_t *words, const int32_t *stream_start, const in
     if (n_rows < 0 || n_cols < 0 || n_tiles < 0 || maxwin1 < 1 || pace_every < 1 || (pace_every & (pace_every - 1))) return AMAR_EINVAL;
     if (n_rows == 0 || n_tiles == 0) return n_rows == 0 ? AMAR_OK : AMAR_EINVAL;
     if (!words || !stream_start || !wsteps || !tile_row0 || !n_win || !vstart || !vcount || !diag || !row_scale || !X) return AMAR_EINVAL;
-    if (F != 4 && F != 8 && F != 16 && F != 32) return AMAR_EUNSUPPORTED;
-    const int rw = LT_TILE_BYTES / (4 * F * LT_WAVES);
-    int lbits = 0;
-    while ((1 << lbits) < rw) ++lbits;
-    const int cbits = 31 - lbits;
-    if ((int64_t)n_cols > (int64_t(1) << cbits)) return AMAR_EUNSUPPORTED;
+    amar_propagate_route_info route;
+    const int route_rc = propagate_route(AMAR_PROPAGATE_LT, n_cols, ldx, F, flags, &route);
+    if (route_rc != AMAR_OK && route.form < 0) return route_rc;      // width, column bits, leading dimension (a refused variant: below)
+    const int cbits = route.col_bits;
     if (!Xself) { if (n_cols < n_rows) return AMAR_EINVAL; Xself = X; }
     if (!amar_aligned16(Xself) || !amar_aligned16(words)) return AMAR_EINVAL;
     const bool accum = flags & AMAR_SPMM_ACCUM;
     if (!Y && !accum) return AMAR_EINVAL;
-    if (!ld_ok(ldx, F) || !amar_aligned16(X)) return AMAR_EINVAL;
+    if (!amar_aligned16(X)) return AMAR_EINVAL;
     if (Y && (!ld_ok(ldy, F) || !amar_aligned16(Y))) return AMAR_EINVAL;
     if ((flags & AMAR_SPMM_BIAS) && (!bias || !amar_aligned16(bias))) return AMAR_EINVAL;
     if (accum && (!acc_in || !acc_out || !ld_ok(ld_acc_in, F) || !ld_ok(ld_acc_out, F) ||
@@ -2062,17 +2113,21 @@ int amar_spmm_lt_f32(const int32_t *words, const int32_t *stream_start, const in
     a.e.acc_in = acc_in; a.e.ld_acc_in = ld_acc_in; a.e.acc_out = acc_out; a.e.ld_acc_out = ld_acc_out;
     a.e.acc_div = acc_div; a.e.accum = accum ? 1 : 0; a.e.accum_div = (flags & AMAR_SPMM_ACCUM_DIV) ? 1 : 0;
     a.e.Wn = Wnext; a.e.Cn = Cn; a.e.Hn = Hnext; a.e.ldhn = ldhn; a.e.n_rows = n_rows;
-    const int off32 = (int64_t)n_cols * ldx * 4 < (int64_t(1) << 32) ? (ldx == F ? 2 : 1) : 0;
-    const bool nopairs = (flags & AMAR_SPMM_LT_NOPAIRS) != 0;
+    if (route_rc != AMAR_OK) return route_rc;                        // the fused GraphSAGE tail has no 64-bit form
     const char *venv = getenv("AMAR_LT_VARIANT");               // on-chip floor of bench.py --full (24, 35)
     const int variant = venv ? atoi(venv) : 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (F) {
-    case 4:  return launch_spmm_lt<4>(a, n_tiles, off32, Wnext != nullptr && !sage, variant, sage, nopairs, st);
-    case 8:  return launch_spmm_lt<8>(a, n_tiles, off32, Wnext != nullptr && !sage, variant, sage, nopairs, st);
-    case 16: return launch_spmm_lt<16>(a, n_tiles, off32, Wnext != nullptr && !sage, variant, sage, nopairs, st);
-    default: return launch_spmm_lt<32>(a, n_tiles, off32, Wnext != nullptr && !sage, variant, sage, nopairs, st);
+    case 4:  return launch_spmm_lt<4>(a, n_tiles, route, Wnext != nullptr && !sage, variant, st);
+    case 8:  return launch_spmm_lt<8>(a, n_tiles, route, Wnext != nullptr && !sage, variant, st);
+    case 16: return launch_spmm_lt<16>(a, n_tiles, route, Wnext != nullptr && !sage, variant, st);
+    default: return launch_spmm_lt<32>(a, n_tiles, route, Wnext != nullptr && !sage, variant, st);
     }
+}
+
+int amar_propagate_route(int32_t kind, int64_t n_cols, int64_t ld, int32_t width, uint32_t flags, amar_propagate_route_info *info) {
+    if (!info) return AMAR_EINVAL;
+    return propagate_route(kind, n_cols, ld, width, flags, info);
 }
 
 int amar_colmax_f32(const float *x, int64_t n, float *out, amar_stream_t stream) {
@@ -2102,9 +2157,10 @@ int amar_gat_lt_f32(const int32_t *words, const int32_t *stream_start, const int
         !H || !s_self || !s_neigh || !s_neigh_max || !bias || !Y) return AMAR_EINVAL;
     if (C != 8 && C != 16 && C != 32) return AMAR_EUNSUPPORTED;
     if ((int64_t)row_offset + n_rows > n_cols) return AMAR_EINVAL;
-    const int cbits = 31 - lt_bits(lt_gat_rw(C));
-    if ((int64_t)n_cols > (int64_t(1) << cbits)) return AMAR_EUNSUPPORTED;
-    if (!ld_ok(ldh, C) || !amar_aligned16(H) || !ld_ok(ldy, C) || !amar_aligned16(Y) || !amar_aligned16(bias) || !amar_aligned16(words)) return AMAR_EINVAL;
+    amar_propagate_route_info route;
+    if (const int rc = propagate_route(AMAR_PROPAGATE_GAT_LT, n_cols, ldh, C, 0u, &route)) return rc;
+    const int cbits = route.col_bits;
+    if (!amar_aligned16(H) || !ld_ok(ldy, C) || !amar_aligned16(Y) || !amar_aligned16(bias) || !amar_aligned16(words)) return AMAR_EINVAL;
     LtArgs a{};
     a.words = words; a.stream_start = stream_start; a.wsteps = wsteps; a.tile_row0 = tile_row0; a.n_win = n_win;
     a.vstart = vstart; a.vcount = vcount;
@@ -2113,7 +2169,7 @@ int amar_gat_lt_f32(const int32_t *words, const int32_t *stream_start, const int
     a.s_neigh = s_neigh; a.bmax = s_neigh_max; a.s_self_rows = s_self + row_offset; a.s_neigh_rows = s_neigh + row_offset;
     a.csr_rowptr = rowptr; a.csr_colidx = colidx; a.self_loop = self_loop ? 1 : 0;
     a.e.X = H; a.e.ldx = ldh; a.e.Y = Y; a.e.ldy = ldy; a.e.bias = bias; a.e.relu = 1; a.e.n_rows = n_rows;
-    const int off32 = (int64_t)n_cols * ldh * 4 < (int64_t(1) << 32) ? (ldh == C ? 2 : 1) : 0;
+    const int off32 = route.form;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (C) {
     case 8:  return launch_gat_lt<8>(a, n_tiles, off32, st);

@@ -107,7 +107,7 @@ class GraphSageConv(Layer):
         if kind == 'xs' and f == self.channels and f in (8, 16, 32):
             from deep_cbrs_amar_renaissance_amd.utilities.lds_tiled import LdsTiled
             img = self._image(a, f)
-            if isinstance(img, LdsTiled) and (x.stride(0) == f or x.shape[0] * x.stride(0) * 4 < (1 << 32)):
+            if isinstance(img, LdsTiled) and capi.sage_tail_on_lt_supported(x, f):     # (a span of 2^32 bytes and more: two launches)
                 # mean / sum aggregate and the layer's tail in ONE launch: the tile's sums never leave the workgroup
                 capi.spmm_lt(img, x, out, prescaled=True, sage_tail=(self.kernel, self.bias), Hnext=dense_out)
                 self._dense_filled = dense_out is not None

@@ -143,6 +143,49 @@ int amar_spmm_lt_f32(const int32_t *words, const int32_t *stream_start, const in
                      const float *acc_in, int64_t ld_acc_in, float *acc_out, int64_t ld_acc_out, float acc_div,
                      const float *Wnext, int32_t Cn, float *Hnext, int64_t ldhn, amar_stream_t stream);
 
+/* Which gather-address form a tiled propagation launch takes (host only: launches nothing, reads no device memory).  The four
+ * kernel families that gather rows of a node table pick their address arithmetic from the table's SPAN, n_cols * ld * 4 bytes
+ * (the packed table of amar_gat_xs_f32: n_cols * 2C * 4, whatever ldh), in one host function that the launchers and this
+ * query share — so a test can assert the form a call runs before it launches it.
+ *   kind      AMAR_PROPAGATE_LT      amar_spmm_lt_f32   (n_cols, ldx, F, flags)
+ *             AMAR_PROPAGATE_GAT_LT  amar_gat_lt_f32    (n_cols, ldh, C; flags ignored)
+ *             AMAR_PROPAGATE_XS      amar_spmm_xs_f32   (n_cols, ldx, F; flags ignored)
+ *             AMAR_PROPAGATE_GAT_XS  amar_gat_xs_f32    (n_cols, ldh, C; flags ignored)
+ *   form      AMAR_ADDR_64        span >= 2^32: X + (int64) column * ld
+ *             AMAR_ADDR_32        span <  2^32: one 32-bit byte offset (column * ld + 4 q) * 4 from a scalar base
+ *             AMAR_ADDR_32_DENSE  span <  2^32 and a compile-time row width (LT kinds: ld == width, a shift; GAT_XS: the packed
+ *                                 table).  AMAR_PROPAGATE_XS has no dense form: its 32-bit form is AMAR_ADDR_32 at every ld.
+ *             -1 when an argument was refused before the form was decided
+ *   kernel    AMAR_PROPAGATE_LT only (0 otherwise): AMAR_LT_KERNEL_PAIRS (the step with the implicit-pair logic),
+ *             AMAR_LT_KERNEL_NOPAIRS (AMAR_SPMM_LT_NOPAIRS, F >= 8, a 32-bit form; on the 64-bit form and at F = 4 an image
+ *             without pairs runs the PAIRS kernel, which is right for it: every repeat is flagged), AMAR_LT_KERNEL_SAGE_TAIL
+ *             (AMAR_SPMM_SAGE_TAIL, F >= 8, a 32-bit form), AMAR_LT_KERNEL_UNSUPPORTED (AMAR_SPMM_SAGE_TAIL otherwise: the call
+ *             returns AMAR_EUNSUPPORTED and the caller takes the aggregate + amar_sage_tail_f32).  The AMAR_LT_VARIANT
+ *             development kernels are not reported.
+ *   col_bits, max_cols = 2^col_bits   columns the packed entry word holds: 31 - ceil(log2(RW)) for the LT kinds (22 / 23 / 24 /
+ *             25 at F = 4 / 8 / 16 / 32; GAT: 23 / 24 / 25 at C = 8 / 16 / 32), 26 for the XS kinds.  n_cols == max_cols is
+ *             accepted, one more returns AMAR_EUNSUPPORTED (from the query and from all four launchers).
+ *   span_bytes  the span compared against 2^32
+ * Returns what the launcher returns for these arguments where it looks at nothing else: AMAR_EINVAL (n_cols < 0, an unknown kind,
+ * ld < width or, except GAT_XS, ld % 4 != 0, info == NULL), AMAR_EUNSUPPORTED (a width without a kernel, n_cols > max_cols, the
+ * GraphSAGE tail without a kernel), in the launcher's order of checks. */
+#define AMAR_PROPAGATE_LT 0
+#define AMAR_PROPAGATE_GAT_LT 1
+#define AMAR_PROPAGATE_XS 2
+#define AMAR_PROPAGATE_GAT_XS 3
+#define AMAR_ADDR_64 0
+#define AMAR_ADDR_32 1
+#define AMAR_ADDR_32_DENSE 2
+#define AMAR_LT_KERNEL_PAIRS 0
+#define AMAR_LT_KERNEL_NOPAIRS 1
+#define AMAR_LT_KERNEL_SAGE_TAIL 2
+#define AMAR_LT_KERNEL_UNSUPPORTED 3
+typedef struct amar_propagate_route_info {
+    int32_t form, kernel, col_bits, reserved;
+    int64_t max_cols, span_bytes;
+} amar_propagate_route_info;
+int amar_propagate_route(int32_t kind, int64_t n_cols, int64_t ld, int32_t width, uint32_t flags, amar_propagate_route_info *info);
+
 /* One fused GCN layer (src/models/gnn.py:289-295 + gnn.py:78, Spektral GCNConv.call):
  *     Y[i, 0:C]      = ReLU( sum_j A_hat[i,j] . H[j, 0:C] + bias )      H = X_prev . W  (pre-multiplied)
  *     Hnext[i, 0:Cn] = Y[i, :] . Wnext[C, Cn]                            (only if Wnext != NULL)
