@@ -122,6 +122,7 @@ SIGNATURES = {
     'amar_bpr_sample_i32': (ctypes.c_int, [_P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _I32, _I32, _P, _P, _P, _P]),
     'amar_loss_counters': (ctypes.c_int32, []),
     'amar_loss_grad_f32': (ctypes.c_int, [_I32, _P, _P, _I64, _P, _P, _P, _I64, _P, _P]),
+    'amar_loss_grad_weighted_f32': (ctypes.c_int, [_I32, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P]),
     'amar_dropout_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I32, ctypes.c_uint64, _P, _U32, _U32, _F32, _P]),
     'amar_dropout_advance': (ctypes.c_int, [_P, _P]),
     'amar_gat_layer_dropout_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32,
@@ -1785,10 +1786,13 @@ def loss_counters():
     return int(load().amar_loss_counters())
 
 
-def loss_grad(loss, hyper, p, y, dz, loss_terms, counters=None):
+def loss_grad(loss, hyper, p, y, dz, loss_terms, counters=None, sample_weight=None, class_weight=None):
     """Per-pair terms and d(mean loss)/d(logit) of Keras loss `loss` (a LOSS_* code; hyper: LOSS_HYPER_FLOATS floats or None) for the
     probability column p ([B] or [B, 1]) and labels y [B]; dz [B, 1] / loss_terms [B] contiguous.  counters: None, or the int64 block
-    of LOSS_COUNTERS cells on the device that this batch is added to (tp, fp, tn, fn, then the 2 x 199 AUC histogram)."""
+    of LOSS_COUNTERS cells on the device that this batch is added to (tp, fp, tn, fn, then the 2 x 199 AUC histogram).
+    sample_weight ([B] floats) / class_weight (two floats: class 0, class 1), device tensors: with either one the call is
+    amar_loss_grad_weighted_f32 and both outputs carry the pair's weight as their last float32 multiplication; with neither it is
+    amar_loss_grad_f32, the launch it always was."""
     B = p.shape[0]
     if p.dim() not in (1, 2) or (p.dim() == 2 and p.shape[1] != 1) or (p.dim() == 1 and B > 1 and p.stride(0) != 1):
         raise ValueError("loss_grad: p must be [B] contiguous or a [B, 1] column")
@@ -1802,6 +1806,18 @@ def loss_grad(loss, hyper, p, y, dz, loss_terms, counters=None):
         if len(hyper) != LOSS_HYPER_FLOATS:
             raise ValueError("loss_grad: hyper must hold {} floats".format(LOSS_HYPER_FLOATS))
         hp = (ctypes.c_float * LOSS_HYPER_FLOATS)(*[float(v) for v in hyper])
+    if sample_weight is not None or class_weight is not None:
+        if sample_weight is not None and (sample_weight.numel() != B or not sample_weight.is_contiguous()):
+            raise ValueError("loss_grad: sample_weight of B contiguous floats expected")
+        if class_weight is not None and (class_weight.numel() != 2 or not class_weight.is_contiguous()):
+            raise ValueError("loss_grad: class_weight must be two contiguous floats (class 0, class 1)")
+        code = load().amar_loss_grad_weighted_f32(int(loss), hp, _ptr(p, torch.float32, 'p'), _ld(p, 'p') if p.dim() == 2 else 1,
+                                                  _ptr(y, torch.float32, 'y'), _ptr(sample_weight, torch.float32, 'sample_weight'),
+                                                  _ptr(class_weight, torch.float32, 'class_weight'), _ptr(dz, torch.float32, 'dz'),
+                                                  _ptr(loss_terms, torch.float32, 'loss_terms'), B,
+                                                  _ptr(counters, torch.int64, 'counters'), _stream())
+        _check(code, 'amar_loss_grad_weighted_f32')
+        return
     code = load().amar_loss_grad_f32(int(loss), hp, _ptr(p, torch.float32, 'p'), _ld(p, 'p') if p.dim() == 2 else 1,
                                      _ptr(y, torch.float32, 'y'), _ptr(dz, torch.float32, 'dz'),
                                      _ptr(loss_terms, torch.float32, 'loss_terms'), B, _ptr(counters, torch.int64, 'counters'), _stream())

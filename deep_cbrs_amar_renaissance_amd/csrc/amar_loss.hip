@@ -100,10 +100,14 @@ __device__ __forceinline__ void loss_pair(const LossHyper &hp, float pi, float y
     }
 }
 
-template <int CODE, bool COUNT>
+// WEIGHTED: the pair's weight w = sample_w[i] * class_w[y[i] > 0.5] (a missing factor is 1) multiplies the finished term and the
+// finished dz as the LAST float32 operation, so a weighted output is float32(w x the unweighted output) and w = 1 gives its bits.
+// The class is read from the 0/1 label itself, before any smoothing; the counters do not see the weights.
+template <int CODE, bool COUNT, bool WEIGHTED>
 __global__ __launch_bounds__(256) void loss_grad_kernel(LossHyper hp, const float *__restrict__ p, int64_t ldp, const float *__restrict__ y,
                                                         float *__restrict__ dz, float *__restrict__ loss_terms, int64_t B,
-                                                        unsigned long long *__restrict__ counters) {
+                                                        unsigned long long *__restrict__ counters, const float *__restrict__ sample_w,
+                                                        const float *__restrict__ class_w) {
     __shared__ unsigned cells[COUNT ? AMAR_LOSS_COUNTERS : 1];
     unsigned tp = 0, fp = 0, tn = 0, fn = 0;
     if (COUNT) {
@@ -113,19 +117,24 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(LossHyper hp, const floa
     const float eps = 1e-7f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < B; i += (int64_t)gridDim.x * blockDim.x) {
         const float pi = p[i * ldp], yi = y[i];
+        float wi = 1.f;
+        if constexpr (WEIGHTED) wi = (sample_w ? sample_w[i] : 1.f) * (class_w ? class_w[yi > 0.5f ? 1 : 0] : 1.f);
         if constexpr (CODE == AMAR_LOSS_BCE) {
             const float pc = fminf(fmaxf(pi, eps), 1.f - eps);
-            loss_terms[i] = -(yi * logf(pc + eps) + (1.f - yi) * logf(1.f - pc + eps));
+            const float term = -(yi * logf(pc + eps) + (1.f - yi) * logf(1.f - pc + eps));
+            loss_terms[i] = WEIGHTED ? wi * term : term;
             const bool inside = pi >= eps && pi <= 1.f - eps;
             const float dp = inside ? -(yi / (pc + eps) - (1.f - yi) / (1.f - pc + eps)) / (float)B : 0.f;
-            dz[i] = dp * pi * (1.f - pi);                                // through the sigmoid of the last Dense layer
+            const float g = dp * pi * (1.f - pi);                        // through the sigmoid of the last Dense layer
+            dz[i] = WEIGHTED ? wi * g : g;
         } else {
             float term, dp;
             if constexpr (CODE == LOSS_BCE_SMOOTH) bce_pair(pi, yi * (1.f - hp.label_smoothing) + 0.5f * hp.label_smoothing, term, dp);
             else loss_pair<CODE>(hp, pi, yi, term, dp);
-            loss_terms[i] = term;
+            loss_terms[i] = WEIGHTED ? wi * term : term;
             const float through = pi * (1.f - pi);                       // a probability of exactly 0 or 1 passes nothing back
-            dz[i] = through == 0.f ? 0.f : dp / (float)B * through;
+            const float g = through == 0.f ? 0.f : dp / (float)B * through;
+            dz[i] = WEIGHTED ? wi * g : g;
         }
         if (COUNT) {
             const bool actual = yi > 0.5f, predicted = pi > 0.5f;
@@ -152,19 +161,23 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(LossHyper hp, const floa
     }
 }
 
-template <int CODE>
-void launch(bool count, unsigned grid, hipStream_t st, const LossHyper &hp, const float *p, int64_t ldp, const float *y, float *dz,
-            float *terms, int64_t B, unsigned long long *counters) {
-    if (count) hipLaunchKernelGGL((loss_grad_kernel<CODE, true>), dim3(grid), dim3(256), 0, st, hp, p, ldp, y, dz, terms, B, counters);
-    else hipLaunchKernelGGL((loss_grad_kernel<CODE, false>), dim3(grid), dim3(256), 0, st, hp, p, ldp, y, dz, terms, B, counters);
+template <int CODE, bool WEIGHTED>
+void launch_counted(bool count, unsigned grid, hipStream_t st, const LossHyper &hp, const float *p, int64_t ldp, const float *y,
+                    const float *sw, const float *cw, float *dz, float *terms, int64_t B, unsigned long long *counters) {
+    if (count) hipLaunchKernelGGL((loss_grad_kernel<CODE, true, WEIGHTED>), dim3(grid), dim3(256), 0, st, hp, p, ldp, y, dz, terms, B, counters, sw, cw);
+    else hipLaunchKernelGGL((loss_grad_kernel<CODE, false, WEIGHTED>), dim3(grid), dim3(256), 0, st, hp, p, ldp, y, dz, terms, B, counters, sw, cw);
 }
 
-}  // namespace
+template <int CODE>
+void launch(bool count, unsigned grid, hipStream_t st, const LossHyper &hp, const float *p, int64_t ldp, const float *y, const float *sw,
+            const float *cw, float *dz, float *terms, int64_t B, unsigned long long *counters) {
+    if (sw || cw) launch_counted<CODE, true>(count, grid, st, hp, p, ldp, y, sw, cw, dz, terms, B, counters);
+    else launch_counted<CODE, false>(count, grid, st, hp, p, ldp, y, nullptr, nullptr, dz, terms, B, counters);
+}
 
-int32_t amar_loss_counters(void) { return AMAR_LOSS_COUNTERS; }
-
-int amar_loss_grad_f32(int32_t loss, const float *hyper, const float *p, int64_t ldp, const float *y, float *dz, float *loss_terms,
-                       int64_t B, int64_t *counters, amar_stream_t stream) {
+// The body of both entry points: sw = cw = NULL launches the unweighted instances.
+int loss_grad(int32_t loss, const float *hyper, const float *p, int64_t ldp, const float *y, const float *sw, const float *cw, float *dz,
+              float *loss_terms, int64_t B, int64_t *counters, amar_stream_t stream) {
     if (B < 1 || !p || !y || !dz || !loss_terms || ldp < 1 || loss < AMAR_LOSS_BCE || loss > AMAR_LOSS_FOCAL) return AMAR_EINVAL;
     LossHyper hp = {0.f, loss == AMAR_LOSS_FOCAL ? 2.f : 1.f, 0.25f, 0.f};
     if (hyper) hp = {hyper[0], hyper[1], hyper[2], hyper[3]};
@@ -177,17 +190,32 @@ int amar_loss_grad_f32(int32_t loss, const float *hyper, const float *p, int64_t
     const bool count = counters != nullptr;
     switch (loss) {
     case AMAR_LOSS_BCE:
-        if (hp.label_smoothing != 0.f) launch<LOSS_BCE_SMOOTH>(count, grid, st, hp, p, ldp, y, dz, loss_terms, B, cnt);
-        else launch<AMAR_LOSS_BCE>(count, grid, st, hp, p, ldp, y, dz, loss_terms, B, cnt);
+        if (hp.label_smoothing != 0.f) launch<LOSS_BCE_SMOOTH>(count, grid, st, hp, p, ldp, y, sw, cw, dz, loss_terms, B, cnt);
+        else launch<AMAR_LOSS_BCE>(count, grid, st, hp, p, ldp, y, sw, cw, dz, loss_terms, B, cnt);
         break;
-    case AMAR_LOSS_MSE: launch<AMAR_LOSS_MSE>(count, grid, st, hp, p, ldp, y, dz, loss_terms, B, cnt); break;
-    case AMAR_LOSS_MAE: launch<AMAR_LOSS_MAE>(count, grid, st, hp, p, ldp, y, dz, loss_terms, B, cnt); break;
-    case AMAR_LOSS_HINGE: launch<AMAR_LOSS_HINGE>(count, grid, st, hp, p, ldp, y, dz, loss_terms, B, cnt); break;
-    case AMAR_LOSS_SQUARED_HINGE: launch<AMAR_LOSS_SQUARED_HINGE>(count, grid, st, hp, p, ldp, y, dz, loss_terms, B, cnt); break;
-    case AMAR_LOSS_HUBER: launch<AMAR_LOSS_HUBER>(count, grid, st, hp, p, ldp, y, dz, loss_terms, B, cnt); break;
-    case AMAR_LOSS_LOG_COSH: launch<AMAR_LOSS_LOG_COSH>(count, grid, st, hp, p, ldp, y, dz, loss_terms, B, cnt); break;
-    case AMAR_LOSS_POISSON: launch<AMAR_LOSS_POISSON>(count, grid, st, hp, p, ldp, y, dz, loss_terms, B, cnt); break;
-    default: launch<AMAR_LOSS_FOCAL>(count, grid, st, hp, p, ldp, y, dz, loss_terms, B, cnt); break;
+    case AMAR_LOSS_MSE: launch<AMAR_LOSS_MSE>(count, grid, st, hp, p, ldp, y, sw, cw, dz, loss_terms, B, cnt); break;
+    case AMAR_LOSS_MAE: launch<AMAR_LOSS_MAE>(count, grid, st, hp, p, ldp, y, sw, cw, dz, loss_terms, B, cnt); break;
+    case AMAR_LOSS_HINGE: launch<AMAR_LOSS_HINGE>(count, grid, st, hp, p, ldp, y, sw, cw, dz, loss_terms, B, cnt); break;
+    case AMAR_LOSS_SQUARED_HINGE: launch<AMAR_LOSS_SQUARED_HINGE>(count, grid, st, hp, p, ldp, y, sw, cw, dz, loss_terms, B, cnt); break;
+    case AMAR_LOSS_HUBER: launch<AMAR_LOSS_HUBER>(count, grid, st, hp, p, ldp, y, sw, cw, dz, loss_terms, B, cnt); break;
+    case AMAR_LOSS_LOG_COSH: launch<AMAR_LOSS_LOG_COSH>(count, grid, st, hp, p, ldp, y, sw, cw, dz, loss_terms, B, cnt); break;
+    case AMAR_LOSS_POISSON: launch<AMAR_LOSS_POISSON>(count, grid, st, hp, p, ldp, y, sw, cw, dz, loss_terms, B, cnt); break;
+    default: launch<AMAR_LOSS_FOCAL>(count, grid, st, hp, p, ldp, y, sw, cw, dz, loss_terms, B, cnt); break;
     }
     return amar_check_launch();
+}
+
+}  // namespace
+
+int32_t amar_loss_counters(void) { return AMAR_LOSS_COUNTERS; }
+
+int amar_loss_grad_f32(int32_t loss, const float *hyper, const float *p, int64_t ldp, const float *y, float *dz, float *loss_terms,
+                       int64_t B, int64_t *counters, amar_stream_t stream) {
+    return loss_grad(loss, hyper, p, ldp, y, nullptr, nullptr, dz, loss_terms, B, counters, stream);
+}
+
+int amar_loss_grad_weighted_f32(int32_t loss, const float *hyper, const float *p, int64_t ldp, const float *y, const float *sample_w,
+                                const float *class_w, float *dz, float *loss_terms, int64_t B, int64_t *counters, amar_stream_t stream) {
+    if (!sample_w && !class_w) return AMAR_EINVAL;
+    return loss_grad(loss, hyper, p, ldp, y, sample_w, class_w, dz, loss_terms, B, counters, stream);
 }

@@ -8,6 +8,9 @@ Same constructor arguments, attributes (``ratings``, ``users``, ``items``, ``adj
     UserItemGraph             ((u_ids[B], i_ids[B]), y[B])                          datasets.py:203
     UserItemGraphEmbeddings   ((u_ids, i_ids, u_emb[B,D], i_emb[B,D]), y)           datasets.py:366
 
+Built with ``sample_weight`` (float [R], row r weighs rating row r) these four yield Keras' three-element batches
+``(inputs, y, w[B])``; a shuffle permutes the weights with the ratings.  Without it nothing changes.
+
 ids are int64 with item ids already offset by |U|; the last batch is short.  Shuffling uses
 ``np.random.RandomState(seed)`` re-drawn at every epoch end, like the reference.
     UserItemGraphPosNegSample ((u_ids[2h], i_ids[2h]), y[2h]), h = batch_size // 2      datasets.py:216-306
@@ -21,9 +24,20 @@ import numpy as np
 from scipy import sparse
 
 
+def _checked_sample_weight(sample_weight, ratings):
+    """None, or the per-rating weights as float32 [R] (row r weighs rating row r).  ValueError: another length or shape."""
+    if sample_weight is None:
+        return None
+    w = np.asarray(sample_weight, dtype=np.float32)
+    if w.ndim != 1 or len(w) != len(ratings):
+        raise ValueError("sample_weight must hold one weight per rating row: shape {} for {} ratings".format(w.shape, len(ratings)))
+    return w
+
+
 class _RatingsSequence:
-    def __init__(self, ratings, users, items, batch_size=512, shuffle=False, seed=42):
+    def __init__(self, ratings, users, items, batch_size=512, shuffle=False, seed=42, sample_weight=None):
         self.ratings = ratings
+        self.sample_weight = _checked_sample_weight(sample_weight, ratings)
         self.users = users
         self.items = items
         self.batch_size = batch_size
@@ -49,6 +63,24 @@ class _RatingsSequence:
             return self.ratings[self.indexes[lo:hi]]
         return self.ratings[lo:hi]
 
+    def _batch_weights(self, idx):
+        """The weights of the rows `_batch_ratings(idx)` returns (the shuffle permutes both alike), or None without sample_weight."""
+        if self.sample_weight is None:
+            return None
+        if idx < 0 or idx >= len(self):
+            raise IndexError(idx)
+        lo = idx * self.batch_size
+        hi = min(lo + self.batch_size, len(self.ratings))
+        if self.shuffle:
+            return self.sample_weight[self.indexes[lo:hi]]
+        return self.sample_weight[lo:hi]
+
+    def _batch(self, idx, inputs, y):
+        """(inputs, y), or (inputs, y, w) for a Sequence built with sample_weight (Keras' three-element batch)."""
+        if self.sample_weight is None:
+            return inputs, y
+        return inputs, y, self._batch_weights(idx)
+
     def on_epoch_end(self):
         if self.shuffle:
             if self.random_state is None:
@@ -61,53 +93,54 @@ class _RatingsSequence:
 class UserItemEmbeddings(_RatingsSequence):
     """Pairs as pre-computed embedding rows (KGE or BERT), gathered on the host per batch."""
 
-    def __init__(self, ratings, users, items, embeddings, batch_size=512, shuffle=False, seed=42):
+    def __init__(self, ratings, users, items, embeddings, batch_size=512, shuffle=False, seed=42, sample_weight=None):
         self.embeddings = embeddings
-        super().__init__(ratings, users, items, batch_size=batch_size, shuffle=shuffle, seed=seed)
+        super().__init__(ratings, users, items, batch_size=batch_size, shuffle=shuffle, seed=seed, sample_weight=sample_weight)
 
     def __getitem__(self, idx):
         r = self._batch_ratings(idx)
-        return (self.embeddings[r[:, 0]], self.embeddings[r[:, 1]]), r[:, 2]
+        return self._batch(idx, (self.embeddings[r[:, 0]], self.embeddings[r[:, 1]]), r[:, 2])
 
 
 class HybridUserItemEmbeddings(_RatingsSequence):
     """Pairs as (graph, BERT) embedding rows for HybridCBRS."""
 
     def __init__(self, ratings, users, items, graph_embeddings, bert_embeddings, batch_size=512, shuffle=False,
-                 seed=42):
+                 seed=42, sample_weight=None):
         self.graph_embeddings = graph_embeddings
         self.bert_embeddings = bert_embeddings
-        super().__init__(ratings, users, items, batch_size=batch_size, shuffle=shuffle, seed=seed)
+        super().__init__(ratings, users, items, batch_size=batch_size, shuffle=shuffle, seed=seed, sample_weight=sample_weight)
 
     def __getitem__(self, idx):
         r = self._batch_ratings(idx)
         u, i = r[:, 0], r[:, 1]
-        return (self.graph_embeddings[u], self.graph_embeddings[i],
-                self.bert_embeddings[u], self.bert_embeddings[i]), r[:, 2]
+        return self._batch(idx, (self.graph_embeddings[u], self.graph_embeddings[i],
+                                 self.bert_embeddings[u], self.bert_embeddings[i]), r[:, 2])
 
 
 class UserItemGraph(_RatingsSequence):
     """Pairs as node ids of the user-item(-properties) graph."""
 
-    def __init__(self, ratings, users, items, adj_matrix, batch_size=512, shuffle=False, seed=42):
+    def __init__(self, ratings, users, items, adj_matrix, batch_size=512, shuffle=False, seed=42, sample_weight=None):
         self.adj_matrix = adj_matrix
-        super().__init__(ratings, users, items, batch_size=batch_size, shuffle=shuffle, seed=seed)
+        super().__init__(ratings, users, items, batch_size=batch_size, shuffle=shuffle, seed=seed, sample_weight=sample_weight)
 
     def __getitem__(self, idx):
         r = self._batch_ratings(idx)
-        return (r[:, 0], r[:, 1]), r[:, 2]
+        return self._batch(idx, (r[:, 0], r[:, 1]), r[:, 2])
 
 
 class UserItemGraphEmbeddings:
     """Node ids plus the matching BERT rows (HybridBertGNN batches)."""
 
-    def __init__(self, ratings, users, items, adj_matrix, embeddings, batch_size=512, shuffle=False, seed=42):
+    def __init__(self, ratings, users, items, adj_matrix, embeddings, batch_size=512, shuffle=False, seed=42, sample_weight=None):
         self.ratings = ratings
         self.users = users
         self.items = items
         self.adj_matrix = adj_matrix
-        self.graph_ids = UserItemGraph(ratings, users, items, adj_matrix,
-                                       batch_size=batch_size, shuffle=shuffle, seed=seed)
+        self.graph_ids = UserItemGraph(ratings, users, items, adj_matrix,                # (the ids Sequence carries the weights)
+                                       batch_size=batch_size, shuffle=shuffle, seed=seed, sample_weight=sample_weight)
+        self.sample_weight = self.graph_ids.sample_weight
         self.embeddings = UserItemEmbeddings(ratings, users, items, embeddings,
                                              batch_size=batch_size, shuffle=shuffle, seed=seed)
 
@@ -118,9 +151,9 @@ class UserItemGraphEmbeddings:
         return (self[b] for b in range(len(self)))
 
     def __getitem__(self, idx):
-        (user_ids, item_ids), ratings = self.graph_ids[idx]
+        (user_ids, item_ids), ratings = self.graph_ids[idx][:2]
         (user_embeddings, item_embeddings), _ = self.embeddings[idx]
-        return (user_ids, item_ids, user_embeddings, item_embeddings), ratings
+        return self.graph_ids._batch(idx, (user_ids, item_ids, user_embeddings, item_embeddings), ratings)
 
     def on_epoch_end(self):
         self.graph_ids.on_epoch_end()

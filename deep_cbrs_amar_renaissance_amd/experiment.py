@@ -295,6 +295,15 @@ class Experimenter:
                                           'ks': [int(k) for k in validation.get('ranking_ks')], 'users': None}
         return args
 
+    def class_weight(self):
+        """fit()'s class_weight from parameters.class_weight — a mapping over the classes 0 and 1 (YAML's string keys included) or
+        `balanced` — resolved against the labels of the training rows (after the validation split, where there is one) and logged as
+        the parameters class_weight.0 / class_weight.1; None without the key."""
+        pair = losses.resolve_class_weight(self.parameters.get('class_weight'), np.asarray(self.trainset.ratings)[:, 2])
+        if pair is not None:
+            self.run_log.log_params({'class_weight.0': pair[0], 'class_weight.1': pair[1]})
+        return pair
+
     def build_optimizer(self):
         accepted = inspect.signature(self.optimizer_class).parameters
         opt_cfg = self.config.parameters.optimizer
@@ -330,7 +339,8 @@ class Experimenter:
         t0 = time.perf_counter()
         # a model or reduction without a training recipe raises here: the experiment fails (MultiExperimenter.run_experiment
         # logs the traceback, ends the run and goes on with the grid, experiment.py:295-302) instead of evaluating random weights
-        self.model.fit(self.trainset, epochs=self.parameters.epochs, workers=self.config.n_workers, **self.validation_fit_args())
+        self.model.fit(self.trainset, epochs=self.parameters.epochs, workers=self.config.n_workers, class_weight=self.class_weight(),
+                       **self.validation_fit_args())
         # the reference's LogCallback reports the fit wall time as 'training_time' (utilities/keras.py:43-51, 69-85)
         self.run_log.log_metrics({'training_time': time.perf_counter() - t0})
 

@@ -391,7 +391,7 @@ class BasicGNN(Model, abc.ABC):
         """Batches of id pairs only (datasets.UserItemGraph): nothing but device work between the first and the last launch."""
         if len(sequence) == 0 or not hasattr(self.gnn, 'gnn_layers'):     # single-graph stacks (TwoStep / TwoWay stay eager)
             return False
-        inputs, _ = sequence[0]
+        inputs = sequence[0][0]
         return isinstance(inputs, tuple) and len(inputs) == 2
 
 

@@ -448,7 +448,7 @@ class _IdsWithoutBlocks:
         return len(self.ids)
 
     def __getitem__(self, b):
-        (u, i), y = self.ids[b]
+        (u, i), y = self.ids[b][:2]
         return (u, i, None, None), y
 
 

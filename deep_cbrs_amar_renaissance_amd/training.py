@@ -38,7 +38,7 @@ from deep_cbrs_amar_renaissance_amd.layers.gat_conv import GATConv
 from deep_cbrs_amar_renaissance_amd.layers.gcn_conv import GCNConv
 from deep_cbrs_amar_renaissance_amd.layers.graphsage_conv import GraphSageConv
 from deep_cbrs_amar_renaissance_amd.layers.lightgcn_conv import LightGCNConv
-from deep_cbrs_amar_renaissance_amd.utilities.losses import BPR, loss_kind
+from deep_cbrs_amar_renaissance_amd.utilities.losses import BPR, loss_kind, resolve_class_weight
 from deep_cbrs_amar_renaissance_amd.utilities.math import spmm_kind
 from deep_cbrs_amar_renaissance_amd.utilities.metrics import metric_values, resolve_compiled
 from deep_cbrs_amar_renaissance_amd.utilities.schedules import InverseTimeDecay, LearningRateSchedule, resolve as resolve_learning_rate
@@ -965,14 +965,46 @@ class Trainer:
             self._counters_read = None
         return self._counters
 
-    def _loss_grad(self, p, yv, dz, terms):
+    def _loss_grad(self, p, yv, dz, terms, w=None):
         """Per-pair loss terms (their sum = B x the batch's loss) and d(loss)/d(logit) of the compiled loss; with metrics compiled
-        the same launch adds the batch to the counter block."""
+        the same launch adds the batch to the counter block.  w (the batch's sample weights on the device) and the class pair of
+        `set_class_weight` route to the weighted entry point; without either this is the launch it always was."""
         code, hyper, names = self._compiled()
+        cw = self._class_w if self._class_weighted else None
         if code == BPR:
+            if w is not None or cw is not None:
+                raise ValueError("BPRLoss has no per-pair label or term: it takes no class_weight and no sample weights")
             capi.bpr_grad(p, dz, terms)
         else:
-            capi.loss_grad(code, hyper, p, yv, dz, terms, counters=self._metric_block() if names else None)
+            capi.loss_grad(code, hyper, p, yv, dz, terms, counters=self._metric_block() if names else None, sample_weight=w, class_weight=cw)
+
+    # -- the weights of the loss (DESIGN §7l) ----------------------------------------------------------------------------------------
+    _class_w, _class_weighted = None, False
+
+    def set_class_weight(self, class_weight, labels=None):
+        """Keras' fit(class_weight=...) from the next batch on: a mapping over the classes 0 and 1, 'balanced' (over `labels`), a pair
+        (class 0, class 1) or None (off).  The pair lives in two floats of device memory that the loss kernel reads: the buffer is
+        allocated once per trainer, so a captured graph follows new values without a new capture; only whether the pair is in use is
+        part of a graph's key."""
+        if isinstance(class_weight, tuple) and len(class_weight) == 2:
+            class_weight = {0: class_weight[0], 1: class_weight[1]}
+        pair = resolve_class_weight(class_weight, labels)
+        if pair is None:
+            self._class_weighted = False
+            return
+        if self._class_w is None:
+            self._class_w = torch.zeros(2, dtype=torch.float32, device=self.device)
+        self._class_w.copy_(torch.tensor([float(pair[0]), float(pair[1])], dtype=torch.float32))
+        self._class_weighted = True
+
+    def _weights_to_device(self, w, b):
+        """A batch's sample weights as a float32 device tensor [b], or None."""
+        if w is None:
+            return None
+        wv = to_device_tensor(np.ascontiguousarray(w, dtype=np.float32).reshape(-1) if not isinstance(w, torch.Tensor) else w.reshape(-1))
+        if wv.numel() != b:
+            raise ValueError("the batch holds {} sample weights for {} pairs".format(wv.numel(), b))
+        return wv
 
     def reset_metrics(self):
         """Clear the counter block (the start of a fit(): batches counted outside an epoch do not belong to it)."""
@@ -1005,9 +1037,9 @@ class Trainer:
         capi.copy_columns(table, rows, ids=ids)
         return rows
 
-    def _forward_backward(self, u, i, yv, rows, ui=None):
+    def _forward_backward(self, u, i, yv, rows, ui=None, w=None):
         """Device-only body of a batch (no host synchronisation, fixed shapes -> capturable as a hipGraph):
-        returns (per-pair loss terms [B], {param: gradient})."""
+        returns (per-pair loss terms [B], {param: gradient}).  w: the batch's sample weights [B] on the device, or None."""
         b = u.numel()
         dev = self.device
         e = self._propagation_forward()                              # full-graph propagation, every batch (basic.py:61-63)
@@ -1025,7 +1057,7 @@ class Trainer:
         # ---- loss and its gradient through the final sigmoid
         dz = torch.empty((b, 1), dtype=torch.float32, device=dev)
         terms = torch.empty(b, dtype=torch.float32, device=dev)
-        self._loss_grad(p, yv, dz, terms)
+        self._loss_grad(p, yv, dz, terms, w)
         grads = {}
         de = torch.zeros((e.shape[0], f), dtype=torch.float32, device=dev)
         both = None
@@ -1044,14 +1076,16 @@ class Trainer:
             capi.dropout_advance(self.dropout_step)
         return terms, grads
 
-    def loss_and_grads(self, u_ids, i_ids, y, bert=None):
+    def loss_and_grads(self, u_ids, i_ids, y, bert=None, sample_weight=None):
         """Forward + reverse pass of one batch. Returns (data loss + regularisation loss, {param: gradient}).
-        `bert` = (user block, item block) for the hybrid head (None: rows of the resident table)."""
+        `bert` = (user block, item block) for the hybrid head (None: rows of the resident table).  `sample_weight` [B] and the pair
+        of `set_class_weight` weigh the data loss: sum(w x term) / B."""
         n_nodes = self.seq.adj_matrix.shape[0] if getattr(self, 'seq', None) is not None else None
         u, i = ids_to_device(u_ids, n_nodes), ids_to_device(i_ids, n_nodes)
         yv = to_device_tensor(np.asarray(y, dtype=np.float32) if not isinstance(y, torch.Tensor) else y)
+        wv = self._weights_to_device(sample_weight, u.numel())
         with torch.no_grad():
-            terms, grads = self._forward_backward(u, i, yv, bert)
+            terms, grads = self._forward_backward(u, i, yv, bert, w=wv)
             loss = float(terms.sum().item()) / u.numel()
             for prm in self.params:
                 l2 = self._l2(prm)
@@ -1066,7 +1100,8 @@ class Trainer:
         for t in tapes:                                              # weight-gradient partials stay partial: the update launch below adds them
             t.defer_reduce = True
         try:
-            terms, grads = self._forward_backward(g['u'], g['i'], g['y'], (g['ub'], g['ib']) if g['ub'] is not None else None, ui=g['ui'])
+            terms, grads = self._forward_backward(g['u'], g['i'], g['y'], (g['ub'], g['ib']) if g['ub'] is not None else None, ui=g['ui'],
+                                                  w=g.get('w'))
         finally:
             for t in tapes:
                 t.defer_reduce = False
@@ -1119,31 +1154,40 @@ class Trainer:
         if 'clip_bytes' in g:
             g['clip_dev'][:g['clip_bytes']].copy_(g['clip_host'][:g['clip_bytes']])
 
-    def train_batch_graphed(self, u_ids, i_ids, y, bert=None, graph=True):
+    def train_batch_graphed(self, u_ids, i_ids, y, bert=None, graph=True, sample_weight=None):
         """One training batch replayed from a hipGraph: the forward, the reverse pass and the Adam update are ~100
         small launches that are otherwise bound by host launch time.  The graph is captured at the second batch of a
         given size (the first one runs eagerly and warms every lazily built buffer); the running loss stays on the
         device (`pop_loss_sum`).  Batches of another size run eagerly.  graph=False: the same body, same buffers and uploads, run
         eagerly at every batch instead of captured and replayed (what fit() does under AMAR_TRAIN_GRAPH=0 when the model drops: the
-        two then agree bit for bit, masks included)."""
+        two then agree bit for bit, masks included).  sample_weight [b]: the batch's weights, uploaded behind the labels into the same
+        static buffer; whether a batch carries them, and whether a class pair is in use, is part of the graph's key — their values
+        are not."""
         b = len(y)
         dev = self.device
         with_blocks = bert is not None and bert[0] is not None
+        weighted = sample_weight is not None
+        if weighted and len(sample_weight) != b:
+            raise ValueError("the batch holds {} sample weights for {} pairs".format(len(sample_weight), b))
         key = (b, with_blocks, self._loss_kind()) + self.dropout_key  # (a compile() with another loss captures anew; so would other dropout state)
+        if weighted or self._class_weighted:                          # (an unweighted batch keeps the key it always had)
+            key += (('weights', weighted, self._class_weighted),)
         self._init_graph_state()
         g = self._captured(key)
         if g is None:
             if key not in self._seen:                               # first batch of this shape: eager (real) step
                 self._seen.add(key)
-                self._eager_loss += self.train_batch(u_ids, i_ids, y, bert=bert) * b
+                self._eager_loss += self.train_batch(u_ids, i_ids, y, bert=bert, sample_weight=sample_weight) * b
                 return
             g = None if graph else self._eager_batches.get(key)
         if g is None:
             d = int(np.asarray(bert[0]).shape[1]) if with_blocks else 0
-            uiy = torch.zeros(3 * b, dtype=torch.int32, device=dev)  # u, i and the labels in ONE buffer: one upload per batch instead of three
+            slots = 4 if weighted else 3                              # (the batch's weights ride behind the labels)
+            uiy = torch.zeros(slots * b, dtype=torch.int32, device=dev)  # u, i and the labels in ONE buffer: one upload per batch instead of three
             ui = uiy[:2 * b]                                          # (u and i side by side: one scatter of both towers' input gradients)
             g = self._g = {'uiy': uiy, 'ui': ui, 'u': ui[:b], 'i': ui[b:],
-                           'y': uiy[2 * b:].view(torch.float32),
+                           'y': uiy[2 * b:3 * b].view(torch.float32),
+                           'w': uiy[3 * b:].view(torch.float32) if weighted else None,
                            'ub': torch.zeros((b, d), dtype=torch.float32, device=dev) if with_blocks else None,
                            'ib': torch.zeros((b, d), dtype=torch.float32, device=dev) if with_blocks else None}
             self._slot_buffers(g)
@@ -1152,8 +1196,9 @@ class Trainer:
             # 0.13 ms of a 0.52 ms batch at ml1m(s=1))
             g['stage'] = []
             for _ in range(4):
-                host = torch.empty(3 * b, dtype=torch.int32).pin_memory()
-                g['stage'].append({'uiy': host, 'u': host[:b], 'i': host[b:2 * b], 'y': host[2 * b:].view(torch.float32), 'done': torch.cuda.Event()})
+                host = torch.empty(slots * b, dtype=torch.int32).pin_memory()
+                g['stage'].append({'uiy': host, 'u': host[:b], 'i': host[b:2 * b], 'y': host[2 * b:3 * b].view(torch.float32),
+                                   'w': host[3 * b:].view(torch.float32) if weighted else None, 'done': torch.cuda.Event()})
             g['turn'] = 0
             if graph:
                 from deep_cbrs_amar_renaissance_amd.engine import capture_graph
@@ -1173,7 +1218,7 @@ class Trainer:
         st = g['stage'][g['turn'] % len(g['stage'])]
         g['turn'] += 1
         st['done'].synchronize()                                     # (the uploads that last used this staging set have landed)
-        on_device = [isinstance(src, torch.Tensor) and src.is_cuda for src in (u_ids, i_ids, y)]
+        on_device = [isinstance(src, torch.Tensor) and src.is_cuda for src in (u_ids, i_ids, y, sample_weight)]
         for name, src, dev_side in (('u', u_ids, on_device[0]), ('i', i_ids, on_device[1])):
             if dev_side:
                 g[name].copy_(src)
@@ -1187,6 +1232,13 @@ class Trainer:
             st['y'].numpy()[...] = y.numpy() if isinstance(y, torch.Tensor) else np.asarray(y, dtype=np.float32)
             if any(on_device):
                 g['y'].copy_(st['y'], non_blocking=True)
+        if weighted:
+            if on_device[3]:
+                g['w'].copy_(sample_weight.reshape(-1))
+            else:
+                st['w'].numpy()[...] = sample_weight.numpy() if isinstance(sample_weight, torch.Tensor) else np.asarray(sample_weight, dtype=np.float32)
+                if any(on_device):
+                    g['w'].copy_(st['w'], non_blocking=True)
         if not any(on_device):
             g['uiy'].copy_(st['uiy'], non_blocking=True)             # ids and labels of the batch: one asynchronous upload
         st['done'].record()
@@ -1400,8 +1452,8 @@ class Trainer:
         if not host_step:
             self._dev_t = self.t
 
-    def train_batch(self, u_ids, i_ids, y, bert=None):
-        loss, grads = self.loss_and_grads(u_ids, i_ids, y, bert=bert)
+    def train_batch(self, u_ids, i_ids, y, bert=None, sample_weight=None):
+        loss, grads = self.loss_and_grads(u_ids, i_ids, y, bert=bert, sample_weight=sample_weight)
         self.apply_gradients(grads)
         return loss
 
@@ -1439,34 +1491,35 @@ class HeadTrainer(Trainer):
                 out.append(rows)
         return out                                                   # (user, item) per table: [gu, gi] or [gu, gi, bu, bi]
 
-    def _forward_backward(self, u, i, yv, rows=None, ui=None):
+    def _forward_backward(self, u, i, yv, rows=None, ui=None, w=None):
         """Trainer's per-batch core for ids: gather the rows, head forward, BCE, head reverse pass (the inputs are constants)."""
         r = self._rows_of(u, i)
         b = u.numel()
         p = self.head.forward(r[0], r[1], (r[2], r[3]) if self.hybrid else None)
         dz = torch.empty((b, 1), dtype=torch.float32, device=p.device)
         terms = torch.empty(b, dtype=torch.float32, device=p.device)
-        self._loss_grad(p, yv, dz, terms)
+        self._loss_grad(p, yv, dz, terms, w)
         grads = {}
         self.head.backward(dz, grads, need_input_grad=False)
         return terms, grads
 
-    def loss_and_grads(self, blocks, y):
+    def loss_and_grads(self, blocks, y, sample_weight=None):
         """blocks = (user rows, item rows) or (user graph, item graph, user BERT, item BERT), each [B, D]."""
         rows = [to_device_tensor(b) for b in blocks]
         yv = to_device_tensor(np.asarray(y, dtype=np.float32) if not isinstance(y, torch.Tensor) else y)
         b = rows[0].shape[0]
+        wv = self._weights_to_device(sample_weight, b)
         with torch.no_grad():
             p = self.head.forward(rows[0], rows[1], (rows[2], rows[3]) if self.hybrid else None)
             dz = torch.empty((b, 1), dtype=torch.float32, device=p.device)
             terms = torch.empty(b, dtype=torch.float32, device=p.device)
-            self._loss_grad(p, yv, dz, terms)
+            self._loss_grad(p, yv, dz, terms, wv)
             grads = {}
             self.head.backward(dz, grads, need_input_grad=False)
             loss = float(terms.sum().item()) / b
         return loss, grads
 
-    def train_batch(self, *args, bert=None):
+    def train_batch(self, *args, bert=None, sample_weight=None):
         """train_batch(blocks, y): the rows themselves; train_batch(u_ids, i_ids, y): ids against `set_tables` (eager: the first
         batch of a shape before Trainer.train_batch_graphed captures)."""
         if len(args) == 3:
@@ -1474,15 +1527,16 @@ class HeadTrainer(Trainer):
             n = self.seq.adj_matrix.shape[0]
             u, i = ids_to_device(u_ids, n), ids_to_device(i_ids, n)
             yv = to_device_tensor(np.asarray(y, dtype=np.float32) if not isinstance(y, torch.Tensor) else y)
+            wv = self._weights_to_device(sample_weight, u.numel())
             with torch.no_grad():
-                terms, grads = self._forward_backward(u, i, yv)
+                terms, grads = self._forward_backward(u, i, yv, w=wv)
                 loss = float(terms.sum().item()) / u.numel()
                 for prm in self.params:
                     l2 = self._l2(prm)
                     if l2:
                         loss += l2 * float((prm.detach().double() ** 2).sum().item())
         else:
-            loss, grads = self.loss_and_grads(*args)
+            loss, grads = self.loss_and_grads(*args, sample_weight=sample_weight)
         self.apply_gradients(grads)
         return loss
 
@@ -1664,14 +1718,30 @@ def _fit_hooks(model, history, callbacks, validation_data, validation_freq, vali
     return _FitHooks(model, history, callbacks, validation_data, validation_freq, validation_ranking)
 
 
+def _split_batch(batch):
+    """(inputs, y, w) of a Sequence's batch: w is the third element of a weighted Sequence's batch (Keras' sample weights), else None."""
+    return batch[0], batch[1], (batch[2] if len(batch) > 2 else None)
+
+
 def fit(model, sequence, epochs=1, callbacks=None, verbose=True, validation_data=None, validation_freq=1, validation_ranking=None,
-        initial_epoch=0, **kwargs):
+        initial_epoch=0, class_weight=None, workers=None):
     """Keras-style ``fit`` over a batch Sequence: epochs ``initial_epoch`` .. ``epochs - 1``, ``on_epoch_end`` reshuffles
     (datasets.py:205-213).  ``callbacks``, ``validation_data``, ``validation_freq``, ``validation_ranking``: _FitHooks; only validated
     epochs add a val_* entry to the returned history, as in Keras.  ``model.stop_training = True`` set by a callback's on_epoch_end
-    ends training after that epoch."""
+    ends training after that epoch.
+
+    ``class_weight`` (a mapping over the classes 0 and 1, 'balanced', or the pair `resolve_class_weight` returns) and the sample weights of a
+    Sequence whose batches are (inputs, y, w) weigh the data loss as Keras 2 does: w_j = sample_weight_j x class_weight[label_j],
+    batch loss = sum_j w_j l_j / B, epoch loss = sum over all pairs / N; the L2 term and the compiled metrics stay unweighted, and
+    validation never applies class_weight.  It holds for this call only.  BPR training refuses both.  ``workers`` (the loader
+    threads of Keras' fit, passed by the experiment) is accepted and not read: batches are taken in the loop.  Any other keyword
+    is a TypeError."""
     if validation_ranking is not None and not hasattr(model, 'recommend'):
         raise NotImplementedError("{} has no recommend(): validation_ranking cannot rank with it".format(type(model).__name__))
+    if class_weight is not None and not isinstance(class_weight, tuple):
+        rows = getattr(sequence, 'ratings', None)                # (the Sequences of data/datasets.py: the labels the mapping must cover)
+        labels = rows[:, 2] if isinstance(rows, np.ndarray) and rows.ndim == 2 and rows.shape[1] >= 3 else None
+        class_weight = resolve_class_weight(class_weight, labels)
     model.stop_training = False
     val = (callbacks, validation_data, validation_freq, validation_ranking)
     spec = OptimizerSpec(getattr(model, 'optimizer', None))
@@ -1700,6 +1770,7 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, validation_data
                 trainer.set_tables(tables)
                 trainer._table_sources = tables
         use_graph = tables is not None and os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
+        trainer.set_class_weight(class_weight)                   # (None: off — the pair of an earlier fit() does not linger)
         history = _History(trainer)
         hooks = _fit_hooks(model, history, *val)
         if hooks is not None:
@@ -1714,13 +1785,14 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, validation_data
                 if tables is not None:
                     r = sequence._batch_ratings(b)
                     u, i, y = r[:, 0], r[:, 1], r[:, 2]
+                    w = sequence._batch_weights(b)
                     if use_graph:
-                        trainer.train_batch_graphed(u, i, y)
+                        trainer.train_batch_graphed(u, i, y, sample_weight=w)
                     else:
-                        total += trainer.train_batch(u, i, y) * len(y)
+                        total += trainer.train_batch(u, i, y, sample_weight=w) * len(y)
                 else:
-                    blocks, y = sequence[b]
-                    total += trainer.train_batch(blocks, y) * len(y)
+                    blocks, y, w = _split_batch(sequence[b])
+                    total += trainer.train_batch(blocks, y, sample_weight=w) * len(y)
                 count += len(y)
                 if hooks is not None and hooks.batch_end:
                     hooks.on_batch_end(b)
@@ -1742,6 +1814,8 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, validation_data
     # (AMAR_RESIDENT_BERT=0: the batches as they come).  A replayed hybrid batch at ml1m(s=1): 0.41 against 0.71 ms.
     from deep_cbrs_amar_renaissance_amd.data.datasets import UserItemGraphPosNegSample
     if isinstance(sequence, UserItemGraphPosNegSample):
+        if class_weight is not None:
+            raise ValueError("class_weight cannot weigh BPR training: the batches are drawn on the device and have no per-pair label")
         return _fit_sampled(model, sequence, epochs, verbose, hp, val, initial_epoch)
     ids_only = model.resident_ids(sequence) if hasattr(model, 'resident_ids') else None
     trainer = _cached_trainer(model, spec)
@@ -1753,6 +1827,9 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, validation_data
         trainer = model._trainer = Trainer(model, **hp)
     use_graph = os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
     same_body = not use_graph and trainer.dropout_step is not None      # a model that drops: the replayed body, run eagerly (same bits)
+    if trainer._loss_kind() == 'bpr' and class_weight is not None:     # (a weighted batch under BPR is refused where it is read)
+        raise ValueError("BPRLoss has no per-pair label or term: it takes no class_weight and no weighted Sequence")
+    trainer.set_class_weight(class_weight)                       # (None: off — the pair of an earlier fit() does not linger)
     history = _History(trainer)
     hooks = _fit_hooks(model, history, *val)
     if hooks is not None:
@@ -1764,13 +1841,13 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, validation_data
         for b in range(len(sequence)):
             if hooks is not None and hooks.batch_begin:
                 hooks.on_batch_begin(b)
-            inputs, y = (ids_only if ids_only is not None else sequence)[b]
+            inputs, y, w = _split_batch((ids_only if ids_only is not None else sequence)[b])
             u, i = inputs[0], inputs[1]
             bert = (inputs[2], inputs[3]) if len(inputs) >= 4 else None     # hybrid batches carry the BERT blocks (datasets.py:112-115)
             if use_graph or same_body:
-                trainer.train_batch_graphed(u, i, y, bert=bert, graph=use_graph)
+                trainer.train_batch_graphed(u, i, y, bert=bert, graph=use_graph, sample_weight=w)
             else:
-                total += trainer.train_batch(u, i, y, bert=bert) * len(y)
+                total += trainer.train_batch(u, i, y, bert=bert, sample_weight=w) * len(y)
             count += len(y)
             if hooks is not None and hooks.batch_end:
                 hooks.on_batch_end(b)
@@ -1792,9 +1869,12 @@ def _fit_sampled(model, sequence, epochs, verbose, hp, val=(None, None, 1, None)
     """fit() on the BPR sample Sequence: its lists go to the device once and every batch is drawn there (amar_bpr_sample_i32), inside
     the replayed training graph (AMAR_TRAIN_GRAPH=0: the same steps eagerly, the same ids).  len(sequence) steps per epoch; the host
     stream of __getitem__ is not read."""
+    if getattr(sequence, 'sample_weight', None) is not None:
+        raise ValueError("the BPR sample Sequence draws its batches on the device: it carries no sample weights")
     trainer = _cached_trainer(model, hp['optimizer'])
     if trainer is None:
         trainer = model._trainer = Trainer(model, **hp)
+    trainer.set_class_weight(None)
     sampler = trainer.sampler_for(sequence)
     use_graph = os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
     history = _History(trainer)

@@ -4,7 +4,8 @@ The experiment looks a name up here first (``hasattr(losses, name)`` -> an insta
 any other value — a Keras loss name, a Keras class name, or a mapping ``{name: ..., <hyper-parameters>}`` — goes through
 `resolve_loss`, which names the pointwise losses the device computes (include/amar_hip.h: amar_loss_grad_f32) and refuses every other
 name: ``binary_crossentropy`` is the default.  ``fit()`` and ``evaluate()`` read the compiled loss through `resolve_loss`
-(`loss_kind` tells BPR from the pointwise losses).  `loss_terms` / `loss_dp` restate every pointwise loss in float64 numpy.
+(`loss_kind` tells BPR from the pointwise losses).  `loss_terms` / `loss_dp` restate every pointwise loss in float64 numpy, with
+the weights of ``fit(class_weight=...)`` and of a weighted Sequence where given (`pair_weights`, `resolve_class_weight`).
 """
 from collections.abc import Mapping
 
@@ -158,21 +159,94 @@ def _pair_parts(code, hyper, y_true, y_pred, f32_constants=False):
     raise ValueError("no pointwise loss with code {}".format(code))
 
 
-def loss_terms(code, hyper, y_true, y_pred, f32_constants=False):
-    """float64 per-pair terms of pointwise loss `code` (their mean is the batch loss): what amar_loss_grad_f32 writes to loss_terms."""
-    return _pair_parts(code, hyper, y_true, y_pred, f32_constants)[0]
+def pair_weights(y_true, sample_weight=None, class_weight=None):
+    """float64 weight of every pair under Keras' fit(): w_j = sample_weight_j * class_weight[label_j], a missing factor 1, the class
+    read from the 0/1 label itself (y > 0.5, before any smoothing).  class_weight: a pair (class 0, class 1) or a mapping with keys
+    0 and 1.  None when neither is given."""
+    if sample_weight is None and class_weight is None:
+        return None
+    y = np.asarray(y_true, dtype=np.float64).reshape(-1)
+    w = np.ones(len(y))
+    if sample_weight is not None:
+        sw = np.asarray(sample_weight, dtype=np.float64).reshape(-1)
+        if len(sw) != len(y):
+            raise ValueError("sample_weight holds {} weights for {} pairs".format(len(sw), len(y)))
+        w = w * sw
+    if class_weight is not None:
+        pair = (class_weight[0], class_weight[1])
+        w = w * np.where(y > 0.5, float(pair[1]), float(pair[0]))
+    return w
 
 
-def loss_dp(code, hyper, y_true, y_pred, f32_constants=False):
-    """float64 d(term_i)/d(p_i) of pointwise loss `code`: 0 where the loss is flat or clipped, TensorFlow's choice (0) at MAE's kink."""
-    return _pair_parts(code, hyper, y_true, y_pred, f32_constants)[1]
+def loss_terms(code, hyper, y_true, y_pred, f32_constants=False, sample_weight=None, class_weight=None):
+    """float64 per-pair terms of pointwise loss `code` (their sum over the batch size is the batch loss): what amar_loss_grad_f32
+    writes to loss_terms; with weights (`pair_weights`) w_j x the term, what amar_loss_grad_weighted_f32 writes."""
+    terms = _pair_parts(code, hyper, y_true, y_pred, f32_constants)[0]
+    w = pair_weights(y_true, sample_weight, class_weight)
+    return terms if w is None else w * terms
 
 
-def loss_value(loss, y_true, y_pred):
-    """float64 batch value of a compiled loss (anything `resolve_loss` accepts) on labels and probabilities: the mean of the
-    per-pair terms, BPRLoss's own value for BPR; an empty batch counts 0."""
+def loss_dp(code, hyper, y_true, y_pred, f32_constants=False, sample_weight=None, class_weight=None):
+    """float64 d(term_i)/d(p_i) of pointwise loss `code`: 0 where the loss is flat or clipped, TensorFlow's choice (0) at MAE's kink;
+    with weights w_i x that."""
+    dp = _pair_parts(code, hyper, y_true, y_pred, f32_constants)[1]
+    w = pair_weights(y_true, sample_weight, class_weight)
+    return dp if w is None else w * dp
+
+
+def loss_value(loss, y_true, y_pred, sample_weight=None, class_weight=None):
+    """float64 batch value of a compiled loss (anything `resolve_loss` accepts) on labels and probabilities: the sum of the per-pair
+    terms over the batch size B — weighted terms too (Keras' SUM_OVER_BATCH_SIZE: the divisor is B, not the sum of the weights);
+    BPRLoss's own value for BPR, which takes no weights; an empty batch counts 0."""
     code, hyper, _ = resolve_loss(loss)
     if code == BPR:
+        if sample_weight is not None or class_weight is not None:
+            raise ValueError("BPRLoss has no per-pair label or term: it takes no class_weight and no sample_weight")
         return BPRLoss()(y_true, y_pred)
-    terms = loss_terms(code, hyper, y_true, y_pred)
-    return float(np.mean(terms)) if len(terms) else 0.0
+    terms = loss_terms(code, hyper, y_true, y_pred, sample_weight=sample_weight, class_weight=class_weight)
+    return float(np.sum(terms) / len(terms)) if len(terms) else 0.0
+
+
+def resolve_class_weight(value, labels=None):
+    """Keras' fit(class_weight=...) for 0/1 labels as the pair (weight of class 0, weight of class 1) of Python floats; None stays None.
+    `value`: a mapping whose keys are 0 and 1, as ints or as the strings YAML gives ('0', '1') — a class it leaves out weighs 1 unless
+    `labels` holds that class — or 'balanced': N / (2 * count_c) over `labels` (scikit-learn's compute_class_weight).
+    ValueError: another key, a negative or non-finite weight, a class of `labels` absent from the mapping, 'balanced' without labels
+    or with an empty class, anything else."""
+    if value is None:
+        return None
+    present = None
+    if labels is not None:
+        lab = np.asarray(labels, dtype=np.float64).reshape(-1) > 0.5
+        present = (int((~lab).sum()), int(lab.sum()))
+    if isinstance(value, str):
+        if value != 'balanced':
+            raise ValueError("class_weight must be a mapping over the classes 0 and 1 or 'balanced' (got {!r})".format(value))
+        if present is None:
+            raise ValueError("class_weight='balanced' needs the labels it balances")
+        if min(present) == 0:
+            raise ValueError("class_weight='balanced': class {} has no label".format(0 if present[0] == 0 else 1))
+        n = float(sum(present))
+        return n / (2.0 * present[0]), n / (2.0 * present[1])
+    if not isinstance(value, Mapping):
+        raise ValueError("class_weight must be a mapping over the classes 0 and 1 or 'balanced' (got {!r})".format(value))
+    pair = [None, None]
+    for key, weight in value.items():
+        if isinstance(key, bool) or key not in (0, 1, '0', '1'):
+            raise ValueError("class_weight has the classes 0 and 1 (got the key {!r})".format(key))
+        c = int(key)
+        if pair[c] is not None:
+            raise ValueError("class_weight names class {} twice".format(c))
+        try:
+            weight = float(weight)
+        except (TypeError, ValueError):
+            raise ValueError("class_weight[{}] must be a number (got {!r})".format(c, weight))
+        if not np.isfinite(weight) or weight < 0.0 or weight > float(np.finfo(np.float32).max):     # (the device holds float32)
+            raise ValueError("class_weight[{}] must be finite and not negative (got {!r})".format(c, weight))
+        pair[c] = weight
+    for c in (0, 1):
+        if pair[c] is None:
+            if present is not None and present[c]:
+                raise ValueError("class {} occurs in the labels and has no weight in class_weight".format(c))
+            pair[c] = 1.0
+    return pair[0], pair[1]

@@ -1010,7 +1010,17 @@ int amar_bpr_sample_i32(const int32_t *pos_ptr, const int32_t *pos_ids, const in
  *                      AUC(num_thresholds=200) — b agrees with the float comparison p > threshold for every p.  Integer sums
  *                      (per wavefront, LDS, one global atomic per non-zero cell and workgroup): the same bits on every run.
  *                      NULL: nothing is counted and nothing is written.
- * amar_loss_counters   AMAR_LOSS_COUNTERS, for a caller that sizes the block at run time. */
+ * amar_loss_counters   AMAR_LOSS_COUNTERS, for a caller that sizes the block at run time.
+ * amar_loss_grad_weighted_f32  amar_loss_grad_f32 under Keras' fit(class_weight=..., sample_weight=...): the pair's weight is
+ *                      w_i = (sample_w ? sample_w[i] : 1) * (class_w ? class_w[y[i] > 0.5] : 1), the class taken from the 0/1 label
+ *                      itself (before label smoothing).  sample_w: [B] floats, class_w: TWO floats (class 0, class 1), both in DEVICE
+ *                      memory and read by the kernel (a captured graph follows new weights without a new capture); either may be
+ *                      NULL, both NULL: AMAR_EINVAL (that call is amar_loss_grad_f32's).  The kernel computes exactly what the
+ *                      unweighted instance computes and multiplies as the LAST float32 operation: loss_terms[i] = w_i * term_i,
+ *                      dz[i] = w_i * dz_i — so every output is float32(w_i x amar_loss_grad_f32's output), w_i = 1 gives its bits and
+ *                      w_i = 0 gives 0.  The divisor of dz stays B (Keras' SUM_OVER_BATCH_SIZE), not sum(w).  The counters, if
+ *                      given, count every pair once as before: compiled metrics are unweighted.  Other arguments and refusals as
+ *                      amar_loss_grad_f32. */
 #define AMAR_LOSS_BCE           0
 #define AMAR_LOSS_MSE           1
 #define AMAR_LOSS_MAE           2
@@ -1026,6 +1036,8 @@ int amar_bpr_sample_i32(const int32_t *pos_ptr, const int32_t *pos_ids, const in
 int32_t amar_loss_counters(void);
 int amar_loss_grad_f32(int32_t loss, const float *hyper, const float *p, int64_t ldp, const float *y, float *dz, float *loss_terms,
                        int64_t B, int64_t *counters, amar_stream_t stream);
+int amar_loss_grad_weighted_f32(int32_t loss, const float *hyper, const float *p, int64_t ldp, const float *y, const float *sample_w,
+                                const float *class_w, float *dz, float *loss_terms, int64_t B, int64_t *counters, amar_stream_t stream);
 
 /* ---- training-time dropout (the `dropout` key of the GNN stacks, `dropout_rate` of GAT) ------------------------------------------
  * No mask is stored: a keep bit is a function of (seed, step, site, element) through Philox4x32-10 and the reverse pass regenerates
