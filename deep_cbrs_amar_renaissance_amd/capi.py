@@ -53,6 +53,7 @@ SIGNATURES = {
     'amar_rowwise_xw_heads_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I32, _I32, _P, _I64, _P, _P, _P, _I32, _P]),
     'amar_gat_heads_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _P]),
     'amar_dense_f32': (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _P]),
+    'amar_dense_route': (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _P]),
     'amar_dense_split_bytes': (ctypes.c_int64, [_I32, _I32]),
     'amar_dense_split_pack_f32': (ctypes.c_int, [_P, _I32, _I32, _P]),
     'amar_dense_split_f32': (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _P]),
@@ -745,6 +746,35 @@ def dense(X, W, bias, Y, act='relu', ids=None, w_transposed=False):
         _ptr(W, torch.float32, 'W'), _ptr(bias, torch.float32, 'bias'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
         M, K, N, ACT_CODES[act] | (DENSE_WT if w_transposed else 0), _stream())
     _check(code, 'amar_dense_f32')
+
+
+class DenseRouteInfo(ctypes.Structure):
+    """include/amar_hip.h: amar_dense_route_info"""
+    _fields_ = [(name, ctypes.c_int32) for name in ('kernel', 'vec_x', 'vec_w', 'w_trans', 'grid_x', 'grid_y', 'n_col_blocks', 'launches')]
+    KERNELS = {0: 'small', 1: 'tile128', 2: 'full', 3: 'guarded', -1: None}
+
+    def as_dict(self):
+        d = {name: int(getattr(self, name)) for name, _ in self._fields_}
+        d['kernel'] = self.KERNELS[d['kernel']]
+        for name in ('vec_x', 'vec_w', 'w_trans'):
+            d[name] = bool(d[name])
+        return d
+
+
+def dense_route(X, W, Y, act='relu', ids=None, w_transposed=False, bias=None):
+    """Which kernel dense() takes for these tensors (amar_dense_route: host only, nothing is launched; the launcher asks the same
+    function).  A dict: kernel 'small' | 'tile128' | 'full' | 'guarded', vec_x, vec_w, w_trans, grid_x, grid_y, n_col_blocks, launches."""
+    K, N = (W.shape[1], W.shape[0]) if w_transposed else W.shape
+    M = ids.numel() if ids is not None else X.shape[0]
+    if X.shape[1] != K or not W.is_contiguous() or tuple(Y.shape) != (M, N):
+        raise ValueError("dense: X [*, K], W [K, N] contiguous, Y [M, N] expected")
+    info = DenseRouteInfo()
+    code = load().amar_dense_route(
+        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), _ptr(ids, torch.int32, 'ids'),
+        _ptr(W, torch.float32, 'W'), _ptr(bias, torch.float32, 'bias'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
+        M, K, N, ACT_CODES[act] | (DENSE_WT if w_transposed else 0), ctypes.byref(info))
+    _check(code, 'amar_dense_route')
+    return info.as_dict()
 
 
 def dense_split_supported(K, N):

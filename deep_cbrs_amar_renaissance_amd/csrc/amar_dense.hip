@@ -490,43 +490,80 @@ __global__ __launch_bounds__(256) void topk_segmented_kernel(const int32_t *__re
 
 }  // namespace
 
-extern "C" {
-
-int amar_dense_f32(const float *X, int64_t ldx, const int32_t *ids,
-                   const float *W, const float *bias, float *Y, int64_t ldy,
-                   int64_t M, int32_t K, int32_t N, int32_t act, amar_stream_t stream) {
+// Which kernel a Dense call takes, and on what grid: decided HERE and nowhere else — amar_dense_f32 launches what this returns and
+// amar_dense_route reports it.  Pointers are looked at for NULL and for their alignment only.  `act` comes back without AMAR_DENSE_WT.
+enum { DENSE_SMALL = AMAR_DENSE_KERNEL_SMALL, DENSE_TILE128 = AMAR_DENSE_KERNEL_TILE128, DENSE_FULL = AMAR_DENSE_KERNEL_FULL,
+       DENSE_GUARDED = AMAR_DENSE_KERNEL_GUARDED };
+struct DenseRoute { int kernel; bool vx, vw; int w_trans; int act; unsigned grid_x, grid_y; int n_col_blocks; bool launch; };
+static int dense_route(const float *X, int64_t ldx, const float *W, const float *Y, int64_t ldy, int64_t M, int32_t K, int32_t N, int32_t act,
+                       DenseRoute &r) {
     if (M < 0 || K < 1 || N < 1 || !X || !W || !Y || ldx < K || ldy < N) return AMAR_EINVAL;
-    const int w_trans = (act & AMAR_DENSE_WT) ? 1 : 0;
-    act &= ~AMAR_DENSE_WT;
-    if (act != AMAR_ACT_NONE && act != AMAR_ACT_RELU && act != AMAR_ACT_SIGMOID) return AMAR_EINVAL;
+    r.w_trans = (act & AMAR_DENSE_WT) ? 1 : 0;
+    r.act = act & ~AMAR_DENSE_WT;
+    if (r.act != AMAR_ACT_NONE && r.act != AMAR_ACT_RELU && r.act != AMAR_ACT_SIGMOID) return AMAR_EINVAL;
+    r.launch = M > 0;
+    r.kernel = -1; r.vx = r.vw = false; r.grid_x = r.grid_y = 0; r.n_col_blocks = 0;
     if (M == 0) return AMAR_OK;
     const int64_t gx = (M + BM - 1) / BM;
     if (gx > 0x7fffffffLL) return AMAR_EUNSUPPORTED;
     const int ny = (N + BN - 1) / BN;
-    DenseArgs a{X, ldx, ids, W, bias, Y, ldy, M, K, N, act, w_trans, ny};
     const int64_t total = ((gx + 7) / 8) * 8 * ny;
     if (total > 0x7fffffffLL) return AMAR_EUNSUPPORTED;
-    const dim3 grid((unsigned)total), block(256);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool vx = (ldx & 3) == 0 && amar_aligned16(X);
-    const bool vw = (N & 3) == 0 && amar_aligned16(W);
-    if (vx && vw && !w_trans && K % SK == 0 && N % SB == 0 && M <= 4096) {
-        hipLaunchKernelGGL(dense_mfma_small_kernel, dim3((unsigned)((M + SB - 1) / SB), (unsigned)(N / SB)), block, 0, st, a);
-        return amar_check_launch();
+    r.vx = (ldx & 3) == 0 && amar_aligned16(X);
+    r.vw = (N & 3) == 0 && amar_aligned16(W);
+    const bool guard_free = r.vx && r.vw && !r.w_trans;
+    if (guard_free && K % SK == 0 && N % SB == 0 && M <= 4096) {
+        r.kernel = DENSE_SMALL;
+        r.grid_x = (unsigned)((M + SB - 1) / SB); r.grid_y = (unsigned)(N / SB); r.n_col_blocks = N / SB;
+        return AMAR_OK;
     }
     // the 128-column tile only where it still fills the chip: a batch-sized product (1 024 rows x 768 -> 256: the first layer of a content
     // tower inside model.fit) is 32 workgroups of it, each walking K alone on its CU — 64 us against 38 with the 64-column tile's 64 workgroups
-    if (vx && vw && !w_trans && K % BK == 0 && N % BN2 == 0 && ((gx + 7) / 8) * 8 * (N / BN2) >= 256) {
-        DenseArgs a2 = a;
-        a2.n_col_blocks = N / BN2;
-        const int64_t total2 = ((gx + 7) / 8) * 8 * a2.n_col_blocks;
-        hipLaunchKernelGGL(dense_mfma128_kernel<16>, dim3((unsigned)total2), block, 0, st, a2);
-        return amar_check_launch();
+    if (guard_free && K % BK == 0 && N % BN2 == 0 && ((gx + 7) / 8) * 8 * (N / BN2) >= 256) {
+        r.kernel = DENSE_TILE128;
+        r.n_col_blocks = N / BN2;
+        r.grid_x = (unsigned)(((gx + 7) / 8) * 8 * r.n_col_blocks); r.grid_y = 1;
+        return AMAR_OK;
     }
-    if (vx && vw && !w_trans && K % BK == 0 && N % BN == 0) hipLaunchKernelGGL((dense_mfma_kernel<true, true, true>), grid, block, 0, st, a);
-    else if (vx && vw) hipLaunchKernelGGL((dense_mfma_kernel<true, true>), grid, block, 0, st, a);
-    else if (vx) hipLaunchKernelGGL((dense_mfma_kernel<true, false>), grid, block, 0, st, a);
-    else if (vw) hipLaunchKernelGGL((dense_mfma_kernel<false, true>), grid, block, 0, st, a);
+    r.kernel = guard_free && K % BK == 0 && N % BN == 0 ? DENSE_FULL : DENSE_GUARDED;
+    r.n_col_blocks = ny;
+    r.grid_x = (unsigned)total; r.grid_y = 1;
+    return AMAR_OK;
+}
+
+extern "C" {
+
+int amar_dense_route(const float *X, int64_t ldx, const int32_t *ids, const float *W, const float *bias, float *Y, int64_t ldy,
+                     int64_t M, int32_t K, int32_t N, int32_t act, amar_dense_route_info *info) {
+    (void)ids; (void)bias;
+    if (!info) return AMAR_EINVAL;
+    memset(info, 0, sizeof(*info));
+    info->kernel = -1;
+    DenseRoute r;
+    if (const int rc = dense_route(X, ldx, W, Y, ldy, M, K, N, act, r)) return rc;
+    info->kernel = r.kernel;
+    info->vec_x = r.vx; info->vec_w = r.vw; info->w_trans = r.w_trans;
+    info->grid_x = (int32_t)r.grid_x; info->grid_y = (int32_t)r.grid_y;
+    info->n_col_blocks = r.n_col_blocks;
+    info->launches = r.launch ? 1 : 0;
+    return AMAR_OK;
+}
+
+int amar_dense_f32(const float *X, int64_t ldx, const int32_t *ids,
+                   const float *W, const float *bias, float *Y, int64_t ldy,
+                   int64_t M, int32_t K, int32_t N, int32_t act, amar_stream_t stream) {
+    DenseRoute r;
+    if (const int rc = dense_route(X, ldx, W, Y, ldy, M, K, N, act, r)) return rc;
+    if (!r.launch) return AMAR_OK;
+    const DenseArgs a{X, ldx, ids, W, bias, Y, ldy, M, K, N, r.act, r.w_trans, r.n_col_blocks};
+    const dim3 grid(r.grid_x, r.grid_y), block(256);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (r.kernel == DENSE_SMALL) hipLaunchKernelGGL(dense_mfma_small_kernel, grid, block, 0, st, a);
+    else if (r.kernel == DENSE_TILE128) hipLaunchKernelGGL(dense_mfma128_kernel<16>, grid, block, 0, st, a);
+    else if (r.kernel == DENSE_FULL) hipLaunchKernelGGL((dense_mfma_kernel<true, true, true>), grid, block, 0, st, a);
+    else if (r.vx && r.vw) hipLaunchKernelGGL((dense_mfma_kernel<true, true>), grid, block, 0, st, a);
+    else if (r.vx) hipLaunchKernelGGL((dense_mfma_kernel<true, false>), grid, block, 0, st, a);
+    else if (r.vw) hipLaunchKernelGGL((dense_mfma_kernel<false, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((dense_mfma_kernel<false, false>), grid, block, 0, st, a);
     return amar_check_launch();
 }

@@ -331,6 +331,33 @@ int amar_gat_heads_f32(const int32_t *rowptr, const int32_t *colidx,
 int amar_dense_f32(const float *X, int64_t ldx, const int32_t *ids,
                    const float *W, const float *bias, float *Y, int64_t ldy,
                    int64_t M, int32_t K, int32_t N, int32_t act, amar_stream_t stream);
+/* Which kernel an amar_dense_f32 call with these arguments takes (host only: nothing is launched, the pointers are looked at for NULL and
+ * for their alignment; `act` may carry AMAR_DENSE_WT).  The launcher asks the same function, so the two cannot disagree.  Returns what the
+ * launcher's argument checks return (AMAR_EINVAL, AMAR_EUNSUPPORTED for a grid past 2^31 - 1; info == NULL: AMAR_EINVAL).
+ *   kernel        first match wins; "aligned" = vec_x and vec_w and no AMAR_DENSE_WT
+ *                 AMAR_DENSE_KERNEL_SMALL    64 x 64 tiles, two k-tiles of 32 in flight: aligned, K % 32 == 0, N % 64 == 0, M <= 4 096
+ *                 AMAR_DENSE_KERNEL_TILE128  128 x 128 tiles, guard-free: aligned, K % 16 == 0, N % 128 == 0 and
+ *                                            ceil8(ceil(M / 128)) * N / 128 >= 256 workgroups
+ *                 AMAR_DENSE_KERNEL_FULL     128 x 64 tiles, guard-free: aligned, K % 16 == 0, N % 64 == 0
+ *                 AMAR_DENSE_KERNEL_GUARDED  128 x 64 tiles with guarded staging, in the (vec_x, vec_w) variant: everything else
+ *                 -1 when an argument was refused
+ *   vec_x         X is read by 16-byte loads where the kernel can: ldx % 4 == 0 and X 16-byte aligned
+ *   vec_w         the same for W: N % 4 == 0 and W 16-byte aligned (a transposed W is read by single floats whatever vec_w says; it still
+ *                 selects the variant).  Y and bias are written / read by single floats: their alignment is not looked at.
+ *   w_trans       AMAR_DENSE_WT was given
+ *   grid_x, grid_y  the launched grid.  SMALL: ceil(M / 64) x N / 64.  The others: ceil8(ceil(M / 128)) * n_col_blocks x 1 (workgroup L
+ *                 runs on XCD L % 8; row tiles past M return at once)
+ *   n_col_blocks  column blocks: N / 64 (SMALL), N / 128 (TILE128), ceil(N / 64) (FULL, GUARDED)
+ *   launches      1, or 0 for M == 0 (AMAR_OK, nothing to do: kernel is -1, vec_x, vec_w, the grid and n_col_blocks are 0) */
+#define AMAR_DENSE_KERNEL_SMALL 0
+#define AMAR_DENSE_KERNEL_TILE128 1
+#define AMAR_DENSE_KERNEL_FULL 2
+#define AMAR_DENSE_KERNEL_GUARDED 3
+typedef struct amar_dense_route_info {
+    int32_t kernel, vec_x, vec_w, w_trans, grid_x, grid_y, n_col_blocks, launches;
+} amar_dense_route_info;
+int amar_dense_route(const float *X, int64_t ldx, const int32_t *ids, const float *W, const float *bias, float *Y, int64_t ldy,
+                     int64_t M, int32_t K, int32_t N, int32_t act, amar_dense_route_info *info);
 
 /* The same layer with its products on the bf16 matrix instruction and BOTH operands split three ways (x = hi + mid + lo
  * exactly, six part products accumulated in f32: as accurate as the f32 instruction, 2.7 times fewer matrix-pipe cycles) for

@@ -275,10 +275,10 @@ def test_dense(hip, M, K, N, act):
 
 
 def test_dense_guard_free_form_with_row_gather(hip):
-    """The guard-free staging forms of amar_dense_f32 (K % 16 == 0): the 128 x 64 tile (N % 64 == 0: N = 64, 192) and the 128 x 128
-    tile with four accumulators per wave (N % 128 == 0: N = 128, 256 — one and two column blocks).  Row gather through ids, last
-    row tiles that are mostly past M (those lanes re-read row M - 1 and are dropped), several row tiles (the XCD-affine tile
-    order), all three activations."""
+    """The guard-free 128 x 64 tile of amar_dense_f32 (K = 48: a multiple of 16 and not of 32; N % 64 == 0: one to four column blocks).
+    Row gather through ids, last row tiles that are mostly past M (those lanes re-read row M - 1 and are dropped), several row tiles
+    (the XCD-affine tile order), all three activations.  Every call here is `full`: at most 16 x 2 workgroups of the 128 x 128 tile, which
+    is taken from 256 on (tests/test_dense_forms_gpu.py runs that one).  The deep product at the end is the 64 x 64 small kernel."""
     rng = np.random.default_rng(5)
     table = rng.standard_normal((400, 48)).astype(np.float32)
     for N in (64, 128, 192, 256):
@@ -288,6 +288,7 @@ def test_dense_guard_free_form_with_row_gather(hip):
             ids = rng.integers(7, 400, size=M).astype(np.int32)
             for act in ('relu', 'sigmoid', None):
                 y = torch.full((M, N), float('nan'), device=DEV)
+                assert hip.dense_route(_t(table), _t(w), y, act=act, ids=_t(ids))['kernel'] == 'full'
                 hip.dense(_t(table), _t(w), _t(b), y, act=act, ids=_t(ids))
                 want = ol.dense(table[ids].astype(np.float64), w.astype(np.float64), b.astype(np.float64), act)
                 assert rel_err(y.cpu().numpy(), want) < 3e-6
@@ -295,6 +296,7 @@ def test_dense_guard_free_form_with_row_gather(hip):
     x = rng.standard_normal((300, 768)).astype(np.float32)
     w = rng.uniform(-0.05, 0.05, (768, 256)).astype(np.float32)
     y = torch.full((300, 256), float('nan'), device=DEV)
+    assert hip.dense_route(_t(x), _t(w), y, act=None)['kernel'] == 'small'
     hip.dense(_t(x), _t(w), None, y, act=None)
     assert rel_err(y.cpu().numpy(), x.astype(np.float64) @ w.astype(np.float64)) < 3e-6
 
@@ -1364,11 +1366,13 @@ def test_dense_batch_sized_wide_layers(hip, M, K, N, act, gather):
     x_d, w_d, b_d = _t(x), _t(w), _t(b)
     ids_d = _t(ids) if gather else None
     y_small = torch.empty((M, N), device=DEV)
+    assert hip.dense_route(x_d if gather else x_d[:M], w_d, y_small, act=act, ids=ids_d[:M] if gather else None)['kernel'] == 'small'
     hip.dense(x_d if gather else x_d[:M], w_d, b_d, y_small, act=act, ids=ids_d[:M] if gather else None)
     src = x[ids[:M]] if gather else x[:M]
     z = src.astype(np.float64) @ w.astype(np.float64) + b
     want = np.maximum(z, 0) if act == 'relu' else 1 / (1 + np.exp(-z)) if act == 'sigmoid' else z
     assert helpers.rel_err(y_small.cpu().numpy(), want) < 3e-6
     y_big = torch.empty((big, N), device=DEV)
+    assert hip.dense_route(x_d, w_d, y_big, act=act, ids=ids_d)['kernel'] == 'full'
     hip.dense(x_d, w_d, b_d, y_big, act=act, ids=ids_d)
     assert torch.equal(y_big[:M], y_small)
