@@ -121,6 +121,8 @@ SIGNATURES = {
     'amar_grad_clip_f32': (ctypes.c_int, [_I32, _F32, _P, _I32, _I64, _P, _P, _F32, _P, _P]),
     'amar_bpr_grad_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P]),
     'amar_bpr_sample_i32': (ctypes.c_int, [_P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _I32, _I32, _P, _P, _P, _P]),
+    'amar_bpr_sample_triplets_i32': (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, ctypes.c_uint64, _P, _I32, _I32, _P, _P,
+                                                    _P, _P]),
     'amar_loss_counters': (ctypes.c_int32, []),
     'amar_loss_grad_f32': (ctypes.c_int, [_I32, _P, _P, _I64, _P, _P, _P, _I64, _P, _P]),
     'amar_loss_grad_weighted_f32': (ctypes.c_int, [_I32, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P]),
@@ -1867,6 +1869,26 @@ def bpr_sample(pos_ptr, pos_ids, neg_ptr, neg_ids, n_users, seed, step, u, items
                                       int(seed) & 0xFFFFFFFFFFFFFFFF, step.data_ptr() if step.is_cuda else _ptr(step), int(bool(advance)), h,
                                       _ptr(u, torch.int32, 'u'), _ptr(items, torch.int32, 'items'), _ptr(y, torch.float32, 'y'), _stream())
     _check(code, 'amar_bpr_sample_i32')
+
+
+def bpr_sample_triplets(pos_ptr, pos_ids, excl_ptr, excl_ids, n_users, n_items, item_base, seed, step, u, items, y=None,
+                        n_negatives=1, mode=0, advance=True):
+    """One batch of h = items.numel() // 2 BPR triples into u [2h], items [2h] (int32) and y [2h] (float32, optional):
+    u[t] = u[h + t] = the triple's user, items[t] its positive, items[h + t] its negative — uniform over the items outside the user's
+    exclusion row.  `n_negatives` triples share one (user, positive) draw; mode 0 draws users uniformly, 1 interactions.  step: one
+    int64 on the device, advanced by one when `advance`.  The CSRs are int32 device tensors, exclusion rows strictly ascending inside
+    [item_base, item_base + n_items) and shorter than n_items, positive rows non-empty (checked by the caller where they are
+    uploaded)."""
+    h = items.numel() // 2
+    if u.numel() != 2 * h or items.numel() != 2 * h or (y is not None and y.numel() != 2 * h) or step.numel() != 1 \
+            or step.dtype != torch.int64 or pos_ptr.numel() != n_users + 1 or excl_ptr.numel() != n_users + 1:
+        raise ValueError("bpr_sample_triplets: u, items (and y) of 2h elements, an int64 step and CSR row pointers [n_users + 1] expected")
+    code = load().amar_bpr_sample_triplets_i32(
+        _ptr(pos_ptr, torch.int32, 'pos_ptr'), _ptr(pos_ids, torch.int32, 'pos_ids'), _ptr(excl_ptr, torch.int32, 'excl_ptr'),
+        _ptr_entries(excl_ids, torch.int32, 'excl_ids'), int(n_users), int(n_items), int(item_base), int(n_negatives), int(mode),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, step.data_ptr() if step.is_cuda else _ptr(step), int(bool(advance)), h,
+        _ptr(u, torch.int32, 'u'), _ptr(items, torch.int32, 'items'), _ptr(y, torch.float32, 'y'), _stream())
+    _check(code, 'amar_bpr_sample_triplets_i32')
 
 
 class Dropout:

@@ -5,6 +5,9 @@
 // amar_bpr_sample_i32 draws one batch of data/datasets.py:UserItemGraphPosNegSample in the reference's layout from a counter-based
 // RNG (Philox4x32-10): the draws depend on (seed, step, j) only, so data/datasets.py:bpr_device_batch restates every id, and a step
 // index read from device memory lets a captured training graph draw new ids on every replay.
+// amar_bpr_sample_triplets_i32 draws (user, positive, negative) triples of data/datasets.py:UserItemGraphTriplets the same way: both
+// items of a pair belong to one user and the negative is uniform over the items outside that user's exclusion row
+// (data/datasets.py:bpr_triplet_device_batch restates it).
 #include "amar_common.h"
 #include "amar_philox.h"
 
@@ -57,6 +60,53 @@ __global__ __launch_bounds__(256) void bpr_sample_kernel(const int32_t *__restri
     if (advance && threadIdx.x == 0) *step = s + 1;
 }
 
+// Triples (user, pos, neg): draw j < h / K picks the user and its positive, triple t = j * K + k its k-th negative — the r-th item
+// outside the user's ascending exclusion row, r uniform in [0, n_items - d).  With e_q the q-th excluded item (0-based in the item
+// range), e_q - q counts the free items below e_q and never decreases, so m = #{q : e_q - q <= r} is one binary search and the
+// r-th free item is r + m.  ONE workgroup, as above: every lane reads *step before the barrier, one lane advances it after.
+__global__ __launch_bounds__(256) void bpr_sample_triplets_kernel(const int32_t *__restrict__ pos_ptr, const int32_t *__restrict__ pos_ids,
+                                                                  const int32_t *__restrict__ excl_ptr, const int32_t *__restrict__ excl_ids,
+                                                                  int32_t n_users, int32_t n_items, int32_t item_base, int32_t K, int32_t mode,
+                                                                  uint32_t key0, uint32_t key1, uint64_t *step, int32_t advance, int32_t h,
+                                                                  int32_t *__restrict__ u, int32_t *__restrict__ items, float *__restrict__ y) {
+    const uint64_t s = *step;
+    for (int32_t t = threadIdx.x; t < h; t += blockDim.x) {
+        uint32_t c[4] = {(uint32_t)(t / K), (uint32_t)s, (uint32_t)(s >> 32), 0u};
+        philox4x32_10(c, key0, key1);
+        int32_t user, pos;
+        if (mode == 0) {                                               // users uniform
+            user = pick(c[0], n_users);
+            const int32_t p0 = pos_ptr[user];
+            pos = pos_ids[p0 + pick(c[1], pos_ptr[user + 1] - p0)];
+        } else {                                                       // interactions uniform: the row that holds entry e
+            const int32_t e = pick(c[0], pos_ptr[n_users]);
+            int32_t lo = 0, hi = n_users - 1;                          // largest r with pos_ptr[r] <= e
+            while (lo < hi) {
+                const int32_t mid = lo + (hi - lo + 1) / 2;
+                if (pos_ptr[mid] <= e) lo = mid; else hi = mid - 1;
+            }
+            user = lo;
+            pos = pos_ids[e];
+        }
+        uint32_t w[4] = {(uint32_t)t, (uint32_t)s, (uint32_t)(s >> 32), 1u};
+        philox4x32_10(w, key0, key1);
+        const int32_t x0 = excl_ptr[user], d = excl_ptr[user + 1] - x0;
+        const int32_t r = pick(w[0], n_items - d);
+        int32_t lo = 0, hi = d;                                        // m = #{q < d : e_q - q <= r}
+        while (lo < hi) {
+            const int32_t mid = lo + (hi - lo) / 2;
+            if (excl_ids[x0 + mid] - item_base - mid <= r) lo = mid + 1; else hi = mid;
+        }
+        u[t] = user;
+        u[h + t] = user;
+        items[t] = pos;
+        items[h + t] = item_base + r + lo;
+        if (y) { y[t] = 1.f; y[h + t] = 0.f; }
+    }
+    __syncthreads();
+    if (advance && threadIdx.x == 0) *step = s + 1;
+}
+
 }  // namespace
 
 int amar_bpr_grad_f32(const float *p, int64_t ldp, float *dz, float *loss_terms, int64_t B, amar_stream_t stream) {
@@ -79,5 +129,18 @@ int amar_bpr_sample_i32(const int32_t *pos_ptr, const int32_t *pos_ids, const in
     if (n_users < 1 || h < 1 || !pos_ptr || !pos_ids || !neg_ptr || !neg_ids || !step || !u || !items) return AMAR_EINVAL;
     hipLaunchKernelGGL(bpr_sample_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), pos_ptr, pos_ids, neg_ptr, neg_ids,
                        n_users, (uint32_t)seed, (uint32_t)(seed >> 32), step, advance, h, u, items, y);
+    return amar_check_launch();
+}
+
+int amar_bpr_sample_triplets_i32(const int32_t *pos_ptr, const int32_t *pos_ids, const int32_t *excl_ptr, const int32_t *excl_ids,
+                                 int32_t n_users, int32_t n_items, int32_t item_base, int32_t n_negatives, int32_t mode, uint64_t seed,
+                                 uint64_t *step, int32_t advance, int32_t h, int32_t *u, int32_t *items, float *y,
+                                 amar_stream_t stream) {
+    if (n_users < 1 || n_items < 1 || h < 1 || n_negatives < 1 || h % n_negatives != 0 || (mode != 0 && mode != 1) || !pos_ptr ||
+        !pos_ids || !excl_ptr || !excl_ids || !step || !u || !items)
+        return AMAR_EINVAL;
+    hipLaunchKernelGGL(bpr_sample_triplets_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), pos_ptr, pos_ids, excl_ptr,
+                       excl_ids, n_users, n_items, item_base, n_negatives, mode, (uint32_t)seed, (uint32_t)(seed >> 32), step, advance, h,
+                       u, items, y);
     return amar_check_launch();
 }

@@ -17,6 +17,10 @@ ids are int64 with item ids already offset by |U|; the last batch is short.  Shu
 
 ``UserItemGraphPosNegSample`` (BPR) draws its batches: on the host in ``__getitem__`` (the reference's stream) and, inside
 ``fit()``, on the device (``bpr_device_batch`` states that kernel's draws).
+
+``UserItemGraphTriplets`` has no counterpart in the reference: BPR triples (user, positive, negative) in the same batch tuple, both
+items under the user they were drawn for, the negative uniform over the user's unobserved items; drawn on the device inside
+``fit()`` and restated by ``bpr_triplet_device_batch``.
 """
 import itertools as it
 
@@ -287,6 +291,129 @@ def bpr_device_batch(pos_csr, neg_csr, n_users, seed, step, h):
     pos = np.asarray(pi)[pp[users] + _pick(w[:, 1], pp[users + 1] - pp[users])].astype(np.int64)
     neg = np.asarray(ni)[npt[users] + _pick(w[:, 2], npt[users + 1] - npt[users])].astype(np.int64)
     return (np.repeat(users, 2), np.concatenate([pos, neg])), np.concatenate([np.ones(h, np.int64), np.zeros(h, np.int64)])
+
+
+# ---- BPR triples: per-user pairs, negatives uniform over a user's unobserved items (amar_bpr_sample_triplets_i32) ----------------
+SAMPLE_BY = {'user': 0, 'interaction': 1}                             # the kernel's `mode`
+
+
+def _philox_words(c0, step, c3, seed):
+    n = len(c0)
+    counter = np.stack([np.asarray(c0, np.uint64), np.full(n, step & 0xFFFFFFFF, np.uint64), np.full(n, step >> 32, np.uint64),
+                        np.full(n, c3, np.uint64)], axis=1)
+    return philox4x32_10(counter.astype(np.uint32), (seed & 0xFFFFFFFF, seed >> 32))
+
+
+def nth_non_excluded(excluded, r):
+    """The r-th (0-based) item outside the strictly ascending list `excluded` (0-based item numbers): with e_q the q-th excluded
+    item, e_q - q counts the free items below it and never decreases, so m = #{q : e_q - q <= r} is one binary search and the
+    answer is r + m.  `r` may be an array."""
+    excluded = np.asarray(excluded, dtype=np.int64)
+    return np.asarray(r, dtype=np.int64) + np.searchsorted(excluded - np.arange(len(excluded)), r, side='right')
+
+
+def bpr_triplet_device_batch(pos_csr, excl_csr, n_users, n_items, item_base, seed, step, h, n_negatives=1, sample_by='user'):
+    """What amar_bpr_sample_triplets_i32 writes for (seed, step): h triples, K = n_negatives of them per draw (P = h / K draws).
+    Philox4x32-10 with key = (seed_lo, seed_hi), pick(w, n) = (uint64(w) * n) >> 32.
+      draw j < P, counter (j, step_lo, step_hi, 0): 'user': user = pick(w0, n_users), pos = its pick(w1, n_pos)-th positive;
+        'interaction': e = pick(w0, all positives), user = the row that holds entry e, pos = pos_ids[e].
+      triple t = j * K + k, counter (t, step_lo, step_hi, 1): neg = item_base + the pick(w0, n_items - d)-th item outside the user's
+        exclusion row (d its length; `nth_non_excluded`): uniform over the complement, one draw, no rejection.
+    Returns ((users[2h], items[2h]), ratings[2h]) with users[t] = users[h + t], items = [pos; neg], ratings = [1]*h + [0]*h (int64)."""
+    if sample_by not in SAMPLE_BY:
+        raise ValueError("sample_by must be 'user' or 'interaction' (got {!r})".format(sample_by))
+    K, h = int(n_negatives), int(h)
+    if K < 1 or h < 1 or h % K:
+        raise ValueError("h = {} triples do not split into draws of n_negatives = {}".format(h, K))
+    seed, step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF
+    (pp, pi), (xp, xi) = pos_csr, excl_csr
+    pp, xp, pi, xi = np.asarray(pp, np.int64), np.asarray(xp, np.int64), np.asarray(pi, np.int64), np.asarray(xi, np.int64)
+    w = _philox_words(np.arange(h // K), step, 0, seed)
+    if SAMPLE_BY[sample_by] == 0:
+        users = _pick(w[:, 0], n_users)
+        pos = pi[pp[users] + _pick(w[:, 1], pp[users + 1] - pp[users])]
+    else:
+        e = _pick(w[:, 0], pp[n_users])
+        users = np.searchsorted(pp[:n_users], e, side='right') - 1    # the largest r with pos_ptr[r] <= e
+        pos = pi[e]
+    users, pos = np.repeat(users, K), np.repeat(pos, K)
+    d = xp[users + 1] - xp[users]
+    r = _pick(_philox_words(np.arange(h), step, 1, seed)[:, 0], n_items - d)
+    neg = np.empty(h, np.int64)
+    for t in range(h):
+        row = xi[xp[users[t]]:xp[users[t] + 1]] - item_base
+        neg[t] = item_base + nth_non_excluded(row, r[t])
+    return (np.concatenate([users, users]), np.concatenate([pos, neg])), np.concatenate([np.ones(h, np.int64), np.zeros(h, np.int64)])
+
+
+def _user_lists(user_ids, item_ids, n_users):
+    """CSR (int32 row pointers [n_users + 1], int32 ids) of the distinct (user, item) pairs, items ascending within a user."""
+    pairs = np.unique(np.stack([np.asarray(user_ids, np.int64), np.asarray(item_ids, np.int64)], axis=1), axis=0) \
+        if len(user_ids) else np.zeros((0, 2), np.int64)
+    ptr = np.zeros(n_users + 1, dtype=np.int64)
+    np.add.at(ptr, pairs[:, 0] + 1, 1)
+    return np.cumsum(ptr).astype(np.int32), pairs[:, 1].astype(np.int32)
+
+
+class UserItemGraphTriplets:
+    """BPR triples (user, positive, negative) drawn per user: both items of a pair are scored against the user they were drawn for,
+    and the negative is uniform over the items outside the user's exclusion list (Rendle et al.'s BPR; LightGCN's sampler).
+
+    `adj_matrix` is the ordinary 'unary' training graph the model propagates over, kept as it is.  The positives are the training
+    ratings with label 1, deduplicated, ascending per user.  ``exclude='positives'``: anything the user has not liked is a candidate,
+    explicit dislikes included; ``exclude='rated'``: every item the user rated in training is excluded.  ``sample_by='user'`` draws
+    users uniformly, ``'interaction'`` draws positive interactions uniformly.  `n_negatives` triples share one (user, positive).
+
+    A batch holds h = batch_size // 2 triples as ``users[t] = users[h + t]``, ``items = [pos; neg]``, ``ratings = [1]*h + [0]*h``:
+    BPRLoss pairs rows (t, h + t).  There is no host RNG stream: ``__getitem__(idx)`` is ``device_batch(idx)``, the batch the device
+    sampler draws at step `idx`.  An epoch has ceil(#positives / (h // n_negatives)) batches, about one draw per training positive.
+
+    ``pos_csr`` / ``excl_csr``: the per-user lists as CSR (int32 row pointers [|U|+1], int32 node ids), what ``fit()`` uploads."""
+
+    def __init__(self, ratings, users, items, adj_matrix, batch_size=512, seed=42, n_negatives=1, sample_by='user',
+                 exclude='positives'):
+        if sample_by not in SAMPLE_BY:
+            raise ValueError("sample_by must be 'user' or 'interaction' (got {!r})".format(sample_by))
+        if exclude not in ('positives', 'rated'):
+            raise ValueError("exclude must be 'positives' or 'rated' (got {!r})".format(exclude))
+        h, K = int(batch_size) // 2, int(n_negatives)
+        if h < 1:
+            raise ValueError("a BPR batch needs batch_size >= 2")
+        if K < 1 or h % K:
+            raise ValueError("batch_size // 2 = {} triples do not split into draws of n_negatives = {}".format(h, n_negatives))
+        self.ratings, self.users, self.items, self.adj_matrix = ratings, users, items, adj_matrix
+        self.batch_size, self.seed, self.n_negatives, self.sample_by, self.exclude = int(batch_size), seed, K, sample_by, exclude
+        n_users = len(users)
+        self.n_items, self.item_base = len(items), n_users
+        r = np.asarray(ratings)
+        liked = r[:, 2] == 1
+        self.pos_csr = _user_lists(r[liked, 0], r[liked, 1], n_users)
+        self.excl_csr = self.pos_csr if exclude == 'positives' else _user_lists(r[:, 0], r[:, 1], n_users)
+        for ids in (self.pos_csr[1], self.excl_csr[1]):
+            if len(ids) and (ids.min() < self.item_base or ids.max() >= self.item_base + self.n_items):
+                raise ValueError("ratings hold item ids outside [{}, {})".format(self.item_base, self.item_base + self.n_items))
+        empty = np.flatnonzero(np.diff(self.pos_csr[0]) < 1)
+        if len(empty):
+            raise ValueError("user {} has no positive rating: every user needs one to be sampled".format(int(empty[0])))
+        full = np.flatnonzero(np.diff(self.excl_csr[0]) >= self.n_items)
+        if len(full):
+            raise ValueError("user {} has no candidate left: its exclusion list covers every item".format(int(full[0])))
+
+    def __len__(self):
+        return int(np.ceil(len(self.pos_csr[1]) / (self.batch_size // 2 // self.n_negatives)))
+
+    def __iter__(self):
+        return (self[b] for b in range(len(self)))
+
+    def __getitem__(self, idx):
+        if idx < 0 or idx >= len(self):
+            raise IndexError(idx)
+        return self.device_batch(idx)
+
+    def device_batch(self, step):
+        """The batch the device sampler draws at `step` (the batches of fit())."""
+        return bpr_triplet_device_batch(self.pos_csr, self.excl_csr, len(self.users), self.n_items, self.item_base, self.seed, step,
+                                        self.batch_size // 2, self.n_negatives, self.sample_by)
 
 
 # ---- the dropout draws, restated (csrc/amar_philox.h; include/amar_hip.h: amar_dropout_f32, amar_gat_layer_dropout_f32) -------------

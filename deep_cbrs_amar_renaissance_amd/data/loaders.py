@@ -14,7 +14,8 @@ import pandas as pd
 
 from deep_cbrs_amar_renaissance_amd.data import jsonstream
 from deep_cbrs_amar_renaissance_amd.data.datasets import UserItemEmbeddings, HybridUserItemEmbeddings
-from deep_cbrs_amar_renaissance_amd.data.datasets import UserItemGraph, UserItemGraphEmbeddings, UserItemGraphPosNegSample
+from deep_cbrs_amar_renaissance_amd.data.datasets import (UserItemGraph, UserItemGraphEmbeddings, UserItemGraphPosNegSample,
+                                                           UserItemGraphTriplets)
 from deep_cbrs_amar_renaissance_amd.data.preprocess import build_adjacency_matrix, get_user_properties
 
 
@@ -226,6 +227,33 @@ def load_user_item_graph_sample(
         sep=sep, return_adjacency=True, type_adjacency=type_adjacency,
         sparse_adjacency=sparse_adjacency, symmetric_adjacency=symmetric_adjacency)
     data_train = UserItemGraphPosNegSample(train_ratings, users, items, adj_matrix, batch_size=train_batch_size)
+    data_test = UserItemGraph(test_ratings, users, items, adj_matrix, batch_size=test_batch_size, shuffle=False)
+    return data_train, data_test
+
+
+def load_user_item_graph_triplets(
+        train_ratings_filepath,
+        test_ratings_filepath,
+        props_triples_filepath=None,
+        sep='\t',
+        type_adjacency='unary',
+        sparse_adjacency=True,
+        symmetric_adjacency=True,
+        train_batch_size=1024,
+        test_batch_size=2048,
+        n_negatives=1,
+        sample_by='user',
+        exclude='positives',
+        seed=42
+):
+    """BPR training on per-user triples (datasets.UserItemGraphTriplets): a triplet Sequence for training and an ordinary
+    UserItemGraph for test, both on the same adjacency object — the ordinary training graph of `type_adjacency`.  The training set
+    needs no dislikes: a user's negatives are drawn from what it has not liked (`exclude='positives'`) or not rated (`'rated'`)."""
+    (train_ratings, test_ratings), (users, items), adj_matrix = _graph_ratings(
+        train_ratings_filepath, test_ratings_filepath, props_triples_filepath, sep, type_adjacency,
+        sparse_adjacency, symmetric_adjacency, False)
+    data_train = UserItemGraphTriplets(train_ratings, users, items, adj_matrix, batch_size=train_batch_size, seed=seed,
+                                       n_negatives=n_negatives, sample_by=sample_by, exclude=exclude)
     data_test = UserItemGraph(test_ratings, users, items, adj_matrix, batch_size=test_batch_size, shuffle=False)
     return data_train, data_test
 

@@ -713,6 +713,58 @@ class DeviceSampler:
         capi.bpr_sample(self.pos_ptr, self.pos_ids, self.neg_ptr, self.neg_ids, self.n_users, self.seed, self.step, u, i, y)
 
 
+class TripletSampler:
+    """DeviceSampler's sibling for a UserItemGraphTriplets (amar_bpr_sample_triplets_i32): the positive and exclusion lists on the
+    device and the step counter of the draws.  Same surface (h, step, serial, matches, sample), same `serial` sequence, so a graph
+    captured for one Sequence never replays against another's lists, whichever kind either is."""
+
+    def __init__(self, sequence, device):
+        from deep_cbrs_amar_renaissance_amd.data.datasets import SAMPLE_BY
+        (pp, pi), (xp, xi) = sequence.pos_csr, sequence.excl_csr
+        n_users, n_items, base = len(sequence.users), int(sequence.n_items), int(sequence.item_base)
+        if n_users < 1 or n_items < 1:
+            raise ValueError("the triplet sampler needs at least one user and one item")
+        # the kernel reads without bounds checks: rows strictly ascending inside the item range, every user with a positive and
+        # with a candidate left
+        for ptr, ids, what in ((pp, pi, 'positive'), (xp, xi, 'exclusion')):
+            ptr, ids = np.asarray(ptr, dtype=np.int64), np.asarray(ids, dtype=np.int64)
+            if len(ptr) != n_users + 1 or ptr[0] != 0 or ptr[-1] != len(ids) or np.any(np.diff(ptr) < 0):
+                raise ValueError("the {} lists are no CSR over {} users".format(what, n_users))
+            if len(ids) and (ids.min() < base or ids.max() >= base + n_items):
+                raise ValueError("{} list holds ids outside the item range [{}, {})".format(what, base, base + n_items))
+            row = np.repeat(np.arange(n_users), np.diff(ptr))
+            if np.any((ids[1:] <= ids[:-1]) & (row[1:] == row[:-1])):
+                raise ValueError("every {} list must be strictly ascending".format(what))
+        if np.any(np.diff(np.asarray(pp, dtype=np.int64)) < 1):
+            raise ValueError("every user needs a non-empty positive list")
+        if np.any(np.diff(np.asarray(xp, dtype=np.int64)) >= n_items):
+            raise ValueError("an exclusion list covers every item: no candidate is left to draw")
+        self.h, self.n_negatives = int(sequence.batch_size) // 2, int(sequence.n_negatives)
+        if self.h < 1:
+            raise ValueError("a BPR batch needs batch_size >= 2")
+        if self.n_negatives < 1 or self.h % self.n_negatives:
+            raise ValueError("batch_size // 2 = {} triples do not split into draws of n_negatives = {}".format(self.h, self.n_negatives))
+        if sequence.sample_by not in SAMPLE_BY:
+            raise ValueError("sample_by must be 'user' or 'interaction' (got {!r})".format(sequence.sample_by))
+        self.mode = SAMPLE_BY[sequence.sample_by]
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)   # noqa: E731
+        self.pos_ptr, self.pos_ids, self.excl_ptr, self.excl_ids = up(pp), up(pi), up(xp), up(xi)
+        self.n_users, self.n_items, self.item_base, self.seed = n_users, n_items, base, int(sequence.seed)
+        self.step = torch.zeros(1, dtype=torch.int64, device=device)
+        self.serial = next(DeviceSampler._serials)
+        self.sequence, self.arrays = sequence, (pp, pi, xp, xi)
+        self.settings = (sequence.batch_size, sequence.n_negatives, sequence.sample_by, sequence.seed)
+
+    def matches(self, sequence):
+        return self.sequence is sequence and all(a is b for a, b in zip(self.arrays, (*sequence.pos_csr, *sequence.excl_csr))) \
+            and self.settings == (sequence.batch_size, sequence.n_negatives, sequence.sample_by, sequence.seed)
+
+    def sample(self, u, i, y):
+        """One batch of h triples into u [2h], i [2h], y [2h]; advances the step counter on the device."""
+        capi.bpr_sample_triplets(self.pos_ptr, self.pos_ids, self.excl_ptr, self.excl_ids, self.n_users, self.n_items, self.item_base,
+                                 self.seed, self.step, u, i, y, n_negatives=self.n_negatives, mode=self.mode)
+
+
 _ADAM_HYPER = dict(learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7)
 # rule -> (AMAR_OPT_* name in capi, Keras' constructor defaults)
 OPTIMIZER_RULES = {
@@ -1261,17 +1313,19 @@ class Trainer:
             self._eager_sampled, self._eager_batches = {}, {}
             self._loss_sum = torch.zeros((), dtype=torch.float32, device=dev)
 
-    # -- batches drawn on the device (BPR: data/datasets.py:UserItemGraphPosNegSample) -------------------------------------------
+    # -- batches drawn on the device (BPR: data/datasets.py:UserItemGraphPosNegSample, UserItemGraphTriplets) --------------------
     def sampler_for(self, sequence):
-        """The DeviceSampler of `sequence`, uploaded once.  Another Sequence (or new lists) gets a new one, and the graphs captured
-        for the old one are dropped with it."""
+        """The DeviceSampler (or, for a UserItemGraphTriplets, TripletSampler) of `sequence`, uploaded once.  Another Sequence (or new
+        lists) gets a new one, and the graphs captured for the old one are dropped with it."""
+        from deep_cbrs_amar_renaissance_amd.data.datasets import UserItemGraphTriplets
+        kind = TripletSampler if isinstance(sequence, UserItemGraphTriplets) else DeviceSampler
         sampler = getattr(self, '_sampler', None)
-        if sampler is None or not sampler.matches(sequence):
+        if sampler is None or type(sampler) is not kind or not sampler.matches(sequence):
             if hasattr(self, '_graphs'):
                 self._graphs = {k: v for k, v in self._graphs.items() if k[0] != 'sampled'}
                 self._seen = {k for k in self._seen if k[0] != 'sampled'}
                 self._eager_sampled = {}
-            sampler = self._sampler = DeviceSampler(sequence, self.device)
+            sampler = self._sampler = kind(sequence, self.device)
         return sampler
 
     def train_sampled(self, sampler, graph=True):
@@ -1812,8 +1866,8 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, validation_data
     # batch's users and items — gathered on the host from ONE table indexed by node id and uploaded every batch (6 MB at batch 1 024).
     # That table is registered once on the device instead and the batches are read as ids only: the same rows, gathered there
     # (AMAR_RESIDENT_BERT=0: the batches as they come).  A replayed hybrid batch at ml1m(s=1): 0.41 against 0.71 ms.
-    from deep_cbrs_amar_renaissance_amd.data.datasets import UserItemGraphPosNegSample
-    if isinstance(sequence, UserItemGraphPosNegSample):
+    from deep_cbrs_amar_renaissance_amd.data.datasets import UserItemGraphPosNegSample, UserItemGraphTriplets
+    if isinstance(sequence, (UserItemGraphPosNegSample, UserItemGraphTriplets)):
         if class_weight is not None:
             raise ValueError("class_weight cannot weigh BPR training: the batches are drawn on the device and have no per-pair label")
         return _fit_sampled(model, sequence, epochs, verbose, hp, val, initial_epoch)
@@ -1866,7 +1920,8 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, validation_data
 
 
 def _fit_sampled(model, sequence, epochs, verbose, hp, val=(None, None, 1, None), initial_epoch=0):
-    """fit() on the BPR sample Sequence: its lists go to the device once and every batch is drawn there (amar_bpr_sample_i32), inside
+    """fit() on a BPR sample Sequence (UserItemGraphPosNegSample or UserItemGraphTriplets): its lists go to the device once and every
+    batch is drawn there (amar_bpr_sample_i32 / amar_bpr_sample_triplets_i32), inside
     the replayed training graph (AMAR_TRAIN_GRAPH=0: the same steps eagerly, the same ids).  len(sequence) steps per epoch; the host
     stream of __getitem__ is not read."""
     if getattr(sequence, 'sample_weight', None) is not None:

@@ -1011,6 +1011,30 @@ int amar_bpr_sample_i32(const int32_t *pos_ptr, const int32_t *pos_ids, const in
                         int32_t n_users, uint64_t seed, uint64_t *step, int32_t advance, int32_t h,
                         int32_t *u, int32_t *items, float *y, amar_stream_t stream);
 
+/* ---- BPR triples (data/datasets.py:UserItemGraphTriplets): both items of a pair scored against the user they were drawn for --------
+ * amar_bpr_sample_triplets_i32  one batch of h triples (user, pos, neg) into u[2h], items[2h] and (y != NULL) y[2h] = [1]*h + [0]*h:
+ *                      u[t] = u[h + t] = user_t, items[t] = pos_t, items[h + t] = neg_t, so amar_bpr_grad_f32's pair (t, h + t) is one
+ *                      user's positive against its own negative.  K = n_negatives triples share a draw: P = h / K draws, triple
+ *                      t = j * K + k belongs to draw j.  Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), s = *step read from
+ *                      DEVICE memory, pick(w, n) = (uint64(w) * n) >> 32.
+ *                        draw j, counter (j, s & 0xffffffff, s >> 32, 0):
+ *                          mode 0 (by user)         user = pick(w0, n_users), pos = pos_ids[pos_ptr[user] + pick(w1, n_pos(user))]
+ *                          mode 1 (by interaction)  e = pick(w0, pos_ptr[n_users]), user = the largest r with pos_ptr[r] <= e (binary
+ *                                                   search), pos = pos_ids[e]
+ *                        triple t, counter (t, s & 0xffffffff, s >> 32, 1): with d the length of the user's exclusion row and
+ *                          e_q = excl_ids[excl_ptr[user] + q] - item_base:  r = pick(w0, n_items - d), m = #{q : e_q - q <= r} (e_q - q
+ *                          never decreases: one binary search), neg = item_base + r + m — the r-th item outside the row, exactly uniform
+ *                          over the complement, no rejection loop.
+ *                      advance != 0: *step = s + 1 after the batch.  CSR row pointers [n_users + 1], int32 node ids; exclusion rows
+ *                      strictly ascending, inside [item_base, item_base + n_items) and shorter than n_items, positive rows non-empty
+ *                      (the caller checks: the kernel reads without bounds checks).  One workgroup of 256 lanes.
+ *                      NULL pointer (y excepted), n_users / n_items / h / n_negatives < 1, h % n_negatives != 0, mode not 0 or 1:
+ *                      AMAR_EINVAL. */
+int amar_bpr_sample_triplets_i32(const int32_t *pos_ptr, const int32_t *pos_ids, const int32_t *excl_ptr, const int32_t *excl_ids,
+                                 int32_t n_users, int32_t n_items, int32_t item_base, int32_t n_negatives, int32_t mode, uint64_t seed,
+                                 uint64_t *step, int32_t advance, int32_t h, int32_t *u, int32_t *items, float *y,
+                                 amar_stream_t stream);
+
 /* ---- the compiled loss and the compiled metrics (Model.compile(loss=..., metrics=...)) -------------------------------------------
  * amar_loss_grad_f32   Keras 2's pointwise losses on ONE sigmoid output, in amar_bce_grad_f32's place and conventions: p is [B] or a
  *                      strided [B, 1] column (leading dimension ldp), y the 0/1 labels, loss_terms[i] the pair's term (their sum =
