@@ -231,7 +231,7 @@ def test_gradients_of_the_other_aggregators_on_a_directed_graph(hip, aggregate, 
 
 
 # ---- 4. the GAT reverse kernel alone ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('C', [4, 8, 16, 24, 32])
+@pytest.mark.parametrize('C', [4, 8, 16, 24, 32, 48, 64])
 @pytest.mark.parametrize('self_loop', [True, False])
 @pytest.mark.parametrize('rate', [None, 0.35])
 def test_gat_bwd_directed_kernel(hip, C, self_loop, rate):

@@ -176,7 +176,7 @@ def test_gat_layer_with_attention_dropout(hip, C, self_loop, shape):
     assert torch.equal(y0, y1)
 
 
-@pytest.mark.parametrize('C', [4, 16, 32, 64, 24, 48])
+@pytest.mark.parametrize('C', [4, 8, 16, 32, 64, 24, 48])
 @pytest.mark.parametrize('self_loop', [True, False])
 def test_gat_bwd_with_attention_dropout(hip, C, self_loop):
     """amar_gat_bwd_dropout_f32 against float64 autograd of the restated forward with the same masks: the bounds of
