@@ -141,6 +141,9 @@ SIGNATURES = {
     'amar_recommend_slices': (ctypes.c_int32, [_I64, _I32, _P, _I32, _I32]),
     'amar_recommend_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P,
                                           _I32, _I32, _P, _P, _P, _P, _P]),
+    'amar_nearest_slices': (ctypes.c_int32, [_I64, _I32, _I32, _I32]),
+    'amar_nearest_workspace_floats': (ctypes.c_int64, [_I64, _I32, _I32, _I32, _I32]),
+    'amar_nearest_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _P, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     'amar_rank_metrics_f64': (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P]),
 }
 
@@ -1415,6 +1418,52 @@ def recommend(Tu, Ti, wpack, dims, acts, in_act, k, users=None, excl_ptr=None, e
         _ptr(out_items) if m else None, _ptr(out_scores) if m else None, _stream())
     _check(code, 'amar_recommend_f32')
     return out_items, out_scores
+
+
+NEAREST_METRICS = {'dot': 0, 'cosine': 1}                              # include/amar_hip.h: AMAR_NEAREST_DOT / _COSINE
+NEAREST_MAX_D, NEAREST_MAX_K = 512, 64
+
+
+def nearest_supported(d, k):
+    """Whether amar_nearest_f32 takes vectors of width d and lists of length k."""
+    return d % 4 == 0 and 4 <= d <= NEAREST_MAX_D and 1 <= k <= NEAREST_MAX_K
+
+
+def nearest(Q, T, k, metric='cosine', query_rows=None, excl_ptr=None, excl_rows=None, n_slices=0):
+    """Fused dot / cosine top-k (amar_nearest_f32): for every listed query (row query_rows[j] of Q, all rows of Q when None) the k
+    best rows of T that are not in segment j of the exclusion CSR (excl_ptr [m + 1], excl_rows sorted per segment).  Returns
+    (rows int32 [m, k] (-1 padded), scores float32 [m, k] (-inf padded)).  n_slices <= 0: the library's automatic table slicing."""
+    if metric not in NEAREST_METRICS:
+        raise ValueError("nearest: metric must be one of {} (got {!r})".format(sorted(NEAREST_METRICS), metric))
+    n_q, d = int(Q.shape[0]), int(Q.shape[1])
+    n_rows = int(T.shape[0])
+    if int(T.shape[1]) != d:
+        raise ValueError("nearest: Q and T must have the same width")
+    m = int(query_rows.numel()) if query_rows is not None else n_q
+    if (excl_ptr is None) != (excl_rows is None):
+        raise ValueError("nearest: excl_ptr and excl_rows go together")
+    if excl_ptr is not None and excl_ptr.numel() != m + 1:
+        raise ValueError("nearest: excl_ptr must have one entry per listed query plus one")
+    lib = load()
+    code = NEAREST_METRICS[metric]
+    slices = lib.amar_nearest_slices(m, n_rows, d, int(n_slices))
+    if slices < 0:
+        _check(int(slices), 'amar_nearest_slices')
+    dev = Q.device
+    out_rows = torch.empty((m, k), dtype=torch.int32, device=dev)
+    out_scores = torch.empty((m, k), dtype=torch.float32, device=dev)
+    floats = lib.amar_nearest_workspace_floats(m, n_rows, int(k), code, int(slices))
+    if floats < 0:
+        _check(int(floats), 'amar_nearest_workspace_floats')
+    ws_s = torch.empty((floats,), dtype=torch.float32, device=dev) if floats else None
+    ws_r = torch.empty((m * slices * k,), dtype=torch.int32, device=dev) if slices > 1 else None
+    code = lib.amar_nearest_f32(
+        _ptr(Q, torch.float32, 'Q'), _ld(Q, 'Q'), n_q, _ptr(T, torch.float32, 'T'), _ld(T, 'T'), n_rows, d, code,
+        _ptr(query_rows, torch.int32, 'query_rows'), m, _ptr(excl_ptr, torch.int32, 'excl_ptr'),
+        _ptr_entries(excl_rows, torch.int32, 'excl_rows') if excl_rows is not None else None,
+        int(k), int(slices), _ptr(ws_r), _ptr(ws_s), _ptr(out_rows) if m else None, _ptr(out_scores) if m else None, _stream())
+    _check(code, 'amar_nearest_f32')
+    return out_rows, out_scores
 
 
 RANK_METRICS_MAX_KS, RANK_METRICS_MAX_BLOCKS = 8, 1024                 # include/amar_hip.h: AMAR_RANK_METRICS_MAX_KS / _MAX_BLOCKS

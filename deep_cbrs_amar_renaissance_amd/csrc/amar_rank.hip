@@ -19,6 +19,7 @@
 //     of a user in slice order (the order is a strict total order, so the result does not depend on the slicing).
 // The result of a user depends on its own Tu row, Ti and the weights only: not on the other users of the block or the call.
 #include "amar_common.h"
+#include "amar_rank_select.h"
 #include <stdlib.h>
 
 namespace {
@@ -27,9 +28,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RANK_MAX_LAYERS = 8;
 constexpr int RANK_WAVES = 4, RANK_UPW = 4, RANK_UB = RANK_WAVES * RANK_UPW;     // users per wave, per workgroup
-constexpr int RANK_CAND = 64;                                                    // candidate buffer entries per user
-constexpr int RANK_LIST = 64;                                                    // top-k list slots per user (k <= 64)
-constexpr int RANK_EMPTY = 0x7fffffff;                                           // item of an empty slot (loses every tie)
 constexpr int RANK_TILE_BYTES = 32 * 1024;
 
 struct RankArgs {
@@ -48,46 +46,6 @@ __device__ __forceinline__ float rank_act(float v, int act) {       // chain_act
     if (act == AMAR_ACT_RELU) return fmaxf(v, 0.f);
     if (act == AMAR_ACT_SIGMOID) return 1.f / (1.f + expf(-v));
     return v;
-}
-
-__device__ __forceinline__ bool rank_better(float s, int i, float ts, int ti) { return s > ts || (s == ts && i < ti); }
-
-// Merge n candidates (cs, ci) into the sorted list (ls, li) of k slots; one wave, every lane calls it.  Each entry's rank is the
-// number of entries that beat it (items are distinct inside a user, empty slots never reach a written rank).
-__device__ void rank_merge(float *ls, int *li, const float *cs, const int *ci, int n, int k, int lane) {
-    const float s0 = lane < k ? ls[lane] : -INFINITY;
-    const int i0 = lane < k ? li[lane] : RANK_EMPTY;
-    const float s1 = lane < n ? cs[lane] : -INFINITY;
-    const int i1 = lane < n ? ci[lane] : RANK_EMPTY;
-    int r0 = 0, r1 = 0;
-    for (int e = 0; e < k; ++e) {
-        const float s = ls[e];
-        const int i = li[e];
-        r0 += rank_better(s, i, s0, i0);
-        r1 += rank_better(s, i, s1, i1);
-    }
-    for (int e = 0; e < n; ++e) {
-        const float s = cs[e];
-        const int i = ci[e];
-        r0 += rank_better(s, i, s0, i0);
-        r1 += rank_better(s, i, s1, i1);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (lane < k) { ls[lane] = -INFINITY; li[lane] = RANK_EMPTY; }
-    if (i0 != RANK_EMPTY && r0 < k) { ls[r0] = s0; li[r0] = i0; }
-    if (i1 != RANK_EMPTY && r1 < k) { ls[r1] = s1; li[r1] = i1; }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// First position in [lo, hi) of the sorted list whose value is >= x.
-__device__ __forceinline__ int rank_lower_bound(const int32_t *v, int lo, int hi, int x) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (v[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 template <int MAXT, int PT>
@@ -283,33 +241,6 @@ __global__ __launch_bounds__(256) void recommend_kernel(const RankArgs a) {
                 a.out_scores[o] = s;
             }
         }
-    }
-}
-
-// Second launch with item slices: one wave per user merges its n_slices partial lists, slice by slice, into the final top-k.
-__global__ __launch_bounds__(256) void recommend_merge_kernel(const int32_t *__restrict__ part_items, const float *__restrict__ part_scores,
-                                                              int64_t m, int n_slices, int k, int32_t *__restrict__ out_items,
-                                                              float *__restrict__ out_scores) {
-    __shared__ float ls_all[4][RANK_LIST], cs_all[4][RANK_CAND];
-    __shared__ int li_all[4][RANK_LIST], ci_all[4][RANK_CAND];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t j = (int64_t)blockIdx.x * 4 + wave;
-    if (j >= m) return;
-    float *ls = ls_all[wave], *cs = cs_all[wave];
-    int *li = li_all[wave], *ci = ci_all[wave];
-    ls[lane] = -INFINITY; li[lane] = RANK_EMPTY;
-    for (int s = 0; s < n_slices; ++s) {
-        const int64_t o = (j * n_slices + s) * k;
-        cs[lane] = lane < k ? part_scores[o + lane] : -INFINITY;
-        ci[lane] = lane < k ? part_items[o + lane] : RANK_EMPTY;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        rank_merge(ls, li, cs, ci, k, k, lane);
-    }
-    if (lane < k) {
-        const int i = li[lane];
-        out_items[j * k + lane] = i == RANK_EMPTY ? -1 : i;
-        out_scores[j * k + lane] = i == RANK_EMPTY ? -INFINITY : ls[lane];
     }
 }
 

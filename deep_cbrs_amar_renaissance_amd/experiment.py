@@ -379,6 +379,8 @@ class Experimenter:
         metrics = pd.DataFrame([precision_at, recall_at, f1_at], index=['precision_at', 'recall_at', 'f1_at'])
         if self.config.parameters.get('full_ranking_ks'):
             self.evaluate_full_ranking([int(k) for k in self.config.parameters.get('full_ranking_ks')])
+        if self.config.parameters.get('similar_items'):
+            self.write_similar_items(**dict(self.config.parameters.get('similar_items')))
         self.logger.info('\n' + str(metrics))
         print('\n' + str(metrics))
         return metrics
@@ -399,6 +401,18 @@ class Experimenter:
         self.run_log.log_metrics({'full_ranking_users_evaluated': full['users_evaluated'],
                                   'full_ranking_users_skipped': full['users_skipped']})
         return full
+
+    def write_similar_items(self, k=10, metric='cosine', space=None):
+        """Opt-in (parameters.similar_items: {k, metric, space}): every item's k most similar items in the trained model's `space`
+        (`similar_items()`), written as <predictions_dest>/similar_items_<k>.tsv (item, neighbour, score; original ids)."""
+        items, neighbours, scores = self.model.similar_items(self.trainset, k=int(k), metric=metric, space=space)
+        n_users, item_ids = len(self.trainset.users), self.trainset.items
+        # recommendations_frame names its first column through the ids it is given: here the items' own, for both columns
+        frame = recommendations_frame(items - n_users, np.where(neighbours >= 0, neighbours - n_users + len(item_ids), -1), scores,
+                                      item_ids, item_ids)
+        path = path_join(self.predictions_dest, "similar_items_{}.tsv".format(int(k)))
+        frame.to_csv(path, sep='\t', header=False, index=False)
+        return path
 
     def run(self):
         self.train()

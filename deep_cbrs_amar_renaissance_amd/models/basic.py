@@ -26,7 +26,7 @@ from deep_cbrs_amar_renaissance_amd.models.tsgnn import TwoStepGCN, TwoStepGraph
 from deep_cbrs_amar_renaissance_amd.models.twgnn import TwoWayGCN, TwoWayGraphSage, TwoWayGAT, TwoWayLightGCN, TwoWayDGCF
 
 
-class BasicRS(Model):
+class BasicRS(rec.SimilarSearch, Model):
     def __init__(
             self,
             dense_units=(512, 256, 128),
@@ -201,6 +201,15 @@ class BasicRS(Model):
             self.build_head(table.shape[1], table.shape[1])
         return table[:n_users], table[n_users:n_users + n_items]
 
+    # -- similarity search (recommend.py:SimilarSearch) ---------------------------------------------------------------
+    def _embedding_spaces(self):
+        return ('tower',)
+
+    def _embedding_tables(self, trainset, space):
+        """'tower': unet / inet once per entity — the plain stacks, not the split form that folds the classifier's first layer in."""
+        u_table, i_table = self._recommend_tables(trainset)
+        return self.unet.apply2(u_table), self.inet.apply2(i_table)
+
     def _rank_plan(self):
         """The rest of the classifier packed for amar_recommend_f32 when the towers themselves are too wide for the split plan
         (basic-kge: 512 -> 256 -> 128): classifier c1 -> ... -> 1 with c1 and every hidden width <= 128, c1 % 4 == 0; else None."""
@@ -302,7 +311,7 @@ class PairPlan:
             raise ValueError("this PairPlan was prepared for another pair list")
 
 
-class BasicGNN(Model, abc.ABC):
+class BasicGNN(rec.SimilarSearch, Model, abc.ABC):
     def __init__(
             self,
             dense_units=(32, 16),
@@ -378,6 +387,17 @@ class BasicGNN(Model, abc.ABC):
         finally:
             self.gnn.hoist, self.gnn._hoisted, self._towers = saved
         return emb[:n_users], emb[n_users:n_users + n_items]
+
+    # -- similarity search (recommend.py:SimilarSearch) ---------------------------------------------------------------
+    def _embedding_spaces(self):
+        return ('graph', 'tower')
+
+    def _embedding_tables(self, trainset, space):
+        """'graph': the user / item rows of one propagation; 'tower': rs.unet / rs.inet over them, once per entity."""
+        emb_u, emb_i = self._recommend_tables(trainset)
+        if space == 'graph':
+            return emb_u, emb_i
+        return self.rs.unet.apply2(emb_u), self.rs.inet.apply2(emb_i)
 
     def _hoist_begin(self, hoist):
         self.gnn.hoist = bool(hoist)

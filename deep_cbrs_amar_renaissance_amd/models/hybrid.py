@@ -33,7 +33,7 @@ from deep_cbrs_amar_renaissance_amd.models.tsgnn import TwoStepGCN, TwoStepGraph
 from deep_cbrs_amar_renaissance_amd.models.twgnn import TwoWayGCN, TwoWayGraphSage, TwoWayGAT, TwoWayLightGCN, TwoWayDGCF
 
 
-class HybridCBRS(Model):
+class HybridCBRS(rec.SimilarSearch, Model):
     """Hybrid recommender system that receives inputs from two sources."""
 
     def __init__(
@@ -290,6 +290,22 @@ class HybridCBRS(Model):
             self.build_head(g.shape[1], b.shape[1])
         return self.towers(g[:n_users], g[n_users:n_users + n_items], b[:n_users], b[n_users:n_users + n_items])
 
+    # -- similarity search (recommend.py:SimilarSearch) ---------------------------------------------------------------
+    def _embedding_spaces(self):
+        return ('tower',)
+
+    def _first_stage(self, ug, ig, ub, ib):
+        """[dense1a(g) || dense2a(b)] per user, [dense1b(g) || dense2b(b)] per item: the plain first-stage outputs, nothing folded in."""
+        return (torch.cat([self.dense1a.apply2(ug), self.dense2a.apply2(ub)], dim=1),
+                torch.cat([self.dense1b.apply2(ig), self.dense2b.apply2(ib)], dim=1))
+
+    def _embedding_tables(self, trainset, space):
+        n_users, n_items = len(trainset.users), len(trainset.items)
+        g, b = to_device_tensor(trainset.graph_embeddings), to_device_tensor(trainset.bert_embeddings)
+        if not self.built:
+            self.build_head(g.shape[1], b.shape[1])
+        return self._first_stage(g[:n_users], g[n_users:n_users + n_items], b[:n_users], b[n_users:n_users + n_items])
+
     @staticmethod
     def _rows(table, ids, base):
         if ids is None:
@@ -310,7 +326,7 @@ class HybridCBRS(Model):
         return self.clf.apply2(s)
 
 
-class HybridBertGNN(Model, abc.ABC):
+class HybridBertGNN(rec.SimilarSearch, Model, abc.ABC):
     def __init__(
             self,
             dense_units=(32, 16),
@@ -428,6 +444,33 @@ class HybridBertGNN(Model, abc.ABC):
             return self.rs.towers(emb[:n_users], emb[n_users:n_users + n_items], bert[:n_users], bert[n_users:n_users + n_items])
         finally:
             self.gnn.hoist, self.gnn._hoisted, self._towers = saved
+
+    # -- similarity search (recommend.py:SimilarSearch) ---------------------------------------------------------------
+    def _embedding_spaces(self):
+        return ('graph', 'tower')
+
+    def _embedding_tables(self, trainset, space):
+        """'graph': the user / item rows of one propagation (the model's hoist state is left as it was found); 'tower': the
+        first-stage networks over them and the registered BERT table, which is needed exactly as recommend() needs it."""
+        n_users, n_items = len(trainset.users), len(trainset.items)
+        bert = None
+        if space == 'tower':
+            self.resident_ids(trainset)
+            if self.bert_table is None:
+                raise ValueError("recommend() needs the BERT table: register it with set_bert_table() or pass the hybrid training Sequence")
+            bert = self.bert_table
+        saved = (self.gnn.hoist, getattr(self.gnn, '_hoisted', None), self._towers)
+        self.gnn.hoist = True
+        try:
+            emb = self.gnn(None)
+        finally:
+            self.gnn.hoist, self.gnn._hoisted, self._towers = saved
+        emb_u, emb_i = emb[:n_users], emb[n_users:n_users + n_items]
+        if space == 'graph':
+            return emb_u, emb_i
+        if not self.rs.built:
+            self.rs.build_head(emb.shape[1], bert.shape[1])
+        return self.rs._first_stage(emb_u, emb_i, bert[:n_users], bert[n_users:n_users + n_items])
 
     def _hoist_begin(self, hoist):
         self.gnn.hoist = bool(hoist)

@@ -19,6 +19,10 @@ fewer than k unexcluded items padded with -1 / -inf.
 Inside ``device_lists()`` both routes stop before that conversion and return ``(users int64 [m] on the host, items int32 [m, k] item
 ROWS on the device, scores float32 [m, k] on the device)``: ``evaluate_ranking`` scores the lists where they are
 (``amar_rank_metrics_f64``), which is what lets ``fit(validation_ranking=...)`` validate every epoch.
+
+The second half of the module is similarity search over the vectors the models learn: ``nearest`` (one ``amar_nearest_f32`` call, dot
+or cosine, nothing of size m x n in memory) and ``SimilarSearch``, the mixin that gives every scoring model ``user_embeddings`` /
+``item_embeddings``, ``similar_items``, ``similar_users`` and ``recommend_like``.
 """
 import contextlib
 import weakref
@@ -194,3 +198,202 @@ def pairs(score_fn, trainset, k, users, exclude_seen, device=None):
         out_i.append(items)
         out_s.append(sc)
     return _finish(u, torch.cat(out_i), torch.cat(out_s), n_users)
+
+
+# -- similarity search (amar_nearest_f32): "which rows of this table are like these vectors?" ---------------------------------------
+METRICS = ('dot', 'cosine')
+
+
+def check_metric(metric):
+    if metric not in METRICS:
+        raise ValueError("metric must be one of {} (got {!r})".format(METRICS, metric))
+    return metric
+
+
+def check_width(d, what='vectors'):
+    """The widths amar_nearest_f32 takes: d % 4 == 0, 4 <= d <= 512."""
+    if not capi.nearest_supported(int(d), 1):
+        raise NotImplementedError("similarity search takes widths that are multiples of 4 in [4, {}]: the {} are {} wide".format(
+            capi.NEAREST_MAX_D, what, int(d)))
+    return int(d)
+
+
+def lists_csr(lists, n_rows, what='exclude'):
+    """Per-query row lists as the exclusion CSR of amar_nearest_f32: (ptr int32 [m+1], rows int32), every segment sorted ascending and
+    de-duplicated, values checked against 0..n_rows-1."""
+    ptr = np.zeros(len(lists) + 1, dtype=np.int64)
+    segs = []
+    for j, l in enumerate(lists):
+        a = np.unique(np.asarray(l, dtype=np.int64).reshape(-1)) if len(l) else np.zeros(0, dtype=np.int64)
+        if a.size and (a[0] < 0 or a[-1] >= n_rows):
+            raise ValueError("{}: rows must lie in [0, {}) (got {}..{})".format(what, n_rows, int(a[0]), int(a[-1])))
+        segs.append(a)
+        ptr[j + 1] = ptr[j] + a.size
+    rows = np.concatenate(segs) if segs else np.zeros(0, dtype=np.int64)
+    return ptr.astype(np.int32), rows.astype(np.int32)
+
+
+def _as_device_matrix(x, dev, name):
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32))
+    if t.dim() != 2:
+        raise ValueError("{} must be a 2-D [n, d] array".format(name))
+    t = t.to(device=dev, dtype=torch.float32)
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        t = t.contiguous()
+    if t.stride(0) % 4 or t.data_ptr() % 16:                # the kernel reads float4s: rows on 16-byte boundaries
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
+def nearest(queries, table, k=10, metric='cosine', exclude=None, query_rows=None):
+    """The k rows of `table` [n, d] most similar to every query vector of `queries` [m, d] (host or device arrays) under `metric`
+    ('cosine' or 'dot'; a zero vector scores 0 under cosine).  `exclude`: one sequence of table rows per query that must not be
+    returned, or an (excl_ptr, excl_rows) CSR already on the device.  `query_rows`: int32 device rows of `queries` to search for
+    (all rows by default).  Returns (rows int64 [m, k] (-1 padded), scores float32 [m, k] (-inf padded)) on the host, ordered by
+    score descending then row ascending; inside ``device_lists()`` the device tensors (rows int32)."""
+    k = check_k(k)
+    check_metric(metric)
+    dev = table.device if isinstance(table, torch.Tensor) and table.is_cuda else (
+        queries.device if isinstance(queries, torch.Tensor) and queries.is_cuda else default_device())
+    q, t = _as_device_matrix(queries, dev, 'queries'), _as_device_matrix(table, dev, 'table')
+    if q.shape[1] != t.shape[1]:
+        raise ValueError("queries are {} wide, the table {}".format(q.shape[1], t.shape[1]))
+    check_width(t.shape[1])
+    m = int(query_rows.numel()) if query_rows is not None else int(q.shape[0])
+    ptr = rows = None
+    if exclude is not None:
+        if isinstance(exclude, tuple) and len(exclude) == 2 and isinstance(exclude[0], torch.Tensor):
+            ptr, rows = exclude
+        else:
+            if len(exclude) != m:
+                raise ValueError("exclude must hold one list per query ({} lists for {} queries)".format(len(exclude), m))
+            p, r = lists_csr(exclude, int(t.shape[0]))
+            ptr, rows = torch.from_numpy(p).to(dev), torch.from_numpy(r).to(dev)
+    out_rows, out_scores = capi.nearest(q, t, k, metric=metric, query_rows=query_rows, excl_ptr=ptr, excl_rows=rows)
+    if _ON_DEVICE:
+        return out_rows, out_scores
+    return out_rows.cpu().numpy().astype(np.int64), out_scores.cpu().numpy().astype(np.float32)
+
+
+def check_ids(ids, lo, hi, what):
+    """Host int64 node ids in [lo, hi) (all of them when None), in the caller's order."""
+    if ids is None:
+        return np.arange(lo, hi, dtype=np.int64)
+    a = ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+    a = a.reshape(-1)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("{} must be integer node ids".format(what))
+    a = a.astype(np.int64)
+    if a.size and (a.min() < lo or a.max() >= hi):
+        raise ValueError("{} must lie in [{}, {}) (got {}..{})".format(what, lo, hi, int(a.min()), int(a.max())))
+    return a
+
+
+def similar_rows(table, rows, k, metric, exclude_self, base):
+    """`nearest` of rows `rows` (host int64) of a device table against the table itself; neighbours come back as node ids (+ base)."""
+    k = check_k(k)
+    check_metric(metric)
+    if len(rows) == 0:
+        return (np.zeros((0, k), dtype=np.int64), np.zeros((0, k), dtype=np.float32)) if not _ON_DEVICE else (
+            torch.zeros((0, k), dtype=torch.int32, device=table.device), torch.zeros((0, k), dtype=torch.float32, device=table.device))
+    dev = table.device
+    q_rows = torch.from_numpy(rows.astype(np.int32)).to(dev)
+    excl = None
+    if exclude_self:                                         # segment j = {rows[j]}
+        excl = (torch.arange(len(rows) + 1, dtype=torch.int32, device=dev), q_rows)
+    nb, sc = nearest(table, table, k, metric, exclude=excl, query_rows=q_rows)
+    if _ON_DEVICE:
+        return nb, sc
+    return np.where(nb >= 0, nb + base, -1), sc
+
+
+def profile_queries(table, liked_rows):
+    """Float32 mean of the liked rows of every profile, on the device: [m, d].  liked_rows: list of host int64 row arrays, none empty."""
+    dev = table.device
+    sizes = np.array([len(l) for l in liked_rows], dtype=np.int64)
+    # profiles padded to the longest one and summed along the padding (no atomics: the same bits on every run)
+    idx = np.zeros((len(liked_rows), int(sizes.max())), dtype=np.int64)
+    for j, l in enumerate(liked_rows):
+        idx[j, :len(l)] = l
+    keep = torch.from_numpy((np.arange(idx.shape[1])[None, :] < sizes[:, None]).astype(np.float32)).to(dev)
+    rows = table.to(torch.float32)[torch.from_numpy(idx).to(dev)] * keep[:, :, None]
+    return rows.sum(1) / torch.from_numpy(sizes.astype(np.float32)).to(dev)[:, None]
+
+
+class SimilarSearch:
+    """Embedding accessors and similarity search shared by the scoring models.  A model names its spaces (`_embedding_spaces`:
+    'graph' = the propagated, reduced node table, 'tower' = the first-stage Dense outputs per entity; the first one is the default)
+    and returns the device tables of one (`_embedding_tables(trainset, space)` -> (users [|U|, d], items [|I|, d]))."""
+
+    def _embedding_spaces(self):
+        raise NotImplementedError
+
+    def _embedding_tables(self, trainset, space):
+        raise NotImplementedError
+
+    def _resolve_space(self, space):
+        spaces = tuple(self._embedding_spaces())
+        if space is None:
+            return spaces[0]
+        if space not in spaces:
+            raise ValueError("{} has no {!r} embedding space: it has {}".format(type(self).__name__, space, list(spaces)))
+        return space
+
+    def _entity_table(self, trainset, space, side):
+        return self._embedding_tables(trainset, self._resolve_space(space))[side]
+
+    def _user_embeddings(self, trainset, space=None):
+        return self._entity_table(trainset, space, 0)
+
+    def _item_embeddings(self, trainset, space=None):
+        return self._entity_table(trainset, space, 1)
+
+    def user_embeddings(self, trainset, space=None):
+        """The learned user vectors, float32 [|U|, d]: space 'graph' (the propagated node table's user rows) or 'tower' (the output
+        of the user's first-stage Dense network(s)); None = 'graph' where the model has a GNN, else 'tower'."""
+        return self._user_embeddings(trainset, space).cpu().numpy().astype(np.float32)
+
+    def item_embeddings(self, trainset, space=None):
+        """The learned item vectors, float32 [|I|, d] (row r = item node |U| + r); spaces as in `user_embeddings`."""
+        return self._item_embeddings(trainset, space).cpu().numpy().astype(np.float32)
+
+    def similar_items(self, trainset, items=None, k=10, metric='cosine', space=None, exclude_self=True):
+        """The k items most similar to every item of `items` (node ids |U|..|U|+|I|-1, all items by default, in the caller's order)
+        in the model's `space`.  Returns (items int64 [m], neighbours int64 [m, k] (node ids, -1 padded), scores float32 [m, k]
+        (-inf padded)): score descending, node id ascending on ties.  One amar_nearest_f32 call: no |I| x |I| matrix."""
+        check_k(k)
+        check_metric(metric)
+        n_users, n_items = _sizes(trainset)
+        ids = check_ids(items, n_users, n_users + n_items, 'items')
+        nb, sc = similar_rows(self._item_embeddings(trainset, space), ids - n_users, k, metric, exclude_self, n_users)
+        return ids, nb, sc
+
+    def similar_users(self, trainset, users=None, k=10, metric='cosine', space=None, exclude_self=True):
+        """`similar_items` over the user rows: ids 0..|U|-1."""
+        check_k(k)
+        check_metric(metric)
+        n_users, _ = _sizes(trainset)
+        ids = check_ids(users, 0, n_users, 'users')
+        nb, sc = similar_rows(self._user_embeddings(trainset, space), ids, k, metric, exclude_self, 0)
+        return ids, nb, sc
+
+    def recommend_like(self, trainset, liked, k=10, metric='cosine', space=None, exclude_liked=True):
+        """The k items most similar to each PROFILE of `liked` (a list of lists of item node ids — a user given only by what they
+        liked, with no row in the graph): the query is the float32 mean of the liked items' vectors.  The profile's own items are
+        left out unless exclude_liked=False.  Returns (neighbours int64 [m, k] (node ids, -1 padded), scores float32 [m, k])."""
+        k = check_k(k)
+        check_metric(metric)
+        n_users, n_items = _sizes(trainset)
+        rows = []
+        for j, profile in enumerate(liked):
+            ids = check_ids(profile, n_users, n_users + n_items, 'liked items')
+            if ids.size == 0:
+                raise ValueError("profile {} is empty: recommend_like needs at least one liked item per profile".format(j))
+            rows.append(ids - n_users)
+        if not rows:
+            return np.zeros((0, k), dtype=np.int64), np.zeros((0, k), dtype=np.float32)
+        table = self._item_embeddings(trainset, space)
+        nb, sc = nearest(profile_queries(table, rows), table, k, metric, exclude=rows if exclude_liked else None)
+        if _ON_DEVICE:
+            return nb, sc
+        return np.where(nb >= 0, nb + n_users, -1), sc

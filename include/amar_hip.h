@@ -1186,6 +1186,36 @@ int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const floa
                        int32_t k, int32_t n_slices, int32_t *workspace_items, float *workspace_scores,
                        int32_t *out_items, float *out_scores, amar_stream_t stream);
 
+/* Nearest rows of a table under dot or cosine similarity, fused score-and-select ("which items are like this one?").
+ * Listed query j is row Q[query_rows[j]] (row j itself when query_rows == NULL, m == n_queries).  For every listed query and EVERY
+ * row i of T[n_rows, d] that is not in the query's exclusion segment,
+ *     AMAR_NEAREST_DOT:     score(j, i) = sum_c Q[q, c] * T[i, c]
+ *     AMAR_NEAREST_COSINE:  score(j, i) = (dot * inv_norm(Q[q])) * inv_norm(T[i]),  inv_norm(x) = 1/sqrt(sum x^2), 0 when the sum is 0
+ * (a zero row scores 0 against everything, never NaN), and the k best (score descending, table row ascending on ties) are written
+ * to out_rows / out_scores [m, k], padded with -1 / -inf when fewer than k rows remain.  Nothing of size m x n_rows is written.
+ * Exclusion CSR (optional, both NULL = rank every row) over the LISTED queries: excl_ptr[m+1], segment j belongs to listed query j
+ * (not to its row in Q); each segment sorted ascending and de-duplicated, values in 0..n_rows-1.  Self-exclusion, profile items
+ * and filters are all expressed through it.  PRECONDITION: every query_rows[j] < n_queries (not checked on the device).
+ * Products run on v_mfma_f32_16x16x4_f32 (f32 in, f32 accumulate: one fmaf chain per score, features in the fragment order
+ * 16t + 4g + r of amar_recommend_f32: t ascending, r ascending inside t); the inverse norms are computed once per table row and
+ * once per listed query in a pre-pass.  A query's result depends on its own row, T, the metric and its exclusion segment only:
+ * not on the other queries of the call, the grid or the slicing; a call returns the same bits on every run (no float atomics).
+ * Limits: d % 4 == 0, 4 <= d <= 512, k <= 64, ldq / ldt multiples of 4 (they may exceed d), Q and T 16-byte aligned; else
+ * AMAR_EUNSUPPORTED.  NULL Q / T, negative sizes, k < 1, an unknown metric, ldq or ldt < d, excl_ptr without excl_rows, a missing
+ * workspace: AMAR_EINVAL.  All of these are checked before any device call.
+ * n_slices: table slices per query block (<= 0: automatic).  amar_nearest_slices returns the count a call will launch (a call that
+ * passes n_slices > 0 must pass that count).  workspace_scores holds amar_nearest_workspace_floats(m, n_rows, k, metric, slices)
+ * floats, 16-byte aligned (the inverse norms for cosine, then the per-slice scores; may be NULL when that is 0), workspace_rows
+ * m * slices * k entries when slices > 1 (else it may be NULL); any contents.  With slices a second launch merges them. */
+#define AMAR_NEAREST_DOT    0
+#define AMAR_NEAREST_COSINE 1
+int32_t amar_nearest_slices(int64_t m, int32_t n_rows, int32_t d, int32_t n_slices);
+int64_t amar_nearest_workspace_floats(int64_t m, int32_t n_rows, int32_t k, int32_t metric, int32_t slices);
+int amar_nearest_f32(const float *Q, int64_t ldq, int32_t n_queries, const float *T, int64_t ldt, int32_t n_rows, int32_t d,
+                     int32_t metric, const int32_t *query_rows, int64_t m, const int32_t *excl_ptr, const int32_t *excl_rows,
+                     int32_t k, int32_t n_slices, int32_t *workspace_rows, float *workspace_scores,
+                     int32_t *out_rows, float *out_scores, amar_stream_t stream);
+
 /* Full-ranking metrics of top-K lists that are already on the device (utilities/metrics.py:full_ranking_metrics, restated):
  * lists [m, K] holds item ROWS best first, padded with -1 (what amar_recommend_f32 / amar_topk_segmented_f32 write); row j
  * belongs to user users[j] (j itself when users == NULL, m == n_users).  The relevant items are a CSR over users:
