@@ -68,6 +68,7 @@ SIGNATURES = {
     'amar_dual_chain_indexed_f32': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _I64, _P, _I64, _P]),
     'amar_copy_columns_f32': (ctypes.c_int, [_P, _I64, _P, _I32, _P, _I64, _I64, _I32, _P]),
     'amar_scatter_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _I32, _P]),
+    'amar_scatter_closed_f32': (ctypes.c_int, [_P, _P, _P, _I64, _P, _I32, _I32, _P]),
     'amar_reduce_layers_f32': (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _I64, _I64, _I32, _P]),
     'amar_reduce_layers_wsum_f32': (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _P, _I64, _I64, _P]),
     'amar_reduce_layers_wsum_bwd_scratch': (ctypes.c_int64, []),
@@ -1016,15 +1017,37 @@ def dual_chain(tables_a, tables_b, ids_a, ids_b, bases_a, bases_b, D, in_act, br
     _check(code, 'amar_dual_chain_f32' if out_index is None else 'amar_dual_chain_indexed_f32')
 
 
-def scatter(src, index, dst, window_off=None, n_windows=1):
-    """dst[index[t]] = src[t] (rows of a [n, 1] / [n] float32 destination), window by window: see amar_scatter_f32."""
+SCATTER_CLOSED_MAX_WINDOW = 65536      # include/amar_hip.h: AMAR_SCATTER_CLOSED_MAX_WINDOW
+
+
+def scatter_route(n, ldd, max_window, closed):
+    """Which form `scatter` takes: 'lds' (amar_scatter_closed_f32: every window finished on chip, whole-line stores) or 'global'
+    (amar_scatter_f32: one store per score).  Host only.  'lds' needs the caller's promise (`closed`: every window's indices are a
+    bijection onto the window's own range), a dense destination (ldd == 1), something to move, and no window longer than
+    SCATTER_CLOSED_MAX_WINDOW (`max_window`: the longest window, known on the host); AMAR_PAIR_SCATTER=global keeps the global form."""
+    if os.environ.get('AMAR_PAIR_SCATTER', '') == 'global':
+        return 'global'
+    if not closed or int(ldd) != 1 or int(n) <= 0 or max_window is None or not 1 <= int(max_window) <= SCATTER_CLOSED_MAX_WINDOW:
+        return 'global'
+    return 'lds'
+
+
+def scatter(src, index, dst, window_off=None, n_windows=1, closed=False, max_window=None):
+    """dst[index[t]] = src[t] (rows of a [n, 1] / [n] float32 destination), window by window: see amar_scatter_f32.  closed=True with
+    max_window (the longest window): the caller's promise of amar_scatter_closed_f32, taken where scatter_route says 'lds'."""
     n = int(index.numel())
     if src.numel() < n or (window_off is not None and window_off.numel() != n_windows + 1):
         raise ValueError("scatter: one source value per index and n_windows + 1 window offsets expected")
     if n == 0:
         return
+    ldd = _ld(dst, 'dst') if dst.dim() == 2 else 1
+    if window_off is not None and scatter_route(n, ldd, max_window, closed) == 'lds':
+        _check(load().amar_scatter_closed_f32(_ptr(src, torch.float32, 'src'), _ptr(index, torch.int32, 'index'), _ptr(dst, torch.float32, 'dst'),
+                                              n, _ptr(window_off, torch.int32, 'window_off'), int(n_windows), int(max_window), _stream()),
+               'amar_scatter_closed_f32')
+        return
     _check(load().amar_scatter_f32(_ptr(src, torch.float32, 'src'), _ptr(index, torch.int32, 'index'), _ptr(dst, torch.float32, 'dst'),
-                                   _ld(dst, 'dst') if dst.dim() == 2 else 1, n, _ptr(window_off, torch.int32, 'window_off'),
+                                   ldd, n, _ptr(window_off, torch.int32, 'window_off'),
                                    int(n_windows), _stream()), 'amar_scatter_f32')
 
 

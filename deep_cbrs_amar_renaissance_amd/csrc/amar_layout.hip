@@ -117,10 +117,73 @@ unsigned grid_for(int64_t total) {
 // window's lines of dst are completed inside one L2 and written back whole — 12 M single-word stores at random over 48 MB are each
 // a line fetched and written back (0.15 ms as a pass of its own, 0.19 ms inside the pair stage).  Workgroup b works through the
 // windows w = b % 8, b % 8 + 8, ... with the other workgroups of equal b % 8 (one XCD under round-robin placement: speed only).
-__global__ __launch_bounds__(256) void scatter_windows_kernel(const float *__restrict__ src, const int32_t *__restrict__ index,
-                                                              float *__restrict__ dst, int64_t ldd, int64_t n,
-                                                              const int32_t *__restrict__ window_off, int n_windows, int per_xcd) {
+// Every lane's store is still a transaction of its own there (12 M of them: one per ~3 cycles and CU, far from any byte limit).
+//
+// CLOSED (amar_scatter_closed_f32): the caller promises that window w's indices are a bijection onto [window_off[w],
+// window_off[w + 1]) itself, so the window is finished ON CHIP: `per_xcd` (here: the parts a window is cut into) workgroups per
+// window, each owning one contiguous piece of the window's destinations of at most `cap` floats.  A workgroup streams the whole
+// window's (index, value) pairs in 16-byte loads, keeps the values of its own piece in LDS at their final offset, and after the
+// barrier (a data dependency: no wave may flush before every wave has placed its values) writes the piece to dst in whole
+// 16-byte stores, a scalar head and tail where dst + lo is not 16-byte aligned.  An index outside the piece is dropped and the
+// window table is clamped to [0, n], so a broken promise gives wrong scores, never a store outside the window.
+constexpr int SCATTER_CLOSED_THREADS = 1024;
+constexpr int SCATTER_CLOSED_PIECE = 32768;                  // floats of LDS a workgroup fills (128 KB), + 4 for the alignment shift
+
+template <bool CLOSED>
+__global__ __launch_bounds__(CLOSED ? SCATTER_CLOSED_THREADS : 256) void scatter_windows_kernel(
+    const float *__restrict__ src, const int32_t *__restrict__ index, float *__restrict__ dst, int64_t ldd, int64_t n,
+    const int32_t *__restrict__ window_off, int n_windows, int per_xcd, int cap) {
     const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
+    if constexpr (CLOSED) {
+        extern __shared__ float piece[];
+        const int parts = per_xcd, w = (j / parts) * 8 + x, part = j % parts;      // the parts of a window: neighbours on one XCD
+        if (w >= n_windows) return;
+        const int nn = (int)n;
+        const int lo = min(max(window_off[w], 0), nn), hi = min(max(window_off[w + 1], lo), nn), len = hi - lo;
+        const int plen = (len + parts - 1) / parts, dlo = lo + part * plen;
+        const int dn = min(min(plen, hi - dlo), cap);                               // this workgroup's destinations: [dlo, dlo + dn)
+        if (dn <= 0) return;                                                        // (uniform over the workgroup: before any barrier)
+        const int a = (int)((reinterpret_cast<uintptr_t>(dst + dlo) >> 2) & 3);     // dst + dlo - a is 16-byte aligned
+        const int tid = threadIdx.x, T = blockDim.x;
+        auto keep = [&](int32_t i, float v) {
+            const unsigned k = (unsigned)(i - dlo);
+            if (k < (unsigned)dn) piece[a + k] = v;
+        };
+        // the window's pairs: scalar up to the first 16-byte boundary of index + lo, quads, scalar rest; all scalar where src + lo
+        // and index + lo are not aligned alike
+        const int mis = (int)((reinterpret_cast<uintptr_t>(index + lo) >> 2) & 3);
+        const bool alike = mis == (int)((reinterpret_cast<uintptr_t>(src + lo) >> 2) & 3);
+        const int head = alike ? min(len, (4 - mis) & 3) : len, nq = (len - head) >> 2;
+        const int4 *iq = reinterpret_cast<const int4 *>(index + lo + head);
+        const float4 *vq = reinterpret_cast<const float4 *>(src + lo + head);
+        int q = tid;
+        for (; q + 3 * T < nq; q += 4 * T) {                  // four independent 16-byte loads of each stream in flight per lane
+            const int4 i0 = iq[q], i1 = iq[q + T], i2 = iq[q + 2 * T], i3 = iq[q + 3 * T];
+            const float4 v0 = vq[q], v1 = vq[q + T], v2 = vq[q + 2 * T], v3 = vq[q + 3 * T];
+            keep(i0.x, v0.x); keep(i0.y, v0.y); keep(i0.z, v0.z); keep(i0.w, v0.w);
+            keep(i1.x, v1.x); keep(i1.y, v1.y); keep(i1.z, v1.z); keep(i1.w, v1.w);
+            keep(i2.x, v2.x); keep(i2.y, v2.y); keep(i2.z, v2.z); keep(i2.w, v2.w);
+            keep(i3.x, v3.x); keep(i3.y, v3.y); keep(i3.z, v3.z); keep(i3.w, v3.w);
+        }
+        for (; q < nq; q += T) {
+            const int4 i0 = iq[q];
+            const float4 v0 = vq[q];
+            keep(i0.x, v0.x); keep(i0.y, v0.y); keep(i0.z, v0.z); keep(i0.w, v0.w);
+        }
+        for (int t = tid; t < head; t += T) keep(index[lo + t], src[lo + t]);
+        for (int t = head + 4 * nq + tid; t < len; t += T) keep(index[lo + t], src[lo + t]);
+        __syncthreads();
+        // the piece, shifted by a: floats [a, a + dn) of `piece` are dst[dlo .. dlo + dn); whole quads in [vs, ve)
+        float *d = dst + dlo - a;
+        const int end = a + dn, vs = min((a + 3) & ~3, end), ve = max(end & ~3, vs);
+        for (int s = vs + 4 * tid; s < ve; s += 4 * T)
+            *reinterpret_cast<float4 *>(d + s) = *reinterpret_cast<const float4 *>(piece + s);
+        if (tid < 4) {
+            if (a + tid < vs) d[a + tid] = piece[a + tid];
+            if (ve + tid < end) d[ve + tid] = piece[ve + tid];
+        }
+        return;
+    }
     for (int w = x; w < n_windows; w += 8) {
         const int64_t lo = window_off ? window_off[w] : n * w / n_windows, hi = window_off ? window_off[w + 1] : n * (w + 1) / n_windows;
         const int64_t step = (int64_t)per_xcd * 256;
@@ -197,8 +260,28 @@ int amar_scatter_f32(const float *src, const int32_t *index, float *dst, int64_t
     if (n < 0 || !src || !index || !dst || ldd < 1 || n_windows < 1 || n >= (1ll << 31)) return AMAR_EINVAL;
     if (n == 0) return AMAR_OK;
     constexpr int per_xcd = 32;                              // 256 workgroups (ml1m(s=64): 0.060 ms against 0.064 at 512, 0.082 at 1 024)
-    hipLaunchKernelGGL(scatter_windows_kernel, dim3(8 * per_xcd), dim3(256), 0, static_cast<hipStream_t>(stream), src, index, dst, ldd, n,
-                       window_off, n_windows, per_xcd);
+    hipLaunchKernelGGL(scatter_windows_kernel<false>, dim3(8 * per_xcd), dim3(256), 0, static_cast<hipStream_t>(stream), src, index, dst, ldd, n,
+                       window_off, n_windows, per_xcd, 0);
+    return amar_check_launch();
+}
+
+int amar_scatter_closed_f32(const float *src, const int32_t *index, float *dst, int64_t n, const int32_t *window_off, int32_t n_windows,
+                            int32_t max_window, amar_stream_t stream) {
+    static_assert(AMAR_SCATTER_CLOSED_MAX_WINDOW % SCATTER_CLOSED_PIECE == 0, "a window of the capacity is cut into whole pieces");
+    if (n < 0 || !src || !index || !dst || !window_off || n_windows < 1 || n >= (1ll << 31) || max_window < 0 ||
+        max_window > AMAR_SCATTER_CLOSED_MAX_WINDOW || (int64_t)max_window * n_windows < n)
+        return AMAR_EINVAL;
+    if (n == 0) return AMAR_OK;
+    const int parts = (max_window + SCATTER_CLOSED_PIECE - 1) / SCATTER_CLOSED_PIECE;
+    const int cap = (max_window + parts - 1) / parts;                            // <= SCATTER_CLOSED_PIECE
+    const size_t lds = (size_t)(cap + 4) * sizeof(float);
+    auto kern = scatter_windows_kernel<true>;
+    static bool allowed[AMAR_MAX_DEVICES] = {};
+    if (const int rc = amar_allow_lds(reinterpret_cast<const void *>(kern), (SCATTER_CLOSED_PIECE + 4) * sizeof(float), allowed)) return rc;
+    const int64_t groups = ((int64_t)n_windows + 7) / 8 * 8 * parts;
+    if (groups >= (1ll << 31)) return AMAR_EINVAL;
+    hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(SCATTER_CLOSED_THREADS), lds, static_cast<hipStream_t>(stream), src, index, dst, (int64_t)1, n,
+                       window_off, n_windows, parts, cap);
     return amar_check_launch();
 }
 }  // extern "C"

@@ -160,7 +160,8 @@ class BasicRS(rec.SimilarSearch, Model):
             if pair_plan.mid_index is not None:
                 capi.chain(tu, blob, dims, acts, pair_plan.mid.view(-1, 1), ids_a=pair_plan.u_ids, base_a=u_base, B=ti, ids_b=pair_plan.i_ids,
                            base_b=i_base, sum_inputs=True, in_act=plan['in_act'], out_index=pair_plan.mid_index)
-                capi.scatter(pair_plan.mid, pair_plan.final_index, out, pair_plan.window_off, pair_plan.n_windows)
+                capi.scatter(pair_plan.mid, pair_plan.final_index, out, pair_plan.window_off, pair_plan.n_windows, closed=True,
+                             max_window=pair_plan.max_window)
                 return out
             capi.chain(tu, blob, dims, acts, out, ids_a=pair_plan.u_ids, base_a=u_base, B=ti, ids_b=pair_plan.i_ids, base_b=i_base,
                        sum_inputs=True, in_act=plan['in_act'], out_index=pair_plan.out_index)
@@ -253,7 +254,7 @@ class PairPlan:
 
     N_XCD, CHUNK = 8, 128
 
-    def __init__(self, u_ids, i_ids, phases=1):
+    def __init__(self, u_ids, i_ids, phases=1, window=None):
         p = int(u_ids.numel())
         dev = u_ids.device
         pos = torch.arange(p, device=dev)
@@ -289,10 +290,15 @@ class PairPlan:
         # 2: 6.0 M pairs 0.289 against 0.242 ms) — AMAR_PAIR_WINDOW_MIN pairs (default 4 Mi).
         # window: about 185 of them (64 Ki scores at ml1m(s=64)'s 12 M pairs, 256 Ki at ml1m(s=256)'s 48 M: every XCD keeps one open line
         # per window, and the second launch's window stays a piece of the destination an L2 holds — ml1m(s=256): 5.05 ms per step
-        # with 256 Ki against 5.14 with 64 Ki and 5.18 with the direct store)
-        self.window = 1 << max(16, min(19, int(round(np.log2(max(p, 1) / 185.0)))))
+        # with 256 Ki against 5.14 with 64 Ki and 5.18 with the direct store).
+        # Where the second launch can finish its windows in LDS (capi.scatter_route: windows up to 64 Ki scores, i.e. lists up to
+        # 16.7 M pairs) the list is cut into 256 windows instead, a multiple of CHUNK each: two workgroups per window, 512 in all, fill
+        # the 256 CUs in two even rounds, and the pair launch sees about as many open lines as before (ml1m(s=64), both launches:
+        # 47 232-score windows 0.442 + 0.033 ms, 64 Ki 0.462 + 0.038, 32 Ki 0.458 + 0.031, 16 Ki 0.506 + 0.029; the global form on
+        # 64 Ki windows 0.442 + 0.073 — profiles/exp_scatter_closed_s64.txt).  `window`: a size of the caller's choice (experiments).
+        self.window = int(window) if window else self.window_for(p)
         self.mid_index = self.final_index = self.window_off = self.mid = None
-        self.n_windows = 0
+        self.n_windows = self.max_window = 0
         if p > 2 * self.window and p >= int(os.environ.get('AMAR_PAIR_WINDOW_MIN', str(1 << 22))):
             n_win = -(-p // self.window)
             key = (src // self.window) * self.N_XCD + (pos // self.CHUNK) % self.N_XCD
@@ -301,10 +307,21 @@ class PairPlan:
             mid_index[by_key] = torch.arange(p, dtype=torch.int32, device=dev)
             self.mid_index = mid_index
             self.final_index = self.out_index[by_key].contiguous()
+            # src is a permutation, so window w holds exactly the final positions [w * window, (w + 1) * window) and sits at those
+            # same positions of `mid`: every window is CLOSED, which is what lets capi.scatter finish it in LDS
             counts = torch.bincount(src // self.window, minlength=n_win)
+            self.max_window = int(counts.max())
             self.window_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts, 0)]).to(torch.int32)
             self.n_windows = n_win
             self.mid = torch.empty(p, dtype=torch.float32, device=dev)
+
+    @classmethod
+    def window_for(cls, p):
+        """The window size the plan cuts a list of p pairs into (see __init__)."""
+        by_cu = -(-(-(-max(p, 1) // 256)) // cls.CHUNK) * cls.CHUNK
+        if capi.scatter_route(p, 1, by_cu, True) == 'lds':
+            return by_cu
+        return 1 << max(16, min(19, int(round(np.log2(max(p, 1) / 185.0)))))
 
     def check(self, u_ids, i_ids):
         if (u_ids.data_ptr(), i_ids.data_ptr(), int(u_ids.numel())) != self._key:

@@ -252,7 +252,8 @@ class HybridCBRS(rec.SimilarSearch, Model):
                                 pair_plan.mid.view(-1, 1) if two_step else out,
                                 out_index=pair_plan.mid_index if two_step else pair_plan.out_index)
                 if two_step:
-                    capi.scatter(pair_plan.mid, pair_plan.final_index, out, pair_plan.window_off, pair_plan.n_windows)
+                    capi.scatter(pair_plan.mid, pair_plan.final_index, out, pair_plan.window_off, pair_plan.n_windows, closed=True,
+                                 max_window=pair_plan.max_window)
                 return out
             capi.dual_chain((in1[0], in2[0]), (in1[1], in2[1]), (args1['ids_a'], args2['ids_a']), (args1['ids_b'], args2['ids_b']),
                             (args1['base_a'], args2['base_a']), (args1['base_b'], args2['base_b']),

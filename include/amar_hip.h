@@ -522,6 +522,23 @@ int amar_reduce_layers_f32(const float *cat, int64_t ld, int32_t n_layers, int32
 int amar_scatter_f32(const float *src, const int32_t *index, float *dst, int64_t ldd, int64_t n,
                      const int32_t *window_off, int32_t n_windows, amar_stream_t stream);
 
+/* The same permutation for a caller that can PROMISE more (models/basic.py:PairPlan does, by construction):
+ *   - every window is CLOSED: the values index[t] of t in [window_off[w], window_off[w + 1]) are a bijection onto that same
+ *     range (sources and destinations of a window are one contiguous range; window_off[0] = 0, window_off[n_windows] = n);
+ *   - dst is dense (one float per position: ldd == 1);
+ *   - no window is longer than max_window, and max_window <= AMAR_SCATTER_CLOSED_MAX_WINDOW.
+ * A window is then finished in LDS — its values placed at their final offset on chip — and written to dst in whole 16-byte
+ * stores (a scalar head and tail where dst + window_off[w] is not 16-byte aligned) instead of one store transaction per
+ * score; windows longer than half the capacity are cut into two destination pieces, one workgroup each.  Same bits as
+ * amar_scatter_f32: the values are moved, never recomputed.  max_window is the host's knowledge of the table (nothing is
+ * read back from the device): AMAR_EINVAL for a null pointer (window_off included), n < 0, n >= 2^31, n_windows < 1,
+ * max_window < 0 or > AMAR_SCATTER_CLOSED_MAX_WINDOW, or n_windows windows of max_window that cannot cover n; AMAR_OK and
+ * nothing written for n == 0.  A table that breaks the promise gives wrong values inside [0, n), never a store outside a
+ * window's own range. */
+#define AMAR_SCATTER_CLOSED_MAX_WINDOW 65536
+int amar_scatter_closed_f32(const float *src, const int32_t *index, float *dst, int64_t n, const int32_t *window_off,
+                            int32_t n_windows, int32_t max_window, amar_stream_t stream);
+
 /* ReductionLayer('w-sum') = WeightedSum (src/layers/reduction.py:36-55): out = sum over the n_layers column blocks of
  * (w[l] * w[l]) * X_l with a learnable device vector w [n_layers] (initialised to ones); products rounded, then added in layer order.
  * n_layers <= 8.  The reverse pass writes d_cat[:, block l] = w[l]^2 d_out and dw[l] = 2 w[l] sum(d_out . X_l), the sums formed per
