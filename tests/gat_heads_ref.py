@@ -36,14 +36,20 @@ def edges(row, col, n, self_loops=True):
     return torch.as_tensor(row, dtype=torch.long), torch.as_tensor(col, dtype=torch.long)
 
 
-def torch_gat_heads(hd, attn_self, attn_neigh, bias, src, tgt, concat=True, keep=None):
+def torch_gat_heads(hd, attn_self, attn_neigh, bias, src, tgt, concat=True, keep=None, scalars=None):
     """One layer from its projection on: hd [n, H, C] (any leading view of [n, H*C]), attn_* [C, H, 1].  Returns the activation
-    [n, H*C] or [n, C].  keep: a dict that receives the attention scalars 's' and 't' [n, H] with their gradients retained."""
+    [n, H*C] or [n, C].  keep: a dict that receives the attention scalars 's' and 't' [n, H] with their gradients retained.
+    scalars: (s, t) [n, H] taken as given leaves in place of hd . attn_* (the entry points take S as an input of its own)."""
     import torch
     n, heads, c = hd.shape
-    s = torch.einsum('nhc,ch->nh', hd, attn_self[:, :, 0])
-    t = torch.einsum('nhc,ch->nh', hd, attn_neigh[:, :, 0])
-    if keep is not None:
+    if scalars is None:
+        s = torch.einsum('nhc,ch->nh', hd, attn_self[:, :, 0])
+        t = torch.einsum('nhc,ch->nh', hd, attn_neigh[:, :, 0])
+    else:
+        s, t = scalars
+    if keep is not None and scalars is not None:
+        keep['s'], keep['t'] = s, t
+    elif keep is not None:
         s.retain_grad(), t.retain_grad()
         keep['s'], keep['t'] = s, t
     e = s[tgt] + t[src]                                              # [E, H]

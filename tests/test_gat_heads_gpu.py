@@ -14,6 +14,7 @@ import yaml
 from scipy import sparse
 
 from tests import helpers, gat_heads_ref as ref
+from tests.gat_heads_ladder_ref import NEW_SHAPES
 from tests.helpers import rel_err
 from tests.test_kernels_gpu import _rand_csr, _dev_csr, _t
 
@@ -23,6 +24,7 @@ CFG = dict(embedding_dim=8, n_hiddens=[8, 8], n_layers=2, dense_units=[24, 24], 
 # (heads, channels): 2 lanes per entry; 6 padded to 8; 16, full; 16 as two heads of 8 quads; 16 as four of 4; 16 as sixteen of 1;
 # then heads of 3 and of 6 quads: no power of two, so the sums over a head's lanes and the averaging gather take their indexed form
 SHAPES = [(2, 4), (3, 8), (8, 8), (2, 32), (4, 16), (16, 4), (2, 12), (2, 24)]
+SHAPES += NEW_SHAPES                                                 # 16 floats as two heads of 2 quads, as four of 1; 12 padded to 16
 
 
 def _graph(seed, symmetric=False, n=350):
