@@ -62,6 +62,8 @@ SIGNATURES = {
     'amar_chain_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I32, _P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _I64, _I64, _P]),
     'amar_chain_indexed_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I32, _P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _I64, _P, _I64, _P]),
     'amar_chain_segments_f32': (ctypes.c_int, [_P, _P, _P, _I32, _P, _I32, _P, _P, _P, _I32, _P, _I64, _I64, _P]),
+    'amar_chain_rows2_route': (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    'amar_chain_rows2_f32': (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
     'amar_chain_route': (ctypes.c_int, [_P, _I64, _I32, _P, _I32, _P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _I64, _P, _I64, _P]),
     'amar_chain_segments_route': (ctypes.c_int, [_P, _P, _P, _I32, _P, _I32, _P, _P, _P, _I32, _P, _I64, _I64, _P]),
     'amar_dual_chain_f32': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _I64, _I64, _P]),
@@ -939,9 +941,46 @@ def chain(A, wpack, dims, acts, out, ids_a=None, base_a=0, B=None, ids_b=None, b
         if A.in_place and B is None and not sum_inputs and out_index is None and chain_segments(A, wpack, dims, acts, out, ids=ids_a, base=base_a):
             return
         A = A.materialize()
-    args = _chain_args(A, wpack, dims, acts, out, ids_a=ids_a, base_a=base_a, B=B, ids_b=ids_b, base_b=base_b, sum_inputs=sum_inputs,
-                       in_act=in_act, out_index=out_index)
-    _check(load().amar_chain_indexed_f32(*args, _stream()), 'amar_chain_indexed_f32' if out_index is not None else 'amar_chain_f32')
+    together = chain_together.active
+    if together is not None and ids_a is None and B is None and not sum_inputs and out_index is None:
+        together.calls.append((A, wpack, list(dims), list(acts), out))      # a one-table call on the rows themselves: launched at the block's end
+        return
+    _chain_launch(A, wpack, dims, acts, out, ids_a=ids_a, base_a=base_a, B=B, ids_b=ids_b, base_b=base_b, sum_inputs=sum_inputs,
+                  in_act=in_act, out_index=out_index)
+
+
+def _chain_launch(A, wpack, dims, acts, out, **kw):
+    args = _chain_args(A, wpack, dims, acts, out, **kw)
+    _check(load().amar_chain_indexed_f32(*args, _stream()), 'amar_chain_indexed_f32' if kw.get('out_index') is not None else 'amar_chain_f32')
+
+
+class chain_together:
+    """`with chain_together():` — the one-table `chain` calls made inside the block (rows themselves: no ids, no second table, no output
+    index) are held back and launched when the block ends: two of them in ONE launch (`chain2`) where the launcher's route takes them
+    (and AMAR_TOWERS_LAUNCH is not 'two'), else each on its own, in the order of the calls.  The outputs are defined after the block;
+    every other `chain` call launches at once.  The same bits either way.
+    Why the holding back sits inside `chain` and the caller does not call `chain2` itself: `chain` is the one place that decides
+    what a table is (a ConcatTable read in place, or assembled first) and the one call the launch-recording tests and tools wrap —
+    a caller keeps making one `chain` call per stack, whichever way they are launched."""
+    active = None
+
+    def __enter__(self):
+        self.calls, self.outer = [], chain_together.active
+        chain_together.active = self
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        chain_together.active = self.outer
+        if exc_type is not None:
+            return False
+        calls = self.calls
+        if len(calls) == 2:
+            # (chain2 asks the launcher's route itself and launches nothing where it declines)
+            if os.environ.get('AMAR_TOWERS_LAUNCH', '') != 'two' and len(calls[0][3]) == len(calls[1][3]) and chain2(calls[0], calls[1]):
+                return False
+        for A, wpack, dims, acts, out in calls:
+            _chain_launch(A, wpack, dims, acts, out)
+        return False
 
 
 CHAIN_KERNEL_GENERIC, CHAIN_KERNEL_PIPE, CHAIN_KERNEL_ROWS = 0, 1, 2
@@ -982,6 +1021,82 @@ def chain_route(A, wpack, dims, acts, out, ids_a=None, base_a=0, B=None, ids_b=N
                        in_act=in_act, out_index=out_index)
     _check(load().amar_chain_route(*args, ctypes.byref(info)), 'amar_chain_route')
     return info.as_dict()
+
+
+class ChainRows2RouteInfo(ctypes.Structure):
+    """include/amar_hip.h: amar_chain_rows2_route_info"""
+    _fields_ = [(name, ctypes.c_int32) for name in ('one_launch', 'shape', 'lastlin', 'threads')] + [('blocks', ctypes.c_int64 * 2),
+                                                                                                 ('lds_bytes', ctypes.c_int64)]
+
+    def as_dict(self):
+        return {'one_launch': bool(self.one_launch), 'shape': int(self.shape), 'lastlin': bool(self.lastlin), 'threads': int(self.threads),
+                'blocks': (int(self.blocks[0]), int(self.blocks[1])), 'lds_bytes': int(self.lds_bytes)}
+
+
+def _chain2_raw(ptrs_a, ldas, ptrs_w, dims, acts, ptrs_out, ldos, rows):
+    """The argument list of amar_chain_rows2_f32 / _route from plain numbers: two entries each (addresses as ints)."""
+    if len(acts[0]) != len(acts[1]) or any(len(d) != len(a) + 1 for d, a in zip(dims, acts)):
+        raise ValueError("chain2: both stacks need the same number of layers, dims one entry longer than acts")
+    keep = [(ctypes.c_int32 * len(d))(*d) for d in dims] + [(ctypes.c_int32 * len(a))(*[ACT_CODES[x] for x in a]) for a in acts]
+    vp = lambda vals: (ctypes.c_void_p * 2)(*vals)                                                # noqa: E731
+    i64 = lambda vals: (ctypes.c_int64 * 2)(*[int(v) for v in vals])                               # noqa: E731
+    args = [vp(ptrs_a), i64(ldas), vp(ptrs_w), vp([ctypes.addressof(keep[0]), ctypes.addressof(keep[1])]),
+            vp([ctypes.addressof(keep[2]), ctypes.addressof(keep[3])]), len(acts[0]), vp(ptrs_out), i64(ldos), i64(rows)]
+    return args, keep
+
+
+def _chain2_args(first, second):
+    """first / second: (A, wpack, dims, acts, out) as `chain` takes them, rows themselves."""
+    for A, _, _, _, out in (first, second):
+        if A.shape[0] < out.shape[0]:
+            raise ValueError("chain2: input blocks have fewer rows than the output")
+    both = (first, second)
+    return _chain2_raw([_ptr(p[0], torch.float32, 'A') for p in both], [_ld(p[0], 'A') for p in both],
+                       [_ptr(p[1], torch.float32, 'wpack') for p in both], [p[2] for p in both], [p[3] for p in both],
+                       [_ptr(p[4], torch.float32, 'out') for p in both], [_ld(p[4], 'out') for p in both], [p[4].shape[0] for p in both])
+
+
+def chain2(first, second):
+    """Two `chain` calls on one table each — first / second = (A, wpack, dims, acts, out), rows themselves — in ONE launch
+    (amar_chain_rows2_f32: the workgroups of one grid dealt to the two problems by their rows; the same bits as two `chain` calls).
+    Returns False, with nothing launched, where chain2_route says one_launch is off: make two `chain` calls."""
+    args, keep = _chain2_args(first, second)
+    code = load().amar_chain_rows2_f32(*args, _stream())
+    if code == -2:                                                   # AMAR_EUNSUPPORTED: not one compile-time tower kernel for both
+        return False
+    _check(code, 'amar_chain_rows2_f32')
+    return True
+
+
+def chain2_route(first, second):
+    """What `chain2` does with these operands (amar_chain_rows2_route: host only, nothing is launched): a dict of the fields of
+    amar_chain_rows2_route_info.  one_launch False: make two `chain` calls."""
+    info = ChainRows2RouteInfo()
+    args, keep = _chain2_args(first, second)
+    _check(load().amar_chain_rows2_route(*args, ctypes.byref(info)), 'amar_chain_rows2_route')
+    return info.as_dict()
+
+
+_MADE_UP = 0x7F0000100000      # a 16-byte aligned address: the route functions look at alignment and NULL only
+
+
+def towers_route(u_dims, u_acts, u_rows, i_dims, i_acts, i_rows, u_ids=False, i_ids=False, info=False):
+    """How BasicRS.towers launches its two stacks: 'one' (chain2: both towers in one grid) or 'two' (a `chain` call each).  Host only:
+    needs no GPU (the same route function as the launcher's, asked with dense tables at made-up addresses).  'one' needs both stacks
+    on the same compile-time tower kernel (ChainRouteInfo: kernel ROWS, equal shape / lastlin), rows on both sides and no id lists;
+    AMAR_TOWERS_LAUNCH=two keeps the two launches.  info=True: (route, the dict of amar_chain_rows2_route_info or None)."""
+    route, d = 'two', None
+    if (os.environ.get('AMAR_TOWERS_LAUNCH', '') != 'two' and not u_ids and not i_ids and len(u_acts) == len(i_acts)
+            and len(u_dims) == len(u_acts) + 1 and len(i_dims) == len(i_acts) + 1):
+        dims, acts = (list(u_dims), list(i_dims)), (list(u_acts), list(i_acts))
+        pad4 = lambda w: (int(w) + 3) // 4 * 4                                                     # noqa: E731
+        args, keep = _chain2_raw([_MADE_UP, _MADE_UP + (1 << 40)], [pad4(d_[0]) for d_ in dims], [_MADE_UP + (2 << 40), _MADE_UP + (3 << 40)],
+                                 dims, acts, [_MADE_UP + (4 << 40), _MADE_UP + (5 << 40)], [pad4(d_[-1]) for d_ in dims], [u_rows, i_rows])
+        r = ChainRows2RouteInfo()
+        if load().amar_chain_rows2_route(*args, ctypes.byref(r)) == 0:
+            d = r.as_dict()
+            route = 'one' if d['one_launch'] else 'two'
+    return (route, d) if info else route
 
 
 def dual_chain_supported(D, n_branch_dims_equal, trunk_dims):

@@ -212,8 +212,10 @@ constexpr int shape_maxt(int s) {
     return m;
 }
 
+// (block / n_blocks: this workgroup's number among the n_blocks that share the problem `a` — the whole grid for chain_rows_kernel, one
+// part of it for chain_rows2_kernel)
 template <int SHAPE, int PT, bool LASTLIN, bool SEG>
-__global__ __launch_bounds__(256) void chain_rows_kernel(const ChainArgs a) {
+__device__ __forceinline__ void chain_rows_body(const ChainArgs &a, const uint32_t block, const uint32_t n_blocks) {
     constexpr int NL = shape_nl(SHAPE), T0 = shape_t(SHAPE, 0), TN = shape_t(SHAPE, NL), MAXT = shape_maxt(SHAPE);
     extern __shared__ __attribute__((aligned(16))) float w_lds[];
     for (int i = threadIdx.x * 4; i < a.wpack_floats; i += blockDim.x * 4)
@@ -222,11 +224,13 @@ __global__ __launch_bounds__(256) void chain_rows_kernel(const ChainArgs a) {
 
     const int lane = threadIdx.x & 63, g = lane >> 4, col = lane & 15;
     constexpr uint32_t rows_per_wave = 16 * PT;
-    const uint32_t stride = gridDim.x * 4 * rows_per_wave;
+    const uint32_t stride = n_blocks * 4 * rows_per_wave;
     const uint32_t P = (uint32_t)a.P, last = P - 1;                 // (the launcher checks P + 2 strides < 2^30 and the row bytes)
     const uint32_t lda = (uint32_t)a.lda * 4u;
     const int f_last = 16 * (T0 - 1) + 4 * g;                      // this lane's features of the last input tile: past Da -> zeros
     const bool tail_ok = f_last < a.Da;
+    // (a ragged width leaves no MFMA to skip: the features past Da are lane groups g of EVERY k-slot r of the last tile — feature 16 t + 4 g + r —,
+    // so each of its four instructions has live k-lanes)
     const char *Ag = reinterpret_cast<const char *>(a.A) + 16 * g;
     const int tail_off = tail_ok ? 64 * (T0 - 1) : -16 * g;        // (a lane past Da in the last tile re-reads the row's first features)
     // SEG: this lane's float4 of input tile t (features 16t + 4g .. +3) lies in ONE of the concatenated tables (their widths are
@@ -259,7 +263,7 @@ __global__ __launch_bounds__(256) void chain_rows_kernel(const ChainArgs a) {
         }
     };
 
-    uint32_t base = (blockIdx.x * 4 + (threadIdx.x >> 6)) * rows_per_wave;
+    uint32_t base = (block * 4 + (threadIdx.x >> 6)) * rows_per_wave;
     if (base >= P) return;
     gather(base);
     for (; base < P; base += stride) {
@@ -311,6 +315,24 @@ __global__ __launch_bounds__(256) void chain_rows_kernel(const ChainArgs a) {
                 if (p < P && 16 * m + 4 * g < a.n_out) *reinterpret_cast<f32x4 *>(po + 16 * m) = x[m][pt];
         }
     }
+}
+
+template <int SHAPE, int PT, bool LASTLIN, bool SEG>
+__global__ __launch_bounds__(256) void chain_rows_kernel(const ChainArgs a) {
+    chain_rows_body<SHAPE, PT, LASTLIN, SEG>(a, blockIdx.x, gridDim.x);
+}
+
+// Both entity towers in ONE grid: two row-chain problems of the same compile-time shape (each with its own table, packed weights and
+// output), the first `split` workgroups on problem 0 and the rest on problem 1.  The launcher deals the workgroups in proportion to the
+// problems' rows, so both parts finish together: one ramp-up and one drain instead of two of each (two launches in a row each leave the
+// chip partly empty at their ends, the item tower with a third of the rows most of all).  A workgroup loads only its own problem's weights
+// and walks its own rows with the stride of its own part: per row the code is chain_rows_kernel's, the tables are bit-identical.
+struct ChainArgs2 { ChainArgs p[2]; uint32_t split, n_blocks; };
+
+template <int SHAPE, int PT, bool LASTLIN>
+__global__ __launch_bounds__(256) void chain_rows2_kernel(const ChainArgs2 a2) {
+    const bool second = blockIdx.x >= a2.split;                     // (wave-uniform: one copy of the body, its arguments read from the chosen problem)
+    chain_rows_body<SHAPE, PT, LASTLIN, false>(a2.p[second], second ? blockIdx.x - a2.split : blockIdx.x, second ? a2.n_blocks - a2.split : a2.split);
 }
 
 // Pair-stage form of the same chain (x = relu(A[ida] + B[idb]), every layer MAXT x MAXT tiles with ReLU, Da = 16 MAXT).
@@ -1326,6 +1348,80 @@ static int chain_run(const float *A, int64_t lda, int32_t Da, const int32_t *ids
     } while (0)
     if (r.maxt == 3) AMAR_CHAIN_LAUNCH(3); else if (r.maxt == 4) AMAR_CHAIN_LAUNCH(4); else AMAR_CHAIN_LAUNCH(8);
 #undef AMAR_CHAIN_LAUNCH
+    return amar_check_launch();
+}
+
+// Both towers in one launch.  Every decision on the host, for the launcher and for amar_chain_rows2_route alike: each problem goes through
+// chain_route as the one-table call it is (rows themselves, no ids), and the launch is taken when both land on the compile-time tower
+// kernel in the same form.  The workgroups are dealt in proportion to the problems' 128-row tiles, at least one each and no more than
+// a problem has tiles.
+// How many: grid1's kernel (24 -> 24 -> 24 -> 48) holds 144 registers (the compiler's resource report, this kernel and the one-table one
+// alike), three waves per SIMD, so 768 workgroups are resident at once; what
+// a grid has beyond them waits for a slot and runs as a second, partly filled round.  ml1m(s=64), both towers, replayed back to back:
+// 768 workgroups 0.0494 ms, 1 536 0.0500, 2 304 0.0518, 1 024 0.0537, the two launches of 1 024 each 0.0555.  grid2's shape (48 -> 48 -> 48 -> 64,
+// 240 registers, two waves per SIMD) and the others keep the 1 024 of the one-table launch: see DESIGN 4b for grid2's step.  The figure
+// follows the register count: if a compiler moves the kernel to another occupancy, measure again.
+static int64_t chain_rows2_blocks(int shape) { return shape == chain_shape(3, 2, 2, 2, 3) ? 768 : 1024; }
+
+static int chain_rows2_route(const float *const *A, const int64_t *lda, const float *const *wpack, const int32_t *const *dims,
+                             const int32_t *const *acts, int32_t n_layers, float *const *out, const int64_t *ldo, const int64_t *P,
+                             ChainArgs2 &a2, amar_chain_rows2_route_info &r) {
+    if (!A || !lda || !wpack || !dims || !acts || !out || !ldo || !P) return AMAR_EINVAL;
+    r = amar_chain_rows2_route_info{};
+    amar_chain_route_info one[2];
+    for (int j = 0; j < 2; ++j) {
+        if (!dims[j]) return AMAR_EINVAL;
+        if (const int rc = chain_route(A[j], lda[j], dims[j][0], nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, AMAR_ACT_NONE, wpack[j], dims[j], acts[j],
+                                       n_layers, out[j], ldo[j], nullptr, P[j], 0, nullptr, nullptr, nullptr, a2.p[j], one[j]))
+            return rc;
+    }
+    if (one[0].kernel != AMAR_CHAIN_KERNEL_ROWS || one[1].kernel != AMAR_CHAIN_KERNEL_ROWS || one[0].shape != one[1].shape ||
+        one[0].lastlin != one[1].lastlin || one[0].lds_bytes != one[1].lds_bytes || P[0] < 1 || P[1] < 1)
+        return AMAR_OK;                                             // r.one_launch == 0: the caller makes two launches
+    const int64_t t0 = (P[0] + 127) / 128, t1 = (P[1] + 127) / 128;   // 4 waves of two 16-row tiles per workgroup
+    const int64_t cap = chain_rows2_blocks(one[0].shape);
+    int64_t b0 = t0, b1 = t1;
+    if (t0 + t1 > cap) {
+        b0 = (cap * t0 + (t0 + t1) / 2) / (t0 + t1);
+        b0 = b0 < 1 ? 1 : (b0 > cap - 1 ? cap - 1 : b0);
+        if (b0 > t0) b0 = t0;
+        b1 = cap - b0;
+        if (b1 > t1) { b1 = t1; b0 = cap - b1; }
+    }
+    r.one_launch = 1; r.shape = one[0].shape; r.lastlin = one[0].lastlin; r.threads = 256;
+    r.blocks[0] = b0; r.blocks[1] = b1; r.lds_bytes = one[0].lds_bytes;
+    a2.split = (uint32_t)b0; a2.n_blocks = (uint32_t)(b0 + b1);
+    return AMAR_OK;
+}
+
+int amar_chain_rows2_route(const float *const *A, const int64_t *lda, const float *const *wpack, const int32_t *const *dims,
+                           const int32_t *const *acts, int32_t n_layers, float *const *out, const int64_t *ldo, const int64_t *P,
+                           amar_chain_rows2_route_info *info) {
+    if (!info) return AMAR_EINVAL;
+    ChainArgs2 a2;
+    return chain_rows2_route(A, lda, wpack, dims, acts, n_layers, out, ldo, P, a2, *info);
+}
+
+int amar_chain_rows2_f32(const float *const *A, const int64_t *lda, const float *const *wpack, const int32_t *const *dims,
+                         const int32_t *const *acts, int32_t n_layers, float *const *out, const int64_t *ldo, const int64_t *P,
+                         amar_stream_t stream) {
+    ChainArgs2 a2;
+    amar_chain_rows2_route_info r;
+    if (const int rc = chain_rows2_route(A, lda, wpack, dims, acts, n_layers, out, ldo, P, a2, r)) return rc;
+    if (!r.one_launch) return AMAR_EUNSUPPORTED;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)(r.blocks[0] + r.blocks[1])), block(256);
+    const size_t lds = (size_t)r.lds_bytes;
+#define AMAR_ROWS2_CASE(NLL, A0, A1, A2, A3)                                                                                      \
+    case chain_shape(NLL, A0, A1, A2, A3):                                                                                        \
+        if (r.lastlin) hipLaunchKernelGGL((chain_rows2_kernel<chain_shape(NLL, A0, A1, A2, A3), 2, true>), grid, block, lds, st, a2);   \
+        else hipLaunchKernelGGL((chain_rows2_kernel<chain_shape(NLL, A0, A1, A2, A3), 2, false>), grid, block, lds, st, a2);            \
+        break;
+    switch (r.shape) {
+    AMAR_ROWS_SHAPES(AMAR_ROWS2_CASE)
+    default: return AMAR_EUNSUPPORTED;                              // (not reached: chain_route knows the same list)
+    }
+#undef AMAR_ROWS2_CASE
     return amar_check_launch();
 }
 

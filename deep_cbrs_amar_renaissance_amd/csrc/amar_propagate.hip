@@ -14,6 +14,7 @@
 #include "amar_common.h"
 #include "amar_philox.h"
 #include <stdlib.h>
+#include <string.h>
 
 namespace {
 
@@ -1245,6 +1246,53 @@ __global__ __launch_bounds__(256) void rowwise_xw_vec_kernel(const XwArgs a) {
     }
 }
 
+// F = C = 8 without attention scalars and without row ids — the GCN stacks' prologue — by 16-byte PIECES instead of rows: a lane pair
+// shares a row, lane `half` loads the row's float4 number `half` and computes the output columns 4 half .. 4 half + 3.  The one-row-per-
+// thread kernel above asks, per instruction, for 16 bytes out of every 32 (loads, H) or 96 (the slice copy): each wave instruction covers
+// twice the lines it uses, and a lane has 64 bytes in flight.  Here a wave's loads and its H stores are 1 KB of consecutive bytes, the
+// slice copy writes each row's 32 bytes from neighbouring lanes, and R pieces per lane are requested before the first FMA.  The
+// other half of the row comes over a lane swap inside the pair; a lane keeps its four columns of W (32 values) in registers for the
+// whole launch.  Per output the operations are those of the kernels above — fmaf over k ascending from 0, then the row scale —: the
+// same bits.
+template <int R>
+__global__ __launch_bounds__(256) void rowwise_xw8_pieces_kernel(const XwArgs a) {
+    const int half = threadIdx.x & 1;
+    float w[8][4];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float4 v = *reinterpret_cast<const float4 *>(a.W + 8 * k + 4 * half);
+        w[k][0] = v.x; w[k][1] = v.y; w[k][2] = v.z; w[k][3] = v.w;
+    }
+    const int64_t n_pieces = 2 * (int64_t)a.n_rows;                   // (even: the two lanes of a pair are inside or outside together)
+    for (int64_t i0 = (int64_t)blockIdx.x * 256 * R + threadIdx.x; i0 < n_pieces; i0 += (int64_t)gridDim.x * 256 * R) {
+        float4 x[R];
+        float sc[R];
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            const int64_t i = i0 + 256 * j < n_pieces ? i0 + 256 * j : i0;   // (past the end: the first piece again, not stored)
+            x[j] = *reinterpret_cast<const float4 *>(a.X + (i >> 1) * a.ldx + 4 * half);
+            sc[j] = a.row_scale ? a.row_scale[i >> 1] : 1.f;
+        }
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            const int64_t i = i0 + 256 * j;
+            if (i >= n_pieces) break;
+            const int64_t row = i >> 1;
+            if (a.copy_to) *reinterpret_cast<float4 *>(a.copy_to + row * a.ld_copy + 4 * half) = x[j];
+            const float4 o = make_float4(__shfl_xor(x[j].x, 1, 64), __shfl_xor(x[j].y, 1, 64), __shfl_xor(x[j].z, 1, 64), __shfl_xor(x[j].w, 1, 64));
+            const float4 lo = half ? o : x[j], hi = half ? x[j] : o;
+            const float xs[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+            float h[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) h[c] = fmaf(xs[k], w[k][c], h[c]);
+            *reinterpret_cast<float4 *>(a.H + row * a.ldh + 4 * half) =
+                a.row_scale ? make_float4(h[0] * sc[j], h[1] * sc[j], h[2] * sc[j], h[3] * sc[j]) : make_float4(h[0], h[1], h[2], h[3]);
+        }
+    }
+}
+
 // ---- GraphSAGE (mean) ------------------------------------------------------------------------
 struct SageArgs {
     const int32_t *rowptr; const int32_t *colidx; const float *X; int64_t ldx;
@@ -1796,6 +1844,15 @@ static int rowwise_xw_run(const float *X, int64_t ldx, int32_t F, const float *W
     XwArgs a{X, ldx, F, W, C, H, ldh, copy_to, ld_copy, a_self, a_neigh, attn ? s_self : nullptr, s_neigh, n_rows, row_scale, row_ids};
     if (F == C && (F == 8 || F == 16) && (ldx & 3) == 0 && (ldh & 3) == 0 && amar_aligned16(X) && amar_aligned16(H) &&
         (!copy_to || ((ld_copy & 3) == 0 && amar_aligned16(copy_to)))) {
+        // the square 8-wide product without attention scalars or row ids: by 16-byte pieces, four per lane (AMAR_XW_FORM=rows keeps the
+        // one-row-per-thread kernel; read at every call: the tests compare the two forms in one process)
+        const char *form = getenv("AMAR_XW_FORM");
+        if (F == 8 && !attn && !row_ids && amar_aligned16(W) && !(form && !strcmp(form, "rows"))) {
+            int64_t pblocks = (2 * (int64_t)n_rows + 1023) / 1024;
+            if (pblocks > 8192) pblocks = 8192;
+            hipLaunchKernelGGL(rowwise_xw8_pieces_kernel<4>, dim3((unsigned)pblocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+            return amar_check_launch();
+        }
         const int rows_per_block = F == 8 ? 512 : 256;              // (two rows per thread at F = 8)
         int64_t vblocks = ((int64_t)n_rows + rows_per_block - 1) / rows_per_block;
         if (vblocks > 8192) vblocks = 8192;

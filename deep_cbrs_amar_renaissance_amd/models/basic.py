@@ -114,11 +114,14 @@ class BasicRS(rec.SimilarSearch, Model):
             return (self.unet.apply2(u_table, ids_a=u_ids), self.inet.apply2(i_table, ids_a=i_ids), False)
         out = []
         for key, table, ids in (('u', u_table, u_ids), ('i', i_table, i_ids)):
-            blob, dims, acts = plan[key]
             m = ids.numel() if ids is not None else table.shape[0]
-            t = torch.empty((m, dims[-1]), dtype=torch.float32, device=table.device)
-            capi.chain(table, blob, dims, acts, t, ids_a=ids)
-            out.append(t)
+            out.append(torch.empty((m, plan[key][1][-1]), dtype=torch.float32, device=table.device))
+        # both towers in one launch where their stacks run the same compile-time kernel on the rows themselves (capi.chain_together /
+        # capi.towers_route; DESIGN 9a: AMAR_TOWERS_LAUNCH=two keeps the launch per tower) — the same bits either way
+        with capi.chain_together():
+            for key, table, ids, t in (('u', u_table, u_ids, out[0]), ('i', i_table, i_ids, out[1])):
+                blob, dims, acts = plan[key]
+                capi.chain(table, blob, dims, acts, t, ids_a=ids)
         return (out[0], out[1], True)
 
     def tower(self, key, table, ids=None):

@@ -478,6 +478,24 @@ int amar_chain_segments_route(const float *const *seg, const int64_t *seg_ld, co
                               const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers,
                               float *out, int64_t ldo, int64_t P, amar_chain_route_info *info);
 
+/* Both entity towers in ONE launch: two one-table row-chain problems (rows themselves, no ids; each with its own table, packed
+ * weights, widths and output) whose stacks run the same compile-time tower kernel (amar_chain_route_info.kernel ==
+ * AMAR_CHAIN_KERNEL_ROWS with equal `shape`, `lastlin` and `lds_bytes`), both with at least one row.  The workgroups of one grid are
+ * dealt to the two problems in proportion to their rows; per row the arithmetic is that of amar_chain_f32, bit for bit.
+ * A, lda, wpack, dims, acts, out, ldo, P are HOST arrays of two entries.  amar_chain_rows2_route (host only, no launch) reports
+ * whether the launch is taken (one_launch) and the workgroups of each part; amar_chain_rows2_f32 returns AMAR_EUNSUPPORTED where
+ * it is not: call amar_chain_f32 once per problem instead.  Argument errors of either problem are those of amar_chain_f32. */
+typedef struct amar_chain_rows2_route_info {
+    int32_t one_launch, shape, lastlin, threads;
+    int64_t blocks[2], lds_bytes;
+} amar_chain_rows2_route_info;
+int amar_chain_rows2_route(const float *const *A, const int64_t *lda, const float *const *wpack, const int32_t *const *dims,
+                           const int32_t *const *acts, int32_t n_layers, float *const *out, const int64_t *ldo, const int64_t *P,
+                           amar_chain_rows2_route_info *info);
+int amar_chain_rows2_f32(const float *const *A, const int64_t *lda, const float *const *wpack, const int32_t *const *dims,
+                         const int32_t *const *acts, int32_t n_layers, float *const *out, const int64_t *ldo, const int64_t *P,
+                         amar_stream_t stream);
+
 /* Fused two-branch scorer for the hybrid head (src/models/hybrid.py:72-89) once the first Dense layers of
  * dense3a / dense3b have been folded into the per-entity tables:
  *     x_b  = in_act( A[b][ida_b(p)] + B[b][idb_b(p)] )            b = 0, 1;  [P, D]
