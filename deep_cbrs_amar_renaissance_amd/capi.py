@@ -148,6 +148,8 @@ SIGNATURES = {
     'amar_nearest_workspace_floats': (ctypes.c_int64, [_I64, _I32, _I32, _I32, _I32]),
     'amar_nearest_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _P, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     'amar_rank_metrics_f64': (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P]),
+    'amar_rerank_mmr_f32': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _F32, _I32, _P, _P, _P, _P, _P]),
+    'amar_list_diversity_f64': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _P]),
 }
 
 _lib = None
@@ -1655,6 +1657,59 @@ def rank_metrics(lists, rel_ptr, rel_items, ks, users=None):
     evaluated, skipped = (int(c) for c in counts.cpu().numpy())
     sums = sums.cpu().numpy()
     return (sums / evaluated if evaluated else sums), evaluated, skipped
+
+
+DIVERSIFY_MAX_P = 64                                                   # include/amar_hip.h: AMAR_DIVERSIFY_MAX_P
+
+
+def _lists_matrix(t, name):
+    if t.dim() != 2 or not t.is_contiguous():
+        raise ValueError("{} must be a contiguous [m, P] tensor".format(name))
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def rerank_mmr(pool_items, pool_scores, T, k, trade_off=0.7, metric='cosine', want_mmr=False, want_ild=False):
+    """Greedy MMR re-ranking of device pools (amar_rerank_mmr_f32): pool_items int32 [m, P] rows of T (valid prefix, -1 padded),
+    pool_scores float32 [m, P], T float32 [n_rows, d].  Returns (items int32 [m, k], scores float32 [m, k]) in selection order,
+    followed by the MMR values float32 [m, k] (want_mmr) and the lists' ILD float64 [m] (want_ild).  One launch, no workspace."""
+    if metric not in NEAREST_METRICS:
+        raise ValueError("rerank_mmr: metric must be one of {} (got {!r})".format(sorted(NEAREST_METRICS), metric))
+    m, P = _lists_matrix(pool_items, 'pool_items')
+    if _lists_matrix(pool_scores, 'pool_scores') != (m, P):
+        raise ValueError("rerank_mmr: pool_items and pool_scores must have the same shape")
+    dev = T.device
+    k = int(k)
+    out_items = torch.empty((m, max(k, 0)), dtype=torch.int32, device=dev)
+    out_scores = torch.empty((m, max(k, 0)), dtype=torch.float32, device=dev)
+    out_mmr = torch.empty((m, max(k, 0)), dtype=torch.float32, device=dev) if want_mmr else None
+    out_ild = torch.empty((m,), dtype=torch.float64, device=dev) if want_ild else None
+    code = load().amar_rerank_mmr_f32(
+        _ptr(pool_items, torch.int32, 'pool_items') if m else None, _ptr(pool_scores, torch.float32, 'pool_scores') if m else None,
+        m, P, _ptr(T, torch.float32, 'T'), _ld(T, 'T'), int(T.shape[0]), int(T.shape[1]), NEAREST_METRICS[metric], float(trade_off),
+        k, _ptr(out_items) if m else None, _ptr(out_scores) if m else None, _ptr(out_mmr) if m else None,
+        _ptr(out_ild) if m else None, _stream())
+    _check(code, 'amar_rerank_mmr_f32')
+    return (out_items, out_scores) + ((out_mmr,) if want_mmr else ()) + ((out_ild,) if want_ild else ())
+
+
+def list_diversity(lists, T, ks, metric='cosine'):
+    """Intra-list diversity of device lists (amar_list_diversity_f64): lists int32 [m, K] rows of T (-1 padded), cutoffs ks.  Returns
+    (ild float64 [m, nk]: the mean of 1 - sim over the pairs of valid items in the first ks[q] ranks, 0 below two items;
+    count int32 [m, nk]: those items), both on the device."""
+    if metric not in NEAREST_METRICS:
+        raise ValueError("list_diversity: metric must be one of {} (got {!r})".format(sorted(NEAREST_METRICS), metric))
+    m, K = _lists_matrix(lists, 'lists')
+    ks = [int(k) for k in ks]
+    dev = T.device
+    out_ild = torch.empty((m, len(ks)), dtype=torch.float64, device=dev)
+    out_count = torch.empty((m, len(ks)), dtype=torch.int32, device=dev)
+    ks_c = (ctypes.c_int32 * max(1, len(ks)))(*ks)
+    code = load().amar_list_diversity_f64(
+        _ptr(lists, torch.int32, 'lists') if m else None, m, K, _ptr(T, torch.float32, 'T'), _ld(T, 'T'), int(T.shape[0]),
+        int(T.shape[1]), NEAREST_METRICS[metric], ks_c, len(ks), _ptr(out_ild) if m else None, _ptr(out_count) if m else None,
+        _stream())
+    _check(code, 'amar_list_diversity_f64')
+    return out_ild, out_count
 
 
 # ---- training step ----------------------------------------------------------------------------------------------

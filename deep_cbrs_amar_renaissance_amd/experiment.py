@@ -381,6 +381,8 @@ class Experimenter:
             self.evaluate_full_ranking([int(k) for k in self.config.parameters.get('full_ranking_ks')])
         if self.config.parameters.get('similar_items'):
             self.write_similar_items(**dict(self.config.parameters.get('similar_items')))
+        if self.config.parameters.get('diversify'):
+            self.write_diverse(**dict(self.config.parameters.get('diversify')))
         self.logger.info('\n' + str(metrics))
         print('\n' + str(metrics))
         return metrics
@@ -413,6 +415,31 @@ class Experimenter:
         path = path_join(self.predictions_dest, "similar_items_{}.tsv".format(int(k)))
         frame.to_csv(path, sep='\t', header=False, index=False)
         return path
+
+    def write_diverse(self, k=10, pool=50, trade_off=0.7, metric='cosine', space=None):
+        """Opt-in (parameters.diversify: {k, pool, trade_off, metric, space}): every user's `pool` best unseen items re-ranked by
+        Maximal Marginal Relevance (`recommend_diverse()`), written as <predictions_dest>/diverse_top_<k>.tsv (user, item, score;
+        original ids, selection order); the intra-list diversity and the catalogue coverage at k of the plain top-k and of the
+        diversified lists are logged as plain_ / diverse_ ild_at_<k> and item_coverage_at_<k>."""
+        import torch
+        from deep_cbrs_amar_renaissance_amd import recommend as rec
+        k = int(k)
+        users, items, scores = self.model.recommend_diverse(self.trainset, k=k, pool=int(pool), trade_off=float(trade_off),
+                                                            metric=metric, space=space)
+        path = path_join(self.predictions_dest, "diverse_top_{}.tsv".format(k))
+        recommendations_frame(users, items, scores, self.trainset.users, self.trainset.items).to_csv(
+            path, sep='\t', header=False, index=False)
+        n_users, n_items = len(self.trainset.users), len(self.trainset.items)
+        table = self.model._item_embeddings(self.trainset, space)
+        with rec.device_lists():
+            _, plain, _ = self.model.recommend(self.trainset, k=k)
+        diverse = torch.from_numpy(np.where(items >= 0, items - n_users, -1).astype(np.int32)).to(table.device)
+        logged = {}
+        for prefix, lists in (('plain_', plain.contiguous()), ('diverse_', diverse)):
+            if len(users):
+                logged.update({prefix + name: value for name, value in rec.diversity_metrics(lists, table, [k], metric, n_items).items()})
+        self.run_log.log_metrics(logged)
+        return path, logged
 
     def run(self):
         self.train()

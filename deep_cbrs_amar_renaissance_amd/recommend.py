@@ -23,6 +23,10 @@ ROWS on the device, scores float32 [m, k] on the device)``: ``evaluate_ranking``
 The second half of the module is similarity search over the vectors the models learn: ``nearest`` (one ``amar_nearest_f32`` call, dot
 or cosine, nothing of size m x n in memory) and ``SimilarSearch``, the mixin that gives every scoring model ``user_embeddings`` /
 ``item_embeddings``, ``similar_items``, ``similar_users`` and ``recommend_like``.
+
+The third part is what a list looks like as a whole: ``rerank_mmr`` (one ``amar_rerank_mmr_f32`` launch re-ranks device pools by
+Maximal Marginal Relevance; nothing of size m x P x P in memory), the mixin's ``recommend_diverse`` / ``list_diversity``, and the
+opt-in ``diversity=`` of ``evaluate_ranking`` (intra-list diversity and catalogue coverage beside the accuracy metrics).
 """
 import contextlib
 import weakref
@@ -120,19 +124,55 @@ def device_lists():
         _ON_DEVICE = saved
 
 
-def evaluate_ranking(model, trainset, test_ratings, ks, users=None, exclude_seen=True):
+def evaluate_ranking(model, trainset, test_ratings, ks, users=None, exclude_seen=True, diversity=None):
     """model.recommend at k = max(ks) with the lists kept on the device, then utilities.metrics.full_ranking_metrics_device: the
-    dict of `full_ranking_metrics(*model.recommend(...)[:2], test_ratings, ks)` without the lists (or a Python loop) on the host."""
+    dict of `full_ranking_metrics(*model.recommend(...)[:2], test_ratings, ks)` without the lists (or a Python loop) on the host.
+    diversity={'metric': 'cosine' | 'dot', 'space': ...} (both optional) adds, for every k, 'ild_at_<k>' (the float64 mean, over the
+    lists with at least two items in their first k ranks, of the intra-list diversity of those ranks in the model's item `space`:
+    amar_list_diversity_f64) and 'item_coverage_at_<k>' (the distinct items in the first k ranks of all lists over |I|)."""
     from deep_cbrs_amar_renaissance_amd.utilities.metrics import full_ranking_metrics, full_ranking_metrics_device
     ks = [int(k) for k in ks]
     if not ks:
         raise ValueError("evaluate_ranking needs at least one k")
+    if diversity is not None:
+        unknown = set(diversity) - {'metric', 'space'}
+        if unknown:
+            raise ValueError("diversity takes the keys 'metric' and 'space' (got {})".format(sorted(unknown)))
+        check_metric(diversity.get('metric', 'cosine'))
     n_users, n_items = _sizes(trainset)
     with device_lists():
         u, items, _ = model.recommend(trainset, k=check_k(max(ks)), users=users, exclude_seen=exclude_seen)
     if len(u) == 0:
-        return full_ranking_metrics(u, items, test_ratings, ks)
-    return full_ranking_metrics_device(None if users is None else u, items.contiguous(), test_ratings, ks, n_users, n_items)
+        out = full_ranking_metrics(u, items, test_ratings, ks)
+        if diversity is not None:
+            for k in ks:
+                out['ild_at_{}'.format(k)], out['item_coverage_at_{}'.format(k)] = 0.0, 0.0
+        return out
+    items = items.contiguous()
+    out = full_ranking_metrics_device(None if users is None else u, items, test_ratings, ks, n_users, n_items)
+    if diversity is not None:
+        table = model._item_embeddings(trainset, diversity.get('space'))
+        out.update(diversity_metrics(items, table, ks, diversity.get('metric', 'cosine'), n_items))
+    return out
+
+
+def diversity_metrics(lists, table, ks, metric, n_items):
+    """{'ild_at_<k>', 'item_coverage_at_<k>'} of device lists (int32 [m, K] item rows, -1 padded): the ILD per list from
+    amar_list_diversity_f64, averaged in float64 over the lists that have at least two items in their first k ranks (0 when none
+    has); the coverage by integer work on the device."""
+    check_width(table.shape[1], 'item vectors')
+    table = _as_device_matrix(table, lists.device, 'table')
+    ild, count = capi.list_diversity(lists, table, ks, metric=check_metric(metric))
+    ild, count = ild.cpu().numpy(), count.cpu().numpy()
+    out = {}
+    for q, k in enumerate(ks):
+        has = count[:, q] >= 2
+        out['ild_at_{}'.format(k)] = float(ild[has, q].mean()) if has.any() else 0.0
+        head = lists[:, :k]
+        seen = torch.zeros(n_items + 1, dtype=torch.bool, device=lists.device)
+        seen[torch.where(head >= 0, head, n_items).reshape(-1).to(torch.int64)] = True
+        out['item_coverage_at_{}'.format(k)] = int(seen[:n_items].sum()) / float(n_items) if n_items else 0.0
+    return out
 
 
 def _finish(users, items, scores, n_users):
@@ -275,6 +315,31 @@ def nearest(queries, table, k=10, metric='cosine', exclude=None, query_rows=None
     return out_rows.cpu().numpy().astype(np.int64), out_scores.cpu().numpy().astype(np.float32)
 
 
+def check_trade_off(trade_off):
+    if isinstance(trade_off, bool) or not isinstance(trade_off, (int, float, np.integer, np.floating)) or not 0.0 <= float(trade_off) <= 1.0:
+        raise ValueError("trade_off must be a number in [0, 1] (got {!r})".format(trade_off))
+    return float(trade_off)
+
+
+def rerank_mmr(items, scores, table, k, trade_off=0.7, metric='cosine'):
+    """Greedy Maximal Marginal Relevance over device pools, one amar_rerank_mmr_f32 launch: `items` int32 [m, P] rows of `table`
+    (the valid entries as a prefix, the rest -1; P <= 64), `scores` float32 [m, P], `table` float32 [n, d].  Step 0 takes the best
+    score; every later step the candidate that maximises trade_off * rel - (1 - trade_off) * max sim(candidate, chosen), rel the
+    scores min-max normalised per pool, ties to the smaller pool position.  Returns the device tensors (items int32 [m, k] in
+    selection order, -1 padded; scores float32 [m, k]: the pool's own scores of the chosen items, -inf padded)."""
+    k = check_k(k)
+    check_metric(metric)
+    trade_off = check_trade_off(trade_off)
+    if items.dim() != 2 or tuple(items.shape) != tuple(scores.shape):
+        raise ValueError("items and scores must be [m, P] tensors of the same shape")
+    if not k <= int(items.shape[1]) <= K_MAX:
+        raise ValueError("the pools must hold between k = {} and {} candidates (got {})".format(k, K_MAX, int(items.shape[1])))
+    check_width(table.shape[1], 'item vectors')
+    table = _as_device_matrix(table, items.device, 'table')
+    return capi.rerank_mmr(items.to(torch.int32).contiguous(), scores.to(torch.float32).contiguous(), table, k,
+                           trade_off=trade_off, metric=metric)
+
+
 def check_ids(ids, lo, hi, what):
     """Host int64 node ids in [lo, hi) (all of them when None), in the caller's order."""
     if ids is None:
@@ -397,3 +462,52 @@ class SimilarSearch:
         if _ON_DEVICE:
             return nb, sc
         return np.where(nb >= 0, nb + n_users, -1), sc
+
+    # -- diversified lists (amar_rerank_mmr_f32, amar_list_diversity_f64) ----------------------------------------------
+    def recommend_diverse(self, trainset, k=10, pool=50, trade_off=0.7, metric='cosine', space=None, users=None, exclude_seen=True):
+        """Diversified top-k: the `pool` best items of every user (`recommend(k=pool)`, kept on the device) re-ranked by Maximal
+        Marginal Relevance over the item vectors of the model's `space` (`rerank_mmr`: trade_off = 1 is `recommend(k)` itself,
+        smaller values weigh dissimilarity to the items already chosen more).  Returns (users int64 [m], items int64 [m, k] node ids
+        in SELECTION order (-1 padded), scores float32 [m, k]: the model's own scores of the chosen items (-inf padded)); inside
+        ``device_lists()`` the device tensors (item rows int32)."""
+        k = check_k(k)
+        check_metric(metric)
+        trade_off = check_trade_off(trade_off)
+        if isinstance(pool, bool) or not isinstance(pool, (int, np.integer)) or not k <= int(pool) <= K_MAX:
+            raise ValueError("pool must be an integer in [k = {}, {}] (got {!r})".format(k, K_MAX, pool))
+        n_users, _ = _sizes(trainset)
+        table = self._item_embeddings(trainset, space)
+        check_width(table.shape[1], 'item vectors')
+        with device_lists():
+            u, items, scores = self.recommend(trainset, k=int(pool), users=users, exclude_seen=exclude_seen)
+        if len(u) == 0:
+            return _empty(k)
+        items, scores = rerank_mmr(items, scores, table, k, trade_off=trade_off, metric=metric)
+        return _finish(u, items, scores, n_users)
+
+    def list_diversity(self, trainset, items, ks=None, metric='cosine', space=None):
+        """Intra-list diversity of lists of items in the model's `space`: `items` [m, K] node ids (host, -1 padded: what `recommend`
+        returns) or, inside ``device_lists()``, int32 item rows on the device; `ks` the cutoffs (K alone by default).  Returns
+        (ild float64 [m, nk]: the mean of 1 - sim over the pairs of items in the first ks[q] ranks, 0 below two items;
+        count int32 [m, nk]: the items in those ranks) — host arrays, device tensors inside ``device_lists()``."""
+        check_metric(metric)
+        n_users, n_items = _sizes(trainset)
+        table = self._item_embeddings(trainset, space)
+        check_width(table.shape[1], 'item vectors')
+        if isinstance(items, torch.Tensor) and items.is_cuda:
+            lists = items.to(torch.int32)
+        else:
+            a = np.asarray(items.cpu() if isinstance(items, torch.Tensor) else items)
+            if a.ndim != 2 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+                raise ValueError("items must be a 2-D [m, K] array of integer node ids")
+            a = a.astype(np.int64)
+            if a.size and (a[a >= 0].size and (a[a >= 0].min() < n_users or a.max() >= n_users + n_items)):
+                raise ValueError("items must be node ids in [{}, {}) or -1".format(n_users, n_users + n_items))
+            lists = torch.from_numpy(np.where(a >= 0, a - n_users, -1).astype(np.int32)).to(table.device)
+        if lists.dim() != 2:
+            raise ValueError("items must be a 2-D [m, K] array")
+        ks, _ = capi.rank_metrics_args(int(lists.shape[1]), [int(lists.shape[1])] if ks is None else ks)
+        ild, count = capi.list_diversity(lists.contiguous(), _as_device_matrix(table, table.device, 'table'), ks, metric=metric)
+        if _ON_DEVICE:
+            return ild, count
+        return ild.cpu().numpy(), count.cpu().numpy()

@@ -123,6 +123,35 @@ def full_ranking_metrics(users, items, test_ratings, ks):
     return out
 
 
+def intra_list_diversity(lists, vectors, ks=None, metric='cosine'):
+    """Intra-list diversity on the host, in float64 (what amar_list_diversity_f64 computes on the device): `lists` [m, K] ROWS of
+    `vectors` [n, d], -1 padded; for every cutoff k of `ks` (K alone by default) the mean over the pairs a < b of valid items in the
+    first k ranks of 1 - sim(a, b), sim the dot product or the cosine (0 against a zero vector); 0 below two items.  Returns
+    (ild float64 [m, nk], count int64 [m, nk])."""
+    if metric not in ('dot', 'cosine'):
+        raise ValueError("metric must be 'dot' or 'cosine' (got {!r})".format(metric))
+    lists = np.asarray(lists, dtype=np.int64)
+    if lists.ndim != 2:
+        raise ValueError("lists must be a 2-D [m, K] array")
+    x = np.asarray(vectors, dtype=np.float64)
+    ks = [int(lists.shape[1])] if ks is None else [int(k) for k in ks]
+    if any(k < 1 or k > lists.shape[1] for k in ks):
+        raise ValueError("every k must lie in [1, {}] (the length of the lists)".format(lists.shape[1]))
+    if metric == 'cosine':
+        sq = (x * x).sum(axis=1)
+        x = x * np.where(sq > 0, 1.0 / np.sqrt(np.where(sq > 0, sq, 1.0)), 0.0)[:, None]
+    ild = np.zeros((len(lists), len(ks)), dtype=np.float64)
+    count = np.zeros((len(lists), len(ks)), dtype=np.int64)
+    for j, row in enumerate(lists):
+        for q, k in enumerate(ks):
+            head = row[:k][row[:k] >= 0]
+            count[j, q] = n = len(head)
+            if n >= 2:
+                gram = x[head] @ x[head].T
+                ild[j, q] = (1.0 - gram[np.triu_indices(n, 1)]).mean()
+    return ild, count
+
+
 def relevant_csr(test_ratings, n_users, n_items):
     """The relevant (label 1) pairs of `test_ratings` as a CSR over users: (ptr int64 [n_users + 1], item ROWS int64, sorted and
     de-duplicated per user) — recommend.exclusion_csr over the liked pairs only."""

@@ -1273,6 +1273,50 @@ int amar_rank_metrics_f64(const int32_t *lists, int64_t m, int32_t K, const int3
                           const int32_t *rel_items, int32_t n_users, const int32_t *ks, int32_t nk, const double *cum_disc,
                           double *workspace, double *out_sums, int64_t *out_counts, amar_stream_t stream);
 
+/* Diversified re-ranking of candidate pools that are already on the device: greedy Maximal Marginal Relevance (MMR), and the
+ * intra-list diversity (ILD) of finished lists.  Both work on the P x P Gram matrix of a list's item vectors, kept on chip.
+ *
+ * T [n_rows, d] (leading dimension ldt) is the item table.  sim(a, b) is amar_nearest_f32's score of row a against row b:
+ *     AMAR_NEAREST_DOT:     sim(a, b) = sum_c T[a, c] * T[b, c]
+ *     AMAR_NEAREST_COSINE:  sim(a, b) = (dot * inv_norm(T[a])) * inv_norm(T[b]),  inv_norm(x) = 1/sqrt(sum x^2), 0 when the sum is 0
+ * (a zero row is similar to nothing, never NaN), products and sums in float32 (v_mfma_f32_16x16x4_f32, one fmaf chain per pair,
+ * features in the fragment order 16t + 4g + r of amar_nearest_f32; the inverse norms come from the Gram matrix's diagonal).
+ *
+ * amar_rerank_mmr_f32: list j of m has the candidates pool_items[j, 0:P] (int32 rows of T, the valid entries as a prefix, the
+ * rest -1; no duplicates among the valid entries: a precondition) with the model's scores pool_scores[j, 0:P] (finite on valid
+ * entries; the pool need not be sorted).
+ *   - relevance, min-max normalised over the list's valid entries: rel_t = (r_t - r_min) / (r_max - r_min); every rel_t is 1 when
+ *     r_max == r_min (one valid entry included).
+ *   - step 0 picks argmax rel_t.  Step s >= 1 picks, among the valid unselected positions t,
+ *         argmax v_t,   v_t = trade_off * rel_t - (1 - trade_off) * max_{u selected} sim(t, u)
+ *     (the maximum runs over the selected set only: no implicit 0).  Ties go to the smaller pool position.  Step 0, and every
+ *     step when 1 - trade_off is 0, compare the scores r_t themselves: the same order, without the rounding of rel.
+ *   - steps beyond the number of valid entries write -1 / -inf.
+ *   - out_items [m, k]: the chosen rows of T in selection order; out_scores [m, k]: their pool_scores, unmodified bits;
+ *     out_mmr [m, k] (optional, may be NULL): the v values, v_0 = trade_off * rel; out_ild [m] (optional, double): the ILD of the
+ *     chosen list as amar_list_diversity_f64 defines it at cutoff k (0 with fewer than 2 items), bit for bit.
+ *   - trade_off = 1: the first k of the pool in (score descending, position ascending) order.
+ * A list's result depends on its own row of the inputs, T, the metric, trade_off and k only: not on m, the other lists or the
+ * grid; a call returns the same bits on every run (no atomics).  One launch, one wavefront per list, no workspace: nothing of size
+ * m x P x P or m x P x d reaches memory.
+ * Limits: 1 <= k <= P <= 64, d % 4 == 0, 4 <= d <= 512, ldt a multiple of 4, T 16-byte aligned; else AMAR_EUNSUPPORTED.  NULL
+ * pointers (out_mmr / out_ild excepted; all but T may be NULL when m == 0), negative sizes, k < 1, P < 1, an unknown metric,
+ * ldt < d, trade_off outside [0, 1] (NaN included): AMAR_EINVAL.  All of these are checked before any device call.
+ * PRECONDITION: every valid item < n_rows; an entry outside 0..n_rows-1 is treated as padding, not read.
+ *
+ * amar_list_diversity_f64: lists [m, K] (int32 rows of T, -1 padded, K <= 64), HOST cutoffs ks[nk] (1 <= ks[q] <= K,
+ * nk <= AMAR_RANK_METRICS_MAX_KS).  out_count [m, nk] (int32): the valid items among the first ks[q] ranks; out_ild [m, nk]
+ * (double): the mean over the pairs a < b of those items of 1 - sim(a, b), 0 where the count is below 2.  The similarities are the
+ * float32 values above; the pairs are summed in float64 in a fixed order (b ascending, a ascending inside b).  Limits and refusals
+ * as above (K in place of P; nk < 1 or a cutoff outside [1, K]: AMAR_EINVAL; nk > AMAR_RANK_METRICS_MAX_KS: AMAR_EUNSUPPORTED). */
+#define AMAR_DIVERSIFY_MAX_P 64
+int amar_rerank_mmr_f32(const int32_t *pool_items, const float *pool_scores, int64_t m, int32_t P, const float *T, int64_t ldt,
+                        int32_t n_rows, int32_t d, int32_t metric, float trade_off, int32_t k, int32_t *out_items,
+                        float *out_scores, float *out_mmr, double *out_ild, amar_stream_t stream);
+int amar_list_diversity_f64(const int32_t *lists, int64_t m, int32_t K, const float *T, int64_t ldt, int32_t n_rows, int32_t d,
+                            int32_t metric, const int32_t *ks, int32_t nk, double *out_ild, int32_t *out_count,
+                            amar_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
