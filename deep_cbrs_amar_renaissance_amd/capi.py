@@ -1257,25 +1257,36 @@ class AdamSlot(ctypes.Structure):
                 ('n', ctypes.c_int64), ('first_block', ctypes.c_int64), ('l2', ctypes.c_float), ('g_groups', ctypes.c_int32)]
 
 
-def adam_slot_table(entries):
-    """entries: [(w, g, m, v, l2)] contiguous fp32 tensors -> (host uint8 tensor holding the slot table, total blocks)."""
-    table = (AdamSlot * len(entries))()
+def _slot_table(struct, entries, name, expected, checked=True):
+    """The slot table of a multi-tensor launch over `struct` (amar_adam_slot, amar_optim_slot, amar_clip_slot: w, g, the struct's state
+    pointers, n, first_block, l2, g_groups).  entries: [(w, g, state arrays, l2)], g a tensor or a DeferredGradient; every parameter takes
+    (n + 1023) // 1024 blocks.  name / expected word the errors; checked: pointers through `_ptr` (on the device, float32).
+    Returns (host uint8 tensor holding the table, total blocks)."""
+    table = (struct * len(entries))()
+    n_arrays = len(struct._fields_) - 6
+    ptr = (lambda t, what: _ptr(t, torch.float32, what)) if checked else (lambda t, what: t.data_ptr())
     block = 0
-    for k, (w, g, m, v, l2) in enumerate(entries):
+    for k, (w, g, arrays, l2) in enumerate(entries):
         groups = 0
         if isinstance(g, DeferredGradient):                          # partial gradients [groups][n] left by dense_bwd(defer=True)
             g, groups = g.partials, g.groups
             if g.numel() != groups * w.numel():
-                raise ValueError("adam_slot_table: deferred gradient of the wrong size")
+                raise ValueError("{}: deferred gradient of the wrong size".format(name))
         elif g.numel() != w.numel():
-            raise ValueError("adam_slot_table: gradient of the wrong size")
-        if not (w.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()) or \
-                not (w.numel() == m.numel() == v.numel()):
-            raise ValueError("adam_slot_table: contiguous tensors of equal size expected")
-        table[k] = AdamSlot(w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), w.numel(), block, float(l2), int(groups))
+            raise ValueError("{}: gradient of the wrong size".format(name))
+        arrays = list(arrays)
+        if len(arrays) > n_arrays or not all(t.is_contiguous() for t in [w, g] + arrays) or not all(a.numel() == w.numel() for a in arrays):
+            raise ValueError("{}: {}".format(name, expected))
+        states = [ptr(a, 'state array') for a in arrays] + [None] * (n_arrays - len(arrays))
+        table[k] = struct(ptr(w, 'w'), ptr(g, 'g'), *states, w.numel(), block, float(l2), int(groups))
         block += (w.numel() + 1023) // 1024
-    host = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).clone()
-    return host, block
+    return torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).clone(), block
+
+
+def adam_slot_table(entries):
+    """entries: [(w, g, m, v, l2)] contiguous fp32 tensors -> (host uint8 tensor holding the slot table, total blocks)."""
+    return _slot_table(AdamSlot, [(w, g, (m, v), l2) for w, g, m, v, l2 in entries], 'adam_slot_table',
+                       'contiguous tensors of equal size expected', checked=False)
 
 
 def adam_multi(table_dev, n_slots, total_blocks, state, beta_1, beta_2, epsilon, reg_scale=0.0, loss_acc=None):
@@ -1336,28 +1347,7 @@ def optim(rule, flags, hyper, w, g, arrays, state, l2=0.0):
 def optim_slot_table(entries):
     """entries: [(w, g, [state arrays], l2)] contiguous fp32 tensors (g: a tensor or a DeferredGradient) -> (host uint8 tensor holding the
     slot table, total blocks): adam_slot_table for amar_optim_multi_f32."""
-    table = (OptimSlot * len(entries))()
-    block = 0
-    for k, (w, g, arrays, l2) in enumerate(entries):
-        groups = 0
-        if isinstance(g, DeferredGradient):                          # partial gradients [groups][n] left by dense_bwd(defer=True)
-            g, groups = g.partials, g.groups
-            if g.numel() != groups * w.numel():
-                raise ValueError("optim_slot_table: deferred gradient of the wrong size")
-        elif g.numel() != w.numel():
-            raise ValueError("optim_slot_table: gradient of the wrong size")
-        arrays = list(arrays)
-        if len(arrays) > 3 or not (w.is_contiguous() and g.is_contiguous()) or \
-                not all(a.is_contiguous() and a.numel() == w.numel() for a in arrays):
-            raise ValueError("optim_slot_table: at most three state arrays, contiguous tensors of equal size expected")
-        for a in arrays:
-            _ptr(a, torch.float32, 'state array')
-        ptrs = [a.data_ptr() for a in arrays] + [None] * (3 - len(arrays))
-        table[k] = OptimSlot(_ptr(w, torch.float32, 'w'), _ptr(g, torch.float32, 'g'), ptrs[0], ptrs[1], ptrs[2], w.numel(), block,
-                             float(l2), int(groups))
-        block += (w.numel() + 1023) // 1024
-    host = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).clone()
-    return host, block
+    return _slot_table(OptimSlot, entries, 'optim_slot_table', 'at most three state arrays, contiguous tensors of equal size expected')
 
 
 def optim_multi(rule, flags, hyper, table_dev, n_slots, total_blocks, state, reg_scale=0.0, loss_acc=None):
@@ -1463,22 +1453,7 @@ class ClipSlot(ctypes.Structure):
 def clip_slot_table(entries):
     """entries: [(w, g, l2)] contiguous fp32 tensors (g: a tensor or a DeferredGradient) -> (host uint8 tensor holding the slot table,
     total blocks): the block partition of adam_slot_table / optim_slot_table over the same parameters."""
-    table = (ClipSlot * len(entries))()
-    block = 0
-    for k, (w, g, l2) in enumerate(entries):
-        groups = 0
-        if isinstance(g, DeferredGradient):
-            g, groups = g.partials, g.groups
-            if g.numel() != groups * w.numel():
-                raise ValueError("clip_slot_table: deferred gradient of the wrong size")
-        elif g.numel() != w.numel():
-            raise ValueError("clip_slot_table: gradient of the wrong size")
-        if not (w.is_contiguous() and g.is_contiguous()):
-            raise ValueError("clip_slot_table: contiguous tensors expected")
-        table[k] = ClipSlot(_ptr(w, torch.float32, 'w'), _ptr(g, torch.float32, 'g'), w.numel(), block, float(l2), int(groups))
-        block += (w.numel() + 1023) // 1024
-    host = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).clone()
-    return host, block
+    return _slot_table(ClipSlot, [(w, g, (), l2) for w, g, l2 in entries], 'clip_slot_table', 'contiguous tensors expected')
 
 
 def finished_gradient(g, n):

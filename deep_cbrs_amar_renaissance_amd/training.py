@@ -883,6 +883,7 @@ class Trainer:
             else:
                 model.rs.build_head(model.gnn.output_dim(), model.gnn.output_dim())
         self.model, self.seq = model, seq
+        self.n_ids = int(seq.adj_matrix.shape[0])                    # how many ids are valid: the range check of every batch of ids
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.device = self.params[0].device
         self._init_optimizer(optimizer, hyper)
@@ -899,6 +900,10 @@ class Trainer:
         self.opt_arrays = {p: self.spec.new_arrays(p) for p in self.params}
         self._opt_state = torch.zeros(capi.OPTIM_STATE_FLOATS, dtype=torch.float32, device=self.device)
         self.capture_count = 0                                       # hipGraph captures so far (a set learning rate must not add one)
+        # the replayed step (`_step`): captured batches by key, the keys past their first batch, the batch buffers last used, those of
+        # the body run eagerly (the last key's), and the loss total of an epoch: first batches on the host, every other on the device
+        self._graphs, self._seen, self._g, self._eager_g = {}, set(), None, {}
+        self._eager_loss, self._loss_sum = 0.0, torch.zeros((), dtype=torch.float32, device=self.device)
         self._lr_state = None                                        # static rate: the launches are those of a trainer without schedules
         if self.spec.schedule is not None:
             self._make_rate_dynamic()
@@ -921,10 +926,9 @@ class Trainer:
         self._lr_state = torch.full((capi.LR_STATE_FLOATS,), base, dtype=torch.float32, device=self.device)
         self._lr_host = torch.zeros(capi.LR_STATE_FLOATS, dtype=torch.float32).pin_memory()
         self._lr_read = None
-        self._init_graph_state()
         self._graphs.clear()
         self._seen.clear()
-        self._eager_sampled, self._eager_batches = {}, {}
+        self._eager_g = {}
 
     def set_learning_rate(self, value):
         """A new base rate from the next batch on: after the first call (which makes the rate dynamic) one write of _lr_state[0]."""
@@ -1132,18 +1136,21 @@ class Trainer:
         """Forward + reverse pass of one batch. Returns (data loss + regularisation loss, {param: gradient}).
         `bert` = (user block, item block) for the hybrid head (None: rows of the resident table).  `sample_weight` [B] and the pair
         of `set_class_weight` weigh the data loss: sum(w x term) / B."""
-        n_nodes = self.seq.adj_matrix.shape[0] if getattr(self, 'seq', None) is not None else None
-        u, i = ids_to_device(u_ids, n_nodes), ids_to_device(i_ids, n_nodes)
+        u, i = ids_to_device(u_ids, self.n_ids), ids_to_device(i_ids, self.n_ids)
         yv = to_device_tensor(np.asarray(y, dtype=np.float32) if not isinstance(y, torch.Tensor) else y)
         wv = self._weights_to_device(sample_weight, u.numel())
         with torch.no_grad():
             terms, grads = self._forward_backward(u, i, yv, bert, w=wv)
-            loss = float(terms.sum().item()) / u.numel()
-            for prm in self.params:
-                l2 = self._l2(prm)
-                if l2:
-                    loss += l2 * float((prm.detach().double() ** 2).sum().item())
-        return loss, grads
+            return self._batch_loss(terms, u.numel()), grads
+
+    def _batch_loss(self, terms, b, with_l2=True):
+        """A batch's loss on the host from its per-pair terms: sum(terms) / b, plus l2 x sum(w^2) of every regularised parameter."""
+        loss = float(terms.sum().item()) / b
+        for prm in self.params if with_l2 else ():
+            l2 = self._l2(prm)
+            if l2:
+                loss += l2 * float((prm.detach().double() ** 2).sum().item())
+        return loss
 
     # -- one batch as a hipGraph ------------------------------------------------------------------------------------
     def _graph_body(self, upload_slots=False):
@@ -1172,7 +1179,7 @@ class Trainer:
         entries = [(w, gr, [a.view(-1) for a in self.opt_arrays[prm]], l2) for prm, (w, gr, l2) in zip(self.params, flat)]
         host, blocks = capi.optim_slot_table(entries)
         g['slot_host'][:host.numel()].copy_(host)                    # pinned buffer allocated before the capture began
-        g['slot_bytes'] = int(host.numel())                          # uploaded ONCE, right after the capture (train_batch_graphed), into a
+        g['slot_bytes'] = int(host.numel())                          # uploaded ONCE, right after the capture (`_step`), into a
         g['keep'] = entries                                          # buffer allocated BEFORE it (memory of the capture's own pool is reused
         #                                                              by the graph's temporaries): the table never changes — the slots point
         #                                                              into tensors of the graph
@@ -1206,17 +1213,84 @@ class Trainer:
         if 'clip_bytes' in g:
             g['clip_dev'][:g['clip_bytes']].copy_(g['clip_host'][:g['clip_bytes']])
 
+    def _new_buffers(self, b, weighted=False, bert_dim=None, staged=False):
+        """The static buffers `g` of the replayed body for batches of b pairs: u, i, the labels (and, weighted, the sample weights behind
+        them) in ONE int32 buffer, the slot tables, with bert_dim the two BERT blocks.  staged: pinned host memory for uploaded
+        batches; batches drawn on the device need none."""
+        dev = self.device
+        slots = 4 if weighted else 3
+        uiy = torch.zeros(slots * b, dtype=torch.int32, device=dev)  # one upload per batch instead of three
+        ui = uiy[:2 * b]                                             # (u and i side by side: one scatter of both towers' input gradients)
+        blocks = [torch.zeros((b, bert_dim), dtype=torch.float32, device=dev) if bert_dim is not None else None for _ in range(2)]
+        g = {'uiy': uiy, 'ui': ui, 'u': ui[:b], 'i': ui[b:], 'y': uiy[2 * b:3 * b].view(torch.float32),
+             'w': uiy[3 * b:].view(torch.float32) if weighted else None, 'ub': blocks[0], 'ib': blocks[1]}
+        self._slot_buffers(g)
+        if staged:
+            # pinned staging for the batch's ids and labels, four sets in turn: the uploads are asynchronous, so the host prepares
+            # batch k + 1 while the device still runs batch k (a pageable copy_ made the host wait for the stream every batch:
+            # 0.13 ms of a 0.52 ms batch at ml1m(s=1))
+            g['stage'], g['turn'] = [], 0
+            for _ in range(4):
+                host = torch.empty(slots * b, dtype=torch.int32).pin_memory()
+                g['stage'].append({'uiy': host, 'u': host[:b], 'i': host[b:2 * b], 'y': host[2 * b:3 * b].view(torch.float32),
+                                   'w': host[3 * b:].view(torch.float32) if weighted else None, 'done': torch.cuda.Event()})
+        return g
+
+    def _step(self, key, b, buffers, fill=None, prologue=None, graph=True, first_batch=None):
+        """One batch through the replayed body under `key`: lookup, first-batch policy, buffers, capture, eager body, replay, step count.
+        The first batch of a key runs eagerly and warms every lazily built buffer — `first_batch()` where given (ids: train_batch,
+        whose loss x b joins `_eager_loss`), else the body itself; the second is captured (graph=False: never; the body runs eagerly
+        on buffers kept in `_eager_g`) and every batch from then on replayed.  buffers(): the static buffers of a new key;
+        fill(g): the batch's inputs into them, ahead of the body; prologue(g): the body's first launches, captured with it."""
+        g = self._captured(key)
+        replay = g is not None
+        if not replay:
+            first = key not in self._seen
+            self._seen.add(key)
+            if first and first_batch is not None:
+                self._eager_loss += first_batch() * b
+                return
+            g = self._g = self._eager_g[key] if key in self._eager_g else buffers()
+            if graph and not first:
+                from deep_cbrs_amar_renaissance_amd.engine import capture_graph
+
+                def body():
+                    with torch.no_grad():
+                        if prologue is not None:
+                            prologue(g)
+                        self._graph_body()
+                g['graph'], _ = capture_graph(body)
+                self.capture_count += 1
+                g['compiled'] = self._loss_spec()
+                self._upload_slots(g)                                # the slot tables of this graph (fixed addresses): once, not per replay
+                self._graphs[key], replay = g, True
+                self._eager_g.pop(key, None)
+            else:
+                self._eager_g = {key: g}                             # (kept for the next eager step of this key)
+        self._g = g
+        if fill is not None:
+            fill(g)
+        self._sync_step()                                            # eager steps happened in between: resynchronise the counter
+        if replay:
+            g['graph'].replay()
+        else:
+            with torch.no_grad():
+                if prologue is not None:
+                    prologue(g)
+                self._graph_body(upload_slots=True)
+        self.t += 1
+        self._dev_t = self.t
+
     def train_batch_graphed(self, u_ids, i_ids, y, bert=None, graph=True, sample_weight=None):
         """One training batch replayed from a hipGraph: the forward, the reverse pass and the Adam update are ~100
         small launches that are otherwise bound by host launch time.  The graph is captured at the second batch of a
-        given size (the first one runs eagerly and warms every lazily built buffer); the running loss stays on the
-        device (`pop_loss_sum`).  Batches of another size run eagerly.  graph=False: the same body, same buffers and uploads, run
+        given size (the first one runs eagerly, through train_batch); the running loss stays on the
+        device (`pop_loss_sum`).  graph=False: the same body, same buffers and uploads, run
         eagerly at every batch instead of captured and replayed (what fit() does under AMAR_TRAIN_GRAPH=0 when the model drops: the
         two then agree bit for bit, masks included).  sample_weight [b]: the batch's weights, uploaded behind the labels into the same
         static buffer; whether a batch carries them, and whether a class pair is in use, is part of the graph's key — their values
         are not."""
         b = len(y)
-        dev = self.device
         with_blocks = bert is not None and bert[0] is not None
         weighted = sample_weight is not None
         if weighted and len(sample_weight) != b:
@@ -1224,94 +1298,39 @@ class Trainer:
         key = (b, with_blocks, self._loss_kind()) + self.dropout_key  # (a compile() with another loss captures anew; so would other dropout state)
         if weighted or self._class_weighted:                          # (an unweighted batch keeps the key it always had)
             key += (('weights', weighted, self._class_weighted),)
-        self._init_graph_state()
-        g = self._captured(key)
-        if g is None:
-            if key not in self._seen:                               # first batch of this shape: eager (real) step
-                self._seen.add(key)
-                self._eager_loss += self.train_batch(u_ids, i_ids, y, bert=bert, sample_weight=sample_weight) * b
-                return
-            g = None if graph else self._eager_batches.get(key)
-        if g is None:
-            d = int(np.asarray(bert[0]).shape[1]) if with_blocks else 0
-            slots = 4 if weighted else 3                              # (the batch's weights ride behind the labels)
-            uiy = torch.zeros(slots * b, dtype=torch.int32, device=dev)  # u, i and the labels in ONE buffer: one upload per batch instead of three
-            ui = uiy[:2 * b]                                          # (u and i side by side: one scatter of both towers' input gradients)
-            g = self._g = {'uiy': uiy, 'ui': ui, 'u': ui[:b], 'i': ui[b:],
-                           'y': uiy[2 * b:3 * b].view(torch.float32),
-                           'w': uiy[3 * b:].view(torch.float32) if weighted else None,
-                           'ub': torch.zeros((b, d), dtype=torch.float32, device=dev) if with_blocks else None,
-                           'ib': torch.zeros((b, d), dtype=torch.float32, device=dev) if with_blocks else None}
-            self._slot_buffers(g)
-            # pinned staging for the batch's ids and labels, four sets in turn: the uploads are asynchronous, so the host prepares
-            # batch k + 1 while the device still runs batch k (a pageable copy_ made the host wait for the stream every batch:
-            # 0.13 ms of a 0.52 ms batch at ml1m(s=1))
-            g['stage'] = []
-            for _ in range(4):
-                host = torch.empty(slots * b, dtype=torch.int32).pin_memory()
-                g['stage'].append({'uiy': host, 'u': host[:b], 'i': host[b:2 * b], 'y': host[2 * b:3 * b].view(torch.float32),
-                                   'w': host[3 * b:].view(torch.float32) if weighted else None, 'done': torch.cuda.Event()})
-            g['turn'] = 0
-            if graph:
-                from deep_cbrs_amar_renaissance_amd.engine import capture_graph
 
-                def body():
-                    with torch.no_grad():
-                        self._graph_body()
-                g['graph'], _ = capture_graph(body)
-                self.capture_count += 1
-                g['compiled'] = self._loss_spec()
-                self._upload_slots(g)                                # the slot tables of this graph (fixed addresses): once, not per replay
-                self._graphs[key] = g
-            else:
-                self._eager_batches = {key: g}
-        self._g = g
-        n_nodes = self.seq.adj_matrix.shape[0] if getattr(self, 'seq', None) is not None else None
-        st = g['stage'][g['turn'] % len(g['stage'])]
-        g['turn'] += 1
-        st['done'].synchronize()                                     # (the uploads that last used this staging set have landed)
-        on_device = [isinstance(src, torch.Tensor) and src.is_cuda for src in (u_ids, i_ids, y, sample_weight)]
-        for name, src, dev_side in (('u', u_ids, on_device[0]), ('i', i_ids, on_device[1])):
-            if dev_side:
-                g[name].copy_(src)
-            else:
-                stage_ids(st[name], src, n_nodes)                    # range check + int32 on the host, into pinned memory
-                if any(on_device):
-                    g[name].copy_(st[name], non_blocking=True)
-        if on_device[2]:
-            g['y'].copy_(y)
-        else:
-            st['y'].numpy()[...] = y.numpy() if isinstance(y, torch.Tensor) else np.asarray(y, dtype=np.float32)
-            if any(on_device):
-                g['y'].copy_(st['y'], non_blocking=True)
-        if weighted:
-            if on_device[3]:
-                g['w'].copy_(sample_weight.reshape(-1))
-            else:
-                st['w'].numpy()[...] = sample_weight.numpy() if isinstance(sample_weight, torch.Tensor) else np.asarray(sample_weight, dtype=np.float32)
-                if any(on_device):
-                    g['w'].copy_(st['w'], non_blocking=True)
-        if not any(on_device):
-            g['uiy'].copy_(st['uiy'], non_blocking=True)             # ids and labels of the batch: one asynchronous upload
-        st['done'].record()
-        if with_blocks:
-            g['ub'].copy_(to_device_tensor(bert[0]))
-            g['ib'].copy_(to_device_tensor(bert[1]))
-        self._sync_step()                                            # eager steps happened in between: resynchronise the counter
-        if 'graph' in g:
-            g['graph'].replay()
-        else:
-            with torch.no_grad():
-                self._graph_body(upload_slots=True)
-        self.t += 1
-        self._dev_t = self.t
+        def fill(g):
+            """Every field from the device, from pinned staging, or — all on the host — staged and sent as ONE upload."""
+            st = g['stage'][g['turn'] % len(g['stage'])]
+            g['turn'] += 1
+            st['done'].synchronize()                                 # (the uploads that last used this staging set have landed)
+            fields = [('u', u_ids, self._stage_ids), ('i', i_ids, self._stage_ids), ('y', y, self._stage_floats)]
+            if weighted:
+                fields.append(('w', sample_weight, self._stage_floats))
+            on_device = [isinstance(src, torch.Tensor) and src.is_cuda for _, src, _ in fields]
+            mixed = any(on_device)
+            for (name, src, to_host), dev_side in zip(fields, on_device):
+                if dev_side:
+                    g[name].copy_(src.reshape(-1))
+                else:
+                    to_host(st[name], src)                           # (ids: range check + int32 on the host, into pinned memory)
+                    if mixed:
+                        g[name].copy_(st[name], non_blocking=True)
+            if not mixed:
+                g['uiy'].copy_(st['uiy'], non_blocking=True)         # ids and labels of the batch: one asynchronous upload
+            st['done'].record()
+            if with_blocks:
+                g['ub'].copy_(to_device_tensor(bert[0]))
+                g['ib'].copy_(to_device_tensor(bert[1]))
+        self._step(key, b, lambda: self._new_buffers(b, weighted, int(np.asarray(bert[0]).shape[1]) if with_blocks else None, staged=True),
+                   fill=fill, graph=graph, first_batch=lambda: self.train_batch(u_ids, i_ids, y, bert=bert, sample_weight=sample_weight))
 
-    def _init_graph_state(self):
-        if not hasattr(self, '_graphs'):
-            dev = self.device
-            self._graphs, self._seen, self._eager_loss = {}, set(), 0.0
-            self._eager_sampled, self._eager_batches = {}, {}
-            self._loss_sum = torch.zeros((), dtype=torch.float32, device=dev)
+    def _stage_ids(self, dst_host, ids):
+        stage_ids(dst_host, ids, self.n_ids)
+
+    @staticmethod
+    def _stage_floats(dst_host, values):
+        dst_host.numpy()[...] = values.numpy() if isinstance(values, torch.Tensor) else np.asarray(values, dtype=np.float32)
 
     # -- batches drawn on the device (BPR: data/datasets.py:UserItemGraphPosNegSample, UserItemGraphTriplets) --------------------
     def sampler_for(self, sequence):
@@ -1321,10 +1340,9 @@ class Trainer:
         kind = TripletSampler if isinstance(sequence, UserItemGraphTriplets) else DeviceSampler
         sampler = getattr(self, '_sampler', None)
         if sampler is None or type(sampler) is not kind or not sampler.matches(sequence):
-            if hasattr(self, '_graphs'):
-                self._graphs = {k: v for k, v in self._graphs.items() if k[0] != 'sampled'}
-                self._seen = {k for k in self._seen if k[0] != 'sampled'}
-                self._eager_sampled = {}
+            self._graphs = {k: v for k, v in self._graphs.items() if k[0] != 'sampled'}
+            self._seen = {k for k in self._seen if k[0] != 'sampled'}
+            self._eager_g = {k: v for k, v in self._eager_g.items() if k[0] != 'sampled'}
             sampler = self._sampler = kind(sequence, self.device)
         return sampler
 
@@ -1336,56 +1354,13 @@ class Trainer:
         if self.hybrid:
             raise NotImplementedError("the BPR sample Sequence carries no BERT rows: hybrid models do not train on it")
         b = 2 * sampler.h
-        key = ('sampled', b, self._loss_kind(), sampler.serial) + self.dropout_key
-        self._init_graph_state()
-        g = self._captured(key)
-        if g is None:
-            g = self._eager_sampled.get(key) if key in self._eager_sampled else self._sampled_buffers(sampler, b)
-            self._g = g
-            if graph and key in self._seen:
-                from deep_cbrs_amar_renaissance_amd.engine import capture_graph
-
-                def body():
-                    with torch.no_grad():
-                        sampler.sample(g['u'], g['i'], g['y'])
-                        self._graph_body()
-                self._sync_step()
-                g['graph'], _ = capture_graph(body)
-                self.capture_count += 1
-                g['compiled'] = self._loss_spec()
-                self._upload_slots(g)
-                self._graphs[key] = g
-            else:
-                self._seen.add(key)
-                self._eager_sampled = {key: g}                       # (buffers of the eager steps, kept for the next one)
-                self._sync_step()
-                with torch.no_grad():
-                    sampler.sample(g['u'], g['i'], g['y'])
-                    self._graph_body(upload_slots=True)
-                self._advanced()
-                return
-        self._g = g
-        self._sync_step()
-        g['graph'].replay()
-        self._advanced()
-
-    def _sampled_buffers(self, sampler, b):
-        dev = self.device
-        uiy = torch.zeros(3 * b, dtype=torch.int32, device=dev)
-        ui = uiy[:2 * b]
-        g = self._g = {'uiy': uiy, 'ui': ui, 'u': ui[:b], 'i': ui[b:], 'y': uiy[2 * b:].view(torch.float32), 'ub': None, 'ib': None,
-                       'sampler': sampler}
-        self._slot_buffers(g)
-        return g
+        self._step(('sampled', b, self._loss_kind(), sampler.serial) + self.dropout_key, b, lambda: dict(self._new_buffers(b), sampler=sampler),
+                   prologue=lambda g: sampler.sample(g['u'], g['i'], g['y']), graph=graph)
 
     def _sync_step(self):
         if self.spec.adam and self._dev_t != self.t:                 # host steps happened in between (apply_gradients under a static
             self._opt_state[0] = float(self.t)                       # rate): resynchronise the counter; the other rules count on the
             #                                                          device in both paths
-
-    def _advanced(self):
-        self.t += 1
-        self._dev_t = self.t
 
     def _all_tapes(self):
         """Every tape of the trainer that owns a fused reverse pass (Dense stacks of the head, convolution stacks)."""
@@ -1395,8 +1370,6 @@ class Trainer:
 
     def pop_loss_sum(self):
         """Sum over the batches since the last call of (batch loss x batch size); one host synchronisation."""
-        if not hasattr(self, '_graphs'):
-            return 0.0
         block = getattr(self, '_counters', None)
         if block is not None:                                        # the metric counters come over under the same synchronisation
             self._counters_host.copy_(block, non_blocking=True)
@@ -1525,7 +1498,7 @@ class HeadTrainer(Trainer):
         self.device = self.params[0].device
         self._init_optimizer(optimizer, hyper)
         self.head = _HybridHead(model) if self.hybrid else _BasicHead(model)
-        self.tables = None
+        self.tables = self.n_ids = None                              # (n_ids: how many ids are valid, once there are tables)
 
     # -- batches as ids against tables kept on the device (round 4) ---------------------------------------------------------------
     def set_tables(self, tables):
@@ -1534,7 +1507,7 @@ class HeadTrainer(Trainer):
         (Trainer.train_batch_graphed) instead of on the host and uploaded every batch — 25 epochs of HybridCBRS at ML-1M size took
         35 s that way, more than any graph model."""
         self.tables = [to_device_tensor(np.ascontiguousarray(t, dtype=np.float32)) for t in tables]
-        self.seq = types.SimpleNamespace(adj_matrix=types.SimpleNamespace(shape=(min(int(t.shape[0]) for t in self.tables),)))   # (range check of the ids)
+        self.n_ids = min(int(t.shape[0]) for t in self.tables)       # (an id is a row of every table)
 
     def _rows_of(self, u, i):
         out = []
@@ -1545,10 +1518,9 @@ class HeadTrainer(Trainer):
                 out.append(rows)
         return out                                                   # (user, item) per table: [gu, gi] or [gu, gi, bu, bi]
 
-    def _forward_backward(self, u, i, yv, rows=None, ui=None, w=None):
-        """Trainer's per-batch core for ids: gather the rows, head forward, BCE, head reverse pass (the inputs are constants)."""
-        r = self._rows_of(u, i)
-        b = u.numel()
+    def _head_step(self, r, yv, w):
+        """Head forward, loss and head reverse pass on the rows r (the inputs are constants): (per-pair terms, {param: gradient})."""
+        b = r[0].shape[0]
         p = self.head.forward(r[0], r[1], (r[2], r[3]) if self.hybrid else None)
         dz = torch.empty((b, 1), dtype=torch.float32, device=p.device)
         terms = torch.empty(b, dtype=torch.float32, device=p.device)
@@ -1557,6 +1529,10 @@ class HeadTrainer(Trainer):
         self.head.backward(dz, grads, need_input_grad=False)
         return terms, grads
 
+    def _forward_backward(self, u, i, yv, rows=None, ui=None, w=None):
+        """Trainer's per-batch core for ids: gather the rows, then the head step."""
+        return self._head_step(self._rows_of(u, i), yv, w)
+
     def loss_and_grads(self, blocks, y, sample_weight=None):
         """blocks = (user rows, item rows) or (user graph, item graph, user BERT, item BERT), each [B, D]."""
         rows = [to_device_tensor(b) for b in blocks]
@@ -1564,31 +1540,15 @@ class HeadTrainer(Trainer):
         b = rows[0].shape[0]
         wv = self._weights_to_device(sample_weight, b)
         with torch.no_grad():
-            p = self.head.forward(rows[0], rows[1], (rows[2], rows[3]) if self.hybrid else None)
-            dz = torch.empty((b, 1), dtype=torch.float32, device=p.device)
-            terms = torch.empty(b, dtype=torch.float32, device=p.device)
-            self._loss_grad(p, yv, dz, terms, wv)
-            grads = {}
-            self.head.backward(dz, grads, need_input_grad=False)
-            loss = float(terms.sum().item()) / b
-        return loss, grads
+            terms, grads = self._head_step(rows, yv, wv)
+            # a finding kept as it is: on blocks the reported loss leaves out the L2 term that the ids paths (below, Trainer) include
+            return self._batch_loss(terms, b, with_l2=False), grads
 
     def train_batch(self, *args, bert=None, sample_weight=None):
         """train_batch(blocks, y): the rows themselves; train_batch(u_ids, i_ids, y): ids against `set_tables` (eager: the first
         batch of a shape before Trainer.train_batch_graphed captures)."""
         if len(args) == 3:
-            u_ids, i_ids, y = args
-            n = self.seq.adj_matrix.shape[0]
-            u, i = ids_to_device(u_ids, n), ids_to_device(i_ids, n)
-            yv = to_device_tensor(np.asarray(y, dtype=np.float32) if not isinstance(y, torch.Tensor) else y)
-            wv = self._weights_to_device(sample_weight, u.numel())
-            with torch.no_grad():
-                terms, grads = self._forward_backward(u, i, yv, w=wv)
-                loss = float(terms.sum().item()) / u.numel()
-                for prm in self.params:
-                    l2 = self._l2(prm)
-                    if l2:
-                        loss += l2 * float((prm.detach().double() ** 2).sum().item())
+            loss, grads = Trainer.loss_and_grads(self, *args, sample_weight=sample_weight)
         else:
             loss, grads = self.loss_and_grads(*args, sample_weight=sample_weight)
         self.apply_gradients(grads)
@@ -1777,6 +1737,68 @@ def _split_batch(batch):
     return batch[0], batch[1], (batch[2] if len(batch) > 2 else None)
 
 
+def _ids_step(trainer, read, replayed_body, graph):
+    """fit()'s step for batches of ids, against the graph or against resident tables: read(b) -> (u, i, y, w, bert).  replayed_body:
+    through train_batch_graphed (the loss stays on the device), else train_batch.  A step returns (pairs, loss x pairs on the host)."""
+    def step(b):
+        u, i, y, w, bert = read(b)
+        if replayed_body:
+            trainer.train_batch_graphed(u, i, y, bert=bert, graph=graph, sample_weight=w)
+            return len(y), 0.0
+        return len(y), trainer.train_batch(u, i, y, bert=bert, sample_weight=w) * len(y)
+    return step
+
+
+def _blocks_step(trainer, sequence):
+    """fit()'s step for a HeadTrainer on the Sequence's own blocks of rows (AMAR_RESIDENT_ROWS=0, or a Sequence without a table)."""
+    def step(b):
+        blocks, y, w = _split_batch(sequence[b])
+        return len(y), trainer.train_batch(blocks, y, sample_weight=w) * len(y)
+    return step
+
+
+def _sampled_step(trainer, sampler, graph):
+    """fit()'s step for batches drawn on the device: 2 h pairs each; the Sequence's host stream is not read."""
+    pairs = 2 * sampler.h
+
+    def step(b):
+        trainer.train_sampled(sampler, graph=graph)
+        return pairs, 0.0
+    return step
+
+
+def _run_epochs(trainer, sequence, hooks, history, step, device_loss, reshuffle, initial_epoch, epochs, verbose):
+    """fit()'s one epoch loop: step(b) for every batch of every epoch, and around it the hooks, the epoch's loss (device_loss: the total
+    the replayed body keeps on the device, else the sum of what the steps return), history, validation, stop.  reshuffle: the Sequence's
+    on_epoch_end() after every epoch."""
+    if hooks is not None:
+        hooks.train_begin()
+    for epoch in range(int(initial_epoch), int(epochs)):
+        total, count = 0.0, 0
+        if hooks is not None:
+            hooks.epoch_begin(epoch)
+        for b in range(len(sequence)):
+            if hooks is not None and hooks.batch_begin:
+                hooks.on_batch_begin(b)
+            pairs, loss = step(b)
+            count += pairs
+            total += loss
+            if hooks is not None and hooks.batch_end:
+                hooks.on_batch_end(b)
+        if device_loss:
+            total = trainer.pop_loss_sum()
+            trainer.touch_parameters()
+        history.epoch(total / max(count, 1), epoch, epochs, verbose)
+        stop = hooks is not None and hooks.epoch_end(epoch, verbose)
+        if reshuffle and hasattr(sequence, 'on_epoch_end'):
+            sequence.on_epoch_end()
+        if stop:
+            break
+    if hooks is not None:
+        hooks.train_end()
+    return history.values
+
+
 def fit(model, sequence, epochs=1, callbacks=None, verbose=True, validation_data=None, validation_freq=1, validation_ranking=None,
         initial_epoch=0, class_weight=None, workers=None):
     """Keras-style ``fit`` over a batch Sequence: epochs ``initial_epoch`` .. ``epochs - 1``, ``on_epoch_end`` reshuffles
@@ -1789,7 +1811,10 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, validation_data
     batch loss = sum_j w_j l_j / B, epoch loss = sum over all pairs / N; the L2 term and the compiled metrics stay unweighted, and
     validation never applies class_weight.  It holds for this call only.  BPR training refuses both.  ``workers`` (the loader
     threads of Keras' fit, passed by the experiment) is accepted and not read: batches are taken in the loop.  Any other keyword
-    is a TypeError."""
+    is a TypeError.
+
+    What differs between models and Sequences is the step chosen here (`_ids_step`, `_blocks_step`, `_sampled_step`); the epochs
+    around it are `_run_epochs`.  AMAR_TRAIN_GRAPH=0: eager batches instead of replayed ones."""
     if validation_ranking is not None and not hasattr(model, 'recommend'):
         raise NotImplementedError("{} has no recommend(): validation_ranking cannot rank with it".format(type(model).__name__))
     if class_weight is not None and not isinstance(class_weight, tuple):
@@ -1797,19 +1822,20 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, validation_data
         labels = rows[:, 2] if isinstance(rows, np.ndarray) and rows.ndim == 2 and rows.shape[1] >= 3 else None
         class_weight = resolve_class_weight(class_weight, labels)
     model.stop_training = False
-    val = (callbacks, validation_data, validation_freq, validation_ranking)
+    from deep_cbrs_amar_renaissance_amd.data.datasets import (HybridUserItemEmbeddings, UserItemEmbeddings, UserItemGraphPosNegSample,
+                                                              UserItemGraphTriplets)
     spec = OptimizerSpec(getattr(model, 'optimizer', None))
-    hp = {'optimizer': spec}
+    use_graph = os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
+    sampled = hasattr(model, 'gnn') and isinstance(sequence, (UserItemGraphPosNegSample, UserItemGraphTriplets))
     if not hasattr(model, 'gnn'):                              # BasicRS / HybridCBRS on pre-computed rows: head-only training
         trainer = _cached_trainer(model, spec)
         if trainer is None:
             if not model.built and len(sequence):
                 model(sequence[0][0])                          # one forward call builds every weight (as Keras does)
-            trainer = model._trainer = HeadTrainer(model, **hp)
+            trainer = model._trainer = HeadTrainer(model, optimizer=spec)
         # the reference's Sequences of pre-computed rows (datasets.py:55-80) gather them on the host from one (BasicRS) or two
         # (HybridCBRS) tables indexed by node id: the tables go to the device once and the batches are read as ids
         # (AMAR_RESIDENT_ROWS=0: the batches as they come, eager)
-        from deep_cbrs_amar_renaissance_amd.data.datasets import HybridUserItemEmbeddings, UserItemEmbeddings
         tables = None
         if os.environ.get('AMAR_RESIDENT_ROWS', '1') != '0':
             if type(sequence) is UserItemEmbeddings and not trainer.hybrid:
@@ -1823,135 +1849,52 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, validation_data
             if src is None or len(src) != len(tables) or any(a is not b for a, b in zip(src, tables)):
                 trainer.set_tables(tables)
                 trainer._table_sources = tables
-        use_graph = tables is not None and os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
-        trainer.set_class_weight(class_weight)                   # (None: off — the pair of an earlier fit() does not linger)
-        history = _History(trainer)
-        hooks = _fit_hooks(model, history, *val)
-        if hooks is not None:
-            hooks.train_begin()
-        for epoch in range(int(initial_epoch), int(epochs)):
-            total, count = 0.0, 0
-            if hooks is not None:
-                hooks.epoch_begin(epoch)
-            for b in range(len(sequence)):
-                if hooks is not None and hooks.batch_begin:
-                    hooks.on_batch_begin(b)
-                if tables is not None:
-                    r = sequence._batch_ratings(b)
-                    u, i, y = r[:, 0], r[:, 1], r[:, 2]
-                    w = sequence._batch_weights(b)
-                    if use_graph:
-                        trainer.train_batch_graphed(u, i, y, sample_weight=w)
-                    else:
-                        total += trainer.train_batch(u, i, y, sample_weight=w) * len(y)
-                else:
-                    blocks, y, w = _split_batch(sequence[b])
-                    total += trainer.train_batch(blocks, y, sample_weight=w) * len(y)
-                count += len(y)
-                if hooks is not None and hooks.batch_end:
-                    hooks.on_batch_end(b)
-            if use_graph:
-                total = trainer.pop_loss_sum()
-                trainer.touch_parameters()
-            history.epoch(total / max(count, 1), epoch, epochs, verbose)
-            stop = hooks is not None and hooks.epoch_end(epoch, verbose)
-            if hasattr(sequence, 'on_epoch_end'):
-                sequence.on_epoch_end()
-            if stop:
-                break
-        if hooks is not None:
-            hooks.train_end()
-        return history.values
-    # Hybrid batches of the reference's own Sequence (datasets.py:95-123 here, 112-115 there) carry, besides the ids, the BERT rows of the
-    # batch's users and items — gathered on the host from ONE table indexed by node id and uploaded every batch (6 MB at batch 1 024).
-    # That table is registered once on the device instead and the batches are read as ids only: the same rows, gathered there
-    # (AMAR_RESIDENT_BERT=0: the batches as they come).  A replayed hybrid batch at ml1m(s=1): 0.41 against 0.71 ms.
-    from deep_cbrs_amar_renaissance_amd.data.datasets import UserItemGraphPosNegSample, UserItemGraphTriplets
-    if isinstance(sequence, (UserItemGraphPosNegSample, UserItemGraphTriplets)):
+
+            def read(b):
+                r = sequence._batch_ratings(b)
+                return r[:, 0], r[:, 1], r[:, 2], sequence._batch_weights(b), None
+            step, device_loss = _ids_step(trainer, read, use_graph, True), use_graph
+        else:
+            step, device_loss = _blocks_step(trainer, sequence), False
+    elif sampled:
+        # a BPR sample Sequence: its lists go to the device once and every batch is drawn there (amar_bpr_sample_i32 /
+        # amar_bpr_sample_triplets_i32), inside the replayed training graph (AMAR_TRAIN_GRAPH=0: the same steps eagerly, the same ids)
         if class_weight is not None:
             raise ValueError("class_weight cannot weigh BPR training: the batches are drawn on the device and have no per-pair label")
-        return _fit_sampled(model, sequence, epochs, verbose, hp, val, initial_epoch)
-    ids_only = model.resident_ids(sequence) if hasattr(model, 'resident_ids') else None
-    trainer = _cached_trainer(model, spec)
-    if trainer is None:
-        if hasattr(model.rs, 'dense1a') and not model.rs.built and len(sequence):
-            first = sequence[0][0]
-            if len(first) >= 4 and first[2] is not None:
-                hp['bert_dim'] = int(np.asarray(first[2]).shape[1])
-        trainer = model._trainer = Trainer(model, **hp)
-    use_graph = os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
-    same_body = not use_graph and trainer.dropout_step is not None      # a model that drops: the replayed body, run eagerly (same bits)
-    if trainer._loss_kind() == 'bpr' and class_weight is not None:     # (a weighted batch under BPR is refused where it is read)
-        raise ValueError("BPRLoss has no per-pair label or term: it takes no class_weight and no weighted Sequence")
+        if getattr(sequence, 'sample_weight', None) is not None:
+            raise ValueError("the BPR sample Sequence draws its batches on the device: it carries no sample weights")
+        trainer = _cached_trainer(model, spec)
+        if trainer is None:
+            trainer = model._trainer = Trainer(model, optimizer=spec)
+    else:
+        # Hybrid batches of the reference's own Sequence (datasets.py:95-123 here, 112-115 there) carry, besides the ids, the BERT rows of
+        # the batch's users and items — gathered on the host from ONE table indexed by node id and uploaded every batch (6 MB at batch
+        # 1 024).  That table is registered once on the device instead and the batches are read as ids only: the same rows, gathered
+        # there (AMAR_RESIDENT_BERT=0: the batches as they come).  A replayed hybrid batch at ml1m(s=1): 0.41 against 0.71 ms.
+        ids_only = model.resident_ids(sequence) if hasattr(model, 'resident_ids') else None
+        trainer = _cached_trainer(model, spec)
+        if trainer is None:
+            hp = {}
+            if hasattr(model.rs, 'dense1a') and not model.rs.built and len(sequence):
+                first = sequence[0][0]
+                if len(first) >= 4 and first[2] is not None:
+                    hp['bert_dim'] = int(np.asarray(first[2]).shape[1])
+            trainer = model._trainer = Trainer(model, optimizer=spec, **hp)
+        if trainer._loss_kind() == 'bpr' and class_weight is not None:     # (a weighted batch under BPR is refused where it is read)
+            raise ValueError("BPRLoss has no per-pair label or term: it takes no class_weight and no weighted Sequence")
+        source = ids_only if ids_only is not None else sequence
+
+        def read(b):
+            inputs, y, w = _split_batch(source[b])
+            # hybrid batches carry the BERT blocks (datasets.py:112-115)
+            return inputs[0], inputs[1], y, w, ((inputs[2], inputs[3]) if len(inputs) >= 4 else None)
+        # a model that drops runs the replayed body under AMAR_TRAIN_GRAPH=0 too, eagerly (same bits, masks included)
+        device_loss = use_graph or trainer.dropout_step is not None
+        step = _ids_step(trainer, read, device_loss, use_graph)
     trainer.set_class_weight(class_weight)                       # (None: off — the pair of an earlier fit() does not linger)
+    if sampled:
+        step, device_loss = _sampled_step(trainer, trainer.sampler_for(sequence), use_graph), True
     history = _History(trainer)
-    hooks = _fit_hooks(model, history, *val)
-    if hooks is not None:
-        hooks.train_begin()
-    for epoch in range(int(initial_epoch), int(epochs)):
-        total, count = 0.0, 0
-        if hooks is not None:
-            hooks.epoch_begin(epoch)
-        for b in range(len(sequence)):
-            if hooks is not None and hooks.batch_begin:
-                hooks.on_batch_begin(b)
-            inputs, y, w = _split_batch((ids_only if ids_only is not None else sequence)[b])
-            u, i = inputs[0], inputs[1]
-            bert = (inputs[2], inputs[3]) if len(inputs) >= 4 else None     # hybrid batches carry the BERT blocks (datasets.py:112-115)
-            if use_graph or same_body:
-                trainer.train_batch_graphed(u, i, y, bert=bert, graph=use_graph, sample_weight=w)
-            else:
-                total += trainer.train_batch(u, i, y, bert=bert, sample_weight=w) * len(y)
-            count += len(y)
-            if hooks is not None and hooks.batch_end:
-                hooks.on_batch_end(b)
-        if use_graph or same_body:
-            total = trainer.pop_loss_sum()
-            trainer.touch_parameters()
-        history.epoch(total / max(count, 1), epoch, epochs, verbose)
-        stop = hooks is not None and hooks.epoch_end(epoch, verbose)
-        if hasattr(sequence, 'on_epoch_end'):
-            sequence.on_epoch_end()
-        if stop:
-            break
-    if hooks is not None:
-        hooks.train_end()
-    return history.values
-
-
-def _fit_sampled(model, sequence, epochs, verbose, hp, val=(None, None, 1, None), initial_epoch=0):
-    """fit() on a BPR sample Sequence (UserItemGraphPosNegSample or UserItemGraphTriplets): its lists go to the device once and every
-    batch is drawn there (amar_bpr_sample_i32 / amar_bpr_sample_triplets_i32), inside
-    the replayed training graph (AMAR_TRAIN_GRAPH=0: the same steps eagerly, the same ids).  len(sequence) steps per epoch; the host
-    stream of __getitem__ is not read."""
-    if getattr(sequence, 'sample_weight', None) is not None:
-        raise ValueError("the BPR sample Sequence draws its batches on the device: it carries no sample weights")
-    trainer = _cached_trainer(model, hp['optimizer'])
-    if trainer is None:
-        trainer = model._trainer = Trainer(model, **hp)
-    trainer.set_class_weight(None)
-    sampler = trainer.sampler_for(sequence)
-    use_graph = os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
-    history = _History(trainer)
-    hooks = _fit_hooks(model, history, *val)
-    if hooks is not None:
-        hooks.train_begin()
-    for epoch in range(int(initial_epoch), int(epochs)):
-        count = 0
-        if hooks is not None:
-            hooks.epoch_begin(epoch)
-        for b in range(len(sequence)):
-            if hooks is not None and hooks.batch_begin:
-                hooks.on_batch_begin(b)
-            trainer.train_sampled(sampler, graph=use_graph)
-            count += 2 * sampler.h
-            if hooks is not None and hooks.batch_end:
-                hooks.on_batch_end(b)
-        total = trainer.pop_loss_sum()
-        trainer.touch_parameters()
-        history.epoch(total / max(count, 1), epoch, epochs, verbose)
-        if hooks is not None and hooks.epoch_end(epoch, verbose):
-            break
-    if hooks is not None:
-        hooks.train_end()
-    return history.values
+    hooks = _fit_hooks(model, history, callbacks, validation_data, validation_freq, validation_ranking)
+    # (the sampled loop never calls on_epoch_end: the host stream of the BPR Sequences must not advance)
+    return _run_epochs(trainer, sequence, hooks, history, step, device_loss, not sampled, initial_epoch, epochs, verbose)

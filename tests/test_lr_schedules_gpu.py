@@ -1,6 +1,6 @@
 """GPU: learning-rate schedules on the device — amar_lr_rates_f32 against the float64 formulas of tests/lr_schedule_ref.py, the two
 advance entry points that evaluate a schedule (amar_adam_advance_lr_f32, amar_optim_advance_lr_f32) against the ones that take the rate
-as an argument, the three training loops under a schedule, a rate set between replays (LearningRateScheduler, ReduceLROnPlateau) and one
+as an argument, fit()'s three batch steps under a schedule, a rate set between replays (LearningRateScheduler, ReduceLROnPlateau) and one
 experiment through the public surface (pytest -m gpu).
 
 The model-level tests train the tiny synthetic graph and CFG of tests/test_optimizers_gpu.py."""
