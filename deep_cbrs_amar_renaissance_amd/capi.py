@@ -123,6 +123,7 @@ SIGNATURES = {
     'amar_grad_clip_workspace_floats': (ctypes.c_int64, [_I32, _I64]),
     'amar_grad_clip_f32': (ctypes.c_int, [_I32, _F32, _P, _I32, _I64, _P, _P, _F32, _P, _P]),
     'amar_bpr_grad_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P]),
+    'amar_group_loss_grad_f32': (ctypes.c_int, [_I32, _F32, _P, _I64, _P, _P, _I64, _I32, _P]),
     'amar_bpr_sample_i32': (ctypes.c_int, [_P, _P, _P, _P, _I32, ctypes.c_uint64, _P, _I32, _I32, _P, _P, _P, _P]),
     'amar_bpr_sample_triplets_i32': (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, ctypes.c_uint64, _P, _I32, _I32, _P, _P,
                                                     _P, _P]),
@@ -2021,6 +2022,25 @@ def bpr_grad(p, dz, loss_terms):
     code = load().amar_bpr_grad_f32(_ptr(p, torch.float32, 'p'), _ld(p, 'p') if p.dim() == 2 else 1, _ptr(dz, torch.float32, 'dz'),
                                     _ptr(loss_terms, torch.float32, 'loss_terms'), B, _stream())
     _check(code, 'amar_bpr_grad_f32')
+
+
+# include/amar_hip.h: AMAR_GROUP_*
+GROUP_SOFTMAX, GROUP_HARDEST, GROUP_MARGIN = range(3)
+
+
+def group_loss_grad(kind, hyper, p, dz, loss_terms, n_negatives=1):
+    """Listwise loss terms and d(loss)/d(logit) on the triplet layout (amar_group_loss_grad_f32): kind one of GROUP_*, hyper the
+    temperature (GROUP_SOFTMAX) or the margin (GROUP_MARGIN), p the probability column ([B] or [B, 1]) whose h = B // 2 triples
+    split into groups of n_negatives; dz [B, 1] / loss_terms [B] contiguous."""
+    B = p.shape[0]
+    if dz.numel() != B or loss_terms.numel() != B or not dz.is_contiguous() or not loss_terms.is_contiguous():
+        raise ValueError("group_loss_grad: p [B] or [B, 1], dz and loss_terms of B contiguous floats expected")
+    K = int(n_negatives)
+    if K < 1 or (B // 2) % K:
+        raise ValueError("group_loss_grad: {} triples do not split into groups of n_negatives = {}".format(B // 2, n_negatives))
+    code = load().amar_group_loss_grad_f32(int(kind), float(hyper), _ptr(p, torch.float32, 'p'), _ld(p, 'p') if p.dim() == 2 else 1,
+                                           _ptr(dz, torch.float32, 'dz'), _ptr(loss_terms, torch.float32, 'loss_terms'), B, K, _stream())
+    _check(code, 'amar_group_loss_grad_f32')
 
 
 # include/amar_hip.h: AMAR_LOSS_*

@@ -35,6 +35,105 @@ __global__ __launch_bounds__(256) void bpr_grad_kernel(const float *__restrict__
     }
 }
 
+// Listwise losses on the triplet layout (include/amar_hip.h: amar_group_loss_grad_f32).  A group occupies a segment of W lanes of
+// one wavefront (W = the next power of two >= K for K <= 32: 64 / W groups per wavefront; W = 64 above: lane l takes the negatives
+// k = l, l + 64, ... in ascending order).  Every reduction is that lane-local ascending pass followed by an xor butterfly inside the
+// segment: both partners of a step add the same two floats, so all W lanes hold the same bits and those bits depend on the group's
+// own floats only.  All 64 lanes stay active through the butterflies (a lane without a group carries neutral values and stores
+// nothing); the loop over groups is uniform over the workgroup.  The launch moves a few thousand floats: a group's negatives beyond
+// the first 64 are read again from L1 in the later passes, nothing is staged.
+template <int W>
+__device__ __forceinline__ float seg_sum(float x) {
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void group_loss_kernel(int32_t kind, float hyper, const float *__restrict__ p, int64_t ldp,
+                                                         float *__restrict__ dz, float *__restrict__ terms, int64_t B, int64_t h,
+                                                         int32_t K, int64_t G) {
+    constexpr int GW = 64 / W;                                        // groups per wavefront
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & (W - 1);
+    const float scale = G ? (float)B / (float)G : 0.f, inv_g = G ? 1.f / (float)G : 0.f, fk = (float)K;
+    const int64_t per_block = 4 * GW;
+    for (int64_t base = (int64_t)blockIdx.x * per_block; base < G; base += (int64_t)gridDim.x * per_block) {
+        const int64_t g = base + wave * GW + lane / W;
+        const bool live = g < G;
+        const int64_t row0 = live ? g * K : 0, nrow = h + row0;       // the positive's row, the first negative's row
+        const float a = live ? p[row0 * ldp] : 0.f;
+        const bool first = live && j < K;
+        const float b0 = first ? p[(nrow + j) * ldp] : 0.f;
+        // f(k, b_k) over this lane's negatives, k ascending
+        auto each = [&](auto f) {
+            if (first) f((int64_t)j, b0);
+            if constexpr (W == 64) {
+                if (live)
+                    for (int64_t k = (int64_t)j + 64; k < K; k += 64) f(k, p[(nrow + k) * ldp]);
+            }
+        };
+        float mx = -INFINITY;                                          // the largest negative and the lowest k that attains it
+        int32_t arg = INT32_MAX;
+        each([&](int64_t k, float b) { if (b > mx) { mx = b; arg = (int32_t)k; } });
+#pragma unroll
+        for (int o = W / 2; o > 0; o >>= 1) {
+            const float om = __shfl_xor(mx, o, 64);
+            const int32_t oa = __shfl_xor(arg, o, 64);
+            if (om > mx || (om == mx && oa < arg)) { mx = om; arg = oa; }
+        }
+        float loss, ga;                                               // l_g and dl_g/da; gk(k, b) = dl_g/db_k
+        if (kind == AMAR_GROUP_SOFTMAX) {
+            const float M = fmaxf(a, mx);
+            float s = 0.f;
+            each([&](int64_t, float b) { s += expf((b - M) / hyper); });
+            s = seg_sum<W>(s);
+            const float S = expf((a - M) / hyper) + s;
+            loss = a >= mx ? log1pf(s) : (M - a) / hyper + logf(S);
+            ga = -(s / S) / hyper;
+            each([&](int64_t k, float b) {
+                dz[nrow + k] = (inv_g * ((expf((b - M) / hyper) / S) / hyper)) * (b * (1.f - b));
+            });
+        } else if (kind == AMAR_GROUP_HARDEST) {
+            const float e = expf(mx - a);                             // in (-1, 1): probabilities, so exp cannot overflow
+            const float gs = e / (1.f + e);                           // 1 - sigmoid(a - mx)
+            loss = log1pf(e);
+            ga = -gs;
+            each([&](int64_t k, float b) { dz[nrow + k] = (int32_t)k == arg ? (inv_g * gs) * (b * (1.f - b)) : 0.f; });
+        } else {
+            const float d = hyper - a;
+            float s = 0.f, c = 0.f;
+            each([&](int64_t, float b) { const float v = d + b; s += fmaxf(v, 0.f); c += v > 0.f ? 1.f : 0.f; });
+            s = seg_sum<W>(s);
+            c = seg_sum<W>(c);                                        // (a count below 2^24: exact)
+            loss = s / fk;
+            ga = -(c / fk);
+            each([&](int64_t k, float b) { dz[nrow + k] = d + b > 0.f ? (inv_g * (1.f / fk)) * (b * (1.f - b)) : 0.f; });
+        }
+        each([&](int64_t k, float) {
+            terms[nrow + k] = 0.f;
+            if (k > 0) { dz[row0 + k] = 0.f; terms[row0 + k] = 0.f; }  // the copies of the positive's pair
+        });
+        if (live && j == 0) {
+            dz[row0] = (inv_g * ga) * (a * (1.f - a));
+            terms[row0] = scale * loss;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && 2 * h < B) {
+        dz[B - 1] = 0.f;
+        terms[B - 1] = 0.f;
+    }
+}
+
+template <int W>
+int launch_group_loss(int32_t kind, float hyper, const float *p, int64_t ldp, float *dz, float *terms, int64_t B, int64_t h, int32_t K,
+                      hipStream_t st) {
+    const int64_t G = h / K, per_block = 4 * (64 / W);
+    int64_t grid = (G + per_block - 1) / per_block;
+    grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);
+    hipLaunchKernelGGL(group_loss_kernel<W>, dim3((unsigned)grid), dim3(256), 0, st, kind, hyper, p, ldp, dz, terms, B, h, K, G);
+    return amar_check_launch();
+}
+
 __device__ __forceinline__ int32_t pick(uint32_t word, int32_t n) { return (int32_t)(((uint64_t)word * (uint32_t)n) >> 32); }
 
 // ONE workgroup: every lane reads *step before the barrier, one lane advances it after, so the batch sees one step value.
@@ -121,6 +220,23 @@ int amar_bpr_grad_f32(const float *p, int64_t ldp, float *dz, float *loss_terms,
     if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(bpr_grad_kernel, dim3((unsigned)grid), dim3(256), 0, st, p, ldp, dz, loss_terms, B, h);
     return amar_check_launch();
+}
+
+int amar_group_loss_grad_f32(int32_t kind, float hyper, const float *p, int64_t ldp, float *dz, float *loss_terms, int64_t B, int32_t K,
+                             amar_stream_t stream) {
+    if (B < 1 || !p || !dz || !loss_terms || ldp < 1 || K < 1) return AMAR_EINVAL;
+    if (kind != AMAR_GROUP_SOFTMAX && kind != AMAR_GROUP_HARDEST && kind != AMAR_GROUP_MARGIN) return AMAR_EINVAL;
+    if ((kind == AMAR_GROUP_SOFTMAX && !(hyper > 0.f)) || (kind == AMAR_GROUP_MARGIN && !(hyper >= 0.f))) return AMAR_EINVAL;
+    const int64_t h = B / 2;
+    if (h % K != 0) return AMAR_EINVAL;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (K > 32) return launch_group_loss<64>(kind, hyper, p, ldp, dz, loss_terms, B, h, K, st);
+    if (K > 16) return launch_group_loss<32>(kind, hyper, p, ldp, dz, loss_terms, B, h, K, st);
+    if (K > 8) return launch_group_loss<16>(kind, hyper, p, ldp, dz, loss_terms, B, h, K, st);
+    if (K > 4) return launch_group_loss<8>(kind, hyper, p, ldp, dz, loss_terms, B, h, K, st);
+    if (K > 2) return launch_group_loss<4>(kind, hyper, p, ldp, dz, loss_terms, B, h, K, st);
+    if (K > 1) return launch_group_loss<2>(kind, hyper, p, ldp, dz, loss_terms, B, h, K, st);
+    return launch_group_loss<1>(kind, hyper, p, ldp, dz, loss_terms, B, h, K, st);
 }
 
 int amar_bpr_sample_i32(const int32_t *pos_ptr, const int32_t *pos_ids, const int32_t *neg_ptr, const int32_t *neg_ids,

@@ -398,13 +398,13 @@ class Model(Layer):
     def evaluate(self, sequence, **kwargs):
         """Loss and metrics on `sequence` (experiment.py:194): [loss, accuracy] when no metric or only accuracy is compiled, else
         [loss, m1, m2, ...] in compile order.  As Keras' evaluate(), 'loss' is the compiled loss (utilities/losses.py: a pointwise
-        loss over all pairs, or BPRLoss per batch) plus
+        loss over all pairs, or BPRLoss per batch; a listwise loss per batch on groups of ``sequence.n_negatives`` triples) plus
         the regularisation losses of the model (l2 * sum(w^2) for every weight carrying a regulariser: gnn.py:45,293-294),
         the same sum fit() reports per epoch, so train and test losses of one run are comparable.  The metrics are those of the
         training counters, restated on the host (utilities/metrics.py: metric_counters, metric_values).  A Sequence built with
         sample_weight (three-element batches) weighs the loss terms with it — sum(w x term) / N, as fit() reports — and leaves the
         metrics unweighted; BPRLoss refuses it.  No class_weight here: Keras' evaluate() has none."""
-        from deep_cbrs_amar_renaissance_amd.utilities.losses import BCE, BPR, BPRLoss, loss_terms
+        from deep_cbrs_amar_renaissance_amd.utilities.losses import BCE, BPR, GROUP_KINDS, LOSS_NAMES, BPRLoss, group_loss_terms, loss_terms
         from deep_cbrs_amar_renaissance_amd.utilities.metrics import metric_counters, metric_values, resolve_compiled
         code, hyper, names = resolve_compiled(getattr(self, 'loss', None), getattr(self, 'metrics', None))
         pred32 = self.predict(sequence).reshape(-1)
@@ -416,6 +416,8 @@ class Model(Layer):
         if any(len(batch) > 2 and batch[2] is not None for batch in batches):
             if code == BPR:
                 raise ValueError("BPRLoss has no per-pair term: evaluate() takes no weighted Sequence under it")
+            if code in GROUP_KINDS:
+                raise ValueError("{} has no per-pair term: evaluate() takes no weighted Sequence under it".format(LOSS_NAMES[code]))
             weights = np.concatenate([np.asarray(batch[2], dtype=np.float64).reshape(-1) if len(batch) > 2 and batch[2] is not None
                                       else np.ones(len(lab)) for batch, lab in zip(batches, labels)])
             if len(weights) != len(y):
@@ -426,6 +428,14 @@ class Model(Layer):
             bpr, total, lo = BPRLoss(), 0.0, 0
             for lab in labels:
                 total += bpr(None, pred[lo:lo + len(lab)]) * len(lab)
+                lo += len(lab)
+            loss = total / len(y) if len(y) else 0.0
+        elif code in GROUP_KINDS:
+            # a listwise loss on each batch's own groups of sequence.n_negatives triples (1 where the Sequence has no groups: every
+            # row (j, h + j) its own pair, BPRLoss's reading), averaged as above
+            k, total, lo = int(getattr(sequence, 'n_negatives', 1)), 0.0, 0
+            for lab in labels:
+                total += float(np.sum(group_loss_terms(code, hyper, pred[lo:lo + len(lab)], k)))
                 lo += len(lab)
             loss = total / len(y) if len(y) else 0.0
         elif weights is not None:

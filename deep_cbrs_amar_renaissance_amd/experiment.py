@@ -320,7 +320,8 @@ class Experimenter:
             self.model = cls(**model_cfg)
         if hasattr(self.model, 'n_users'):                   # lets hoisted scoring run each tower on its own rows
             self.model.n_users, self.model.n_items = len(self.trainset.users), len(self.trainset.items)
-        # custom loss class (experiment.py:155-157); any other name, or a mapping {name: ..., <hyper-parameters>}, goes to compile()
+        # custom loss class (experiment.py:155-157: BPRLoss and the listwise losses, with their defaults); any other name, or a
+        # mapping {name: ..., <hyper-parameters>} such as {name: SampledSoftmaxLoss, temperature: 0.2}, goes to compile()
         custom = getattr(losses, self.parameters.loss, None) if isinstance(self.parameters.loss, str) else None
         if isinstance(custom, type) and custom.__module__ == losses.__name__:
             self.parameters['loss'] = custom()

@@ -38,10 +38,13 @@ from deep_cbrs_amar_renaissance_amd.layers.gat_conv import GATConv
 from deep_cbrs_amar_renaissance_amd.layers.gcn_conv import GCNConv
 from deep_cbrs_amar_renaissance_amd.layers.graphsage_conv import GraphSageConv
 from deep_cbrs_amar_renaissance_amd.layers.lightgcn_conv import LightGCNConv
-from deep_cbrs_amar_renaissance_amd.utilities.losses import BPR, loss_kind, resolve_class_weight
+from deep_cbrs_amar_renaissance_amd.utilities.losses import BPR, GROUP_KINDS, LOSS_NAMES, loss_kind, resolve_class_weight, resolve_loss
 from deep_cbrs_amar_renaissance_amd.utilities.math import spmm_kind
 from deep_cbrs_amar_renaissance_amd.utilities.metrics import metric_values, resolve_compiled
 from deep_cbrs_amar_renaissance_amd.utilities.schedules import InverseTimeDecay, LearningRateSchedule, resolve as resolve_learning_rate
+
+_NEEDS_TRIPLETS = ("{} groups each positive with the negatives drawn for the same user: it trains on the triplet Sequence of "
+                   "load_user_item_graph_triplets (data/datasets.py:UserItemGraphTriplets) only")
 
 
 def _spmm(a, x, out):
@@ -1031,8 +1034,17 @@ class Trainer:
             if w is not None or cw is not None:
                 raise ValueError("BPRLoss has no per-pair label or term: it takes no class_weight and no sample weights")
             capi.bpr_grad(p, dz, terms)
+        elif code in GROUP_KINDS:                                    # the listwise losses, in bpr_grad's slot: one launch
+            if w is not None or cw is not None:
+                raise ValueError("{} has no per-pair label or term: it takes no class_weight and no sample weights".format(LOSS_NAMES[code]))
+            if self._group_k is None:
+                raise ValueError(_NEEDS_TRIPLETS.format(LOSS_NAMES[code]))
+            capi.group_loss_grad(GROUP_KINDS[code], hyper[0], p, dz, terms, n_negatives=self._group_k)
         else:
             capi.loss_grad(code, hyper, p, yv, dz, terms, counters=self._metric_block() if names else None, sample_weight=w, class_weight=cw)
+
+    # the group size of the batch being trained on (TripletSampler.n_negatives, set by `train_sampled`); None: no triplet batch yet
+    _group_k = None
 
     # -- the weights of the loss ----------------------------------------------------------------------------------------
     _class_w, _class_weighted = None, False
@@ -1354,6 +1366,7 @@ class Trainer:
         if self.hybrid:
             raise NotImplementedError("the BPR sample Sequence carries no BERT rows: hybrid models do not train on it")
         b = 2 * sampler.h
+        self._group_k = getattr(sampler, 'n_negatives', None)       # (a new group size is a new sampler: `serial` keys the graph)
         self._step(('sampled', b, self._loss_kind(), sampler.serial) + self.dropout_key, b, lambda: dict(self._new_buffers(b), sampler=sampler),
                    prologue=lambda g: sampler.sample(g['u'], g['i'], g['y']), graph=graph)
 
@@ -1827,6 +1840,13 @@ def fit(model, sequence, epochs=1, callbacks=None, verbose=True, validation_data
     spec = OptimizerSpec(getattr(model, 'optimizer', None))
     use_graph = os.environ.get('AMAR_TRAIN_GRAPH', '1') != '0'
     sampled = hasattr(model, 'gnn') and isinstance(sequence, (UserItemGraphPosNegSample, UserItemGraphTriplets))
+    group_code, _, group_name = resolve_loss(getattr(model, 'loss', None))
+    if group_code in GROUP_KINDS:
+        # a listwise loss reads the batch as groups of one user's positive and its n_negatives negatives: only the triplet Sequence
+        # lays them out so (rows (j, h + j) of a UserItemGraphPosNegSample pair do not share a user; a rating batch has no groups)
+        if not (sampled and isinstance(sequence, UserItemGraphTriplets)):
+            raise ValueError(_NEEDS_TRIPLETS.format(group_name))
+        resolve_compiled(model.loss, getattr(model, 'metrics', None))    # (compiled metrics are refused as under BPRLoss)
     if not hasattr(model, 'gnn'):                              # BasicRS / HybridCBRS on pre-computed rows: head-only training
         trainer = _cached_trainer(model, spec)
         if trainer is None:

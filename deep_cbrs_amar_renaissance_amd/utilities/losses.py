@@ -6,6 +6,10 @@ any other value — a Keras loss name, a Keras class name, or a mapping ``{name:
 name: ``binary_crossentropy`` is the default.  ``fit()`` and ``evaluate()`` read the compiled loss through `resolve_loss`
 (`loss_kind` tells BPR from the pointwise losses).  `loss_terms` / `loss_dp` restate every pointwise loss in float64 numpy, with
 the weights of ``fit(class_weight=...)`` and of a weighted Sequence where given (`pair_weights`, `resolve_class_weight`).
+
+Beside BPRLoss stand three listwise losses on the groups the triplet sampler draws (one positive and ``n_negatives`` negatives of one
+user): SampledSoftmaxLoss, HardestNegativeBPRLoss, MarginRankingLoss (include/amar_hip.h: amar_group_loss_grad_f32).  They route
+wherever BPR routes (`loss_kind` says 'bpr'); `group_loss_terms` / `group_loss_dp` restate them in float64 numpy.
 """
 from collections.abc import Mapping
 
@@ -31,9 +35,68 @@ class BPRLoss:
         return float(np.mean(np.logaddexp(0.0, -x)))          # -log sigmoid(x)
 
 
+class _GroupLoss:
+    """A listwise loss on the groups of data/datasets.py:UserItemGraphTriplets, on the model's sigmoid outputs as BPRLoss: a batch of
+    B = 2h rows (an odd B drops its last) holds G = h / n_negatives groups; group g has the positive ``p[g K]`` and the negatives
+    ``p[h + g K + k]``, k < K = n_negatives (rows g K + 1 .. g K + K - 1 repeat the positive's pair and carry nothing).  The batch
+    loss is the mean of the group losses (include/amar_hip.h: amar_group_loss_grad_f32)."""
+    code, hyper_name = None, None
+
+    def hyper(self):
+        """The kernel's four floats: (temperature | margin, 0, 0, 0)."""
+        return (float(getattr(self, self.hyper_name)) if self.hyper_name else 0.0, 0.0, 0.0, 0.0)
+
+    def __call__(self, y_true, y_pred, n_negatives=1):
+        """float64 value of the loss for one batch (y_true is not read).  A batch without a pair (B < 2) counts 0."""
+        p = np.asarray(y_pred, dtype=np.float64).reshape(-1)
+        return float(np.sum(group_loss_terms(self.code, self.hyper(), p, n_negatives)) / len(p)) if len(p) else 0.0
+
+
+class SampledSoftmaxLoss(_GroupLoss):
+    """Sampled softmax over one positive and K negatives: ``l_g = -p+/t + log(exp(p+/t) + sum_k exp(p-_k/t))``, temperature t > 0,
+    evaluated with the group's maximum subtracted.  K = 1, t = 1 is BPRLoss's value."""
+    code, hyper_name = -2, 'temperature'
+
+    def __init__(self, temperature=1.0, name="sampled_softmax_loss"):
+        self.temperature, self.name = _positive(temperature, 'temperature', strict=True), name
+
+
+class HardestNegativeBPRLoss(_GroupLoss):
+    """BPR against the hardest of K sampled negatives (dynamic negative sampling): ``l_g = -log sigmoid(p+ - max_k p-_k)``; the
+    negative side's gradient goes to the lowest k that attains the maximum."""
+    code = -3
+
+    def __init__(self, name="hardest_negative_BPR_loss"):
+        self.name = name
+
+
+class MarginRankingLoss(_GroupLoss):
+    """Margin ranking hinge: ``l_g = (1 / K) sum_k max(0, m - p+ + p-_k)``, margin m >= 0; the subgradient is 0 where the hinge
+    argument is not strictly positive."""
+    code, hyper_name = -4, 'margin'
+
+    def __init__(self, margin=0.5, name="margin_ranking_loss"):
+        self.margin, self.name = _positive(margin, 'margin', strict=False), name
+
+
+def _positive(value, what, strict):
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError("{} must be a number (got {!r})".format(what, value))
+    if isinstance(value, bool) or not np.isfinite(v) or v < 0.0 or (strict and v == 0.0):
+        raise ValueError("{} must be finite and {} (got {!r})".format(what, 'positive' if strict else 'not negative', value))
+    return v
+
+
 def loss_kind(loss):
-    """'bpr' for a BPRLoss (instance or name), 'bce' for anything else (the reference's default binary cross-entropy)."""
-    if isinstance(loss, BPRLoss) or loss == 'BPRLoss':
+    """'bpr' for a BPRLoss (instance or name) and for the listwise losses on its batches (SampledSoftmaxLoss, HardestNegativeBPRLoss,
+    MarginRankingLoss: instance, name or mapping), 'bce' for anything else (the reference's default binary cross-entropy)."""
+    if isinstance(loss, (BPRLoss, _GroupLoss)) or loss == 'BPRLoss':
+        return 'bpr'
+    if isinstance(loss, Mapping):
+        loss = loss.get('name', loss.get('class_name'))
+    if isinstance(loss, str) and loss in _GROUP_CLASSES:
         return 'bpr'
     return 'bce'
 
@@ -41,10 +104,16 @@ def loss_kind(loss):
 # ---- Keras 2's pointwise losses on one sigmoid output (include/amar_hip.h: AMAR_LOSS_*) ---------------------------------------------
 BCE, MSE, MAE, HINGE, SQUARED_HINGE, HUBER, LOG_COSH, POISSON, FOCAL = range(9)
 BPR = -1                                                              # (no code of amar_loss_grad_f32: amar_bpr_grad_f32's loss)
+# the listwise losses on BPR's batches, and their kinds in amar_group_loss_grad_f32 (include/amar_hip.h: AMAR_GROUP_*)
+SAMPLED_SOFTMAX, HARDEST_NEGATIVE, MARGIN_RANKING = SampledSoftmaxLoss.code, HardestNegativeBPRLoss.code, MarginRankingLoss.code
+GROUP_KINDS = {SAMPLED_SOFTMAX: 0, HARDEST_NEGATIVE: 1, MARGIN_RANKING: 2}
+_GROUP_CLASSES = {'SampledSoftmaxLoss': SampledSoftmaxLoss, 'HardestNegativeBPRLoss': HardestNegativeBPRLoss,
+                  'MarginRankingLoss': MarginRankingLoss}
 
 LOSS_NAMES = {BCE: 'binary_crossentropy', MSE: 'mean_squared_error', MAE: 'mean_absolute_error', HINGE: 'hinge',
               SQUARED_HINGE: 'squared_hinge', HUBER: 'huber', LOG_COSH: 'log_cosh', POISSON: 'poisson',
-              FOCAL: 'binary_focal_crossentropy', BPR: 'BPRLoss'}
+              FOCAL: 'binary_focal_crossentropy', BPR: 'BPRLoss', SAMPLED_SOFTMAX: 'SampledSoftmaxLoss',
+              HARDEST_NEGATIVE: 'HardestNegativeBPRLoss', MARGIN_RANKING: 'MarginRankingLoss'}
 _ALIASES = {
     'binary_crossentropy': BCE, 'BinaryCrossentropy': BCE,
     'mean_squared_error': MSE, 'mse': MSE, 'MSE': MSE, 'MeanSquaredError': MSE,
@@ -56,6 +125,7 @@ _ALIASES = {
     'poisson': POISSON, 'Poisson': POISSON,
     'binary_focal_crossentropy': FOCAL, 'BinaryFocalCrossentropy': FOCAL,
     'BPRLoss': BPR,
+    'SampledSoftmaxLoss': SAMPLED_SOFTMAX, 'HardestNegativeBPRLoss': HARDEST_NEGATIVE, 'MarginRankingLoss': MARGIN_RANKING,
 }
 # what tf.keras.losses.get resolves and no kernel here computes (multi-class, distribution and similarity losses)
 _KERAS_WITHOUT_KERNEL = {
@@ -66,7 +136,8 @@ _KERAS_WITHOUT_KERNEL = {
 }
 # hyper-parameters a mapping may carry, with Keras' defaults; the kernel's array is (label_smoothing, delta | gamma, alpha, balancing)
 _HYPER_DEFAULTS = {BCE: {'label_smoothing': 0.0}, HUBER: {'delta': 1.0},
-                   FOCAL: {'gamma': 2.0, 'apply_class_balancing': False, 'alpha': 0.25, 'label_smoothing': 0.0}}
+                   FOCAL: {'gamma': 2.0, 'apply_class_balancing': False, 'alpha': 0.25, 'label_smoothing': 0.0},
+                   SAMPLED_SOFTMAX: {'temperature': 1.0}, MARGIN_RANKING: {'margin': 0.5}}
 
 
 def supported_losses():
@@ -78,10 +149,16 @@ def resolve_loss(loss):
     """(code, hyper, name) of a compiled loss: `code` one of the AMAR_LOSS_* codes (or BPR), `hyper` the kernel's four floats
     (label_smoothing, delta or gamma, alpha, apply_class_balancing as 0 / 1) as a tuple, `name` Keras' function name.
     Accepts None (binary cross-entropy), a Keras loss or class name, a BPRLoss, or a mapping {name: ..., <hyper-parameters>}.
+    The listwise losses (instance, class name, or a mapping such as {name: SampledSoftmaxLoss, temperature: 0.2}) have the codes
+    SAMPLED_SOFTMAX / HARDEST_NEGATIVE / MARGIN_RANKING and hyper = (temperature | margin, 0, 0, 0).
     NotImplementedError: a loss Keras knows and no kernel here computes; ValueError: any other name or hyper-parameter."""
     values = {}
     if isinstance(loss, BPRLoss):
         return BPR, (0.0, 0.0, 0.0, 0.0), LOSS_NAMES[BPR]
+    if isinstance(loss, _GroupLoss):
+        if loss.hyper_name:                                          # (an attribute set after the constructor is checked again)
+            _positive(getattr(loss, loss.hyper_name), loss.hyper_name, strict=loss.code == SAMPLED_SOFTMAX)
+        return loss.code, loss.hyper(), LOSS_NAMES[loss.code]
     if isinstance(loss, Mapping):
         values = {k: v for k, v in loss.items() if k not in ('name', 'class_name')}
         loss = loss.get('name', loss.get('class_name'))
@@ -99,6 +176,8 @@ def resolve_loss(loss):
     if unknown:
         raise ValueError("loss '{}' takes no hyper-parameter {} (it takes: {})".format(loss, unknown, sorted(known) or 'none'))
     known.update(values)
+    if code in GROUP_KINDS:                                          # (the classes check the temperature and the margin)
+        return code, _GROUP_CLASSES[loss](**known).hyper(), LOSS_NAMES[code]
     ls = float(known.get('label_smoothing', 0.0))
     shape = float(known.get('delta', known.get('gamma', 0.0)))
     if not 0.0 <= ls <= 1.0 or shape < 0.0:
@@ -194,11 +273,76 @@ def loss_dp(code, hyper, y_true, y_pred, f32_constants=False, sample_weight=None
     return dp if w is None else w * dp
 
 
-def loss_value(loss, y_true, y_pred, sample_weight=None, class_weight=None):
+def _group_parts(code, hyper, y_pred, n_negatives):
+    """(terms [B], d(batch loss)/dp [B]) of listwise loss `code` in float64, group by group in vector form."""
+    if code not in GROUP_KINDS:
+        raise ValueError("no listwise loss with code {}".format(code))
+    p = np.asarray(y_pred, dtype=np.float64).reshape(-1)
+    B, h, K = len(p), len(p) // 2, int(n_negatives)
+    if K < 1 or h % K:
+        raise ValueError("{} triples do not split into groups of n_negatives = {}".format(h, n_negatives))
+    terms, dp = np.zeros(B), np.zeros(B)
+    G = h // K
+    if G == 0:
+        return terms, dp
+    a, b = p[:h:K], p[h:2 * h].reshape(G, K)                          # the positives [G], the negatives [G, K]
+    da, db = dp[:h:K], dp[h:2 * h].reshape(G, K)                      # (views: written in place)
+    if code == SAMPLED_SOFTMAX:
+        t = float(hyper[0])
+        if not t > 0.0:
+            raise ValueError("temperature must be positive (got {!r})".format(hyper[0]))
+        m = np.maximum(a, b.max(axis=1))
+        ea, eb = np.exp((a - m) / t), np.exp((b - m[:, None]) / t)
+        s = ea + eb.sum(axis=1)
+        loss = -(a - m) / t + np.log(s)
+        da[:] = (ea / s - 1.0) / t
+        db[:] = eb / s[:, None] / t
+    elif code == HARDEST_NEGATIVE:
+        k = np.argmax(b, axis=1)                                      # (the first k that attains the maximum)
+        x = a - b[np.arange(G), k]
+        loss = np.logaddexp(0.0, -x)
+        g = 1.0 / (1.0 + np.exp(x))                                   # 1 - sigmoid(x)
+        da[:] = -g
+        db[np.arange(G), k] = g
+    else:
+        mgn = float(hyper[0])
+        if not mgn >= 0.0:
+            raise ValueError("margin must not be negative (got {!r})".format(hyper[0]))
+        v = (mgn - a)[:, None] + b
+        on = v > 0.0
+        loss = np.where(on, v, 0.0).sum(axis=1) / K
+        da[:] = -on.sum(axis=1) / K
+        db[:] = on / K
+    terms[:h:K] = (B / G) * loss
+    dp /= G
+    return terms, dp
+
+
+def group_loss_terms(code, hyper, y_pred, n_negatives=1):
+    """float64 terms of listwise loss `code` (SAMPLED_SOFTMAX, HARDEST_NEGATIVE, MARGIN_RANKING) on one batch of probabilities in
+    UserItemGraphTriplets' layout: terms[g K] = (B / G) l_g, every other element 0, so their sum over B is the batch loss — what
+    amar_group_loss_grad_f32 writes to loss_terms.  hyper: `resolve_loss`'s tuple, [0] the temperature or the margin."""
+    return _group_parts(code, hyper, y_pred, n_negatives)[0]
+
+
+def group_loss_dp(code, hyper, y_pred, n_negatives=1):
+    """float64 d(batch loss)/d(p_i) of listwise loss `code`: (1 / G) dl_g/dp_i, the positive's whole gradient on row g K and 0 on
+    its copies and on the trailing element of an odd batch; the hardest negative's share goes to the lowest k at the maximum, a
+    hinge that is not strictly positive gives 0.  amar_group_loss_grad_f32's dz is this times p (1 - p)."""
+    return _group_parts(code, hyper, y_pred, n_negatives)[1]
+
+
+def loss_value(loss, y_true, y_pred, sample_weight=None, class_weight=None, n_negatives=1):
     """float64 batch value of a compiled loss (anything `resolve_loss` accepts) on labels and probabilities: the sum of the per-pair
     terms over the batch size B — weighted terms too (Keras' SUM_OVER_BATCH_SIZE: the divisor is B, not the sum of the weights);
-    BPRLoss's own value for BPR, which takes no weights; an empty batch counts 0."""
-    code, hyper, _ = resolve_loss(loss)
+    BPRLoss's own value for BPR, which takes no weights; the mean over the groups of `n_negatives` triples for the listwise losses,
+    which take none either (every other loss ignores n_negatives); an empty batch counts 0."""
+    code, hyper, name = resolve_loss(loss)
+    if code in GROUP_KINDS:
+        if sample_weight is not None or class_weight is not None:
+            raise ValueError("{} has no per-pair label or term: it takes no class_weight and no sample_weight".format(name))
+        terms = group_loss_terms(code, hyper, y_pred, n_negatives)
+        return float(np.sum(terms) / len(terms)) if len(terms) else 0.0
     if code == BPR:
         if sample_weight is not None or class_weight is not None:
             raise ValueError("BPRLoss has no per-pair label or term: it takes no class_weight and no sample_weight")

@@ -323,13 +323,13 @@ def resolve_compiled(loss, metrics):
     """(loss code, hyper, metric history names) of a Model.compile(loss=..., metrics=...), with the errors of `resolve_loss` and
     `resolve_metrics`.  Under BPRLoss the labels carry no meaning: 'accuracy' is accepted and left out, any other metric raises
     NotImplementedError."""
-    from deep_cbrs_amar_renaissance_amd.utilities.losses import BPR, resolve_loss
-    code, hyper, _ = resolve_loss(loss)
+    from deep_cbrs_amar_renaissance_amd.utilities.losses import BPR, GROUP_KINDS, resolve_loss
+    code, hyper, loss_name = resolve_loss(loss)
     names = resolve_metrics(metrics)
-    if code == BPR:
+    if code == BPR or code in GROUP_KINDS:                           # (the listwise losses train on BPR's batches)
         if any(name != 'accuracy' for name in names):
-            raise NotImplementedError("BPRLoss trains on (positive, negative) pairs whose labels carry no meaning: metrics {} are not "
-                                      "defined under it".format([n for n in names if n != 'accuracy']))
+            raise NotImplementedError("{} trains on (positive, negative) pairs whose labels carry no meaning: metrics {} are not "
+                                      "defined under it".format(loss_name, [n for n in names if n != 'accuracy']))
         names = []
     return code, hyper, names
 

@@ -1070,6 +1070,34 @@ int amar_bpr_sample_triplets_i32(const int32_t *pos_ptr, const int32_t *pos_ids,
                                  uint64_t *step, int32_t advance, int32_t h, int32_t *u, int32_t *items, float *y,
                                  amar_stream_t stream);
 
+/* ---- listwise ranking losses on the triplet sampler's groups (utilities/losses.py: SampledSoftmaxLoss, HardestNegativeBPRLoss,
+ *      MarginRankingLoss) ---------------------------------------------------------------------------------------------------------
+ * amar_group_loss_grad_f32  in amar_bpr_grad_f32's place and conventions, on amar_bpr_sample_triplets_i32's layout: h = B / 2 (an odd B
+ *                      drops its last element), G = h / K groups; group g has the positive a = p[g K] and the negatives
+ *                      b_k = p[h + g K + k], k < K (rows g K + 1 .. g K + K - 1 repeat the positive's pair and carry nothing).
+ *                        AMAR_GROUP_SOFTMAX  l_g = -a / t + log(exp(a / t) + sum_k exp(b_k / t)), t = hyper > 0, evaluated with
+ *                                            the group's maximum M subtracted: s = sum_k exp((b_k - M) / t), S = exp((a - M) / t) + s,
+ *                                            l_g = log1p(s) where a = M, else (M - a) / t + log S; dl/da = -(s / S) / t,
+ *                                            dl/db_k = (exp((b_k - M) / t) / S) / t
+ *                        AMAR_GROUP_HARDEST  l_g = -log sigmoid(a - max_k b_k); the negative side's gradient goes to the LOWEST k
+ *                                            that attains the maximum, every other negative gets 0 (hyper is not read)
+ *                        AMAR_GROUP_MARGIN   l_g = (1 / K) sum_k max(0, (m - a) + b_k), m = hyper >= 0; a hinge that is not strictly
+ *                                            positive contributes no gradient
+ *                      loss = mean_g l_g.  loss_terms[g K] = (B / G) l_g and every other term 0 (sum = B x loss);
+ *                      dz[i] = (1 / G) dl_g/dp_i . p_i (1 - p_i): the positive's whole gradient on row g K, exactly 0 on its copies and
+ *                      on the dropped trailing element.  dz and loss_terms contiguous [B]; p [B] or a strided column (ldp).
+ *                      B = 1: zeros.  AMAR_EINVAL: K < 1, h % K != 0, an unknown kind, t <= 0, m < 0 (or either not a number).
+ *                      One launch, float32, no atomics.  K <= 32: a group takes a segment of the next power of two >= K lanes, several
+ *                      groups per wavefront; K > 32: one wavefront per group, lane l takes k = l, l + 64, ... in ascending order.
+ *                      Every reduction is a lane-local ascending sum followed by an xor butterfly inside the segment, so a group's
+ *                      bits depend on its own floats, K and hyper only — not on the grid, the wavefront or the group's place in the
+ *                      batch. */
+#define AMAR_GROUP_SOFTMAX 0
+#define AMAR_GROUP_HARDEST 1
+#define AMAR_GROUP_MARGIN  2
+int amar_group_loss_grad_f32(int32_t kind, float hyper, const float *p, int64_t ldp, float *dz, float *loss_terms, int64_t B, int32_t K,
+                             amar_stream_t stream);
+
 /* ---- the compiled loss and the compiled metrics (Model.compile(loss=..., metrics=...)) -------------------------------------------
  * amar_loss_grad_f32   Keras 2's pointwise losses on ONE sigmoid output, in amar_bce_grad_f32's place and conventions: p is [B] or a
  *                      strided [B, 1] column (leading dimension ldp), y the 0/1 labels, loss_terms[i] the pair's term (their sum =
