@@ -4,6 +4,15 @@ torch is only the carrier here: tensors provide device memory (``data_ptr()``) a
 HIP stream; every function below checks shapes on the host, hands raw pointers to the library
 and raises on a non-zero return code.  There is NO fallback: if the shared library is missing,
 or a tensor is not on a GPU, the call fails loudly.
+
+Binding a new entry point:
+  1. add its (restype, argtypes) to SIGNATURES, at its place in the header's order;
+  2. check shapes on the host first and raise ValueError naming the wrapper;
+  3. marshal with _ptr(t, F32 | I32, name) (typed pointer, None -> NULL), _ptr_entries (per-non-zero arrays), _mat (pointer and
+     leading dimension of a 2-D float32 view, (None, 0) for None) and _col (a [B] or [B, 1] column); _ptr(t) for a buffer made here;
+  4. launch with _launch('amar_x_f32', ...): it appends the current stream and raises on a non-zero code.  A host-only
+     function (a route query) goes through _call('amar_x_route', ..., ctypes.byref(info)): no stream;
+  5. a launcher and its route query share one _x_args builder; a route-info structure derives from _RouteInfo.
 """
 import ctypes
 import os
@@ -216,9 +225,90 @@ def _stream():
 
 def _ld(t, name):
     """Leading dimension of a 2-D row-major view (last dim contiguous)."""
-    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+    shape, stride = t.shape, t.stride()                                  # (read once each: this runs for every matrix operand of a launch)
+    if len(shape) != 2 or (shape[1] > 1 and stride[1] != 1):
         raise ValueError("{} must be a 2-D tensor whose last dimension is contiguous".format(name))
-    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+    return stride[0] if shape[0] > 1 else max(stride[0], shape[1])
+
+
+# The typed pointers are `_ptr(t, F32, name)` / `_ptr(t, I32, name)`: a wrapper of their own would add a Python call per operand to
+# every launch, which an eager step pays a few hundred times.
+F32, I32 = torch.float32, torch.int32
+
+
+def _mat(t, name):
+    """(pointer, leading dimension) of a 2-D float32 view; (None, 0) for None."""
+    if t is None:
+        return None, 0
+    return _ptr(t, F32, name), _ld(t, name)
+
+
+def _col(p, name):
+    """(pointer, row stride) of a float32 column given as [B] or as [B, 1]."""
+    return _ptr(p, F32, name), _ld(p, name) if p.dim() == 2 else 1
+
+
+def _call(symbol, *args):
+    """One call into the library: raises unless the entry point returns AMAR_OK."""
+    code = getattr(load(), symbol)(*args)
+    if code:
+        _check(code, symbol)
+
+
+def _launch(symbol, *args):
+    """_call with the current stream as the last argument: every entry point that launches takes it there."""
+    code = getattr(load(), symbol)(*args, _stream())
+    if code:
+        _check(code, symbol)
+
+
+class _RouteInfo(ctypes.Structure):
+    """Base of the amar_*_route_info structures.  as_dict(): every field but HIDDEN as int, those of BOOLS as bool, an array
+    field as the list of its first n_layers entries, and the `kernel` code as its name where the class has KERNELS."""
+    KERNELS, BOOLS, HIDDEN = None, (), ()
+
+    def as_dict(self, n_layers=None):
+        d = {}
+        for name, _ in self._fields_:
+            if name not in self.HIDDEN:
+                v, conv = getattr(self, name), bool if name in self.BOOLS else int
+                d[name] = [conv(x) for x in v[:n_layers]] if isinstance(v, ctypes.Array) else conv(v)
+        if self.KERNELS is not None:
+            d['kernel'] = self.KERNELS[d['kernel']]
+        return d
+
+
+def _next_product(what, width_name, n_rows, F, Wnext, Hnext):
+    """The epilogue that makes the next layer's dense product, Hnext = Y . Wnext: checked, as (Wnext, Cn, Hnext, ldh)."""
+    Cn = 0
+    if Wnext is not None:
+        if Wnext.shape[0] != F or not Wnext.is_contiguous() or Hnext is None or tuple(Hnext.shape) != (n_rows, Wnext.shape[1]):
+            raise ValueError("{}: Wnext [{}, Cn] contiguous and Hnext [n_rows, Cn] expected".format(what, width_name))
+        Cn = Wnext.shape[1]
+    return (_ptr(Wnext, F32, 'Wnext'), Cn, *_mat(Hnext, 'Hnext'))
+
+
+def _spmm_epilogue(what, n_rows, F, Y, bias, relu, acc_in, acc_out, acc_div, Wnext, Hnext):
+    """The epilogue the SpMM entry points share, checked.  Returns (flags, tail): the BIAS / RELU / ACCUM / ACCUM_DIV bits and the
+    arguments after `flags`: bias, acc_in, ld, acc_out, ld, acc_div, Wnext, Cn, Hnext, ld (amar_spmm_csr_f32 ends after acc_div).
+    Call it after the wrapper's own checks: it is where marshalling starts."""
+    flags = (SPMM_BIAS if bias is not None else 0) | (SPMM_RELU if relu else 0)
+    if acc_out is not None:
+        flags |= SPMM_ACCUM | (SPMM_ACCUM_DIV if acc_div is not None else 0)
+        if acc_in is None or tuple(acc_in.shape) != (n_rows, F) or tuple(acc_out.shape) != (n_rows, F):
+            raise ValueError("acc_in/acc_out must be [n_rows, F]")
+    if Y is not None and tuple(Y.shape) != (n_rows, F):
+        raise ValueError("Y must be [n_rows, F]")
+    product = _next_product(what, 'F', n_rows, F, Wnext, Hnext)
+    return flags, (_ptr(bias, F32, 'bias'), *_mat(acc_in, 'acc_in'), *_mat(acc_out, 'acc_out'),
+                   float(acc_div) if acc_div is not None else 1.0, *product)
+
+
+def _scaled_table(X, scale):
+    """S.X in a fresh table: what a value-free image A = S C S gathers from."""
+    Xs = torch.empty((X.shape[0], X.shape[1]), dtype=torch.float32, device=X.device)
+    row_affine(X, scale, Xs)
+    return Xs
 
 
 def spmm_csr(rowptr, colidx, vals, X, Y=None, bias=None, relu=False, acc_in=None, acc_out=None, acc_div=None):
@@ -227,23 +317,11 @@ def spmm_csr(rowptr, colidx, vals, X, Y=None, bias=None, relu=False, acc_in=None
     F = X.shape[1]
     if colidx.numel() and int(X.shape[0]) < 1:
         raise ValueError("X has no rows")
-    flags = (SPMM_BIAS if bias is not None else 0) | (SPMM_RELU if relu else 0)
-    if acc_out is not None:
-        flags |= SPMM_ACCUM | (SPMM_ACCUM_DIV if acc_div is not None else 0)
-        if acc_in is None or acc_in.shape != (n_rows, F) or acc_out.shape != (n_rows, F):
-            raise ValueError("acc_in/acc_out must be [n_rows, F]")
-    if Y is not None and tuple(Y.shape) != (n_rows, F):
-        raise ValueError("Y must be [n_rows, F]")
     if vals is not None and vals.numel() != colidx.numel():
         raise ValueError("vals and colidx differ in length")
-    code = load().amar_spmm_csr_f32(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), _ptr_entries(vals, torch.float32, 'vals'),
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y') if Y is not None else 0,
-        n_rows, F, flags, _ptr(bias, torch.float32, 'bias'),
-        _ptr(acc_in, torch.float32, 'acc_in'), _ld(acc_in, 'acc_in') if acc_in is not None else 0,
-        _ptr(acc_out, torch.float32, 'acc_out'), _ld(acc_out, 'acc_out') if acc_out is not None else 0,
-        float(acc_div) if acc_div is not None else 1.0, _stream())
-    _check(code, 'amar_spmm_csr_f32')
+    flags, tail = _spmm_epilogue('spmm_csr', n_rows, F, Y, bias, relu, acc_in, acc_out, acc_div, None, None)
+    _launch('amar_spmm_csr_f32', _ptr(rowptr, I32, 'rowptr'), _ptr_entries(colidx, I32, 'colidx'), _ptr_entries(vals, F32, 'vals'),
+            *_mat(X, 'X'), *_mat(Y, 'Y'), n_rows, F, flags, *tail[:6])
 
 
 def spmm_sj(sj, X, Y=None, bias=None, relu=False, acc_in=None, acc_out=None, acc_div=None, Wnext=None, Hnext=None):
@@ -251,31 +329,11 @@ def spmm_sj(sj, X, Y=None, bias=None, relu=False, acc_in=None, acc_out=None, acc
     spmm_csr / gcn_layer.  Used when the node table does not fit the per-XCD L2."""
     n_rows = sj.shape[0]
     F = X.shape[1]
-    flags = (SPMM_BIAS if bias is not None else 0) | (SPMM_RELU if relu else 0)
-    if acc_out is not None:
-        flags |= SPMM_ACCUM | (SPMM_ACCUM_DIV if acc_div is not None else 0)
-        if acc_in is None or tuple(acc_in.shape) != (n_rows, F) or tuple(acc_out.shape) != (n_rows, F):
-            raise ValueError("acc_in/acc_out must be [n_rows, F]")
-    if Y is not None and tuple(Y.shape) != (n_rows, F):
-        raise ValueError("Y must be [n_rows, F]")
     if X.shape[0] < sj.shape[1]:
         raise ValueError("X has fewer rows than the matrix has columns")
-    Cn = 0
-    if Wnext is not None:
-        if Wnext.shape[0] != F or not Wnext.is_contiguous() or Hnext is None or tuple(Hnext.shape) != (n_rows, Wnext.shape[1]):
-            raise ValueError("spmm_sj: Wnext [F, Cn] contiguous and Hnext [n_rows, Cn] expected")
-        Cn = Wnext.shape[1]
-    code = load().amar_spmm_sj_f32(
-        _ptr(sj.entries, torch.int32, 'entries'), _ptr(sj.counts, torch.int16, 'counts'),
-        _ptr(sj.wave_start, torch.int32, 'wave_start'), sj.n_slices,
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y') if Y is not None else 0,
-        n_rows, F, flags, _ptr(bias, torch.float32, 'bias'),
-        _ptr(acc_in, torch.float32, 'acc_in'), _ld(acc_in, 'acc_in') if acc_in is not None else 0,
-        _ptr(acc_out, torch.float32, 'acc_out'), _ld(acc_out, 'acc_out') if acc_out is not None else 0,
-        float(acc_div) if acc_div is not None else 1.0,
-        _ptr(Wnext, torch.float32, 'Wnext'), Cn, _ptr(Hnext, torch.float32, 'Hnext'),
-        _ld(Hnext, 'Hnext') if Hnext is not None else 0, _stream())
-    _check(code, 'amar_spmm_sj_f32')
+    flags, tail = _spmm_epilogue('spmm_sj', n_rows, F, Y, bias, relu, acc_in, acc_out, acc_div, Wnext, Hnext)
+    _launch('amar_spmm_sj_f32', _ptr(sj.entries, I32, 'entries'), _ptr(sj.counts, torch.int16, 'counts'), _ptr(sj.wave_start, I32, 'wave_start'),
+            sj.n_slices, *_mat(X, 'X'), *_mat(Y, 'Y'), n_rows, F, flags, *tail)
 
 
 def spmm_xs(xs, X, Y=None, bias=None, relu=False, acc_in=None, acc_out=None, acc_div=None, Wnext=None, Hnext=None,
@@ -296,56 +354,34 @@ def spmm_xs(xs, X, Y=None, bias=None, relu=False, acc_in=None, acc_out=None, acc
                        prescaled=prescaled, scale_next=scale_next, xself=xself, rows_needed=rows_needed)
     n_rows = xs.shape[0]
     F = X.shape[1]
-    flags = (SPMM_BIAS if bias is not None else 0) | (SPMM_RELU if relu else 0)
-    if acc_out is not None:
-        flags |= SPMM_ACCUM | (SPMM_ACCUM_DIV if acc_div is not None else 0)
-        if acc_in is None or tuple(acc_in.shape) != (n_rows, F) or tuple(acc_out.shape) != (n_rows, F):
-            raise ValueError("acc_in/acc_out must be [n_rows, F]")
-    if Y is not None and tuple(Y.shape) != (n_rows, F):
-        raise ValueError("Y must be [n_rows, F]")
     diag_offset = int(getattr(xs, 'diag_offset', 0))
     if X.shape[0] != xs.shape[1] or diag_offset + n_rows > X.shape[0]:
         raise ValueError("X must have one row per column of the matrix")
-    Cn = 0
-    if Wnext is not None:
-        if Wnext.shape[0] != F or not Wnext.is_contiguous() or Hnext is None or tuple(Hnext.shape) != (n_rows, Wnext.shape[1]):
-            raise ValueError("spmm_xs: Wnext [F, Cn] contiguous and Hnext [n_rows, Cn] expected")
-        Cn = Wnext.shape[1]
-    P = xs.partials(F)
     row_scale = getattr(xs, 'row_scale', None)
     if row_scale is None and (prescaled or scale_next):
         raise ValueError("spmm_xs: prescaled / scale_next need a value-free image")
+    flags, tail = _spmm_epilogue('spmm_xs', n_rows, F, Y, bias, relu, acc_in, acc_out, acc_div, Wnext, Hnext)
+    P = xs.partials(F)
     if row_scale is not None and not prescaled:
         col_scale = getattr(xs, 'col_scale', None)
-        Xs = torch.empty((X.shape[0], F), dtype=torch.float32, device=X.device)
-        row_affine(X, col_scale if col_scale is not None else row_scale, Xs)
-        X = Xs
+        X = _scaled_table(X, col_scale if col_scale is not None else row_scale)
     if scale_next:
         flags |= SPMM_SCALE_NEXT
-    code = load().amar_spmm_xs_f32(
-        _ptr(xs.diag, torch.float32, 'diag'), _ptr(xs.rowptr, torch.int32, 'rowptr'), _ptr(xs.colidx, torch.int32, 'colidx'),
-        _ptr(xs.vals, torch.float32, 'vals'), _ptr(row_scale, torch.float32, 'row_scale'), xs.n_slices,
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), X.shape[0], _xself_ptr(xself, X, diag_offset, n_rows, prescaled or row_scale is None),
-        _ptr(P, torch.float32, 'partials'),
-        _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y') if Y is not None else 0,
-        n_rows, F, flags, _ptr(bias, torch.float32, 'bias'),
-        _ptr(acc_in, torch.float32, 'acc_in'), _ld(acc_in, 'acc_in') if acc_in is not None else 0,
-        _ptr(acc_out, torch.float32, 'acc_out'), _ld(acc_out, 'acc_out') if acc_out is not None else 0,
-        float(acc_div) if acc_div is not None else 1.0,
-        _ptr(Wnext, torch.float32, 'Wnext'), Cn, _ptr(Hnext, torch.float32, 'Hnext'),
-        _ld(Hnext, 'Hnext') if Hnext is not None else 0, _stream())
-    _check(code, 'amar_spmm_xs_f32')
+    _launch('amar_spmm_xs_f32', _ptr(xs.diag, F32, 'diag'), _ptr(xs.rowptr, I32, 'rowptr'), _ptr(xs.colidx, I32, 'colidx'), _ptr(xs.vals, F32, 'vals'),
+            _ptr(row_scale, F32, 'row_scale'), xs.n_slices, *_mat(X, 'X'), X.shape[0],
+            _xself_ptr(xself, X, diag_offset, n_rows, prescaled or row_scale is None), _ptr(P, F32, 'partials'),
+            *_mat(Y, 'Y'), n_rows, F, flags, *tail)
 
 
 def _xself_ptr(xself, X, diag_offset, n_rows, usable):
     """The pointer the SpMM kernels read the rows' own entries of X through: `xself` when given, else X[diag_offset:] (None: X)."""
     if xself is None:
-        return _ptr(X[diag_offset:], torch.float32, 'X') if diag_offset else None
+        return _ptr(X[diag_offset:], F32, 'X') if diag_offset else None
     if not usable:
         raise ValueError("xself needs the table as the kernel gathers it (prescaled=True on a value-free image)")
     if tuple(xself.shape) != (n_rows, X.shape[1]) or _ld(xself, 'xself') != _ld(X, 'X'):
         raise ValueError("xself must be [n_rows, F] with the leading dimension of X")
-    return _ptr(xself, torch.float32, 'xself')
+    return _ptr(xself, F32, 'xself')
 
 
 def spmm_lt(lt, X, Y=None, bias=None, relu=False, acc_in=None, acc_out=None, acc_div=None, Wnext=None, Hnext=None,
@@ -361,34 +397,22 @@ def spmm_lt(lt, X, Y=None, bias=None, relu=False, acc_in=None, acc_out=None, acc
             raise ValueError("spmm_lt: sage_tail takes the un-scaled table (prescaled=True), Y, and no other epilogue")
         if Hnext is not None and tuple(Hnext.shape) != (n_rows, F):
             raise ValueError("spmm_lt: with sage_tail, Hnext is a second [n_rows, F] copy of Y")
-        Wnext, bias = sage_tail
-        if tuple(Wnext.shape) != (2 * F, F) or not Wnext.is_contiguous() or bias.numel() != F:
+        kernel, kernel_bias = sage_tail
+        if tuple(kernel.shape) != (2 * F, F) or not kernel.is_contiguous() or kernel_bias.numel() != F:
             raise ValueError("spmm_lt: sage_tail = (kernel [2F, F] contiguous, bias [F]) expected")
     if F != lt.F:
         raise ValueError("spmm_lt: the image was built for width {}, X is {} wide".format(lt.F, F))
     from deep_cbrs_amar_renaissance_amd.utilities import lds_tiled
     if lt.rw > lds_tiled.geometry(F)[1]:
         raise ValueError("spmm_lt: the image's tiles hold {} rows per wave, the kernel's {}".format(lt.rw, lds_tiled.geometry(F)[1]))
-    flags = (SPMM_SAGE_TAIL if sage_tail is not None else (SPMM_BIAS if bias is not None else 0) | (SPMM_RELU if relu else 0))
-    if acc_out is not None:
-        flags |= SPMM_ACCUM | (SPMM_ACCUM_DIV if acc_div is not None else 0)
-        if acc_in is None or tuple(acc_in.shape) != (n_rows, F) or tuple(acc_out.shape) != (n_rows, F):
-            raise ValueError("acc_in/acc_out must be [n_rows, F]")
-    if Y is not None and tuple(Y.shape) != (n_rows, F):
-        raise ValueError("Y must be [n_rows, F]")
     if X.shape[0] != n_cols or lt.diag_offset + n_rows > X.shape[0]:
         raise ValueError("X must have one row per column of the matrix")
-    Cn = 0
+    flags, tail = _spmm_epilogue('spmm_lt', n_rows, F, Y, bias, relu, acc_in, acc_out, acc_div, Wnext, Hnext)
     if sage_tail is not None:
-        Cn = F
-    elif Wnext is not None:
-        if Wnext.shape[0] != F or not Wnext.is_contiguous() or Hnext is None or tuple(Hnext.shape) != (n_rows, Wnext.shape[1]):
-            raise ValueError("spmm_lt: Wnext [F, Cn] contiguous and Hnext [n_rows, Cn] expected")
-        Cn = Wnext.shape[1]
+        # (no other epilogue came through the checks above) the tail's kernel and bias travel in the Wnext / Cn and bias places
+        flags, tail = SPMM_SAGE_TAIL, (_ptr(kernel_bias, F32, 'bias'), *tail[1:6], _ptr(kernel, F32, 'Wnext'), F, *tail[8:])
     if not prescaled:
-        Xs = torch.empty((X.shape[0], F), dtype=torch.float32, device=X.device)
-        row_affine(X, lt.col_scale if lt.col_scale is not None else lt.row_scale, Xs)
-        X = Xs
+        X = _scaled_table(X, lt.col_scale if lt.col_scale is not None else lt.row_scale)
     if scale_next:
         flags |= SPMM_SCALE_NEXT
     if not getattr(lt, 'pairs', True):
@@ -404,19 +428,14 @@ def spmm_lt(lt, X, Y=None, bias=None, relu=False, acc_in=None, acc_out=None, acc
         n_tiles = cache[rows_needed]
         if n_tiles == 0:
             return
-    code = load().amar_spmm_lt_f32(
-        _ptr(lt.words, torch.int32, 'words'), _ptr(lt.stream_start, torch.int32, 'stream_start'),
-        _ptr(lt.wsteps, torch.int32, 'wsteps'), _ptr(lt.tile_row0, torch.int32, 'tile_row0'), _ptr(lt.n_win, torch.int32, 'n_win'),
-        _ptr(lt.vstart, torch.int32, 'vstart'), _ptr(lt.vcount, torch.int32, 'vcount'), n_tiles, lt.maxwin1, lt.pace_every, _ptr(lt.diag, torch.float32, 'diag'), _ptr(lt.row_scale, torch.float32, 'row_scale'),
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), X.shape[0], _xself_ptr(xself, X, off, n_rows, prescaled),
-        _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y') if Y is not None else 0,
-        n_rows, F, flags, _ptr(bias, torch.float32, 'bias'),
-        _ptr(acc_in, torch.float32, 'acc_in'), _ld(acc_in, 'acc_in') if acc_in is not None else 0,
-        _ptr(acc_out, torch.float32, 'acc_out'), _ld(acc_out, 'acc_out') if acc_out is not None else 0,
-        float(acc_div) if acc_div is not None else 1.0,
-        _ptr(Wnext, torch.float32, 'Wnext'), Cn, _ptr(Hnext, torch.float32, 'Hnext'),
-        _ld(Hnext, 'Hnext') if Hnext is not None else 0, _stream())
-    _check(code, 'amar_spmm_lt_f32')
+    _launch('amar_spmm_lt_f32', *_lt_image_args(lt, n_tiles), _ptr(lt.diag, F32, 'diag'), _ptr(lt.row_scale, F32, 'row_scale'),
+            *_mat(X, 'X'), X.shape[0], _xself_ptr(xself, X, off, n_rows, prescaled), *_mat(Y, 'Y'), n_rows, F, flags, *tail)
+
+
+def _lt_image_args(lt, n_tiles):
+    """What amar_spmm_lt_f32 and amar_gat_lt_f32 take first: the arrays of an LDS-tiled image and its tile count, window bound and pace."""
+    return (_ptr(lt.words, I32, 'words'), _ptr(lt.stream_start, I32, 'stream_start'), _ptr(lt.wsteps, I32, 'wsteps'), _ptr(lt.tile_row0, I32, 'tile_row0'),
+            _ptr(lt.n_win, I32, 'n_win'), _ptr(lt.vstart, I32, 'vstart'), _ptr(lt.vcount, I32, 'vcount'), n_tiles, lt.maxwin1, lt.pace_every)
 
 
 PROPAGATE_KINDS = {'lt': 0, 'gat_lt': 1, 'xs': 2, 'gat_xs': 3}
@@ -424,14 +443,11 @@ ADDR_64, ADDR_32, ADDR_32_DENSE = 0, 1, 2
 LT_KERNELS = ('pairs', 'nopairs', 'sage_tail', 'unsupported')
 
 
-class PropagateRouteInfo(ctypes.Structure):
+class PropagateRouteInfo(_RouteInfo):
     """include/amar_hip.h: amar_propagate_route_info"""
     _fields_ = [(name, ctypes.c_int32) for name in ('form', 'kernel', 'col_bits', 'reserved')] + \
                [(name, ctypes.c_int64) for name in ('max_cols', 'span_bytes')]
-
-    def as_dict(self):
-        return {'form': int(self.form), 'kernel': LT_KERNELS[self.kernel], 'col_bits': int(self.col_bits),
-                'max_cols': int(self.max_cols), 'span_bytes': int(self.span_bytes)}
+    KERNELS, HIDDEN = LT_KERNELS, ('reserved',)
 
 
 def propagate_route(kind, n_cols, ld, width, flags=0, code=False):
@@ -462,18 +478,9 @@ def gcn_layer(rowptr, colidx, vals, H, bias, Y, Wnext=None, Hnext=None):
     C = H.shape[1]
     if tuple(Y.shape) != (n_rows, C) or bias.numel() != C or H.shape[0] < n_rows:
         raise ValueError("gcn_layer: H [>=n_rows, C], bias [C], Y [n_rows, C] expected")
-    Cn = 0
-    if Wnext is not None:
-        if Wnext.shape[0] != C or not Wnext.is_contiguous() or Hnext is None or tuple(Hnext.shape) != (n_rows, Wnext.shape[1]):
-            raise ValueError("gcn_layer: Wnext [C, Cn] contiguous and Hnext [n_rows, Cn] expected")
-        Cn = Wnext.shape[1]
-    code = load().amar_gcn_layer_f32(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), _ptr_entries(vals, torch.float32, 'vals'),
-        _ptr(H, torch.float32, 'H'), _ld(H, 'H'), C, _ptr(bias, torch.float32, 'bias'),
-        _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
-        _ptr(Wnext, torch.float32, 'Wnext'), Cn, _ptr(Hnext, torch.float32, 'Hnext'),
-        _ld(Hnext, 'Hnext') if Hnext is not None else 0, n_rows, _stream())
-    _check(code, 'amar_gcn_layer_f32')
+    product = _next_product('gcn_layer', 'C', n_rows, C, Wnext, Hnext)
+    _launch('amar_gcn_layer_f32', _ptr(rowptr, I32, 'rowptr'), _ptr_entries(colidx, I32, 'colidx'), _ptr_entries(vals, F32, 'vals'),
+            *_mat(H, 'H'), C, _ptr(bias, F32, 'bias'), *_mat(Y, 'Y'), *product, n_rows)
 
 
 def rowwise_xw(X, W, H, copy_to=None, a_self=None, a_neigh=None, s_self=None, s_neigh=None, row_scale=None, row_ids=None):
@@ -487,10 +494,8 @@ def rowwise_xw(X, W, H, copy_to=None, a_self=None, a_neigh=None, s_self=None, s_
             raise ValueError("rowwise_xw: W [F, C] contiguous, row_ids contiguous and H [len(row_ids), C] expected")
         if row_scale is not None and (row_scale.numel() != n_out or not row_scale.is_contiguous()):
             raise ValueError("rowwise_xw: row_scale must be a contiguous [len(row_ids)] vector")
-        code = load().amar_rowwise_xw_gather_f32(
-            _ptr(X, torch.float32, 'X'), _ld(X, 'X'), F, _ptr(row_ids, torch.int32, 'row_ids'), _ptr(W, torch.float32, 'W'), W.shape[1],
-            _ptr(H, torch.float32, 'H'), _ld(H, 'H'), _ptr(row_scale, torch.float32, 'row_scale'), n_out, _stream())
-        _check(code, 'amar_rowwise_xw_gather_f32')
+        _launch('amar_rowwise_xw_gather_f32', *_mat(X, 'X'), F, _ptr(row_ids, I32, 'row_ids'), _ptr(W, F32, 'W'), W.shape[1], *_mat(H, 'H'),
+                _ptr(row_scale, F32, 'row_scale'), n_out)
         return
     n_rows, F = X.shape
     if W.shape[0] != F or not W.is_contiguous() or tuple(H.shape) != (n_rows, W.shape[1]):
@@ -502,14 +507,9 @@ def rowwise_xw(X, W, H, copy_to=None, a_self=None, a_neigh=None, s_self=None, s_
     for v, nm in ((s_self, 's_self'), (s_neigh, 's_neigh')):
         if v is not None and (v.numel() != n_rows or not v.is_contiguous()):
             raise ValueError("rowwise_xw: {} must be a contiguous [n_rows] vector".format(nm))
-    code = load().amar_rowwise_xw_f32(
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), F, _ptr(W, torch.float32, 'W'), W.shape[1],
-        _ptr(H, torch.float32, 'H'), _ld(H, 'H'),
-        _ptr(copy_to, torch.float32, 'copy_to'), _ld(copy_to, 'copy_to') if copy_to is not None else 0,
-        _ptr(a_self, torch.float32, 'a_self'), _ptr(a_neigh, torch.float32, 'a_neigh'),
-        _ptr(s_self, torch.float32, 's_self'), _ptr(s_neigh, torch.float32, 's_neigh'),
-        _ptr(row_scale, torch.float32, 'row_scale'), n_rows, _stream())
-    _check(code, 'amar_rowwise_xw_f32')
+    _launch('amar_rowwise_xw_f32', *_mat(X, 'X'), F, _ptr(W, F32, 'W'), W.shape[1], *_mat(H, 'H'), *_mat(copy_to, 'copy_to'),
+            _ptr(a_self, F32, 'a_self'), _ptr(a_neigh, F32, 'a_neigh'), _ptr(s_self, F32, 's_self'), _ptr(s_neigh, F32, 's_neigh'),
+            _ptr(row_scale, F32, 'row_scale'), n_rows)
 
 
 def sage_layer(rowptr, colidx, X, W, bias, Y, self_loop=True):
@@ -518,11 +518,8 @@ def sage_layer(rowptr, colidx, X, W, bias, Y, self_loop=True):
     if W.shape[0] != 2 * F or not W.is_contiguous() or bias.numel() != W.shape[1] or \
             tuple(Y.shape) != (n_rows, W.shape[1]) or X.shape[0] < n_rows:
         raise ValueError("sage_layer: W [2F, C] contiguous, bias [C], Y [n_rows, C] expected")
-    code = load().amar_sage_layer_f32(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'),
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), F, _ptr(W, torch.float32, 'W'), _ptr(bias, torch.float32, 'bias'),
-        W.shape[1], _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'), 1 if self_loop else 0, n_rows, _stream())
-    _check(code, 'amar_sage_layer_f32')
+    _launch('amar_sage_layer_f32', _ptr(rowptr, I32, 'rowptr'), _ptr_entries(colidx, I32, 'colidx'), *_mat(X, 'X'), F, _ptr(W, F32, 'W'),
+            _ptr(bias, F32, 'bias'), W.shape[1], *_mat(Y, 'Y'), 1 if self_loop else 0, n_rows)
 
 
 def sage_tail(X, agg, W, bias, Y):
@@ -531,10 +528,7 @@ def sage_tail(X, agg, W, bias, Y):
     if X.shape[1] != F or X.shape[0] < n_rows or W.shape[0] != 2 * F or not W.is_contiguous() or bias.numel() != W.shape[1] or \
             tuple(Y.shape) != (n_rows, W.shape[1]):
         raise ValueError("sage_tail: X [>=n_rows, F], agg [n_rows, F], W [2F, C] contiguous, bias [C], Y [n_rows, C] expected")
-    code = load().amar_sage_tail_f32(_ptr(X, torch.float32, 'X'), _ld(X, 'X'), _ptr(agg, torch.float32, 'agg'), _ld(agg, 'agg'), F,
-                                     _ptr(W, torch.float32, 'W'), _ptr(bias, torch.float32, 'bias'), W.shape[1],
-                                     _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'), n_rows, _stream())
-    _check(code, 'amar_sage_tail_f32')
+    _launch('amar_sage_tail_f32', *_mat(X, 'X'), *_mat(agg, 'agg'), F, _ptr(W, F32, 'W'), _ptr(bias, F32, 'bias'), W.shape[1], *_mat(Y, 'Y'), n_rows)
 
 
 def sage_tail_supported(F, C):
@@ -554,11 +548,8 @@ def sage_layer_agg(rowptr, colidx, X, W, bias, Y, op, self_loop=True):
     if W.shape[0] != 2 * F or not W.is_contiguous() or bias.numel() != W.shape[1] or \
             tuple(Y.shape) != (n_rows, W.shape[1]) or X.shape[0] < n_rows:
         raise ValueError("sage_layer_agg: W [2F, C] contiguous, bias [C], Y [n_rows, C] expected")
-    code = load().amar_sage_layer_agg_f32(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'),
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), F, _ptr(W, torch.float32, 'W'), _ptr(bias, torch.float32, 'bias'),
-        W.shape[1], _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'), 1 if self_loop else 0, _agg_code(op, 'sage_layer_agg'), n_rows, _stream())
-    _check(code, 'amar_sage_layer_agg_f32')
+    _launch('amar_sage_layer_agg_f32', _ptr(rowptr, I32, 'rowptr'), _ptr_entries(colidx, I32, 'colidx'), *_mat(X, 'X'), F, _ptr(W, F32, 'W'),
+            _ptr(bias, F32, 'bias'), W.shape[1], *_mat(Y, 'Y'), 1 if self_loop else 0, _agg_code(op, 'sage_layer_agg'), n_rows)
 
 
 def sage_agg_layer_supported(F, C):
@@ -571,12 +562,8 @@ def sage_aggregate(rowptr, colidx, X, agg, op, cnt=None, self_loop=True):
     F = X.shape[1]
     if tuple(agg.shape) != (n_rows, F) or X.shape[0] < n_rows or (cnt is not None and tuple(cnt.shape) != (n_rows, F)):
         raise ValueError("sage_aggregate: X [>=n_rows, F], agg [n_rows, F], cnt [n_rows, F] or None expected")
-    code = load().amar_sage_aggregate_f32(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'),
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), F, _ptr(agg, torch.float32, 'agg'), _ld(agg, 'agg'),
-        _ptr(cnt, torch.float32, 'cnt'), _ld(cnt, 'cnt') if cnt is not None else 0,
-        1 if self_loop else 0, _agg_code(op, 'sage_aggregate'), n_rows, _stream())
-    _check(code, 'amar_sage_aggregate_f32')
+    _launch('amar_sage_aggregate_f32', _ptr(rowptr, I32, 'rowptr'), _ptr_entries(colidx, I32, 'colidx'), *_mat(X, 'X'), F, *_mat(agg, 'agg'),
+            *_mat(cnt, 'cnt'), 1 if self_loop else 0, _agg_code(op, 'sage_aggregate'), n_rows)
 
 
 def sage_aggregate_bwd(rowptr, colidx, X, agg, cnt, d_agg, dX, self_loop=True, pack=None):
@@ -595,25 +582,23 @@ def sage_aggregate_bwd(rowptr, colidx, X, agg, cnt, d_agg, dX, self_loop=True, p
         pack = torch.empty((n_rows, 2 * F), dtype=torch.float32, device=X.device)
     if tuple(pack.shape) != (n_rows, 2 * F) or not pack.is_contiguous():
         raise ValueError("sage_aggregate_bwd: pack [n_rows, 2F] contiguous expected")
-    code = load().amar_sage_aggregate_bwd_f32(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'),
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), _ptr(agg, torch.float32, 'agg'), _ld(agg, 'agg'),
-        _ptr(cnt, torch.float32, 'cnt'), _ld(cnt, 'cnt'), _ptr(d_agg, torch.float32, 'd_agg'), _ld(d_agg, 'd_agg'), F,
-        _ptr(pack, torch.float32, 'pack'), _ptr(dX, torch.float32, 'dX'), _ld(dX, 'dX'), 1 if self_loop else 0, n_rows, _stream())
-    _check(code, 'amar_sage_aggregate_bwd_f32')
+    _launch('amar_sage_aggregate_bwd_f32', _ptr(rowptr, I32, 'rowptr'), _ptr_entries(colidx, I32, 'colidx'), *_mat(X, 'X'), *_mat(agg, 'agg'),
+            *_mat(cnt, 'cnt'), *_mat(d_agg, 'd_agg'), F, _ptr(pack, F32, 'pack'), *_mat(dX, 'dX'), 1 if self_loop else 0, n_rows)
 
 
-def gat_layer(rowptr, colidx, H, s_self, s_neigh, bias, Y, self_loop=True):
+def _gat_layer(what, rowptr, colidx, H, s_self, s_neigh, bias, Y, self_loop, drop):
+    """gat_layer (drop None) and gat_layer_dropout: amar_gat_layer_f32 / amar_gat_layer_dropout_f32, which ends with the dropout site."""
     n_rows = rowptr.numel() - 1
     C = H.shape[1]
     if tuple(Y.shape) != (n_rows, C) or bias.numel() != C or s_self.numel() < n_rows or s_neigh.numel() < H.shape[0]:
-        raise ValueError("gat_layer: bias [C], Y [n_rows, C], s_self/s_neigh [n] expected")
-    code = load().amar_gat_layer_f32(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'),
-        _ptr(H, torch.float32, 'H'), _ld(H, 'H'), C, _ptr(s_self, torch.float32, 's_self'),
-        _ptr(s_neigh, torch.float32, 's_neigh'), _ptr(bias, torch.float32, 'bias'),
-        _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'), 1 if self_loop else 0, n_rows, _stream())
-    _check(code, 'amar_gat_layer_f32')
+        raise ValueError("{}: bias [C], Y [n_rows, C], s_self/s_neigh [n] expected".format(what))
+    _launch('amar_gat_layer_f32' if drop is None else 'amar_gat_layer_dropout_f32', _ptr(rowptr, I32, 'rowptr'), _ptr_entries(colidx, I32, 'colidx'),
+            *_mat(H, 'H'), C, _ptr(s_self, F32, 's_self'), _ptr(s_neigh, F32, 's_neigh'), _ptr(bias, F32, 'bias'), *_mat(Y, 'Y'),
+            1 if self_loop else 0, n_rows, *(drop._args() if drop is not None else ()))
+
+
+def gat_layer(rowptr, colidx, H, s_self, s_neigh, bias, Y, self_loop=True):
+    _gat_layer('gat_layer', rowptr, colidx, H, s_self, s_neigh, bias, Y, self_loop, None)
 
 
 GAT_HEADS_MAX_WIDTH = 64                                             # heads * channels the multi-head row kernels hold in one wavefront's lanes
@@ -634,10 +619,8 @@ def rowwise_xw_heads(X, W, Hd, a_self, a_neigh, S):
     if tuple(Hd.shape) != (n_rows, heads * C) or tuple(S.shape) != (n_rows, 2 * heads) or not S.is_contiguous() or \
             any(v.numel() != C * heads or not v.is_contiguous() for v in (a_self, a_neigh)):
         raise ValueError("rowwise_xw_heads: Hd [n, heads*C], S [n, 2*heads] contiguous, a_self / a_neigh [C, heads, 1] contiguous expected")
-    code = load().amar_rowwise_xw_heads_f32(
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), F, _ptr(W, torch.float32, 'W'), heads, C, _ptr(Hd, torch.float32, 'Hd'), _ld(Hd, 'Hd'),
-        _ptr(a_self, torch.float32, 'a_self'), _ptr(a_neigh, torch.float32, 'a_neigh'), _ptr(S, torch.float32, 'S'), n_rows, _stream())
-    _check(code, 'amar_rowwise_xw_heads_f32')
+    _launch('amar_rowwise_xw_heads_f32', *_mat(X, 'X'), F, _ptr(W, F32, 'W'), heads, C, *_mat(Hd, 'Hd'), _ptr(a_self, F32, 'a_self'),
+            _ptr(a_neigh, F32, 'a_neigh'), _ptr(S, F32, 'S'), n_rows)
 
 
 def _gat_heads_shapes(what, rowptr, Hd, heads, S, bias, Y, concat):
@@ -656,11 +639,8 @@ def gat_heads(rowptr, colidx, Hd, heads, S, bias, Y, concat=True, self_loop=True
     n, C = _gat_heads_shapes('gat_heads', rowptr, Hd, heads, S, bias, Y, concat)
     if out_tape is not None and (tuple(out_tape.shape) != (n, heads * C) or not out_tape.is_contiguous()):
         raise ValueError("gat_heads: out_tape must be a contiguous [n, heads*C] buffer")
-    code = load().amar_gat_heads_f32(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), _ptr(Hd, torch.float32, 'Hd'), _ld(Hd, 'Hd'), heads, C,
-        _ptr(S, torch.float32, 'S'), _ptr(bias, torch.float32, 'bias'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
-        _ptr(out_tape, torch.float32, 'out_tape'), 1 if concat else 0, 1 if self_loop else 0, n, _stream())
-    _check(code, 'amar_gat_heads_f32')
+    _launch('amar_gat_heads_f32', _ptr(rowptr, I32, 'rowptr'), _ptr_entries(colidx, I32, 'colidx'), *_mat(Hd, 'Hd'), heads, C, _ptr(S, F32, 'S'),
+            _ptr(bias, F32, 'bias'), *_mat(Y, 'Y'), _ptr(out_tape, F32, 'out_tape'), 1 if concat else 0, 1 if self_loop else 0, n)
 
 
 def gat_heads_bwd(rowptr, colidx, Hd, heads, S, Y, dY, bias, a_self, a_neigh, concat=True, self_loop=True, out_tape=None, transposed=None):
@@ -678,14 +658,11 @@ def gat_heads_bwd(rowptr, colidx, Hd, heads, S, Y, dY, bias, a_self, a_neigh, co
     scratch = torch.empty(3 * heads * n, dtype=torch.float32, device=dev)
     dS = torch.empty((n, 2 * heads), dtype=torch.float32, device=dev)
     dHd = torch.empty((n, heads * C), dtype=torch.float32, device=dev)
-    t_ptrs = _transposed_ptrs(transposed, n, colidx) or (_ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'))
-    code = load().amar_gat_heads_bwd_f32(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), *t_ptrs,
-        _ptr(Hd, torch.float32, 'Hd'), _ld(Hd, 'Hd'), heads, C, _ptr(S, torch.float32, 'S'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
-        _ptr(dY, torch.float32, 'dY'), _ld(dY, 'dY'), _ptr(bias, torch.float32, 'bias'), _ptr(a_self, torch.float32, 'a_self'),
-        _ptr(a_neigh, torch.float32, 'a_neigh'), _ptr(out_tape, torch.float32, 'out_tape'), _ptr(dout), _ptr(scratch), _ptr(dS), _ptr(dHd),
-        heads * C, 1 if concat else 0, 1 if self_loop else 0, n, _stream())
-    _check(code, 'amar_gat_heads_bwd_f32')
+    structure = (_ptr(rowptr, I32, 'rowptr'), _ptr_entries(colidx, I32, 'colidx'))
+    _launch('amar_gat_heads_bwd_f32', *structure, *(_transposed_ptrs(transposed, n, colidx) or structure), *_mat(Hd, 'Hd'), heads, C,
+            _ptr(S, F32, 'S'), *_mat(Y, 'Y'), *_mat(dY, 'dY'), _ptr(bias, F32, 'bias'), _ptr(a_self, F32, 'a_self'), _ptr(a_neigh, F32, 'a_neigh'),
+            _ptr(out_tape, F32, 'out_tape'), _ptr(dout), _ptr(scratch), _ptr(dS), _ptr(dHd), heads * C, 1 if concat else 0,
+            1 if self_loop else 0, n)
     return dout, dS, dHd
 
 
@@ -702,19 +679,16 @@ def gat_xs(xs, H, s_self, s_neigh, bias, Y, self_loop=True):
         scratch[C] = (torch.empty((n_cols, 2 * C), dtype=torch.float32, device=H.device),
                       torch.empty((xs.n_slices, n, 2 * C), dtype=torch.float32, device=H.device))
     packed, partials = scratch[C]
-    code = load().amar_gat_xs_f32(
-        _ptr(xs.rowptr, torch.int32, 'rowptr'), _ptr(xs.colidx, torch.int32, 'colidx'), xs.n_slices,
-        _ptr(H, torch.float32, 'H'), _ld(H, 'H'), C, _ptr(s_self, torch.float32, 's_self'), _ptr(s_neigh, torch.float32, 's_neigh'),
-        _ptr(bias, torch.float32, 'bias'), _ptr(packed), _ptr(partials), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
-        1 if self_loop else 0, n, n_cols, row_offset, _stream())
-    _check(code, 'amar_gat_xs_f32')
+    _launch('amar_gat_xs_f32', _ptr(xs.rowptr, I32, 'rowptr'), _ptr(xs.colidx, I32, 'colidx'), xs.n_slices, *_mat(H, 'H'), C,
+            _ptr(s_self, F32, 's_self'), _ptr(s_neigh, F32, 's_neigh'), _ptr(bias, F32, 'bias'), _ptr(packed), _ptr(partials), *_mat(Y, 'Y'),
+            1 if self_loop else 0, n, n_cols, row_offset)
 
 
 def colmax(x, out):
     """out[0] = max(x) (a 1-element float32 device tensor), in-stream."""
     if not x.is_contiguous() or out.numel() < 1:
         raise ValueError("colmax: contiguous x and a 1-element out expected")
-    _check(load().amar_colmax_f32(_ptr(x, torch.float32, 'x'), x.numel(), _ptr(out, torch.float32, 'out'), _stream()), 'amar_colmax_f32')
+    _launch('amar_colmax_f32', _ptr(x, F32, 'x'), x.numel(), _ptr(out, F32, 'out'))
 
 
 def gat_lt(lt, csr, H, s_self, s_neigh, bias, Y, self_loop=True):
@@ -729,62 +703,45 @@ def gat_lt(lt, csr, H, s_self, s_neigh, bias, Y, self_loop=True):
         raise ValueError("gat_lt: the CSR and the image must describe the same block")
     bmax = lt.__dict__.setdefault('_gat_bound', torch.empty(1, dtype=torch.float32, device=H.device))
     colmax(s_neigh, bmax)
-    code = load().amar_gat_lt_f32(
-        _ptr(lt.words, torch.int32, 'words'), _ptr(lt.stream_start, torch.int32, 'stream_start'),
-        _ptr(lt.wsteps, torch.int32, 'wsteps'), _ptr(lt.tile_row0, torch.int32, 'tile_row0'), _ptr(lt.n_win, torch.int32, 'n_win'),
-        _ptr(lt.vstart, torch.int32, 'vstart'), _ptr(lt.vcount, torch.int32, 'vcount'), lt.n_tiles, lt.maxwin1, lt.pace_every,
-        int(lt.rw), _ptr(lt.diag, torch.float32, 'diag'), _ptr(csr.rowptr, torch.int32, 'rowptr'), _ptr_entries(csr.colidx, torch.int32, 'colidx'),
-        _ptr(H, torch.float32, 'H'), _ld(H, 'H'), C, _ptr(s_self, torch.float32, 's_self'), _ptr(s_neigh, torch.float32, 's_neigh'),
-        _ptr(bmax, torch.float32, 'bmax'), _ptr(bias, torch.float32, 'bias'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
-        1 if self_loop else 0, n, n_cols, row_offset, _stream())
-    _check(code, 'amar_gat_lt_f32')
+    _launch('amar_gat_lt_f32', *_lt_image_args(lt, lt.n_tiles), int(lt.rw), _ptr(lt.diag, F32, 'diag'), _ptr(csr.rowptr, I32, 'rowptr'),
+            _ptr_entries(csr.colidx, I32, 'colidx'), *_mat(H, 'H'), C, _ptr(s_self, F32, 's_self'), _ptr(s_neigh, F32, 's_neigh'), _ptr(bmax, F32, 'bmax'),
+            _ptr(bias, F32, 'bias'), *_mat(Y, 'Y'), 1 if self_loop else 0, n, n_cols, row_offset)
 
 
 DENSE_WT = 0x100
 
 
-def dense(X, W, bias, Y, act='relu', ids=None, w_transposed=False):
-    """Y = act(X[ids] . W + bias). Y may be a column slice of a wider buffer (concatenation).
-    w_transposed: W holds the transpose ([N, K]), i.e. Y = X . W^T — the reverse pass' dX = dZ . W^T without a transpose launch."""
+def _dense_args(X, W, bias, Y, act, ids, w_transposed, check_bias):
+    """The argument list of amar_dense_f32 / amar_dense_route without the last one.  check_bias: the launcher's check of the bias,
+    which the route query does not make."""
     K, N = (W.shape[1], W.shape[0]) if w_transposed else W.shape
     M = ids.numel() if ids is not None else X.shape[0]
     if X.shape[1] != K or not W.is_contiguous() or tuple(Y.shape) != (M, N):
         raise ValueError("dense: X [*, K], W [K, N] contiguous, Y [M, N] expected")
-    if bias is not None and (bias.numel() != N or not bias.is_contiguous()):
+    if check_bias and bias is not None and (bias.numel() != N or not bias.is_contiguous()):
         raise ValueError("dense: bias must be a contiguous [N] vector")
-    code = load().amar_dense_f32(
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), _ptr(ids, torch.int32, 'ids'),
-        _ptr(W, torch.float32, 'W'), _ptr(bias, torch.float32, 'bias'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
-        M, K, N, ACT_CODES[act] | (DENSE_WT if w_transposed else 0), _stream())
-    _check(code, 'amar_dense_f32')
+    return [*_mat(X, 'X'), _ptr(ids, I32, 'ids'), _ptr(W, F32, 'W'), _ptr(bias, F32, 'bias'), *_mat(Y, 'Y'), M, K, N,
+            ACT_CODES[act] | (DENSE_WT if w_transposed else 0)]
 
 
-class DenseRouteInfo(ctypes.Structure):
+def dense(X, W, bias, Y, act='relu', ids=None, w_transposed=False):
+    """Y = act(X[ids] . W + bias). Y may be a column slice of a wider buffer (concatenation).
+    w_transposed: W holds the transpose ([N, K]), i.e. Y = X . W^T — the reverse pass' dX = dZ . W^T without a transpose launch."""
+    _launch('amar_dense_f32', *_dense_args(X, W, bias, Y, act, ids, w_transposed, check_bias=True))
+
+
+class DenseRouteInfo(_RouteInfo):
     """include/amar_hip.h: amar_dense_route_info"""
     _fields_ = [(name, ctypes.c_int32) for name in ('kernel', 'vec_x', 'vec_w', 'w_trans', 'grid_x', 'grid_y', 'n_col_blocks', 'launches')]
     KERNELS = {0: 'small', 1: 'tile128', 2: 'full', 3: 'guarded', -1: None}
-
-    def as_dict(self):
-        d = {name: int(getattr(self, name)) for name, _ in self._fields_}
-        d['kernel'] = self.KERNELS[d['kernel']]
-        for name in ('vec_x', 'vec_w', 'w_trans'):
-            d[name] = bool(d[name])
-        return d
+    BOOLS = ('vec_x', 'vec_w', 'w_trans')
 
 
 def dense_route(X, W, Y, act='relu', ids=None, w_transposed=False, bias=None):
     """Which kernel dense() takes for these tensors (amar_dense_route: host only, nothing is launched; the launcher asks the same
     function).  A dict: kernel 'small' | 'tile128' | 'full' | 'guarded', vec_x, vec_w, w_trans, grid_x, grid_y, n_col_blocks, launches."""
-    K, N = (W.shape[1], W.shape[0]) if w_transposed else W.shape
-    M = ids.numel() if ids is not None else X.shape[0]
-    if X.shape[1] != K or not W.is_contiguous() or tuple(Y.shape) != (M, N):
-        raise ValueError("dense: X [*, K], W [K, N] contiguous, Y [M, N] expected")
     info = DenseRouteInfo()
-    code = load().amar_dense_route(
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), _ptr(ids, torch.int32, 'ids'),
-        _ptr(W, torch.float32, 'W'), _ptr(bias, torch.float32, 'bias'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
-        M, K, N, ACT_CODES[act] | (DENSE_WT if w_transposed else 0), ctypes.byref(info))
-    _check(code, 'amar_dense_route')
+    _call('amar_dense_route', *_dense_args(X, W, bias, Y, act, ids, w_transposed, check_bias=False), ctypes.byref(info))
     return info.as_dict()
 
 
@@ -798,12 +755,11 @@ def dense_split_pack(W):
     import numpy as np
     W = np.ascontiguousarray(W, dtype=np.float32)
     K, N = W.shape
-    lib = load()
-    nbytes = int(lib.amar_dense_split_bytes(K, N))
+    nbytes = int(load().amar_dense_split_bytes(K, N))
     if nbytes < 0:
         _check(nbytes, 'amar_dense_split_bytes')
     out = np.empty(nbytes, dtype=np.uint8)
-    _check(lib.amar_dense_split_pack_f32(W.ctypes.data, K, N, out.ctypes.data), 'amar_dense_split_pack_f32')
+    _call('amar_dense_split_pack_f32', W.ctypes.data, K, N, out.ctypes.data)
     return out
 
 
@@ -814,10 +770,8 @@ def dense_split(X, Wq, K, N, bias, Y, act='relu', ids=None):
         raise ValueError("dense_split: X [*, K], Wq of K N 6 bytes, Y [M, N] expected")
     if bias is not None and (bias.numel() != N or not bias.is_contiguous()):
         raise ValueError("dense_split: bias must be a contiguous [N] vector")
-    code = load().amar_dense_split_f32(
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X'), _ptr(ids, torch.int32, 'ids'), _ptr(Wq, torch.uint8, 'Wq'),
-        _ptr(bias, torch.float32, 'bias'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'), M, K, N, ACT_CODES[act], _stream())
-    _check(code, 'amar_dense_split_f32')
+    _launch('amar_dense_split_f32', *_mat(X, 'X'), _ptr(ids, I32, 'ids'), _ptr(Wq, torch.uint8, 'Wq'), _ptr(bias, F32, 'bias'), *_mat(Y, 'Y'),
+            M, K, N, ACT_CODES[act])
 
 
 CHAIN_MAX_WIDTH, CHAIN_MAX_LAYERS, CHAIN_MAX_BLOB_BYTES = 128, 8, 150 * 1024
@@ -845,15 +799,14 @@ def chain_pack(kernels, biases):
     for k, b, kin, n in zip(ks, bs, dims[:-1], dims[1:]):
         if k.shape != (kin, n) or b.shape != (n,):
             raise ValueError("chain_pack: inconsistent layer shapes")
-    lib = load()
     dims_c = (ctypes.c_int32 * len(dims))(*dims)
-    total = lib.amar_chain_pack_floats(dims_c, len(ks))
+    total = load().amar_chain_pack_floats(dims_c, len(ks))
     if total < 0:
         _check(int(total), 'amar_chain_pack_floats')
     out = np.empty(total, dtype=np.float32)
     kp = (ctypes.c_void_p * len(ks))(*[k.ctypes.data for k in ks])
     bp = (ctypes.c_void_p * len(bs))(*[b.ctypes.data for b in bs])
-    _check(lib.amar_chain_pack_f32(kp, bp, dims_c, len(ks), out.ctypes.data), 'amar_chain_pack_f32')
+    _call('amar_chain_pack_f32', kp, bp, dims_c, len(ks), out.ctypes.data)
     return out, dims
 
 
@@ -898,13 +851,12 @@ def _chain_segments_args(table, wpack, dims, acts, out, ids=None, base=0):
     if ids is None and table.shape[0] < P:
         raise ValueError("chain: input blocks have fewer rows than the output")
     n = len(segs)
-    ptrs = (ctypes.c_void_p * n)(*[_ptr(t, torch.float32, 'segment') for t in segs])
+    ptrs = (ctypes.c_void_p * n)(*[_ptr(t, F32, 'segment') for t in segs])
     lds = (ctypes.c_int64 * n)(*[_ld(t, 'segment') for t in segs])
     ws = (ctypes.c_int32 * n)(*[int(t.shape[1]) for t in segs])
     dims_c = (ctypes.c_int32 * len(dims))(*dims)
     acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
-    return [ptrs, lds, ws, n, _ptr(ids, torch.int32, 'ids'), int(base), _ptr(wpack, torch.float32, 'wpack'), dims_c, acts_c, len(acts),
-            _ptr(out, torch.float32, 'out'), _ld(out, 'out'), P]
+    return [ptrs, lds, ws, n, _ptr(ids, I32, 'ids'), int(base), _ptr(wpack, F32, 'wpack'), dims_c, acts_c, len(acts), *_mat(out, 'out'), P]
 
 
 def chain_segments(table, wpack, dims, acts, out, ids=None, base=0):
@@ -928,11 +880,9 @@ def _chain_args(A, wpack, dims, acts, out, ids_a=None, base_a=0, B=None, ids_b=N
     acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
     if out_index is not None and out_index.numel() != P:
         raise ValueError("chain: out_index must have one entry per output row")
-    return [_ptr(A, torch.float32, 'A'), _ld(A, 'A'), Da, _ptr(ids_a, torch.int32, 'ids_a'), int(base_a),
-            _ptr(B, torch.float32, 'B'), _ld(B, 'B') if B is not None else 0, Db, _ptr(ids_b, torch.int32, 'ids_b'), int(base_b),
-            1 if sum_inputs else 0, ACT_CODES[in_act],
-            _ptr(wpack, torch.float32, 'wpack'), dims_c, acts_c, len(acts),
-            _ptr(out, torch.float32, 'out'), _ld(out, 'out'), _ptr(out_index, torch.int32, 'out_index'), P]
+    return [*_mat(A, 'A'), Da, _ptr(ids_a, I32, 'ids_a'), int(base_a), *_mat(B, 'B'), Db, _ptr(ids_b, I32, 'ids_b'), int(base_b),
+            1 if sum_inputs else 0, ACT_CODES[in_act], _ptr(wpack, F32, 'wpack'), dims_c, acts_c, len(acts),
+            *_mat(out, 'out'), _ptr(out_index, I32, 'out_index'), P]
 
 
 def chain(A, wpack, dims, acts, out, ids_a=None, base_a=0, B=None, ids_b=None, base_b=0, sum_inputs=False, in_act=None, out_index=None):
@@ -989,16 +939,11 @@ class chain_together:
 CHAIN_KERNEL_GENERIC, CHAIN_KERNEL_PIPE, CHAIN_KERNEL_ROWS = 0, 1, 2
 
 
-class ChainRouteInfo(ctypes.Structure):
-    """include/amar_hip.h: amar_chain_route_info"""
+class ChainRouteInfo(_RouteInfo):
+    """include/amar_hip.h: amar_chain_route_info (`kernel` stays a CHAIN_KERNEL_* code)"""
     _fields_ = [(name, ctypes.c_int32) for name in ('kernel', 'maxt', 'full', 'am', 'split', 'scatter', 'shape', 'lastlin', 'seg', 'has_dot',
                                                     'layers', 'threads')] + [('blocks', ctypes.c_int64), ('lds_bytes', ctypes.c_int64)]
-
-    def as_dict(self):
-        d = {name: int(getattr(self, name)) for name, _ in self._fields_}
-        for name in ('full', 'split', 'scatter', 'lastlin', 'seg', 'has_dot'):
-            d[name] = bool(d[name])
-        return d
+    BOOLS = ('full', 'split', 'scatter', 'lastlin', 'seg', 'has_dot')
 
 
 def chain_shape(*tiles):
@@ -1018,22 +963,24 @@ def chain_route(A, wpack, dims, acts, out, ids_a=None, base_a=0, B=None, ids_b=N
         if not (A.in_place and B is None and not sum_inputs and out_index is None):
             raise ValueError("chain_route: this ConcatTable call is assembled first; ask about the assembled table")
         args = _chain_segments_args(A, wpack, dims, acts, out, ids=ids_a, base=base_a)
-        _check(load().amar_chain_segments_route(*args, ctypes.byref(info)), 'amar_chain_segments_route')
+        _call('amar_chain_segments_route', *args, ctypes.byref(info))
         return info.as_dict()
     args = _chain_args(A, wpack, dims, acts, out, ids_a=ids_a, base_a=base_a, B=B, ids_b=ids_b, base_b=base_b, sum_inputs=sum_inputs,
                        in_act=in_act, out_index=out_index)
-    _check(load().amar_chain_route(*args, ctypes.byref(info)), 'amar_chain_route')
+    _call('amar_chain_route', *args, ctypes.byref(info))
     return info.as_dict()
 
 
-class ChainRows2RouteInfo(ctypes.Structure):
+class ChainRows2RouteInfo(_RouteInfo):
     """include/amar_hip.h: amar_chain_rows2_route_info"""
     _fields_ = [(name, ctypes.c_int32) for name in ('one_launch', 'shape', 'lastlin', 'threads')] + [('blocks', ctypes.c_int64 * 2),
                                                                                                  ('lds_bytes', ctypes.c_int64)]
+    BOOLS = ('one_launch', 'lastlin')
 
     def as_dict(self):
-        return {'one_launch': bool(self.one_launch), 'shape': int(self.shape), 'lastlin': bool(self.lastlin), 'threads': int(self.threads),
-                'blocks': (int(self.blocks[0]), int(self.blocks[1])), 'lds_bytes': int(self.lds_bytes)}
+        d = super().as_dict()
+        d['blocks'] = tuple(d['blocks'])                                # the two problems' block counts as a pair
+        return d
 
 
 def _chain2_raw(ptrs_a, ldas, ptrs_w, dims, acts, ptrs_out, ldos, rows):
@@ -1054,9 +1001,9 @@ def _chain2_args(first, second):
         if A.shape[0] < out.shape[0]:
             raise ValueError("chain2: input blocks have fewer rows than the output")
     both = (first, second)
-    return _chain2_raw([_ptr(p[0], torch.float32, 'A') for p in both], [_ld(p[0], 'A') for p in both],
-                       [_ptr(p[1], torch.float32, 'wpack') for p in both], [p[2] for p in both], [p[3] for p in both],
-                       [_ptr(p[4], torch.float32, 'out') for p in both], [_ld(p[4], 'out') for p in both], [p[4].shape[0] for p in both])
+    return _chain2_raw([_ptr(p[0], F32, 'A') for p in both], [_ld(p[0], 'A') for p in both],
+                       [_ptr(p[1], F32, 'wpack') for p in both], [p[2] for p in both], [p[3] for p in both],
+                       [_ptr(p[4], F32, 'out') for p in both], [_ld(p[4], 'out') for p in both], [p[4].shape[0] for p in both])
 
 
 def chain2(first, second):
@@ -1076,7 +1023,7 @@ def chain2_route(first, second):
     amar_chain_rows2_route_info.  one_launch False: make two `chain` calls."""
     info = ChainRows2RouteInfo()
     args, keep = _chain2_args(first, second)
-    _check(load().amar_chain_rows2_route(*args, ctypes.byref(info)), 'amar_chain_rows2_route')
+    _call('amar_chain_rows2_route', *args, ctypes.byref(info))
     return info.as_dict()
 
 
@@ -1113,10 +1060,10 @@ def dual_chain(tables_a, tables_b, ids_a, ids_b, bases_a, bases_b, D, in_act, br
     pair p goes to out[out_index[p]] (amar_dual_chain_indexed_f32)."""
     P = out.shape[0]
     arr = lambda vals, ctype: (ctype * 2)(*vals)
-    A = arr([_ptr(t, torch.float32, 'A') for t in tables_a], ctypes.c_void_p)
-    B = arr([_ptr(t, torch.float32, 'B') for t in tables_b], ctypes.c_void_p)
-    IA = arr([_ptr(t, torch.int32, 'ida') for t in ids_a], ctypes.c_void_p)
-    IB = arr([_ptr(t, torch.int32, 'idb') for t in ids_b], ctypes.c_void_p)
+    A = arr([_ptr(t, F32, 'A') for t in tables_a], ctypes.c_void_p)
+    B = arr([_ptr(t, F32, 'B') for t in tables_b], ctypes.c_void_p)
+    IA = arr([_ptr(t, I32, 'ida') for t in ids_a], ctypes.c_void_p)
+    IB = arr([_ptr(t, I32, 'idb') for t in ids_b], ctypes.c_void_p)
     for ids in list(ids_a) + list(ids_b):
         if ids is not None and ids.numel() != P:
             raise ValueError("dual_chain: one id per output row expected")
@@ -1128,11 +1075,11 @@ def dual_chain(tables_a, tables_b, ids_a, ids_b, bases_a, bases_b, D, in_act, br
     tacts = (ctypes.c_int32 * len(trunk_acts))(*[ACT_CODES[a] for a in trunk_acts])
     if out_index is not None and out_index.numel() != P:
         raise ValueError("dual_chain: out_index must have one entry per output row")
-    code = load().amar_dual_chain_indexed_f32(A, lda, IA, ba, B, ldb, IB, bb, D, ACT_CODES[in_act], len(branch_acts), bacts,
-                                              tdims, tacts, len(trunk_acts), _ptr(wpack, torch.float32, 'wpack'),
-                                              _ptr(out, torch.float32, 'out'), _ld(out, 'out'), _ptr(out_index, torch.int32, 'out_index'),
-                                              P, _stream())
-    _check(code, 'amar_dual_chain_f32' if out_index is None else 'amar_dual_chain_indexed_f32')
+    # (one entry point serves both: without an index the error names the call the caller made, amar_dual_chain_f32 — hence no _launch)
+    _check(load().amar_dual_chain_indexed_f32(A, lda, IA, ba, B, ldb, IB, bb, D, ACT_CODES[in_act], len(branch_acts), bacts, tdims, tacts,
+                                              len(trunk_acts), _ptr(wpack, F32, 'wpack'), *_mat(out, 'out'), _ptr(out_index, I32, 'out_index'),
+                                              P, _stream()),
+           'amar_dual_chain_f32' if out_index is None else 'amar_dual_chain_indexed_f32')
 
 
 SCATTER_CLOSED_MAX_WINDOW = 65536      # include/amar_hip.h: AMAR_SCATTER_CLOSED_MAX_WINDOW
@@ -1160,13 +1107,11 @@ def scatter(src, index, dst, window_off=None, n_windows=1, closed=False, max_win
         return
     ldd = _ld(dst, 'dst') if dst.dim() == 2 else 1
     if window_off is not None and scatter_route(n, ldd, max_window, closed) == 'lds':
-        _check(load().amar_scatter_closed_f32(_ptr(src, torch.float32, 'src'), _ptr(index, torch.int32, 'index'), _ptr(dst, torch.float32, 'dst'),
-                                              n, _ptr(window_off, torch.int32, 'window_off'), int(n_windows), int(max_window), _stream()),
-               'amar_scatter_closed_f32')
+        _launch('amar_scatter_closed_f32', _ptr(src, F32, 'src'), _ptr(index, I32, 'index'), _ptr(dst, F32, 'dst'), n, _ptr(window_off, I32, 'window_off'),
+                int(n_windows), int(max_window))
         return
-    _check(load().amar_scatter_f32(_ptr(src, torch.float32, 'src'), _ptr(index, torch.int32, 'index'), _ptr(dst, torch.float32, 'dst'),
-                                   ldd, n, _ptr(window_off, torch.int32, 'window_off'),
-                                   int(n_windows), _stream()), 'amar_scatter_f32')
+    _launch('amar_scatter_f32', _ptr(src, F32, 'src'), _ptr(index, I32, 'index'), _ptr(dst, F32, 'dst'), ldd, n, _ptr(window_off, I32, 'window_off'),
+            int(n_windows))
 
 
 def copy_columns(src, dst, ids=None, base=0):
@@ -1174,29 +1119,20 @@ def copy_columns(src, dst, ids=None, base=0):
     n = ids.numel() if ids is not None else src.shape[0]
     if src.shape[1] != dst.shape[1] or dst.shape[0] != n:
         raise ValueError("copy_columns: shapes differ")
-    code = load().amar_copy_columns_f32(_ptr(src, torch.float32, 'src'), _ld(src, 'src'),
-                                        _ptr(ids, torch.int32, 'ids'), int(base),
-                                        _ptr(dst, torch.float32, 'dst'), _ld(dst, 'dst'),
-                                        n, src.shape[1], _stream())
-    _check(code, 'amar_copy_columns_f32')
+    _launch('amar_copy_columns_f32', *_mat(src, 'src'), _ptr(ids, I32, 'ids'), int(base), *_mat(dst, 'dst'), n, src.shape[1])
 
 
 def reduce_layers(cat, n_layers, width, out, mean=False):
     if cat.shape[1] != n_layers * width or tuple(out.shape) != (cat.shape[0], width):
         raise ValueError("reduce_layers: cat [n, n_layers*width], out [n, width] expected")
-    code = load().amar_reduce_layers_f32(_ptr(cat, torch.float32, 'cat'), _ld(cat, 'cat'), n_layers, width,
-                                         _ptr(out, torch.float32, 'out'), _ld(out, 'out'), cat.shape[0],
-                                         1 if mean else 0, _stream())
-    _check(code, 'amar_reduce_layers_f32')
+    _launch('amar_reduce_layers_f32', *_mat(cat, 'cat'), n_layers, width, *_mat(out, 'out'), cat.shape[0], 1 if mean else 0)
 
 
 def reduce_layers_wsum(cat, n_layers, width, w, out):
     """out = sum_l (w_l * w_l) * cat[:, block l]  (ReductionLayer('w-sum'), reduction.py:36-55); w: device vector of n_layers floats."""
     if cat.shape[1] != n_layers * width or tuple(out.shape) != (cat.shape[0], width) or w.numel() != n_layers or not w.is_contiguous():
         raise ValueError("reduce_layers_wsum: cat [n, n_layers*width], w [n_layers], out [n, width] expected")
-    code = load().amar_reduce_layers_wsum_f32(_ptr(cat, torch.float32, 'cat'), _ld(cat, 'cat'), n_layers, width, _ptr(w, torch.float32, 'w'),
-                                              _ptr(out, torch.float32, 'out'), _ld(out, 'out'), cat.shape[0], _stream())
-    _check(code, 'amar_reduce_layers_wsum_f32')
+    _launch('amar_reduce_layers_wsum_f32', *_mat(cat, 'cat'), n_layers, width, _ptr(w, F32, 'w'), *_mat(out, 'out'), cat.shape[0])
 
 
 def reduce_layers_wsum_bwd(cat, n_layers, width, w, d_out, d_cat, dw):
@@ -1206,28 +1142,22 @@ def reduce_layers_wsum_bwd(cat, n_layers, width, w, d_out, d_cat, dw):
             or w.numel() != n_layers or dw.numel() != n_layers or not w.is_contiguous() or not dw.is_contiguous()):
         raise ValueError("reduce_layers_wsum_bwd: cat / d_cat [n, n_layers*width], d_out [n, width], w / dw [n_layers] expected")
     scratch = torch.empty(int(load().amar_reduce_layers_wsum_bwd_scratch()), dtype=torch.float32, device=cat.device)
-    code = load().amar_reduce_layers_wsum_bwd_f32(_ptr(cat, torch.float32, 'cat'), _ld(cat, 'cat'), n_layers, width, _ptr(w, torch.float32, 'w'),
-                                                  _ptr(d_out, torch.float32, 'd_out'), _ld(d_out, 'd_out'),
-                                                  _ptr(d_cat, torch.float32, 'd_cat'), _ld(d_cat, 'd_cat'), _ptr(dw, torch.float32, 'dw'),
-                                                  _ptr(scratch, torch.float32, 'scratch'), n, _stream())
-    _check(code, 'amar_reduce_layers_wsum_bwd_f32')
+    _launch('amar_reduce_layers_wsum_bwd_f32', *_mat(cat, 'cat'), n_layers, width, _ptr(w, F32, 'w'), *_mat(d_out, 'd_out'),
+            *_mat(d_cat, 'd_cat'), _ptr(dw, F32, 'dw'), _ptr(scratch, F32, 'scratch'), n)
 
 
 def adam_advance(state, learning_rate, beta_1, beta_2):
     if state.numel() != 2 or not state.is_contiguous():
         raise ValueError("adam_advance: state must be 2 contiguous floats (t, lr_t)")
-    _check(load().amar_adam_advance_f32(_ptr(state, torch.float32, 'state'), float(learning_rate), float(beta_1), float(beta_2),
-                                        _stream()), 'amar_adam_advance_f32')
+    _launch('amar_adam_advance_f32', _ptr(state, F32, 'state'), float(learning_rate), float(beta_1), float(beta_2))
 
 
 def adam_dev(w, g, m, v, state, beta_1, beta_2, epsilon, l2=0.0):
     if not (w.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()) or \
             not (w.numel() == g.numel() == m.numel() == v.numel()):
         raise ValueError("adam_dev: contiguous tensors of equal size expected")
-    code = load().amar_adam_dev_f32(_ptr(w, torch.float32, 'w'), _ptr(g, torch.float32, 'g'), _ptr(m, torch.float32, 'm'),
-                                    _ptr(v, torch.float32, 'v'), w.numel(), _ptr(state, torch.float32, 'state'), float(beta_1),
-                                    float(beta_2), float(epsilon), float(l2), _stream())
-    _check(code, 'amar_adam_dev_f32')
+    _launch('amar_adam_dev_f32', _ptr(w, F32, 'w'), _ptr(g, F32, 'g'), _ptr(m, F32, 'm'), _ptr(v, F32, 'v'), w.numel(), _ptr(state, F32, 'state'), float(beta_1),
+            float(beta_2), float(epsilon), float(l2))
 
 
 class DeferredGradient:
@@ -1265,7 +1195,7 @@ def _slot_table(struct, entries, name, expected, checked=True):
     Returns (host uint8 tensor holding the table, total blocks)."""
     table = (struct * len(entries))()
     n_arrays = len(struct._fields_) - 6
-    ptr = (lambda t, what: _ptr(t, torch.float32, what)) if checked else (lambda t, what: t.data_ptr())
+    ptr = (lambda t, what: _ptr(t, F32, what)) if checked else (lambda t, what: t.data_ptr())
     block = 0
     for k, (w, g, arrays, l2) in enumerate(entries):
         groups = 0
@@ -1291,10 +1221,8 @@ def adam_slot_table(entries):
 
 
 def adam_multi(table_dev, n_slots, total_blocks, state, beta_1, beta_2, epsilon, reg_scale=0.0, loss_acc=None):
-    code = load().amar_adam_multi_f32(ctypes.c_void_p(table_dev.data_ptr()), n_slots, total_blocks, _ptr(state, torch.float32, 'state'),
-                                      float(beta_1), float(beta_2), float(epsilon), float(reg_scale),
-                                      _ptr(loss_acc, torch.float32, 'loss_acc'), _stream())
-    _check(code, 'amar_adam_multi_f32')
+    _launch('amar_adam_multi_f32', ctypes.c_void_p(table_dev.data_ptr()), n_slots, total_blocks, _ptr(state, F32, 'state'),
+            float(beta_1), float(beta_2), float(epsilon), float(reg_scale), _ptr(loss_acc, F32, 'loss_acc'))
 
 
 # ---- the optimizers as rules (include/amar_hip.h: AMAR_OPT_*) --------------------------------------------------------------------------
@@ -1328,8 +1256,7 @@ def optim_state_arrays(rule, flags=0, momentum=0.0):
 def optim_advance(state, rule, flags, hyper):
     if state.numel() != OPTIM_STATE_FLOATS or not state.is_contiguous():
         raise ValueError("optim_advance: state must be {} contiguous floats".format(OPTIM_STATE_FLOATS))
-    _check(load().amar_optim_advance_f32(_ptr(state, torch.float32, 'state'), int(rule), int(flags), ctypes.byref(hyper), _stream()),
-           'amar_optim_advance_f32')
+    _launch('amar_optim_advance_f32', _ptr(state, F32, 'state'), int(rule), int(flags), ctypes.byref(hyper))
 
 
 def optim(rule, flags, hyper, w, g, arrays, state, l2=0.0):
@@ -1339,10 +1266,8 @@ def optim(rule, flags, hyper, w, g, arrays, state, l2=0.0):
         raise ValueError("optim: contiguous tensors of equal size expected")
     if state.numel() != OPTIM_STATE_FLOATS:
         raise ValueError("optim: state must be {} floats".format(OPTIM_STATE_FLOATS))
-    code = load().amar_optim_f32(int(rule), int(flags), ctypes.byref(hyper), _ptr(w, torch.float32, 'w'), _ptr(g, torch.float32, 'g'),
-                                 _ptr(arrays[0], torch.float32, 's0'), _ptr(arrays[1], torch.float32, 's1'),
-                                 _ptr(arrays[2], torch.float32, 's2'), w.numel(), _ptr(state, torch.float32, 'state'), float(l2), _stream())
-    _check(code, 'amar_optim_f32')
+    _launch('amar_optim_f32', int(rule), int(flags), ctypes.byref(hyper), _ptr(w, F32, 'w'), _ptr(g, F32, 'g'), _ptr(arrays[0], F32, 's0'),
+            _ptr(arrays[1], F32, 's1'), _ptr(arrays[2], F32, 's2'), w.numel(), _ptr(state, F32, 'state'), float(l2))
 
 
 def optim_slot_table(entries):
@@ -1354,10 +1279,8 @@ def optim_slot_table(entries):
 def optim_multi(rule, flags, hyper, table_dev, n_slots, total_blocks, state, reg_scale=0.0, loss_acc=None):
     if state.numel() != OPTIM_STATE_FLOATS:
         raise ValueError("optim_multi: state must be {} floats".format(OPTIM_STATE_FLOATS))
-    code = load().amar_optim_multi_f32(int(rule), int(flags), ctypes.byref(hyper), ctypes.c_void_p(table_dev.data_ptr()), n_slots,
-                                       total_blocks, _ptr(state, torch.float32, 'state'), float(reg_scale),
-                                       _ptr(loss_acc, torch.float32, 'loss_acc'), _stream())
-    _check(code, 'amar_optim_multi_f32')
+    _launch('amar_optim_multi_f32', int(rule), int(flags), ctypes.byref(hyper), ctypes.c_void_p(table_dev.data_ptr()), n_slots,
+            total_blocks, _ptr(state, F32, 'state'), float(reg_scale), _ptr(loss_acc, F32, 'loss_acc'))
 
 
 # ---- learning-rate schedules (include/amar_hip.h: AMAR_LR_*) ---------------------------------------------------------------------------
@@ -1408,7 +1331,7 @@ def lr_schedule(schedule=None):
 def _lr_state(lr_state, what):
     if lr_state.numel() != LR_STATE_FLOATS or not lr_state.is_contiguous():
         raise ValueError("{}: lr_state must be {} contiguous floats (base rate, rate of the last step)".format(what, LR_STATE_FLOATS))
-    return _ptr(lr_state, torch.float32, 'lr_state')
+    return _ptr(lr_state, F32, 'lr_state')
 
 
 def lr_rates(sched, lr_state, first_step, n, out=None):
@@ -1421,24 +1344,22 @@ def lr_rates(sched, lr_state, first_step, n, out=None):
         out = torch.empty(n, dtype=torch.float32, device=lr_state.device)
     if out.numel() < n or not out.is_contiguous():
         raise ValueError("lr_rates: out must hold {} contiguous floats".format(n))
-    _check(load().amar_lr_rates_f32(ctypes.byref(sched), _lr_state(lr_state, 'lr_rates'), first_step, n, _ptr(out, torch.float32, 'out'),
-                                    _stream()), 'amar_lr_rates_f32')
+    _launch('amar_lr_rates_f32', ctypes.byref(sched), _lr_state(lr_state, 'lr_rates'), first_step, n, _ptr(out, F32, 'out'))
     return out
 
 
 def adam_advance_lr(state, sched, lr_state, beta_1, beta_2):
     if state.numel() != 2 or not state.is_contiguous():
         raise ValueError("adam_advance_lr: state must be 2 contiguous floats (t, lr_t)")
-    _check(load().amar_adam_advance_lr_f32(_ptr(state, torch.float32, 'state'), ctypes.byref(sched), _lr_state(lr_state, 'adam_advance_lr'),
-                                           float(beta_1), float(beta_2), _stream()), 'amar_adam_advance_lr_f32')
+    _launch('amar_adam_advance_lr_f32', _ptr(state, F32, 'state'), ctypes.byref(sched), _lr_state(lr_state, 'adam_advance_lr'),
+            float(beta_1), float(beta_2))
 
 
 def optim_advance_lr(state, rule, flags, hyper, sched, lr_state):
     if state.numel() != OPTIM_STATE_FLOATS or not state.is_contiguous():
         raise ValueError("optim_advance_lr: state must be {} contiguous floats".format(OPTIM_STATE_FLOATS))
-    _check(load().amar_optim_advance_lr_f32(_ptr(state, torch.float32, 'state'), int(rule), int(flags), ctypes.byref(hyper),
-                                            ctypes.byref(sched), _lr_state(lr_state, 'optim_advance_lr'), _stream()),
-           'amar_optim_advance_lr_f32')
+    _launch('amar_optim_advance_lr_f32', _ptr(state, F32, 'state'), int(rule), int(flags), ctypes.byref(hyper), ctypes.byref(sched),
+            _lr_state(lr_state, 'optim_advance_lr'))
 
 
 # ---- gradient clipping (include/amar_hip.h: AMAR_CLIP_*) -------------------------------------------------------------------------------
@@ -1474,26 +1395,21 @@ def grad_clip(mode, clip, table_dev, n_slots, total_blocks, workspace=None, norm
         raise ValueError("grad_clip: workspace of grad_clip_workspace_floats(n_slots, total_blocks) floats expected")
     if norms is not None and mode in (CLIP_NORM, CLIP_GLOBAL_NORM) and norms.numel() < (n_slots if mode == CLIP_NORM else 1):
         raise ValueError("grad_clip: norms must hold one float per slot (CLIP_NORM) or one float (CLIP_GLOBAL_NORM)")
-    code = load().amar_grad_clip_f32(int(mode), float(clip), None if table_dev is None else ctypes.c_void_p(table_dev.data_ptr()),
-                                     int(n_slots), int(total_blocks), _ptr(workspace, torch.float32, 'workspace'),
-                                     _ptr(norms, torch.float32, 'norms'), float(reg_scale), _ptr(loss_acc, torch.float32, 'loss_acc'),
-                                     _stream())
-    _check(code, 'amar_grad_clip_f32')
+    _launch('amar_grad_clip_f32', int(mode), float(clip), None if table_dev is None else ctypes.c_void_p(table_dev.data_ptr()),
+            int(n_slots), int(total_blocks), _ptr(workspace, F32, 'workspace'), _ptr(norms, F32, 'norms'), float(reg_scale),
+            _ptr(loss_acc, F32, 'loss_acc'))
 
 
 def sum_into(x, acc, scale=1.0):
-    _check(load().amar_sum_into_f32(_ptr(x, torch.float32, 'x'), x.numel(), float(scale), _ptr(acc, torch.float32, 'acc'), _stream()),
-           'amar_sum_into_f32')
+    _launch('amar_sum_into_f32', _ptr(x, F32, 'x'), x.numel(), float(scale), _ptr(acc, F32, 'acc'))
 
 
 def topk_segmented(seg_ptr, item_ids, scores, k):
     n_users = seg_ptr.numel() - 1
     out_items = torch.empty((n_users, k), dtype=torch.int32, device=scores.device)
     out_scores = torch.empty((n_users, k), dtype=torch.float32, device=scores.device)
-    code = load().amar_topk_segmented_f32(
-        _ptr(seg_ptr, torch.int32, 'seg_ptr'), _ptr(item_ids, torch.int32, 'item_ids'),
-        _ptr(scores, torch.float32, 'scores'), n_users, k, _ptr(out_items), _ptr(out_scores), _stream())
-    _check(code, 'amar_topk_segmented_f32')
+    _launch('amar_topk_segmented_f32', _ptr(seg_ptr, I32, 'seg_ptr'), _ptr(item_ids, I32, 'item_ids'), _ptr(scores, F32, 'scores'), n_users, k,
+            _ptr(out_items), _ptr(out_scores))
     return out_items, out_scores
 
 
@@ -1508,10 +1424,9 @@ def recommend(Tu, Ti, wpack, dims, acts, in_act, k, users=None, excl_ptr=None, e
     m = int(users.numel()) if users is not None else n_users
     if n_slices <= 0:
         n_slices = int(os.environ.get('AMAR_RECOMMEND_SLICES', '0'))
-    lib = load()
     dims_c = (ctypes.c_int32 * len(dims))(*dims)
     acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
-    slices = lib.amar_recommend_slices(m, n_items, dims_c, len(acts), int(n_slices))
+    slices = load().amar_recommend_slices(m, n_items, dims_c, len(acts), int(n_slices))
     if slices < 0:
         _check(int(slices), 'amar_recommend_slices')
     dev = Tu.device
@@ -1525,14 +1440,10 @@ def recommend(Tu, Ti, wpack, dims, acts, in_act, k, users=None, excl_ptr=None, e
         raise ValueError("recommend: excl_ptr and excl_items go together")
     if excl_ptr is not None and excl_ptr.numel() != n_users + 1:
         raise ValueError("recommend: excl_ptr must have n_users + 1 entries")
-    code = lib.amar_recommend_f32(
-        _ptr(Tu, torch.float32, 'Tu'), _ld(Tu, 'Tu'), n_users, _ptr(Ti, torch.float32, 'Ti'), _ld(Ti, 'Ti'), n_items, c1,
-        _ptr(wpack, torch.float32, 'wpack'), dims_c, acts_c, len(acts), ACT_CODES[in_act],
-        _ptr(users, torch.int32, 'users'), m, _ptr(excl_ptr, torch.int32, 'excl_ptr'),
-        _ptr_entries(excl_items, torch.int32, 'excl_items') if excl_items is not None else None,
-        int(k), int(slices) if slices > 1 else 1, _ptr(ws_i), _ptr(ws_s),
-        _ptr(out_items) if m else None, _ptr(out_scores) if m else None, _stream())
-    _check(code, 'amar_recommend_f32')
+    _launch('amar_recommend_f32', *_mat(Tu, 'Tu'), n_users, *_mat(Ti, 'Ti'), n_items, c1, _ptr(wpack, F32, 'wpack'), dims_c, acts_c, len(acts),
+            ACT_CODES[in_act], _ptr(users, I32, 'users'), m, _ptr(excl_ptr, I32, 'excl_ptr'), _ptr_entries(excl_items, I32, 'excl_items'),
+            int(k), int(slices) if slices > 1 else 1, _ptr(ws_i), _ptr(ws_s),
+            _ptr(out_items) if m else None, _ptr(out_scores) if m else None)
     return out_items, out_scores
 
 
@@ -1561,24 +1472,21 @@ def nearest(Q, T, k, metric='cosine', query_rows=None, excl_ptr=None, excl_rows=
     if excl_ptr is not None and excl_ptr.numel() != m + 1:
         raise ValueError("nearest: excl_ptr must have one entry per listed query plus one")
     lib = load()
-    code = NEAREST_METRICS[metric]
+    metric_code = NEAREST_METRICS[metric]
     slices = lib.amar_nearest_slices(m, n_rows, d, int(n_slices))
     if slices < 0:
         _check(int(slices), 'amar_nearest_slices')
     dev = Q.device
     out_rows = torch.empty((m, k), dtype=torch.int32, device=dev)
     out_scores = torch.empty((m, k), dtype=torch.float32, device=dev)
-    floats = lib.amar_nearest_workspace_floats(m, n_rows, int(k), code, int(slices))
+    floats = lib.amar_nearest_workspace_floats(m, n_rows, int(k), metric_code, int(slices))
     if floats < 0:
         _check(int(floats), 'amar_nearest_workspace_floats')
     ws_s = torch.empty((floats,), dtype=torch.float32, device=dev) if floats else None
     ws_r = torch.empty((m * slices * k,), dtype=torch.int32, device=dev) if slices > 1 else None
-    code = lib.amar_nearest_f32(
-        _ptr(Q, torch.float32, 'Q'), _ld(Q, 'Q'), n_q, _ptr(T, torch.float32, 'T'), _ld(T, 'T'), n_rows, d, code,
-        _ptr(query_rows, torch.int32, 'query_rows'), m, _ptr(excl_ptr, torch.int32, 'excl_ptr'),
-        _ptr_entries(excl_rows, torch.int32, 'excl_rows') if excl_rows is not None else None,
-        int(k), int(slices), _ptr(ws_r), _ptr(ws_s), _ptr(out_rows) if m else None, _ptr(out_scores) if m else None, _stream())
-    _check(code, 'amar_nearest_f32')
+    _launch('amar_nearest_f32', *_mat(Q, 'Q'), n_q, *_mat(T, 'T'), n_rows, d, metric_code, _ptr(query_rows, I32, 'query_rows'), m,
+            _ptr(excl_ptr, I32, 'excl_ptr'), _ptr_entries(excl_rows, I32, 'excl_rows'), int(k), int(slices), _ptr(ws_r), _ptr(ws_s),
+            _ptr(out_rows) if m else None, _ptr(out_scores) if m else None)
     return out_rows, out_scores
 
 
@@ -1625,11 +1533,9 @@ def rank_metrics(lists, rel_ptr, rel_items, ks, users=None):
     sums = torch.empty((len(ks), 4), dtype=torch.float64, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     ks_c = (ctypes.c_int32 * len(ks))(*ks)
-    code = load().amar_rank_metrics_f64(
-        _ptr(lists, torch.int32, 'lists') if m else None, m, K, _ptr(users, torch.int32, 'users'), _ptr(rel_ptr, torch.int32, 'rel_ptr'),
-        _ptr_entries(rel_items, torch.int32, 'rel_items'), n_users, ks_c, len(ks), cum.ctypes.data_as(ctypes.c_void_p),
-        _ptr(ws), _ptr(sums), _ptr(counts), _stream())
-    _check(code, 'amar_rank_metrics_f64')
+    _launch('amar_rank_metrics_f64', _ptr(lists, I32, 'lists') if m else None, m, K, _ptr(users, I32, 'users'), _ptr(rel_ptr, I32, 'rel_ptr'),
+            _ptr_entries(rel_items, I32, 'rel_items'), n_users, ks_c, len(ks), cum.ctypes.data_as(ctypes.c_void_p),
+            _ptr(ws), _ptr(sums), _ptr(counts))
     evaluated, skipped = (int(c) for c in counts.cpu().numpy())
     sums = sums.cpu().numpy()
     return (sums / evaluated if evaluated else sums), evaluated, skipped
@@ -1659,12 +1565,10 @@ def rerank_mmr(pool_items, pool_scores, T, k, trade_off=0.7, metric='cosine', wa
     out_scores = torch.empty((m, max(k, 0)), dtype=torch.float32, device=dev)
     out_mmr = torch.empty((m, max(k, 0)), dtype=torch.float32, device=dev) if want_mmr else None
     out_ild = torch.empty((m,), dtype=torch.float64, device=dev) if want_ild else None
-    code = load().amar_rerank_mmr_f32(
-        _ptr(pool_items, torch.int32, 'pool_items') if m else None, _ptr(pool_scores, torch.float32, 'pool_scores') if m else None,
-        m, P, _ptr(T, torch.float32, 'T'), _ld(T, 'T'), int(T.shape[0]), int(T.shape[1]), NEAREST_METRICS[metric], float(trade_off),
-        k, _ptr(out_items) if m else None, _ptr(out_scores) if m else None, _ptr(out_mmr) if m else None,
-        _ptr(out_ild) if m else None, _stream())
-    _check(code, 'amar_rerank_mmr_f32')
+    _launch('amar_rerank_mmr_f32', _ptr(pool_items, I32, 'pool_items') if m else None, _ptr(pool_scores, F32, 'pool_scores') if m else None,
+            m, P, *_mat(T, 'T'), int(T.shape[0]), int(T.shape[1]), NEAREST_METRICS[metric], float(trade_off),
+            k, _ptr(out_items) if m else None, _ptr(out_scores) if m else None, _ptr(out_mmr) if m else None,
+            _ptr(out_ild) if m else None)
     return (out_items, out_scores) + ((out_mmr,) if want_mmr else ()) + ((out_ild,) if want_ild else ())
 
 
@@ -1680,11 +1584,8 @@ def list_diversity(lists, T, ks, metric='cosine'):
     out_ild = torch.empty((m, len(ks)), dtype=torch.float64, device=dev)
     out_count = torch.empty((m, len(ks)), dtype=torch.int32, device=dev)
     ks_c = (ctypes.c_int32 * max(1, len(ks)))(*ks)
-    code = load().amar_list_diversity_f64(
-        _ptr(lists, torch.int32, 'lists') if m else None, m, K, _ptr(T, torch.float32, 'T'), _ld(T, 'T'), int(T.shape[0]),
-        int(T.shape[1]), NEAREST_METRICS[metric], ks_c, len(ks), _ptr(out_ild) if m else None, _ptr(out_count) if m else None,
-        _stream())
-    _check(code, 'amar_list_diversity_f64')
+    _launch('amar_list_diversity_f64', _ptr(lists, I32, 'lists') if m else None, m, K, *_mat(T, 'T'), int(T.shape[0]), int(T.shape[1]),
+            NEAREST_METRICS[metric], ks_c, len(ks), _ptr(out_ild) if m else None, _ptr(out_count) if m else None)
     return out_ild, out_count
 
 
@@ -1693,49 +1594,43 @@ def act_bwd(dY, Y, dZ, act):
     """dZ = dY * act'(Y) with Y the layer output (dZ may alias dY)."""
     if tuple(dY.shape) != tuple(Y.shape) or tuple(dZ.shape) != tuple(Y.shape):
         raise ValueError("act_bwd: shapes differ")
-    code = load().amar_act_bwd_f32(_ptr(dY, torch.float32, 'dY'), _ld(dY, 'dY'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
-                                   _ptr(dZ, torch.float32, 'dZ'), _ld(dZ, 'dZ'), Y.shape[0], Y.shape[1], ACT_CODES[act], _stream())
-    _check(code, 'amar_act_bwd_f32')
+    _launch('amar_act_bwd_f32', *_mat(dY, 'dY'), *_mat(Y, 'Y'), *_mat(dZ, 'dZ'), Y.shape[0], Y.shape[1], ACT_CODES[act])
+
+
+def _wgrad_args(X, dZ, dW, db, checked):
+    """The arguments amar_wgrad_f32 and amar_wgrad_route share (all but the last two / one), and (M, K, N).  checked: the launcher's
+    shape checks, which the route query does not make."""
+    M, N = dZ.shape
+    K = X.shape[1] if X is not None else 0
+    if checked and dW is not None and (X is None or X.shape[0] != M or tuple(dW.shape) != (K, N) or not dW.is_contiguous()):
+        raise ValueError("wgrad: X [M, K], dZ [M, N], dW [K, N] contiguous expected")
+    if checked and db is not None and (db.numel() != N or not db.is_contiguous()):
+        raise ValueError("wgrad: db must be a contiguous [N] vector")
+    # X travels only where dW is asked for (not _mat: a dW without an X stays an error in the route query too)
+    x_ptr, ldx = (_ptr(X, F32, 'X'), _ld(X, 'X')) if dW is not None else (None, 0)
+    return [x_ptr, ldx, *_mat(dZ, 'dZ'), M, K, N, _ptr(dW, F32, 'dW'), _ptr(db, F32, 'db')], (M, K, N)
 
 
 def wgrad(X, dZ, dW=None, db=None):
     """dW = X^T . dZ and / or db = column sums of dZ (deterministic two-stage reduction)."""
-    M, N = dZ.shape
-    K = X.shape[1] if X is not None else 0
-    if dW is not None and (X is None or X.shape[0] != M or tuple(dW.shape) != (K, N) or not dW.is_contiguous()):
-        raise ValueError("wgrad: X [M, K], dZ [M, N], dW [K, N] contiguous expected")
-    if db is not None and (db.numel() != N or not db.is_contiguous()):
-        raise ValueError("wgrad: db must be a contiguous [N] vector")
-    lib = load()
-    n_scratch = lib.amar_wgrad_scratch_floats(M, K if dW is not None else 0, N)
+    args, (M, K, N) = _wgrad_args(X, dZ, dW, db, checked=True)
+    n_scratch = load().amar_wgrad_scratch_floats(M, K if dW is not None else 0, N)
     scratch = torch.empty(max(int(n_scratch), 1), dtype=torch.float32, device=dZ.device)
-    code = lib.amar_wgrad_f32(_ptr(X if dW is not None else None, torch.float32, 'X'), _ld(X, 'X') if dW is not None else 0,
-                              _ptr(dZ, torch.float32, 'dZ'), _ld(dZ, 'dZ'), M, K, N,
-                              _ptr(dW, torch.float32, 'dW'), _ptr(db, torch.float32, 'db'), _ptr(scratch), _stream())
-    _check(code, 'amar_wgrad_f32')
+    _launch('amar_wgrad_f32', *args, _ptr(scratch))
 
 
-class WgradRouteInfo(ctypes.Structure):
+class WgradRouteInfo(_RouteInfo):
     """include/amar_hip.h: amar_wgrad_route_info"""
     _fields_ = [(name, ctypes.c_int32) for name in ('kernel', 'wg_rows', 'grid_k', 'grid_n')] + \
                [('chunks', ctypes.c_int64), ('scratch_floats', ctypes.c_int64)]
-
-    def as_dict(self):
-        d = {name: int(getattr(self, name)) for name, _ in self._fields_}
-        d['kernel'] = 'mfma' if d['kernel'] == 1 else 'partial'
-        return d
+    KERNELS = {0: 'partial', 1: 'mfma'}
 
 
 def wgrad_route(X, dZ, dW=None, db=None):
     """Which kernel wgrad takes for these operands (amar_wgrad_route: host only, nothing is launched; the launcher asks the same
     function).  A dict: kernel 'mfma' | 'partial', wg_rows, chunks, grid_k, grid_n, scratch_floats."""
-    M, N = dZ.shape
-    K = X.shape[1] if X is not None else 0
     info = WgradRouteInfo()
-    code = load().amar_wgrad_route(_ptr(X if dW is not None else None, torch.float32, 'X'), _ld(X, 'X') if dW is not None else 0,
-                                   _ptr(dZ, torch.float32, 'dZ'), _ld(dZ, 'dZ'), M, K, N,
-                                   _ptr(dW, torch.float32, 'dW'), _ptr(db, torch.float32, 'db'), ctypes.byref(info))
-    _check(code, 'amar_wgrad_route')
+    _call('amar_wgrad_route', *_wgrad_args(X, dZ, dW, db, checked=False)[0], ctypes.byref(info))
     return info.as_dict()
 
 
@@ -1759,21 +1654,19 @@ def _dense_stack_args(X, weights, biases, acts, outs, ids=None, xcopy=None):
     if xcopy is not None and tuple(xcopy.shape) != (M, dims[0]):
         raise ValueError("dense_stack: xcopy must be [M, K_0]")
     arr_p = ctypes.c_void_p * n
-    wp = arr_p(*[_ptr(w, torch.float32, 'W') for w in weights])
-    bp = arr_p(*[_ptr(b, torch.float32, 'bias') for b in biases])
-    yp = arr_p(*[_ptr(y, torch.float32, 'Y') for y in outs])
+    wp = arr_p(*[_ptr(w, F32, 'W') for w in weights])
+    bp = arr_p(*[_ptr(b, F32, 'bias') for b in biases])
+    yp = arr_p(*[_ptr(y, F32, 'Y') for y in outs])
     ld = (ctypes.c_int64 * n)(*[_ld(y, 'Y') for y in outs])
     dm = (ctypes.c_int32 * (n + 1))(*dims)
     ac = (ctypes.c_int32 * n)(*[ACT_CODES[a] for a in acts])
-    return [_ptr(X, torch.float32, 'X'), _ld(X, 'X'), _ptr(ids, torch.int32, 'ids'), _ptr(xcopy, torch.float32, 'xcopy'),
-            _ld(xcopy, 'xcopy') if xcopy is not None else 0, n, wp, bp, dm, ac, yp, ld, M]
+    return [*_mat(X, 'X'), _ptr(ids, I32, 'ids'), *_mat(xcopy, 'xcopy'), n, wp, bp, dm, ac, yp, ld, M]
 
 
 def dense_stack(X, weights, biases, acts, outs, ids=None, xcopy=None):
     """A Dense stack forward in one launch with every layer's output kept (amar_dense_stack_f32): y_0 = X[ids], outs[l] = act_l(y_l . W_l + b_l).
     outs[l] may be column slices of wider buffers; xcopy ([M, K_0]): also receives the gathered input rows."""
-    args = _dense_stack_args(X, weights, biases, acts, outs, ids=ids, xcopy=xcopy)
-    _check(load().amar_dense_stack_f32(*args, _stream()), 'amar_dense_stack_f32')
+    _launch('amar_dense_stack_f32', *_dense_stack_args(X, weights, biases, acts, outs, ids=ids, xcopy=xcopy))
 
 
 class DenseStackDesc(ctypes.Structure):
@@ -1803,7 +1696,7 @@ def dense_stack_pair(first, second):
     (X, weights, biases, acts, outs, ids, xcopy).  Same results as two dense_stack calls."""
     a0, a1 = _dense_stack_args(**first), _dense_stack_args(**second)
     d0, d1 = DenseStackDesc(*[_as_pointer(v) for v in a0]), DenseStackDesc(*[_as_pointer(v) for v in a1])
-    _check(load().amar_dense_stack_pair_f32(ctypes.byref(d0), ctypes.byref(d1), _stream()), 'amar_dense_stack_pair_f32')
+    _launch('amar_dense_stack_pair_f32', ctypes.byref(d0), ctypes.byref(d1))
 
 
 def dense_stack_bwd_supported(dims, M):
@@ -1832,18 +1725,17 @@ def _dense_stack_bwd_args(dYtop, Ytop, inputs, weights, acts, workspace, dWs, db
     if dX0 is not None and tuple(dX0.shape) != (M, dims[0]):
         raise ValueError("dense_stack_bwd: dX0 must be [M, K_0]")
     arr_p = ctypes.c_void_p * n
-    xp = arr_p(*[_ptr(x, torch.float32, 'X') for x in inputs])
+    xp = arr_p(*[_ptr(x, F32, 'X') for x in inputs])
     lx = (ctypes.c_int64 * n)(*[_ld(x, 'X') for x in inputs])
-    wp = arr_p(*[_ptr(w, torch.float32, 'W') for w in weights])
-    dwp = arr_p(*[_ptr(w, torch.float32, 'dW') for w in dWs])
-    dbp = arr_p(*[_ptr(b, torch.float32, 'db') for b in dbs])
+    wp = arr_p(*[_ptr(w, F32, 'W') for w in weights])
+    dwp = arr_p(*[_ptr(w, F32, 'dW') for w in dWs])
+    dbp = arr_p(*[_ptr(b, F32, 'db') for b in dbs])
     dm = (ctypes.c_int32 * (n + 1))(*dims)
     ac = (ctypes.c_int32 * n)(*[ACT_CODES[a] for a in acts])
     if workspace.numel() < load().amar_dense_stack_bwd_workspace_floats(M, n, dm):
         raise ValueError("dense_stack_bwd: workspace too small (capi.dense_stack_bwd_workspace)")
-    args = [_ptr(dYtop, torch.float32, 'dYtop'), _ld(dYtop, 'dYtop'), _ptr(Ytop, torch.float32, 'Ytop'), _ld(Ytop, 'Ytop') if Ytop is not None else 0,
-            n, xp, lx, wp, dm, ac, _ptr(dX0, torch.float32, 'dX0'), _ld(dX0, 'dX0') if dX0 is not None else 0, dwp, dbp,
-            _ptr(workspace, torch.float32, 'workspace'), DENSE_BWD_DEFER if defer else 0, M]
+    args = [*_mat(dYtop, 'dYtop'), *_mat(Ytop, 'Ytop'), n, xp, lx, wp, dm, ac, *_mat(dX0, 'dX0'), dwp, dbp,
+            _ptr(workspace, F32, 'workspace'), DENSE_BWD_DEFER if defer else 0, M]
     return args, (n, M, dims)
 
 
@@ -1863,7 +1755,7 @@ def dense_stack_bwd(dYtop, Ytop, inputs, weights, acts, workspace, dWs, dbs, dX0
     output (None: dYtop already is the last pre-activation's gradient).  defer=True: dWs / dbs are not written; returns one
     (DeferredGradient dW, DeferredGradient db) per layer."""
     args, (n, M, dims) = _dense_stack_bwd_args(dYtop, Ytop, inputs, weights, acts, workspace, dWs, dbs, dX0=dX0, defer=defer)
-    _check(load().amar_dense_stack_bwd_f32(*args, _stream()), 'amar_dense_stack_bwd_f32')
+    _launch('amar_dense_stack_bwd_f32', *args)
     return _deferred_stack_gradients(workspace, n, M, dims) if defer else None
 
 
@@ -1872,29 +1764,23 @@ def dense_stack_bwd_pair(first, second):
     dense_stack_bwd's arguments.  Returns the two results dense_stack_bwd would have returned."""
     (a0, m0), (a1, m1) = _dense_stack_bwd_args(**first), _dense_stack_bwd_args(**second)
     d0, d1 = DenseStackBwdDesc(*[_as_pointer(v) for v in a0]), DenseStackBwdDesc(*[_as_pointer(v) for v in a1])
-    _check(load().amar_dense_stack_bwd_pair_f32(ctypes.byref(d0), ctypes.byref(d1), _stream()), 'amar_dense_stack_bwd_pair_f32')
+    _launch('amar_dense_stack_bwd_pair_f32', ctypes.byref(d0), ctypes.byref(d1))
     return (_deferred_stack_gradients(first['workspace'], *m0) if first.get('defer') else None,
             _deferred_stack_gradients(second['workspace'], *m1) if second.get('defer') else None)
 
 
-class DenseStackRouteInfo(ctypes.Structure):
-    """include/amar_hip.h: amar_dense_stack_route_info"""
+class DenseStackRouteInfo(_RouteInfo):
+    """include/amar_hip.h: amar_dense_stack_route_info (as_dict(n_layers): vec_w one per layer)"""
     _fields_ = [('rows', ctypes.c_int32), ('vec_x', ctypes.c_int32), ('vec_w', ctypes.c_int32 * 4), ('groups', ctypes.c_int64),
                 ('lds_bytes', ctypes.c_int64)]
-
-    def as_dict(self, n_layers=4):
-        return dict(rows=int(self.rows), groups=int(self.groups), lds_bytes=int(self.lds_bytes), vec_x=bool(self.vec_x),
-                    vec_w=[bool(v) for v in self.vec_w[:n_layers]])
+    BOOLS = ('vec_x', 'vec_w')
 
 
-class DenseStackBwdRouteInfo(ctypes.Structure):
-    """include/amar_hip.h: amar_dense_stack_bwd_route_info"""
+class DenseStackBwdRouteInfo(_RouteInfo):
+    """include/amar_hip.h: amar_dense_stack_bwd_route_info (as_dict(n_layers): vec_x and vec_w one per layer)"""
     _fields_ = [('rows', ctypes.c_int32), ('vec_top', ctypes.c_int32), ('vec_x', ctypes.c_int32 * 4), ('vec_w', ctypes.c_int32 * 4),
                 ('groups', ctypes.c_int64), ('lds_bytes', ctypes.c_int64)]
-
-    def as_dict(self, n_layers=4):
-        return dict(rows=int(self.rows), groups=int(self.groups), lds_bytes=int(self.lds_bytes), vec_top=bool(self.vec_top),
-                    vec_x=[bool(v) for v in self.vec_x[:n_layers]], vec_w=[bool(v) for v in self.vec_w[:n_layers]])
+    BOOLS = ('vec_top', 'vec_x', 'vec_w')
 
 
 def dense_stack_route(X, weights, biases, acts, outs, ids=None, xcopy=None):
@@ -1902,7 +1788,7 @@ def dense_stack_route(X, weights, biases, acts, outs, ids=None, xcopy=None):
     functions).  A dict: rows (16 | 64), groups, lds_bytes, vec_x, vec_w (one per layer)."""
     args = _dense_stack_args(X, weights, biases, acts, outs, ids=ids, xcopy=xcopy)
     info = DenseStackRouteInfo()
-    _check(load().amar_dense_stack_route(*args, ctypes.byref(info)), 'amar_dense_stack_route')
+    _call('amar_dense_stack_route', *args, ctypes.byref(info))
     return info.as_dict(len(weights))
 
 
@@ -1911,7 +1797,7 @@ def dense_stack_bwd_route(dYtop, Ytop, inputs, weights, acts, workspace, dWs, db
     lds_bytes, vec_top, vec_x and vec_w (one per layer)."""
     args, _ = _dense_stack_bwd_args(dYtop, Ytop, inputs, weights, acts, workspace, dWs, dbs, dX0=dX0, defer=defer)
     info = DenseStackBwdRouteInfo()
-    _check(load().amar_dense_stack_bwd_route(*args, ctypes.byref(info)), 'amar_dense_stack_bwd_route')
+    _call('amar_dense_stack_bwd_route', *args, ctypes.byref(info))
     return info.as_dict(len(weights))
 
 
@@ -1943,75 +1829,63 @@ DENSE_BWD_DEFER = 0x100
 DENSE_BWD_ACCUM_DX = 0x200
 
 
+def _dense_bwd_args(X, Y, dY, W, act, workspace, dX, dW, db, defer, dZ, accumulate_dx, K, checked):
+    """The arguments amar_dense_bwd_f32 and amar_dense_bwd_route share (up to dZ's leading dimension; the launcher's workspace
+    follows, then M, K, N in both), and (M, K, N).  checked: the launcher's checks, which the route query does not make."""
+    M, N = dY.shape
+    K = W.shape[0] if W is not None else (X.shape[1] if X is not None else int(K or 1))    # (K only sizes the workspace when neither is given)
+    if checked:
+        if dX is not None and (W is None or tuple(W.shape) != (K, N) or not W.is_contiguous() or tuple(dX.shape) != (M, K)):
+            raise ValueError("dense_bwd: W [K, N] contiguous and dX [M, K] expected")
+        if dW is not None and (X is None or tuple(X.shape) != (M, K) or tuple(dW.shape) != (K, N) or not dW.is_contiguous()):
+            raise ValueError("dense_bwd: X [M, K] and dW [K, N] contiguous expected")
+        if db is not None and (db.numel() != N or not db.is_contiguous()):
+            raise ValueError("dense_bwd: db must be a contiguous [N] vector")
+        if Y is not None and tuple(Y.shape) != (M, N):
+            raise ValueError("dense_bwd: Y [M, N] expected")
+        if dZ is not None and tuple(dZ.shape) != (M, N):
+            raise ValueError("dense_bwd: dZ [M, N] expected")
+        if workspace is None or workspace.numel() < load().amar_dense_bwd_workspace_floats(M, K, N):
+            raise ValueError("dense_bwd: workspace too small (capi.dense_bwd_workspace)")
+    return [*_mat(X, 'X'), *_mat(Y, 'Y'), *_mat(dY, 'dY'), _ptr(W, F32, 'W'),
+            ACT_CODES[act] | (DENSE_BWD_DEFER if defer else 0) | (DENSE_BWD_ACCUM_DX if accumulate_dx else 0),
+            *_mat(dX, 'dX'), _ptr(dW, F32, 'dW'), _ptr(db, F32, 'db'), *_mat(dZ, 'dZ')], (M, K, N)
+
+
 def dense_bwd(X, Y, dY, W, act, workspace, dX=None, dW=None, db=None, defer=False, dZ=None, accumulate_dx=False, K=None):
     """The reverse pass of one Dense layer in two launches instead of four (amar_dense_bwd_f32): dZ = dY * act'(Y); dX = dZ . W^T; dW = X^T . dZ;
     db = column sums of dZ.  Y is the layer's OUTPUT (None with act None: dY already is dZ); any of dX / dW / db may be None."""
-    M, N = dY.shape
-    K = W.shape[0] if W is not None else (X.shape[1] if X is not None else int(K or 1))    # (K only sizes the workspace when neither is given)
-    if dX is not None and (W is None or tuple(W.shape) != (K, N) or not W.is_contiguous() or tuple(dX.shape) != (M, K)):
-        raise ValueError("dense_bwd: W [K, N] contiguous and dX [M, K] expected")
-    if dW is not None and (X is None or tuple(X.shape) != (M, K) or tuple(dW.shape) != (K, N) or not dW.is_contiguous()):
-        raise ValueError("dense_bwd: X [M, K] and dW [K, N] contiguous expected")
-    if db is not None and (db.numel() != N or not db.is_contiguous()):
-        raise ValueError("dense_bwd: db must be a contiguous [N] vector")
-    if Y is not None and tuple(Y.shape) != (M, N):
-        raise ValueError("dense_bwd: Y [M, N] expected")
-    if dZ is not None and tuple(dZ.shape) != (M, N):
-        raise ValueError("dense_bwd: dZ [M, N] expected")
-    lib = load()
-    if workspace is None or workspace.numel() < lib.amar_dense_bwd_workspace_floats(M, K, N):
-        raise ValueError("dense_bwd: workspace too small (capi.dense_bwd_workspace)")
-    code = lib.amar_dense_bwd_f32(
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X') if X is not None else 0, _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y') if Y is not None else 0,
-        _ptr(dY, torch.float32, 'dY'), _ld(dY, 'dY'), _ptr(W, torch.float32, 'W'),
-        ACT_CODES[act] | (DENSE_BWD_DEFER if defer else 0) | (DENSE_BWD_ACCUM_DX if accumulate_dx else 0),
-        _ptr(dX, torch.float32, 'dX'), _ld(dX, 'dX') if dX is not None else 0, _ptr(dW, torch.float32, 'dW'), _ptr(db, torch.float32, 'db'),
-        _ptr(dZ, torch.float32, 'dZ'), _ld(dZ, 'dZ') if dZ is not None else 0,
-        _ptr(workspace, torch.float32, 'workspace'), M, K, N, _stream())
-    _check(code, 'amar_dense_bwd_f32')
+    args, (M, K, N) = _dense_bwd_args(X, Y, dY, W, act, workspace, dX, dW, db, defer, dZ, accumulate_dx, K, checked=True)
+    _launch('amar_dense_bwd_f32', *args, _ptr(workspace, F32, 'workspace'), M, K, N)
     if defer:
         # defer=True: dW / db are NOT written; the partial sums stay in the workspace — returned as DeferredGradients (dW's, db's)
-        g = int(lib.amar_dense_bwd_groups(M))
+        g = int(load().amar_dense_bwd_groups(M))
         nw = g * K * N if dW is not None else 0
         return (DeferredGradient(workspace[4:4 + nw], g, (K, N)) if dW is not None else None,
                 DeferredGradient(workspace[4 + nw:4 + nw + g * N], g, (N,)) if db is not None else None)
     return None
 
 
-class DenseBwdRouteInfo(ctypes.Structure):
+class DenseBwdRouteInfo(_RouteInfo):
     """include/amar_hip.h: amar_dense_bwd_route_info"""
     _fields_ = [(name, ctypes.c_int32) for name in ('kernel', 'mt', 'kp', 'np', 'vec', 'x_scalar', 'subtiles', 'fold', 'fold_launch')] + \
                [('launched_groups', ctypes.c_int64), ('out_groups', ctypes.c_int64)]
-
-    def as_dict(self):
-        d = {name: int(getattr(self, name)) for name, _ in self._fields_}
-        d['kernel'] = 'rows' if d['kernel'] == 1 else 'tile'
-        d['vec'], d['x_scalar'], d['fold_launch'] = bool(d['vec']), bool(d['x_scalar']), bool(d['fold_launch'])
-        return d
+    KERNELS, BOOLS = {0: 'tile', 1: 'rows'}, ('vec', 'x_scalar', 'fold_launch')
 
 
 def dense_bwd_route(X, Y, dY, W, act, workspace=None, dX=None, dW=None, db=None, defer=False, dZ=None, accumulate_dx=False, K=None):
     """Which kernel dense_bwd takes for these operands (amar_dense_bwd_route: host only, nothing is launched; the launcher asks the same
     function).  A dict: kernel 'tile' | 'rows', mt (tile), kp / np (rows), vec, x_scalar, subtiles, launched_groups, fold, fold_launch,
     out_groups."""
-    M, N = dY.shape
-    K = W.shape[0] if W is not None else (X.shape[1] if X is not None else int(K or 1))
+    args, (M, K, N) = _dense_bwd_args(X, Y, dY, W, act, workspace, dX, dW, db, defer, dZ, accumulate_dx, K, checked=False)
     info = DenseBwdRouteInfo()
-    code = load().amar_dense_bwd_route(
-        _ptr(X, torch.float32, 'X'), _ld(X, 'X') if X is not None else 0, _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y') if Y is not None else 0,
-        _ptr(dY, torch.float32, 'dY'), _ld(dY, 'dY'), _ptr(W, torch.float32, 'W'),
-        ACT_CODES[act] | (DENSE_BWD_DEFER if defer else 0) | (DENSE_BWD_ACCUM_DX if accumulate_dx else 0),
-        _ptr(dX, torch.float32, 'dX'), _ld(dX, 'dX') if dX is not None else 0, _ptr(dW, torch.float32, 'dW'), _ptr(db, torch.float32, 'db'),
-        _ptr(dZ, torch.float32, 'dZ'), _ld(dZ, 'dZ') if dZ is not None else 0, M, K, N, ctypes.byref(info))
-    _check(code, 'amar_dense_bwd_route')
+    _call('amar_dense_bwd_route', *args, M, K, N, ctypes.byref(info))
     return info.as_dict()
 
 
 def bce_grad(p, y, dz, loss_terms):
     B = y.numel()
-    code = load().amar_bce_grad_f32(_ptr(p, torch.float32, 'p'), _ld(p, 'p') if p.dim() == 2 else 1, _ptr(y, torch.float32, 'y'),
-                                    _ptr(dz, torch.float32, 'dz'), _ptr(loss_terms, torch.float32, 'loss_terms'), B, _stream())
-    _check(code, 'amar_bce_grad_f32')
+    _launch('amar_bce_grad_f32', *_col(p, 'p'), _ptr(y, F32, 'y'), _ptr(dz, F32, 'dz'), _ptr(loss_terms, F32, 'loss_terms'), B)
 
 
 def bpr_grad(p, dz, loss_terms):
@@ -2019,9 +1893,7 @@ def bpr_grad(p, dz, loss_terms):
     B = p.shape[0]
     if dz.numel() != B or loss_terms.numel() != B or not dz.is_contiguous() or not loss_terms.is_contiguous():
         raise ValueError("bpr_grad: p [B] or [B, 1], dz and loss_terms of B contiguous floats expected")
-    code = load().amar_bpr_grad_f32(_ptr(p, torch.float32, 'p'), _ld(p, 'p') if p.dim() == 2 else 1, _ptr(dz, torch.float32, 'dz'),
-                                    _ptr(loss_terms, torch.float32, 'loss_terms'), B, _stream())
-    _check(code, 'amar_bpr_grad_f32')
+    _launch('amar_bpr_grad_f32', *_col(p, 'p'), _ptr(dz, F32, 'dz'), _ptr(loss_terms, F32, 'loss_terms'), B)
 
 
 # include/amar_hip.h: AMAR_GROUP_*
@@ -2038,9 +1910,7 @@ def group_loss_grad(kind, hyper, p, dz, loss_terms, n_negatives=1):
     K = int(n_negatives)
     if K < 1 or (B // 2) % K:
         raise ValueError("group_loss_grad: {} triples do not split into groups of n_negatives = {}".format(B // 2, n_negatives))
-    code = load().amar_group_loss_grad_f32(int(kind), float(hyper), _ptr(p, torch.float32, 'p'), _ld(p, 'p') if p.dim() == 2 else 1,
-                                           _ptr(dz, torch.float32, 'dz'), _ptr(loss_terms, torch.float32, 'loss_terms'), B, K, _stream())
-    _check(code, 'amar_group_loss_grad_f32')
+    _launch('amar_group_loss_grad_f32', int(kind), float(hyper), *_col(p, 'p'), _ptr(dz, F32, 'dz'), _ptr(loss_terms, F32, 'loss_terms'), B, K)
 
 
 # include/amar_hip.h: AMAR_LOSS_*
@@ -2080,17 +1950,12 @@ def loss_grad(loss, hyper, p, y, dz, loss_terms, counters=None, sample_weight=No
             raise ValueError("loss_grad: sample_weight of B contiguous floats expected")
         if class_weight is not None and (class_weight.numel() != 2 or not class_weight.is_contiguous()):
             raise ValueError("loss_grad: class_weight must be two contiguous floats (class 0, class 1)")
-        code = load().amar_loss_grad_weighted_f32(int(loss), hp, _ptr(p, torch.float32, 'p'), _ld(p, 'p') if p.dim() == 2 else 1,
-                                                  _ptr(y, torch.float32, 'y'), _ptr(sample_weight, torch.float32, 'sample_weight'),
-                                                  _ptr(class_weight, torch.float32, 'class_weight'), _ptr(dz, torch.float32, 'dz'),
-                                                  _ptr(loss_terms, torch.float32, 'loss_terms'), B,
-                                                  _ptr(counters, torch.int64, 'counters'), _stream())
-        _check(code, 'amar_loss_grad_weighted_f32')
+        _launch('amar_loss_grad_weighted_f32', int(loss), hp, *_col(p, 'p'), _ptr(y, F32, 'y'), _ptr(sample_weight, F32, 'sample_weight'),
+                _ptr(class_weight, F32, 'class_weight'), _ptr(dz, F32, 'dz'), _ptr(loss_terms, F32, 'loss_terms'), B,
+                _ptr(counters, torch.int64, 'counters'))
         return
-    code = load().amar_loss_grad_f32(int(loss), hp, _ptr(p, torch.float32, 'p'), _ld(p, 'p') if p.dim() == 2 else 1,
-                                     _ptr(y, torch.float32, 'y'), _ptr(dz, torch.float32, 'dz'),
-                                     _ptr(loss_terms, torch.float32, 'loss_terms'), B, _ptr(counters, torch.int64, 'counters'), _stream())
-    _check(code, 'amar_loss_grad_f32')
+    _launch('amar_loss_grad_f32', int(loss), hp, *_col(p, 'p'), _ptr(y, F32, 'y'), _ptr(dz, F32, 'dz'), _ptr(loss_terms, F32, 'loss_terms'), B,
+            _ptr(counters, torch.int64, 'counters'))
 
 
 def bpr_sample(pos_ptr, pos_ids, neg_ptr, neg_ids, n_users, seed, step, u, items, y=None, advance=True):
@@ -2101,11 +1966,9 @@ def bpr_sample(pos_ptr, pos_ids, neg_ptr, neg_ids, n_users, seed, step, u, items
     if u.numel() != 2 * h or items.numel() != 2 * h or (y is not None and y.numel() != 2 * h) or step.numel() != 1 \
             or step.dtype != torch.int64 or pos_ptr.numel() != n_users + 1 or neg_ptr.numel() != n_users + 1:
         raise ValueError("bpr_sample: u, items (and y) of 2h elements, an int64 step and CSR row pointers [n_users + 1] expected")
-    code = load().amar_bpr_sample_i32(_ptr(pos_ptr, torch.int32, 'pos_ptr'), _ptr(pos_ids, torch.int32, 'pos_ids'),
-                                      _ptr(neg_ptr, torch.int32, 'neg_ptr'), _ptr(neg_ids, torch.int32, 'neg_ids'), int(n_users),
-                                      int(seed) & 0xFFFFFFFFFFFFFFFF, step.data_ptr() if step.is_cuda else _ptr(step), int(bool(advance)), h,
-                                      _ptr(u, torch.int32, 'u'), _ptr(items, torch.int32, 'items'), _ptr(y, torch.float32, 'y'), _stream())
-    _check(code, 'amar_bpr_sample_i32')
+    _launch('amar_bpr_sample_i32', _ptr(pos_ptr, I32, 'pos_ptr'), _ptr(pos_ids, I32, 'pos_ids'), _ptr(neg_ptr, I32, 'neg_ptr'), _ptr(neg_ids, I32, 'neg_ids'),
+            int(n_users), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(step), int(bool(advance)), h, _ptr(u, I32, 'u'), _ptr(items, I32, 'items'),
+            _ptr(y, F32, 'y'))
 
 
 def bpr_sample_triplets(pos_ptr, pos_ids, excl_ptr, excl_ids, n_users, n_items, item_base, seed, step, u, items, y=None,
@@ -2120,12 +1983,9 @@ def bpr_sample_triplets(pos_ptr, pos_ids, excl_ptr, excl_ids, n_users, n_items, 
     if u.numel() != 2 * h or items.numel() != 2 * h or (y is not None and y.numel() != 2 * h) or step.numel() != 1 \
             or step.dtype != torch.int64 or pos_ptr.numel() != n_users + 1 or excl_ptr.numel() != n_users + 1:
         raise ValueError("bpr_sample_triplets: u, items (and y) of 2h elements, an int64 step and CSR row pointers [n_users + 1] expected")
-    code = load().amar_bpr_sample_triplets_i32(
-        _ptr(pos_ptr, torch.int32, 'pos_ptr'), _ptr(pos_ids, torch.int32, 'pos_ids'), _ptr(excl_ptr, torch.int32, 'excl_ptr'),
-        _ptr_entries(excl_ids, torch.int32, 'excl_ids'), int(n_users), int(n_items), int(item_base), int(n_negatives), int(mode),
-        int(seed) & 0xFFFFFFFFFFFFFFFF, step.data_ptr() if step.is_cuda else _ptr(step), int(bool(advance)), h,
-        _ptr(u, torch.int32, 'u'), _ptr(items, torch.int32, 'items'), _ptr(y, torch.float32, 'y'), _stream())
-    _check(code, 'amar_bpr_sample_triplets_i32')
+    _launch('amar_bpr_sample_triplets_i32', _ptr(pos_ptr, I32, 'pos_ptr'), _ptr(pos_ids, I32, 'pos_ids'), _ptr(excl_ptr, I32, 'excl_ptr'),
+            _ptr_entries(excl_ids, I32, 'excl_ids'), int(n_users), int(n_items), int(item_base), int(n_negatives), int(mode),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(step), int(bool(advance)), h, _ptr(u, I32, 'u'), _ptr(items, I32, 'items'), _ptr(y, F32, 'y'))
 
 
 class Dropout:
@@ -2175,9 +2035,7 @@ def dropout(X, drop, out=None):
     if X.dim() != 2 or tuple(Y.shape) != tuple(X.shape):
         raise ValueError("dropout: X and out [n, C] expected")
     n, C = X.shape
-    code = load().amar_dropout_f32(_ptr(X, torch.float32, 'X'), _ld(X, 'X'), _ptr(Y, torch.float32, 'out'), _ld(Y, 'out'), n, C,
-                                   *drop._args(), _stream())
-    _check(code, 'amar_dropout_f32')
+    _launch('amar_dropout_f32', *_mat(X, 'X'), *_mat(Y, 'out'), n, C, *drop._args())
     return Y
 
 
@@ -2185,82 +2043,46 @@ def dropout_advance(step):
     """step += 1 on the device: once per training step, after the last kernel that reads it."""
     if step.numel() != 1 or step.dtype != torch.int64:
         raise ValueError("dropout_advance: one int64 on the device expected")
-    _check(load().amar_dropout_advance(_ptr(step, torch.int64, 'step'), _stream()), 'amar_dropout_advance')
+    _launch('amar_dropout_advance', _ptr(step, torch.int64, 'step'))
 
 
 def gat_layer_dropout(rowptr, colidx, H, s_self, s_neigh, bias, Y, drop, self_loop=True):
     """gat_layer with the attention coefficients dropped after the softmax (training); sorted columns.  Entries (i, j, o) and
     (j, i, o) share one bit (a symmetric multiset's two images of an edge; on a directed graph, a reciprocal pair)."""
-    n_rows = rowptr.numel() - 1
-    C = H.shape[1]
-    if tuple(Y.shape) != (n_rows, C) or bias.numel() != C or s_self.numel() < n_rows or s_neigh.numel() < H.shape[0]:
-        raise ValueError("gat_layer_dropout: bias [C], Y [n_rows, C], s_self/s_neigh [n] expected")
-    code = load().amar_gat_layer_dropout_f32(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'),
-        _ptr(H, torch.float32, 'H'), _ld(H, 'H'), C, _ptr(s_self, torch.float32, 's_self'),
-        _ptr(s_neigh, torch.float32, 's_neigh'), _ptr(bias, torch.float32, 'bias'),
-        _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'), 1 if self_loop else 0, n_rows, *drop._args(), _stream())
-    _check(code, 'amar_gat_layer_dropout_f32')
+    _gat_layer('gat_layer_dropout', rowptr, colidx, H, s_self, s_neigh, bias, Y, self_loop, drop)
 
 
 def gat_bwd_dropout(rowptr, colidx, H, s_self, s_neigh, Y, dY, bias, a_self, a_neigh, drop, self_loop=True, transposed=None):
     """Reverse of gat_layer_dropout with the regenerated bits. Returns (dout [n, C], ds [n], dt [n], dH [n, C]).
     transposed = (t_rowptr, t_colidx), the stable transpose of the structure, for an edge multiset that is not symmetric
     (amar_gat_bwd_directed_dropout_f32); None: the structure is its own transpose."""
-    n = rowptr.numel() - 1
-    C = H.shape[1]
-    if tuple(Y.shape) != (n, C) or tuple(dY.shape) != (n, C) or H.shape[0] != n or bias.numel() != C or \
-            a_self.numel() != C or a_neigh.numel() != C:
-        raise ValueError("gat_bwd_dropout: H, Y, dY [n, C]; bias, a_self, a_neigh [C] expected")
-    dev = H.device
-    dout = torch.empty((n, C), dtype=torch.float32, device=dev)
-    scratch = torch.empty(3 * n, dtype=torch.float32, device=dev)
-    ds, dt = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
-    dH = torch.empty((n, C), dtype=torch.float32, device=dev)
-    name = 'amar_gat_bwd_dropout_f32' if transposed is None else 'amar_gat_bwd_directed_dropout_f32'
-    code = getattr(load(), name)(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), *_transposed_ptrs(transposed, n, colidx),
-        _ptr(H, torch.float32, 'H'), _ld(H, 'H'), C,
-        _ptr(s_self, torch.float32, 's_self'), _ptr(s_neigh, torch.float32, 's_neigh'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
-        _ptr(dY, torch.float32, 'dY'), _ld(dY, 'dY'), _ptr(bias, torch.float32, 'bias'), _ptr(a_self, torch.float32, 'a_self'),
-        _ptr(a_neigh, torch.float32, 'a_neigh'), _ptr(dout), _ptr(scratch), _ptr(ds), _ptr(dt), _ptr(dH), C,
-        1 if self_loop else 0, n, *drop._args(), _stream())
-    _check(code, name)
-    return dout, ds, dt, dH
+    return _gat_bwd('gat_bwd_dropout', rowptr, colidx, H, s_self, s_neigh, Y, dY, bias, a_self, a_neigh, self_loop, transposed, drop)
 
 
-class ScatterAddRowsRouteInfo(ctypes.Structure):
+class ScatterAddRowsRouteInfo(_RouteInfo):
     """include/amar_hip.h: amar_scatter_add_rows_route_info"""
     _fields_ = [(name, ctypes.c_int32) for name in ('kernel', 'blocks', 'lds_bytes', 'positions_per_wave')]
-
-    def as_dict(self):
-        d = {name: int(getattr(self, name)) for name, _ in self._fields_}
-        d['kernel'] = 'atomic' if d['kernel'] == 1 else 'owner'
-        return d
+    KERNELS = {0: 'owner', 1: 'atomic'}
 
 
 def scatter_add_rows_route(M, W):
     """Which kernel scatter_add_rows takes for M ids of W columns (amar_scatter_add_rows_route: host only).  A dict: kernel 'owner' |
     'atomic', blocks, lds_bytes, positions_per_wave."""
     info = ScatterAddRowsRouteInfo()
-    _check(load().amar_scatter_add_rows_route(int(M), int(W), ctypes.byref(info)), 'amar_scatter_add_rows_route')
+    _call('amar_scatter_add_rows_route', int(M), int(W), ctypes.byref(info))
     return info.as_dict()
 
 
 def scatter_add_rows(src, ids, dst, base=0):
     if src.shape[0] != ids.numel() or src.shape[1] != dst.shape[1]:
         raise ValueError("scatter_add_rows: src [M, W], ids [M], dst [*, W] expected")
-    code = load().amar_scatter_add_rows_f32(_ptr(src, torch.float32, 'src'), _ld(src, 'src'), _ptr(ids, torch.int32, 'ids'), int(base),
-                                            _ptr(dst, torch.float32, 'dst'), _ld(dst, 'dst'), src.shape[0], src.shape[1], _stream())
-    _check(code, 'amar_scatter_add_rows_f32')
+    _launch('amar_scatter_add_rows_f32', *_mat(src, 'src'), _ptr(ids, I32, 'ids'), int(base), *_mat(dst, 'dst'), src.shape[0], src.shape[1])
 
 
 def add_inplace(dst, src, scale=1.0):
     if tuple(dst.shape) != tuple(src.shape):
         raise ValueError("add_inplace: shapes differ")
-    code = load().amar_add_inplace_f32(_ptr(dst, torch.float32, 'dst'), _ld(dst, 'dst'), _ptr(src, torch.float32, 'src'), _ld(src, 'src'),
-                                       dst.shape[0], dst.shape[1], float(scale), _stream())
-    _check(code, 'amar_add_inplace_f32')
+    _launch('amar_add_inplace_f32', *_mat(dst, 'dst'), *_mat(src, 'src'), dst.shape[0], dst.shape[1], float(scale))
 
 
 def row_affine(a, scale, out, b=None):
@@ -2268,10 +2090,7 @@ def row_affine(a, scale, out, b=None):
     M, W = a.shape
     if tuple(out.shape) != (M, W) or scale.numel() != M or (b is not None and tuple(b.shape) != (M, W)):
         raise ValueError("row_affine: a, b, out [M, W] and scale [M] expected")
-    code = load().amar_row_affine_f32(_ptr(a, torch.float32, 'a'), _ld(a, 'a'), _ptr(b, torch.float32, 'b'),
-                                      _ld(b, 'b') if b is not None else 0, _ptr(scale, torch.float32, 'scale'),
-                                      _ptr(out, torch.float32, 'out'), _ld(out, 'out'), M, W, _stream())
-    _check(code, 'amar_row_affine_f32')
+    _launch('amar_row_affine_f32', *_mat(a, 'a'), *_mat(b, 'b'), _ptr(scale, F32, 'scale'), *_mat(out, 'out'), M, W)
 
 
 def l2norm_fwd(z, nrm, inv, y, act='relu'):
@@ -2279,20 +2098,14 @@ def l2norm_fwd(z, nrm, inv, y, act='relu'):
     M, C = z.shape
     if tuple(nrm.shape) != (M, C) or tuple(y.shape) != (M, C) or inv.numel() != M:
         raise ValueError("l2norm_fwd: z, nrm, y [M, C] and inv [M] expected")
-    code = load().amar_l2norm_fwd_f32(_ptr(z, torch.float32, 'z'), _ld(z, 'z'), _ptr(nrm, torch.float32, 'nrm'), _ld(nrm, 'nrm'),
-                                      _ptr(inv, torch.float32, 'inv'), _ptr(y, torch.float32, 'y'), _ld(y, 'y'), M, C,
-                                      ACT_CODES[act], _stream())
-    _check(code, 'amar_l2norm_fwd_f32')
+    _launch('amar_l2norm_fwd_f32', *_mat(z, 'z'), *_mat(nrm, 'nrm'), _ptr(inv, F32, 'inv'), *_mat(y, 'y'), M, C, ACT_CODES[act])
 
 
 def l2norm_bwd(dy, nrm, inv, dz, act='relu'):
     M, C = dy.shape
     if tuple(nrm.shape) != (M, C) or tuple(dz.shape) != (M, C) or inv.numel() != M:
         raise ValueError("l2norm_bwd: dy, nrm, dz [M, C] and inv [M] expected")
-    code = load().amar_l2norm_bwd_f32(_ptr(dy, torch.float32, 'dy'), _ld(dy, 'dy'), _ptr(nrm, torch.float32, 'nrm'), _ld(nrm, 'nrm'),
-                                      _ptr(inv, torch.float32, 'inv'), _ptr(dz, torch.float32, 'dz'), _ld(dz, 'dz'), M, C,
-                                      ACT_CODES[act], _stream())
-    _check(code, 'amar_l2norm_bwd_f32')
+    _launch('amar_l2norm_bwd_f32', *_mat(dy, 'dy'), *_mat(nrm, 'nrm'), _ptr(inv, F32, 'inv'), *_mat(dz, 'dz'), M, C, ACT_CODES[act])
 
 
 def _transposed_ptrs(transposed, n, colidx):
@@ -2302,32 +2115,38 @@ def _transposed_ptrs(transposed, n, colidx):
     t_rowptr, t_colidx = transposed
     if t_rowptr.numel() != n + 1 or t_colidx.numel() != colidx.numel():
         raise ValueError("gat_bwd: transposed = (t_rowptr [n + 1], t_colidx [nnz]) of the same square structure expected")
-    return _ptr(t_rowptr, torch.int32, 't_rowptr'), _ptr_entries(t_colidx, torch.int32, 't_colidx')
+    return _ptr(t_rowptr, I32, 't_rowptr'), _ptr_entries(t_colidx, I32, 't_colidx')
 
 
-def gat_bwd(rowptr, colidx, H, s_self, s_neigh, Y, dY, bias, a_self, a_neigh, self_loop=True, transposed=None):
-    """Reverse of gat_layer. Returns (dout [n, C], ds [n], dt [n], dH [n, C]).  transposed = (t_rowptr, t_colidx): as
-    gat_bwd_dropout (amar_gat_bwd_directed_f32)."""
+# (directed structure, dropout) -> the reverse entry point: the directed ones take the transpose after the structure, the
+# dropout ones the dropout site before the stream
+_GAT_BWD_SYMBOLS = {(False, False): 'amar_gat_bwd_f32', (True, False): 'amar_gat_bwd_directed_f32',
+                    (False, True): 'amar_gat_bwd_dropout_f32', (True, True): 'amar_gat_bwd_directed_dropout_f32'}
+
+
+def _gat_bwd(what, rowptr, colidx, H, s_self, s_neigh, Y, dY, bias, a_self, a_neigh, self_loop, transposed, drop):
+    """gat_bwd (drop None) and gat_bwd_dropout."""
     n = rowptr.numel() - 1
     C = H.shape[1]
     if tuple(Y.shape) != (n, C) or tuple(dY.shape) != (n, C) or H.shape[0] != n or bias.numel() != C or \
             a_self.numel() != C or a_neigh.numel() != C:
-        raise ValueError("gat_bwd: H, Y, dY [n, C]; bias, a_self, a_neigh [C] expected")
+        raise ValueError("{}: H, Y, dY [n, C]; bias, a_self, a_neigh [C] expected".format(what))
     dev = H.device
     dout = torch.empty((n, C), dtype=torch.float32, device=dev)
     scratch = torch.empty(3 * n, dtype=torch.float32, device=dev)
     ds, dt = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
     dH = torch.empty((n, C), dtype=torch.float32, device=dev)
-    name = 'amar_gat_bwd_f32' if transposed is None else 'amar_gat_bwd_directed_f32'
-    code = getattr(load(), name)(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), *_transposed_ptrs(transposed, n, colidx),
-        _ptr(H, torch.float32, 'H'), _ld(H, 'H'), C,
-        _ptr(s_self, torch.float32, 's_self'), _ptr(s_neigh, torch.float32, 's_neigh'), _ptr(Y, torch.float32, 'Y'), _ld(Y, 'Y'),
-        _ptr(dY, torch.float32, 'dY'), _ld(dY, 'dY'), _ptr(bias, torch.float32, 'bias'), _ptr(a_self, torch.float32, 'a_self'),
-        _ptr(a_neigh, torch.float32, 'a_neigh'), _ptr(dout), _ptr(scratch), _ptr(ds), _ptr(dt), _ptr(dH), C,
-        1 if self_loop else 0, n, _stream())
-    _check(code, name)
+    _launch(_GAT_BWD_SYMBOLS[transposed is not None, drop is not None], _ptr(rowptr, I32, 'rowptr'), _ptr_entries(colidx, I32, 'colidx'),
+            *_transposed_ptrs(transposed, n, colidx), *_mat(H, 'H'), C, _ptr(s_self, F32, 's_self'), _ptr(s_neigh, F32, 's_neigh'), *_mat(Y, 'Y'),
+            *_mat(dY, 'dY'), _ptr(bias, F32, 'bias'), _ptr(a_self, F32, 'a_self'), _ptr(a_neigh, F32, 'a_neigh'), _ptr(dout), _ptr(scratch), _ptr(ds),
+            _ptr(dt), _ptr(dH), C, 1 if self_loop else 0, n, *(drop._args() if drop is not None else ()))
     return dout, ds, dt, dH
+
+
+def gat_bwd(rowptr, colidx, H, s_self, s_neigh, Y, dY, bias, a_self, a_neigh, self_loop=True, transposed=None):
+    """Reverse of gat_layer. Returns (dout [n, C], ds [n], dt [n], dH [n, C]).  transposed = (t_rowptr, t_colidx): as
+    gat_bwd_dropout (amar_gat_bwd_directed_f32)."""
+    return _gat_bwd('gat_bwd', rowptr, colidx, H, s_self, s_neigh, Y, dY, bias, a_self, a_neigh, self_loop, transposed, None)
 
 
 def csr_transpose(rowptr, colidx, n_cols):
@@ -2339,7 +2158,7 @@ def csr_transpose(rowptr, colidx, n_cols):
     if n_rows < 0 or n_cols < 0:
         raise ValueError("csr_transpose: rowptr [n_rows + 1] and n_cols >= 0 expected")
     dev = rowptr.device
-    _ptr(rowptr, torch.int32, 'rowptr'), _ptr(colidx, torch.int32, 'colidx')
+    _ptr(rowptr, I32, 'rowptr'), _ptr(colidx, I32, 'colidx')                     # on the device, int32: before the host reads below
     if int(rowptr[0]) != 0 or int(rowptr[-1]) != nnz:
         raise ValueError("csr_transpose: rowptr must run from 0 to nnz")
     if nnz and (n_rows < 1 or bool((rowptr[1:] < rowptr[:-1]).any()) or int(colidx.min()) < 0 or int(colidx.max()) >= n_cols):
@@ -2348,11 +2167,8 @@ def csr_transpose(rowptr, colidx, n_cols):
     t_colidx = torch.empty(nnz, dtype=torch.int32, device=dev)
     perm = torch.empty(nnz, dtype=torch.int32, device=dev)
     cursor = torch.empty(max(n_cols, 1), dtype=torch.int32, device=dev)
-    code = load().amar_csr_transpose_i32(
-        _ptr(rowptr, torch.int32, 'rowptr'), _ptr_entries(colidx, torch.int32, 'colidx'), n_rows, n_cols, nnz,
-        _ptr(t_rowptr, torch.int32, 't_rowptr'), _ptr_entries(t_colidx, torch.int32, 't_colidx'), _ptr_entries(perm, torch.int32, 'perm'),
-        _ptr(cursor, torch.int32, 'cursor'), _stream())
-    _check(code, 'amar_csr_transpose_i32')
+    _launch('amar_csr_transpose_i32', _ptr(rowptr, I32, 'rowptr'), _ptr_entries(colidx, I32, 'colidx'), n_rows, n_cols, nnz, _ptr(t_rowptr, I32, 't_rowptr'),
+            _ptr_entries(t_colidx, I32, 't_colidx'), _ptr_entries(perm, I32, 'perm'), _ptr(cursor, I32, 'cursor'))
     return t_rowptr, t_colidx, perm
 
 
@@ -2361,10 +2177,7 @@ def attention_mix(a, b, ta, tb, out):
     M, D = a.shape
     if any(tuple(t.shape) != (M, D) for t in (b, ta, tb, out)):
         raise ValueError("attention_mix: five [M, D] blocks expected")
-    code = load().amar_attention_mix_f32(_ptr(a, torch.float32, 'a'), _ld(a, 'a'), _ptr(b, torch.float32, 'b'), _ld(b, 'b'),
-                                         _ptr(ta, torch.float32, 'ta'), _ld(ta, 'ta'), _ptr(tb, torch.float32, 'tb'), _ld(tb, 'tb'),
-                                         _ptr(out, torch.float32, 'out'), _ld(out, 'out'), M, D, _stream())
-    _check(code, 'amar_attention_mix_f32')
+    _launch('amar_attention_mix_f32', *_mat(a, 'a'), *_mat(b, 'b'), *_mat(ta, 'ta'), *_mat(tb, 'tb'), *_mat(out, 'out'), M, D)
 
 
 def attention_mix_bwd(dout, a, b, ta, tb):
@@ -2373,11 +2186,8 @@ def attention_mix_bwd(dout, a, b, ta, tb):
     if any(tuple(t.shape) != (M, D) for t in (dout, b, ta, tb)):
         raise ValueError("attention_mix_bwd: five [M, D] blocks expected")
     outs = [torch.empty((M, D), dtype=torch.float32, device=a.device) for _ in range(4)]
-    code = load().amar_attention_mix_bwd_f32(_ptr(dout, torch.float32, 'dout'), _ld(dout, 'dout'), _ptr(a, torch.float32, 'a'), _ld(a, 'a'),
-                                             _ptr(b, torch.float32, 'b'), _ld(b, 'b'), _ptr(ta, torch.float32, 'ta'), _ld(ta, 'ta'),
-                                             _ptr(tb, torch.float32, 'tb'), _ld(tb, 'tb'), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
-                                             _ptr(outs[3]), M, D, _stream())
-    _check(code, 'amar_attention_mix_bwd_f32')
+    _launch('amar_attention_mix_bwd_f32', *_mat(dout, 'dout'), *_mat(a, 'a'), *_mat(b, 'b'), *_mat(ta, 'ta'), *_mat(tb, 'tb'),
+            _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]), M, D)
     return outs
 
 
@@ -2385,10 +2195,7 @@ def add3_act(a, b, c, out, act='relu'):
     M, W = a.shape
     if any(tuple(t.shape) != (M, W) for t in (b, c, out)):
         raise ValueError("add3_act: four [M, W] blocks expected")
-    code = load().amar_add3_act_f32(_ptr(a, torch.float32, 'a'), _ld(a, 'a'), _ptr(b, torch.float32, 'b'), _ld(b, 'b'),
-                                    _ptr(c, torch.float32, 'c'), _ld(c, 'c'), _ptr(out, torch.float32, 'out'), _ld(out, 'out'),
-                                    M, W, ACT_CODES[act], _stream())
-    _check(code, 'amar_add3_act_f32')
+    _launch('amar_add3_act_f32', *_mat(a, 'a'), *_mat(b, 'b'), *_mat(c, 'c'), *_mat(out, 'out'), M, W, ACT_CODES[act])
 
 
 def locality_scale(x, w, out):
@@ -2396,19 +2203,15 @@ def locality_scale(x, w, out):
     M, W = x.shape
     if tuple(out.shape) != (M, W) or w.numel() != M or not w.is_contiguous():
         raise ValueError("locality_scale: x, out [M, W] and contiguous w [M] expected")
-    code = load().amar_locality_scale_f32(_ptr(x, torch.float32, 'x'), _ld(x, 'x'), _ptr(w, torch.float32, 'w'),
-                                          _ptr(out, torch.float32, 'out'), _ld(out, 'out'), M, W, _stream())
-    _check(code, 'amar_locality_scale_f32')
+    _launch('amar_locality_scale_f32', *_mat(x, 'x'), _ptr(w, F32, 'w'), *_mat(out, 'out'), M, W)
 
 
 def locality_scale_bwd(dout, x, w, dx, dw, accumulate=False):
     M, W = x.shape
     if tuple(dout.shape) != (M, W) or tuple(dx.shape) != (M, W) or w.numel() != M or dw.numel() != M:
         raise ValueError("locality_scale_bwd: dout, x, dx [M, W]; w, dw [M] expected")
-    code = load().amar_locality_scale_bwd_f32(_ptr(dout, torch.float32, 'dout'), _ld(dout, 'dout'), _ptr(x, torch.float32, 'x'), _ld(x, 'x'),
-                                              _ptr(w, torch.float32, 'w'), _ptr(dx, torch.float32, 'dx'), _ld(dx, 'dx'),
-                                              _ptr(dw, torch.float32, 'dw'), M, W, 1 if accumulate else 0, _stream())
-    _check(code, 'amar_locality_scale_bwd_f32')
+    _launch('amar_locality_scale_bwd_f32', *_mat(dout, 'dout'), *_mat(x, 'x'), _ptr(w, F32, 'w'), *_mat(dx, 'dx'), _ptr(dw, F32, 'dw'), M, W,
+            1 if accumulate else 0)
 
 
 def transpose(src):
@@ -2416,7 +2219,7 @@ def transpose(src):
     if not src.is_contiguous():
         raise ValueError("transpose: contiguous [K, N] expected")
     dst = torch.empty((N, K), dtype=torch.float32, device=src.device)
-    _check(load().amar_transpose_f32(_ptr(src, torch.float32, 'src'), K, N, _ptr(dst), _stream()), 'amar_transpose_f32')
+    _launch('amar_transpose_f32', _ptr(src, F32, 'src'), K, N, _ptr(dst))
     return dst
 
 
@@ -2424,7 +2227,5 @@ def adam(w, g, m, v, lr_t, beta_1, beta_2, epsilon, l2=0.0):
     if not (w.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()) or \
             not (w.numel() == g.numel() == m.numel() == v.numel()):
         raise ValueError("adam: contiguous tensors of equal size expected")
-    code = load().amar_adam_f32(_ptr(w, torch.float32, 'w'), _ptr(g, torch.float32, 'g'), _ptr(m, torch.float32, 'm'),
-                                _ptr(v, torch.float32, 'v'), w.numel(), float(lr_t), float(beta_1), float(beta_2), float(epsilon),
-                                float(l2), _stream())
-    _check(code, 'amar_adam_f32')
+    _launch('amar_adam_f32', _ptr(w, F32, 'w'), _ptr(g, F32, 'g'), _ptr(m, F32, 'm'), _ptr(v, F32, 'v'), w.numel(), float(lr_t), float(beta_1), float(beta_2),
+            float(epsilon), float(l2))
