@@ -160,6 +160,8 @@ SIGNATURES = {
     'amar_rank_metrics_f64': (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P]),
     'amar_rerank_mmr_f32': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _F32, _I32, _P, _P, _P, _P, _P]),
     'amar_list_diversity_f64': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _P]),
+    'amar_explain_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, _I32, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _I32, _I32,
+                                        _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -1587,6 +1589,41 @@ def list_diversity(lists, T, ks, metric='cosine'):
     _launch('amar_list_diversity_f64', _ptr(lists, I32, 'lists') if m else None, m, K, *_mat(T, 'T'), int(T.shape[0]), int(T.shape[1]),
             NEAREST_METRICS[metric], ks_c, len(ks), _ptr(out_ild) if m else None, _ptr(out_count) if m else None)
     return out_ild, out_count
+
+
+EXPLAIN_MAX_K, EXPLAIN_MAX_E, EXPLAIN_MAX_PROP_ROW = 64, 16, 2048      # include/amar_hip.h: AMAR_EXPLAIN_MAX_*
+
+
+def explain(lists, liked_ptr, liked_items, T, n_evidence=3, n_properties=0, metric='cosine', users=None, prop_ptr=None, prop_ids=None,
+            prop_weight=None, max_prop_row=0):
+    """Evidence items and shared properties of device lists (amar_explain_f32): lists int32 [m, K] rows of T (-1 padded), row j
+    belonging to users[j] (int32 [m]; None: user j), the liked items as a CSR over users, the item-property links as an optional CSR
+    over items with float32 weights (max_prop_row: its longest row).  Returns (evidence int32 [m, K, E], evidence_sim float32 [m, K, E],
+    props int32 [m, K, Q], prop_score float32 [m, K, Q], prop_support int32 [m, K, Q]) on the device.  One launch, no workspace."""
+    if metric not in NEAREST_METRICS:
+        raise ValueError("explain: metric must be one of {} (got {!r})".format(sorted(NEAREST_METRICS), metric))
+    m, K = _lists_matrix(lists, 'lists')
+    if users is not None and int(users.numel()) != m:
+        raise ValueError("explain: users must name one user per list")
+    n_users = int(liked_ptr.numel()) - 1
+    n_items = int(T.shape[0])
+    if prop_ptr is not None and int(prop_ptr.numel()) != n_items + 1:
+        raise ValueError("explain: prop_ptr must have one entry per row of T plus one")
+    E, Q = int(n_evidence), int(n_properties)
+    dev = T.device
+    out_ev = torch.empty((m, K, max(E, 0)), dtype=torch.int32, device=dev)
+    out_sim = torch.empty((m, K, max(E, 0)), dtype=torch.float32, device=dev)
+    out_p = torch.empty((m, K, max(Q, 0)), dtype=torch.int32, device=dev)
+    out_ps = torch.empty((m, K, max(Q, 0)), dtype=torch.float32, device=dev)
+    out_pc = torch.empty((m, K, max(Q, 0)), dtype=torch.int32, device=dev)
+    filled = m > 0 and Q > 0
+    _launch('amar_explain_f32', _ptr(lists, I32, 'lists') if m else None, m, K, _ptr(users, I32, 'users'), _ptr(liked_ptr, I32, 'liked_ptr'),
+            _ptr_entries(liked_items, I32, 'liked_items'), n_users, *_mat(T, 'T'), n_items, int(T.shape[1]), NEAREST_METRICS[metric],
+            _ptr(prop_ptr, I32, 'prop_ptr'), _ptr_entries(prop_ids, I32, 'prop_ids'), _ptr_entries(prop_weight, F32, 'prop_weight'),
+            int(prop_weight.numel()) if prop_weight is not None else 0, int(max_prop_row), E, Q,
+            _ptr(out_ev) if m else None, _ptr(out_sim) if m else None, _ptr(out_p) if filled else None, _ptr(out_ps) if filled else None,
+            _ptr(out_pc) if filled else None)
+    return out_ev, out_sim, out_p, out_ps, out_pc
 
 
 # ---- training step ----------------------------------------------------------------------------------------------

@@ -50,6 +50,11 @@ def index_props(props_triples, items):
     return np.stack([it, p_idx + len(items), ones], axis=1), props
 
 
+def property_identifiers(props_filepath, sep='\t'):
+    """The original property identifiers in the order of `index_props`' property indices (its second return value)."""
+    return np.unique(_read_tsv(props_filepath, sep)[:, 1])
+
+
 def load_train_test_ratings(
         train_filepath,
         test_filepath,

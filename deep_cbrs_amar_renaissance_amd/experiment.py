@@ -38,8 +38,8 @@ from deep_cbrs_amar_renaissance_amd.models.basic import BasicRS, BasicGNN, Basic
 from deep_cbrs_amar_renaissance_amd.models.hybrid import HybridCBRS, HybridBertGNN
 from deep_cbrs_amar_renaissance_amd.utilities import losses
 from deep_cbrs_amar_renaissance_amd.utilities.keras import Callback, EarlyStopping, ReduceLROnPlateau, get_total_parameters
-from deep_cbrs_amar_renaissance_amd.utilities.metrics import full_ranking_metrics, recommendations_frame, resolve_compiled, top_k_predictions, \
-    top_k_metrics
+from deep_cbrs_amar_renaissance_amd.utilities.metrics import explanations_frame, full_ranking_metrics, recommendations_frame, resolve_compiled, \
+    top_k_predictions, top_k_metrics
 from deep_cbrs_amar_renaissance_amd.utilities.schedules import resolve as resolve_learning_rate
 from deep_cbrs_amar_renaissance_amd.utilities.utils import \
     get_experiment_logger, nested_dict_update, make_grid, mlflow_linearize, setup_mlflow
@@ -274,6 +274,10 @@ class Experimenter:
             kwargs['train_ratings_filepath'] = kept_path
             _, self.valset = self.load_function(**dict(kwargs, test_ratings_filepath=held_path))
         self.trainset, self.testset = self.load_function(**kwargs)
+        # the loaders index the properties and drop their original identifiers: explanations are written with them
+        self.property_ids = None
+        if kwargs.get('props_triples_filepath') and kwargs.get('type_adjacency') in ('unary-uip', 'unary-kg'):
+            self.property_ids = loaders.property_identifiers(kwargs['props_triples_filepath'], kwargs.get('sep', '\t'))
 
     def validation_fit_args(self):
         """fit()'s validation arguments from parameters.validation ({fraction, freq, ranking_ks, early_stopping, reduce_lr}); {} without
@@ -384,6 +388,8 @@ class Experimenter:
             self.write_similar_items(**dict(self.config.parameters.get('similar_items')))
         if self.config.parameters.get('diversify'):
             self.write_diverse(**dict(self.config.parameters.get('diversify')))
+        if self.config.parameters.get('explain'):
+            self.write_explanations(**dict(self.config.parameters.get('explain')))
         self.logger.info('\n' + str(metrics))
         print('\n' + str(metrics))
         return metrics
@@ -441,6 +447,18 @@ class Experimenter:
                 logged.update({prefix + name: value for name, value in rec.diversity_metrics(lists, table, [k], metric, n_items).items()})
         self.run_log.log_metrics(logged)
         return path, logged
+
+    def write_explanations(self, k=10, n_evidence=3, n_properties=3, metric='cosine', space=None):
+        """Opt-in (parameters.explain: {k, n_evidence, n_properties, metric, space}): every user's top-k explained (`explain()`),
+        written as <predictions_dest>/explanations_<k>.tsv, one row per (user, item, rank): user, item, rank, evidence items,
+        their similarities, shared properties, their scores, their supports (lists joined by spaces; original identifiers, the
+        properties by the loader's identifiers or, for a trainset that came without them, by property index)."""
+        out = self.model.explain(self.trainset, k=int(k), n_evidence=int(n_evidence), n_properties=int(n_properties), metric=metric,
+                                 space=space)
+        path = path_join(self.predictions_dest, "explanations_{}.tsv".format(int(k)))
+        explanations_frame(out, self.trainset.users, self.trainset.items, getattr(self, 'property_ids', None)).to_csv(
+            path, sep='\t', header=False, index=False)
+        return path
 
     def run(self):
         self.train()

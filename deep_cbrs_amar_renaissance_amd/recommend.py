@@ -27,6 +27,10 @@ or cosine, nothing of size m x n in memory) and ``SimilarSearch``, the mixin tha
 The third part is what a list looks like as a whole: ``rerank_mmr`` (one ``amar_rerank_mmr_f32`` launch re-ranks device pools by
 Maximal Marginal Relevance; nothing of size m x P x P in memory), the mixin's ``recommend_diverse`` / ``list_diversity``, and the
 opt-in ``diversity=`` of ``evaluate_ranking`` (intra-list diversity and catalogue coverage beside the accuracy metrics).
+
+The fourth part answers "why this item for this user?": ``liked_csr`` and ``item_property_csr`` read the liked items and the
+item-property links off the trainset, ``explain_lists`` joins them with the item vectors in one ``amar_explain_f32`` launch (nothing
+of size m x K x L in memory) and the mixin's ``explain`` runs it on ``recommend(k)``'s device lists or on the caller's items.
 """
 import contextlib
 import weakref
@@ -100,6 +104,98 @@ def _exclusion_device(trainset, n_users, n_items, exclude_seen):
         ref = (lambda obj: (lambda: obj))(ratings)
     _EXCL_CACHE[key] = (ref, np.shape(ratings), entry)
     return entry
+
+
+def liked_csr(ratings, n_users, n_items):
+    """Label-1 training pairs as a CSR over users: (ptr int64 [n_users+1], items int64) with item ROWS 0..n_items-1, sorted and
+    de-duplicated per user; the checks of `exclusion_csr`."""
+    r = np.asarray(ratings)
+    if r.size:
+        r = r[r[:, 2] == 1]
+    return exclusion_csr(r, n_users, n_items)
+
+
+def item_property_csr(trainset):
+    """The item-property links a trainset's graph already holds, as a CSR over items: (ptr int64 [|I|+1], props int64 property
+    indices 0..|P|-1 sorted and de-duplicated per item, df int64 [|P|]: the distinct items of every property, max_row: the longest
+    row), or None when the graph has no properties.  One adjacency larger than |U| + |I| ('unary-uip'): item rows |U|..|U|+|I|-1,
+    columns >= |U|+|I|; a pair of adjacencies ('unary-kg'): the item-property one, items at rows 0..|I|-1.  Duplicate (item,
+    property) links collapse to one."""
+    n_users, n_items = _sizes(trainset)
+    adj = getattr(trainset, 'adj_matrix', None)
+    if isinstance(adj, (tuple, list)):
+        if len(adj) < 2 or not hasattr(adj[1], 'tocoo'):                # (user-item, item-property[, user-property])
+            return None
+        coo, row0, col0 = adj[1].tocoo(), 0, n_items
+    elif hasattr(adj, 'tocoo') and adj.shape[0] > n_users + n_items:
+        coo, row0, col0 = adj.tocoo(), n_users, n_users + n_items
+    else:
+        return None
+    n_props = int(coo.shape[0]) - col0
+    if n_props <= 0:
+        return None
+    row, col = coo.row.astype(np.int64), coo.col.astype(np.int64)
+    keep = (row >= row0) & (row < row0 + n_items) & (col >= col0)
+    key = np.unique((row[keep] - row0) * n_props + (col[keep] - col0))
+    it, pr = key // n_props, key % n_props
+    ptr = np.zeros(n_items + 1, dtype=np.int64)
+    np.cumsum(np.bincount(it, minlength=n_items), out=ptr[1:])
+    return ptr, pr, np.bincount(pr, minlength=n_props).astype(np.int64), int(np.diff(ptr).max()) if n_items else 0
+
+
+def property_weights(df, n_items, kind='idf'):
+    """Float32 weights of the properties: 'idf' = log(|I| / df_p) computed in float64 (0 for a property nobody has), 'none' = 1."""
+    if kind == 'none':
+        return np.ones(len(df), dtype=np.float32)
+    if kind != 'idf':
+        raise ValueError("property_weight must be 'idf' or 'none' (got {!r})".format(kind))
+    df = np.asarray(df, dtype=np.float64)
+    return np.where(df > 0, np.log(float(n_items) / np.maximum(df, 1.0)), 0.0).astype(np.float32)
+
+
+# Liked and property CSRs on the device, built once per ratings array / graph (held weakly where the object allows it).  As with
+# _EXCL_CACHE the key is the object's identity: an array or graph mutated in place is not noticed, and the finalizer of a dead
+# object whose id was reused may drop the new object's entry, which only costs a rebuild.
+_LIKED_CACHE, _PROP_CACHE = {}, {}
+
+
+def _device_cached(cache, obj, key, build):
+    hit = cache.get(key)
+    if hit is not None and hit[0]() is obj:
+        return hit[1]
+    entry = build()
+    try:
+        ref = weakref.ref(obj)
+        weakref.finalize(obj, cache.pop, key, None)
+    except TypeError:                                    # not weakly referenceable: keep the object alive with its entry
+        ref = (lambda o: (lambda: o))(obj)
+    cache[key] = (ref, entry)
+    return entry
+
+
+def _liked_device(trainset, n_users, n_items):
+    ratings, dev = trainset.ratings, default_device()
+
+    def build():
+        ptr, items = liked_csr(ratings, n_users, n_items)
+        return torch.from_numpy(ptr.astype(np.int32)).to(dev), torch.from_numpy(items.astype(np.int32)).to(dev)
+    return _device_cached(_LIKED_CACHE, ratings, (id(ratings), np.shape(ratings), n_users, n_items, str(dev)), build)
+
+
+def _props_device(trainset, n_items, kind):
+    """(prop_ptr, prop_ids, weights) on the device and the longest row, or None for a trainset without properties."""
+    adj, dev = getattr(trainset, 'adj_matrix', None), default_device()
+    if adj is None:
+        return None
+
+    def build():
+        csr = item_property_csr(trainset)
+        if csr is None:
+            return None
+        ptr, ids, df, max_row = csr
+        w = torch.from_numpy(property_weights(df, n_items, kind)).to(dev)
+        return torch.from_numpy(ptr.astype(np.int32)).to(dev), torch.from_numpy(ids.astype(np.int32)).to(dev), w, max_row
+    return _device_cached(_PROP_CACHE, adj, (id(adj), n_items, kind, str(dev)), build)
 
 
 def _sizes(trainset):
@@ -385,6 +481,31 @@ def profile_queries(table, liked_rows):
     return rows.sum(1) / torch.from_numpy(sizes.astype(np.float32)).to(dev)[:, None]
 
 
+EXPLAIN_KEYS = ('users', 'items', 'evidence', 'evidence_sim', 'properties', 'property_score', 'property_support')
+
+
+def check_count(n, lo, hi, what):
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not lo <= int(n) <= hi:
+        raise ValueError("{} must be an integer in [{}, {}] (got {!r})".format(what, lo, hi, n))
+    return int(n)
+
+
+def explain_lists(lists, users, liked, table, props, n_evidence, n_properties, metric='cosine'):
+    """One amar_explain_f32 launch over device lists (int32 [m, K] rows of `table`, -1 padded; `users` int32 [m] on the device or
+    None for the identity): `liked` = (ptr, items) of `liked_csr` on the device, `props` = (ptr, ids, weights, longest row) of the
+    item-property CSR on the device or None.  Returns the device tensors (evidence int32 [m, K, E], evidence_sim float32,
+    properties int32 [m, K, Q], property_score float32, property_support int32); without `props` Q is 0.  The caller has checked the
+    table's width (`check_width`); the library refuses any other."""
+    table = _as_device_matrix(table, lists.device, 'table')
+    if props is None:
+        return capi.explain(lists, liked[0], liked[1], table, n_evidence, 0, metric=check_metric(metric), users=users)
+    if props[3] > capi.EXPLAIN_MAX_PROP_ROW:
+        raise NotImplementedError("explain takes items with at most {} properties: the longest row has {}".format(
+            capi.EXPLAIN_MAX_PROP_ROW, props[3]))
+    return capi.explain(lists, liked[0], liked[1], table, n_evidence, n_properties, metric=check_metric(metric), users=users,
+                        prop_ptr=props[0], prop_ids=props[1], prop_weight=props[2], max_prop_row=props[3])
+
+
 class SimilarSearch:
     """Embedding accessors and similarity search shared by the scoring models.  A model names its spaces (`_embedding_spaces`:
     'graph' = the propagated, reduced node table, 'tower' = the first-stage Dense outputs per entity; the first one is the default)
@@ -511,3 +632,53 @@ class SimilarSearch:
         if _ON_DEVICE:
             return ild, count
         return ild.cpu().numpy(), count.cpu().numpy()
+
+    # -- explanations (amar_explain_f32) --------------------------------------------------------------------------------
+    def explain(self, trainset, users=None, items=None, k=10, n_evidence=3, n_properties=3, metric='cosine', space=None,
+                property_weight='idf', exclude_seen=True):
+        """Why these items for these users, in the model's item `space`.  items=None explains `recommend(k)` (the lists stay on the
+        device between the two launches); otherwise `items` is an [m, K] array of item node ids (-1 padded) for `users`.  For every
+        (user, item): the `n_evidence` liked training items of the user most similar to the item (similarity descending, node id
+        ascending on ties, never the item itself), and the `n_properties` properties the item shares with other liked items,
+        by score w_p * sum max(sim, 0) over those items (w_p = log(|I| / df_p) for property_weight='idf', 1 for 'none'), with
+        their support (how many liked items have the property).  Returns a dict of host arrays: users int64 [m], items int64 [m, K]
+        node ids, evidence int64 [m, K, n_evidence] node ids (-1 padded), evidence_sim float32 (-inf padded), properties int64
+        [m, K, n_properties] property indices (-1 padded), property_score float32 (-inf padded), property_support int32 (0 padded);
+        the three property arrays have a last dimension of 0 for a trainset without properties.  Inside ``device_lists()`` the
+        device tensors (item rows int32)."""
+        check_metric(metric)
+        E = check_count(n_evidence, 1, capi.EXPLAIN_MAX_E, 'n_evidence')
+        Q = check_count(n_properties, 0, capi.EXPLAIN_MAX_E, 'n_properties')
+        if property_weight not in ('idf', 'none'):
+            raise ValueError("property_weight must be 'idf' or 'none' (got {!r})".format(property_weight))
+        n_users, n_items = _sizes(trainset)
+        if items is None:
+            k = check_k(k)
+        table = self._item_embeddings(trainset, space)
+        check_width(table.shape[1], 'item vectors')
+        if items is None:
+            with device_lists():
+                u, lists, _ = self.recommend(trainset, k=k, users=users, exclude_seen=exclude_seen)
+            if len(u) == 0:
+                lists = torch.zeros((0, k), dtype=torch.int32, device=table.device)
+        else:
+            u = check_users(users, n_users)
+            a = np.asarray(items.cpu() if isinstance(items, torch.Tensor) else items)
+            if a.ndim != 2 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+                raise ValueError("items must be a 2-D [m, K] array of integer node ids")
+            if a.shape[0] != len(u) or not 1 <= a.shape[1] <= K_MAX:
+                raise ValueError("items must hold one row of 1..{} node ids per user ({} rows for {} users)".format(K_MAX, a.shape[0], len(u)))
+            a = a.astype(np.int64)
+            real = a[a != -1]
+            if real.size and (real.min() < n_users or real.max() >= n_users + n_items):
+                raise ValueError("items must be node ids in [{}, {}) or -1".format(n_users, n_users + n_items))
+            lists = torch.from_numpy(np.where(a >= 0, a - n_users, -1).astype(np.int32)).to(table.device)
+        u_dev = None if users is None else torch.from_numpy(u.astype(np.int32)).to(table.device)
+        out = explain_lists(lists.contiguous(), u_dev, _liked_device(trainset, n_users, n_items), table,
+                            _props_device(trainset, n_items, property_weight), E, Q, metric)
+        if _ON_DEVICE:
+            return dict(zip(EXPLAIN_KEYS, (u, lists) + out))
+        rows = lambda t: (lambda x: np.where(x >= 0, x + n_users, -1))(t.cpu().numpy().astype(np.int64))
+        ev, sim, pr, ps, pc = out
+        return dict(zip(EXPLAIN_KEYS, (u, rows(lists), rows(ev), sim.cpu().numpy(), pr.cpu().numpy().astype(np.int64), ps.cpu().numpy(),
+                                       pc.cpu().numpy())))

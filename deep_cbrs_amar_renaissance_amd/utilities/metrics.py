@@ -81,6 +81,31 @@ def recommendations_frame(users, items, scores, user_ids, item_ids):
     return df
 
 
+def explanations_frame(explained, user_ids, item_ids, prop_ids=None):
+    """`model.explain()`'s dict as a DataFrame with one row per (user, item, rank): original user and item identifiers, the rank
+    (1 = best), and — padding dropped, best first, joined by spaces — the evidence items with their similarities and the shared
+    properties (original identifiers from `prop_ids`, property indices without it) with their scores and supports."""
+    users = np.asarray(explained['users'], dtype=np.int64).reshape(-1)
+    items = np.asarray(explained['items'], dtype=np.int64).reshape(len(users), -1)
+    item_ids, n_users = np.asarray(item_ids), len(user_ids)
+    join = lambda values: ' '.join(str(v) for v in values)
+    rows = []
+    for j, u in enumerate(users):
+        for t, i in enumerate(items[j]):
+            if i < 0:
+                continue
+            ev = np.asarray(explained['evidence'][j, t])
+            pr = np.asarray(explained['properties'][j, t])
+            keep_e, keep_p = ev >= 0, pr >= 0
+            props = pr[keep_p] if prop_ids is None else np.asarray(prop_ids)[pr[keep_p]]
+            rows.append((np.asarray(user_ids)[u], item_ids[i - n_users], t + 1, join(item_ids[ev[keep_e] - n_users]),
+                         join(np.asarray(explained['evidence_sim'][j, t])[keep_e]), join(props),
+                         join(np.asarray(explained['property_score'][j, t])[keep_p]),
+                         join(np.asarray(explained['property_support'][j, t])[keep_p])))
+    return pd.DataFrame(rows, columns=['users', 'items', 'rank', 'evidence', 'evidence_sim', 'properties', 'property_score',
+                                       'property_support'])
+
+
 def full_ranking_metrics(users, items, test_ratings, ks):
     """Full-ranking evaluation of `recommend()`'s lists (users [m], node ids [m, K] best first, -1 padded) against the test
     ratings ([P, 3]: user index, item node id, label): for every k in `ks` (<= K) the means over the users of `users` that have at

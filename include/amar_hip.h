@@ -1345,6 +1345,55 @@ int amar_list_diversity_f64(const int32_t *lists, int64_t m, int32_t K, const fl
                             int32_t metric, const int32_t *ks, int32_t nk, double *out_ild, int32_t *out_count,
                             amar_stream_t stream);
 
+/* Explanations of recommended pairs: for every target of device lists, the liked items of the list's user that are most similar to
+ * it, and the properties it shares with other liked items ("why this item for this user?").
+ *
+ * lists [m, K] (int32 rows of T, -1 padded: what amar_recommend_f32 writes); row j belongs to user users[j] (j itself when
+ * users == NULL, m == n_users).  The liked items are a CSR over users: liked_ptr[n_users+1], liked_items sorted ascending and
+ * de-duplicated per user.  T [n_items, d] (leading dimension ldt) is the item table; sim(a, b) is amar_nearest_f32's score of row
+ * a against row b:
+ *     AMAR_NEAREST_DOT:     sim(a, b) = sum_c T[a, c] * T[b, c]
+ *     AMAR_NEAREST_COSINE:  sim(a, b) = (dot * inv_norm(T[a])) * inv_norm(T[b]),  inv_norm(x) = 1/sqrt(sum x^2), 0 when the sum is 0
+ * (a zero row is similar to nothing, never NaN), products and sums in float32 (v_mfma_f32_16x16x4_f32, one fmaf chain per pair,
+ * features in the fragment order 16t + 4g + r of amar_nearest_f32; the squared norms are fmaf chains over the columns, ascending).
+ * The item-property links are an optional CSR over items: prop_ptr[n_items+1], prop_ids sorted ascending and de-duplicated per
+ * item, values in 0..n_props-1, with the weights prop_weight[n_props]; all three NULL = no property part (the property outputs
+ * are then padding).  For target i = lists[j, t] of user u:
+ *   - out_evidence / out_evidence_sim [m, K, n_evidence]: the n_evidence items of liked(u) other than i with the largest
+ *     sim(i, .), similarity descending, item row ascending on ties; padded with -1 / -inf.
+ *   - for every property p of i:  support(p) = |{j in liked(u), j != i, p in props(j)}|  and
+ *         score(p) = prop_weight[p] * sum over those j, item row ascending, of max(sim(i, j), 0).
+ *     out_props / out_prop_score / out_prop_support [m, K, n_properties]: the n_properties properties of support > 0 with the
+ *     largest scores, score descending, property index ascending on ties; padded with -1 / -inf / 0.  They may be NULL when
+ *     n_properties == 0.
+ * A padded list entry (or a row outside 0..n_items-1) writes padding only; a user id outside 0..n_users-1 writes padding for the
+ * whole list.  A list's result depends on its own row of lists, its user's segment, the touched rows of T, the property rows and
+ * weights, the metric, n_evidence and n_properties only: not on m, the other lists or the grid; a call returns the same bits on
+ * every run (no atomics, in LDS either: every sum runs in liked-row order).  One launch, one wavefront per list, no workspace:
+ * nothing of size m x L, m x K x L or m x L x d (L a liked-list length) reaches memory.  The user's liked rows are gathered once
+ * per list while the property rows of the list's targets together hold at most AMAR_EXPLAIN_MAX_PROP_ROW entries, and once per
+ * group of targets that does beyond.
+ * max_prop_row: the longest row of the property CSR (a precondition; ignored without one).  PRECONDITIONS, not checked on the
+ * device: max_prop_row is not understated (a target's row longer than AMAR_EXPLAIN_MAX_PROP_ROW that slips through that way is read
+ * up to the cap only, so that LDS is never overrun: the result is then undefined, not an error); T and prop_weight are finite (a
+ * similarity that is NaN counts as -inf in the evidence order, and a property whose score is NaN or -inf is not reported even with
+ * support > 0).
+ * Limits: K <= AMAR_EXPLAIN_MAX_K, 1 <= n_evidence <= AMAR_EXPLAIN_MAX_E, 0 <= n_properties <= AMAR_EXPLAIN_MAX_E, d % 4 == 0,
+ * 4 <= d <= 512, ldt a multiple of 4, T 16-byte aligned, max_prop_row <= AMAR_EXPLAIN_MAX_PROP_ROW; else AMAR_EUNSUPPORTED (a longer
+ * row is never truncated).  Liked lists and the property rows of liked items may have any length.  NULL T / liked_ptr, NULL lists
+ * / liked_items / outputs with m > 0, negative sizes, K < 1, n_evidence < 1, n_properties < 0, an unknown metric, ldt < d,
+ * users == NULL with m != n_users, some but not all of prop_ptr / prop_ids / prop_weight: AMAR_EINVAL.  All of these are checked
+ * before any device call. */
+#define AMAR_EXPLAIN_MAX_K        64
+#define AMAR_EXPLAIN_MAX_E        16
+#define AMAR_EXPLAIN_MAX_PROP_ROW 2048
+int amar_explain_f32(const int32_t *lists, int64_t m, int32_t K, const int32_t *users, const int32_t *liked_ptr,
+                     const int32_t *liked_items, int32_t n_users, const float *T, int64_t ldt, int32_t n_items, int32_t d,
+                     int32_t metric, const int32_t *prop_ptr, const int32_t *prop_ids, const float *prop_weight, int32_t n_props,
+                     int32_t max_prop_row, int32_t n_evidence, int32_t n_properties, int32_t *out_evidence,
+                     float *out_evidence_sim, int32_t *out_props, float *out_prop_score, int32_t *out_prop_support,
+                     amar_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
