@@ -1415,6 +1415,18 @@ def topk_segmented(seg_ptr, item_ids, scores, k):
     return out_items, out_scores
 
 
+def _sliced_topk(slices_fn, slices_args, m, k, dev):
+    """What the two fused rankers allocate alike: the slices the library will launch (its `slices_fn`; a negative answer raises), the
+    [m, k] outputs and the int32 workspace of the per-slice lists (None with one slice)."""
+    slices = getattr(load(), slices_fn)(*slices_args)
+    if slices < 0:
+        _check(int(slices), slices_fn)
+    out_rows = torch.empty((m, k), dtype=torch.int32, device=dev)
+    out_scores = torch.empty((m, k), dtype=torch.float32, device=dev)
+    ws_rows = torch.empty((m * slices * k,), dtype=torch.int32, device=dev) if slices > 1 else None
+    return slices, out_rows, out_scores, ws_rows
+
+
 def recommend(Tu, Ti, wpack, dims, acts, in_act, k, users=None, excl_ptr=None, excl_items=None, n_slices=0):
     """Fused full-catalogue top-k of the split head (amar_recommend_f32): for every user row of `users` (all rows of Tu when None)
     the k best items of Ti that are not in its exclusion CSR.  Returns (items int32 [m, k] (-1 padded), scores float32 [m, k]).
@@ -1428,16 +1440,8 @@ def recommend(Tu, Ti, wpack, dims, acts, in_act, k, users=None, excl_ptr=None, e
         n_slices = int(os.environ.get('AMAR_RECOMMEND_SLICES', '0'))
     dims_c = (ctypes.c_int32 * len(dims))(*dims)
     acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
-    slices = load().amar_recommend_slices(m, n_items, dims_c, len(acts), int(n_slices))
-    if slices < 0:
-        _check(int(slices), 'amar_recommend_slices')
-    dev = Tu.device
-    out_items = torch.empty((m, k), dtype=torch.int32, device=dev)
-    out_scores = torch.empty((m, k), dtype=torch.float32, device=dev)
-    ws_i = ws_s = None
-    if slices > 1:
-        ws_i = torch.empty((m * slices * k,), dtype=torch.int32, device=dev)
-        ws_s = torch.empty((m * slices * k,), dtype=torch.float32, device=dev)
+    slices, out_items, out_scores, ws_i = _sliced_topk('amar_recommend_slices', (m, n_items, dims_c, len(acts), int(n_slices)), m, k, Tu.device)
+    ws_s = torch.empty((m * slices * k,), dtype=torch.float32, device=Tu.device) if slices > 1 else None
     if (excl_ptr is None) != (excl_items is None):
         raise ValueError("recommend: excl_ptr and excl_items go together")
     if excl_ptr is not None and excl_ptr.numel() != n_users + 1:
@@ -1475,17 +1479,11 @@ def nearest(Q, T, k, metric='cosine', query_rows=None, excl_ptr=None, excl_rows=
         raise ValueError("nearest: excl_ptr must have one entry per listed query plus one")
     lib = load()
     metric_code = NEAREST_METRICS[metric]
-    slices = lib.amar_nearest_slices(m, n_rows, d, int(n_slices))
-    if slices < 0:
-        _check(int(slices), 'amar_nearest_slices')
-    dev = Q.device
-    out_rows = torch.empty((m, k), dtype=torch.int32, device=dev)
-    out_scores = torch.empty((m, k), dtype=torch.float32, device=dev)
+    slices, out_rows, out_scores, ws_r = _sliced_topk('amar_nearest_slices', (m, n_rows, d, int(n_slices)), m, k, Q.device)
     floats = lib.amar_nearest_workspace_floats(m, n_rows, int(k), metric_code, int(slices))
     if floats < 0:
         _check(int(floats), 'amar_nearest_workspace_floats')
-    ws_s = torch.empty((floats,), dtype=torch.float32, device=dev) if floats else None
-    ws_r = torch.empty((m * slices * k,), dtype=torch.int32, device=dev) if slices > 1 else None
+    ws_s = torch.empty((floats,), dtype=torch.float32, device=Q.device) if floats else None
     _launch('amar_nearest_f32', *_mat(Q, 'Q'), n_q, *_mat(T, 'T'), n_rows, d, metric_code, _ptr(query_rows, I32, 'query_rows'), m,
             _ptr(excl_ptr, I32, 'excl_ptr'), _ptr_entries(excl_rows, I32, 'excl_rows'), int(k), int(slices), _ptr(ws_r), _ptr(ws_s),
             _ptr(out_rows) if m else None, _ptr(out_scores) if m else None)

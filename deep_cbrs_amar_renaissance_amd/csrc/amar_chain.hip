@@ -50,19 +50,13 @@ struct ChainArgs {
 
 __device__ __forceinline__ int64_t chain_out_row(const ChainArgs &a, int64_t p) { return a.out_index ? (int64_t)a.out_index[p] : p; }
 
-__device__ __forceinline__ float chain_act(float v, int act) {
-    if (act == AMAR_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == AMAR_ACT_SIGMOID) return 1.f / (1.f + expf(-v));
-    return v;
-}
-
 // RELU (template flag of the kernels below): the summed-input activation and every MFMA layer's activation are ReLU — true
 // for every head of the reference's configs (dense.py:4-17 applies one `activation` throughout, 'relu' in config.yaml:27).
 // With the activation a run-time value every one of the 48 activated registers per 32 pairs went through a chain of
 // scalar branches (3 000 instructions in the loop, the VALU as busy as the matrix pipe); known at compile time the loop
 // body is straight-line code.
 template <bool RELU>
-__device__ __forceinline__ float chain_act_t(float v, int act) { return RELU ? fmaxf(v, 0.f) : chain_act(v, act); }
+__device__ __forceinline__ float chain_act_t(float v, int act) { return RELU ? fmaxf(v, 0.f) : amar_act(v, act); }
 // AM (activation mode of chain_kernel): 0 = run-time values, 1 = ReLU everywhere, 2 = ReLU everywhere but the LAST MFMA layer, which is
 // linear — the per-entity towers that end in the folded half of the classifier's first layer (models/basic.py:_split_plan).
 
@@ -176,7 +170,7 @@ __global__ __launch_bounds__(256) void chain_kernel(const ChainArgs a) {
                 s += __shfl_xor(s, 16, 64);
                 s += __shfl_xor(s, 32, 64);
                 const int64_t p = base + 16 * pt + col;
-                if (g == 0 && p < a.P) a.out[chain_out_row(a, p) * a.ldo] = chain_act(s + bd, a.dot_act);
+                if (g == 0 && p < a.P) a.out[chain_out_row(a, p) * a.ldo] = amar_act(s + bd, a.dot_act);
             }
         } else {
 #pragma unroll
@@ -598,7 +592,7 @@ __global__ __launch_bounds__(256) void chain_pipe_kernel(const ChainArgs a) {
 #pragma unroll
             for (int pt = 1; pt < PT; ++pt) z = g == pt ? s[pt] : z;
             z += bd;
-            z = chain_act(z, a.dot_act);                            // same expression as the generic kernel: bit-identical scores
+            z = amar_act(z, a.dot_act);                            // same expression as the generic kernel: bit-identical scores
             const uint32_t p = base + 16 * g + col;
             if (g < PT && p < P) a.out[(SCATTER ? (int64_t)out_row : (int64_t)p) * a.ldo] = z;
         } else {
@@ -678,7 +672,7 @@ __global__ __launch_bounds__(1024) void dual_chain_kernel(const DualArgs a) {
                         const f32x4 vb = *reinterpret_cast<const f32x4 *>(a.B[br] + rb * a.ldb[br] + f);
                         v = va + vb;
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = chain_act(v[r], a.in_act);
+                        for (int r = 0; r < 4; ++r) v[r] = amar_act(v[r], a.in_act);
                     }
                     xb[br][t][pt] = v;
                 }
@@ -712,7 +706,7 @@ __global__ __launch_bounds__(1024) void dual_chain_kernel(const DualArgs a) {
                         if (m < TB) {
                             v = y[m][pt];
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) v[r] = chain_act(v[r], a.b_act[l]);
+                            for (int r = 0; r < 4; ++r) v[r] = amar_act(v[r], a.b_act[l]);
                         }
                         xb[br][m][pt] = v;
                     }
@@ -758,7 +752,7 @@ __global__ __launch_bounds__(1024) void dual_chain_kernel(const DualArgs a) {
                     if (m < TT) {
                         v = y[m][pt];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = chain_act(v[r], a.t_act[l]);
+                        for (int r = 0; r < 4; ++r) v[r] = amar_act(v[r], a.t_act[l]);
                     }
                     x[m][pt] = v;
                 }
@@ -778,7 +772,7 @@ __global__ __launch_bounds__(1024) void dual_chain_kernel(const DualArgs a) {
             sacc += __shfl_xor(sacc, 16, 64);
             sacc += __shfl_xor(sacc, 32, 64);
             const int64_t p = base + 16 * pt + col;
-            if (g == 0 && p < a.P) a.out[(a.out_index ? (int64_t)a.out_index[p] : p) * a.ldo] = chain_act(sacc + bd, a.dot_act);
+            if (g == 0 && p < a.P) a.out[(a.out_index ? (int64_t)a.out_index[p] : p) * a.ldo] = amar_act(sacc + bd, a.dot_act);
         }
     }
 }
@@ -890,7 +884,7 @@ __global__ __launch_bounds__(1024) void dual_chain_full_kernel(const DualArgs a)
         }
         sacc += __shfl_xor(sacc, 16, 64);
         sacc += __shfl_xor(sacc, 32, 64);
-        if (g == 0 && ok) a.out[(a.out_index ? (int64_t)a.out_index[p] : p) * a.ldo] = chain_act(sacc + w_lds[a.dot_bias_off], a.dot_act);
+        if (g == 0 && ok) a.out[(a.out_index ? (int64_t)a.out_index[p] : p) * a.ldo] = amar_act(sacc + w_lds[a.dot_bias_off], a.dot_act);
     }
 }
 
@@ -1038,7 +1032,7 @@ __global__ __launch_bounds__(THREADS) void dual_chain_split_kernel(const DualArg
             sacc += __shfl_xor(sacc, 16, 64);
             sacc += __shfl_xor(sacc, 32, 64);
             const int64_t p = base + 16 * pt + col;
-            if (g == 0 && p < a.P) a.out[(a.out_index ? (int64_t)a.out_index[p] : p) * a.ldo] = chain_act(sacc + tail[a.dot_bias_tail], a.dot_act);
+            if (g == 0 && p < a.P) a.out[(a.out_index ? (int64_t)a.out_index[p] : p) * a.ldo] = amar_act(sacc + tail[a.dot_bias_tail], a.dot_act);
         }
     }
 }

@@ -32,6 +32,13 @@ static inline int amar_allow_lds(const void *kern, size_t bytes, bool (&done)[AM
     return AMAR_OK;
 }
 
+// The activation of the fused scoring kernels (amar_chain.hip, amar_rank.hip): one definition, so their scores agree bit for bit.
+__device__ __forceinline__ float amar_act(float v, int act) {
+    if (act == AMAR_ACT_RELU) return fmaxf(v, 0.f);
+    if (act == AMAR_ACT_SIGMOID) return 1.f / (1.f + expf(-v));
+    return v;
+}
+
 __device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ float4 f4_fma(float a, float4 x, float4 acc) {
     acc.x = fmaf(a, x.x, acc.x); acc.y = fmaf(a, x.y, acc.y);

@@ -444,50 +444,6 @@ __global__ __launch_bounds__(256) void dense_split128_kernel(const DenseSplitArg
     }
 }
 
-// ---- per-user top-k --------------------------------------------------------------------------
-// One wave per user.  Round t picks the best pair that comes strictly after round t-1's winner in
-// the order (score descending, item id ascending); items are distinct within a user.
-__global__ __launch_bounds__(256) void topk_segmented_kernel(const int32_t *__restrict__ seg_ptr,
-                                                              const int32_t *__restrict__ item_ids,
-                                                              const float *__restrict__ scores, int n_users, int k,
-                                                              int32_t *__restrict__ out_items,
-                                                              float *__restrict__ out_scores) {
-    const int lane = threadIdx.x & 63;
-    const int u = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (u >= n_users) return;
-    const int beg = seg_ptr[u], end = seg_ptr[u + 1];
-    float prev_s = INFINITY;
-    int prev_i = -1;
-    for (int t = 0; t < k; ++t) {
-        float best_s = -INFINITY;
-        int best_i = 0x7fffffff;
-        for (int p = beg + lane; p < end; p += 64) {
-            const float s = scores[p];
-            const int it = item_ids[p];
-            const bool after_prev = (s < prev_s) || (s == prev_s && it > prev_i);
-            const bool better = (s > best_s) || (s == best_s && it < best_i);
-            if (after_prev && better) { best_s = s; best_i = it; }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const float os = __shfl_xor(best_s, off, 64);
-            const int oi = __shfl_xor(best_i, off, 64);
-            if (os > best_s || (os == best_s && oi < best_i)) { best_s = os; best_i = oi; }
-        }
-        const bool found = best_i != 0x7fffffff;
-        if (lane == 0) {
-            out_items[(int64_t)u * k + t] = found ? best_i : -1;
-            out_scores[(int64_t)u * k + t] = found ? best_s : -INFINITY;
-        }
-        if (!found) {
-            if (lane == 0)
-                for (int r = t + 1; r < k; ++r) { out_items[(int64_t)u * k + r] = -1; out_scores[(int64_t)u * k + r] = -INFINITY; }
-            break;
-        }
-        prev_s = best_s; prev_i = best_i;
-    }
-}
-
 }  // namespace
 
 // Which kernel a Dense call takes, and on what grid: decided HERE and nowhere else — amar_dense_f32 launches what this returns and
@@ -618,18 +574,6 @@ int amar_dense_split_f32(const float *X, int64_t ldx, const int32_t *ids, const 
     if (total > 0x7fffffffLL) return AMAR_EUNSUPPORTED;
     DenseSplitArgs a{X, ldx, ids, static_cast<const u32x4 *>(Wq), bias, Y, ldy, M, K, N, act, N / BN2};
     hipLaunchKernelGGL(dense_split128_kernel, dim3((unsigned)total), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    return amar_check_launch();
-}
-
-int amar_topk_segmented_f32(const int32_t *seg_ptr, const int32_t *item_ids, const float *scores,
-                            int32_t n_users, int32_t k, int32_t *out_items, float *out_scores,
-                            amar_stream_t stream) {
-    if (n_users < 0 || k < 1 || !seg_ptr) return AMAR_EINVAL;
-    if (k > 64) return AMAR_EUNSUPPORTED;
-    if (n_users == 0) return AMAR_OK;                                    // nothing to rank: the outputs may be empty (NULL)
-    if (!item_ids || !scores || !out_items || !out_scores) return AMAR_EINVAL;
-    hipLaunchKernelGGL(topk_segmented_kernel, dim3((n_users + 3) / 4), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), seg_ptr, item_ids, scores, n_users, k, out_items, out_scores);
     return amar_check_launch();
 }
 

@@ -13,11 +13,10 @@
 //         (A = the 16 queries, B = 16 table rows, both read from LDS as float4 at features 16t + 4g + r, the fragment order of
 //         recommend_kernel / chain_kernel: t ascending, r ascending inside t, one fmaf chain per score).  The scaled scores go to
 //         a [16][TR] LDS window: the matrix layout holds 4 queries x 16 rows per register, the selection wants 64 rows of one query.
-//       - selection (amar_rank_select.h, the scheme of recommend_kernel): each wave owns 4 queries; per query a threshold = the
-//         current k-th best (score, row), a forward-walking exclusion pointer with a binary search in the remaining window, a
-//         64-entry candidate buffer merged into the sorted list by rank counting.
-//   * with several table slices each workgroup leaves its slice's list in a workspace and recommend_merge_kernel merges them in
-//     slice order; the order is a strict total order, so the result does not depend on the slicing.
+//       - selection: the RankSlot of amar_rank_select.h, one per query (the selector recommend_kernel uses); each wave owns 4
+//         queries and hands its slots the window's scores 64 rows at a time.
+//   * with several table slices each workgroup leaves its slice's list in a workspace and rank_merge_slices (amar_rank.hip)
+//     merges them in slice order; the order is a strict total order, so the result does not depend on the slicing.
 // A score depends on its query row, its table row, d and the metric only: not on the block, the tile, the slice or the call.
 #include "amar_common.h"
 #include "amar_rank_select.h"
@@ -35,8 +34,8 @@ struct NearArgs {
     const int32_t *query_rows; int64_t m;
     const int32_t *excl_ptr, *excl_rows;
     const float *t_inv, *q_inv;                // cosine: inverse norms per table row / per listed query
-    int k, kt, tile_rows, stride, sstride, slice_rows, n_slices;
-    int32_t *out_rows; float *out_scores;      // n_slices == 1: the result [m, k]; else the per-slice lists [m][n_slices][k]
+    int kt, tile_rows, stride, sstride, slice_rows;
+    RankOut out;
 };
 
 // inv_norm of n rows of X (rows[j] or j itself), 16 lanes per row: lane s squares the float4s s, s + 16, ... in that order,
@@ -67,14 +66,7 @@ __global__ __launch_bounds__(256) void nearest_kernel(const NearArgs a) {
     float *sc = tile + a.tile_rows * a.stride;                       // [16][sstride]: the tile's scores
     float *t_inv = sc + NEAR_QB * a.sstride;                         // [tile_rows]
     float *q_inv = t_inv + a.tile_rows;                              // [16]
-    float *list_s = q_inv + NEAR_QB;
-    int *list_i = reinterpret_cast<int *>(list_s + NEAR_QB * RANK_LIST);
-    float *cand_s = reinterpret_cast<float *>(list_i + NEAR_QB * RANK_LIST);
-    int *cand_i = reinterpret_cast<int *>(cand_s + NEAR_QB * RANK_CAND);
-    int *st_cnt = cand_i + NEAR_QB * RANK_CAND;          // per query: candidates buffered, exclusion pointer, threshold
-    int *st_ep = st_cnt + NEAR_QB;
-    float *st_ts = reinterpret_cast<float *>(st_ep + NEAR_QB);
-    int *st_ti = reinterpret_cast<int *>(st_ts + NEAR_QB);
+    float *select = q_inv + NEAR_QB;                                 // NEAR_QB selector slots (amar_rank_select.h)
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
     const int64_t j0 = (int64_t)blockIdx.x * NEAR_QB;
@@ -95,14 +87,10 @@ __global__ __launch_bounds__(256) void nearest_kernel(const NearArgs a) {
     }
     for (int qw = 0; qw < NEAR_QPW; ++qw) {
         const int slot = wave * NEAR_QPW + qw;
-        list_s[slot * RANK_LIST + lane] = -INFINITY;
-        list_i[slot * RANK_LIST + lane] = RANK_EMPTY;
-        if (lane == 0) {
-            const int64_t j = j0 + slot;
-            int ep = 0;
-            if (j < a.m && a.excl_ptr) ep = rank_lower_bound(a.excl_rows, a.excl_ptr[j], a.excl_ptr[j + 1], s0);
-            st_cnt[slot] = 0; st_ep[slot] = ep; st_ts[slot] = -INFINITY; st_ti[slot] = RANK_EMPTY;
-        }
+        const int64_t j = j0 + slot;
+        int eb = 0, ee = 0;                                      // the query's excluded rows
+        if (lane == 0 && j < a.m && a.excl_ptr) { eb = a.excl_ptr[j]; ee = a.excl_ptr[j + 1]; }
+        RankSlot<NEAR_QB>(select, slot).init(lane, a.excl_rows, eb, ee, s0);
     }
 
     for (int t0 = s0; t0 < s1; t0 += a.tile_rows) {
@@ -157,71 +145,26 @@ __global__ __launch_bounds__(256) void nearest_kernel(const NearArgs a) {
             const int slot = wave * NEAR_QPW + qw;
             const int64_t j = j0 + slot;
             if (j >= a.m) break;
-            int cnt = st_cnt[slot], ep = st_ep[slot];
-            float ts = st_ts[slot];
-            int ti = st_ti[slot];
+            RankSlot<NEAR_QB> top(select, slot);
+            top.load();
             const int ee = a.excl_ptr ? a.excl_ptr[j + 1] : 0;
-            float *ls = list_s + slot * RANK_LIST, *cs = cand_s + slot * RANK_CAND;
-            int *li = list_i + slot * RANK_LIST, *ci = cand_i + slot * RANK_CAND;
             const float *srow = sc + slot * a.sstride;
 
             for (int grp = 0; grp < rows; grp += 64) {
                 const bool in = grp + lane < rows;
                 const float z = in ? srow[grp + lane] : -INFINITY;
-                const int item = t0 + grp + lane;
-                bool pred = in && rank_better(z, item, ts, ti);
-                if (__ballot(pred) == 0) continue;
-                if (pred && ep < ee) {                               // excluded for this query?
-                    const int pos = rank_lower_bound(a.excl_rows, ep, ee, item);
-                    pred = !(pos < ee && a.excl_rows[pos] == item);
-                }
-                const uint64_t mask = __ballot(pred);
-                if (mask == 0) continue;
-                const int n = __popcll(mask);
-                if (cnt + n > RANK_CAND) {
-                    rank_merge(ls, li, cs, ci, cnt, a.k, lane);
-                    cnt = 0;
-                    ts = ls[a.k - 1]; ti = li[a.k - 1];
-                    pred = pred && rank_better(z, item, ts, ti);
-                }
-                const uint64_t mask2 = __ballot(pred);
-                if (pred) {
-                    const int pos = cnt + __popcll(mask2 & ((1ull << lane) - 1ull));
-                    cs[pos] = z; ci[pos] = item;
-                }
-                cnt += __popcll(mask2);
+                top.offer(z, t0 + grp + lane, in, a.excl_rows, ee, a.out.k, lane);
             }
-            // the exclusion pointer moves past this tile
-            if (a.excl_ptr && ep < ee) ep = rank_lower_bound(a.excl_rows, ep, ee, t0 + rows);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (lane == 0) { st_cnt[slot] = cnt; st_ep[slot] = ep; st_ts[slot] = ts; st_ti[slot] = ti; }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            top.advance(a.excl_rows, ee, t0 + rows);
+            top.store(lane);
         }
     }
     __syncthreads();                                             // n_rows == 0: the lists and states above are written
-    // slice done: last merge, then the list goes out (final result or this slice's partial list)
     for (int qw = 0; qw < NEAR_QPW; ++qw) {
         const int slot = wave * NEAR_QPW + qw;
         const int64_t j = j0 + slot;
         if (j >= a.m) break;
-        float *ls = list_s + slot * RANK_LIST;
-        int *li = list_i + slot * RANK_LIST;
-        const int cnt = st_cnt[slot];
-        if (cnt > 0) rank_merge(ls, li, cand_s + slot * RANK_CAND, cand_i + slot * RANK_CAND, cnt, a.k, lane);
-        if (lane < a.k) {
-            const float s = ls[lane];
-            const int i = li[lane];
-            if (a.n_slices == 1) {
-                a.out_rows[j * a.k + lane] = i == RANK_EMPTY ? -1 : i;
-                a.out_scores[j * a.k + lane] = i == RANK_EMPTY ? -INFINITY : s;
-            } else {
-                const int64_t o = (j * a.n_slices + slice) * a.k + lane;
-                a.out_rows[o] = i;
-                a.out_scores[o] = s;
-            }
-        }
+        RankSlot<NEAR_QB>(select, slot).finish(j, slice, a.out, lane);
     }
 }
 
@@ -252,23 +195,7 @@ int32_t amar_nearest_slices(int64_t m, int32_t n_rows, int32_t d, int32_t n_slic
     NearShape s;
     const int rc = near_shape(d, s);
     if (rc != AMAR_OK) return rc;
-    const int64_t tiles = ((int64_t)n_rows + s.tile_rows - 1) / s.tile_rows;
-    const int64_t blocks = (m + NEAR_QB - 1) / NEAR_QB;
-    int64_t want = n_slices;
-    if (want <= 0) {
-        // automatic: about four resident workgroups per CU of the 256 (a slice covers at least four tiles)
-        want = blocks > 0 ? (1024 + blocks - 1) / blocks : 1;
-        const int64_t cap = tiles / 4 > 0 ? tiles / 4 : 1;
-        want = want > cap ? cap : want;
-        want = want > 16 ? 16 : want;
-    }
-    if (want < 1) want = 1;
-    if (want > tiles) want = tiles > 0 ? tiles : 1;
-    if (want > 64) want = 64;
-    // slices cover whole tiles: the count actually launched
-    const int64_t per = ((tiles + want - 1) / want) * s.tile_rows;
-    const int64_t eff = per > 0 ? (n_rows + per - 1) / per : 1;
-    return (int32_t)(eff > 0 ? eff : 1);
+    return rank_slices(m, n_rows, s.tile_rows, NEAR_QB, n_slices);
 }
 
 int64_t amar_nearest_workspace_floats(int64_t m, int32_t n_rows, int32_t k, int32_t metric, int32_t slices) {
@@ -318,19 +245,17 @@ int amar_nearest_f32(const float *Q, int64_t ldq, int32_t n_queries, const float
         if (e != AMAR_OK) return e;
     }
 
-    const int64_t tiles = ((int64_t)n_rows + sh.tile_rows - 1) / sh.tile_rows;
-    const int64_t per_tiles = (tiles + slices - 1) / slices;
     NearArgs a{};
     a.Q = Q; a.ldq = ldq; a.T = T; a.ldt = ldt; a.d = d; a.n_rows = n_rows; a.cosine = cosine ? 1 : 0;
     a.query_rows = query_rows; a.m = m; a.excl_ptr = excl_ptr; a.excl_rows = excl_rows;
     a.t_inv = t_inv; a.q_inv = q_inv;
-    a.k = k; a.kt = sh.kt; a.tile_rows = sh.tile_rows; a.stride = sh.stride; a.sstride = sh.sstride;
-    a.slice_rows = (int)(per_tiles * sh.tile_rows > 0 ? per_tiles * sh.tile_rows : sh.tile_rows);
-    a.n_slices = slices;
-    a.out_rows = slices > 1 ? workspace_rows : out_rows;
-    a.out_scores = slices > 1 ? part_scores : out_scores;
+    a.out.k = k; a.kt = sh.kt; a.tile_rows = sh.tile_rows; a.stride = sh.stride; a.sstride = sh.sstride;
+    a.slice_rows = (int)rank_slice_rows(n_rows, sh.tile_rows, slices);
+    a.out.n_slices = slices;
+    a.out.rows = slices > 1 ? workspace_rows : out_rows;
+    a.out.scores = slices > 1 ? part_scores : out_scores;
     const size_t lds_bytes = ((size_t)(NEAR_QB + sh.tile_rows) * sh.stride + (size_t)NEAR_QB * sh.sstride + sh.tile_rows + NEAR_QB +
-                              (size_t)NEAR_QB * (2 * RANK_LIST + 2 * RANK_CAND + 4)) * 4;
+                              (size_t)rank_select_state_floats(NEAR_QB)) * 4;
     if (lds_bytes > 160 * 1024) return AMAR_EUNSUPPORTED;
     if (lds_bytes > 64 * 1024) {
         static bool done[AMAR_MAX_DEVICES];
@@ -340,9 +265,7 @@ int amar_nearest_f32(const float *Q, int64_t ldq, int32_t n_queries, const float
     hipLaunchKernelGGL(nearest_kernel, dim3((unsigned)blocks, (unsigned)slices), dim3(256), lds_bytes, st, a);
     const int e = amar_check_launch();
     if (e != AMAR_OK || slices == 1) return e;
-    hipLaunchKernelGGL(recommend_merge_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, workspace_rows, part_scores, m, slices,
-                       k, out_rows, out_scores);
-    return amar_check_launch();
+    return rank_merge_slices(workspace_rows, part_scores, m, slices, k, out_rows, out_scores, st);
 }
 
 }  // extern "C"

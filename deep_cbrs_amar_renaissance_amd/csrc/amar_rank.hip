@@ -11,13 +11,13 @@
 //   * the rest stack runs on v_mfma_f32_16x16x4_f32 with chain_kernel's loop order, fragment blob and dot stage, so a score is
 //     bit-identical to what amar_chain_f32's generic kernel returns for the same pair (the pair stage of predict() for heads
 //     whose widths it takes).
-//   * selection: per user a threshold = the current k-th best (score, item); a pair beating it is checked against the user's
-//     sorted exclusion list (a pointer walked forward tile by tile, binary search inside the remaining window) and appended to a
-//     64-entry LDS candidate buffer; a full buffer (and the end of the slice) is merged into the sorted top-k list by rank
-//     counting.  Expected inserts ~ k ln(|I| / k): per pair the selection is one compare.
-//   * with several item slices each workgroup leaves its slice's top-k in a workspace and a second launch merges the slices
-//     of a user in slice order (the order is a strict total order, so the result does not depend on the slicing).
+//   * selection: the RankSlot of amar_rank_select.h, one per user (threshold, exclusion walk over the user's training items,
+//     candidate buffer, rank-counting merge); the kernel hands it 16 PT scores at a time, lane group g holding pair tile g.
+//   * with several item slices each workgroup leaves its slice's top-k in a workspace and a second launch (recommend_merge_kernel
+//     below, also amar_nearest.hip's second launch) merges the slices of a user in slice order (the order is a strict total
+//     order, so the result does not depend on the slicing).
 // The result of a user depends on its own Tu row, Ti and the weights only: not on the other users of the block or the call.
+// The pair route's ranker (amar_topk_segmented_f32: scores already in memory, one wave per user) is at the end of the file.
 #include "amar_common.h"
 #include "amar_rank_select.h"
 #include <stdlib.h>
@@ -38,29 +38,16 @@ struct RankArgs {
     int in_act, n_layers;
     int kt[RANK_MAX_LAYERS], nt[RANK_MAX_LAYERS], act[RANK_MAX_LAYERS], w_off[RANK_MAX_LAYERS], b_off[RANK_MAX_LAYERS];
     int dot_off, dot_bias_off, dot_kt, dot_act;
-    int k, tile_items, tile_stride, slice_items, n_slices;
-    int32_t *out_items; float *out_scores;     // n_slices == 1: the result [m, k]; else the per-slice lists [m][n_slices][k]
+    int tile_items, tile_stride, slice_items;
+    RankOut out;
 };
-
-__device__ __forceinline__ float rank_act(float v, int act) {       // chain_act of amar_chain.hip: the same expressions
-    if (act == AMAR_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == AMAR_ACT_SIGMOID) return 1.f / (1.f + expf(-v));
-    return v;
-}
 
 template <int MAXT, int PT>
 __global__ __launch_bounds__(256) void recommend_kernel(const RankArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *w_lds = lds;
     float *tile = lds + ((a.wpack_floats + 3) & ~3);
-    float *list_s = tile + a.tile_items * a.tile_stride;
-    int *list_i = reinterpret_cast<int *>(list_s + RANK_UB * RANK_LIST);
-    float *cand_s = reinterpret_cast<float *>(list_i + RANK_UB * RANK_LIST);
-    int *cand_i = reinterpret_cast<int *>(cand_s + RANK_UB * RANK_CAND);
-    int *st_cnt = cand_i + RANK_UB * RANK_CAND;          // per user: candidates buffered, exclusion pointer, threshold
-    int *st_ep = st_cnt + RANK_UB;
-    float *st_ts = reinterpret_cast<float *>(st_ep + RANK_UB);
-    int *st_ti = reinterpret_cast<int *>(st_ts + RANK_UB);
+    float *select = tile + a.tile_items * a.tile_stride;         // RANK_UB selector slots (amar_rank_select.h)
 
     for (int i = threadIdx.x * 4; i < a.wpack_floats; i += blockDim.x * 4)
         *reinterpret_cast<float4 *>(&w_lds[i]) = *reinterpret_cast<const float4 *>(a.wpack + i);
@@ -70,17 +57,13 @@ __global__ __launch_bounds__(256) void recommend_kernel(const RankArgs a) {
     const int s0 = slice * a.slice_items, s1 = min(a.n_items, s0 + a.slice_items);
     for (int uw = 0; uw < RANK_UPW; ++uw) {
         const int slot = wave * RANK_UPW + uw;
-        list_s[slot * RANK_LIST + lane] = -INFINITY;
-        list_i[slot * RANK_LIST + lane] = RANK_EMPTY;
-        if (lane == 0) {
-            const int64_t j = j0 + slot;
-            int ep = 0;
-            if (j < a.m && a.excl_ptr) {
-                const int u = a.users ? a.users[j] : (int)j;
-                ep = rank_lower_bound(a.excl_items, a.excl_ptr[u], a.excl_ptr[u + 1], s0);
-            }
-            st_cnt[slot] = 0; st_ep[slot] = ep; st_ts[slot] = -INFINITY; st_ti[slot] = RANK_EMPTY;
+        const int64_t j = j0 + slot;
+        int eb = 0, ee = 0;                                      // the user's training items
+        if (lane == 0 && j < a.m && a.excl_ptr) {
+            const int u = a.users ? a.users[j] : (int)j;
+            eb = a.excl_ptr[u]; ee = a.excl_ptr[u + 1];
         }
+        RankSlot<RANK_UB>(select, slot).init(lane, a.excl_items, eb, ee, s0);
     }
     const int KT0 = a.kt[0];
     const int f4_per_row = 4 * KT0;                              // float4s of a staged row (16 KT0 features, zero past c1)
@@ -107,12 +90,9 @@ __global__ __launch_bounds__(256) void recommend_kernel(const RankArgs a) {
                 const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
                 tu[t] = (t < KT0 && f < a.c1) ? *reinterpret_cast<const f32x4 *>(a.Tu + (int64_t)u * a.ldu + f) : zero;
             }
-            int cnt = st_cnt[slot], ep = st_ep[slot];
-            float ts = st_ts[slot];
-            int ti = st_ti[slot];
+            RankSlot<RANK_UB> top(select, slot);
+            top.load();
             const int ee = a.excl_ptr ? a.excl_ptr[u + 1] : 0;
-            float *ls = list_s + slot * RANK_LIST, *cs = cand_s + slot * RANK_CAND;
-            int *li = list_i + slot * RANK_LIST, *ci = cand_i + slot * RANK_CAND;
 
             for (int grp = 0; grp < rows; grp += 16 * PT) {
                 f32x4 x[MAXT][PT];
@@ -126,7 +106,7 @@ __global__ __launch_bounds__(256) void recommend_kernel(const RankArgs a) {
                         if (t < KT0 && f < a.c1) {
                             v = tu[t] + *reinterpret_cast<const f32x4 *>(row + f);
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) v[r] = rank_act(v[r], a.in_act);
+                            for (int r = 0; r < 4; ++r) v[r] = amar_act(v[r], a.in_act);
                         }
                         x[t][pt] = v;
                     }
@@ -164,7 +144,7 @@ __global__ __launch_bounds__(256) void recommend_kernel(const RankArgs a) {
                             if (mm < NT) {
                                 v = y[mm][pt];
 #pragma unroll
-                                for (int r = 0; r < 4; ++r) v[r] = rank_act(v[r], act);
+                                for (int r = 0; r < 4; ++r) v[r] = amar_act(v[r], act);
                             }
                             x[mm][pt] = v;
                         }
@@ -187,60 +167,87 @@ __global__ __launch_bounds__(256) void recommend_kernel(const RankArgs a) {
                     s += __shfl_xor(s, 32, 64);
                     sel = g == pt ? s : sel;
                 }
-                const float z = rank_act(sel + w_lds[a.dot_bias_off], a.dot_act);
+                const float z = amar_act(sel + w_lds[a.dot_bias_off], a.dot_act);
                 const int item = t0 + grp + 16 * g + col;
-                bool pred = g < PT && grp + 16 * g + col < rows && rank_better(z, item, ts, ti);
-                if (__ballot(pred) == 0) continue;
-                if (pred && ep < ee) {                               // training item of this user?
-                    const int pos = rank_lower_bound(a.excl_items, ep, ee, item);
-                    pred = !(pos < ee && a.excl_items[pos] == item);
-                }
-                const uint64_t mask = __ballot(pred);
-                if (mask == 0) continue;
-                const int n = __popcll(mask);
-                if (cnt + n > RANK_CAND) {
-                    rank_merge(ls, li, cs, ci, cnt, a.k, lane);
-                    cnt = 0;
-                    ts = ls[a.k - 1]; ti = li[a.k - 1];
-                    pred = pred && rank_better(z, item, ts, ti);
-                }
-                const uint64_t mask2 = __ballot(pred);
-                if (pred) {
-                    const int pos = cnt + __popcll(mask2 & ((1ull << lane) - 1ull));
-                    cs[pos] = z; ci[pos] = item;
-                }
-                cnt += __popcll(mask2);
+                top.offer(z, item, g < PT && grp + 16 * g + col < rows, a.excl_items, ee, a.out.k, lane);
             }
-            // the exclusion pointer moves past this tile
-            if (a.excl_ptr && ep < ee) ep = rank_lower_bound(a.excl_items, ep, ee, t0 + rows);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (lane == 0) { st_cnt[slot] = cnt; st_ep[slot] = ep; st_ts[slot] = ts; st_ti[slot] = ti; }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            top.advance(a.excl_items, ee, t0 + rows);
+            top.store(lane);
         }
     }
-    // slice done: last merge, then the list goes out (final result or this slice's partial list)
     for (int uw = 0; uw < RANK_UPW; ++uw) {
         const int slot = wave * RANK_UPW + uw;
         const int64_t j = j0 + slot;
         if (j >= a.m) break;
-        float *ls = list_s + slot * RANK_LIST;
-        int *li = list_i + slot * RANK_LIST;
-        const int cnt = st_cnt[slot];
-        if (cnt > 0) rank_merge(ls, li, cand_s + slot * RANK_CAND, cand_i + slot * RANK_CAND, cnt, a.k, lane);
-        if (lane < a.k) {
-            const float s = ls[lane];
-            const int i = li[lane];
-            if (a.n_slices == 1) {
-                a.out_items[j * a.k + lane] = i == RANK_EMPTY ? -1 : i;
-                a.out_scores[j * a.k + lane] = i == RANK_EMPTY ? -INFINITY : s;
-            } else {
-                const int64_t o = (j * a.n_slices + slice) * a.k + lane;
-                a.out_items[o] = i;
-                a.out_scores[o] = s;
-            }
+        RankSlot<RANK_UB>(select, slot).finish(j, slice, a.out, lane);
+    }
+}
+
+// Second launch with item slices: one wave per user merges its n_slices partial lists, slice by slice, into the final top-k.
+__global__ __launch_bounds__(256) void recommend_merge_kernel(const int32_t *__restrict__ part_items, const float *__restrict__ part_scores,
+                                                              int64_t m, int n_slices, int k, int32_t *__restrict__ out_items,
+                                                              float *__restrict__ out_scores) {
+    __shared__ float ls_all[4][RANK_LIST], cs_all[4][RANK_CAND];
+    __shared__ int li_all[4][RANK_LIST], ci_all[4][RANK_CAND];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t j = (int64_t)blockIdx.x * 4 + wave;
+    if (j >= m) return;
+    float *ls = ls_all[wave], *cs = cs_all[wave];
+    int *li = li_all[wave], *ci = ci_all[wave];
+    ls[lane] = -INFINITY; li[lane] = RANK_EMPTY;
+    for (int s = 0; s < n_slices; ++s) {
+        const int64_t o = (j * n_slices + s) * k;
+        cs[lane] = lane < k ? part_scores[o + lane] : -INFINITY;
+        ci[lane] = lane < k ? part_items[o + lane] : RANK_EMPTY;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        rank_merge(ls, li, cs, ci, k, k, lane);
+    }
+    if (lane < k) {
+        const int i = li[lane];
+        out_items[j * k + lane] = i == RANK_EMPTY ? -1 : i;
+        out_scores[j * k + lane] = i == RANK_EMPTY ? -INFINITY : ls[lane];
+    }
+}
+
+// The pair route's ranker: one wave per user over scores already in memory.  Round t picks the best pair that comes strictly
+// after round t-1's winner in the order of rank_better; items are distinct within a user.
+__global__ __launch_bounds__(256) void topk_segmented_kernel(const int32_t *__restrict__ seg_ptr,
+                                                              const int32_t *__restrict__ item_ids,
+                                                              const float *__restrict__ scores, int n_users, int k,
+                                                              int32_t *__restrict__ out_items,
+                                                              float *__restrict__ out_scores) {
+    const int lane = threadIdx.x & 63;
+    const int u = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u >= n_users) return;
+    const int beg = seg_ptr[u], end = seg_ptr[u + 1];
+    float prev_s = INFINITY;
+    int prev_i = -1;
+    for (int t = 0; t < k; ++t) {
+        float best_s = -INFINITY;
+        int best_i = RANK_EMPTY;
+        for (int p = beg + lane; p < end; p += 64) {
+            const float s = scores[p];
+            const int it = item_ids[p];
+            if (rank_better(prev_s, prev_i, s, it) && rank_better(s, it, best_s, best_i)) { best_s = s; best_i = it; }
         }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const float os = __shfl_xor(best_s, off, 64);
+            const int oi = __shfl_xor(best_i, off, 64);
+            if (rank_better(os, oi, best_s, best_i)) { best_s = os; best_i = oi; }
+        }
+        const bool found = best_i != RANK_EMPTY;
+        if (lane == 0) {
+            out_items[(int64_t)u * k + t] = found ? best_i : -1;
+            out_scores[(int64_t)u * k + t] = found ? best_s : -INFINITY;
+        }
+        if (!found) {
+            if (lane == 0)
+                for (int r = t + 1; r < k; ++r) { out_items[(int64_t)u * k + r] = -1; out_scores[(int64_t)u * k + r] = -INFINITY; }
+            break;
+        }
+        prev_s = best_s; prev_i = best_i;
     }
 }
 
@@ -266,6 +273,13 @@ int rank_shape(const int32_t *dims, int32_t n_layers, RankShape &s) {
 
 }  // namespace
 
+int rank_merge_slices(const int32_t *part_rows, const float *part_scores, int64_t m, int slices, int k, int32_t *out_rows,
+                      float *out_scores, hipStream_t stream) {
+    hipLaunchKernelGGL(recommend_merge_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, part_rows, part_scores, m, slices, k,
+                       out_rows, out_scores);
+    return amar_check_launch();
+}
+
 extern "C" {
 
 int32_t amar_recommend_slices(int64_t m, int32_t n_items, const int32_t *dims, int32_t n_layers, int32_t n_slices) {
@@ -273,23 +287,7 @@ int32_t amar_recommend_slices(int64_t m, int32_t n_items, const int32_t *dims, i
     RankShape s;
     const int rc = rank_shape(dims, n_layers, s);
     if (rc != AMAR_OK) return rc;
-    const int64_t tiles = (n_items + s.tile_items - 1) / s.tile_items;
-    const int64_t blocks = (m + RANK_UB - 1) / RANK_UB;
-    int64_t want = n_slices;
-    if (want <= 0) {
-        // automatic: about four resident workgroups per CU of the 256 (a slice covers at least four tiles)
-        want = blocks > 0 ? (1024 + blocks - 1) / blocks : 1;
-        const int64_t cap = tiles / 4 > 0 ? tiles / 4 : 1;
-        want = want > cap ? cap : want;
-        want = want > 16 ? 16 : want;
-    }
-    if (want < 1) want = 1;
-    if (want > tiles) want = tiles > 0 ? tiles : 1;
-    if (want > 64) want = 64;
-    // slices cover whole tiles: the count actually launched
-    const int64_t per = ((tiles + want - 1) / want) * s.tile_items;
-    const int64_t eff = per > 0 ? (n_items + per - 1) / per : 1;
-    return (int32_t)(eff > 0 ? eff : 1);
+    return rank_slices(m, n_items, s.tile_items, RANK_UB, n_slices);
 }
 
 int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const float *Ti, int64_t ldi, int32_t n_items, int32_t c1,
@@ -338,18 +336,16 @@ int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const floa
     if (slices > 1 && (!workspace_items || !workspace_scores)) return AMAR_EINVAL;
     if (m == 0) return AMAR_OK;
     if (!out_items || !out_scores) return AMAR_EINVAL;
-    const int64_t tiles = (n_items + sh.tile_items - 1) / sh.tile_items;
-    const int64_t per_tiles = (tiles + slices - 1) / slices;
     a.Tu = Tu; a.ldu = ldu; a.Ti = Ti; a.ldi = ldi; a.c1 = c1; a.n_items = n_items;
     a.users = users; a.m = m; a.excl_ptr = excl_ptr; a.excl_items = excl_items;
-    a.wpack = wpack; a.in_act = in_act; a.k = k;
+    a.wpack = wpack; a.in_act = in_act; a.out.k = k;
     a.tile_items = sh.tile_items; a.tile_stride = sh.tile_stride;
-    a.slice_items = (int)(per_tiles * sh.tile_items > 0 ? per_tiles * sh.tile_items : sh.tile_items);
-    a.n_slices = slices;
-    a.out_items = slices > 1 ? workspace_items : out_items;
-    a.out_scores = slices > 1 ? workspace_scores : out_scores;
+    a.slice_items = (int)rank_slice_rows(n_items, sh.tile_items, slices);
+    a.out.n_slices = slices;
+    a.out.rows = slices > 1 ? workspace_items : out_items;
+    a.out.scores = slices > 1 ? workspace_scores : out_scores;
     const size_t lds_bytes = (size_t)((a.wpack_floats + 3) & ~3) * 4 + (size_t)sh.tile_items * sh.tile_stride * 4 +
-                             (size_t)RANK_UB * (2 * RANK_LIST + 2 * RANK_CAND + 4) * 4;
+                             (size_t)rank_select_state_floats(RANK_UB) * 4;
     if (lds_bytes > 160 * 1024) return AMAR_EUNSUPPORTED;
     const int64_t blocks = (m + RANK_UB - 1) / RANK_UB;
     if (blocks >= (1ll << 31)) return AMAR_EUNSUPPORTED;
@@ -374,8 +370,18 @@ int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const floa
 #undef AMAR_RANK_LAUNCH
     const int e = amar_check_launch();
     if (e != AMAR_OK || slices == 1) return e;
-    hipLaunchKernelGGL(recommend_merge_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, workspace_items, workspace_scores, m, slices,
-                       k, out_items, out_scores);
+    return rank_merge_slices(workspace_items, workspace_scores, m, slices, k, out_items, out_scores, st);
+}
+
+int amar_topk_segmented_f32(const int32_t *seg_ptr, const int32_t *item_ids, const float *scores,
+                            int32_t n_users, int32_t k, int32_t *out_items, float *out_scores,
+                            amar_stream_t stream) {
+    if (n_users < 0 || k < 1 || !seg_ptr) return AMAR_EINVAL;
+    if (k > 64) return AMAR_EUNSUPPORTED;
+    if (n_users == 0) return AMAR_OK;                                    // nothing to rank: the outputs may be empty (NULL)
+    if (!item_ids || !scores || !out_items || !out_scores) return AMAR_EINVAL;
+    hipLaunchKernelGGL(topk_segmented_kernel, dim3((n_users + 3) / 4), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), seg_ptr, item_ids, scores, n_users, k, out_items, out_scores);
     return amar_check_launch();
 }
 

@@ -51,18 +51,23 @@ def check_k(k):
     return int(k)
 
 
+def check_ids(ids, lo, hi, what, not_integer="{what} must be integer node ids", out_of_range="{what} must lie in [{lo}, {hi}) (got {min}..{max})"):
+    """Host int64 node ids in [lo, hi) (all of them when None), in the caller's order."""
+    if ids is None:
+        return np.arange(lo, hi, dtype=np.int64)
+    a = ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+    a = a.reshape(-1)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(not_integer.format(what=what))
+    a = a.astype(np.int64)
+    if a.size and (a.min() < lo or a.max() >= hi):
+        raise ValueError(out_of_range.format(what=what, lo=lo, hi=hi, min=int(a.min()), max=int(a.max())))
+    return a
+
+
 def check_users(users, n_users):
     """Host int64 user indices in 0..n_users-1 (all users when None), in the caller's order."""
-    if users is None:
-        return np.arange(n_users, dtype=np.int64)
-    u = users.detach().cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
-    u = u.reshape(-1)
-    if u.size and not np.issubdtype(u.dtype, np.integer):
-        raise ValueError("users must be integer indices")
-    u = u.astype(np.int64)
-    if u.size and (u.min() < 0 or u.max() >= n_users):
-        raise ValueError("user indices must lie in [0, {}) (got {}..{})".format(n_users, int(u.min()), int(u.max())))
-    return u
+    return check_ids(users, 0, n_users, 'users', "{what} must be integer indices", "user indices must lie in [{lo}, {hi}) (got {min}..{max})")
 
 
 def exclusion_csr(ratings, n_users, n_items):
@@ -80,30 +85,6 @@ def exclusion_csr(ratings, n_users, n_items):
     ptr = np.zeros(n_users + 1, dtype=np.int64)
     np.cumsum(np.bincount(uu, minlength=n_users), out=ptr[1:])
     return ptr, ii
-
-
-# Exclusion CSRs on the device, built once per ratings array (held weakly: a dropped trainset frees its entry).
-_EXCL_CACHE = {}
-
-
-def _exclusion_device(trainset, n_users, n_items, exclude_seen):
-    if not exclude_seen:
-        return None
-    ratings = trainset.ratings
-    dev = default_device()
-    key = (id(ratings), n_users, n_items, str(dev))
-    hit = _EXCL_CACHE.get(key)
-    if hit is not None and hit[0]() is ratings and hit[1] == np.shape(ratings):
-        return hit[2]
-    ptr, items = exclusion_csr(ratings, n_users, n_items)
-    entry = (torch.from_numpy(ptr.astype(np.int32)).to(dev), torch.from_numpy(items.astype(np.int32)).to(dev))
-    try:
-        ref = weakref.ref(ratings)
-        weakref.finalize(ratings, _EXCL_CACHE.pop, key, None)
-    except TypeError:                                    # not weakly referenceable: keep the array alive with its entry
-        ref = (lambda obj: (lambda: obj))(ratings)
-    _EXCL_CACHE[key] = (ref, np.shape(ratings), entry)
-    return entry
 
 
 def liked_csr(ratings, n_users, n_items):
@@ -153,10 +134,10 @@ def property_weights(df, n_items, kind='idf'):
     return np.where(df > 0, np.log(float(n_items) / np.maximum(df, 1.0)), 0.0).astype(np.float32)
 
 
-# Liked and property CSRs on the device, built once per ratings array / graph (held weakly where the object allows it).  As with
-# _EXCL_CACHE the key is the object's identity: an array or graph mutated in place is not noticed, and the finalizer of a dead
-# object whose id was reused may drop the new object's entry, which only costs a rebuild.
-_LIKED_CACHE, _PROP_CACHE = {}, {}
+# Exclusion, liked and property CSRs on the device, built once per ratings array / graph (held weakly where the object allows it: a
+# dropped trainset frees its entries).  The key is the object's identity: an array or graph mutated in place is not noticed, and the
+# finalizer of a dead object whose id was reused may drop the new object's entry, which only costs a rebuild.
+_EXCL_CACHE, _LIKED_CACHE, _PROP_CACHE = {}, {}, {}
 
 
 def _device_cached(cache, obj, key, build):
@@ -171,6 +152,17 @@ def _device_cached(cache, obj, key, build):
         ref = (lambda o: (lambda: o))(obj)
     cache[key] = (ref, entry)
     return entry
+
+
+def _exclusion_device(trainset, n_users, n_items, exclude_seen):
+    if not exclude_seen:
+        return None
+    ratings, dev = trainset.ratings, default_device()
+
+    def build():
+        ptr, items = exclusion_csr(ratings, n_users, n_items)
+        return torch.from_numpy(ptr.astype(np.int32)).to(dev), torch.from_numpy(items.astype(np.int32)).to(dev)
+    return _device_cached(_EXCL_CACHE, ratings, (id(ratings), np.shape(ratings), n_users, n_items, str(dev)), build)
 
 
 def _liked_device(trainset, n_users, n_items):
@@ -436,18 +428,19 @@ def rerank_mmr(items, scores, table, k, trade_off=0.7, metric='cosine'):
                            trade_off=trade_off, metric=metric)
 
 
-def check_ids(ids, lo, hi, what):
-    """Host int64 node ids in [lo, hi) (all of them when None), in the caller's order."""
-    if ids is None:
-        return np.arange(lo, hi, dtype=np.int64)
-    a = ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
-    a = a.reshape(-1)
-    if a.size and not np.issubdtype(a.dtype, np.integer):
-        raise ValueError("{} must be integer node ids".format(what))
+def _item_rows_device(items, n_users, n_items, device, rows=None, widths=None):
+    """An [m, K] host array of item node ids (-1 padded) as int32 item rows on `device` (-1 stays -1).  rows: the m the caller
+    expects; widths: the (least, greatest) K it takes; None: any."""
+    a = np.asarray(items.cpu() if isinstance(items, torch.Tensor) else items)
+    if a.ndim != 2 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError("items must be a 2-D [m, K] array of integer node ids")
+    if (rows is not None and a.shape[0] != rows) or (widths is not None and not widths[0] <= a.shape[1] <= widths[1]):
+        raise ValueError("items must hold one row of {}..{} node ids per user ({} rows for {} users)".format(widths[0], widths[1], a.shape[0], rows))
     a = a.astype(np.int64)
-    if a.size and (a.min() < lo or a.max() >= hi):
-        raise ValueError("{} must lie in [{}, {}) (got {}..{})".format(what, lo, hi, int(a.min()), int(a.max())))
-    return a
+    real = a[a != -1]
+    if real.size and (real.min() < n_users or real.max() >= n_users + n_items):
+        raise ValueError("items must be node ids in [{}, {}) or -1".format(n_users, n_users + n_items))
+    return torch.from_numpy(np.where(a >= 0, a - n_users, -1).astype(np.int32)).to(device)
 
 
 def similar_rows(table, rows, k, metric, exclude_self, base):
@@ -618,13 +611,7 @@ class SimilarSearch:
         if isinstance(items, torch.Tensor) and items.is_cuda:
             lists = items.to(torch.int32)
         else:
-            a = np.asarray(items.cpu() if isinstance(items, torch.Tensor) else items)
-            if a.ndim != 2 or (a.size and not np.issubdtype(a.dtype, np.integer)):
-                raise ValueError("items must be a 2-D [m, K] array of integer node ids")
-            a = a.astype(np.int64)
-            if a.size and (a[a >= 0].size and (a[a >= 0].min() < n_users or a.max() >= n_users + n_items)):
-                raise ValueError("items must be node ids in [{}, {}) or -1".format(n_users, n_users + n_items))
-            lists = torch.from_numpy(np.where(a >= 0, a - n_users, -1).astype(np.int32)).to(table.device)
+            lists = _item_rows_device(items, n_users, n_items, table.device)
         if lists.dim() != 2:
             raise ValueError("items must be a 2-D [m, K] array")
         ks, _ = capi.rank_metrics_args(int(lists.shape[1]), [int(lists.shape[1])] if ks is None else ks)
@@ -663,16 +650,7 @@ class SimilarSearch:
                 lists = torch.zeros((0, k), dtype=torch.int32, device=table.device)
         else:
             u = check_users(users, n_users)
-            a = np.asarray(items.cpu() if isinstance(items, torch.Tensor) else items)
-            if a.ndim != 2 or (a.size and not np.issubdtype(a.dtype, np.integer)):
-                raise ValueError("items must be a 2-D [m, K] array of integer node ids")
-            if a.shape[0] != len(u) or not 1 <= a.shape[1] <= K_MAX:
-                raise ValueError("items must hold one row of 1..{} node ids per user ({} rows for {} users)".format(K_MAX, a.shape[0], len(u)))
-            a = a.astype(np.int64)
-            real = a[a != -1]
-            if real.size and (real.min() < n_users or real.max() >= n_users + n_items):
-                raise ValueError("items must be node ids in [{}, {}) or -1".format(n_users, n_users + n_items))
-            lists = torch.from_numpy(np.where(a >= 0, a - n_users, -1).astype(np.int32)).to(table.device)
+            lists = _item_rows_device(items, n_users, n_items, table.device, rows=len(u), widths=(1, K_MAX))
         u_dev = None if users is None else torch.from_numpy(u.astype(np.int32)).to(table.device)
         out = explain_lists(lists.contiguous(), u_dev, _liked_device(trainset, n_users, n_items), table,
                             _props_device(trainset, n_items, property_weight), E, Q, metric)

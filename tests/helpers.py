@@ -170,3 +170,29 @@ def load_oracle_weights(model, gnn, head):
         for layer, (w, b) in zip(getattr(model.rs, name).layers, head[name]):
             put(layer.kernel, w)
             put(layer.bias, b)
+
+
+# ---- the fused rankers' adversarial selection case (test_recommend_gpu.py, test_similar_gpu.py) ----------------------
+SELECT_ROWS, SELECT_QUERIES = 197, 19        # three full 64-row groups plus five; one full 16-query block plus three
+
+
+def select_case_exclusions(k, tile_rows, n=SELECT_ROWS, m=SELECT_QUERIES):
+    """Exclusion sets of the m queries: query 0 excludes every row, query 1 all but k - 1, queries 2..5 the first rows of the 64-row
+    groups, their last rows, both together with the rows on either side of every tile boundary, and the 67 highest rows; the
+    rest three scattered rows each."""
+    firsts, lasts = set(range(0, n, 64)), set(range(63, n, 64)) | {n - 1}
+    edges = {r for t in range(tile_rows, n + 1, tile_rows) for r in (t - 1, t) if r < n}
+    excl = {0: set(range(n)), 1: set(range(n)) - {(3 * j) % n for j in range(k - 1)}, 2: firsts, 3: lasts, 4: firsts | lasts | edges,
+            5: set(range(n - 67, n))}
+    for q in range(6, m):
+        excl[q] = {q, 64 + q, n - q}
+    return excl
+
+
+def select_case_expected(excl, k, best_first):
+    """[m, k] rows every query must return: its unexcluded rows in the order `best_first` (all rows, best score first), -1 padded."""
+    out = np.full((len(excl), k), -1, dtype=np.int64)
+    for q in range(len(excl)):
+        keep = [r for r in best_first if r not in excl[q]][:k]
+        out[q, :len(keep)] = keep
+    return out

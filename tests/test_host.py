@@ -1,4 +1,5 @@
 """CPU: host-side logic of the drop-in boundary (no kernels run here)."""
+import json
 import os
 import re
 
@@ -492,3 +493,35 @@ def test_dense_bwd_plan_host_functions():
     g = lib.amar_dense_stack_bwd_groups(1024)
     assert g in (16, 64) and lib.amar_dense_stack_bwd_groups(4096) == 64 and lib.amar_dense_stack_bwd_groups(1) == 1
     assert lib.amar_dense_stack_bwd_workspace_floats(1024, 2, dims) == 4 + g * (24 * 16 + 16 + 16 * 8 + 8)
+
+
+RANK_SLICES_GRID = dict(m=[0, 1, 16, 17, 1000, 6040, 100000], rows=[0, 1, 255, 256, 257, 3706, 30000, 10 ** 6], slices=[0, 1, 2, 5, 64, 100])
+
+
+def rank_slices_answers(lib):
+    """amar_nearest_slices / amar_recommend_slices over RANK_SLICES_GRID (m outermost, requested slices innermost) for the width
+    classes listed in tests/golden/rank_slices.json."""
+    import ctypes
+    import itertools
+    z = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'rank_slices.json')))
+    grid = list(itertools.product(RANK_SLICES_GRID['m'], RANK_SLICES_GRID['rows'], RANK_SLICES_GRID['slices']))
+    got = {'nearest': {}, 'recommend': {}}
+    for d in z['nearest_widths']:
+        got['nearest'][str(d)] = [int(lib.amar_nearest_slices(m, n, d, s)) for m, n, s in grid]
+    for dims in z['recommend_dims']:
+        c = (ctypes.c_int32 * len(dims))(*dims)
+        got['recommend'][','.join(map(str, dims))] = [int(lib.amar_recommend_slices(m, n, c, len(dims) - 1, s)) for m, n, s in grid]
+    return z, got
+
+
+def test_rank_slices_answers_are_the_recorded_ones():
+    """How the fused rankers cut a call into table slices is host arithmetic shared by both (csrc/amar_rank_select.h: rank_slices):
+    its answers over a grid of queries x rows x requested slices, for every tile width of each kernel and for the widths each
+    refuses, are the ones recorded in tests/golden/rank_slices.json from the build before the arithmetic was shared."""
+    from deep_cbrs_amar_renaissance_amd import capi
+    z, got = rank_slices_answers(capi.load())
+    assert z['grid'] == RANK_SLICES_GRID
+    for kernel in ('nearest', 'recommend'):
+        assert got[kernel].keys() == z[kernel].keys()
+        for width, want in z[kernel].items():
+            assert got[kernel][width] == want, (kernel, width)

@@ -138,6 +138,44 @@ def test_kernel_against_float64(hip, c1, n_layers, n_items):
         assert [i for i in row if i in dup] == sorted(dup)  # tied duplicates in item order
 
 
+@pytest.mark.parametrize('k', [1, 63, 64])
+def test_selector_adversarial_orders(hip, k):
+    """The shared selector where it merges most and least: 197 items, 19 users, scores strictly ascending in the item row (every
+    item beats the threshold: a merge per full buffer) and the table reversed (nothing after the first k passes), exclusions on
+    group and tile edges, one user with nothing left and one with k - 1 items left.  Tu = 0, Ti[i, 0] = i / 197 through an identity
+    Dense(16, relu) and Dense(1, sigmoid) on feature 0: sigmoid(i / 197), about 1e-3 apart, so the lists are known exactly."""
+    import torch
+    from deep_cbrs_amar_renaissance_amd import capi
+    n, m, c1 = helpers.SELECT_ROWS, helpers.SELECT_QUERIES, 16
+    dev = torch.device('cuda')
+    excl = helpers.select_case_exclusions(k, tile_rows=256)                              # c1 = 16 stages 256-item tiles
+    ptr = np.cumsum([0] + [len(excl[u]) for u in range(m)])
+    ptr_d = torch.from_numpy(ptr.astype(np.int32)).to(dev)
+    ex_d = torch.from_numpy(np.array([i for u in range(m) for i in sorted(excl[u])], dtype=np.int32)).to(dev)
+    dot = np.zeros((c1, 1), dtype=np.float32)
+    dot[0, 0] = 1.0
+    blob, _ = capi.chain_pack([np.eye(c1, dtype=np.float32), dot], [np.zeros(c1, dtype=np.float32), np.zeros(1, dtype=np.float32)])
+    blob, dims, acts = torch.from_numpy(blob).to(dev), [c1, c1, 1], ['relu', 'sigmoid']
+    tu_d = torch.zeros((m, c1), dtype=torch.float32, device=dev)
+    for reverse in (False, True):
+        value = np.arange(n)[::-1] if reverse else np.arange(n)                          # item i scores sigmoid(value[i] / 197)
+        ti = np.zeros((n, c1), dtype=np.float32)
+        ti[:, 0] = value / np.float32(n)
+        want_i = helpers.select_case_expected(excl, k, np.argsort(-value, kind='stable').tolist())
+        want_s = np.where(want_i >= 0, 1.0 / (1.0 + np.exp(-ti[np.maximum(want_i, 0), 0].astype(np.float64))), -np.inf)
+        ti_d = torch.from_numpy(ti).to(dev)
+        first = None
+        for slices in (1, 2, 3):
+            if hip.load().amar_recommend_slices(m, n, ctypes_dims(dims), len(dims) - 1, slices) != slices:
+                continue
+            got_i, got_s = capi.recommend(tu_d, ti_d, blob, dims, acts, 'relu', k, excl_ptr=ptr_d, excl_items=ex_d, n_slices=slices)
+            got_i, got_s = got_i.cpu().numpy(), got_s.cpu().numpy()
+            assert np.array_equal(got_i, want_i), (k, reverse, slices)
+            assert np.array_equal(np.isneginf(got_s), want_i < 0) and np.abs(got_s[want_i >= 0] - want_s[want_i >= 0]).max() <= 1e-6
+            first = got_s if first is None else first
+            assert np.array_equal(got_s.view(np.int32), first.view(np.int32)), (k, reverse, slices)
+
+
 def ctypes_dims(dims):
     import ctypes
     return (ctypes.c_int32 * len(dims))(*dims)

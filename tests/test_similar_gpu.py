@@ -96,6 +96,34 @@ def test_kernel_against_float64(hip, n_rows, d, metric):
     assert torch.all(t_buf[:, :4] == 7.0) and torch.all(t_buf[:, 4 + d:] == 7.0)         # the buffer around the slice is untouched
 
 
+@pytest.mark.parametrize('k', [1, 63, 64])
+def test_selector_adversarial_orders(hip, k):
+    """The shared selector where it merges most and least: 197 rows, 19 queries, scores strictly ascending in the row id (every row
+    beats the threshold: a merge per full buffer) and the table reversed (nothing after the first k passes), exclusions on group
+    and tile edges, one query with nothing left and one with k - 1 rows left.  dot with Q = e0 and T[i] = i e0: the scores are the
+    integers, exact in float32, so the lists are known exactly."""
+    import torch
+    capi, n, m, d = hip, helpers.SELECT_ROWS, helpers.SELECT_QUERIES, 4
+    dev = torch.device('cuda')
+    excl = helpers.select_case_exclusions(k, tile_rows=256)                              # d = 4 stages 256-row tiles
+    ptr_d, ex_d = _csr(excl, range(m), dev)
+    Q = np.zeros((m, d), dtype=np.float32)
+    Q[:, 0] = 1.0
+    for reverse in (False, True):
+        value = np.arange(n)[::-1] if reverse else np.arange(n)                          # score of row i
+        T = np.zeros((n, d), dtype=np.float32)
+        T[:, 0] = value
+        want_r = helpers.select_case_expected(excl, k, np.argsort(-value, kind='stable').tolist())
+        want_s = np.where(want_r >= 0, value[np.maximum(want_r, 0)], -np.inf).astype(np.float32)
+        q_d, t_d = torch.from_numpy(Q).to(dev), torch.from_numpy(T).to(dev)
+        for slices in (1, 2, 3):
+            if capi.load().amar_nearest_slices(m, n, d, slices) != slices:
+                continue
+            got_r, got_s = capi.nearest(q_d, t_d, k, metric='dot', excl_ptr=ptr_d, excl_rows=ex_d, n_slices=slices)
+            assert np.array_equal(got_r.cpu().numpy(), want_r), (k, reverse, slices)
+            assert np.array_equal(got_s.cpu().numpy(), want_s), (k, reverse, slices)
+
+
 def test_slicing_is_exercised(hip):
     """The grid above really reaches the sliced form (two launches) at its large table."""
     s = hip.load().amar_nearest_slices
