@@ -154,6 +154,9 @@ SIGNATURES = {
     'amar_recommend_slices': (ctypes.c_int32, [_I64, _I32, _P, _I32, _I32]),
     'amar_recommend_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P,
                                           _I32, _I32, _P, _P, _P, _P, _P]),
+    'amar_recommend_group_slices': (ctypes.c_int32, [_I64, _I64, _I32, _P, _I32, _I32]),
+    'amar_recommend_group_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I64, _I64, _P, _P,
+                                                _I32, _F32, _I32, _I32, _P, _P, _P, _P, _P]),
     'amar_nearest_slices': (ctypes.c_int32, [_I64, _I32, _I32, _I32]),
     'amar_nearest_workspace_floats': (ctypes.c_int64, [_I64, _I32, _I32, _I32, _I32]),
     'amar_nearest_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _P, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
@@ -1450,6 +1453,45 @@ def recommend(Tu, Ti, wpack, dims, acts, in_act, k, users=None, excl_ptr=None, e
             ACT_CODES[in_act], _ptr(users, I32, 'users'), m, _ptr(excl_ptr, I32, 'excl_ptr'), _ptr_entries(excl_items, I32, 'excl_items'),
             int(k), int(slices) if slices > 1 else 1, _ptr(ws_i), _ptr(ws_s),
             _ptr(out_items) if m else None, _ptr(out_scores) if m else None)
+    return out_items, out_scores
+
+
+GROUP_STRATEGIES = {'mean': 0, 'min': 1, 'max': 2}                      # include/amar_hip.h: AMAR_GROUP_MEAN / _MIN / _MAX
+
+
+def recommend_group(Tu, Ti, wpack, dims, acts, in_act, k, grp_ptr, grp_users, strategy='mean', min_score=None, excl_ptr=None, excl_items=None,
+                    n_slices=0):
+    """Fused group top-k of the split head (amar_recommend_group_f32): group j has the members grp_users[grp_ptr[j]:grp_ptr[j + 1]]
+    (int32 rows of Tu, ascending and distinct inside a group); every item's member scores are combined by `strategy` ('mean', 'min' =
+    least misery, 'max' = most pleasure), an item is dropped when any member scores it below `min_score` (None: no veto), and the k
+    best items that are not in segment j of the exclusion CSR (excl_ptr [g + 1], a CSR over GROUPS) are kept.  Returns (items int32
+    [g, k] (-1 padded), scores float32 [g, k] (-inf padded)).  n_slices <= 0: the library's automatic item slicing
+    (AMAR_RECOMMEND_SLICES overrides it)."""
+    if strategy not in GROUP_STRATEGIES:
+        raise ValueError("recommend_group: strategy must be one of {} (got {!r})".format(sorted(GROUP_STRATEGIES), strategy))
+    n_users, c1 = int(Tu.shape[0]), int(Tu.shape[1])
+    n_items = int(Ti.shape[0])
+    if int(Ti.shape[1]) != c1:
+        raise ValueError("recommend_group: Tu and Ti must have the same width")
+    g, n_members = int(grp_ptr.numel()) - 1, int(grp_users.numel())
+    if g < 0:
+        raise ValueError("recommend_group: grp_ptr must have one entry per group plus one")
+    if (excl_ptr is None) != (excl_items is None):
+        raise ValueError("recommend_group: excl_ptr and excl_items go together")
+    if excl_ptr is not None and excl_ptr.numel() != g + 1:
+        raise ValueError("recommend_group: excl_ptr must have one entry per group plus one")
+    if n_slices <= 0:
+        n_slices = int(os.environ.get('AMAR_RECOMMEND_SLICES', '0'))
+    dims_c = (ctypes.c_int32 * len(dims))(*dims)
+    acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
+    slices, out_items, out_scores, ws_i = _sliced_topk('amar_recommend_group_slices', (g, n_members, n_items, dims_c, len(acts), int(n_slices)),
+                                                       g, k, Tu.device)
+    ws_s = torch.empty((g * slices * k,), dtype=torch.float32, device=Tu.device) if slices > 1 else None
+    _launch('amar_recommend_group_f32', *_mat(Tu, 'Tu'), n_users, *_mat(Ti, 'Ti'), n_items, c1, _ptr(wpack, F32, 'wpack'), dims_c, acts_c,
+            len(acts), ACT_CODES[in_act], _ptr(grp_ptr, I32, 'grp_ptr'), _ptr_entries(grp_users, I32, 'grp_users'), g, n_members,
+            _ptr(excl_ptr, I32, 'excl_ptr'), _ptr_entries(excl_items, I32, 'excl_items'), GROUP_STRATEGIES[strategy],
+            float('-inf') if min_score is None else float(min_score), int(k), int(slices) if slices > 1 else 1, _ptr(ws_i), _ptr(ws_s),
+            _ptr(out_items) if g else None, _ptr(out_scores) if g else None)
     return out_items, out_scores
 
 

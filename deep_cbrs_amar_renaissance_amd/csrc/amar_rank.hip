@@ -10,7 +10,7 @@
 //     the layout of chain_kernel in amar_chain.hip) is formed in registers as in_act(Tu[u] + Ti[i]): no per-pair gathers.
 //   * the rest stack runs on v_mfma_f32_16x16x4_f32 with chain_kernel's loop order, fragment blob and dot stage, so a score is
 //     bit-identical to what amar_chain_f32's generic kernel returns for the same pair (the pair stage of predict() for heads
-//     whose widths it takes).
+//     whose widths it takes).  These two steps are amar_rank_score.inc, the fragment amar_group.hip's kernel includes too.
 //   * selection: the RankSlot of amar_rank_select.h, one per user (threshold, exclusion walk over the user's training items,
 //     candidate buffer, rank-counting merge); the kernel hands it 16 PT scores at a time, lane group g holding pair tile g.
 //   * with several item slices each workgroup leaves its slice's top-k in a workspace and a second launch (recommend_merge_kernel
@@ -18,29 +18,10 @@
 //     order, so the result does not depend on the slicing).
 // The result of a user depends on its own Tu row, Ti and the weights only: not on the other users of the block or the call.
 // The pair route's ranker (amar_topk_segmented_f32: scores already in memory, one wave per user) is at the end of the file.
-#include "amar_common.h"
-#include "amar_rank_select.h"
+#include "amar_rank_score.h"
 #include <stdlib.h>
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int RANK_MAX_LAYERS = 8;
-constexpr int RANK_WAVES = 4, RANK_UPW = 4, RANK_UB = RANK_WAVES * RANK_UPW;     // users per wave, per workgroup
-constexpr int RANK_TILE_BYTES = 32 * 1024;
-
-struct RankArgs {
-    const float *Tu; int64_t ldu; const float *Ti; int64_t ldi; int c1; int n_items;
-    const int32_t *users; int64_t m;
-    const int32_t *excl_ptr, *excl_items;
-    const float *wpack; int wpack_floats;
-    int in_act, n_layers;
-    int kt[RANK_MAX_LAYERS], nt[RANK_MAX_LAYERS], act[RANK_MAX_LAYERS], w_off[RANK_MAX_LAYERS], b_off[RANK_MAX_LAYERS];
-    int dot_off, dot_bias_off, dot_kt, dot_act;
-    int tile_items, tile_stride, slice_items;
-    RankOut out;
-};
 
 template <int MAXT, int PT>
 __global__ __launch_bounds__(256) void recommend_kernel(const RankArgs a) {
@@ -95,79 +76,7 @@ __global__ __launch_bounds__(256) void recommend_kernel(const RankArgs a) {
             const int ee = a.excl_ptr ? a.excl_ptr[u + 1] : 0;
 
             for (int grp = 0; grp < rows; grp += 16 * PT) {
-                f32x4 x[MAXT][PT];
-#pragma unroll
-                for (int pt = 0; pt < PT; ++pt) {
-                    const float *row = tile + (grp + 16 * pt + col) * a.tile_stride;
-#pragma unroll
-                    for (int t = 0; t < MAXT; ++t) {
-                        const int f = 16 * t + 4 * g;
-                        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                        if (t < KT0 && f < a.c1) {
-                            v = tu[t] + *reinterpret_cast<const f32x4 *>(row + f);
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) v[r] = amar_act(v[r], a.in_act);
-                        }
-                        x[t][pt] = v;
-                    }
-                }
-                for (int l = 0; l < a.n_layers; ++l) {
-                    const int KT = a.kt[l], NT = a.nt[l];
-                    const float *wl = w_lds + a.w_off[l];
-                    const float *bl = w_lds + a.b_off[l];
-                    f32x4 y[MAXT][PT];
-#pragma unroll
-                    for (int mm = 0; mm < MAXT; ++mm) {
-                        if (mm < NT) {
-                            const f32x4 b4 = *reinterpret_cast<const f32x4 *>(bl + 16 * mm + 4 * g);
-#pragma unroll
-                            for (int pt = 0; pt < PT; ++pt) y[mm][pt] = b4;
-#pragma unroll
-                            for (int t = 0; t < MAXT; ++t) {
-                                if (t < KT) {
-                                    const f32x4 w4 = *reinterpret_cast<const f32x4 *>(wl + ((mm * KT + t) * 64 + lane) * 4);
-#pragma unroll
-                                    for (int r = 0; r < 4; ++r)
-#pragma unroll
-                                        for (int pt = 0; pt < PT; ++pt)
-                                            y[mm][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[r], x[t][pt][r], y[mm][pt], 0, 0, 0);
-                                }
-                            }
-                        }
-                    }
-                    const int act = a.act[l];
-#pragma unroll
-                    for (int mm = 0; mm < MAXT; ++mm)
-#pragma unroll
-                        for (int pt = 0; pt < PT; ++pt) {
-                            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                            if (mm < NT) {
-                                v = y[mm][pt];
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) v[r] = amar_act(v[r], act);
-                            }
-                            x[mm][pt] = v;
-                        }
-                }
-                // the 1-unit layer: chain_kernel's dot, then lane group g keeps pair tile g
-                const float *wd = w_lds + a.dot_off;
-                float sel = 0.f;
-#pragma unroll
-                for (int pt = 0; pt < PT; ++pt) {
-                    float s = 0.f;
-#pragma unroll
-                    for (int t = 0; t < MAXT; ++t) {
-                        if (t < a.dot_kt) {
-                            const f32x4 w4 = *reinterpret_cast<const f32x4 *>(wd + 16 * t + 4 * g);
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) s = fmaf(x[t][pt][r], w4[r], s);
-                        }
-                    }
-                    s += __shfl_xor(s, 16, 64);
-                    s += __shfl_xor(s, 32, 64);
-                    sel = g == pt ? s : sel;
-                }
-                const float z = amar_act(sel + w_lds[a.dot_bias_off], a.dot_act);
+#include "amar_rank_score.inc"
                 const int item = t0 + grp + 16 * g + col;
                 top.offer(z, item, g < PT && grp + 16 * g + col < rows, a.excl_items, ee, a.out.k, lane);
             }
@@ -251,26 +160,6 @@ __global__ __launch_bounds__(256) void topk_segmented_kernel(const int32_t *__re
     }
 }
 
-inline int tiles16(int n) { return (n + 15) / 16; }
-
-// Launch geometry of a rest stack: tile budget MAXT (widest layer / 16, rounded up to a power of two), pair tiles per wave PT.
-struct RankShape { int maxt, pt, tile_items, tile_stride; };
-
-int rank_shape(const int32_t *dims, int32_t n_layers, RankShape &s) {
-    int maxw = 0;
-    for (int l = 0; l < n_layers; ++l) maxw = dims[l] > maxw ? dims[l] : maxw;   // dims[n_layers] == 1 (the dot)
-    if (maxw > 128) return AMAR_EUNSUPPORTED;
-    s.maxt = maxw <= 16 ? 1 : (maxw <= 32 ? 2 : (maxw <= 64 ? 4 : 8));
-    s.pt = s.maxt <= 2 ? 4 : (s.maxt == 4 ? 2 : 1);
-    s.tile_stride = 16 * tiles16(dims[0]) + 4;                     // +4 floats: neighbouring items start on different banks
-    const int group = 16 * s.pt;
-    int ti = RANK_TILE_BYTES / (4 * s.tile_stride);
-    ti = ti > 256 ? 256 : ti;
-    ti = (ti / group) * group;
-    s.tile_items = ti < group ? group : ti;
-    return AMAR_OK;
-}
-
 }  // namespace
 
 int rank_merge_slices(const int32_t *part_rows, const float *part_scores, int64_t m, int slices, int k, int32_t *out_rows,
@@ -299,36 +188,13 @@ int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const floa
     if (k > 64) return AMAR_EUNSUPPORTED;
     if (!users && m != n_users) return AMAR_EINVAL;
     if (excl_ptr && !excl_items) return AMAR_EINVAL;
-    if (c1 < 4 || (c1 & 3) || (ldu & 3) || (ldi & 3) || ldu < c1 || ldi < c1 || !amar_aligned16(Tu) || !amar_aligned16(Ti) ||
-        !amar_aligned16(wpack))
-        return AMAR_EINVAL;
-    if (c1 > 128) return AMAR_EUNSUPPORTED;
-    if (in_act != AMAR_ACT_NONE && in_act != AMAR_ACT_RELU && in_act != AMAR_ACT_SIGMOID) return AMAR_EINVAL;
-    // the rest stack: >= 1 MFMA layer, then Dense(1) as the dot stage
-    if (n_layers < 2 || n_layers > RANK_MAX_LAYERS + 1 || dims[0] != c1 || dims[n_layers] != 1) return AMAR_EUNSUPPORTED;
+    int rc = rank_check_tables(Tu, ldu, Ti, ldi, c1, wpack, dims, n_layers, in_act);
+    if (rc != AMAR_OK) return rc;
     RankArgs a{};
-    int off = 0;
-    for (int l = 0; l < n_layers; ++l) {
-        const int K = dims[l], N = dims[l + 1], act = acts[l];
-        if (K < 1 || N < 1 || (act != AMAR_ACT_NONE && act != AMAR_ACT_RELU && act != AMAR_ACT_SIGMOID)) return AMAR_EINVAL;
-        if (l == n_layers - 1) {
-            a.dot_off = off; a.dot_kt = tiles16(K); a.dot_act = act;
-            off += 16 * tiles16(K);
-            a.dot_bias_off = off;
-            off += 4;
-        } else {
-            if (N == 1) return AMAR_EUNSUPPORTED;
-            a.kt[l] = tiles16(K); a.nt[l] = tiles16(N); a.act[l] = act;
-            a.w_off[l] = off;
-            off += tiles16(N) * tiles16(K) * 256;
-            a.b_off[l] = off;
-            off += 16 * tiles16(N);
-        }
-    }
-    a.n_layers = n_layers - 1;
-    a.wpack_floats = off;
+    rc = rank_pack_args(dims, acts, n_layers, a);
+    if (rc != AMAR_OK) return rc;
     RankShape sh;
-    const int rc = rank_shape(dims, n_layers, sh);
+    rc = rank_shape(dims, n_layers, sh);
     if (rc != AMAR_OK) return rc;
     const int32_t slices = amar_recommend_slices(m, n_items, dims, n_layers, n_slices);
     if (slices < 1) return slices < 0 ? slices : AMAR_EINVAL;
@@ -344,30 +210,14 @@ int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const floa
     a.out.n_slices = slices;
     a.out.rows = slices > 1 ? workspace_items : out_items;
     a.out.scores = slices > 1 ? workspace_scores : out_scores;
-    const size_t lds_bytes = (size_t)((a.wpack_floats + 3) & ~3) * 4 + (size_t)sh.tile_items * sh.tile_stride * 4 +
-                             (size_t)rank_select_state_floats(RANK_UB) * 4;
+    const size_t lds_bytes = rank_lds_bytes(a, sh);
     if (lds_bytes > 160 * 1024) return AMAR_EUNSUPPORTED;
     const int64_t blocks = (m + RANK_UB - 1) / RANK_UB;
     if (blocks >= (1ll << 31)) return AMAR_EUNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)blocks, (unsigned)slices), block(256);
     static bool done[4][AMAR_MAX_DEVICES];
-#define AMAR_RANK_LAUNCH(MT, PTT, D)                                                                                    \
-    do {                                                                                                                \
-        auto kern = recommend_kernel<MT, PTT>;                                                                          \
-        if (lds_bytes > 64 * 1024) {                                                                                    \
-            const int e = amar_allow_lds(reinterpret_cast<const void *>(kern), 160 * 1024, done[D]);                   \
-            if (e != AMAR_OK) return e;                                                                                 \
-        }                                                                                                               \
-        hipLaunchKernelGGL(kern, grid, block, lds_bytes, st, a);                                                        \
-    } while (0)
-    switch (sh.maxt) {
-    case 1: AMAR_RANK_LAUNCH(1, 4, 0); break;
-    case 2: AMAR_RANK_LAUNCH(2, 4, 1); break;
-    case 4: AMAR_RANK_LAUNCH(4, 2, 2); break;
-    default: AMAR_RANK_LAUNCH(8, 1, 3); break;
-    }
-#undef AMAR_RANK_LAUNCH
+    AMAR_RANK_DISPATCH(recommend_kernel, sh.maxt, grid, block, lds_bytes, st, a, done)
     const int e = amar_check_launch();
     if (e != AMAR_OK || slices == 1) return e;
     return rank_merge_slices(workspace_items, workspace_scores, m, slices, k, out_items, out_scores, st);

@@ -1,0 +1,148 @@
+// What the fused rankers of the split head share (amar_rank.hip: one user per selector; amar_group.hip: a group of users per
+// selector) besides the selector of amar_rank_select.h:
+//   * RankArgs, the kernels' argument block, and the constants of their decomposition;
+//   * the score stage itself is amar_rank_score.inc, a fragment both kernel bodies include (one text, the same bits per pair);
+//   * device helpers around it, as amar_group.hip uses them: the packed rest stack and an item tile go to LDS
+//     (rank_stage_weights, rank_stage_tile), a user's Tu row becomes MFMA fragments (rank_load_user).  recommend_kernel keeps these
+//     few lines in its own body, as it always had them: it must compile to what it compiled to;
+//   * host: the argument checks the entry points share (rank_check_tables), the walk over the packed stack (rank_pack_args), the
+//     launch geometry of a stack (rank_shape), the LDS a launch needs (rank_lds_bytes) and the MAXT / PT dispatch
+//     (AMAR_RANK_DISPATCH).
+#pragma once
+#include "amar_common.h"
+#include "amar_rank_select.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int RANK_MAX_LAYERS = 8;
+constexpr int RANK_WAVES = 4, RANK_UPW = 4, RANK_UB = RANK_WAVES * RANK_UPW;     // selectors per wave, per workgroup
+constexpr int RANK_TILE_BYTES = 32 * 1024;
+
+struct RankArgs {
+    const float *Tu; int64_t ldu; const float *Ti; int64_t ldi; int c1; int n_items;
+    const int32_t *users; int64_t m;
+    const int32_t *excl_ptr, *excl_items;
+    const float *wpack; int wpack_floats;
+    int in_act, n_layers;
+    int kt[RANK_MAX_LAYERS], nt[RANK_MAX_LAYERS], act[RANK_MAX_LAYERS], w_off[RANK_MAX_LAYERS], b_off[RANK_MAX_LAYERS];
+    int dot_off, dot_bias_off, dot_kt, dot_act;
+    int tile_items, tile_stride, slice_items;
+    RankOut out;
+};
+
+// The packed rest stack goes to LDS once per workgroup.
+__device__ __forceinline__ void rank_stage_weights(const RankArgs &a, float *w_lds) {
+    for (int i = threadIdx.x * 4; i < a.wpack_floats; i += blockDim.x * 4)
+        *reinterpret_cast<float4 *>(&w_lds[i]) = *reinterpret_cast<const float4 *>(a.wpack + i);
+}
+
+// Rows t0 .. t0 + rows - 1 of Ti go to the tile (16 KT0 features a row, zero past c1 and past `rows`); the caller's barriers
+// stand on either side.
+__device__ __forceinline__ void rank_stage_tile(const RankArgs &a, float *tile, int t0, int rows) {
+    const int f4_per_row = 4 * a.kt[0];
+    for (int idx = threadIdx.x; idx < a.tile_items * f4_per_row; idx += blockDim.x) {
+        const int r = idx / f4_per_row, f = 4 * (idx - r * f4_per_row);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < rows && f < a.c1) v = *reinterpret_cast<const float4 *>(a.Ti + (int64_t)(t0 + r) * a.ldi + f);
+        *reinterpret_cast<float4 *>(&tile[r * a.tile_stride + f]) = v;
+    }
+}
+
+// Row u of Tu as this lane's fragments: features 16t + 4g .. + 3 of k-step t.
+template <int MAXT>
+__device__ __forceinline__ void rank_load_user(const RankArgs &a, int u, int g, f32x4 (&tu)[MAXT]) {
+    const int KT0 = a.kt[0];
+#pragma unroll
+    for (int t = 0; t < MAXT; ++t) {
+        const int f = 16 * t + 4 * g;
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        tu[t] = (t < KT0 && f < a.c1) ? *reinterpret_cast<const f32x4 *>(a.Tu + (int64_t)u * a.ldu + f) : zero;
+    }
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------
+inline int tiles16(int n) { return (n + 15) / 16; }
+
+// Launch geometry of a rest stack: tile budget MAXT (widest layer / 16, rounded up to a power of two), pair tiles per wave PT.
+struct RankShape { int maxt, pt, tile_items, tile_stride; };
+
+inline int rank_shape(const int32_t *dims, int32_t n_layers, RankShape &s) {
+    int maxw = 0;
+    for (int l = 0; l < n_layers; ++l) maxw = dims[l] > maxw ? dims[l] : maxw;   // dims[n_layers] == 1 (the dot)
+    if (maxw > 128) return AMAR_EUNSUPPORTED;
+    s.maxt = maxw <= 16 ? 1 : (maxw <= 32 ? 2 : (maxw <= 64 ? 4 : 8));
+    s.pt = s.maxt <= 2 ? 4 : (s.maxt == 4 ? 2 : 1);
+    s.tile_stride = 16 * tiles16(dims[0]) + 4;                     // +4 floats: neighbouring items start on different banks
+    const int group = 16 * s.pt;
+    int ti = RANK_TILE_BYTES / (4 * s.tile_stride);
+    ti = ti > 256 ? 256 : ti;
+    ti = (ti / group) * group;
+    s.tile_items = ti < group ? group : ti;
+    return AMAR_OK;
+}
+
+// The tables, the input activation and the outline of the rest stack (>= 1 MFMA layer, then Dense(1) as the dot stage).
+inline int rank_check_tables(const float *Tu, int64_t ldu, const float *Ti, int64_t ldi, int32_t c1, const float *wpack,
+                             const int32_t *dims, int32_t n_layers, int32_t in_act) {
+    if (c1 < 4 || (c1 & 3) || (ldu & 3) || (ldi & 3) || ldu < c1 || ldi < c1 || !amar_aligned16(Tu) || !amar_aligned16(Ti) ||
+        !amar_aligned16(wpack))
+        return AMAR_EINVAL;
+    if (c1 > 128) return AMAR_EUNSUPPORTED;
+    if (in_act != AMAR_ACT_NONE && in_act != AMAR_ACT_RELU && in_act != AMAR_ACT_SIGMOID) return AMAR_EINVAL;
+    if (n_layers < 2 || n_layers > RANK_MAX_LAYERS + 1 || dims[0] != c1 || dims[n_layers] != 1) return AMAR_EUNSUPPORTED;
+    return AMAR_OK;
+}
+
+// Where every layer of the blob packed by amar_chain_pack_f32 sits: a's layer fields, n_layers (the MFMA layers) and wpack_floats.
+inline int rank_pack_args(const int32_t *dims, const int32_t *acts, int32_t n_layers, RankArgs &a) {
+    int off = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        const int K = dims[l], N = dims[l + 1], act = acts[l];
+        if (K < 1 || N < 1 || (act != AMAR_ACT_NONE && act != AMAR_ACT_RELU && act != AMAR_ACT_SIGMOID)) return AMAR_EINVAL;
+        if (l == n_layers - 1) {
+            a.dot_off = off; a.dot_kt = tiles16(K); a.dot_act = act;
+            off += 16 * tiles16(K);
+            a.dot_bias_off = off;
+            off += 4;
+        } else {
+            if (N == 1) return AMAR_EUNSUPPORTED;
+            a.kt[l] = tiles16(K); a.nt[l] = tiles16(N); a.act[l] = act;
+            a.w_off[l] = off;
+            off += tiles16(N) * tiles16(K) * 256;
+            a.b_off[l] = off;
+            off += 16 * tiles16(N);
+        }
+    }
+    a.n_layers = n_layers - 1;
+    a.wpack_floats = off;
+    return AMAR_OK;
+}
+
+// Dynamic LDS of a launch: the stack, one item tile, RANK_UB selectors.
+inline size_t rank_lds_bytes(const RankArgs &a, const RankShape &sh) {
+    return (size_t)((a.wpack_floats + 3) & ~3) * 4 + (size_t)sh.tile_items * sh.tile_stride * 4 +
+           (size_t)rank_select_state_floats(RANK_UB) * 4;
+}
+
+}  // namespace
+
+// Launches KERN<MAXT, PT> for the stack's shape (the four forms 1/4, 2/4, 4/2, 8/1), allowing it the large LDS where the launch
+// needs more than 64 KB.  `done`: the call site's static bool [4][AMAR_MAX_DEVICES].  Returns from the caller on a refusal.
+#define AMAR_RANK_LAUNCH_FORM(KERN, MT, PTT, D, grid, block, lds_bytes, st, args, done)                                 \
+    do {                                                                                                                \
+        auto kern = KERN<MT, PTT>;                                                                                      \
+        if ((lds_bytes) > 64 * 1024) {                                                                                  \
+            const int e = amar_allow_lds(reinterpret_cast<const void *>(kern), 160 * 1024, done[D]);                   \
+            if (e != AMAR_OK) return e;                                                                                 \
+        }                                                                                                               \
+        hipLaunchKernelGGL(kern, grid, block, lds_bytes, st, args);                                                     \
+    } while (0)
+#define AMAR_RANK_DISPATCH(KERN, maxt, grid, block, lds_bytes, st, args, done)                                          \
+    switch (maxt) {                                                                                                     \
+    case 1: AMAR_RANK_LAUNCH_FORM(KERN, 1, 4, 0, grid, block, lds_bytes, st, args, done); break;                        \
+    case 2: AMAR_RANK_LAUNCH_FORM(KERN, 2, 4, 1, grid, block, lds_bytes, st, args, done); break;                        \
+    case 4: AMAR_RANK_LAUNCH_FORM(KERN, 4, 2, 2, grid, block, lds_bytes, st, args, done); break;                        \
+    default: AMAR_RANK_LAUNCH_FORM(KERN, 8, 1, 3, grid, block, lds_bytes, st, args, done); break;                       \
+    }

@@ -390,6 +390,8 @@ class Experimenter:
             self.write_diverse(**dict(self.config.parameters.get('diversify')))
         if self.config.parameters.get('explain'):
             self.write_explanations(**dict(self.config.parameters.get('explain')))
+        if self.config.parameters.get('group_recommend'):
+            self.write_group_recommend(**dict(self.config.parameters.get('group_recommend')))
         self.logger.info('\n' + str(metrics))
         print('\n' + str(metrics))
         return metrics
@@ -458,6 +460,46 @@ class Experimenter:
         path = path_join(self.predictions_dest, "explanations_{}.tsv".format(int(k)))
         explanations_frame(out, self.trainset.users, self.trainset.items, getattr(self, 'property_ids', None)).to_csv(
             path, sep='\t', header=False, index=False)
+        return path
+
+    def group_members(self, groups):
+        """The groups of parameters.group_recommend.groups as (group ids, list of user-index arrays): a path to a two-column TSV
+        (group id, original user id; users that are not in the training set are dropped with a log line, groups in order of first
+        appearance) or {size, count, seed}: `count` random groups of `size` distinct training users from
+        numpy.random.default_rng(seed)."""
+        n_users = len(self.trainset.users)
+        if isinstance(groups, str):
+            frame = pd.read_csv(groups, sep='\t', header=None, usecols=[0, 1])
+            index = {u: r for r, u in enumerate(np.asarray(self.trainset.users).tolist())}
+            rows = frame[1].map(index)
+            if rows.isna().any():
+                self.logger.info("group_recommend: {} of {} listed users are not in the training set: dropped".format(
+                    int(rows.isna().sum()), len(frame)))
+            frame = frame.assign(row=rows)[rows.notna()]
+            ids = list(dict.fromkeys(frame[0].tolist()))
+            return ids, [np.unique(frame['row'][frame[0] == gid].astype(np.int64).to_numpy()) for gid in ids]
+        size, count = int(groups['size']), int(groups['count'])
+        if not 1 <= size <= n_users or count < 0:
+            raise ValueError("group_recommend.groups: size must lie in [1, {}] and count must not be negative".format(n_users))
+        rng = np.random.default_rng(int(groups.get('seed', 0)))
+        return list(range(count)), [rng.choice(n_users, size=size, replace=False).astype(np.int64) for _ in range(count)]
+
+    def write_group_recommend(self, k=10, strategy='mean', min_score=None, groups=None):
+        """Opt-in (parameters.group_recommend: {k, strategy, min_score, groups}): the k best unseen items of every group
+        (`recommend_group()`; `groups` as `group_members` reads them), written as <predictions_dest>/group_top_<k>.tsv, one row
+        per (group, rank): group, rank, item (original id), score."""
+        if groups is None:
+            raise ValueError("parameters.group_recommend needs `groups`: a TSV path or {size, count, seed}")
+        k = int(k)
+        ids, members = self.group_members(groups)
+        items, scores = self.model.recommend_group(self.trainset, members, k=k, strategy=strategy,
+                                                   min_score=None if min_score is None else float(min_score))
+        n_users, item_ids = len(self.trainset.users), np.asarray(self.trainset.items)
+        g, r = np.nonzero(items >= 0)
+        frame = pd.DataFrame({'group': np.asarray(ids, dtype=object)[g] if len(ids) else [], 'rank': r + 1,
+                              'item': item_ids[items[g, r] - n_users], 'score': scores[g, r]})
+        path = path_join(self.predictions_dest, "group_top_{}.tsv".format(k))
+        frame.to_csv(path, sep='\t', header=False, index=False)
         return path
 
     def run(self):

@@ -192,6 +192,14 @@ class BasicRS(rec.SimilarSearch, Model):
         towers = towers if towers is not None else self.towers(*self._recommend_tables(trainset))
         return rec.pairs(lambda u, i: self.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
 
+    def _group_route(self, trainset):
+        tables = self._recommend_tables(trainset)
+        split = self._recommend_split(*tables)
+        if split is not None:
+            return 'fused', split, split[2]
+        towers = self.towers(*tables)
+        return 'pairs', lambda u, i: self.score_towers(towers, u, i), towers[0].device
+
     def _recommend_route(self, trainset):
         d = np.asarray(trainset.embeddings).shape[1]
         if not self.built:
@@ -392,6 +400,14 @@ class BasicGNN(rec.SimilarSearch, Model, abc.ABC):
         rec.check_users(users, len(trainset.users))
         towers = towers if towers is not None else self.rs.towers(*self._recommend_tables(trainset))
         return rec.pairs(lambda u, i: self.rs.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
+
+    def _group_route(self, trainset):
+        tables = self._recommend_tables(trainset)
+        split = self.rs._recommend_split(*tables)
+        if split is not None:
+            return 'fused', split, split[2]
+        towers = self.rs.towers(*tables)
+        return 'pairs', lambda u, i: self.rs.score_towers(towers, u, i), towers[0].device
 
     def _recommend_route(self, trainset):
         d = self.gnn.output_dim()

@@ -281,6 +281,10 @@ class HybridCBRS(rec.SimilarSearch, Model):
         towers = towers if towers is not None else self._recommend_towers(trainset)
         return rec.pairs(lambda u, i: self.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
 
+    def _group_route(self, trainset):
+        towers = self._recommend_towers(trainset)
+        return 'pairs', lambda u, i: self.score_towers(towers, u, i), towers[0].device
+
     def _recommend_route(self, trainset):
         return 'pairs'
 
@@ -426,6 +430,10 @@ class HybridBertGNN(rec.SimilarSearch, Model, abc.ABC):
         rec.check_users(users, len(trainset.users))
         towers = towers if towers is not None else self._recommend_towers(trainset)
         return rec.pairs(lambda u, i: self.rs.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
+
+    def _group_route(self, trainset):
+        towers = self._recommend_towers(trainset)
+        return 'pairs', lambda u, i: self.rs.score_towers(towers, u, i), towers[0].device
 
     def _recommend_route(self, trainset):
         return 'pairs'

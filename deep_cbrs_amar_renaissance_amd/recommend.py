@@ -31,6 +31,12 @@ opt-in ``diversity=`` of ``evaluate_ranking`` (intra-list diversity and catalogu
 The fourth part answers "why this item for this user?": ``liked_csr`` and ``item_property_csr`` read the liked items and the
 item-property links off the trainset, ``explain_lists`` joins them with the item vectors in one ``amar_explain_f32`` launch (nothing
 of size m x K x L in memory) and the mixin's ``explain`` runs it on ``recommend(k)``'s device lists or on the caller's items.
+
+The fifth part answers "what should WE watch?": ``group_csr`` / ``group_exclusion_csr`` turn groups of users into the CSRs of
+``amar_recommend_group_f32``, ``group_fused`` is that one launch over the split towers (every member's score of every item combined
+by the mean, the minimum or the maximum, with an optional veto, and selected on chip: nothing of size members x |I| in memory),
+``group_pairs`` the same arithmetic over pair-route scores for the heads without a fused kernel, and the mixin's
+``recommend_group`` picks between them exactly as ``recommend()`` does.
 """
 import contextlib
 import weakref
@@ -499,12 +505,180 @@ def explain_lists(lists, users, liked, table, props, n_evidence, n_properties, m
                         prop_ptr=props[0], prop_ids=props[1], prop_weight=props[2], max_prop_row=props[3])
 
 
+# -- group recommendation (amar_recommend_group_f32): "what should WE watch?" --------------------------------------------------------
+def check_strategy(name):
+    if not isinstance(name, str) or name not in capi.GROUP_STRATEGIES:
+        raise ValueError("strategy must be one of {} (got {!r})".format(sorted(capi.GROUP_STRATEGIES), name))
+    return name
+
+
+def check_min_score(x):
+    """The veto floor as a float: None = -inf (no veto); a finite number or -inf; NaN, +inf and non-numbers are ValueErrors."""
+    if x is None:
+        return float('-inf')
+    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or np.isnan(x) or float(x) == float('inf'):
+        raise ValueError("min_score must be None, a finite number or -inf (got {!r})".format(x))
+    return float(x)
+
+
+def group_csr(groups, n_users):
+    """A sequence of user-index sequences as (ptr int32 [g + 1], users int32): the members of every group sorted ascending, so that
+    a result never depends on the order a caller lists people in.  Empty groups are allowed.  ValueError for a duplicate member, a
+    non-integer or out-of-range index, or `groups` that is not a sequence of sequences."""
+    not_nested = "groups must be a sequence of sequences of user indices"
+    if isinstance(groups, (str, bytes, dict)) or not hasattr(groups, '__len__') or not hasattr(groups, '__iter__'):
+        raise ValueError(not_nested)
+    ptr, segs = np.zeros(len(groups) + 1, dtype=np.int64), []
+    for j, members in enumerate(groups):
+        if isinstance(members, (str, bytes, dict)) or not hasattr(members, '__len__') or np.ndim(members) != 1:
+            raise ValueError(not_nested)
+        a = np.sort(check_ids(members, 0, n_users, 'group members', "{what} must be integer indices",
+                              "user indices must lie in [{lo}, {hi}) (got {min}..{max})"))
+        if a.size > 1 and (a[1:] == a[:-1]).any():
+            raise ValueError("group {} lists a member twice".format(j))
+        segs.append(a)
+        ptr[j + 1] = ptr[j] + a.size
+    users = np.concatenate(segs) if segs else np.zeros(0, dtype=np.int64)
+    return ptr.astype(np.int32), users.astype(np.int32)
+
+
+def group_exclusion_csr(ratings, grp_ptr, grp_users, n_users, n_items):
+    """The union of the members' training items per group, as a CSR over groups: (ptr int64 [g + 1], items int64) with item ROWS
+    sorted and de-duplicated per group (`exclusion_csr` per user, then the union)."""
+    ptr, items = exclusion_csr(ratings, n_users, n_items)
+    grp_ptr, members = np.asarray(grp_ptr, dtype=np.int64), np.asarray(grp_users, dtype=np.int64)
+    g = len(grp_ptr) - 1
+    cnt = ptr[members + 1] - ptr[members]
+    total = int(cnt.sum())
+    out = np.zeros(g + 1, dtype=np.int64)
+    if total == 0:
+        return out, np.zeros(0, dtype=np.int64)
+    group_of = np.repeat(np.arange(g, dtype=np.int64), np.diff(grp_ptr))
+    pos = np.repeat(ptr[members] - (np.cumsum(cnt) - cnt), cnt) + np.arange(total, dtype=np.int64)
+    key = np.unique(np.repeat(group_of, cnt) * n_items + items[pos])      # sorted by (group, item), duplicates gone
+    np.cumsum(np.bincount(key // n_items, minlength=g), out=out[1:])
+    return out, key % n_items
+
+
+def _i32_device(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+
+
+def group_fused(towers, plan, grp_ptr, grp_users, excl, k, strategy, min_score):
+    """One amar_recommend_group_f32 call over the split towers (tu [U, c1], ti [I, c1] with b1 folded in); `excl` = the host CSR
+    over groups or None.  Returns the device tensors (item rows int32 [g, k], scores float32 [g, k])."""
+    tu, ti = towers[0], towers[1]
+    blob, dims, acts = plan['rest']
+    return capi.recommend_group(tu, ti, blob, dims, acts, plan['in_act'], k, _i32_device(grp_ptr, tu.device), _i32_device(grp_users, tu.device),
+                                strategy=strategy, min_score=min_score,
+                                excl_ptr=None if excl is None else _i32_device(excl[0], tu.device),
+                                excl_items=None if excl is None else _i32_device(excl[1], tu.device))
+
+
+MEMBER_SCORE_GROUPS = 32             # groups whose chosen items share one compact table in `fused_member_scores`
+
+
+def fused_member_scores(towers, plan, grp_ptr, grp_users, rows, per):
+    """Every member's own score of every chosen item of its group (rows int64 [g, k] item rows, -1 padded), written into per[j]
+    [n_members_j, k], with the bits the fused ranking gave them: the ranking kernel itself scores them.  (The pair stage would not
+    do: for some heads it multiplies on split bf16 operands, a few float32 ulps away.)  Per chunk of MEMBER_SCORE_GROUPS groups the
+    chosen items' Ti rows form one compact table, every member is a group of one, and its exclusion segment is the rest of the
+    table: one amar_recommend_group_f32 launch per chunk, nothing of size members x |I|."""
+    tu, ti = towers[0], towers[1]
+    blob, dims, acts = plan['rest']
+    g, k = rows.shape
+    sizes = np.diff(np.asarray(grp_ptr, dtype=np.int64))
+    for lo in range(0, g, MEMBER_SCORE_GROUPS):
+        hi = min(g, lo + MEMBER_SCORE_GROUPS)
+        c, m0, m1 = hi - lo, int(grp_ptr[lo]), int(grp_ptr[hi])
+        valid = rows[lo:hi] >= 0                                          # [c, k]
+        if m1 == m0 or not valid.any():
+            continue
+        table = ti[torch.from_numpy(np.maximum(rows[lo:hi], 0).reshape(-1)).to(ti.device)]      # compact row q * k + r = rows[lo + q, r]
+        group_of = np.repeat(np.arange(c), sizes[lo:hi])                  # member -> its group in the chunk
+        allowed = np.zeros((m1 - m0, c, k), dtype=bool)
+        allowed[np.arange(m1 - m0), group_of] = valid[group_of]
+        banned = ~allowed.reshape(m1 - m0, c * k)
+        e_ptr = np.zeros(m1 - m0 + 1, dtype=np.int64)
+        np.cumsum(banned.sum(1), out=e_ptr[1:])
+        items, scores = capi.recommend_group(tu, table, blob, dims, acts, plan['in_act'], k, _i32_device(np.arange(m1 - m0 + 1), tu.device),
+                                             _i32_device(grp_users[m0:m1], tu.device), strategy='max',
+                                             excl_ptr=_i32_device(e_ptr, tu.device), excl_items=_i32_device(np.nonzero(banned)[1], tu.device))
+        items, scores = items.cpu().numpy(), scores.cpu().numpy()
+        for s_, q in enumerate(group_of.tolist()):
+            got = items[s_] >= 0
+            per[lo + q][s_ + m0 - int(grp_ptr[lo + q]), items[s_][got] - q * k] = scores[s_][got]
+
+
+def group_pairs(score_fn, n_items, grp_ptr, grp_users, excl, k, strategy, min_score, dev):
+    """Pair route of the group ranking: per chunk of groups, members x all items scored by `score_fn(u_ids, i_ids)`, aggregated on
+    the device by a loop over the member position (acc = acc + s_t elementwise, or the running minimum / maximum: the float32 order
+    of amar_recommend_group_f32, not a tree sum), divided by the group size, the group's union and the vetoed items masked out,
+    then amar_topk_segmented_f32.  Returns the device tensors (item rows int32 [g, k], scores float32 [g, k])."""
+    g = len(grp_ptr) - 1
+    sizes = np.diff(np.asarray(grp_ptr, dtype=np.int64))
+    budget = max(1, PAIRS_PER_CHUNK // max(1, n_items))              # member rows scored per chunk
+    all_items = torch.arange(n_items, dtype=torch.int32, device=dev)
+    out_i, out_s = [], []
+    lo = 0
+    while lo < g:
+        hi = lo + 1
+        while hi < g and int(grp_ptr[hi + 1] - grp_ptr[lo]) <= budget:
+            hi += 1
+        c, m0, m1 = hi - lo, int(grp_ptr[lo]), int(grp_ptr[hi])
+        size = sizes[lo:hi]
+        keep = torch.ones((c, n_items), dtype=torch.bool, device=dev)
+        agg = torch.zeros((c, n_items), dtype=torch.float32, device=dev)
+        if m1 > m0 and n_items:
+            members = _i32_device(grp_users[m0:m1], dev)
+            s = score_fn(torch.repeat_interleave(members, n_items).contiguous(), all_items.repeat(m1 - m0).contiguous()).reshape(m1 - m0, n_items)
+            low = torch.zeros_like(agg)
+            first = np.asarray(grp_ptr[lo:hi], dtype=np.int64) - m0
+            for t in range(int(size.max())):                         # member position t of every group that has one
+                has = np.nonzero(size > t)[0]
+                rows, st = torch.from_numpy(has).to(dev), s[torch.from_numpy(first[has] + t).to(dev)]
+                if t == 0:
+                    agg[rows], low[rows] = st, st
+                    continue
+                at = agg[rows]
+                agg[rows] = at + st if strategy == 'mean' else (torch.minimum(at, st) if strategy == 'min' else torch.maximum(at, st))
+                low[rows] = torch.minimum(low[rows], st)
+            if strategy == 'mean':
+                # the quotient in float64, rounded once more to float32: the correctly rounded float32 quotient (53 >= 2 * 24 + 2 bits)
+                n = torch.from_numpy(np.maximum(size, 1).astype(np.float64)).to(dev)[:, None]
+                agg = (agg.to(torch.float64) / n).to(torch.float32)
+            keep &= low >= min_score
+        keep &= torch.from_numpy(size > 0).to(dev)[:, None]
+        if excl is not None:
+            e0, e1 = int(excl[0][lo]), int(excl[0][hi])
+            if e1 > e0:
+                rows = np.repeat(np.arange(c), np.diff(np.asarray(excl[0][lo:hi + 1], dtype=np.int64)))
+                keep[torch.from_numpy(rows).to(dev), torch.from_numpy(np.asarray(excl[1][e0:e1], dtype=np.int64)).to(dev)] = False
+        r, i = keep.nonzero(as_tuple=True)                           # row-major: groups in order, items ascending
+        seg = torch.zeros(c + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(keep.sum(1), 0, out=seg[1:])
+        i_ids, scores = i.to(torch.int32).contiguous(), agg[r, i].contiguous()
+        if i_ids.numel() == 0:
+            scores = torch.zeros(1, dtype=torch.float32, device=dev)
+            i_ids = torch.zeros(1, dtype=torch.int32, device=dev)
+        items, sc = capi.topk_segmented(seg.to(torch.int32), i_ids, scores, k)
+        out_i.append(items)
+        out_s.append(sc)
+        lo = hi
+    return torch.cat(out_i), torch.cat(out_s)
+
+
 class SimilarSearch:
     """Embedding accessors and similarity search shared by the scoring models.  A model names its spaces (`_embedding_spaces`:
     'graph' = the propagated, reduced node table, 'tower' = the first-stage Dense outputs per entity; the first one is the default)
     and returns the device tables of one (`_embedding_tables(trainset, space)` -> (users [|U|, d], items [|I|, d]))."""
 
     def _embedding_spaces(self):
+        raise NotImplementedError
+
+    def _group_route(self, trainset):
+        """How the model ranks a catalogue, chosen as its `recommend()` chooses: ('fused', (tu, ti, ...), plan) = the split towers and
+        their plan, or ('pairs', score_fn(u_ids, i_ids) -> [P, 1] scores, device)."""
         raise NotImplementedError
 
     def _embedding_tables(self, trainset, space):
@@ -660,3 +834,53 @@ class SimilarSearch:
         ev, sim, pr, ps, pc = out
         return dict(zip(EXPLAIN_KEYS, (u, rows(lists), rows(ev), sim.cpu().numpy(), pr.cpu().numpy().astype(np.int64), ps.cpu().numpy(),
                                        pc.cpu().numpy())))
+
+    # -- group recommendation (amar_recommend_group_f32) ----------------------------------------------------------------
+    def recommend_group(self, trainset, groups, k=10, strategy='mean', min_score=None, exclude_seen=True, member_scores=False):
+        """The k best items for every GROUP of `groups` (a sequence of sequences of user indices 0..|U|-1; the order of the members
+        does not matter, empty groups are allowed) among all items of `trainset`: every member's score of every item, combined by
+        `strategy` — 'mean' (average: the scores added in ascending member order, divided by the group size), 'min' (least misery)
+        or 'max' (most pleasure) — in float32; an item that any member scores below `min_score` is dropped (None: no veto), and so is,
+        unless exclude_seen=False, every training item of any member.  Heads with a fused ranking kernel run one
+        amar_recommend_group_f32 launch (nothing of size members x |I| in memory); the others aggregate pair-route scores.
+        Returns (items int64 [g, k] node ids, -1 padded; scores float32 [g, k], -inf padded): aggregate descending, node id ascending
+        on ties.  member_scores=True adds a list of g float32 arrays [n_members_j, k]: each member's own score of each chosen item
+        (members in ascending order; NaN where the list is padded), with the bits that went into the aggregate: from the ranking
+        kernel on the fused route (`fused_member_scores`), from one pair-scoring call over the (member, chosen item) pairs on the
+        pair route."""
+        k, strategy, floor = check_k(k), check_strategy(strategy), check_min_score(min_score)
+        n_users, n_items = _sizes(trainset)
+        ptr, members = group_csr(groups, n_users)
+        g = len(ptr) - 1
+        if g == 0:
+            out = (np.zeros((0, k), dtype=np.int64), np.zeros((0, k), dtype=np.float32))
+            return out + ([],) if member_scores else out
+        excl = group_exclusion_csr(trainset.ratings, ptr, members, n_users, n_items) if exclude_seen else None
+        route = self._group_route(trainset)
+        if route[0] == 'fused':
+            towers, plan = route[1], route[2]
+            score_fn = None
+            rows, scores = group_fused(towers, plan, ptr, members, excl, k, strategy, floor)
+        else:
+            score_fn, dev = route[1], route[2] or default_device()
+            rows, scores = group_pairs(score_fn, n_items, ptr, members, excl, k, strategy, floor, dev)
+        rows = rows.cpu().numpy().astype(np.int64)
+        out = (np.where(rows >= 0, rows + n_users, -1), scores.cpu().numpy().astype(np.float32))
+        if not member_scores:
+            return out
+        sizes = np.diff(ptr.astype(np.int64))
+        valid = rows >= 0                                                # [g, k]
+        per = [np.full((int(sizes[j]), k), np.nan, dtype=np.float32) for j in range(g)]
+        if score_fn is None:
+            fused_member_scores(towers, plan, ptr, members, rows, per)
+            return out + (per,)
+        u_ids = np.concatenate([np.repeat(members[ptr[j]:ptr[j + 1]], int(valid[j].sum())) for j in range(g)])
+        i_ids = np.concatenate([np.tile(rows[j][valid[j]], int(sizes[j])) for j in range(g)])
+        if u_ids.size:
+            s = score_fn(_i32_device(u_ids, dev), _i32_device(i_ids, dev)).reshape(-1).cpu().numpy().astype(np.float32)
+            at = 0
+            for j in range(g):
+                n_j, v_j = int(sizes[j]), int(valid[j].sum())
+                per[j][:, valid[j]] = s[at:at + n_j * v_j].reshape(n_j, v_j)
+                at += n_j * v_j
+        return out + (per,)

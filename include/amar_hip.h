@@ -1249,6 +1249,44 @@ int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const floa
                        int32_t k, int32_t n_slices, int32_t *workspace_items, float *workspace_scores,
                        int32_t *out_items, float *out_scores, amar_stream_t stream);
 
+/* Group recommendation over the same split head, fused: the members' scores of every item are combined by a social-choice rule
+ * and each group's k best items are selected on chip ("what should WE watch?").  Tables, packed rest stack, limits, alignment
+ * rules and slicing contract are those of amar_recommend_f32.
+ * Group j of n_groups has the members grp_users[grp_ptr[j] .. grp_ptr[j+1]): rows of Tu, ascending and distinct inside a group
+ * (a PRECONDITION, like every member < n_users: not checked on the device); n_members = grp_ptr[n_groups], which the host caller
+ * knows.  Exclusion CSR (optional, both NULL = rank every item) over the GROUPS: excl_ptr[n_groups+1], segment j sorted and
+ * de-duplicated, values in 0..n_items-1; it belongs to group j, not to a user.
+ * All in float32, for item i not in the group's segment: s_t = score(member_t, i), exactly the value amar_recommend_f32 computes
+ * for that pair (one score routine: the same fragments, loop order and dot stage), and
+ *     AMAR_GROUP_MEAN:  acc = s_0, then acc = acc + s_t for t = 1..n-1 in member order; the aggregate is acc / (float)n, correctly
+ *                       rounded (IEEE division, no reciprocal, nothing contracted)
+ *     AMAR_GROUP_MIN:   the smallest s_t (least misery)          AMAR_GROUP_MAX:  the largest s_t (most pleasure)
+ * Veto: the item is dropped for the group when any s_t < min_score; min_score = -INFINITY turns it off.
+ * The k best (aggregate descending, item ascending on ties) go to out_items / out_scores [n_groups, k], padded with -1 / -inf; an
+ * empty group, or one with nothing left, gives an all-padding row.  A group of one member returns, under every strategy, the bits
+ * amar_recommend_f32 returns for that user with the same exclusion list.  Nothing of size members x n_items or
+ * n_groups x n_items is written; selection runs once per item per group.  A group's result depends on its own members, Ti, the
+ * weights, the strategy, min_score and its segment only: not on the other groups of the call, the grid or the slicing; no atomics,
+ * the same bits on every run.
+ * n_slices: item slices per block of 16 groups (<= 0: automatic, sized from n_groups AND n_members: a workgroup's work is its
+ * members' walks over its tiles).  amar_recommend_group_slices returns the count a call will launch (a call that passes
+ * n_slices > 0 must pass that count); with more than one, workspace_items / workspace_scores hold n_groups * slices * k entries
+ * each (any contents) and a second launch merges the slices.
+ * NULL tables, negative sizes, k < 1, an unknown strategy, a NaN min_score, grp_ptr == NULL with n_groups > 0, grp_users == NULL
+ * with n_members > 0, excl_ptr without excl_items, a missing workspace: AMAR_EINVAL; the shape limits: AMAR_EUNSUPPORTED; all
+ * checked before any device call.  n_groups == 0: AMAR_OK, nothing is launched. */
+#define AMAR_GROUP_MEAN 0   /* additive / average */
+#define AMAR_GROUP_MIN  1   /* least misery */
+#define AMAR_GROUP_MAX  2   /* most pleasure */
+int32_t amar_recommend_group_slices(int64_t n_groups, int64_t n_members, int32_t n_items, const int32_t *dims, int32_t n_layers,
+                                    int32_t n_slices);
+int amar_recommend_group_f32(const float *Tu, int64_t ldu, int32_t n_users, const float *Ti, int64_t ldi, int32_t n_items, int32_t c1,
+                             const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers, int32_t in_act,
+                             const int32_t *grp_ptr, const int32_t *grp_users, int64_t n_groups, int64_t n_members,
+                             const int32_t *excl_ptr, const int32_t *excl_items, int32_t strategy, float min_score,
+                             int32_t k, int32_t n_slices, int32_t *workspace_items, float *workspace_scores,
+                             int32_t *out_items, float *out_scores, amar_stream_t stream);
+
 /* Nearest rows of a table under dot or cosine similarity, fused score-and-select ("which items are like this one?").
  * Listed query j is row Q[query_rows[j]] (row j itself when query_rows == NULL, m == n_queries).  For every listed query and EVERY
  * row i of T[n_rows, d] that is not in the query's exclusion segment,
