@@ -165,6 +165,9 @@ SIGNATURES = {
     'amar_list_diversity_f64': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _P]),
     'amar_explain_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, _I32, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _I32, _I32,
                                         _P, _P, _P, _P, _P, _P]),
+    'amar_rerank_calibrated_f32': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _I32, _P, _P, _I32, _I32, _I32, _F32, _F32, _I32,
+                                                  _P, _P, _P, _P, _P, _P]),
+    'amar_list_calibration_f64': (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, _I32, _P, _P, _I32, _I32, _F32, _P, _I32, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -1664,6 +1667,61 @@ def explain(lists, liked_ptr, liked_items, T, n_evidence=3, n_properties=0, metr
             _ptr(out_ev) if m else None, _ptr(out_sim) if m else None, _ptr(out_p) if filled else None, _ptr(out_ps) if filled else None,
             _ptr(out_pc) if filled else None)
     return out_ev, out_sim, out_p, out_ps, out_pc
+
+
+CALIBRATE_MAX_P, CALIBRATE_MAX_G, CALIBRATE_POOL_BUDGET = 64, 1024, 4096   # include/amar_hip.h: AMAR_CALIBRATE_*
+
+
+def _calibrate_sizes(what, m, users, liked_ptr, cat_ptr):
+    if users is not None and int(users.numel()) != m:
+        raise ValueError("{}: users must name one user per list".format(what))
+    return int(liked_ptr.numel()) - 1, int(cat_ptr.numel()) - 1
+
+
+def rerank_calibrated(pool_items, pool_scores, liked_ptr, liked_items, cat_ptr, cat_ids, n_categories, k, trade_off=0.5, smoothing=0.01,
+                      users=None, max_cat_row=0, want_value=False, want_kl=False, want_target=False):
+    """Greedy calibrated re-ranking of device pools (amar_rerank_calibrated_f32): pool_items int32 [m, P] item rows (-1 padded),
+    pool_scores float32 [m, P], row j belonging to users[j] (int32 [m]; None: user j), the liked items as a CSR over users, the
+    categories as a CSR over items with values in 0..n_categories-1 (max_cat_row: its longest row).  Returns (items int32 [m, k],
+    scores float32 [m, k]) in selection order, followed by the step values float32 [m, k] (want_value), the miscalibration after
+    each step float32 [m, k] (want_kl) and the users' targets float32 [m, G] (want_target).  One launch, no workspace."""
+    m, P = _lists_matrix(pool_items, 'pool_items')
+    if _lists_matrix(pool_scores, 'pool_scores') != (m, P):
+        raise ValueError("rerank_calibrated: pool_items and pool_scores must have the same shape")
+    n_users, n_items = _calibrate_sizes('rerank_calibrated', m, users, liked_ptr, cat_ptr)
+    dev = pool_items.device
+    k, G = int(k), int(n_categories)
+    out_items = torch.empty((m, max(k, 0)), dtype=torch.int32, device=dev)
+    out_scores = torch.empty((m, max(k, 0)), dtype=torch.float32, device=dev)
+    out_value = torch.empty((m, max(k, 0)), dtype=torch.float32, device=dev) if want_value else None
+    out_kl = torch.empty((m, max(k, 0)), dtype=torch.float32, device=dev) if want_kl else None
+    out_target = torch.empty((m, max(G, 0)), dtype=torch.float32, device=dev) if want_target else None
+    _launch('amar_rerank_calibrated_f32', _ptr(pool_items, I32, 'pool_items') if m else None, _ptr(pool_scores, F32, 'pool_scores') if m else None,
+            m, P, _ptr(users, I32, 'users'), _ptr(liked_ptr, I32, 'liked_ptr'), _ptr_entries(liked_items, I32, 'liked_items'), n_users,
+            _ptr(cat_ptr, I32, 'cat_ptr'), _ptr_entries(cat_ids, I32, 'cat_ids'), n_items, G, int(max_cat_row), float(trade_off),
+            float(smoothing), k, _ptr(out_items) if m else None, _ptr(out_scores) if m else None, _ptr(out_value) if m else None,
+            _ptr(out_kl) if m else None, _ptr(out_target) if m else None)
+    return (out_items, out_scores) + tuple(t for t in (out_value, out_kl, out_target) if t is not None)
+
+
+def list_calibration(lists, liked_ptr, liked_items, cat_ptr, cat_ids, n_categories, ks, smoothing=0.01, users=None):
+    """Miscalibration of device lists (amar_list_calibration_f64): lists int32 [m, K] item rows (-1 padded) of users[j] (None: user
+    j), CSRs as in rerank_calibrated, cutoffs ks.  Returns (kl float64 [m, nk]: C(p, the first ks[q] ranks), 0 for a user without a
+    target; count int32 [m, nk]: the items with a category in those ranks; support int32 [m]: the user's liked items with a
+    category), all on the device."""
+    m, K = _lists_matrix(lists, 'lists')
+    n_users, n_items = _calibrate_sizes('list_calibration', m, users, liked_ptr, cat_ptr)
+    ks = [int(k) for k in ks]
+    dev = lists.device
+    out_kl = torch.empty((m, len(ks)), dtype=torch.float64, device=dev)
+    out_count = torch.empty((m, len(ks)), dtype=torch.int32, device=dev)
+    out_support = torch.empty((m,), dtype=torch.int32, device=dev)
+    ks_c = (ctypes.c_int32 * max(1, len(ks)))(*ks)
+    _launch('amar_list_calibration_f64', _ptr(lists, I32, 'lists') if m else None, m, K, _ptr(users, I32, 'users'),
+            _ptr(liked_ptr, I32, 'liked_ptr'), _ptr_entries(liked_items, I32, 'liked_items'), n_users, _ptr(cat_ptr, I32, 'cat_ptr'),
+            _ptr_entries(cat_ids, I32, 'cat_ids'), n_items, int(n_categories), float(smoothing), ks_c, len(ks),
+            _ptr(out_kl) if m else None, _ptr(out_count) if m else None, _ptr(out_support) if m else None)
+    return out_kl, out_count, out_support
 
 
 # ---- training step ----------------------------------------------------------------------------------------------

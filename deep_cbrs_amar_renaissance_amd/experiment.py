@@ -388,6 +388,8 @@ class Experimenter:
             self.write_similar_items(**dict(self.config.parameters.get('similar_items')))
         if self.config.parameters.get('diversify'):
             self.write_diverse(**dict(self.config.parameters.get('diversify')))
+        if self.config.parameters.get('calibrate'):
+            self.write_calibrated(**dict(self.config.parameters.get('calibrate')))
         if self.config.parameters.get('explain'):
             self.write_explanations(**dict(self.config.parameters.get('explain')))
         if self.config.parameters.get('group_recommend'):
@@ -447,6 +449,33 @@ class Experimenter:
         for prefix, lists in (('plain_', plain.contiguous()), ('diverse_', diverse)):
             if len(users):
                 logged.update({prefix + name: value for name, value in rec.diversity_metrics(lists, table, [k], metric, n_items).items()})
+        self.run_log.log_metrics(logged)
+        return path, logged
+
+    def write_calibrated(self, k=10, pool=50, trade_off=0.5, smoothing=0.01, categories=None):
+        """Opt-in (parameters.calibrate: {k, pool, trade_off, smoothing, categories}; categories null or an int): every user's `pool`
+        best unseen items re-ranked towards the categories of what the user liked (`recommend_calibrated()`), written as
+        <predictions_dest>/calibrated_top_<k>.tsv (user, item, score; original ids, selection order); the miscalibration at k of the
+        plain top-k and of the calibrated lists is logged as plain_ / calibrated_miscalibration_at_<k>."""
+        import torch
+        from deep_cbrs_amar_renaissance_amd import recommend as rec
+        k = int(k)
+        if categories is not None and (isinstance(categories, bool) or not isinstance(categories, int)):
+            raise ValueError("parameters.calibrate.categories must be null or an integer (got {!r})".format(categories))
+        users, items, scores = self.model.recommend_calibrated(self.trainset, k=k, pool=int(pool), trade_off=float(trade_off),
+                                                               smoothing=float(smoothing), categories=categories)
+        path = path_join(self.predictions_dest, "calibrated_top_{}.tsv".format(k))
+        recommendations_frame(users, items, scores, self.trainset.users, self.trainset.items).to_csv(
+            path, sep='\t', header=False, index=False)
+        n_users, n_items = len(self.trainset.users), len(self.trainset.items)
+        logged = {}
+        if len(users):
+            with rec.device_lists():
+                _, plain, _ = self.model.recommend(self.trainset, k=k)
+            calibrated = torch.from_numpy(np.where(items >= 0, items - n_users, -1).astype(np.int32)).to(plain.device)
+            liked, cats = rec._liked_device(self.trainset, n_users, n_items), rec._cats_device(self.trainset, n_items, categories)
+            for prefix, lists in (('plain_', plain.contiguous()), ('calibrated_', calibrated)):
+                logged.update({prefix + name: value for name, value in rec.calibration_metrics(lists, None, liked, cats, [k], smoothing).items()})
         self.run_log.log_metrics(logged)
         return path, logged
 

@@ -37,6 +37,11 @@ The fifth part answers "what should WE watch?": ``group_csr`` / ``group_exclusio
 by the mean, the minimum or the maximum, with an optional veto, and selected on chip: nothing of size members x |I| in memory),
 ``group_pairs`` the same arithmetic over pair-route scores for the heads without a fused kernel, and the mixin's
 ``recommend_group`` picks between them exactly as ``recommend()`` does.
+
+The sixth part keeps a list in proportion to its user's tastes: ``item_category_csr`` turns the item-property links (or a membership
+matrix) into the categories of ``amar_rerank_calibrated_f32``, ``rerank_calibrated`` is that one launch over device pools (the user's
+and the list's category distributions stay in LDS: nothing of size m x P x G in memory), the mixin's ``recommend_calibrated`` /
+``list_calibration`` run it and its float64 metric (``amar_list_calibration_f64``), and ``evaluate_ranking`` takes ``calibration=``.
 """
 import contextlib
 import weakref
@@ -140,10 +145,75 @@ def property_weights(df, n_items, kind='idf'):
     return np.where(df > 0, np.log(float(n_items) / np.maximum(df, 1.0)), 0.0).astype(np.float32)
 
 
+def _is_matrix(x):
+    return hasattr(x, 'tocoo') or (isinstance(x, np.ndarray) and x.ndim == 2)
+
+
+def item_category_csr(trainset, categories=None):
+    """The categories calibration works in, as a CSR over item rows: (ptr int64 [|I|+1], ids int64 category numbers 0..G-1 sorted and
+    de-duplicated per item, category_props int64 [G]: the property index of every category, max_row: the longest row).
+    categories=None: the min(|P|, MAX_G) properties of `item_property_csr` with the largest document frequency (only df > 0 counts;
+    ties to the smaller property index), numbered in ascending property index.  An int N: the N most frequent ones.  A sequence of
+    property indices (unique, in range, at most MAX_G of them): those, numbered in ascending property index.  A scipy-sparse or dense
+    0/1 membership matrix [|I|, G] (G <= MAX_G; category_props is then 0..G-1) serves trainsets without a property graph.
+    ValueError for anything else, and for a trainset that has no properties when no matrix is given."""
+    n_users, n_items = _sizes(trainset)
+    max_g = capi.CALIBRATE_MAX_G
+    if categories is not None and _is_matrix(categories):
+        if tuple(categories.shape) != (n_items, categories.shape[1]) or not 1 <= categories.shape[1] <= max_g:
+            raise ValueError("a category matrix must be [{} items, 1..{} categories] (got {})".format(n_items, max_g, tuple(categories.shape)))
+        if hasattr(categories, 'tocoo'):
+            coo = categories.tocoo()
+            keep = np.asarray(coo.data) != 0
+            it, g = coo.row[keep].astype(np.int64), coo.col[keep].astype(np.int64)
+        else:
+            it, g = (a.astype(np.int64) for a in np.nonzero(np.asarray(categories)))
+        G = int(categories.shape[1])
+        key = np.unique(it * G + g)
+        props = np.arange(G, dtype=np.int64)
+    else:
+        csr = item_property_csr(trainset)
+        if csr is None:
+            raise ValueError("the trainset has no item properties: pass `categories` as an [items, categories] membership matrix")
+        ptr, pr, df, _ = csr
+        n_props = len(df)
+        if categories is None or (isinstance(categories, (int, np.integer)) and not isinstance(categories, bool)):
+            want = max_g if categories is None else int(categories)
+            if not 1 <= want <= max_g:
+                raise ValueError("categories must be an integer in [1, {}] (got {!r})".format(max_g, categories))
+            order = np.lexsort((np.arange(n_props), -df))                # df descending, property index ascending
+            props = np.sort(order[:want][df[order[:want]] > 0]).astype(np.int64)
+        else:
+            try:
+                props = list(categories)
+            except TypeError:
+                props = None
+            if props is None or np.ndim(props) != 1:                      # a nested list is no matrix: an ndarray or a scipy matrix is
+                raise ValueError("categories must be None, an integer, a sequence of property indices or a membership matrix")
+            try:
+                props = check_ids(props, 0, n_props, 'categories')
+            except TypeError:
+                raise ValueError("categories must be None, an integer, a sequence of property indices or a membership matrix")
+            if len(props) > max_g or len(np.unique(props)) != len(props):
+                raise ValueError("categories must be at most {} distinct property indices".format(max_g))
+            props = np.sort(props)
+        if len(props) == 0:
+            raise ValueError("no property is linked to any item: there is no category to calibrate on")
+        G = len(props)
+        number = np.full(n_props, -1, dtype=np.int64)
+        number[props] = np.arange(G)
+        it = np.repeat(np.arange(n_items, dtype=np.int64), np.diff(ptr))
+        g = number[pr]
+        key = (it * G + g)[g >= 0]                                        # already sorted by (item, category): props ascending
+    ptr = np.zeros(n_items + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key // G, minlength=n_items), out=ptr[1:])
+    return ptr, key % G, props, int(np.diff(ptr).max()) if n_items else 0
+
+
 # Exclusion, liked and property CSRs on the device, built once per ratings array / graph (held weakly where the object allows it: a
 # dropped trainset frees its entries).  The key is the object's identity: an array or graph mutated in place is not noticed, and the
 # finalizer of a dead object whose id was reused may drop the new object's entry, which only costs a rebuild.
-_EXCL_CACHE, _LIKED_CACHE, _PROP_CACHE = {}, {}, {}
+_EXCL_CACHE, _LIKED_CACHE, _PROP_CACHE, _CAT_CACHE = {}, {}, {}, {}
 
 
 def _device_cached(cache, obj, key, build):
@@ -196,6 +266,30 @@ def _props_device(trainset, n_items, kind):
     return _device_cached(_PROP_CACHE, adj, (id(adj), n_items, kind, str(dev)), build)
 
 
+def _cats_device(trainset, n_items, categories):
+    """(cat_ptr, cat_ids) on the device, the number of categories and the longest row, cached per graph (or per membership matrix)
+    and category choice; the ValueErrors of `item_category_csr`."""
+    dev = default_device()
+    if categories is not None and _is_matrix(categories):
+        obj, choice = categories, 'matrix'
+    else:
+        obj = getattr(trainset, 'adj_matrix', None)
+        choice = categories
+        if not (categories is None or (isinstance(categories, (int, np.integer)) and not isinstance(categories, bool))):
+            try:
+                choice = repr(list(categories))                           # [1.0] is not [1]: a hit must not skip the checks
+            except TypeError:
+                choice, obj = None, None                                  # not a sequence: item_category_csr says so
+    if obj is None:
+        item_category_csr(trainset, categories)                           # raises: nothing to hold an entry for
+        raise ValueError("the trainset has no graph to take categories from")
+
+    def build():
+        ptr, ids, props, max_row = item_category_csr(trainset, categories)
+        return torch.from_numpy(ptr.astype(np.int32)).to(dev), torch.from_numpy(ids.astype(np.int32)).to(dev), len(props), max_row
+    return _device_cached(_CAT_CACHE, obj, (id(obj), n_items, choice, str(dev)), build)
+
+
 def _sizes(trainset):
     return len(trainset.users), len(trainset.items)
 
@@ -218,12 +312,15 @@ def device_lists():
         _ON_DEVICE = saved
 
 
-def evaluate_ranking(model, trainset, test_ratings, ks, users=None, exclude_seen=True, diversity=None):
+def evaluate_ranking(model, trainset, test_ratings, ks, users=None, exclude_seen=True, diversity=None, calibration=None):
     """model.recommend at k = max(ks) with the lists kept on the device, then utilities.metrics.full_ranking_metrics_device: the
     dict of `full_ranking_metrics(*model.recommend(...)[:2], test_ratings, ks)` without the lists (or a Python loop) on the host.
     diversity={'metric': 'cosine' | 'dot', 'space': ...} (both optional) adds, for every k, 'ild_at_<k>' (the float64 mean, over the
     lists with at least two items in their first k ranks, of the intra-list diversity of those ranks in the model's item `space`:
-    amar_list_diversity_f64) and 'item_coverage_at_<k>' (the distinct items in the first k ranks of all lists over |I|)."""
+    amar_list_diversity_f64) and 'item_coverage_at_<k>' (the distinct items in the first k ranks of all lists over |I|).
+    calibration={'smoothing': 0.01, 'categories': None} (both optional) adds 'miscalibration_at_<k>': the float64 mean, over the users
+    that have a target, of C(p, the first k ranks) (amar_list_calibration_f64; categories as in `item_category_csr`), 0 when no user
+    has one."""
     from deep_cbrs_amar_renaissance_amd.utilities.metrics import full_ranking_metrics, full_ranking_metrics_device
     ks = [int(k) for k in ks]
     if not ks:
@@ -233,7 +330,13 @@ def evaluate_ranking(model, trainset, test_ratings, ks, users=None, exclude_seen
         if unknown:
             raise ValueError("diversity takes the keys 'metric' and 'space' (got {})".format(sorted(unknown)))
         check_metric(diversity.get('metric', 'cosine'))
+    if calibration is not None:
+        unknown = set(calibration) - {'smoothing', 'categories'}
+        if unknown:
+            raise ValueError("calibration takes the keys 'smoothing' and 'categories' (got {})".format(sorted(unknown)))
+        check_smoothing(calibration.get('smoothing', 0.01))
     n_users, n_items = _sizes(trainset)
+    cats = _cats_device(trainset, n_items, calibration.get('categories')) if calibration is not None else None
     with device_lists():
         u, items, _ = model.recommend(trainset, k=check_k(max(ks)), users=users, exclude_seen=exclude_seen)
     if len(u) == 0:
@@ -241,13 +344,28 @@ def evaluate_ranking(model, trainset, test_ratings, ks, users=None, exclude_seen
         if diversity is not None:
             for k in ks:
                 out['ild_at_{}'.format(k)], out['item_coverage_at_{}'.format(k)] = 0.0, 0.0
+        if calibration is not None:
+            for k in ks:
+                out['miscalibration_at_{}'.format(k)] = 0.0
         return out
     items = items.contiguous()
     out = full_ranking_metrics_device(None if users is None else u, items, test_ratings, ks, n_users, n_items)
     if diversity is not None:
         table = model._item_embeddings(trainset, diversity.get('space'))
         out.update(diversity_metrics(items, table, ks, diversity.get('metric', 'cosine'), n_items))
+    if calibration is not None:
+        u_dev = None if users is None else torch.from_numpy(u.astype(np.int32)).to(items.device)
+        out.update(calibration_metrics(items, u_dev, _liked_device(trainset, n_users, n_items), cats, ks, calibration.get('smoothing', 0.01)))
     return out
+
+
+def calibration_metrics(lists, users, liked, cats, ks, smoothing=0.01):
+    """{'miscalibration_at_<k>'} of device lists (int32 [m, K] item rows, -1 padded) of `users` (int32 [m] on the device, None = the
+    identity): C per list from amar_list_calibration_f64 (`liked` = the liked CSR on the device, `cats` = `_cats_device`), averaged
+    in float64 over the users that have a target (0 when none has)."""
+    kl, _, support = capi.list_calibration(lists, liked[0], liked[1], cats[0], cats[1], cats[2], ks, smoothing=check_smoothing(smoothing), users=users)
+    kl, has = kl.cpu().numpy(), support.cpu().numpy() > 0
+    return {'miscalibration_at_{}'.format(k): float(kl[has, q].mean()) if has.any() else 0.0 for q, k in enumerate(ks)}
 
 
 def diversity_metrics(lists, table, ks, metric, n_items):
@@ -432,6 +550,36 @@ def rerank_mmr(items, scores, table, k, trade_off=0.7, metric='cosine'):
     table = _as_device_matrix(table, items.device, 'table')
     return capi.rerank_mmr(items.to(torch.int32).contiguous(), scores.to(torch.float32).contiguous(), table, k,
                            trade_off=trade_off, metric=metric)
+
+
+def check_smoothing(smoothing):
+    if isinstance(smoothing, bool) or not isinstance(smoothing, (int, float, np.integer, np.floating)) or not 0.0 < float(np.float32(smoothing)) < 1.0:
+        raise ValueError("smoothing must be a number in (0, 1) (got {!r})".format(smoothing))
+    return float(smoothing)
+
+
+def check_pool(pool, k):
+    if isinstance(pool, bool) or not isinstance(pool, (int, np.integer)) or not k <= int(pool) <= K_MAX:
+        raise ValueError("pool must be an integer in [k = {}, {}] (got {!r})".format(k, K_MAX, pool))
+    return int(pool)
+
+
+def rerank_calibrated(items, scores, users, liked, cats, k, trade_off=0.5, smoothing=0.01):
+    """Greedy calibrated re-ranking over device pools, one amar_rerank_calibrated_f32 launch: `items` int32 [m, P] item rows (-1
+    padded; P <= 64), `scores` float32 [m, P], `users` int32 [m] on the device or None for the identity, `liked` = (ptr, items) of
+    `liked_csr` on the device, `cats` = (ptr, ids, G, longest row) of `item_category_csr` on the device.  Every step takes the
+    candidate that maximises trade_off * rel - (1 - trade_off) * C(p, chosen + candidate): rel the scores min-max normalised per
+    pool, C the smoothed Kullback-Leibler distance between the categories of what the user liked and of the list; ties to the
+    smaller pool position.  Returns the device tensors (items int32 [m, k] in selection order, -1 padded; scores float32 [m, k]:
+    the pool's own scores of the chosen items, -inf padded)."""
+    k = check_k(k)
+    trade_off, smoothing = check_trade_off(trade_off), check_smoothing(smoothing)
+    if items.dim() != 2 or tuple(items.shape) != tuple(scores.shape):
+        raise ValueError("items and scores must be [m, P] tensors of the same shape")
+    if not k <= int(items.shape[1]) <= K_MAX:
+        raise ValueError("the pools must hold between k = {} and {} candidates (got {})".format(k, K_MAX, int(items.shape[1])))
+    return capi.rerank_calibrated(items.to(torch.int32).contiguous(), scores.to(torch.float32).contiguous(), liked[0], liked[1],
+                                  cats[0], cats[1], cats[2], k, trade_off=trade_off, smoothing=smoothing, users=users, max_cat_row=cats[3])
 
 
 def _item_rows_device(items, n_users, n_items, device, rows=None, widths=None):
@@ -793,6 +941,51 @@ class SimilarSearch:
         if _ON_DEVICE:
             return ild, count
         return ild.cpu().numpy(), count.cpu().numpy()
+
+    # -- calibrated lists (amar_rerank_calibrated_f32, amar_list_calibration_f64) -----------------------------------------
+    def recommend_calibrated(self, trainset, k=10, pool=50, trade_off=0.5, smoothing=0.01, categories=None, users=None, exclude_seen=True):
+        """Calibrated top-k (Steck 2018): the `pool` best items of every user (`recommend(k=pool)`, kept on the device) re-ranked so
+        that the list's categories follow the categories of what the user liked in training (`rerank_calibrated`: trade_off = 1 is
+        `recommend(k)` itself, smaller values weigh the proportion more; `categories` as in `item_category_csr`).  A user without a
+        liked item that has a category keeps the score order.  Returns (users int64 [m], items int64 [m, k] node ids in SELECTION
+        order (-1 padded), scores float32 [m, k]: the model's own scores of the chosen items (-inf padded)); inside
+        ``device_lists()`` the device tensors (item rows int32)."""
+        k = check_k(k)
+        trade_off, smoothing, pool = check_trade_off(trade_off), check_smoothing(smoothing), check_pool(pool, k)
+        n_users, n_items = _sizes(trainset)
+        cats = _cats_device(trainset, n_items, categories)
+        with device_lists():
+            u, items, scores = self.recommend(trainset, k=pool, users=users, exclude_seen=exclude_seen)
+        if len(u) == 0:
+            return _empty(k)
+        u_dev = None if users is None else torch.from_numpy(u.astype(np.int32)).to(items.device)
+        items, scores = rerank_calibrated(items, scores, u_dev, _liked_device(trainset, n_users, n_items), cats, k,
+                                          trade_off=trade_off, smoothing=smoothing)
+        return _finish(u, items, scores, n_users)
+
+    def list_calibration(self, trainset, items, users=None, ks=None, smoothing=0.01, categories=None):
+        """Miscalibration of lists of items against their users' liked training items: `items` [m, K] node ids (host, -1 padded: what
+        `recommend` returns) or, inside ``device_lists()``, int32 item rows on the device, one row per user of `users` (all users by
+        default); `ks` the cutoffs (K alone by default).  Returns (kl float64 [m, nk]: C(p, the first ks[q] ranks), 0 for a user
+        without a target; count int32 [m, nk]: the items with a category in those ranks; support int32 [m]: the user's liked items
+        with a category) — host arrays, device tensors inside ``device_lists()``."""
+        smoothing = check_smoothing(smoothing)
+        n_users, n_items = _sizes(trainset)
+        u = check_users(users, n_users)
+        cats = _cats_device(trainset, n_items, categories)
+        if isinstance(items, torch.Tensor) and items.is_cuda:
+            lists = items.to(torch.int32)
+        else:
+            lists = _item_rows_device(items, n_users, n_items, default_device())
+        if lists.dim() != 2 or int(lists.shape[0]) != len(u):
+            raise ValueError("items must be a 2-D [m, K] array with one row per user ({} rows for {} users)".format(int(lists.shape[0]), len(u)))
+        ks, _ = capi.rank_metrics_args(int(lists.shape[1]), [int(lists.shape[1])] if ks is None else ks)
+        u_dev = None if users is None else torch.from_numpy(u.astype(np.int32)).to(lists.device)
+        liked = _liked_device(trainset, n_users, n_items)
+        out = capi.list_calibration(lists.contiguous(), liked[0], liked[1], cats[0], cats[1], cats[2], ks, smoothing=smoothing, users=u_dev)
+        if _ON_DEVICE:
+            return out
+        return tuple(t.cpu().numpy() for t in out)
 
     # -- explanations (amar_explain_f32) --------------------------------------------------------------------------------
     def explain(self, trainset, users=None, items=None, k=10, n_evidence=3, n_properties=3, metric='cosine', space=None,

@@ -177,6 +177,69 @@ def intra_list_diversity(lists, vectors, ks=None, metric='cosine'):
     return ild, count
 
 
+def miscalibration(lists, users, liked, cats, ks=None, smoothing=0.01):
+    """Miscalibration (Steck 2018) on the host, in float64 (what amar_list_calibration_f64 computes on the device): `lists` [m, K]
+    item ROWS, -1 padded, row j belonging to users[j] (None: user j); `liked` = (ptr, items), the liked items as a CSR over users
+    (recommend.liked_csr); `cats` = (ptr, ids, ...), the categories as a CSR over item rows (recommend.item_category_csr).  With
+    p(g) = the mean over the user's liked items that have a category of 1/len_i on the categories of item i, and q(g) the same mean
+    over the items with a category in the first k ranks (0 when there is none),
+        C = sum over p(g) > 0, g ascending, of p(g) log(p(g) / ((1 - a) q(g) + a p(g))),    a = smoothing as a float32 (the C ABI's),
+    for every cutoff k of `ks` (K alone by default); 0 for a user without a liked item that has a category.  The sums run liked item
+    ascending, rank ascending and g ascending.  Returns (kl float64 [m, nk], count int64 [m, nk]: the items with a category in the
+    first k ranks, support int64 [m]: the user's liked items with a category)."""
+    lists = np.asarray(lists, dtype=np.int64)
+    if lists.ndim != 2:
+        raise ValueError("lists must be a 2-D [m, K] array")
+    m, K = lists.shape
+    ks = [int(K)] if ks is None else [int(k) for k in ks]
+    if any(k < 1 or k > K for k in ks):
+        raise ValueError("every k must lie in [1, {}] (the length of the lists)".format(K))
+    alpha = float(np.float32(smoothing))
+    if not 0.0 < alpha < 1.0:
+        raise ValueError("smoothing must lie in (0, 1) (got {!r})".format(smoothing))
+    l_ptr, l_items = np.asarray(liked[0], dtype=np.int64), np.asarray(liked[1], dtype=np.int64)
+    c_ptr, c_ids = np.asarray(cats[0], dtype=np.int64), np.asarray(cats[1], dtype=np.int64)
+    n_items, G = len(c_ptr) - 1, int(c_ids.max()) + 1 if len(c_ids) else 1
+    users = np.arange(m, dtype=np.int64) if users is None else np.asarray(users, dtype=np.int64).reshape(-1)
+    if len(users) != m:
+        raise ValueError("users must name one user per list")
+    oma = 1.0 - alpha
+    kl = np.zeros((m, len(ks)), dtype=np.float64)
+    count = np.zeros((m, len(ks)), dtype=np.int64)
+    support = np.zeros(m, dtype=np.int64)
+
+    def add_rows(acc, items):
+        added = []
+        for i in items:
+            row = c_ids[c_ptr[i]:c_ptr[i + 1]] if 0 <= i < n_items else c_ids[:0]
+            if len(row):
+                acc[row] += 1.0 / len(row)                    # the ids of a row are distinct
+            added.append(len(row) > 0)
+        return added
+
+    for j, u in enumerate(users):
+        if not 0 <= u < len(l_ptr) - 1:
+            continue
+        p = np.zeros(G, dtype=np.float64)
+        support[j] = sum(add_rows(p, l_items[l_ptr[u]:l_ptr[u + 1]]))
+        full = np.cumsum(add_rows(np.zeros(G), lists[j]))       # the items with a category among the first r + 1 ranks
+        if support[j]:
+            p /= float(support[j])
+        has = np.nonzero(p > 0)[0]
+        for q, k in enumerate(ks):
+            count[j, q] = full[k - 1]
+            if not support[j]:
+                continue
+            n = np.zeros(G, dtype=np.float64)
+            add_rows(n, lists[j, :k])
+            qg = n / float(count[j, q]) if count[j, q] else n
+            c = 0.0
+            for t in (p[has] * np.log(p[has] / (oma * qg[has] + alpha * p[has]))).tolist():
+                c += t
+            kl[j, q] = c
+    return kl, count, support
+
+
 def relevant_csr(test_ratings, n_users, n_items):
     """The relevant (label 1) pairs of `test_ratings` as a CSR over users: (ptr int64 [n_users + 1], item ROWS int64, sorted and
     de-duplicated per user) — recommend.exclusion_csr over the liked pairs only."""

@@ -1432,6 +1432,76 @@ int amar_explain_f32(const int32_t *lists, int64_t m, int32_t K, const int32_t *
                      float *out_evidence_sim, int32_t *out_props, float *out_prop_score, int32_t *out_prop_support,
                      amar_stream_t stream);
 
+/* Calibrated re-ranking (Steck, "Calibrated recommendations", RecSys 2018): keep a list in proportion to the categories of what its
+ * user liked, and measure how far a finished list is from that proportion.
+ *
+ * Categories: a CSR over item rows, cat_ptr[n_items+1] and cat_ids, every row sorted ascending and de-duplicated, values in 0..G-1,
+ * 1 <= G <= AMAR_CALIBRATE_MAX_G.  len_i is the length of row i and p(g|i) = 1/len_i for g in row i; an item with an empty row is
+ * NEUTRAL: it has no distribution.
+ * User target: L(u) is the liked segment of u (the liked CSR of amar_explain_f32: liked_ptr[n_users+1], liked_items sorted ascending
+ * and de-duplicated per user), L+(u) its items with a non-empty row, support(u) = |L+(u)|,
+ *     psum(g) = sum over i in L+(u), item row ascending, of 1/len_i        p(g) = psum(g) / support(u);
+ * a user with support 0 has no target.
+ * List distribution: for the chosen items S in selection order, S+ the non-neutral ones,
+ *     n(g) = sum over i in S+, selection order, of 1/len_i                  q(g) = n(g) / |S+|, 0 everywhere when S+ is empty.
+ * Miscalibration, with the smoothing a (0 < a < 1):
+ *     C(p, S) = sum over the g with p(g) > 0, g ascending, of  p(g) log( p(g) / ((1 - a) q(g) + a p(g)) ),
+ * 0 <= C <= log(1/a), and C = log(1/a) when S+ is empty.
+ *
+ * amar_rerank_calibrated_f32: list j of m has the candidates pool_items[j, 0:P] (int32 item rows, -1 = padding, no duplicates among
+ * the valid entries: a precondition) with the model's scores pool_scores[j, 0:P] (finite on valid entries; the pool need not be
+ * sorted) and belongs to user users[j] (j itself when users == NULL, m == n_users).
+ *   - rel_t is the min-max normalised score of amar_rerank_mmr_f32: (r_t - r_min) / (r_max - r_min) over the valid entries, 1
+ *     everywhere when r_max == r_min.
+ *   - every step s >= 0, step 0 included, picks among the valid unselected positions t
+ *         argmax v_t,   v_t = trade_off * rel_t - (1 - trade_off) * C(p, S + {t}),
+ *     ties to the smaller pool position.  When 1 - trade_off is 0, or the user has no target (C then counts as 0), the steps compare
+ *     the scores r_t themselves: the score order, position ascending on ties.
+ *   - steps beyond the number of valid entries write -1 / -inf; a user id outside 0..n_users-1 writes padding for the whole list
+ *     (and a target of zeros).
+ *   - out_items [m, k]: the chosen item rows in selection order; out_scores [m, k]: their pool_scores, unmodified bits;
+ *     out_value [m, k] (optional, may be NULL): the v values; out_kl [m, k] (optional): C after each step; out_target [m, G]
+ *     (optional): p, zeros for a user without a target.
+ * Arithmetic, part of the contract: float32 throughout.  1/len_i is the correctly rounded quotient; psum and n are sequential
+ * additions in the orders above; p = psum / support is one division; a is the float32 argument and 1 - a one float32 subtraction;
+ * a cell's term is p * logf(p / fmaf(1 - a, x / N, a * p)) with x = n(g) and N = |S+| (x / N = 0 when N is 0), logf the accurate one
+ * (no fast-math).  Per step the terms of all g are added once for N = |S+| and once for N = |S+| + 1 (lane l adds g = l, l + 64, ...
+ * in that order, then a 6-level xor butterfly over the 64 lanes); a non-neutral candidate adds to the second sum, for the cells of
+ * its row with p > 0 in row order, term(x + 1/len_t) - term(x); a neutral candidate takes the first sum.  out_target therefore has
+ * the bits of a float32 loop on the host.
+ * A list's result depends on its own row of the inputs, its user's liked segment, the touched category rows, trade_off, smoothing
+ * and k only: not on m, the other lists or the grid; a call returns the same bits on every run (no atomics, in LDS either).  One
+ * launch, one wavefront per list, no workspace: nothing of size m x P x G reaches memory.  p and n live in LDS; the pool's category
+ * rows are staged there, position after position, while they fit AMAR_CALIBRATE_POOL_BUDGET entries together, and the positions past
+ * that read their rows from memory: nothing is truncated.
+ * max_cat_row: the longest row of the category CSR.  The host refuses a value that no valid CSR can have (negative; above G, since
+ * a row is de-duplicated) and the kernel does not otherwise use it: whatever the caller states, a pool row is read up to G entries
+ * only and an id outside 0..G-1 is skipped, so that LDS is never overrun; a CSR that breaks the rules above gives an undefined
+ * result, not an error.  Pool or liked items outside 0..n_items-1 are padding and are never read.
+ * Limits: 1 <= k <= P <= AMAR_CALIBRATE_MAX_P, G <= AMAR_CALIBRATE_MAX_G, max_cat_row <= G; else AMAR_EUNSUPPORTED.  NULL pointers
+ * (out_value / out_kl / out_target and users excepted; the pools and outputs may be NULL when m == 0), negative sizes, P < 1, k < 1, G < 1, trade_off outside [0, 1] or smoothing
+ * outside (0, 1) (NaN included), users == NULL with m != n_users: AMAR_EINVAL.  All of these are checked before any device call.
+ *
+ * amar_list_calibration_f64: lists [m, K] (int32 item rows, -1 padded, K <= 64) of users[j] (NULL as above), HOST cutoffs ks[nk]
+ * (1 <= ks[q] <= K, nk <= AMAR_RANK_METRICS_MAX_KS).  out_kl [m, nk] (double) = C(p, the first ks[q] ranks) entirely in float64:
+ * 1.0/len, the sums in the orders above, p = psum / support, a = (double)smoothing, the accurate log, g ascending; 0 for a user
+ * without a target.  out_count [m, nk] (int32): the non-neutral valid items in those ranks; out_support [m] (int32): |L+(u)|, 0 for
+ * a user id outside 0..n_users-1 (whose row is otherwise zeros).  Limits and refusals as above (K in place of P; nk < 1 or a cutoff
+ * outside [1, K]: AMAR_EINVAL; nk > AMAR_RANK_METRICS_MAX_KS: AMAR_EUNSUPPORTED).  One wavefront per list, the same bits on every
+ * run. */
+#define AMAR_CALIBRATE_MAX_P       64
+#define AMAR_CALIBRATE_MAX_G       1024
+#define AMAR_CALIBRATE_POOL_BUDGET 4096
+int amar_rerank_calibrated_f32(const int32_t *pool_items, const float *pool_scores, int64_t m, int32_t P, const int32_t *users,
+                               const int32_t *liked_ptr, const int32_t *liked_items, int32_t n_users, const int32_t *cat_ptr,
+                               const int32_t *cat_ids, int32_t n_items, int32_t G, int32_t max_cat_row, float trade_off,
+                               float smoothing, int32_t k, int32_t *out_items, float *out_scores, float *out_value, float *out_kl,
+                               float *out_target, amar_stream_t stream);
+int amar_list_calibration_f64(const int32_t *lists, int64_t m, int32_t K, const int32_t *users, const int32_t *liked_ptr,
+                              const int32_t *liked_items, int32_t n_users, const int32_t *cat_ptr, const int32_t *cat_ids,
+                              int32_t n_items, int32_t G, float smoothing, const int32_t *ks, int32_t nk, double *out_kl,
+                              int32_t *out_count, int32_t *out_support, amar_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
