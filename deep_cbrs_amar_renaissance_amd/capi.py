@@ -161,6 +161,10 @@ SIGNATURES = {
     'amar_nearest_workspace_floats': (ctypes.c_int64, [_I64, _I32, _I32, _I32, _I32]),
     'amar_nearest_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _P, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     'amar_rank_metrics_f64': (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P]),
+    'amar_rank_of_slices': (ctypes.c_int32, [_I64, _I32, _P, _I32, _I32]),
+    'amar_rank_of_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P,
+                                        _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
+    'amar_rank_of_metrics_f64': (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _P]),
     'amar_rerank_mmr_f32': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _F32, _I32, _P, _P, _P, _P, _P]),
     'amar_list_diversity_f64': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _P]),
     'amar_explain_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, _I32, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _I32, _I32,
@@ -1584,6 +1588,94 @@ def rank_metrics(lists, rel_ptr, rel_items, ks, users=None):
     evaluated, skipped = (int(c) for c in counts.cpu().numpy())
     sums = sums.cpu().numpy()
     return (sums / evaluated if evaluated else sums), evaluated, skipped
+
+
+RANK_OF_MAX_TARGETS = 64                                               # include/amar_hip.h: AMAR_RANK_OF_MAX_TARGETS
+
+
+def rank_of_entries(users, tgt_ptr, max_targets=RANK_OF_MAX_TARGETS):
+    """Entries of at most `max_targets` targets from rows of any length: (users int32 [m'], tgt_ptr int32 [m' + 1]) on the host.  A
+    row of n targets becomes ceil(n / max_targets) consecutive entries of the same user (an empty row: none), so the flat order of
+    the targets, and with it of the outputs, is the caller's."""
+    import numpy as np
+    users = np.asarray(users, dtype=np.int64).reshape(-1)
+    ptr = np.asarray(tgt_ptr, dtype=np.int64).reshape(-1)
+    if len(ptr) != len(users) + 1 or (len(ptr) and ptr[0] != 0) or (np.diff(ptr) < 0).any():
+        raise ValueError("rank_of: tgt_ptr must be a CSR pointer over the listed users ({} users, {} entries)".format(len(users), len(ptr)))
+    n = np.diff(ptr)
+    pieces = (n + max_targets - 1) // max_targets
+    owner = np.repeat(np.arange(len(users)), pieces)
+    first = np.cumsum(pieces) - pieces
+    start = ptr[:-1][owner] + (np.arange(len(owner)) - first[owner]) * max_targets
+    out_ptr = np.append(start, ptr[-1] if len(ptr) else 0)
+    return users[owner].astype(np.int32), out_ptr.astype(np.int32)
+
+
+def rank_of(Tu, Ti, wpack, dims, acts, in_act, users, tgt_ptr, tgt_items, excl_ptr=None, excl_items=None, n_slices=0, split=True):
+    """Exact full-catalogue positions by counting (amar_rank_of_f32).  `users` (rows of Tu, host integers [m]; the same user may be
+    listed more than once) and `tgt_ptr` [m + 1] / `tgt_items` (host integers: the item rows asked about per listed user, ascending
+    and distinct inside a row) name the pairs; the exclusion CSR over the rows of Tu is on the device, as for `recommend`.  Rows
+    longer than RANK_OF_MAX_TARGETS are cut into several entries of the same user (`rank_of_entries`; split=False hands them to the
+    library as they are, which refuses them).  Returns the device tensors (scores float32, greater int32, eq_before int32,
+    eq_after int32), one value per target in the order of `tgt_items`: 1 + greater + eq_before is the item's position in the user's
+    full ranking (score descending, item row ascending) among the items outside the user's exclusion row.
+    n_slices <= 0: the library's automatic item slicing."""
+    import numpy as np
+    n_users, c1 = int(Tu.shape[0]), int(Tu.shape[1])
+    n_items = int(Ti.shape[0])
+    if int(Ti.shape[1]) != c1:
+        raise ValueError("rank_of: Tu and Ti must have the same width")
+    if (excl_ptr is None) != (excl_items is None):
+        raise ValueError("rank_of: excl_ptr and excl_items go together")
+    if excl_ptr is not None and excl_ptr.numel() != n_users + 1:
+        raise ValueError("rank_of: excl_ptr must have n_users + 1 entries")
+    items = np.ascontiguousarray(np.asarray(tgt_items).reshape(-1), dtype=np.int32)
+    if split:
+        users_h, ptr_h = rank_of_entries(users, tgt_ptr)
+    else:
+        users_h, ptr_h = np.asarray(users, dtype=np.int32).reshape(-1), np.asarray(tgt_ptr, dtype=np.int32).reshape(-1)
+        if len(ptr_h) != len(users_h) + 1:
+            raise ValueError("rank_of: tgt_ptr must have one entry per listed user plus one")
+    m, n_targets = len(users_h), len(items)
+    if (int(ptr_h[-1]) if len(ptr_h) else 0) != n_targets:
+        raise ValueError("rank_of: tgt_ptr must end at the number of targets ({} != {})".format(int(ptr_h[-1]) if len(ptr_h) else 0, n_targets))
+    if m and (users_h.min() < 0 or users_h.max() >= n_users):
+        raise ValueError("rank_of: users must be rows of Tu")
+    if n_targets and (items.min() < 0 or items.max() >= n_items):
+        raise ValueError("rank_of: targets must be rows of Ti")
+    dev = Tu.device
+    _ptr(Tu, F32, 'Tu')                                                # (a host tensor is refused before anything is allocated beside it)
+    scores = torch.empty(n_targets, dtype=torch.float32, device=dev)
+    greater, before, after = (torch.empty(n_targets, dtype=torch.int32, device=dev) for _ in range(3))
+    dims_c = (ctypes.c_int32 * len(dims))(*dims)
+    acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
+    users_d, ptr_d, items_d = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (users_h, ptr_h, items))
+    longest = int(np.diff(ptr_h.astype(np.int64)).max()) if m else 0
+    _launch('amar_rank_of_f32', *_mat(Tu, 'Tu'), n_users, *_mat(Ti, 'Ti'), n_items, c1, _ptr(wpack, F32, 'wpack'), dims_c, acts_c, len(acts),
+            ACT_CODES[in_act], _ptr_entries(users_d, I32, 'users'), m, _ptr(excl_ptr, I32, 'excl_ptr'), _ptr_entries(excl_items, I32, 'excl_items'),
+            _ptr(ptr_d, I32, 'tgt_ptr'), _ptr_entries(items_d, I32, 'tgt_items'), n_targets, longest, int(n_slices) if n_slices > 0 else 0,
+            _ptr_entries(scores, F32, 'scores'), _ptr_entries(greater, I32, 'greater'), _ptr_entries(before, I32, 'eq_before'),
+            _ptr_entries(after, I32, 'eq_after'))
+    return scores, greater, before, after
+
+
+def rank_of_metrics(scores, greater, eq_before, eq_after, rel_ptr, n_cand):
+    """AUC, reciprocal rank and average precision per evaluated user from `rank_of`'s flat outputs (amar_rank_of_metrics_f64):
+    rel_ptr int32 [n_eval + 1] cuts the flat order into the users' held-out items, n_cand int32 [n_eval] = the items outside each
+    user's exclusion row.  Returns the device tensors (out float64 [n_eval, 3]: auc, rr, ap; valid int32 [n_eval]: 0 for a user
+    without a target or without a candidate that is not one)."""
+    n_eval, n_targets = int(rel_ptr.numel()) - 1, int(scores.numel())
+    if n_eval < 0 or int(n_cand.numel()) != n_eval:
+        raise ValueError("rank_of_metrics: rel_ptr must have one entry per evaluated user plus one, n_cand one per user")
+    if any(int(t.numel()) != n_targets for t in (greater, eq_before, eq_after)):
+        raise ValueError("rank_of_metrics: scores, greater, eq_before and eq_after must have one value per target")
+    dev = rel_ptr.device
+    out = torch.empty((n_eval, 3), dtype=torch.float64, device=dev)
+    valid = torch.empty(n_eval, dtype=torch.int32, device=dev)
+    _launch('amar_rank_of_metrics_f64', _ptr_entries(scores, F32, 'scores'), _ptr_entries(greater, I32, 'greater'),
+            _ptr_entries(eq_before, I32, 'eq_before'), _ptr_entries(eq_after, I32, 'eq_after'), n_targets, _ptr(rel_ptr, I32, 'rel_ptr'),
+            _ptr_entries(n_cand, I32, 'n_cand'), n_eval, _ptr_entries(out, torch.float64, 'out'), _ptr_entries(valid, I32, 'valid'))
+    return out, valid
 
 
 DIVERSIFY_MAX_P = 64                                                   # include/amar_hip.h: AMAR_DIVERSIFY_MAX_P

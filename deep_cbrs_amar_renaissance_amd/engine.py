@@ -385,17 +385,18 @@ class Model(Layer):
                     raise ValueError("load_weights: {} is {} in the archive, {} in the model".format(name, tuple(value.shape), tuple(prm.shape)))
                 prm.copy_(torch.from_numpy(np.ascontiguousarray(value, dtype=np.float32)).to(prm.device))
 
-    def evaluate_ranking(self, trainset, test_ratings, ks, users=None, exclude_seen=True, diversity=None, calibration=None):
+    def evaluate_ranking(self, trainset, test_ratings, ks, users=None, exclude_seen=True, diversity=None, calibration=None, rank_metrics=None):
         """Full-ranking Precision / Recall / NDCG / HitRate @k for every k of `ks`: `recommend(trainset, k=max(ks), users, exclude_seen)`
         scored against the label-1 pairs of `test_ratings` ([P, 3]: user index, item node id, label) on the device — the lists never
         reach the host.  Returns the dict of utilities.metrics.full_ranking_metrics; diversity={'metric', 'space'} adds 'ild_at_<k>' and
-        'item_coverage_at_<k>', calibration={'smoothing', 'categories'} adds 'miscalibration_at_<k>' (recommend.evaluate_ranking).  Models
-        without recommend(): NotImplementedError."""
+        'item_coverage_at_<k>', calibration={'smoothing', 'categories'} adds 'miscalibration_at_<k>', rank_metrics=('auc', 'mrr', 'map')
+        (any subset; `ks` may then be empty) adds those cut-off-free measures from the exact rank of every held-out item and
+        'rank_metrics_users' = (evaluated, skipped) (recommend.evaluate_ranking).  Models without recommend(): NotImplementedError."""
         if not hasattr(self, 'recommend'):
             raise NotImplementedError("{} has no recommend(): no full-ranking evaluation".format(type(self).__name__))
         from deep_cbrs_amar_renaissance_amd import recommend as rec
         return rec.evaluate_ranking(self, trainset, test_ratings, ks, users=users, exclude_seen=exclude_seen, diversity=diversity,
-                                    calibration=calibration)
+                                    calibration=calibration, rank_metrics=rank_metrics)
 
     def evaluate(self, sequence, **kwargs):
         """Loss and metrics on `sequence` (experiment.py:194): [loss, accuracy] when no metric or only accuracy is compiled, else

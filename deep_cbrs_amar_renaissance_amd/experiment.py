@@ -38,7 +38,7 @@ from deep_cbrs_amar_renaissance_amd.models.basic import BasicRS, BasicGNN, Basic
 from deep_cbrs_amar_renaissance_amd.models.hybrid import HybridCBRS, HybridBertGNN
 from deep_cbrs_amar_renaissance_amd.utilities import losses
 from deep_cbrs_amar_renaissance_amd.utilities.keras import Callback, EarlyStopping, ReduceLROnPlateau, get_total_parameters
-from deep_cbrs_amar_renaissance_amd.utilities.metrics import explanations_frame, full_ranking_metrics, recommendations_frame, resolve_compiled, \
+from deep_cbrs_amar_renaissance_amd.utilities.metrics import check_rank_metrics, explanations_frame, full_ranking_metrics, recommendations_frame, resolve_compiled, \
     top_k_predictions, top_k_metrics
 from deep_cbrs_amar_renaissance_amd.utilities.schedules import resolve as resolve_learning_rate
 from deep_cbrs_amar_renaissance_amd.utilities.utils import \
@@ -280,8 +280,8 @@ class Experimenter:
             self.property_ids = loaders.property_identifiers(kwargs['props_triples_filepath'], kwargs.get('sep', '\t'))
 
     def validation_fit_args(self):
-        """fit()'s validation arguments from parameters.validation ({fraction, freq, ranking_ks, early_stopping, reduce_lr}); {} without
-        the key."""
+        """fit()'s validation arguments from parameters.validation ({fraction, freq, ranking_ks, full_ranking_rank_metrics,
+        early_stopping, reduce_lr}); {} without the key."""
         validation = self.config.parameters.get('validation')
         if not validation:
             return {}
@@ -294,9 +294,11 @@ class Experimenter:
             callbacks.append(ReduceLROnPlateau(**dict(validation.get('reduce_lr'))))
         callbacks.append(RunLogCallback(self.run_log, stopping))     # (last: it logs what the others added, `lr` among it)
         args = {'validation_data': self.valset, 'validation_freq': int(validation.get('freq', 1)), 'callbacks': callbacks}
-        if validation.get('ranking_ks'):
+        if validation.get('ranking_ks') or validation.get('full_ranking_rank_metrics'):
             args['validation_ranking'] = {'trainset': self.trainset, 'ratings': self.valset.ratings,
-                                          'ks': [int(k) for k in validation.get('ranking_ks')], 'users': None}
+                                          'ks': [int(k) for k in validation.get('ranking_ks') or []], 'users': None}
+            if validation.get('full_ranking_rank_metrics'):          # val_auc / val_mrr / val_map per validated epoch
+                args['validation_ranking']['rank_metrics'] = check_rank_metrics(validation.get('full_ranking_rank_metrics'))
         return args
 
     def class_weight(self):
@@ -337,6 +339,8 @@ class Experimenter:
 
     def train(self):
         self.logger.info("Experiment folder: " + self.config.dest)
+        if self.config.parameters.get('full_ranking_rank_metrics'):  # an unknown name fails here, not after the training
+            check_rank_metrics(self.config.parameters.get('full_ranking_rank_metrics'))
         self.build_dataset()
         self.build_optimizer()
         self.build_model()
@@ -384,6 +388,8 @@ class Experimenter:
         metrics = pd.DataFrame([precision_at, recall_at, f1_at], index=['precision_at', 'recall_at', 'f1_at'])
         if self.config.parameters.get('full_ranking_ks'):
             self.evaluate_full_ranking([int(k) for k in self.config.parameters.get('full_ranking_ks')])
+        if self.config.parameters.get('full_ranking_rank_metrics'):
+            self.evaluate_full_ranking_rank_metrics(self.config.parameters.get('full_ranking_rank_metrics'))
         if self.config.parameters.get('similar_items'):
             self.write_similar_items(**dict(self.config.parameters.get('similar_items')))
         if self.config.parameters.get('diversify'):
@@ -414,6 +420,17 @@ class Experimenter:
         self.run_log.log_metrics({'full_ranking_users_evaluated': full['users_evaluated'],
                                   'full_ranking_users_skipped': full['users_skipped']})
         return full
+
+    def evaluate_full_ranking_rank_metrics(self, names):
+        """Opt-in (parameters.full_ranking_rank_metrics: [auc, mrr, map] or a subset): the cut-off-free measures of the full ranking —
+        the exact rank of every relevant test item among ALL items its user has not rated in training (`evaluate_ranking(rank_metrics=...)`)
+        — logged as full_auc / full_mrr / full_map beside the `full_ranking_ks` metrics.  An unknown name is a ValueError."""
+        names = check_rank_metrics(names)
+        found = self.model.evaluate_ranking(self.trainset, self.testset.ratings, [], rank_metrics=names)
+        evaluated, skipped = found.pop('rank_metrics_users')
+        self.run_log.log_metrics({'full_' + name: value for name, value in found.items()})
+        self.run_log.log_metrics({'full_rank_metrics_users_evaluated': evaluated, 'full_rank_metrics_users_skipped': skipped})
+        return found
 
     def write_similar_items(self, k=10, metric='cosine', space=None):
         """Opt-in (parameters.similar_items: {k, metric, space}): every item's k most similar items in the trained model's `space`

@@ -42,6 +42,12 @@ The sixth part keeps a list in proportion to its user's tastes: ``item_category_
 matrix) into the categories of ``amar_rerank_calibrated_f32``, ``rerank_calibrated`` is that one launch over device pools (the user's
 and the list's category distributions stay in LDS: nothing of size m x P x G in memory), the mixin's ``recommend_calibrated`` /
 ``list_calibration`` run it and its float64 metric (``amar_list_calibration_f64``), and ``evaluate_ranking`` takes ``calibration=``.
+
+The seventh part turns the question round: "where does THIS item stand for this user?".  ``rank_of_fused`` is one
+``amar_rank_of_f32`` launch over the split towers (every pair of the catalogue scored by the rankers' own score routine and counted
+against the targets' scores on chip: nothing of size |U| x |I| in memory), ``rank_of_pairs`` the same counts from pair-route scores
+per user chunk for the heads without a fused kernel, the mixin's ``rank_items`` answers per (user, item) pair, and
+``evaluate_ranking`` takes ``rank_metrics=`` (AUC, MRR, MAP from the exact ranks of every held-out item: ``amar_rank_of_metrics_f64``).
 """
 import contextlib
 import weakref
@@ -312,7 +318,7 @@ def device_lists():
         _ON_DEVICE = saved
 
 
-def evaluate_ranking(model, trainset, test_ratings, ks, users=None, exclude_seen=True, diversity=None, calibration=None):
+def evaluate_ranking(model, trainset, test_ratings, ks, users=None, exclude_seen=True, diversity=None, calibration=None, rank_metrics=None):
     """model.recommend at k = max(ks) with the lists kept on the device, then utilities.metrics.full_ranking_metrics_device: the
     dict of `full_ranking_metrics(*model.recommend(...)[:2], test_ratings, ks)` without the lists (or a Python loop) on the host.
     diversity={'metric': 'cosine' | 'dot', 'space': ...} (both optional) adds, for every k, 'ild_at_<k>' (the float64 mean, over the
@@ -320,9 +326,22 @@ def evaluate_ranking(model, trainset, test_ratings, ks, users=None, exclude_seen
     amar_list_diversity_f64) and 'item_coverage_at_<k>' (the distinct items in the first k ranks of all lists over |I|).
     calibration={'smoothing': 0.01, 'categories': None} (both optional) adds 'miscalibration_at_<k>': the float64 mean, over the users
     that have a target, of C(p, the first k ranks) (amar_list_calibration_f64; categories as in `item_category_csr`), 0 when no user
-    has one."""
-    from deep_cbrs_amar_renaissance_amd.utilities.metrics import full_ranking_metrics, full_ranking_metrics_device
+    has one.
+    rank_metrics=('auc', 'mrr', 'map') (any subset) adds those keys — the cut-off-free measures from the exact rank of every
+    held-out item (`heldout_rank_metrics`; utilities.metrics.full_ranking_rank_metrics has the definitions) — and
+    'rank_metrics_users' = (evaluated, skipped); `ks` may then be empty."""
+    from deep_cbrs_amar_renaissance_amd.utilities.metrics import check_rank_metrics, full_ranking_metrics, full_ranking_metrics_device
     ks = [int(k) for k in ks]
+    if rank_metrics is not None:
+        rank_metrics = check_rank_metrics(rank_metrics)
+        if not ks:
+            if diversity is not None or calibration is not None:
+                raise ValueError("diversity and calibration are measured at cutoffs: evaluate_ranking needs at least one k for them")
+            return heldout_rank_metrics(model, trainset, test_ratings, users, exclude_seen, rank_metrics)
+        out = evaluate_ranking(model, trainset, test_ratings, ks, users=users, exclude_seen=exclude_seen, diversity=diversity,
+                               calibration=calibration)
+        out.update(heldout_rank_metrics(model, trainset, test_ratings, users, exclude_seen, rank_metrics))
+        return out
     if not ks:
         raise ValueError("evaluate_ranking needs at least one k")
     if diversity is not None:
@@ -411,6 +430,23 @@ def fused(towers, plan, trainset, k, users, exclude_seen):
     return _finish(u, items, scores, n_users)
 
 
+def _unseen_mask(uc, n_items, excl, dev):
+    """bool [c, n_items] on the device: True where the item row is not in the exclusion row of user uc[row] (`excl` = the device
+    CSR of `_exclusion_device`, None: everything is kept)."""
+    c = int(uc.numel())
+    keep = torch.ones((c, n_items), dtype=torch.bool, device=dev)
+    if excl is not None:
+        ptr = excl[0].to(torch.int64)
+        beg, cnt = ptr[uc], ptr[uc + 1] - ptr[uc]
+        total = int(cnt.sum())
+        if total:
+            rows = torch.repeat_interleave(torch.arange(c, device=dev), cnt)
+            first = torch.repeat_interleave(torch.cumsum(cnt, 0) - cnt, cnt)
+            pos = torch.repeat_interleave(beg, cnt) + torch.arange(total, device=dev) - first
+            keep[rows, excl[1].to(torch.int64)[pos]] = False
+    return keep
+
+
 def pairs(score_fn, trainset, k, users, exclude_seen, device=None):
     """Pair route: per user chunk, the unexcluded (user, item) list built on the device, scored by `score_fn(u_ids, i_ids)` (int32 rows
     of the user / item tower tables -> [P, 1] scores) and ranked by amar_topk_segmented_f32."""
@@ -426,16 +462,7 @@ def pairs(score_fn, trainset, k, users, exclude_seen, device=None):
     for lo in range(0, len(u), chunk):
         uc = torch.from_numpy(u[lo:lo + chunk]).to(dev)
         c = int(uc.numel())
-        keep = torch.ones((c, n_items), dtype=torch.bool, device=dev)
-        if excl is not None:
-            ptr = excl[0].to(torch.int64)
-            beg, cnt = ptr[uc], ptr[uc + 1] - ptr[uc]
-            total = int(cnt.sum())
-            if total:
-                rows = torch.repeat_interleave(torch.arange(c, device=dev), cnt)
-                first = torch.repeat_interleave(torch.cumsum(cnt, 0) - cnt, cnt)
-                pos = torch.repeat_interleave(beg, cnt) + torch.arange(total, device=dev) - first
-                keep[rows, excl[1].to(torch.int64)[pos]] = False
+        keep = _unseen_mask(uc, n_items, excl, dev)
         r, i = keep.nonzero(as_tuple=True)                       # row-major: users in chunk order, items ascending
         seg = torch.zeros(c + 1, dtype=torch.int64, device=dev)
         torch.cumsum(keep.sum(1), 0, out=seg[1:])
@@ -816,6 +843,157 @@ def group_pairs(score_fn, n_items, grp_ptr, grp_users, excl, k, strategy, min_sc
     return torch.cat(out_i), torch.cat(out_s)
 
 
+# -- exact positions (amar_rank_of_f32): "where does THIS item stand for this user?" --------------------------------------------------
+RANK_KEYS = ('scores', 'greater', 'eq_before', 'eq_after')
+
+
+def check_targets_csr(targets_csr, n_entries, n_items):
+    """(ptr int64 [n_entries + 1], item rows int64) of a targets CSR over the listed users, checked: rows in 0..n_items-1, ascending
+    and distinct inside an entry."""
+    ptr, items = (np.asarray(x, dtype=np.int64).reshape(-1) for x in targets_csr)
+    if len(ptr) != n_entries + 1 or ptr[0] != 0 or ptr[-1] != len(items) or (np.diff(ptr) < 0).any():
+        raise ValueError("targets must be a CSR over the listed users ({} users, {} pointers, {} items)".format(n_entries, len(ptr), len(items)))
+    if len(items) and (items.min() < 0 or items.max() >= n_items):
+        raise ValueError("target items must be item rows in [0, {})".format(n_items))
+    if len(items) > 1:
+        inside = np.ones(len(items) - 1, dtype=bool)
+        inside[ptr[1:-1][(ptr[1:-1] > 0) & (ptr[1:-1] < len(items))] - 1] = False       # pairs that straddle two entries
+        if (np.diff(items)[inside] <= 0).any():
+            raise ValueError("the targets of an entry must be ascending and distinct")
+    return ptr, items
+
+
+def rank_of_fused(towers, plan, trainset, users, targets_csr, exclude_seen):
+    """One amar_rank_of_f32 call over the split towers (tu [U, c1], ti [I, c1] with b1 folded in): for every listed user (host
+    indices; a user may be listed more than once) and every item row of its entry of `targets_csr` = (ptr, item rows) the score and
+    the counts of the candidates that score higher / the same with a smaller row / the same with a larger row, among the items
+    outside the user's training row (all items with exclude_seen=False).  Returns the four device tensors of `capi.rank_of`, one
+    value per target in the CSR's order."""
+    n_users, n_items = _sizes(trainset)
+    u = check_users(users, n_users)
+    ptr, items = check_targets_csr(targets_csr, len(u), n_items)
+    tu, ti = towers[0], towers[1]
+    excl = _exclusion_device(trainset, n_users, n_items, exclude_seen)
+    blob, dims, acts = plan['rest']
+    return capi.rank_of(tu, ti, blob, dims, acts, plan['in_act'], u, ptr, items,
+                        excl_ptr=excl[0] if excl else None, excl_items=excl[1] if excl else None)
+
+
+def rank_of_pairs(score_fn, trainset, users, targets_csr, exclude_seen, device=None):
+    """Pair route of `rank_of_fused`, for the hybrids and the heads without a split plan: per user chunk the unexcluded pair list of
+    `pairs()` scored by `score_fn`, the targets scored by one more call, and torch comparisons of every candidate row against its
+    targets' scores (at most PAIRS_PER_CHUNK comparisons in memory at a time).  The same four outputs in the same order."""
+    n_users, n_items = _sizes(trainset)
+    u = check_users(users, n_users)
+    ptr, items = check_targets_csr(targets_csr, len(u), n_items)
+    dev = device or default_device()
+    excl = _exclusion_device(trainset, n_users, n_items, exclude_seen)
+    n_t = len(items)
+    scores = torch.zeros(n_t, dtype=torch.float32, device=dev)
+    greater, before, after = (torch.zeros(n_t, dtype=torch.int32, device=dev) for _ in range(3))
+    chunk = max(1, PAIRS_PER_CHUNK // max(1, n_items))
+    rows_all = torch.arange(n_items, device=dev)[None, :]
+    for lo in range(0, len(u), chunk):
+        hi = min(len(u), lo + chunk)
+        t0, t1 = int(ptr[lo]), int(ptr[hi])
+        if t1 == t0:
+            continue
+        uc = torch.from_numpy(u[lo:hi]).to(dev)
+        keep = _unseen_mask(uc, n_items, excl, dev)
+        r, i = keep.nonzero(as_tuple=True)
+        S = torch.full((hi - lo, n_items), float('nan'), dtype=torch.float32, device=dev)
+        if i.numel():
+            S[r, i] = score_fn(uc[r].to(torch.int32).contiguous(), i.to(torch.int32).contiguous()).reshape(-1)
+        row_of = torch.from_numpy(np.repeat(np.arange(hi - lo), np.diff(ptr[lo:hi + 1]))).to(dev)
+        tgt = torch.from_numpy(items[t0:t1]).to(dev)
+        s_t = score_fn(uc[row_of].to(torch.int32).contiguous(), tgt.to(torch.int32).contiguous()).reshape(-1)
+        scores[t0:t1] = s_t
+        for b0 in range(0, t1 - t0, chunk):
+            b1 = min(t1 - t0, b0 + chunk)
+            rows, st, it = row_of[b0:b1], s_t[b0:b1, None], tgt[b0:b1, None]
+            kept, sc = keep[rows], S[rows]
+            greater[t0 + b0:t0 + b1] = (kept & (sc > st)).sum(1).to(torch.int32)
+            tie = kept & (sc == st)
+            before[t0 + b0:t0 + b1] = (tie & (rows_all < it)).sum(1).to(torch.int32)
+            after[t0 + b0:t0 + b1] = (tie & (rows_all > it)).sum(1).to(torch.int32)
+    return scores, greater, before, after
+
+
+def rank_of_route(model, trainset, users, targets_csr, exclude_seen):
+    """`rank_of_fused` or `rank_of_pairs`, chosen as the model's `recommend()` chooses its route."""
+    route = model._group_route(trainset)
+    if route[0] == 'fused':
+        return rank_of_fused(route[1], route[2], trainset, users, targets_csr, exclude_seen)
+    return rank_of_pairs(route[1], trainset, users, targets_csr, exclude_seen, device=route[2])
+
+
+# Held-out targets per ratings pair (test ratings, training ratings), built once: R'(u) = relevant(u) \ excl(u) as a host CSR over
+# all users and |C(u)|.  Keyed and held like the device CSRs above; the training ratings are checked by identity on every hit.
+_HELDOUT_CACHE = {}
+
+
+def heldout_targets(trainset, test_ratings, exclude_seen=True):
+    """(ptr int64 [|U| + 1], item rows int64, n_cand int64 [|U|]): for every user the label-1 test items that are not among its
+    training items (all of them with exclude_seen=False), ascending, and the number of items outside its training row."""
+    from deep_cbrs_amar_renaissance_amd.utilities.metrics import relevant_csr
+    n_users, n_items = _sizes(trainset)
+    ratings = trainset.ratings
+
+    def build():
+        r_ptr, r_items = relevant_csr(test_ratings, n_users, n_items)
+        n_cand = np.full(n_users, n_items, dtype=np.int64)
+        if exclude_seen:
+            e_ptr, e_items = exclusion_csr(ratings, n_users, n_items)
+            n_cand -= np.diff(e_ptr)
+            rel = np.repeat(np.arange(n_users, dtype=np.int64), np.diff(r_ptr)) * n_items + r_items
+            seen = np.repeat(np.arange(n_users, dtype=np.int64), np.diff(e_ptr)) * n_items + e_items
+            rel = np.setdiff1d(rel, seen, assume_unique=True)
+            r_ptr = np.zeros(n_users + 1, dtype=np.int64)
+            np.cumsum(np.bincount(rel // n_items, minlength=n_users), out=r_ptr[1:])
+            r_items = rel % n_items
+        try:
+            held = weakref.ref(ratings)
+        except TypeError:
+            held = (lambda o: (lambda: o))(ratings)
+        return held, (r_ptr, r_items, n_cand)
+    key = (id(test_ratings), np.shape(test_ratings), id(ratings), np.shape(ratings), n_users, n_items, bool(exclude_seen))
+    entry = _device_cached(_HELDOUT_CACHE, test_ratings, key, build)
+    if entry[0]() is not ratings:                                     # the id of a dead training array, reused
+        _HELDOUT_CACHE.pop(key, None)
+        entry = _device_cached(_HELDOUT_CACHE, test_ratings, key, build)
+    return entry[1]
+
+
+def heldout_rank_metrics(model, trainset, test_ratings, users, exclude_seen, names):
+    """{name: the float64 mean over the evaluated users, 'rank_metrics_users': (evaluated, skipped)} for `names` out of 'auc', 'mrr',
+    'map': every listed user's held-out items (`heldout_targets`) ranked exactly in the full catalogue (`rank_of_route`: one
+    amar_rank_of_f32 launch on the fused route) and turned into per-user AUC / reciprocal rank / average precision on the device
+    (amar_rank_of_metrics_f64).  A user without a held-out item, or without a candidate that is not one, is skipped and counted; with
+    nobody evaluated the means are 0."""
+    n_users, n_items = _sizes(trainset)
+    u = check_users(users, n_users)
+    all_ptr, all_items, n_cand = heldout_targets(trainset, test_ratings, exclude_seen)
+    cnt = all_ptr[u + 1] - all_ptr[u]
+    ptr = np.zeros(len(u) + 1, dtype=np.int64)
+    np.cumsum(cnt, out=ptr[1:])
+    items = all_items[np.repeat(all_ptr[u] - ptr[:-1], cnt) + np.arange(int(ptr[-1]), dtype=np.int64)]
+    mean, evaluated = np.zeros(3), 0
+    if len(u):
+        flat = rank_of_route(model, trainset, u, (ptr, items), exclude_seen)
+        dev = flat[0].device
+        values, valid = capi.rank_of_metrics(*flat, _i32_device(ptr, dev), _i32_device(n_cand[u], dev))
+        values, valid = values.cpu().numpy(), valid.cpu().numpy() > 0
+        evaluated = int(valid.sum())
+        if evaluated:
+            mean = values[valid].mean(axis=0)
+    out = {name: float(mean[('auc', 'mrr', 'map').index(name)]) for name in names}
+    out['rank_metrics_users'] = (evaluated, len(u) - evaluated)
+    return out
+
+
+RANK_ITEMS_KEYS = ('rank', 'score', 'ties', 'candidates', 'percentile')
+
+
 class SimilarSearch:
     """Embedding accessors and similarity search shared by the scoring models.  A model names its spaces (`_embedding_spaces`:
     'graph' = the propagated, reduced node table, 'tower' = the first-stage Dense outputs per entity; the first one is the default)
@@ -1027,6 +1205,46 @@ class SimilarSearch:
         ev, sim, pr, ps, pc = out
         return dict(zip(EXPLAIN_KEYS, (u, rows(lists), rows(ev), sim.cpu().numpy(), pr.cpu().numpy().astype(np.int64), ps.cpu().numpy(),
                                        pc.cpu().numpy())))
+
+    # -- exact positions (amar_rank_of_f32) ---------------------------------------------------------------------------------
+    def rank_items(self, trainset, users, items, exclude_seen=True):
+        """Where every (users[p], items[p]) pair stands in the user's full ranking: `users` user indices 0..|U|-1 and `items` item
+        node ids |U|..|U|+|I|-1, parallel arrays.  The candidates of a user are all items of `trainset` outside its training row
+        (all items with exclude_seen=False).  Returns a dict of host arrays, one value per pair: 'rank' int64 (1-based: the position
+        `recommend()` with an unbounded k would list the item at — score descending, node id ascending on ties; 0 = "seen": the item
+        is in the user's training row), 'score' float32 (the model's score, filled for seen items too), 'ties' int64 (the other
+        candidates with exactly that score), 'candidates' int64 (the user's |C(u)|) and 'percentile' float64
+        (1 - (rank - 1) / candidates: 1 for the best item; NaN for a seen one).  Heads with a fused ranking kernel run one
+        amar_rank_of_f32 launch (nothing of size |U| x |I| in memory); the others compare pair-route scores per user chunk."""
+        n_users, n_items = _sizes(trainset)
+        if users is None or items is None:
+            raise ValueError("rank_items needs `users` and `items`: parallel arrays of user indices and item node ids")
+        u = check_users(users, n_users)
+        it = check_ids(items, n_users, n_users + n_items, 'items')
+        if len(u) != len(it):
+            raise ValueError("users and items must be parallel arrays ({} users, {} items)".format(len(u), len(it)))
+        if len(u) == 0:
+            return {'rank': np.zeros(0, dtype=np.int64), 'score': np.zeros(0, dtype=np.float32), 'ties': np.zeros(0, dtype=np.int64),
+                    'candidates': np.zeros(0, dtype=np.int64), 'percentile': np.zeros(0, dtype=np.float64)}
+        pair, inverse = np.unique(u * n_items + (it - n_users), return_inverse=True)        # by user, then item row: the entries
+        uu, rows = pair // n_items, pair % n_items
+        entry_users, counts = np.unique(uu, return_counts=True)
+        ptr = np.zeros(len(entry_users) + 1, dtype=np.int64)
+        np.cumsum(counts, out=ptr[1:])
+        score, greater, before, after = (t.cpu().numpy() for t in rank_of_route(self, trainset, entry_users, (ptr, rows), exclude_seen))
+        candidates = np.full(len(pair), n_items, dtype=np.int64)
+        seen = np.zeros(len(pair), dtype=bool)
+        excl = _exclusion_device(trainset, n_users, n_items, exclude_seen)
+        if excl is not None:
+            e_ptr, e_items = excl[0].cpu().numpy().astype(np.int64), excl[1].cpu().numpy().astype(np.int64)
+            candidates -= np.diff(e_ptr)[uu]
+            seen = np.isin(pair, np.repeat(np.arange(n_users, dtype=np.int64), np.diff(e_ptr)) * n_items + e_items)
+        rank = np.where(seen, 0, 1 + greater.astype(np.int64) + before.astype(np.int64))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            percentile = np.where(seen, np.nan, 1.0 - (rank - 1).astype(np.float64) / candidates.astype(np.float64))
+        out = (rank, score.astype(np.float32), before.astype(np.int64) + after.astype(np.int64), candidates, percentile)
+        inverse = inverse.reshape(-1)
+        return {key: value[inverse] for key, value in zip(RANK_ITEMS_KEYS, out)}
 
     # -- group recommendation (amar_recommend_group_f32) ----------------------------------------------------------------
     def recommend_group(self, trainset, groups, k=10, strategy='mean', min_score=None, exclude_seen=True, member_scores=False):

@@ -1650,7 +1650,8 @@ class _FitHooks:
     on_epoch_begin / on_epoch_end(epoch, logs), on_train_batch_begin / on_train_batch_end(batch, logs), set_model(model)), a validation
     pass every `validation_freq`-th epoch (`validation_data`: anything evaluate() accepts -> val_loss, val_<metric>;
     `validation_ranking`: {'trainset', 'ratings', 'ks', 'users'} -> val_precision_at_<k>, val_recall_at_<k>, val_ndcg_at_<k>,
-    val_hit_at_<k> through evaluate_ranking) and `model.stop_training`.
+    val_hit_at_<k> through evaluate_ranking; with 'rank_metrics': ['auc', 'mrr', 'map'] (any subset; 'ks' may then be empty) also
+    val_auc / val_mrr / val_map from the exact rank of every held-out item) and `model.stop_training`.
 
     One `logs` dict per epoch goes to every callback in list order: the epoch's training entries, then its val_* entries; a callback
     may add keys for the callbacks after it.  The batch hooks are called only on callbacks that define them (a method inherited from
@@ -1678,6 +1679,9 @@ class _FitHooks:
             if missing:
                 raise ValueError("validation_ranking needs the keys 'trainset', 'ratings' and 'ks' (missing {})".format(missing))
             self.ranking = dict(validation_ranking)
+            if self.ranking.get('rank_metrics') is not None:
+                from deep_cbrs_amar_renaissance_amd.utilities.metrics import check_rank_metrics
+                self.ranking['rank_metrics'] = check_rank_metrics(self.ranking['rank_metrics'])
         names = history.trainer._compiled()[2]
         self.val_names = ['loss'] + (['accuracy'] if all(name == 'accuracy' for name in names) else list(names))   # what evaluate() returns
         self.hooks = {}
@@ -1718,8 +1722,9 @@ class _FitHooks:
         if self.ranking is not None:
             r = self.ranking
             found = self.model.evaluate_ranking(r['trainset'], r['ratings'], r['ks'], users=r.get('users'),
-                                                exclude_seen=r.get('exclude_seen', True))
-            out.update(('val_' + name, float(value)) for name, value in found.items() if not name.startswith('users_'))
+                                                exclude_seen=r.get('exclude_seen', True), rank_metrics=r.get('rank_metrics'))
+            out.update(('val_' + name, float(value)) for name, value in found.items()
+                       if not name.startswith('users_') and name != 'rank_metrics_users')
         return out
 
     def epoch_end(self, epoch, verbose):

@@ -148,6 +148,76 @@ def full_ranking_metrics(users, items, test_ratings, ks):
     return out
 
 
+RANK_METRICS = ('auc', 'mrr', 'map')
+
+
+def check_rank_metrics(names):
+    """The cut-off-free measures asked for, as a tuple in the order given, each once: a subset of RANK_METRICS; ValueError otherwise."""
+    if isinstance(names, str) or not hasattr(names, '__iter__'):
+        raise ValueError("rank_metrics must be a sequence of names out of {} (got {!r})".format(RANK_METRICS, names))
+    out = []
+    for name in names:
+        if not isinstance(name, str) or name not in RANK_METRICS:
+            raise ValueError("unknown rank metric {!r}; supported: {}".format(name, ', '.join(RANK_METRICS)))
+        if name not in out:
+            out.append(name)
+    if not out:
+        raise ValueError("rank_metrics names no metric; supported: {}".format(', '.join(RANK_METRICS)))
+    return tuple(out)
+
+
+def full_ranking_rank_metrics(scores_by_user, relevant, excluded=None, per_user=False):
+    """AUC, MRR and MAP of full rankings on the host, in float64, from dense score rows: what amar_rank_of_f32 +
+    amar_rank_of_metrics_f64 compute on the device without the rows (include/amar_hip.h has the same formulas).
+    `scores_by_user` [n, |I|]: row v holds user v's score of every item row (compared as float32); `relevant[v]` / `excluded[v]`: the
+    item rows that are relevant / excluded for the user (any iterable; excluded=None: nothing is).  Per user, with
+    C = {items} minus excluded, the targets R' = relevant minus excluded in ascending item row, R = |R'|, N_neg = |C| - R, and for t in R'
+        greater_t = #{i in C, i != t : s_i > s_t},  eq_before_t / eq_after_t = #{i in C, i != t : s_i == s_t, i < t / i > t},
+        r_t = 1 + greater_t + eq_before_t   (the position recommend() with an unbounded k would list t at),
+        h_t = #{t' in R' : r_t' <= r_t}:
+        rr = 1 / min_t r_t,   ap = (1 / R) sum_t h_t / r_t   (terms added in target order),
+        auc = 1 - [sum_t (neg_greater_t + neg_equal_t / 2)] / (R N_neg),
+    neg_greater_t = greater_t - #{t' != t : s_t' > s_t} and neg_equal_t = eq_before_t + eq_after_t - #{t' != t : s_t' == s_t}: the
+    Mann-Whitney statistic with ties at 1/2, which does not depend on the numbering of the items (rr and ap do, through r_t, when
+    scores tie).  A user with R = 0 or N_neg = 0 is skipped and counted.  Returns {'auc', 'mrr', 'map': the float64 means over the
+    evaluated users (0 when there is none), 'rank_metrics_users': (evaluated, skipped)}; per_user=True returns instead
+    (values float64 [n, 3] in the order auc, rr, ap — zeros for a skipped user —, valid bool [n])."""
+    S = np.asarray(scores_by_user, dtype=np.float32)
+    if S.ndim != 2 or len(relevant) != len(S) or (excluded is not None and len(excluded) != len(S)):
+        raise ValueError("scores_by_user must be [n, items] with one relevant (and one excluded) collection per row")
+    n, n_items = S.shape
+    values, valid = np.zeros((n, 3), dtype=np.float64), np.zeros(n, dtype=bool)
+    for v in range(n):
+        cand = np.ones(n_items, dtype=bool)
+        if excluded is not None:
+            cand[np.asarray(sorted(excluded[v]), dtype=np.int64)] = False
+        rel = np.asarray(sorted(set(int(i) for i in relevant[v])), dtype=np.int64)
+        if rel.size and (rel[0] < 0 or rel[-1] >= n_items):
+            raise ValueError("relevant items must be item rows in [0, {})".format(n_items))
+        targets = rel[cand[rel]] if rel.size else rel
+        R, n_neg = len(targets), int(cand.sum()) - len(targets)
+        if R == 0 or n_neg <= 0:
+            continue
+        s, rows = S[v], np.arange(n_items)
+        greater = np.array([int((cand & (s > s[t])).sum()) for t in targets], dtype=np.int64)
+        before = np.array([int((cand & (s == s[t]) & (rows < t)).sum()) for t in targets], dtype=np.int64)
+        after = np.array([int((cand & (s == s[t]) & (rows > t)).sum()) for t in targets], dtype=np.int64)
+        st = s[targets]
+        r = 1 + greater + before
+        h = (r[None, :] <= r[:, None]).sum(axis=1)
+        neg_greater = greater - (st[None, :] > st[:, None]).sum(axis=1)
+        neg_equal = before + after - ((st[None, :] == st[:, None]).sum(axis=1) - 1)
+        ap = 0.0
+        for term in (h.astype(np.float64) / r.astype(np.float64)).tolist():
+            ap += term
+        values[v] = (1.0 - float((neg_greater + 0.5 * neg_equal).sum()) / (float(R) * float(n_neg)), 1.0 / float(r.min()), ap / float(R))
+        valid[v] = True
+    if per_user:
+        return values, valid
+    mean = values[valid].mean(axis=0) if valid.any() else np.zeros(3)
+    return {'auc': float(mean[0]), 'mrr': float(mean[1]), 'map': float(mean[2]), 'rank_metrics_users': (int(valid.sum()), int(n - valid.sum()))}
+
+
 def intra_list_diversity(lists, vectors, ks=None, metric='cosine'):
     """Intra-list diversity on the host, in float64 (what amar_list_diversity_f64 computes on the device): `lists` [m, K] ROWS of
     `vectors` [n, d], -1 padded; for every cutoff k of `ks` (K alone by default) the mean over the pairs a < b of valid items in the

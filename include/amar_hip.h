@@ -1339,6 +1339,62 @@ int amar_rank_metrics_f64(const int32_t *lists, int64_t m, int32_t K, const int3
                           const int32_t *rel_items, int32_t n_users, const int32_t *ks, int32_t nk, const double *cum_disc,
                           double *workspace, double *out_sums, int64_t *out_counts, amar_stream_t stream);
 
+/* Where does THIS item stand?  Exact positions of chosen (user, item) pairs in the full catalogue of the split scoring head, by
+ * counting: the third consumer of the score routine of amar_recommend_f32 / amar_recommend_group_f32 (one text, the same bits per
+ * pair wherever it is staged).  Tables, packed rest stack, limits, alignment rules, users[m] and the exclusion CSR over USERS are
+ * exactly those of amar_recommend_f32.
+ * Targets: a CSR over the m LISTED entries, tgt_ptr[m+1] and tgt_items (item rows in 0..n_items-1, ascending and de-duplicated per
+ * entry; n_targets = tgt_ptr[m], which the host caller knows).  The same user may be listed in several entries; an entry holds at
+ * most AMAR_RANK_OF_MAX_TARGETS targets (the host caller passes max_targets, the longest entry it built; more: AMAR_EUNSUPPORTED).
+ * For entry j with user u, C(u) = {items} \ excl(u) and target t at position e of tgt_items, in float32:
+ *     out_scores[e]    = s_t = score(u, t)
+ *     out_greater[e]   = #{ i in C(u), i != t : score(u, i) >  s_t }
+ *     out_eq_before[e] = #{ i in C(u), i != t : score(u, i) == s_t, i < t }
+ *     out_eq_after[e]  = #{ i in C(u), i != t : score(u, i) == s_t, i > t }
+ * so 1 + greater + eq_before is the position at which amar_recommend_f32 with an unbounded k would list t.  A target that is
+ * itself in excl(u) is scored and counted against C(u) like any other (the host decides what that means); other targets of the
+ * same user are ordinary candidates.  Counts are int32.  Nothing of size m x n_items is written.
+ * How: blocks of 16 entries x item slices, as amar_recommend_f32.  Per entry the targets' Ti rows are gathered into a tile-shaped
+ * LDS buffer and scored, then sorted by (score, item); every catalogue pair costs one binary search among them and one integer LDS
+ * add; the user's excluded items of the slice are scored as gathered tiles and subtracted (exact: a pair's bits do not depend on
+ * where it is staged); the slices add their integer partials to the outputs with integer atomics.  No float atomics: an entry's
+ * result depends on its own user row, Ti, the weights, its exclusion row and its targets only, not on the other entries, the grid
+ * or the slicing, and a call returns the same bits on every run.
+ * AMAR_RANK_OF_MAX_TARGETS = 64: one lane per target in the sort and the final prefix sums, and 16 entries' sorted targets and
+ * counters (6 x 64 + 2 words each, 25 KB) fit beside the largest stack the rankers take (128 -> 128 -> 1: 67 KB of weights, a 25 KB
+ * tile, 34 KB of gather buffers: 151 of the 160 KB).
+ * n_slices: item slices per entry block (<= 0: automatic).  amar_rank_of_slices returns the count a call will launch (a call that
+ * passes n_slices > 0 must pass that count).  PRECONDITION: every users[j] < n_users (not checked on the device); a target or
+ * excluded row outside 0..n_items-1 is scored as a row of zeros, never read.
+ * NULL tables or outputs, negative sizes, tgt_ptr == NULL with m > 0, tgt_items == NULL with n_targets > 0, excl_ptr without
+ * excl_items, users == NULL with m != n_users: AMAR_EINVAL; the shape limits: AMAR_EUNSUPPORTED; all checked before any device
+ * call.  m == 0 or n_targets == 0: AMAR_OK, nothing is launched. */
+#define AMAR_RANK_OF_MAX_TARGETS 64
+int32_t amar_rank_of_slices(int64_t m, int32_t n_items, const int32_t *dims, int32_t n_layers, int32_t n_slices);
+int amar_rank_of_f32(const float *Tu, int64_t ldu, int32_t n_users, const float *Ti, int64_t ldi, int32_t n_items, int32_t c1,
+                     const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers, int32_t in_act,
+                     const int32_t *users, int64_t m, const int32_t *excl_ptr, const int32_t *excl_items,
+                     const int32_t *tgt_ptr, const int32_t *tgt_items, int64_t n_targets, int32_t max_targets, int32_t n_slices,
+                     float *out_scores, int32_t *out_greater, int32_t *out_eq_before, int32_t *out_eq_after, amar_stream_t stream);
+
+/* Cut-off-free ranking metrics from amar_rank_of_f32's flat outputs: AUC, reciprocal rank and average precision per evaluated
+ * user, in float64.  Evaluated user v of n_eval owns the targets rel_ptr[v] .. rel_ptr[v+1] of the flat order (a CSR over USERS,
+ * independent of how the entries were chunked): R' = relevant(u) \ excl(u), the user's held-out items; n_cand[v] = |C(u)|.
+ * With r_t = 1 + greater_t + eq_before_t, h_t = #{t' in R' : r_t' <= r_t}, R = |R'| and N_neg = n_cand - R:
+ *     rr  = 1 / min_t r_t
+ *     ap  = (1 / R) sum_t h_t / r_t                                     (terms added in target order)
+ *     auc = 1 - [ sum_t ( neg_greater_t + neg_equal_t / 2 ) ] / ( R N_neg )
+ * neg_greater_t = greater_t - #{t' != t : s_t' > s_t}, neg_equal_t = eq_before_t + eq_after_t - #{t' != t : s_t' == s_t}: the
+ * candidates that are not targets, the target-target corrections from comparing `scores` pairwise.  This is the Mann-Whitney
+ * statistic with ties at 1/2; it does not depend on the numbering of the items (the sum is an exact integer count of halves).
+ * out [n_eval, 3] = (auc, rr, ap); valid [n_eval] (int32) = 0 for R = 0 or N_neg <= 0 (the row is then 0, 0, 0: the caller skips
+ * and counts it), else 1.  One wavefront per user, no atomics, the same bits on every run; the caller means the valid rows.
+ * NULL rel_ptr / n_cand / out / valid with n_eval > 0, NULL flat arrays with n_targets > 0, negative sizes: AMAR_EINVAL.
+ * n_eval == 0: AMAR_OK, nothing is launched. */
+int amar_rank_of_metrics_f64(const float *scores, const int32_t *greater, const int32_t *eq_before, const int32_t *eq_after,
+                             int64_t n_targets, const int32_t *rel_ptr, const int32_t *n_cand, int64_t n_eval,
+                             double *out, int32_t *valid, amar_stream_t stream);
+
 /* Diversified re-ranking of candidate pools that are already on the device: greedy Maximal Marginal Relevance (MMR), and the
  * intra-list diversity (ILD) of finished lists.  Both work on the P x P Gram matrix of a list's item vectors, kept on chip.
  *
