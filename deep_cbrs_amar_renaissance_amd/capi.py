@@ -165,6 +165,7 @@ SIGNATURES = {
     'amar_rank_of_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P,
                                         _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     'amar_rank_of_metrics_f64': (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _P]),
+    'amar_rank_route': (ctypes.c_int, [_I32, _P, _I32, _P]),
     'amar_rerank_mmr_f32': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _F32, _I32, _P, _P, _P, _P, _P]),
     'amar_list_diversity_f64': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _P]),
     'amar_explain_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, _I32, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _I32, _I32,
@@ -1435,6 +1436,40 @@ def _sliced_topk(slices_fn, slices_args, m, k, dev):
     out_scores = torch.empty((m, k), dtype=torch.float32, device=dev)
     ws_rows = torch.empty((m * slices * k,), dtype=torch.int32, device=dev) if slices > 1 else None
     return slices, out_rows, out_scores, ws_rows
+
+
+RANK_KINDS = {'recommend': 0, 'group': 1, 'rank_of': 2}                # include/amar_hip.h: AMAR_RANK_RECOMMEND / _GROUP / _RANK_OF
+
+
+class RankRouteInfo(_RouteInfo):
+    """include/amar_hip.h: amar_rank_route_info"""
+    _fields_ = [(name, ctypes.c_int32) for name in ('maxt', 'pt', 'tile_items', 'tile_stride', 'wpack_floats', 'fits', 'large_lds',
+                                                    'reserved')] + [('lds_bytes', ctypes.c_int64)]
+    BOOLS, HIDDEN = ('fits', 'large_lds'), ('reserved',)
+
+
+def rank_route(kind, dims, code=False):
+    """What `recommend` ('recommend'), `recommend_group` ('group') or `rank_of` ('rank_of') does with a rest stack of the widths
+    `dims` (c1, ..., 1): the launch geometry (maxt, pt, tile_items, tile_stride), wpack_floats, the dynamic LDS of a launch
+    (lds_bytes), `fits` (lds_bytes <= 160 KB: False = the entry point refuses the head with AMAR_EUNSUPPORTED) and `large_lds`
+    (> 64 KB).  amar_rank_route: host only, the launchers ask the same function.  A dict; with code=True the return code is added as
+    `code` and nothing is raised, else dims the launchers refuse raise as their wrappers would."""
+    info = RankRouteInfo()
+    dims = [int(d) for d in dims]
+    rc = load().amar_rank_route(RANK_KINDS[kind], (ctypes.c_int32 * max(len(dims), 1))(*dims), len(dims) - 1, ctypes.byref(info))
+    if not code:
+        _check(rc, 'amar_rank_route')
+    d = info.as_dict()
+    if code:
+        d['code'] = int(rc)
+    return d
+
+
+def rank_fits(kind, dims):
+    """Whether the fused ranker `kind` takes a rest stack of these widths: its argument checks pass and its LDS sum fits
+    (`rank_route`).  False sends the caller to its pair route; nothing is raised."""
+    r = rank_route(kind, dims, code=True)
+    return r['code'] == 0 and r['fits']
 
 
 def recommend(Tu, Ti, wpack, dims, acts, in_act, k, users=None, excl_ptr=None, excl_items=None, n_slices=0):

@@ -137,10 +137,9 @@ int amar_recommend_group_f32(const float *Tu, int64_t ldu, int32_t n_users, cons
     if (rc != AMAR_OK) return rc;
     GroupArgs ga{};
     RankArgs &a = ga.r;
-    rc = rank_pack_args(dims, acts, n_layers, a);
-    if (rc != AMAR_OK) return rc;
     RankShape sh;
-    rc = rank_shape(dims, n_layers, sh);
+    amar_rank_route_info route;
+    rc = rank_route(AMAR_RANK_GROUP, dims, acts, n_layers, a, sh, route);
     if (rc != AMAR_OK) return rc;
     const int32_t slices = group_slices(n_groups, n_members, n_items, sh.tile_items, n_slices);
     if (slices < 1) return slices < 0 ? slices : AMAR_EINVAL;
@@ -151,20 +150,19 @@ int amar_recommend_group_f32(const float *Tu, int64_t ldu, int32_t n_users, cons
     a.Tu = Tu; a.ldu = ldu; a.Ti = Ti; a.ldi = ldi; a.c1 = c1; a.n_items = n_items;
     a.users = grp_users; a.m = n_groups; a.excl_ptr = excl_ptr; a.excl_items = excl_items;
     a.wpack = wpack; a.in_act = in_act; a.out.k = k;
-    a.tile_items = sh.tile_items; a.tile_stride = sh.tile_stride;
     a.slice_items = (int)rank_slice_rows(n_items, sh.tile_items, slices);
     a.out.n_slices = slices;
     a.out.rows = slices > 1 ? workspace_items : out_items;
     a.out.scores = slices > 1 ? workspace_scores : out_scores;
     ga.grp_ptr = grp_ptr; ga.strategy = strategy; ga.min_score = min_score;
-    const size_t lds_bytes = rank_lds_bytes(a, sh);
-    if (lds_bytes > 160 * 1024) return AMAR_EUNSUPPORTED;
+    if (!route.fits) return AMAR_EUNSUPPORTED;
+    const size_t lds_bytes = (size_t)route.lds_bytes;
     const int64_t blocks = (n_groups + RANK_UB - 1) / RANK_UB;
     if (blocks >= (1ll << 31)) return AMAR_EUNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)blocks, (unsigned)slices), block(256);
     static bool done[4][AMAR_MAX_DEVICES];
-    AMAR_RANK_DISPATCH(recommend_group_kernel, sh.maxt, grid, block, lds_bytes, st, ga, done)
+    AMAR_RANK_DISPATCH(recommend_group_kernel, route.maxt, grid, block, lds_bytes, st, ga, done)
     const int e = amar_check_launch();
     if (e != AMAR_OK || slices == 1) return e;
     return rank_merge_slices(workspace_items, workspace_scores, n_groups, slices, k, out_items, out_scores, st);

@@ -191,10 +191,9 @@ int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const floa
     int rc = rank_check_tables(Tu, ldu, Ti, ldi, c1, wpack, dims, n_layers, in_act);
     if (rc != AMAR_OK) return rc;
     RankArgs a{};
-    rc = rank_pack_args(dims, acts, n_layers, a);
-    if (rc != AMAR_OK) return rc;
     RankShape sh;
-    rc = rank_shape(dims, n_layers, sh);
+    amar_rank_route_info route;
+    rc = rank_route(AMAR_RANK_RECOMMEND, dims, acts, n_layers, a, sh, route);
     if (rc != AMAR_OK) return rc;
     const int32_t slices = amar_recommend_slices(m, n_items, dims, n_layers, n_slices);
     if (slices < 1) return slices < 0 ? slices : AMAR_EINVAL;
@@ -205,22 +204,34 @@ int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const floa
     a.Tu = Tu; a.ldu = ldu; a.Ti = Ti; a.ldi = ldi; a.c1 = c1; a.n_items = n_items;
     a.users = users; a.m = m; a.excl_ptr = excl_ptr; a.excl_items = excl_items;
     a.wpack = wpack; a.in_act = in_act; a.out.k = k;
-    a.tile_items = sh.tile_items; a.tile_stride = sh.tile_stride;
     a.slice_items = (int)rank_slice_rows(n_items, sh.tile_items, slices);
     a.out.n_slices = slices;
     a.out.rows = slices > 1 ? workspace_items : out_items;
     a.out.scores = slices > 1 ? workspace_scores : out_scores;
-    const size_t lds_bytes = rank_lds_bytes(a, sh);
-    if (lds_bytes > 160 * 1024) return AMAR_EUNSUPPORTED;
+    if (!route.fits) return AMAR_EUNSUPPORTED;
+    const size_t lds_bytes = (size_t)route.lds_bytes;
     const int64_t blocks = (m + RANK_UB - 1) / RANK_UB;
     if (blocks >= (1ll << 31)) return AMAR_EUNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)blocks, (unsigned)slices), block(256);
     static bool done[4][AMAR_MAX_DEVICES];
-    AMAR_RANK_DISPATCH(recommend_kernel, sh.maxt, grid, block, lds_bytes, st, a, done)
+    AMAR_RANK_DISPATCH(recommend_kernel, route.maxt, grid, block, lds_bytes, st, a, done)
     const int e = amar_check_launch();
     if (e != AMAR_OK || slices == 1) return e;
     return rank_merge_slices(workspace_items, workspace_scores, m, slices, k, out_items, out_scores, st);
+}
+
+int amar_rank_route(int32_t kind, const int32_t *dims, int32_t n_layers, amar_rank_route_info *info) {
+    if (!dims || !info) return AMAR_EINVAL;
+    *info = amar_rank_route_info{};
+    if (kind != AMAR_RANK_RECOMMEND && kind != AMAR_RANK_GROUP && kind != AMAR_RANK_RANK_OF) return AMAR_EINVAL;
+    if (n_layers < 2 || n_layers > RANK_MAX_LAYERS + 1) return AMAR_EUNSUPPORTED;
+    const int32_t c1 = dims[0];                                          // the head's part of rank_check_tables, in its order
+    if (c1 < 4 || (c1 & 3)) return AMAR_EINVAL;
+    if (c1 > 128 || dims[n_layers] != 1) return AMAR_EUNSUPPORTED;
+    RankArgs a{};
+    RankShape sh;
+    return rank_route(kind, dims, nullptr, n_layers, a, sh, *info);
 }
 
 int amar_topk_segmented_f32(const int32_t *seg_ptr, const int32_t *item_ids, const float *scores,

@@ -26,7 +26,7 @@
 namespace {
 
 constexpr int RO_T = AMAR_RANK_OF_MAX_TARGETS;
-constexpr int RO_WORDS = 6 * RO_T + 2;           // per entry: ts, ti, tp [T], cnt [T + 1, padded to T + 2], bf, af [T]
+constexpr int RO_WORDS = RANK_OF_WORDS;         // per entry: ts, ti, tp [T], cnt [T + 1, padded to T + 2], bf, af [T] (6 T + 2)
 static_assert(RO_T == AMAR_WAVE, "one lane per target");
 
 struct RankOfArgs {
@@ -207,11 +207,6 @@ __global__ __launch_bounds__(256) void rank_of_kernel(const RankOfArgs ra) {
     }
 }
 
-inline size_t rank_of_lds_bytes(const RankArgs &a, const RankShape &sh) {
-    return (size_t)((a.wpack_floats + 3) & ~3) * 4 + (size_t)sh.tile_items * sh.tile_stride * 4 +
-           (size_t)RANK_WAVES * 16 * sh.pt * sh.tile_stride * 4 + (size_t)RANK_UB * RO_WORDS * 4;
-}
-
 // AUC, reciprocal rank and average precision of one evaluated user per wavefront, from the flat counts (include/amar_hip.h).
 __global__ __launch_bounds__(256) void rank_of_metrics_kernel(const float *__restrict__ scores, const int32_t *__restrict__ greater,
                                                                const int32_t *__restrict__ before, const int32_t *__restrict__ after,
@@ -294,10 +289,9 @@ int amar_rank_of_f32(const float *Tu, int64_t ldu, int32_t n_users, const float 
     if (rc != AMAR_OK) return rc;
     RankOfArgs ra{};
     RankArgs &a = ra.r;
-    rc = rank_pack_args(dims, acts, n_layers, a);
-    if (rc != AMAR_OK) return rc;
     RankShape sh;
-    rc = rank_shape(dims, n_layers, sh);
+    amar_rank_route_info route;
+    rc = rank_route(AMAR_RANK_RANK_OF, dims, acts, n_layers, a, sh, route);
     if (rc != AMAR_OK) return rc;
     if (max_targets > AMAR_RANK_OF_MAX_TARGETS || n_targets >= (1ll << 31)) return AMAR_EUNSUPPORTED;
     const int32_t slices = amar_rank_of_slices(m, n_items, dims, n_layers, n_slices);
@@ -306,12 +300,11 @@ int amar_rank_of_f32(const float *Tu, int64_t ldu, int32_t n_users, const float 
     a.Tu = Tu; a.ldu = ldu; a.Ti = Ti; a.ldi = ldi; a.c1 = c1; a.n_items = n_items;
     a.users = users; a.m = m; a.excl_ptr = excl_ptr; a.excl_items = excl_items;
     a.wpack = wpack; a.in_act = in_act;
-    a.tile_items = sh.tile_items; a.tile_stride = sh.tile_stride;
     a.slice_items = (int)rank_slice_rows(n_items, sh.tile_items, slices);
-    ra.tgt_ptr = tgt_ptr; ra.tgt_items = tgt_items; ra.gather_floats = 16 * sh.pt * sh.tile_stride;
+    ra.tgt_ptr = tgt_ptr; ra.tgt_items = tgt_items; ra.gather_floats = rank_of_gather_floats(sh);
     ra.out_scores = out_scores; ra.out_greater = out_greater; ra.out_before = out_eq_before; ra.out_after = out_eq_after;
-    const size_t lds_bytes = rank_of_lds_bytes(a, sh);
-    if (lds_bytes > 160 * 1024) return AMAR_EUNSUPPORTED;
+    if (!route.fits) return AMAR_EUNSUPPORTED;
+    const size_t lds_bytes = (size_t)route.lds_bytes;
     const int64_t blocks = (m + RANK_UB - 1) / RANK_UB;
     if (blocks >= (1ll << 31)) return AMAR_EUNSUPPORTED;
     if (m == 0 || n_targets == 0) return AMAR_OK;
@@ -323,7 +316,7 @@ int amar_rank_of_f32(const float *Tu, int64_t ldu, int32_t n_users, const float 
     }
     const dim3 grid((unsigned)blocks, (unsigned)slices), block(256);
     static bool done[4][AMAR_MAX_DEVICES];
-    AMAR_RANK_DISPATCH(rank_of_kernel, sh.maxt, grid, block, lds_bytes, st, ra, done)
+    AMAR_RANK_DISPATCH(rank_of_kernel, route.maxt, grid, block, lds_bytes, st, ra, done)
     return amar_check_launch();
 }
 

@@ -6,8 +6,9 @@
 //     (rank_stage_weights, rank_stage_tile), a user's Tu row becomes MFMA fragments (rank_load_user).  recommend_kernel keeps these
 //     few lines in its own body, as it always had them: it must compile to what it compiled to;
 //   * host: the argument checks the entry points share (rank_check_tables), the walk over the packed stack (rank_pack_args), the
-//     launch geometry of a stack (rank_shape), the LDS a launch needs (rank_lds_bytes) and the MAXT / PT dispatch
-//     (AMAR_RANK_DISPATCH).
+//     launch geometry of a stack (rank_shape), the LDS a launch needs (rank_lds_bytes, rank_of_lds_bytes), rank_route — the one
+//     function the three launchers and the query amar_rank_route take all of that and the capacity refusal from — and the
+//     MAXT / PT dispatch (AMAR_RANK_DISPATCH).
 #pragma once
 #include "amar_common.h"
 #include "amar_rank_select.h"
@@ -126,6 +127,41 @@ inline size_t rank_lds_bytes(const RankArgs &a, const RankShape &sh) {
            (size_t)rank_select_state_floats(RANK_UB) * 4;
 }
 
+// amar_rank_of.hip's share of the LDS: per entry RANK_OF_WORDS words of sorted targets and counters (its RankOfSlot), per wave a
+// gather buffer of one step's rows; rank_of_kernel's carve-up reads the same two numbers.
+constexpr int RANK_OF_WORDS = 6 * AMAR_RANK_OF_MAX_TARGETS + 2;
+inline int rank_of_gather_floats(const RankShape &sh) { return 16 * sh.pt * sh.tile_stride; }
+inline size_t rank_of_lds_bytes(const RankArgs &a, const RankShape &sh) {
+    return (size_t)((a.wpack_floats + 3) & ~3) * 4 + (size_t)sh.tile_items * sh.tile_stride * 4 +
+           (size_t)RANK_WAVES * rank_of_gather_floats(sh) * 4 + (size_t)RANK_UB * RANK_OF_WORDS * 4;
+}
+
+constexpr size_t RANK_LDS_LIMIT = 160 * 1024, RANK_LDS_PLAIN = 64 * 1024;
+
+// The one decision about a rest stack that amar_recommend_f32, amar_recommend_group_f32, amar_rank_of_f32 and the query
+// amar_rank_route share: where its layers sit in the packed blob (a's layer fields, rank_pack_args), the launch geometry (sh,
+// rank_shape; a.tile_items / a.tile_stride), the LDS the kind's kernel asks for and whether that fits.  The launchers refuse on
+// !r.fits, size the launch by r.lds_bytes and dispatch on r.maxt, so the query cannot say anything else.  No HIP call.
+// acts == NULL (the query): every layer counts as linear, which the layout does not depend on.
+inline int rank_route(int kind, const int32_t *dims, const int32_t *acts, int32_t n_layers, RankArgs &a, RankShape &sh,
+                      amar_rank_route_info &r) {
+    r = amar_rank_route_info{};
+    if (kind != AMAR_RANK_RECOMMEND && kind != AMAR_RANK_GROUP && kind != AMAR_RANK_RANK_OF) return AMAR_EINVAL;
+    int32_t linear[RANK_MAX_LAYERS + 1] = {};
+    int rc = rank_pack_args(dims, acts ? acts : linear, n_layers, a);
+    if (rc != AMAR_OK) return rc;
+    rc = rank_shape(dims, n_layers, sh);
+    if (rc != AMAR_OK) return rc;
+    a.tile_items = sh.tile_items; a.tile_stride = sh.tile_stride;
+    const size_t bytes = kind == AMAR_RANK_RANK_OF ? rank_of_lds_bytes(a, sh) : rank_lds_bytes(a, sh);
+    r.maxt = sh.maxt; r.pt = sh.pt; r.tile_items = sh.tile_items; r.tile_stride = sh.tile_stride;
+    r.wpack_floats = a.wpack_floats;
+    r.lds_bytes = (int64_t)bytes;
+    r.fits = bytes <= RANK_LDS_LIMIT ? 1 : 0;
+    r.large_lds = bytes > RANK_LDS_PLAIN ? 1 : 0;
+    return AMAR_OK;
+}
+
 }  // namespace
 
 // Launches KERN<MAXT, PT> for the stack's shape (the four forms 1/4, 2/4, 4/2, 8/1), allowing it the large LDS where the launch
@@ -133,8 +169,8 @@ inline size_t rank_lds_bytes(const RankArgs &a, const RankShape &sh) {
 #define AMAR_RANK_LAUNCH_FORM(KERN, MT, PTT, D, grid, block, lds_bytes, st, args, done)                                 \
     do {                                                                                                                \
         auto kern = KERN<MT, PTT>;                                                                                      \
-        if ((lds_bytes) > 64 * 1024) {                                                                                  \
-            const int e = amar_allow_lds(reinterpret_cast<const void *>(kern), 160 * 1024, done[D]);                   \
+        if ((lds_bytes) > RANK_LDS_PLAIN) {                                                                             \
+            const int e = amar_allow_lds(reinterpret_cast<const void *>(kern), RANK_LDS_LIMIT, done[D]);               \
             if (e != AMAR_OK) return e;                                                                                 \
         }                                                                                                               \
         hipLaunchKernelGGL(kern, grid, block, lds_bytes, st, args);                                                     \

@@ -192,9 +192,9 @@ class BasicRS(rec.SimilarSearch, Model):
         towers = towers if towers is not None else self.towers(*self._recommend_tables(trainset))
         return rec.pairs(lambda u, i: self.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
 
-    def _group_route(self, trainset):
+    def _group_route(self, trainset, kind='group'):
         tables = self._recommend_tables(trainset)
-        split = self._recommend_split(*tables)
+        split = self._recommend_split(*tables, kind=kind)
         if split is not None:
             return 'fused', split, split[2]
         towers = self.towers(*tables)
@@ -204,7 +204,7 @@ class BasicRS(rec.SimilarSearch, Model):
         d = np.asarray(trainset.embeddings).shape[1]
         if not self.built:
             self.build_head(d, d)
-        return 'fused' if self._split_plan(d, d) is not None or self._rank_plan() is not None else 'pairs'
+        return 'fused' if self._ranker_plan(d, d, 'recommend')[0] is not None else 'pairs'
 
     def _recommend_tables(self, trainset):
         n_users, n_items = len(trainset.users), len(trainset.items)
@@ -224,9 +224,10 @@ class BasicRS(rec.SimilarSearch, Model):
 
     def _rank_plan(self):
         """The rest of the classifier packed for amar_recommend_f32 when the towers themselves are too wide for the split plan
-        (basic-kge: 512 -> 256 -> 128): classifier c1 -> ... -> 1 with c1 and every hidden width <= 128, c1 % 4 == 0; else None."""
+        (basic-kge: 512 -> 256 -> 128): classifier c1 -> ... -> 1 with c1 and every hidden width <= 128, c1 % 4 == 0 and at most
+        CHAIN_MAX_LAYERS layers after the first (what amar_chain_pack_f32 packs); else None."""
         clf = list(self.clf.layers)
-        if len(clf) < 3 or clf[-1].units != 1 or len(clf) - 1 > capi.CHAIN_MAX_LAYERS + 1:
+        if len(clf) < 3 or clf[-1].units != 1 or len(clf) - 1 > capi.CHAIN_MAX_LAYERS:
             return None
         rdims = [clf[0].units] + [l.units for l in clf[1:]]
         if max(rdims) > capi.CHAIN_MAX_WIDTH or rdims[0] % 4:
@@ -235,17 +236,30 @@ class BasicRS(rec.SimilarSearch, Model):
         rb, _ = capi.chain_pack([np_(l.kernel) for l in clf[1:]], [np_(l.bias) for l in clf[1:]])
         return {'rest': (torch.from_numpy(rb).to(clf[0].kernel.device), rdims, [l.activation for l in clf[1:]]), 'in_act': clf[0].activation}
 
-    def _recommend_split(self, u_table, i_table):
-        """(Tu, Ti, plan) for the fused ranking: the towers with the classifier's first layer folded in (b1 on the item side), per
-        entity — through the split plan's chains where it exists, else the towers' Dense stacks and one Dense launch per side.
-        None when the classifier's rest has no fused ranking kernel (the pair route then ranks)."""
-        plan = self._split_plan(u_table.shape[1], i_table.shape[1])
-        if plan is not None:
-            tu, ti, _ = self.towers(u_table, i_table)
-            return tu, ti, plan
-        plan = self._rank_plan()
+    def _ranker_plan(self, u_dim, i_dim, kind):
+        """(plan, split) for the fused ranker `kind` ('recommend' | 'group' | 'rank_of'): the split plan (split True) or, where the
+        towers are too wide for it, the rank plan (split False) — (None, False) when the head has neither or when that kernel
+        refuses the rest stack for capacity (capi.rank_fits: stack + item tile + the kernel's own state must fit 160 KB of LDS)."""
+        plan, split = self._split_plan(u_dim, i_dim), True
+        if plan is None:
+            plan, split = self._rank_plan(), False
+        if plan is None or not capi.rank_fits(kind, plan['rest'][1]):
+            return None, False
+        return plan, split
+
+    def _recommend_split(self, u_table, i_table, kind='recommend'):
+        """(Tu, Ti, plan) for the fused ranking kernel `kind`: the towers with the classifier's first layer folded in (b1 on the item
+        side), per entity — through the split plan's chains where it exists, else the towers' Dense stacks and one Dense launch per
+        side.  None when the classifier's rest has no fused ranking kernel, or when that kernel has no room for it (the widths
+        pass but stack, item tile and the kernel's state exceed 160 KB of LDS: capi.rank_route) — the pair route then ranks, so no
+        head that predict() scores is refused.  The answer is per kernel: 128 -> 128 -> 64 -> 1 ranks fused in recommend() and
+        recommend_group() and by pairs in rank_items()."""
+        plan, split = self._ranker_plan(u_table.shape[1], i_table.shape[1], kind)
         if plan is None:
             return None
+        if split:
+            tu, ti, _ = self.towers(u_table, i_table)
+            return tu, ti, plan
         tu_full, ti_full = self.unet.apply2(u_table), self.inet.apply2(i_table)
         l0 = self.clf.layers[0]
         w1, d, c1 = l0.kernel.detach(), tu_full.shape[1], l0.units
@@ -401,9 +415,9 @@ class BasicGNN(rec.SimilarSearch, Model, abc.ABC):
         towers = towers if towers is not None else self.rs.towers(*self._recommend_tables(trainset))
         return rec.pairs(lambda u, i: self.rs.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
 
-    def _group_route(self, trainset):
+    def _group_route(self, trainset, kind='group'):
         tables = self._recommend_tables(trainset)
-        split = self.rs._recommend_split(*tables)
+        split = self.rs._recommend_split(*tables, kind=kind)
         if split is not None:
             return 'fused', split, split[2]
         towers = self.rs.towers(*tables)
@@ -411,7 +425,7 @@ class BasicGNN(rec.SimilarSearch, Model, abc.ABC):
 
     def _recommend_route(self, trainset):
         d = self.gnn.output_dim()
-        return 'fused' if self.rs._split_plan(d, d) is not None or self.rs._rank_plan() is not None else 'pairs'
+        return 'fused' if self.rs._ranker_plan(d, d, 'recommend')[0] is not None else 'pairs'
 
     def _recommend_tables(self, trainset):
         """User / item rows of one (hoisted) propagation; the model's hoist state is left as it was found."""

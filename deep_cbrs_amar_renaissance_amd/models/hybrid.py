@@ -281,7 +281,7 @@ class HybridCBRS(rec.SimilarSearch, Model):
         towers = towers if towers is not None else self._recommend_towers(trainset)
         return rec.pairs(lambda u, i: self.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
 
-    def _group_route(self, trainset):
+    def _group_route(self, trainset, kind='group'):
         towers = self._recommend_towers(trainset)
         return 'pairs', lambda u, i: self.score_towers(towers, u, i), towers[0].device
 
@@ -431,7 +431,7 @@ class HybridBertGNN(rec.SimilarSearch, Model, abc.ABC):
         towers = towers if towers is not None else self._recommend_towers(trainset)
         return rec.pairs(lambda u, i: self.rs.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
 
-    def _group_route(self, trainset):
+    def _group_route(self, trainset, kind='group'):
         towers = self._recommend_towers(trainset)
         return 'pairs', lambda u, i: self.rs.score_towers(towers, u, i), towers[0].device
 

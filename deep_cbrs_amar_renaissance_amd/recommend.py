@@ -8,7 +8,11 @@ Two routes, chosen by the head alone (no user-facing switch):
   least one hidden layer).  The towers are computed once per call in split form (b1 folded into the item table) and ONE
   ``amar_recommend_f32`` launch (two with item slices) scores every (user, item) pair and keeps each user's top-k on chip;
   nothing of size |U| x |I| reaches memory.
-* pairs (`_recommend_pairs`): every other head (the hybrids, BasicRS without classifier hidden layers).  Per user chunk the
+  A head ranks fused only where the kernel has room for it: the rest stack, an item tile and the kernel's own state must fit
+  160 KB of LDS (``capi.rank_route`` / ``capi.rank_fits``, asked per kernel: ``amar_recommend_f32``, ``amar_recommend_group_f32`` and
+  ``amar_rank_of_f32`` have different sums, so 128 -> 128 -> 64 -> 1 is fused in ``recommend()`` and ranked by pairs in ``rank_items()``).
+* pairs (`_recommend_pairs`): every other head (the hybrids, BasicRS without classifier hidden layers, a rest stack the kernel has no
+  room for such as 128 -> 128 -> 128 -> 1: whatever ``predict()`` scores is ranked, nothing raises).  Per user chunk the
   unexcluded pair list is built on the device, scored by the model's hoisted pair scoring (``score_towers``) and ranked by
   ``amar_topk_segmented_f32``.  The tests also use it as the in-library yardstick of the fused route.
 
@@ -920,8 +924,9 @@ def rank_of_pairs(score_fn, trainset, users, targets_csr, exclude_seen, device=N
 
 
 def rank_of_route(model, trainset, users, targets_csr, exclude_seen):
-    """`rank_of_fused` or `rank_of_pairs`, chosen as the model's `recommend()` chooses its route."""
-    route = model._group_route(trainset)
+    """`rank_of_fused` or `rank_of_pairs`, chosen as the model's `recommend()` chooses its route — for amar_rank_of_f32's own capacity:
+    its LDS sum is the largest of the three rankers', so a head whose `recommend()` is fused may be counted by pairs here."""
+    route = model._group_route(trainset, 'rank_of')
     if route[0] == 'fused':
         return rank_of_fused(route[1], route[2], trainset, users, targets_csr, exclude_seen)
     return rank_of_pairs(route[1], trainset, users, targets_csr, exclude_seen, device=route[2])
@@ -1002,9 +1007,11 @@ class SimilarSearch:
     def _embedding_spaces(self):
         raise NotImplementedError
 
-    def _group_route(self, trainset):
-        """How the model ranks a catalogue, chosen as its `recommend()` chooses: ('fused', (tu, ti, ...), plan) = the split towers and
-        their plan, or ('pairs', score_fn(u_ids, i_ids) -> [P, 1] scores, device)."""
+    def _group_route(self, trainset, kind='group'):
+        """How the model ranks a catalogue for the fused kernel `kind` ('recommend' | 'group' | 'rank_of': capi.RANK_KINDS), chosen as
+        its `recommend()` chooses: ('fused', (tu, ti, ...), plan) = the split towers and their plan where the head has one and that
+        kernel takes it (capi.rank_fits: the kernels' LDS sums differ, so a head may rank fused in one and by pairs in another),
+        or ('pairs', score_fn(u_ids, i_ids) -> [P, 1] scores, device)."""
         raise NotImplementedError
 
     def _embedding_tables(self, trainset, space):

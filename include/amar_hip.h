@@ -1395,6 +1395,35 @@ int amar_rank_of_metrics_f64(const float *scores, const int32_t *greater, const 
                              int64_t n_targets, const int32_t *rel_ptr, const int32_t *n_cand, int64_t n_eval,
                              double *out, int32_t *valid, amar_stream_t stream);
 
+/* What the three fused rankers above do with a rest stack of these widths, without a device call: the launch geometry, the LDS a
+ * launch asks for, and whether the kernel takes the head at all.  dims[0] = c1, dims[n_layers] = 1, as for amar_recommend_f32.
+ * amar_recommend_f32, amar_recommend_group_f32 and amar_rank_of_f32 take their geometry and their capacity refusal from the function
+ * behind this query, so what it reports is what a launch with these dims does.
+ *     maxt         16-wide tiles of the widest layer (hidden layers included), rounded up to 1, 2, 4 or 8: the kernel form
+ *     pt           16-item pair tiles a wave scores per step: 4, 4, 2, 1 for maxt 1, 2, 4, 8 (a step is 16 pt items)
+ *     tile_items   items of a staged tile: a multiple of 16 pt, at most 256, within a 32 KB budget (at least one step)
+ *     tile_stride  floats between staged rows: 16 ceil(c1 / 16) + 4
+ *     wpack_floats floats of the packed stack (amar_chain_pack_floats of the same dims)
+ *     lds_bytes    dynamic LDS of a launch: the stack (rounded up to 16 bytes) + tile_items * tile_stride * 4 + per kind:
+ *                  RECOMMEND, GROUP: 16 640 (sixteen selectors);  RANK_OF: 4 * 16 pt * tile_stride * 4 (a gather buffer per wave)
+ *                  + 16 * (6 * AMAR_RANK_OF_MAX_TARGETS + 2) * 4 = 24 704 (sixteen entries' sorted targets and counters)
+ *     fits         lds_bytes <= 160 KB.  0: the entry point returns AMAR_EUNSUPPORTED for this head, before any device call
+ *     large_lds    lds_bytes > 64 KB: the launch first asks for the large dynamic LDS attribute
+ * The capacity rule in short: recommend / group take a stack of up to 121 856 B next to a 128-wide c1 (128 -> 128 -> 64 -> 1 fits,
+ * 128 -> 128 -> 128 -> 1 does not); rank_of takes up to 80 000 B there (128 -> 128 -> 1 fits, 128 -> 128 -> 64 -> 1 does not).
+ * Returns AMAR_OK with `fits` 0 or 1 for every head the argument checks of the launchers pass; AMAR_EINVAL for dims or info == NULL,
+ * an unknown kind, c1 < 4 or c1 % 4 != 0, a width < 1; AMAR_EUNSUPPORTED for n_layers outside [2, 9], dims[n_layers] != 1, a 1-unit
+ * layer before the last, a width above 128: the code the launchers return for these dims. */
+#define AMAR_RANK_RECOMMEND 0
+#define AMAR_RANK_GROUP     1
+#define AMAR_RANK_RANK_OF   2
+typedef struct amar_rank_route_info {
+    int32_t maxt, pt, tile_items, tile_stride;
+    int32_t wpack_floats, fits, large_lds, reserved;
+    int64_t lds_bytes;
+} amar_rank_route_info;
+int amar_rank_route(int32_t kind, const int32_t *dims, int32_t n_layers, amar_rank_route_info *info);
+
 /* Diversified re-ranking of candidate pools that are already on the device: greedy Maximal Marginal Relevance (MMR), and the
  * intra-list diversity (ILD) of finished lists.  Both work on the P x P Gram matrix of a list's item vectors, kept on chip.
  *
