@@ -157,6 +157,8 @@ SIGNATURES = {
     'amar_recommend_group_slices': (ctypes.c_int32, [_I64, _I64, _I32, _P, _I32, _I32]),
     'amar_recommend_group_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I64, _I64, _P, _P,
                                                 _I32, _F32, _I32, _I32, _P, _P, _P, _P, _P]),
+    'amar_recommend_among_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P,
+                                                _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     'amar_nearest_slices': (ctypes.c_int32, [_I64, _I32, _I32, _I32]),
     'amar_nearest_workspace_floats': (ctypes.c_int64, [_I64, _I32, _I32, _I32, _I32]),
     'amar_nearest_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _P, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
@@ -1438,7 +1440,7 @@ def _sliced_topk(slices_fn, slices_args, m, k, dev):
     return slices, out_rows, out_scores, ws_rows
 
 
-RANK_KINDS = {'recommend': 0, 'group': 1, 'rank_of': 2}                # include/amar_hip.h: AMAR_RANK_RECOMMEND / _GROUP / _RANK_OF
+RANK_KINDS = {'recommend': 0, 'group': 1, 'rank_of': 2, 'among': 4}    # include/amar_hip.h: AMAR_RANK_RECOMMEND / _GROUP / _RANK_OF / _AMONG
 
 
 class RankRouteInfo(_RouteInfo):
@@ -1449,7 +1451,7 @@ class RankRouteInfo(_RouteInfo):
 
 
 def rank_route(kind, dims, code=False):
-    """What `recommend` ('recommend'), `recommend_group` ('group') or `rank_of` ('rank_of') does with a rest stack of the widths
+    """What `recommend` ('recommend'), `recommend_group` ('group'), `rank_of` ('rank_of') or `recommend_among` ('among') does with a rest stack of the widths
     `dims` (c1, ..., 1): the launch geometry (maxt, pt, tile_items, tile_stride), wpack_floats, the dynamic LDS of a launch
     (lds_bytes), `fits` (lds_bytes <= 160 KB: False = the entry point refuses the head with AMAR_EUNSUPPORTED) and `large_lds`
     (> 64 KB).  amar_rank_route: host only, the launchers ask the same function.  A dict; with code=True the return code is added as
@@ -1498,7 +1500,55 @@ def recommend(Tu, Ti, wpack, dims, acts, in_act, k, users=None, excl_ptr=None, e
     return out_items, out_scores
 
 
-GROUP_STRATEGIES = {'mean': 0, 'min': 1, 'max': 2}                      # include/amar_hip.h: AMAR_GROUP_MEAN / _MIN / _MAX
+def check_candidate_rows(cand, n_items, what='recommend_among'):
+    """Host int32 item rows of a candidate list as amar_recommend_among_f32 wants them: integers, strictly ascending (so distinct),
+    each in [0, n_items).  The kernel cannot check its list, so nothing that fails here is uploaded: ValueError."""
+    import numpy as np
+    a = cand.detach().cpu().numpy() if isinstance(cand, torch.Tensor) else np.asarray(cand)
+    if a.ndim != 1 or (a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer))):
+        raise ValueError("{}: cand must be a 1-D sequence of integer item rows".format(what))
+    a = a.astype(np.int64)
+    if a.size and (a.min() < 0 or a.max() >= n_items):
+        raise ValueError("{}: cand must lie in [0, {}) (got {}..{})".format(what, n_items, int(a.min()), int(a.max())))
+    if a.size > 1 and (np.diff(a) <= 0).any():
+        raise ValueError("{}: cand must be strictly ascending (sorted, no duplicates)".format(what))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def recommend_among(Tu, Ti, wpack, dims, acts, in_act, k, cand, users=None, excl_ptr=None, excl_items=None, n_slices=0):
+    """Fused top-k among a candidate slice of the items (amar_recommend_among_f32): for every user row of `users` (all rows of Tu
+    when None) the k best of the item rows `cand` that are not in its exclusion CSR.  `cand` is a HOST sequence of item rows; it is
+    checked here (`check_candidate_rows`: ascending, distinct, in range — ValueError) before it is uploaded, because the kernel
+    cannot check it.  Returns (items int32 [m, k] item rows (-1 padded), scores float32 [m, k] (-inf padded)): what `recommend`
+    returns with the complement of `cand` merged into every exclusion row, bit for bit.  n_slices <= 0: the library's automatic
+    slicing of the candidate positions (AMAR_RECOMMEND_SLICES overrides it)."""
+    n_users, c1 = int(Tu.shape[0]), int(Tu.shape[1])
+    n_items = int(Ti.shape[0])
+    if int(Ti.shape[1]) != c1:
+        raise ValueError("recommend_among: Tu and Ti must have the same width")
+    rows = check_candidate_rows(cand, n_items)
+    n_cand = int(rows.size)
+    if (excl_ptr is None) != (excl_items is None):
+        raise ValueError("recommend_among: excl_ptr and excl_items go together")
+    if excl_ptr is not None and excl_ptr.numel() != n_users + 1:
+        raise ValueError("recommend_among: excl_ptr must have n_users + 1 entries")
+    m = int(users.numel()) if users is not None else n_users
+    if n_slices <= 0:
+        n_slices = int(os.environ.get('AMAR_RECOMMEND_SLICES', '0'))
+    dims_c = (ctypes.c_int32 * len(dims))(*dims)
+    acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
+    slices, out_items, out_scores, ws_i = _sliced_topk('amar_recommend_slices', (m, n_cand, dims_c, len(acts), int(n_slices)), m, k, Tu.device)
+    ws_s = torch.empty((m * slices * k,), dtype=torch.float32, device=Tu.device) if slices > 1 else None
+    cand_dev = torch.from_numpy(rows).to(Tu.device) if n_cand else None
+    _launch('amar_recommend_among_f32', *_mat(Tu, 'Tu'), n_users, *_mat(Ti, 'Ti'), n_items, c1, _ptr(wpack, F32, 'wpack'), dims_c, acts_c,
+            len(acts), ACT_CODES[in_act], _ptr(users, I32, 'users'), m, _ptr(excl_ptr, I32, 'excl_ptr'),
+            _ptr_entries(excl_items, I32, 'excl_items'), _ptr(cand_dev, I32, 'cand'), n_cand,
+            int(k), int(slices) if slices > 1 else 1, _ptr(ws_i), _ptr(ws_s),
+            _ptr(out_items) if m else None, _ptr(out_scores) if m else None)
+    return out_items, out_scores
+
+
+GROUP_STRATEGIES = {'mean': 0, 'min': 1, 'max': 2}                     # include/amar_hip.h: AMAR_GROUP_MEAN / _MIN / _MAX
 
 
 def recommend_group(Tu, Ti, wpack, dims, acts, in_act, k, grp_ptr, grp_users, strategy='mean', min_score=None, excl_ptr=None, excl_items=None,

@@ -127,6 +127,9 @@ inline size_t rank_lds_bytes(const RankArgs &a, const RankShape &sh) {
            (size_t)rank_select_state_floats(RANK_UB) * 4;
 }
 
+// amar_rank_among.hip: the same, and behind it the item row of every tile row (recommend_among_kernel's tile_rows).
+inline size_t rank_among_lds_bytes(const RankArgs &a, const RankShape &sh) { return rank_lds_bytes(a, sh) + (size_t)sh.tile_items * 4; }
+
 // amar_rank_of.hip's share of the LDS: per entry RANK_OF_WORDS words of sorted targets and counters (its RankOfSlot), per wave a
 // gather buffer of one step's rows; rank_of_kernel's carve-up reads the same two numbers.
 constexpr int RANK_OF_WORDS = 6 * AMAR_RANK_OF_MAX_TARGETS + 2;
@@ -138,22 +141,23 @@ inline size_t rank_of_lds_bytes(const RankArgs &a, const RankShape &sh) {
 
 constexpr size_t RANK_LDS_LIMIT = 160 * 1024, RANK_LDS_PLAIN = 64 * 1024;
 
-// The one decision about a rest stack that amar_recommend_f32, amar_recommend_group_f32, amar_rank_of_f32 and the query
-// amar_rank_route share: where its layers sit in the packed blob (a's layer fields, rank_pack_args), the launch geometry (sh,
+// The one decision about a rest stack that amar_recommend_f32, amar_recommend_group_f32, amar_rank_of_f32, amar_recommend_among_f32
+// and the query amar_rank_route share: where its layers sit in the packed blob (a's layer fields, rank_pack_args), the launch geometry (sh,
 // rank_shape; a.tile_items / a.tile_stride), the LDS the kind's kernel asks for and whether that fits.  The launchers refuse on
 // !r.fits, size the launch by r.lds_bytes and dispatch on r.maxt, so the query cannot say anything else.  No HIP call.
 // acts == NULL (the query): every layer counts as linear, which the layout does not depend on.
 inline int rank_route(int kind, const int32_t *dims, const int32_t *acts, int32_t n_layers, RankArgs &a, RankShape &sh,
                       amar_rank_route_info &r) {
     r = amar_rank_route_info{};
-    if (kind != AMAR_RANK_RECOMMEND && kind != AMAR_RANK_GROUP && kind != AMAR_RANK_RANK_OF) return AMAR_EINVAL;
+    if (kind != AMAR_RANK_RECOMMEND && kind != AMAR_RANK_GROUP && kind != AMAR_RANK_RANK_OF && kind != AMAR_RANK_AMONG) return AMAR_EINVAL;
     int32_t linear[RANK_MAX_LAYERS + 1] = {};
     int rc = rank_pack_args(dims, acts ? acts : linear, n_layers, a);
     if (rc != AMAR_OK) return rc;
     rc = rank_shape(dims, n_layers, sh);
     if (rc != AMAR_OK) return rc;
     a.tile_items = sh.tile_items; a.tile_stride = sh.tile_stride;
-    const size_t bytes = kind == AMAR_RANK_RANK_OF ? rank_of_lds_bytes(a, sh) : rank_lds_bytes(a, sh);
+    const size_t bytes = kind == AMAR_RANK_RANK_OF ? rank_of_lds_bytes(a, sh)
+                         : (kind == AMAR_RANK_AMONG ? rank_among_lds_bytes(a, sh) : rank_lds_bytes(a, sh));
     r.maxt = sh.maxt; r.pt = sh.pt; r.tile_items = sh.tile_items; r.tile_stride = sh.tile_stride;
     r.wpack_floats = a.wpack_floats;
     r.lds_bytes = (int64_t)bytes;

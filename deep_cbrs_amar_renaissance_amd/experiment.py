@@ -400,6 +400,8 @@ class Experimenter:
             self.write_explanations(**dict(self.config.parameters.get('explain')))
         if self.config.parameters.get('group_recommend'):
             self.write_group_recommend(**dict(self.config.parameters.get('group_recommend')))
+        if self.config.parameters.get('recommend_among'):
+            self.write_recommend_among(**dict(self.config.parameters.get('recommend_among')))
         self.logger.info('\n' + str(metrics))
         print('\n' + str(metrics))
         return metrics
@@ -545,6 +547,36 @@ class Experimenter:
         frame = pd.DataFrame({'group': np.asarray(ids, dtype=object)[g] if len(ids) else [], 'rank': r + 1,
                               'item': item_ids[items[g, r] - n_users], 'score': scores[g, r]})
         path = path_join(self.predictions_dest, "group_top_{}.tsv".format(k))
+        frame.to_csv(path, sep='\t', header=False, index=False)
+        return path
+
+    def write_recommend_among(self, k=10, candidates=None, any_of=None, all_of=None, none_of=None):
+        """Opt-in (parameters.recommend_among: {k, candidates: [...]} or {k, any_of / all_of / none_of: [...]}): every user's k best
+        unseen items among a candidate set (`recommend_among()`), written as <predictions_dest>/among_top_<k>.tsv, one row per
+        (user, rank): user (original id), rank, item (original id), score.  `candidates` lists ORIGINAL item ids (those that are not
+        in the training set are dropped with a log line); the property filters take property indices as `items_with_properties`
+        does and are used when `candidates` is absent."""
+        from deep_cbrs_amar_renaissance_amd.recommend import items_with_properties
+        k = int(k)
+        n_users, item_ids = len(self.trainset.users), np.asarray(self.trainset.items)
+        if candidates is not None:
+            if any_of is not None or all_of is not None or none_of is not None:
+                raise ValueError("parameters.recommend_among takes `candidates` or the property filters, not both")
+            index = {i: r for r, i in enumerate(item_ids.tolist())}
+            rows = [index[c] for c in list(candidates) if c in index]
+            if len(rows) != len(list(candidates)):
+                self.logger.info("recommend_among: {} of {} listed items are not in the training set: dropped".format(
+                    len(list(candidates)) - len(rows), len(list(candidates))))
+            chosen = np.asarray(rows, dtype=np.int64) + n_users
+        elif any_of is None and all_of is None and none_of is None:
+            raise ValueError("parameters.recommend_among needs `candidates` (item ids) or one of any_of / all_of / none_of (property indices)")
+        else:
+            chosen = items_with_properties(self.trainset, any_of=any_of, all_of=all_of, none_of=none_of)
+        users, items, scores = self.model.recommend_among(self.trainset, chosen, k=k)
+        u, r = np.nonzero(items >= 0)
+        frame = pd.DataFrame({'user': np.asarray(self.trainset.users)[users[u]] if len(users) else [], 'rank': r + 1,
+                              'item': item_ids[items[u, r] - n_users], 'score': scores[u, r]})
+        path = path_join(self.predictions_dest, "among_top_{}.tsv".format(k))
         frame.to_csv(path, sep='\t', header=False, index=False)
         return path
 

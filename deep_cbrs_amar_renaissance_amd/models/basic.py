@@ -186,11 +186,12 @@ class BasicRS(rec.SimilarSearch, Model):
             return rec.fused(split, split[2], trainset, k, users, exclude_seen)
         return self._recommend_pairs(trainset, k, users, exclude_seen, towers=self.towers(*tables))
 
-    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None):
+    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None, keep_items=None):
         rec.check_k(k)
         rec.check_users(users, len(trainset.users))
         towers = towers if towers is not None else self.towers(*self._recommend_tables(trainset))
-        return rec.pairs(lambda u, i: self.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
+        return rec.pairs(lambda u, i: self.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device,
+                         keep_items=keep_items)
 
     def _group_route(self, trainset, kind='group'):
         tables = self._recommend_tables(trainset)
@@ -409,11 +410,12 @@ class BasicGNN(rec.SimilarSearch, Model, abc.ABC):
             return rec.fused(split, split[2], trainset, k, users, exclude_seen)
         return self._recommend_pairs(trainset, k, users, exclude_seen, towers=self.rs.towers(*tables))
 
-    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None):
+    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None, keep_items=None):
         rec.check_k(k)
         rec.check_users(users, len(trainset.users))
         towers = towers if towers is not None else self.rs.towers(*self._recommend_tables(trainset))
-        return rec.pairs(lambda u, i: self.rs.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
+        return rec.pairs(lambda u, i: self.rs.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device,
+                         keep_items=keep_items)
 
     def _group_route(self, trainset, kind='group'):
         tables = self._recommend_tables(trainset)

@@ -275,11 +275,12 @@ class HybridCBRS(rec.SimilarSearch, Model):
         items int64 [m, k] (node ids, -1 padded), scores float32 [m, k] (-inf padded)), see recommend.py."""
         return self._recommend_pairs(trainset, k, users, exclude_seen)
 
-    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None):
+    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None, keep_items=None):
         rec.check_k(k)
         rec.check_users(users, len(trainset.users))
         towers = towers if towers is not None else self._recommend_towers(trainset)
-        return rec.pairs(lambda u, i: self.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
+        return rec.pairs(lambda u, i: self.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device,
+                         keep_items=keep_items)
 
     def _group_route(self, trainset, kind='group'):
         towers = self._recommend_towers(trainset)
@@ -425,11 +426,12 @@ class HybridBertGNN(rec.SimilarSearch, Model, abc.ABC):
         scores float32 [m, k] (-inf padded)), see recommend.py."""
         return self._recommend_pairs(trainset, k, users, exclude_seen)
 
-    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None):
+    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None, keep_items=None):
         rec.check_k(k)
         rec.check_users(users, len(trainset.users))
         towers = towers if towers is not None else self._recommend_towers(trainset)
-        return rec.pairs(lambda u, i: self.rs.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device)
+        return rec.pairs(lambda u, i: self.rs.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device,
+                         keep_items=keep_items)
 
     def _group_route(self, trainset, kind='group'):
         towers = self._recommend_towers(trainset)

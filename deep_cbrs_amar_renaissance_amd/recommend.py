@@ -52,6 +52,11 @@ The seventh part turns the question round: "where does THIS item stand for this 
 against the targets' scores on chip: nothing of size |U| x |I| in memory), ``rank_of_pairs`` the same counts from pair-route scores
 per user chunk for the heads without a fused kernel, the mixin's ``rank_items`` answers per (user, item) pair, and
 ``evaluate_ranking`` takes ``rank_metrics=`` (AUC, MRR, MAP from the exact ranks of every held-out item: ``amar_rank_of_metrics_f64``).
+
+The eighth part narrows the catalogue: "the best k among THESE items".  ``check_candidates`` reads a candidate set (node ids, a mask,
+or one set per listed user), ``items_with_properties`` builds one from the graph's item-property links, ``among_fused`` is one
+``amar_recommend_among_f32`` launch over the split towers (|U| x |C| pairs scored, the candidates' rows gathered into the item tile),
+``pairs(keep_items=...)`` the pair route over the kept pairs, and the mixin's ``recommend_among`` picks between them.
 """
 import contextlib
 import weakref
@@ -451,9 +456,24 @@ def _unseen_mask(uc, n_items, excl, dev):
     return keep
 
 
-def pairs(score_fn, trainset, k, users, exclude_seen, device=None):
+def _kept_mask(ptr, rows, lo, c, n_items, dev):
+    """bool [c, n_items] on the device: True where the item row is in segment lo + row of the host CSR (ptr, rows) over the listed
+    users — `_unseen_mask`'s construction, with True for the listed rows."""
+    keep = torch.zeros((c, n_items), dtype=torch.bool, device=dev)
+    b, e = int(ptr[lo]), int(ptr[lo + c])
+    if e > b:
+        cnt = torch.from_numpy(np.diff(ptr[lo:lo + c + 1])).to(dev)
+        at = torch.repeat_interleave(torch.arange(c, device=dev), cnt)
+        keep[at, torch.from_numpy(np.ascontiguousarray(rows[b:e], dtype=np.int64)).to(dev)] = True
+    return keep
+
+
+def pairs(score_fn, trainset, k, users, exclude_seen, device=None, keep_items=None):
     """Pair route: per user chunk, the unexcluded (user, item) list built on the device, scored by `score_fn(u_ids, i_ids)` (int32 rows
-    of the user / item tower tables -> [P, 1] scores) and ranked by amar_topk_segmented_f32."""
+    of the user / item tower tables -> [P, 1] scores) and ranked by amar_topk_segmented_f32.
+    keep_items (None: every item) restricts the list to candidates, as `check_candidates` returns them: item rows (one set for
+    every user, a bool row ANDed into the chunk's mask) or a CSR (ptr, rows) over the listed users (a mask per chunk).  Only kept
+    pairs are scored."""
     n_users, n_items = _sizes(trainset)
     k = check_k(k)
     u = check_users(users, n_users)
@@ -462,11 +482,19 @@ def pairs(score_fn, trainset, k, users, exclude_seen, device=None):
     dev = device or default_device()
     excl = _exclusion_device(trainset, n_users, n_items, exclude_seen)
     chunk = max(1, PAIRS_PER_CHUNK // max(1, n_items))
+    keep_row = None
+    if keep_items is not None and not isinstance(keep_items, tuple):
+        keep_row = torch.zeros(n_items, dtype=torch.bool, device=dev)
+        keep_row[torch.from_numpy(np.ascontiguousarray(keep_items, dtype=np.int64)).to(dev)] = True
     out_i, out_s = [], []
     for lo in range(0, len(u), chunk):
         uc = torch.from_numpy(u[lo:lo + chunk]).to(dev)
         c = int(uc.numel())
         keep = _unseen_mask(uc, n_items, excl, dev)
+        if keep_row is not None:
+            keep &= keep_row[None, :]
+        elif keep_items is not None:
+            keep &= _kept_mask(keep_items[0], keep_items[1], lo, c, n_items, dev)
         r, i = keep.nonzero(as_tuple=True)                       # row-major: users in chunk order, items ascending
         seg = torch.zeros(c + 1, dtype=torch.int64, device=dev)
         torch.cumsum(keep.sum(1), 0, out=seg[1:])
@@ -481,6 +509,95 @@ def pairs(score_fn, trainset, k, users, exclude_seen, device=None):
         out_i.append(items)
         out_s.append(sc)
     return _finish(u, torch.cat(out_i), torch.cat(out_s), n_users)
+
+
+# -- candidates (amar_recommend_among_f32): "the best k among THESE items" ----------------------------------------------------------
+def _candidate_rows(c, n_users, n_items, what):
+    """One candidate set as sorted, distinct item rows (int64): a bool mask of length |I| or integer item node ids."""
+    try:
+        a = c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
+    except ValueError:                                                    # ragged: neither a set nor one set per user
+        a = np.empty(0, dtype=object)
+    if a.dtype == np.bool_:
+        if a.ndim != 1 or len(a) != n_items:
+            raise ValueError("{}: a boolean mask must have one entry per item ({} items, shape {})".format(what, n_items, a.shape))
+        return np.flatnonzero(a).astype(np.int64)
+    if a.ndim != 1 or a.dtype == object:
+        raise ValueError("{} must be a 1-D sequence of item node ids, a boolean mask over the items, or one such sequence per listed "
+                         "user".format(what))
+    return np.unique(check_ids(a, n_users, n_users + n_items, what)) - n_users
+
+
+def check_candidates(candidates, n_users, n_items, n_listed=None):
+    """The `candidates` argument of `recommend_among`, checked and in the form the routes take:
+      * a 1-D integer sequence of item NODE ids (|U|..|U|+|I|-1: what `recommend()` returns and `similar_items(items=)` takes;
+        duplicates collapse, the order does not matter) or a boolean mask of length |I| -> item rows, int64, ascending and distinct:
+        one set for every user;
+      * a sequence of such sequences, one per listed user (`n_listed` of them, in the order of `users`) -> a CSR (ptr int64
+        [n_listed + 1], item rows int64 ascending and distinct per user): per-user candidates.
+    ValueError, naming `candidates`, for anything else: a non-integer dtype, ids out of range, a mask of the wrong length, a per-user
+    list whose length is not the number of listed users."""
+    what = 'candidates'
+    if isinstance(candidates, torch.Tensor):
+        candidates = candidates.detach().cpu().numpy()
+    if candidates is None or isinstance(candidates, (str, bytes, dict)) or not hasattr(candidates, '__len__'):
+        raise ValueError("{} must be a sequence of item node ids, a boolean mask over the items, or one such sequence per listed "
+                         "user".format(what))
+    if isinstance(candidates, np.ndarray):
+        nested = candidates.ndim == 2
+    else:
+        nested = len(candidates) > 0 and all(hasattr(c, '__len__') and not isinstance(c, (str, bytes, dict)) for c in candidates)
+    if not nested:
+        return _candidate_rows(candidates, n_users, n_items, what)
+    if n_listed is not None and len(candidates) != n_listed:
+        raise ValueError("{}: per-user candidates need one sequence per listed user ({} users, {} sequences)".format(
+            what, n_listed, len(candidates)))
+    segs = [_candidate_rows(c, n_users, n_items, what) for c in candidates]
+    ptr = np.zeros(len(segs) + 1, dtype=np.int64)
+    np.cumsum([len(s) for s in segs], out=ptr[1:])
+    return ptr, (np.concatenate(segs) if segs else np.zeros(0, dtype=np.int64))
+
+
+def items_with_properties(trainset, any_of=None, all_of=None, none_of=None):
+    """Sorted item node ids of the items whose properties (`item_property_csr(trainset)`, property indices 0..|P|-1 as that CSR numbers
+    them) pass the filter: at least one of `any_of`, every one of `all_of`, none of `none_of`; an argument left at None does not
+    constrain.  ValueError for a trainset without properties and for indices outside 0..|P|-1.  Pure numpy: feed the result to
+    `recommend_among(candidates=...)`."""
+    csr = item_property_csr(trainset)
+    if csr is None:
+        raise ValueError("items_with_properties: the trainset's graph has no item properties")
+    ptr, props, df, _ = csr
+    n_users, n_items = _sizes(trainset)
+    n_props = len(df)
+    item_of = np.repeat(np.arange(n_items, dtype=np.int64), np.diff(ptr))
+    passed = np.ones(n_items, dtype=bool)
+    for name, chosen in (('any_of', any_of), ('all_of', all_of), ('none_of', none_of)):
+        if chosen is None:
+            continue
+        if isinstance(chosen, (str, bytes, dict)) or np.ndim(chosen) != 1:
+            raise ValueError("items_with_properties: {} must be a 1-D sequence of property indices".format(name))
+        p = np.unique(check_ids(chosen, 0, n_props, name, "items_with_properties: {what} must be integer property indices",
+                                "items_with_properties: {what} must lie in [{lo}, {hi}) (got {min}..{max})"))
+        held = np.bincount(item_of[np.isin(props, p)], minlength=n_items)          # how many of the chosen ones every item has
+        passed &= (held > 0) if name == 'any_of' else ((held == len(p)) if name == 'all_of' else (held == 0))
+    return np.flatnonzero(passed).astype(np.int64) + n_users
+
+
+def among_fused(towers, plan, trainset, cand_rows, k, users, exclude_seen):
+    """One amar_recommend_among_f32 call over the split towers (tu [U, c1], ti [I, c1] with b1 folded in): `fused` with the tile loop
+    over `cand_rows` (host item rows, ascending and distinct: `check_candidates`) instead of the catalogue."""
+    n_users, n_items = _sizes(trainset)
+    k = check_k(k)
+    u = check_users(users, n_users)
+    if len(u) == 0:
+        return _empty(k)
+    tu, ti = towers[0], towers[1]
+    excl = _exclusion_device(trainset, n_users, n_items, exclude_seen)
+    blob, dims, acts = plan['rest']
+    u_dev = None if users is None else torch.from_numpy(u.astype(np.int32)).to(tu.device)
+    items, scores = capi.recommend_among(tu, ti, blob, dims, acts, plan['in_act'], k, cand_rows, users=u_dev,
+                                         excl_ptr=excl[0] if excl else None, excl_items=excl[1] if excl else None)
+    return _finish(u, items, scores, n_users)
 
 
 # -- similarity search (amar_nearest_f32): "which rows of this table are like these vectors?" ---------------------------------------
@@ -1252,6 +1369,30 @@ class SimilarSearch:
         out = (rank, score.astype(np.float32), before.astype(np.int64) + after.astype(np.int64), candidates, percentile)
         inverse = inverse.reshape(-1)
         return {key: value[inverse] for key, value in zip(RANK_ITEMS_KEYS, out)}
+
+    # -- candidates (amar_recommend_among_f32) ------------------------------------------------------------------------------
+    def recommend_among(self, trainset, candidates, k=10, users=None, exclude_seen=True):
+        """The k best items of every user in `users` (user indices, all users by default) among `candidates` only: one genre, what
+        is in stock, a shelf, the output of a retrieval stage.  `candidates` (`check_candidates`): item node ids |U|..|U|+|I|-1 in
+        any order, a boolean mask over the items, or one such sequence per listed user (`items_with_properties` builds sets from the
+        graph's properties).  Training pairs are excluded unless exclude_seen=False.  Returns (users int64 [m], items int64 [m, k]
+        node ids, -1 padded, scores float32 [m, k], -inf padded), shaped and ordered like `recommend()`: exactly the user's full
+        ranking with everything outside the candidates struck out.
+        One candidate set for every user and a head with a fused ranking kernel: one amar_recommend_among_f32 launch over
+        |U| x |C| pairs (nothing of that size in memory).  Everything else — a head that kernel does not take, the hybrids,
+        per-user candidates — is ranked by the pair route over the kept pairs; nothing raises."""
+        n_users, n_items = _sizes(trainset)
+        k = check_k(k)
+        u = check_users(users, n_users)
+        cand = check_candidates(candidates, n_users, n_items, n_listed=len(u))
+        if len(u) == 0:
+            return _empty(k)
+        if isinstance(cand, tuple):                                       # per-user candidates: the model's pair route
+            return self._recommend_pairs(trainset, k, users, exclude_seen, keep_items=cand)
+        route = self._group_route(trainset, kind='among')
+        if route[0] == 'fused':
+            return among_fused(route[1], route[2], trainset, cand, k, users, exclude_seen)
+        return pairs(route[1], trainset, k, users, exclude_seen, device=route[2], keep_items=cand)
 
     # -- group recommendation (amar_recommend_group_f32) ----------------------------------------------------------------
     def recommend_group(self, trainset, groups, k=10, strategy='mean', min_score=None, exclude_seen=True, member_scores=False):

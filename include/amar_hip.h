@@ -1235,7 +1235,8 @@ int amar_topk_segmented_f32(const int32_t *seg_ptr, const int32_t *item_ids, con
  * 1-unit scorer), and the k best (score descending, item ascending on ties) are written to out_items / out_scores [m, k],
  * padded with -1 / -inf when fewer than k items remain.  Nothing of size m x n_items is written.  Item ids are Ti rows.
  * Exclusion CSR (optional, both NULL = rank every item): excl_ptr[n_users+1], excl_items sorted and de-duplicated per user,
- * values in 0..n_items-1.  PRECONDITION: every users[j] < n_users (not checked on the device).
+ * values in 0..n_items-1.  PRECONDITION: every users[j] < n_users (not checked on the device).  The CSR holds fewer than 2^30
+ * entries (the selector's binary search adds two int32 positions); the host caller knows its length, the library does not.
  * A score is bit-identical to amar_chain_f32's f32 generic kernel on the same pair (its loop order, fragments and dot stage).
  * Limits: c1 and every width <= 128, c1 % 4 == 0, <= 8 Dense layers before the scorer, k <= 64; else AMAR_EUNSUPPORTED.
  * Tu, Ti, wpack 16-byte aligned, ldu / ldi multiples of 4.
@@ -1286,6 +1287,35 @@ int amar_recommend_group_f32(const float *Tu, int64_t ldu, int32_t n_users, cons
                              const int32_t *excl_ptr, const int32_t *excl_items, int32_t strategy, float min_score,
                              int32_t k, int32_t n_slices, int32_t *workspace_items, float *workspace_scores,
                              int32_t *out_items, float *out_scores, amar_stream_t stream);
+
+/* Top-k among a candidate slice of the catalogue ("the best k among THESE items": one genre, what is in stock, a shelf, the
+ * output of a retrieval stage), fused: amar_recommend_f32 with the tile loop running over a candidate list instead of the rows
+ * 0..n_items-1.  Tables, packed rest stack, limits, alignment rules, users[m] and the exclusion CSR over USERS are exactly those of
+ * amar_recommend_f32.
+ * Candidates: cand_items[n_cand], device item rows.  PRECONDITION: strictly ascending (so distinct) and each in [0, n_items); the
+ * library cannot check device memory, a list that breaks this is read out of bounds or walks the exclusion rows wrongly.  Host
+ * callers check the list before they upload it (capi.recommend_among does).
+ * For every listed user and every candidate that is not in the user's exclusion row the score is the one amar_recommend_f32
+ * computes for the pair, bit for bit (one score routine), and the k best (score descending, item row ascending on ties) go to
+ * out_items / out_scores [m, k] as item ROWS, padded with -1 / -inf: the lists amar_recommend_f32 returns with the complement of
+ * the candidates merged into every exclusion row.  m x n_cand pairs are scored, not m x n_items; nothing of either size is written.
+ * n_cand == 0 is a valid call: every list is padding and cand_items is not read (it may be NULL).
+ * How: the workgroup gathers the candidates' Ti rows into the item tile and keeps the tile's item rows beside it in LDS
+ * (4 * tile_items bytes more than amar_recommend_f32: amar_rank_route with AMAR_RANK_AMONG); selection and the exclusion walk
+ * stay in item-row space, which ascending candidates keep valid.  A user's result depends on its own Tu row, the candidates' Ti
+ * rows, the weights and its exclusion row only: not on the other users, the grid or the slicing; the same bits on every run.
+ * n_slices: slices of candidate POSITIONS per user block (<= 0: automatic).  amar_recommend_slices(m, n_cand, ...) returns the
+ * count a call will launch (a call that passes n_slices > 0 must pass that count); with more than one, workspace_items /
+ * workspace_scores hold m * slices * k entries each (any contents) and a second launch merges the slices.
+ * NULL tables, negative sizes, k < 1, n_cand > n_items, cand_items == NULL with n_cand > 0, users == NULL with m != n_users,
+ * excl_ptr without excl_items, a missing workspace or output: AMAR_EINVAL; k > 64, the shape limits, a head whose LDS sum does not
+ * fit (amar_rank_route: fits == 0): AMAR_EUNSUPPORTED; all checked before any device call.  m == 0: AMAR_OK, nothing is launched. */
+int amar_recommend_among_f32(const float *Tu, int64_t ldu, int32_t n_users, const float *Ti, int64_t ldi, int32_t n_items, int32_t c1,
+                             const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers, int32_t in_act,
+                             const int32_t *users, int64_t m, const int32_t *excl_ptr, const int32_t *excl_items,
+                             const int32_t *cand_items, int32_t n_cand, int32_t k, int32_t n_slices,
+                             int32_t *workspace_items, float *workspace_scores, int32_t *out_items, float *out_scores,
+                             amar_stream_t stream);
 
 /* Nearest rows of a table under dot or cosine similarity, fused score-and-select ("which items are like this one?").
  * Listed query j is row Q[query_rows[j]] (row j itself when query_rows == NULL, m == n_queries).  For every listed query and EVERY
@@ -1417,6 +1447,7 @@ int amar_rank_of_metrics_f64(const float *scores, const int32_t *greater, const 
 #define AMAR_RANK_RECOMMEND 0
 #define AMAR_RANK_GROUP     1
 #define AMAR_RANK_RANK_OF   2
+#define AMAR_RANK_AMONG     4   /* amar_recommend_among_f32: RECOMMEND's sum + 4 * tile_items (the tile's item rows); 3 stays unknown */
 typedef struct amar_rank_route_info {
     int32_t maxt, pt, tile_items, tile_stride;
     int32_t wpack_floats, fits, large_lds, reserved;
