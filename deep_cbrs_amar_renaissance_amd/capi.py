@@ -1428,16 +1428,21 @@ def topk_segmented(seg_ptr, item_ids, scores, k):
     return out_items, out_scores
 
 
-def _sliced_topk(slices_fn, slices_args, m, k, dev):
-    """What the two fused rankers allocate alike: the slices the library will launch (its `slices_fn`; a negative answer raises), the
-    [m, k] outputs and the int32 workspace of the per-slice lists (None with one slice)."""
-    slices = getattr(load(), slices_fn)(*slices_args)
+def _sliced_topk(slices_fn, slices_args, n_slices, m, k, dev, split_head=True):
+    """What the fused rankers allocate alike: the slices the library will launch for the request `n_slices` (its `slices_fn` over
+    `slices_args`, then the request; a negative answer raises), the [m, k] outputs and the int32 workspace of the per-slice lists
+    (None with one slice).  split_head (the rankers of the split head, not `nearest`): a request <= 0 is read from
+    AMAR_RECOMMEND_SLICES, and the float32 workspace of the per-slice scores is the fifth value (else None)."""
+    if split_head and n_slices <= 0:
+        n_slices = int(os.environ.get('AMAR_RECOMMEND_SLICES', '0'))
+    slices = getattr(load(), slices_fn)(*slices_args, int(n_slices))
     if slices < 0:
         _check(int(slices), slices_fn)
     out_rows = torch.empty((m, k), dtype=torch.int32, device=dev)
     out_scores = torch.empty((m, k), dtype=torch.float32, device=dev)
     ws_rows = torch.empty((m * slices * k,), dtype=torch.int32, device=dev) if slices > 1 else None
-    return slices, out_rows, out_scores, ws_rows
+    ws_scores = torch.empty((m * slices * k,), dtype=torch.float32, device=dev) if split_head and slices > 1 else None
+    return slices, out_rows, out_scores, ws_rows, ws_scores
 
 
 RANK_KINDS = {'recommend': 0, 'group': 1, 'rank_of': 2, 'among': 4}    # include/amar_hip.h: AMAR_RANK_RECOMMEND / _GROUP / _RANK_OF / _AMONG
@@ -1474,28 +1479,40 @@ def rank_fits(kind, dims):
     return r['code'] == 0 and r['fits']
 
 
+def _rank_head(what, Tu, Ti, wpack, dims, acts, in_act):
+    """The head of a fused ranker's call, as `recommend`, `recommend_among`, `recommend_group` and `rank_of` marshal it: the width
+    check (ValueError, prefixed by `what`) and the `dims` / `acts` arrays.  Returns (n_users, n_items, dims_c, head): `head()` gives
+    the twelve leading arguments of the entry point, Tu .. in_act; the tensors are looked at (device, dtype, layout) when it is
+    called, in the argument list of the launch, so a wrapper's own host checks keep their place in front of them."""
+    n_users, c1, n_items = int(Tu.shape[0]), int(Tu.shape[1]), int(Ti.shape[0])
+    if int(Ti.shape[1]) != c1:
+        raise ValueError("{}: Tu and Ti must have the same width".format(what))
+    dims_c = (ctypes.c_int32 * len(dims))(*dims)
+    acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
+
+    def head():
+        return (*_mat(Tu, 'Tu'), n_users, *_mat(Ti, 'Ti'), n_items, c1, _ptr(wpack, F32, 'wpack'), dims_c, acts_c, len(acts), ACT_CODES[in_act])
+    return n_users, n_items, dims_c, head
+
+
+def _check_exclusion(what, excl_ptr, excl_items, rows, entries='n_users + 1 entries'):
+    """The two checks of a ranker's exclusion CSR over `rows` rows (ValueError, prefixed by `what`)."""
+    if (excl_ptr is None) != (excl_items is None):
+        raise ValueError("{}: excl_ptr and excl_items go together".format(what))
+    if excl_ptr is not None and excl_ptr.numel() != rows + 1:
+        raise ValueError("{}: excl_ptr must have {}".format(what, entries))
+
+
 def recommend(Tu, Ti, wpack, dims, acts, in_act, k, users=None, excl_ptr=None, excl_items=None, n_slices=0):
     """Fused full-catalogue top-k of the split head (amar_recommend_f32): for every user row of `users` (all rows of Tu when None)
     the k best items of Ti that are not in its exclusion CSR.  Returns (items int32 [m, k] (-1 padded), scores float32 [m, k]).
     n_slices <= 0: the library's automatic item slicing (AMAR_RECOMMEND_SLICES overrides it)."""
-    n_users, c1 = int(Tu.shape[0]), int(Tu.shape[1])
-    n_items = int(Ti.shape[0])
-    if int(Ti.shape[1]) != c1:
-        raise ValueError("recommend: Tu and Ti must have the same width")
+    n_users, n_items, dims_c, head = _rank_head('recommend', Tu, Ti, wpack, dims, acts, in_act)
     m = int(users.numel()) if users is not None else n_users
-    if n_slices <= 0:
-        n_slices = int(os.environ.get('AMAR_RECOMMEND_SLICES', '0'))
-    dims_c = (ctypes.c_int32 * len(dims))(*dims)
-    acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
-    slices, out_items, out_scores, ws_i = _sliced_topk('amar_recommend_slices', (m, n_items, dims_c, len(acts), int(n_slices)), m, k, Tu.device)
-    ws_s = torch.empty((m * slices * k,), dtype=torch.float32, device=Tu.device) if slices > 1 else None
-    if (excl_ptr is None) != (excl_items is None):
-        raise ValueError("recommend: excl_ptr and excl_items go together")
-    if excl_ptr is not None and excl_ptr.numel() != n_users + 1:
-        raise ValueError("recommend: excl_ptr must have n_users + 1 entries")
-    _launch('amar_recommend_f32', *_mat(Tu, 'Tu'), n_users, *_mat(Ti, 'Ti'), n_items, c1, _ptr(wpack, F32, 'wpack'), dims_c, acts_c, len(acts),
-            ACT_CODES[in_act], _ptr(users, I32, 'users'), m, _ptr(excl_ptr, I32, 'excl_ptr'), _ptr_entries(excl_items, I32, 'excl_items'),
-            int(k), int(slices) if slices > 1 else 1, _ptr(ws_i), _ptr(ws_s),
+    slices, out_items, out_scores, ws_i, ws_s = _sliced_topk('amar_recommend_slices', (m, n_items, dims_c, len(acts)), n_slices, m, k, Tu.device)
+    _check_exclusion('recommend', excl_ptr, excl_items, n_users)
+    _launch('amar_recommend_f32', *head(), _ptr(users, I32, 'users'), m, _ptr(excl_ptr, I32, 'excl_ptr'),
+            _ptr_entries(excl_items, I32, 'excl_items'), int(k), int(slices) if slices > 1 else 1, _ptr(ws_i), _ptr(ws_s),
             _ptr(out_items) if m else None, _ptr(out_scores) if m else None)
     return out_items, out_scores
 
@@ -1522,26 +1539,14 @@ def recommend_among(Tu, Ti, wpack, dims, acts, in_act, k, cand, users=None, excl
     cannot check it.  Returns (items int32 [m, k] item rows (-1 padded), scores float32 [m, k] (-inf padded)): what `recommend`
     returns with the complement of `cand` merged into every exclusion row, bit for bit.  n_slices <= 0: the library's automatic
     slicing of the candidate positions (AMAR_RECOMMEND_SLICES overrides it)."""
-    n_users, c1 = int(Tu.shape[0]), int(Tu.shape[1])
-    n_items = int(Ti.shape[0])
-    if int(Ti.shape[1]) != c1:
-        raise ValueError("recommend_among: Tu and Ti must have the same width")
+    n_users, n_items, dims_c, head = _rank_head('recommend_among', Tu, Ti, wpack, dims, acts, in_act)
     rows = check_candidate_rows(cand, n_items)
     n_cand = int(rows.size)
-    if (excl_ptr is None) != (excl_items is None):
-        raise ValueError("recommend_among: excl_ptr and excl_items go together")
-    if excl_ptr is not None and excl_ptr.numel() != n_users + 1:
-        raise ValueError("recommend_among: excl_ptr must have n_users + 1 entries")
+    _check_exclusion('recommend_among', excl_ptr, excl_items, n_users)
     m = int(users.numel()) if users is not None else n_users
-    if n_slices <= 0:
-        n_slices = int(os.environ.get('AMAR_RECOMMEND_SLICES', '0'))
-    dims_c = (ctypes.c_int32 * len(dims))(*dims)
-    acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
-    slices, out_items, out_scores, ws_i = _sliced_topk('amar_recommend_slices', (m, n_cand, dims_c, len(acts), int(n_slices)), m, k, Tu.device)
-    ws_s = torch.empty((m * slices * k,), dtype=torch.float32, device=Tu.device) if slices > 1 else None
+    slices, out_items, out_scores, ws_i, ws_s = _sliced_topk('amar_recommend_slices', (m, n_cand, dims_c, len(acts)), n_slices, m, k, Tu.device)
     cand_dev = torch.from_numpy(rows).to(Tu.device) if n_cand else None
-    _launch('amar_recommend_among_f32', *_mat(Tu, 'Tu'), n_users, *_mat(Ti, 'Ti'), n_items, c1, _ptr(wpack, F32, 'wpack'), dims_c, acts_c,
-            len(acts), ACT_CODES[in_act], _ptr(users, I32, 'users'), m, _ptr(excl_ptr, I32, 'excl_ptr'),
+    _launch('amar_recommend_among_f32', *head(), _ptr(users, I32, 'users'), m, _ptr(excl_ptr, I32, 'excl_ptr'),
             _ptr_entries(excl_items, I32, 'excl_items'), _ptr(cand_dev, I32, 'cand'), n_cand,
             int(k), int(slices) if slices > 1 else 1, _ptr(ws_i), _ptr(ws_s),
             _ptr(out_items) if m else None, _ptr(out_scores) if m else None)
@@ -1561,26 +1566,14 @@ def recommend_group(Tu, Ti, wpack, dims, acts, in_act, k, grp_ptr, grp_users, st
     (AMAR_RECOMMEND_SLICES overrides it)."""
     if strategy not in GROUP_STRATEGIES:
         raise ValueError("recommend_group: strategy must be one of {} (got {!r})".format(sorted(GROUP_STRATEGIES), strategy))
-    n_users, c1 = int(Tu.shape[0]), int(Tu.shape[1])
-    n_items = int(Ti.shape[0])
-    if int(Ti.shape[1]) != c1:
-        raise ValueError("recommend_group: Tu and Ti must have the same width")
+    n_users, n_items, dims_c, head = _rank_head('recommend_group', Tu, Ti, wpack, dims, acts, in_act)
     g, n_members = int(grp_ptr.numel()) - 1, int(grp_users.numel())
     if g < 0:
         raise ValueError("recommend_group: grp_ptr must have one entry per group plus one")
-    if (excl_ptr is None) != (excl_items is None):
-        raise ValueError("recommend_group: excl_ptr and excl_items go together")
-    if excl_ptr is not None and excl_ptr.numel() != g + 1:
-        raise ValueError("recommend_group: excl_ptr must have one entry per group plus one")
-    if n_slices <= 0:
-        n_slices = int(os.environ.get('AMAR_RECOMMEND_SLICES', '0'))
-    dims_c = (ctypes.c_int32 * len(dims))(*dims)
-    acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
-    slices, out_items, out_scores, ws_i = _sliced_topk('amar_recommend_group_slices', (g, n_members, n_items, dims_c, len(acts), int(n_slices)),
-                                                       g, k, Tu.device)
-    ws_s = torch.empty((g * slices * k,), dtype=torch.float32, device=Tu.device) if slices > 1 else None
-    _launch('amar_recommend_group_f32', *_mat(Tu, 'Tu'), n_users, *_mat(Ti, 'Ti'), n_items, c1, _ptr(wpack, F32, 'wpack'), dims_c, acts_c,
-            len(acts), ACT_CODES[in_act], _ptr(grp_ptr, I32, 'grp_ptr'), _ptr_entries(grp_users, I32, 'grp_users'), g, n_members,
+    _check_exclusion('recommend_group', excl_ptr, excl_items, g, 'one entry per group plus one')
+    slices, out_items, out_scores, ws_i, ws_s = _sliced_topk('amar_recommend_group_slices', (g, n_members, n_items, dims_c, len(acts)), n_slices,
+                                                             g, k, Tu.device)
+    _launch('amar_recommend_group_f32', *head(), _ptr(grp_ptr, I32, 'grp_ptr'), _ptr_entries(grp_users, I32, 'grp_users'), g, n_members,
             _ptr(excl_ptr, I32, 'excl_ptr'), _ptr_entries(excl_items, I32, 'excl_items'), GROUP_STRATEGIES[strategy],
             float('-inf') if min_score is None else float(min_score), int(k), int(slices) if slices > 1 else 1, _ptr(ws_i), _ptr(ws_s),
             _ptr(out_items) if g else None, _ptr(out_scores) if g else None)
@@ -1613,7 +1606,7 @@ def nearest(Q, T, k, metric='cosine', query_rows=None, excl_ptr=None, excl_rows=
         raise ValueError("nearest: excl_ptr must have one entry per listed query plus one")
     lib = load()
     metric_code = NEAREST_METRICS[metric]
-    slices, out_rows, out_scores, ws_r = _sliced_topk('amar_nearest_slices', (m, n_rows, d, int(n_slices)), m, k, Q.device)
+    slices, out_rows, out_scores, ws_r, _ = _sliced_topk('amar_nearest_slices', (m, n_rows, d), n_slices, m, k, Q.device, split_head=False)
     floats = lib.amar_nearest_workspace_floats(m, n_rows, int(k), metric_code, int(slices))
     if floats < 0:
         _check(int(floats), 'amar_nearest_workspace_floats')
@@ -1706,14 +1699,8 @@ def rank_of(Tu, Ti, wpack, dims, acts, in_act, users, tgt_ptr, tgt_items, excl_p
     full ranking (score descending, item row ascending) among the items outside the user's exclusion row.
     n_slices <= 0: the library's automatic item slicing."""
     import numpy as np
-    n_users, c1 = int(Tu.shape[0]), int(Tu.shape[1])
-    n_items = int(Ti.shape[0])
-    if int(Ti.shape[1]) != c1:
-        raise ValueError("rank_of: Tu and Ti must have the same width")
-    if (excl_ptr is None) != (excl_items is None):
-        raise ValueError("rank_of: excl_ptr and excl_items go together")
-    if excl_ptr is not None and excl_ptr.numel() != n_users + 1:
-        raise ValueError("rank_of: excl_ptr must have n_users + 1 entries")
+    n_users, n_items, _, head = _rank_head('rank_of', Tu, Ti, wpack, dims, acts, in_act)
+    _check_exclusion('rank_of', excl_ptr, excl_items, n_users)
     items = np.ascontiguousarray(np.asarray(tgt_items).reshape(-1), dtype=np.int32)
     if split:
         users_h, ptr_h = rank_of_entries(users, tgt_ptr)
@@ -1732,12 +1719,9 @@ def rank_of(Tu, Ti, wpack, dims, acts, in_act, users, tgt_ptr, tgt_items, excl_p
     _ptr(Tu, F32, 'Tu')                                                # (a host tensor is refused before anything is allocated beside it)
     scores = torch.empty(n_targets, dtype=torch.float32, device=dev)
     greater, before, after = (torch.empty(n_targets, dtype=torch.int32, device=dev) for _ in range(3))
-    dims_c = (ctypes.c_int32 * len(dims))(*dims)
-    acts_c = (ctypes.c_int32 * len(acts))(*[ACT_CODES[a] for a in acts])
     users_d, ptr_d, items_d = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (users_h, ptr_h, items))
     longest = int(np.diff(ptr_h.astype(np.int64)).max()) if m else 0
-    _launch('amar_rank_of_f32', *_mat(Tu, 'Tu'), n_users, *_mat(Ti, 'Ti'), n_items, c1, _ptr(wpack, F32, 'wpack'), dims_c, acts_c, len(acts),
-            ACT_CODES[in_act], _ptr_entries(users_d, I32, 'users'), m, _ptr(excl_ptr, I32, 'excl_ptr'), _ptr_entries(excl_items, I32, 'excl_items'),
+    _launch('amar_rank_of_f32', *head(), _ptr_entries(users_d, I32, 'users'), m, _ptr(excl_ptr, I32, 'excl_ptr'), _ptr_entries(excl_items, I32, 'excl_items'),
             _ptr(ptr_d, I32, 'tgt_ptr'), _ptr_entries(items_d, I32, 'tgt_items'), n_targets, longest, int(n_slices) if n_slices > 0 else 0,
             _ptr_entries(scores, F32, 'scores'), _ptr_entries(greater, I32, 'greater'), _ptr_entries(before, I32, 'eq_before'),
             _ptr_entries(after, I32, 'eq_after'))

@@ -114,11 +114,9 @@ extern "C" {
 
 int32_t amar_recommend_group_slices(int64_t n_groups, int64_t n_members, int32_t n_items, const int32_t *dims, int32_t n_layers,
                                     int32_t n_slices) {
-    if (n_groups < 0 || n_members < 0 || n_items < 0 || !dims || n_layers < 2 || n_layers > RANK_MAX_LAYERS + 1) return AMAR_EINVAL;
     RankShape s;
-    const int rc = rank_shape(dims, n_layers, s);
-    if (rc != AMAR_OK) return rc;
-    return group_slices(n_groups, n_members, n_items, s.tile_items, n_slices);
+    const int rc = rank_slices_tile(n_groups, n_members, n_items, dims, n_layers, s);
+    return rc != AMAR_OK ? rc : group_slices(n_groups, n_members, n_items, s.tile_items, n_slices);
 }
 
 int amar_recommend_group_f32(const float *Tu, int64_t ldu, int32_t n_users, const float *Ti, int64_t ldi, int32_t n_items, int32_t c1,
@@ -133,39 +131,13 @@ int amar_recommend_group_f32(const float *Tu, int64_t ldu, int32_t n_users, cons
     if ((n_groups > 0 && !grp_ptr) || (n_members > 0 && !grp_users)) return AMAR_EINVAL;
     if (excl_ptr && !excl_items) return AMAR_EINVAL;
     if (k > 64) return AMAR_EUNSUPPORTED;
-    int rc = rank_check_tables(Tu, ldu, Ti, ldi, c1, wpack, dims, n_layers, in_act);
-    if (rc != AMAR_OK) return rc;
+    const RankHead head = {Tu, ldu, Ti, ldi, n_items, c1, wpack, dims, acts, n_layers, in_act, grp_users, excl_ptr, excl_items};
     GroupArgs ga{};
-    RankArgs &a = ga.r;
-    RankShape sh;
-    amar_rank_route_info route;
-    rc = rank_route(AMAR_RANK_GROUP, dims, acts, n_layers, a, sh, route);
-    if (rc != AMAR_OK) return rc;
-    const int32_t slices = group_slices(n_groups, n_members, n_items, sh.tile_items, n_slices);
-    if (slices < 1) return slices < 0 ? slices : AMAR_EINVAL;
-    if (n_slices > 0 && slices != n_slices) return AMAR_EINVAL;       // the caller sizes the workspace from amar_recommend_group_slices
-    if (slices > 1 && (!workspace_items || !workspace_scores)) return AMAR_EINVAL;
-    if (n_groups == 0) return AMAR_OK;
-    if (!out_items || !out_scores) return AMAR_EINVAL;
-    a.Tu = Tu; a.ldu = ldu; a.Ti = Ti; a.ldi = ldi; a.c1 = c1; a.n_items = n_items;
-    a.users = grp_users; a.m = n_groups; a.excl_ptr = excl_ptr; a.excl_items = excl_items;
-    a.wpack = wpack; a.in_act = in_act; a.out.k = k;
-    a.slice_items = (int)rank_slice_rows(n_items, sh.tile_items, slices);
-    a.out.n_slices = slices;
-    a.out.rows = slices > 1 ? workspace_items : out_items;
-    a.out.scores = slices > 1 ? workspace_scores : out_scores;
     ga.grp_ptr = grp_ptr; ga.strategy = strategy; ga.min_score = min_score;
-    if (!route.fits) return AMAR_EUNSUPPORTED;
-    const size_t lds_bytes = (size_t)route.lds_bytes;
-    const int64_t blocks = (n_groups + RANK_UB - 1) / RANK_UB;
-    if (blocks >= (1ll << 31)) return AMAR_EUNSUPPORTED;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)blocks, (unsigned)slices), block(256);
-    static bool done[4][AMAR_MAX_DEVICES];
-    AMAR_RANK_DISPATCH(recommend_group_kernel, route.maxt, grid, block, lds_bytes, st, ga, done)
-    const int e = amar_check_launch();
-    if (e != AMAR_OK || slices == 1) return e;
-    return rank_merge_slices(workspace_items, workspace_scores, n_groups, slices, k, out_items, out_scores, st);
+    static RankForms<GroupArgs> forms = AMAR_RANK_FORMS(recommend_group_kernel);
+    return rank_topk(forms, AMAR_RANK_GROUP, head, ga, n_groups, n_items,
+                     amar_recommend_group_slices(n_groups, n_members, n_items, dims, n_layers, n_slices), n_slices, k,
+                     workspace_items, workspace_scores, out_items, out_scores, stream);
 }
 
 }  // extern "C"

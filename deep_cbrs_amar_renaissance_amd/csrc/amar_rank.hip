@@ -172,11 +172,9 @@ int rank_merge_slices(const int32_t *part_rows, const float *part_scores, int64_
 extern "C" {
 
 int32_t amar_recommend_slices(int64_t m, int32_t n_items, const int32_t *dims, int32_t n_layers, int32_t n_slices) {
-    if (m < 0 || n_items < 0 || !dims || n_layers < 2 || n_layers > RANK_MAX_LAYERS + 1) return AMAR_EINVAL;
     RankShape s;
-    const int rc = rank_shape(dims, n_layers, s);
-    if (rc != AMAR_OK) return rc;
-    return rank_slices(m, n_items, s.tile_items, RANK_UB, n_slices);
+    const int rc = rank_slices_tile(m, 0, n_items, dims, n_layers, s);
+    return rc != AMAR_OK ? rc : rank_slices(m, n_items, s.tile_items, RANK_UB, n_slices);
 }
 
 int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const float *Ti, int64_t ldi, int32_t n_items, int32_t c1,
@@ -188,37 +186,11 @@ int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const floa
     if (k > 64) return AMAR_EUNSUPPORTED;
     if (!users && m != n_users) return AMAR_EINVAL;
     if (excl_ptr && !excl_items) return AMAR_EINVAL;
-    int rc = rank_check_tables(Tu, ldu, Ti, ldi, c1, wpack, dims, n_layers, in_act);
-    if (rc != AMAR_OK) return rc;
+    const RankHead head = {Tu, ldu, Ti, ldi, n_items, c1, wpack, dims, acts, n_layers, in_act, users, excl_ptr, excl_items};
     RankArgs a{};
-    RankShape sh;
-    amar_rank_route_info route;
-    rc = rank_route(AMAR_RANK_RECOMMEND, dims, acts, n_layers, a, sh, route);
-    if (rc != AMAR_OK) return rc;
-    const int32_t slices = amar_recommend_slices(m, n_items, dims, n_layers, n_slices);
-    if (slices < 1) return slices < 0 ? slices : AMAR_EINVAL;
-    if (n_slices > 0 && slices != n_slices) return AMAR_EINVAL;       // the caller sizes the workspace from amar_recommend_slices
-    if (slices > 1 && (!workspace_items || !workspace_scores)) return AMAR_EINVAL;
-    if (m == 0) return AMAR_OK;
-    if (!out_items || !out_scores) return AMAR_EINVAL;
-    a.Tu = Tu; a.ldu = ldu; a.Ti = Ti; a.ldi = ldi; a.c1 = c1; a.n_items = n_items;
-    a.users = users; a.m = m; a.excl_ptr = excl_ptr; a.excl_items = excl_items;
-    a.wpack = wpack; a.in_act = in_act; a.out.k = k;
-    a.slice_items = (int)rank_slice_rows(n_items, sh.tile_items, slices);
-    a.out.n_slices = slices;
-    a.out.rows = slices > 1 ? workspace_items : out_items;
-    a.out.scores = slices > 1 ? workspace_scores : out_scores;
-    if (!route.fits) return AMAR_EUNSUPPORTED;
-    const size_t lds_bytes = (size_t)route.lds_bytes;
-    const int64_t blocks = (m + RANK_UB - 1) / RANK_UB;
-    if (blocks >= (1ll << 31)) return AMAR_EUNSUPPORTED;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)blocks, (unsigned)slices), block(256);
-    static bool done[4][AMAR_MAX_DEVICES];
-    AMAR_RANK_DISPATCH(recommend_kernel, route.maxt, grid, block, lds_bytes, st, a, done)
-    const int e = amar_check_launch();
-    if (e != AMAR_OK || slices == 1) return e;
-    return rank_merge_slices(workspace_items, workspace_scores, m, slices, k, out_items, out_scores, st);
+    static RankForms<RankArgs> forms = AMAR_RANK_FORMS(recommend_kernel);
+    return rank_topk(forms, AMAR_RANK_RECOMMEND, head, a, m, n_items, amar_recommend_slices(m, n_items, dims, n_layers, n_slices), n_slices, k,
+                     workspace_items, workspace_scores, out_items, out_scores, stream);
 }
 
 int amar_rank_route(int32_t kind, const int32_t *dims, int32_t n_layers, amar_rank_route_info *info) {

@@ -268,11 +268,9 @@ __global__ __launch_bounds__(256) void rank_of_metrics_kernel(const float *__res
 extern "C" {
 
 int32_t amar_rank_of_slices(int64_t m, int32_t n_items, const int32_t *dims, int32_t n_layers, int32_t n_slices) {
-    if (m < 0 || n_items < 0 || !dims || n_layers < 2 || n_layers > RANK_MAX_LAYERS + 1) return AMAR_EINVAL;
     RankShape s;
-    const int rc = rank_shape(dims, n_layers, s);
-    if (rc != AMAR_OK) return rc;
-    return rank_slices(m, n_items, s.tile_items, RANK_UB, n_slices);
+    const int rc = rank_slices_tile(m, 0, n_items, dims, n_layers, s);
+    return rc != AMAR_OK ? rc : rank_slices(m, n_items, s.tile_items, RANK_UB, n_slices);
 }
 
 int amar_rank_of_f32(const float *Tu, int64_t ldu, int32_t n_users, const float *Ti, int64_t ldi, int32_t n_items, int32_t c1,
@@ -285,26 +283,21 @@ int amar_rank_of_f32(const float *Tu, int64_t ldu, int32_t n_users, const float 
     if (excl_ptr && !excl_items) return AMAR_EINVAL;
     if ((m > 0 && !tgt_ptr) || (n_targets > 0 && !tgt_items)) return AMAR_EINVAL;
     if (n_targets > 0 && (!out_scores || !out_greater || !out_eq_before || !out_eq_after)) return AMAR_EINVAL;
-    int rc = rank_check_tables(Tu, ldu, Ti, ldi, c1, wpack, dims, n_layers, in_act);
-    if (rc != AMAR_OK) return rc;
+    const RankHead head = {Tu, ldu, Ti, ldi, n_items, c1, wpack, dims, acts, n_layers, in_act, users, excl_ptr, excl_items};
     RankOfArgs ra{};
     RankArgs &a = ra.r;
     RankShape sh;
     amar_rank_route_info route;
-    rc = rank_route(AMAR_RANK_RANK_OF, dims, acts, n_layers, a, sh, route);
+    const int rc = rank_prepare(AMAR_RANK_RANK_OF, head, m, a, sh, route);
     if (rc != AMAR_OK) return rc;
     if (max_targets > AMAR_RANK_OF_MAX_TARGETS || n_targets >= (1ll << 31)) return AMAR_EUNSUPPORTED;
     const int32_t slices = amar_rank_of_slices(m, n_items, dims, n_layers, n_slices);
     if (slices < 1) return slices < 0 ? slices : AMAR_EINVAL;
     if (n_slices > 0 && slices != n_slices) return AMAR_EINVAL;
-    a.Tu = Tu; a.ldu = ldu; a.Ti = Ti; a.ldi = ldi; a.c1 = c1; a.n_items = n_items;
-    a.users = users; a.m = m; a.excl_ptr = excl_ptr; a.excl_items = excl_items;
-    a.wpack = wpack; a.in_act = in_act;
     a.slice_items = (int)rank_slice_rows(n_items, sh.tile_items, slices);
     ra.tgt_ptr = tgt_ptr; ra.tgt_items = tgt_items; ra.gather_floats = rank_of_gather_floats(sh);
     ra.out_scores = out_scores; ra.out_greater = out_greater; ra.out_before = out_eq_before; ra.out_after = out_eq_after;
     if (!route.fits) return AMAR_EUNSUPPORTED;
-    const size_t lds_bytes = (size_t)route.lds_bytes;
     const int64_t blocks = (m + RANK_UB - 1) / RANK_UB;
     if (blocks >= (1ll << 31)) return AMAR_EUNSUPPORTED;
     if (m == 0 || n_targets == 0) return AMAR_OK;
@@ -314,10 +307,8 @@ int amar_rank_of_f32(const float *Tu, int64_t ldu, int32_t n_users, const float 
         const hipError_t e = hipMemsetAsync(counts[c], 0, (size_t)n_targets * sizeof(int32_t), st);
         if (e != hipSuccess) { amar_tls_hip_error = (int)e; return AMAR_ELAUNCH; }
     }
-    const dim3 grid((unsigned)blocks, (unsigned)slices), block(256);
-    static bool done[4][AMAR_MAX_DEVICES];
-    AMAR_RANK_DISPATCH(rank_of_kernel, route.maxt, grid, block, lds_bytes, st, ra, done)
-    return amar_check_launch();
+    static RankForms<RankOfArgs> forms = AMAR_RANK_FORMS(rank_of_kernel);
+    return rank_launch_form(forms, route, dim3((unsigned)blocks, (unsigned)slices), st, ra);
 }
 
 int amar_rank_of_metrics_f64(const float *scores, const int32_t *greater, const int32_t *eq_before, const int32_t *eq_after,

@@ -1,14 +1,17 @@
-// What the fused rankers of the split head share (amar_rank.hip: one user per selector; amar_group.hip: a group of users per
-// selector) besides the selector of amar_rank_select.h:
+// What the fused rankers of the split head share (amar_rank.hip: one user per selector; amar_rank_among.hip: the same over a
+// candidate list; amar_group.hip: a group of users per selector; amar_rank_of.hip: counting instead of selecting) besides the
+// selector of amar_rank_select.h:
 //   * RankArgs, the kernels' argument block, and the constants of their decomposition;
-//   * the score stage itself is amar_rank_score.inc, a fragment both kernel bodies include (one text, the same bits per pair);
+//   * the score stage itself is amar_rank_score.inc, a fragment every kernel body includes (one text, the same bits per pair);
 //   * device helpers around it, as amar_group.hip uses them: the packed rest stack and an item tile go to LDS
 //     (rank_stage_weights, rank_stage_tile), a user's Tu row becomes MFMA fragments (rank_load_user).  recommend_kernel keeps these
 //     few lines in its own body, as it always had them: it must compile to what it compiled to;
 //   * host: the argument checks the entry points share (rank_check_tables), the walk over the packed stack (rank_pack_args), the
 //     launch geometry of a stack (rank_shape), the LDS a launch needs (rank_lds_bytes, rank_of_lds_bytes), rank_route — the one
-//     function the three launchers and the query amar_rank_route take all of that and the capacity refusal from — and the
-//     MAXT / PT dispatch (AMAR_RANK_DISPATCH).
+//     function the four launchers and the query amar_rank_route take all of that and the capacity refusal from — and the launch
+//     path itself: rank_prepare (tables, route, the argument fields every ranker sets alike), rank_launch_form (the MAXT / PT
+//     dispatch over a kernel's four forms), rank_topk (everything the three top-k launchers do after their own leading checks)
+//     and rank_slices_tile (what the *_slices queries check before they count).
 #pragma once
 #include "amar_common.h"
 #include "amar_rank_select.h"
@@ -166,23 +169,93 @@ inline int rank_route(int kind, const int32_t *dims, const int32_t *acts, int32_
     return AMAR_OK;
 }
 
-}  // namespace
+// ---- the launch path ------------------------------------------------------------------------------------------------------------
+// The head arguments the four entry points take alike (`users`: the user row of a selector; amar_group.hip: the members).
+struct RankHead {
+    const float *Tu; int64_t ldu; const float *Ti; int64_t ldi; int32_t n_items, c1;
+    const float *wpack; const int32_t *dims, *acts; int32_t n_layers, in_act;
+    const int32_t *users, *excl_ptr, *excl_items;
+};
 
-// Launches KERN<MAXT, PT> for the stack's shape (the four forms 1/4, 2/4, 4/2, 8/1), allowing it the large LDS where the launch
-// needs more than 64 KB.  `done`: the call site's static bool [4][AMAR_MAX_DEVICES].  Returns from the caller on a refusal.
-#define AMAR_RANK_LAUNCH_FORM(KERN, MT, PTT, D, grid, block, lds_bytes, st, args, done)                                 \
-    do {                                                                                                                \
-        auto kern = KERN<MT, PTT>;                                                                                      \
-        if ((lds_bytes) > RANK_LDS_PLAIN) {                                                                             \
-            const int e = amar_allow_lds(reinterpret_cast<const void *>(kern), RANK_LDS_LIMIT, done[D]);               \
-            if (e != AMAR_OK) return e;                                                                                 \
-        }                                                                                                               \
-        hipLaunchKernelGGL(kern, grid, block, lds_bytes, st, args);                                                     \
-    } while (0)
-#define AMAR_RANK_DISPATCH(KERN, maxt, grid, block, lds_bytes, st, args, done)                                          \
-    switch (maxt) {                                                                                                     \
-    case 1: AMAR_RANK_LAUNCH_FORM(KERN, 1, 4, 0, grid, block, lds_bytes, st, args, done); break;                        \
-    case 2: AMAR_RANK_LAUNCH_FORM(KERN, 2, 4, 1, grid, block, lds_bytes, st, args, done); break;                        \
-    case 4: AMAR_RANK_LAUNCH_FORM(KERN, 4, 2, 2, grid, block, lds_bytes, st, args, done); break;                        \
-    default: AMAR_RANK_LAUNCH_FORM(KERN, 8, 1, 3, grid, block, lds_bytes, st, args, done); break;                       \
+// The first half of every launcher once its own leading checks have passed: the table check, the route, and the fields of `a`
+// that all four set alike (`m`: the selector rows).  slice_items and out stay with the caller.
+inline int rank_prepare(int kind, const RankHead &h, int64_t m, RankArgs &a, RankShape &sh, amar_rank_route_info &route) {
+    int rc = rank_check_tables(h.Tu, h.ldu, h.Ti, h.ldi, h.c1, h.wpack, h.dims, h.n_layers, h.in_act);
+    if (rc != AMAR_OK) return rc;
+    rc = rank_route(kind, h.dims, h.acts, h.n_layers, a, sh, route);
+    if (rc != AMAR_OK) return rc;
+    a.Tu = h.Tu; a.ldu = h.ldu; a.Ti = h.Ti; a.ldi = h.ldi; a.c1 = h.c1; a.n_items = h.n_items;
+    a.users = h.users; a.m = m; a.excl_ptr = h.excl_ptr; a.excl_items = h.excl_items;
+    a.wpack = h.wpack; a.in_act = h.in_act;
+    return AMAR_OK;
+}
+
+// The four instantiated forms of a ranking kernel, KERN<MAXT, PT> = <1, 4> <2, 4> <4, 2> <8, 1> in this order, and which of them
+// has been allowed the large LDS on which device.  One static object per call site (AMAR_RANK_FORMS names the instantiations).
+template <class Args>
+struct RankForms {
+    void (*kern[4])(Args);
+    bool done[4][AMAR_MAX_DEVICES];
+};
+#define AMAR_RANK_FORMS(KERN) {{KERN<1, 4>, KERN<2, 4>, KERN<4, 2>, KERN<8, 1>}, {}}
+
+// Launches the form of the stack's shape (route.maxt) on 256 threads, allowing it the large LDS where the launch needs more than
+// 64 KB (once per device and form), and checks the launch.
+template <class Args>
+inline int rank_launch_form(RankForms<Args> &forms, const amar_rank_route_info &route, dim3 grid, hipStream_t st, const Args &args) {
+    const int f = route.maxt == 1 ? 0 : (route.maxt == 2 ? 1 : (route.maxt == 4 ? 2 : 3));
+    const size_t lds_bytes = (size_t)route.lds_bytes;
+    if (lds_bytes > RANK_LDS_PLAIN) {
+        const int e = amar_allow_lds(reinterpret_cast<const void *>(forms.kern[f]), RANK_LDS_LIMIT, forms.done[f]);
+        if (e != AMAR_OK) return e;
     }
+    hipLaunchKernelGGL(forms.kern[f], grid, dim3(256), lds_bytes, st, args);
+    return amar_check_launch();
+}
+
+// The RankArgs of a kernel's argument block: the block itself, or its first member `r`.
+inline RankArgs &rank_args_of(RankArgs &a) { return a; }
+template <class Args> inline RankArgs &rank_args_of(Args &args) { return args.r; }
+
+// Everything amar_recommend_f32, amar_recommend_among_f32 and amar_recommend_group_f32 do after their own leading checks, in the
+// order their callers rely on: tables, route; the slice count (`slices`: what the entry point's own *_slices rule gave for
+// `n_slices`, negative = its refusal), its cross-check with the count the caller sized the workspaces from, the workspaces; the
+// empty call; the outputs; the fit, the grid limit; the launch and, with several slices, their merge.  `m`: the selector rows
+// (users or groups); `n_rows`: the length the tile loop runs over (items or candidates); `args`: zeroed but for the entry
+// point's own fields.
+template <class Args>
+inline int rank_topk(RankForms<Args> &forms, int kind, const RankHead &h, Args &args, int64_t m, int64_t n_rows, int32_t slices,
+                     int32_t n_slices, int32_t k, int32_t *workspace_items, float *workspace_scores, int32_t *out_items,
+                     float *out_scores, amar_stream_t stream) {
+    RankArgs &a = rank_args_of(args);
+    RankShape sh;
+    amar_rank_route_info route;
+    const int rc = rank_prepare(kind, h, m, a, sh, route);
+    if (rc != AMAR_OK) return rc;
+    if (slices < 1) return slices < 0 ? slices : AMAR_EINVAL;
+    if (n_slices > 0 && slices != n_slices) return AMAR_EINVAL;       // the caller sizes the workspace from the *_slices query
+    if (slices > 1 && (!workspace_items || !workspace_scores)) return AMAR_EINVAL;
+    if (m == 0) return AMAR_OK;
+    if (!out_items || !out_scores) return AMAR_EINVAL;
+    a.out.k = k;
+    a.slice_items = (int)rank_slice_rows(n_rows, sh.tile_items, slices);
+    a.out.n_slices = slices;
+    a.out.rows = slices > 1 ? workspace_items : out_items;
+    a.out.scores = slices > 1 ? workspace_scores : out_scores;
+    if (!route.fits) return AMAR_EUNSUPPORTED;
+    const int64_t blocks = (m + RANK_UB - 1) / RANK_UB;
+    if (blocks >= (1ll << 31)) return AMAR_EUNSUPPORTED;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int e = rank_launch_form(forms, route, dim3((unsigned)blocks, (unsigned)slices), st, args);
+    if (e != AMAR_OK || slices == 1) return e;
+    return rank_merge_slices(workspace_items, workspace_scores, m, slices, k, out_items, out_scores, st);
+}
+
+// What amar_recommend_slices, amar_rank_of_slices and amar_recommend_group_slices check before they count, and the tile a
+// stack's launches walk (s.tile_items).  `members`: 0 where the query has none.
+inline int rank_slices_tile(int64_t rows, int64_t members, int32_t n_items, const int32_t *dims, int32_t n_layers, RankShape &s) {
+    if (rows < 0 || members < 0 || n_items < 0 || !dims || n_layers < 2 || n_layers > RANK_MAX_LAYERS + 1) return AMAR_EINVAL;
+    return rank_shape(dims, n_layers, s);
+}
+
+}  // namespace

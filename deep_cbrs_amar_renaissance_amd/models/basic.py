@@ -178,34 +178,10 @@ class BasicRS(rec.SimilarSearch, Model):
         """The k best items of every user in `users` (all users by default) among all items of `trainset` — every training pair of
         `trainset.ratings` excluded unless exclude_seen=False.  The towers read `trainset.embeddings` (node-indexed rows).
         Returns (users int64 [m], items int64 [m, k] (node ids, -1 padded), scores float32 [m, k] (-inf padded)), see recommend.py."""
-        rec.check_k(k)
-        rec.check_users(users, len(trainset.users))
-        tables = self._recommend_tables(trainset)
-        split = self._recommend_split(*tables)
-        if split is not None:
-            return rec.fused(split, split[2], trainset, k, users, exclude_seen)
-        return self._recommend_pairs(trainset, k, users, exclude_seen, towers=self.towers(*tables))
+        return super().recommend(trainset, k, users, exclude_seen)
 
-    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None, keep_items=None):
-        rec.check_k(k)
-        rec.check_users(users, len(trainset.users))
-        towers = towers if towers is not None else self.towers(*self._recommend_tables(trainset))
-        return rec.pairs(lambda u, i: self.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device,
-                         keep_items=keep_items)
-
-    def _group_route(self, trainset, kind='group'):
-        tables = self._recommend_tables(trainset)
-        split = self._recommend_split(*tables, kind=kind)
-        if split is not None:
-            return 'fused', split, split[2]
-        towers = self.towers(*tables)
-        return 'pairs', lambda u, i: self.score_towers(towers, u, i), towers[0].device
-
-    def _recommend_route(self, trainset):
-        d = np.asarray(trainset.embeddings).shape[1]
-        if not self.built:
-            self.build_head(d, d)
-        return 'fused' if self._ranker_plan(d, d, 'recommend')[0] is not None else 'pairs'
+    def _scoring_head(self):
+        return self
 
     def _recommend_tables(self, trainset):
         n_users, n_items = len(trainset.users), len(trainset.items)
@@ -402,42 +378,15 @@ class BasicGNN(rec.SimilarSearch, Model, abc.ABC):
         `trainset.ratings` excluded unless exclude_seen=False.  One propagation, the towers once per entity, then one fused
         score-and-select launch (amar_recommend_f32).  Returns (users int64 [m], items int64 [m, k] (node ids, -1 padded),
         scores float32 [m, k] (-inf padded)), see recommend.py."""
-        rec.check_k(k)
-        rec.check_users(users, len(trainset.users))
-        tables = self._recommend_tables(trainset)
-        split = self.rs._recommend_split(*tables)
-        if split is not None:
-            return rec.fused(split, split[2], trainset, k, users, exclude_seen)
-        return self._recommend_pairs(trainset, k, users, exclude_seen, towers=self.rs.towers(*tables))
+        return super().recommend(trainset, k, users, exclude_seen)
 
-    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None, keep_items=None):
-        rec.check_k(k)
-        rec.check_users(users, len(trainset.users))
-        towers = towers if towers is not None else self.rs.towers(*self._recommend_tables(trainset))
-        return rec.pairs(lambda u, i: self.rs.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device,
-                         keep_items=keep_items)
-
-    def _group_route(self, trainset, kind='group'):
-        tables = self._recommend_tables(trainset)
-        split = self.rs._recommend_split(*tables, kind=kind)
-        if split is not None:
-            return 'fused', split, split[2]
-        towers = self.rs.towers(*tables)
-        return 'pairs', lambda u, i: self.rs.score_towers(towers, u, i), towers[0].device
-
-    def _recommend_route(self, trainset):
-        d = self.gnn.output_dim()
-        return 'fused' if self.rs._ranker_plan(d, d, 'recommend')[0] is not None else 'pairs'
+    def _scoring_head(self):
+        return self.rs
 
     def _recommend_tables(self, trainset):
         """User / item rows of one (hoisted) propagation; the model's hoist state is left as it was found."""
         n_users, n_items = len(trainset.users), len(trainset.items)
-        saved = (self.gnn.hoist, getattr(self.gnn, '_hoisted', None), self._towers)
-        self.gnn.hoist = True
-        try:
-            emb = self.gnn(None)
-        finally:
-            self.gnn.hoist, self.gnn._hoisted, self._towers = saved
+        emb = self._propagated()
         return emb[:n_users], emb[n_users:n_users + n_items]
 
     # -- similarity search (recommend.py:SimilarSearch) ---------------------------------------------------------------

@@ -273,28 +273,17 @@ class HybridCBRS(rec.SimilarSearch, Model):
         """The k best items of every user in `users` (all users by default) among all items of `trainset` (a HybridUserItemEmbeddings:
         node-indexed graph and BERT tables) — every training pair excluded unless exclude_seen=False.  Returns (users int64 [m],
         items int64 [m, k] (node ids, -1 padded), scores float32 [m, k] (-inf padded)), see recommend.py."""
-        return self._recommend_pairs(trainset, k, users, exclude_seen)
+        return super().recommend(trainset, k, users, exclude_seen)
 
-    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None, keep_items=None):
-        rec.check_k(k)
-        rec.check_users(users, len(trainset.users))
-        towers = towers if towers is not None else self._recommend_towers(trainset)
-        return rec.pairs(lambda u, i: self.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device,
-                         keep_items=keep_items)
+    def _scoring_head(self):
+        return self
 
-    def _group_route(self, trainset, kind='group'):
-        towers = self._recommend_towers(trainset)
-        return 'pairs', lambda u, i: self.score_towers(towers, u, i), towers[0].device
-
-    def _recommend_route(self, trainset):
-        return 'pairs'
-
-    def _recommend_towers(self, trainset):
+    def _recommend_tables(self, trainset):
         n_users, n_items = len(trainset.users), len(trainset.items)
         g, b = to_device_tensor(trainset.graph_embeddings), to_device_tensor(trainset.bert_embeddings)
         if not self.built:
             self.build_head(g.shape[1], b.shape[1])
-        return self.towers(g[:n_users], g[n_users:n_users + n_items], b[:n_users], b[n_users:n_users + n_items])
+        return g[:n_users], g[n_users:n_users + n_items], b[:n_users], b[n_users:n_users + n_items]
 
     # -- similarity search (recommend.py:SimilarSearch) ---------------------------------------------------------------
     def _embedding_spaces(self):
@@ -306,11 +295,7 @@ class HybridCBRS(rec.SimilarSearch, Model):
                 torch.cat([self.dense1b.apply2(ig), self.dense2b.apply2(ib)], dim=1))
 
     def _embedding_tables(self, trainset, space):
-        n_users, n_items = len(trainset.users), len(trainset.items)
-        g, b = to_device_tensor(trainset.graph_embeddings), to_device_tensor(trainset.bert_embeddings)
-        if not self.built:
-            self.build_head(g.shape[1], b.shape[1])
-        return self._first_stage(g[:n_users], g[n_users:n_users + n_items], b[:n_users], b[n_users:n_users + n_items])
+        return self._first_stage(*self._recommend_tables(trainset))
 
     @staticmethod
     def _rows(table, ids, base):
@@ -424,37 +409,26 @@ class HybridBertGNN(rec.SimilarSearch, Model, abc.ABC):
         excluded unless exclude_seen=False.  The BERT rows come from the registered table (`set_bert_table`, or the reference's
         hybrid Sequence, registered as predict() does).  Returns (users int64 [m], items int64 [m, k] (node ids, -1 padded),
         scores float32 [m, k] (-inf padded)), see recommend.py."""
-        return self._recommend_pairs(trainset, k, users, exclude_seen)
+        return super().recommend(trainset, k, users, exclude_seen)
 
-    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None, keep_items=None):
-        rec.check_k(k)
-        rec.check_users(users, len(trainset.users))
-        towers = towers if towers is not None else self._recommend_towers(trainset)
-        return rec.pairs(lambda u, i: self.rs.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device,
-                         keep_items=keep_items)
+    def _scoring_head(self):
+        return self.rs
 
-    def _group_route(self, trainset, kind='group'):
-        towers = self._recommend_towers(trainset)
-        return 'pairs', lambda u, i: self.rs.score_towers(towers, u, i), towers[0].device
-
-    def _recommend_route(self, trainset):
-        return 'pairs'
-
-    def _recommend_towers(self, trainset):
-        n_users, n_items = len(trainset.users), len(trainset.items)
-        self.resident_ids(trainset)                      # the reference's hybrid Sequence: its BERT table, registered as predict() does
+    def _registered_bert(self, trainset):
+        """The resident BERT table; the reference's hybrid Sequence registers its own, as predict() does."""
+        self.resident_ids(trainset)
         if self.bert_table is None:
             raise ValueError("recommend() needs the BERT table: register it with set_bert_table() or pass the hybrid training Sequence")
-        bert = self.bert_table
-        saved = (self.gnn.hoist, getattr(self.gnn, '_hoisted', None), self._towers)
-        self.gnn.hoist = True
-        try:
-            emb = self.gnn(None)
-            if not self.rs.built:
-                self.rs.build_head(emb.shape[1], bert.shape[1])
-            return self.rs.towers(emb[:n_users], emb[n_users:n_users + n_items], bert[:n_users], bert[n_users:n_users + n_items])
-        finally:
-            self.gnn.hoist, self.gnn._hoisted, self._towers = saved
+        return self.bert_table
+
+    def _recommend_tables(self, trainset):
+        """Graph rows of one propagation (the model's hoist state is left as it was found) and the registered BERT rows."""
+        n_users, n_items = len(trainset.users), len(trainset.items)
+        bert = self._registered_bert(trainset)
+        emb = self._propagated()
+        if not self.rs.built:
+            self.rs.build_head(emb.shape[1], bert.shape[1])
+        return emb[:n_users], emb[n_users:n_users + n_items], bert[:n_users], bert[n_users:n_users + n_items]
 
     # -- similarity search (recommend.py:SimilarSearch) ---------------------------------------------------------------
     def _embedding_spaces(self):
@@ -463,25 +437,11 @@ class HybridBertGNN(rec.SimilarSearch, Model, abc.ABC):
     def _embedding_tables(self, trainset, space):
         """'graph': the user / item rows of one propagation (the model's hoist state is left as it was found); 'tower': the
         first-stage networks over them and the registered BERT table, which is needed exactly as recommend() needs it."""
-        n_users, n_items = len(trainset.users), len(trainset.items)
-        bert = None
         if space == 'tower':
-            self.resident_ids(trainset)
-            if self.bert_table is None:
-                raise ValueError("recommend() needs the BERT table: register it with set_bert_table() or pass the hybrid training Sequence")
-            bert = self.bert_table
-        saved = (self.gnn.hoist, getattr(self.gnn, '_hoisted', None), self._towers)
-        self.gnn.hoist = True
-        try:
-            emb = self.gnn(None)
-        finally:
-            self.gnn.hoist, self.gnn._hoisted, self._towers = saved
-        emb_u, emb_i = emb[:n_users], emb[n_users:n_users + n_items]
-        if space == 'graph':
-            return emb_u, emb_i
-        if not self.rs.built:
-            self.rs.build_head(emb.shape[1], bert.shape[1])
-        return self.rs._first_stage(emb_u, emb_i, bert[:n_users], bert[n_users:n_users + n_items])
+            return self.rs._first_stage(*self._recommend_tables(trainset))
+        n_users, n_items = len(trainset.users), len(trainset.items)
+        emb = self._propagated()
+        return emb[:n_users], emb[n_users:n_users + n_items]
 
     def _hoist_begin(self, hoist):
         self.gnn.hoist = bool(hoist)

@@ -423,6 +423,20 @@ def _finish(users, items, scores, n_users):
     return users, items, scores.cpu().numpy().astype(np.float32)
 
 
+def _ranker_args(towers, plan, trainset=None, exclude_seen=False, listed=None):
+    """What the fused routes hand capi's rankers, as (head, keywords): head = (tu, ti, wpack, dims, acts, in_act), their six leading
+    arguments, from the split towers and their plan; with a `trainset`, excl_ptr / excl_items = its exclusion CSR on the device
+    (None without exclude_seen); with `listed` (host user indices), users = those rows as int32 on the towers' device."""
+    blob, dims, acts = plan['rest']
+    kw = {}
+    if trainset is not None:
+        excl = _exclusion_device(trainset, *_sizes(trainset), exclude_seen)
+        kw.update(excl_ptr=excl[0] if excl else None, excl_items=excl[1] if excl else None)
+    if listed is not None:
+        kw['users'] = torch.from_numpy(listed.astype(np.int32)).to(towers[0].device)
+    return (towers[0], towers[1], blob, dims, acts, plan['in_act']), kw
+
+
 def fused(towers, plan, trainset, k, users, exclude_seen):
     """One amar_recommend_f32 call over the split towers (tu [U, c1], ti [I, c1] with b1 folded in)."""
     n_users, n_items = _sizes(trainset)
@@ -430,12 +444,8 @@ def fused(towers, plan, trainset, k, users, exclude_seen):
     u = check_users(users, n_users)
     if len(u) == 0:
         return _empty(k)
-    tu, ti = towers[0], towers[1]
-    excl = _exclusion_device(trainset, n_users, n_items, exclude_seen)
-    blob, dims, acts = plan['rest']
-    u_dev = None if users is None else torch.from_numpy(u.astype(np.int32)).to(tu.device)
-    items, scores = capi.recommend(tu, ti, blob, dims, acts, plan['in_act'], k, users=u_dev,
-                                   excl_ptr=excl[0] if excl else None, excl_items=excl[1] if excl else None)
+    head, kw = _ranker_args(towers, plan, trainset, exclude_seen, None if users is None else u)
+    items, scores = capi.recommend(*head, k, **kw)
     return _finish(u, items, scores, n_users)
 
 
@@ -591,12 +601,8 @@ def among_fused(towers, plan, trainset, cand_rows, k, users, exclude_seen):
     u = check_users(users, n_users)
     if len(u) == 0:
         return _empty(k)
-    tu, ti = towers[0], towers[1]
-    excl = _exclusion_device(trainset, n_users, n_items, exclude_seen)
-    blob, dims, acts = plan['rest']
-    u_dev = None if users is None else torch.from_numpy(u.astype(np.int32)).to(tu.device)
-    items, scores = capi.recommend_among(tu, ti, blob, dims, acts, plan['in_act'], k, cand_rows, users=u_dev,
-                                         excl_ptr=excl[0] if excl else None, excl_items=excl[1] if excl else None)
+    head, kw = _ranker_args(towers, plan, trainset, exclude_seen, None if users is None else u)
+    items, scores = capi.recommend_among(*head, k, cand_rows, **kw)
     return _finish(u, items, scores, n_users)
 
 
@@ -863,12 +869,11 @@ def _i32_device(a, dev):
 def group_fused(towers, plan, grp_ptr, grp_users, excl, k, strategy, min_score):
     """One amar_recommend_group_f32 call over the split towers (tu [U, c1], ti [I, c1] with b1 folded in); `excl` = the host CSR
     over groups or None.  Returns the device tensors (item rows int32 [g, k], scores float32 [g, k])."""
-    tu, ti = towers[0], towers[1]
-    blob, dims, acts = plan['rest']
-    return capi.recommend_group(tu, ti, blob, dims, acts, plan['in_act'], k, _i32_device(grp_ptr, tu.device), _i32_device(grp_users, tu.device),
-                                strategy=strategy, min_score=min_score,
-                                excl_ptr=None if excl is None else _i32_device(excl[0], tu.device),
-                                excl_items=None if excl is None else _i32_device(excl[1], tu.device))
+    head, _ = _ranker_args(towers, plan)
+    dev = head[0].device
+    return capi.recommend_group(*head, k, _i32_device(grp_ptr, dev), _i32_device(grp_users, dev), strategy=strategy, min_score=min_score,
+                                excl_ptr=None if excl is None else _i32_device(excl[0], dev),
+                                excl_items=None if excl is None else _i32_device(excl[1], dev))
 
 
 MEMBER_SCORE_GROUPS = 32             # groups whose chosen items share one compact table in `fused_member_scores`
@@ -880,8 +885,7 @@ def fused_member_scores(towers, plan, grp_ptr, grp_users, rows, per):
     do: for some heads it multiplies on split bf16 operands, a few float32 ulps away.)  Per chunk of MEMBER_SCORE_GROUPS groups the
     chosen items' Ti rows form one compact table, every member is a group of one, and its exclusion segment is the rest of the
     table: one amar_recommend_group_f32 launch per chunk, nothing of size members x |I|."""
-    tu, ti = towers[0], towers[1]
-    blob, dims, acts = plan['rest']
+    (tu, ti, *rest), _ = _ranker_args(towers, plan)
     g, k = rows.shape
     sizes = np.diff(np.asarray(grp_ptr, dtype=np.int64))
     for lo in range(0, g, MEMBER_SCORE_GROUPS):
@@ -897,7 +901,7 @@ def fused_member_scores(towers, plan, grp_ptr, grp_users, rows, per):
         banned = ~allowed.reshape(m1 - m0, c * k)
         e_ptr = np.zeros(m1 - m0 + 1, dtype=np.int64)
         np.cumsum(banned.sum(1), out=e_ptr[1:])
-        items, scores = capi.recommend_group(tu, table, blob, dims, acts, plan['in_act'], k, _i32_device(np.arange(m1 - m0 + 1), tu.device),
+        items, scores = capi.recommend_group(tu, table, *rest, k, _i32_device(np.arange(m1 - m0 + 1), tu.device),
                                              _i32_device(grp_users[m0:m1], tu.device), strategy='max',
                                              excl_ptr=_i32_device(e_ptr, tu.device), excl_items=_i32_device(np.nonzero(banned)[1], tu.device))
         items, scores = items.cpu().numpy(), scores.cpu().numpy()
@@ -993,11 +997,8 @@ def rank_of_fused(towers, plan, trainset, users, targets_csr, exclude_seen):
     n_users, n_items = _sizes(trainset)
     u = check_users(users, n_users)
     ptr, items = check_targets_csr(targets_csr, len(u), n_items)
-    tu, ti = towers[0], towers[1]
-    excl = _exclusion_device(trainset, n_users, n_items, exclude_seen)
-    blob, dims, acts = plan['rest']
-    return capi.rank_of(tu, ti, blob, dims, acts, plan['in_act'], u, ptr, items,
-                        excl_ptr=excl[0] if excl else None, excl_items=excl[1] if excl else None)
+    head, kw = _ranker_args(towers, plan, trainset, exclude_seen)
+    return capi.rank_of(*head, u, ptr, items, **kw)
 
 
 def rank_of_pairs(score_fn, trainset, users, targets_csr, exclude_seen, device=None):
@@ -1124,12 +1125,68 @@ class SimilarSearch:
     def _embedding_spaces(self):
         raise NotImplementedError
 
-    def _group_route(self, trainset, kind='group'):
-        """How the model ranks a catalogue for the fused kernel `kind` ('recommend' | 'group' | 'rank_of': capi.RANK_KINDS), chosen as
-        its `recommend()` chooses: ('fused', (tu, ti, ...), plan) = the split towers and their plan where the head has one and that
-        kernel takes it (capi.rank_fits: the kernels' LDS sums differ, so a head may rank fused in one and by pairs in another),
-        or ('pairs', score_fn(u_ids, i_ids) -> [P, 1] scores, device)."""
+    # -- full-catalogue top-k: the route.  A model says which object scores and which tables one pass of it reads ---------------
+    def _scoring_head(self):
+        """The object that scores pairs (the model itself, or its `rs`): `towers(*tables)` per entity, `score_towers(towers, u_ids,
+        i_ids)` per pair and, where the head has a fused ranking form, `_ranker_plan` / `_recommend_split` (models/basic.py:BasicRS;
+        a head without them always ranks by pairs)."""
         raise NotImplementedError
+
+    def _recommend_tables(self, trainset):
+        """The arguments of the head's `towers()` for one pass over the users and items of `trainset`."""
+        raise NotImplementedError
+
+    def recommend(self, trainset, k=10, users=None, exclude_seen=True):
+        """The k best items of every user in `users` (all users by default) among all items of `trainset` — every training pair of
+        `trainset.ratings` excluded unless exclude_seen=False.  Returns (users int64 [m], items int64 [m, k] (node ids, -1 padded),
+        scores float32 [m, k] (-inf padded)), see the module's docstring.  k and the users are checked before any tower is computed."""
+        check_k(k)
+        check_users(users, len(trainset.users))
+        route = self._group_route(trainset, 'recommend')
+        if route[0] == 'fused':
+            return fused(route[1], route[2], trainset, k, users, exclude_seen)
+        return pairs(route[1], trainset, k, users, exclude_seen, device=route[2])
+
+    def _recommend_pairs(self, trainset, k=10, users=None, exclude_seen=True, towers=None, keep_items=None):
+        """`recommend()` on the pair route, whatever the head (the tests' yardstick of the fused route); `towers`: the head's towers
+        where the caller has them, `keep_items`: candidates as `pairs()` takes them."""
+        check_k(k)
+        check_users(users, len(trainset.users))
+        head = self._scoring_head()
+        towers = towers if towers is not None else head.towers(*self._recommend_tables(trainset))
+        return pairs(lambda u, i: head.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device,
+                     keep_items=keep_items)
+
+    def _group_route(self, trainset, kind='group'):
+        """How the model ranks a catalogue for the fused kernel `kind` ('recommend' | 'group' | 'rank_of' | 'among': capi.RANK_KINDS):
+        ('fused', (tu, ti, ...), plan) = the split towers and their plan where the head has one and that kernel takes it
+        (capi.rank_fits: the kernels' LDS sums differ, so a head may rank fused in one and by pairs in another), or
+        ('pairs', score_fn(u_ids, i_ids) -> [P, 1] scores, device)."""
+        head = self._scoring_head()
+        tables = self._recommend_tables(trainset)
+        split = head._recommend_split(*tables, kind=kind) if hasattr(head, '_recommend_split') else None
+        if split is not None:
+            return 'fused', split, split[2]
+        towers = head.towers(*tables)
+        return 'pairs', lambda u, i: head.score_towers(towers, u, i), towers[0].device
+
+    def _recommend_route(self, trainset):
+        """'fused' or 'pairs': the route `recommend()` takes for this trainset (the tables of one pass give the towers' input width)."""
+        head = self._scoring_head()
+        if not hasattr(head, '_ranker_plan'):
+            return 'pairs'
+        d = self._recommend_tables(trainset)[0].shape[1]
+        return 'fused' if head._ranker_plan(d, d, 'recommend')[0] is not None else 'pairs'
+
+    def _propagated(self):
+        """The node table of one hoisted propagation of a model with a `gnn`; the model's hoist state (`gnn.hoist`, `gnn._hoisted`,
+        `_towers`) is left as it was found."""
+        saved = (self.gnn.hoist, getattr(self.gnn, '_hoisted', None), self._towers)
+        self.gnn.hoist = True
+        try:
+            return self.gnn(None)
+        finally:
+            self.gnn.hoist, self.gnn._hoisted, self._towers = saved
 
     def _embedding_tables(self, trainset, space):
         raise NotImplementedError
