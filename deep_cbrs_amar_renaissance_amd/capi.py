@@ -151,6 +151,7 @@ SIGNATURES = {
     'amar_adam_multi_f32': (ctypes.c_int, [_P, _I32, _I64, _P, _F32, _F32, _F32, _F32, _P, _P]),
     'amar_sum_into_f32': (ctypes.c_int, [_P, _I64, _F32, _P, _P]),
     'amar_topk_segmented_f32': (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
+    'amar_topk_segmented_after_f32': (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     'amar_recommend_slices': (ctypes.c_int32, [_I64, _I32, _P, _I32, _I32]),
     'amar_recommend_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P,
                                           _I32, _I32, _P, _P, _P, _P, _P]),
@@ -159,6 +160,8 @@ SIGNATURES = {
                                                 _I32, _F32, _I32, _I32, _P, _P, _P, _P, _P]),
     'amar_recommend_among_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P,
                                                 _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    'amar_recommend_after_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P,
+                                                _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     'amar_nearest_slices': (ctypes.c_int32, [_I64, _I32, _I32, _I32]),
     'amar_nearest_workspace_floats': (ctypes.c_int64, [_I64, _I32, _I32, _I32, _I32]),
     'amar_nearest_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _P, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
@@ -1428,6 +1431,28 @@ def topk_segmented(seg_ptr, item_ids, scores, k):
     return out_items, out_scores
 
 
+def _check_cursor(what, after_items, after_scores, rows):
+    """The cursor of a paging call: one (item, score) per row, both given (ValueError, prefixed by `what`)."""
+    if after_items is None or after_scores is None:
+        raise ValueError("{}: after_items and after_scores are both required".format(what))
+    if after_items.numel() != rows or after_scores.numel() != rows:
+        raise ValueError("{}: after_items and after_scores must hold one entry per listed row ({} and {} for {})".format(
+            what, after_items.numel(), after_scores.numel(), rows))
+
+
+def topk_segmented_after(seg_ptr, item_ids, scores, k, after_items, after_scores):
+    """amar_topk_segmented_after_f32: `topk_segmented` from a cursor.  User u's list holds the k best pairs strictly after the
+    position (after_scores[u], after_items[u]) (int32 / float32 device arrays of n_users entries) in the order score descending, item
+    id ascending; (+inf, -1) is the start, (-inf, -1) admits nothing.  The scores are only read: one call per page of one scored chunk."""
+    n_users = seg_ptr.numel() - 1
+    _check_cursor('topk_segmented_after', after_items, after_scores, n_users)
+    out_items = torch.empty((n_users, k), dtype=torch.int32, device=scores.device)
+    out_scores = torch.empty((n_users, k), dtype=torch.float32, device=scores.device)
+    _launch('amar_topk_segmented_after_f32', _ptr(seg_ptr, I32, 'seg_ptr'), _ptr(item_ids, I32, 'item_ids'), _ptr(scores, F32, 'scores'),
+            n_users, k, _ptr(after_scores, F32, 'after_scores'), _ptr(after_items, I32, 'after_items'), _ptr(out_items), _ptr(out_scores))
+    return out_items, out_scores
+
+
 def _sliced_topk(slices_fn, slices_args, n_slices, m, k, dev, split_head=True):
     """What the fused rankers allocate alike: the slices the library will launch for the request `n_slices` (its `slices_fn` over
     `slices_args`, then the request; a negative answer raises), the [m, k] outputs and the int32 workspace of the per-slice lists
@@ -1553,7 +1578,26 @@ def recommend_among(Tu, Ti, wpack, dims, acts, in_act, k, cand, users=None, excl
     return out_items, out_scores
 
 
-GROUP_STRATEGIES = {'mean': 0, 'min': 1, 'max': 2}                     # include/amar_hip.h: AMAR_GROUP_MEAN / _MIN / _MAX
+def recommend_after(Tu, Ti, wpack, dims, acts, in_act, k, after_items, after_scores, users=None, excl_ptr=None, excl_items=None, n_slices=0):
+    """Fused top-k after a position of every listed user's ranking (amar_recommend_after_f32): `recommend` with a cursor per listed
+    row.  after_items int32 [m] / after_scores float32 [m] on the device, indexed by the listed row (not by the user row): row j's
+    list holds the k best unexcluded items strictly after (after_scores[j], after_items[j]) in the order score descending, item row
+    ascending.  (+inf, -1) is the start (`recommend`'s output, bit for bit); (-inf, -1), the padding of an exhausted list, admits
+    nothing; the item is only a position (it may be excluded or no row at all).  Returns (items int32 [m, k] (-1 padded), scores
+    float32 [m, k] (-inf padded)); the typical next cursor is (items[:, -1], scores[:, -1]).  n_slices as in `recommend`."""
+    n_users, n_items, dims_c, head = _rank_head('recommend_after', Tu, Ti, wpack, dims, acts, in_act)
+    m = int(users.numel()) if users is not None else n_users
+    _check_cursor('recommend_after', after_items, after_scores, m)
+    slices, out_items, out_scores, ws_i, ws_s = _sliced_topk('amar_recommend_slices', (m, n_items, dims_c, len(acts)), n_slices, m, k, Tu.device)
+    _check_exclusion('recommend_after', excl_ptr, excl_items, n_users)
+    _launch('amar_recommend_after_f32', *head(), _ptr(users, I32, 'users'), m, _ptr(excl_ptr, I32, 'excl_ptr'),
+            _ptr_entries(excl_items, I32, 'excl_items'), _ptr_entries(after_scores, F32, 'after_scores'),
+            _ptr_entries(after_items, I32, 'after_items'), int(k), int(slices) if slices > 1 else 1, _ptr(ws_i), _ptr(ws_s),
+            _ptr(out_items) if m else None, _ptr(out_scores) if m else None)
+    return out_items, out_scores
+
+
+GROUP_STRATEGIES = {'mean': 0, 'min': 1, 'max': 2}                    # include/amar_hip.h: AMAR_GROUP_MEAN / _MIN / _MAX
 
 
 def recommend_group(Tu, Ti, wpack, dims, acts, in_act, k, grp_ptr, grp_users, strategy='mean', min_score=None, excl_ptr=None, excl_items=None,

@@ -17,7 +17,8 @@
 //     below, also amar_nearest.hip's second launch) merges the slices of a user in slice order (the order is a strict total
 //     order, so the result does not depend on the slicing).
 // The result of a user depends on its own Tu row, Ti and the weights only: not on the other users of the block or the call.
-// The pair route's ranker (amar_topk_segmented_f32: scores already in memory, one wave per user) is at the end of the file.
+// The pair route's ranker (amar_topk_segmented_f32: scores already in memory, one wave per user; amar_topk_segmented_after_f32: the
+// same from a cursor) is at the end of the file.
 #include "amar_rank_score.h"
 #include <stdlib.h>
 
@@ -120,18 +121,22 @@ __global__ __launch_bounds__(256) void recommend_merge_kernel(const int32_t *__r
 }
 
 // The pair route's ranker: one wave per user over scores already in memory.  Round t picks the best pair that comes strictly
-// after round t-1's winner in the order of rank_better; items are distinct within a user.
+// after round t-1's winner in the order of rank_better; items are distinct within a user.  AFTER (amar_topk_segmented_after_f32):
+// round 0 starts from the user's cursor (after_scores[u], after_items[u]) instead of (+inf, -1), the position before every pair.
+template <bool AFTER>
 __global__ __launch_bounds__(256) void topk_segmented_kernel(const int32_t *__restrict__ seg_ptr,
                                                               const int32_t *__restrict__ item_ids,
                                                               const float *__restrict__ scores, int n_users, int k,
+                                                              const float *__restrict__ after_scores,
+                                                              const int32_t *__restrict__ after_items,
                                                               int32_t *__restrict__ out_items,
                                                               float *__restrict__ out_scores) {
     const int lane = threadIdx.x & 63;
     const int u = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (u >= n_users) return;
     const int beg = seg_ptr[u], end = seg_ptr[u + 1];
-    float prev_s = INFINITY;
-    int prev_i = -1;
+    float prev_s = AFTER ? after_scores[u] : INFINITY;
+    int prev_i = AFTER ? after_items[u] : -1;
     for (int t = 0; t < k; ++t) {
         float best_s = -INFINITY;
         int best_i = RANK_EMPTY;
@@ -213,8 +218,22 @@ int amar_topk_segmented_f32(const int32_t *seg_ptr, const int32_t *item_ids, con
     if (k > 64) return AMAR_EUNSUPPORTED;
     if (n_users == 0) return AMAR_OK;                                    // nothing to rank: the outputs may be empty (NULL)
     if (!item_ids || !scores || !out_items || !out_scores) return AMAR_EINVAL;
-    hipLaunchKernelGGL(topk_segmented_kernel, dim3((n_users + 3) / 4), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), seg_ptr, item_ids, scores, n_users, k, out_items, out_scores);
+    hipLaunchKernelGGL(topk_segmented_kernel<false>, dim3((n_users + 3) / 4), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), seg_ptr, item_ids, scores, n_users, k, nullptr, nullptr, out_items, out_scores);
+    return amar_check_launch();
+}
+
+int amar_topk_segmented_after_f32(const int32_t *seg_ptr, const int32_t *item_ids, const float *scores,
+                                  int32_t n_users, int32_t k, const float *after_scores, const int32_t *after_items,
+                                  int32_t *out_items, float *out_scores, amar_stream_t stream) {
+    if (n_users < 0 || k < 1 || !seg_ptr) return AMAR_EINVAL;
+    if (k > 64) return AMAR_EUNSUPPORTED;
+    if (!after_scores != !after_items || (n_users > 0 && !after_scores)) return AMAR_EINVAL;
+    if (n_users == 0) return AMAR_OK;                                    // nothing to rank: the outputs may be empty (NULL)
+    if (!item_ids || !scores || !out_items || !out_scores) return AMAR_EINVAL;
+    hipLaunchKernelGGL(topk_segmented_kernel<true>, dim3((n_users + 3) / 4), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), seg_ptr, item_ids, scores, n_users, k, after_scores, after_items, out_items,
+                       out_scores);
     return amar_check_launch();
 }
 

@@ -1,5 +1,5 @@
 // What the fused rankers of the split head share (amar_rank.hip: one user per selector; amar_rank_among.hip: the same over a
-// candidate list; amar_group.hip: a group of users per selector; amar_rank_of.hip: counting instead of selecting) besides the
+// candidate list; amar_rank_after.hip: the same from a cursor; amar_group.hip: a group of users per selector; amar_rank_of.hip: counting) besides the
 // selector of amar_rank_select.h:
 //   * RankArgs, the kernels' argument block, and the constants of their decomposition;
 //   * the score stage itself is amar_rank_score.inc, a fragment every kernel body includes (one text, the same bits per pair);

@@ -402,6 +402,8 @@ class Experimenter:
             self.write_group_recommend(**dict(self.config.parameters.get('group_recommend')))
         if self.config.parameters.get('recommend_among'):
             self.write_recommend_among(**dict(self.config.parameters.get('recommend_among')))
+        if self.config.parameters.get('recommend_deep'):
+            self.write_recommend_deep(**dict(self.config.parameters.get('recommend_deep')))
         self.logger.info('\n' + str(metrics))
         print('\n' + str(metrics))
         return metrics
@@ -578,6 +580,16 @@ class Experimenter:
                               'item': item_ids[items[u, r] - n_users], 'score': scores[u, r]})
         path = path_join(self.predictions_dest, "among_top_{}.tsv".format(k))
         frame.to_csv(path, sep='\t', header=False, index=False)
+        return path
+
+    def write_recommend_deep(self, k=100):
+        """Opt-in (parameters.recommend_deep: {k}): every user's first k unseen items for k up to 1024 (`recommend_deep()`: chained
+        pages past the 64 of one `recommend()` call), written as <predictions_dest>/deep_top_<k>.tsv (user, item, score; original ids)."""
+        k = int(k)
+        users, items, scores = self.model.recommend_deep(self.trainset, k=k)
+        path = path_join(self.predictions_dest, "deep_top_{}.tsv".format(k))
+        recommendations_frame(users, items, scores, self.trainset.users, self.trainset.items).to_csv(
+            path, sep='\t', header=False, index=False)
         return path
 
     def run(self):

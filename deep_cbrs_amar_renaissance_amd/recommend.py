@@ -57,6 +57,12 @@ The eighth part narrows the catalogue: "the best k among THESE items".  ``check_
 or one set per listed user), ``items_with_properties`` builds one from the graph's item-property links, ``among_fused`` is one
 ``amar_recommend_among_f32`` launch over the split towers (|U| x |C| pairs scored, the candidates' rows gathered into the item tile),
 ``pairs(keep_items=...)`` the pair route over the kept pairs, and the mixin's ``recommend_among`` picks between them.
+
+The ninth part pages: "the best k AFTER this position of the user's ranking".  The order is a strict total order, so a position is a
+pair (score, item); ``check_after`` reads the cursors, ``after_fused`` is one ``amar_recommend_after_f32`` launch (``fused`` with one
+more compare per pair), ``pairs(after=...)`` the pair route from a cursor (``amar_topk_segmented_after_f32``), ``deep_fused`` /
+``deep_pairs`` chain ceil(k / K_MAX) pages into lists of up to ``DEEP_K_MAX`` = 1024, and the mixin's ``recommend_after`` /
+``recommend_deep`` pick between them as ``recommend()`` does.
 """
 import contextlib
 import weakref
@@ -478,25 +484,17 @@ def _kept_mask(ptr, rows, lo, c, n_items, dev):
     return keep
 
 
-def pairs(score_fn, trainset, k, users, exclude_seen, device=None, keep_items=None):
-    """Pair route: per user chunk, the unexcluded (user, item) list built on the device, scored by `score_fn(u_ids, i_ids)` (int32 rows
-    of the user / item tower tables -> [P, 1] scores) and ranked by amar_topk_segmented_f32.
-    keep_items (None: every item) restricts the list to candidates, as `check_candidates` returns them: item rows (one set for
-    every user, a bool row ANDed into the chunk's mask) or a CSR (ptr, rows) over the listed users (a mask per chunk).  Only kept
-    pairs are scored."""
+def _scored_chunks(score_fn, trainset, u, exclude_seen, dev, keep_items=None):
+    """The pair route's scoring, per chunk of the listed users `u` (host int64): the unexcluded (user, item) list built on the device
+    and scored once by `score_fn`.  Yields (lo, c, seg_ptr int32 [c + 1], item rows int32, scores float32): the arguments of
+    amar_topk_segmented_f32 / amar_topk_segmented_after_f32 for the listed rows lo .. lo + c - 1.  keep_items as in `pairs`."""
     n_users, n_items = _sizes(trainset)
-    k = check_k(k)
-    u = check_users(users, n_users)
-    if len(u) == 0:
-        return _empty(k)
-    dev = device or default_device()
     excl = _exclusion_device(trainset, n_users, n_items, exclude_seen)
     chunk = max(1, PAIRS_PER_CHUNK // max(1, n_items))
     keep_row = None
     if keep_items is not None and not isinstance(keep_items, tuple):
         keep_row = torch.zeros(n_items, dtype=torch.bool, device=dev)
         keep_row[torch.from_numpy(np.ascontiguousarray(keep_items, dtype=np.int64)).to(dev)] = True
-    out_i, out_s = [], []
     for lo in range(0, len(u), chunk):
         uc = torch.from_numpy(u[lo:lo + chunk]).to(dev)
         c = int(uc.numel())
@@ -515,9 +513,138 @@ def pairs(score_fn, trainset, k, users, exclude_seen, device=None, keep_items=No
         else:
             scores = torch.zeros(1, dtype=torch.float32, device=dev)
             i_ids = torch.zeros(1, dtype=torch.int32, device=dev)
-        items, sc = capi.topk_segmented(seg.to(torch.int32), i_ids, scores, k)
+        yield lo, c, seg.to(torch.int32), i_ids, scores
+
+
+def pairs(score_fn, trainset, k, users, exclude_seen, device=None, keep_items=None, after=None):
+    """Pair route: per user chunk, the unexcluded (user, item) list built on the device, scored by `score_fn(u_ids, i_ids)` (int32 rows
+    of the user / item tower tables -> [P, 1] scores) and ranked by amar_topk_segmented_f32.
+    keep_items (None: every item) restricts the list to candidates, as `check_candidates` returns them: item rows (one set for
+    every user, a bool row ANDed into the chunk's mask) or a CSR (ptr, rows) over the listed users (a mask per chunk).  Only kept
+    pairs are scored.
+    after (None: from the start) = (item rows int32 [m], scores float32 [m]) on the device, one cursor per listed user as
+    `check_after` reads them: every list starts strictly after its cursor (amar_topk_segmented_after_f32)."""
+    n_users, n_items = _sizes(trainset)
+    k = check_k(k)
+    u = check_users(users, n_users)
+    if len(u) == 0:
+        return _empty(k)
+    dev = device or default_device()
+    out_i, out_s = [], []
+    for lo, c, seg, i_ids, scores in _scored_chunks(score_fn, trainset, u, exclude_seen, dev, keep_items):
+        if after is None:
+            items, sc = capi.topk_segmented(seg, i_ids, scores, k)
+        else:
+            items, sc = capi.topk_segmented_after(seg, i_ids, scores, k, after[0][lo:lo + c], after[1][lo:lo + c])
         out_i.append(items)
         out_s.append(sc)
+    return _finish(u, torch.cat(out_i), torch.cat(out_s), n_users)
+
+
+# -- paging (amar_recommend_after_f32 / amar_topk_segmented_after_f32): "the next page", and lists longer than K_MAX ------------------
+DEEP_K_MAX = 1024                    # recommend_deep: ceil(k / K_MAX) chained pages; K_MAX stays the length of one launch's list
+
+
+def check_deep_k(k):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= DEEP_K_MAX:
+        raise ValueError("k must be an integer in [1, {}] (got {!r})".format(DEEP_K_MAX, k))
+    return int(k)
+
+
+def page_sizes(k):
+    """The lengths of the chained pages of a list of k: whole pages of K_MAX, then the rest."""
+    return [min(K_MAX, k - at) for at in range(0, k, K_MAX)]
+
+
+def check_after(after, n_listed, n_users, n_items):
+    """The `after` argument of `recommend_after`, checked: (items, scores) with one entry per listed user — items integer node ids
+    as `recommend()` returns them (|U|..|U|+|I|-1, or -1: the padding of an exhausted list), scores numbers that are not NaN (the
+    infinities are the start and the end).  Returns the host cursor (item rows int32 [n_listed] with -1 kept, scores float32
+    [n_listed]).  ValueError, naming `after`, for anything else."""
+    if isinstance(after, (str, bytes, dict)) or not hasattr(after, '__len__') or len(after) != 2:
+        raise ValueError("after must be a pair (items, scores) with one entry per listed user")
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    try:
+        items, scores = host(after[0]).reshape(-1), host(after[1]).reshape(-1)
+    except (ValueError, TypeError):
+        raise ValueError("after must be a pair (items, scores) of 1-D sequences")
+    if len(items) != n_listed or len(scores) != n_listed:
+        raise ValueError("after must hold one item and one score per listed user ({} items and {} scores for {} users)".format(
+            len(items), len(scores), n_listed))
+    if items.size and (items.dtype == np.bool_ or not np.issubdtype(items.dtype, np.integer)):
+        raise ValueError("after: the items must be integer node ids")
+    if scores.size and (scores.dtype == np.bool_ or not (np.issubdtype(scores.dtype, np.floating) or np.issubdtype(scores.dtype, np.integer))):
+        raise ValueError("after: the scores must be numbers")
+    items = items.astype(np.int64)
+    real = items[items != -1]
+    if real.size and (real.min() < n_users or real.max() >= n_users + n_items):
+        raise ValueError("after: the items must be node ids in [{}, {}) or -1".format(n_users, n_users + n_items))
+    scores = scores.astype(np.float32)
+    if np.isnan(scores).any():
+        raise ValueError("after: a NaN score is no position in a ranking")
+    return np.where(items >= 0, items - n_users, -1).astype(np.int32), scores
+
+
+def _cursor_device(after, dev):
+    return torch.from_numpy(after[0]).to(dev), torch.from_numpy(after[1]).to(dev)
+
+
+def after_fused(towers, plan, trainset, k, users, exclude_seen, after):
+    """One amar_recommend_after_f32 call over the split towers: `fused` from the cursors `after` (host item rows / scores of
+    `check_after`, one per listed user)."""
+    n_users, n_items = _sizes(trainset)
+    k = check_k(k)
+    u = check_users(users, n_users)
+    if len(u) == 0:
+        return _empty(k)
+    head, kw = _ranker_args(towers, plan, trainset, exclude_seen, None if users is None else u)
+    items, scores = capi.recommend_after(*head, k, *_cursor_device(after, towers[0].device), **kw)
+    return _finish(u, items, scores, n_users)
+
+
+def deep_fused(towers, plan, trainset, k, users, exclude_seen):
+    """The first k entries of every listed user's ranking, k <= DEEP_K_MAX, fused: amar_recommend_f32 for the first page, then one
+    amar_recommend_after_f32 launch per further page of K_MAX with the previous page's last column as its cursor.  The cursors are
+    slices of the previous outputs: they never leave the device and nothing waits between the pages.  Every page scores the whole
+    catalogue again."""
+    n_users, n_items = _sizes(trainset)
+    k = check_deep_k(k)
+    u = check_users(users, n_users)
+    if len(u) == 0:
+        return _empty(k)
+    head, kw = _ranker_args(towers, plan, trainset, exclude_seen, None if users is None else u)
+    out_i, out_s = [], []
+    for page_k in page_sizes(k):
+        if not out_i:
+            items, scores = capi.recommend(*head, page_k, **kw)
+        else:
+            items, scores = capi.recommend_after(*head, page_k, out_i[-1][:, -1].contiguous(), out_s[-1][:, -1].contiguous(), **kw)
+        out_i.append(items)
+        out_s.append(scores)
+    return _finish(u, torch.cat(out_i, 1), torch.cat(out_s, 1), n_users)
+
+
+def deep_pairs(score_fn, trainset, k, users, exclude_seen, device=None):
+    """`deep_fused` on the pair route: every user chunk is scored ONCE (`_scored_chunks`) and ranked page by page on the same scores,
+    amar_topk_segmented_f32 first and amar_topk_segmented_after_f32 from each page's last column."""
+    n_users, n_items = _sizes(trainset)
+    k = check_deep_k(k)
+    u = check_users(users, n_users)
+    if len(u) == 0:
+        return _empty(k)
+    dev = device or default_device()
+    out_i, out_s = [], []
+    for lo, c, seg, i_ids, scores in _scored_chunks(score_fn, trainset, u, exclude_seen, dev):
+        page_i, page_s = [], []
+        for page_k in page_sizes(k):
+            if not page_i:
+                items, sc = capi.topk_segmented(seg, i_ids, scores, page_k)
+            else:
+                items, sc = capi.topk_segmented_after(seg, i_ids, scores, page_k, page_i[-1][:, -1].contiguous(), page_s[-1][:, -1].contiguous())
+            page_i.append(items)
+            page_s.append(sc)
+        out_i.append(torch.cat(page_i, 1))
+        out_s.append(torch.cat(page_s, 1))
     return _finish(u, torch.cat(out_i), torch.cat(out_s), n_users)
 
 
@@ -1156,6 +1283,45 @@ class SimilarSearch:
         towers = towers if towers is not None else head.towers(*self._recommend_tables(trainset))
         return pairs(lambda u, i: head.score_towers(towers, u, i), trainset, k, users, exclude_seen, device=towers[0].device,
                      keep_items=keep_items)
+
+    # -- paging (amar_recommend_after_f32) -------------------------------------------------------------------------------------
+    def recommend_after(self, trainset, after, k=10, users=None, exclude_seen=True):
+        """The next page: the k best items (1 <= k <= K_MAX) of every user in `users` (all users by default) that come strictly AFTER
+        a position of the user's ranking.  after = (items, scores), one entry per listed user: items are node ids as `recommend()`
+        returns them (-1 = an exhausted list: the page is all padding), scores float32; typically `(items[:, -1], scores[:, -1])` of
+        the previous page.  The order is `recommend()`'s (score descending, node id ascending), a strict total order, so the page is
+        exactly what `recommend()` would return with the earlier pages added to every user's excluded items; the cursor's item need
+        not be in the user's list (it is only a position).  Returns (users, items, scores) shaped and padded like `recommend()`'s.
+        A front end pages without rebuilding any exclusion list; `recommend_deep` chains the pages itself.
+        ValueError — before any tower is computed — for a bad k, bad users, lengths that do not match the users, non-integer items,
+        node ids that are neither -1 nor items of the trainset, a NaN score.  The route is `recommend()`'s: one
+        amar_recommend_after_f32 launch where `recommend()` is fused, amar_topk_segmented_after_f32 over pair scores elsewhere."""
+        n_users, n_items = _sizes(trainset)
+        k = check_k(k)
+        u = check_users(users, n_users)
+        cursor = check_after(after, len(u), n_users, n_items)
+        if len(u) == 0:
+            return _empty(k)
+        route = self._group_route(trainset, 'recommend')
+        if route[0] == 'fused':
+            return after_fused(route[1], route[2], trainset, k, users, exclude_seen, cursor)
+        dev = route[2] or default_device()
+        return pairs(route[1], trainset, k, users, exclude_seen, device=dev, after=_cursor_device(cursor, dev))
+
+    def recommend_deep(self, trainset, k, users=None, exclude_seen=True):
+        """The first k entries of every listed user's full ranking for k up to DEEP_K_MAX = 1024: Recall@100, a 200-item retrieval
+        stage, a hand-over to another system (`recommend()` stops at K_MAX = 64, the length of one launch's list).  Returns (users
+        int64 [m], items int64 [m, k] node ids, -1 padded, scores float32 [m, k], -inf padded) in `recommend()`'s order; the first
+        min(k, K_MAX) columns are `recommend()`'s.  utilities.metrics.full_ranking_metrics scores lists of any length.
+        Fused route: ceil(k / 64) launches — amar_recommend_f32, then amar_recommend_after_f32 from the previous page's last column,
+        the cursors staying on the device; every page scores the catalogue again.  Pair route: every user chunk is scored once and
+        amar_topk_segmented_after_f32 pages over the same scores.  The route is `recommend()`'s."""
+        check_deep_k(k)
+        check_users(users, len(trainset.users))
+        route = self._group_route(trainset, 'recommend')
+        if route[0] == 'fused':
+            return deep_fused(route[1], route[2], trainset, k, users, exclude_seen)
+        return deep_pairs(route[1], trainset, k, users, exclude_seen, device=route[2])
 
     def _group_route(self, trainset, kind='group'):
         """How the model ranks a catalogue for the fused kernel `kind` ('recommend' | 'group' | 'rank_of' | 'among': capi.RANK_KINDS):

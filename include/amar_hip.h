@@ -1227,6 +1227,17 @@ int amar_topk_segmented_f32(const int32_t *seg_ptr, const int32_t *item_ids, con
                             int32_t n_users, int32_t k, int32_t *out_items, float *out_scores,
                             amar_stream_t stream);
 
+/* The same from a cursor ("the next page" of the pair route): user u's list holds the k best pairs that come STRICTLY AFTER the
+ * position (after_scores[u], after_items[u]) in the order above, i.e. score < after_scores[u], or score == after_scores[u] and
+ * item id > after_items[u]; after_scores / after_items [n_users] go together and are required when n_users > 0 (AMAR_EINVAL).
+ * The cursor values are those of amar_recommend_after_f32 below: (+inf, -1) is the start (amar_topk_segmented_f32's output, bit for
+ * bit), (-inf, -1) and a NaN score admit nothing, the cursor's item need not be one of the user's pairs.  The scores are read, never
+ * recomputed: a caller pages through one scored chunk with one call per page.  k <= 64; the other checks, in
+ * amar_topk_segmented_f32's order, are that entry point's. */
+int amar_topk_segmented_after_f32(const int32_t *seg_ptr, const int32_t *item_ids, const float *scores,
+                                  int32_t n_users, int32_t k, const float *after_scores, const int32_t *after_items,
+                                  int32_t *out_items, float *out_scores, amar_stream_t stream);
+
 /* Full-catalogue top-k of the split scoring head (models/basic.py:_split_plan: the classifier's first Dense layer folded
  * into the towers), fused: for every listed user j (users[j], or j itself when users == NULL, m == n_users) and EVERY item
  * i in 0..n_items-1 that is not in the user's exclusion list,
@@ -1314,6 +1325,35 @@ int amar_recommend_among_f32(const float *Tu, int64_t ldu, int32_t n_users, cons
                              const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers, int32_t in_act,
                              const int32_t *users, int64_t m, const int32_t *excl_ptr, const int32_t *excl_items,
                              const int32_t *cand_items, int32_t n_cand, int32_t k, int32_t n_slices,
+                             int32_t *workspace_items, float *workspace_scores, int32_t *out_items, float *out_scores,
+                             amar_stream_t stream);
+
+/* Top-k AFTER a position of the user's ranking ("the next page"; chained, lists longer than 64), fused: amar_recommend_f32 with a
+ * cursor per selector row.  Tables, packed rest stack, limits, alignment rules, users[m], the exclusion CSR, the slicing contract
+ * (amar_recommend_slices, the workspaces, the merge launch), the LDS sum (amar_rank_route with AMAR_RANK_RECOMMEND) and the
+ * -1 / -inf padding are exactly those of amar_recommend_f32.
+ * Cursor: after_scores[m], after_items[m], device arrays indexed by the selector row j of the call, NOT by the user row users[j]:
+ * the same user may stand twice in a call with two cursors.  The order of the rankers (score descending, item row ascending) is a
+ * strict total order, so (score, item row) is a position in a user's ranking; a pair (z, item) is offered to the selector only if
+ * it comes strictly after the cursor: z < after_scores[j], or z == after_scores[j] and item > after_items[j].  For every pair that
+ * passes the score is the one amar_recommend_f32 computes, bit for bit (one score routine), and the list is that user's ranking
+ * with everything up to and including the cursor struck out: the list amar_recommend_f32 returns with the earlier pages merged
+ * into the user's exclusion row.  Cursor values:
+ *     the start         (+inf, -1)  admits every pair: the call returns amar_recommend_f32's output, bit for bit
+ *     the end           (-inf, -1)  admits nothing: no sigmoid, ReLU or linear score is below -inf.  It is the padding of an
+ *                                   exhausted list, so a page chained onto an exhausted list is all padding
+ *     the cursor's item need not be a real row (it may be >= n_items) and may be an excluded row: it is only a position
+ *     a NaN score admits nothing (every comparison with it is false); host callers refuse it
+ * The typical cursor is the last column of the previous page: (out_scores[j, k-1], out_items[j, k-1]).
+ * NULL tables, negative sizes, k < 1, users == NULL with m != n_users, excl_ptr without excl_items, one of after_scores /
+ * after_items without the other, either missing with m > 0, a missing workspace or output: AMAR_EINVAL; k > 64, the shape limits,
+ * a head whose LDS sum does not fit: AMAR_EUNSUPPORTED; amar_recommend_f32's checks in its order, then the cursor's, all before any
+ * device call.  m == 0: AMAR_OK, nothing is launched. */
+#define AMAR_AFTER_NO_ITEM (-1)   /* the item of both constant cursors: with +INFINITY the start, with -INFINITY the end */
+int amar_recommend_after_f32(const float *Tu, int64_t ldu, int32_t n_users, const float *Ti, int64_t ldi, int32_t n_items, int32_t c1,
+                             const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers, int32_t in_act,
+                             const int32_t *users, int64_t m, const int32_t *excl_ptr, const int32_t *excl_items,
+                             const float *after_scores, const int32_t *after_items, int32_t k, int32_t n_slices,
                              int32_t *workspace_items, float *workspace_scores, int32_t *out_items, float *out_scores,
                              amar_stream_t stream);
 
