@@ -4,8 +4,9 @@
 // amar_recommend_f32 computes for the pair, bit for bit) are combined by a social-choice rule — the mean, the minimum (least
 // misery) or the maximum (most pleasure), optionally with a veto on any member's score below a floor — and the group's k best
 // items are kept on chip.  Nothing of size members x |I| or groups x |I| is written.  Decomposition:
+//   * the kernel is rank_topk_kernel (amar_rank_score.h) with the variant RankGroup below.
 //   * grid (group blocks of 16, item slices); 4 waves per workgroup, each owning 4 groups of the block, one RankSlot per group.
-//   * per item tile: the workgroup stages the tile in LDS as recommend_kernel does; a wave then walks the tile for each of its
+//   * per item tile: the workgroup stages the tile in LDS as every ranker does; a wave then walks the tile for each of its
 //     groups.  For every step of 16 PT items it loops over the group's members in member order: the member's Tu row comes from
 //     global memory (c1 floats, L2-resident), the score stage (amar_rank_score.inc) gives the lane its score, and the lane folds it into one aggregate
 //     register and one running-minimum register.  After the last member the selector is offered the aggregate once, with
@@ -25,69 +26,32 @@ struct GroupArgs {
     float min_score;
 };
 
-template <int MAXT, int PT>
-__global__ __launch_bounds__(256) void recommend_group_kernel(const GroupArgs ga) {
-    const RankArgs &a = ga.r;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float *w_lds = lds;
-    float *tile = lds + ((a.wpack_floats + 3) & ~3);
-    float *select = tile + a.tile_items * a.tile_stride;         // RANK_UB selector slots (amar_rank_select.h)
-
-    rank_stage_weights(a, w_lds);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
-    const int64_t j0 = (int64_t)blockIdx.x * RANK_UB;
-    const int slice = blockIdx.y;
-    const int s0 = slice * a.slice_items, s1 = min(a.n_items, s0 + a.slice_items);
-    const int KT0 = a.kt[0];
-    for (int uw = 0; uw < RANK_UPW; ++uw) {
-        const int slot = wave * RANK_UPW + uw;
-        const int64_t j = j0 + slot;
-        int eb = 0, ee = 0;                                      // the group's excluded items
-        if (lane == 0 && j < a.m && a.excl_ptr) { eb = a.excl_ptr[j]; ee = a.excl_ptr[j + 1]; }
-        RankSlot<RANK_UB>(select, slot).init(lane, a.excl_items, eb, ee, s0);
+// A group per selector row: the exclusion CSR runs over groups, an empty group is skipped, and what the selector is offered is the
+// fold of the members' scores in member order, admitted where no member scores below the floor.
+struct RankGroup : RankVariant<GroupArgs> {
+    static constexpr bool MEMBERS = true;
+    static __device__ __forceinline__ int64_t excl_row(const RankArgs &, int64_t j) { return j; }
+    static __device__ __forceinline__ void fold(const GroupArgs &ga, bool first, float z, float &acc, float &low) {
+        const float both = ga.strategy == AMAR_GROUP_MEAN ? acc + z : (ga.strategy == AMAR_GROUP_MIN ? fminf(acc, z) : fmaxf(acc, z));
+        acc = first ? z : both;
+        low = first ? z : fminf(low, z);
+    }
+    static __device__ __forceinline__ float close(const GroupArgs &ga, float acc, float n) {
+        return ga.strategy == AMAR_GROUP_MEAN ? __fdiv_rn(acc, n) : acc;
     }
 
-    for (int t0 = s0; t0 < s1; t0 += a.tile_items) {
-        const int rows = min(a.tile_items, s1 - t0);
-        __syncthreads();                                         // the previous tile is no longer read
-        rank_stage_tile(a, tile, t0, rows);
-        __syncthreads();
-        for (int uw = 0; uw < RANK_UPW; ++uw) {
-            const int slot = wave * RANK_UPW + uw;
-            const int64_t j = j0 + slot;
-            if (j >= a.m) break;
-            const int mb = ga.grp_ptr[j], me = ga.grp_ptr[j + 1];
-            if (mb >= me) continue;                              // an empty group: its list stays empty
-            const float n = (float)(me - mb);
-            RankSlot<RANK_UB> top(select, slot);
-            top.load();
-            const int ee = a.excl_ptr ? a.excl_ptr[j + 1] : 0;
-
-            for (int grp = 0; grp < rows; grp += 16 * PT) {
-                float acc = 0.f, low = 0.f;                      // the aggregate so far, the smallest member score so far
-                for (int t = mb; t < me; ++t) {
-                    f32x4 tu[MAXT];
-                    rank_load_user<MAXT>(a, a.users[t], g, tu);
-#include "amar_rank_score.inc"
-                    const float both = ga.strategy == AMAR_GROUP_MEAN ? acc + z : (ga.strategy == AMAR_GROUP_MIN ? fminf(acc, z) : fmaxf(acc, z));
-                    acc = t == mb ? z : both;
-                    low = t == mb ? z : fminf(low, z);
-                }
-                if (ga.strategy == AMAR_GROUP_MEAN) acc = __fdiv_rn(acc, n);
-                const int item = t0 + grp + 16 * g + col;
-                top.offer(acc, item, g < PT && grp + 16 * g + col < rows && low >= ga.min_score, a.excl_items, ee, a.out.k, lane);
-            }
-            top.advance(a.excl_items, ee, t0 + rows);
-            top.store(lane);
+    template <int MAXT>
+    struct Sel {
+        int mb, me;                              // the group's members: a.users[mb .. me)
+        float n;
+        __device__ __forceinline__ bool begin(const RankArgs &, const GroupArgs &ga, int64_t j, int64_t, int) {
+            mb = ga.grp_ptr[j]; me = ga.grp_ptr[j + 1];
+            n = (float)(me - mb);
+            return mb < me;                      // an empty group: its list stays empty
         }
-    }
-    for (int uw = 0; uw < RANK_UPW; ++uw) {
-        const int slot = wave * RANK_UPW + uw;
-        const int64_t j = j0 + slot;
-        if (j >= a.m) break;
-        RankSlot<RANK_UB>(select, slot).finish(j, slice, a.out, lane);
-    }
-}
+        __device__ __forceinline__ bool admit(const GroupArgs &ga, float, int, float low) const { return low >= ga.min_score; }
+    };
+};
 
 // Item slices of a call.  Requested (n_slices > 0): clamped as rank_slices clamps.  Automatic: enough slices for about four
 // resident workgroups per CU, as for amar_recommend_f32, but a workgroup's work is its members' walks over its tiles, not its
@@ -134,7 +98,7 @@ int amar_recommend_group_f32(const float *Tu, int64_t ldu, int32_t n_users, cons
     const RankHead head = {Tu, ldu, Ti, ldi, n_items, c1, wpack, dims, acts, n_layers, in_act, grp_users, excl_ptr, excl_items};
     GroupArgs ga{};
     ga.grp_ptr = grp_ptr; ga.strategy = strategy; ga.min_score = min_score;
-    static RankForms<GroupArgs> forms = AMAR_RANK_FORMS(recommend_group_kernel);
+    static RankForms<GroupArgs> forms = AMAR_RANK_TOPK_FORMS(RankGroup);
     return rank_topk(forms, AMAR_RANK_GROUP, head, ga, n_groups, n_items,
                      amar_recommend_group_slices(n_groups, n_members, n_items, dims, n_layers, n_slices), n_slices, k,
                      workspace_items, workspace_scores, out_items, out_scores, stream);

@@ -11,9 +11,9 @@
 //     table tile the workgroup stages TR rows of T, then
 //       - product: the tile's 16-row units are dealt to the waves; a unit is one 16 x 16 accumulator of v_mfma_f32_16x16x4_f32
 //         (A = the 16 queries, B = 16 table rows, both read from LDS as float4 at features 16t + 4g + r, the fragment order of
-//         recommend_kernel / chain_kernel: t ascending, r ascending inside t, one fmaf chain per score).  The scaled scores go to
+//         rank_topk_kernel / chain_kernel: t ascending, r ascending inside t, one fmaf chain per score).  The scaled scores go to
 //         a [16][TR] LDS window: the matrix layout holds 4 queries x 16 rows per register, the selection wants 64 rows of one query.
-//       - selection: the RankSlot of amar_rank_select.h, one per query (the selector recommend_kernel uses); each wave owns 4
+//       - selection: the RankSlot of amar_rank_select.h, one per query (the selector rank_topk_kernel uses); each wave owns 4
 //         queries and hands its slots the window's scores 64 rows at a time.
 //   * with several table slices each workgroup leaves its slice's list in a workspace and rank_merge_slices (amar_rank.hip)
 //     merges them in slice order; the order is a strict total order, so the result does not depend on the slicing.

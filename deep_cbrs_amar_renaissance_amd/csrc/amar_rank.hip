@@ -10,13 +10,15 @@
 //     the layout of chain_kernel in amar_chain.hip) is formed in registers as in_act(Tu[u] + Ti[i]): no per-pair gathers.
 //   * the rest stack runs on v_mfma_f32_16x16x4_f32 with chain_kernel's loop order, fragment blob and dot stage, so a score is
 //     bit-identical to what amar_chain_f32's generic kernel returns for the same pair (the pair stage of predict() for heads
-//     whose widths it takes).  These two steps are amar_rank_score.inc, the fragment amar_group.hip's kernel includes too.
+//     whose widths it takes).  These two steps are amar_rank_score.inc, the fragment every ranker's body includes.
 //   * selection: the RankSlot of amar_rank_select.h, one per user (threshold, exclusion walk over the user's training items,
 //     candidate buffer, rank-counting merge); the kernel hands it 16 PT scores at a time, lane group g holding pair tile g.
 //   * with several item slices each workgroup leaves its slice's top-k in a workspace and a second launch (recommend_merge_kernel
 //     below, also amar_nearest.hip's second launch) merges the slices of a user in slice order (the order is a strict total
 //     order, so the result does not depend on the slicing).
 // The result of a user depends on its own Tu row, Ti and the weights only: not on the other users of the block or the call.
+// The kernel is rank_topk_kernel (amar_rank_score.h), the body the top-k rankers share, with the variant that changes
+// nothing: RankPlain below.
 // The pair route's ranker (amar_topk_segmented_f32: scores already in memory, one wave per user; amar_topk_segmented_after_f32: the
 // same from a cursor) is at the end of the file.
 #include "amar_rank_score.h"
@@ -24,74 +26,7 @@
 
 namespace {
 
-template <int MAXT, int PT>
-__global__ __launch_bounds__(256) void recommend_kernel(const RankArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float *w_lds = lds;
-    float *tile = lds + ((a.wpack_floats + 3) & ~3);
-    float *select = tile + a.tile_items * a.tile_stride;         // RANK_UB selector slots (amar_rank_select.h)
-
-    for (int i = threadIdx.x * 4; i < a.wpack_floats; i += blockDim.x * 4)
-        *reinterpret_cast<float4 *>(&w_lds[i]) = *reinterpret_cast<const float4 *>(a.wpack + i);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
-    const int64_t j0 = (int64_t)blockIdx.x * RANK_UB;
-    const int slice = blockIdx.y;
-    const int s0 = slice * a.slice_items, s1 = min(a.n_items, s0 + a.slice_items);
-    for (int uw = 0; uw < RANK_UPW; ++uw) {
-        const int slot = wave * RANK_UPW + uw;
-        const int64_t j = j0 + slot;
-        int eb = 0, ee = 0;                                      // the user's training items
-        if (lane == 0 && j < a.m && a.excl_ptr) {
-            const int u = a.users ? a.users[j] : (int)j;
-            eb = a.excl_ptr[u]; ee = a.excl_ptr[u + 1];
-        }
-        RankSlot<RANK_UB>(select, slot).init(lane, a.excl_items, eb, ee, s0);
-    }
-    const int KT0 = a.kt[0];
-    const int f4_per_row = 4 * KT0;                              // float4s of a staged row (16 KT0 features, zero past c1)
-
-    for (int t0 = s0; t0 < s1; t0 += a.tile_items) {
-        const int rows = min(a.tile_items, s1 - t0);
-        __syncthreads();                                         // the previous tile is no longer read
-        for (int idx = threadIdx.x; idx < a.tile_items * f4_per_row; idx += blockDim.x) {
-            const int r = idx / f4_per_row, f = 4 * (idx - r * f4_per_row);
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < rows && f < a.c1) v = *reinterpret_cast<const float4 *>(a.Ti + (int64_t)(t0 + r) * a.ldi + f);
-            *reinterpret_cast<float4 *>(&tile[r * a.tile_stride + f]) = v;
-        }
-        __syncthreads();
-        for (int uw = 0; uw < RANK_UPW; ++uw) {
-            const int slot = wave * RANK_UPW + uw;
-            const int64_t j = j0 + slot;
-            if (j >= a.m) break;
-            const int u = a.users ? a.users[j] : (int)j;
-            f32x4 tu[MAXT];
-#pragma unroll
-            for (int t = 0; t < MAXT; ++t) {
-                const int f = 16 * t + 4 * g;
-                const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-                tu[t] = (t < KT0 && f < a.c1) ? *reinterpret_cast<const f32x4 *>(a.Tu + (int64_t)u * a.ldu + f) : zero;
-            }
-            RankSlot<RANK_UB> top(select, slot);
-            top.load();
-            const int ee = a.excl_ptr ? a.excl_ptr[u + 1] : 0;
-
-            for (int grp = 0; grp < rows; grp += 16 * PT) {
-#include "amar_rank_score.inc"
-                const int item = t0 + grp + 16 * g + col;
-                top.offer(z, item, g < PT && grp + 16 * g + col < rows, a.excl_items, ee, a.out.k, lane);
-            }
-            top.advance(a.excl_items, ee, t0 + rows);
-            top.store(lane);
-        }
-    }
-    for (int uw = 0; uw < RANK_UPW; ++uw) {
-        const int slot = wave * RANK_UPW + uw;
-        const int64_t j = j0 + slot;
-        if (j >= a.m) break;
-        RankSlot<RANK_UB>(select, slot).finish(j, slice, a.out, lane);
-    }
-}
+typedef RankVariant<RankArgs> RankPlain;         // one user per selector row, every row of Ti, nothing to add
 
 // Second launch with item slices: one wave per user merges its n_slices partial lists, slice by slice, into the final top-k.
 __global__ __launch_bounds__(256) void recommend_merge_kernel(const int32_t *__restrict__ part_items, const float *__restrict__ part_scores,
@@ -193,7 +128,7 @@ int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const floa
     if (excl_ptr && !excl_items) return AMAR_EINVAL;
     const RankHead head = {Tu, ldu, Ti, ldi, n_items, c1, wpack, dims, acts, n_layers, in_act, users, excl_ptr, excl_items};
     RankArgs a{};
-    static RankForms<RankArgs> forms = AMAR_RANK_FORMS(recommend_kernel);
+    static RankForms<RankArgs> forms = AMAR_RANK_TOPK_FORMS(RankPlain);
     return rank_topk(forms, AMAR_RANK_RECOMMEND, head, a, m, n_items, amar_recommend_slices(m, n_items, dims, n_layers, n_slices), n_slices, k,
                      workspace_items, workspace_scores, out_items, out_scores, stream);
 }

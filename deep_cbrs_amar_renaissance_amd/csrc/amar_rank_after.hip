@@ -3,8 +3,12 @@
 // "The next page": amar_recommend_f32 with a cursor per selector row.  The order of the rankers (rank_better: score descending, item
 // row ascending) is a strict total order, so a position in a user's ranking is a pair (score, item row) and "strictly after it" is
 // one comparison per scored pair.  Decomposition:
-//   * grid, waves, item tiles, the staged stack and the selectors are recommend_kernel's (amar_rank.hip): the LDS sum, the slicing
-//     and the capacity rule are AMAR_RANK_RECOMMEND's, amar_recommend_slices counts the slices, rank_merge_slices merges them.
+//   * grid, waves, item tiles, the staged stack and the selectors are amar_recommend_f32's: the LDS sum, the slicing and the
+//     capacity rule are AMAR_RANK_RECOMMEND's, amar_recommend_slices counts the slices, rank_merge_slices merges them.
+//   * the kernel below is still its own copy of the walk that rank_topk_kernel (amar_rank_score.h) holds for the other three
+//     top-k rankers.  As a variant of that body (a Sel with the cursor, admit = rank_better(cursor, pair)) it returned the same
+//     bits but measured 0.3 % slower than this kernel at ml1m(s=8), just past the run-to-run band of two builds of one source
+//     (DESIGN.md, 8a10), so it stays until that is gone.  A fix to the walk has to be made here too.
 //   * the cursor of selector row j, (after_scores[j], after_items[j]), is indexed by the ROW of the call, not by users[j]: the same
 //     user may stand twice in a call with two cursors.  It lives in two lane-uniform registers, loaded where the user's exclusion end
 //     is loaded; rank_better(cursor, pair) is ANDed into the in_range predicate of RankSlot::offer.

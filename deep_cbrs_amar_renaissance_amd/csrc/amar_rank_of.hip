@@ -2,15 +2,15 @@
 // (gfx950), and the cut-off-free metrics (AUC, reciprocal rank, average precision) that follow from the counts.
 //
 // The third consumer of the score stage (amar_rank_score.inc: the value amar_recommend_f32 computes for the pair, bit for bit): where
-// amar_rank.hip and amar_group.hip select, this file counts.  For entry j (a user u and up to AMAR_RANK_OF_MAX_TARGETS target items)
+// rank_topk_kernel (amar_rank_score.h) selects, this file counts.  For entry j (a user u and up to AMAR_RANK_OF_MAX_TARGETS target items)
 // and every target t it returns s_t = score(u, t) and, over the candidates C(u) = {items} \ excl(u) other than t, how many score
 // higher, how many score the same with a smaller item row, and how many the same with a larger one.  Nothing of size m x |I| is
 // written.  Decomposition:
-//   * grid (entry blocks of 16, item slices); 4 waves per workgroup, each owning 4 entries of the block: recommend_kernel's grid.
+//   * grid (entry blocks of 16, item slices); 4 waves per workgroup, each owning 4 entries of the block: rank_topk_kernel's grid.
 //   * prologue, per entry: the targets' Ti rows are gathered into the wave's own tile-shaped LDS buffer (16 PT rows) and scored by
 //     the same fragment; the (score, item) pairs are sorted ascending by rank counting, one lane per target.  Then the user's
 //     excluded items that fall into the slice are gathered and scored the same way and counted with weight -1.
-//   * per item tile: the workgroup stages the tile as recommend_kernel does; a wave walks it for each of its entries.  Per pair: a
+//   * per item tile: the workgroup stages the tile as rank_topk_kernel does; a wave walks it for each of its entries.  Per pair: a
 //     binary search of z among the entry's sorted target scores (p = targets scoring below z) and one integer LDS add into cnt[p];
 //     a lane whose z equals a target's score also walks that run of equal targets and adds to their before / after counters by
 //     item row.  cnt[p] of an equal pair lands on the first target of its run, so for the target at sorted position q

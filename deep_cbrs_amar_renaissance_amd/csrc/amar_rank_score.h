@@ -1,20 +1,25 @@
-// What the fused rankers of the split head share (amar_rank.hip: one user per selector; amar_rank_among.hip: the same over a
-// candidate list; amar_rank_after.hip: the same from a cursor; amar_group.hip: a group of users per selector; amar_rank_of.hip: counting) besides the
-// selector of amar_rank_select.h:
+// What the fused rankers of the split head share besides the selector of amar_rank_select.h:
 //   * RankArgs, the kernels' argument block, and the constants of their decomposition;
-//   * the score stage itself is amar_rank_score.inc, a fragment every kernel body includes (one text, the same bits per pair);
-//   * device helpers around it, as amar_group.hip uses them: the packed rest stack and an item tile go to LDS
-//     (rank_stage_weights, rank_stage_tile), a user's Tu row becomes MFMA fragments (rank_load_user).  recommend_kernel keeps these
-//     few lines in its own body, as it always had them: it must compile to what it compiled to;
+//   * device helpers: the packed rest stack and an item tile go to LDS (rank_stage_weights, rank_stage_tile), a user's Tu row
+//     becomes MFMA fragments (rank_load_user);
+//   * the score stage itself is amar_rank_score.inc, a fragment of a kernel body (one text, the same bits per pair):
+//     rank_topk_kernel includes it, and amar_rank_of.hip wraps it in a function of its own;
+//   * rank_topk_kernel<MAXT, PT, V>, the one body of three of the four top-k kernels, and RankVariant, what a variant V says by default.
+//     The variants: RankPlain (amar_rank.hip, amar_recommend_f32: one user per selector), RankAmong (amar_rank_among.hip: the
+//     same over a candidate list), RankGroup (amar_group.hip: a group of users per selector).  amar_rank_after.hip (the same
+//     from a cursor) still has its own copy of the walk, and amar_rank_of.hip counts instead of selecting: its kernel has its
+//     own walk; both call the helpers and include the fragment;
 //   * host: the argument checks the entry points share (rank_check_tables), the walk over the packed stack (rank_pack_args), the
 //     launch geometry of a stack (rank_shape), the LDS a launch needs (rank_lds_bytes, rank_of_lds_bytes), rank_route — the one
-//     function the four launchers and the query amar_rank_route take all of that and the capacity refusal from — and the launch
+//     function the launchers and the query amar_rank_route take all of that and the capacity refusal from — and the launch
 //     path itself: rank_prepare (tables, route, the argument fields every ranker sets alike), rank_launch_form (the MAXT / PT
-//     dispatch over a kernel's four forms), rank_topk (everything the three top-k launchers do after their own leading checks)
+//     dispatch over a kernel's four forms), rank_topk (everything the top-k launchers do after their own leading checks)
 //     and rank_slices_tile (what the *_slices queries check before they count).
 #pragma once
 #include "amar_common.h"
 #include "amar_rank_select.h"
+#include <limits.h>
+#include <type_traits>
 
 namespace {
 
@@ -43,14 +48,21 @@ __device__ __forceinline__ void rank_stage_weights(const RankArgs &a, float *w_l
 }
 
 // Rows t0 .. t0 + rows - 1 of Ti go to the tile (16 KT0 features a row, zero past c1 and past `rows`); the caller's barriers
-// stand on either side.
-__device__ __forceinline__ void rank_stage_tile(const RankArgs &a, float *tile, int t0, int rows) {
+// stand on either side.  LISTED: the rows are cand[t0 .. t0 + rows - 1] instead, and tile_rows keeps the item row of every tile
+// row (RANK_EMPTY past `rows`; such an entry is never used as a row of Ti).
+template <bool LISTED = false>
+__device__ __forceinline__ void rank_stage_tile(const RankArgs &a, float *tile, int t0, int rows, const int32_t *cand = nullptr,
+                                                int *tile_rows = nullptr) {
     const int f4_per_row = 4 * a.kt[0];
     for (int idx = threadIdx.x; idx < a.tile_items * f4_per_row; idx += blockDim.x) {
         const int r = idx / f4_per_row, f = 4 * (idx - r * f4_per_row);
+        int row = t0 + r;
+        if constexpr (LISTED) row = r < rows ? cand[t0 + r] : RANK_EMPTY;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (r < rows && f < a.c1) v = *reinterpret_cast<const float4 *>(a.Ti + (int64_t)(t0 + r) * a.ldi + f);
+        if (r < rows && f < a.c1) v = *reinterpret_cast<const float4 *>(a.Ti + (int64_t)row * a.ldi + f);
         *reinterpret_cast<float4 *>(&tile[r * a.tile_stride + f]) = v;
+        if constexpr (LISTED)
+            if (f == 0) tile_rows[r] = row;
     }
 }
 
@@ -63,6 +75,133 @@ __device__ __forceinline__ void rank_load_user(const RankArgs &a, int u, int g, 
         const int f = 16 * t + 4 * g;
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
         tu[t] = (t < KT0 && f < a.c1) ? *reinterpret_cast<const f32x4 *>(a.Tu + (int64_t)u * a.ldu + f) : zero;
+    }
+}
+
+// ---- the top-k walk -----------------------------------------------------------------------------------------------------------
+// What a variant V tells rank_topk_kernel, all of it resolved at compile time; RankVariant<Args> is amar_recommend_f32's answer
+// and the base the others change one thing of:
+//   * Args: the kernel's argument block, RankArgs or a struct whose first member r is one;
+//   * LISTED: the rows of a tile are va.cand_items[t0 + r], positions t0 + r < va.n_cand (false: the rows t0 + r of Ti);
+//   * excl_row(a, j): the row of the exclusion CSR that belongs to selector row j;
+//   * Sel<MAXT>: what a wave holds for one selector row while it walks a tile.  begin() loads it (false: the row is skipped,
+//     its list stays empty): the user's Tu row `tu`, or — MEMBERS — the range [mb, me) of a.users the row folds over and its
+//     length n.  admit(va, z, item, low) is the variant's own condition beside "the row is inside the tile";
+//   * MEMBERS only: fold(va, first, z, acc, low) takes one member's score into the aggregate and the running minimum,
+//     close(va, acc, n) turns the aggregate into what the selector is offered.
+// The score itself is amar_rank_score.inc, the fragment the body includes: one text, the same bits per pair.
+template <class A>
+struct RankVariant {
+    typedef A Args;
+    static constexpr bool LISTED = false, MEMBERS = false;
+    static __device__ __forceinline__ int64_t excl_row(const RankArgs &a, int64_t j) { return a.users ? a.users[j] : (int)j; }
+
+    template <int MAXT>
+    struct Sel {                                 // one user (row u of Tu: excl_row's), scored once, nothing to add
+        f32x4 tu[MAXT];
+        __device__ __forceinline__ bool begin(const RankArgs &a, const A &, int64_t, int64_t u, int g) {
+            rank_load_user<MAXT>(a, (int)u, g, tu);
+            return true;
+        }
+        __device__ __forceinline__ bool admit(const A &, float, int, float) const { return true; }
+    };
+};
+
+// The RankArgs of a kernel's argument block: the block itself, or its first member `r`.
+template <class Args>
+__host__ __device__ inline auto &rank_args_of(Args &args) {
+    if constexpr (std::is_same_v<std::remove_const_t<Args>, RankArgs>) return args;
+    else return args.r;
+}
+
+// The one body of amar_recommend_f32, amar_recommend_among_f32 and amar_recommend_group_f32:
+//   * grid (blocks of RANK_UB selector rows, slices of the tile loop's rows); 4 waves per workgroup, each owning RANK_UPW
+//     selector rows of the block, one RankSlot each;
+//   * LDS: the packed stack, one item tile, the selectors and — LISTED only, behind everything else, so that the other offsets
+//     are every variant's — the item row of every tile row (rank_lds_bytes, rank_among_lds_bytes);
+//   * per tile: the workgroup stages it once between two barriers; every wave then walks it for each of its selector rows, 16 PT
+//     rows a step: the score stage (MEMBERS: once per member, folded), the selector's offer; then the exclusion pointer moves to the next tile's first row;
+//   * with several slices each workgroup leaves its slice's top-k in a workspace (RankSlot::finish) for rank_merge_slices.
+template <int MAXT, int PT, class V>
+__global__ __launch_bounds__(256) void rank_topk_kernel(const typename V::Args va) {
+    const RankArgs &a = rank_args_of(va);
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *w_lds = lds;
+    float *tile = lds + ((a.wpack_floats + 3) & ~3);
+    float *select = tile + a.tile_items * a.tile_stride;         // RANK_UB selector slots (amar_rank_select.h)
+    int *tile_rows = nullptr;                                    // LISTED: the item row of every tile row
+    if constexpr (V::LISTED) tile_rows = reinterpret_cast<int *>(select + rank_select_state_floats(RANK_UB));
+
+    rank_stage_weights(a, w_lds);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
+    const int64_t j0 = (int64_t)blockIdx.x * RANK_UB;
+    const int slice = blockIdx.y;
+    int n_rows = a.n_items;
+    if constexpr (V::LISTED) n_rows = va.n_cand;
+    const int s0 = slice * a.slice_items, s1 = min(n_rows, s0 + a.slice_items);
+    int first_row = s0;                                          // where the exclusion walk starts
+    if constexpr (V::LISTED) first_row = s0 < n_rows ? va.cand_items[s0] : 0;
+    const int KT0 = a.kt[0];
+    for (int uw = 0; uw < RANK_UPW; ++uw) {
+        const int slot = wave * RANK_UPW + uw;
+        const int64_t j = j0 + slot;
+        int eb = 0, ee = 0;                                      // the selector row's excluded items
+        if (lane == 0 && j < a.m && a.excl_ptr) {
+            const int64_t e = V::excl_row(a, j);
+            eb = a.excl_ptr[e]; ee = a.excl_ptr[e + 1];
+        }
+        RankSlot<RANK_UB>(select, slot).init(lane, a.excl_items, eb, ee, first_row);
+    }
+
+    for (int t0 = s0; t0 < s1; t0 += a.tile_items) {
+        const int rows = min(a.tile_items, s1 - t0);
+        int next_row = t0 + rows;                                // the row the next tile starts at (LISTED: INT_MAX at the end)
+        if constexpr (V::LISTED) next_row = t0 + rows < n_rows ? va.cand_items[t0 + rows] : INT_MAX;
+        __syncthreads();                                         // the previous tile is no longer read
+        if constexpr (V::LISTED) rank_stage_tile<true>(a, tile, t0, rows, va.cand_items, tile_rows);
+        else rank_stage_tile(a, tile, t0, rows);
+        __syncthreads();
+        for (int uw = 0; uw < RANK_UPW; ++uw) {
+            const int slot = wave * RANK_UPW + uw;
+            const int64_t j = j0 + slot;
+            if (j >= a.m) break;
+            const int64_t e = V::excl_row(a, j);
+            typename V::template Sel<MAXT> cur;
+            if (!cur.begin(a, va, j, e, g)) continue;
+            RankSlot<RANK_UB> top(select, slot);
+            top.load();
+            const int ee = a.excl_ptr ? a.excl_ptr[e + 1] : 0;
+
+            for (int grp = 0; grp < rows; grp += 16 * PT) {
+                float offered, low = 0.f;                        // MEMBERS: the smallest member score of the step
+                if constexpr (V::MEMBERS) {                      // the members' scores, folded in member order
+                    float acc = 0.f;
+                    for (int t = cur.mb; t < cur.me; ++t) {
+                        f32x4 tu[MAXT];
+                        rank_load_user<MAXT>(a, a.users[t], g, tu);
+#include "amar_rank_score.inc"
+                        V::fold(va, t == cur.mb, z, acc, low);
+                    }
+                    offered = V::close(va, acc, cur.n);
+                } else {
+                    const f32x4 (&tu)[MAXT] = cur.tu;
+#include "amar_rank_score.inc"
+                    offered = z;
+                }
+                const bool in_range = g < PT && grp + 16 * g + col < rows;
+                int item = t0 + grp + 16 * g + col;
+                if constexpr (V::LISTED) item = in_range ? tile_rows[grp + 16 * g + col] : RANK_EMPTY;
+                top.offer(offered, item, in_range && cur.admit(va, offered, item, low), a.excl_items, ee, a.out.k, lane);
+            }
+            top.advance(a.excl_items, ee, next_row);
+            top.store(lane);
+        }
+    }
+    for (int uw = 0; uw < RANK_UPW; ++uw) {
+        const int slot = wave * RANK_UPW + uw;
+        const int64_t j = j0 + slot;
+        if (j >= a.m) break;
+        RankSlot<RANK_UB>(select, slot).finish(j, slice, a.out, lane);
     }
 }
 
@@ -130,7 +269,7 @@ inline size_t rank_lds_bytes(const RankArgs &a, const RankShape &sh) {
            (size_t)rank_select_state_floats(RANK_UB) * 4;
 }
 
-// amar_rank_among.hip: the same, and behind it the item row of every tile row (recommend_among_kernel's tile_rows).
+// amar_rank_among.hip: the same, and behind it the item row of every tile row (rank_topk_kernel's tile_rows, LISTED).
 inline size_t rank_among_lds_bytes(const RankArgs &a, const RankShape &sh) { return rank_lds_bytes(a, sh) + (size_t)sh.tile_items * 4; }
 
 // amar_rank_of.hip's share of the LDS: per entry RANK_OF_WORDS words of sorted targets and counters (its RankOfSlot), per wave a
@@ -198,6 +337,8 @@ struct RankForms {
     bool done[4][AMAR_MAX_DEVICES];
 };
 #define AMAR_RANK_FORMS(KERN) {{KERN<1, 4>, KERN<2, 4>, KERN<4, 2>, KERN<8, 1>}, {}}
+#define AMAR_RANK_TOPK_FORMS(V) \
+    {{rank_topk_kernel<1, 4, V>, rank_topk_kernel<2, 4, V>, rank_topk_kernel<4, 2, V>, rank_topk_kernel<8, 1, V>}, {}}
 
 // Launches the form of the stack's shape (route.maxt) on 256 threads, allowing it the large LDS where the launch needs more than
 // 64 KB (once per device and form), and checks the launch.
@@ -212,10 +353,6 @@ inline int rank_launch_form(RankForms<Args> &forms, const amar_rank_route_info &
     hipLaunchKernelGGL(forms.kern[f], grid, dim3(256), lds_bytes, st, args);
     return amar_check_launch();
 }
-
-// The RankArgs of a kernel's argument block: the block itself, or its first member `r`.
-inline RankArgs &rank_args_of(RankArgs &a) { return a; }
-template <class Args> inline RankArgs &rank_args_of(Args &args) { return args.r; }
 
 // Everything amar_recommend_f32, amar_recommend_among_f32 and amar_recommend_group_f32 do after their own leading checks, in the
 // order their callers rely on: tables, route; the slice count (`slices`: what the entry point's own *_slices rule gave for

@@ -1,6 +1,8 @@
-// The score stage of the fused rankers of the split head, as a fragment of a kernel body: amar_rank.hip (recommend_kernel) and
-// amar_group.hip (recommend_group_kernel) include it inside their loop over the 16 PT-item steps of a staged tile, so that a pair
-// has the same bits in both and recommend_kernel compiles to what it compiled to with these lines in its own body.
+// The score stage of the fused rankers of the split head, as a fragment of a kernel body: rank_topk_kernel (amar_rank_score.h)
+// includes it inside its loop over the 16 PT-item steps of a staged tile — once for a selector row that is one user, once inside
+// the member loop of a row that folds over several — amar_rank_after.hip's kernel includes it, and amar_rank_of.hip wraps it in ro_score, so that a pair has the same bits
+// everywhere.  It is text, not a function: as an always-inline function the same lines made hipcc allocate the top-k kernels'
+// registers differently, and the <1, 4> form measurably slower (DESIGN.md, 8a10).
 // In scope where it is included: MAXT, PT; a (RankArgs); w_lds, tile (LDS); grp (tile row of the step); tu[MAXT] (the user's Tu
 // row as fragments: rank_load_user); lane, g = lane / 16, col = lane % 16; KT0 = a.kt[0].  It defines z: the score of the user
 // against item 16 g + col of the step (lane group g holds pair tile g).

@@ -227,6 +227,41 @@ def test_form(hip, name):
     _run_form(hip, rf.FORMS[rf.FORM_NAMES.index(name)])
 
 
+# ---- 1b. the variants of the one top-k body, where they must be amar_recommend_f32 ---------------------------------------------
+@pytest.mark.parametrize('maxt', [1, 2, 4, 8])
+def test_variants_that_add_nothing_equal_recommend(hip, maxt):
+    """On each of the four kernel forms, item rows and score bits: (a) the cursor (+inf, -1), (b) the candidate list 0..n_items-1
+    and (c) groups of one under `mean` return amar_recommend_f32's lists — 19 users, one tile + one step + 3 items, one slice and
+    the most the *_slices query accepts, the exclusion rows of helpers.select_case_exclusions."""
+    capi = hip
+    forms = [f for f in rf.FORMS if capi.rank_route('recommend', rf.dims_of(f))['maxt'] == maxt]
+    form = min(forms, key=lambda f: (max(rf.dims_of(f)), sum(rf.dims_of(f))))        # the narrowest head of the grid on this kernel form
+    dims = rf.dims_of(form)
+    route = capi.rank_route('recommend', dims)
+    assert all(capi.rank_fits(kind, dims) for kind in ('recommend', 'among', 'group'))
+    n_users, n_items = rf.N_USERS, route['tile_items'] + 16 * route['pt'] + 3
+    head = Head(capi, form, rf.build(form, n_items, dims=dims))
+    start = (_dev(np.full(n_users, -1)), _dev(np.full(n_users, np.inf), np.float32))
+    ones = np.arange(n_users + 1), np.arange(n_users)                     # groups of one: the exclusion CSR over groups is the users'
+    slices = sorted({1, _largest_slices(capi, 'amar_recommend_slices', n_users, n_items, dims)})
+    group_slices = sorted({1, _largest_slices(capi, 'amar_recommend_group_slices', n_users, n_items, dims, n_users)})
+    assert slices[-1] > 1 and group_slices[-1] > 1
+    host = lambda pair: (pair[0].cpu().numpy(), _bits(pair[1].cpu().numpy()))
+    same = lambda got, want: np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+    for k in KS:
+        e_ptr, e_items = _csr(_exclusions(k, route, n_items))
+        kw = dict(excl_ptr=_dev(e_ptr), excl_items=_dev(e_items))
+        want = host(capi.recommend(*head.args(), k, n_slices=1, **kw))
+        assert (want[0][0] == -1).all() and (want[0][2:] >= 0).any()
+        for s in slices:
+            assert same(host(capi.recommend(*head.args(), k, n_slices=s, **kw)), want), (form.name, k, s)
+            assert same(host(capi.recommend_after(*head.args(), k, *start, n_slices=s, **kw)), want), (form.name, 'after', k, s)
+            assert same(host(capi.recommend_among(*head.args(), k, np.arange(n_items), n_slices=s, **kw)), want), (form.name, 'among', k, s)
+        for s in group_slices:
+            got = capi.recommend_group(*head.args(), k, _dev(ones[0]), _dev(ones[1]), strategy='mean', n_slices=s, **kw)
+            assert same(host(got), want), (form.name, 'group', k, s)
+
+
 # ---- 2. capacity ---------------------------------------------------------------------------------------------------------------
 def _raw_call(capi, kind, head, n_users, n_items, outs):
     """The entry point itself (ctypes), with valid arguments for a one-user, one-target call: its return code."""
