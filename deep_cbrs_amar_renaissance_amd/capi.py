@@ -53,8 +53,10 @@ SIGNATURES = {
     'amar_gcn_layer_f32': (ctypes.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _I64, _P, _I32, _P, _I64, _I32, _P]),
     'amar_rowwise_xw_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I32, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I32, _P]),
     'amar_rowwise_xw_gather_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _P, _I32, _P, _I64, _P, _I32, _P]),
+    'amar_rowwise_xw_route': (ctypes.c_int, [_P, _I64, _I32, _P, _I32, _P, _I64, _P, _I64, _I32, _I32, _I32, _P]),
     'amar_sage_layer_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _I32, _P, _I64, _I32, _I32, _P]),
     'amar_sage_tail_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I32, _P, _P, _I32, _P, _I64, _I64, _P]),
+    'amar_sage_tail_route': (ctypes.c_int, [_I32, _I32, _I64, _P]),
     'amar_sage_layer_agg_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _I32, _P, _I64, _I32, _I32, _I32, _P]),
     'amar_sage_aggregate_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _I64, _P, _I64, _I32, _I32, _I32, _P]),
     'amar_sage_aggregate_bwd_f32': (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I32, _P, _P, _I64, _I32, _I32, _P]),
@@ -530,6 +532,30 @@ def rowwise_xw(X, W, H, copy_to=None, a_self=None, a_neigh=None, s_self=None, s_
             _ptr(row_scale, F32, 'row_scale'), n_rows)
 
 
+XW_KERNELS = ('generic', 'vec8', 'vec16', 'pieces8')
+
+
+class XwRouteInfo(_RouteInfo):
+    """include/amar_hip.h: amar_xw_route_info"""
+    _fields_ = [(name, ctypes.c_int32) for name in ('kernel', 'cp', 'rows_per_block', 'blocks')] + [('trips', ctypes.c_int64)]
+    KERNELS = XW_KERNELS
+
+
+def rowwise_xw_route(X, W, H, copy_to=None, attn=False, row_ids=None):
+    """Which kernel rowwise_xw() runs for these tensors and how its capped grid walks the rows (amar_rowwise_xw_route: host only,
+    nothing is launched; the launcher asks the same function, AMAR_XW_FORM included).  attn: the call computes the attention scalars;
+    row_ids: the gather form, H has one row per id.  A dict: kernel 'generic' | 'vec8' | 'vec16' | 'pieces8', cp, rows_per_block,
+    blocks, trips.  The product of rowwise_xw_heads() is the call with W viewed as [F, heads*C]."""
+    n_rows = int(row_ids.numel()) if row_ids is not None else X.shape[0]
+    F = X.shape[1]
+    if W.dim() != 2 or W.shape[0] != F or not W.is_contiguous() or tuple(H.shape) != (n_rows, W.shape[1]):
+        raise ValueError("rowwise_xw_route: W [F, C] contiguous and H [n_rows, C] expected")
+    info = XwRouteInfo()
+    _call('amar_rowwise_xw_route', *_mat(X, 'X'), F, _ptr(W, F32, 'W'), W.shape[1], *_mat(H, 'H'), *_mat(copy_to, 'copy_to'),
+          1 if attn else 0, 1 if row_ids is not None else 0, n_rows, ctypes.byref(info))
+    return info.as_dict()
+
+
 def sage_layer(rowptr, colidx, X, W, bias, Y, self_loop=True):
     n_rows = rowptr.numel() - 1
     F = X.shape[1]
@@ -547,6 +573,19 @@ def sage_tail(X, agg, W, bias, Y):
             tuple(Y.shape) != (n_rows, W.shape[1]):
         raise ValueError("sage_tail: X [>=n_rows, F], agg [n_rows, F], W [2F, C] contiguous, bias [C], Y [n_rows, C] expected")
     _launch('amar_sage_tail_f32', *_mat(X, 'X'), *_mat(agg, 'agg'), F, _ptr(W, F32, 'W'), _ptr(bias, F32, 'bias'), W.shape[1], *_mat(Y, 'Y'), n_rows)
+
+
+class SageTailRouteInfo(_RouteInfo):
+    """include/amar_hip.h: amar_sage_tail_route_info"""
+    _fields_ = [('cp', ctypes.c_int32), ('blocks', ctypes.c_int32), ('trips', ctypes.c_int64)]
+
+
+def sage_tail_route(F, C, n_rows):
+    """The instantiation (cp accumulators per thread) and the capped grid of sage_tail() for these sizes (amar_sage_tail_route: host
+    only; the launcher takes both from the same function).  A dict: cp, blocks, trips."""
+    info = SageTailRouteInfo()
+    _call('amar_sage_tail_route', int(F), int(C), int(n_rows), ctypes.byref(info))
+    return info.as_dict()
 
 
 def sage_tail_supported(F, C):

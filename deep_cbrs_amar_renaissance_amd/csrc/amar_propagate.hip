@@ -1828,44 +1828,68 @@ int amar_rowwise_xw_gather_f32(const float *X, int64_t ldx, int32_t F, const int
     return rowwise_xw_run(X, ldx, F, W, C, H, ldh, nullptr, 0, nullptr, nullptr, nullptr, nullptr, row_scale, row_ids, n_rows, stream);
 }
 
+// ONE decision for the four prologue kernels: rowwise_xw_run and the host-only query amar_rowwise_xw_route both call it, so what the
+// query reports is what a launch with those arguments runs (AMAR_XW_FORM is read here, at every call: the tests compare the forms in
+// one process).  The pointers are looked at for NULL and alignment only.  Refusals are the launcher's first ones, in its order.
+static int rowwise_xw_route(const float *X, int64_t ldx, int32_t F, const float *W, int32_t C, const float *H, int64_t ldh,
+                            const float *copy_to, int64_t ld_copy, bool attn, bool has_row_ids, int32_t n_rows, amar_xw_route_info *r) {
+    r->kernel = AMAR_XW_KERNEL_GENERIC; r->cp = 0; r->rows_per_block = 0; r->blocks = 0; r->trips = 0;
+    if (n_rows < 0 || !X || !W || !H || F < 1 || C < 1 || ldx < F || ldh < C) return AMAR_EINVAL;
+    if (F > 64 || C > 64) return AMAR_EUNSUPPORTED;
+    if (copy_to && ld_copy < F) return AMAR_EINVAL;
+    int CP = 1;
+    while (CP < C) CP <<= 1;
+    r->cp = CP;
+    if (F == C && (F == 8 || F == 16) && (ldx & 3) == 0 && (ldh & 3) == 0 && amar_aligned16(X) && amar_aligned16(H) &&
+        (!copy_to || ((ld_copy & 3) == 0 && amar_aligned16(copy_to)))) {
+        // the square 8-wide product without attention scalars or row ids: by 16-byte pieces, four per lane (AMAR_XW_FORM=rows keeps the
+        // one-row-per-thread kernel)
+        const char *form = getenv("AMAR_XW_FORM");
+        if (F == 8 && !attn && !has_row_ids && amar_aligned16(W) && !(form && !strcmp(form, "rows"))) {
+            r->kernel = AMAR_XW_KERNEL_PIECES8;
+            r->rows_per_block = 512;                                 // (1 024 pieces: four per lane, two lanes per row)
+        } else {
+            r->kernel = F == 8 ? AMAR_XW_KERNEL_VEC8 : AMAR_XW_KERNEL_VEC16;
+            r->rows_per_block = F == 8 ? 512 : 256;                  // (two rows per thread at F = 8)
+        }
+    } else {
+        r->rows_per_block = 256 / CP;
+    }
+    int64_t blocks = ((int64_t)n_rows + r->rows_per_block - 1) / r->rows_per_block;
+    if (blocks > 8192) blocks = 8192;
+    r->blocks = (int32_t)blocks;
+    const int64_t per_trip = blocks * r->rows_per_block;
+    r->trips = blocks ? ((int64_t)n_rows + per_trip - 1) / per_trip : 0;
+    return AMAR_OK;
+}
+
 static int rowwise_xw_run(const float *X, int64_t ldx, int32_t F, const float *W, int32_t C,
                           float *H, int64_t ldh, float *copy_to, int64_t ld_copy,
                           const float *a_self, const float *a_neigh, float *s_self, float *s_neigh,
                           const float *row_scale, const int32_t *row_ids, int32_t n_rows, amar_stream_t stream) {
-    if (n_rows < 0 || !X || !W || !H || F < 1 || C < 1 || ldx < F || ldh < C) return AMAR_EINVAL;
-    if (F > 64 || C > 64) return AMAR_EUNSUPPORTED;
-    if (copy_to && ld_copy < F) return AMAR_EINVAL;
     const bool attn = a_self || a_neigh || s_self || s_neigh;
+    amar_xw_route_info route;
+    if (const int rc = rowwise_xw_route(X, ldx, F, W, C, H, ldh, copy_to, ld_copy, attn, row_ids != nullptr, n_rows, &route)) return rc;
     if (attn && !(a_self && a_neigh && s_self && s_neigh)) return AMAR_EINVAL;
     if (n_rows == 0) return AMAR_OK;
-    int CP = 1;
-    while (CP < C) CP <<= 1;
     if (attn && row_scale) return AMAR_EINVAL;                       // the attention scalars are defined on the un-scaled product
     XwArgs a{X, ldx, F, W, C, H, ldh, copy_to, ld_copy, a_self, a_neigh, attn ? s_self : nullptr, s_neigh, n_rows, row_scale, row_ids};
-    if (F == C && (F == 8 || F == 16) && (ldx & 3) == 0 && (ldh & 3) == 0 && amar_aligned16(X) && amar_aligned16(H) &&
-        (!copy_to || ((ld_copy & 3) == 0 && amar_aligned16(copy_to)))) {
-        // the square 8-wide product without attention scalars or row ids: by 16-byte pieces, four per lane (AMAR_XW_FORM=rows keeps the
-        // one-row-per-thread kernel; read at every call: the tests compare the two forms in one process)
-        const char *form = getenv("AMAR_XW_FORM");
-        if (F == 8 && !attn && !row_ids && amar_aligned16(W) && !(form && !strcmp(form, "rows"))) {
-            int64_t pblocks = (2 * (int64_t)n_rows + 1023) / 1024;
-            if (pblocks > 8192) pblocks = 8192;
-            hipLaunchKernelGGL(rowwise_xw8_pieces_kernel<4>, dim3((unsigned)pblocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-            return amar_check_launch();
-        }
-        const int rows_per_block = F == 8 ? 512 : 256;              // (two rows per thread at F = 8)
-        int64_t vblocks = ((int64_t)n_rows + rows_per_block - 1) / rows_per_block;
-        if (vblocks > 8192) vblocks = 8192;
-        if (F == 8) hipLaunchKernelGGL(rowwise_xw_vec_kernel<8>, dim3((unsigned)vblocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-        else hipLaunchKernelGGL(rowwise_xw_vec_kernel<16>, dim3((unsigned)vblocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-        return amar_check_launch();
+    const dim3 grid((unsigned)route.blocks), block(256);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (route.kernel) {
+    case AMAR_XW_KERNEL_PIECES8: hipLaunchKernelGGL(rowwise_xw8_pieces_kernel<4>, grid, block, 0, st, a); break;
+    case AMAR_XW_KERNEL_VEC8:    hipLaunchKernelGGL(rowwise_xw_vec_kernel<8>, grid, block, 0, st, a); break;
+    case AMAR_XW_KERNEL_VEC16:   hipLaunchKernelGGL(rowwise_xw_vec_kernel<16>, grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL(rowwise_xw_kernel, grid, block, (size_t)F * C * sizeof(float), st, a, route.cp); break;
     }
-    const int rows_per_block = 256 / CP;
-    int64_t blocks = ((int64_t)n_rows + rows_per_block - 1) / rows_per_block;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(rowwise_xw_kernel, dim3((unsigned)blocks), dim3(256), (size_t)F * C * sizeof(float),
-                       static_cast<hipStream_t>(stream), a, CP);
     return amar_check_launch();
+}
+
+int amar_rowwise_xw_route(const float *X, int64_t ldx, int32_t F, const float *W, int32_t C,
+                          const float *H, int64_t ldh, const float *copy_to, int64_t ld_copy,
+                          int32_t has_attn, int32_t has_row_ids, int32_t n_rows, amar_xw_route_info *info) {
+    if (!info) return AMAR_EINVAL;
+    return rowwise_xw_route(X, ldx, F, W, C, H, ldh, copy_to, ld_copy, has_attn != 0, has_row_ids != 0, n_rows, info);
 }
 
 int amar_sage_layer_f32(const int32_t *rowptr, const int32_t *colidx,
@@ -1891,6 +1915,15 @@ int amar_sage_layer_f32(const int32_t *rowptr, const int32_t *colidx,
     return amar_check_launch();
 }
 
+// The instantiation and the capped grid of amar_sage_tail_f32, for the launcher and for amar_sage_tail_route (4 <= C <= 64, n_rows >= 0).
+static void sage_tail_plan(int32_t C, int64_t n_rows, amar_sage_tail_route_info *r) {
+    r->cp = C <= 4 ? 4 : C <= 8 ? 8 : C <= 16 ? 16 : C <= 32 ? 32 : 64;
+    int64_t blocks = (n_rows + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    r->blocks = (int32_t)blocks;
+    r->trips = blocks ? (n_rows + blocks * 256 - 1) / (blocks * 256) : 0;
+}
+
 int amar_sage_tail_f32(const float *X, int64_t ldx, const float *AGG, int64_t lda, int32_t F,
                        const float *W, const float *bias, int32_t C, float *Y, int64_t ldy,
                        int64_t n_rows, amar_stream_t stream) {
@@ -1901,16 +1934,27 @@ int amar_sage_tail_f32(const float *X, int64_t ldx, const float *AGG, int64_t ld
     if (n_rows == 0) return AMAR_OK;
     SageTailArgs a{X, ldx, AGG, lda, F, W, bias, C, Y, ldy, n_rows};
     const size_t lds = (size_t)(2 * F * C + C) * sizeof(float);   // <= 33 KB
-    int64_t blocks = (n_rows + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    const dim3 grid((unsigned)blocks), block(256);
+    amar_sage_tail_route_info route;
+    sage_tail_plan(C, n_rows, &route);
+    const dim3 grid((unsigned)route.blocks), block(256);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (C <= 4) hipLaunchKernelGGL(sage_tail_kernel<4>, grid, block, lds, st, a);
-    else if (C <= 8) hipLaunchKernelGGL(sage_tail_kernel<8>, grid, block, lds, st, a);
-    else if (C <= 16) hipLaunchKernelGGL(sage_tail_kernel<16>, grid, block, lds, st, a);
-    else if (C <= 32) hipLaunchKernelGGL(sage_tail_kernel<32>, grid, block, lds, st, a);
-    else hipLaunchKernelGGL(sage_tail_kernel<64>, grid, block, lds, st, a);
+    switch (route.cp) {
+    case 4:  hipLaunchKernelGGL(sage_tail_kernel<4>, grid, block, lds, st, a); break;
+    case 8:  hipLaunchKernelGGL(sage_tail_kernel<8>, grid, block, lds, st, a); break;
+    case 16: hipLaunchKernelGGL(sage_tail_kernel<16>, grid, block, lds, st, a); break;
+    case 32: hipLaunchKernelGGL(sage_tail_kernel<32>, grid, block, lds, st, a); break;
+    default: hipLaunchKernelGGL(sage_tail_kernel<64>, grid, block, lds, st, a); break;
+    }
     return amar_check_launch();
+}
+
+int amar_sage_tail_route(int32_t F, int32_t C, int64_t n_rows, amar_sage_tail_route_info *info) {
+    if (!info) return AMAR_EINVAL;
+    info->cp = 0; info->blocks = 0; info->trips = 0;
+    if (n_rows < 0 || F < 4 || C < 4 || (F & 3) || (C & 3)) return AMAR_EINVAL;
+    if (F > 64 || C > 64) return AMAR_EUNSUPPORTED;
+    sage_tail_plan(C, n_rows, info);
+    return AMAR_OK;
 }
 
 // drop == nullptr: the inference kernels; else the DROP instantiations (training, attention dropout)

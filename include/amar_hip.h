@@ -220,6 +220,37 @@ int amar_rowwise_xw_f32(const float *X, int64_t ldx, int32_t F, const float *W, 
 int amar_rowwise_xw_gather_f32(const float *X, int64_t ldx, int32_t F, const int32_t *row_ids, const float *W, int32_t C,
                                float *H, int64_t ldh, const float *row_scale, int32_t n_rows, amar_stream_t stream);
 
+/* Which kernel the two entry points above (and the product of amar_rowwise_xw_heads_f32, asked with C = heads * C) run for a call,
+ * and how its capped grid walks the rows (host only: launches nothing, the pointers are looked at for NULL and alignment only).  The
+ * launcher calls the same function, AMAR_XW_FORM read at every call included, so a test can assert the form before it launches it.
+ *   kernel   AMAR_XW_KERNEL_PIECES8  F == C == 8, no attention scalars, no row ids, AMAR_XW_FORM != "rows"; ldx, ldh (and ld_copy)
+ *                                    multiples of 4; X, H, W (and copy_to) 16-byte aligned: 16-byte pieces, two lanes per row
+ *            AMAR_XW_KERNEL_VEC8     the same alignment of X, H, copy_to and the leading dimensions, with attention scalars, row ids,
+ *                                    a W that is not 16-byte aligned or AMAR_XW_FORM=rows: one thread per row, two rows per thread
+ *            AMAR_XW_KERNEL_VEC16    F == C == 16 under the same alignment rules (W's alignment is not looked at): one row per thread
+ *            AMAR_XW_KERNEL_GENERIC  everything else: cp lanes per row, cp = C rounded up to a power of two
+ *   cp              C rounded up to a power of two (every kernel)
+ *   rows_per_block  rows one workgroup of 256 threads takes per trip: 256 / cp (generic), 512 (pieces, vec 8), 256 (vec 16)
+ *   blocks          min(ceil(n_rows / rows_per_block), 8192) workgroups; 0 for n_rows == 0 (nothing is launched)
+ *   trips           iterations of the grid-stride loop of the thread that makes most: ceil(n_rows / (blocks * rows_per_block)).  The
+ *                   second trip starts at n_rows = 8192 * rows_per_block + 1: 4 194 305 (pieces, vec 8), 2 097 153 (vec 16),
+ *                   32 768 * (64 / cp) + 1 (generic).
+ * has_attn: any of a_self / a_neigh / s_self / s_neigh is given; has_row_ids: the call is amar_rowwise_xw_gather_f32's.
+ * Returns the launcher's first refusals in its order: AMAR_EINVAL (n_rows < 0, X, W or H NULL, F or C < 1, ldx < F, ldh < C,
+ * info == NULL), AMAR_EUNSUPPORTED (F or C > 64), AMAR_EINVAL (copy_to with ld_copy < F).  What the launcher refuses after these (an
+ * incomplete set of attention operands; attention scalars together with row_scale) is not asked here. */
+#define AMAR_XW_KERNEL_GENERIC 0
+#define AMAR_XW_KERNEL_VEC8 1
+#define AMAR_XW_KERNEL_VEC16 2
+#define AMAR_XW_KERNEL_PIECES8 3
+typedef struct amar_xw_route_info {
+    int32_t kernel, cp, rows_per_block, blocks;
+    int64_t trips;
+} amar_xw_route_info;
+int amar_rowwise_xw_route(const float *X, int64_t ldx, int32_t F, const float *W, int32_t C,
+                          const float *H, int64_t ldh, const float *copy_to, int64_t ld_copy,
+                          int32_t has_attn, int32_t has_row_ids, int32_t n_rows, amar_xw_route_info *info);
+
 /* One GraphSAGE-mean layer (Spektral 1.x GraphSageConv, built at src/models/gnn.py:354-361):
  *     agg_i = ( [self_loop] X_i + sum_{j in N(i)} X_j ) / ( [self_loop] 1 + |N(i)| )
  *     Y_i   = ReLU( l2_normalize( [X_i || agg_i] . W[2F, C] + bias ) )
@@ -238,6 +269,18 @@ int amar_sage_layer_f32(const int32_t *rowptr, const int32_t *colidx,
 int amar_sage_tail_f32(const float *X, int64_t ldx, const float *AGG, int64_t lda, int32_t F,
                        const float *W, const float *bias, int32_t C, float *Y, int64_t ldy,
                        int64_t n_rows, amar_stream_t stream);
+
+/* The instantiation and the grid of amar_sage_tail_f32 (host only; the launcher takes both from the same function):
+ *   cp      accumulators per thread: the smallest of 4, 8, 16, 32, 64 that holds C (C = 12, 20, 36 .. leave cp - C of them guarded off)
+ *   blocks  min(ceil(n_rows / 256), 8192) workgroups of 256 threads, one row per thread; 0 for n_rows == 0
+ *   trips   ceil(n_rows / (blocks * 256)): the second trip starts at n_rows = 2 097 153
+ * Returns the launcher's shape refusals: AMAR_EINVAL (n_rows < 0, F or C < 4 or not a multiple of 4, info == NULL), AMAR_EUNSUPPORTED
+ * (F or C > 64).  The launcher looks at its pointers and leading dimensions between the two. */
+typedef struct amar_sage_tail_route_info {
+    int32_t cp, blocks;
+    int64_t trips;
+} amar_sage_tail_route_info;
+int amar_sage_tail_route(int32_t F, int32_t C, int64_t n_rows, amar_sage_tail_route_info *info);
 
 /* GraphSAGE's other aggregators (config.yaml:17-18 `model.aggregate`, handed to Spektral's GraphSageConv at
  * src/models/gnn.py:331-361; Spektral 1.x resolves the name to a segment reduction).  The entries of row i are its CSR row
