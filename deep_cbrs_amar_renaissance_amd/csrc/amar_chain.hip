@@ -357,8 +357,15 @@ __global__ __launch_bounds__(256) void chain_rows2_kernel(const ChainArgs2 a2) {
 // so the splitting (4.5 VALU instructions per activation) and the rest of the loop run beside the matrix pipe instead of behind it.
 // k-slot j of k-step s at lane group g is feature 16 (2s + j/4) + 4g + j%4: the two f32 tiles 2s, 2s+1 the lane already holds, so the
 // gathers, the register-resident hand-over between layers and the host-side weight pack are those of the f32 form — the workgroup
-// splits its LDS copy of the packed weights into bf16 fragments once, at its start.  With an odd tile count (48 = 3 tiles) the spare
-// half k-step carries the bias (activation 1.0 at feature 16 MAXT, the bias in the weight's row), so accumulators start at 0.
+// splits its LDS copy of the packed weights into bf16 fragments once, at its start.  With an odd tile count (48 = 3 tiles) the last
+// tile T has no partner, and a k-step of its own would multiply zeros in its other half (36 MFMAs for 18 MFMAs' products per 32 pairs).
+// It is folded over PARTS instead: three k-steps carry its six part products, one product in dwords 0,1 and one in dwords 2,3,
+//      step   activations (B)        weights (A)
+//      a      x.hi(T) || x.lo(T)     w.lo(T)  || w.hi(T)
+//      b      x.mid(T) || x.hi(T)    w.mid(T) || w.mid(T)
+//      c      x.mid(T) || x.hi(T)    w.hi(T)  || w.hi(T)
+// small products first as in a full step (a, b, c after the full steps); b and c share their B operand, both B operands are the dwords
+// split_pair makes for the tile anyway, and a (layer, m) still has six fragments in LDS.  Accumulators start at the bias in every form.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -411,24 +418,33 @@ __global__ __launch_bounds__(256) void chain_pipe_kernel(const ChainArgs a) {
     __syncthreads();
 
     const int lane = threadIdx.x & 63, g = lane >> 4, col = lane & 15;
-    constexpr int KS = (MAXT + 1) / 2;                       // bf16 k-steps of 32 (two f32 tiles each)
-    constexpr bool BIASK = SPLIT && (MAXT & 1);              // the bias rides in the spare half k-step
-    u32x4 *frag = reinterpret_cast<u32x4 *>(w_lds + ((a.wpack_floats + 3) & ~3));   // bf16 fragments [layer][m][s][part][lane]
+    constexpr int FS = MAXT / 2;                             // full bf16 k-steps of 32 (the f32 tiles 2s, 2s + 1)
+    constexpr bool FOLD = SPLIT && (MAXT & 1);               // the odd last tile: three k-steps of two part products each
+    constexpr int NF = 3 * FS + (MAXT & 1 ? 3 : 0);          // fragments per (layer, m): three parts per full step, three folded ones
+    u32x4 *frag = reinterpret_cast<u32x4 *>(w_lds + ((a.wpack_floats + 3) & ~3));   // bf16 fragments [layer][m][s][part][lane], then [layer][m][fold a, b, c][lane]
     if (SPLIT) {
-        for (int idx = threadIdx.x >> 6; idx < a.n_layers * MAXT * KS; idx += 4) {
-            const int l = idx / (MAXT * KS), m = (idx % (MAXT * KS)) / KS, sk = idx % KS;
+        for (int idx = threadIdx.x >> 6; idx < a.n_layers * MAXT * (NF / 3); idx += 4) {
+            const int l = idx / (MAXT * (NF / 3)), m = (idx % (MAXT * (NF / 3))) / (NF / 3), sk = idx % (NF / 3);
             const float *wl = w_lds + a.w_off[l];
             const f32x4 wa = *reinterpret_cast<const f32x4 *>(wl + ((m * MAXT + 2 * sk) * 64 + lane) * 4);
-            f32x4 wb = {0.f, 0.f, 0.f, 0.f};
-            if (2 * sk + 1 < MAXT) wb = *reinterpret_cast<const f32x4 *>(wl + ((m * MAXT + 2 * sk + 1) * 64 + lane) * 4);
-            else if (BIASK && g == 0) wb[0] = w_lds[a.b_off[l] + 16 * m + col];
             u32x4 *dst = frag + idx * 3 * 64 + lane;
-            const Split3 q0 = split_pair(wa[0], wa[1]), q1 = split_pair(wa[2], wa[3]), q2 = split_pair(wb[0], wb[1]), q3 = split_pair(wb[2], wb[3]);
-            u32x4 h, mm, lo;
-            h[0] = q0.h; h[1] = q1.h; h[2] = q2.h; h[3] = q3.h;
-            mm[0] = q0.m; mm[1] = q1.m; mm[2] = q2.m; mm[3] = q3.m;
-            lo[0] = q0.l; lo[1] = q1.l; lo[2] = q2.l; lo[3] = q3.l;
-            dst[0] = h; dst[64] = mm; dst[128] = lo;
+            const Split3 q0 = split_pair(wa[0], wa[1]), q1 = split_pair(wa[2], wa[3]);
+            if (FOLD && sk == FS) {
+                // the last tile alone: lo || hi, mid || mid, hi || hi against the activations' hi || lo, mid || hi, mid || hi
+                u32x4 fa, fb, fc;
+                fa[0] = q0.l; fa[1] = q1.l; fa[2] = q0.h; fa[3] = q1.h;
+                fb[0] = q0.m; fb[1] = q1.m; fb[2] = q0.m; fb[3] = q1.m;
+                fc[0] = q0.h; fc[1] = q1.h; fc[2] = q0.h; fc[3] = q1.h;
+                dst[0] = fa; dst[64] = fb; dst[128] = fc;
+            } else {
+                const f32x4 wb = *reinterpret_cast<const f32x4 *>(wl + ((m * MAXT + 2 * sk + 1) * 64 + lane) * 4);
+                const Split3 q2 = split_pair(wb[0], wb[1]), q3 = split_pair(wb[2], wb[3]);
+                u32x4 h, mm, lo;
+                h[0] = q0.h; h[1] = q1.h; h[2] = q2.h; h[3] = q3.h;
+                mm[0] = q0.m; mm[1] = q1.m; mm[2] = q2.m; mm[3] = q3.m;
+                lo[0] = q0.l; lo[1] = q1.l; lo[2] = q2.l; lo[3] = q3.l;
+                dst[0] = h; dst[64] = mm; dst[128] = lo;
+            }
         }
         __syncthreads();
     }
@@ -488,45 +504,56 @@ __global__ __launch_bounds__(256) void chain_pipe_kernel(const ChainArgs a) {
         load_ids(base + 2 * stride, ra, rb);
         for (int l = 0; SPLIT && l < a.n_layers; ++l) {
             // activations -> bf16 parts, in B-operand order: dwords 0,1 = tile 2s, dwords 2,3 = tile 2s + 1
-            u32x4 xq[3][KS][PT];
+            u32x4 xq[3][FS > 0 ? FS : 1][PT];
 #pragma unroll
-            for (int sk = 0; sk < KS; ++sk)
+            for (int sk = 0; sk < FS; ++sk)
 #pragma unroll
                 for (int pt = 0; pt < PT; ++pt) {
 #pragma unroll
                     for (int hf = 0; hf < 2; ++hf) {
                         const int t = 2 * sk + hf;
-                        if (t < MAXT) {
-                            const Split3 q0 = split_pair(x[t][pt][0], x[t][pt][1]), q1 = split_pair(x[t][pt][2], x[t][pt][3]);
-                            xq[0][sk][pt][2 * hf] = q0.h; xq[1][sk][pt][2 * hf] = q0.m; xq[2][sk][pt][2 * hf] = q0.l;
-                            xq[0][sk][pt][2 * hf + 1] = q1.h; xq[1][sk][pt][2 * hf + 1] = q1.m; xq[2][sk][pt][2 * hf + 1] = q1.l;
-                        } else {
-                            xq[0][sk][pt][2] = (BIASK && g == 0) ? 0x00003f80u : 0u;       // bf16 1.0 at feature 16 MAXT
-                            xq[0][sk][pt][3] = 0u;
-                            xq[1][sk][pt][2] = xq[1][sk][pt][3] = xq[2][sk][pt][2] = xq[2][sk][pt][3] = 0u;
-                        }
+                        const Split3 q0 = split_pair(x[t][pt][0], x[t][pt][1]), q1 = split_pair(x[t][pt][2], x[t][pt][3]);
+                        xq[0][sk][pt][2 * hf] = q0.h; xq[1][sk][pt][2 * hf] = q0.m; xq[2][sk][pt][2 * hf] = q0.l;
+                        xq[0][sk][pt][2 * hf + 1] = q1.h; xq[1][sk][pt][2 * hf + 1] = q1.m; xq[2][sk][pt][2 * hf + 1] = q1.l;
                     }
                 }
-            const u32x4 *fl = frag + (size_t)l * MAXT * KS * 3 * 64 + lane;
+            // the odd last tile by itself: hi || lo for fold step a, mid || hi for steps b and c (six dwords, four of them in each operand)
+            u32x4 xf[2][PT];
+            if (FOLD) {
+#pragma unroll
+                for (int pt = 0; pt < PT; ++pt) {
+                    const Split3 q0 = split_pair(x[MAXT - 1][pt][0], x[MAXT - 1][pt][1]), q1 = split_pair(x[MAXT - 1][pt][2], x[MAXT - 1][pt][3]);
+                    xf[0][pt][0] = q0.h; xf[0][pt][1] = q1.h; xf[0][pt][2] = q0.l; xf[0][pt][3] = q1.l;
+                    xf[1][pt][0] = q0.m; xf[1][pt][1] = q1.m; xf[1][pt][2] = q0.h; xf[1][pt][3] = q1.h;
+                }
+            }
+            const u32x4 *fl = frag + (size_t)l * MAXT * NF * 64 + lane;
             const float *bl = w_lds + a.b_off[l];
             f32x4 y[MAXT][PT];
 #pragma unroll
             for (int m = 0; m < MAXT; ++m) {
-                f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
-                if (!BIASK) b4 = *reinterpret_cast<const f32x4 *>(bl + 16 * m + 4 * g);
+                const f32x4 b4 = *reinterpret_cast<const f32x4 *>(bl + 16 * m + 4 * g);
 #pragma unroll
                 for (int pt = 0; pt < PT; ++pt) y[m][pt] = b4;
 #pragma unroll
-                for (int sk = 0; sk < KS; ++sk) {
-                    const bf16x8 wh = __builtin_bit_cast(bf16x8, fl[((m * KS + sk) * 3 + 0) * 64]);
-                    const bf16x8 wm = __builtin_bit_cast(bf16x8, fl[((m * KS + sk) * 3 + 1) * 64]);
-                    const bf16x8 wo = __builtin_bit_cast(bf16x8, fl[((m * KS + sk) * 3 + 2) * 64]);
+                for (int sk = 0; sk < FS; ++sk) {
+                    const bf16x8 wh = __builtin_bit_cast(bf16x8, fl[(m * NF + sk * 3 + 0) * 64]);
+                    const bf16x8 wm = __builtin_bit_cast(bf16x8, fl[(m * NF + sk * 3 + 1) * 64]);
+                    const bf16x8 wo = __builtin_bit_cast(bf16x8, fl[(m * NF + sk * 3 + 2) * 64]);
                     AMAR_SPLIT_MFMA(wo, xq[0][sk]);
                     AMAR_SPLIT_MFMA(wh, xq[2][sk]);
                     AMAR_SPLIT_MFMA(wm, xq[1][sk]);
                     AMAR_SPLIT_MFMA(wm, xq[0][sk]);
                     AMAR_SPLIT_MFMA(wh, xq[1][sk]);
                     AMAR_SPLIT_MFMA(wh, xq[0][sk]);
+                }
+                if (FOLD) {
+                    const bf16x8 wa = __builtin_bit_cast(bf16x8, fl[(m * NF + FS * 3 + 0) * 64]);
+                    const bf16x8 wb = __builtin_bit_cast(bf16x8, fl[(m * NF + FS * 3 + 1) * 64]);
+                    const bf16x8 wc = __builtin_bit_cast(bf16x8, fl[(m * NF + FS * 3 + 2) * 64]);
+                    AMAR_SPLIT_MFMA(wa, xf[0]);                    // lo.hi + hi.lo
+                    AMAR_SPLIT_MFMA(wb, xf[1]);                    // mid.mid + mid.hi
+                    AMAR_SPLIT_MFMA(wc, xf[1]);                    // hi.mid + hi.hi
                 }
             }
 #pragma unroll
@@ -1229,7 +1256,8 @@ static int chain_route(const float *A, int64_t lda, int32_t Da, const int32_t *i
         a.Db == a.Da && maxt <= 4 && lds_bytes <= 64 * 1024 && small_tables && (a.has_dot || !a.out_index)) {
         // products on the bf16 matrix instruction with three-way split operands (see the kernel's header); AMAR_PAIR_MFMA=f32: the f32 one
         static const bool f32_only = getenv("AMAR_PAIR_MFMA") && !strcmp(getenv("AMAR_PAIR_MFMA"), "f32");
-        const size_t split_bytes = (((size_t)off + 3) & ~(size_t)3) * sizeof(float) + (size_t)a.n_layers * maxt * ((maxt + 1) / 2) * 3 * 1024;
+        // fragments of 1 KB per (layer, m): three parts per full k-step and the three folded ones of an odd last tile
+        const size_t split_bytes = (((size_t)off + 3) & ~(size_t)3) * sizeof(float) + (size_t)a.n_layers * maxt * (3 * (maxt / 2) + 3 * (maxt & 1)) * 1024;
         r.kernel = AMAR_CHAIN_KERNEL_PIPE;
         r.split = !f32_only && split_bytes <= 64 * 1024;
         r.scatter = a.out_index != nullptr;
