@@ -162,6 +162,8 @@ SIGNATURES = {
                                                 _I32, _F32, _I32, _I32, _P, _P, _P, _P, _P]),
     'amar_recommend_among_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P,
                                                 _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    'amar_recommend_lists_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P,
+                                                _P, _P, _I32, _P, _P, _P]),
     'amar_recommend_after_f32': (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I64, _P, _P,
                                                 _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     'amar_nearest_slices': (ctypes.c_int32, [_I64, _I32, _I32, _I32]),
@@ -1509,7 +1511,7 @@ def _sliced_topk(slices_fn, slices_args, n_slices, m, k, dev, split_head=True):
     return slices, out_rows, out_scores, ws_rows, ws_scores
 
 
-RANK_KINDS = {'recommend': 0, 'group': 1, 'rank_of': 2, 'among': 4}    # include/amar_hip.h: AMAR_RANK_RECOMMEND / _GROUP / _RANK_OF / _AMONG
+RANK_KINDS = {'recommend': 0, 'group': 1, 'rank_of': 2, 'among': 4, 'lists': 5}    # include/amar_hip.h: AMAR_RANK_RECOMMEND / _GROUP / _RANK_OF / _AMONG / _LISTS
 
 
 class RankRouteInfo(_RouteInfo):
@@ -1520,7 +1522,8 @@ class RankRouteInfo(_RouteInfo):
 
 
 def rank_route(kind, dims, code=False):
-    """What `recommend` ('recommend'), `recommend_group` ('group'), `rank_of` ('rank_of') or `recommend_among` ('among') does with a rest stack of the widths
+    """What `recommend` ('recommend'), `recommend_group` ('group'), `rank_of` ('rank_of'), `recommend_among` ('among') or
+    `recommend_lists` ('lists': no item tile in its sum, so it takes heads the others refuse) does with a rest stack of the widths
     `dims` (c1, ..., 1): the launch geometry (maxt, pt, tile_items, tile_stride), wpack_floats, the dynamic LDS of a launch
     (lds_bytes), `fits` (lds_bytes <= 160 KB: False = the entry point refuses the head with AMAR_EUNSUPPORTED) and `large_lds`
     (> 64 KB).  amar_rank_route: host only, the launchers ask the same function.  A dict; with code=True the return code is added as
@@ -1614,6 +1617,58 @@ def recommend_among(Tu, Ti, wpack, dims, acts, in_act, k, cand, users=None, excl
             _ptr_entries(excl_items, I32, 'excl_items'), _ptr(cand_dev, I32, 'cand'), n_cand,
             int(k), int(slices) if slices > 1 else 1, _ptr(ws_i), _ptr(ws_s),
             _ptr(out_items) if m else None, _ptr(out_scores) if m else None)
+    return out_items, out_scores
+
+
+def check_candidate_lists(cand_ptr, cand_items, m, n_items, what='recommend_lists'):
+    """A HOST CSR of candidate lists as amar_recommend_lists_f32 wants it: cand_ptr m + 1 non-decreasing integers from 0 to
+    len(cand_items) < 2^31, cand_items integer item rows in [0, n_items), strictly ascending inside every list.  The kernel cannot
+    check its lists, so nothing that fails here is uploaded: ValueError.  Returns (ptr int32, items int32)."""
+    import numpy as np
+    ptr, rows = np.asarray(cand_ptr), np.asarray(cand_items)
+    for a, name in ((ptr, 'cand_ptr'), (rows, 'cand_items')):
+        if a.ndim != 1 or (a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer))):
+            raise ValueError("{}: {} must be a 1-D sequence of integers".format(what, name))
+    ptr, rows = ptr.astype(np.int64), rows.astype(np.int64)
+    if ptr.size != m + 1 or ptr[0] != 0 or (np.diff(ptr) < 0).any() or ptr[-1] != rows.size:
+        raise ValueError("{}: cand_ptr must hold {} non-decreasing offsets from 0 to len(cand_items)".format(what, m + 1))
+    if rows.size >= 1 << 31:
+        raise ValueError("{}: the candidate lists must hold fewer than 2^31 entries together".format(what))
+    if rows.size and (rows.min() < 0 or rows.max() >= n_items):
+        raise ValueError("{}: cand_items must lie in [0, {}) (got {}..{})".format(what, n_items, int(rows.min()), int(rows.max())))
+    if rows.size > 1:
+        falls = np.diff(rows) <= 0                                           # allowed only where a new list starts
+        falls[ptr[1:-1][(ptr[1:-1] > 0) & (ptr[1:-1] < rows.size)] - 1] = False
+        if falls.any():
+            raise ValueError("{}: cand_items must be strictly ascending inside every list (sorted, no duplicates)".format(what))
+    return np.ascontiguousarray(ptr, dtype=np.int32), np.ascontiguousarray(rows, dtype=np.int32)
+
+
+def recommend_lists(Tu, Ti, wpack, dims, acts, in_act, k, cand_ptr, cand_items, users=None, excl_ptr=None, excl_items=None):
+    """Fused top-k over per-user candidate lists (amar_recommend_lists_f32): for listed row j (user users[j]; row j of Tu when
+    `users` is None) the k best of the item rows cand_items[cand_ptr[j] : cand_ptr[j + 1]] that are not in the user's exclusion CSR.
+    The CSR is either a pair of HOST sequences, checked here (`check_candidate_lists`: ascending inside every list, distinct, in
+    range — ValueError) before it is uploaded, or a pair of int32 DEVICE tensors, which the caller answers for: the kernel cannot
+    check its lists.  Returns (items int32 [m, k] item rows (-1 padded), scores float32 [m, k] (-inf padded)): what `recommend`
+    returns with the complement of every row's list merged into its exclusion row, bit for bit.  One launch, no workspace."""
+    n_users, n_items, dims_c, head = _rank_head('recommend_lists', Tu, Ti, wpack, dims, acts, in_act)
+    m = int(users.numel()) if users is not None else n_users
+    on_device = isinstance(cand_ptr, torch.Tensor) and cand_ptr.is_cuda
+    if on_device != (isinstance(cand_items, torch.Tensor) and cand_items.is_cuda):
+        raise ValueError("recommend_lists: cand_ptr and cand_items must both be host sequences or both device tensors")
+    if on_device:
+        if cand_ptr.dim() != 1 or cand_ptr.numel() != m + 1 or cand_items.dim() != 1 or cand_items.numel() >= 1 << 31:
+            raise ValueError("recommend_lists: cand_ptr must have {} entries, cand_items fewer than 2^31".format(m + 1))
+    else:
+        ptr, rows = check_candidate_lists(cand_ptr.cpu().numpy() if isinstance(cand_ptr, torch.Tensor) else cand_ptr,
+                                          cand_items.cpu().numpy() if isinstance(cand_items, torch.Tensor) else cand_items, m, n_items)
+        cand_ptr, cand_items = torch.from_numpy(ptr).to(Tu.device), torch.from_numpy(rows).to(Tu.device)
+    _check_exclusion('recommend_lists', excl_ptr, excl_items, n_users)
+    out_items = torch.empty((m, k), dtype=torch.int32, device=Tu.device)
+    out_scores = torch.empty((m, k), dtype=torch.float32, device=Tu.device)
+    _launch('amar_recommend_lists_f32', *head(), _ptr(users, I32, 'users'), m, _ptr(excl_ptr, I32, 'excl_ptr'),
+            _ptr_entries(excl_items, I32, 'excl_items'), _ptr(cand_ptr, I32, 'cand_ptr'), _ptr_entries(cand_items, I32, 'cand_items'),
+            int(k), _ptr(out_items) if m else None, _ptr(out_scores) if m else None)
     return out_items, out_scores
 
 

@@ -136,7 +136,7 @@ int amar_recommend_f32(const float *Tu, int64_t ldu, int32_t n_users, const floa
 int amar_rank_route(int32_t kind, const int32_t *dims, int32_t n_layers, amar_rank_route_info *info) {
     if (!dims || !info) return AMAR_EINVAL;
     *info = amar_rank_route_info{};
-    if (kind != AMAR_RANK_RECOMMEND && kind != AMAR_RANK_GROUP && kind != AMAR_RANK_RANK_OF && kind != AMAR_RANK_AMONG) return AMAR_EINVAL;
+    if (!rank_kind_known(kind)) return AMAR_EINVAL;
     if (n_layers < 2 || n_layers > RANK_MAX_LAYERS + 1) return AMAR_EUNSUPPORTED;
     const int32_t c1 = dims[0];                                          // the head's part of rank_check_tables, in its order
     if (c1 < 4 || (c1 & 3)) return AMAR_EINVAL;

@@ -37,34 +37,12 @@ struct RankOfArgs {
     int32_t *out_greater, *out_before, *out_after;
 };
 
-__device__ __forceinline__ void ro_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
-
 // The score stage on the 16 PT rows that start at row `grp` of `tile`: the score of the user against row grp + 16 g + col.
 template <int MAXT, int PT>
 __device__ __forceinline__ float ro_score(const RankArgs &a, const float *w_lds, const float *tile, int grp, const f32x4 (&tu)[MAXT],
                                           int lane, int g, int col, int KT0) {
 #include "amar_rank_score.inc"
     return z;
-}
-
-// Rows ids[0 .. count) of Ti go to the wave's buffer (16 PT rows of 16 KT0 features, zero past c1, past `count` and for an id
-// outside the table); the caller's wave syncs stand on either side.
-template <int PT>
-__device__ __forceinline__ void ro_gather(const RankArgs &a, float *buf, const int32_t *ids, int count, int lane) {
-    const int f4_per_row = 4 * a.kt[0];
-    for (int idx = lane; idx < 16 * PT * f4_per_row; idx += AMAR_WAVE) {
-        const int r = idx / f4_per_row, f = 4 * (idx - r * f4_per_row);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (r < count && f < a.c1) {
-            const int it = ids[r];
-            if ((unsigned)it < (unsigned)a.n_items) v = *reinterpret_cast<const float4 *>(a.Ti + (int64_t)it * a.ldi + f);
-        }
-        *reinterpret_cast<float4 *>(&buf[r * a.tile_stride + f]) = v;
-    }
 }
 
 // One entry's sorted targets and counters in LDS; a wave owns its entries.
@@ -125,12 +103,12 @@ __global__ __launch_bounds__(256) void rank_of_kernel(const RankOfArgs ra) {
         rank_load_user<MAXT>(a, u, g, tu);
         RankOfSlot st(state, slot);
         for (int b = 0; b < n; b += 16 * PT) {
-            ro_gather<PT>(a, buf, ra.tgt_items + tb + b, min(16 * PT, n - b), lane);
-            ro_wave_sync();
+            rank_gather<PT>(a, buf, ra.tgt_items + tb + b, min(16 * PT, n - b), lane);
+            rank_wave_sync();
             const float z = ro_score<MAXT, PT>(a, w_lds, buf, 0, tu, lane, g, col, KT0);
             const int e = b + 16 * g + col;
             if (g < PT && e < n) { st.bf[e] = __float_as_int(z); st.af[e] = ra.tgt_items[tb + e]; }      // in segment order, for the sort
-            ro_wave_sync();
+            rank_wave_sync();
         }
         const float s = lane < n ? __int_as_float(st.bf[lane]) : 0.f;
         const int it = lane < n ? st.af[lane] : 0;
@@ -139,27 +117,27 @@ __global__ __launch_bounds__(256) void rank_of_kernel(const RankOfArgs ra) {
             const float se = __int_as_float(st.bf[e]);
             rank += (se < s || (se == s && st.af[e] < it)) ? 1 : 0;
         }
-        ro_wave_sync();
+        rank_wave_sync();
         if (lane < n) { st.ts[rank] = s; st.ti[rank] = it; st.tp[rank] = lane; }
         st.bf[lane] = 0; st.af[lane] = 0; st.cnt[lane] = 0;
         if (lane < 2) st.cnt[RO_T + lane] = 0;
         if (slice == 0 && lane < n) ra.out_scores[tb + lane] = s;
-        ro_wave_sync();
+        rank_wave_sync();
         if (a.excl_ptr) {
             const int ee = a.excl_ptr[u + 1];
             const int xb = rank_lower_bound(a.excl_items, a.excl_ptr[u], ee, s0);
             const int xe = rank_lower_bound(a.excl_items, xb, ee, s1);
             for (int b = xb; b < xe; b += 16 * PT) {
                 const int rows = min(16 * PT, xe - b);
-                ro_gather<PT>(a, buf, a.excl_items + b, rows, lane);
-                ro_wave_sync();
+                rank_gather<PT>(a, buf, a.excl_items + b, rows, lane);
+                rank_wave_sync();
                 const float z = ro_score<MAXT, PT>(a, w_lds, buf, 0, tu, lane, g, col, KT0);
                 const int r = 16 * g + col;
                 if (g < PT && r < rows) {
                     const int item = a.excl_items[b + r];
                     if (item >= s0 && item < s1) st.count(z, item, n, -1);
                 }
-                ro_wave_sync();
+                rank_wave_sync();
             }
         }
     }
@@ -193,7 +171,7 @@ __global__ __launch_bounds__(256) void rank_of_kernel(const RankOfArgs ra) {
         const int tb = ra.tgt_ptr[j], n = min(ra.tgt_ptr[j + 1] - tb, RO_T);
         if (n <= 0) continue;
         const RankOfSlot st(state, slot);
-        ro_wave_sync();
+        rank_wave_sync();
         if (lane < n) {
             int greater = 0;
             for (int p = lane + 1; p <= n; ++p) greater += st.cnt[p];
@@ -245,10 +223,10 @@ __global__ __launch_bounds__(256) void rank_of_metrics_kernel(const float *__res
             r_min = min(r_min, r_t);
         }
         terms[lane] = active ? (double)h / (double)r_t : 0.0;
-        ro_wave_sync();
+        rank_wave_sync();
         if (lane == 0)
             for (int i = 0; i < AMAR_WAVE; ++i) ap += terms[i];
-        ro_wave_sync();
+        rank_wave_sync();
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {

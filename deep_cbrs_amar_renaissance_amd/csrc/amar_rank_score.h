@@ -1,7 +1,8 @@
 // What the fused rankers of the split head share besides the selector of amar_rank_select.h:
 //   * RankArgs, the kernels' argument block, and the constants of their decomposition;
 //   * device helpers: the packed rest stack and an item tile go to LDS (rank_stage_weights, rank_stage_tile), a user's Tu row
-//     becomes MFMA fragments (rank_load_user);
+//     becomes MFMA fragments (rank_load_user); a wave gathers listed Ti rows into a tile-shaped buffer of its own (rank_gather,
+//     rank_wave_sync: amar_rank_of.hip's targets and excluded rows, amar_rank_lists.hip's candidates);
 //   * the score stage itself is amar_rank_score.inc, a fragment of a kernel body (one text, the same bits per pair):
 //     rank_topk_kernel includes it, and amar_rank_of.hip wraps it in a function of its own;
 //   * rank_topk_kernel<MAXT, PT, V>, the one body of three of the four top-k kernels, and RankVariant, what a variant V says by default.
@@ -10,7 +11,8 @@
 //     from a cursor) still has its own copy of the walk, and amar_rank_of.hip counts instead of selecting: its kernel has its
 //     own walk; both call the helpers and include the fragment;
 //   * host: the argument checks the entry points share (rank_check_tables), the walk over the packed stack (rank_pack_args), the
-//     launch geometry of a stack (rank_shape), the LDS a launch needs (rank_lds_bytes, rank_of_lds_bytes), rank_route — the one
+//     launch geometry of a stack (rank_shape), the LDS a launch needs (rank_lds_bytes, rank_of_lds_bytes, rank_lists_lds_bytes),
+//     rank_route — the one
 //     function the launchers and the query amar_rank_route take all of that and the capacity refusal from — and the launch
 //     path itself: rank_prepare (tables, route, the argument fields every ranker sets alike), rank_launch_form (the MAXT / PT
 //     dispatch over a kernel's four forms), rank_topk (everything the top-k launchers do after their own leading checks)
@@ -75,6 +77,29 @@ __device__ __forceinline__ void rank_load_user(const RankArgs &a, int u, int g, 
         const int f = 16 * t + 4 * g;
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
         tu[t] = (t < KT0 && f < a.c1) ? *reinterpret_cast<const f32x4 *>(a.Tu + (int64_t)u * a.ldu + f) : zero;
+    }
+}
+
+// What orders a wave's own LDS writes before its own LDS reads of other lanes' words: no other wave is waited for.
+__device__ __forceinline__ void rank_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+// Rows ids[0 .. count) of Ti go to the wave's buffer (16 PT rows of 16 KT0 features, zero past c1, past `count` and for an id
+// outside the table); the caller's wave syncs stand on either side.
+template <int PT>
+__device__ __forceinline__ void rank_gather(const RankArgs &a, float *buf, const int32_t *ids, int count, int lane) {
+    const int f4_per_row = 4 * a.kt[0];
+    for (int idx = lane; idx < 16 * PT * f4_per_row; idx += AMAR_WAVE) {
+        const int r = idx / f4_per_row, f = 4 * (idx - r * f4_per_row);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < count && f < a.c1) {
+            const int it = ids[r];
+            if ((unsigned)it < (unsigned)a.n_items) v = *reinterpret_cast<const float4 *>(a.Ti + (int64_t)it * a.ldi + f);
+        }
+        *reinterpret_cast<float4 *>(&buf[r * a.tile_stride + f]) = v;
     }
 }
 
@@ -281,17 +306,29 @@ inline size_t rank_of_lds_bytes(const RankArgs &a, const RankShape &sh) {
            (size_t)RANK_WAVES * rank_of_gather_floats(sh) * 4 + (size_t)RANK_UB * RANK_OF_WORDS * 4;
 }
 
+// amar_rank_lists.hip: the stack, a gather buffer per wave and one selector per wave; no item tile.
+inline size_t rank_lists_lds_bytes(const RankArgs &a, const RankShape &sh) {
+    return (size_t)((a.wpack_floats + 3) & ~3) * 4 + (size_t)RANK_WAVES * rank_of_gather_floats(sh) * 4 +
+           (size_t)rank_select_state_floats(RANK_WAVES) * 4;
+}
+
 constexpr size_t RANK_LDS_LIMIT = 160 * 1024, RANK_LDS_PLAIN = 64 * 1024;
 
-// The one decision about a rest stack that amar_recommend_f32, amar_recommend_group_f32, amar_rank_of_f32, amar_recommend_among_f32
-// and the query amar_rank_route share: where its layers sit in the packed blob (a's layer fields, rank_pack_args), the launch geometry (sh,
+// The kinds amar_rank_route answers for (include/amar_hip.h; 3 is none of them).
+inline bool rank_kind_known(int kind) {
+    return kind == AMAR_RANK_RECOMMEND || kind == AMAR_RANK_GROUP || kind == AMAR_RANK_RANK_OF || kind == AMAR_RANK_AMONG ||
+           kind == AMAR_RANK_LISTS;
+}
+
+// The one decision about a rest stack that amar_recommend_f32, amar_recommend_group_f32, amar_rank_of_f32, amar_recommend_among_f32,
+// amar_recommend_lists_f32 and the query amar_rank_route share: where its layers sit in the packed blob (a's layer fields, rank_pack_args), the launch geometry (sh,
 // rank_shape; a.tile_items / a.tile_stride), the LDS the kind's kernel asks for and whether that fits.  The launchers refuse on
 // !r.fits, size the launch by r.lds_bytes and dispatch on r.maxt, so the query cannot say anything else.  No HIP call.
 // acts == NULL (the query): every layer counts as linear, which the layout does not depend on.
 inline int rank_route(int kind, const int32_t *dims, const int32_t *acts, int32_t n_layers, RankArgs &a, RankShape &sh,
                       amar_rank_route_info &r) {
     r = amar_rank_route_info{};
-    if (kind != AMAR_RANK_RECOMMEND && kind != AMAR_RANK_GROUP && kind != AMAR_RANK_RANK_OF && kind != AMAR_RANK_AMONG) return AMAR_EINVAL;
+    if (!rank_kind_known(kind)) return AMAR_EINVAL;
     int32_t linear[RANK_MAX_LAYERS + 1] = {};
     int rc = rank_pack_args(dims, acts ? acts : linear, n_layers, a);
     if (rc != AMAR_OK) return rc;
@@ -299,7 +336,8 @@ inline int rank_route(int kind, const int32_t *dims, const int32_t *acts, int32_
     if (rc != AMAR_OK) return rc;
     a.tile_items = sh.tile_items; a.tile_stride = sh.tile_stride;
     const size_t bytes = kind == AMAR_RANK_RANK_OF ? rank_of_lds_bytes(a, sh)
-                         : (kind == AMAR_RANK_AMONG ? rank_among_lds_bytes(a, sh) : rank_lds_bytes(a, sh));
+                         : (kind == AMAR_RANK_AMONG ? rank_among_lds_bytes(a, sh)
+                            : (kind == AMAR_RANK_LISTS ? rank_lists_lds_bytes(a, sh) : rank_lds_bytes(a, sh)));
     r.maxt = sh.maxt; r.pt = sh.pt; r.tile_items = sh.tile_items; r.tile_stride = sh.tile_stride;
     r.wpack_floats = a.wpack_floats;
     r.lds_bytes = (int64_t)bytes;

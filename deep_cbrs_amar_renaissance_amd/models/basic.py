@@ -214,7 +214,7 @@ class BasicRS(rec.SimilarSearch, Model):
         return {'rest': (torch.from_numpy(rb).to(clf[0].kernel.device), rdims, [l.activation for l in clf[1:]]), 'in_act': clf[0].activation}
 
     def _ranker_plan(self, u_dim, i_dim, kind):
-        """(plan, split) for the fused ranker `kind` ('recommend' | 'group' | 'rank_of'): the split plan (split True) or, where the
+        """(plan, split) for the fused ranker `kind` ('recommend' | 'group' | 'rank_of' | 'among' | 'lists'): the split plan (split True) or, where the
         towers are too wide for it, the rank plan (split False) — (None, False) when the head has neither or when that kernel
         refuses the rest stack for capacity (capi.rank_fits: stack + item tile + the kernel's own state must fit 160 KB of LDS)."""
         plan, split = self._split_plan(u_dim, i_dim), True

@@ -63,6 +63,12 @@ pair (score, item); ``check_after`` reads the cursors, ``after_fused`` is one ``
 more compare per pair), ``pairs(after=...)`` the pair route from a cursor (``amar_topk_segmented_after_f32``), ``deep_fused`` /
 ``deep_pairs`` chain ceil(k / K_MAX) pages into lists of up to ``DEEP_K_MAX`` = 1024, and the mixin's ``recommend_after`` /
 ``recommend_deep`` pick between them as ``recommend()`` does.
+
+The tenth part gives every user its own candidates: "the best k of THIS user's list".  ``check_candidate_lists`` reads one list per
+listed user (sequences, or an [m, P] array / device tensor of node ids padded with -1), ``device_candidate_csr`` sorts and compacts a
+device tensor where it is, ``lists_fused`` is one ``amar_recommend_lists_f32`` launch over the split towers (sum |C_u| pairs scored,
+every wave walking its own user's list: nothing of size |U| x |I| anywhere), the mixin's ``recommend_from`` picks between it and
+``pairs(keep_items=CSR)``, and ``evaluate_ranking_sampled`` is its in-library consumer: the 1 + N sampled-negatives protocol.
 """
 import contextlib
 import weakref
@@ -733,6 +739,118 @@ def among_fused(towers, plan, trainset, cand_rows, k, users, exclude_seen):
     return _finish(u, items, scores, n_users)
 
 
+# -- per-user candidate lists (amar_recommend_lists_f32): "the best k of THIS user's candidates" --------------------------------------
+def _is_padded_lists(c):
+    """A 2-D integer array or tensor [m, P] of node ids, -1 padded: the shape `recommend()`, `similar_items()` and
+    `device_lists()` hand out."""
+    if isinstance(c, torch.Tensor):
+        return c.dim() == 2 and not c.dtype.is_floating_point and c.dtype != torch.bool and not c.dtype.is_complex
+    return isinstance(c, np.ndarray) and c.ndim == 2 and c.dtype != np.bool_ and np.issubdtype(c.dtype, np.integer)
+
+
+def check_candidate_lists(candidates, n_users, n_items, n_listed):
+    """The `candidates` argument of `recommend_from`, checked and as a CSR over the listed users: (ptr int64 [n_listed + 1], item
+    rows int64, ascending and distinct inside every list).  It takes
+      * one sequence of item node ids (|U|..|U|+|I|-1, any order, duplicates collapse; or a boolean mask over the items) per listed
+        user, in the order of `users`: the per-user form of `check_candidates`, with its ValueErrors;
+      * a 2-D integer array or HOST tensor [n_listed, P] of node ids padded with -1 (any order, duplicates collapse).
+    A DEVICE tensor [n_listed, P] is not read here: the shape and the dtype are checked and the tensor itself comes back
+    (`device_candidate_csr` turns it into the CSR where it is).  One flat sequence is refused: a set for every user is
+    `recommend_among`'s."""
+    what = 'candidates'
+    if candidates is None or isinstance(candidates, (str, bytes, dict)) or not hasattr(candidates, '__len__'):
+        check_candidates(candidates, n_users, n_items)                    # raises
+    if isinstance(candidates, torch.Tensor) and (candidates.is_cuda or candidates.dim() == 2):
+        if not _is_padded_lists(candidates):
+            raise ValueError("{}: a tensor must be a 2-D integer tensor [listed users, P] of item node ids, -1 padded".format(what))
+        if candidates.shape[0] != n_listed:
+            raise ValueError("{}: per-user candidates need one sequence per listed user ({} users, {} sequences)".format(
+                what, n_listed, candidates.shape[0]))
+        if candidates.is_cuda:
+            return candidates
+        candidates = candidates.numpy()
+    if _is_padded_lists(candidates):
+        if len(candidates) != n_listed:
+            raise ValueError("{}: per-user candidates need one sequence per listed user ({} users, {} sequences)".format(
+                what, n_listed, len(candidates)))
+        candidates = [row[row != -1] for row in candidates]
+    got = check_candidates(candidates, n_users, n_items, n_listed=n_listed) if len(candidates) or n_listed else \
+        (np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int64))
+    if not isinstance(got, tuple):
+        raise ValueError("{} must hold one sequence of item node ids per listed user (one set for every user is "
+                         "recommend_among's)".format(what))
+    return got
+
+
+def device_candidate_csr(lists, n_users, n_items):
+    """A device tensor [m, P] of item node ids (any order, duplicates allowed; an entry that is no item node id of the trainset, the
+    -1 padding among them, is no candidate) as the CSR of amar_recommend_lists_f32 on the same device: (ptr int32 [m + 1], item rows
+    int32, strictly ascending inside every list).  Sorted, de-duplicated and compacted where it is: no value is read on the host."""
+    m, P = int(lists.shape[0]), int(lists.shape[1])
+    if m * P >= 1 << 31:
+        raise ValueError("candidates: the lists must hold fewer than 2^31 entries together")
+    dev = lists.device
+    if m == 0 or P == 0:
+        return torch.zeros(m + 1, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)
+    rows = lists.to(torch.int64) - n_users
+    rows = torch.where((rows >= 0) & (rows < n_items), rows, torch.full_like(rows, n_items))       # n_items: sorts last, is dropped
+    rows, _ = torch.sort(rows, dim=1)
+    keep = rows < n_items
+    keep[:, 1:] &= rows[:, 1:] != rows[:, :-1]
+    within = torch.cumsum(keep, dim=1)                                                              # kept entries up to and with this one
+    ptr = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(within[:, -1], dim=0, out=ptr[1:])
+    at = torch.where(keep, ptr[:-1, None] + within - 1, torch.full_like(within, m * P))             # dropped entries: one spare slot
+    out = torch.empty(m * P + 1, dtype=torch.int32, device=dev)
+    out[at.reshape(-1)] = rows.reshape(-1).to(torch.int32)
+    return ptr.to(torch.int32), out[:m * P]
+
+
+def lists_fused(towers, plan, trainset, lists, k, users, exclude_seen):
+    """One amar_recommend_lists_f32 call over the split towers (tu [U, c1], ti [I, c1] with b1 folded in): `fused` with every listed
+    user walking its own candidates.  `lists`: what `check_candidate_lists` returned, the host CSR or the device tensor."""
+    n_users, n_items = _sizes(trainset)
+    k = check_k(k)
+    u = check_users(users, n_users)
+    if len(u) == 0:
+        return _empty(k)
+    head, kw = _ranker_args(towers, plan, trainset, exclude_seen, None if users is None else u)
+    if isinstance(lists, torch.Tensor):
+        ptr, rows = device_candidate_csr(lists.to(towers[0].device), n_users, n_items)
+    else:
+        ptr, rows = lists
+    items, scores = capi.recommend_lists(*head, k, ptr, rows, **kw)
+    return _finish(u, items, scores, n_users)
+
+
+def evaluate_ranking_sampled(model, trainset, test_ratings, ks, n_negatives=99, seed=0, users=None):
+    """The 1 + N sampled-negatives protocol: every listed user (all by default) that has a held-out positive ranks its held-out items
+    against `n_negatives` items it rated neither in training nor in test (utilities.metrics.sampled_negatives: uniform without
+    replacement, a function of `seed` and the user alone), and Precision / Recall / NDCG / HitRate @k are taken over those short
+    lists: HR@10 / NDCG@10 against 99 negatives as most implicit-feedback papers report them.  One `recommend_from` call with the
+    lists kept on the device, scored by amar_rank_metrics_f64.  Returns the dict of `evaluate_ranking`, same keys; users without a
+    held-out positive are skipped and counted.  With n_negatives >= every user's unrated items, and test ratings that hold no
+    disliked pair (an item rated in test is never drawn, so a label-0 one is no candidate at all), it is `evaluate_ranking` itself."""
+    from deep_cbrs_amar_renaissance_amd.utilities.metrics import full_ranking_metrics, full_ranking_metrics_device, sampled_negatives
+    ks = [int(k) for k in ks]
+    if not ks:
+        raise ValueError("evaluate_ranking_sampled needs at least one k")
+    k = check_k(max(ks))
+    n_users, n_items = _sizes(trainset)
+    u = check_users(users, n_users)
+    drawn_users, drawn = sampled_negatives(trainset, test_ratings, n_negatives, seed)
+    row_of = np.full(n_users, -1, dtype=np.int64)
+    row_of[drawn_users] = np.arange(len(drawn_users))
+    has = row_of[u] >= 0
+    lists = np.full((len(u), max(1, drawn.shape[1])), -1, dtype=np.int64)                  # no held-out positive: an empty list
+    lists[has, :drawn.shape[1]] = drawn[row_of[u[has]]]
+    with device_lists():
+        u, items, _ = model.recommend_from(trainset, lists, k=k, users=users)
+    if len(u) == 0:
+        return full_ranking_metrics(u, items, test_ratings, ks)
+    return full_ranking_metrics_device(None if users is None else u, items.contiguous(), test_ratings, ks, n_users, n_items)
+
+
 # -- similarity search (amar_nearest_f32): "which rows of this table are like these vectors?" ---------------------------------------
 METRICS = ('dot', 'cosine')
 
@@ -1324,7 +1442,7 @@ class SimilarSearch:
         return deep_pairs(route[1], trainset, k, users, exclude_seen, device=route[2])
 
     def _group_route(self, trainset, kind='group'):
-        """How the model ranks a catalogue for the fused kernel `kind` ('recommend' | 'group' | 'rank_of' | 'among': capi.RANK_KINDS):
+        """How the model ranks a catalogue for the fused kernel `kind` ('recommend' | 'group' | 'rank_of' | 'among' | 'lists': capi.RANK_KINDS):
         ('fused', (tu, ti, ...), plan) = the split towers and their plan where the head has one and that kernel takes it
         (capi.rank_fits: the kernels' LDS sums differ, so a head may rank fused in one and by pairs in another), or
         ('pairs', score_fn(u_ids, i_ids) -> [P, 1] scores, device)."""
@@ -1616,6 +1734,38 @@ class SimilarSearch:
         if route[0] == 'fused':
             return among_fused(route[1], route[2], trainset, cand, k, users, exclude_seen)
         return pairs(route[1], trainset, k, users, exclude_seen, device=route[2], keep_items=cand)
+
+    # -- per-user candidate lists (amar_recommend_lists_f32) ------------------------------------------------------------------
+    def recommend_from(self, trainset, candidates, k=10, users=None, exclude_seen=True):
+        """The k best items of every user in `users` (user indices, all users by default) among THAT USER's candidates: a retrieval
+        stage's output to re-rank, per-user availability, a "similar to what you liked" pool, a held-out item against sampled
+        negatives.  `candidates` (`check_candidate_lists`): one sequence of item node ids |U|..|U|+|I|-1 per listed user, or a 2-D
+        integer array / tensor [m, P] of node ids padded with -1 — the shape `recommend()`, `similar_items()` and `device_lists()`
+        hand out; any order, duplicates collapse.  Training pairs are excluded unless exclude_seen=False.  Returns (users int64 [m],
+        items int64 [m, k] node ids, -1 padded, scores float32 [m, k], -inf padded), shaped and ordered like `recommend()`: exactly
+        the user's full ranking with everything outside its own list struck out — on the fused route bit for bit.
+        A head with a fused ranking kernel: one amar_recommend_lists_f32 launch over sum |C_u| pairs, nothing of size |U| x |I| built
+        anywhere; a device tensor is sorted, de-duplicated and compacted on the device without a host round trip (an entry that is
+        no item node id counts as padding there).  The kernel keeps no item tile in LDS, so it also takes heads `recommend()` has no
+        room for.  The hybrids and heads past its capacity rank the kept pairs on the pair route; nothing raises.  One set for all
+        users is `recommend_among`'s case."""
+        n_users, n_items = _sizes(trainset)
+        k = check_k(k)
+        u = check_users(users, n_users)
+        lists = check_candidate_lists(candidates, n_users, n_items, len(u))
+        if len(u) == 0:
+            return _empty(k)
+        route = self._group_route(trainset, kind='lists')
+        if route[0] == 'fused':
+            return lists_fused(route[1], route[2], trainset, lists, k, users, exclude_seen)
+        if isinstance(lists, torch.Tensor):                               # the pair route reads its candidates on the host
+            lists = check_candidate_lists(lists.cpu(), n_users, n_items, len(u))
+        return pairs(route[1], trainset, k, users, exclude_seen, device=route[2], keep_items=lists)
+
+    def evaluate_ranking_sampled(self, trainset, test_ratings, ks, n_negatives=99, seed=0, users=None):
+        """Precision / Recall / NDCG / HitRate @k under the 1 + N sampled-negatives protocol (recommend.evaluate_ranking_sampled):
+        every user's held-out positives ranked against `n_negatives` unrated items drawn from `seed` and the user alone."""
+        return evaluate_ranking_sampled(self, trainset, test_ratings, ks, n_negatives=n_negatives, seed=seed, users=users)
 
     # -- group recommendation (amar_recommend_group_f32) ----------------------------------------------------------------
     def recommend_group(self, trainset, groups, k=10, strategy='mean', min_score=None, exclude_seen=True, member_scores=False):

@@ -318,6 +318,38 @@ def relevant_csr(test_ratings, n_users, n_items):
     return exclusion_csr(t[t[:, 2] == 1] if len(t) else t, n_users, n_items)
 
 
+def sampled_negatives(trainset, test_ratings, n_negatives=99, seed=0):
+    """The candidate lists of the 1 + N sampled-negatives protocol, in host numpy.  For every user with a held-out positive (a
+    label-1 pair of `test_ratings`) its held-out items plus `n_negatives` items it rated neither in `trainset.ratings` nor in
+    `test_ratings` (whatever the label), drawn uniformly without replacement — all of them where fewer exist.  The draw of a user is
+    a function of `seed` and the user's index alone: not of the other users, their order or their number.
+    Returns (users int64 [n] ascending, lists int64 [n, P] of item NODE ids, -1 padded; a row holds the held-out items ascending,
+    then the negatives ascending): the second form of `recommend_from(candidates=)`."""
+    from deep_cbrs_amar_renaissance_amd.recommend import exclusion_csr
+    if isinstance(n_negatives, bool) or not isinstance(n_negatives, (int, np.integer)) or n_negatives < 0:
+        raise ValueError("n_negatives must be a non-negative integer (got {!r})".format(n_negatives))
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
+        raise ValueError("seed must be a non-negative integer (got {!r})".format(seed))
+    n_users, n_items = len(trainset.users), len(trainset.items)
+    t = np.asarray(test_ratings).reshape(-1, 3)
+    pos_ptr, pos_items = relevant_csr(t, n_users, n_items)
+    train = np.asarray(trainset.ratings).reshape(-1, 3)
+    rated_ptr, rated_items = exclusion_csr(np.concatenate([train[:, :3], t]) if len(train) else t, n_users, n_items)
+    users = np.flatnonzero(np.diff(pos_ptr) > 0).astype(np.int64)
+    rows = []
+    for u in users.tolist():
+        free = np.ones(n_items, dtype=bool)
+        free[rated_items[rated_ptr[u]:rated_ptr[u + 1]]] = False
+        free = np.flatnonzero(free)
+        if len(free) > n_negatives:
+            free = np.sort(np.random.default_rng([int(seed), u]).choice(free, size=int(n_negatives), replace=False))
+        rows.append(np.concatenate([pos_items[pos_ptr[u]:pos_ptr[u + 1]], free]))
+    lists = np.full((len(users), max([len(r) for r in rows], default=0)), -1, dtype=np.int64)
+    for j, r in enumerate(rows):
+        lists[j, :len(r)] = r + n_users
+    return users, lists
+
+
 # Relevant CSRs on the device, built once per ratings array (held weakly, as recommend._EXCL_CACHE holds the exclusion CSRs).
 _REL_CACHE = {}
 

@@ -1371,6 +1371,36 @@ int amar_recommend_among_f32(const float *Tu, int64_t ldu, int32_t n_users, cons
                              int32_t *workspace_items, float *workspace_scores, int32_t *out_items, float *out_scores,
                              amar_stream_t stream);
 
+/* Top-k over PER-USER candidate lists ("the best k of THIS user's candidates": a retrieval stage's output to re-rank, per-user
+ * availability, the 1 + N sampled-negatives protocol), fused.  Tables, packed rest stack, limits, alignment rules, users[m] and
+ * the exclusion CSR over USERS are exactly those of amar_recommend_f32.
+ * Candidates: a CSR over the m LISTED rows, cand_ptr[m + 1] (int32, so the lists hold fewer than 2^31 entries together) and
+ * cand_items (device item rows).  PRECONDITION: inside every listed row j, cand_items[cand_ptr[j] .. cand_ptr[j + 1]) is strictly
+ * ascending (so distinct) and lies in [0, n_items) — the contract amar_recommend_among_f32 puts on its one list.  Nothing on the
+ * device checks it; host callers check a host list before they upload it (capi.recommend_lists does).  The same user may be
+ * listed twice with two lists; a list may be empty (the row is all padding).
+ * For every listed row and every candidate of its list that is not in the user's exclusion row the score is the one
+ * amar_recommend_f32 computes for the pair, bit for bit (one score routine, the same user fragments), and the k best (score
+ * descending, item row ascending on ties) go to out_items / out_scores [m, k] as item ROWS, padded with -1 / -inf: the lists
+ * amar_recommend_f32 returns with the complement of the row's candidates merged into its exclusion row.  sum_j |C_j| pairs are
+ * scored; nothing of size m x n_items is built, read or written, and there is no workspace.
+ * How: ceil(m / 4) workgroups of 4 waves, one listed row and one selector per wave.  The packed stack is staged once per
+ * workgroup, followed by the kernel's only workgroup barrier; from there a wave walks its own list 16 pt candidates a step —
+ * it gathers their Ti rows into its own tile-shaped LDS buffer, scores them, offers them to its selector — and synchronises at
+ * wave scope only: the four lists of a workgroup may have any lengths.  A wave walks its whole list: there are no slices and no
+ * merge launch, so a call whose lists are all the same long set is amar_recommend_among_f32's, not this one's.  LDS: the stack +
+ * 4 gather buffers + 4 selectors and no item tile (amar_rank_route with AMAR_RANK_LISTS), so a head may fit here that
+ * amar_recommend_f32 refuses.  A row's result depends on its own Tu row, its candidates' Ti rows, the weights and its exclusion row
+ * only; the same bits on every run.
+ * NULL tables, negative sizes, k < 1, users == NULL with m != n_users, excl_ptr without excl_items, cand_ptr == NULL with m > 0,
+ * cand_ptr without cand_items, a missing output with m > 0: AMAR_EINVAL; k > 64, the shape limits, a head whose LDS sum does not
+ * fit (amar_rank_route: fits == 0): AMAR_EUNSUPPORTED; all checked before any device call.  m == 0: AMAR_OK, nothing is launched. */
+int amar_recommend_lists_f32(const float *Tu, int64_t ldu, int32_t n_users, const float *Ti, int64_t ldi, int32_t n_items, int32_t c1,
+                             const float *wpack, const int32_t *dims, const int32_t *acts, int32_t n_layers, int32_t in_act,
+                             const int32_t *users, int64_t m, const int32_t *excl_ptr, const int32_t *excl_items,
+                             const int32_t *cand_ptr, const int32_t *cand_items, int32_t k,
+                             int32_t *out_items, float *out_scores, amar_stream_t stream);
+
 /* Top-k AFTER a position of the user's ranking ("the next page"; chained, lists longer than 64), fused: amar_recommend_f32 with a
  * cursor per selector row.  Tables, packed rest stack, limits, alignment rules, users[m], the exclusion CSR, the slicing contract
  * (amar_recommend_slices, the workspaces, the merge launch), the LDS sum (amar_rank_route with AMAR_RANK_RECOMMEND) and the
@@ -1520,7 +1550,9 @@ int amar_rank_of_metrics_f64(const float *scores, const int32_t *greater, const 
  *     lds_bytes    dynamic LDS of a launch: the stack (rounded up to 16 bytes) + tile_items * tile_stride * 4 + per kind:
  *                  RECOMMEND, GROUP: 16 640 (sixteen selectors);  RANK_OF: 4 * 16 pt * tile_stride * 4 (a gather buffer per wave)
  *                  + 16 * (6 * AMAR_RANK_OF_MAX_TARGETS + 2) * 4 = 24 704 (sixteen entries' sorted targets and counters)
- *     fits         lds_bytes <= 160 KB.  0: the entry point returns AMAR_EUNSUPPORTED for this head, before any device call
+ *                  LISTS is the one kind without the tile term: the stack + 4 * 16 pt * tile_stride * 4 (a gather buffer per wave)
+ *                  + 4 160 (four selectors)
+ *     fits        lds_bytes <= 160 KB.  0: the entry point returns AMAR_EUNSUPPORTED for this head, before any device call
  *     large_lds    lds_bytes > 64 KB: the launch first asks for the large dynamic LDS attribute
  * The capacity rule in short: recommend / group take a stack of up to 121 856 B next to a 128-wide c1 (128 -> 128 -> 64 -> 1 fits,
  * 128 -> 128 -> 128 -> 1 does not); rank_of takes up to 80 000 B there (128 -> 128 -> 1 fits, 128 -> 128 -> 64 -> 1 does not).
@@ -1531,6 +1563,8 @@ int amar_rank_of_metrics_f64(const float *scores, const int32_t *greater, const 
 #define AMAR_RANK_GROUP     1
 #define AMAR_RANK_RANK_OF   2
 #define AMAR_RANK_AMONG     4   /* amar_recommend_among_f32: RECOMMEND's sum + 4 * tile_items (the tile's item rows); 3 stays unknown */
+#define AMAR_RANK_LISTS     5   /* amar_recommend_lists_f32: the stack + 4 * 16 pt * tile_stride * 4 (a gather buffer per wave)
+                                 * + 4 160 (four selectors); no item tile */
 typedef struct amar_rank_route_info {
     int32_t maxt, pt, tile_items, tile_stride;
     int32_t wpack_floats, fits, large_lds, reserved;
